@@ -2,7 +2,7 @@
 """Headline benchmark: DOF-updates/s of the backward-Euler time loop on geballe_with_diamond
 refined to ~1M DOF (BASELINE.json configs[2] / BASELINE.md C3).
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|sweep64]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|sweep64] [--dump-outputs DIR]
 
 * ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment: this process starts the N ranks itself
   (``python -m torch.distributed.run --nproc-per-node N bench.py ...`` as a fresh child, before torch or HIP
@@ -67,6 +67,7 @@ SWEEP_POINTS = 64          # BASELINE C5
 SWEEP_BATCH = 16           # points per batched time loop (hf_batch_*): columns of one multi-vector PCG; a rank with fewer points takes 8 / 4 / 2
 SWEEP_CONCURRENT = 2       # time loops in flight per rank (64 points on one GPU, round 3: batches of 16, 1 / 2 in flight = 1.09 / 1.20e9 DOF-updates/s;
                            # batches of 8: 0.90 / 1.08e9; round 2, batches of 8: 7.1 / 9.0e8; unbatched, 6 in flight: 4.5e8)
+DUMP_BYTES = 64 * 10**6    # --dump-outputs: bytes of array data in all (a 1M-DOF field is 8 MB; 16M DOF would be 128 MB)
 
 
 def parse_args(argv=None):
@@ -107,6 +108,10 @@ def parse_args(argv=None):
     ap.add_argument("--cpu-farm-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="form the process group, report its size and exit: checks the launcher plumbing (no GPU work)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed as DIR/<name>.npy (float64, at most 64 MB in all): "
+                         "c3 = temperature.npy, rank 0's field after the last timed step; sweep64 = watchers.npy, the watcher curves "
+                         "(points x rows of watcher_points.csv x watchers) of every point in kappa order")
     args = ap.parse_args(argv)
     if args.steps is None:
         args.steps = 100 if args.workload == "sweep64" else 60
@@ -165,6 +170,36 @@ def make_problem(cfg, stack, coords, tris, tags, material_tags, k_sample, device
         tag_to_k[material_tags["p_sample"]] = float(k_sample)
     dt = float(cfg["timing"]["t_final"]) / int(cfg["timing"]["num_steps"])
     return HeatProblem(coords, tris, tags, tag_to_k, tag_to_rc, dt, bcs, ic, device_id=device_id, precond=precond, pattern=pattern)
+
+
+def dump_outputs(folder, arrays):
+    """--dump-outputs: every array of {name: array} as <folder>/<name>.npy in float64.  An array larger than its share of
+    DUMP_BYTES keeps a sample of its rows instead, drawn with a fixed seed (the same rows in every run with the same arguments);
+    the sampled row numbers go beside it as <name>_rows.npy."""
+    import numpy as np
+
+    os.makedirs(folder, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            keep = share // (a[:1].nbytes + 8)             # per kept row: its values + its row number
+            rows = np.sort(np.random.default_rng(0).choice(len(a), size=keep, replace=False))
+            np.save(os.path.join(folder, f"{name}_rows.npy"), rows.astype(np.float64))
+            a = a[rows]
+        np.save(os.path.join(folder, f"{name}.npy"), a)
+
+
+def watcher_curves(out_dir):
+    """{point folder name (its kappa): rows of its watcher_points.csv without the time column} of the sweep points under out_dir."""
+    import numpy as np
+
+    curves = {}
+    for name in os.listdir(out_dir):
+        path = os.path.join(out_dir, name, "watcher_points.csv")
+        if os.path.isfile(path):
+            curves[name] = np.genfromtxt(path, delimiter=",", skip_header=1, ndmin=2)[:, 1:]
+    return curves
 
 
 def cpu_baseline(cfg, mesh, n_sample_steps, first_step):
@@ -532,10 +567,11 @@ class Ranks:
             self.dist.destroy_process_group()
 
 
-def run_sweep64(ranks, n_points, steps_per_point, warmup_steps, concurrent, batch=1):
+def run_sweep64(ranks, n_points, steps_per_point, warmup_steps, concurrent, batch=1, collect=False):
     """BASELINE C5: `n_points` kappa_sample values on geballe_with_diamond at stock mesh size, point i ->
     rank i mod world, mesh + tag map broadcast once, `concurrent` points in flight per rank
-    (reference parameter_sweep.py:423-446, sweep_test.py:47-115).  Returns the measurement (rank 0) or None."""
+    (reference parameter_sweep.py:423-446, sweep_test.py:47-115).  Returns the measurement (rank 0) or None;
+    with `collect` it holds the watcher curves of every point in kappa order under "watchers"."""
     import shutil
     import tempfile
 
@@ -566,8 +602,13 @@ def run_sweep64(ranks, n_points, steps_per_point, warmup_steps, concurrent, batc
                                   device_id=ranks.dev_index, concurrent=concurrent, warmup_steps=warmup_steps,
                                   on_ready=on_ready, on_done=on_done, timing=timing, batch=batch)
         t_all = time.perf_counter() - t_all
+        curves = watcher_curves(os.path.join(tmp, "out")) if collect else None
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
+    if collect and ranks.dist is not None:
+        parts = [None] * ranks.world
+        ranks.dist.all_gather_object(parts, curves)
+        curves = {k: v for part in parts for k, v in part.items()}
     wall = ranks.max_over_ranks(clock["all"])
     whole = ranks.max_over_ranks(t_all)          # mesh + broadcasts + connectivity tables + multigrid set-up + warm-up + point loop, slowest rank
     setup_max = ranks.max_over_ranks(t_all - clock["all"])
@@ -588,7 +629,7 @@ def run_sweep64(ranks, n_points, steps_per_point, warmup_steps, concurrent, batc
     if not n_dof:
         with open(os.path.join(ROOT, "cfgs", "geballe_with_diamond.yaml")) as f:
             n_dof = _stock_dof(yaml.safe_load(f))
-    return {
+    res = {
         "workload": (f"{n_points}-point kappa_sample sweep [{ks[0]}..{ks[-1]}] on cfgs/geballe_with_diamond.yaml, stock mesh "
                      f"(BASELINE C5), point i -> rank i mod {ranks.world}, batches of up to {batch} points per time loop, "
                      f"{concurrent} loops in flight per rank, steps 0..{steps_per_point - 1} per point"),
@@ -608,6 +649,9 @@ def run_sweep64(ranks, n_points, steps_per_point, warmup_steps, concurrent, batc
         "value_whole_call_note": ("the same DOF-updates over the whole call of the slowest rank: mesh, broadcasts, connectivity tables, "
                                   "multigrid set-up and the untimed warm-up steps included - what a user of the sweep waits for"),
     }
+    if curves is not None:
+        res["watchers"] = np.stack([curves[k] for k in sorted(curves, key=float)])
+    return res
 
 
 _STOCK_DOF = {}
@@ -758,8 +802,11 @@ def main(argv=None):
               "vs_baseline": None, "dtype": "f64", "data": "synthetic"}
 
     if args.workload == "sweep64":
-        sw = run_sweep64(ranks, SWEEP_POINTS, args.steps, args.warmup, args.sweep_concurrent, args.sweep_batch)
+        sw = run_sweep64(ranks, SWEEP_POINTS, args.steps, args.warmup, args.sweep_concurrent, args.sweep_batch,
+                         collect=args.dump_outputs is not None)
         if rank == 0:
+            if args.dump_outputs is not None:
+                dump_outputs(args.dump_outputs, {"watchers": sw.pop("watchers")})
             roof = batch_head_roofline(dev_index, args.sweep_batch, traffic_mode=args.traffic) if (world == 1 and args.batch_roofline and args.sweep_batch > 1) else None
             out = dict(common, metric="DOF-updates/s (timesteps/s x nDOF) on geballe_with_diamond", value=sw["value"],
                        ms_per_step=1e3 * sw["wall_s"] / args.steps, scaling="strong",
@@ -811,6 +858,8 @@ def main(argv=None):
     elapsed = time.perf_counter() - t0
     gpu_ms = be.last_gpu_ms()
     elapsed = ranks.max_over_ranks(elapsed)
+    if args.dump_outputs is not None and rank == 0:       # before the profiled steps below advance the state
+        dump_outputs(args.dump_outputs, {"temperature": prob.state()})
 
     # ---- dominant kernel k_spmv<9>: vals 8 + colidx 4 per nnz; per row rowptr 4, z 8 (gathered operand),
     # Ap 8+8 and p 8+8 (read-modify-write by the direction recurrence) = 12*nnz + 44*n (SURVEY 8d formula bytes)

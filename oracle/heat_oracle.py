@@ -13,7 +13,7 @@ pinned by analytic identities and known-answer tests in tests/test_oracle.py
 1-D slab equivalence, a manufactured Bessel mode) and by fixtures generated
 from it (tests/golden/, script tests/golden/make_golden.py).
 
-What it restates (file:line in /root/reference):
+What it restates (file:line in the reference, cebarker1000/heatflow):
   * forms        run_with_diamond.py:321-337 == run_no_diamond.py:271-287 ==
                  space/space_and_forms.py:98-116
   * coefficients run_with_diamond.py:286-301 (cell tag -> kappa, rho*cv)

@@ -1,5 +1,6 @@
-import cProfile, pstats, sys, time
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+import cProfile, os, pstats, sys, time
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from conftest import build_case
 build_case("geballe_with_diamond", 2.0)
 for scale in (1.0, 0.43):

@@ -85,3 +85,40 @@ def test_side_guard_writes_the_headline_and_ends_the_process_when_a_side_measure
     ok = subprocess.run([sys.executable, str(script), "ok"], capture_output=True, text=True, timeout=60)
     assert ok.returncode == 0, ok.stderr[-1000:]
     assert json.loads(ok.stdout.strip())["config"]["sweep64"] == {"value": 2.0}
+
+
+def test_dump_outputs_keeps_to_its_budget_with_a_fixed_sample(tmp_path):
+    """--dump-outputs: float64 .npy files, at most bench.DUMP_BYTES of array data in all; an array beyond its share keeps the same
+    seeded sample of rows in every run, and names them in <name>_rows.npy.  The sweep's watcher curves are read back from the
+    per-point folders it writes."""
+    import numpy as np
+
+    script = tmp_path / "dump.py"
+    script.write_text(
+        "import os, sys\n"
+        "import numpy as np\n"
+        f"sys.path.insert(0, {ROOT!r})\n"
+        "import bench\n"
+        "bench.DUMP_BYTES = 40000\n"
+        "field = np.arange(10000, dtype=np.float32) * 0.5\n"
+        "for d in sys.argv[1:3]:\n"
+        "    bench.dump_outputs(d, {'temperature': field, 'small': np.ones((3, 2))})\n"
+        "out = sys.argv[3]\n"
+        "for k, rows in (('3.30', [[0.0, 300.0, 301.0], [1e-7, 302.5, 303.25]]), ('4.10', [[0.0, 300.0, 300.0], [1e-7, 310.0, 311.0]])):\n"
+        "    os.makedirs(os.path.join(out, k))\n"
+        "    with open(os.path.join(out, k, 'watcher_points.csv'), 'w') as f:\n"
+        "        f.write('time,pside,oside\\n' + ''.join(','.join(repr(v) for v in r) + '\\n' for r in rows))\n"
+        "os.makedirs(os.path.join(out, '3.50'))\n"                      # a point folder without curves is not a point
+        "c = bench.watcher_curves(out)\n"
+        "assert sorted(c) == ['3.30', '4.10'] and c['3.30'].tolist() == [[300.0, 301.0], [302.5, 303.25]], c\n")
+    a, b = tmp_path / "a", tmp_path / "b"
+    p = subprocess.run([sys.executable, str(script), str(a), str(b), str(tmp_path / "sweep")], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert sorted(os.listdir(a)) == ["small.npy", "temperature.npy", "temperature_rows.npy"]
+    t, rows = np.load(a / "temperature.npy"), np.load(a / "temperature_rows.npy")
+    assert t.dtype == np.float64 and rows.dtype == np.float64 and 0 < len(t) == len(rows) < 10000
+    assert np.all(np.diff(rows) > 0) and np.array_equal(t, rows * 0.5)
+    assert t.nbytes + rows.nbytes + np.load(a / "small.npy").nbytes <= 40000
+    assert np.array_equal(np.load(a / "small.npy"), np.ones((3, 2)))
+    for name in os.listdir(a):
+        assert np.array_equal(np.load(a / name), np.load(b / name)), name

@@ -290,9 +290,10 @@ def test_c5_sixty_four_point_kappa_sweep_on_one_gpu(hip, tmp_path):
           f"({64 * len(coords) * 100 / timing['points_s']:.3e} DOF-updates/s)")
 
 
-def test_bench_line_keeps_its_contract_on_a_small_mesh(hip):
+def test_bench_line_keeps_its_contract_on_a_small_mesh(hip, tmp_path):
     """bench.py end to end on a coarse mesh (seconds): exactly one JSON line with the driver's keys, value consistent with
-    ms_per_step, a roofline object for the dominant kernel with live in-loop timing, and a cpu_baseline from the oracle."""
+    ms_per_step, a roofline object for the dominant kernel with live in-loop timing, and a cpu_baseline from the oracle.
+    --dump-outputs writes the field the timed path left after its last step."""
     import json
     import subprocess
     import sys
@@ -301,7 +302,7 @@ def test_bench_line_keeps_its_contract_on_a_small_mesh(hip):
 
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "3.0", "--steps", "8", "--warmup", "5", "--cpu-steps", "3",
            "--jacobi-steps", "2", "--sweep-points", "0", "--hbm-scale", "0", "--cpu-farm-points", "0", "--device-warmup-s", "0",
-           "--profile-steps", "2"]
+           "--profile-steps", "2", "--dump-outputs", str(tmp_path / "dump")]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -325,3 +326,14 @@ def test_bench_line_keeps_its_contract_on_a_small_mesh(hip):
     c = out["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0 and c["unit"] == out["unit"]
     assert out["config"]["gpu_over_cpu"] == pytest.approx(out["value"] / c["value"])
+    # the dump: steps 0..12 of the same problem run here (5 warm-up + 8 timed; the 2 profiled steps after them would heat further)
+    got = np.load(tmp_path / "dump" / "temperature.npy")
+    assert got.dtype == np.float64 and got.shape == (n,)
+    cfg, stack, mesh = build_case("geballe_with_diamond", 3.0)
+    prob = make_problem(cfg, stack, mesh, precond=1)
+    try:
+        prob.run(5, time_varying=[prob.bcs[3]], first_step=0)
+        prob.run(8, time_varying=[prob.bcs[3]], first_step=5)
+        assert np.abs(got - prob.state()).max() <= 1e-8
+    finally:
+        prob.close()
