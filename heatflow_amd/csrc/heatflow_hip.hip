@@ -37,12 +37,55 @@ struct BlobHeader {
   int64_t count[12];            // elements per section, in the order written below
 };
 
+// The steady operator's fields trade places with the transient's (hf_ctx::Steady): on the swapped context the lifting,
+// elimination, multigrid set-up and PCG code runs on K_hat_S, its set S and its hierarchy, and the transient's stay as they
+// are.  A second call swaps back.
+void steady_swap(hf_ctx* ctx) {
+  hf_ctx::Steady& S = ctx->steady;
+  std::swap(ctx->nbc, S.nbc); std::swap(ctx->d_bc_dofs, S.bc_dofs); std::swap(ctx->d_g, S.g);
+  std::swap(ctx->nlift_rows, S.nlift_rows); std::swap(ctx->nlift, S.nlift);
+  std::swap(ctx->d_lift_rows, S.lift_rows); std::swap(ctx->d_lift_ptr, S.lift_ptr); std::swap(ctx->d_lift_bc, S.lift_bc);
+  std::swap(ctx->d_lift_slot, S.lift_slot); std::swap(ctx->d_lift_val, S.lift_val);
+  std::swap(ctx->d_A, S.K); std::swap(ctx->d_dinv, S.dinv);
+  std::swap(ctx->amg, S.amg); std::swap(ctx->d_coarse_inv, S.coarse_inv); std::swap(ctx->d_coarse_inv_f, S.coarse_inv_f);
+  std::swap(ctx->coarse_n, S.coarse_n); std::swap(ctx->coarse_ld, S.coarse_ld); std::swap(ctx->amg_ready, S.amg_ready);
+  std::swap(ctx->amg_fine_stale, S.amg_fine_stale); std::swap(ctx->amg_opc, S.amg_opc); std::swap(ctx->amg_setup_s, S.amg_setup_s);
+  std::swap(ctx->amg_print, S.amg_print);
+}
+struct SteadyScope {   // the steady operator in place for the lifetime of the scope, on every exit path
+  hf_ctx* c;
+  explicit SteadyScope(hf_ctx* ctx) : c(ctx) { steady_swap(c); }
+  ~SteadyScope() { steady_swap(c); }
+  SteadyScope(const SteadyScope&) = delete;
+  SteadyScope& operator=(const SteadyScope&) = delete;
+};
+
+void steady_free(hf_ctx* ctx) {
+  {
+    SteadyScope sw(ctx);
+    free_amg(ctx);
+  }
+  hf_ctx::Steady& S = ctx->steady;
+  dev_free(&S.bc_dofs); dev_free(&S.g); dev_free(&S.lift_rows); dev_free(&S.lift_ptr); dev_free(&S.lift_bc);
+  dev_free(&S.lift_slot); dev_free(&S.lift_val); dev_free(&S.K); dev_free(&S.dinv); dev_free(&S.Kfree);
+  S.nbc = S.nlift_rows = S.nlift = 0;
+  S.ready = false;
+  S.pred_iters = 0;
+}
+
+void load_free(hf_ctx* ctx) {
+  dev_free(&ctx->d_load);
+  ctx->have_load = false;
+}
+
 // Upload the tables and size every buffer of the context for the mesh.
 int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int32_t* tri, const int32_t* tag, MeshTables& T) {
   free_batch(ctx);
   free_batch_state(ctx->fluxb);
   free_batch_cols(ctx);
   proj_free(ctx);
+  steady_free(ctx);
+  load_free(ctx);
   ctx->n = n; ctx->ne = ne; ctx->nnz = static_cast<int64_t>(T.colidx.size());
   ctx->nchunks = (n + RB - 1) / RB;
   ctx->nblk_a = (n + RBA - 1) / RBA;
@@ -94,6 +137,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   HF_HIP(copy_sync(ctx, ctx->d_zr, zr, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
   ctx->rg_ok = T.rg.ok && rowgather_smem_bytes(T.max_blk_nnz, T.rg.cols.max_dict) <= 160 * 1024;
   ctx->rg_grid = 0;
+  ctx->rg_grid_k = 0;
   if (ctx->rg_ok) {
     const RowGather& G = T.rg;
     ctx->rg_max_dict = G.cols.max_dict;
@@ -442,6 +486,7 @@ int hf_destroy(hf_ctx* ctx) {
   dev_free(&ctx->d_uprev); dev_free(&ctx->d_ustart);
   dev_free(&ctx->d_u); dev_free(&ctx->d_b); dev_free(&ctx->d_r); dev_free(&ctx->d_p); dev_free(&ctx->d_Ap);
   free_batch(ctx); free_batch_state(ctx->fluxb); free_batch_cols(ctx); free_amg(ctx); free_responses(ctx); proj_free(ctx); dev_free(&ctx->d_z); dev_free(&ctx->d_z2);
+  steady_free(ctx); load_free(ctx);
   dev_free(&ctx->d_M1); dev_free(&ctx->d_dinv1); dev_free(&ctx->d_gz); dev_free(&ctx->d_gr); dev_free(&ctx->d_bz); dev_free(&ctx->d_br);
   dev_free(&ctx->d_tmp); dev_free(&ctx->d_part_pAp); dev_free(&ctx->d_part_rz); dev_free(&ctx->d_part_zz);
   dev_free(&ctx->d_part_bn); dev_free(&ctx->d_scal); dev_free(&ctx->d_samp_idx); dev_free(&ctx->d_samp); dev_free(&ctx->d_fsamp_idx);
@@ -543,6 +588,7 @@ int hf_set_materials(hf_ctx* ctx, int32_t n_mat, const int32_t* tags, const doub
   HF_TRY(upload_rg_tables(ctx, tk, &tc));
   ctx->have_mat = true;
   ctx->assembled = false;
+  ctx->steady.ready = false;   // K depends on kappa: hf_steady_setup again
   return HF_OK;
 }
 
@@ -561,6 +607,7 @@ int hf_update_kappa(hf_ctx* ctx, int32_t n_mat, const int32_t* tags, const doubl
   }
   HF_HIP(copy_sync(ctx, ctx->d_kappa, tk.data(), sizeof(double) * ctx->tab_len, hipMemcpyHostToDevice));
   HF_TRY(upload_rg_tables(ctx, tk, nullptr));
+  ctx->steady.ready = false;
   return hf_assemble(ctx, ctx->dt, ctx->mode);
 }
 
@@ -962,9 +1009,152 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
   return rc;
 }
 
+int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t precond) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh || !ctx->have_mat) return fail(ctx, HF_ERR_STATE, "hf_steady_setup needs hf_set_mesh and hf_set_materials first");
+  if (n_s <= 0 || !dofs) return fail(ctx, HF_ERR_ARG, "hf_steady_setup: empty Dirichlet set (the stiffness alone is singular)");
+  if (precond < 0 || precond > 1) return fail(ctx, HF_ERR_ARG, "hf_steady_setup: unknown preconditioner %d", precond);
+  if (!ctx->rg_ok || (ctx->assembled && ctx->mode != HF_ASM_ROW_GATHER))
+    return fail(ctx, HF_ERR_ARG, "hf_steady_setup: the steady operator is assembled by the row-gather kernel only (HF_ASM_ROW_GATHER on a mesh with row-gather lists)");
+  std::vector<char> seen(ctx->n, 0);
+  for (int32_t q = 0; q < n_s; ++q) {
+    if (dofs[q] < 0 || dofs[q] >= ctx->n) return fail(ctx, HF_ERR_ARG, "hf_steady_setup: dof %d outside [0,%d)", dofs[q], ctx->n);
+    if (seen[dofs[q]]) return fail(ctx, HF_ERR_ARG, "hf_steady_setup: dof %d listed twice (resolve overlaps on the host)", dofs[q]);
+    seen[dofs[q]] = 1;
+  }
+  HF_HIP(hipSetDevice(ctx->dev));
+  steady_free(ctx);
+  hf_ctx::Steady& S = ctx->steady;
+  const int n = ctx->n;
+  S.nbc = n_s;
+  HF_TRY(dev_alloc(ctx, &S.bc_dofs, n_s));
+  HF_TRY(dev_alloc(ctx, &S.g, n_s));
+  HF_TRY(dev_alloc(ctx, &S.Kfree, ctx->nnz));
+  HF_TRY(dev_alloc(ctx, &S.K, ctx->nnz));
+  HF_TRY(dev_alloc(ctx, &S.dinv, n));
+  HF_HIP(copy_sync(ctx, S.bc_dofs, dofs, sizeof(int32_t) * n_s, hipMemcpyHostToDevice));
+  HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  // K = the dt K part of the transient operator at dt = 1 (r-weighted), kept as assembled for hf_hold_load
+  HF_TRY(launch_assemble_rows<true>(ctx, ctx->d_kappa_rg, ctx->d_rhoc_rg, 1.0, nullptr, S.Kfree));
+  HF_HIP(hipMemcpyAsync(S.K, S.Kfree, sizeof(double) * ctx->nnz, hipMemcpyDeviceToDevice, ctx->stream));
+  {
+    SteadyScope sw(ctx);
+    HF_TRY(build_lift(ctx));    // lifting lists of S (into the swapped fields)
+    if (ctx->nlift > 0)
+      hipLaunchKernelGGL(k_take_lift, dim3((ctx->nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift, ctx->d_lift_slot,
+                         ctx->d_A, ctx->d_lift_val);
+    hipLaunchKernelGGL(k_bc_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs, ctx->d_rowptr,
+                       ctx->d_colidx, ctx->d_A);
+    hipLaunchKernelGGL(k_dinv, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, ctx->d_rowptr, ctx->d_colidx, ctx->d_A, ctx->d_dinv);
+    HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    HF_HIP(hipGetLastError());
+    HF_HIP(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->last_ms = ms;
+    if (precond == 1) HF_TRY(build_amg_auto(ctx));   // hierarchy of K_hat_S, apart from the transient's
+  }
+  S.precond = precond;
+  S.pred_iters = 0;
+  S.ready = true;
+  return HF_OK;
+}
+
+int hf_steady_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, double rtol, double atol, int32_t max_it, int32_t* iters,
+                    double* resid) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->steady.ready) return fail(ctx, HF_ERR_STATE, "hf_steady_solve before hf_steady_setup (or the materials changed since)");
+  if (!g_s) return fail(ctx, HF_ERR_ARG, "hf_steady_solve: g_S is null");
+  if (max_it <= 0 || rtol < 0 || atol < 0) return fail(ctx, HF_ERR_ARG, "hf_steady_solve: bad tolerances");
+  HF_HIP(hipSetDevice(ctx->dev));
+  const bool with_load = use_load != 0 && ctx->have_load;
+  int rc = HF_OK;
+  {
+    SteadyScope sw(ctx);
+    const int nb = ctx->nbc;
+    HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    // b = F (or 0) - K[:, S] g_S on the free rows, b_S = g_S; the iterate starts from the current state with u_S = g_S
+    if (with_load) HF_HIP(hipMemcpyAsync(ctx->d_b, ctx->d_load, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+    else HF_HIP(hipMemsetAsync(ctx->d_b, 0, sizeof(double) * ctx->n, ctx->stream));
+    HF_HIP(hipMemcpyAsync(ctx->d_g, g_s, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
+    if (ctx->nlift_rows > 0)
+      hipLaunchKernelGGL(k_lift, dim3((ctx->nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift_rows, ctx->d_lift_rows,
+                         ctx->d_lift_ptr, ctx->d_lift_bc, ctx->d_lift_val, ctx->d_g, ctx->d_b);
+    hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, ctx->d_g, ctx->d_b, ctx->d_u);
+    HF_HIP(hipGetLastError());
+    const LinSys sys{ctx->d_A, ctx->d_dinv, ctx->d_u, ctx->d_b};
+    const bool use_amg = ctx->steady.precond == 1 && ctx->amg_ready;
+    rc = pcg_solve(ctx, sys, use_amg, rtol, atol, max_it, &ctx->steady.pred_iters);
+    if (rc == HF_ERR_NOCONV && use_amg && ctx->h_scal->done == 2) {   // as hf_step: finish with Jacobi on a breakdown
+      ctx->amg_fallbacks += 1;
+      int pred = 0;
+      rc = pcg_solve(ctx, sys, false, rtol, atol, max_it, &pred);
+    }
+    if (rc == HF_ERR_HIP) return rc;
+    HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    HF_HIP(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->last_ms = ms;
+  }
+  // a new state, as hf_set_state: the history of the start vector does not continue
+  ctx->have_prev = false;
+  ctx->g_hist = 0;
+  proj_clear(ctx, true);
+  if (iters) *iters = ctx->h_scal->iters;
+  if (resid) *resid = std::sqrt(ctx->h_scal->zz / std::max(ctx->h_scal->bn2, 1e-300));
+  return rc;
+}
+
+int hf_set_load(hf_ctx* ctx, const double* F) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_set_load before hf_set_mesh");
+  HF_HIP(hipSetDevice(ctx->dev));
+  if (!F) { load_free(ctx); return HF_OK; }
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_set_load: a batch is open (the batched loop has no load term)");
+  HF_TRY(dev_alloc(ctx, &ctx->d_load, ctx->n));
+  HF_HIP(copy_sync(ctx, ctx->d_load, F, sizeof(double) * ctx->n, hipMemcpyHostToDevice));
+  ctx->have_load = true;
+  return HF_OK;
+}
+
+int hf_get_load(hf_ctx* ctx, double* F) {
+  if (!ctx || !F) return HF_ERR_ARG;
+  if (!ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_get_load: no load set");
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_HIP(copy_sync(ctx, F, ctx->d_load, sizeof(double) * ctx->n, hipMemcpyDeviceToHost));
+  return HF_OK;
+}
+
+int hf_hold_load(hf_ctx* ctx) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->steady.ready) return fail(ctx, HF_ERR_STATE, "hf_hold_load before hf_steady_setup (it needs the stiffness)");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_hold_load: a batch is open (the batched loop has no load term)");
+  HF_HIP(hipSetDevice(ctx->dev));
+  const int n = ctx->n;
+  DevTemp<unsigned char> t_mask;
+  HF_TRY(dev_alloc(ctx, &t_mask.p, n));
+  if (!ctx->d_load) HF_TRY(dev_alloc(ctx, &ctx->d_load, n));
+  HF_HIP(hipMemsetAsync(t_mask.p, 0, n, ctx->stream));
+  HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  if (ctx->nbc > 0)    // rows of the transient's Dirichlet set B
+    hipLaunchKernelGGL(k_mark_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs, t_mask.p);
+  hipLaunchKernelGGL(k_hold_load, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, ctx->stream, n, ctx->d_rowptr, ctx->d_colidx,
+                     ctx->steady.Kfree, ctx->d_u, t_mask.p, ctx->d_load);
+  HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+  HF_HIP(hipGetLastError());
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  ctx->last_ms = ms;
+  ctx->have_load = true;
+  return HF_OK;
+}
+
 int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_batch_begin before hf_assemble");
+  if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_batch_begin: a load is set (the batched loop has no load term; hf_set_load(NULL) first)");
   if (nv != 2 && nv != 4 && nv != 8 && nv != 16) return fail(ctx, HF_ERR_ARG, "hf_batch_begin: 2, 4, 8 or 16 columns (got %d)", nv);
   if (operator_kind < 0 || operator_kind > 2) return fail(ctx, HF_ERR_ARG, "hf_batch_begin: unknown operator kind %d", operator_kind);
   if (operator_kind == HF_BATCH_PER_COLUMN && ctx->precond == 1 && !ctx->amg_reuse)

@@ -143,7 +143,7 @@ struct hf_ctx {
   uint16_t *d_rg_ell = nullptr, *d_rg_cid = nullptr;
   int32_t* d_rg_dict = nullptr;     // the blocks' column lists (global node ids)
   double2* d_rg_zrb = nullptr;      // coordinates of every block's column list (own rows + halo)
-  int rg_max_dict = 0, rg_grid = 0;
+  int rg_max_dict = 0, rg_grid = 0, rg_grid_k = 0;   // (rg_grid_k: grid of the stiffness-only variant)
   int64_t n_rg_ell = 0, n_rg_dict = 0, n_cdict = 0;
   std::vector<int32_t> h_rg_tags;
   double *d_kappa_rg = nullptr, *d_rhoc_rg = nullptr;
@@ -224,6 +224,27 @@ struct hf_ctx {
   // tables, Dirichlet set - compared with the context's own operator whenever a kept or installed hierarchy meets a new hf_assemble
   struct OperatorPrint { double dt = 0.0; std::vector<double> kappa, rhoc; int32_t nbc = 0; uint64_t bc_hash = 0; } amg_print;
   long long amg_fallbacks = 0;   // steps finished by Jacobi-PCG after a multigrid-PCG breakdown
+  // steady state (hf_steady_setup / hf_steady_solve): the stiffness K on the pattern - as assembled (Kfree, for hf_hold_load)
+  // and with its own Dirichlet set S eliminated (K) -, the lifting columns K[free, S], D^-1 and a multigrid hierarchy of
+  // its own.  While the steady operator is set up or solved these fields trade places with the transient's (steady_swap in
+  // heatflow_hip.hip), so that the solver code runs on them unchanged and the transient's stay untouched.
+  struct Steady {
+    bool ready = false;
+    int precond = 0, pred_iters = 0;
+    int32_t nbc = 0, nlift_rows = 0, nlift = 0;
+    int32_t *bc_dofs = nullptr, *lift_rows = nullptr, *lift_ptr = nullptr, *lift_bc = nullptr, *lift_slot = nullptr;
+    double *g = nullptr, *lift_val = nullptr, *K = nullptr, *dinv = nullptr, *Kfree = nullptr;
+    std::vector<DevLevel> amg;
+    double* coarse_inv = nullptr;
+    float* coarse_inv_f = nullptr;
+    int coarse_n = 0, coarse_ld = 0;
+    bool amg_ready = false, amg_fine_stale = false;
+    double amg_opc = 0.0, amg_setup_s = 0.0;
+    OperatorPrint amg_print;
+  } steady;
+  // load term of the time step (hf_set_load / hf_hold_load): b = M u^n + dt F
+  double* d_load = nullptr;
+  bool have_load = false;
   double *d_z = nullptr, *d_z2 = nullptr;
   // read-flux projection (hf_flux_setup): unit-rho_c r-weighted mass matrix and the projected gradient
   bool flux_ready = false;

@@ -263,6 +263,9 @@ __device__ __forceinline__ ElemRow element_row(const double2 Pi, const double2 P
 constexpr int RG_NC = 4;   // 16-byte vectors of column positions a lane can prefetch (RBA * 8 * RG_NC >= slab slots: rows hold <= 32 entries)
 constexpr int RG_NX = 5;   // coordinate pairs a lane can prefetch (RBA * RG_NX >= column-list length, checked on the host)
 
+// KONLY: the stiffness alone (the steady operator, hf_steady_setup): Av receives K, the slab's M half stays zero, Mv is not
+// written (may be null); rhoc_idx and dt are not used.
+template <bool KONLY>
 __global__ __launch_bounds__(RBA) void k_assemble_rows(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
                                                        const int32_t* __restrict__ rowptr,
                                                        const int4* __restrict__ hdr /* 2 per block */,
@@ -329,6 +332,13 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows(int nblk, int cap /* slab
           if (e == 0xFFFFu) continue;
           const int pj = e & 31u, pk = (e >> 5) & 31u, tg = e >> 10;
           const double2 Pj = sXd[sC[sbase + pj]], Pk = sXd[sC[sbase + pk]];
+          if (KONLY) {
+            const ElemRow r = element_row(Pi, Pj, Pk, 0.0, kappa_idx[tg]);
+            dA += r.k0;
+            sMA[base + pj].y += r.k1;
+            sMA[base + pk].y += r.k2;
+            continue;
+          }
           const ElemRow r = element_row(Pi, Pj, Pk, rhoc_idx[tg], kappa_idx[tg]);
           dM += r.m0;
           dA += fma(dt, r.k0, r.m0);
@@ -348,7 +358,7 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows(int nblk, int cap /* slab
     // stream the slab out and leave it zeroed for the next block (slot k stays with the lane that reads it here)
     for (int k = t; k < cA.y; k += RBA) {
       const double2 v = sMA[k];
-      Mv[cA.x + k] = v.x;
+      if (!KONLY) Mv[cA.x + k] = v.x;
       Av[cA.x + k] = v.y;
       sMA[k] = make_double2(0.0, 0.0);
     }
@@ -552,6 +562,24 @@ __global__ void k_gather(int ns, const int32_t* __restrict__ idx, const double* 
   if (q < ns) out[q] = u[idx[q]];
 }
 
+// Hold load of a pre-heated transient (hf_hold_load): F_i = (K u)_i on the rows outside the transient's Dirichlet set B
+// (mask[i] = 0), F_i = 0 on B.  One lane per row, products summed in CSR order (bitwise reproducible); runs once per run.
+__global__ __launch_bounds__(TPB) void k_hold_load(int n, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+                                                   const double* __restrict__ K, const double* __restrict__ u,
+                                                   const unsigned char* __restrict__ mask, double* __restrict__ F) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= n) return;
+  double s = 0.0;
+  if (!mask[row])
+    for (int k = rowptr[row]; k < rowptr[row + 1]; ++k) s += K[k] * u[colidx[k]];
+  F[row] = s;
+}
+
+__global__ void k_mark_rows(int nq, const int32_t* __restrict__ idx, unsigned char* __restrict__ mask) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < nq) mask[idx[q]] = 1;
+}
+
 // ------------------------------------------------------------------------------------------
 // CSR SpMV, LDS-staged ("CSR-stream"): a workgroup takes chunks of RB consecutive rows; all
 // 256 lanes stream the chunk's values and column indices in nnz order (fully coalesced) and
@@ -568,6 +596,8 @@ __global__ void k_gather(int ns, const int32_t* __restrict__ idx, const double* 
 //           2 u^n - u^{n-1} of the next solve; `b` carries u^{n-1})
 //   MODE 9: PCG iteration head (x = z): convergence test, beta, Ap <- A z + beta Ap, p <- z + beta p,
 //           p.Ap partials - SpMV and direction update in one pass
+//   MODE 10: y = A x + w F            (RHS with a load: b = M u^n + dt F; F comes in the `dinv` operand)
+//   MODE 11: y = A x + w F; p = 2 x - b   (MODE 8 with the load of MODE 10)
 // The chunk is `rpc` rows (512 for the fine operator; fewer for long-row transfer operators so
 // that a chunk's products fit the 64-KB LDS window).
 // ------------------------------------------------------------------------------------------
@@ -707,11 +737,11 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   // would then cover all loads in flight, the prefetched ones of the next chunk included
   auto row_operands = [&](int prc, bool from_slice) {
     RowOps e{0.0, 0.0, 0.0, 0.0, 0.0};
-    if (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 7 || MODE == 8) e.b = bvec[prc];
-    if (MODE == 2 || MODE == 4 || MODE == 5) e.d = dinv[prc];
+    if (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 7 || MODE == 8 || MODE == 11) e.b = bvec[prc];
+    if (MODE == 2 || MODE == 4 || MODE == 5 || MODE == 10 || MODE == 11) e.d = dinv[prc];
     if (MODE == 6 || (MODE == 9 && !first9)) e.y = y[prc];
     if (MODE == 9 && !first9) e.p = pvec[prc];
-    if ((MODE == 4 || MODE == 8 || MODE == 9) && !from_slice) e.x = x[prc];
+    if ((MODE == 4 || MODE == 8 || MODE == 9 || MODE == 11) && !from_slice) e.x = x[prc];
     return e;
   };
   // the chunk's products are parked in sprod: row sums in CSR order and the mode's epilogue
@@ -759,6 +789,11 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         y[row] = e.y + s;
       } else if (MODE == 8) {
         y[row] = s;
+        pvec[row] = 2.0 * e.x - e.b;
+      } else if (MODE == 10) {
+        y[row] = s + w * e.d;
+      } else if (MODE == 11) {
+        y[row] = s + w * e.d;
         pvec[row] = 2.0 * e.x - e.b;
       } else {
         const double api = first9 ? s : s + beta * e.y;          // first iteration: p = z, Ap = A z
@@ -827,7 +862,7 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         const int i = static_cast<int>(threadIdx.x) + u * TS;
         if (i < nd) {
           xd[i] = x0[u];
-          if ((MODE == 4 || MODE == 8 || MODE == 9) && c0[u] == r0) s_own = i;
+          if ((MODE == 4 || MODE == 8 || MODE == 9 || MODE == 11) && c0[u] == r0) s_own = i;
         }
       }
       for (int i = threadIdx.x + HF_STAGE_U * TS; i < nd; i += HF_STAGE_U * TS) {   // lists longer than the head (rare)
@@ -841,12 +876,12 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         for (int u = 0; u < HF_STAGE_U; ++u)
           if (i + u * TS < nd) {
             xd[i + u * TS] = xv[u];
-            if ((MODE == 4 || MODE == 8 || MODE == 9) && c[u] == r0) s_own = i + u * TS;
+            if ((MODE == 4 || MODE == 8 || MODE == 9 || MODE == 11) && c[u] == r0) s_own = i + u * TS;
           }
       }
       __syncthreads();
       HF_STAMP(stamp_at); ++stamp_at;
-      if ((MODE == 4 || MODE == 8 || MODE == 9) && comp.own && pin) e.x = xd[s_own + (prow - r0)];
+      if ((MODE == 4 || MODE == 8 || MODE == 9 || MODE == 11) && comp.own && pin) e.x = xd[s_own + (prow - r0)];
       // (3) products in stream order
 #pragma unroll
       for (int u = 0; u < UN; ++u) {
@@ -917,12 +952,12 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
         for (int u = 0; u < HF_STAGE_U; ++u)
           if (i + u * TS < nd) {
             xd[i + u * TS] = xv[u];
-            if ((MODE == 4 || MODE == 8 || MODE == 9) && c[u] == r0) s_own = i + u * TS;
+            if ((MODE == 4 || MODE == 8 || MODE == 9 || MODE == 11) && c[u] == r0) s_own = i + u * TS;
           }
       }
       __syncthreads();
       HF_STAMP(stamp_at); ++stamp_at;
-      if ((MODE == 4 || MODE == 8 || MODE == 9) && comp.own && pin) e.x = xd[s_own + (prow - r0)];
+      if ((MODE == 4 || MODE == 8 || MODE == 9 || MODE == 11) && comp.own && pin) e.x = xd[s_own + (prow - r0)];
       while (k < k1) {
         const int kn = k + HF_UNROLL * TS;
         double vn[HF_UNROLL];

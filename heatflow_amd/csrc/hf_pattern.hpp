@@ -364,21 +364,23 @@ size_t rowgather_smem_bytes(int max_blk_nnz, int max_dict) {
   return cap * 16 + static_cast<size_t>(max_dict) * 16 + (RBA + 4) * 4 + (cap / 8 + 3) * 16;
 }
 
-// Row-gather element kernel into (Mout, Aout); coefficient tables indexed by the tag dictionary.
+// Row-gather element kernel into (Mout, Aout); coefficient tables indexed by the tag dictionary.  KONLY: the stiffness
+// alone into Aout (Mout, rhoc_idx and dt unused).
+template <bool KONLY = false>
 int launch_assemble_rows(hf_ctx* ctx, const double* kappa_idx, const double* rhoc_idx, double dt, double* Mout, double* Aout) {
   const int cap = (ctx->max_blk_nnz + 1) & ~1;
   const int capd = ctx->rg_max_dict;
   const size_t sm = rowgather_smem_bytes(ctx->max_blk_nnz, capd);
-  if (ctx->rg_grid == 0) {   // persistent workgroups: as many as fit the chip at this LDS footprint
-    if (sm > 64 * 1024)
-      HF_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_assemble_rows), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 static_cast<int>(sm)));
+  const void* fn = reinterpret_cast<const void*>(&k_assemble_rows<KONLY>);
+  int& grid = KONLY ? ctx->rg_grid_k : ctx->rg_grid;
+  if (grid == 0) {   // persistent workgroups: as many as fit the chip at this LDS footprint
+    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
     int per_cu = 0, ncu = 0;
-    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&k_assemble_rows), RBA, sm));
+    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
     HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
-    ctx->rg_grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
   }
-  hipLaunchKernelGGL(k_assemble_rows, dim3(ctx->rg_grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr,
+  hipLaunchKernelGGL(k_assemble_rows<KONLY>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr,
                      ctx->d_rg_hdr, reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid),
                      ctx->d_rg_zrb, kappa_idx, rhoc_idx, dt, Mout, Aout);
   HF_HIP(hipGetLastError());

@@ -733,6 +733,14 @@ int prepare_response(hf_ctx* ctx, const double* g_new, int max_it, RespArgs* ra)
   return HF_OK;
 }
 
+// b = M u^n, plus dt F when a load is set (hf_set_load / hf_hold_load); without a load exactly the kernel of before
+void launch_rhs(hf_ctx* ctx) {
+  if (ctx->have_load)
+    launch_spmv<10>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, nullptr, nullptr, nullptr, nullptr, ctx->dt, ctx->d_load);
+  else
+    launch_spmv<0>(ctx, ctx->d_M, ctx->d_u, ctx->d_b);
+}
+
 // One time step to the boundary values g_host (n_bc doubles on the host; g_dev = the same values already on
 // the device, or null).  Leaves iteration count / residual in h_scal.
 int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double rtol, double atol, int max_it) {
@@ -748,12 +756,15 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
   if (projected) {
     // b = M u^n, lifting, set_bc; then the start vector = A-norm projection of the new solution on the span of the last
     // solutions and the boundary responses (kind 3)
-    launch_spmv<0>(ctx, ctx->d_M, ctx->d_u, ctx->d_b);
+    launch_rhs(ctx);
     ctx->have_prev = true;
   } else if (ctx->extrapolate && ctx->have_prev) {
     // b = M u^n   (assemble_vector, run_with_diamond.py:476); with a previous step available the same
     // pass writes the extrapolated start vector 2 u^n - u^{n-1}, and the three state buffers rotate
-    launch_spmv<8>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, ctx->d_uprev, ctx->d_ustart);
+    if (ctx->have_load)
+      launch_spmv<11>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, ctx->d_uprev, ctx->d_ustart, nullptr, nullptr, ctx->dt, ctx->d_load);
+    else
+      launch_spmv<8>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, ctx->d_uprev, ctx->d_ustart);
     // u^{n-1} <- u^n, iterate <- start vector
     HF_HIP(hipMemcpyAsync(ctx->d_uprev, ctx->d_u, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
     if (ra.k > 0)
@@ -761,7 +772,7 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
     else
       HF_HIP(hipMemcpyAsync(ctx->d_u, ctx->d_ustart, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
   } else {
-    launch_spmv<0>(ctx, ctx->d_M, ctx->d_u, ctx->d_b);
+    launch_rhs(ctx);
     if (ctx->extrapolate) {         // keep u^n for the next step
       HF_HIP(hipMemcpyAsync(ctx->d_uprev, ctx->d_u, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
       ctx->have_prev = true;

@@ -25,7 +25,8 @@ EXPORTS = [
     "hf_pattern_export", "hf_amg_export_size", "hf_amg_export", "hf_amg_install", "hf_set_materials",
     "hf_update_kappa", "hf_set_dirichlet", "hf_assemble", "hf_set_precond", "hf_set_start_vector", "hf_get_response_solves", "hf_get_amg_info", "hf_get_amg_fallbacks", "hf_set_state", "hf_get_state", "hf_sample", "hf_step", "hf_run",
     "hf_batch_begin", "hf_batch_load_column", "hf_batch_set_affine", "hf_batch_set_state", "hf_batch_get_state", "hf_batch_run", "hf_batch_run_flux", "hf_batch_end",
-    "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample", "hf_get_sizes", "hf_get_csr", "hf_spmv", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
+    "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
+    "hf_steady_setup", "hf_steady_solve", "hf_set_load", "hf_get_load", "hf_hold_load", "hf_get_sizes", "hf_get_csr", "hf_spmv", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
 
 
@@ -117,6 +118,11 @@ def load_library():
         "hf_flux_project": [vp, dbl, i32, pd, pd, pi],
         "hf_flux_solve": [vp, i32, dbl, i32, pi],
         "hf_flux_sample": [vp, i32, pi, pd, pd],
+        "hf_steady_setup": [vp, i32, pi, i32],
+        "hf_steady_solve": [vp, pd, i32, dbl, dbl, i32, pi, pd],
+        "hf_set_load": [vp, pd],
+        "hf_get_load": [vp, pd],
+        "hf_hold_load": [vp],
         "hf_get_sizes": [vp, pi, pi, C.POINTER(i64), pi],
         "hf_get_csr": [vp, pi, pi, pd, pd],
         "hf_spmv": [vp, i32, pd, pd],
@@ -445,6 +451,45 @@ class HeatflowHIP:
         gr = np.empty(len(nodes), dtype=np.float64) if want_r else None
         self._check(self._lib.hf_flux_sample(self._ctx, len(nodes), _pi(nodes), _pd(gz), _pd(gr)))
         return gz, gr
+
+    # -- steady state and loads (with_ir_steady.ipynb cells 17-23) ---------------------------
+    def steady_setup(self, dofs, precond=PC_JACOBI):
+        """Assemble the r-weighted stiffness K and eliminate the steady Dirichlet set ``dofs`` (its own, independent of
+        set_dirichlet's); ``precond``: PC_JACOBI or PC_AMG (a hierarchy of its own).  An empty set raises ValueError."""
+        d = _i32(dofs)
+        self._check(self._lib.hf_steady_setup(self._ctx, len(d), _pi(d) if len(d) else None, int(precond)))
+        self.n_steady = len(d)
+
+    def steady_solve(self, g, use_load=False, rtol=1e-10, atol=0.0, max_it=20000):
+        """K u = F on the free rows with u = g on the steady set (order of steady_setup's dofs); F = the load when
+        ``use_load`` and one is set, else 0.  The answer becomes the state.  Returns (iterations, relative residual)."""
+        g = _f64(g)
+        if g.shape != (getattr(self, "n_steady", -1),):
+            raise ValueError(f"steady_solve: expected {getattr(self, 'n_steady', 0)} boundary values (steady_setup first)")
+        it, res = C.c_int32(), C.c_double()
+        rc = self._lib.hf_steady_solve(self._ctx, _pd(g), 1 if use_load else 0, rtol, atol, int(max_it), C.byref(it), C.byref(res))
+        self.last_iters, self.last_resid = it.value, res.value
+        self._check(rc)
+        return it.value, res.value
+
+    def set_load(self, F):
+        """Load of the time step (b = M u^n + dt F): n values, or None to clear it."""
+        if F is None:
+            self._check(self._lib.hf_set_load(self._ctx, None))
+            return
+        F = _f64(F)
+        if F.shape != (self.n,):
+            raise ValueError(f"set_load: expected {self.n} values")
+        self._check(self._lib.hf_set_load(self._ctx, _pd(F)))
+
+    def hold_load(self):
+        """Set the load that holds the current state: (K u)_i off the Dirichlet rows of set_dirichlet, 0 on them."""
+        self._check(self._lib.hf_hold_load(self._ctx))
+
+    def get_load(self):
+        F = np.empty(self.n, dtype=np.float64)
+        self._check(self._lib.hf_get_load(self._ctx, _pd(F)))
+        return F
 
     # -- inspection ----------------------------------------------------------------------
     def get_csr(self, values=True):

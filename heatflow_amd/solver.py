@@ -133,6 +133,33 @@ class HeatProblem:
         return times, samples, iters
 
 
+    # -- steady state and pre-heated transients (with_ir_steady.ipynb cells 17-23) -------------
+    def solve_steady(self, bcs=None, t=0.0, use_load=False):
+        """Steady state K u = F with its own Dirichlet list ``bcs`` (default: the problem's), merged last-wins and
+        evaluated at ``t``; K is the r-weighted stiffness of the transient operator (steady state), F the
+        load when ``use_load`` and one is set, else 0.  The answer becomes the state.  Returns (u, iters, resid)."""
+        bcs = self.bcs if bcs is None else list(bcs)
+        if not bcs:
+            raise ValueError("solve_steady: no Dirichlet condition (the stiffness alone is singular)")
+        dofs, owner, pos = merge_bcs(bcs)
+        for bc in bcs:
+            bc.update(t)
+        g = gather_bc_values(bcs, owner, pos)
+        self.backend.steady_setup(dofs, self.precond)
+        it, res = self.backend.steady_solve(g, use_load, self.rtol, self.atol, self.max_it)
+        return self.backend.get_state(), it, res
+
+    def set_load(self, F):
+        """Load term of every following step, b = M u^n + dt F (n values); None removes it."""
+        self.backend.set_load(None if F is None else np.asarray(F, dtype=np.float64))
+
+    def hold_load(self):
+        """The load that holds the current state (the notebook's b_equiv = A_free u_ss): (K u)_i off the problem's merged
+        Dirichlet rows, 0 on them; it becomes the load and is returned.  Needs a solve_steady before (for K)."""
+        self.backend.hold_load()
+        return self.backend.get_load()
+
+
 def nearest_nodes(coords, points):
     """Nearest mesh node of each (z, r) point (run_with_diamond.py:443-449 asks a cKDTree over geometry.x[:, :2] for it).
     A handful of watcher points does not repay a tree over the whole mesh (60 ms to build at 2e5 nodes, plus the import of

@@ -21,6 +21,12 @@
  *   hf_get_state       u_n.x.array (what xdmf.write_function would write)   :483-484
  *   hf_flux_setup      assemble_matrix(a_proj) + KSP/LU set-up       run_no_diamond.py:471-491
  *   hf_flux_project    assemble_vector(rhs_proj) + solver_proj.solve run_no_diamond.py:543-550
+ *   hf_steady_setup    Space.build_steady_state_variational_forms + assemble_matrix(a_ss, bcs_ss) + solver set-up
+ *                                                           space/space_and_forms.py:119-149, with_ir_steady.ipynb cell 17
+ *   hf_steady_solve    assemble_vector(L_ss) + apply_lifting + set_bc + solve     with_ir_steady.ipynb cell 17
+ *   hf_set_load        the load term dt * f * v * r * dx of build_variational_forms  space/space_and_forms.py:77-117;
+ *                      b_equiv uploaded as it stands                    with_ir_steady.ipynb cells 18, 22
+ *   hf_hold_load       b_equiv = A_free . u_ss with the transient's Dirichlet rows zeroed   with_ir_steady.ipynb cell 18
  *
  * Conventions
  *   - All functions return 0 (HF_OK) or a negative HF_ERR_* code; hf_last_error(ctx)
@@ -242,6 +248,34 @@ int hf_flux_project(hf_ctx* ctx, double rtol, int32_t max_it, double* grad_z, do
 int hf_flux_solve(hf_ctx* ctx, int32_t components, double rtol, int32_t max_it, int32_t* iters);
 int hf_flux_sample(hf_ctx* ctx, int32_t n_s, const int32_t* nodes, double* grad_z, double* grad_r);
 
+/* Steady state and pre-heated transients (reference: Space.build_steady_state_variational_forms,
+ * space/space_and_forms.py:119-149, and the load term of build_variational_forms, :77-117; used by
+ * with_ir_steady.ipynb cells 17-23).
+ *   K  = the r-weighted P1 stiffness: the dt K part of hf_assemble's operator at dt = 1, entry for entry.  The reference's
+ *        steady form is planar (un-weighted) while its transient form is r-weighted; here both are r-weighted, so that the
+ *        steady state is the stationary point of the transient operator and a held state does not drift.
+ * hf_steady_setup  assembles K (row-gather kernel only: HF_ERR_ARG after an hf_assemble in another mode, or on a mesh
+ *        without row-gather lists), keeps it as assembled (K_free, for hf_hold_load), eliminates its own Dirichlet set S
+ *        (n_s unique dofs; it may differ from the transient's set B of hf_set_dirichlet) symmetrically with unit diagonal,
+ *        keeps the lifting columns K[free, S] aside and forms D^-1; precond 0 = Jacobi, 1 = a multigrid hierarchy of
+ *        K_hat_S of its own (the transient's operators, lifting and hierarchy are not touched).  n_s = 0 -> HF_ERR_ARG
+ *        (K alone is singular), before any launch.  hf_set_materials / hf_update_kappa make it stale: set up again.
+ * hf_steady_solve  K_hat_S u = F - K[:, S] g_S on the free rows, u_S = g_S (g_S in the order of dofs_S); F = the load of
+ *        hf_set_load / hf_hold_load when use_load != 0 and one is set, else zero.  PCG started from the current state,
+ *        stopping rule of hf_step.  The result becomes the state; the start-vector history is reset as by hf_set_state.
+ * hf_set_load      F (n doubles; NULL clears it).  While a load is set every hf_step / hf_run step uses
+ *        b = M u^n + dt F, then lifting and set_bc as before (F has no effect on Dirichlet rows).  hf_batch_begin with a
+ *        load set and hf_set_load / hf_hold_load while a batch is open return HF_ERR_STATE: a load is never dropped.
+ * hf_hold_load     F_i = (K_free u)_i for the rows outside the transient's set B, F_i = 0 on B, from the current state u
+ *        (needs hf_steady_setup), and sets it as the load: from u = u_ss with boundary values u_ss on B the transient stays.
+ * hf_get_load      copies the current load out (HF_ERR_STATE if none is set). */
+int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs_s, int32_t precond);
+int hf_steady_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, double rtol, double atol, int32_t max_it, int32_t* iters,
+                    double* resid);
+int hf_set_load(hf_ctx* ctx, const double* F);
+int hf_hold_load(hf_ctx* ctx);
+int hf_get_load(hf_ctx* ctx, double* F);
+
 int hf_get_sizes(hf_ctx* ctx, int32_t* n, int32_t* n_e, int64_t* nnz, int32_t* n_bc);
 /* Any pointer may be NULL.  A is the matrix as it stands (eliminated when BCs are set). */
 int hf_get_csr(hf_ctx* ctx, int32_t* rowptr, int32_t* colidx, double* A, double* M);
@@ -257,7 +291,8 @@ int hf_time_kernel(hf_ctx* ctx, int32_t which, int32_t reps, double* ms_avg);
  * hf_get_profile returns the summed duration and the number of launches. */
 int hf_set_profile(hf_ctx* ctx, int32_t on);
 int hf_get_profile(hf_ctx* ctx, double* spmv_ms_sum, int64_t* spmv_launches);
-/* GPU time (ms, HIP events on the ctx stream) of the last hf_step / hf_run / hf_assemble. */
+/* GPU time (ms, HIP events on the ctx stream) of the last hf_step / hf_run / hf_assemble / hf_steady_setup (assembly and
+ * elimination) / hf_steady_solve / hf_hold_load. */
 int hf_last_gpu_ms(hf_ctx* ctx, double* ms);
 
 #ifdef __cplusplus
