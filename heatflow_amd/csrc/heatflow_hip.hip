@@ -78,6 +78,12 @@ void load_free(hf_ctx* ctx) {
   ctx->have_load = false;
 }
 
+void tangent_free(hf_ctx* ctx) {
+  free_batch_state(ctx->tanb);
+  dev_free(&ctx->tan.col); dev_free(&ctx->tan.F);
+  ctx->tan = hf_ctx::Tangent();
+}
+
 // Upload the tables and size every buffer of the context for the mesh.
 int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int32_t* tri, const int32_t* tag, MeshTables& T) {
   free_batch(ctx);
@@ -86,6 +92,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   proj_free(ctx);
   steady_free(ctx);
   load_free(ctx);
+  tangent_free(ctx);
   ctx->n = n; ctx->ne = ne; ctx->nnz = static_cast<int64_t>(T.colidx.size());
   ctx->nchunks = (n + RB - 1) / RB;
   ctx->nblk_a = (n + RBA - 1) / RBA;
@@ -353,6 +360,73 @@ int upload_rg_tables(hf_ctx* ctx, const std::vector<double>& by_tag_k, const std
   if (by_tag_c) HF_HIP(copy_sync(ctx, ctx->d_rhoc_rg, c.data(), sizeof(double) * 64, hipMemcpyHostToDevice));
   return HF_OK;
 }
+// Vectors, partial sums, per-column scalars, host mirrors and projection ring of an nv-column batch state, zeroed
+// (hf_batch_begin; the tangent columns of hf_tangent_setup)
+int batch_alloc(hf_ctx* ctx, hf_ctx::Batch& B, int nv) {
+  const size_t n = static_cast<size_t>(ctx->n), vec = n * nv;
+  for (double** v : {&B.u, &B.uprev, &B.ustart, &B.b, &B.r, &B.p, &B.Ap, &B.z, &B.z2, &B.tmp}) {
+    HF_TRY(dev_alloc(ctx, v, vec));
+    HF_HIP(hipMemsetAsync(*v, 0, sizeof(double) * vec, ctx->stream));
+  }
+  HF_TRY(dev_alloc(ctx, &B.part_pAp, static_cast<size_t>(nv) * MAXP));
+  HF_TRY(dev_alloc(ctx, &B.part_rz, 2 * static_cast<size_t>(nv) * MAXP));
+  HF_TRY(dev_alloc(ctx, &B.part_zz, static_cast<size_t>(nv) * MAXP));
+  HF_TRY(dev_alloc(ctx, &B.part_bn, static_cast<size_t>(nv) * MAXP));
+  HF_TRY(dev_alloc(ctx, &B.scal, nv));
+  HF_HIP(hipMemsetAsync(B.scal, 0, sizeof(Scal) * nv, ctx->stream));
+  HF_TRY(dev_alloc(ctx, &B.red, 1));
+  HF_HIP(hipMemsetAsync(B.red, 0, sizeof(BRed), ctx->stream));
+  for (int k = 0; k < PROJ_MH; ++k) {
+    HF_TRY(dev_alloc(ctx, &B.pV[k], vec));
+    HF_TRY(dev_alloc(ctx, &B.pF[k], vec));
+    B.pused[k] = false;
+  }
+  HF_TRY(dev_alloc(ctx, &B.pG, static_cast<size_t>(nv) * PROJ_MT * PROJ_MT));
+  HF_TRY(dev_alloc(ctx, &B.palpha, static_cast<size_t>(nv) * (PROJ_MT + 1)));
+  HF_TRY(dev_alloc(ctx, &B.ppart, static_cast<size_t>(nv) * 2 * PROJ_MT * MAXP));
+  HF_HIP(hipMemsetAsync(B.pG, 0, sizeof(double) * nv * PROJ_MT * PROJ_MT, ctx->stream));
+  B.pnext = 0; B.ppending = -1;
+  if (hipHostMalloc(reinterpret_cast<void**>(&B.h_scal), sizeof(Scal) * nv) != hipSuccess) return fail(ctx, HF_ERR_ALLOC, "hipHostMalloc failed");
+  if (hipHostMalloc(reinterpret_cast<void**>(&B.h_mirror), sizeof(ScalMirror) * nv, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+      hipHostGetDevicePointer(reinterpret_cast<void**>(&B.d_mirror), B.h_mirror, 0) != hipSuccess)
+    return fail(ctx, HF_ERR_ALLOC, "hipHostMalloc (mapped) failed");
+  for (int j = 0; j < nv; ++j) B.h_mirror[j] = ScalMirror{};
+  B.epoch = 0;
+  const int rpb = TPB / nv;
+  B.Pb = static_cast<int>(std::min<size_t>((n + rpb - 1) / rpb, MAXP));
+  if (B.Pb >= 64) B.Pb &= ~7;
+  return HF_OK;
+}
+
+// the V-cycle's level vectors of an nv-column batch state for the context's current hierarchy (none without one)
+int batch_levels(hf_ctx* ctx, hf_ctx::Batch& B, int nv) {
+  if (ctx->precond == 1 && ctx->amg_ready) {   // level vectors, laid out as build_amg lays out the single-column ones
+    const size_t nl = ctx->amg.size();
+    B.lev.resize(nl);
+    for (size_t l = 1; l < nl; ++l) {
+      const DevLevel& L = ctx->amg[l];
+      hf_ctx::BatchLevel& Q = B.lev[l];
+      if (l + 1 < nl) {
+        const size_t len = (static_cast<size_t>(L.n) + L.P.ncol + 2) * nv;
+        HF_TRY(dev_alloc(ctx, &Q.cat, len));
+        HF_HIP(hipMemsetAsync(Q.cat, 0, sizeof(double) * len, ctx->stream));
+        Q.b = Q.cat;
+      } else {
+        HF_TRY(dev_alloc(ctx, &Q.b, (static_cast<size_t>(L.n) + 2) * nv));
+        Q.own_b = true;
+        HF_HIP(hipMemsetAsync(Q.b, 0, sizeof(double) * (static_cast<size_t>(L.n) + 2) * nv, ctx->stream));
+      }
+      if (l == 1) {
+        HF_TRY(dev_alloc(ctx, &Q.x, (static_cast<size_t>(L.n) + 2) * nv));
+        Q.res = Q.x;
+      } else {
+        Q.res = B.lev[l - 1].cat + static_cast<size_t>(ctx->amg[l - 1].n) * nv;
+      }
+    }
+  }
+  return HF_OK;
+}
+
 // nv-column Jacobi-PCG state of the batched loop's read-flux projection (one gradient component of every column per solve,
 // on the unit-coefficient mass matrix of hf_flux_setup); `uprev` keeps the z component's last projection when both are asked for
 int ensure_batch_flux(hf_ctx* ctx, int nv, int ncomp) {
@@ -431,6 +505,54 @@ int batch_flux_step(hf_ctx* ctx, int components, double rtol, int max_it, int nf
   }
   return HF_OK;
 }
+// ---- tangent runs (hf_tangent_setup / hf_run_tangent) ----
+// every tangent back to zero and the columns' start-vector history cleared (a new state, new materials, a new operator)
+int tangent_reset(hf_ctx* ctx) {
+  hf_ctx::Batch& T = ctx->tanb;
+  if (T.nv == 0) return HF_OK;
+  HF_HIP(hipMemsetAsync(T.u, 0, sizeof(double) * static_cast<size_t>(ctx->n) * T.nv, ctx->stream));
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  for (bool& u_ : T.pused) u_ = false;
+  T.pnext = 0; T.ppending = -1;
+  T.pred_iters = 0;
+  return HF_OK;
+}
+
+// the tangent columns' V-cycle vectors follow the context's hierarchy (hf_assemble may have rebuilt it since the last run)
+int tangent_levels(hf_ctx* ctx) {
+  hf_ctx::Batch& T = ctx->tanb;
+  std::vector<int64_t> sig;
+  if (ctx->precond == 1 && ctx->amg_ready)
+    for (const DevLevel& L : ctx->amg) { sig.push_back(L.n); sig.push_back(L.P.ncol); }
+  if (sig == ctx->tan.lev_sig) return HF_OK;
+  for (auto& L : T.lev) { dev_free(&L.x); dev_free(&L.cat); if (L.own_b) dev_free(&L.b); }
+  T.lev.clear();
+  HF_TRY(batch_levels(ctx, T, T.nv));
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  ctx->tan.lev_sig = sig;
+  return HF_OK;
+}
+
+// F = -K_j u for every tangent column j, from the context's current state
+int tangent_load(hf_ctx* ctx) {
+  const int capd = ctx->rg_max_dict;
+  const size_t sm = static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 + (RBA + 4) * 4 +
+                    (static_cast<size_t>((ctx->max_blk_nnz + 1) & ~1) / 8 + 3) * 16;
+  const int grid = std::min(ctx->nblk_a, 2048);
+#define HF_TL(NV) hipLaunchKernelGGL(k_tangent_load<NV>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr, \
+                                     reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), \
+                                     ctx->d_rg_zrb, ctx->d_rg_dict, ctx->d_rowptr, ctx->tan.col, ctx->d_u, ctx->tan.F)
+  switch (ctx->tan.nv) {
+    case 2: HF_TL(2); break;
+    case 4: HF_TL(4); break;
+    case 8: HF_TL(8); break;
+    default: HF_TL(16); break;
+  }
+#undef HF_TL
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -486,7 +608,7 @@ int hf_destroy(hf_ctx* ctx) {
   dev_free(&ctx->d_uprev); dev_free(&ctx->d_ustart);
   dev_free(&ctx->d_u); dev_free(&ctx->d_b); dev_free(&ctx->d_r); dev_free(&ctx->d_p); dev_free(&ctx->d_Ap);
   free_batch(ctx); free_batch_state(ctx->fluxb); free_batch_cols(ctx); free_amg(ctx); free_responses(ctx); proj_free(ctx); dev_free(&ctx->d_z); dev_free(&ctx->d_z2);
-  steady_free(ctx); load_free(ctx);
+  steady_free(ctx); load_free(ctx); tangent_free(ctx);
   dev_free(&ctx->d_M1); dev_free(&ctx->d_dinv1); dev_free(&ctx->d_gz); dev_free(&ctx->d_gr); dev_free(&ctx->d_bz); dev_free(&ctx->d_br);
   dev_free(&ctx->d_tmp); dev_free(&ctx->d_part_pAp); dev_free(&ctx->d_part_rz); dev_free(&ctx->d_part_zz);
   dev_free(&ctx->d_part_bn); dev_free(&ctx->d_scal); dev_free(&ctx->d_samp_idx); dev_free(&ctx->d_samp); dev_free(&ctx->d_fsamp_idx);
@@ -589,7 +711,7 @@ int hf_set_materials(hf_ctx* ctx, int32_t n_mat, const int32_t* tags, const doub
   ctx->have_mat = true;
   ctx->assembled = false;
   ctx->steady.ready = false;   // K depends on kappa: hf_steady_setup again
-  return HF_OK;
+  return tangent_reset(ctx);   // the tangents belonged to the old coefficients
 }
 
 int hf_update_kappa(hf_ctx* ctx, int32_t n_mat, const int32_t* tags, const double* kappa) {
@@ -679,7 +801,7 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
   ctx->pred_iters = 0;
   ctx->have_prev = false;
   free_responses(ctx);   // R depends on the operator
-  return HF_OK;
+  return tangent_reset(ctx);   // and so do the tangents (hf_update_kappa comes here too)
 }
 
 int hf_set_precond(hf_ctx* ctx, int32_t kind, int32_t reuse) {
@@ -925,7 +1047,8 @@ int hf_set_state(hf_ctx* ctx, const double* u) {
   ctx->have_prev = false;
   ctx->g_hist = 0;       // the state no longer continues the recursion the boundary history belongs to
   proj_clear(ctx, true);
-  return HF_OK;
+  ctx->tan.steady_state = false;
+  return tangent_reset(ctx);
 }
 
 int hf_get_state(hf_ctx* ctx, double* u) {
@@ -1007,6 +1130,129 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
   ctx->last_ms = ms;
   if (ns > 0 && rc == HF_OK) (void)copy_sync(ctx, samples, d_sall, sizeof(double) * n_steps * ns, hipMemcpyDeviceToHost);
   return rc;
+}
+
+int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup before hf_set_mesh");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a batch is open");
+  if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a load is set (tangents of pre-heated runs are not supported)");
+  if (n_par < 1 || n_par > NV_MAX) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: 1..%d parameters (got %d)", NV_MAX, n_par);
+  if (!tag_col) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tag_col is null");
+  for (int t = 0; t < ctx->tab_len; ++t) {
+    if (tag_col[t] < -1 || tag_col[t] >= n_par)
+      return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tag %d maps to column %d outside [-1,%d)", t, tag_col[t], n_par);
+    if (tag_col[t] >= 0 && !ctx->h_tag_used[t]) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tag %d is not a cell tag of the mesh", t);
+  }
+  if (!ctx->rg_ok || (ctx->assembled && ctx->mode != HF_ASM_ROW_GATHER))
+    return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tangent loads are formed by the row-gather kernel only (HF_ASM_ROW_GATHER on a mesh with row-gather lists)");
+  HF_HIP(hipSetDevice(ctx->dev));
+  const bool from_steady = ctx->tan.steady_state;
+  tangent_free(ctx);
+  ctx->tan.steady_state = from_steady;
+  const int nv = n_par <= 2 ? 2 : n_par <= 4 ? 4 : n_par <= 8 ? 8 : 16;
+  std::vector<int32_t> col(64, -1);    // by row-gather tag-dictionary index, as the coefficient tables of the kernel
+  for (size_t q = 0; q < ctx->h_rg_tags.size(); ++q) col[q] = tag_col[ctx->h_rg_tags[q]];
+  hf_ctx::Batch& T = ctx->tanb;
+  T.opk = HF_BATCH_SHARED;
+  HF_TRY(batch_alloc(ctx, T, nv));
+  HF_TRY(dev_alloc(ctx, &ctx->tan.col, 64));
+  HF_TRY(dev_alloc(ctx, &ctx->tan.F, static_cast<size_t>(ctx->n) * nv));
+  HF_HIP(copy_sync(ctx, ctx->tan.col, col.data(), sizeof(int32_t) * 64, hipMemcpyHostToDevice));
+  T.nv = nv;
+  T.load = ctx->tan.F;
+  ctx->tan.npar = n_par;
+  ctx->tan.nv = nv;
+  ctx->tan.ready = true;
+  return HF_OK;
+}
+
+int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const double* h_all, double rtol, double atol, int32_t max_it,
+                   int32_t ns, const int32_t* nodes, double* samples, int32_t* iters, double* tangent_samples, int32_t* tangent_iters) {
+  if (!ctx) return HF_ERR_ARG;
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a batch is open");
+  if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a load is set (tangents of pre-heated runs are not supported)");
+  if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_run_tangent before hf_tangent_setup");
+  if (ctx->tan.steady_state)
+    return fail(ctx, HF_ERR_STATE, "hf_run_tangent: the state comes from hf_steady_solve and depends on the conductivities (tangents start at zero): hf_set_state first");
+  if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_run_tangent before hf_assemble");
+  if (ctx->mode != HF_ASM_ROW_GATHER) return fail(ctx, HF_ERR_ARG, "hf_run_tangent: the operator was not assembled by the row-gather kernel");
+  if (n_steps <= 0 || (ctx->nbc > 0 && !g_all) || max_it <= 0 || rtol < 0 || atol < 0) return fail(ctx, HF_ERR_ARG, "hf_run_tangent: bad arguments");
+  if (ns < 0 || (ns > 0 && (!nodes || !samples || !tangent_samples))) return fail(ctx, HF_ERR_ARG, "hf_run_tangent: bad sample arguments");
+  for (int32_t q = 0; q < ns; ++q)
+    if (nodes[q] < 0 || nodes[q] >= ctx->n) return fail(ctx, HF_ERR_ARG, "hf_run_tangent: node %d outside [0,%d)", nodes[q], ctx->n);
+  HF_HIP(hipSetDevice(ctx->dev));
+  hf_ctx::Batch& T = ctx->tanb;
+  const int nv = T.nv;
+  const size_t hstep = static_cast<size_t>(ctx->nbc) * nv;
+  DevTemp<double> t_gall, t_hall, t_sall, t_tall;
+  if (ctx->nbc > 0) {
+    HF_TRY(dev_alloc(ctx, &t_gall.p, static_cast<size_t>(n_steps) * ctx->nbc));
+    HF_HIP(copy_sync(ctx, t_gall.p, g_all, sizeof(double) * n_steps * ctx->nbc, hipMemcpyHostToDevice));
+    HF_TRY(dev_alloc(ctx, &t_hall.p, h_all ? hstep * n_steps : hstep));
+    if (h_all) HF_HIP(copy_sync(ctx, t_hall.p, h_all, sizeof(double) * hstep * n_steps, hipMemcpyHostToDevice));
+    else HF_HIP(hipMemsetAsync(t_hall.p, 0, sizeof(double) * hstep, ctx->stream));   // every step's h = 0
+  }
+  if (ns > 0) {
+    HF_TRY(ensure_samples(ctx, ns));
+    HF_TRY(dev_alloc(ctx, &t_sall.p, static_cast<size_t>(n_steps) * ns));
+    HF_TRY(dev_alloc(ctx, &t_tall.p, static_cast<size_t>(n_steps) * nv * ns));
+    HF_HIP(copy_sync(ctx, ctx->d_samp_idx, nodes, sizeof(int32_t) * ns, hipMemcpyHostToDevice));
+  }
+  HF_TRY(ensure_batch_cols(ctx, nv));     // (a sweep since the last run may have laid the tables out for another width)
+  T.lds = ctx->bcols.nv == nv;
+  HF_TRY(tangent_levels(ctx));
+  int rc = HF_OK;
+  HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  for (int32_t s = 0; s < n_steps && rc == HF_OK; ++s) {
+    // the primal step, exactly hf_run's
+    rc = step_device(ctx, ctx->nbc > 0 ? g_all + static_cast<size_t>(s) * ctx->nbc : nullptr,
+                     ctx->nbc > 0 ? t_gall.p + static_cast<size_t>(s) * ctx->nbc : nullptr, rtol, atol, max_it);
+    if (iters) iters[s] = ctx->h_scal->iters;
+    if (rc != HF_OK) break;
+    if (ns > 0)
+      hipLaunchKernelGGL(k_gather, dim3((ns + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, ctx->d_u,
+                         t_sall.p + static_cast<size_t>(s) * ns);
+    // the tangent stage: F = -K_j u^{n+1}, then one batched step of the columns with that load and boundary values h^{n+1}
+    HF_TRY(tangent_load(ctx));
+    const double* hs = ctx->nbc == 0 ? nullptr : t_hall.p + (h_all ? hstep * s : 0);
+    std::swap(ctx->batch, ctx->tanb);
+    rc = batch_dispatch(ctx, [&](auto ops) { return decltype(ops)::step(ctx, hs, rtol, atol, max_it); });
+    std::swap(ctx->batch, ctx->tanb);
+    if (tangent_iters)
+      for (int j = 0; j < nv; ++j) tangent_iters[static_cast<size_t>(s) * nv + j] = T.h_scal[j].iters;
+    if (ns > 0 && rc == HF_OK) {
+      double* out = t_tall.p + static_cast<size_t>(s) * nv * ns;
+      const int thr = ns * nv;
+      switch (nv) {
+        case 2: hipLaunchKernelGGL((kb_gather<2>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, T.u, out); break;
+        case 4: hipLaunchKernelGGL((kb_gather<4>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, T.u, out); break;
+        case 8: hipLaunchKernelGGL((kb_gather<8>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, T.u, out); break;
+        default: hipLaunchKernelGGL((kb_gather<16>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, T.u, out); break;
+      }
+    }
+  }
+  (void)hipEventRecord(ctx->ev1, ctx->stream);
+  (void)hipStreamSynchronize(ctx->stream);
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1);
+  ctx->last_ms = ms;
+  if (ns > 0 && rc == HF_OK) {
+    (void)copy_sync(ctx, samples, t_sall.p, sizeof(double) * n_steps * ns, hipMemcpyDeviceToHost);
+    (void)copy_sync(ctx, tangent_samples, t_tall.p, sizeof(double) * n_steps * nv * ns, hipMemcpyDeviceToHost);
+  }
+  return rc;
+}
+
+int hf_get_tangent(hf_ctx* ctx, int32_t j, double* s) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_get_tangent before hf_tangent_setup");
+  if (j < 0 || j >= ctx->tan.nv || !s) return fail(ctx, HF_ERR_ARG, "hf_get_tangent: column %d outside [0,%d) or null pointer", j, ctx->tan.nv);
+  HF_HIP(hipSetDevice(ctx->dev));
+  hipLaunchKernelGGL(kb_get_column, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->n), ctx->tan.nv, j, ctx->tanb.u, ctx->d_tmp);
+  HF_HIP(hipGetLastError());
+  HF_HIP(copy_sync(ctx, s, ctx->d_tmp, sizeof(double) * ctx->n, hipMemcpyDeviceToHost));
+  return HF_OK;
 }
 
 int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t precond) {
@@ -1101,6 +1347,8 @@ int hf_steady_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, double rto
   ctx->have_prev = false;
   ctx->g_hist = 0;
   proj_clear(ctx, true);
+  if (rc != HF_ERR_HIP) HF_TRY(tangent_reset(ctx));
+  ctx->tan.steady_state = true;     // hf_run_tangent refuses this state (its derivative is not zero) until hf_set_state
   if (iters) *iters = ctx->h_scal->iters;
   if (resid) *resid = std::sqrt(ctx->h_scal->zz / std::max(ctx->h_scal->bn2, 1e-300));
   return rc;
@@ -1162,7 +1410,7 @@ int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
   HF_HIP(hipSetDevice(ctx->dev));
   free_batch(ctx);
   hf_ctx::Batch& B = ctx->batch;
-  const size_t n = static_cast<size_t>(ctx->n), vec = n * nv;
+  const size_t vec = static_cast<size_t>(ctx->n) * nv;
   B.opk = operator_kind;
   for (double& d : B.delta) d = 0.0;
   if (B.opk == HF_BATCH_PER_COLUMN) {
@@ -1174,61 +1422,8 @@ int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
     HF_TRY(dev_alloc(ctx, &B.lift1, static_cast<size_t>(std::max(ctx->nlift, 1))));
   }
   if (B.opk != HF_BATCH_SHARED) HF_TRY(dev_alloc(ctx, &B.dinv, vec));
-  for (double** v : {&B.u, &B.uprev, &B.ustart, &B.b, &B.r, &B.p, &B.Ap, &B.z, &B.z2, &B.tmp}) {
-    HF_TRY(dev_alloc(ctx, v, vec));
-    HF_HIP(hipMemsetAsync(*v, 0, sizeof(double) * vec, ctx->stream));
-  }
-  HF_TRY(dev_alloc(ctx, &B.part_pAp, static_cast<size_t>(nv) * MAXP));
-  HF_TRY(dev_alloc(ctx, &B.part_rz, 2 * static_cast<size_t>(nv) * MAXP));
-  HF_TRY(dev_alloc(ctx, &B.part_zz, static_cast<size_t>(nv) * MAXP));
-  HF_TRY(dev_alloc(ctx, &B.part_bn, static_cast<size_t>(nv) * MAXP));
-  HF_TRY(dev_alloc(ctx, &B.scal, nv));
-  HF_HIP(hipMemsetAsync(B.scal, 0, sizeof(Scal) * nv, ctx->stream));
-  HF_TRY(dev_alloc(ctx, &B.red, 1));
-  HF_HIP(hipMemsetAsync(B.red, 0, sizeof(BRed), ctx->stream));
-  for (int k = 0; k < PROJ_MH; ++k) {
-    HF_TRY(dev_alloc(ctx, &B.pV[k], vec));
-    HF_TRY(dev_alloc(ctx, &B.pF[k], vec));
-    B.pused[k] = false;
-  }
-  HF_TRY(dev_alloc(ctx, &B.pG, static_cast<size_t>(nv) * PROJ_MT * PROJ_MT));
-  HF_TRY(dev_alloc(ctx, &B.palpha, static_cast<size_t>(nv) * (PROJ_MT + 1)));
-  HF_TRY(dev_alloc(ctx, &B.ppart, static_cast<size_t>(nv) * 2 * PROJ_MT * MAXP));
-  HF_HIP(hipMemsetAsync(B.pG, 0, sizeof(double) * nv * PROJ_MT * PROJ_MT, ctx->stream));
-  B.pnext = 0; B.ppending = -1;
-  if (hipHostMalloc(reinterpret_cast<void**>(&B.h_scal), sizeof(Scal) * nv) != hipSuccess) return fail(ctx, HF_ERR_ALLOC, "hipHostMalloc failed");
-  if (hipHostMalloc(reinterpret_cast<void**>(&B.h_mirror), sizeof(ScalMirror) * nv, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-      hipHostGetDevicePointer(reinterpret_cast<void**>(&B.d_mirror), B.h_mirror, 0) != hipSuccess)
-    return fail(ctx, HF_ERR_ALLOC, "hipHostMalloc (mapped) failed");
-  for (int j = 0; j < nv; ++j) B.h_mirror[j] = ScalMirror{};
-  B.epoch = 0;
-  const int rpb = TPB / nv;
-  B.Pb = static_cast<int>(std::min<size_t>((n + rpb - 1) / rpb, MAXP));
-  if (B.Pb >= 64) B.Pb &= ~7;
-  if (ctx->precond == 1 && ctx->amg_ready) {   // level vectors, laid out as build_amg lays out the single-column ones
-    const size_t nl = ctx->amg.size();
-    B.lev.resize(nl);
-    for (size_t l = 1; l < nl; ++l) {
-      const DevLevel& L = ctx->amg[l];
-      hf_ctx::BatchLevel& Q = B.lev[l];
-      if (l + 1 < nl) {
-        const size_t len = (static_cast<size_t>(L.n) + L.P.ncol + 2) * nv;
-        HF_TRY(dev_alloc(ctx, &Q.cat, len));
-        HF_HIP(hipMemsetAsync(Q.cat, 0, sizeof(double) * len, ctx->stream));
-        Q.b = Q.cat;
-      } else {
-        HF_TRY(dev_alloc(ctx, &Q.b, (static_cast<size_t>(L.n) + 2) * nv));
-        Q.own_b = true;
-        HF_HIP(hipMemsetAsync(Q.b, 0, sizeof(double) * (static_cast<size_t>(L.n) + 2) * nv, ctx->stream));
-      }
-      if (l == 1) {
-        HF_TRY(dev_alloc(ctx, &Q.x, (static_cast<size_t>(L.n) + 2) * nv));
-        Q.res = Q.x;
-      } else {
-        Q.res = B.lev[l - 1].cat + static_cast<size_t>(ctx->amg[l - 1].n) * nv;
-      }
-    }
-  }
+  HF_TRY(batch_alloc(ctx, B, nv));
+  HF_TRY(batch_levels(ctx, B, nv));
   HF_HIP(hipStreamSynchronize(ctx->stream));
   HF_TRY(ensure_batch_cols(ctx, nv));
   B.lds = ctx->bcols.nv == nv;

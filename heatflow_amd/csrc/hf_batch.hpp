@@ -105,7 +105,8 @@ __device__ __forceinline__ double op_value(const BOp& op, size_t k, int j) {
   return op.v0[k];
 }
 
-// Fine-pattern SpMV on NV interleaved columns, thread = (row, column).  Modes as k_spmv (0, 2, 3, 4, 5, 8, 9).
+// Fine-pattern SpMV on NV interleaved columns, thread = (row, column).  Modes as k_spmv (0, 2, 3, 4, 5, 8, 9, 10); mode 10
+// (the right-hand side with a per-column load, b = M u + dt F) takes the interleaved load F in `bvec` and dt in `w`.
 #ifndef HF_KB_U
 #define HF_KB_U 4
 #endif
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(KB_BT) void kb_spmv(int n, const int32_t* __restric
     const int k0 = rowptr[row], k1 = rowptr[row + 1];
     const size_t o = static_cast<size_t>(row) * NV + j;
     double e_b = 0.0, e_d = 0.0, e_y = 0.0, e_p = 0.0, e_x = 0.0;
-    if (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 8) e_b = bvec[o];
+    if (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 8 || MODE == 10) e_b = bvec[o];
     if (MODE == 2 || MODE == 4 || MODE == 5) e_d = OPK != OP_SHARED ? dinv[o] : dinv[row];
     if (MODE == 9 && !first9) { e_y = y[o]; e_p = pvec[o]; }
     if (MODE == 4 || MODE == 8 || MODE == 9) e_x = x[o];
@@ -189,6 +190,8 @@ __global__ __launch_bounds__(KB_BT) void kb_spmv(int n, const int32_t* __restric
     } else if (MODE == 8) {
       y[o] = s;
       pvec[o] = 2.0 * e_x - e_b;
+    } else if (MODE == 10) {
+      y[o] = s + w * e_b;
     } else {
       const double api = first9 ? s : s + beta * e_y;
       const double pi = first9 ? e_x : e_x + beta * e_p;
@@ -319,7 +322,7 @@ __global__ __launch_bounds__(KB_BT) void kb_spmv_lds(int n, const int32_t* __res
       const int pa = rowptr[row] - k0, pb = rowptr[row + 1] - k0;
       const size_t o = static_cast<size_t>(row) * NV + j;
       double e_b = 0.0, e_d = 0.0, e_y = 0.0, e_p = 0.0, e_x = 0.0;
-      if (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 8) e_b = bvec[o];
+      if (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 8 || MODE == 10) e_b = bvec[o];
       if (MODE == 2 || MODE == 4 || MODE == 5) e_d = OPK != OP_SHARED ? dinv[o] : dinv[row];
       if (MODE == 9 && !first9) { e_y = y[o]; e_p = pvec[o]; }
       if (MODE == 4 || MODE == 8 || MODE == 9) e_x = sx[static_cast<size_t>(own + (row - r0)) * NV + j];
@@ -352,6 +355,8 @@ __global__ __launch_bounds__(KB_BT) void kb_spmv_lds(int n, const int32_t* __res
       } else if (MODE == 8) {
         y[o] = s;
         pvec[o] = 2.0 * e_x - e_b;
+      } else if (MODE == 10) {
+        y[o] = s + w * e_b;
       } else {
         const double api = first9 ? s : s + beta * e_y;
         const double pi = first9 ? e_x : e_x + beta * e_p;
@@ -1189,13 +1194,15 @@ struct BatchOps {
     return a;
   }
 
-  // one time step of all columns to the boundary values g_dev (n_bc x NV, interleaved, on the device).  Start vector:
+  // one time step of all columns to the boundary values g_dev (n_bc x NV, interleaved, on the device), with the per-column
+  // load B.load (interleaved; the tangent stage of hf_run_tangent) when one is set.  Start vector:
   // per column the A-norm projection of the new solution on the span of its last solutions (kind 3 of the
   // single-column loop, without the boundary responses)
   static int step(hf_ctx* ctx, const double* g_dev, double rtol, double atol, int max_it) {
     hf_ctx::Batch& B = ctx->batch;
     const int nb = ctx->nbc;
-    spmv<0>(ctx, ctx->d_M, B.u, B.b);
+    if (B.load != nullptr) spmv<10>(ctx, ctx->d_M, B.u, B.b, nullptr, B.load, nullptr, nullptr, nullptr, ctx->dt);   // b = M u + dt F
+    else spmv<0>(ctx, ctx->d_M, B.u, B.b);
     if (nb > 0) {
       if (ctx->nlift_rows > 0) {
         const int thr = ctx->nlift_rows * NV;

@@ -277,6 +277,7 @@ struct hf_ctx {
     int pnext = 0, ppending = -1;
     unsigned loaded = 0;         // bit j: column j's operator has been loaded (percol)
     bool lds = false;            // fine-pattern products through kb_spmv_lds (the context's `bcols` tables are for this nv)
+    const double* load = nullptr;   // per-column load F (interleaved): b = M u + dt F (the tangent stage); null: b = M u
   } batch;
   // compressed columns of the batched loop's LDS-staged SpMV (BComp in hf_batch.hpp): per chunk of `rpc` rows a sorted
   // column list and per nonzero a 16-bit position in it; built on the first hf_batch_begin with a given nv, kept per mesh
@@ -288,6 +289,17 @@ struct hf_ctx {
   Batch fluxb;                   // two-column state of the read-flux projection (both components in one PCG), swapped into `batch` while it runs
   Batch fluxnb;                  // nv-column state of the batched loop's read-flux projection (hf_batch_run_flux): one gradient component of every column per PCG
   int32_t* d_fsamp_idx = nullptr;   // its sample nodes
+  // tangent runs (hf_tangent_setup / hf_run_tangent): nv tangent columns s_j = du/dtheta_j in their own batch state, swapped
+  // into `batch` for the tangent stage of every step; their load F_j = -K_j u^{n+1} (k_tangent_load)
+  Batch tanb;
+  struct Tangent {
+    bool ready = false;
+    int npar = 0, nv = 0;
+    int32_t* col = nullptr;      // tangent column of each row-gather tag-dictionary entry (64), -1 = none
+    double* F = nullptr;         // n x nv, interleaved
+    bool steady_state = false;   // the state comes from hf_steady_solve (it depends on kappa; s^0 = 0 would be wrong) until hf_set_state
+    std::vector<int64_t> lev_sig;   // multigrid level sizes tanb.lev was laid out for
+  } tan;
   int fsamp_cap = 0;
   // optional in-situ kernel timing (hf_set_profile): event pairs around each PCG SpMV launch
   bool prof = false;

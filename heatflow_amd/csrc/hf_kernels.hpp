@@ -423,6 +423,67 @@ __global__ __launch_bounds__(RBA) void k_grad_rows(int nblk, int capd, const int
   }
 }
 
+// Per-parameter stiffness products of a tangent run (hf_run_tangent) by row gather (same lists and staging as k_grad_rows):
+// F[i * NV + j] = -sum over the triangles e at node i whose tag maps to column j (col[tag-dictionary index] = j) of
+// (K_e u)_i, K_e the r-weighted element stiffness at unit conductivity (element_row, as k_assemble_rows<true> forms it).
+// One pass over the triangles serves all NV columns: u is read once, K_j is never formed.  Each column's sum runs in list
+// order in a register of the row's lane - bitwise reproducible; columns no tag maps to are written as zeros.
+template <int NV>
+__global__ __launch_bounds__(RBA) void k_tangent_load(int nblk, int capd, const int4* __restrict__ hdr, const uint4* __restrict__ ell,
+                                                      const uint4* __restrict__ cid16, const double2* __restrict__ zrb,
+                                                      const int32_t* __restrict__ dict, const int32_t* __restrict__ rowptr,
+                                                      const int32_t* __restrict__ col, const double* __restrict__ u,
+                                                      double* __restrict__ F) {
+  extern __shared__ double smem[];
+  __shared__ int scol[64];
+  double2* sXd = reinterpret_cast<double2*>(smem);
+  double* sU = smem + 2 * capd;
+  int* sR = reinterpret_cast<int*>(sU + capd + (capd & 1));
+  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);
+  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
+  const int t = threadIdx.x;
+  if (t < 64) scol[t] = col[t];
+  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const int4 cA = hdr[2 * blk], cB = hdr[2 * blk + 1];
+    const int c0 = cA.x >> 3, nc = ((cA.x + cA.y + 7) >> 3) - c0;
+    for (int i = t; i < nc; i += RBA) sC4[i] = cid16[c0 + i];
+    for (int i = t; i < cA.w; i += RBA) { sXd[i] = zrb[cA.z + i]; sU[i] = u[dict[cA.z + i]]; }
+    if (t < cB.w) sR[t] = rowptr[blk * RBA + t] - cA.x;
+    __syncthreads();
+    if (t < cB.w) {
+#pragma clang fp contract(off)
+      const int sbase = sR[t] + (cA.x & 7);
+      const int ci = cB.z + t;
+      const double2 Pi = sXd[ci];
+      const double ui = sU[ci];
+      double acc[NV];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+      for (int g = 0; g < cB.y; ++g) {
+        const uint4 ev = ell[cB.x + g * RBA + t];
+        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
+          if (e == 0xFFFFu) continue;
+          const int cj = scol[e >> 10];
+          if (cj < 0) continue;
+          const int pj = sC[sbase + (e & 31u)], pk = sC[sbase + ((e >> 5) & 31u)];
+          const ElemRow r = element_row(Pi, sXd[pj], sXd[pk], 0.0, 1.0);
+          const double ku = (r.k0 * ui + r.k1 * sU[pj]) + r.k2 * sU[pk];
+#pragma unroll
+          for (int j = 0; j < NV; ++j)
+            if (j == cj) acc[j] += ku;
+        }
+      }
+      double* out = F + static_cast<size_t>(blk * RBA + t) * NV;
+#pragma unroll
+      for (int j = 0; j < NV; ++j) out[j] = -acc[j];
+    }
+    __syncthreads();
+  }
+}
+
 // per-block copy of the coordinates of each block's column list (hf_set_mesh, once)
 __global__ void k_gather_coords(int64_t total, const int32_t* __restrict__ dict, const double2* __restrict__ zr,
                                 double2* __restrict__ zrb) {

@@ -237,12 +237,14 @@ class SimulationSession:
             located("top", ic_temp),      # named bottom_bc in the reference, location 'top'
             located("x", heat.gaussian, coord=float(stack.heated_z), length=abs(stack.r_sample) * 2, center=0.0),
         ]
+        self._heats = [heat]            # the heated lines' curves, by position after the three edges (fwhm tangents)
         if two_sided:
             # EXTENSION without a reference implementation (BASELINE config 4 "konopkova two-sided",
             # SURVEY 8d C4): a second Gaussian Dirichlet line on the outer face of the o-side coupler,
             # driven by the CSV's `oside` column with the same offset-to-ic_temp convention.
             heat_o = HeatingCurve(_resolve(cfg["heating"]["file"]), ic_temp, float(cfg["heating"]["fwhm"]), column="oside")
             bcs.append(located("x", heat_o.gaussian, coord=float(stack.heated_z_oside), length=abs(stack.r_sample) * 2, center=0.0))
+            self._heats.append(heat_o)
         return bcs
 
     def _problem_key(self, dt, tag_to_rc, bcs):
@@ -392,10 +394,13 @@ class SimulationSession:
                  "iters": iters[:, j].copy(), "loop_time": loop_time / nv, "startup_time": (t_loop - t_start) / nv,
                  "n_dof": prob.n, "dt": dt, "flux": fluxes[j], "batch": nv} for j in range(nv)]
 
-    def run(self, cfg, stack, watcher_points=None, field_sink=None, read_flux=False, two_sided=False):
+    def run(self, cfg, stack, watcher_points=None, field_sink=None, read_flux=False, two_sided=False, tangents=None):
         """One simulation (reference loop run_with_diamond.py:456-504).  Returns a dict with
         ``times``, ``watchers`` {name: array}, ``iters``, timing numbers.  ``read_flux`` adds the
-        per-step gradient projection of run_no_diamond.py:543-566 (``flux`` entry of the result)."""
+        per-step gradient projection of run_no_diamond.py:543-566 (``flux`` entry of the result).
+        ``tangents`` = parameter names (material names - the derivative with respect to that material's conductivity
+        k - and / or "fwhm" of the heating profile) adds ``tangents`` {param: {watcher: d watcher / d param}} and
+        ``tangent_iters`` (HeatProblem.run_tangent; not with a field sink or the flux projection)."""
         t_start = time.time()
         t_final = float(cfg["timing"]["t_final"])
         num_steps = int(cfg["timing"]["num_steps"])
@@ -420,7 +425,24 @@ class SimulationSession:
             prob._flux_ready = True
         print("Beginning loop...")
         t_loop = time.time()
-        if field_sink is None and flux is None:
+        tangent_out = None
+        if tangents:
+            if field_sink is not None or flux is not None:
+                raise ValueError("tangents: not combined with a field sink or the read-flux projection")
+            params = list(tangents)
+            cond, bnd = [], {}
+            for j, p in enumerate(params):
+                if p == "fwhm":
+                    cond.append([])
+                    bnd[j] = {3 + q: h.gaussian_dfwhm for q, h in enumerate(self._heats)}
+                elif p in self.material_tags:
+                    cond.append([self.material_tags[p]])
+                else:
+                    raise ValueError(f"tangents: unknown parameter {p!r} (a material name or 'fwhm')")
+            times, samples, tsamp, iters, titers = prob.run_tangent(num_steps, nodes, conductivity=cond, boundary=bnd,
+                                                                    time_varying=varying)
+            tangent_out = {p: {nm: tsamp[:, j, k] for k, nm in enumerate(names)} for j, p in enumerate(params)}
+        elif field_sink is None and flux is None:
             times, samples, iters = prob.run(num_steps, watcher_nodes=nodes, time_varying=varying)
         else:  # step-wise: every field goes to the sink (visualisation) and / or through the flux projection
             for bc in bcs:
@@ -449,6 +471,7 @@ class SimulationSession:
             "watchers": {nm: samples[:, k] for k, nm in enumerate(names)},
             "iters": np.asarray(iters), "loop_time": loop_time, "startup_time": t_loop - t_start,
             "n_dof": prob.n, "dt": dt, "flux": flux,
+            **({"tangents": tangent_out, "tangent_iters": titers} if tangent_out is not None else {}),
         }
 
 
@@ -573,7 +596,7 @@ class _FieldWriter:
 def run_simulation_impl(kind, cfg, mesh_folder, rebuild_mesh=False, visualize_mesh=False, output_folder=None,
                         watcher_points=None, write_xdmf=True, suppress_print=False, *, device_id=0, backend=None,
                         session=None, rtol=DEFAULT_RTOL, max_it=DEFAULT_MAX_IT, read_flux=True, precond=None,
-                        two_sided=False):
+                        two_sided=False, tangents=None):
     with suppress_output(suppress_print):
         program_start = time.time()
         stack = stack_with_diamond(cfg) if kind == "with_diamond" else stack_no_diamond(cfg)
@@ -600,7 +623,7 @@ def run_simulation_impl(kind, cfg, mesh_folder, rebuild_mesh=False, visualize_me
             if sink is not None:
                 sink(0.0, np.full(len(session.coords), float(cfg["heating"]["ic_temp"])))
             result = session.run(cfg, stack, watcher_points, field_sink=sink, read_flux=read_flux and kind == "no_diamond",
-                                 two_sided=two_sided)
+                                 two_sided=two_sided, tangents=tangents)
         finally:
             if sink is not None:
                 sink.close()

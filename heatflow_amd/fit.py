@@ -1,0 +1,185 @@
+"""Least-squares fit of material parameters to a measured o-side curve, on tangent runs.
+
+The objective is the kappa sweep's (parameter_sweep.oside_rmse, sweep_test.py:76-93): the simulated o-side rise
+(o - o[0]) / (p.max - p.min), interpolated onto the experimental times, against the experiment's normalised o-side curve.
+Instead of a grid, Levenberg-Marquardt steps in log(theta) (theta stays positive) on the residuals r_i, with the Jacobian
+from one tangent run per accepted iterate (HeatProblem.run_tangent): the derivative of the normalised curve is chain-ruled through
+the normalisation with the p-side's argmax and argmin held fixed.  A trial step costs one primal run; the tangents run
+only at accepted iterates.  Standard errors come from s^2 (J^T J)^-1, s^2 = sum r^2 / (m - p).
+
+    python -m heatflow_amd.fit --config cfgs/geballe_with_diamond.yaml --params p_sample [fwhm] --output-dir DIR
+"""
+from __future__ import annotations
+
+import argparse
+import copy
+import json
+import os
+import time
+
+import numpy as np
+
+from .parameter_sweep import build_stack, get_watcher_points, oside_curves
+
+DEFAULT_EXP_CSV = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "experimental_data",
+                               "geballe_heat_data.csv")
+
+
+def get_param(cfg, name):
+    return float(cfg["heating"]["fwhm"]) if name == "fwhm" else float(cfg["mats"][name]["k"])
+
+
+def set_params(cfg, params, values):
+    """A copy of ``cfg`` with the parameters set: "fwhm" of the heating profile, else the conductivity k of a material."""
+    c = copy.deepcopy(cfg)
+    for name, v in zip(params, values):
+        if name == "fwhm":
+            c["heating"]["fwhm"] = float(v)
+        else:
+            c["mats"][name]["k"] = float(v)
+    return c
+
+
+def load_experiment(exp_csv):
+    """The experiment's columns (time, temp, oside): a CSV path, or a structured array / dict already loaded."""
+    if isinstance(exp_csv, (str, os.PathLike)):
+        return np.genfromtxt(exp_csv, delimiter=",", names=True)
+    return exp_csv
+
+
+def residual_and_jacobian(res, params, exp, ic_temp):
+    """Residuals r = exp curve - sim curve on the experimental times and dr/dtheta (m x p) of one tangent run's result
+    (Session.run(..., tangents=params)).  The normalisation's argmax / argmin of the p-side curve are held fixed."""
+    ps, os_ = res["watchers"]["pside"], res["watchers"]["oside"]
+    t_exp, y_exp, t_sim, y_sim = oside_curves(exp, ic_temp, res["times"], ps, os_)
+    r = y_exp - np.interp(t_exp, t_sim, y_sim)
+    imax, imin = int(np.argmax(ps)), int(np.argmin(ps))
+    span = ps[imax] - ps[imin]
+    J = np.empty((len(r), len(params)))
+    for j, p in enumerate(params):
+        dp, do = res["tangents"][p]["pside"], res["tangents"][p]["oside"]
+        dy = (do - do[0]) / span - (os_ - os_[0]) * (dp[imax] - dp[imin]) / span ** 2
+        J[:, j] = -np.interp(t_exp, t_sim, dy)        # interpolation is linear in the values
+    return r, J
+
+
+def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_CSV, x0=None, max_iter=20, *, xtol=1e-9,
+                   ftol=1e-10, session=None, backend=None, device_id=0, rtol=1e-10, mesh=None, rebuild_mesh=None,
+                   verbose=False):
+    """Levenberg-Marquardt fit of ``params`` (material names and / or "fwhm") to the experiment's o-side curve.
+    ``x0`` = start values (default: the configuration's).  ``session`` / ``backend`` / ``mesh`` = (coords, tris, tags,
+    tag_map) reuse what the caller has; otherwise the mesh is loaded from ``mesh_folder``, or built there (``rebuild_mesh``
+    True, or None and the folder holds no mesh).  A trial step costs one primal run; only an accepted step is followed by a
+    tangent run for the next Jacobian.  Returns {params, values, rmse, converged, iterations, history, stderr, runs,
+    tangent_runs, seconds}."""
+    from .driver import SimulationSession, prepare_mesh
+
+    t0 = time.time()
+    params = tuple(params)
+    exp = load_experiment(exp_csv)
+    ic = float(cfg["heating"]["ic_temp"])
+    stack = build_stack(cfg)
+    own = session is None
+    if own:
+        if mesh is None:
+            if rebuild_mesh is None:
+                rebuild_mesh = not all(os.path.isfile(os.path.join(mesh_folder, f)) for f in ("mesh.msh", "mesh_cfg.yaml"))
+            mesh = prepare_mesh(cfg, mesh_folder, rebuild_mesh, stack)
+        coords, tris, tags, tag_map = mesh
+        session = SimulationSession(coords, tris, tags, tag_map, device_id=device_id, backend=backend, rtol=rtol)
+    watchers = get_watcher_points(cfg)
+    runs = tangent_runs = 0
+
+    def run(theta, tangents):
+        nonlocal runs, tangent_runs
+        c = set_params(cfg, params, theta)
+        res = session.run(c, build_stack(c), watchers, tangents=params if tangents else None)
+        runs += 1
+        tangent_runs += bool(tangents)
+        return res
+
+    def resid_only(res):
+        t_exp, y_exp, t_sim, y_sim = oside_curves(exp, ic, res["times"], res["watchers"]["pside"], res["watchers"]["oside"])
+        return y_exp - np.interp(t_exp, t_sim, y_sim)
+
+    try:
+        theta = np.array([get_param(cfg, p) for p in params] if x0 is None else x0, dtype=np.float64)
+        res = run(theta, True)
+        r, J = residual_and_jacobian(res, params, exp, ic)
+        cost = float(r @ r)
+        lam = 1e-6
+        history = [{"values": theta.tolist(), "rmse": float(np.sqrt(cost / len(r))), "lambda": lam}]
+        it = 0
+        converged = False
+        while it < max_iter and not converged:
+            it += 1
+            Jl = J * theta                                   # d r / d log(theta)
+            A, g = Jl.T @ Jl, Jl.T @ r
+            while True:
+                step = np.linalg.solve(A + lam * np.diag(np.diag(A)), -g)
+                pred = -(2.0 * g @ step + step @ A @ step)   # decrease of r.r the linearised model predicts
+                if np.max(np.abs(step)) < xtol or pred <= ftol * cost:
+                    converged = True                         # at the minimum to the model's resolution: no trial run
+                    break
+                trial = theta * np.exp(step)
+                r_t = resid_only(run(trial, False))          # trial: the primal alone
+                cost_t = float(r_t @ r_t)
+                if cost_t <= cost:
+                    theta, cost = trial, cost_t
+                    lam = max(lam / 3.0, 1e-12)
+                    res = run(theta, True)                   # accepted: the Jacobian there
+                    r, J = residual_and_jacobian(res, params, exp, ic)
+                    break
+                lam *= 4.0
+                if lam > 1e12:                               # no decrease along any damped step: a stationary point
+                    converged = True
+                    break
+            history.append({"values": theta.tolist(), "rmse": float(np.sqrt(cost / len(r))), "lambda": lam})
+            if verbose:
+                print(f"fit iteration {it}: {dict(zip(params, theta))} rmse {np.sqrt(cost / len(r)):.6e}")
+        m, p = len(r), len(params)
+        s2 = cost / max(m - p, 1)
+        try:
+            stderr = np.sqrt(np.diag(s2 * np.linalg.inv(J.T @ J)))
+        except np.linalg.LinAlgError:
+            stderr = np.full(p, np.nan)
+    finally:
+        if own:
+            session.close()
+    return {"params": list(params), "values": theta.tolist(), "rmse": float(np.sqrt(cost / len(r))), "converged": bool(converged),
+            "iterations": it, "history": history, "stderr": stderr.tolist(), "runs": runs, "tangent_runs": tangent_runs,
+            "seconds": time.time() - t0, "tangent_iters_mean": float(np.mean(res["tangent_iters"])),
+            "pcg_iters_mean": float(np.mean(res["iters"]))}
+
+
+def main(argv=None, backend=None):
+    """The command line; ``backend`` (tests): a stand-in for the HIP backend."""
+    import yaml
+
+    ap = argparse.ArgumentParser(description="Fit conductivities (and fwhm) to the experimental o-side curve with tangent runs")
+    ap.add_argument("--config", required=True)
+    ap.add_argument("--params", nargs="+", default=["p_sample"], help="material names and / or fwhm")
+    ap.add_argument("--exp-csv", default=DEFAULT_EXP_CSV)
+    ap.add_argument("--mesh-folder", default=None,
+                    help="mesh.msh + mesh_cfg.yaml to use; built there when absent (default: <output-dir>/mesh)")
+    ap.add_argument("--rebuild-mesh", action="store_true", help="build the mesh even if the folder holds one")
+    ap.add_argument("--output-dir", required=True)
+    ap.add_argument("--x0", nargs="+", type=float, default=None)
+    ap.add_argument("--max-iter", type=int, default=20)
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    with open(a.config) as f:
+        cfg = yaml.safe_load(f)
+    os.makedirs(a.output_dir, exist_ok=True)
+    mesh_folder = a.mesh_folder or os.path.join(a.output_dir, "mesh")
+    out = fit_parameters(cfg, mesh_folder, a.params, a.exp_csv, a.x0, a.max_iter, device_id=a.device, backend=backend,
+                         rebuild_mesh=True if a.rebuild_mesh else None, verbose=True)
+    out["config"] = a.config
+    with open(os.path.join(a.output_dir, "fit_summary.json"), "w") as f:
+        json.dump(out, f, indent=2)
+    print(json.dumps({k: out[k] for k in ("params", "values", "stderr", "rmse", "converged", "iterations", "runs", "seconds")}))
+    return 0
+
+
+if __name__ == "__main__":
+    raise SystemExit(main())

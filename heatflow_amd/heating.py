@@ -55,3 +55,10 @@ class HeatingCurve:
         """Boundary value at (z=x, r=y): (amp - ic) exp(coeff r^2) + ic (:357-359)."""
         amp = self.amplitude(t)
         return (amp - self.ic_temp) * np.exp(self.coeff * (np.asarray(y) - 0.0) ** 2) + self.ic_temp
+
+    def gaussian_dfwhm(self, x, y, t):
+        """d gaussian / d fwhm at (z=x, r=y): the profile (amp - ic) exp(coeff r^2) times r^2 d coeff / d fwhm, with
+        coeff = -4 ln 2 / fwhm^2 (the boundary derivative of a fwhm tangent, HeatProblem.run_tangent)."""
+        amp = self.amplitude(t)
+        r2 = (np.asarray(y) - 0.0) ** 2
+        return (amp - self.ic_temp) * np.exp(self.coeff * r2) * r2 * (8.0 * np.log(2.0) / self.fwhm ** 3)

@@ -26,7 +26,8 @@ EXPORTS = [
     "hf_update_kappa", "hf_set_dirichlet", "hf_assemble", "hf_set_precond", "hf_set_start_vector", "hf_get_response_solves", "hf_get_amg_info", "hf_get_amg_fallbacks", "hf_set_state", "hf_get_state", "hf_sample", "hf_step", "hf_run",
     "hf_batch_begin", "hf_batch_load_column", "hf_batch_set_affine", "hf_batch_set_state", "hf_batch_get_state", "hf_batch_run", "hf_batch_run_flux", "hf_batch_end",
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
-    "hf_steady_setup", "hf_steady_solve", "hf_set_load", "hf_get_load", "hf_hold_load", "hf_get_sizes", "hf_get_csr", "hf_spmv", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
+    "hf_steady_setup", "hf_steady_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
+    "hf_tangent_setup", "hf_run_tangent", "hf_get_tangent", "hf_get_sizes", "hf_get_csr", "hf_spmv", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
 
 
@@ -123,6 +124,9 @@ def load_library():
         "hf_set_load": [vp, pd],
         "hf_get_load": [vp, pd],
         "hf_hold_load": [vp],
+        "hf_tangent_setup": [vp, i32, pi],
+        "hf_run_tangent": [vp, i32, pd, pd, dbl, dbl, i32, i32, pi, pd, pi, pd, pi],
+        "hf_get_tangent": [vp, i32, pd],
         "hf_get_sizes": [vp, pi, pi, C.POINTER(i64), pi],
         "hf_get_csr": [vp, pi, pi, pd, pd],
         "hf_spmv": [vp, i32, pd, pd],
@@ -219,6 +223,8 @@ class HeatflowHIP:
         zr, tri, tag = _f64(coords), _i32(tris), _i32(tags)
         if zr.ndim != 2 or zr.shape[1] != 2 or tri.ndim != 2 or tri.shape[1] != 3 or tag.shape != (tri.shape[0],):
             raise ValueError("set_mesh: coords (n,2), tris (n_e,3), tags (n_e,) expected")
+        self.tab_len = int(tag.max()) + 1 if tag.size else 0     # entries of the per-tag tables (hf_tangent_setup)
+        self.tangent_nv = 0
         if pattern is None:
             self._check(self._lib.hf_set_mesh(self._ctx, zr.shape[0], tri.shape[0], _pd(zr), _pi(tri), _pi(tag)))
         else:
@@ -357,6 +363,50 @@ class HeatflowHIP:
         self.last_run_iters = iters
         self._check(rc)
         return samples, iters
+
+    # -- tangent runs: derivatives of the time loop with respect to conductivities and boundary parameters ----------
+    def tangent_setup(self, n_par, tag_col):
+        """``n_par`` tangent columns (1..16; the library pads them to nv = 2, 4, 8 or 16); ``tag_col`` = {cell tag: column}
+        for the tags whose conductivity a column scales (other tags: none).  Every tangent starts at zero."""
+        tab = np.full(self.tab_len, -1, dtype=np.int32)
+        for t, j in dict(tag_col).items():
+            if not 0 <= int(t) < self.tab_len:
+                raise ValueError(f"tangent_setup: tag {t} is not a cell tag of the mesh")
+            tab[int(t)] = int(j)
+        self.tangent_nv = 0
+        self._check(self._lib.hf_tangent_setup(self._ctx, int(n_par), _pi(tab)))
+        self.tangent_nv = next(v for v in (2, 4, 8, 16) if v >= int(n_par))
+
+    def run_tangent(self, g_all, h_all=None, rtol=1e-10, atol=0.0, max_it=20000, nodes=None):
+        """hf_run plus the tangents.  g_all (n_steps, n_bc); h_all (n_steps, n_bc, nv) or None (all zero).  Returns the
+        primal samples (n_steps, n_s) and iterations (n_steps,), the tangent samples (n_steps, nv, n_s) and the tangent
+        iterations (n_steps, nv)."""
+        g = _f64(g_all)
+        if g.ndim != 2 or g.shape[1] != self.n_bc:
+            raise ValueError(f"run_tangent: g_all must be (n_steps, {self.n_bc})")
+        nsteps, nv = g.shape[0], self.tangent_nv or 2     # (no set-up: the library reports it)
+        h = None
+        if h_all is not None:
+            h = _f64(h_all)
+            if h.shape != (nsteps, self.n_bc, nv):
+                raise ValueError(f"run_tangent: h_all must be ({nsteps}, {self.n_bc}, {nv})")
+        idx = _i32(nodes) if nodes is not None and len(nodes) else None
+        ns = 0 if idx is None else len(idx)
+        samples = np.empty((nsteps, ns), dtype=np.float64)
+        tsamples = np.empty((nsteps, nv, ns), dtype=np.float64)
+        iters = np.zeros(nsteps, dtype=np.int32)
+        titers = np.zeros((nsteps, nv), dtype=np.int32)
+        rc = self._lib.hf_run_tangent(self._ctx, nsteps, _pd(g) if self.n_bc else None, _pd(h) if (h is not None and self.n_bc) else None,
+                                      rtol, atol, int(max_it), ns, _pi(idx), _pd(samples) if ns else None, _pi(iters),
+                                      _pd(tsamples) if ns else None, _pi(titers))
+        self.last_run_iters = iters
+        self._check(rc)
+        return samples, iters, tsamples, titers
+
+    def get_tangent(self, j):
+        s = np.empty(self.n, dtype=np.float64)
+        self._check(self._lib.hf_get_tangent(self._ctx, int(j), _pd(s)))
+        return s
 
     # -- batched time loop: nv sweep points as the columns of one multi-vector PCG ------------------
     def batch_begin(self, nv, per_column_operator=False):

@@ -467,6 +467,25 @@ def get_k_values(k0=3.8, half_width=0.5, step=0.02, count=None):
     return np.round(np.arange(k0 - half_width, k0 + half_width + step, step), 4)
 
 
+def oside_curves(exp, ic_temp, times, pside, oside):
+    """The curves the kappa sweep compares (sweep_test.py:76-93): the experimental o-side curve offset to ic_temp and
+    normalised by the experimental p-side span, and the simulated o-side rise (o - o[0]) / (p.max - p.min).
+    ``exp`` = the experiment's columns (time, temp, oside).  Returns (exp time, exp curve, sim times, sim curve)."""
+    ps, os_ = np.asarray(pside), np.asarray(oside)
+    sim_o = (os_ - os_[0]) / (ps.max() - ps.min())
+    exp_o = exp["oside"] - exp["oside"][0] + ic_temp
+    exp_o = (exp_o - exp_o[0]) / (exp["temp"].max() - exp["temp"].min())
+    return exp["time"], exp_o, times, sim_o
+
+
+def oside_rmse(exp, ic_temp, times, pside, oside):
+    """The objective of the kappa sweep: RMSE of the normalised o-side curve against the experiment, the simulation
+    interpolated onto the experimental times (analysis_utils.calculate_rmse).  fit.py minimises the same number."""
+    from .analysis_utils import calculate_rmse
+
+    return calculate_rmse(*oside_curves(exp, ic_temp, times, pside, oside))
+
+
 def run_kappa_sweep(cfg, mesh_folder, k_values, output_dir, *, rebuild_mesh=False, session_factory=None,
                     device_id=None, exp_csv=None, concurrent=1, warmup_steps=0, on_ready=None, on_done=None,
                     timing=None, pattern_builder=None, batch=1):
@@ -485,8 +504,6 @@ def run_kappa_sweep(cfg, mesh_folder, k_values, output_dir, *, rebuild_mesh=Fals
     first point before the point loop (mesh, pattern, matrices and multigrid levels are then resident);
     ``on_ready()`` / ``on_done()`` are called right before / after the point loop (barrier + clock);
     ``timing`` (dict) receives the wall times of the phases on this rank."""
-    from .analysis_utils import calculate_rmse
-
     rank, world = world_info()
     if device_id is None:
         device_id = local_device()
@@ -530,13 +547,7 @@ def run_kappa_sweep(cfg, mesh_folder, k_values, output_dir, *, rebuild_mesh=Fals
     digits = 2 if len({f"{k:.2f}" for k in k_values}) == len(list(k_values)) else 4
 
     def rmse_against_experiment(c, res):
-        ps, os_ = res["watchers"]["pside"], res["watchers"]["oside"]
-        span = ps.max() - ps.min()
-        sim_o = (os_ - os_[0]) / span
-        ic = float(c["heating"]["ic_temp"])
-        exp_o = exp["oside"] - exp["oside"][0] + ic
-        exp_o = (exp_o - exp_o[0]) / (exp["temp"].max() - exp["temp"].min())
-        return calculate_rmse(exp["time"], exp_o, res["times"], sim_o)
+        return oside_rmse(exp, float(c["heating"]["ic_temp"]), res["times"], res["watchers"]["pside"], res["watchers"]["oside"])
 
     def one_point(k, sess):
         c = copy.deepcopy(cfg)

@@ -132,12 +132,64 @@ class HeatProblem:
         self.iters.extend(int(i) for i in iters)
         return times, samples, iters
 
+    def run_tangent(self, num_steps, watcher_nodes, conductivity=(), boundary=None, time_varying=None, first_step=0):
+        """:meth:`run` plus the derivatives of the watcher curves with respect to parameters theta_j (hf_run_tangent,
+        DESIGN.md 3.7).  Column j of ``conductivity`` = the cell tags whose conductivity theta_j is (they move together);
+        ``boundary`` = {column: {bc index: dg/dtheta_j callable (x, y, t)}} for parameters that enter the Dirichlet values
+        (e.g. ``HeatingCurve.gaussian_dfwhm`` on the heated line).  A column may be both.  The derivatives are tabulated
+        exactly as :meth:`run` tabulates g.  The first call after a set-up starts every tangent at zero, later calls
+        continue them (as the state continues).  The tangents start at zero, i.e. the initial state is taken as independent
+        of the parameters: after :meth:`solve_steady` (whose answer depends on the conductivities) the backend refuses a
+        tangent run until :meth:`set_state`.  Returns (times, samples, tangent samples (n_steps, n_par, n_s), iters,
+        tangent iters (n_steps, n_par))."""
+        conductivity = [list(c) for c in conductivity]
+        boundary = {int(j): dict(m) for j, m in (boundary or {}).items()}
+        n_par = max([len(conductivity)] + [j + 1 for j in boundary])
+        if n_par == 0:
+            raise ValueError("run_tangent: no parameter (conductivity or boundary) given")
+        tag_col = {}
+        for j, tags in enumerate(conductivity):
+            for t in tags:
+                if int(t) in tag_col:
+                    raise ValueError(f"run_tangent: cell tag {t} is listed in two conductivity columns")
+                tag_col[int(t)] = j
+        spec = (n_par, tuple(sorted(tag_col.items())))
+        if getattr(self, "_tangent_spec", None) != spec:     # a new set of parameters: the tangents start from zero
+            self.backend.tangent_setup(n_par, tag_col)
+            self._tangent_spec = spec
+        nv = self.backend.tangent_nv
+        for bc in self.bcs:
+            bc.update(0.0)
+        times = (np.arange(first_step, first_step + num_steps) + 1) * self.dt
+        g_all = np.empty((num_steps, len(self.bc_dofs)), dtype=np.float64)
+        h_all = np.zeros((num_steps, len(self.bc_dofs), nv), dtype=np.float64) if boundary else None
+        for k, t in enumerate(times):
+            g_all[k] = self.bc_values(t, time_varying)
+            for j, per_bc in boundary.items():
+                for q, deriv in per_bc.items():
+                    bc = self.bcs[q]
+                    sel, src = self._plan[q]
+                    if sel.size == 0:
+                        continue
+                    te = t if (time_varying is None or any(bc is b for b in time_varying)) else 0.0
+                    h_all[k, sel, j] = _eval_on_dofs(deriv, bc.dof_coords, te)[src]
+        samples, iters, tsamples, titers = self.backend.run_tangent(g_all, h_all, self.rtol, self.atol, self.max_it,
+                                                                    watcher_nodes)
+        self.iters.extend(int(i) for i in iters)
+        return times, samples, tsamples[:, :n_par], iters, titers[:, :n_par]
+
+    def tangent(self, j):
+        """The current tangent field of column j (n values)."""
+        return self.backend.get_tangent(j)
+
 
     # -- steady state and pre-heated transients (with_ir_steady.ipynb cells 17-23) -------------
     def solve_steady(self, bcs=None, t=0.0, use_load=False):
         """Steady state K u = F with its own Dirichlet list ``bcs`` (default: the problem's), merged last-wins and
         evaluated at ``t``; K is the r-weighted stiffness of the transient operator (steady state), F the
-        load when ``use_load`` and one is set, else 0.  The answer becomes the state.  Returns (u, iters, resid)."""
+        load when ``use_load`` and one is set, else 0.  The answer becomes the state.  Returns (u, iters, resid).
+        :meth:`run_tangent` refuses the steady state (HF_ERR_STATE) until :meth:`set_state`: it depends on the
+        conductivities, and the tangents of a run start at zero."""
         bcs = self.bcs if bcs is None else list(bcs)
         if not bcs:
             raise ValueError("solve_steady: no Dirichlet condition (the stiffness alone is singular)")
@@ -158,6 +210,20 @@ class HeatProblem:
         Dirichlet rows, 0 on them; it becomes the load and is returned.  Needs a solve_steady before (for K)."""
         self.backend.hold_load()
         return self.backend.get_load()
+
+
+def _eval_on_dofs(fn, xy, t):
+    """fn(x, y, t) on a BC's DOF coordinates: on whole arrays, else point by point (as RowDirichletBC.update)."""
+    x, y = xy[:, 0], xy[:, 1]
+    try:
+        v = np.asarray(fn(x, y, t), dtype=np.float64)
+        if v.shape == ():
+            v = np.full(x.shape, float(v))
+        if v.shape != x.shape:
+            raise ValueError
+    except (TypeError, ValueError):
+        v = np.array([fn(a, b, t) for a, b in zip(x, y)], dtype=np.float64)
+    return v
 
 
 def nearest_nodes(coords, points):

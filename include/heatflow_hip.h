@@ -27,6 +27,8 @@
  *   hf_set_load        the load term dt * f * v * r * dx of build_variational_forms  space/space_and_forms.py:77-117;
  *                      b_equiv uploaded as it stands                    with_ir_steady.ipynb cells 18, 22
  *   hf_hold_load       b_equiv = A_free . u_ss with the transient's Dirichlet rows zeroed   with_ir_steady.ipynb cell 18
+ *   hf_tangent_setup / hf_run_tangent / hf_get_tangent   no counterpart: the reference fits by re-running the forward model
+ *                      over a grid (sweep_test.py:47-75, parameter_sweep.py:195-235); these give the derivatives of a run
  *
  * Conventions
  *   - All functions return 0 (HF_OK) or a negative HF_ERR_* code; hf_last_error(ctx)
@@ -275,6 +277,35 @@ int hf_steady_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, double rto
 int hf_set_load(hf_ctx* ctx, const double* F);
 int hf_hold_load(hf_ctx* ctx);
 int hf_get_load(hf_ctx* ctx, double* F);
+
+/* Tangent runs: the exact derivatives s_j = du/dtheta_j of the time loop with respect to up to 16 parameters, advanced next to
+ * the primal.  A column's parameter scales the conductivity of the cell tags mapped to it (K_j = the sum of
+ * their unit-conductivity r-weighted stiffness), enters the Dirichlet values through h_j = dg/dtheta_j, or both.  After every
+ * primal step A_hat u^{n+1} = ..., each column solves
+ *     A_hat s_j^{n+1} = M s_j^n + dt F_j - A[:,B] h_j^{n+1} on the free rows, (s_j)_B = h_j^{n+1},  F_j = -K_j u^{n+1}
+ * (F_j over every row, Dirichlet entries of u included), as the interleaved columns of one batched PCG on the shared
+ * operator with the context's preconditioner (Jacobi, or the transient's multigrid hierarchy), per column the stopping rule
+ * and the start-vector projection of the batched loop.  F is formed by a row-gather kernel in one pass for all columns.
+ * hf_tangent_setup  n_par = 1..16 parameters; the columns are n_par rounded up to nv = 2, 4, 8 or 16 (the padded ones stay
+ *        exactly zero and report 0 iterations).  tag_col = tab_len entries (one per tag value 0..max cell tag): the column
+ *        whose conductivity tag t carries, -1 = none.  Every tangent starts at zero.  HF_ERR_ARG: n_par outside 1..16, a
+ *        column outside [-1, n_par), a mapped tag that is not a cell tag of the mesh, or a mesh / operator without the
+ *        row-gather lists (HF_ASM_ROW_GATHER only).  HF_ERR_STATE: no mesh, a batch open or a load set.
+ * hf_run_tangent  hf_run plus the tangent stage: g_all, rtol, atol, max_it, n_s, nodes, samples and iters as hf_run, and the
+ *        primal samples, iteration counts and final state are bitwise those of hf_run with the same arguments.
+ *        h_all = n_steps x n_bc x nv ([step][bc][column]) or NULL (all zero); tangent_samples = n_steps x nv x n_s
+ *        ([step][column][node]; needed when n_s > 0); tangent_iters = n_steps x nv (may be NULL).  A second call continues
+ *        both the primal and the tangents.  HF_ERR_STATE before hf_tangent_setup, with a batch open or a load set, or
+ *        after hf_steady_solve until hf_set_state (a steady state depends on the conductivities, the tangents start at zero);
+ *        HF_ERR_ARG after an hf_assemble in another mode than HF_ASM_ROW_GATHER; all before any launch.  HF_ERR_NOCONV if the
+ *        primal or any tangent column fails.
+ * hf_get_tangent  copies column j (0 <= j < nv) of the tangent state out (n doubles).
+ * hf_set_state, hf_set_materials, hf_assemble (hence hf_update_kappa), hf_steady_solve and hf_tangent_setup reset every
+ * tangent to zero; hf_set_mesh removes the set-up. */
+int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col);
+int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const double* h_all, double rtol, double atol, int32_t max_it,
+                   int32_t n_s, const int32_t* nodes, double* samples, int32_t* iters, double* tangent_samples, int32_t* tangent_iters);
+int hf_get_tangent(hf_ctx* ctx, int32_t j, double* s);
 
 int hf_get_sizes(hf_ctx* ctx, int32_t* n, int32_t* n_e, int64_t* nnz, int32_t* n_bc);
 /* Any pointer may be NULL.  A is the matrix as it stands (eliminated when BCs are set). */
