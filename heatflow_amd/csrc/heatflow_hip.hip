@@ -176,6 +176,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   HF_TRY(dev_alloc(ctx, &ctx->d_uprev, n));
   HF_TRY(dev_alloc(ctx, &ctx->d_ustart, n));
   ctx->have_prev = false;
+  ctx->bdf_hist = false;
   free_responses(ctx);
   HF_TRY(dev_alloc(ctx, &ctx->d_b, n));
   HF_TRY(dev_alloc(ctx, &ctx->d_r, 2 * static_cast<size_t>(n) + 4));   // the level-1 result of a fused finest level lives behind r: [r; x_1]
@@ -512,6 +513,7 @@ int tangent_reset(hf_ctx* ctx) {
   if (T.nv == 0) return HF_OK;
   HF_HIP(hipMemsetAsync(T.u, 0, sizeof(double) * static_cast<size_t>(ctx->n) * T.nv, ctx->stream));
   HF_HIP(hipStreamSynchronize(ctx->stream));
+  T.bdf_hist = false;    // BDF2: s^{-1} = s^0 = 0
   for (bool& u_ : T.pused) u_ = false;
   T.pnext = 0; T.ppending = -1;
   T.pred_iters = 0;
@@ -730,7 +732,7 @@ int hf_update_kappa(hf_ctx* ctx, int32_t n_mat, const int32_t* tags, const doubl
   HF_HIP(copy_sync(ctx, ctx->d_kappa, tk.data(), sizeof(double) * ctx->tab_len, hipMemcpyHostToDevice));
   HF_TRY(upload_rg_tables(ctx, tk, nullptr));
   ctx->steady.ready = false;
-  return hf_assemble(ctx, ctx->dt, ctx->mode);
+  return hf_assemble(ctx, ctx->dt_step, ctx->mode);
 }
 
 int hf_set_dirichlet(hf_ctx* ctx, int32_t n_bc, const int32_t* dofs) {
@@ -762,7 +764,8 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
   if (!(dt > 0.0)) return fail(ctx, HF_ERR_ARG, "hf_assemble: dt must be positive");
   if (mode < 0 || mode > 3) return fail(ctx, HF_ERR_ARG, "hf_assemble: unknown mode %d", mode);
   HF_HIP(hipSetDevice(ctx->dev));
-  ctx->dt = dt;
+  ctx->dt_step = dt;
+  ctx->dt = ctx->scheme == HF_TIME_BDF2 ? 2.0 * dt / 3.0 : dt;   // BDF2: A' = M + (2/3) dt K
   ctx->mode = mode;
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   HF_TRY(launch_assemble(ctx));
@@ -800,6 +803,7 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
   ctx->assembled = true;
   ctx->pred_iters = 0;
   ctx->have_prev = false;
+  ctx->bdf_hist = false;
   free_responses(ctx);   // R depends on the operator
   return tangent_reset(ctx);   // and so do the tangents (hf_update_kappa comes here too)
 }
@@ -811,6 +815,19 @@ int hf_set_precond(hf_ctx* ctx, int32_t kind, int32_t reuse) {
   if (kind == 0) { (void)hipSetDevice(ctx->dev); free_amg(ctx); }
   ctx->precond = kind;
   ctx->amg_reuse = reuse ? 1 : 0;
+  return HF_OK;
+}
+
+int hf_set_time_scheme(hf_ctx* ctx, int32_t scheme) {
+  if (!ctx) return HF_ERR_ARG;
+  if (scheme != HF_TIME_BACKWARD_EULER && scheme != HF_TIME_BDF2) return fail(ctx, HF_ERR_ARG, "hf_set_time_scheme: unknown scheme %d", scheme);
+  if (scheme != ctx->scheme) {   // the assembled operator and an open batch belong to the other scheme
+    (void)hipSetDevice(ctx->dev);
+    free_batch(ctx);
+    ctx->assembled = false;
+    ctx->pred_iters = 0;
+    ctx->scheme = scheme;
+  }
   return HF_OK;
 }
 
@@ -1045,6 +1062,7 @@ int hf_set_state(hf_ctx* ctx, const double* u) {
   HF_HIP(hipMemcpyAsync(ctx->d_u, u, sizeof(double) * ctx->n, hipMemcpyHostToDevice, ctx->stream));
   HF_HIP(hipStreamSynchronize(ctx->stream));
   ctx->have_prev = false;
+  ctx->bdf_hist = false;   // BDF2: a rest start, u^{-1} = u^n
   ctx->g_hist = 0;       // the state no longer continues the recursion the boundary history belongs to
   proj_clear(ctx, true);
   ctx->tan.steady_state = false;
@@ -1160,6 +1178,7 @@ int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
   HF_TRY(dev_alloc(ctx, &ctx->tan.F, static_cast<size_t>(ctx->n) * nv));
   HF_HIP(copy_sync(ctx, ctx->tan.col, col.data(), sizeof(int32_t) * 64, hipMemcpyHostToDevice));
   T.nv = nv;
+  T.bdf_hist = false;
   T.load = ctx->tan.F;
   ctx->tan.npar = n_par;
   ctx->tan.nv = nv;
@@ -1343,8 +1362,9 @@ int hf_steady_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, double rto
     HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     ctx->last_ms = ms;
   }
-  // a new state, as hf_set_state: the history of the start vector does not continue
+  // a new state, as hf_set_state: the history of the start vector (and of BDF2) does not continue
   ctx->have_prev = false;
+  ctx->bdf_hist = false;
   ctx->g_hist = 0;
   proj_clear(ctx, true);
   if (rc != HF_ERR_HIP) HF_TRY(tangent_reset(ctx));
@@ -1429,6 +1449,7 @@ int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
   B.lds = ctx->bcols.nv == nv;
   B.nv = nv;
   B.have_prev = false;
+  B.bdf_hist = false;
   B.pred_iters = 0;
   B.loaded = 0;
   return HF_OK;
@@ -1523,6 +1544,9 @@ int hf_batch_set_state(hf_ctx* ctx, int32_t j, const double* u) {
   HF_HIP(hipSetDevice(ctx->dev));
   HF_HIP(copy_sync(ctx, ctx->d_tmp, u, sizeof(double) * ctx->n, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(kb_put_column, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->n), B.nv, j, ctx->d_tmp, B.u);
+  // BDF2: column j starts at rest (u^{-1} = u^0); the other columns keep their history
+  if (B.bdf_hist)
+    hipLaunchKernelGGL(kb_put_column, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->n), B.nv, j, ctx->d_tmp, B.uprev);
   HF_HIP(hipGetLastError());
   HF_HIP(hipStreamSynchronize(ctx->stream));
   B.have_prev = false;

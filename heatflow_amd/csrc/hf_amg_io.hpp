@@ -21,6 +21,7 @@ struct AmgBlobHeader {
   int32_t n, nl, fuse0, f32, coarse_n, coarse_ld, nbc, tab_len;
   double opc, dt;
   uint64_t bc_hash;
+  int32_t scheme, pad_;   // time scheme of the operator (hf_set_time_scheme); dt is the step hf_assemble was called with
 };
 
 struct CsrRecord {      // one operator: scalars, then ptr / idx / values / (dptr, dict, cid)
@@ -37,7 +38,8 @@ uint64_t fnv1a(const void* data, size_t bytes, uint64_t h = 1469598103934665603u
 using OperatorPrint = hf_ctx::OperatorPrint;
 
 int operator_print(hf_ctx* ctx, OperatorPrint& f) {
-  f.dt = ctx->dt;
+  f.dt = ctx->dt_step;
+  f.scheme = ctx->scheme;
   f.kappa.resize(ctx->tab_len);
   f.rhoc.resize(ctx->tab_len);
   HF_HIP(copy_sync(ctx, f.kappa.data(), ctx->d_kappa, sizeof(double) * ctx->tab_len, hipMemcpyDeviceToHost));
@@ -52,7 +54,7 @@ int operator_print(hf_ctx* ctx, OperatorPrint& f) {
 }
 
 bool same_print(const OperatorPrint& a, const OperatorPrint& b) {
-  return a.dt == b.dt && a.nbc == b.nbc && a.bc_hash == b.bc_hash && a.kappa == b.kappa && a.rhoc == b.rhoc;
+  return a.dt == b.dt && a.scheme == b.scheme && a.nbc == b.nbc && a.bc_hash == b.bc_hash && a.kappa == b.kappa && a.rhoc == b.rhoc;
 }
 
 struct BlobOut {          // sizes first (dst == nullptr), then the same walk writes
@@ -97,6 +99,7 @@ int walk_hierarchy(hf_ctx* ctx, BlobOut& o, const OperatorPrint& f) {
   h.nnz = ctx->nnz; h.n = ctx->n; h.nl = static_cast<int32_t>(ctx->amg.size()); h.fuse0 = ctx->amg_fuse0; h.f32 = ctx->amg_f32 ? 1 : 0;
   h.coarse_n = ctx->coarse_n; h.coarse_ld = ctx->coarse_ld; h.nbc = f.nbc; h.tab_len = ctx->tab_len; h.opc = ctx->amg_opc; h.dt = f.dt;
   h.bc_hash = f.bc_hash;
+  h.scheme = f.scheme;
   const size_t head_at = o.at;
   o.host(&h, sizeof h);
   o.host(f.kappa.data(), sizeof(double) * f.kappa.size());
@@ -229,7 +232,7 @@ int install_hierarchy(hf_ctx* ctx, const unsigned char* blob, size_t bytes) {
   if (h.nl < 1 || h.nl > 32 || h.tab_len != ctx->tab_len || h.coarse_n < 0 || h.coarse_n > 4096 || (h.coarse_n > 0 && (h.coarse_ld < h.coarse_n || (h.coarse_ld & 3))))
     return fail(ctx, HF_ERR_ARG, "hf_amg_install: header does not fit this context");
   OperatorPrint theirs;
-  theirs.dt = h.dt; theirs.nbc = h.nbc; theirs.bc_hash = h.bc_hash;
+  theirs.dt = h.dt; theirs.nbc = h.nbc; theirs.bc_hash = h.bc_hash; theirs.scheme = h.scheme;
   const double* pk = static_cast<const double*>(in.take(sizeof(double) * h.tab_len));
   const double* pc = static_cast<const double*>(in.take(sizeof(double) * h.tab_len));
   if (!in.ok) return fail(ctx, HF_ERR_ARG, "hf_amg_install: blob truncated");

@@ -105,8 +105,10 @@ __device__ __forceinline__ double op_value(const BOp& op, size_t k, int j) {
   return op.v0[k];
 }
 
-// Fine-pattern SpMV on NV interleaved columns, thread = (row, column).  Modes as k_spmv (0, 2, 3, 4, 5, 8, 9, 10); mode 10
-// (the right-hand side with a per-column load, b = M u + dt F) takes the interleaved load F in `bvec` and dt in `w`.
+// Fine-pattern SpMV on NV interleaved columns, thread = (row, column).  Modes as k_spmv (0, 2, 3, 4, 5, 8, 9, 10, 12, 14); mode 10
+// (the right-hand side with a per-column load, b = M u + dt F) takes the interleaved load F in `bvec` and dt in `w`.  The BDF2
+// right-hand sides 12 (y = M (4/3 x - 1/3 b), p = x) and 14 (the same + w F) take u^{n-1} in `bvec`, the interleaved load F in
+// `dinv` and write the copy of u^n to `pvec`; the operand combination is formed where x is read (kb_spmv_lds: staged).
 #ifndef HF_KB_U
 #define HF_KB_U 4
 #endif
@@ -149,8 +151,9 @@ __global__ __launch_bounds__(KB_BT) void kb_spmv(int n, const int32_t* __restric
     double e_b = 0.0, e_d = 0.0, e_y = 0.0, e_p = 0.0, e_x = 0.0;
     if (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 8 || MODE == 10) e_b = bvec[o];
     if (MODE == 2 || MODE == 4 || MODE == 5) e_d = OPK != OP_SHARED ? dinv[o] : dinv[row];
+    if (MODE == 14) e_d = dinv[o];
     if (MODE == 9 && !first9) { e_y = y[o]; e_p = pvec[o]; }
-    if (MODE == 4 || MODE == 8 || MODE == 9) e_x = x[o];
+    if (MODE == 4 || MODE == 8 || MODE == 9 || MODE == 12 || MODE == 14) e_x = x[o];
     double s = 0.0;
     for (int k = k0; k < k1; k += KB_U) {
       int c[KB_U];
@@ -162,7 +165,10 @@ __global__ __launch_bounds__(KB_BT) void kb_spmv(int n, const int32_t* __restric
         v[u] = in ? op_value<OPK, NV>(op, static_cast<size_t>(k + u), j) : 0.0;
       }
 #pragma unroll
-      for (int u = 0; u < KB_U; ++u) xv[u] = (k + u < k1) ? x[static_cast<size_t>(c[u]) * NV + j] : 0.0;
+      for (int u = 0; u < KB_U; ++u) {
+        const size_t oc = static_cast<size_t>(c[u]) * NV + j;
+        xv[u] = (k + u < k1) ? ((MODE == 12 || MODE == 14) ? bdf2_operand(x[oc], bvec[oc]) : x[oc]) : 0.0;
+      }
 #pragma unroll
       for (int u = 0; u < KB_U; ++u) s += v[u] * xv[u];
     }
@@ -192,6 +198,9 @@ __global__ __launch_bounds__(KB_BT) void kb_spmv(int n, const int32_t* __restric
       pvec[o] = 2.0 * e_x - e_b;
     } else if (MODE == 10) {
       y[o] = s + w * e_b;
+    } else if (MODE == 12 || MODE == 14) {
+      y[o] = MODE == 14 ? s + w * e_d : s;
+      pvec[o] = e_x;
     } else {
       const double api = first9 ? s : s + beta * e_y;
       const double pi = first9 ? e_x : e_x + beta * e_p;
@@ -308,7 +317,15 @@ __global__ __launch_bounds__(KB_BT) void kb_spmv_lds(int n, const int32_t* __res
     for (int i = threadIdx.x; i < nx; i += 2 * KB_BT) {
       const bool two = i + KB_BT < nx;
       const int c0 = comp.dict[d0 + i / NV], c1 = two ? comp.dict[d0 + (i + KB_BT) / NV] : 0;     // KB_BT is a multiple of NV: i % NV == j
-      const double x0 = x[static_cast<size_t>(c0) * NV + j], x1 = two ? x[static_cast<size_t>(c1) * NV + j] : 0.0;
+      const size_t o0 = static_cast<size_t>(c0) * NV + j, o1 = static_cast<size_t>(c1) * NV + j;
+      double x0, x1;
+      if (MODE == 12 || MODE == 14) {   // BDF2: the slice holds 4/3 u^n - 1/3 u^{n-1}
+        x0 = bdf2_operand(x[o0], bvec[o0]);
+        x1 = two ? bdf2_operand(x[o1], bvec[o1]) : 0.0;
+      } else {
+        x0 = x[o0];
+        x1 = two ? x[o1] : 0.0;
+      }
       sx[i] = x0;
       if (two) sx[i + KB_BT] = x1;
     }
@@ -324,8 +341,10 @@ __global__ __launch_bounds__(KB_BT) void kb_spmv_lds(int n, const int32_t* __res
       double e_b = 0.0, e_d = 0.0, e_y = 0.0, e_p = 0.0, e_x = 0.0;
       if (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 8 || MODE == 10) e_b = bvec[o];
       if (MODE == 2 || MODE == 4 || MODE == 5) e_d = OPK != OP_SHARED ? dinv[o] : dinv[row];
+      if (MODE == 14) e_d = dinv[o];
       if (MODE == 9 && !first9) { e_y = y[o]; e_p = pvec[o]; }
       if (MODE == 4 || MODE == 8 || MODE == 9) e_x = sx[static_cast<size_t>(own + (row - r0)) * NV + j];
+      if (MODE == 12 || MODE == 14) e_x = x[o];     // (the staged slice holds the combination)
       double s = 0.0;
       for (int k = pa; k < pb; ++k) {
         const double v = OPK == OP_AFFINE ? sv0[k] + dj * sv1[k] : sv0[k];
@@ -357,6 +376,9 @@ __global__ __launch_bounds__(KB_BT) void kb_spmv_lds(int n, const int32_t* __res
         pvec[o] = 2.0 * e_x - e_b;
       } else if (MODE == 10) {
         y[o] = s + w * e_b;
+      } else if (MODE == 12 || MODE == 14) {
+        y[o] = MODE == 14 ? s + w * e_d : s;
+        pvec[o] = e_x;
       } else {
         const double api = first9 ? s : s + beta * e_y;
         const double pi = first9 ? e_x : e_x + beta * e_p;
@@ -980,6 +1002,33 @@ struct BatchOps {
     }
   }
 
+  // BDF2 right-hand side on the shared M (kb_spmv / kb_spmv_lds mode 12, or 14 with the per-column load F)
+  static void rhs_bdf2(hf_ctx* c, const double* u, const double* uprev, double* b, const double* F, double* ucopy, double w) {
+    hf_ctx::Batch& B = c->batch;
+    BOp m{};
+    m.v0 = c->d_M;
+    if (B.lds) {
+      const hf_ctx::BatchCols& T = c->bcols;
+      const BComp comp{T.ptr, T.dict, T.own, T.id, T.rpc, T.nchunks, T.cap_nnz, T.cap_dict};
+      int grid = std::min(T.nchunks, B.Pb);
+      if (grid >= 64) grid &= ~7;
+      const size_t sm = batch_lds_bytes(T.cap_nnz, T.cap_dict, NV, false);
+      if (F != nullptr)
+        hipLaunchKernelGGL((kb_spmv_lds<14, NV, OP_SHARED>), dim3(grid), dim3(KB_BT), sm, c->stream, c->n, c->d_rowptr, m, u, b, B.scal,
+                           nullptr, uprev, F, ucopy, nullptr, nullptr, w, B.red, 0, comp, B.Pb);
+      else
+        hipLaunchKernelGGL((kb_spmv_lds<12, NV, OP_SHARED>), dim3(grid), dim3(KB_BT), sm, c->stream, c->n, c->d_rowptr, m, u, b, B.scal,
+                           nullptr, uprev, nullptr, ucopy, nullptr, nullptr, w, B.red, 0, comp, B.Pb);
+      return;
+    }
+    if (F != nullptr)
+      hipLaunchKernelGGL((kb_spmv<14, NV, OP_SHARED>), dim3(B.Pb), dim3(KB_BT), 0, c->stream, c->n, c->d_rowptr, c->d_colidx, m, u, b,
+                         B.scal, nullptr, uprev, F, ucopy, nullptr, nullptr, w, B.red, 0);
+    else
+      hipLaunchKernelGGL((kb_spmv<12, NV, OP_SHARED>), dim3(B.Pb), dim3(KB_BT), 0, c->stream, c->n, c->d_rowptr, c->d_colidx, m, u, b,
+                         B.scal, nullptr, uprev, nullptr, ucopy, nullptr, nullptr, w, B.red, 0);
+  }
+
   static void reduce(hf_ctx* c, const double* part_a, double* out_a, const double* part_b = nullptr, double* out_b = nullptr,
                      Scal* test = nullptr) {
     hipLaunchKernelGGL(kb_reduce, dim3(part_b ? 2 * NV : NV), dim3(TPB), 0, c->stream, c->batch.Pb, NV, part_a, out_a, part_b, out_b, test,
@@ -1201,8 +1250,17 @@ struct BatchOps {
   static int step(hf_ctx* ctx, const double* g_dev, double rtol, double atol, int max_it) {
     hf_ctx::Batch& B = ctx->batch;
     const int nb = ctx->nbc;
-    if (B.load != nullptr) spmv<10>(ctx, ctx->d_M, B.u, B.b, nullptr, B.load, nullptr, nullptr, nullptr, ctx->dt);   // b = M u + dt F
-    else spmv<0>(ctx, ctx->d_M, B.u, B.b);
+    if (ctx->scheme == HF_TIME_BDF2) {
+      // b = M (4/3 u^n - 1/3 u^{n-1}) (+ dt' F) in one pass over M; the same pass copies u^n into `ustart`, which then
+      // becomes u^{n-1} of the next step (pointer swap, no copy).  From a rest start (no history) u^{n-1} = u^n.
+      rhs_bdf2(ctx, B.u, B.bdf_hist ? B.uprev : B.u, B.b, B.load, B.ustart, ctx->dt);
+      std::swap(B.uprev, B.ustart);
+      B.bdf_hist = true;
+    } else if (B.load != nullptr) {
+      spmv<10>(ctx, ctx->d_M, B.u, B.b, nullptr, B.load, nullptr, nullptr, nullptr, ctx->dt);   // b = M u + dt F
+    } else {
+      spmv<0>(ctx, ctx->d_M, B.u, B.b);
+    }
     if (nb > 0) {
       if (ctx->nlift_rows > 0) {
         const int thr = ctx->nlift_rows * NV;

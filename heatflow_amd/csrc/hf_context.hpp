@@ -116,8 +116,10 @@ struct hf_ctx {
   bool cdict_own = false;      // every chunk's own rows sit contiguously in its column list (each row stores its diagonal): the kernels take x[row] from the staged slice
   bool c16 = true;             // HEATFLOW_SPMV_C16=0 keeps the 32-bit column stream
   bool have_mesh = false, have_mat = false, assembled = false;
-  double dt = 0.0;
+  double dt = 0.0;             // step of the assembled operator A = M + dt K: the step of hf_assemble (backward Euler) or 2/3 of it (BDF2)
+  double dt_step = 0.0;        // the step hf_assemble was called with
   int mode = 0;
+  int scheme = HF_TIME_BACKWARD_EULER;   // hf_set_time_scheme
 
   // host copies of the pattern (needed to build lifting structures and the multigrid hierarchy) and of the
   // elements (the lists of the LDS scatter kernels are built from them on first use)
@@ -159,6 +161,7 @@ struct hf_ctx {
   double *d_u = nullptr, *d_b = nullptr, *d_r = nullptr, *d_p = nullptr, *d_Ap = nullptr;
   double *d_uprev = nullptr, *d_ustart = nullptr;   // u^{n-1} and the buffer of the next start vector (rotated with d_u)
   bool have_prev = false;
+  bool bdf_hist = false;       // BDF2: d_uprev holds u^{n-1} of the current trajectory (false: a rest start, u^{n-1} = u^n)
   int extrapolate = 1;         // start PCG from 2 u^n - u^{n-1} (same answer, fewer iterations)
   // hf_set_start_vector kind 2: boundary-response correction of the start vector.  Host copies of the last two
   // boundary vectors, an orthonormal set of directions seen in their second difference and, per direction d,
@@ -222,7 +225,7 @@ struct hf_ctx {
   double amg_opc = 0.0, amg_setup_s = 0.0;
   // what the fine operator the hierarchy was built from depends on besides the mesh (hf_amg_io.hpp): time step, coefficient
   // tables, Dirichlet set - compared with the context's own operator whenever a kept or installed hierarchy meets a new hf_assemble
-  struct OperatorPrint { double dt = 0.0; std::vector<double> kappa, rhoc; int32_t nbc = 0; uint64_t bc_hash = 0; } amg_print;
+  struct OperatorPrint { double dt = 0.0; std::vector<double> kappa, rhoc; int32_t nbc = 0; uint64_t bc_hash = 0; int32_t scheme = 0; } amg_print;
   long long amg_fallbacks = 0;   // steps finished by Jacobi-PCG after a multigrid-PCG breakdown
   // steady state (hf_steady_setup / hf_steady_solve): the stiffness K on the pattern - as assembled (Kfree, for hf_hold_load)
   // and with its own Dirichlet set S eliminated (K) -, the lifting columns K[free, S], D^-1 and a multigrid hierarchy of
@@ -271,6 +274,7 @@ struct hf_ctx {
     std::vector<BatchLevel> lev;
     int Pb = 0, pred_iters = 0;
     bool have_prev = false;
+    bool bdf_hist = false;       // BDF2: uprev holds every column's u^{n-1} (false: u^{n-1} = u^n)
     // projection start vector per column: ring of (solutions with zeroed Dirichlet entries, right-hand sides)
     double *pV[PROJ_MH] = {nullptr}, *pF[PROJ_MH] = {nullptr}, *pG = nullptr, *palpha = nullptr, *ppart = nullptr;
     bool pused[PROJ_MH] = {false};

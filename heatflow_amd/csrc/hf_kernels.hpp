@@ -659,6 +659,10 @@ __global__ void k_mark_rows(int nq, const int32_t* __restrict__ idx, unsigned ch
 //           p.Ap partials - SpMV and direction update in one pass
 //   MODE 10: y = A x + w F            (RHS with a load: b = M u^n + dt F; F comes in the `dinv` operand)
 //   MODE 11: y = A x + w F; p = 2 x - b   (MODE 8 with the load of MODE 10)
+//   MODE 12..15: BDF2 right-hand sides, `b` carries u^{n-1} and the operand is formed while the column slice is staged:
+//   MODE 12: y = A (4/3 x - 1/3 b); p = x             (p: the copy of u^n that becomes the next step's u^{n-1})
+//   MODE 13: y = A (4/3 x - 1/3 b); p = 2 x - b       (with the extrapolated start vector, as MODE 8)
+//   MODE 14: MODE 12 + w F    MODE 15: MODE 13 + w F  (load in the `dinv` operand, as MODE 10 / 11)
 // The chunk is `rpc` rows (512 for the fine operator; fewer for long-row transfer operators so
 // that a chunk's products fit the 64-KB LDS window).
 // ------------------------------------------------------------------------------------------
@@ -722,6 +726,9 @@ __device__ __forceinline__ T stream_load(const T* p) {
 #endif
 }
 
+// BDF2 operand of the right-hand side: 4/3 u^n - 1/3 u^{n-1}
+__device__ __forceinline__ double bdf2_operand(double un, double unm1) { return (4.0 * un - unm1) * (1.0 / 3.0); }
+
 template <int MODE, bool C16 = false, typename VT = double, int UN = 8>
 __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_spmv(int n, int nchunks, int rpc /* rows per chunk, <= TS */,
                                               const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
@@ -734,7 +741,10 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                                               int parity, ColComp comp) {
   extern __shared__ double sprod[];
   __shared__ double s4[TS / 64];
-  __shared__ int s_own;   // position of the chunk's first row in its column list (ColComp::own)
+  __shared__ int s_own;
+  constexpr bool BDF = MODE >= 12 && MODE <= 15;   // operand x[c] -> 4/3 x[c] - 1/3 bvec[c]
+  // the operand slice as staged: x, or the BDF2 combination of x and bvec (two gathers per list entry, one slice in LDS)
+  auto opnd = [&](int c) { return BDF ? bdf2_operand(x[c], bvec[c]) : x[c]; };   // position of the chunk's first row in its column list (ColComp::own)
   // launches inside the PCG loop return at once after convergence; MODE 0 / 7 are also used outside it (right-hand
   // side, debug products), where the launcher passes no `scal`
   if ((MODE == 3 || MODE == 4 || MODE == 6 || MODE == 9) && scal->done) return;
@@ -798,11 +808,12 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
   // would then cover all loads in flight, the prefetched ones of the next chunk included
   auto row_operands = [&](int prc, bool from_slice) {
     RowOps e{0.0, 0.0, 0.0, 0.0, 0.0};
-    if (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 7 || MODE == 8 || MODE == 11) e.b = bvec[prc];
-    if (MODE == 2 || MODE == 4 || MODE == 5 || MODE == 10 || MODE == 11) e.d = dinv[prc];
+    if (MODE == 2 || MODE == 3 || MODE == 4 || MODE == 5 || MODE == 7 || MODE == 8 || MODE == 11 || MODE == 13 || MODE == 15) e.b = bvec[prc];
+    if (MODE == 2 || MODE == 4 || MODE == 5 || MODE == 10 || MODE == 11 || MODE == 14 || MODE == 15) e.d = dinv[prc];
     if (MODE == 6 || (MODE == 9 && !first9)) e.y = y[prc];
     if (MODE == 9 && !first9) e.p = pvec[prc];
     if ((MODE == 4 || MODE == 8 || MODE == 9 || MODE == 11) && !from_slice) e.x = x[prc];
+    if (BDF) e.x = x[prc];     // the staged slice holds the combination, not u^n
     return e;
   };
   // the chunk's products are parked in sprod: row sums in CSR order and the mode's epilogue
@@ -856,6 +867,9 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       } else if (MODE == 11) {
         y[row] = s + w * e.d;
         pvec[row] = 2.0 * e.x - e.b;
+      } else if (BDF) {
+        y[row] = (MODE == 14 || MODE == 15) ? s + w * e.d : s;
+        pvec[row] = (MODE == 13 || MODE == 15) ? 2.0 * e.x - e.b : e.x;
       } else {
         const double api = first9 ? s : s + beta * e.y;          // first iteration: p = z, Ap = A z
         const double pi = first9 ? e.x : e.x + beta * e.p;
@@ -913,7 +927,7 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       int c0[HF_STAGE_U];
       double x0[HF_STAGE_U];
 #pragma unroll
-      for (int u = 0; u < HF_STAGE_U; ++u) { c0[u] = lhead[u]; x0[u] = x[c0[u]]; }
+      for (int u = 0; u < HF_STAGE_U; ++u) { c0[u] = lhead[u]; x0[u] = opnd(c0[u]); }
       const Bounds nxt = bounds(more ? chunk + sched.step : chunk);
       const int pa = rowptr[prc] - k0, pb = rowptr[prc + 1] - k0;
       RowOps e = row_operands(prc, comp.own != 0);
@@ -932,7 +946,7 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 #pragma unroll
         for (int u = 0; u < HF_STAGE_U; ++u) c[u] = comp.dict[d0 + min(i + u * TS, nd - 1)];
 #pragma unroll
-        for (int u = 0; u < HF_STAGE_U; ++u) xv[u] = x[c[u]];
+        for (int u = 0; u < HF_STAGE_U; ++u) xv[u] = opnd(c[u]);
 #pragma unroll
         for (int u = 0; u < HF_STAGE_U; ++u)
           if (i + u * TS < nd) {
@@ -1008,7 +1022,7 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
 #pragma unroll
         for (int u = 0; u < HF_STAGE_U; ++u) c[u] = (i + u * TS < nd) ? comp.dict[d0 + i + u * TS] : 0;
 #pragma unroll
-        for (int u = 0; u < HF_STAGE_U; ++u) xv[u] = (i + u * TS < nd) ? x[c[u]] : 0.0;
+        for (int u = 0; u < HF_STAGE_U; ++u) xv[u] = (i + u * TS < nd) ? opnd(c[u]) : 0.0;
 #pragma unroll
         for (int u = 0; u < HF_STAGE_U; ++u)
           if (i + u * TS < nd) {
@@ -1048,7 +1062,7 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
           v[u] = in ? static_cast<double>(vals[k + u * TS]) : 0.0;
         }
 #pragma unroll
-        for (int u = 0; u < HF_UNROLL; ++u) xv[u] = (k + u * TS < k1) ? x[c[u]] : 0.0;
+        for (int u = 0; u < HF_UNROLL; ++u) xv[u] = (k + u * TS < k1) ? opnd(c[u]) : 0.0;
 #pragma unroll
         for (int u = 0; u < HF_UNROLL; ++u)
           if (k + u * TS < k1) sprod[k - k0 + u * TS] = v[u] * xv[u];

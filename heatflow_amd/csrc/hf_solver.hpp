@@ -741,6 +741,20 @@ void launch_rhs(hf_ctx* ctx) {
     launch_spmv<0>(ctx, ctx->d_M, ctx->d_u, ctx->d_b);
 }
 
+// BDF2: b = M (4/3 u^n - 1/3 u^{n-1}), plus dt' F when a load is set, in one pass over M (k_spmv modes 12-15).  The same pass
+// writes `ustart`: the extrapolated start vector 2 u^n - u^{n-1} (extrap) or a copy of u^n, which the caller turns into the
+// next step's u^{n-1} by a pointer swap.  Without a history (a rest start) u^{n-1} = u^n.
+void launch_rhs_bdf2(hf_ctx* ctx, bool extrap) {
+  const double* um1 = ctx->bdf_hist ? ctx->d_uprev : ctx->d_u;
+  if (ctx->have_load) {
+    if (extrap) launch_spmv<15>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, um1, ctx->d_ustart, nullptr, nullptr, ctx->dt, ctx->d_load);
+    else launch_spmv<14>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, um1, ctx->d_ustart, nullptr, nullptr, ctx->dt, ctx->d_load);
+  } else {
+    if (extrap) launch_spmv<13>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, um1, ctx->d_ustart);
+    else launch_spmv<12>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, um1, ctx->d_ustart);
+  }
+}
+
 // One time step to the boundary values g_host (n_bc doubles on the host; g_dev = the same values already on
 // the device, or null).  Leaves iteration count / residual in h_scal.
 int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double rtol, double atol, int max_it) {
@@ -748,12 +762,28 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
   RespArgs ra{};
   ra.k = 0;
   const bool projected = ctx->start_kind == 3;
+  const bool bdf2 = ctx->scheme == HF_TIME_BDF2;
   if (projected) HF_TRY(proj_ensure(ctx));
   const bool hist_ok = nb > 0 && ctx->extrapolate && ctx->have_prev && ctx->g_hist >= 2;
-  if (ctx->start_kind >= 2 && hist_ok) HF_TRY(prepare_response(ctx, g_host, max_it, &ra));
+  // (BDF2: kind 2's correction assumes backward Euler's one-step recursion - kind 2 runs as kind 1; kind 3 keeps the
+  // responses as basis vectors: each solves A' w = f with a known f, whatever the scheme)
+  if (ctx->start_kind >= 2 && hist_ok && !(bdf2 && ctx->start_kind == 2)) HF_TRY(prepare_response(ctx, g_host, max_it, &ra));
   const double* g = g_dev ? g_dev : ctx->d_g;   // hf_run has every step's boundary values on the device already
   if (nb > 0 && !g_dev) HF_HIP(hipMemcpyAsync(ctx->d_g, g_host, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
-  if (projected) {
+  if (bdf2 && (projected || !ctx->extrapolate)) {
+    // BDF2 with the projected start vector (kind 3) or u^n (kind 0): the right-hand side's pass keeps u^n for the next step
+    launch_rhs_bdf2(ctx, false);
+    std::swap(ctx->d_uprev, ctx->d_ustart);
+    ctx->bdf_hist = true;
+    ctx->have_prev = true;
+  } else if (bdf2) {
+    // BDF2 with the extrapolated start vector (kinds 1 and 2); from a rest start it is u^n
+    launch_rhs_bdf2(ctx, true);
+    HF_HIP(hipMemcpyAsync(ctx->d_uprev, ctx->d_u, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+    HF_HIP(hipMemcpyAsync(ctx->d_u, ctx->d_ustart, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+    ctx->bdf_hist = true;
+    ctx->have_prev = true;
+  } else if (projected) {
     // b = M u^n, lifting, set_bc; then the start vector = A-norm projection of the new solution on the span of the last
     // solutions and the boundary responses (kind 3)
     launch_rhs(ctx);

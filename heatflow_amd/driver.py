@@ -154,6 +154,25 @@ def prepare_mesh(cfg, mesh_folder, rebuild_mesh, stack, defer_write=False):
     return coords, tris, tags, tag_map
 
 
+def time_scheme(cfg):
+    """The time scheme a configuration asks for: ``timing.scheme`` = "backward_euler" (also when the key is absent: the
+    reference's scheme) or "bdf2"; ValueError for anything else."""
+    from .hip_backend import time_scheme_code
+
+    name = (cfg.get("timing") or {}).get("scheme", "backward_euler")
+    if name is None:
+        name = "backward_euler"
+    time_scheme_code(name)
+    return name
+
+
+def _with_scheme(cfg):
+    """``cfg`` with the time scheme it runs with written out (``timing.scheme``), for used_config.yaml."""
+    out = dict(cfg)
+    out["timing"] = dict(cfg.get("timing") or {}, scheme=time_scheme(cfg))
+    return out
+
+
 def build_pattern_blob(coords, tris, tags, device_id=0):
     """The connectivity-derived tables of a mesh (CSR pattern, compressed column lists, row-gather assembly
     lists), built ONCE on this GPU and returned as a uint8 array: a sweep hands it to every solver session of
@@ -209,7 +228,9 @@ class SimulationSession:
         dt = float(cfg["timing"]["t_final"]) / num_steps
         bcs = self._boundary_conditions(cfg, stack)
         tag_to_k, tag_to_rc = self._tables(stack)
-        self._ensure_problem(self._problem_key(dt, tag_to_rc, bcs), tag_to_k, tag_to_rc, dt, bcs, float(cfg["heating"]["ic_temp"]))
+        scheme = time_scheme(cfg)
+        self._ensure_problem(self._problem_key(dt, tag_to_rc, bcs, scheme), tag_to_k, tag_to_rc, dt, bcs, float(cfg["heating"]["ic_temp"]),
+                             scheme)
 
     def _tables(self, stack):
         tag_to_k = {self.material_tags[m.name]: m.properties["k"] for m in stack.materials}
@@ -247,12 +268,13 @@ class SimulationSession:
             self._heats.append(heat_o)
         return bcs
 
-    def _problem_key(self, dt, tag_to_rc, bcs):
-        # the resident problem is reusable only for exactly the same Dirichlet DOF sets, in the same order
+    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler"):
+        # the resident problem is reusable only for exactly the same Dirichlet DOF sets, in the same order, and time scheme
         return (dt, tuple(sorted(tag_to_rc.items())),
-                tuple(hashlib.sha1(np.ascontiguousarray(b.row_dofs, dtype=np.int64).tobytes()).hexdigest() for b in bcs))
+                tuple(hashlib.sha1(np.ascontiguousarray(b.row_dofs, dtype=np.int64).tobytes()).hexdigest() for b in bcs),
+                scheme)
 
-    def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp):
+    def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme="backward_euler"):
         """The resident HeatProblem for ``key`` (built if absent), its operator valued for ``tag_to_k``."""
         if self.problem is None or key != self._key:
             self.close()
@@ -261,7 +283,8 @@ class SimulationSession:
             self.problem = HeatProblem(self.coords, self.tris, self.tags, tag_to_k, tag_to_rc, dt, bcs, ic_temp,
                                        backend=self.backend, device_id=self.device_id, rtol=self.rtol,
                                        max_it=self.max_it, assembly_mode=self.assembly_mode, precond=self.precond,
-                                       amg_reuse=True, pattern=self.pattern, amg=shared["blob"] if shared else None)
+                                       amg_reuse=True, pattern=self.pattern, amg=shared["blob"] if shared else None,
+                                       scheme=scheme)
             self._key = key
             self._k = dict(tag_to_k)
             # conductivities the multigrid levels were built for: this problem's, or those of the session that shared them
@@ -315,21 +338,22 @@ class SimulationSession:
         num_steps = int(cfg0["timing"]["num_steps"])
         dt = float(cfg0["timing"]["t_final"]) / num_steps
         ic_temp = float(cfg0["heating"]["ic_temp"])
+        scheme = time_scheme(cfg0)
         cols = []
         for cfg, stack in zip(cfgs, stacks):
             bcs = self._boundary_conditions(cfg, stack)
             tk, trc = self._tables(stack)
-            key = self._problem_key(float(cfg["timing"]["t_final"]) / int(cfg["timing"]["num_steps"]), trc, bcs)
+            key = self._problem_key(float(cfg["timing"]["t_final"]) / int(cfg["timing"]["num_steps"]), trc, bcs, time_scheme(cfg))
             cols.append((bcs, tk, trc, key))
             if int(cfg["timing"]["num_steps"]) != num_steps or float(cfg["heating"]["ic_temp"]) != ic_temp or key != cols[0][3]:
-                raise ValueError("run_batch: the configurations must share time stepping, ic_temp, rho_c and the Dirichlet sets")
+                raise ValueError("run_batch: the configurations must share time stepping (and scheme), ic_temp, rho_c and the Dirichlet sets")
         percol = any(c[1] != cols[0][1] for c in cols)
         mid = cols[nv // 2]
         # conductivities that differ between the columns; a single one (sweep_test.py's kappa_sample list) makes
         # the operators an affine family A + (kappa_j - kappa_ref) A1: two shared matrices instead of nv
         varying = [t for t in mid[1] if any(c[1][t] != mid[1][t] for c in cols)]
         affine = percol and len(varying) == 1
-        self._ensure_problem(mid[3], mid[1], mid[2], dt, mid[0], ic_temp)
+        self._ensure_problem(mid[3], mid[1], mid[2], dt, mid[0], ic_temp, scheme)
         prob = self.problem
         be = prob.backend
         if percol and self.precond == 1:             # all columns share the hierarchy: keep every column within its range
@@ -409,9 +433,10 @@ class SimulationSession:
         bcs = self._boundary_conditions(cfg, stack, two_sided)
         varying = bcs[3:]
         tag_to_k, tag_to_rc = self._tables(stack)
-        key = self._problem_key(dt, tag_to_rc, bcs)
+        scheme = time_scheme(cfg)
+        key = self._problem_key(dt, tag_to_rc, bcs, scheme)
         fresh = self.problem is None or key != self._key
-        self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp)
+        self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme)
         if not fresh:
             self.problem.set_state(ic_temp)
             self.problem.iters = []
@@ -613,7 +638,7 @@ def run_simulation_impl(kind, cfg, mesh_folder, rebuild_mesh=False, visualize_me
             save_folder = output_folder
             os.makedirs(save_folder, exist_ok=True)
             with open(os.path.join(save_folder, "used_config.yaml"), "w") as f:
-                _dump_yaml(cfg, f)
+                _dump_yaml(_with_scheme(cfg), f)
         else:
             save_folder = os.path.join(os.getcwd(), "sim_outputs", "refactor_test")
             os.makedirs(save_folder, exist_ok=True)
@@ -666,7 +691,7 @@ def run_simulation_batch_impl(kind, cfgs, output_folders, watcher_points_list, s
         for cfg, folder in zip(cfgs, output_folders):
             os.makedirs(folder, exist_ok=True)
             with open(os.path.join(folder, "used_config.yaml"), "w") as f:
-                _dump_yaml(cfg, f)
+                _dump_yaml(_with_scheme(cfg), f)
         results = session.run_batch(cfgs, stacks, watcher_points_list[0], read_flux=read_flux and kind == "no_diamond")
         for res, folder, wp in zip(results, output_folders, watcher_points_list):
             if wp is not None:

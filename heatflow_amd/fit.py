@@ -71,10 +71,12 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     tag_map) reuse what the caller has; otherwise the mesh is loaded from ``mesh_folder``, or built there (``rebuild_mesh``
     True, or None and the folder holds no mesh).  A trial step costs one primal run; only an accepted step is followed by a
     tangent run for the next Jacobian.  Returns {params, values, rmse, converged, iterations, history, stderr, runs,
-    tangent_runs, seconds}."""
-    from .driver import SimulationSession, prepare_mesh
+    tangent_runs, seconds, scheme}.  The time scheme is the configuration's (``timing.scheme``, default backward Euler);
+    the tangents are those of the discrete loop of that scheme."""
+    from .driver import SimulationSession, prepare_mesh, time_scheme
 
     t0 = time.time()
+    scheme = time_scheme(cfg)
     params = tuple(params)
     exp = load_experiment(exp_csv)
     ic = float(cfg["heating"]["ic_temp"])
@@ -149,7 +151,7 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     return {"params": list(params), "values": theta.tolist(), "rmse": float(np.sqrt(cost / len(r))), "converged": bool(converged),
             "iterations": it, "history": history, "stderr": stderr.tolist(), "runs": runs, "tangent_runs": tangent_runs,
             "seconds": time.time() - t0, "tangent_iters_mean": float(np.mean(res["tangent_iters"])),
-            "pcg_iters_mean": float(np.mean(res["iters"]))}
+            "pcg_iters_mean": float(np.mean(res["iters"])), "scheme": scheme}
 
 
 def main(argv=None, backend=None):
@@ -167,9 +169,13 @@ def main(argv=None, backend=None):
     ap.add_argument("--x0", nargs="+", type=float, default=None)
     ap.add_argument("--max-iter", type=int, default=20)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--scheme", choices=("backward_euler", "bdf2"), default=None,
+                    help="time scheme (default: the configuration's timing.scheme, else backward_euler)")
     a = ap.parse_args(argv)
     with open(a.config) as f:
         cfg = yaml.safe_load(f)
+    if a.scheme is not None:
+        cfg.setdefault("timing", {})["scheme"] = a.scheme
     os.makedirs(a.output_dir, exist_ok=True)
     mesh_folder = a.mesh_folder or os.path.join(a.output_dir, "mesh")
     out = fit_parameters(cfg, mesh_folder, a.params, a.exp_csv, a.x0, a.max_iter, device_id=a.device, backend=backend,
@@ -177,7 +183,7 @@ def main(argv=None, backend=None):
     out["config"] = a.config
     with open(os.path.join(a.output_dir, "fit_summary.json"), "w") as f:
         json.dump(out, f, indent=2)
-    print(json.dumps({k: out[k] for k in ("params", "values", "stderr", "rmse", "converged", "iterations", "runs", "seconds")}))
+    print(json.dumps({k: out[k] for k in ("params", "values", "stderr", "rmse", "converged", "iterations", "runs", "seconds", "scheme")}))
     return 0
 
 

@@ -19,11 +19,20 @@ ASM_LDS_ATOMIC, ASM_LDS_COLORED, ASM_GLOBAL_ATOMIC, ASM_ROW_GATHER = 0, 1, 2, 3
 PC_JACOBI, PC_AMG = 0, 1
 K_SPMV, K_PCG_SPMV, K_PCG_UPDATE, K_PCG_DIR, K_ASSEMBLE, K_RHS, K_STREAM_READ = range(7)
 BATCH_SHARED, BATCH_PER_COLUMN, BATCH_AFFINE = 0, 1, 2
+TIME_BACKWARD_EULER, TIME_BDF2 = 0, 1
+TIME_SCHEMES = {"backward_euler": TIME_BACKWARD_EULER, "bdf2": TIME_BDF2}   # config / CLI names
+
+
+def time_scheme_code(name):
+    """The hf_set_time_scheme code of a scheme name ("backward_euler" or "bdf2"); ValueError for anything else."""
+    if name not in TIME_SCHEMES:
+        raise ValueError(f"unknown time scheme {name!r} (expected one of {sorted(TIME_SCHEMES)})")
+    return TIME_SCHEMES[name]
 
 EXPORTS = [
     "hf_version", "hf_create", "hf_destroy", "hf_last_error", "hf_set_mesh", "hf_set_mesh_prebuilt", "hf_pattern_export_size",
     "hf_pattern_export", "hf_amg_export_size", "hf_amg_export", "hf_amg_install", "hf_set_materials",
-    "hf_update_kappa", "hf_set_dirichlet", "hf_assemble", "hf_set_precond", "hf_set_start_vector", "hf_get_response_solves", "hf_get_amg_info", "hf_get_amg_fallbacks", "hf_set_state", "hf_get_state", "hf_sample", "hf_step", "hf_run",
+    "hf_update_kappa", "hf_set_dirichlet", "hf_assemble", "hf_set_time_scheme", "hf_set_precond", "hf_set_start_vector", "hf_get_response_solves", "hf_get_amg_info", "hf_get_amg_fallbacks", "hf_set_state", "hf_get_state", "hf_sample", "hf_step", "hf_run",
     "hf_batch_begin", "hf_batch_load_column", "hf_batch_set_affine", "hf_batch_set_state", "hf_batch_get_state", "hf_batch_run", "hf_batch_run_flux", "hf_batch_end",
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
@@ -97,6 +106,7 @@ def load_library():
         "hf_update_kappa": [vp, i32, pi, pd],
         "hf_set_dirichlet": [vp, i32, pi],
         "hf_assemble": [vp, dbl, i32],
+        "hf_set_time_scheme": [vp, i32],
         "hf_set_precond": [vp, i32, i32],
         "hf_set_start_vector": [vp, i32],
         "hf_get_response_solves": [vp, C.POINTER(i64)],
@@ -297,6 +307,12 @@ class HeatflowHIP:
     def set_precond(self, kind=PC_JACOBI, reuse=False):
         """PC_JACOBI (0) or PC_AMG (1); call before assemble()."""
         self._check(self._lib.hf_set_precond(self._ctx, int(kind), 1 if reuse else 0))
+
+    def set_time_scheme(self, scheme=TIME_BACKWARD_EULER):
+        """TIME_BACKWARD_EULER (0, default) or TIME_BDF2 (1), or their names; call before assemble(), which keeps taking the
+        real step.  A change invalidates the assembly and closes an open batch."""
+        code = time_scheme_code(scheme) if isinstance(scheme, str) else int(scheme)
+        self._check(self._lib.hf_set_time_scheme(self._ctx, code))
 
     def set_start_vector(self, kind=3):
         """0: u^n, 1: 2u^n - u^{n-1}, 2: that + response to the boundary values' second difference, 3 (default):

@@ -33,7 +33,7 @@ import yaml
 import sys
 
 from .driver import (SimulationSession, build_pattern_blob, flush_mesh_writes, prepare_mesh, run_simulation_batch_impl,
-                     run_simulation_impl)
+                     run_simulation_impl, time_scheme)
 from .geometry import build_stack, watcher_points as _watcher_points
 from .hip_backend import HipError, NotConverged
 
@@ -365,15 +365,19 @@ def run_simulation_group(items, base_config, mesh_folder, output_dir, write_xdmf
 
 def run_parameter_sweep(base_config_path, output_dir, fwhm_range, k_range, width_range, num_points,
                         base_mesh_folder="meshes", write_xdmf=False, suppress_print=True, num_processes=None, *,
-                        session_factory=None, device_id=None, pattern_builder=None, batch=1):
+                        session_factory=None, device_id=None, pattern_builder=None, batch=1, scheme=None):
     """Sweep driver.  ``num_processes`` is accepted for signature parity; the degree of
     parallelism is the size of the torch.distributed world (one rank per GPU).
     ``session_factory(coords, tris, tags, tag_map)`` lets tests substitute the solver session.
     ``batch`` > 1: up to that many (16, 8, 4 or 2) consecutive points of a rank advance together through the batched
-    time loop (points that share k share one operator, others get one operator per column)."""
+    time loop (points that share k share one operator, others get one operator per column).
+    ``scheme`` ("backward_euler" / "bdf2") overrides the base configuration's ``timing.scheme``."""
     rank, world = world_info()
     with open(base_config_path) as f:
         base_config = yaml.safe_load(f)
+    if scheme is not None:
+        base_config.setdefault("timing", {})["scheme"] = scheme
+    time_scheme(base_config)          # an unknown scheme raises before any work
     combos, fwhm_vals, k_vals, width_vals = create_parameter_grid(fwhm_range, k_range, width_range, num_points)
     if device_id is None:
         device_id = local_device()
@@ -503,8 +507,10 @@ def run_kappa_sweep(cfg, mesh_folder, k_values, output_dir, *, rebuild_mesh=Fals
     Measurement hooks (bench.py): ``warmup_steps`` > 0 makes every session run that many untimed steps of the
     first point before the point loop (mesh, pattern, matrices and multigrid levels are then resident);
     ``on_ready()`` / ``on_done()`` are called right before / after the point loop (barrier + clock);
-    ``timing`` (dict) receives the wall times of the phases on this rank."""
+    ``timing`` (dict) receives the wall times of the phases on this rank.
+    The time scheme is the configuration's ``timing.scheme`` (default backward Euler)."""
     rank, world = world_info()
+    time_scheme(cfg)                  # an unknown scheme raises before any work
     if device_id is None:
         device_id = local_device()
     stack = build_stack(cfg)
@@ -685,6 +691,8 @@ def main(argv=None):
     p.add_argument("--verbose", action="store_true")
     p.add_argument("--batch", type=int, default=16,
                    help="points of a rank advanced together by the batched time loop (16, 8, 4, 2; 1 = one run per point)")
+    p.add_argument("--scheme", choices=("backward_euler", "bdf2"), default=None,
+                   help="time scheme (default: the configuration's timing.scheme, else backward_euler)")
     a = p.parse_args(argv)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         import torch
@@ -695,7 +703,7 @@ def main(argv=None):
             torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
         dist.init_process_group("nccl" if use_gpu else "gloo")
     run_parameter_sweep(a.config, a.output_dir, tuple(a.fwhm_range), tuple(a.k_range), tuple(a.width_range),
-                        tuple(a.num_points), a.mesh_folder, a.write_xdmf, not a.verbose, batch=a.batch)
+                        tuple(a.num_points), a.mesh_folder, a.write_xdmf, not a.verbose, batch=a.batch, scheme=a.scheme)
     d = _dist()
     if d is not None:
         d.destroy_process_group()

@@ -89,6 +89,10 @@ def _thomas_solve(fac, b):
 def run_1d(cfg, mesh_folder_2d, mesh_folder_1d=None, rebuild_mesh=False, visualize_mesh=False, output_folder=None,
            watcher_points=None, write_xdmf=True, suppress_print=False, use_radial_correction=True,
            radial_gradient_path=None, *, kappa_lookup="reference"):
+    # the host 1-D model steps with backward Euler only: a configuration that asks for another scheme is refused, not ignored
+    scheme = (cfg.get("timing") or {}).get("scheme") or "backward_euler"
+    if scheme != "backward_euler":
+        raise ValueError(f"run_1d: timing.scheme {scheme!r} is not supported by the 1-D model (backward Euler only)")
     with suppress_output(suppress_print):
         t_start = time.time()
         mesh_cfg_path = os.path.join(mesh_folder_2d, "mesh_cfg.yaml")

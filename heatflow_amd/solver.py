@@ -1,4 +1,4 @@
-"""Backward-Euler heat problem on the HIP backend.
+"""Backward-Euler (or, opt-in, BDF2) heat problem on the HIP backend.
 
 Host-side equivalent of the block *forms -> assemble_matrix -> KSP -> time loop* of the
 reference drivers (run_with_diamond.py:321-394, 456-504), with the seven dolfinx/PETSc
@@ -16,7 +16,7 @@ import time
 import numpy as np
 
 from .bc import gather_bc_values, gather_plan, merge_bcs
-from .hip_backend import ASM_ROW_GATHER, PC_AMG, PC_JACOBI, HeatflowHIP
+from .hip_backend import ASM_ROW_GATHER, PC_AMG, PC_JACOBI, HeatflowHIP, time_scheme_code
 
 # Default PCG tolerance: at rtol = 1e-10 the temperature field agrees with a sparse
 # direct solve of the same system to ~3e-6 K (measured on the stock and the 1M-DOF
@@ -44,11 +44,13 @@ class HeatProblem:
               and amg_reuse=True): installed instead of being built
     precond : PC_JACOBI (Jacobi-PCG, the north-star solver) or PC_AMG (PCG preconditioned by a
               smoothed-aggregation V-cycle: same stopping rule and answer, ~50x fewer iterations)
+    scheme : "backward_euler" (default, the reference's scheme) or "bdf2" (second order, hf_set_time_scheme); ``dt`` stays
+              the time step and the sample times stay (k+1) dt
     """
 
     def __init__(self, coords, tris, tags, tag_to_k, tag_to_rho_cv, dt, bcs, u0, *, backend=None, device_id=0,
                  assembly_mode=ASM_ROW_GATHER, rtol=DEFAULT_RTOL, atol=0.0, max_it=DEFAULT_MAX_IT,
-                 precond=PC_JACOBI, amg_reuse=False, pattern=None, amg=None):
+                 precond=PC_JACOBI, amg_reuse=False, pattern=None, amg=None, scheme="backward_euler"):
         self.coords = np.ascontiguousarray(coords, dtype=np.float64)
         self.n = self.coords.shape[0]
         self.dt = float(dt)
@@ -56,6 +58,8 @@ class HeatProblem:
         self.rtol, self.atol, self.max_it = float(rtol), float(atol), int(max_it)
         self.assembly_mode = assembly_mode
         self.precond = precond
+        self.scheme = scheme
+        scheme_code = time_scheme_code(scheme)     # (an unknown name raises before any backend call)
         self.backend = backend if backend is not None else HeatflowHIP(device_id)
         self._own_backend = backend is None
 
@@ -73,6 +77,8 @@ class HeatProblem:
             self._owner = self._pos = np.zeros(0, dtype=np.int64)
         self.backend.set_dirichlet(self.bc_dofs)
         self.backend.set_precond(precond, amg_reuse)
+        if scheme_code != 0:     # backward Euler is every context's default: its path makes no extra call
+            self.backend.set_time_scheme(scheme_code)
         if amg is not None and precond == PC_AMG and amg_reuse:
             self.backend.amg_install(amg)
         self.backend.assemble(self.dt, self.assembly_mode)
@@ -202,7 +208,8 @@ class HeatProblem:
         return self.backend.get_state(), it, res
 
     def set_load(self, F):
-        """Load term of every following step, b = M u^n + dt F (n values); None removes it."""
+        """Load term of every following step, b = M u^n + dt F (BDF2: M (4/3 u^n - 1/3 u^{n-1}) + 2/3 dt F; n values); None
+        removes it."""
         self.backend.set_load(None if F is None else np.asarray(F, dtype=np.float64))
 
     def hold_load(self):

@@ -27,6 +27,8 @@
  *   hf_set_load        the load term dt * f * v * r * dx of build_variational_forms  space/space_and_forms.py:77-117;
  *                      b_equiv uploaded as it stands                    with_ir_steady.ipynb cells 18, 22
  *   hf_hold_load       b_equiv = A_free . u_ss with the transient's Dirichlet rows zeroed   with_ir_steady.ipynb cell 18
+ *   hf_set_time_scheme no counterpart: the reference steps with backward Euler only (run_with_diamond.py:321-337);
+ *                      HF_TIME_BDF2 is the second-order alternative
  *   hf_tangent_setup / hf_run_tangent / hf_get_tangent   no counterpart: the reference fits by re-running the forward model
  *                      over a grid (sweep_test.py:47-75, parameter_sweep.py:195-235); these give the derivatives of a run
  *
@@ -134,6 +136,26 @@ int hf_set_dirichlet(hf_ctx* ctx, int32_t n_bc, const int32_t* dofs);
  * zeroed with unit diagonal (the lifting columns are kept aside) and D^-1 is formed. */
 int hf_assemble(hf_ctx* ctx, double dt, int32_t mode);
 
+/* Time scheme of every transient loop (hf_step, hf_run, the batched loop, tangent runs):
+ *   HF_TIME_BACKWARD_EULER (default)  A u^{n+1} = M u^n + dt F,                       A = M + dt K
+ *   HF_TIME_BDF2                      A' u^{n+1} = M (4/3 u^n - 1/3 u^{n-1}) + dt' F,  A' = M + dt' K, dt' = 2 dt / 3
+ *                                     (the constant-step BDF2 formula (3/2 M + dt K) u^{n+1} = 2 M u^n - 1/2 M u^{n-1} + dt F
+ *                                     divided by 3/2; lifting and set_bc as before, with A').
+ * Call before hf_assemble, which keeps taking the real step dt and, under BDF2, assembles A' - so hf_get_csr / hf_spmv then
+ * return A' = M + (2/3) dt K (Dirichlet-eliminated), hf_update_kappa / hf_batch_set_affine re-value A' and the affine part is
+ * dt' K.  A change of scheme invalidates the assembly (hf_step, hf_run, hf_batch_begin / hf_batch_run, hf_run_tangent return
+ * HF_ERR_STATE until the next hf_assemble) and closes an open batch; setting the current scheme again changes nothing.  The
+ * multigrid fingerprint includes the scheme: a hierarchy built for one scheme meets the other's operator as a frozen one.
+ * History: u^{n-1} is kept under BDF2 whatever the start-vector kind.  hf_set_state, hf_steady_solve, hf_assemble (hence
+ * hf_update_kappa), hf_batch_begin and hf_tangent_setup / the tangent resets start it at rest, u^{-1} = u^n (s^{-1} = s^0 = 0
+ * for tangents): exact for a uniform initial state and for a held steady state.  hf_batch_set_state(j) sets column j's
+ * history to its new state.  A second hf_run / hf_batch_run / hf_run_tangent continues with the true u^{n-1}.
+ * Start vectors under BDF2: kinds 0, 1 and 3 as documented; kind 2's response correction assumes the one-step recursion of
+ * backward Euler and is not used - kind 2 runs as kind 1.  The boundary responses stay in kind 3's projection basis.
+ * HF_ERR_ARG for an unknown scheme. */
+enum { HF_TIME_BACKWARD_EULER = 0, HF_TIME_BDF2 = 1 };
+int hf_set_time_scheme(hf_ctx* ctx, int32_t scheme);
+
 /* Preconditioner of the PCG solve: kind 0 = Jacobi (D^-1, the north-star path), kind 1 =
  * smoothed-aggregation multigrid V(1,1) with damped-Jacobi smoothing, built on the host from the
  * assembled operator at hf_assemble time and applied on the GPU with CSR SpMV kernels.  With
@@ -183,7 +205,7 @@ int hf_set_state(hf_ctx* ctx, const double* u);
 int hf_get_state(hf_ctx* ctx, double* u);
 int hf_sample(hf_ctx* ctx, int32_t n_s, const int32_t* nodes, double* out);
 
-/* One backward-Euler step: b = M u^n - A[:,B] g, b_B = g, solve A_hat u^{n+1} = b by
+/* One time step (backward Euler; see hf_set_time_scheme for BDF2): b = M u^n - A[:,B] g, b_B = g, solve A_hat u^{n+1} = b by
  * Jacobi-PCG started from u^n (with u_B = g), in place.  Stops when
  * ||D^-1 r||_2 <= max(rtol * ||D^-1 b||_2, atol)  (a zero right-hand side - the answer is then zero - is measured
  * against the start residual instead).  iters / resid (relative) may be NULL. */
