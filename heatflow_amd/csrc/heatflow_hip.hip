@@ -84,6 +84,12 @@ void tangent_free(hf_ctx* ctx) {
   ctx->tan = hf_ctx::Tangent();
 }
 
+void kt_free(hf_ctx* ctx) {
+  hf_ctx::KappaT& K = ctx->kt;
+  dev_free(&K.hdr); dev_free(&K.vals); dev_free(&K.pic); dev_free(&K.b0); dev_free(&K.change);
+  K = hf_ctx::KappaT();
+}
+
 // Upload the tables and size every buffer of the context for the mesh.
 int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int32_t* tri, const int32_t* tag, MeshTables& T) {
   free_batch(ctx);
@@ -93,6 +99,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   steady_free(ctx);
   load_free(ctx);
   tangent_free(ctx);
+  kt_free(ctx);
   ctx->n = n; ctx->ne = ne; ctx->nnz = static_cast<int64_t>(T.colidx.size());
   ctx->nchunks = (n + RB - 1) / RB;
   ctx->nblk_a = (n + RBA - 1) / RBA;
@@ -610,7 +617,7 @@ int hf_destroy(hf_ctx* ctx) {
   dev_free(&ctx->d_uprev); dev_free(&ctx->d_ustart);
   dev_free(&ctx->d_u); dev_free(&ctx->d_b); dev_free(&ctx->d_r); dev_free(&ctx->d_p); dev_free(&ctx->d_Ap);
   free_batch(ctx); free_batch_state(ctx->fluxb); free_batch_cols(ctx); free_amg(ctx); free_responses(ctx); proj_free(ctx); dev_free(&ctx->d_z); dev_free(&ctx->d_z2);
-  steady_free(ctx); load_free(ctx); tangent_free(ctx);
+  steady_free(ctx); load_free(ctx); tangent_free(ctx); kt_free(ctx);
   dev_free(&ctx->d_M1); dev_free(&ctx->d_dinv1); dev_free(&ctx->d_gz); dev_free(&ctx->d_gr); dev_free(&ctx->d_bz); dev_free(&ctx->d_br);
   dev_free(&ctx->d_tmp); dev_free(&ctx->d_part_pAp); dev_free(&ctx->d_part_rz); dev_free(&ctx->d_part_zz);
   dev_free(&ctx->d_part_bn); dev_free(&ctx->d_scal); dev_free(&ctx->d_samp_idx); dev_free(&ctx->d_samp); dev_free(&ctx->d_fsamp_idx);
@@ -727,6 +734,10 @@ int hf_update_kappa(hf_ctx* ctx, int32_t n_mat, const int32_t* tags, const doubl
     if (tags[i] < 0 || tags[i] >= ctx->tab_len || !ctx->h_tag_used[tags[i]])
       return fail(ctx, HF_ERR_ARG, "hf_update_kappa: tag %d is not a cell tag of the mesh", tags[i]);
     if (!(kappa[i] > 0.0)) return fail(ctx, HF_ERR_ARG, "hf_update_kappa: kappa must be positive");
+    if (ctx->kt.on && ctx->kt.tabled[tags[i]])
+      return fail(ctx, HF_ERR_ARG, "hf_update_kappa: tag %d carries a kappa(T) table (hf_set_kappa_tables)", tags[i]);
+  }
+  for (int32_t i = 0; i < n_mat; ++i) {
     tk[tags[i]] = kappa[i];
   }
   HF_HIP(copy_sync(ctx, ctx->d_kappa, tk.data(), sizeof(double) * ctx->tab_len, hipMemcpyHostToDevice));
@@ -763,21 +774,28 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
   if (!ctx->have_mesh || !ctx->have_mat) return fail(ctx, HF_ERR_STATE, "hf_assemble needs hf_set_mesh and hf_set_materials first");
   if (!(dt > 0.0)) return fail(ctx, HF_ERR_ARG, "hf_assemble: dt must be positive");
   if (mode < 0 || mode > 3) return fail(ctx, HF_ERR_ARG, "hf_assemble: unknown mode %d", mode);
+  if (ctx->kt.on && mode != HF_ASM_ROW_GATHER)
+    return fail(ctx, HF_ERR_ARG, "hf_assemble: kappa(T) tables are evaluated by the row-gather kernel only (HF_ASM_ROW_GATHER)");
   HF_HIP(hipSetDevice(ctx->dev));
   ctx->dt_step = dt;
   ctx->dt = ctx->scheme == HF_TIME_BDF2 ? 2.0 * dt / 3.0 : dt;   // BDF2: A' = M + (2/3) dt K
   ctx->mode = mode;
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   HF_TRY(launch_assemble(ctx));
-  if (ctx->nbc > 0) {
-    if (ctx->nlift > 0)
-      hipLaunchKernelGGL(k_take_lift, dim3((ctx->nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift,
-                         ctx->d_lift_slot, ctx->d_A, ctx->d_lift_val);
-    hipLaunchKernelGGL(k_bc_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs,
-                       ctx->d_rowptr, ctx->d_colidx, ctx->d_A);
+  if (ctx->kt.on) {
+    // kappa(T): M as assembled above, A re-valued at the current state, then elimination, lifting values and D^-1
+    HF_TRY(kt_revalue(ctx, ctx->d_u, nullptr));
+  } else {
+    if (ctx->nbc > 0) {
+      if (ctx->nlift > 0)
+        hipLaunchKernelGGL(k_take_lift, dim3((ctx->nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift,
+                           ctx->d_lift_slot, ctx->d_A, ctx->d_lift_val);
+      hipLaunchKernelGGL(k_bc_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs,
+                         ctx->d_rowptr, ctx->d_colidx, ctx->d_A);
+    }
+    hipLaunchKernelGGL(k_dinv, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr,
+                       ctx->d_colidx, ctx->d_A, ctx->d_dinv);
   }
-  hipLaunchKernelGGL(k_dinv, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr,
-                     ctx->d_colidx, ctx->d_A, ctx->d_dinv);
   HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
   HF_HIP(hipGetLastError());
   HF_HIP(hipStreamSynchronize(ctx->stream));
@@ -793,7 +811,7 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
     } else {
       // hierarchy kept (reuse) or installed from another context (hf_amg_install): its fused fine-level operators hold the
       // operator it was built from - usable only if that is this one
-      ctx->amg_fine_stale = !same_print(now, ctx->amg_print);
+      ctx->amg_fine_stale = !same_print(now, ctx->amg_print) || ctx->kt.on;   // (kappa(T): built from A at another state)
     }
   }
   if (ctx->precond == 1 && ctx->amg_ready) {  // level 0 aliases the fine operator: refresh its pointers
@@ -828,6 +846,75 @@ int hf_set_time_scheme(hf_ctx* ctx, int32_t scheme) {
     ctx->pred_iters = 0;
     ctx->scheme = scheme;
   }
+  return HF_OK;
+}
+
+int hf_set_kappa_tables(hf_ctx* ctx, int32_t n_tab, const int32_t* tags, const double* t0, const double* dT, const int32_t* n_knots,
+                        const double* values, int32_t picard_sweeps) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_set_kappa_tables before hf_set_mesh");
+  if (n_tab < 0) return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: negative table count");
+  HF_HIP(hipSetDevice(ctx->dev));
+  if (n_tab == 0) {   // clear: every path is the constant-kappa one again
+    if (ctx->kt.on) {
+      free_batch(ctx);
+      ctx->assembled = false;
+      ctx->pred_iters = 0;
+    }
+    kt_free(ctx);
+    return HF_OK;
+  }
+  if (!tags || !t0 || !dT || !n_knots || !values) return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: null pointer");
+  if (picard_sweeps < 1 || picard_sweeps > KT_MAX_PICARD)
+    return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: picard_sweeps %d outside 1..%d", picard_sweeps, KT_MAX_PICARD);
+  if (!ctx->rg_ok || (ctx->assembled && ctx->mode != HF_ASM_ROW_GATHER))
+    return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: kappa(T) is evaluated by the row-gather kernel only (HF_ASM_ROW_GATHER on a mesh with row-gather lists)");
+  std::vector<KTab> hdr(64, KTab{0.0, 0.0, 0, 0});
+  std::vector<double> vals;
+  std::vector<char> tabled(ctx->tab_len, 0);
+  for (int32_t i = 0; i < n_tab; ++i) {
+    const int32_t tg = tags[i];
+    if (tg < 0 || tg >= ctx->tab_len || !ctx->h_tag_used[tg]) return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: tag %d is not a cell tag of the mesh", tg);
+    if (tabled[tg]) return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: tag %d listed twice", tg);
+    if (n_knots[i] < 2 || n_knots[i] > KT_MAX_KNOTS)
+      return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: table of tag %d has %d knots (2..%d)", tg, n_knots[i], KT_MAX_KNOTS);
+    if (!std::isfinite(t0[i]) || !(dT[i] > 0.0) || !std::isfinite(dT[i]) || !std::isfinite(t0[i] + (n_knots[i] - 1) * dT[i]))
+      return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: table of tag %d: T0 finite and dT > 0 needed", tg);
+    tabled[tg] = 1;
+    const size_t q = std::find(ctx->h_rg_tags.begin(), ctx->h_rg_tags.end(), tg) - ctx->h_rg_tags.begin();
+    if (q >= ctx->h_rg_tags.size()) return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: tag %d has no row-gather dictionary entry", tg);
+    hdr[q] = KTab{t0[i], 1.0 / dT[i], n_knots[i], static_cast<int>(vals.size())};
+    for (int32_t k = 0; k < n_knots[i]; ++k) {     // values: the tables' knots concatenated in the order of `tags`
+      const double v = values[vals.size()];
+      if (!(v > 0.0) || !std::isfinite(v)) return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: value %d of the table of tag %d is not positive and finite", k, tg);
+      vals.push_back(v);
+    }
+  }
+  kt_free(ctx);
+  free_batch(ctx);
+  hf_ctx::KappaT& K = ctx->kt;
+  HF_TRY(dev_alloc(ctx, &K.hdr, 64));
+  HF_TRY(dev_alloc(ctx, &K.vals, vals.size()));
+  HF_TRY(dev_alloc(ctx, &K.pic, ctx->n));
+  HF_TRY(dev_alloc(ctx, &K.b0, ctx->n));
+  HF_TRY(dev_alloc(ctx, &K.change, 1));
+  HF_HIP(copy_sync(ctx, K.hdr, hdr.data(), sizeof(KTab) * 64, hipMemcpyHostToDevice));
+  HF_HIP(copy_sync(ctx, K.vals, vals.data(), sizeof(double) * vals.size(), hipMemcpyHostToDevice));
+  K.tabled = std::move(tabled);
+  K.picard = picard_sweeps;
+  K.on = true;
+  ctx->assembled = false;
+  ctx->pred_iters = 0;
+  return HF_OK;
+}
+
+int hf_get_picard_change(hf_ctx* ctx, double* max_du) {
+  if (!ctx || !max_du) return HF_ERR_ARG;
+  if (!ctx->kt.on || !ctx->kt.have_change) return fail(ctx, HF_ERR_STATE, "hf_get_picard_change: no step with kappa(T) tables since they were set");
+  HF_HIP(hipSetDevice(ctx->dev));
+  unsigned long long bits = 0;
+  HF_HIP(copy_sync(ctx, &bits, ctx->kt.change, sizeof bits, hipMemcpyDeviceToHost));
+  std::memcpy(max_du, &bits, sizeof bits);
   return HF_OK;
 }
 
@@ -1135,7 +1222,7 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   for (int32_t s = 0; s < n_steps && rc == HF_OK; ++s) {
     rc = step_device(ctx, ctx->nbc > 0 ? g_all + static_cast<size_t>(s) * ctx->nbc : nullptr,
-                     ctx->nbc > 0 ? d_gall + static_cast<size_t>(s) * ctx->nbc : nullptr, rtol, atol, max_it);
+                     ctx->nbc > 0 ? d_gall + static_cast<size_t>(s) * ctx->nbc : nullptr, rtol, atol, max_it, s == n_steps - 1);
     if (iters) iters[s] = ctx->h_scal->iters;
     if (ns > 0 && rc == HF_OK)
       hipLaunchKernelGGL(k_gather, dim3((ns + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, ctx->d_u,
@@ -1153,6 +1240,7 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
 int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup before hf_set_mesh");
+  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: kappa(T) tables are set (tangents of the nonlinear loop are not supported)");
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a batch is open");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a load is set (tangents of pre-heated runs are not supported)");
   if (n_par < 1 || n_par > NV_MAX) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: 1..%d parameters (got %d)", NV_MAX, n_par);
@@ -1190,6 +1278,7 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
                    int32_t ns, const int32_t* nodes, double* samples, int32_t* iters, double* tangent_samples, int32_t* tangent_iters) {
   if (!ctx) return HF_ERR_ARG;
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a batch is open");
+  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: kappa(T) tables are set (tangents of the nonlinear loop are not supported)");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a load is set (tangents of pre-heated runs are not supported)");
   if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_run_tangent before hf_tangent_setup");
   if (ctx->tan.steady_state)
@@ -1277,6 +1366,7 @@ int hf_get_tangent(hf_ctx* ctx, int32_t j, double* s) {
 int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t precond) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->have_mesh || !ctx->have_mat) return fail(ctx, HF_ERR_STATE, "hf_steady_setup needs hf_set_mesh and hf_set_materials first");
+  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_steady_setup: kappa(T) tables are set (a Picard steady state is not supported)");
   if (n_s <= 0 || !dofs) return fail(ctx, HF_ERR_ARG, "hf_steady_setup: empty Dirichlet set (the stiffness alone is singular)");
   if (precond < 0 || precond > 1) return fail(ctx, HF_ERR_ARG, "hf_steady_setup: unknown preconditioner %d", precond);
   if (!ctx->rg_ok || (ctx->assembled && ctx->mode != HF_ASM_ROW_GATHER))
@@ -1328,6 +1418,7 @@ int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t preco
 int hf_steady_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, double rtol, double atol, int32_t max_it, int32_t* iters,
                     double* resid) {
   if (!ctx) return HF_ERR_ARG;
+  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_steady_solve: kappa(T) tables are set (a Picard steady state is not supported)");
   if (!ctx->steady.ready) return fail(ctx, HF_ERR_STATE, "hf_steady_solve before hf_steady_setup (or the materials changed since)");
   if (!g_s) return fail(ctx, HF_ERR_ARG, "hf_steady_solve: g_S is null");
   if (max_it <= 0 || rtol < 0 || atol < 0) return fail(ctx, HF_ERR_ARG, "hf_steady_solve: bad tolerances");
@@ -1421,6 +1512,7 @@ int hf_hold_load(hf_ctx* ctx) {
 
 int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
   if (!ctx) return HF_ERR_ARG;
+  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_batch_begin: kappa(T) tables are set (batched sweeps of the nonlinear loop are not supported)");
   if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_batch_begin before hf_assemble");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_batch_begin: a load is set (the batched loop has no load term; hf_set_load(NULL) first)");
   if (nv != 2 && nv != 4 && nv != 8 && nv != 16) return fail(ctx, HF_ERR_ARG, "hf_batch_begin: 2, 4, 8 or 16 columns (got %d)", nv);

@@ -94,6 +94,12 @@ struct Scal {                  // device-resident PCG scalars
 constexpr int NV_MAX = 16;    // columns of the widest batch
 struct BRed { double pAp[NV_MAX], rz[2][NV_MAX], zz[NV_MAX], bn[NV_MAX]; };
 
+// Conductivity table of one tag-dictionary entry (hf_set_kappa_tables): kappa(T) piecewise linear on the uniform grid
+// t0 + i / inv_dt, i = 0..n-1, values vals[off + i], clamped to the end values outside it; n = 0: no table
+constexpr int KT_MAX_KNOTS = 256;
+constexpr int KT_MAX_PICARD = 8;
+struct KTab { double t0, inv_dt; int n, off; };
+
 }  // namespace
 
 struct hf_ctx {
@@ -305,6 +311,19 @@ struct hf_ctx {
     std::vector<int64_t> lev_sig;   // multigrid level sizes tanb.lev was laid out for
   } tan;
   int fsamp_cap = 0;
+  // temperature-dependent conductivities (hf_set_kappa_tables): per row-gather tag-dictionary entry a table header (KTab,
+  // n = 0: the constant of d_kappa_rg) and one value array; every step re-values A at the evaluation state (k_assemble_rows_kT)
+  struct KappaT {
+    bool on = false;
+    int picard = 1;
+    KTab* hdr = nullptr;          // 64 entries
+    double* vals = nullptr;
+    std::vector<char> tabled;     // by cell tag: the tag carries a table
+    double *pic = nullptr, *b0 = nullptr;   // evaluation state of the last sweep (for the change), b before lifting (sweeps > 1)
+    unsigned long long* change = nullptr;   // max |u^{n+1,p} - u^{n+1,p-1}| of the last step's last sweep (bits of a double >= 0)
+    bool have_change = false;
+    int grid = 0;
+  } kt;
   // optional in-situ kernel timing (hf_set_profile): event pairs around each PCG SpMV launch
   bool prof = false;
   std::vector<hipEvent_t> prof_ev;

@@ -484,6 +484,148 @@ __global__ __launch_bounds__(RBA) void k_tangent_load(int nblk, int capd, const 
   }
 }
 
+// kappa(T) of one table (KTab): s = (T - t0) / dT, clamped to the end values, else v_i + (s - i) (v_{i+1} - v_i), i = floor(s)
+__device__ __forceinline__ double ktab_eval(const KTab h, const double* __restrict__ vals, double T) {
+#pragma clang fp contract(off)
+  const double s = (T - h.t0) * h.inv_dt;
+  if (!(s > 0.0)) return vals[h.off];
+  if (s >= static_cast<double>(h.n - 1)) return vals[h.off + h.n - 1];
+  const int i = min(static_cast<int>(s), h.n - 2);
+  const double a = vals[h.off + i], b = vals[h.off + i + 1];
+  return a + (s - static_cast<double>(i)) * (b - a);
+}
+
+// Re-valuation of A = M + dt K(kappa(T)) at an evaluation state u* (hf_set_kappa_tables): the lists, staging, persistent
+// workgroups and summation order of k_assemble_rows<false>, plus the block's slice of u* staged next to the coordinates (as
+// k_grad_rows stages u).  u* = u, or 2 u - uprev when uprev is given (BDF2's extrapolated state).  Per triangle
+// T_e = ((lo + mid) + hi) / 3 of its three sorted nodal values - the same bits from each vertex's point of view, so A stays
+// exactly symmetric - and kappa_e = table(T_e) for a tabled tag, the constant kappa_idx otherwise.  M does not change: only
+// A is written, and a constant table gives A bit for bit as k_assemble_rows does.
+__global__ __launch_bounds__(RBA) void k_assemble_rows_kT(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
+                                                          const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
+                                                          const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
+                                                          const double2* __restrict__ zrb, const int32_t* __restrict__ dict,
+                                                          const KTab* __restrict__ ktab, const double* __restrict__ kvals,
+                                                          const double* __restrict__ kappa_idx, const double* __restrict__ rhoc_idx,
+                                                          double dt, const double* __restrict__ u, const double* __restrict__ uprev,
+                                                          double* __restrict__ Av) {
+  extern __shared__ double smem[];
+  __shared__ KTab sK[64];
+  double* sA = smem;                                                 // A per slot
+  double2* sXd = reinterpret_cast<double2*>(sA + cap);               // coordinates of the block's column list
+  double* sU = reinterpret_cast<double*>(sXd + capd);                // u* on the block's column list
+  int* sR = reinterpret_cast<int*>(sU + capd + (capd & 1));          // row starts inside the slab
+  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);               // column-list position per slot, from the 8-aligned start
+  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
+
+  const int t = threadIdx.x;
+  if (t < 64) sK[t] = ktab[t];
+  for (int k = t; k < cap; k += RBA) sA[k] = 0.0;
+
+  int4 hA, hB;
+  uint4 pe, pc[RG_NC];
+  double2 px[RG_NX];
+  double pu[RG_NX];
+  int pr = 0;
+  auto prefetch = [&](int blk) {
+#pragma clang fp contract(off)
+    hA = hdr[2 * blk];
+    hB = hdr[2 * blk + 1];
+    pe = ell[hB.x + t];
+    const int c0 = hA.x >> 3, nc = ((hA.x + hA.y + 7) >> 3) - c0;
+#pragma unroll
+    for (int q = 0; q < RG_NC; ++q) pc[q] = (t + q * RBA < nc) ? cid16[c0 + t + q * RBA] : make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int q = 0; q < RG_NX; ++q) {
+      const bool in = t + q * RBA < hA.w;
+      px[q] = in ? zrb[hA.z + t + q * RBA] : make_double2(0.0, 0.0);
+      const int node = in ? dict[hA.z + t + q * RBA] : 0;
+      pu[q] = !in ? 0.0 : uprev ? 2.0 * u[node] - uprev[node] : u[node];
+    }
+    pr = (t < hB.w) ? rowptr[blk * RBA + t] - hA.x : 0;
+  };
+  int blk = blockIdx.x;
+  if (blk < nblk) prefetch(blk);
+  while (blk < nblk) {
+    const int4 cA = hA, cB = hB;
+    const uint4 ce = pe;
+    const int nc = ((cA.x + cA.y + 7) >> 3) - (cA.x >> 3);
+#pragma unroll
+    for (int q = 0; q < RG_NC; ++q) if (t + q * RBA < nc) sC4[t + q * RBA] = pc[q];
+#pragma unroll
+    for (int q = 0; q < RG_NX; ++q) if (t + q * RBA < cA.w) { sXd[t + q * RBA] = px[q]; sU[t + q * RBA] = pu[q]; }
+    sR[t] = pr;
+    __syncthreads();
+    const int nxt = blk + gridDim.x;
+    if (nxt < nblk) prefetch(nxt);
+
+    if (t < cB.w) {
+      const int base = sR[t];
+      const int sbase = base + (cA.x & 7);
+      const int ci = cB.z + t;
+      const double2 Pi = sXd[ci];
+      const double ui = sU[ci];
+      double dA = 0.0;
+      int pd = 0;
+      while (pd < 31 && sC[sbase + pd] < ci) ++pd;
+      for (int g = 0; g < cB.y; ++g) {
+        const uint4 ev = g == 0 ? ce : ell[cB.x + g * RBA + t];
+        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
+          if (e == 0xFFFFu) continue;
+          const int pj = e & 31u, pk = (e >> 5) & 31u, tg = e >> 10;
+          const int cj = sC[sbase + pj], ck = sC[sbase + pk];
+          const double2 Pj = sXd[cj], Pk = sXd[ck];
+          const KTab kh = sK[tg];
+          double kappa = kappa_idx[tg];
+          if (kh.n > 0) {
+#pragma clang fp contract(off)
+            const double uj = sU[cj], uk = sU[ck];
+            const double ab_lo = fmin(ui, uj), ab_hi = fmax(ui, uj);
+            const double lo = fmin(ab_lo, uk), hi = fmax(ab_hi, uk), mid = fmax(ab_lo, fmin(ab_hi, uk));
+            kappa = ktab_eval(kh, kvals, ((lo + mid) + hi) * (1.0 / 3.0));
+          }
+          const ElemRow r = element_row(Pi, Pj, Pk, rhoc_idx[tg], kappa);
+          dA += fma(dt, r.k0, r.m0);
+          sA[base + pj] += fma(dt, r.k1, r.m1);
+          sA[base + pk] += fma(dt, r.k2, r.m2);
+        }
+      }
+      sA[base + pd] = dA;
+    }
+    __syncthreads();
+    for (int k = t; k < cA.y; k += RBA) {
+      Av[cA.x + k] = sA[k];
+      sA[k] = 0.0;
+    }
+    blk = nxt;
+  }
+}
+
+// max |a - b| over n entries into *out (the bits of a double >= 0, which order as unsigned integers; *out zeroed before)
+__global__ __launch_bounds__(TPB) void k_max_abs_diff(int n, const double* __restrict__ a, const double* __restrict__ b,
+                                                      unsigned long long* __restrict__ out) {
+  __shared__ double s[TPB];
+  double m = 0.0;
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) m = fmax(m, fabs(a[i] - b[i]));
+  s[threadIdx.x] = m;
+  __syncthreads();
+  for (int h = TPB / 2; h > 0; h >>= 1) {
+    if (threadIdx.x < h) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + h]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) atomicMax(out, static_cast<unsigned long long>(__double_as_longlong(s[0])));
+}
+
+// u* = u, or 2 u - uprev (the evaluation state of k_assemble_rows_kT, kept for the Picard change)
+__global__ __launch_bounds__(TPB) void k_eval_state(int n, const double* __restrict__ u, const double* __restrict__ uprev,
+                                                    double* __restrict__ out) {
+#pragma clang fp contract(off)
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) out[i] = uprev ? 2.0 * u[i] - uprev[i] : u[i];
+}
+
 // per-block copy of the coordinates of each block's column list (hf_set_mesh, once)
 __global__ void k_gather_coords(int64_t total, const int32_t* __restrict__ dict, const double2* __restrict__ zr,
                                 double2* __restrict__ zrb) {

@@ -755,19 +755,84 @@ void launch_rhs_bdf2(hf_ctx* ctx, bool extrap) {
   }
 }
 
+// kappa(T): A = M + dt K(kappa(T_e)) at the evaluation state u (or 2 u - uprev) by the row-gather kernel, then the Dirichlet
+// elimination, the lifting values and D^-1 as hf_assemble forms them - all on the stream, no host synchronisation.  The
+// hierarchy (if any) stays the one hf_assemble built: its fused fine-level legs hold the old operator from here on.
+int kt_revalue(hf_ctx* ctx, const double* u, const double* uprev) {
+  const int cap = (ctx->max_blk_nnz + 1) & ~1;
+  const int capd = ctx->rg_max_dict;
+  const size_t sm = static_cast<size_t>(cap) * 8 + static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 +
+                    (RBA + 4) * 4 + (static_cast<size_t>(cap) / 8 + 3) * 16;
+  if (ctx->kt.grid == 0) {   // persistent workgroups: as many as fit the chip at this LDS footprint
+    const void* fn = reinterpret_cast<const void*>(&k_assemble_rows_kT);
+    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
+    int per_cu = 0, ncu = 0;
+    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
+    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
+    ctx->kt.grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+  }
+  hipLaunchKernelGGL(k_assemble_rows_kT, dim3(ctx->kt.grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr,
+                     ctx->d_rg_hdr, reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid),
+                     ctx->d_rg_zrb, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev,
+                     ctx->d_A);
+  if (ctx->nbc > 0) {
+    if (ctx->nlift > 0)
+      hipLaunchKernelGGL(k_take_lift, dim3((ctx->nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift, ctx->d_lift_slot, ctx->d_A,
+                         ctx->d_lift_val);
+    hipLaunchKernelGGL(k_bc_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs, ctx->d_rowptr,
+                       ctx->d_colidx, ctx->d_A);
+  }
+  hipLaunchKernelGGL(k_dinv, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr, ctx->d_colidx, ctx->d_A,
+                     ctx->d_dinv);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+// The solve of a step on the current operator, with the Jacobi fallback after a multigrid breakdown
+int step_solve(hf_ctx* ctx, double rtol, double atol, int max_it) {
+  const LinSys sys{ctx->d_A, ctx->d_dinv, ctx->d_u, ctx->d_b};
+  const bool use_amg = ctx->precond == 1 && ctx->amg_ready;
+  int rc = pcg_solve(ctx, sys, use_amg, rtol, atol, max_it, &ctx->pred_iters);
+  if (rc == HF_ERR_NOCONV && use_amg && ctx->h_scal->done == 2) {
+    // breakdown inside the multigrid-preconditioned loop (p.Ap <= 0: the preconditioner was not SPD for
+    // this operator): finish the step with the Jacobi preconditioner from the current iterate - still on
+    // the GPU - and count the event
+    ctx->amg_fallbacks += 1;
+    int pred = 0;
+    rc = pcg_solve(ctx, sys, false, rtol, atol, max_it, &pred);
+  }
+  return rc;
+}
+
 // One time step to the boundary values g_host (n_bc doubles on the host; g_dev = the same values already on
-// the device, or null).  Leaves iteration count / residual in h_scal.
-int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double rtol, double atol, int max_it) {
+// the device, or null).  Leaves iteration count / residual in h_scal (kappa(T): the iterations of all Picard sweeps).
+// last: the step whose Picard change hf_get_picard_change reports (kappa(T) only).
+int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double rtol, double atol, int max_it, bool last = true) {
   const int nb = ctx->nbc;
   RespArgs ra{};
   ra.k = 0;
-  const bool projected = ctx->start_kind == 3;
+  const bool kt = ctx->kt.on;
+  // kappa(T): kinds 2 and 3 assume one operator for the whole run (the boundary responses and the projection basis solve
+  // with it) - under tables they run as kind 1; kind 0 stays
+  const int kind = kt && ctx->start_kind >= 2 ? 1 : ctx->start_kind;
+  const bool projected = kind == 3;
   const bool bdf2 = ctx->scheme == HF_TIME_BDF2;
   if (projected) HF_TRY(proj_ensure(ctx));
   const bool hist_ok = nb > 0 && ctx->extrapolate && ctx->have_prev && ctx->g_hist >= 2;
   // (BDF2: kind 2's correction assumes backward Euler's one-step recursion - kind 2 runs as kind 1; kind 3 keeps the
   // responses as basis vectors: each solves A' w = f with a known f, whatever the scheme)
-  if (ctx->start_kind >= 2 && hist_ok && !(bdf2 && ctx->start_kind == 2)) HF_TRY(prepare_response(ctx, g_host, max_it, &ra));
+  if (kind >= 2 && hist_ok && !(bdf2 && kind == 2)) HF_TRY(prepare_response(ctx, g_host, max_it, &ra));
+  const int sweeps = kt ? ctx->kt.picard : 1;
+  const bool track = kt && last;   // the Picard change of this step is kept
+  if (kt) {
+    // the first sweep evaluates at u^n (backward Euler) or 2 u^n - u^{n-1} (BDF2 with a history), before the right-hand side's
+    // pass moves the state buffers
+    const double* um1 = bdf2 && ctx->bdf_hist ? ctx->d_uprev : nullptr;
+    HF_TRY(kt_revalue(ctx, ctx->d_u, um1));
+    if (ctx->precond == 1 && ctx->amg_ready) ctx->amg_fine_stale = true;
+    if (track && sweeps == 1)
+      hipLaunchKernelGGL(k_eval_state, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u, um1, ctx->kt.pic);
+  }
   const double* g = g_dev ? g_dev : ctx->d_g;   // hf_run has every step's boundary values on the device already
   if (nb > 0 && !g_dev) HF_HIP(hipMemcpyAsync(ctx->d_g, g_host, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
   if (bdf2 && (projected || !ctx->extrapolate)) {
@@ -809,6 +874,8 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
     }
   }
   const bool combine = projected && proj_active(ctx).m > 0;
+  if (sweeps > 1)   // b before lifting: the same for every sweep of the step
+    HF_HIP(hipMemcpyAsync(ctx->kt.b0, ctx->d_b, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
   if (nb > 0) {
     if (ctx->nlift_rows > 0)  // apply_lifting (:477)
       hipLaunchKernelGGL(k_lift, dim3((ctx->nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift_rows,
@@ -827,16 +894,30 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
     if (nb > 0)
       hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, g, ctx->d_b, ctx->d_u);
   }
-  const LinSys sys{ctx->d_A, ctx->d_dinv, ctx->d_u, ctx->d_b};
-  const bool use_amg = ctx->precond == 1 && ctx->amg_ready;
-  int rc = pcg_solve(ctx, sys, use_amg, rtol, atol, max_it, &ctx->pred_iters);
-  if (rc == HF_ERR_NOCONV && use_amg && ctx->h_scal->done == 2) {
-    // breakdown inside the multigrid-preconditioned loop (p.Ap <= 0: the preconditioner was not SPD for
-    // this operator): finish the step with the Jacobi preconditioner from the current iterate - still on
-    // the GPU - and count the event
-    ctx->amg_fallbacks += 1;
-    int pred = 0;
-    rc = pcg_solve(ctx, sys, false, rtol, atol, max_it, &pred);
+  int rc = step_solve(ctx, rtol, atol, max_it);
+  if (kt) {
+    // Picard sweeps 2..p: re-evaluate at the latest iterate, lift with the new operator and solve again from that iterate
+    int total = ctx->h_scal->iters;
+    for (int k = 2; k <= sweeps && rc == HF_OK; ++k) {
+      if (track && k == sweeps)
+        HF_HIP(hipMemcpyAsync(ctx->kt.pic, ctx->d_u, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+      HF_TRY(kt_revalue(ctx, ctx->d_u, nullptr));
+      HF_HIP(hipMemcpyAsync(ctx->d_b, ctx->kt.b0, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+      if (nb > 0) {
+        if (ctx->nlift_rows > 0)
+          hipLaunchKernelGGL(k_lift, dim3((ctx->nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift_rows,
+                             ctx->d_lift_rows, ctx->d_lift_ptr, ctx->d_lift_bc, ctx->d_lift_val, g, ctx->d_b);
+        hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, g, ctx->d_b, ctx->d_u);
+      }
+      rc = step_solve(ctx, rtol, atol, max_it);
+      total += ctx->h_scal->iters;
+    }
+    ctx->h_scal->iters = total;
+    if (rc == HF_OK && track) {
+      HF_HIP(hipMemsetAsync(ctx->kt.change, 0, sizeof(unsigned long long), ctx->stream));
+      hipLaunchKernelGGL(k_max_abs_diff, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u, ctx->kt.pic, ctx->kt.change);
+      ctx->kt.have_change = true;
+    }
   }
   if (rc == HF_OK && projected) {   // the new solution and its right-hand side join the projection basis
     hf_ctx::Proj& Q = ctx->proj;

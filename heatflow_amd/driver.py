@@ -42,6 +42,7 @@ def _dump_yaml(obj, f):
 from .bc import P1Space, RowDirichletBC
 from .geometry import stack_no_diamond, stack_with_diamond
 from .heating import HeatingCurve
+from .kappa_t import material_table, picard_sweeps, refuse_tables
 from .mesh import Mesh, load_mesh_arrays
 from .solver import DEFAULT_MAX_IT, DEFAULT_RTOL, HeatProblem
 
@@ -167,9 +168,18 @@ def time_scheme(cfg):
 
 
 def _with_scheme(cfg):
-    """``cfg`` with the time scheme it runs with written out (``timing.scheme``), for used_config.yaml."""
+    """``cfg`` with the time scheme it runs with written out (``timing.scheme``), for used_config.yaml; with kappa(T) also
+    ``timing.picard_sweeps`` and the tables that ran (``kappa_tables``: {material: {T0, dT, k}})."""
     out = dict(cfg)
     out["timing"] = dict(cfg.get("timing") or {}, scheme=time_scheme(cfg))
+    tables = {}
+    for name, mat in sorted((cfg.get("mats") or {}).items()):
+        t = material_table(name, mat) if isinstance(mat, dict) else None
+        if t is not None:
+            tables[name] = {"T0": float(t[0]), "dT": float(t[1]), "k": [float(v) for v in t[2]]}
+    if tables:
+        out["timing"]["picard_sweeps"] = picard_sweeps(cfg)
+        out["kappa_tables"] = tables
     return out
 
 
@@ -229,13 +239,19 @@ class SimulationSession:
         bcs = self._boundary_conditions(cfg, stack)
         tag_to_k, tag_to_rc = self._tables(stack)
         scheme = time_scheme(cfg)
-        self._ensure_problem(self._problem_key(dt, tag_to_rc, bcs, scheme), tag_to_k, tag_to_rc, dt, bcs, float(cfg["heating"]["ic_temp"]),
-                             scheme)
+        kt = self._kappa_tables(cfg, stack)
+        self._ensure_problem(self._problem_key(dt, tag_to_rc, bcs, scheme, kt), tag_to_k, tag_to_rc, dt, bcs,
+                             float(cfg["heating"]["ic_temp"]), scheme, kt)
 
     def _tables(self, stack):
         tag_to_k = {self.material_tags[m.name]: m.properties["k"] for m in stack.materials}
         tag_to_rc = {self.material_tags[m.name]: m.properties["rho_cv"] for m in stack.materials}
         return tag_to_k, tag_to_rc
+
+    def _kappa_tables(self, cfg, stack):
+        """(tables {tag: (T0, dT, values)}, Picard sweeps) of a kappa(T) configuration, or None."""
+        tables = {self.material_tags[m.name]: m.properties["k_table"] for m in stack.materials if "k_table" in m.properties}
+        return (tables, picard_sweeps(cfg)) if tables else None
 
     def _boundary_conditions(self, cfg, stack, two_sided=False):
         """[left, right, top, heated line(s)] of one configuration (reference run_with_diamond.py:343-374)."""
@@ -268,13 +284,17 @@ class SimulationSession:
             self._heats.append(heat_o)
         return bcs
 
-    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler"):
+    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler", kt=None):
         # the resident problem is reusable only for exactly the same Dirichlet DOF sets, in the same order, and time scheme
-        return (dt, tuple(sorted(tag_to_rc.items())),
-                tuple(hashlib.sha1(np.ascontiguousarray(b.row_dofs, dtype=np.int64).tobytes()).hexdigest() for b in bcs),
-                scheme)
+        # (and kappa(T) tables and Picard sweeps, when a configuration has them)
+        key = (dt, tuple(sorted(tag_to_rc.items())),
+               tuple(hashlib.sha1(np.ascontiguousarray(b.row_dofs, dtype=np.int64).tobytes()).hexdigest() for b in bcs),
+               scheme)
+        if kt is not None:
+            key += (tuple((t, float(v[0]), float(v[1]), tuple(float(x) for x in v[2])) for t, v in sorted(kt[0].items())), kt[1])
+        return key
 
-    def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme="backward_euler"):
+    def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme="backward_euler", kt=None):
         """The resident HeatProblem for ``key`` (built if absent), its operator valued for ``tag_to_k``."""
         if self.problem is None or key != self._key:
             self.close()
@@ -284,7 +304,7 @@ class SimulationSession:
                                        backend=self.backend, device_id=self.device_id, rtol=self.rtol,
                                        max_it=self.max_it, assembly_mode=self.assembly_mode, precond=self.precond,
                                        amg_reuse=True, pattern=self.pattern, amg=shared["blob"] if shared else None,
-                                       scheme=scheme)
+                                       scheme=scheme, **({"kappa_tables": kt[0], "picard": kt[1]} if kt else {}))
             self._key = key
             self._k = dict(tag_to_k)
             # conductivities the multigrid levels were built for: this problem's, or those of the session that shared them
@@ -331,6 +351,8 @@ class SimulationSession:
         frozen multigrid hierarchy).  ``read_flux`` adds run_no_diamond's per-step gradient projection for every
         column (hf_batch_run_flux).  Returns one result dict per configuration, as :meth:`run` does."""
         nv = len(cfgs)
+        for c in cfgs:
+            refuse_tables(c, "run_batch (the batched loop)")
         if nv not in (2, 4, 8, 16):
             raise ValueError("run_batch: 2, 4, 8 or 16 configurations at a time")
         t_start = time.time()
@@ -434,9 +456,12 @@ class SimulationSession:
         varying = bcs[3:]
         tag_to_k, tag_to_rc = self._tables(stack)
         scheme = time_scheme(cfg)
-        key = self._problem_key(dt, tag_to_rc, bcs, scheme)
+        kt = self._kappa_tables(cfg, stack)
+        if kt is not None and tangents:
+            refuse_tables(cfg, "tangents")
+        key = self._problem_key(dt, tag_to_rc, bcs, scheme, kt)
         fresh = self.problem is None or key != self._key
-        self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme)
+        self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme, kt)
         if not fresh:
             self.problem.set_state(ic_temp)
             self.problem.iters = []

@@ -12,6 +12,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 
+from .kappa_t import material_table
 from .materials import Material
 
 
@@ -20,13 +21,13 @@ def _f(cfg, mat, key):
 
 
 def _material(cfg, name, box):
-    """Material with rho_cv = rho*cv and k, as run_with_diamond.py:100-181."""
-    return Material(
-        name,
-        boundaries=box,
-        properties={"rho_cv": _f(cfg, name, "rho") * _f(cfg, name, "cv"), "k": _f(cfg, name, "k")},
-        mesh_size=_f(cfg, name, "mesh"),
-    )
+    """Material with rho_cv = rho*cv and k, as run_with_diamond.py:100-181; a kappa(T) key (k_table / k_power,
+    heatflow_amd.kappa_t) adds the tabulated ``k_table`` = (T0, dT, values)."""
+    props = {"rho_cv": _f(cfg, name, "rho") * _f(cfg, name, "cv"), "k": _f(cfg, name, "k")}
+    table = material_table(name, cfg["mats"][name])
+    if table is not None:
+        props["k_table"] = table
+    return Material(name, boundaries=box, properties=props, mesh_size=_f(cfg, name, "mesh"))
 
 
 @dataclass

@@ -36,7 +36,7 @@ EXPORTS = [
     "hf_batch_begin", "hf_batch_load_column", "hf_batch_set_affine", "hf_batch_set_state", "hf_batch_get_state", "hf_batch_run", "hf_batch_run_flux", "hf_batch_end",
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
-    "hf_tangent_setup", "hf_run_tangent", "hf_get_tangent", "hf_get_sizes", "hf_get_csr", "hf_spmv", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
+    "hf_tangent_setup", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_get_sizes", "hf_get_csr", "hf_spmv", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
 
 
@@ -137,6 +137,8 @@ def load_library():
         "hf_tangent_setup": [vp, i32, pi],
         "hf_run_tangent": [vp, i32, pd, pd, dbl, dbl, i32, i32, pi, pd, pi, pd, pi],
         "hf_get_tangent": [vp, i32, pd],
+        "hf_set_kappa_tables": [vp, i32, pi, pd, pd, pi, pd, i32],
+        "hf_get_picard_change": [vp, pd],
         "hf_get_sizes": [vp, pi, pi, C.POINTER(i64), pi],
         "hf_get_csr": [vp, pi, pi, pd, pd],
         "hf_spmv": [vp, i32, pd, pd],
@@ -423,6 +425,30 @@ class HeatflowHIP:
         s = np.empty(self.n, dtype=np.float64)
         self._check(self._lib.hf_get_tangent(self._ctx, int(j), _pd(s)))
         return s
+
+    # -- temperature-dependent conductivities (hf_set_kappa_tables) ---------------------
+    def set_kappa_tables(self, tables, picard=1):
+        """``tables`` = {cell tag: (T0, dT, values)}: kappa(T) piecewise linear on T0 + i dT, clamped outside; an empty dict
+        clears them.  Every step then re-values A at u^n (BDF2: 2 u^n - u^{n-1}), with ``picard`` sweeps per step (1..8).
+        Invalidates the assembly: set the state, then assemble()."""
+        items = sorted((int(t), v) for t, v in (tables or {}).items())
+        if not items:
+            self._check(self._lib.hf_set_kappa_tables(self._ctx, 0, None, None, None, None, None, int(picard)))
+            return
+        tags = _i32([t for t, _ in items])
+        t0 = _f64([float(v[0]) for _, v in items])
+        dT = _f64([float(v[1]) for _, v in items])
+        vals = [np.asarray(v[2], dtype=np.float64).ravel() for _, v in items]
+        nk = _i32([len(v) for v in vals])
+        allv = _f64(np.concatenate(vals))
+        self._check(self._lib.hf_set_kappa_tables(self._ctx, len(tags), _pi(tags), _pd(t0), _pd(dT), _pi(nk), _pd(allv),
+                                                  int(picard)))
+
+    def picard_change(self):
+        """max |u^{n+1,p} - u^{n+1,p-1}| of the last step's last Picard sweep (u^{n+1,0} = the evaluation state)."""
+        d = C.c_double()
+        self._check(self._lib.hf_get_picard_change(self._ctx, C.byref(d)))
+        return float(d.value)
 
     # -- batched time loop: nv sweep points as the columns of one multi-vector PCG ------------------
     def batch_begin(self, nv, per_column_operator=False):

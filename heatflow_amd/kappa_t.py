@@ -1,0 +1,78 @@
+"""Temperature-dependent conductivities: tables from configuration keys and the refusals of the paths that
+do not support them.
+
+A material of ``cfg["mats"]`` may carry, besides its constant ``k``:
+  ``k_table: {T_min, T_max, k: [...]}``                 values on a uniform grid from T_min to T_max (2..256 knots)
+  ``k_power: {T_ref, exponent, T_min, T_max[, knots]}``  k (T_ref / T)^exponent tabulated on [T_min, T_max] (default 256 knots),
+                                                        with the material's ``k`` as the value at T_ref
+The table is what the library evaluates: piecewise linear, clamped to the end values outside [T_min, T_max].
+``timing.picard_sweeps`` (default 1) sets the Picard sweeps per step.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+MAX_KNOTS = 256
+MAX_PICARD = 8
+TABLE_KEYS = ("k_table", "k_power")
+
+
+def power_law_table(k_ref, T_ref, exponent, T_min, T_max, knots=MAX_KNOTS):
+    """(T0, dT, values) of k_ref (T_ref / T)^exponent at ``knots`` uniform points of [T_min, T_max]."""
+    knots = int(knots)
+    if not 2 <= knots <= MAX_KNOTS:
+        raise ValueError(f"k_power: knots must be 2..{MAX_KNOTS} (got {knots})")
+    T_min, T_max, T_ref = float(T_min), float(T_max), float(T_ref)
+    if not (0.0 < T_min < T_max) or not T_ref > 0.0 or not float(k_ref) > 0.0:
+        raise ValueError("k_power: need 0 < T_min < T_max, T_ref > 0 and k > 0")
+    dT = (T_max - T_min) / (knots - 1)
+    T = T_min + dT * np.arange(knots)
+    return T_min, dT, float(k_ref) * (T_ref / T) ** float(exponent)
+
+
+def uniform_table(T_min, T_max, values):
+    """(T0, dT, values) of values given on a uniform grid from T_min to T_max."""
+    v = np.asarray(values, dtype=np.float64).ravel()
+    if not 2 <= v.size <= MAX_KNOTS:
+        raise ValueError(f"k_table: 2..{MAX_KNOTS} values needed (got {v.size})")
+    if not float(T_max) > float(T_min) or not np.all(v > 0.0) or not np.all(np.isfinite(v)):
+        raise ValueError("k_table: need T_max > T_min and positive values")
+    return float(T_min), (float(T_max) - float(T_min)) / (v.size - 1), v
+
+
+def material_table(name, mat):
+    """The (T0, dT, values) table of one material entry of cfg["mats"], or None without a table key."""
+    if "k_table" in mat and "k_power" in mat:
+        raise ValueError(f"mats.{name}: k_table and k_power are exclusive")
+    if "k_table" in mat:
+        t = mat["k_table"]
+        return uniform_table(t["T_min"], t["T_max"], t["k"])
+    if "k_power" in mat:
+        p = mat["k_power"]
+        return power_law_table(mat["k"], p["T_ref"], p["exponent"], p["T_min"], p["T_max"], p.get("knots", MAX_KNOTS))
+    return None
+
+
+def picard_sweeps(cfg):
+    """``timing.picard_sweeps`` (default 1), checked against 1..8."""
+    p = int((cfg.get("timing") or {}).get("picard_sweeps", 1) or 1)
+    if not 1 <= p <= MAX_PICARD:
+        raise ValueError(f"timing.picard_sweeps must be 1..{MAX_PICARD} (got {p})")
+    return p
+
+
+def table_keys(cfg):
+    """['mats.<name>.k_table', ...] of every material of ``cfg`` that carries a kappa(T) key."""
+    out = []
+    for name, mat in sorted((cfg.get("mats") or {}).items()):
+        for key in TABLE_KEYS:
+            if isinstance(mat, dict) and key in mat:
+                out.append(f"mats.{name}.{key}")
+    return out
+
+
+def refuse_tables(cfg, where):
+    """ValueError naming the key if ``cfg`` asks for kappa(T): ``where`` does not support it (yet)."""
+    keys = table_keys(cfg)
+    if keys:
+        raise ValueError(f"{where} does not support temperature-dependent conductivities ({', '.join(keys)})")

@@ -36,6 +36,7 @@ from .driver import (SimulationSession, build_pattern_blob, flush_mesh_writes, p
                      run_simulation_impl, time_scheme)
 from .geometry import build_stack, watcher_points as _watcher_points
 from .hip_backend import HipError, NotConverged
+from .kappa_t import refuse_tables
 
 
 def batch_failure(e, n_points):
@@ -378,6 +379,7 @@ def run_parameter_sweep(base_config_path, output_dir, fwhm_range, k_range, width
     if scheme is not None:
         base_config.setdefault("timing", {})["scheme"] = scheme
     time_scheme(base_config)          # an unknown scheme raises before any work
+    refuse_tables(base_config, "run_parameter_sweep")
     combos, fwhm_vals, k_vals, width_vals = create_parameter_grid(fwhm_range, k_range, width_range, num_points)
     if device_id is None:
         device_id = local_device()
@@ -511,6 +513,7 @@ def run_kappa_sweep(cfg, mesh_folder, k_values, output_dir, *, rebuild_mesh=Fals
     The time scheme is the configuration's ``timing.scheme`` (default backward Euler)."""
     rank, world = world_info()
     time_scheme(cfg)                  # an unknown scheme raises before any work
+    refuse_tables(cfg, "run_kappa_sweep")
     if device_id is None:
         device_id = local_device()
     stack = build_stack(cfg)

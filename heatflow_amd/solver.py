@@ -46,11 +46,16 @@ class HeatProblem:
               smoothed-aggregation V-cycle: same stopping rule and answer, ~50x fewer iterations)
     scheme : "backward_euler" (default, the reference's scheme) or "bdf2" (second order, hf_set_time_scheme); ``dt`` stays
               the time step and the sample times stay (k+1) dt
+    kappa_tables : {cell tag: (T0, dT, values)} - temperature-dependent conductivities (hf_set_kappa_tables):
+              every step re-values the operator at u^n (BDF2: 2 u^n - u^{n-1}); the state u0 is set before the assembly, so
+              the multigrid hierarchy is built from A(u0).  None / {}: constant conductivities, the call sequence of before.
+    picard : Picard sweeps per step with tables (1..8; 1 = the lagged scheme)
     """
 
     def __init__(self, coords, tris, tags, tag_to_k, tag_to_rho_cv, dt, bcs, u0, *, backend=None, device_id=0,
                  assembly_mode=ASM_ROW_GATHER, rtol=DEFAULT_RTOL, atol=0.0, max_it=DEFAULT_MAX_IT,
-                 precond=PC_JACOBI, amg_reuse=False, pattern=None, amg=None, scheme="backward_euler"):
+                 precond=PC_JACOBI, amg_reuse=False, pattern=None, amg=None, scheme="backward_euler", kappa_tables=None,
+                 picard=1):
         self.coords = np.ascontiguousarray(coords, dtype=np.float64)
         self.n = self.coords.shape[0]
         self.dt = float(dt)
@@ -59,6 +64,8 @@ class HeatProblem:
         self.assembly_mode = assembly_mode
         self.precond = precond
         self.scheme = scheme
+        self.kappa_tables = dict(kappa_tables or {})
+        self.picard = int(picard)
         scheme_code = time_scheme_code(scheme)     # (an unknown name raises before any backend call)
         self.backend = backend if backend is not None else HeatflowHIP(device_id)
         self._own_backend = backend is None
@@ -81,9 +88,14 @@ class HeatProblem:
             self.backend.set_time_scheme(scheme_code)
         if amg is not None and precond == PC_AMG and amg_reuse:
             self.backend.amg_install(amg)
-        self.backend.assemble(self.dt, self.assembly_mode)
         u = np.full(self.n, float(u0)) if np.isscalar(u0) else np.asarray(u0, dtype=np.float64)
-        self.backend.set_state(u)
+        if self.kappa_tables:     # kappa(T): the operator (and the hierarchy built from it) is evaluated at u0
+            self.backend.set_kappa_tables(self.kappa_tables, self.picard)
+            self.backend.set_state(u)
+            self.backend.assemble(self.dt, self.assembly_mode)
+        else:
+            self.backend.assemble(self.dt, self.assembly_mode)
+            self.backend.set_state(u)
         self.setup_seconds = time.perf_counter() - t0
         self.iters = []
 
@@ -96,6 +108,10 @@ class HeatProblem:
                                    np.array([tag_to_rho_cv[t] for t in tags], dtype=np.float64))
         if assemble:
             self.backend.assemble(self.dt, self.assembly_mode)
+
+    def picard_change(self):
+        """max |u^{n+1,p} - u^{n+1,p-1}| of the last step's last Picard sweep (kappa(T) only)."""
+        return self.backend.picard_change()
 
     def close(self):
         if self._own_backend:

@@ -31,6 +31,8 @@
  *                      HF_TIME_BDF2 is the second-order alternative
  *   hf_tangent_setup / hf_run_tangent / hf_get_tangent   no counterpart: the reference fits by re-running the forward model
  *                      over a grid (sweep_test.py:47-75, parameter_sweep.py:195-235); these give the derivatives of a run
+ *   hf_set_kappa_tables / hf_get_picard_change   no counterpart: the reference's conductivities are constants per material
+ *                      (run_with_diamond.py:286-301); these make them functions of the temperature
  *
  * Conventions
  *   - All functions return 0 (HF_OK) or a negative HF_ERR_* code; hf_last_error(ctx)
@@ -328,6 +330,41 @@ int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col);
 int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const double* h_all, double rtol, double atol, int32_t max_it,
                    int32_t n_s, const int32_t* nodes, double* samples, int32_t* iters, double* tangent_samples, int32_t* tangent_iters);
 int hf_get_tangent(hf_ctx* ctx, int32_t j, double* s);
+
+/* Temperature-dependent conductivities: the conductivity stays piecewise constant per element (DG0), but a
+ * cell tag may carry a table, and every step of hf_step / hf_run re-values the operator at an evaluation state u*.
+ *   kappa_e = table_tag(T_e),  T_e = ((lo + mid) + hi) * (1/3) of the element's three nodal values of u* sorted by value (the same
+ *             bits from each vertex's point of view: A stays exactly symmetric).
+ *   table     piecewise linear on the uniform grid T0 + i dT, i = 0..n_knots-1 (dT > 0, 2 <= n_knots <= 256, values > 0); outside
+ *             [T0, T0 + (n_knots-1) dT] clamped to the end value.  s = (T - T0) * (1/dT), i = floor(s), v_i + (s - i)(v_{i+1} - v_i).
+ *             A tag without a table keeps its constant from hf_set_materials / hf_update_kappa.
+ *   u*        backward Euler: u^n (lagged); BDF2: 2 u^n - u^{n-1} once a history exists, else u^n.  Dirichlet entries are whatever
+ *             the state holds.
+ *   Picard    picard_sweeps = p (1..8, fixed count: the polled loop never waits on a host-side test): sweep k > 1 re-evaluates at
+ *             the latest iterate u^{n+1,k-1} and solves again from it.  p = 1 is the lagged scheme.
+ * Each evaluation re-values A (M and rho_c stay), redoes the Dirichlet elimination, the lifting values and D^-1, and the
+ * right-hand side b = M u^n (+ dt F) (BDF2: M (4/3 u^n - 1/3 u^{n-1}) + dt' F) is lifted with the new A.  One row-gather launch
+ * (k_assemble_rows_kT) per evaluation, on the stream, no host synchronisation.  The iteration count of a step is the sum over
+ * its sweeps.
+ * hf_set_kappa_tables  n_tab tables: tags[i], t0[i], dT[i], n_knots[i]; values = the knots of all tables concatenated in the order
+ *        of `tags`.  n_tab = 0 clears the tables (every path then launches what it launches without them).  Setting or clearing
+ *        invalidates the assembly (like a scheme change) and closes an open batch.  With tables set, hf_assemble evaluates at the
+ *        current state (so set the state first): the multigrid hierarchy it builds is the one of A(u) at that state and stays
+ *        frozen for the run; the fine level uses the current A and D^-1 (the fused fine-level legs hold the old operator and are
+ *        not used after the first re-valuation).  Start vectors: kinds 2 and 3 assume one operator for the whole run and run as
+ *        kind 1; kind 0 stays kind 0.
+ *        HF_ERR_ARG: a tag that is not a cell tag of the mesh (or listed twice), bad knots or values, picard_sweeps outside 1..8,
+ *        a mesh without row-gather lists or an operator assembled in a mode other than HF_ASM_ROW_GATHER.  HF_ERR_STATE before
+ *        hf_set_mesh.  hf_set_mesh removes the tables.
+ * While tables are set: hf_assemble in another mode and hf_update_kappa on a tabled tag -> HF_ERR_ARG; hf_batch_begin,
+ * hf_tangent_setup / hf_run_tangent and hf_steady_setup / hf_steady_solve -> HF_ERR_STATE.  Every error returns before any
+ * launch.  hf_set_load keeps working.  Not supported (refused, never approximated): a temperature-dependent rho_c, a Picard
+ * steady state, batched / affine sweeps, tangents, and rebuilding the hierarchy during a run.
+ * hf_get_picard_change  max over all nodes of |u^{n+1,p} - u^{n+1,p-1}| of the last step's last sweep (u^{n+1,0} = u*, so for
+ *        p = 1 the change from the evaluation state); HF_ERR_STATE before the first step with tables. */
+int hf_set_kappa_tables(hf_ctx* ctx, int32_t n_tab, const int32_t* tags, const double* t0, const double* dT, const int32_t* n_knots,
+                        const double* values, int32_t picard_sweeps);
+int hf_get_picard_change(hf_ctx* ctx, double* max_du);
 
 int hf_get_sizes(hf_ctx* ctx, int32_t* n, int32_t* n_e, int64_t* nnz, int32_t* n_bc);
 /* Any pointer may be NULL.  A is the matrix as it stands (eliminated when BCs are set). */
