@@ -1770,6 +1770,143 @@ int hf_spmv(hf_ctx* ctx, int32_t which, const double* x, double* y) {
   return HF_OK;
 }
 
+// Test and diagnosis entry points of the preconditioner: z = B r by the cycle PCG runs (vcycle, BatchOps::vcycle) and the
+// coarsest level's dense inverse on any SPD matrix (dense_inverse).  The level vectors the cycle writes are set to NaN
+// first, so that an entry read before it is written shows in z; the zero pads wire_levels lays out stay as they are.
+int hf_amg_apply(hf_ctx* ctx, const double* r, double* z, double* rz) {
+  if (!ctx || !r || !z) return HF_ERR_ARG;
+  if (ctx->precond != 1 || !ctx->amg_ready || !ctx->assembled || ctx->amg.empty())
+    return fail(ctx, HF_ERR_STATE, "hf_amg_apply: no assembled operator with a multigrid hierarchy (hf_set_precond(1, ...) and hf_assemble first)");
+  HF_HIP(hipSetDevice(ctx->dev));
+  const int n = ctx->n, nl = static_cast<int>(ctx->amg.size());
+  HF_TRY(reset_scal(ctx));
+  // z0 = w0 D^-1 r, as k_pcg_update_amg leaves it (w * (dinv * r))
+  std::vector<double> dinv(n), z0(n);
+  HF_HIP(copy_sync(ctx, dinv.data(), ctx->d_dinv, sizeof(double) * n, hipMemcpyDeviceToHost));
+  const double w0 = ctx->amg[0].omega;
+  for (int i = 0; i < n; ++i) z0[i] = w0 * (dinv[i] * r[i]);
+  auto poison = [&](double* p, size_t count) { return count ? hipMemsetAsync(p, 0xFF, sizeof(double) * count, ctx->stream) : hipSuccess; };
+  HF_HIP(poison(ctx->d_tmp, n));
+  HF_HIP(poison(ctx->d_z2, n));
+  HF_HIP(poison(ctx->d_part_rz, MAXP));
+  for (int l = 1; l < nl; ++l) {
+    DevLevel& L = ctx->amg[l];
+    if (L.cat) HF_HIP(poison(L.cat, static_cast<size_t>(L.n) + ctx->amg[l + 1].n));   // [b_l ; x_{l+1}], not the 2-entry tail
+    else HF_HIP(poison(L.b, L.n));                                                       // coarsest: not the pad [n, n + 4)
+    if (l == 1) HF_HIP(poison(L.res, L.n));                                              // level 1's own x, or behind d_r
+  }
+  HF_HIP(copy_sync(ctx, ctx->d_r, r, sizeof(double) * n, hipMemcpyHostToDevice));
+  HF_HIP(copy_sync(ctx, ctx->d_z, z0.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+  vcycle(ctx, 0);
+  HF_HIP(hipGetLastError());
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  HF_HIP(copy_sync(ctx, z, ctx->d_z2, sizeof(double) * n, hipMemcpyDeviceToHost));
+  if (rz) {
+    std::vector<double> part(ctx->P);
+    HF_HIP(copy_sync(ctx, part.data(), ctx->d_part_rz, sizeof(double) * ctx->P, hipMemcpyDeviceToHost));
+    double s = 0.0;
+    for (double v : part) s += v;
+    *rz = s;
+  }
+  return HF_OK;
+}
+
+int hf_batch_apply_precond(hf_ctx* ctx, const double* r, double* z, double* rz) {
+  if (!ctx || !r || !z) return HF_ERR_ARG;
+  hf_ctx::Batch& B = ctx->batch;
+  if (B.nv == 0) return fail(ctx, HF_ERR_STATE, "hf_batch_apply_precond: no batch is open (hf_batch_begin)");
+  if (ctx->precond != 1 || !ctx->amg_ready || !ctx->assembled || ctx->amg.empty() || B.lev.size() != ctx->amg.size())
+    return fail(ctx, HF_ERR_STATE, "hf_batch_apply_precond: the batch has no multigrid hierarchy");
+  HF_HIP(hipSetDevice(ctx->dev));
+  const int nv = B.nv, nl = static_cast<int>(ctx->amg.size());
+  const size_t n = static_cast<size_t>(ctx->n), vec = n * nv;
+  // interleaved r and z0 = w0 D_j^-1 r_j (D^-1 per column unless the columns share the operator)
+  const bool dpc = B.opk != HF_BATCH_SHARED;
+  std::vector<double> dinv(dpc ? vec : n), ri(vec), z0(vec);
+  HF_HIP(copy_sync(ctx, dinv.data(), dpc ? B.dinv : ctx->d_dinv, sizeof(double) * dinv.size(), hipMemcpyDeviceToHost));
+  const double w0 = ctx->amg[0].omega;
+  for (size_t i = 0; i < n; ++i)
+    for (int j = 0; j < nv; ++j) {
+      const size_t q = i * nv + j;
+      ri[q] = r[static_cast<size_t>(j) * n + i];
+      z0[q] = w0 * ((dpc ? dinv[q] : dinv[i]) * ri[q]);
+    }
+  auto poison = [&](double* p, size_t count) { return count ? hipMemsetAsync(p, 0xFF, sizeof(double) * count, ctx->stream) : hipSuccess; };
+  HF_HIP(poison(B.tmp, vec));
+  HF_HIP(poison(B.z2, vec));
+  HF_HIP(poison(B.part_rz, static_cast<size_t>(nv) * MAXP));
+  for (int l = 1; l < nl; ++l) {
+    const hf_ctx::BatchLevel& Q = B.lev[l];
+    const size_t ln = static_cast<size_t>(ctx->amg[l].n);
+    if (Q.cat) HF_HIP(poison(Q.cat, (ln + ctx->amg[l + 1].n) * nv));
+    else HF_HIP(poison(Q.b, ln * nv));
+    if (l == 1) HF_HIP(poison(Q.res, ln * nv));
+  }
+  HF_HIP(hipMemsetAsync(B.scal, 0, sizeof(Scal) * nv, ctx->stream));     // every column runs
+  HF_HIP(copy_sync(ctx, B.r, ri.data(), sizeof(double) * vec, hipMemcpyHostToDevice));
+  HF_HIP(copy_sync(ctx, B.z, z0.data(), sizeof(double) * vec, hipMemcpyHostToDevice));
+  HF_TRY(batch_dispatch(ctx, [&](auto ops) { decltype(ops)::vcycle(ctx, 0); return HF_OK; }));
+  HF_HIP(hipGetLastError());
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  std::vector<double> zi(vec);
+  HF_HIP(copy_sync(ctx, zi.data(), B.z2, sizeof(double) * vec, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; ++i)
+    for (int j = 0; j < nv; ++j) z[static_cast<size_t>(j) * n + i] = zi[i * nv + j];
+  if (rz) {
+    BRed red;
+    HF_HIP(copy_sync(ctx, &red, B.red, sizeof(BRed), hipMemcpyDeviceToHost));
+    for (int j = 0; j < nv; ++j) rz[j] = red.rz[0][j];
+  }
+  return HF_OK;
+}
+
+int hf_dense_inverse(hf_ctx* ctx, int32_t n, const int32_t* ptr, const int32_t* idx, const double* val, const double* b,
+                     double* inv, double* x64, double* x32) {
+  if (!ctx) return HF_ERR_ARG;
+  if (n < 1 || n > 4096 || !ptr || (ptr[n] > 0 && (!idx || !val)))
+    return fail(ctx, HF_ERR_ARG, "hf_dense_inverse: n = %d outside [1, 4096] or a null array", n);
+  if (ptr[0] != 0) return fail(ctx, HF_ERR_ARG, "hf_dense_inverse: row pointer does not start at 0");
+  for (int i = 0; i < n; ++i)
+    if (ptr[i + 1] < ptr[i]) return fail(ctx, HF_ERR_ARG, "hf_dense_inverse: row pointer decreases at row %d", i);
+  if ((x64 || x32) && !b) return fail(ctx, HF_ERR_ARG, "hf_dense_inverse: products asked for without b");
+  HF_HIP(hipSetDevice(ctx->dev));
+  const int ld = (n + 3) & ~3;
+  const size_t cnt = static_cast<size_t>(n) * ld;
+  DevTemp<double> t_inv, t_b, t_x;
+  DevTemp<float> t_invf;
+  DevTemp<Scal> t_scal;                                     // zeroed: done = 0 (the context's own scalars stay as they are)
+  HF_TRY(dev_alloc(ctx, &t_inv.p, cnt));
+  HF_TRY(dense_inverse(ctx, n, ptr, idx, val, t_inv.p));
+  if (inv) {
+    HF_HIP(hipMemcpy2DAsync(inv, sizeof(double) * n, t_inv.p, sizeof(double) * ld, sizeof(double) * n, n, hipMemcpyDeviceToHost, ctx->stream));
+    HF_HIP(hipStreamSynchronize(ctx->stream));
+  }
+  if (x64 || x32) {
+    HF_TRY(dev_alloc(ctx, &t_b.p, static_cast<size_t>(n) + 4));           // zero-padded as wire_levels pads the coarsest b
+    HF_TRY(dev_alloc(ctx, &t_x.p, n));
+    HF_TRY(dev_alloc(ctx, &t_scal.p, 1));
+    HF_HIP(hipMemsetAsync(t_b.p, 0, sizeof(double) * (n + 4), ctx->stream));
+    HF_HIP(hipMemsetAsync(t_scal.p, 0, sizeof(Scal), ctx->stream));
+    HF_HIP(copy_sync(ctx, t_b.p, b, sizeof(double) * n, hipMemcpyHostToDevice));
+    const int g = std::max(1, std::min((n + 1) / 2, 2048));                // the grid of vcycle's coarsest level
+    if (x64) {
+      HF_HIP(hipMemsetAsync(t_x.p, 0xFF, sizeof(double) * n, ctx->stream));
+      hipLaunchKernelGGL(k_dense_mv, dim3(g), dim3(TPB), 0, ctx->stream, n, ld, t_inv.p, t_b.p, t_x.p, t_scal.p);
+      HF_HIP(hipGetLastError());
+      HF_HIP(copy_sync(ctx, x64, t_x.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+    }
+    if (x32) {
+      HF_TRY(dev_alloc(ctx, &t_invf.p, cnt));
+      hipLaunchKernelGGL(k_to_float, dim3(1024), dim3(256), 0, ctx->stream, cnt, t_inv.p, t_invf.p);
+      HF_HIP(hipMemsetAsync(t_x.p, 0xFF, sizeof(double) * n, ctx->stream));
+      hipLaunchKernelGGL(k_dense_mv_f32, dim3(g), dim3(TPB), 0, ctx->stream, n, ld, t_invf.p, t_b.p, t_x.p, t_scal.p);
+      HF_HIP(hipGetLastError());
+      HF_HIP(copy_sync(ctx, x32, t_x.p, sizeof(double) * n, hipMemcpyDeviceToHost));
+    }
+  }
+  return HF_OK;
+}
+
 int hf_time_kernel(hf_ctx* ctx, int32_t which, int32_t reps, double* ms_avg) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->assembled || reps <= 0 || !ms_avg) return fail(ctx, HF_ERR_STATE, "hf_time_kernel: not assembled or bad arguments");

@@ -175,7 +175,7 @@ int get_csr(hf_ctx* ctx, BlobIn& in, DevCsr& d, int want_rows /* -1: any */, int
     ok = dptr[0] == 0 && dptr[r.nchunks] == r.ndict;
     for (int c = 0; c < r.nchunks && ok; ++c) {
       const int nd = dptr[c + 1] - dptr[c];
-      ok = nd > 0 && nd <= r.max_dict && dptr[c] >= 0 && dptr[c + 1] <= r.ndict;
+      ok = nd >= 0 && nd <= r.max_dict && dptr[c] >= 0 && dptr[c + 1] <= r.ndict;   // (a chunk of empty rows has an empty list)
       max_dict = std::max(max_dict, nd);
     }
     if (ok) {

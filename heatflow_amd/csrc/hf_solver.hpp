@@ -167,6 +167,45 @@ int upload_host_levels(hf_ctx* ctx, const amg::Hierarchy& H, size_t base) {
   return HF_OK;
 }
 
+// Dense inverse of an SPD operator of n <= 4096 rows given in CSR form (host arrays) on the device: W = [A | I] (the operator
+// travels in CSR form), blocked Gauss-Jordan (hf_kernels.hpp), A^-1 = the right half, written to `inv` (device, n rows of
+// leading dimension (n + 3) & ~3, the pad columns zero).  The coarsest level of the hierarchy (finish_amg) and the test
+// entry point hf_dense_inverse.  Complete on return.
+int dense_inverse(hf_ctx* ctx, int nc, const int32_t* ptr, const int32_t* idx, const double* val, double* inv) {
+  const int ld = (nc + 3) & ~3;
+  const int64_t nnz = ptr[nc];
+  for (int i = 0; i < nc; ++i)
+    for (int k = ptr[i]; k < ptr[i + 1]; ++k)
+      if (idx[k] < 0 || idx[k] >= nc) return fail(ctx, HF_ERR_ARG, "coarsest operator: column %d outside [0,%d)", idx[k], nc);
+  DevTemp<double> t_w, t_r, t_val;
+  DevTemp<int32_t> t_ptr, t_idx;
+  HF_TRY(dev_alloc(ctx, &t_w.p, static_cast<size_t>(nc) * 2 * nc));
+  HF_TRY(dev_alloc(ctx, &t_r.p, static_cast<size_t>(GJ_B) * nc));
+  HF_TRY(dev_alloc(ctx, &t_ptr.p, static_cast<size_t>(nc) + 1));
+  HF_TRY(dev_alloc(ctx, &t_idx.p, std::max<size_t>(nnz, 1)));
+  HF_TRY(dev_alloc(ctx, &t_val.p, std::max<size_t>(nnz, 1)));
+  HF_HIP(copy_sync(ctx, t_ptr.p, ptr, sizeof(int32_t) * (static_cast<size_t>(nc) + 1), hipMemcpyHostToDevice));
+  if (nnz > 0) {
+    HF_HIP(copy_sync(ctx, t_idx.p, idx, sizeof(int32_t) * nnz, hipMemcpyHostToDevice));
+    HF_HIP(copy_sync(ctx, t_val.p, val, sizeof(double) * nnz, hipMemcpyHostToDevice));
+  }
+  HF_HIP(hipMemsetAsync(t_w.p, 0, sizeof(double) * nc * 2 * nc, ctx->stream));
+  hipLaunchKernelGGL(k_gjb_fill, dim3((nc + 255) / 256), dim3(256), 0, ctx->stream, nc, t_ptr.p, t_idx.p, t_val.p, t_w.p);
+  const int tiles = (nc + 63) / 64;
+  for (int c0 = 0; c0 < nc; c0 += GJ_B) {
+    const int bsz = std::min(GJ_B, nc - c0);
+    hipLaunchKernelGGL(k_gjb_rows, dim3(std::max(1, std::min((nc + TPB - 1) / TPB, 64))), dim3(TPB), 0, ctx->stream, nc, c0, bsz, t_w.p, t_r.p);
+    hipLaunchKernelGGL(k_gjb_update, dim3(tiles, tiles), dim3(TPB), 0, ctx->stream, nc, c0, bsz, t_w.p, t_r.p);
+  }
+  HF_HIP(hipGetLastError());
+  // rows re-pitched to the even leading dimension (zero pad column)
+  HF_HIP(hipMemsetAsync(inv, 0, sizeof(double) * nc * ld, ctx->stream));
+  HF_HIP(hipMemcpy2DAsync(inv, sizeof(double) * ld, t_w.p + nc, sizeof(double) * 2 * nc, sizeof(double) * nc, nc,
+                          hipMemcpyDeviceToDevice, ctx->stream));
+  HF_HIP(hipStreamSynchronize(ctx->stream));     // (the temporaries are released on return)
+  return HF_OK;
+}
+
 // Last steps of a set-up once every level's operators are on the device: the finest level's fused legs are dropped when they
 // are too small for the only kernel that carries their epilogues, the level vectors are wired, the dense inverse of the
 // coarsest operator (host copy Ac) is formed on the device by Gauss-Jordan.
@@ -201,36 +240,8 @@ int finish_amg(hf_ctx* ctx, const amg::Csr& Ac, int coarse_n, double op_complexi
   if (nl > 1 && coarse_n > 0 && coarse_n <= 4096) {
     const int nc = coarse_n;
     const int ld = (nc + 3) & ~3;
-    for (int i = 0; i < nc; ++i)
-      for (int k = Ac.ptr[i]; k < Ac.ptr[i + 1]; ++k)
-        if (Ac.idx[k] < 0 || Ac.idx[k] >= nc) return fail(ctx, HF_ERR_ARG, "coarsest operator: column %d outside [0,%d)", Ac.idx[k], nc);
-    // W = [A | I] on the device (the operator travels in CSR form), blocked Gauss-Jordan (hf_kernels.hpp), A^-1 = the right half
-    DevTemp<double> t_w, t_r, t_val;
-    DevTemp<int32_t> t_ptr, t_idx;
-    HF_TRY(dev_alloc(ctx, &t_w.p, static_cast<size_t>(nc) * 2 * nc));
-    HF_TRY(dev_alloc(ctx, &t_r.p, static_cast<size_t>(GJ_B) * nc));
-    HF_TRY(dev_alloc(ctx, &t_ptr.p, Ac.ptr.size()));
-    HF_TRY(dev_alloc(ctx, &t_idx.p, std::max<size_t>(Ac.idx.size(), 1)));
-    HF_TRY(dev_alloc(ctx, &t_val.p, std::max<size_t>(Ac.val.size(), 1)));
     HF_TRY(dev_alloc(ctx, &ctx->d_coarse_inv, static_cast<size_t>(nc) * ld));
-    HF_HIP(copy_sync(ctx, t_ptr.p, Ac.ptr.data(), sizeof(int32_t) * Ac.ptr.size(), hipMemcpyHostToDevice));
-    if (!Ac.idx.empty()) {
-      HF_HIP(copy_sync(ctx, t_idx.p, Ac.idx.data(), sizeof(int32_t) * Ac.idx.size(), hipMemcpyHostToDevice));
-      HF_HIP(copy_sync(ctx, t_val.p, Ac.val.data(), sizeof(double) * Ac.val.size(), hipMemcpyHostToDevice));
-    }
-    HF_HIP(hipMemsetAsync(t_w.p, 0, sizeof(double) * nc * 2 * nc, ctx->stream));
-    hipLaunchKernelGGL(k_gjb_fill, dim3((nc + 255) / 256), dim3(256), 0, ctx->stream, nc, t_ptr.p, t_idx.p, t_val.p, t_w.p);
-    const int tiles = (nc + 63) / 64;
-    for (int c0 = 0; c0 < nc; c0 += GJ_B) {
-      const int bsz = std::min(GJ_B, nc - c0);
-      hipLaunchKernelGGL(k_gjb_rows, dim3(std::max(1, std::min((nc + TPB - 1) / TPB, 64))), dim3(TPB), 0, ctx->stream, nc, c0, bsz, t_w.p, t_r.p);
-      hipLaunchKernelGGL(k_gjb_update, dim3(tiles, tiles), dim3(TPB), 0, ctx->stream, nc, c0, bsz, t_w.p, t_r.p);
-    }
-    HF_HIP(hipGetLastError());
-    // rows re-pitched to the even leading dimension (zero pad column)
-    HF_HIP(hipMemsetAsync(ctx->d_coarse_inv, 0, sizeof(double) * nc * ld, ctx->stream));
-    HF_HIP(hipMemcpy2DAsync(ctx->d_coarse_inv, sizeof(double) * ld, t_w.p + nc, sizeof(double) * 2 * nc, sizeof(double) * nc, nc,
-                            hipMemcpyDeviceToDevice, ctx->stream));
+    HF_TRY(dense_inverse(ctx, nc, Ac.ptr.data(), Ac.idx.data(), Ac.val.data(), ctx->d_coarse_inv));
     if (f32) {
       HF_TRY(dev_alloc(ctx, &ctx->d_coarse_inv_f, static_cast<size_t>(nc) * ld));
       hipLaunchKernelGGL(k_to_float, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(nc) * ld, ctx->d_coarse_inv, ctx->d_coarse_inv_f);

@@ -36,7 +36,8 @@ EXPORTS = [
     "hf_batch_begin", "hf_batch_load_column", "hf_batch_set_affine", "hf_batch_set_state", "hf_batch_get_state", "hf_batch_run", "hf_batch_run_flux", "hf_batch_end",
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
-    "hf_tangent_setup", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_get_sizes", "hf_get_csr", "hf_spmv", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
+    "hf_tangent_setup", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_get_sizes", "hf_get_csr", "hf_spmv",
+    "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
 
 
@@ -142,6 +143,9 @@ def load_library():
         "hf_get_sizes": [vp, pi, pi, C.POINTER(i64), pi],
         "hf_get_csr": [vp, pi, pi, pd, pd],
         "hf_spmv": [vp, i32, pd, pd],
+        "hf_amg_apply": [vp, pd, pd, pd],
+        "hf_batch_apply_precond": [vp, pd, pd, pd],
+        "hf_dense_inverse": [vp, i32, pi, pi, pd, pd, pd, pd, pd],
         "hf_time_kernel": [vp, i32, i32, pd],
         "hf_last_gpu_ms": [vp, pd],
         "hf_set_profile": [vp, i32],
@@ -597,6 +601,40 @@ class HeatflowHIP:
         y = np.empty(self.n, dtype=np.float64)
         self._check(self._lib.hf_spmv(self._ctx, int(which), _pd(x), _pd(y)))
         return y
+
+    # -- preconditioner test entry points (tests/test_gpu_vcycle.py) ------------------------------------
+    def amg_apply(self, r):
+        """(z, rz): z = B r, one V-cycle as the single-run PCG applies it, and the r.z sum it leaves for PCG."""
+        r = _f64(r)
+        if r.shape != (self.n,):
+            raise ValueError(f"amg_apply: vector of {self.n} entries expected")
+        z = np.empty(self.n, dtype=np.float64)
+        rz = C.c_double()
+        self._check(self._lib.hf_amg_apply(self._ctx, _pd(r), _pd(z), C.byref(rz)))
+        return z, rz.value
+
+    def batch_apply_precond(self, R):
+        """(Z, rz): the batched V-cycle of the open batch on the columns R[j] (shape (nv, n)), and the nv r.z values."""
+        R = _f64(R)
+        if R.shape != (self.batch_nv, self.n):
+            raise ValueError(f"batch_apply_precond: array of shape ({self.batch_nv}, {self.n}) expected")
+        Z = np.empty_like(R)
+        rz = np.empty(self.batch_nv, dtype=np.float64)
+        self._check(self._lib.hf_batch_apply_precond(self._ctx, _pd(R), _pd(Z), _pd(rz)))
+        return Z, rz
+
+    def dense_inverse(self, S, b):
+        """(inv, x64, x32) of the coarsest level's dense solve on the SPD scipy sparse matrix S: the f64 inverse formed on
+        the device, inv @ b through the f64 dense mat-vec, and through the f32 one on float(inv)."""
+        S = S.tocsr()
+        S.sort_indices()
+        n = S.shape[0]
+        ptr, idx, val, b = _i32(S.indptr), _i32(S.indices), _f64(S.data), _f64(b)
+        inv = np.empty((n, n), dtype=np.float64)
+        x64 = np.empty(n, dtype=np.float64)
+        x32 = np.empty(n, dtype=np.float64)
+        self._check(self._lib.hf_dense_inverse(self._ctx, int(n), _pi(ptr), _pi(idx), _pd(val), _pd(b), _pd(inv), _pd(x64), _pd(x32)))
+        return inv, x64, x32
 
     def time_kernel(self, which, reps=50):
         ms = C.c_double()

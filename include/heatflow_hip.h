@@ -372,6 +372,28 @@ int hf_get_csr(hf_ctx* ctx, int32_t* rowptr, int32_t* colidx, double* A, double*
 /* y = A x (which = 0) or y = M x (which = 1) through the SpMV kernel; host vectors. */
 int hf_spmv(hf_ctx* ctx, int32_t which, const double* x, double* y);
 
+/* Test and diagnosis entry points of the multigrid preconditioner: each runs the production code path on its own, so
+ * that a test can compare what the device computes with a restatement of the same algebra (tests/vcycle_oracle.py).
+ *   hf_amg_apply           z = B r: one V(1,1) cycle exactly as the single-run PCG applies it (needs hf_set_precond(1, ...)
+ *                          and hf_assemble, else HF_ERR_STATE), starting from z0 = w0 D^-1 r; *rz (may be NULL) = the host sum
+ *                          of the r.z partial slots the cycle leaves for PCG.  The level vectors the cycle writes are set to
+ *                          NaN before it runs (an entry read before it is written shows in z); r, z host vectors of n.
+ *   hf_batch_apply_precond the batched cycle of the open batch (HF_ERR_STATE without one) on nv host columns of length n,
+ *                          column j at r + j n / z + j n, from z0_j = w0 D_j^-1 r_j (D^-1 per column for per-column and
+ *                          affine operators); rz (may be NULL) receives the nv reduced r.z values.  Every column runs.
+ *   hf_dense_inverse       the coarsest level's dense inverse (blocked Gauss-Jordan on the device) of any SPD matrix of
+ *                          1 <= n <= 4096 rows given in CSR form (else HF_ERR_ARG): inv (n x n, row-major, may be NULL),
+ *                          x64 = the f64 dense mat-vec inv b and x32 = the same with the inverse rounded to float (either
+ *                          may be NULL; b is needed for them).  Works on temporaries of its own: any hierarchy of the
+ *                          context stays as it was, and the context needs no mesh.
+ * Diagnosis only: hf_amg_apply overwrites the context's PCG vectors (r, z and the cycle's work vectors) and its device
+ * scalars, hf_batch_apply_precond those of the open batch (r, z, every column's PCG scalars); a solve in progress cannot
+ * be continued after them.  Start the next hf_step / hf_run / hf_batch_run from its own state (both leave u alone). */
+int hf_amg_apply(hf_ctx* ctx, const double* r, double* z, double* rz);
+int hf_batch_apply_precond(hf_ctx* ctx, const double* r, double* z, double* rz);
+int hf_dense_inverse(hf_ctx* ctx, int32_t n, const int32_t* ptr, const int32_t* idx, const double* val, const double* b,
+                     double* inv, double* x64, double* x32);
+
 /* Average duration (ms) of `reps` back-to-back launches of one kernel on the ctx stream,
  * bracketed by HIP events on that stream. */
 int hf_time_kernel(hf_ctx* ctx, int32_t which, int32_t reps, double* ms_avg);
