@@ -2,8 +2,13 @@
 """Headline benchmark: DOF-updates/s of the backward-Euler time loop on geballe_with_diamond
 refined to ~1M DOF (BASELINE.json configs[2] / BASELINE.md C3).
 
-    python bench.py --gpus N --steps K --warmup W [--workload c3|sweep64] [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--workload c3|sweep64] [--dump-outputs DIR] [--full]
 
+* a plain run does only what the headline needs: it sets up, warms up, times the K steps, writes its outputs if
+  ``--dump-outputs`` is given and prints the JSON line (``roofline`` and ``cpu_baseline`` are null in it).  Everything
+  else below - roofline figures and the runs they take, PMC traffic, the Jacobi-PCG record, the C5 sweep as a side
+  measurement of the default workload, the HBM-resident point, the CPU baselines and farms - runs only with ``--full``;
+  the options that tune those measurements have no effect without it.
 * ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment: this process starts the N ranks itself
   (``python -m torch.distributed.run --nproc-per-node N bench.py ...`` as a fresh child, before torch or HIP
   is touched here) and forwards the child's single JSON line.  Under an outside launcher (the driver's
@@ -19,8 +24,8 @@ refined to ~1M DOF (BASELINE.json configs[2] / BASELINE.md C3).
 * workload ``sweep64`` (BASELINE C5): 64 kappa_sample values (parameter_sweep.get_k_values(count=64)) at stock
   mesh size, point i -> rank i mod world, batches of up to 16 points per time loop (hf_batch_*), 2 loops in flight per rank; K = time steps per point (default: the
   config's 100), W = untimed steps every solver session runs first.  value = 64*n*K / wall of the point loop
-  (max over ranks), "strong" scaling (the 64 points are fixed).  The same sweep is also run as a side
-  measurement of the default workload (``config.sweep64``; ``--sweep-points 0`` skips it).
+  (max over ranks), "strong" scaling (the 64 points are fixed).  With ``--full`` the same sweep is also run as a
+  side measurement of the default workload (``config.sweep64``; ``--sweep-points 0`` skips it).
 * roofline: the dominant kernel is the PCG iteration head k_spmv<9> (CSR SpMV A z with the direction
   update p <- z + beta p, Ap <- A z + beta Ap fused).  achieved = algorithmic bytes per launch
   (SpMV 12*nnz + 20*n of SURVEY.md section 8d, plus 24*n for reading the old p and Ap and writing p)
@@ -104,6 +109,11 @@ def parse_args(argv=None):
                     help="roofline.traffic (HBM bytes of the dominant kernel per launch, PMC): live = measured now by two child runs of this "
                          "script under `rocprofv3 --pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (N = 1; +15-20 s), falling back to the figures kept "
                          "under profiles/ when the profiler is not available; file = those figures only")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline (rooflines, PMC traffic, Jacobi-PCG record, C5 side sweep, "
+                         "HBM-resident point, CPU baselines); a plain run does only the headline.  --cpu-steps, --profile-steps, "
+                         "--jacobi-steps, --sweep-points, --hbm-scale, --cpu-farm-points, --cpu-farm-procs, --batch-roofline and "
+                         "--traffic act only with it")
     ap.add_argument("--pmc-child", choices=["c3", "batch"], default=None, help=argparse.SUPPRESS)
     ap.add_argument("--cpu-farm-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--rendezvous-only", action="store_true",
@@ -766,7 +776,7 @@ def main(argv=None):
         return spawn_ranks(args, argv)
     # C5's CPU baseline is a pool of processes: it runs to completion here, before this process touches the GPU
     farm = farm8 = None
-    if (int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.cpu_farm_points > 0 and not args.rendezvous_only
+    if (args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1 and args.cpu_farm_points > 0 and not args.rendezvous_only
             and (args.workload == "sweep64" or (args.sweep_points > 0 and args.cpu_steps > 0))):
         farm_steps = args.steps if args.workload == "sweep64" else 100
         farm = run_cpu_farm(args, farm_steps)
@@ -807,7 +817,7 @@ def main(argv=None):
         if rank == 0:
             if args.dump_outputs is not None:
                 dump_outputs(args.dump_outputs, {"watchers": sw.pop("watchers")})
-            roof = batch_head_roofline(dev_index, args.sweep_batch, traffic_mode=args.traffic) if (world == 1 and args.batch_roofline and args.sweep_batch > 1) else None
+            roof = batch_head_roofline(dev_index, args.sweep_batch, traffic_mode=args.traffic) if (args.full and world == 1 and args.batch_roofline and args.sweep_batch > 1) else None
             out = dict(common, metric="DOF-updates/s (timesteps/s x nDOF) on geballe_with_diamond", value=sw["value"],
                        ms_per_step=1e3 * sw["wall_s"] / args.steps, scaling="strong",
                        config={"workload": sw["workload"], "solver": SOLVER_TEXT, "precision": PRECISION_TEXT,
@@ -861,40 +871,41 @@ def main(argv=None):
     if args.dump_outputs is not None and rank == 0:       # before the profiled steps below advance the state
         dump_outputs(args.dump_outputs, {"temperature": prob.state()})
 
-    # ---- dominant kernel k_spmv<9>: vals 8 + colidx 4 per nnz; per row rowptr 4, z 8 (gathered operand),
-    # Ap 8+8 and p 8+8 (read-modify-write by the direction recurrence) = 12*nnz + 44*n (SURVEY 8d formula bytes)
-    k_us = kernel_rooflines(be, prob, hb, heated, args.warmup + args.steps, args.profile_steps)
-    spmv_bytes = 12 * nnz + 44 * n
-    spmv_us = k_us["spmv9_in_loop"] if k_us["spmv9_in_loop"] else k_us["spmv9_back_to_back"]
-    achieved = spmv_bytes / (spmv_us * 1e-6) / 1e9
-    stream_gbs = 12 * nnz / (k_us["stream_read"] * 1e-6) / 1e9
-    # HBM traffic of that kernel from the PMC passes kept under profiles/ (rocprofv3 cannot wrap itself):
-    # only quoted when it was collected on exactly this matrix
-    traffic, traffic_note = None, "not measured"
-    if args.traffic == "live" and world == 1:
-        traffic, traffic_note = live_traffic("c3", r"k_spmv<9, ", ["--scale", str(args.scale)])
-        if traffic is None:
-            traffic_note = f"live measurement not available ({traffic_note}); "
-    if traffic is None and args.traffic != "none":
-        try:
-            with open(os.path.join(ROOT, "profiles", "pmc_traffic_latest.json")) as f:
-                pmc = json.load(f)
-            if pmc["n"] == n and pmc["nnz"] == nnz:
-                traffic = pmc["kernels"]["k_spmv<9>"]["hbm_bytes"]
-                traffic_note = (traffic_note if traffic_note.startswith("live") else "") + \
-                    "figure kept under profiles/pmc_traffic_latest.json (same matrix; rocprofv3 --pmc passes of scripts/profile_round.sh)"
-        except (OSError, KeyError, ValueError):
-            pass
-    moved = traffic if traffic else 10 * nnz + 44 * n
+    if args.full:
+        # ---- dominant kernel k_spmv<9>: vals 8 + colidx 4 per nnz; per row rowptr 4, z 8 (gathered operand),
+        # Ap 8+8 and p 8+8 (read-modify-write by the direction recurrence) = 12*nnz + 44*n (SURVEY 8d formula bytes)
+        k_us = kernel_rooflines(be, prob, hb, heated, args.warmup + args.steps, args.profile_steps)
+        spmv_bytes = 12 * nnz + 44 * n
+        spmv_us = k_us["spmv9_in_loop"] if k_us["spmv9_in_loop"] else k_us["spmv9_back_to_back"]
+        achieved = spmv_bytes / (spmv_us * 1e-6) / 1e9
+        stream_gbs = 12 * nnz / (k_us["stream_read"] * 1e-6) / 1e9
+        # HBM traffic of that kernel from the PMC passes kept under profiles/ (rocprofv3 cannot wrap itself):
+        # only quoted when it was collected on exactly this matrix
+        traffic, traffic_note = None, "not measured"
+        if args.traffic == "live" and world == 1:
+            traffic, traffic_note = live_traffic("c3", r"k_spmv<9, ", ["--scale", str(args.scale)])
+            if traffic is None:
+                traffic_note = f"live measurement not available ({traffic_note}); "
+        if traffic is None and args.traffic != "none":
+            try:
+                with open(os.path.join(ROOT, "profiles", "pmc_traffic_latest.json")) as f:
+                    pmc = json.load(f)
+                if pmc["n"] == n and pmc["nnz"] == nnz:
+                    traffic = pmc["kernels"]["k_spmv<9>"]["hbm_bytes"]
+                    traffic_note = (traffic_note if traffic_note.startswith("live") else "") + \
+                        "figure kept under profiles/pmc_traffic_latest.json (same matrix; rocprofv3 --pmc passes of scripts/profile_round.sh)"
+            except (OSError, KeyError, ValueError):
+                pass
+        moved = traffic if traffic else 10 * nnz + 44 * n
     amg_info = be.amg_info() if precond == 1 else None
     asm_roof = None
-    if world == 1:
+    if args.full and world == 1:
         be.set_precond(0, False)          # the element kernel is timed without a multigrid set-up behind every re-assembly
         asm_roof = assembly_rooflines(be, prob, hb, n, ne, nnz)
 
     # ---- for the record: the plain Jacobi-PCG loop (north-star solver) on the same steps
     jacobi = None
-    if precond == 1 and args.jacobi_steps > 0 and world == 1:
+    if args.full and precond == 1 and args.jacobi_steps > 0 and world == 1:
         be.assemble(prob.dt, prob.assembly_mode)
         prob.set_state(float(cfg["heating"]["ic_temp"]))
         if args.warmup > 0:
@@ -917,63 +928,65 @@ def main(argv=None):
             "pcg_rtol": prob.rtol, "pcg_iters_per_step_mean": float(np.mean(iters)), "pcg_iters_per_step_max": int(np.max(iters)),
             "points": "1 sweep point per GPU (kappa_sample = 3.8 + 0.02*rank)" if world > 1 else "1 run",
             "gpu_ms_per_step_events": gpu_ms / args.steps, "rank0_setup_s": setup_s}
-        out["roofline"] = {
-            "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-            "traffic": traffic,
-            "kernel": "k_spmv<9> (PCG iteration head: CSR SpMV with the direction update p, Ap fused)",
-            "bytes_per_launch": spmv_bytes, "us_per_launch": spmv_us,
-            "timing": ("in-loop: kernel-attached HIP events on the k_spmv<9> launches of the time loop"
-                       if k_us["spmv9_in_loop"] else "back-to-back launches (no in-loop sample)"),
-            "cache_resident": bool(12 * nnz + 64 * n < 256 * 2**20),
-            "note": ("at this size the iteration's working set sits in the 256 MiB Infinity Cache: frac is against the HBM "
-                     "peak but is not an HBM measurement - see hbm_resident"),
-            "us_back_to_back": {k: v for k, v in k_us.items() if k.endswith("back_to_back")},
-            "frac_back_to_back": spmv_bytes / (k_us["spmv9_back_to_back"] * 1e-6) / 1e9 / HBM_PEAK_GBS,
-            "bytes_moved_per_launch": moved,
-            "frac_bytes_moved": moved / (spmv_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-            "bytes_moved_note": "PMC traffic when collected on this matrix, else 10*nnz + 44*n (16-bit column stream)",
-            "traffic_source": traffic_note,
-            "measured_stream_read": {"GB/s": stream_gbs, "us": k_us["stream_read"], "bytes": 12 * nnz,
-                                     "what": "16-byte-load read of the operator's values + column indices on this box",
-                                     "frac_of_it": achieved / stream_gbs},
-            "assembly": asm_roof, "hbm_resident": None}
-        if precond == 1:
-            # the whole multigrid-PCG iteration (iteration head, update, V-cycle: 10 launches at C3): HBM bytes = the per-launch PMC
-            # means kept under profiles/ (scripts/pmc_summary.py; only quoted for exactly this matrix), over the time the loop
-            # spends per iteration - right-hand side, start vector, first residual and the extra cycle of every step included
-            try:
-                with open(os.path.join(ROOT, "profiles", "pmc_traffic_latest.json")) as f:
-                    pmc_it = json.load(f)
-                if pmc_it["n"] == n and pmc_it["nnz"] == nnz and pmc_it.get("multigrid_iteration"):
-                    it_bytes = float(pmc_it["multigrid_iteration"]["bytes"])
-                    it_us = 1e3 * (1e3 * elapsed / args.steps) / max(float(np.mean(iters)), 1.0)
-                    out["roofline"]["multigrid_pcg_iteration"] = {
-                        "bytes": it_bytes, "bytes_source": "profiles/pmc_traffic_latest.json (rocprofv3 --pmc passes of scripts/profile_round.sh, same matrix): mean HBM bytes per launch, summed over the launches of one iteration",
-                        "us_per_iteration_in_loop": it_us, "achieved": it_bytes / (it_us * 1e-6) / 1e9,
-                        "frac": it_bytes / (it_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                        "note": "time per iteration = time per step / iterations per step: includes the step's right-hand side, start vector, first residual and first cycle; the launches of one iteration alone take 119-122 us under rocprofv3 (profiles/r03_c3_iteration_breakdown.txt)"}
-            except (OSError, KeyError, ValueError):
-                pass
-        if jacobi is not None:
-            # the whole Jacobi-PCG iteration = iteration head + update, 12*nnz + 84*n bytes, over the time the
-            # loop really spends per iteration (steps incl. right-hand side and start vector / iterations)
-            it_us = 1e3 * jacobi["ms_per_step"] / max(jacobi["pcg_iters_per_step_mean"], 1.0)
-            it_bytes = 12 * nnz + 84 * n
-            out["roofline"]["jacobi_pcg_iteration"] = {
-                "bytes": it_bytes, "formula": "12*nnz + 84*n (SURVEY 8d: SpMV + x, r, p read-modify-write + Ap, dinv reads)",
-                "us_per_iteration_in_loop": it_us, "achieved": it_bytes / (it_us * 1e-6) / 1e9,
-                "frac": it_bytes / (it_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
-                "us_kernels_back_to_back": k_us["spmv9_back_to_back"] + k_us["update_back_to_back"]}
+        out["roofline"] = None
+        if args.full:
+            out["roofline"] = {
+                "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                "traffic": traffic,
+                "kernel": "k_spmv<9> (PCG iteration head: CSR SpMV with the direction update p, Ap fused)",
+                "bytes_per_launch": spmv_bytes, "us_per_launch": spmv_us,
+                "timing": ("in-loop: kernel-attached HIP events on the k_spmv<9> launches of the time loop"
+                           if k_us["spmv9_in_loop"] else "back-to-back launches (no in-loop sample)"),
+                "cache_resident": bool(12 * nnz + 64 * n < 256 * 2**20),
+                "note": ("at this size the iteration's working set sits in the 256 MiB Infinity Cache: frac is against the HBM "
+                         "peak but is not an HBM measurement - see hbm_resident"),
+                "us_back_to_back": {k: v for k, v in k_us.items() if k.endswith("back_to_back")},
+                "frac_back_to_back": spmv_bytes / (k_us["spmv9_back_to_back"] * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                "bytes_moved_per_launch": moved,
+                "frac_bytes_moved": moved / (spmv_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                "bytes_moved_note": "PMC traffic when collected on this matrix, else 10*nnz + 44*n (16-bit column stream)",
+                "traffic_source": traffic_note,
+                "measured_stream_read": {"GB/s": stream_gbs, "us": k_us["stream_read"], "bytes": 12 * nnz,
+                                         "what": "16-byte-load read of the operator's values + column indices on this box",
+                                         "frac_of_it": achieved / stream_gbs},
+                "assembly": asm_roof, "hbm_resident": None}
+            if precond == 1:
+                # the whole multigrid-PCG iteration (iteration head, update, V-cycle: 10 launches at C3): HBM bytes = the per-launch PMC
+                # means kept under profiles/ (scripts/pmc_summary.py; only quoted for exactly this matrix), over the time the loop
+                # spends per iteration - right-hand side, start vector, first residual and the extra cycle of every step included
+                try:
+                    with open(os.path.join(ROOT, "profiles", "pmc_traffic_latest.json")) as f:
+                        pmc_it = json.load(f)
+                    if pmc_it["n"] == n and pmc_it["nnz"] == nnz and pmc_it.get("multigrid_iteration"):
+                        it_bytes = float(pmc_it["multigrid_iteration"]["bytes"])
+                        it_us = 1e3 * (1e3 * elapsed / args.steps) / max(float(np.mean(iters)), 1.0)
+                        out["roofline"]["multigrid_pcg_iteration"] = {
+                            "bytes": it_bytes, "bytes_source": "profiles/pmc_traffic_latest.json (rocprofv3 --pmc passes of scripts/profile_round.sh, same matrix): mean HBM bytes per launch, summed over the launches of one iteration",
+                            "us_per_iteration_in_loop": it_us, "achieved": it_bytes / (it_us * 1e-6) / 1e9,
+                            "frac": it_bytes / (it_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                            "note": "time per iteration = time per step / iterations per step: includes the step's right-hand side, start vector, first residual and first cycle; the launches of one iteration alone take 119-122 us under rocprofv3 (profiles/r03_c3_iteration_breakdown.txt)"}
+                except (OSError, KeyError, ValueError):
+                    pass
+            if jacobi is not None:
+                # the whole Jacobi-PCG iteration = iteration head + update, 12*nnz + 84*n bytes, over the time the
+                # loop really spends per iteration (steps incl. right-hand side and start vector / iterations)
+                it_us = 1e3 * jacobi["ms_per_step"] / max(jacobi["pcg_iters_per_step_mean"], 1.0)
+                it_bytes = 12 * nnz + 84 * n
+                out["roofline"]["jacobi_pcg_iteration"] = {
+                    "bytes": it_bytes, "formula": "12*nnz + 84*n (SURVEY 8d: SpMV + x, r, p read-modify-write + Ap, dinv reads)",
+                    "us_per_iteration_in_loop": it_us, "achieved": it_bytes / (it_us * 1e-6) / 1e9,
+                    "frac": it_bytes / (it_us * 1e-6) / 1e9 / HBM_PEAK_GBS,
+                    "us_kernels_back_to_back": k_us["spmv9_back_to_back"] + k_us["update_back_to_back"]}
         if precond == 1:
             out["config"]["amg"] = dict(amg_info, precision=PRECISION_TEXT)
         if jacobi is not None:
             out["config"]["jacobi_pcg"] = jacobi
-    # ---- side measurements: the C5 sweep (every N), the HBM-resident roofline point (N = 1)
+    # ---- side measurements (--full): the C5 sweep (every N), the HBM-resident roofline point (N = 1)
     # (the headline's timing and every collective it needs are done: a failure of a side measurement is reported in its place,
     # it does not take the line with it.  N > 1: the sweep's collectives have a deadline of their own - a rank that hangs in one
     # would otherwise end in the process group's watchdog abort and take the finished headline with it)
     sweep = None
-    if args.sweep_points > 0:
+    if args.full and args.sweep_points > 0:
         guard = SideGuard(out if rank == 0 else None, emit, float(os.environ.get("HEATFLOW_BENCH_SIDE_TIMEOUT_S", "150"))) if world > 1 else None
         try:
             sweep = run_sweep64(ranks, args.sweep_points, 100, max(1, args.warmup), args.sweep_concurrent, args.sweep_batch)
@@ -982,11 +995,12 @@ def main(argv=None):
             sweep = {"error": f"{type(e).__name__}: {e}"} if rank == 0 else None
         if guard is not None and not guard.disarm():
             return 0                          # the guard has written the line (and is ending the process)
-    hbm = hbm_resident_point(args.hbm_scale, dev_index, 3) if (world == 1 and args.hbm_scale > 0) else None
+    hbm = hbm_resident_point(args.hbm_scale, dev_index, 3) if (args.full and world == 1 and args.hbm_scale > 0) else None
     batch_roof = batch_head_roofline(dev_index, args.sweep_batch, traffic_mode="file" if args.traffic == "live" else args.traffic) if (world == 1 and sweep is not None and "error" not in sweep and args.batch_roofline and args.sweep_batch > 1) else None
 
     if rank == 0:
-        out["roofline"]["hbm_resident"] = hbm
+        if out["roofline"] is not None:
+            out["roofline"]["hbm_resident"] = hbm
         if sweep is not None and "error" in sweep:
             out["config"]["sweep64"] = sweep
         elif sweep is not None:
@@ -996,7 +1010,7 @@ def main(argv=None):
             if batch_roof is not None:
                 sweep["roofline"] = batch_roof
             out["config"]["sweep64"] = sweep
-        if world == 1 and args.cpu_steps > 0:
+        if args.full and world == 1 and args.cpu_steps > 0:
             out["cpu_baseline"] = cpu_baseline(cfg, mesh, args.cpu_steps, args.warmup)
             out["config"]["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
             if jacobi is not None:

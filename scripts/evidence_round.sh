@@ -4,8 +4,8 @@
 # multigrid-PCG beyond the Infinity Cache, connectivity-table sharing, robustness sweep, operator table.
 tag=$1
 O=gpurun_out
-python bench.py > $O/${tag}_bench.json 2> $O/${tag}_bench.err || exit 1
-HEATFLOW_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 20 --sweep-points 0 --cpu-steps 0 --hbm-scale 0 --jacobi-steps 0 > $O/${tag}_bench_gloo2.json 2> $O/${tag}_bench_gloo2.err || exit 1
+python bench.py --full > $O/${tag}_bench.json 2> $O/${tag}_bench.err || exit 1
+HEATFLOW_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 20 --sweep-points 0 --cpu-steps 0 --hbm-scale 0 --jacobi-steps 0 > $O/${tag}_bench_gloo2.json 2> $O/${tag}_bench_gloo2.err || exit 1
 HEATFLOW_BENCH_BACKEND=gloo python bench.py --gpus 2 --workload sweep64 > $O/${tag}_sweep64_gloo2.json 2> $O/${tag}_sweep64_gloo2.err || exit 1
 { python scripts/gpu_probe.py 0.215 12 3 1 | grep -v "assemble mode" ; python scripts/gpu_probe.py 0.1075 12 3 1 | grep -v "assemble mode"; } > $O/${tag}_amg_large.txt 2>&1 || exit 1
 python scripts/pattern_share_probe.py 0.43 > $O/${tag}_pattern_share.txt 2>&1 || exit 1

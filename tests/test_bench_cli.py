@@ -42,6 +42,15 @@ def test_more_ranks_than_gpus_fails_loudly_with_rccl():
     assert "GPU(s) visible" in p.stderr
 
 
+def test_side_measurements_wait_for_full():
+    """A plain run measures only the headline; --full (off by default) adds every other measurement."""
+    code = (f"import sys; sys.path.insert(0, {ROOT!r}); import bench; "
+            "print(bench.parse_args([]).full, bench.parse_args(['--full', '--steps', '3']).full)")
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert p.stdout.split() == ["False", "True"]
+
+
 def test_bad_arguments_are_rejected():
     p = _run(["--gpus", "0"])
     assert p.returncode != 0

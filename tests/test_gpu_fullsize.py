@@ -291,8 +291,8 @@ def test_c5_sixty_four_point_kappa_sweep_on_one_gpu(hip, tmp_path):
 
 
 def test_bench_line_keeps_its_contract_on_a_small_mesh(hip, tmp_path):
-    """bench.py end to end on a coarse mesh (seconds): exactly one JSON line with the driver's keys, value consistent with
-    ms_per_step, a roofline object for the dominant kernel with live in-loop timing, and a cpu_baseline from the oracle.
+    """bench.py --full end to end on a coarse mesh (seconds): exactly one JSON line with the driver's keys, value consistent
+    with ms_per_step, a roofline object for the dominant kernel with live in-loop timing, and a cpu_baseline from the oracle.
     --dump-outputs writes the field the timed path left after its last step."""
     import json
     import subprocess
@@ -300,7 +300,7 @@ def test_bench_line_keeps_its_contract_on_a_small_mesh(hip, tmp_path):
 
     from conftest import ROOT
 
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "3.0", "--steps", "8", "--warmup", "5", "--cpu-steps", "3",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--scale", "3.0", "--steps", "8", "--warmup", "5", "--cpu-steps", "3",
            "--jacobi-steps", "2", "--sweep-points", "0", "--hbm-scale", "0", "--cpu-farm-points", "0", "--device-warmup-s", "0",
            "--profile-steps", "2", "--dump-outputs", str(tmp_path / "dump")]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
@@ -335,5 +335,39 @@ def test_bench_line_keeps_its_contract_on_a_small_mesh(hip, tmp_path):
         prob.run(5, time_varying=[prob.bcs[3]], first_step=0)
         prob.run(8, time_varying=[prob.bcs[3]], first_step=5)
         assert np.abs(got - prob.state()).max() <= 1e-8
+    finally:
+        prob.close()
+
+
+def test_plain_bench_run_measures_only_the_headline(hip, tmp_path):
+    """bench.py without --full: the headline keys and the field the timed path left after its last step, and nothing beside
+    them - no roofline, no CPU baseline, no Jacobi-PCG record, no side sweep - even when options of those measurements are given."""
+    import json
+    import subprocess
+    import sys
+
+    from conftest import ROOT
+
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "3.0", "--steps", "8", "--warmup", "5", "--cpu-steps", "3",
+           "--jacobi-steps", "2", "--sweep-points", "2", "--device-warmup-s", "0", "--dump-outputs", str(tmp_path / "dump")]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["metric"] == "DOF-updates/s (timesteps/s x nDOF) on geballe_with_diamond"
+    assert out["unit"] == "DOF-updates/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["n_gpus"] == 1 and out["steps"] == 8 and out["warmup"] == 5
+    n = out["config"]["n_dof"]
+    assert abs(out["value"] - n * 8 / (out["ms_per_step"] * 8e-3)) <= 1e-6 * out["value"]
+    assert out["roofline"] is None and out["cpu_baseline"] is None
+    assert not {"jacobi_pcg", "sweep64", "gpu_over_cpu"} & set(out["config"])
+    got = np.load(tmp_path / "dump" / "temperature.npy")
+    cfg, stack, mesh = build_case("geballe_with_diamond", 3.0)
+    prob = make_problem(cfg, stack, mesh, precond=1)
+    try:
+        prob.run(5, time_varying=[prob.bcs[3]], first_step=0)
+        prob.run(8, time_varying=[prob.bcs[3]], first_step=5)
+        assert got.shape == (n,) and np.abs(got - prob.state()).max() <= 1e-8
     finally:
         prob.close()
