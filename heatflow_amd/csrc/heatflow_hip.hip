@@ -87,8 +87,12 @@ void tangent_free(hf_ctx* ctx) {
 void kt_free(hf_ctx* ctx) {
   hf_ctx::KappaT& K = ctx->kt;
   dev_free(&K.hdr); dev_free(&K.vals); dev_free(&K.pic); dev_free(&K.b0); dev_free(&K.change);
+  dev_free(&K.chdr); dev_free(&K.cvals); dev_free(&K.w);
   K = hf_ctx::KappaT();
 }
+
+// "kappa(T)" or "rho_c(T)": the kind of tables a refusal names (conductivity tables first: their texts are the ones of before)
+const char* kt_kind(const hf_ctx* ctx) { return ctx->kt.k_on || !ctx->kt.c_on ? "kappa(T)" : "rho_c(T)"; }
 
 // Upload the tables and size every buffer of the context for the mesh.
 int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int32_t* tri, const int32_t* tag, MeshTables& T) {
@@ -734,7 +738,7 @@ int hf_update_kappa(hf_ctx* ctx, int32_t n_mat, const int32_t* tags, const doubl
     if (tags[i] < 0 || tags[i] >= ctx->tab_len || !ctx->h_tag_used[tags[i]])
       return fail(ctx, HF_ERR_ARG, "hf_update_kappa: tag %d is not a cell tag of the mesh", tags[i]);
     if (!(kappa[i] > 0.0)) return fail(ctx, HF_ERR_ARG, "hf_update_kappa: kappa must be positive");
-    if (ctx->kt.on && ctx->kt.tabled[tags[i]])
+    if (ctx->kt.k_on && ctx->kt.tabled[tags[i]])
       return fail(ctx, HF_ERR_ARG, "hf_update_kappa: tag %d carries a kappa(T) table (hf_set_kappa_tables)", tags[i]);
   }
   for (int32_t i = 0; i < n_mat; ++i) {
@@ -775,7 +779,7 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
   if (!(dt > 0.0)) return fail(ctx, HF_ERR_ARG, "hf_assemble: dt must be positive");
   if (mode < 0 || mode > 3) return fail(ctx, HF_ERR_ARG, "hf_assemble: unknown mode %d", mode);
   if (ctx->kt.on && mode != HF_ASM_ROW_GATHER)
-    return fail(ctx, HF_ERR_ARG, "hf_assemble: kappa(T) tables are evaluated by the row-gather kernel only (HF_ASM_ROW_GATHER)");
+    return fail(ctx, HF_ERR_ARG, "hf_assemble: %s tables are evaluated by the row-gather kernel only (HF_ASM_ROW_GATHER)", kt_kind(ctx));
   HF_HIP(hipSetDevice(ctx->dev));
   ctx->dt_step = dt;
   ctx->dt = ctx->scheme == HF_TIME_BDF2 ? 2.0 * dt / 3.0 : dt;   // BDF2: A' = M + (2/3) dt K
@@ -784,6 +788,7 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
   HF_TRY(launch_assemble(ctx));
   if (ctx->kt.on) {
     // kappa(T): M as assembled above, A re-valued at the current state, then elimination, lifting values and D^-1
+    // (capacity tables: M re-valued by the same launch)
     HF_TRY(kt_revalue(ctx, ctx->d_u, nullptr));
   } else {
     if (ctx->nbc > 0) {
@@ -849,62 +854,109 @@ int hf_set_time_scheme(hf_ctx* ctx, int32_t scheme) {
   return HF_OK;
 }
 
-int hf_set_kappa_tables(hf_ctx* ctx, int32_t n_tab, const int32_t* tags, const double* t0, const double* dT, const int32_t* n_knots,
-                        const double* values, int32_t picard_sweeps) {
+// hf_set_kappa_tables (cap = false) and hf_set_rhoc_tables (cap = true): one check list and one table layout.  Clearing one kind
+// leaves the other; the buffers of the Picard loop live while either is set.
+int kt_set_tables(hf_ctx* ctx, bool cap, int32_t n_tab, const int32_t* tags, const double* t0, const double* dT, const int32_t* n_knots,
+                  const double* values) {
+  const char* fn = cap ? "hf_set_rhoc_tables" : "hf_set_kappa_tables";
+  const char* what = cap ? "rho_c(T)" : "kappa(T)";
   if (!ctx) return HF_ERR_ARG;
-  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_set_kappa_tables before hf_set_mesh");
-  if (n_tab < 0) return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: negative table count");
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "%s before hf_set_mesh", fn);
+  if (n_tab < 0) return fail(ctx, HF_ERR_ARG, "%s: negative table count", fn);
   HF_HIP(hipSetDevice(ctx->dev));
-  if (n_tab == 0) {   // clear: every path is the constant-kappa one again
-    if (ctx->kt.on) {
+  hf_ctx::KappaT& K = ctx->kt;
+  if (n_tab == 0) {   // clear: without tables of the other kind every path is the constant-coefficient one again
+    if (cap ? K.c_on : K.k_on) {
       free_batch(ctx);
       ctx->assembled = false;
       ctx->pred_iters = 0;
     }
-    kt_free(ctx);
+    if (!(cap ? K.k_on : K.c_on)) { kt_free(ctx); return HF_OK; }
+    if (cap ? K.c_on : K.k_on) {
+      const std::vector<KTab> none(64, KTab{0.0, 0.0, 0, 0});
+      HF_HIP(copy_sync(ctx, cap ? K.chdr : K.hdr, none.data(), sizeof(KTab) * 64, hipMemcpyHostToDevice));
+      dev_free(cap ? &K.cvals : &K.vals);
+      (cap ? K.ctabled : K.tabled).clear();
+      (cap ? K.c_on : K.k_on) = false;
+      K.have_change = false;
+    }
     return HF_OK;
   }
-  if (!tags || !t0 || !dT || !n_knots || !values) return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: null pointer");
-  if (picard_sweeps < 1 || picard_sweeps > KT_MAX_PICARD)
-    return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: picard_sweeps %d outside 1..%d", picard_sweeps, KT_MAX_PICARD);
+  if (!tags || !t0 || !dT || !n_knots || !values) return fail(ctx, HF_ERR_ARG, "%s: null pointer", fn);
   if (!ctx->rg_ok || (ctx->assembled && ctx->mode != HF_ASM_ROW_GATHER))
-    return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: kappa(T) is evaluated by the row-gather kernel only (HF_ASM_ROW_GATHER on a mesh with row-gather lists)");
+    return fail(ctx, HF_ERR_ARG, "%s: %s is evaluated by the row-gather kernel only (HF_ASM_ROW_GATHER on a mesh with row-gather lists)", fn, what);
+  if (cap && ct_smem_bytes(ctx->max_blk_nnz, ctx->rg_max_dict) + 2 * 64 * sizeof(KTab) > 160 * 1024)
+    return fail(ctx, HF_ERR_ARG, "%s: the (M, A) slab, the staged state and the table headers of this mesh exceed the 160 KiB of LDS", fn);
   std::vector<KTab> hdr(64, KTab{0.0, 0.0, 0, 0});
   std::vector<double> vals;
   std::vector<char> tabled(ctx->tab_len, 0);
   for (int32_t i = 0; i < n_tab; ++i) {
     const int32_t tg = tags[i];
-    if (tg < 0 || tg >= ctx->tab_len || !ctx->h_tag_used[tg]) return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: tag %d is not a cell tag of the mesh", tg);
-    if (tabled[tg]) return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: tag %d listed twice", tg);
+    if (tg < 0 || tg >= ctx->tab_len || !ctx->h_tag_used[tg]) return fail(ctx, HF_ERR_ARG, "%s: tag %d is not a cell tag of the mesh", fn, tg);
+    if (tabled[tg]) return fail(ctx, HF_ERR_ARG, "%s: tag %d listed twice", fn, tg);
     if (n_knots[i] < 2 || n_knots[i] > KT_MAX_KNOTS)
-      return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: table of tag %d has %d knots (2..%d)", tg, n_knots[i], KT_MAX_KNOTS);
+      return fail(ctx, HF_ERR_ARG, "%s: table of tag %d has %d knots (2..%d)", fn, tg, n_knots[i], KT_MAX_KNOTS);
     if (!std::isfinite(t0[i]) || !(dT[i] > 0.0) || !std::isfinite(dT[i]) || !std::isfinite(t0[i] + (n_knots[i] - 1) * dT[i]))
-      return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: table of tag %d: T0 finite and dT > 0 needed", tg);
+      return fail(ctx, HF_ERR_ARG, "%s: table of tag %d: T0 finite and dT > 0 needed", fn, tg);
     tabled[tg] = 1;
     const size_t q = std::find(ctx->h_rg_tags.begin(), ctx->h_rg_tags.end(), tg) - ctx->h_rg_tags.begin();
-    if (q >= ctx->h_rg_tags.size()) return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: tag %d has no row-gather dictionary entry", tg);
+    if (q >= ctx->h_rg_tags.size()) return fail(ctx, HF_ERR_ARG, "%s: tag %d has no row-gather dictionary entry", fn, tg);
     hdr[q] = KTab{t0[i], 1.0 / dT[i], n_knots[i], static_cast<int>(vals.size())};
     for (int32_t k = 0; k < n_knots[i]; ++k) {     // values: the tables' knots concatenated in the order of `tags`
       const double v = values[vals.size()];
-      if (!(v > 0.0) || !std::isfinite(v)) return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: value %d of the table of tag %d is not positive and finite", k, tg);
+      if (!(v > 0.0) || !std::isfinite(v)) return fail(ctx, HF_ERR_ARG, "%s: value %d of the table of tag %d is not positive and finite", fn, k, tg);
       vals.push_back(v);
     }
   }
-  kt_free(ctx);
   free_batch(ctx);
-  hf_ctx::KappaT& K = ctx->kt;
-  HF_TRY(dev_alloc(ctx, &K.hdr, 64));
-  HF_TRY(dev_alloc(ctx, &K.vals, vals.size()));
-  HF_TRY(dev_alloc(ctx, &K.pic, ctx->n));
-  HF_TRY(dev_alloc(ctx, &K.b0, ctx->n));
-  HF_TRY(dev_alloc(ctx, &K.change, 1));
-  HF_HIP(copy_sync(ctx, K.hdr, hdr.data(), sizeof(KTab) * 64, hipMemcpyHostToDevice));
-  HF_HIP(copy_sync(ctx, K.vals, vals.data(), sizeof(double) * vals.size(), hipMemcpyHostToDevice));
-  K.tabled = std::move(tabled);
-  K.picard = picard_sweeps;
+  if (!K.hdr) {   // first tables of either kind: the buffers of the loop
+    HF_TRY(dev_alloc(ctx, &K.hdr, 64));
+    HF_TRY(dev_alloc(ctx, &K.pic, ctx->n));
+    HF_TRY(dev_alloc(ctx, &K.b0, ctx->n));
+    HF_TRY(dev_alloc(ctx, &K.change, 1));
+  }
+  if (cap && !K.chdr) {   // first capacity tables: their headers, the sweeps' operand, and empty conductivity headers if none are set
+    HF_TRY(dev_alloc(ctx, &K.chdr, 64));
+    HF_TRY(dev_alloc(ctx, &K.w, ctx->n));
+    if (!K.k_on) {
+      const std::vector<KTab> none(64, KTab{0.0, 0.0, 0, 0});
+      HF_HIP(copy_sync(ctx, K.hdr, none.data(), sizeof(KTab) * 64, hipMemcpyHostToDevice));
+    }
+  }
+  double*& dvals = cap ? K.cvals : K.vals;
+  dev_free(&dvals);
+  HF_TRY(dev_alloc(ctx, &dvals, vals.size()));
+  HF_HIP(copy_sync(ctx, cap ? K.chdr : K.hdr, hdr.data(), sizeof(KTab) * 64, hipMemcpyHostToDevice));
+  HF_HIP(copy_sync(ctx, dvals, vals.data(), sizeof(double) * vals.size(), hipMemcpyHostToDevice));
+  (cap ? K.ctabled : K.tabled) = std::move(tabled);
+  (cap ? K.c_on : K.k_on) = true;
   K.on = true;
+  K.have_change = false;
   ctx->assembled = false;
   ctx->pred_iters = 0;
+  return HF_OK;
+}
+
+int hf_set_kappa_tables(hf_ctx* ctx, int32_t n_tab, const int32_t* tags, const double* t0, const double* dT, const int32_t* n_knots,
+                        const double* values, int32_t picard_sweeps) {
+  if (ctx && ctx->have_mesh && n_tab > 0 && tags && t0 && dT && n_knots && values &&
+      (picard_sweeps < 1 || picard_sweeps > KT_MAX_PICARD))
+    return fail(ctx, HF_ERR_ARG, "hf_set_kappa_tables: picard_sweeps %d outside 1..%d", picard_sweeps, KT_MAX_PICARD);
+  HF_TRY(kt_set_tables(ctx, false, n_tab, tags, t0, dT, n_knots, values));
+  if (n_tab > 0) ctx->kt.picard = picard_sweeps;
+  return HF_OK;
+}
+
+int hf_set_rhoc_tables(hf_ctx* ctx, int32_t n_tab, const int32_t* tags, const double* t0, const double* dT, const int32_t* n_knots,
+                       const double* values) {
+  return kt_set_tables(ctx, true, n_tab, tags, t0, dT, n_knots, values);
+}
+
+int hf_set_picard(hf_ctx* ctx, int32_t sweeps) {
+  if (!ctx) return HF_ERR_ARG;
+  if (sweeps < 1 || sweeps > KT_MAX_PICARD) return fail(ctx, HF_ERR_ARG, "hf_set_picard: sweeps %d outside 1..%d", sweeps, KT_MAX_PICARD);
+  if (!ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_set_picard: no tables are set (hf_set_kappa_tables / hf_set_rhoc_tables first)");
+  ctx->kt.picard = sweeps;
   return HF_OK;
 }
 
@@ -1240,7 +1292,7 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
 int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup before hf_set_mesh");
-  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: kappa(T) tables are set (tangents of the nonlinear loop are not supported)");
+  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: %s tables are set (tangents of the nonlinear loop are not supported)", kt_kind(ctx));
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a batch is open");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a load is set (tangents of pre-heated runs are not supported)");
   if (n_par < 1 || n_par > NV_MAX) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: 1..%d parameters (got %d)", NV_MAX, n_par);
@@ -1278,7 +1330,7 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
                    int32_t ns, const int32_t* nodes, double* samples, int32_t* iters, double* tangent_samples, int32_t* tangent_iters) {
   if (!ctx) return HF_ERR_ARG;
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a batch is open");
-  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: kappa(T) tables are set (tangents of the nonlinear loop are not supported)");
+  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: %s tables are set (tangents of the nonlinear loop are not supported)", kt_kind(ctx));
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a load is set (tangents of pre-heated runs are not supported)");
   if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_run_tangent before hf_tangent_setup");
   if (ctx->tan.steady_state)
@@ -1366,7 +1418,7 @@ int hf_get_tangent(hf_ctx* ctx, int32_t j, double* s) {
 int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t precond) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->have_mesh || !ctx->have_mat) return fail(ctx, HF_ERR_STATE, "hf_steady_setup needs hf_set_mesh and hf_set_materials first");
-  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_steady_setup: kappa(T) tables are set (a Picard steady state is not supported)");
+  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_steady_setup: %s tables are set (a Picard steady state is not supported)", kt_kind(ctx));
   if (n_s <= 0 || !dofs) return fail(ctx, HF_ERR_ARG, "hf_steady_setup: empty Dirichlet set (the stiffness alone is singular)");
   if (precond < 0 || precond > 1) return fail(ctx, HF_ERR_ARG, "hf_steady_setup: unknown preconditioner %d", precond);
   if (!ctx->rg_ok || (ctx->assembled && ctx->mode != HF_ASM_ROW_GATHER))
@@ -1418,7 +1470,7 @@ int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t preco
 int hf_steady_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, double rtol, double atol, int32_t max_it, int32_t* iters,
                     double* resid) {
   if (!ctx) return HF_ERR_ARG;
-  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_steady_solve: kappa(T) tables are set (a Picard steady state is not supported)");
+  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_steady_solve: %s tables are set (a Picard steady state is not supported)", kt_kind(ctx));
   if (!ctx->steady.ready) return fail(ctx, HF_ERR_STATE, "hf_steady_solve before hf_steady_setup (or the materials changed since)");
   if (!g_s) return fail(ctx, HF_ERR_ARG, "hf_steady_solve: g_S is null");
   if (max_it <= 0 || rtol < 0 || atol < 0) return fail(ctx, HF_ERR_ARG, "hf_steady_solve: bad tolerances");
@@ -1512,7 +1564,7 @@ int hf_hold_load(hf_ctx* ctx) {
 
 int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
   if (!ctx) return HF_ERR_ARG;
-  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_batch_begin: kappa(T) tables are set (batched sweeps of the nonlinear loop are not supported)");
+  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_batch_begin: %s tables are set (batched sweeps of the nonlinear loop are not supported)", kt_kind(ctx));
   if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_batch_begin before hf_assemble");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_batch_begin: a load is set (the batched loop has no load term; hf_set_load(NULL) first)");
   if (nv != 2 && nv != 4 && nv != 8 && nv != 16) return fail(ctx, HF_ERR_ARG, "hf_batch_begin: 2, 4, 8 or 16 columns (got %d)", nv);

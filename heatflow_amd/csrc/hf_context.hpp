@@ -313,12 +313,20 @@ struct hf_ctx {
   int fsamp_cap = 0;
   // temperature-dependent conductivities (hf_set_kappa_tables): per row-gather tag-dictionary entry a table header (KTab,
   // n = 0: the constant of d_kappa_rg) and one value array; every step re-values A at the evaluation state (k_assemble_rows_kT)
+  // temperature-dependent heat capacities (hf_set_rhoc_tables): a second header array and value array of the same shape; while
+  // one is set every evaluation re-values M as well as A (k_assemble_rows_cT).  `on` = tables of either kind are set.
   struct KappaT {
     bool on = false;
+    bool k_on = false, c_on = false;   // conductivity tables / capacity tables are set
     int picard = 1;
-    KTab* hdr = nullptr;          // 64 entries
+    KTab* hdr = nullptr;          // 64 entries (all n = 0 while only capacity tables are set)
     double* vals = nullptr;
     std::vector<char> tabled;     // by cell tag: the tag carries a table
+    KTab* chdr = nullptr;         // capacity tables: 64 entries
+    double* cvals = nullptr;
+    std::vector<char> ctabled;    // by cell tag: the tag carries a capacity table
+    double* w = nullptr;          // capacity tables, sweeps > 1: the vector the re-valued M multiplies (u^n, or BDF2's operand)
+    int cgrid = 0;
     double *pic = nullptr, *b0 = nullptr;   // evaluation state of the last sweep (for the change), b before lifting (sweeps > 1)
     unsigned long long* change = nullptr;   // max |u^{n+1,p} - u^{n+1,p-1}| of the last step's last sweep (bits of a double >= 0)
     bool have_change = false;

@@ -364,6 +364,11 @@ size_t rowgather_smem_bytes(int max_blk_nnz, int max_dict) {
   return cap * 16 + static_cast<size_t>(max_dict) * 16 + (RBA + 4) * 4 + (cap / 8 + 3) * 16;
 }
 
+// k_assemble_rows_cT: the (M, A) slab of k_assemble_rows<false> plus the staged evaluation state of k_assemble_rows_kT
+size_t ct_smem_bytes(int max_blk_nnz, int max_dict) {
+  return rowgather_smem_bytes(max_blk_nnz, max_dict) + static_cast<size_t>(max_dict + (max_dict & 1)) * 8;
+}
+
 // Row-gather element kernel into (Mout, Aout); coefficient tables indexed by the tag dictionary.  KONLY: the stiffness
 // alone into Aout (Mout, rhoc_idx and dt unused).
 template <bool KONLY = false>

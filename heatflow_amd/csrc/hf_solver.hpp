@@ -766,12 +766,43 @@ void launch_rhs_bdf2(hf_ctx* ctx, bool extrap) {
   }
 }
 
+// After a re-valuation of A: the Dirichlet elimination, the lifting values and D^-1 as hf_assemble forms them
+int kt_finish(hf_ctx* ctx) {
+  if (ctx->nbc > 0) {
+    if (ctx->nlift > 0)
+      hipLaunchKernelGGL(k_take_lift, dim3((ctx->nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift, ctx->d_lift_slot, ctx->d_A,
+                         ctx->d_lift_val);
+    hipLaunchKernelGGL(k_bc_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs, ctx->d_rowptr,
+                       ctx->d_colidx, ctx->d_A);
+  }
+  hipLaunchKernelGGL(k_dinv, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr, ctx->d_colidx, ctx->d_A,
+                     ctx->d_dinv);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
 // kappa(T): A = M + dt K(kappa(T_e)) at the evaluation state u (or 2 u - uprev) by the row-gather kernel, then the Dirichlet
 // elimination, the lifting values and D^-1 as hf_assemble forms them - all on the stream, no host synchronisation.  The
 // hierarchy (if any) stays the one hf_assemble built: its fused fine-level legs hold the old operator from here on.
 int kt_revalue(hf_ctx* ctx, const double* u, const double* uprev) {
   const int cap = (ctx->max_blk_nnz + 1) & ~1;
   const int capd = ctx->rg_max_dict;
+  if (ctx->kt.c_on) {   // capacity tables: M and A in one pass (k_assemble_rows_cT), then the same three kernels
+    const size_t smc = ct_smem_bytes(ctx->max_blk_nnz, capd);
+    if (ctx->kt.cgrid == 0) {
+      const void* fn = reinterpret_cast<const void*>(&k_assemble_rows_cT);
+      if (smc > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smc)));
+      int per_cu = 0, ncu = 0;
+      HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, smc));
+      HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
+      ctx->kt.cgrid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+    }
+    hipLaunchKernelGGL(k_assemble_rows_cT, dim3(ctx->kt.cgrid), dim3(RBA), smc, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr,
+                       ctx->d_rg_hdr, reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid),
+                       ctx->d_rg_zrb, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals, ctx->kt.chdr, ctx->kt.cvals, ctx->d_kappa_rg,
+                       ctx->d_rhoc_rg, ctx->dt, u, uprev, ctx->d_M, ctx->d_A);
+    return kt_finish(ctx);
+  }
   const size_t sm = static_cast<size_t>(cap) * 8 + static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 +
                     (RBA + 4) * 4 + (static_cast<size_t>(cap) / 8 + 3) * 16;
   if (ctx->kt.grid == 0) {   // persistent workgroups: as many as fit the chip at this LDS footprint
@@ -786,17 +817,7 @@ int kt_revalue(hf_ctx* ctx, const double* u, const double* uprev) {
                      ctx->d_rg_hdr, reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid),
                      ctx->d_rg_zrb, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev,
                      ctx->d_A);
-  if (ctx->nbc > 0) {
-    if (ctx->nlift > 0)
-      hipLaunchKernelGGL(k_take_lift, dim3((ctx->nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift, ctx->d_lift_slot, ctx->d_A,
-                         ctx->d_lift_val);
-    hipLaunchKernelGGL(k_bc_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs, ctx->d_rowptr,
-                       ctx->d_colidx, ctx->d_A);
-  }
-  hipLaunchKernelGGL(k_dinv, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr, ctx->d_colidx, ctx->d_A,
-                     ctx->d_dinv);
-  HF_HIP(hipGetLastError());
-  return HF_OK;
+  return kt_finish(ctx);
 }
 
 // The solve of a step on the current operator, with the Jacobi fallback after a multigrid breakdown
@@ -834,6 +855,7 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
   // responses as basis vectors: each solves A' w = f with a known f, whatever the scheme)
   if (kind >= 2 && hist_ok && !(bdf2 && kind == 2)) HF_TRY(prepare_response(ctx, g_host, max_it, &ra));
   const int sweeps = kt ? ctx->kt.picard : 1;
+  const bool ct = kt && ctx->kt.c_on;   // capacity tables: M is re-valued too, so every sweep forms its own right-hand side
   const bool track = kt && last;   // the Picard change of this step is kept
   if (kt) {
     // the first sweep evaluates at u^n (backward Euler) or 2 u^n - u^{n-1} (BDF2 with a history), before the right-hand side's
@@ -843,6 +865,9 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
     if (ctx->precond == 1 && ctx->amg_ready) ctx->amg_fine_stale = true;
     if (track && sweeps == 1)
       hipLaunchKernelGGL(k_eval_state, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u, um1, ctx->kt.pic);
+    if (ct && sweeps > 1)   // the vector M multiplies, for the sweeps that form the right-hand side again
+      hipLaunchKernelGGL(k_picard_w, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u,
+                         bdf2 ? (ctx->bdf_hist ? ctx->d_uprev : ctx->d_u) : nullptr, ctx->kt.w);
   }
   const double* g = g_dev ? g_dev : ctx->d_g;   // hf_run has every step's boundary values on the device already
   if (nb > 0 && !g_dev) HF_HIP(hipMemcpyAsync(ctx->d_g, g_host, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
@@ -885,7 +910,7 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
     }
   }
   const bool combine = projected && proj_active(ctx).m > 0;
-  if (sweeps > 1)   // b before lifting: the same for every sweep of the step
+  if (sweeps > 1 && !ct)   // b before lifting: the same for every sweep of the step while M is fixed
     HF_HIP(hipMemcpyAsync(ctx->kt.b0, ctx->d_b, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
   if (nb > 0) {
     if (ctx->nlift_rows > 0)  // apply_lifting (:477)
@@ -913,7 +938,12 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
       if (track && k == sweeps)
         HF_HIP(hipMemcpyAsync(ctx->kt.pic, ctx->d_u, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
       HF_TRY(kt_revalue(ctx, ctx->d_u, nullptr));
-      HF_HIP(hipMemcpyAsync(ctx->d_b, ctx->kt.b0, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+      if (!ct)
+        HF_HIP(hipMemcpyAsync(ctx->d_b, ctx->kt.b0, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+      else if (ctx->have_load)   // b = M_k w + dt' F with the M of this sweep (the history was rotated by sweep 1's pass)
+        launch_spmv<10>(ctx, ctx->d_M, ctx->kt.w, ctx->d_b, nullptr, nullptr, nullptr, nullptr, nullptr, ctx->dt, ctx->d_load);
+      else
+        launch_spmv<0>(ctx, ctx->d_M, ctx->kt.w, ctx->d_b);
       if (nb > 0) {
         if (ctx->nlift_rows > 0)
           hipLaunchKernelGGL(k_lift, dim3((ctx->nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift_rows,

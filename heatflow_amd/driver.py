@@ -42,7 +42,7 @@ def _dump_yaml(obj, f):
 from .bc import P1Space, RowDirichletBC
 from .geometry import stack_no_diamond, stack_with_diamond
 from .heating import HeatingCurve
-from .kappa_t import material_table, picard_sweeps, refuse_tables
+from .kappa_t import material_cv_table, material_table, picard_sweeps, refuse_tables
 from .mesh import Mesh, load_mesh_arrays
 from .solver import DEFAULT_MAX_IT, DEFAULT_RTOL, HeatProblem
 
@@ -169,7 +169,8 @@ def time_scheme(cfg):
 
 def _with_scheme(cfg):
     """``cfg`` with the time scheme it runs with written out (``timing.scheme``), for used_config.yaml; with kappa(T) also
-    ``timing.picard_sweeps`` and the tables that ran (``kappa_tables``: {material: {T0, dT, k}})."""
+    ``timing.picard_sweeps`` and the tables that ran (``kappa_tables``: {material: {T0, dT, k}}); with cv(T) the same under
+    ``rhoc_tables``: {material: {T0, dT, rho_cv}}, written only when a capacity table is set."""
     out = dict(cfg)
     out["timing"] = dict(cfg.get("timing") or {}, scheme=time_scheme(cfg))
     tables = {}
@@ -180,6 +181,14 @@ def _with_scheme(cfg):
     if tables:
         out["timing"]["picard_sweeps"] = picard_sweeps(cfg)
         out["kappa_tables"] = tables
+    ctables = {}
+    for name, mat in sorted((cfg.get("mats") or {}).items()):
+        t = material_cv_table(name, mat) if isinstance(mat, dict) else None
+        if t is not None:
+            ctables[name] = {"T0": float(t[0]), "dT": float(t[1]), "rho_cv": [float(v) for v in t[2]]}
+    if ctables:
+        out["timing"]["picard_sweeps"] = picard_sweeps(cfg)
+        out["rhoc_tables"] = ctables
     return out
 
 
@@ -249,9 +258,12 @@ class SimulationSession:
         return tag_to_k, tag_to_rc
 
     def _kappa_tables(self, cfg, stack):
-        """(tables {tag: (T0, dT, values)}, Picard sweeps) of a kappa(T) configuration, or None."""
+        """(tables {tag: (T0, dT, values)}, Picard sweeps, capacity tables {tag: (T0, dT, values)}) of a kappa(T) / cv(T)
+        configuration, or None."""
         tables = {self.material_tags[m.name]: m.properties["k_table"] for m in stack.materials if "k_table" in m.properties}
-        return (tables, picard_sweeps(cfg)) if tables else None
+        ctables = {self.material_tags[m.name]: m.properties["rho_cv_table"] for m in stack.materials
+                   if "rho_cv_table" in m.properties}
+        return (tables, picard_sweeps(cfg), ctables) if tables or ctables else None
 
     def _boundary_conditions(self, cfg, stack, two_sided=False):
         """[left, right, top, heated line(s)] of one configuration (reference run_with_diamond.py:343-374)."""
@@ -292,6 +304,8 @@ class SimulationSession:
                scheme)
         if kt is not None:
             key += (tuple((t, float(v[0]), float(v[1]), tuple(float(x) for x in v[2])) for t, v in sorted(kt[0].items())), kt[1])
+            if kt[2]:
+                key += (tuple((t, float(v[0]), float(v[1]), tuple(float(x) for x in v[2])) for t, v in sorted(kt[2].items())),)
         return key
 
     def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme="backward_euler", kt=None):
@@ -304,7 +318,8 @@ class SimulationSession:
                                        backend=self.backend, device_id=self.device_id, rtol=self.rtol,
                                        max_it=self.max_it, assembly_mode=self.assembly_mode, precond=self.precond,
                                        amg_reuse=True, pattern=self.pattern, amg=shared["blob"] if shared else None,
-                                       scheme=scheme, **({"kappa_tables": kt[0], "picard": kt[1]} if kt else {}))
+                                       scheme=scheme, **({"kappa_tables": kt[0], "picard": kt[1]} if kt else {}),
+                                       **({"rhoc_tables": kt[2]} if kt and kt[2] else {}))
             self._key = key
             self._k = dict(tag_to_k)
             # conductivities the multigrid levels were built for: this problem's, or those of the session that shared them

@@ -12,7 +12,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 
-from .kappa_t import material_table
+from .kappa_t import material_cv_table, material_table
 from .materials import Material
 
 
@@ -22,11 +22,15 @@ def _f(cfg, mat, key):
 
 def _material(cfg, name, box):
     """Material with rho_cv = rho*cv and k, as run_with_diamond.py:100-181; a kappa(T) key (k_table / k_power,
-    heatflow_amd.kappa_t) adds the tabulated ``k_table`` = (T0, dT, values)."""
+    heatflow_amd.kappa_t) adds the tabulated ``k_table`` = (T0, dT, values), a cv(T) key (cv_table / cv_einstein) the tabulated
+    ``rho_cv_table`` = (T0, dT, values of rho * cv)."""
     props = {"rho_cv": _f(cfg, name, "rho") * _f(cfg, name, "cv"), "k": _f(cfg, name, "k")}
     table = material_table(name, cfg["mats"][name])
     if table is not None:
         props["k_table"] = table
+    cv_table = material_cv_table(name, cfg["mats"][name])
+    if cv_table is not None:
+        props["rho_cv_table"] = cv_table
     return Material(name, boundaries=box, properties=props, mesh_size=_f(cfg, name, "mesh"))
 
 

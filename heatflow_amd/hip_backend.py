@@ -36,7 +36,7 @@ EXPORTS = [
     "hf_batch_begin", "hf_batch_load_column", "hf_batch_set_affine", "hf_batch_set_state", "hf_batch_get_state", "hf_batch_run", "hf_batch_run_flux", "hf_batch_end",
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
-    "hf_tangent_setup", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_get_sizes", "hf_get_csr", "hf_spmv",
+    "hf_tangent_setup", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_get_sizes", "hf_get_csr", "hf_spmv",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
 
@@ -140,6 +140,8 @@ def load_library():
         "hf_get_tangent": [vp, i32, pd],
         "hf_set_kappa_tables": [vp, i32, pi, pd, pd, pi, pd, i32],
         "hf_get_picard_change": [vp, pd],
+        "hf_set_rhoc_tables": [vp, i32, pi, pd, pd, pi, pd],
+        "hf_set_picard": [vp, i32],
         "hf_get_sizes": [vp, pi, pi, C.POINTER(i64), pi],
         "hf_get_csr": [vp, pi, pi, pd, pd],
         "hf_spmv": [vp, i32, pd, pd],
@@ -447,6 +449,26 @@ class HeatflowHIP:
         allv = _f64(np.concatenate(vals))
         self._check(self._lib.hf_set_kappa_tables(self._ctx, len(tags), _pi(tags), _pd(t0), _pd(dT), _pi(nk), _pd(allv),
                                                   int(picard)))
+
+    def set_rhoc_tables(self, tables):
+        """``tables`` = {cell tag: (T0, dT, values of rho * cv)}: heat capacities of the shape and evaluation of a conductivity
+        table (hf_set_rhoc_tables); an empty dict clears them.  Every evaluation then re-values M as well as A.
+        The Picard count is the one of set_kappa_tables, or set_picard.  Invalidates the assembly: set the state, then assemble()."""
+        items = sorted((int(t), v) for t, v in (tables or {}).items())
+        if not items:
+            self._check(self._lib.hf_set_rhoc_tables(self._ctx, 0, None, None, None, None, None))
+            return
+        tags = _i32([t for t, _ in items])
+        t0 = _f64([float(v[0]) for _, v in items])
+        dT = _f64([float(v[1]) for _, v in items])
+        vals = [np.asarray(v[2], dtype=np.float64).ravel() for _, v in items]
+        nk = _i32([len(v) for v in vals])
+        allv = _f64(np.concatenate(vals))
+        self._check(self._lib.hf_set_rhoc_tables(self._ctx, len(tags), _pi(tags), _pd(t0), _pd(dT), _pi(nk), _pd(allv)))
+
+    def set_picard(self, sweeps):
+        """Picard sweeps per step (1..8) while tables of either kind are set (hf_set_picard)."""
+        self._check(self._lib.hf_set_picard(self._ctx, int(sweeps)))
 
     def picard_change(self):
         """max |u^{n+1,p} - u^{n+1,p-1}| of the last step's last Picard sweep (u^{n+1,0} = the evaluation state)."""

@@ -5,6 +5,10 @@ A material of ``cfg["mats"]`` may carry, besides its constant ``k``:
   ``k_table: {T_min, T_max, k: [...]}``                 values on a uniform grid from T_min to T_max (2..256 knots)
   ``k_power: {T_ref, exponent, T_min, T_max[, knots]}``  k (T_ref / T)^exponent tabulated on [T_min, T_max] (default 256 knots),
                                                         with the material's ``k`` as the value at T_ref
+and, besides its constant ``cv``:
+  ``cv_table: {T_min, T_max, cv: [...]}``               values of cv on a uniform grid; the table handed down is rho * cv
+  ``cv_einstein: {theta, T_ref, T_min, T_max[, knots]}`` rho cv E(theta / T) / E(theta / T_ref), E(x) = x^2 e^x / (e^x - 1)^2 (an
+                                                        Einstein solid), with the material's ``cv`` as the value at T_ref
 The table is what the library evaluates: piecewise linear, clamped to the end values outside [T_min, T_max].
 ``timing.picard_sweeps`` (default 1) sets the Picard sweeps per step.
 """
@@ -15,6 +19,7 @@ import numpy as np
 MAX_KNOTS = 256
 MAX_PICARD = 8
 TABLE_KEYS = ("k_table", "k_power")
+CV_TABLE_KEYS = ("cv_table", "cv_einstein")
 
 
 def power_law_table(k_ref, T_ref, exponent, T_min, T_max, knots=MAX_KNOTS):
@@ -53,6 +58,49 @@ def material_table(name, mat):
     return None
 
 
+def einstein_function(x):
+    """E(x) = x^2 e^x / (e^x - 1)^2: the heat capacity of an Einstein solid over its Dulong-Petit limit, x = theta / T."""
+    x = np.asarray(x, dtype=np.float64)
+    ex = np.exp(x)
+    return x * x * ex / (ex - 1.0) ** 2
+
+
+def einstein_table(rho_cv_ref, theta, T_ref, T_min, T_max, knots=MAX_KNOTS):
+    """(T0, dT, values) of rho_cv_ref E(theta / T) / E(theta / T_ref) at ``knots`` uniform points of [T_min, T_max]."""
+    knots = int(knots)
+    if not 2 <= knots <= MAX_KNOTS:
+        raise ValueError(f"cv_einstein: knots must be 2..{MAX_KNOTS} (got {knots})")
+    T_min, T_max, T_ref, theta = float(T_min), float(T_max), float(T_ref), float(theta)
+    if not (0.0 < T_min < T_max) or not T_ref > 0.0 or not theta > 0.0 or not float(rho_cv_ref) > 0.0:
+        raise ValueError("cv_einstein: need 0 < T_min < T_max, T_ref > 0, theta > 0 and rho cv > 0")
+    dT = (T_max - T_min) / (knots - 1)
+    T = T_min + dT * np.arange(knots)
+    v = float(rho_cv_ref) * (einstein_function(theta / T) / float(einstein_function(theta / T_ref)))   # exactly rho cv at a knot T_ref
+    if not np.all(v > 0.0) or not np.all(np.isfinite(v)):
+        raise ValueError("cv_einstein: the table is not positive and finite on [T_min, T_max] (theta / T_min too large)")
+    return T_min, dT, v
+
+
+def material_cv_table(name, mat):
+    """The (T0, dT, values of rho * cv) capacity table of one material entry of cfg["mats"], or None without a cv key."""
+    if "cv_table" in mat and "cv_einstein" in mat:
+        raise ValueError(f"mats.{name}: cv_table and cv_einstein are exclusive")
+    if "cv_table" in mat:
+        t = mat["cv_table"]
+        v = np.asarray(t["cv"], dtype=np.float64).ravel()
+        if not 2 <= v.size <= MAX_KNOTS:
+            raise ValueError(f"cv_table: 2..{MAX_KNOTS} values needed (got {v.size})")
+        rho = float(mat["rho"])
+        if not float(t["T_max"]) > float(t["T_min"]) or not rho > 0.0 or not np.all(v > 0.0) or not np.all(np.isfinite(v)):
+            raise ValueError("cv_table: need T_max > T_min, rho > 0 and positive values")
+        return float(t["T_min"]), (float(t["T_max"]) - float(t["T_min"])) / (v.size - 1), rho * v
+    if "cv_einstein" in mat:
+        p = mat["cv_einstein"]
+        return einstein_table(float(mat["rho"]) * float(mat["cv"]), p["theta"], p["T_ref"], p["T_min"], p["T_max"],
+                              p.get("knots", MAX_KNOTS))
+    return None
+
+
 def picard_sweeps(cfg):
     """``timing.picard_sweeps`` (default 1), checked against 1..8."""
     p = int((cfg.get("timing") or {}).get("picard_sweeps", 1) or 1)
@@ -61,18 +109,21 @@ def picard_sweeps(cfg):
     return p
 
 
-def table_keys(cfg):
-    """['mats.<name>.k_table', ...] of every material of ``cfg`` that carries a kappa(T) key."""
+def table_keys(cfg, keys=TABLE_KEYS + CV_TABLE_KEYS):
+    """['mats.<name>.k_table', ...] of every material of ``cfg`` that carries a kappa(T) or cv(T) key (one of ``keys``)."""
     out = []
     for name, mat in sorted((cfg.get("mats") or {}).items()):
-        for key in TABLE_KEYS:
+        for key in keys:
             if isinstance(mat, dict) and key in mat:
                 out.append(f"mats.{name}.{key}")
     return out
 
 
 def refuse_tables(cfg, where):
-    """ValueError naming the key if ``cfg`` asks for kappa(T): ``where`` does not support it (yet)."""
-    keys = table_keys(cfg)
+    """ValueError naming the key if ``cfg`` asks for kappa(T) or cv(T): ``where`` does not support it (yet)."""
+    keys = table_keys(cfg, TABLE_KEYS)
     if keys:
         raise ValueError(f"{where} does not support temperature-dependent conductivities ({', '.join(keys)})")
+    keys = table_keys(cfg, CV_TABLE_KEYS)
+    if keys:
+        raise ValueError(f"{where} does not support temperature-dependent heat capacities ({', '.join(keys)})")

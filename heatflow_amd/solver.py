@@ -49,13 +49,16 @@ class HeatProblem:
     kappa_tables : {cell tag: (T0, dT, values)} - temperature-dependent conductivities (hf_set_kappa_tables):
               every step re-values the operator at u^n (BDF2: 2 u^n - u^{n-1}); the state u0 is set before the assembly, so
               the multigrid hierarchy is built from A(u0).  None / {}: constant conductivities, the call sequence of before.
+    rhoc_tables : {cell tag: (T0, dT, values of rho * cv)} - temperature-dependent heat capacities (hf_set_rhoc_tables, DESIGN.md
+              3.10): every evaluation re-values M as well as A.  With or without kappa_tables; the same order (tables, state,
+              assembly).  None / {}: constant capacities.
     picard : Picard sweeps per step with tables (1..8; 1 = the lagged scheme)
     """
 
     def __init__(self, coords, tris, tags, tag_to_k, tag_to_rho_cv, dt, bcs, u0, *, backend=None, device_id=0,
                  assembly_mode=ASM_ROW_GATHER, rtol=DEFAULT_RTOL, atol=0.0, max_it=DEFAULT_MAX_IT,
                  precond=PC_JACOBI, amg_reuse=False, pattern=None, amg=None, scheme="backward_euler", kappa_tables=None,
-                 picard=1):
+                 picard=1, rhoc_tables=None):
         self.coords = np.ascontiguousarray(coords, dtype=np.float64)
         self.n = self.coords.shape[0]
         self.dt = float(dt)
@@ -65,6 +68,7 @@ class HeatProblem:
         self.precond = precond
         self.scheme = scheme
         self.kappa_tables = dict(kappa_tables or {})
+        self.rhoc_tables = dict(rhoc_tables or {})
         self.picard = int(picard)
         scheme_code = time_scheme_code(scheme)     # (an unknown name raises before any backend call)
         self.backend = backend if backend is not None else HeatflowHIP(device_id)
@@ -89,8 +93,12 @@ class HeatProblem:
         if amg is not None and precond == PC_AMG and amg_reuse:
             self.backend.amg_install(amg)
         u = np.full(self.n, float(u0)) if np.isscalar(u0) else np.asarray(u0, dtype=np.float64)
-        if self.kappa_tables:     # kappa(T): the operator (and the hierarchy built from it) is evaluated at u0
-            self.backend.set_kappa_tables(self.kappa_tables, self.picard)
+        if self.kappa_tables or self.rhoc_tables:   # tables: the operator (and the hierarchy built from it) is evaluated at u0
+            if self.kappa_tables:
+                self.backend.set_kappa_tables(self.kappa_tables, self.picard)
+            if self.rhoc_tables:
+                self.backend.set_rhoc_tables(self.rhoc_tables)
+                self.backend.set_picard(self.picard)
             self.backend.set_state(u)
             self.backend.assemble(self.dt, self.assembly_mode)
         else:
@@ -110,7 +118,7 @@ class HeatProblem:
             self.backend.assemble(self.dt, self.assembly_mode)
 
     def picard_change(self):
-        """max |u^{n+1,p} - u^{n+1,p-1}| of the last step's last Picard sweep (kappa(T) only)."""
+        """max |u^{n+1,p} - u^{n+1,p-1}| of the last step's last Picard sweep (with tables only)."""
         return self.backend.picard_change()
 
     def close(self):

@@ -33,6 +33,7 @@
  *                      over a grid (sweep_test.py:47-75, parameter_sweep.py:195-235); these give the derivatives of a run
  *   hf_set_kappa_tables / hf_get_picard_change   no counterpart: the reference's conductivities are constants per material
  *                      (run_with_diamond.py:286-301); these make them functions of the temperature
+ *   hf_set_rhoc_tables / hf_set_picard   no counterpart: the same for the heat capacity rho * cv (run_with_diamond.py:286-301)
  *
  * Conventions
  *   - All functions return 0 (HF_OK) or a negative HF_ERR_* code; hf_last_error(ctx)
@@ -358,13 +359,37 @@ int hf_get_tangent(hf_ctx* ctx, int32_t j, double* s);
  *        hf_set_mesh.  hf_set_mesh removes the tables.
  * While tables are set: hf_assemble in another mode and hf_update_kappa on a tabled tag -> HF_ERR_ARG; hf_batch_begin,
  * hf_tangent_setup / hf_run_tangent and hf_steady_setup / hf_steady_solve -> HF_ERR_STATE.  Every error returns before any
- * launch.  hf_set_load keeps working.  Not supported (refused, never approximated): a temperature-dependent rho_c, a Picard
+ * launch.  hf_set_load keeps working.  Not supported (refused, never approximated): a Picard
  * steady state, batched / affine sweeps, tangents, and rebuilding the hierarchy during a run.
  * hf_get_picard_change  max over all nodes of |u^{n+1,p} - u^{n+1,p-1}| of the last step's last sweep (u^{n+1,0} = u*, so for
  *        p = 1 the change from the evaluation state); HF_ERR_STATE before the first step with tables. */
 int hf_set_kappa_tables(hf_ctx* ctx, int32_t n_tab, const int32_t* tags, const double* t0, const double* dT, const int32_t* n_knots,
                         const double* values, int32_t picard_sweeps);
 int hf_get_picard_change(hf_ctx* ctx, double* max_du);
+
+/* Temperature-dependent heat capacities: rho_c stays piecewise constant per element, but a cell tag may carry a
+ * table of exactly the shape and evaluation of a conductivity table, taken at the same T_e of the same evaluation state u*.  A tag
+ * may carry a capacity table, a conductivity table, both or neither; capacity tables work with no conductivity table set.
+ *   model     the non-conservative form rho_c(T) dT/dt = div(k grad T) with the capacity lagged (p = 1) or iterated (p > 1); an
+ *             enthalpy formulation is not attempted.
+ *   step      x_0 = u*;  sweep k = 1..p:  M_k = M(rho_c(x_{k-1})),  A_k = M_k + dt' K(kappa(x_{k-1})),
+ *             A_k x_k = M_k w (+ dt' F) - A_k[:, B] g on the free rows, (x_k)_B = g;  u^{n+1} = x_p.  w = u^n (BDF2:
+ *             (4 u^n - u^{n-1}) / 3).  The right-hand side is formed again in every sweep, with the M of that sweep (one more pass
+ *             over M per sweep); BDF2's history rotates once per step, in sweep 1's pass.
+ * Each evaluation writes M and A in one row-gather launch (k_assemble_rows_cT, launched only while a capacity table is set), followed
+ * by the elimination, the lifting values and D^-1 as under conductivity tables: four launches, no host synchronisation.
+ * hf_set_rhoc_tables   arguments, checks and error texts as hf_set_kappa_tables (values = rho * cv at the knots, > 0); n_tab = 0
+ *        clears the capacity tables and leaves conductivity tables as they are (and the other way round).  A rho_c given through
+ *        hf_set_materials for a tabled tag is the constant the table replaces.  With capacity tables set hf_assemble values M and
+ *        A at the current state, hf_get_csr returns the current M and A, and everything said above of "tables are set" (the
+ *        refusals, the row-gather requirement, start-vector kinds 2 and 3 as kind 1, the frozen hierarchy, hf_get_picard_change)
+ *        holds for tables of either kind.  The Picard count is the one of hf_set_kappa_tables.
+ *        HF_ERR_ARG additionally: a mesh whose (M, A) slab, staged state and headers exceed the 160 KiB of LDS.
+ * hf_set_picard   the Picard count p (1..8) of the loop, for use with capacity tables alone; HF_ERR_STATE while no tables are set
+ *        (clearing the last table resets it to 1), HF_ERR_ARG outside 1..8.  Does not invalidate the assembly. */
+int hf_set_rhoc_tables(hf_ctx* ctx, int32_t n_tab, const int32_t* tags, const double* t0, const double* dT, const int32_t* n_knots,
+                       const double* values);
+int hf_set_picard(hf_ctx* ctx, int32_t sweeps);
 
 int hf_get_sizes(hf_ctx* ctx, int32_t* n, int32_t* n_e, int64_t* nnz, int32_t* n_bc);
 /* Any pointer may be NULL.  A is the matrix as it stands (eliminated when BCs are set). */
