@@ -68,6 +68,8 @@ void steady_free(hf_ctx* ctx) {
   hf_ctx::Steady& S = ctx->steady;
   dev_free(&S.bc_dofs); dev_free(&S.g); dev_free(&S.lift_rows); dev_free(&S.lift_ptr); dev_free(&S.lift_bc);
   dev_free(&S.lift_slot); dev_free(&S.lift_val); dev_free(&S.K); dev_free(&S.dinv); dev_free(&S.Kfree);
+  dev_free(&S.hdr0); dev_free(&S.xprev); dev_free(&S.change);
+  S.picard = false;
   S.nbc = S.nlift_rows = S.nlift = 0;
   S.ready = false;
   S.pred_iters = 0;
@@ -156,6 +158,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   ctx->rg_ok = T.rg.ok && rowgather_smem_bytes(T.max_blk_nnz, T.rg.cols.max_dict) <= 160 * 1024;
   ctx->rg_grid = 0;
   ctx->rg_grid_k = 0;
+  ctx->rg_grid_p = 0;
   if (ctx->rg_ok) {
     const RowGather& G = T.rg;
     ctx->rg_max_dict = G.cols.max_dict;
@@ -866,6 +869,7 @@ int kt_set_tables(hf_ctx* ctx, bool cap, int32_t n_tab, const int32_t* tags, con
   HF_HIP(hipSetDevice(ctx->dev));
   hf_ctx::KappaT& K = ctx->kt;
   if (n_tab == 0) {   // clear: without tables of the other kind every path is the constant-coefficient one again
+    if (ctx->steady.picard) ctx->steady.ready = false;   // a Picard steady set-up belongs to the tables it was valued with
     if (cap ? K.c_on : K.k_on) {
       free_batch(ctx);
       ctx->assembled = false;
@@ -909,6 +913,7 @@ int kt_set_tables(hf_ctx* ctx, bool cap, int32_t n_tab, const int32_t* tags, con
     }
   }
   free_batch(ctx);
+  if (ctx->steady.picard) ctx->steady.ready = false;   // (a linear set-up keeps its constant-coefficient stiffness)
   if (!K.hdr) {   // first tables of either kind: the buffers of the loop
     HF_TRY(dev_alloc(ctx, &K.hdr, 64));
     HF_TRY(dev_alloc(ctx, &K.pic, ctx->n));
@@ -1415,18 +1420,31 @@ int hf_get_tangent(hf_ctx* ctx, int32_t j, double* s) {
   return HF_OK;
 }
 
-int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t precond) {
-  if (!ctx) return HF_ERR_ARG;
-  if (!ctx->have_mesh || !ctx->have_mat) return fail(ctx, HF_ERR_STATE, "hf_steady_setup needs hf_set_mesh and hf_set_materials first");
-  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_steady_setup: %s tables are set (a Picard steady state is not supported)", kt_kind(ctx));
-  if (n_s <= 0 || !dofs) return fail(ctx, HF_ERR_ARG, "hf_steady_setup: empty Dirichlet set (the stiffness alone is singular)");
-  if (precond < 0 || precond > 1) return fail(ctx, HF_ERR_ARG, "hf_steady_setup: unknown preconditioner %d", precond);
+// After a valuation of the stiffness into steady.Kfree (on the swapped context): K_hat_S = the copy with the set S eliminated, the
+// lifting values K[free, S] taken before, and D^-1
+int steady_eliminate(hf_ctx* ctx) {
+  HF_HIP(hipMemcpyAsync(ctx->d_A, ctx->steady.Kfree, sizeof(double) * ctx->nnz, hipMemcpyDeviceToDevice, ctx->stream));
+  if (ctx->nlift > 0)
+    hipLaunchKernelGGL(k_take_lift, dim3((ctx->nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift, ctx->d_lift_slot,
+                       ctx->d_A, ctx->d_lift_val);
+  hipLaunchKernelGGL(k_bc_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs, ctx->d_rowptr,
+                     ctx->d_colidx, ctx->d_A);
+  hipLaunchKernelGGL(k_dinv, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr, ctx->d_colidx, ctx->d_A, ctx->d_dinv);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+// hf_steady_setup (picard = false: the constant-coefficient K) and hf_steady_picard_setup (picard = true: K valued at the
+// current state through the conductivity tables): one check list, one set of buffers, one hierarchy.
+int steady_setup_impl(hf_ctx* ctx, const char* fn, bool picard, int32_t n_s, const int32_t* dofs, int32_t precond) {
+  if (n_s <= 0 || !dofs) return fail(ctx, HF_ERR_ARG, "%s: empty Dirichlet set (the stiffness alone is singular)", fn);
+  if (precond < 0 || precond > 1) return fail(ctx, HF_ERR_ARG, "%s: unknown preconditioner %d", fn, precond);
   if (!ctx->rg_ok || (ctx->assembled && ctx->mode != HF_ASM_ROW_GATHER))
-    return fail(ctx, HF_ERR_ARG, "hf_steady_setup: the steady operator is assembled by the row-gather kernel only (HF_ASM_ROW_GATHER on a mesh with row-gather lists)");
+    return fail(ctx, HF_ERR_ARG, "%s: the steady operator is assembled by the row-gather kernel only (HF_ASM_ROW_GATHER on a mesh with row-gather lists)", fn);
   std::vector<char> seen(ctx->n, 0);
   for (int32_t q = 0; q < n_s; ++q) {
-    if (dofs[q] < 0 || dofs[q] >= ctx->n) return fail(ctx, HF_ERR_ARG, "hf_steady_setup: dof %d outside [0,%d)", dofs[q], ctx->n);
-    if (seen[dofs[q]]) return fail(ctx, HF_ERR_ARG, "hf_steady_setup: dof %d listed twice (resolve overlaps on the host)", dofs[q]);
+    if (dofs[q] < 0 || dofs[q] >= ctx->n) return fail(ctx, HF_ERR_ARG, "%s: dof %d outside [0,%d)", fn, dofs[q], ctx->n);
+    if (seen[dofs[q]]) return fail(ctx, HF_ERR_ARG, "%s: dof %d listed twice (resolve overlaps on the host)", fn, dofs[q]);
     seen[dofs[q]] = 1;
   }
   HF_HIP(hipSetDevice(ctx->dev));
@@ -1439,20 +1457,24 @@ int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t preco
   HF_TRY(dev_alloc(ctx, &S.Kfree, ctx->nnz));
   HF_TRY(dev_alloc(ctx, &S.K, ctx->nnz));
   HF_TRY(dev_alloc(ctx, &S.dinv, n));
+  if (picard) {
+    HF_TRY(dev_alloc(ctx, &S.xprev, n));
+    HF_TRY(dev_alloc(ctx, &S.change, 1));
+    if (!ctx->kt.hdr) {   // no table of either kind: every tag keeps its constant
+      const std::vector<KTab> none(64, KTab{0.0, 0.0, 0, 0});
+      HF_TRY(dev_alloc(ctx, &S.hdr0, 64));
+      HF_HIP(copy_sync(ctx, S.hdr0, none.data(), sizeof(KTab) * 64, hipMemcpyHostToDevice));
+    }
+  }
   HF_HIP(copy_sync(ctx, S.bc_dofs, dofs, sizeof(int32_t) * n_s, hipMemcpyHostToDevice));
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   // K = the dt K part of the transient operator at dt = 1 (r-weighted), kept as assembled for hf_hold_load
-  HF_TRY(launch_assemble_rows<true>(ctx, ctx->d_kappa_rg, ctx->d_rhoc_rg, 1.0, nullptr, S.Kfree));
-  HF_HIP(hipMemcpyAsync(S.K, S.Kfree, sizeof(double) * ctx->nnz, hipMemcpyDeviceToDevice, ctx->stream));
+  if (picard) HF_TRY(steady_revalue(ctx, ctx->kt.hdr ? ctx->kt.hdr : S.hdr0, ctx->d_u, S.Kfree));
+  else HF_TRY(launch_assemble_rows<true>(ctx, ctx->d_kappa_rg, ctx->d_rhoc_rg, 1.0, nullptr, S.Kfree));
   {
     SteadyScope sw(ctx);
     HF_TRY(build_lift(ctx));    // lifting lists of S (into the swapped fields)
-    if (ctx->nlift > 0)
-      hipLaunchKernelGGL(k_take_lift, dim3((ctx->nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift, ctx->d_lift_slot,
-                         ctx->d_A, ctx->d_lift_val);
-    hipLaunchKernelGGL(k_bc_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs, ctx->d_rowptr,
-                       ctx->d_colidx, ctx->d_A);
-    hipLaunchKernelGGL(k_dinv, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, ctx->d_rowptr, ctx->d_colidx, ctx->d_A, ctx->d_dinv);
+    HF_TRY(steady_eliminate(ctx));
     HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
     HF_HIP(hipGetLastError());
     HF_HIP(hipStreamSynchronize(ctx->stream));
@@ -1463,7 +1485,119 @@ int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t preco
   }
   S.precond = precond;
   S.pred_iters = 0;
+  S.picard = picard;
   S.ready = true;
+  return HF_OK;
+}
+
+int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t precond) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh || !ctx->have_mat) return fail(ctx, HF_ERR_STATE, "hf_steady_setup needs hf_set_mesh and hf_set_materials first");
+  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_steady_setup: %s tables are set (a Picard steady state is not supported)", kt_kind(ctx));
+  return steady_setup_impl(ctx, "hf_steady_setup", false, n_s, dofs, precond);
+}
+
+int hf_steady_picard_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t precond) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh || !ctx->have_mat) return fail(ctx, HF_ERR_STATE, "hf_steady_picard_setup needs hf_set_mesh and hf_set_materials first");
+  return steady_setup_impl(ctx, "hf_steady_picard_setup", true, n_s, dofs, precond);
+}
+
+int hf_steady_picard_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, double rtol, double atol, int32_t max_it, double picard_tol,
+                           int32_t max_sweeps, int32_t* sweeps, int32_t* iters, double* change, double* nl_resid) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->steady.ready || !ctx->steady.picard)
+    return fail(ctx, HF_ERR_STATE, "hf_steady_picard_solve before hf_steady_picard_setup (or the materials or the tables changed since)");
+  if (!g_s) return fail(ctx, HF_ERR_ARG, "hf_steady_picard_solve: g_S is null");
+  if (max_it <= 0 || !(rtol >= 0) || !(atol >= 0)) return fail(ctx, HF_ERR_ARG, "hf_steady_picard_solve: bad tolerances");
+  if (!(picard_tol >= 0)) return fail(ctx, HF_ERR_ARG, "hf_steady_picard_solve: picard_tol must not be negative");
+  if (max_sweeps < 1 || max_sweeps > 1000) return fail(ctx, HF_ERR_ARG, "hf_steady_picard_solve: max_sweeps %d outside 1..1000", max_sweeps);
+  HF_HIP(hipSetDevice(ctx->dev));
+  const bool with_load = use_load != 0 && ctx->have_load;
+  hf_ctx::Steady& S = ctx->steady;   // (inside the scope below its swapped fields hold the transient's: use the context's)
+  const KTab* hdr = ctx->kt.hdr ? ctx->kt.hdr : S.hdr0;
+  int rc = HF_OK, nsweeps = 0;
+  double chg = 0.0, nl = 0.0;
+  {
+    SteadyScope sw(ctx);
+    const int n = ctx->n, nb = ctx->nbc;
+    HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+    HF_HIP(hipMemcpyAsync(ctx->d_g, g_s, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
+    // K_hat_S, the lifting values and D^-1 at the current iterate; the hierarchy stays the one of the set-up, whose fused
+    // finest-level legs hold the operator it was built from
+    auto value = [&]() -> int {
+      HF_TRY(steady_revalue(ctx, hdr, ctx->d_u, S.Kfree));
+      HF_TRY(steady_eliminate(ctx));
+      if (S.precond == 1 && ctx->amg_ready) ctx->amg_fine_stale = true;
+      return HF_OK;
+    };
+    // b = F (or 0) - K[:, S] g_S on the free rows, b_S = g_S; the iterate receives u_S = g_S
+    auto rhs = [&]() -> int {
+      if (with_load) HF_HIP(hipMemcpyAsync(ctx->d_b, ctx->d_load, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
+      else HF_HIP(hipMemsetAsync(ctx->d_b, 0, sizeof(double) * n, ctx->stream));
+      if (ctx->nlift_rows > 0)
+        hipLaunchKernelGGL(k_lift, dim3((ctx->nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift_rows, ctx->d_lift_rows,
+                           ctx->d_lift_ptr, ctx->d_lift_bc, ctx->d_lift_val, ctx->d_g, ctx->d_b);
+      hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, ctx->d_g, ctx->d_b, ctx->d_u);
+      HF_HIP(hipGetLastError());
+      return HF_OK;
+    };
+    const LinSys sys{ctx->d_A, ctx->d_dinv, ctx->d_u, ctx->d_b};
+    for (int k = 1; k <= max_sweeps; ++k) {
+      HF_TRY(value());
+      HF_HIP(hipMemcpyAsync(S.xprev, ctx->d_u, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
+      HF_TRY(rhs());
+      const bool use_amg = S.precond == 1 && ctx->amg_ready;
+      rc = pcg_solve(ctx, sys, use_amg, rtol, atol, max_it, &S.pred_iters);
+      int it = ctx->h_scal->iters;
+      if (rc == HF_ERR_NOCONV && use_amg && ctx->h_scal->done == 2) {   // as hf_steady_solve: finish the sweep with Jacobi on a breakdown
+        ctx->amg_fallbacks += 1;
+        int pred = 0;
+        rc = pcg_solve(ctx, sys, false, rtol, atol, max_it, &pred);
+        it += ctx->h_scal->iters;
+      }
+      if (rc == HF_ERR_HIP) return rc;
+      nsweeps = k;
+      if (iters) iters[k - 1] = it;
+      // the one scalar the host reads per sweep: change_k = max |x_k - x_{k-1}|
+      unsigned long long bits = 0;
+      HF_HIP(hipMemsetAsync(S.change, 0, sizeof(unsigned long long), ctx->stream));
+      hipLaunchKernelGGL(k_max_abs_diff, dim3(ctx->P), dim3(TPB), 0, ctx->stream, n, ctx->d_u, S.xprev, S.change);
+      HF_HIP(hipGetLastError());
+      HF_HIP(copy_sync(ctx, &bits, S.change, sizeof bits, hipMemcpyDeviceToHost));
+      std::memcpy(&chg, &bits, sizeof bits);
+      if (rc != HF_OK || chg <= picard_tol) break;
+    }
+    // the final valuation, at the returned state: Kfree for hf_hold_load, and the relative start residual a further sweep
+    // would see (the start kernels of the Jacobi loop: ||D^-1 (b - K_hat_S u)|| / ||D^-1 b||)
+    HF_TRY(value());
+    HF_TRY(rhs());
+    ctx->epoch += 1;
+    launch_spmv<2>(ctx, ctx->d_A, ctx->d_u, ctx->d_r, ctx->d_part_rz, ctx->d_b, ctx->d_z, ctx->d_part_zz, ctx->d_part_bn, 0.0, ctx->d_dinv);
+    hipLaunchKernelGGL(k_pcg_begin, dim3(1), dim3(TPB), 0, ctx->stream, ctx->P, rtol, atol, ctx->d_part_zz, ctx->d_part_bn, ctx->d_scal,
+                       ctx->epoch);
+    HF_HIP(hipGetLastError());
+    HF_TRY(read_scal(ctx));
+    nl = std::sqrt(ctx->h_scal->zz / std::max(ctx->h_scal->bn2, 1e-300));
+    HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+    HF_HIP(hipStreamSynchronize(ctx->stream));
+    float ms = 0.f;
+    HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+    ctx->last_ms = ms;
+  }
+  // a new state, as hf_set_state: the history of the start vector (and of BDF2) does not continue
+  ctx->have_prev = false;
+  ctx->bdf_hist = false;
+  ctx->g_hist = 0;
+  proj_clear(ctx, true);
+  HF_TRY(tangent_reset(ctx));
+  ctx->tan.steady_state = true;
+  if (sweeps) *sweeps = nsweeps;
+  if (change) *change = chg;
+  if (nl_resid) *nl_resid = nl;
+  if (rc != HF_OK) return rc;   // a linear solve failed: its message stands
+  if (!(chg <= picard_tol))
+    return fail(ctx, HF_ERR_NOCONV, "hf_steady_picard_solve: change %.3e above picard_tol %.3e after %d sweeps", chg, picard_tol, nsweeps);
   return HF_OK;
 }
 

@@ -152,6 +152,7 @@ struct hf_ctx {
   int32_t* d_rg_dict = nullptr;     // the blocks' column lists (global node ids)
   double2* d_rg_zrb = nullptr;      // coordinates of every block's column list (own rows + halo)
   int rg_max_dict = 0, rg_grid = 0, rg_grid_k = 0;   // (rg_grid_k: grid of the stiffness-only variant)
+  int rg_grid_p = 0;                                 // grid of the stiffness-only table re-valuation (k_assemble_rows_kT_K)
   int64_t n_rg_ell = 0, n_rg_dict = 0, n_cdict = 0;
   std::vector<int32_t> h_rg_tags;
   double *d_kappa_rg = nullptr, *d_rhoc_rg = nullptr;
@@ -237,8 +238,14 @@ struct hf_ctx {
   // and with its own Dirichlet set S eliminated (K) -, the lifting columns K[free, S], D^-1 and a multigrid hierarchy of
   // its own.  While the steady operator is set up or solved these fields trade places with the transient's (steady_swap in
   // heatflow_hip.hip), so that the solver code runs on them unchanged and the transient's stay untouched.
+  // picard: the set-up made last is hf_steady_picard_setup's - K and Kfree are valued at a state through the tables
+  // (k_assemble_rows_kT_K) and go stale with the tables as well as with the materials.
   struct Steady {
     bool ready = false;
+    bool picard = false;
+    KTab* hdr0 = nullptr;                   // 64 empty table headers, for a Picard set-up while no table is set
+    double* xprev = nullptr;                // the iterate a Picard sweep started from (for the change)
+    unsigned long long* change = nullptr;   // max |x_k - x_{k-1}| of the last sweep (bits of a double >= 0)
     int precond = 0, pred_iters = 0;
     int32_t nbc = 0, nlift_rows = 0, nlift = 0;
     int32_t *bc_dofs = nullptr, *lift_rows = nullptr, *lift_ptr = nullptr, *lift_bc = nullptr, *lift_slot = nullptr;

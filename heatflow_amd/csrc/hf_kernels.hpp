@@ -724,6 +724,110 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_cT(int nblk, int cap /* s
   }
 }
 
+// Re-valuation of the stiffness alone, K = K(kappa(T)) at the state u (hf_steady_picard_setup / hf_steady_picard_solve): the
+// lists, the staging of the state, the persistent workgroups, the register prefetch and the summation order of
+// k_assemble_rows_kT with the additions of k_assemble_rows<true> - no M half, no dt - in a one-value slab.  With no table (every
+// header n = 0) or constant tables it gives the K of k_assemble_rows<true> bit for bit; the sorted T_e keeps K exactly symmetric.
+__global__ __launch_bounds__(RBA) void k_assemble_rows_kT_K(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
+                                                            const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
+                                                            const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
+                                                            const double2* __restrict__ zrb, const int32_t* __restrict__ dict,
+                                                            const KTab* __restrict__ ktab, const double* __restrict__ kvals,
+                                                            const double* __restrict__ kappa_idx, const double* __restrict__ u,
+                                                            double* __restrict__ Kv) {
+  extern __shared__ double smem[];
+  __shared__ KTab sK[64];
+  double* sA = smem;                                                 // K per slot
+  double2* sXd = reinterpret_cast<double2*>(sA + cap);               // coordinates of the block's column list
+  double* sU = reinterpret_cast<double*>(sXd + capd);                // the state on the block's column list
+  int* sR = reinterpret_cast<int*>(sU + capd + (capd & 1));          // row starts inside the slab
+  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);               // column-list position per slot, from the 8-aligned start
+  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
+
+  const int t = threadIdx.x;
+  if (t < 64) sK[t] = ktab[t];
+  for (int k = t; k < cap; k += RBA) sA[k] = 0.0;
+
+  int4 hA, hB;
+  uint4 pe, pc[RG_NC];
+  double2 px[RG_NX];
+  double pu[RG_NX];
+  int pr = 0;
+  auto prefetch = [&](int blk) {
+    hA = hdr[2 * blk];
+    hB = hdr[2 * blk + 1];
+    pe = ell[hB.x + t];
+    const int c0 = hA.x >> 3, nc = ((hA.x + hA.y + 7) >> 3) - c0;
+#pragma unroll
+    for (int q = 0; q < RG_NC; ++q) pc[q] = (t + q * RBA < nc) ? cid16[c0 + t + q * RBA] : make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int q = 0; q < RG_NX; ++q) {
+      const bool in = t + q * RBA < hA.w;
+      px[q] = in ? zrb[hA.z + t + q * RBA] : make_double2(0.0, 0.0);
+      pu[q] = in ? u[dict[hA.z + t + q * RBA]] : 0.0;
+    }
+    pr = (t < hB.w) ? rowptr[blk * RBA + t] - hA.x : 0;
+  };
+  int blk = blockIdx.x;
+  if (blk < nblk) prefetch(blk);
+  while (blk < nblk) {
+    const int4 cA = hA, cB = hB;
+    const uint4 ce = pe;
+    const int nc = ((cA.x + cA.y + 7) >> 3) - (cA.x >> 3);
+#pragma unroll
+    for (int q = 0; q < RG_NC; ++q) if (t + q * RBA < nc) sC4[t + q * RBA] = pc[q];
+#pragma unroll
+    for (int q = 0; q < RG_NX; ++q) if (t + q * RBA < cA.w) { sXd[t + q * RBA] = px[q]; sU[t + q * RBA] = pu[q]; }
+    sR[t] = pr;
+    __syncthreads();
+    const int nxt = blk + gridDim.x;
+    if (nxt < nblk) prefetch(nxt);
+
+    if (t < cB.w) {
+      const int base = sR[t];
+      const int sbase = base + (cA.x & 7);
+      const int ci = cB.z + t;
+      const double2 Pi = sXd[ci];
+      const double ui = sU[ci];
+      double dA = 0.0;
+      int pd = 0;
+      while (pd < 31 && sC[sbase + pd] < ci) ++pd;
+      for (int g = 0; g < cB.y; ++g) {
+        const uint4 ev = g == 0 ? ce : ell[cB.x + g * RBA + t];
+        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
+          if (e == 0xFFFFu) continue;
+          const int pj = e & 31u, pk = (e >> 5) & 31u, tg = e >> 10;
+          const int cj = sC[sbase + pj], ck = sC[sbase + pk];
+          const double2 Pj = sXd[cj], Pk = sXd[ck];
+          const KTab kh = sK[tg];
+          double kappa = kappa_idx[tg];
+          if (kh.n > 0) {
+#pragma clang fp contract(off)
+            const double uj = sU[cj], uk = sU[ck];
+            const double ab_lo = fmin(ui, uj), ab_hi = fmax(ui, uj);
+            const double lo = fmin(ab_lo, uk), hi = fmax(ab_hi, uk), mid = fmax(ab_lo, fmin(ab_hi, uk));
+            kappa = ktab_eval(kh, kvals, ((lo + mid) + hi) * (1.0 / 3.0));
+          }
+          const ElemRow r = element_row(Pi, Pj, Pk, 0.0, kappa);
+          dA += r.k0;
+          sA[base + pj] += r.k1;
+          sA[base + pk] += r.k2;
+        }
+      }
+      sA[base + pd] = dA;
+    }
+    __syncthreads();
+    for (int k = t; k < cA.y; k += RBA) {
+      Kv[cA.x + k] = sA[k];
+      sA[k] = 0.0;
+    }
+    blk = nxt;
+  }
+}
+
 // w = u^n, or BDF2's operand (4 u^n - u^{n-1}) / 3: the vector the re-valued M multiplies in Picard sweeps 2..p of a step with
 // capacity tables (kept before the right-hand side's pass of sweep 1 rotates the state buffers)
 __global__ __launch_bounds__(TPB) void k_picard_w(int n, const double* __restrict__ u, const double* __restrict__ um1,

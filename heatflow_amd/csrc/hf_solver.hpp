@@ -820,6 +820,31 @@ int kt_revalue(hf_ctx* ctx, const double* u, const double* uprev) {
   return kt_finish(ctx);
 }
 
+// Picard steady state: Kout = K(kappa(T_e)) at the state u by the stiffness-only row-gather kernel (k_assemble_rows_kT_K, the
+// LDS footprint of k_assemble_rows_kT).  `hdr`: the conductivity table headers, or 64 empty ones while none are set.
+int steady_revalue(hf_ctx* ctx, const KTab* hdr, const double* u, double* Kout) {
+  const int cap = (ctx->max_blk_nnz + 1) & ~1;
+  const int capd = ctx->rg_max_dict;
+  const size_t sm = static_cast<size_t>(cap) * 8 + static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 +
+                    (RBA + 4) * 4 + (static_cast<size_t>(cap) / 8 + 3) * 16;
+  if (ctx->rg_grid_p == 0) {   // persistent workgroups: as many as fit the chip at this LDS footprint
+    const void* fn = reinterpret_cast<const void*>(&k_assemble_rows_kT_K);
+    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
+    int per_cu = 0, ncu = 0;
+    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
+    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
+    ctx->rg_grid_p = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+    if (std::getenv("HEATFLOW_DEBUG"))
+      std::fprintf(stderr, "[steady picard] k_assemble_rows_kT_K: %zu bytes of dynamic LDS, %d workgroups per CU, grid %d of %d blocks\n", sm,
+                   per_cu, ctx->rg_grid_p, ctx->nblk_a);
+  }
+  hipLaunchKernelGGL(k_assemble_rows_kT_K, dim3(ctx->rg_grid_p), dim3(RBA), sm, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr,
+                     ctx->d_rg_hdr, reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid),
+                     ctx->d_rg_zrb, ctx->d_rg_dict, hdr, ctx->kt.vals, ctx->d_kappa_rg, u, Kout);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
 // The solve of a step on the current operator, with the Jacobi fallback after a multigrid breakdown
 int step_solve(hf_ctx* ctx, double rtol, double atol, int max_it) {
   const LinSys sys{ctx->d_A, ctx->d_dinv, ctx->d_u, ctx->d_b};

@@ -35,7 +35,7 @@ EXPORTS = [
     "hf_update_kappa", "hf_set_dirichlet", "hf_assemble", "hf_set_time_scheme", "hf_set_precond", "hf_set_start_vector", "hf_get_response_solves", "hf_get_amg_info", "hf_get_amg_fallbacks", "hf_set_state", "hf_get_state", "hf_sample", "hf_step", "hf_run",
     "hf_batch_begin", "hf_batch_load_column", "hf_batch_set_affine", "hf_batch_set_state", "hf_batch_get_state", "hf_batch_run", "hf_batch_run_flux", "hf_batch_end",
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
-    "hf_steady_setup", "hf_steady_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
+    "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
     "hf_tangent_setup", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_get_sizes", "hf_get_csr", "hf_spmv",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
@@ -132,6 +132,8 @@ def load_library():
         "hf_flux_sample": [vp, i32, pi, pd, pd],
         "hf_steady_setup": [vp, i32, pi, i32],
         "hf_steady_solve": [vp, pd, i32, dbl, dbl, i32, pi, pd],
+        "hf_steady_picard_setup": [vp, i32, pi, i32],
+        "hf_steady_picard_solve": [vp, pd, i32, dbl, dbl, i32, dbl, i32, pi, pi, pd, pd],
         "hf_set_load": [vp, pd],
         "hf_get_load": [vp, pd],
         "hf_hold_load": [vp],
@@ -589,6 +591,32 @@ class HeatflowHIP:
         self.last_iters, self.last_resid = it.value, res.value
         self._check(rc)
         return it.value, res.value
+
+    def steady_picard_setup(self, dofs, precond=PC_JACOBI):
+        """steady_setup for the steady state under kappa(T) / rho_c(T) tables (hf_steady_picard_setup): K is
+        valued at the current state through the conductivity tables; with no table set it is steady_setup's K."""
+        d = _i32(dofs)
+        self._check(self._lib.hf_steady_picard_setup(self._ctx, len(d), _pi(d) if len(d) else None, int(precond)))
+        self.n_steady = len(d)
+
+    def steady_picard_solve(self, g, use_load=False, rtol=1e-10, atol=0.0, max_it=20000, picard_tol=1e-6, max_sweeps=50):
+        """Picard iteration K(x_{k-1}) x_k = F on the free rows, x_k = g on the steady set, from the current state until
+        max |x_k - x_{k-1}| <= picard_tol.  The answer becomes the state.  Returns {"sweeps", "iters" (per sweep), "change",
+        "nl_resid"}, also kept as ``last_picard``; raises NotConverged when max_sweeps run out or a linear solve fails (the
+        state is then the last iterate and ``last_picard`` is filled)."""
+        g = _f64(g)
+        if g.shape != (getattr(self, "n_steady", -1),):
+            raise ValueError(f"steady_picard_solve: expected {getattr(self, 'n_steady', 0)} boundary values (steady_picard_setup first)")
+        ms = int(max_sweeps)
+        sw, chg, nl = C.c_int32(), C.c_double(), C.c_double()
+        its = np.zeros(max(ms, 1), dtype=np.int32)
+        rc = self._lib.hf_steady_picard_solve(self._ctx, _pd(g), 1 if use_load else 0, rtol, atol, int(max_it), float(picard_tol), ms,
+                                              C.byref(sw), _pi(its), C.byref(chg), C.byref(nl))
+        info = {"sweeps": sw.value, "iters": [int(v) for v in its[:sw.value]], "change": chg.value, "nl_resid": nl.value}
+        self.last_picard = info
+        self.last_iters, self.last_resid = sum(info["iters"]), nl.value
+        self._check(rc)
+        return info
 
     def set_load(self, F):
         """Load of the time step (b = M u^n + dt F): n values, or None to clear it."""

@@ -214,12 +214,16 @@ class HeatProblem:
 
 
     # -- steady state and pre-heated transients (with_ir_steady.ipynb cells 17-23) -------------
-    def solve_steady(self, bcs=None, t=0.0, use_load=False):
+    def solve_steady(self, bcs=None, t=0.0, use_load=False, picard_tol=1e-6, max_sweeps=50):
         """Steady state K u = F with its own Dirichlet list ``bcs`` (default: the problem's), merged last-wins and
         evaluated at ``t``; K is the r-weighted stiffness of the transient operator (steady state), F the
         load when ``use_load`` and one is set, else 0.  The answer becomes the state.  Returns (u, iters, resid).
         :meth:`run_tangent` refuses the steady state (HF_ERR_STATE) until :meth:`set_state`: it depends on the
-        conductivities, and the tangents of a run start at zero."""
+        conductivities, and the tangents of a run start at zero.
+        With ``kappa_tables`` or ``rhoc_tables`` the steady state is nonlinear: a Picard iteration from the current state
+         until max |x_k - x_{k-1}| <= ``picard_tol``, at most ``max_sweeps`` sweeps (NotConverged beyond).  Then
+        ``iters`` is the sum over the sweeps, ``resid`` the relative residual of the nonlinear problem at the answer, and
+        ``steady_info`` holds {"sweeps", "iters" per sweep, "change", "nl_resid"}."""
         bcs = self.bcs if bcs is None else list(bcs)
         if not bcs:
             raise ValueError("solve_steady: no Dirichlet condition (the stiffness alone is singular)")
@@ -227,6 +231,11 @@ class HeatProblem:
         for bc in bcs:
             bc.update(t)
         g = gather_bc_values(bcs, owner, pos)
+        if self.kappa_tables or self.rhoc_tables:
+            self.backend.steady_picard_setup(dofs, self.precond)
+            info = self.backend.steady_picard_solve(g, use_load, self.rtol, self.atol, self.max_it, picard_tol, max_sweeps)
+            self.steady_info = info
+            return self.backend.get_state(), sum(info["iters"]), info["nl_resid"]
         self.backend.steady_setup(dofs, self.precond)
         it, res = self.backend.steady_solve(g, use_load, self.rtol, self.atol, self.max_it)
         return self.backend.get_state(), it, res

@@ -295,10 +295,35 @@ int hf_flux_sample(hf_ctx* ctx, int32_t n_s, const int32_t* nodes, double* grad_
  *        load set and hf_set_load / hf_hold_load while a batch is open return HF_ERR_STATE: a load is never dropped.
  * hf_hold_load     F_i = (K_free u)_i for the rows outside the transient's set B, F_i = 0 on B, from the current state u
  *        (needs hf_steady_setup), and sets it as the load: from u = u_ss with boundary values u_ss on B the transient stays.
+ *        It uses the steady set-up made last, hf_steady_setup's or hf_steady_picard_setup's.
  * hf_get_load      copies the current load out (HF_ERR_STATE if none is set). */
 int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs_s, int32_t precond);
 int hf_steady_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, double rtol, double atol, int32_t max_it, int32_t* iters,
                     double* resid);
+
+/* Steady state under kappa(T) / rho_c(T) tables: a Picard iteration.  K(x) = the r-weighted stiffness with
+ * kappa_e = table_tag(T_e(x)) for a tabled tag and the constant otherwise - T_e, the table evaluation and the element matrix of
+ * the transient's re-valuation, entry for entry its dt K part at dt = 1 valued at the same state.  Capacity tables do not enter K.
+ *     x_0 = the current state (hf_set_state first)
+ *     sweep k = 1, 2, ...:  K_hat_S(x_{k-1}) x_k = F - K(x_{k-1})[:, S] g_S on the free rows, (x_k)_S = g_S; PCG started from
+ *                           x_{k-1} with the stopping rule of hf_step; change_k = max |x_k - x_{k-1}|; stop when <= picard_tol
+ *     after the last sweep: K is valued once more at the returned state u and kept as assembled (K_free, for hf_hold_load)
+ * hf_steady_picard_setup  arguments and checks of hf_steady_setup; values K at the current state and, for precond = 1, builds the
+ *        steady hierarchy from that K_hat_S.  The hierarchy stays frozen over the sweeps (the fine level uses the current K and
+ *        D^-1; the fused fine-level legs are not used after a re-valuation).  Works with conductivity tables, capacity tables,
+ *        both or none (then it is the linear problem: sweep 2 starts converged).  hf_set_kappa_tables, hf_set_rhoc_tables
+ *        (setting or clearing), hf_set_materials and hf_update_kappa make it stale.  (A set-up of hf_steady_setup made before
+ *        tables were set stays ready with its constant-coefficient stiffness.)
+ * hf_steady_picard_solve  sweeps = number of sweeps run, iters[k-1] = PCG iterations of sweep k (max_sweeps entries, may be
+ *        NULL), change = the last change_k, nl_resid = ||D^-1 (b(u) - K_hat_S(u) u)|| / ||D^-1 b(u)|| from the final valuation:
+ *        the relative start residual a further sweep would see.  HF_OK when change <= picard_tol.  HF_ERR_NOCONV when max_sweeps
+ *        run out or a linear solve fails: the state is the last iterate, every output is filled and K is valued at that state,
+ *        so hf_hold_load still holds it.  A multigrid breakdown finishes the sweep with Jacobi.  HF_ERR_ARG (before any launch):
+ *        null g_s, bad tolerances, picard_tol < 0, max_sweeps outside 1..1000.  HF_ERR_STATE: before hf_steady_picard_setup, or
+ *        the materials / tables changed since.  The result becomes the state; history and tangents as after hf_steady_solve. */
+int hf_steady_picard_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs_s, int32_t precond);
+int hf_steady_picard_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, double rtol, double atol, int32_t max_it,
+                           double picard_tol, int32_t max_sweeps, int32_t* sweeps, int32_t* iters, double* change, double* nl_resid);
 int hf_set_load(hf_ctx* ctx, const double* F);
 int hf_hold_load(hf_ctx* ctx);
 int hf_get_load(hf_ctx* ctx, double* F);
@@ -359,8 +384,8 @@ int hf_get_tangent(hf_ctx* ctx, int32_t j, double* s);
  *        hf_set_mesh.  hf_set_mesh removes the tables.
  * While tables are set: hf_assemble in another mode and hf_update_kappa on a tabled tag -> HF_ERR_ARG; hf_batch_begin,
  * hf_tangent_setup / hf_run_tangent and hf_steady_setup / hf_steady_solve -> HF_ERR_STATE.  Every error returns before any
- * launch.  hf_set_load keeps working.  Not supported (refused, never approximated): a Picard
- * steady state, batched / affine sweeps, tangents, and rebuilding the hierarchy during a run.
+ * launch.  hf_set_load keeps working.  The steady state under tables is hf_steady_picard_setup / hf_steady_picard_solve.  Not
+ * supported (refused, never approximated): batched / affine sweeps, tangents, and rebuilding the hierarchy during a run.
  * hf_get_picard_change  max over all nodes of |u^{n+1,p} - u^{n+1,p-1}| of the last step's last sweep (u^{n+1,0} = u*, so for
  *        p = 1 the change from the evaluation state); HF_ERR_STATE before the first step with tables. */
 int hf_set_kappa_tables(hf_ctx* ctx, int32_t n_tab, const int32_t* tags, const double* t0, const double* dT, const int32_t* n_knots,
@@ -429,7 +454,7 @@ int hf_time_kernel(hf_ctx* ctx, int32_t which, int32_t reps, double* ms_avg);
 int hf_set_profile(hf_ctx* ctx, int32_t on);
 int hf_get_profile(hf_ctx* ctx, double* spmv_ms_sum, int64_t* spmv_launches);
 /* GPU time (ms, HIP events on the ctx stream) of the last hf_step / hf_run / hf_assemble / hf_steady_setup (assembly and
- * elimination) / hf_steady_solve / hf_hold_load. */
+ * elimination) / hf_steady_solve / hf_steady_picard_solve (the whole solve) / hf_hold_load. */
 int hf_last_gpu_ms(hf_ctx* ctx, double* ms);
 
 #ifdef __cplusplus
