@@ -1,0 +1,70 @@
+"""Anisotropic conductivities of a configuration (hf_set_anisotropy).
+
+A material keeps its ``k`` and may add ``k_aniso: {r: m_r, z: m_z}``: it then conducts with k_r = m_r k along the radius and
+k_z = m_z k along the cell axis.  Either key may be absent and is then 1; both must be positive and finite.  Multipliers, not two
+absolute values, so that everything that scales a material's ``k`` (kappa sweeps, ``--k-range``, the affine batch) keeps its
+meaning: both directions scale and the ratio stays.
+
+Not combined with the temperature-dependent keys (k_table, k_power, cv_table, cv_einstein) in one configuration - the table
+kernels are isotropic - nor with a fit or tangent on the anisotropic material itself, nor with the 1-D model.
+"""
+from __future__ import annotations
+
+import math
+
+from .kappa_t import CV_TABLE_KEYS, TABLE_KEYS, table_keys
+
+KEY = "k_aniso"
+
+
+def material_aniso(name, mat):
+    """(m_r, m_z) of the material block ``mat`` (``mats.<name>``), or None when it has no ``k_aniso`` key.  ValueError naming
+    the material for anything but ``{r: > 0, z: > 0}`` (either key optional)."""
+    if not isinstance(mat, dict) or KEY not in mat:
+        return None
+    block = mat[KEY]
+    if not isinstance(block, dict):
+        raise ValueError(f"mats.{name}.{KEY}: a mapping with the keys r and / or z expected (got {block!r})")
+    extra = sorted(str(k) for k in block if k not in ("r", "z"))
+    if extra:
+        raise ValueError(f"mats.{name}.{KEY}: unknown key(s) {', '.join(extra)} (r and z are the multipliers of k along r and z)")
+    out = []
+    for key in ("r", "z"):
+        try:
+            v = float(block.get(key, 1.0))
+        except (TypeError, ValueError):
+            raise ValueError(f"mats.{name}.{KEY}.{key}: not a number ({block.get(key)!r})") from None
+        if not (math.isfinite(v) and v > 0.0):
+            raise ValueError(f"mats.{name}.{KEY}.{key} must be positive and finite (got {v!r})")
+        out.append(v)
+    return out[0], out[1]
+
+
+def aniso_keys(cfg, names=None):
+    """['mats.<name>.k_aniso', ...] of the materials of ``cfg`` (of ``names`` only, when given) that carry the key."""
+    return [f"mats.{name}.{KEY}" for name, mat in sorted((cfg.get("mats") or {}).items())
+            if isinstance(mat, dict) and KEY in mat and (names is None or name in names)]
+
+
+def check_config(cfg):
+    """Every ``k_aniso`` block of ``cfg`` parsed (ValueError for a bad one), and ValueError naming the keys if the configuration
+    also carries a kappa(T) or cv(T) key.  Returns {material name: (m_r, m_z)}."""
+    out = {}
+    for name, mat in sorted((cfg.get("mats") or {}).items()):
+        m = material_aniso(name, mat)
+        if m is not None:
+            out[name] = m
+    if out:
+        tables = table_keys(cfg, TABLE_KEYS + CV_TABLE_KEYS)
+        if tables:
+            raise ValueError(f"anisotropic conductivities ({', '.join(aniso_keys(cfg))}) are not supported together with "
+                             f"temperature-dependent coefficients ({', '.join(tables)}): the table kernels are isotropic")
+    return out
+
+
+def refuse_aniso(cfg, where, names=None):
+    """ValueError naming the keys if ``cfg`` (its materials ``names`` only, when given) asks for an anisotropic conductivity:
+    ``where`` does not support it."""
+    keys = aniso_keys(cfg, names)
+    if keys:
+        raise ValueError(f"{where} does not support anisotropic conductivities ({', '.join(keys)})")

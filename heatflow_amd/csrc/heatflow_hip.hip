@@ -93,6 +93,12 @@ void kt_free(hf_ctx* ctx) {
   K = hf_ctx::KappaT();
 }
 
+// hf_set_anisotropy's state: every tag isotropic again
+void an_free(hf_ctx* ctx) {
+  dev_free(&ctx->an.d_m);
+  ctx->an = hf_ctx::Aniso();
+}
+
 // "kappa(T)" or "rho_c(T)": the kind of tables a refusal names (conductivity tables first: their texts are the ones of before)
 const char* kt_kind(const hf_ctx* ctx) { return ctx->kt.k_on || !ctx->kt.c_on ? "kappa(T)" : "rho_c(T)"; }
 
@@ -106,6 +112,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   load_free(ctx);
   tangent_free(ctx);
   kt_free(ctx);
+  an_free(ctx);
   ctx->n = n; ctx->ne = ne; ctx->nnz = static_cast<int64_t>(T.colidx.size());
   ctx->nchunks = (n + RB - 1) / RB;
   ctx->nblk_a = (n + RBA - 1) / RBA;
@@ -624,7 +631,7 @@ int hf_destroy(hf_ctx* ctx) {
   dev_free(&ctx->d_uprev); dev_free(&ctx->d_ustart);
   dev_free(&ctx->d_u); dev_free(&ctx->d_b); dev_free(&ctx->d_r); dev_free(&ctx->d_p); dev_free(&ctx->d_Ap);
   free_batch(ctx); free_batch_state(ctx->fluxb); free_batch_cols(ctx); free_amg(ctx); free_responses(ctx); proj_free(ctx); dev_free(&ctx->d_z); dev_free(&ctx->d_z2);
-  steady_free(ctx); load_free(ctx); tangent_free(ctx); kt_free(ctx);
+  steady_free(ctx); load_free(ctx); tangent_free(ctx); kt_free(ctx); an_free(ctx);
   dev_free(&ctx->d_M1); dev_free(&ctx->d_dinv1); dev_free(&ctx->d_gz); dev_free(&ctx->d_gr); dev_free(&ctx->d_bz); dev_free(&ctx->d_br);
   dev_free(&ctx->d_tmp); dev_free(&ctx->d_part_pAp); dev_free(&ctx->d_part_rz); dev_free(&ctx->d_part_zz);
   dev_free(&ctx->d_part_bn); dev_free(&ctx->d_scal); dev_free(&ctx->d_samp_idx); dev_free(&ctx->d_samp); dev_free(&ctx->d_fsamp_idx);
@@ -730,6 +737,58 @@ int hf_set_materials(hf_ctx* ctx, int32_t n_mat, const int32_t* tags, const doub
   return tangent_reset(ctx);   // the tangents belonged to the old coefficients
 }
 
+int hf_set_anisotropy(hf_ctx* ctx, int32_t n, const int32_t* tags, const double* m_z, const double* m_r) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh || !ctx->have_mat) return fail(ctx, HF_ERR_STATE, "hf_set_anisotropy needs hf_set_mesh and hf_set_materials first");
+  if (n < 0) return fail(ctx, HF_ERR_ARG, "hf_set_anisotropy: negative tag count");
+  if (n > 0 && (!tags || !m_z || !m_r)) return fail(ctx, HF_ERR_ARG, "hf_set_anisotropy: null pointer");
+  std::vector<double> by_tag(2 * static_cast<size_t>(ctx->tab_len), 1.0);   // (m_z, m_r) by cell tag: what the fingerprint hashes
+  std::vector<char> listed(ctx->tab_len, 0), aniso(ctx->tab_len, 0);
+  std::vector<double2> m(64, make_double2(1.0, 1.0));
+  bool any = false;
+  for (int32_t i = 0; i < n; ++i) {
+    const int32_t tg = tags[i];
+    if (tg < 0 || tg >= ctx->tab_len || !ctx->h_tag_used[tg]) return fail(ctx, HF_ERR_ARG, "hf_set_anisotropy: tag %d is not a cell tag of the mesh", tg);
+    if (listed[tg]) return fail(ctx, HF_ERR_ARG, "hf_set_anisotropy: tag %d listed twice", tg);
+    if (!(m_z[i] > 0.0) || !std::isfinite(m_z[i]) || !(m_r[i] > 0.0) || !std::isfinite(m_r[i]))
+      return fail(ctx, HF_ERR_ARG, "hf_set_anisotropy: multipliers of tag %d are not positive and finite", tg);
+    listed[tg] = 1;
+    if (m_z[i] == 1.0 && m_r[i] == 1.0) continue;   // both 1: an isotropic tag
+    aniso[tg] = 1; any = true;
+    by_tag[2 * tg] = m_z[i]; by_tag[2 * tg + 1] = m_r[i];
+  }
+  if (any && ctx->kt.on)
+    return fail(ctx, HF_ERR_STATE, "hf_set_anisotropy: %s tables are set (the table kernels are isotropic)", kt_kind(ctx));
+  if (any && (!ctx->rg_ok || (ctx->assembled && ctx->mode != HF_ASM_ROW_GATHER)))
+    return fail(ctx, HF_ERR_ARG, "hf_set_anisotropy: anisotropic conductivities are assembled by the row-gather kernel only (HF_ASM_ROW_GATHER on a mesh with row-gather lists)");
+  for (int tg = 0; tg < ctx->tab_len; ++tg) {
+    if (!aniso[tg]) continue;
+    const size_t q = std::find(ctx->h_rg_tags.begin(), ctx->h_rg_tags.end(), tg) - ctx->h_rg_tags.begin();
+    if (q >= ctx->h_rg_tags.size() || q >= 64) return fail(ctx, HF_ERR_ARG, "hf_set_anisotropy: tag %d has no row-gather dictionary entry", tg);
+    m[q] = make_double2(by_tag[2 * tg], by_tag[2 * tg + 1]);
+  }
+  HF_HIP(hipSetDevice(ctx->dev));
+  if (!any && !ctx->an.on) return HF_OK;   // nothing was and nothing is anisotropic: the existing kernels and their operators stay
+  if (any) {
+    if (!ctx->an.d_m) HF_TRY(dev_alloc(ctx, &ctx->an.d_m, 64));
+    HF_HIP(copy_sync(ctx, ctx->an.d_m, m.data(), sizeof(double2) * 64, hipMemcpyHostToDevice));
+    ctx->an.h_tag = std::move(aniso);
+    ctx->an.hash = fnv1a(by_tag.data(), sizeof(double) * by_tag.size());
+    ctx->an.on = true;
+  } else {
+    an_free(ctx);
+  }
+  free_batch(ctx);             // a batch holds operators of the old coefficients
+  ctx->assembled = false;
+  ctx->pred_iters = 0;
+  ctx->steady.ready = false;   // K depends on the multipliers: hf_steady_setup again
+  // the tangent columns were checked against the old set of anisotropic tags: hf_tangent_setup again
+  const bool from_steady = ctx->tan.steady_state;
+  tangent_free(ctx);
+  ctx->tan.steady_state = from_steady;
+  return HF_OK;
+}
+
 int hf_update_kappa(hf_ctx* ctx, int32_t n_mat, const int32_t* tags, const double* kappa) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->have_mat || !ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_update_kappa needs a completed hf_assemble first");
@@ -783,6 +842,8 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
   if (mode < 0 || mode > 3) return fail(ctx, HF_ERR_ARG, "hf_assemble: unknown mode %d", mode);
   if (ctx->kt.on && mode != HF_ASM_ROW_GATHER)
     return fail(ctx, HF_ERR_ARG, "hf_assemble: %s tables are evaluated by the row-gather kernel only (HF_ASM_ROW_GATHER)", kt_kind(ctx));
+  if (ctx->an.on && (mode != HF_ASM_ROW_GATHER || !ctx->rg_ok))
+    return fail(ctx, HF_ERR_ARG, "hf_assemble: anisotropic conductivities (hf_set_anisotropy) are assembled by the row-gather kernel only (HF_ASM_ROW_GATHER)");
   HF_HIP(hipSetDevice(ctx->dev));
   ctx->dt_step = dt;
   ctx->dt = ctx->scheme == HF_TIME_BDF2 ? 2.0 * dt / 3.0 : dt;   // BDF2: A' = M + (2/3) dt K
@@ -887,6 +948,7 @@ int kt_set_tables(hf_ctx* ctx, bool cap, int32_t n_tab, const int32_t* tags, con
     return HF_OK;
   }
   if (!tags || !t0 || !dT || !n_knots || !values) return fail(ctx, HF_ERR_ARG, "%s: null pointer", fn);
+  if (ctx->an.on) return fail(ctx, HF_ERR_STATE, "%s: anisotropic conductivities are set (hf_set_anisotropy; the table kernels are isotropic)", fn);
   if (!ctx->rg_ok || (ctx->assembled && ctx->mode != HF_ASM_ROW_GATHER))
     return fail(ctx, HF_ERR_ARG, "%s: %s is evaluated by the row-gather kernel only (HF_ASM_ROW_GATHER on a mesh with row-gather lists)", fn, what);
   if (cap && ct_smem_bytes(ctx->max_blk_nnz, ctx->rg_max_dict) + 2 * 64 * sizeof(KTab) > 160 * 1024)
@@ -1303,6 +1365,8 @@ int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
   if (n_par < 1 || n_par > NV_MAX) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: 1..%d parameters (got %d)", NV_MAX, n_par);
   if (!tag_col) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tag_col is null");
   for (int t = 0; t < ctx->tab_len; ++t) {
+    if (ctx->an.on && tag_col[t] >= 0 && tag_col[t] < n_par && ctx->an.h_tag[t])
+      return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tag %d is anisotropic (hf_set_anisotropy; tangents of an anisotropic conductivity are not supported)", t);
     if (tag_col[t] < -1 || tag_col[t] >= n_par)
       return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tag %d maps to column %d outside [-1,%d)", t, tag_col[t], n_par);
     if (tag_col[t] >= 0 && !ctx->h_tag_used[t]) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tag %d is not a cell tag of the mesh", t);
@@ -1470,7 +1534,7 @@ int steady_setup_impl(hf_ctx* ctx, const char* fn, bool picard, int32_t n_s, con
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   // K = the dt K part of the transient operator at dt = 1 (r-weighted), kept as assembled for hf_hold_load
   if (picard) HF_TRY(steady_revalue(ctx, ctx->kt.hdr ? ctx->kt.hdr : S.hdr0, ctx->d_u, S.Kfree));
-  else HF_TRY(launch_assemble_rows<true>(ctx, ctx->d_kappa_rg, ctx->d_rhoc_rg, 1.0, nullptr, S.Kfree));
+  else HF_TRY(launch_assemble_rows_any<true>(ctx, ctx->d_kappa_rg, ctx->d_rhoc_rg, 1.0, nullptr, S.Kfree));
   {
     SteadyScope sw(ctx);
     HF_TRY(build_lift(ctx));    // lifting lists of S (into the swapped fields)
@@ -1500,6 +1564,8 @@ int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t preco
 int hf_steady_picard_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t precond) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->have_mesh || !ctx->have_mat) return fail(ctx, HF_ERR_STATE, "hf_steady_picard_setup needs hf_set_mesh and hf_set_materials first");
+  if (ctx->an.on)
+    return fail(ctx, HF_ERR_STATE, "hf_steady_picard_setup: anisotropic conductivities are set (hf_set_anisotropy; the table kernels are isotropic)");
   return steady_setup_impl(ctx, "hf_steady_picard_setup", true, n_s, dofs, precond);
 }
 
@@ -1787,7 +1853,7 @@ int hf_batch_set_affine(hf_ctx* ctx, int32_t n_tags, const int32_t* tags, const 
   HF_TRY(dev_alloc(ctx, &t_scratch.p, ctx->nnz));
   HF_HIP(copy_sync(ctx, t_k.p, ind.data(), sizeof(double) * tab, hipMemcpyHostToDevice));
   HF_HIP(copy_sync(ctx, t_c.p, zeros.data(), sizeof(double) * tab, hipMemcpyHostToDevice));
-  if (ctx->rg_ok) HF_TRY(launch_assemble_rows(ctx, t_k.p, t_c.p, ctx->dt, t_scratch.p, B.A1));
+  if (ctx->rg_ok) HF_TRY(launch_assemble_rows_any(ctx, t_k.p, t_c.p, ctx->dt, t_scratch.p, B.A1));   // (multipliers kept: A + delta A1 shifts k)
   else HF_TRY(launch_assemble_lds(ctx, true, t_k.p, t_c.p, ctx->dt, t_scratch.p, B.A1));
   // Dirichlet elimination of A1: lifting entries kept aside, Dirichlet rows and columns zero (the unit diagonal is A's)
   if (ctx->nbc > 0) {

@@ -4,7 +4,7 @@
 // parameter_sweep.py:401-446 re-reads the mesh and factorises for itself, run_with_diamond.py:389-394).  The blob holds
 // what build_amg uploads: per level the smoother's D^-1 and damping, the operators A_l, P_l, R_l and the fused legs with
 // their kernel geometry and compressed column streams, and the dense inverse of the coarsest level; plus a fingerprint
-// of the fine operator it was built from (time step, coefficient tables, Dirichlet set), so that the installing context
+// of the fine operator it was built from (time step, coefficient tables, anisotropy multipliers, Dirichlet set), so that the installing context
 // knows whether its own operator is that one (fused finest-level legs usable) or another point of the sweep (frozen
 // hierarchy: explicit legs on the finest level until the next rebuild).
 #pragma once
@@ -22,6 +22,7 @@ struct AmgBlobHeader {
   double opc, dt;
   uint64_t bc_hash;
   int32_t scheme, pad_;   // time scheme of the operator (hf_set_time_scheme); dt is the step hf_assemble was called with
+  uint64_t an_hash;       // hf_set_anisotropy's multipliers (0: none); the header keeps its padded size
 };
 
 struct CsrRecord {      // one operator: scalars, then ptr / idx / values / (dptr, dict, cid)
@@ -50,11 +51,12 @@ int operator_print(hf_ctx* ctx, OperatorPrint& f) {
   std::vector<int32_t> dofs(ctx->nbc);
   if (ctx->nbc > 0) HF_HIP(copy_sync(ctx, dofs.data(), ctx->d_bc_dofs, sizeof(int32_t) * ctx->nbc, hipMemcpyDeviceToHost));
   f.bc_hash = fnv1a(dofs.data(), sizeof(int32_t) * dofs.size());
+  f.an_hash = ctx->an.on ? ctx->an.hash : 0;
   return HF_OK;
 }
 
 bool same_print(const OperatorPrint& a, const OperatorPrint& b) {
-  return a.dt == b.dt && a.scheme == b.scheme && a.nbc == b.nbc && a.bc_hash == b.bc_hash && a.kappa == b.kappa && a.rhoc == b.rhoc;
+  return a.dt == b.dt && a.scheme == b.scheme && a.nbc == b.nbc && a.bc_hash == b.bc_hash && a.an_hash == b.an_hash && a.kappa == b.kappa && a.rhoc == b.rhoc;
 }
 
 struct BlobOut {          // sizes first (dst == nullptr), then the same walk writes
@@ -100,6 +102,7 @@ int walk_hierarchy(hf_ctx* ctx, BlobOut& o, const OperatorPrint& f) {
   h.coarse_n = ctx->coarse_n; h.coarse_ld = ctx->coarse_ld; h.nbc = f.nbc; h.tab_len = ctx->tab_len; h.opc = ctx->amg_opc; h.dt = f.dt;
   h.bc_hash = f.bc_hash;
   h.scheme = f.scheme;
+  h.an_hash = f.an_hash;
   const size_t head_at = o.at;
   o.host(&h, sizeof h);
   o.host(f.kappa.data(), sizeof(double) * f.kappa.size());
@@ -232,7 +235,7 @@ int install_hierarchy(hf_ctx* ctx, const unsigned char* blob, size_t bytes) {
   if (h.nl < 1 || h.nl > 32 || h.tab_len != ctx->tab_len || h.coarse_n < 0 || h.coarse_n > 4096 || (h.coarse_n > 0 && (h.coarse_ld < h.coarse_n || (h.coarse_ld & 3))))
     return fail(ctx, HF_ERR_ARG, "hf_amg_install: header does not fit this context");
   OperatorPrint theirs;
-  theirs.dt = h.dt; theirs.nbc = h.nbc; theirs.bc_hash = h.bc_hash; theirs.scheme = h.scheme;
+  theirs.dt = h.dt; theirs.nbc = h.nbc; theirs.bc_hash = h.bc_hash; theirs.scheme = h.scheme; theirs.an_hash = h.an_hash;
   const double* pk = static_cast<const double*>(in.take(sizeof(double) * h.tab_len));
   const double* pc = static_cast<const double*>(in.take(sizeof(double) * h.tab_len));
   if (!in.ok) return fail(ctx, HF_ERR_ARG, "hf_amg_install: blob truncated");

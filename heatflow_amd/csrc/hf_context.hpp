@@ -156,6 +156,15 @@ struct hf_ctx {
   int64_t n_rg_ell = 0, n_rg_dict = 0, n_cdict = 0;
   std::vector<int32_t> h_rg_tags;
   double *d_kappa_rg = nullptr, *d_rhoc_rg = nullptr;
+  // Anisotropic conductivities (hf_set_anisotropy): multipliers (m_z, m_r) by tag-dictionary index for k_assemble_rows_an, which
+  // runs in place of k_assemble_rows while `on` (some tag has m_z != 1 or m_r != 1); h_tag: that, by cell tag.
+  struct Aniso {
+    bool on = false;
+    double2* d_m = nullptr;
+    std::vector<char> h_tag;
+    uint64_t hash = 0;          // of the multipliers by cell tag (0 while off): part of the operator's fingerprint (OperatorPrint)
+    int grid = 0, grid_k = 0;   // persistent grids of k_assemble_rows_an<false> / <true>
+  } an;
   // device: matrices
   double *d_M = nullptr, *d_A = nullptr, *d_dinv = nullptr;
   // device: Dirichlet
@@ -232,7 +241,7 @@ struct hf_ctx {
   double amg_opc = 0.0, amg_setup_s = 0.0;
   // what the fine operator the hierarchy was built from depends on besides the mesh (hf_amg_io.hpp): time step, coefficient
   // tables, Dirichlet set - compared with the context's own operator whenever a kept or installed hierarchy meets a new hf_assemble
-  struct OperatorPrint { double dt = 0.0; std::vector<double> kappa, rhoc; int32_t nbc = 0; uint64_t bc_hash = 0; int32_t scheme = 0; } amg_print;
+  struct OperatorPrint { double dt = 0.0; std::vector<double> kappa, rhoc; int32_t nbc = 0; uint64_t bc_hash = 0; int32_t scheme = 0; uint64_t an_hash = 0; } amg_print;
   long long amg_fallbacks = 0;   // steps finished by Jacobi-PCG after a multigrid-PCG breakdown
   // steady state (hf_steady_setup / hf_steady_solve): the stiffness K on the pattern - as assembled (Kfree, for hf_hold_load)
   // and with its own Dirichlet set S eliminated (K) -, the lifting columns K[free, S], D^-1 and a multigrid hierarchy of

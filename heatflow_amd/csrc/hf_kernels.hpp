@@ -368,6 +368,143 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows(int nblk, int cap /* slab
   }
 }
 
+// Anisotropic element stiffness (hf_set_anisotropy): the tensor diag(k_z, k_r) in (z, r), constant per element.  The gradient of
+// a hat function is perpendicular to the opposite edge, so the z-differences of the edges carry k_r and the r-differences k_z:
+//   K_ab = ks * (k_r * (e_a.x * e_b.x) + k_z * (e_a.y * e_b.y)),  ks = area * (rsum / 3) / d^2
+// Everything else - edges, d, rsum, M - is element_row's, and the products commute, so the three per-vertex evaluations of a
+// triangle still agree bit for bit (A stays exactly symmetric).
+__device__ __forceinline__ ElemRow element_row_an(const double2 Pi, const double2 Pj, const double2 Pk, double rho_c, double k_z, double k_r) {
+#pragma clang fp contract(off)
+  const double eix = Pk.x - Pj.x, eiy = Pk.y - Pj.y;     // edge opposite "me"
+  const double ejx = Pi.x - Pk.x, ejy = Pi.y - Pk.y;     // opposite next
+  const double ekx = Pj.x - Pi.x, eky = Pj.y - Pi.y;     // opposite previous
+  const double c1 = fabs(ejx * eky - ejy * ekx), c2 = fabs(ekx * eiy - eky * eix), c3 = fabs(eix * ejy - eiy * ejx);
+  const double d = fmax(fmax(c1, c2), c3);
+  const double ab_lo = fmin(Pi.y, Pj.y), ab_hi = fmax(Pi.y, Pj.y);
+  const double lo = fmin(ab_lo, Pk.y), hi = fmax(ab_hi, Pk.y), mid = fmax(ab_lo, fmin(ab_hi, Pk.y));
+  const double rsum = (lo + mid) + hi;
+  const double area = 0.5 * d;
+  const double ks = area * (rsum * (1.0 / 3.0)) * (1.0 / (d * d));
+  const double ms30 = rho_c * area * (1.0 / 30.0), ms60 = rho_c * area * (1.0 / 60.0);
+  ElemRow o;
+  o.k0 = ks * (k_r * (eix * eix) + k_z * (eiy * eiy));
+  o.k1 = ks * (k_r * (eix * ejx) + k_z * (eiy * ejy));
+  o.k2 = ks * (k_r * (eix * ekx) + k_z * (eiy * eky));
+  o.m0 = ms30 * (2.0 * Pi.y + rsum);
+  o.m1 = ms60 * (rsum + (Pi.y + Pj.y));
+  o.m2 = ms60 * (rsum + (Pi.y + Pk.y));
+  return o;
+}
+
+// k_assemble_rows with a second 64-entry table by tag-dictionary index, an_idx[tg] = (m_z, m_r): the conductivity of tag tg is
+// k_z = m_z kappa along z and k_r = m_r kappa along r.  Lists, staging, persistent workgroups, the LDS slab (same footprint) and
+// the list-order summation are k_assemble_rows'.  An element whose tag has m_z == m_r goes through element_row with kappa * m, so
+// with every multiplier 1 (x * 1.0 is exact) M and A come out bit for bit as k_assemble_rows gives them, and in a mixed mesh
+// every row that touches only such elements keeps its bits.
+template <bool KONLY>
+__global__ __launch_bounds__(RBA) void k_assemble_rows_an(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
+                                                          const int32_t* __restrict__ rowptr,
+                                                          const int4* __restrict__ hdr /* 2 per block */,
+                                                          const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
+                                                          const double2* __restrict__ zrb,
+                                                          const double* __restrict__ kappa_idx, const double* __restrict__ rhoc_idx,
+                                                          const double2* __restrict__ an_idx /* (m_z, m_r) */,
+                                                          double dt, double* __restrict__ Mv, double* __restrict__ Av) {
+  extern __shared__ double smem[];
+  double2* sMA = reinterpret_cast<double2*>(smem);                   // (M, A) per slot
+  double2* sXd = sMA + cap;                                          // coordinates of the block's column list
+  int* sR = reinterpret_cast<int*>(sXd + capd);                      // row starts inside the slab
+  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);               // column-list position per slot, from the 8-aligned start
+  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
+
+  const int t = threadIdx.x;
+  for (int k = t; k < cap; k += RBA) sMA[k] = make_double2(0.0, 0.0);
+
+  // prefetch registers of the next block
+  int4 hA, hB;
+  uint4 pe, pc[RG_NC];
+  double2 px[RG_NX];
+  int pr = 0;
+  auto prefetch = [&](int blk) {
+    hA = hdr[2 * blk];                                               // (k0, nk, d0, nd)
+    hB = hdr[2 * blk + 1];                                           // (ell offset in 16-byte units, groups of 8 visits, local id of row r0, rows)
+    pe = ell[hB.x + t];
+    const int c0 = hA.x >> 3, nc = ((hA.x + hA.y + 7) >> 3) - c0;
+#pragma unroll
+    for (int u = 0; u < RG_NC; ++u) pc[u] = (t + u * RBA < nc) ? cid16[c0 + t + u * RBA] : make_uint4(0, 0, 0, 0);
+#pragma unroll
+    for (int u = 0; u < RG_NX; ++u) px[u] = (t + u * RBA < hA.w) ? zrb[hA.z + t + u * RBA] : make_double2(0.0, 0.0);
+    pr = (t < hB.w) ? rowptr[blk * RBA + t] - hA.x : 0;
+  };
+  int blk = blockIdx.x;
+  if (blk < nblk) prefetch(blk);
+  while (blk < nblk) {
+    // stage the prefetched block
+    const int4 cA = hA, cB = hB;
+    const uint4 ce = pe;
+    const int nc = ((cA.x + cA.y + 7) >> 3) - (cA.x >> 3);
+#pragma unroll
+    for (int u = 0; u < RG_NC; ++u) if (t + u * RBA < nc) sC4[t + u * RBA] = pc[u];
+#pragma unroll
+    for (int u = 0; u < RG_NX; ++u) if (t + u * RBA < cA.w) sXd[t + u * RBA] = px[u];
+    sR[t] = pr;
+    __syncthreads();
+    const int nxt = blk + gridDim.x;
+    if (nxt < nblk) prefetch(nxt);                                   // in flight during the visit loop
+
+    if (t < cB.w) {
+      const int base = sR[t];
+      const int sbase = base + (cA.x & 7);                           // the position array starts at the 8-aligned slot
+      const int ci = cB.z + t;                                       // my own position in the column list
+      const double2 Pi = sXd[ci];
+      double dM = 0.0, dA = 0.0;
+      int pd = 0;                                                    // diagonal: the slot whose column is my own row
+      while (pd < 31 && sC[sbase + pd] < ci) ++pd;
+      for (int g = 0; g < cB.y; ++g) {
+        const uint4 ev = g == 0 ? ce : ell[cB.x + g * RBA + t];
+        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const unsigned e = (w[u >> 1] >> ((u & 1) * 16)) & 0xFFFFu;
+          if (e == 0xFFFFu) continue;
+          const int pj = e & 31u, pk = (e >> 5) & 31u, tg = e >> 10;
+          const double2 Pj = sXd[sC[sbase + pj]], Pk = sXd[sC[sbase + pk]];
+          const double2 m = an_idx[tg];
+          const double kap = kappa_idx[tg], rc = KONLY ? 0.0 : rhoc_idx[tg];
+          const ElemRow r = m.x == m.y ? element_row(Pi, Pj, Pk, rc, kap * m.x) : element_row_an(Pi, Pj, Pk, rc, m.x * kap, m.y * kap);
+          if (KONLY) {
+            dA += r.k0;
+            sMA[base + pj].y += r.k1;
+            sMA[base + pk].y += r.k2;
+            continue;
+          }
+          dM += r.m0;
+          dA += fma(dt, r.k0, r.m0);
+          double2 v = sMA[base + pj];
+          v.x += r.m1;
+          v.y += fma(dt, r.k1, r.m1);
+          sMA[base + pj] = v;
+          v = sMA[base + pk];
+          v.x += r.m2;
+          v.y += fma(dt, r.k2, r.m2);
+          sMA[base + pk] = v;
+        }
+      }
+      sMA[base + pd] = make_double2(dM, dA);
+    }
+    __syncthreads();
+    // stream the slab out and leave it zeroed for the next block (slot k stays with the lane that reads it here)
+    for (int k = t; k < cA.y; k += RBA) {
+      const double2 v = sMA[k];
+      if (!KONLY) Mv[cA.x + k] = v.x;
+      Av[cA.x + k] = v.y;
+      sMA[k] = make_double2(0.0, 0.0);
+    }
+    blk = nxt;
+    // (no barrier needed here, for the reasons given in k_assemble_rows)
+  }
+}
+
 // Read-flux projection right-hand sides by row gather (same lists and staging as k_assemble_rows, plus the block's
 // slice of the state u): b_c[i] = sum over the triangles at node i of (d_c T)_e * |K| (2 r_i + r_j + r_k)/12, summed
 // in list order in a register - no LDS accumulation, no atomics, bitwise reproducible.

@@ -392,9 +392,43 @@ int launch_assemble_rows(hf_ctx* ctx, const double* kappa_idx, const double* rho
   return HF_OK;
 }
 
+// The same with the multipliers of hf_set_anisotropy (k_assemble_rows_an: the LDS footprint of k_assemble_rows, a grid of its own
+// from the occupancy query).  HEATFLOW_ANISO_INFO=1 prints the footprint, the workgroups per CU and the grid once per variant.
+template <bool KONLY = false>
+int launch_assemble_rows_an(hf_ctx* ctx, const double* kappa_idx, const double* rhoc_idx, double dt, double* Mout, double* Aout) {
+  const int cap = (ctx->max_blk_nnz + 1) & ~1;
+  const int capd = ctx->rg_max_dict;
+  const size_t sm = rowgather_smem_bytes(ctx->max_blk_nnz, capd);
+  const void* fn = reinterpret_cast<const void*>(&k_assemble_rows_an<KONLY>);
+  int& grid = KONLY ? ctx->an.grid_k : ctx->an.grid;
+  if (grid == 0) {
+    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
+    int per_cu = 0, ncu = 0;
+    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
+    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
+    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+    if (const char* e = std::getenv("HEATFLOW_ANISO_INFO"))
+      if (e[0] == '1')
+        std::fprintf(stderr, "[aniso] k_assemble_rows_an<%s>: %zu bytes of dynamic LDS, %d workgroups per CU, grid %d of %d blocks\n",
+                     KONLY ? "true" : "false", sm, per_cu, grid, ctx->nblk_a);
+  }
+  hipLaunchKernelGGL(k_assemble_rows_an<KONLY>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr,
+                     ctx->d_rg_hdr, reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid),
+                     ctx->d_rg_zrb, kappa_idx, rhoc_idx, ctx->an.d_m, dt, Mout, Aout);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+// Row-gather assembly with whatever hf_set_anisotropy left: the existing kernel while no tag is anisotropic
+template <bool KONLY = false>
+int launch_assemble_rows_any(hf_ctx* ctx, const double* kappa_idx, const double* rhoc_idx, double dt, double* Mout, double* Aout) {
+  if (ctx->an.on) return launch_assemble_rows_an<KONLY>(ctx, kappa_idx, rhoc_idx, dt, Mout, Aout);
+  return launch_assemble_rows<KONLY>(ctx, kappa_idx, rhoc_idx, dt, Mout, Aout);
+}
+
 int launch_assemble(hf_ctx* ctx) {
   if (ctx->mode == HF_ASM_ROW_GATHER && ctx->rg_ok)
-    return launch_assemble_rows(ctx, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, ctx->d_M, ctx->d_A);
+    return launch_assemble_rows_any(ctx, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, ctx->d_M, ctx->d_A);
   if (ctx->mode == HF_ASM_ROW_GATHER)   // lists not available for this mesh (row > 32 entries or > 64 cell tags): deterministic LDS variant
     return launch_assemble_lds(ctx, true, ctx->d_kappa, ctx->d_rhoc, ctx->dt, ctx->d_M, ctx->d_A);
   if (ctx->mode == HF_ASM_LDS_COLORED || ctx->mode == HF_ASM_LDS_ATOMIC) {

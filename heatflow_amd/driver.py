@@ -42,6 +42,7 @@ def _dump_yaml(obj, f):
 from .bc import P1Space, RowDirichletBC
 from .geometry import stack_no_diamond, stack_with_diamond
 from .heating import HeatingCurve
+from .aniso import check_config, refuse_aniso
 from .kappa_t import material_cv_table, material_table, picard_sweeps, refuse_tables
 from .mesh import Mesh, load_mesh_arrays
 from .solver import DEFAULT_MAX_IT, DEFAULT_RTOL, HeatProblem
@@ -170,7 +171,8 @@ def time_scheme(cfg):
 def _with_scheme(cfg):
     """``cfg`` with the time scheme it runs with written out (``timing.scheme``), for used_config.yaml; with kappa(T) also
     ``timing.picard_sweeps`` and the tables that ran (``kappa_tables``: {material: {T0, dT, k}}); with cv(T) the same under
-    ``rhoc_tables``: {material: {T0, dT, rho_cv}}, written only when a capacity table is set."""
+    ``rhoc_tables``: {material: {T0, dT, rho_cv}}, written only when a capacity table is set.  An anisotropic conductivity
+    travels with its material (``mats.<name>.k_aniso``), so it is written exactly when it is set."""
     out = dict(cfg)
     out["timing"] = dict(cfg.get("timing") or {}, scheme=time_scheme(cfg))
     tables = {}
@@ -249,13 +251,18 @@ class SimulationSession:
         tag_to_k, tag_to_rc = self._tables(stack)
         scheme = time_scheme(cfg)
         kt = self._kappa_tables(cfg, stack)
-        self._ensure_problem(self._problem_key(dt, tag_to_rc, bcs, scheme, kt), tag_to_k, tag_to_rc, dt, bcs,
-                             float(cfg["heating"]["ic_temp"]), scheme, kt)
+        an = self._aniso(stack)
+        self._ensure_problem(self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an), tag_to_k, tag_to_rc, dt, bcs,
+                             float(cfg["heating"]["ic_temp"]), scheme, kt, an)
 
     def _tables(self, stack):
         tag_to_k = {self.material_tags[m.name]: m.properties["k"] for m in stack.materials}
         tag_to_rc = {self.material_tags[m.name]: m.properties["rho_cv"] for m in stack.materials}
         return tag_to_k, tag_to_rc
+
+    def _aniso(self, stack):
+        """{cell tag: (m_r, m_z)} of the materials of ``stack`` with a ``k_aniso`` block ({}: an isotropic configuration)."""
+        return {self.material_tags[m.name]: m.properties["k_aniso"] for m in stack.materials if "k_aniso" in m.properties}
 
     def _kappa_tables(self, cfg, stack):
         """(tables {tag: (T0, dT, values)}, Picard sweeps, capacity tables {tag: (T0, dT, values)}) of a kappa(T) / cv(T)
@@ -296,9 +303,9 @@ class SimulationSession:
             self._heats.append(heat_o)
         return bcs
 
-    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler", kt=None):
+    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler", kt=None, an=None):
         # the resident problem is reusable only for exactly the same Dirichlet DOF sets, in the same order, and time scheme
-        # (and kappa(T) tables and Picard sweeps, when a configuration has them)
+        # (and kappa(T) tables and Picard sweeps, or anisotropy multipliers, when a configuration has them)
         key = (dt, tuple(sorted(tag_to_rc.items())),
                tuple(hashlib.sha1(np.ascontiguousarray(b.row_dofs, dtype=np.int64).tobytes()).hexdigest() for b in bcs),
                scheme)
@@ -306,9 +313,11 @@ class SimulationSession:
             key += (tuple((t, float(v[0]), float(v[1]), tuple(float(x) for x in v[2])) for t, v in sorted(kt[0].items())), kt[1])
             if kt[2]:
                 key += (tuple((t, float(v[0]), float(v[1]), tuple(float(x) for x in v[2])) for t, v in sorted(kt[2].items())),)
+        if an:
+            key += (("k_aniso",) + tuple(sorted(an.items())),)
         return key
 
-    def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme="backward_euler", kt=None):
+    def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme="backward_euler", kt=None, an=None):
         """The resident HeatProblem for ``key`` (built if absent), its operator valued for ``tag_to_k``."""
         if self.problem is None or key != self._key:
             self.close()
@@ -319,7 +328,8 @@ class SimulationSession:
                                        max_it=self.max_it, assembly_mode=self.assembly_mode, precond=self.precond,
                                        amg_reuse=True, pattern=self.pattern, amg=shared["blob"] if shared else None,
                                        scheme=scheme, **({"kappa_tables": kt[0], "picard": kt[1]} if kt else {}),
-                                       **({"rhoc_tables": kt[2]} if kt and kt[2] else {}))
+                                       **({"rhoc_tables": kt[2]} if kt and kt[2] else {}),
+                                       **({"k_aniso": an} if an else {}))
             self._key = key
             self._k = dict(tag_to_k)
             # conductivities the multigrid levels were built for: this problem's, or those of the session that shared them
@@ -380,17 +390,19 @@ class SimulationSession:
         for cfg, stack in zip(cfgs, stacks):
             bcs = self._boundary_conditions(cfg, stack)
             tk, trc = self._tables(stack)
-            key = self._problem_key(float(cfg["timing"]["t_final"]) / int(cfg["timing"]["num_steps"]), trc, bcs, time_scheme(cfg))
+            key = self._problem_key(float(cfg["timing"]["t_final"]) / int(cfg["timing"]["num_steps"]), trc, bcs, time_scheme(cfg),
+                                    None, self._aniso(stack))
             cols.append((bcs, tk, trc, key))
             if int(cfg["timing"]["num_steps"]) != num_steps or float(cfg["heating"]["ic_temp"]) != ic_temp or key != cols[0][3]:
-                raise ValueError("run_batch: the configurations must share time stepping (and scheme), ic_temp, rho_c and the Dirichlet sets")
+                raise ValueError("run_batch: the configurations must share time stepping (and scheme), ic_temp, rho_c, the Dirichlet sets "
+                                 "and the anisotropy multipliers (k_aniso)")
         percol = any(c[1] != cols[0][1] for c in cols)
         mid = cols[nv // 2]
         # conductivities that differ between the columns; a single one (sweep_test.py's kappa_sample list) makes
         # the operators an affine family A + (kappa_j - kappa_ref) A1: two shared matrices instead of nv
         varying = [t for t in mid[1] if any(c[1][t] != mid[1][t] for c in cols)]
         affine = percol and len(varying) == 1
-        self._ensure_problem(mid[3], mid[1], mid[2], dt, mid[0], ic_temp, scheme)
+        self._ensure_problem(mid[3], mid[1], mid[2], dt, mid[0], ic_temp, scheme, None, self._aniso(stacks[nv // 2]))
         prob = self.problem
         be = prob.backend
         if percol and self.precond == 1:             # all columns share the hierarchy: keep every column within its range
@@ -474,9 +486,12 @@ class SimulationSession:
         kt = self._kappa_tables(cfg, stack)
         if kt is not None and tangents:
             refuse_tables(cfg, "tangents")
-        key = self._problem_key(dt, tag_to_rc, bcs, scheme, kt)
+        an = self._aniso(stack)
+        if an and tangents:      # the derivative with respect to an anisotropic material's k is a follow-up; others work
+            refuse_aniso(cfg, "a tangent with respect to the conductivity of an anisotropic material", set(tangents))
+        key = self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an)
         fresh = self.problem is None or key != self._key
-        self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme, kt)
+        self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme, kt, an)
         if not fresh:
             self.problem.set_state(ic_temp)
             self.problem.iters = []
@@ -664,6 +679,7 @@ def run_simulation_impl(kind, cfg, mesh_folder, rebuild_mesh=False, visualize_me
                         two_sided=False, tangents=None):
     with suppress_output(suppress_print):
         program_start = time.time()
+        check_config(cfg)   # k_aniso blocks, and none of them next to a table key, before any mesh or session is made
         stack = stack_with_diamond(cfg) if kind == "with_diamond" else stack_no_diamond(cfg)
         own_session = session is None
         if own_session:
@@ -722,6 +738,8 @@ def run_simulation_batch_impl(kind, cfgs, output_folders, watcher_points_list, s
     points of a sweep group share their geometry and therefore do).  Returns the list of result dicts."""
     with suppress_output(suppress_print):
         t0 = time.time()
+        for c in cfgs:
+            check_config(c)
         stacks = [stack_with_diamond(c) if kind == "with_diamond" else stack_no_diamond(c) for c in cfgs]
         parsed = [_parse_watchers(wp) for wp in watcher_points_list]
         for names_j, coords_j in parsed[1:]:

@@ -20,6 +20,7 @@ import time
 import numpy as np
 
 from .parameter_sweep import build_stack, get_watcher_points, oside_curves
+from .aniso import refuse_aniso
 from .kappa_t import refuse_tables
 
 DEFAULT_EXP_CSV = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "experimental_data",
@@ -80,6 +81,7 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     scheme = time_scheme(cfg)
     refuse_tables(cfg, "heatflow_amd.fit")
     params = tuple(params)
+    refuse_aniso(cfg, "heatflow_amd.fit of the conductivity of an anisotropic material", set(params))
     exp = load_experiment(exp_csv)
     ic = float(cfg["heating"]["ic_temp"])
     stack = build_stack(cfg)

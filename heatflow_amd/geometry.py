@@ -12,6 +12,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass, field
 
+from .aniso import check_config, material_aniso
 from .kappa_t import material_cv_table, material_table
 from .materials import Material
 
@@ -23,7 +24,8 @@ def _f(cfg, mat, key):
 def _material(cfg, name, box):
     """Material with rho_cv = rho*cv and k, as run_with_diamond.py:100-181; a kappa(T) key (k_table / k_power,
     heatflow_amd.kappa_t) adds the tabulated ``k_table`` = (T0, dT, values), a cv(T) key (cv_table / cv_einstein) the tabulated
-    ``rho_cv_table`` = (T0, dT, values of rho * cv)."""
+    ``rho_cv_table`` = (T0, dT, values of rho * cv), a ``k_aniso`` block (heatflow_amd.aniso) the multipliers ``k_aniso`` =
+    (m_r, m_z)."""
     props = {"rho_cv": _f(cfg, name, "rho") * _f(cfg, name, "cv"), "k": _f(cfg, name, "k")}
     table = material_table(name, cfg["mats"][name])
     if table is not None:
@@ -31,6 +33,9 @@ def _material(cfg, name, box):
     cv_table = material_cv_table(name, cfg["mats"][name])
     if cv_table is not None:
         props["rho_cv_table"] = cv_table
+    aniso = material_aniso(name, cfg["mats"][name])
+    if aniso is not None:
+        props["k_aniso"] = aniso
     return Material(name, boundaries=box, properties=props, mesh_size=_f(cfg, name, "mesh"))
 
 
@@ -128,7 +133,9 @@ def stack_no_diamond(cfg) -> Stack:
 
 
 def build_stack(cfg) -> Stack:
-    """Pick the stack by the presence of ``p_diam`` (as parameter_sweep.py:92)."""
+    """Pick the stack by the presence of ``p_diam`` (as parameter_sweep.py:92).  A configuration that combines ``k_aniso`` with
+    a kappa(T) / cv(T) key is refused here (ValueError naming the keys), before any mesh or GPU work."""
+    check_config(cfg)
     return stack_with_diamond(cfg) if "p_diam" in cfg["mats"] else stack_no_diamond(cfg)
 
 

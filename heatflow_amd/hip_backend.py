@@ -36,7 +36,7 @@ EXPORTS = [
     "hf_batch_begin", "hf_batch_load_column", "hf_batch_set_affine", "hf_batch_set_state", "hf_batch_get_state", "hf_batch_run", "hf_batch_run_flux", "hf_batch_end",
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
-    "hf_tangent_setup", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_get_sizes", "hf_get_csr", "hf_spmv",
+    "hf_tangent_setup", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
 
@@ -144,6 +144,7 @@ def load_library():
         "hf_get_picard_change": [vp, pd],
         "hf_set_rhoc_tables": [vp, i32, pi, pd, pd, pi, pd],
         "hf_set_picard": [vp, i32],
+        "hf_set_anisotropy": [vp, i32, pi, pd, pd],
         "hf_get_sizes": [vp, pi, pi, C.POINTER(i64), pi],
         "hf_get_csr": [vp, pi, pi, pd, pd],
         "hf_spmv": [vp, i32, pd, pd],
@@ -467,6 +468,23 @@ class HeatflowHIP:
         nk = _i32([len(v) for v in vals])
         allv = _f64(np.concatenate(vals))
         self._check(self._lib.hf_set_rhoc_tables(self._ctx, len(tags), _pi(tags), _pd(t0), _pd(dT), _pi(nk), _pd(allv)))
+
+    # -- anisotropic conductivities (hf_set_anisotropy) ---------------------------------
+    def set_anisotropy(self, multipliers):
+        """``multipliers`` = {cell tag: (m_r, m_z)}: the tag conducts with k_r = m_r k along r and k_z = m_z k along z; tags
+        not listed are isotropic and an empty dict clears everything.  Call after set_materials.  Invalidates the assembly, a
+        steady set-up and a tangent set-up: assemble() again."""
+        items = sorted((int(t), v) for t, v in (multipliers or {}).items())
+        if not items:
+            self._check(self._lib.hf_set_anisotropy(self._ctx, 0, None, None, None))
+            return
+        for t, v in items:
+            if len(tuple(v)) != 2:
+                raise ValueError(f"set_anisotropy: tag {t} needs a pair (m_r, m_z)")
+        tags = _i32([t for t, _ in items])
+        m_r = _f64([float(v[0]) for _, v in items])
+        m_z = _f64([float(v[1]) for _, v in items])
+        self._check(self._lib.hf_set_anisotropy(self._ctx, len(tags), _pi(tags), _pd(m_z), _pd(m_r)))
 
     def set_picard(self, sweeps):
         """Picard sweeps per step (1..8) while tables of either kind are set (hf_set_picard)."""

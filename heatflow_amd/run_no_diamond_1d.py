@@ -31,6 +31,7 @@ from .bc import P1Space, RowDirichletBC, gather_bc_values, merge_bcs
 from .driver import _parse_watchers, _resolve, suppress_output, write_watcher_csv
 from .heating import HeatingCurve
 from .mesh import load_mesh_arrays
+from .aniso import refuse_aniso
 from .kappa_t import refuse_tables
 
 
@@ -95,6 +96,7 @@ def run_1d(cfg, mesh_folder_2d, mesh_folder_1d=None, rebuild_mesh=False, visuali
     if scheme != "backward_euler":
         raise ValueError(f"run_1d: timing.scheme {scheme!r} is not supported by the 1-D model (backward Euler only)")
     refuse_tables(cfg, "run_1d (the 1-D model)")
+    refuse_aniso(cfg, "run_1d (the 1-D model)")
     with suppress_output(suppress_print):
         t_start = time.time()
         mesh_cfg_path = os.path.join(mesh_folder_2d, "mesh_cfg.yaml")

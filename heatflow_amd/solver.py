@@ -53,12 +53,15 @@ class HeatProblem:
               3.10): every evaluation re-values M as well as A.  With or without kappa_tables; the same order (tables, state,
               assembly).  None / {}: constant capacities.
     picard : Picard sweeps per step with tables (1..8; 1 = the lagged scheme)
+    k_aniso : {cell tag: (m_r, m_z)} - anisotropic conductivities (hf_set_anisotropy): the tag conducts with
+              k_r = m_r k along r and k_z = m_z k along z.  Set right after the materials, before the first assembly.  Not
+              together with kappa_tables / rhoc_tables (ValueError).  None / {}: isotropic, the call sequence of before.
     """
 
     def __init__(self, coords, tris, tags, tag_to_k, tag_to_rho_cv, dt, bcs, u0, *, backend=None, device_id=0,
                  assembly_mode=ASM_ROW_GATHER, rtol=DEFAULT_RTOL, atol=0.0, max_it=DEFAULT_MAX_IT,
                  precond=PC_JACOBI, amg_reuse=False, pattern=None, amg=None, scheme="backward_euler", kappa_tables=None,
-                 picard=1, rhoc_tables=None):
+                 picard=1, rhoc_tables=None, k_aniso=None):
         self.coords = np.ascontiguousarray(coords, dtype=np.float64)
         self.n = self.coords.shape[0]
         self.dt = float(dt)
@@ -70,6 +73,10 @@ class HeatProblem:
         self.kappa_tables = dict(kappa_tables or {})
         self.rhoc_tables = dict(rhoc_tables or {})
         self.picard = int(picard)
+        self.k_aniso = check_k_aniso(k_aniso)
+        if self.k_aniso and (self.kappa_tables or self.rhoc_tables):
+            raise ValueError("HeatProblem: k_aniso together with kappa_tables / rhoc_tables is not supported "
+                             "(the table kernels are isotropic)")
         scheme_code = time_scheme_code(scheme)     # (an unknown name raises before any backend call)
         self.backend = backend if backend is not None else HeatflowHIP(device_id)
         self._own_backend = backend is None
@@ -81,6 +88,8 @@ class HeatProblem:
             self.backend.set_mesh(self.coords, tris, tags, pattern=pattern)
         self.mesh_seconds = time.perf_counter() - t0
         self.set_materials(tag_to_k, tag_to_rho_cv, assemble=False)
+        if self.k_aniso:         # isotropic problems make no extra call
+            self.backend.set_anisotropy(self.k_aniso)
         if self.bcs:
             self.bc_dofs, self._owner, self._pos = merge_bcs(self.bcs)
         else:
@@ -250,6 +259,21 @@ class HeatProblem:
         Dirichlet rows, 0 on them; it becomes the load and is returned.  Needs a solve_steady before (for K)."""
         self.backend.hold_load()
         return self.backend.get_load()
+
+
+def check_k_aniso(k_aniso):
+    """{cell tag: (m_r, m_z)} with int tags and float pairs; ValueError for anything that is not a pair of positive finite
+    numbers (before any backend call)."""
+    out = {}
+    for t, v in dict(k_aniso or {}).items():
+        try:
+            m_r, m_z = (float(x) for x in v)
+        except (TypeError, ValueError):
+            raise ValueError(f"k_aniso: cell tag {t} needs a pair (m_r, m_z), got {v!r}") from None
+        if not (np.isfinite(m_r) and np.isfinite(m_z) and m_r > 0.0 and m_z > 0.0):
+            raise ValueError(f"k_aniso: multipliers of cell tag {t} must be positive and finite, got {(m_r, m_z)!r}")
+        out[int(t)] = (m_r, m_z)
+    return out
 
 
 def _eval_on_dofs(fn, xy, t):

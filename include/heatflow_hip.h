@@ -34,6 +34,8 @@
  *   hf_set_kappa_tables / hf_get_picard_change   no counterpart: the reference's conductivities are constants per material
  *                      (run_with_diamond.py:286-301); these make them functions of the temperature
  *   hf_set_rhoc_tables / hf_set_picard   no counterpart: the same for the heat capacity rho * cv (run_with_diamond.py:286-301)
+ *   hf_set_anisotropy  no counterpart: the reference's conductivities are scalars (run_with_diamond.py:286-301); this makes
+ *                      them diagonal tensors in (z, r)
  *
  * Conventions
  *   - All functions return 0 (HF_OK) or a negative HF_ERR_* code; hf_last_error(ctx)
@@ -131,6 +133,25 @@ int hf_set_materials(hf_ctx* ctx, int32_t n_mat, const int32_t* tags, const doub
  * entries that changed (reference: a new run_simulation per kappa, sweep_test.py:55-75). */
 int hf_update_kappa(hf_ctx* ctx, int32_t n_mat, const int32_t* tags, const double* kappa);
 
+/* Anisotropic conductivities: cells with tag == tags[i] conduct with k_z = m_z[i] * kappa along z and k_r = m_r[i] * kappa along
+ * r (kappa from hf_set_materials / hf_update_kappa, which scale both directions: the ratio stays).  The tensor is diagonal in
+ * (z, r) and constant per element; M does not change.  Unlisted tags are isotropic, a listed tag with both multipliers 1 counts
+ * as isotropic, n = 0 clears.  While no tag is anisotropic the existing kernels run and nothing changes; otherwise the row-gather
+ * kernel k_assemble_rows_an assembles M, A (hf_assemble, hf_update_kappa), the stiffness of hf_steady_setup (hence hf_hold_load)
+ * and the A1 of hf_batch_set_affine; everything above the assembly reads M and A only and works unchanged.
+ * Call after hf_set_materials (it stays over later hf_set_materials calls; hf_set_mesh clears it).  A call that changes anything
+ * invalidates the assembly, a steady set-up and a tangent set-up, and closes an open batch: hf_assemble (hf_steady_setup,
+ * hf_tangent_setup) again.  The multipliers belong to the multigrid fingerprint: a hierarchy kept under hf_set_precond(1, reuse = 1)
+ * or installed by hf_amg_install meets an operator with other multipliers as a frozen one.
+ * Errors: HF_ERR_STATE before hf_set_materials, and, for a call that leaves a tag anisotropic, while kappa(T) / rho_c(T) tables
+ * are set (the table kernels are isotropic);
+ * HF_ERR_ARG for a tag that is not a cell tag of the mesh, a tag listed twice, a multiplier that is not finite and positive, and
+ * on a mesh without row-gather lists or after hf_assemble in another mode.  While a tag is anisotropic: hf_assemble in a mode
+ * other than HF_ASM_ROW_GATHER -> HF_ERR_ARG; hf_set_kappa_tables, hf_set_rhoc_tables and hf_steady_picard_setup -> HF_ERR_STATE;
+ * hf_tangent_setup with a column on an anisotropic tag -> HF_ERR_ARG (columns on isotropic tags work: their load is the unit
+ * stiffness of those tags and the operator is the primal's).  Tangents with respect to m_z, m_r are not provided. */
+int hf_set_anisotropy(hf_ctx* ctx, int32_t n, const int32_t* tags, const double* m_z, const double* m_r);
+
 /* Dirichlet DOFs (unique; the host resolves overlaps "later BC wins" beforehand).
  * The order defines the order of g_bc in hf_step.  n_bc = 0 removes all BCs. */
 int hf_set_dirichlet(hf_ctx* ctx, int32_t n_bc, const int32_t* dofs);
@@ -178,7 +199,7 @@ int hf_get_amg_info(hf_ctx* ctx, int32_t* n_levels, int32_t* level_rows, int32_t
  * preconditioner; blob = host or device memory of hf_amg_export_size bytes.  hf_amg_install needs hf_set_mesh,
  * hf_set_dirichlet and hf_set_precond(1, reuse = 1) on the same mesh and is followed by hf_assemble, which keeps the
  * installed hierarchy instead of building one and compares its own operator with the fingerprint in the blob (time step,
- * coefficient tables, Dirichlet set): the same operator -> the cycle is the one the exporting context runs, bit for bit;
+ * coefficient tables, hf_set_anisotropy's multipliers, Dirichlet set): the same operator -> the cycle is the one the exporting context runs, bit for bit;
  * another point of a sweep -> the hierarchy is a frozen one (see hf_set_precond).  Every index in the blob is
  * verified; HF_ERR_ARG if it does not belong to this mesh. */
 int hf_amg_export_size(hf_ctx* ctx, int64_t* bytes);
