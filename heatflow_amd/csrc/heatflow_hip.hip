@@ -163,9 +163,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   ctx->n_cdict = static_cast<int64_t>(T.spmv.dict.size());
   HF_HIP(copy_sync(ctx, ctx->d_zr, zr, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
   ctx->rg_ok = T.rg.ok && rowgather_smem_bytes(T.max_blk_nnz, T.rg.cols.max_dict) <= 160 * 1024;
-  ctx->rg_grid = 0;
-  ctx->rg_grid_k = 0;
-  ctx->rg_grid_p = 0;
+  std::fill_n(ctx->rg_grid, static_cast<int>(RG_VARIANTS), 0);
   if (ctx->rg_ok) {
     const RowGather& G = T.rg;
     ctx->rg_max_dict = G.cols.max_dict;

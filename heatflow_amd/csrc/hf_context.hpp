@@ -100,6 +100,10 @@ constexpr int KT_MAX_KNOTS = 256;
 constexpr int KT_MAX_PICARD = 8;
 struct KTab { double t0, inv_dt; int n, off; };
 
+// The row-gather assembly kernels: k_assemble_rows<false / true>, k_assemble_rows_an<false / true>, k_assemble_rows_kT,
+// k_assemble_rows_cT, k_assemble_rows_kT_K
+enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_VARIANTS };
+
 }  // namespace
 
 struct hf_ctx {
@@ -151,8 +155,8 @@ struct hf_ctx {
   uint16_t *d_rg_ell = nullptr, *d_rg_cid = nullptr;
   int32_t* d_rg_dict = nullptr;     // the blocks' column lists (global node ids)
   double2* d_rg_zrb = nullptr;      // coordinates of every block's column list (own rows + halo)
-  int rg_max_dict = 0, rg_grid = 0, rg_grid_k = 0;   // (rg_grid_k: grid of the stiffness-only variant)
-  int rg_grid_p = 0;                                 // grid of the stiffness-only table re-valuation (k_assemble_rows_kT_K)
+  int rg_max_dict = 0;
+  int rg_grid[RG_VARIANTS] = {};    // persistent grid of each row-gather kernel on this mesh (0: not yet queried; launch_rowgather)
   int64_t n_rg_ell = 0, n_rg_dict = 0, n_cdict = 0;
   std::vector<int32_t> h_rg_tags;
   double *d_kappa_rg = nullptr, *d_rhoc_rg = nullptr;
@@ -163,7 +167,6 @@ struct hf_ctx {
     double2* d_m = nullptr;
     std::vector<char> h_tag;
     uint64_t hash = 0;          // of the multipliers by cell tag (0 while off): part of the operator's fingerprint (OperatorPrint)
-    int grid = 0, grid_k = 0;   // persistent grids of k_assemble_rows_an<false> / <true>
   } an;
   // device: matrices
   double *d_M = nullptr, *d_A = nullptr, *d_dinv = nullptr;
@@ -342,11 +345,9 @@ struct hf_ctx {
     double* cvals = nullptr;
     std::vector<char> ctabled;    // by cell tag: the tag carries a capacity table
     double* w = nullptr;          // capacity tables, sweeps > 1: the vector the re-valued M multiplies (u^n, or BDF2's operand)
-    int cgrid = 0;
     double *pic = nullptr, *b0 = nullptr;   // evaluation state of the last sweep (for the change), b before lifting (sweeps > 1)
     unsigned long long* change = nullptr;   // max |u^{n+1,p} - u^{n+1,p-1}| of the last step's last sweep (bits of a double >= 0)
     bool have_change = false;
-    int grid = 0;
   } kt;
   // optional in-situ kernel timing (hf_set_profile): event pairs around each PCG SpMV launch
   bool prof = false;

@@ -1,5 +1,7 @@
 // Part of libheatflow_hip.so (see heatflow_hip.hip): device code - element assembly, CSR SpMV (LDS-staged and sub-wave), PCG and multigrid kernels
 #pragma once
+#include <type_traits>
+
 #include "hf_context.hpp"
 
 namespace {
@@ -214,17 +216,8 @@ __global__ __launch_bounds__(RBA) void k_assemble_lds(int n, int cap, const int3
 }
 
 // ------------------------------------------------------------------------------------------
-// Assembly, row gather (HF_ASM_ROW_GATHER): lane t of a workgroup owns CSR row r0 + t and visits the
-// triangles at its node one after another (ELL slab of 16-bit entries, hf_pattern.hpp RowGather).  A
-// triangle is described by the positions of its two other vertices inside the row's column list, so a
-// contribution's slot is known without any search or offset table, and the element array is never read.
-// Per block of RBA rows the kernel stages, all as coalesced 16-byte streams: the rows' 16-bit column
-// positions, the coordinates of the block's column list (own rows + halo, a per-block copy made at
-// hf_set_mesh) and its ELL entries; the (M, A) value slab lives in LDS and is streamed out once.  The
-// visit loop touches LDS only.  Rows are private to their lane: no atomics, no colours, no barriers
-// inside the loop, and the order of additions is the list order - bitwise reproducible.
-// Workgroups are persistent: while block b is computed the loads of the workgroup's next block are in
-// flight into registers and the stores of its previous block drain, so the three phases overlap.
+// Assembly, row gather (HF_ASM_ROW_GATHER): the element routines, then one body (rowgather_assemble) behind the five kernels
+// k_assemble_rows, k_assemble_rows_an, k_assemble_rows_kT, k_assemble_rows_cT and k_assemble_rows_kT_K.
 // Every triangle is evaluated once per vertex ("me", next, previous in the triangle's own cyclic
 // order).  The formulas are symmetric by construction, so the three evaluations agree bit for bit
 // where they must (A_ij == A_ji) without agreeing on a vertex order:
@@ -237,56 +230,103 @@ __global__ __launch_bounds__(RBA) void k_assemble_lds(int n, int cap, const int3
 // ------------------------------------------------------------------------------------------
 struct ElemRow { double m0, m1, m2, k0, k1, k2; };   // row "me" of the element matrices: (me,me) (me,next) (me,prev)
 
-__device__ __forceinline__ ElemRow element_row(const double2 Pi, const double2 Pj, const double2 Pk, double rho_c, double kappa) {
+// (lo + mid) + hi of three values sorted by value: the same bits in whichever order they are given (rsum, and 3 T_e of the tables)
+__device__ __forceinline__ double sorted_sum3(double a, double b, double c) {
+#pragma clang fp contract(off)
+  const double ab_lo = fmin(a, b), ab_hi = fmax(a, b);
+  const double lo = fmin(ab_lo, c), hi = fmax(ab_hi, c), mid = fmax(ab_lo, fmin(ab_hi, c));
+  return (lo + mid) + hi;
+}
+
+// Anisotropic element stiffness (hf_set_anisotropy): the tensor diag(k_z, k_r) in (z, r), constant per element.  The gradient of
+// a hat function is perpendicular to the opposite edge, so the z-differences of the edges carry k_r and the r-differences k_z:
+//   K_ab = ks * (k_r * (e_a.x * e_b.x) + k_z * (e_a.y * e_b.y)),  ks = area * (rsum / 3) / d^2
+// Everything else - edges, d, rsum, M - is the isotropic row's, and the products commute, so the three per-vertex evaluations of
+// a triangle still agree bit for bit (A stays exactly symmetric).
+// ANISO = false: K_ab = ks * (e_a . e_b), ks = k_z * area * (rsum / 3) / d^2 (k_z holds kappa, k_r is not used).
+// One routine with both formulas statement for statement, not a geometry helper under two callers: the helper (tried with a
+// functor for the stiffness form) made the compiler commute k_assemble_rows_an's v_add_f64 operands.  The bits stay either way,
+// the machine code does not; keep the order of the statements.
+template <bool ANISO>
+__device__ __forceinline__ ElemRow element_row_of(const double2 Pi, const double2 Pj, const double2 Pk, double rho_c, double k_z, double k_r) {
 #pragma clang fp contract(off)
   const double eix = Pk.x - Pj.x, eiy = Pk.y - Pj.y;     // edge opposite "me"
   const double ejx = Pi.x - Pk.x, ejy = Pi.y - Pk.y;     // opposite next
   const double ekx = Pj.x - Pi.x, eky = Pj.y - Pi.y;     // opposite previous
   const double c1 = fabs(ejx * eky - ejy * ekx), c2 = fabs(ekx * eiy - eky * eix), c3 = fabs(eix * ejy - eiy * ejx);
   const double d = fmax(fmax(c1, c2), c3);
-  const double ab_lo = fmin(Pi.y, Pj.y), ab_hi = fmax(Pi.y, Pj.y);
-  const double lo = fmin(ab_lo, Pk.y), hi = fmax(ab_hi, Pk.y), mid = fmax(ab_lo, fmin(ab_hi, Pk.y));
-  const double rsum = (lo + mid) + hi;
+  const double rsum = sorted_sum3(Pi.y, Pj.y, Pk.y);
   const double area = 0.5 * d;
-  const double ks = kappa * area * (rsum * (1.0 / 3.0)) * (1.0 / (d * d));
+  const double ks = ANISO ? area * (rsum * (1.0 / 3.0)) * (1.0 / (d * d)) : k_z * area * (rsum * (1.0 / 3.0)) * (1.0 / (d * d));
   const double ms30 = rho_c * area * (1.0 / 30.0), ms60 = rho_c * area * (1.0 / 60.0);
   ElemRow o;
-  o.k0 = ks * (eix * eix + eiy * eiy);
-  o.k1 = ks * (eix * ejx + eiy * ejy);
-  o.k2 = ks * (eix * ekx + eiy * eky);
+  o.k0 = ks * (ANISO ? k_r * (eix * eix) + k_z * (eiy * eiy) : eix * eix + eiy * eiy);
+  o.k1 = ks * (ANISO ? k_r * (eix * ejx) + k_z * (eiy * ejy) : eix * ejx + eiy * ejy);
+  o.k2 = ks * (ANISO ? k_r * (eix * ekx) + k_z * (eiy * eky) : eix * ekx + eiy * eky);
   o.m0 = ms30 * (2.0 * Pi.y + rsum);
   o.m1 = ms60 * (rsum + (Pi.y + Pj.y));
   o.m2 = ms60 * (rsum + (Pi.y + Pk.y));
   return o;
 }
 
+__device__ __forceinline__ ElemRow element_row(const double2 Pi, const double2 Pj, const double2 Pk, double rho_c, double kappa) {
+  return element_row_of<false>(Pi, Pj, Pk, rho_c, kappa, 0.0);
+}
+
+__device__ __forceinline__ ElemRow element_row_an(const double2 Pi, const double2 Pj, const double2 Pk, double rho_c, double k_z, double k_r) {
+  return element_row_of<true>(Pi, Pj, Pk, rho_c, k_z, k_r);
+}
+
 constexpr int RG_NC = 4;   // 16-byte vectors of column positions a lane can prefetch (RBA * 8 * RG_NC >= slab slots: rows hold <= 32 entries)
 constexpr int RG_NX = 5;   // coordinate pairs a lane can prefetch (RBA * RG_NX >= column-list length, checked on the host)
 
-// KONLY: the stiffness alone (the steady operator, hf_steady_setup): Av receives K, the slab's M half stays zero, Mv is not
-// written (may be null); rhoc_idx and dt are not used.
-template <bool KONLY>
-__global__ __launch_bounds__(RBA) void k_assemble_rows(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
-                                                       const int32_t* __restrict__ rowptr,
-                                                       const int4* __restrict__ hdr /* 2 per block */,
-                                                       const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
-                                                       const double2* __restrict__ zrb,
-                                                       const double* __restrict__ kappa_idx, const double* __restrict__ rhoc_idx,
-                                                       double dt, double* __restrict__ Mv, double* __restrict__ Av) {
-  extern __shared__ double smem[];
-  double2* sMA = reinterpret_cast<double2*>(smem);                   // (M, A) per slot
-  double2* sXd = sMA + cap;                                          // coordinates of the block's column list
-  int* sR = reinterpret_cast<int*>(sXd + capd);                      // row starts inside the slab
+// The body of the row-gather kernels.  Lane t of a workgroup owns CSR row r0 + t and visits the
+// triangles at its node one after another (ELL slab of 16-bit entries, hf_pattern.hpp RowGather).  A
+// triangle is described by the positions of its two other vertices inside the row's column list, so a
+// contribution's slot is known without any search or offset table, and the element array is never read.
+// Per block of RBA rows the kernel stages, all as coalesced 16-byte streams: the rows' 16-bit column
+// positions, the coordinates of the block's column list (own rows + halo, a per-block copy made at
+// hf_set_mesh) and its ELL entries; the value slab lives in LDS and is streamed out once.  The
+// visit loop touches LDS only.  Rows are private to their lane: no atomics, no colours, no barriers
+// inside the loop, and the order of additions is the list order - bitwise reproducible.
+// Workgroups are persistent: while block b is computed the loads of the workgroup's next block are in
+// flight into registers and the stores of its previous block drain, so the three phases overlap.
+// What a kernel adds is its coefficient policy V:
+//   V::PAIR    the slab holds (M, A) as a double2 per slot, else one double
+//   V::STATE   the block's slice of an evaluation state is staged next to the coordinates (sU; dict: the column lists' node ids)
+//   V::KONLY   the stiffness alone: no M half, no dt
+//   V::NODE_FIRST  (STATE only) the prefetch reads the node id in a guarded load of its own before the state, as the kernels
+//              with a two-array state were written, or inside the state's guard.  The same values either way, but the compiler
+//              schedules the two spellings differently, and each kernel keeps the machine code it had
+//              (profiles/rowgather_unify_asm_compare.txt)
+//   V::ID      its RgVariant: the host's index of the kernel's cached grid
+//   v.state(node)                              the evaluation state at a node (STATE only)
+//   v.row(tg, Pi, Pj, Pk, sU, ui, cj, ck)      the ElemRow of a visit: tg the tag-dictionary index, cj / ck the other two
+//                                              vertices' positions in the column list, ui = sU[my own position]
+//   v.dt                                       of A = M + dt K (not KONLY)
+// Out: PAIR - Mv (not KONLY) and Av; one value - Av alone.
+template <class V>
+__device__ __forceinline__ void rowgather_assemble(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
+                                                   const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr /* 2 per block */,
+                                                   const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
+                                                   const double2* __restrict__ zrb, const int32_t* __restrict__ dict, const V v,
+                                                   double* __restrict__ Mv, double* __restrict__ Av, double* smem) {
+  using Slot = std::conditional_t<V::PAIR, double2, double>;
+  Slot* sS = reinterpret_cast<Slot*>(smem);                          // (M, A), A or K per slot
+  double2* sXd = reinterpret_cast<double2*>(sS + cap);               // coordinates of the block's column list
+  double* sU = reinterpret_cast<double*>(sXd + capd);                // STATE: the evaluation state on the block's column list
+  int* sR = reinterpret_cast<int*>(V::STATE ? sU + capd + (capd & 1) : sU);   // row starts inside the slab
   uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);               // column-list position per slot, from the 8-aligned start
   const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
 
   const int t = threadIdx.x;
-  for (int k = t; k < cap; k += RBA) sMA[k] = make_double2(0.0, 0.0);
+  for (int k = t; k < cap; k += RBA) sS[k] = Slot();
 
   // prefetch registers of the next block
   int4 hA, hB;
   uint4 pe, pc[RG_NC];
   double2 px[RG_NX];
+  double pu[V::STATE ? RG_NX : 1];
   int pr = 0;
   auto prefetch = [&](int blk) {
     hA = hdr[2 * blk];                                               // (k0, nk, d0, nd)
@@ -294,9 +334,20 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows(int nblk, int cap /* slab
     pe = ell[hB.x + t];
     const int c0 = hA.x >> 3, nc = ((hA.x + hA.y + 7) >> 3) - c0;
 #pragma unroll
-    for (int u = 0; u < RG_NC; ++u) pc[u] = (t + u * RBA < nc) ? cid16[c0 + t + u * RBA] : make_uint4(0, 0, 0, 0);
+    for (int q = 0; q < RG_NC; ++q) pc[q] = (t + q * RBA < nc) ? cid16[c0 + t + q * RBA] : make_uint4(0, 0, 0, 0);
 #pragma unroll
-    for (int u = 0; u < RG_NX; ++u) px[u] = (t + u * RBA < hA.w) ? zrb[hA.z + t + u * RBA] : make_double2(0.0, 0.0);
+    for (int q = 0; q < RG_NX; ++q) {
+      const bool in = t + q * RBA < hA.w;
+      px[q] = in ? zrb[hA.z + t + q * RBA] : make_double2(0.0, 0.0);
+      if constexpr (V::STATE) {
+        if constexpr (V::NODE_FIRST) {
+          const int node = in ? dict[hA.z + t + q * RBA] : 0;
+          pu[q] = in ? v.state(node) : 0.0;
+        } else {
+          pu[q] = in ? v.state(dict[hA.z + t + q * RBA]) : 0.0;
+        }
+      }
+    }
     pr = (t < hB.w) ? rowptr[blk * RBA + t] - hA.x : 0;
   };
   int blk = blockIdx.x;
@@ -307,9 +358,13 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows(int nblk, int cap /* slab
     const uint4 ce = pe;
     const int nc = ((cA.x + cA.y + 7) >> 3) - (cA.x >> 3);
 #pragma unroll
-    for (int u = 0; u < RG_NC; ++u) if (t + u * RBA < nc) sC4[t + u * RBA] = pc[u];
+    for (int q = 0; q < RG_NC; ++q) if (t + q * RBA < nc) sC4[t + q * RBA] = pc[q];
 #pragma unroll
-    for (int u = 0; u < RG_NX; ++u) if (t + u * RBA < cA.w) sXd[t + u * RBA] = px[u];
+    for (int q = 0; q < RG_NX; ++q)
+      if (t + q * RBA < cA.w) {
+        sXd[t + q * RBA] = px[q];
+        if constexpr (V::STATE) sU[t + q * RBA] = pu[q];
+      }
     sR[t] = pr;
     __syncthreads();
     const int nxt = blk + gridDim.x;
@@ -320,6 +375,8 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows(int nblk, int cap /* slab
       const int sbase = base + (cA.x & 7);                           // the position array starts at the 8-aligned slot
       const int ci = cB.z + t;                                       // my own position in the column list
       const double2 Pi = sXd[ci];
+      double ui = 0.0;
+      if constexpr (V::STATE) ui = sU[ci];
       double dM = 0.0, dA = 0.0;
       int pd = 0;                                                    // diagonal: the slot whose column is my own row
       while (pd < 31 && sC[sbase + pd] < ci) ++pd;
@@ -327,80 +384,104 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows(int nblk, int cap /* slab
         const uint4 ev = g == 0 ? ce : ell[cB.x + g * RBA + t];
         const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const unsigned e = (w[u >> 1] >> ((u & 1) * 16)) & 0xFFFFu;
+        for (int q = 0; q < 8; ++q) {
+          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
           if (e == 0xFFFFu) continue;
           const int pj = e & 31u, pk = (e >> 5) & 31u, tg = e >> 10;
-          const double2 Pj = sXd[sC[sbase + pj]], Pk = sXd[sC[sbase + pk]];
-          if (KONLY) {
-            const ElemRow r = element_row(Pi, Pj, Pk, 0.0, kappa_idx[tg]);
+          const int cj = sC[sbase + pj], ck = sC[sbase + pk];
+          const double2 Pj = sXd[cj], Pk = sXd[ck];
+          const ElemRow r = v.row(tg, Pi, Pj, Pk, sU, ui, cj, ck);
+          if constexpr (V::PAIR && V::KONLY) {
             dA += r.k0;
-            sMA[base + pj].y += r.k1;
-            sMA[base + pk].y += r.k2;
-            continue;
+            sS[base + pj].y += r.k1;
+            sS[base + pk].y += r.k2;
+          } else if constexpr (V::PAIR) {
+            dM += r.m0;
+            dA += fma(v.dt, r.k0, r.m0);
+            double2 s = sS[base + pj];
+            s.x += r.m1;
+            s.y += fma(v.dt, r.k1, r.m1);
+            sS[base + pj] = s;
+            s = sS[base + pk];
+            s.x += r.m2;
+            s.y += fma(v.dt, r.k2, r.m2);
+            sS[base + pk] = s;
+          } else if constexpr (V::KONLY) {
+            dA += r.k0;
+            sS[base + pj] += r.k1;
+            sS[base + pk] += r.k2;
+          } else {
+            dA += fma(v.dt, r.k0, r.m0);
+            sS[base + pj] += fma(v.dt, r.k1, r.m1);
+            sS[base + pk] += fma(v.dt, r.k2, r.m2);
           }
-          const ElemRow r = element_row(Pi, Pj, Pk, rhoc_idx[tg], kappa_idx[tg]);
-          dM += r.m0;
-          dA += fma(dt, r.k0, r.m0);
-          double2 v = sMA[base + pj];
-          v.x += r.m1;
-          v.y += fma(dt, r.k1, r.m1);
-          sMA[base + pj] = v;
-          v = sMA[base + pk];
-          v.x += r.m2;
-          v.y += fma(dt, r.k2, r.m2);
-          sMA[base + pk] = v;
         }
       }
-      sMA[base + pd] = make_double2(dM, dA);
+      if constexpr (V::PAIR) sS[base + pd] = make_double2(dM, dA);
+      else sS[base + pd] = dA;
     }
     __syncthreads();
     // stream the slab out and leave it zeroed for the next block (slot k stays with the lane that reads it here)
     for (int k = t; k < cA.y; k += RBA) {
-      const double2 v = sMA[k];
-      if (!KONLY) Mv[cA.x + k] = v.x;
-      Av[cA.x + k] = v.y;
-      sMA[k] = make_double2(0.0, 0.0);
+      const Slot s = sS[k];
+      if constexpr (V::PAIR) {
+        if (!V::KONLY) Mv[cA.x + k] = s.x;
+        Av[cA.x + k] = s.y;
+      } else {
+        Av[cA.x + k] = s;
+      }
+      sS[k] = Slot();
     }
     blk = nxt;
-    // no barrier needed here: the staging stores above touch sC / sXd / sR only after every lane has passed the
+    // no barrier needed here: the staging stores above touch sC / sXd / sU / sR only after every lane has passed the
     // barrier that ended the visit loop, and the slab is re-read only behind the next staging barrier
   }
 }
 
-// Anisotropic element stiffness (hf_set_anisotropy): the tensor diag(k_z, k_r) in (z, r), constant per element.  The gradient of
-// a hat function is perpendicular to the opposite edge, so the z-differences of the edges carry k_r and the r-differences k_z:
-//   K_ab = ks * (k_r * (e_a.x * e_b.x) + k_z * (e_a.y * e_b.y)),  ks = area * (rsum / 3) / d^2
-// Everything else - edges, d, rsum, M - is element_row's, and the products commute, so the three per-vertex evaluations of a
-// triangle still agree bit for bit (A stays exactly symmetric).
-__device__ __forceinline__ ElemRow element_row_an(const double2 Pi, const double2 Pj, const double2 Pk, double rho_c, double k_z, double k_r) {
-#pragma clang fp contract(off)
-  const double eix = Pk.x - Pj.x, eiy = Pk.y - Pj.y;     // edge opposite "me"
-  const double ejx = Pi.x - Pk.x, ejy = Pi.y - Pk.y;     // opposite next
-  const double ekx = Pj.x - Pi.x, eky = Pj.y - Pi.y;     // opposite previous
-  const double c1 = fabs(ejx * eky - ejy * ekx), c2 = fabs(ekx * eiy - eky * eix), c3 = fabs(eix * ejy - eiy * ejx);
-  const double d = fmax(fmax(c1, c2), c3);
-  const double ab_lo = fmin(Pi.y, Pj.y), ab_hi = fmax(Pi.y, Pj.y);
-  const double lo = fmin(ab_lo, Pk.y), hi = fmax(ab_hi, Pk.y), mid = fmax(ab_lo, fmin(ab_hi, Pk.y));
-  const double rsum = (lo + mid) + hi;
-  const double area = 0.5 * d;
-  const double ks = area * (rsum * (1.0 / 3.0)) * (1.0 / (d * d));
-  const double ms30 = rho_c * area * (1.0 / 30.0), ms60 = rho_c * area * (1.0 / 60.0);
-  ElemRow o;
-  o.k0 = ks * (k_r * (eix * eix) + k_z * (eiy * eiy));
-  o.k1 = ks * (k_r * (eix * ejx) + k_z * (eiy * ejy));
-  o.k2 = ks * (k_r * (eix * ekx) + k_z * (eiy * eky));
-  o.m0 = ms30 * (2.0 * Pi.y + rsum);
-  o.m1 = ms60 * (rsum + (Pi.y + Pj.y));
-  o.m2 = ms60 * (rsum + (Pi.y + Pk.y));
-  return o;
+// Constant coefficients by tag-dictionary index.  KONLY (the steady operator, hf_steady_setup): Av receives K, the slab's M
+// half stays zero, Mv is not written (may be null); rhoc_idx and dt are not used.
+template <bool K>
+struct RowsConst {
+  static constexpr bool PAIR = true, STATE = false, KONLY = K;
+  static constexpr RgVariant ID = K ? RG_ROWS_K : RG_ROWS;
+  const double *kappa_idx, *rhoc_idx;
+  double dt;
+  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double*, double, int, int) const {
+    if (KONLY) return element_row(Pi, Pj, Pk, 0.0, kappa_idx[tg]);
+    return element_row(Pi, Pj, Pk, rhoc_idx[tg], kappa_idx[tg]);
+  }
+};
+
+template <bool KONLY>
+__global__ __launch_bounds__(RBA) void k_assemble_rows(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
+                                                       const int32_t* __restrict__ rowptr,
+                                                       const int4* __restrict__ hdr /* 2 per block */,
+                                                       const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
+                                                       const double2* __restrict__ zrb,
+                                                       const double* __restrict__ kappa_idx, const double* __restrict__ rhoc_idx,
+                                                       double dt, double* __restrict__ Mv, double* __restrict__ Av) {
+  extern __shared__ double smem[];
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, nullptr, RowsConst<KONLY>{kappa_idx, rhoc_idx, dt}, Mv, Av, smem);
 }
 
-// k_assemble_rows with a second 64-entry table by tag-dictionary index, an_idx[tg] = (m_z, m_r): the conductivity of tag tg is
-// k_z = m_z kappa along z and k_r = m_r kappa along r.  Lists, staging, persistent workgroups, the LDS slab (same footprint) and
-// the list-order summation are k_assemble_rows'.  An element whose tag has m_z == m_r goes through element_row with kappa * m, so
-// with every multiplier 1 (x * 1.0 is exact) M and A come out bit for bit as k_assemble_rows gives them, and in a mixed mesh
-// every row that touches only such elements keeps its bits.
+// RowsConst with a second 64-entry table by tag-dictionary index, an_idx[tg] = (m_z, m_r): the conductivity of tag tg is
+// k_z = m_z kappa along z and k_r = m_r kappa along r.  An element whose tag has m_z == m_r goes through element_row with
+// kappa * m, so with every multiplier 1 (x * 1.0 is exact) M and A come out bit for bit as k_assemble_rows gives them, and in a
+// mixed mesh every row that touches only such elements keeps its bits.
+template <bool K>
+struct RowsAniso {
+  static constexpr bool PAIR = true, STATE = false, KONLY = K;
+  static constexpr RgVariant ID = K ? RG_AN_K : RG_AN;
+  const double *kappa_idx, *rhoc_idx;
+  const double2* an_idx;
+  double dt;
+  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double*, double, int, int) const {
+    const double2 m = an_idx[tg];
+    const double kap = kappa_idx[tg], rc = KONLY ? 0.0 : rhoc_idx[tg];
+    return m.x == m.y ? element_row(Pi, Pj, Pk, rc, kap * m.x) : element_row_an(Pi, Pj, Pk, rc, m.x * kap, m.y * kap);
+  }
+};
+
 template <bool KONLY>
 __global__ __launch_bounds__(RBA) void k_assemble_rows_an(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
                                                           const int32_t* __restrict__ rowptr,
@@ -411,98 +492,7 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_an(int nblk, int cap /* s
                                                           const double2* __restrict__ an_idx /* (m_z, m_r) */,
                                                           double dt, double* __restrict__ Mv, double* __restrict__ Av) {
   extern __shared__ double smem[];
-  double2* sMA = reinterpret_cast<double2*>(smem);                   // (M, A) per slot
-  double2* sXd = sMA + cap;                                          // coordinates of the block's column list
-  int* sR = reinterpret_cast<int*>(sXd + capd);                      // row starts inside the slab
-  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);               // column-list position per slot, from the 8-aligned start
-  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
-
-  const int t = threadIdx.x;
-  for (int k = t; k < cap; k += RBA) sMA[k] = make_double2(0.0, 0.0);
-
-  // prefetch registers of the next block
-  int4 hA, hB;
-  uint4 pe, pc[RG_NC];
-  double2 px[RG_NX];
-  int pr = 0;
-  auto prefetch = [&](int blk) {
-    hA = hdr[2 * blk];                                               // (k0, nk, d0, nd)
-    hB = hdr[2 * blk + 1];                                           // (ell offset in 16-byte units, groups of 8 visits, local id of row r0, rows)
-    pe = ell[hB.x + t];
-    const int c0 = hA.x >> 3, nc = ((hA.x + hA.y + 7) >> 3) - c0;
-#pragma unroll
-    for (int u = 0; u < RG_NC; ++u) pc[u] = (t + u * RBA < nc) ? cid16[c0 + t + u * RBA] : make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int u = 0; u < RG_NX; ++u) px[u] = (t + u * RBA < hA.w) ? zrb[hA.z + t + u * RBA] : make_double2(0.0, 0.0);
-    pr = (t < hB.w) ? rowptr[blk * RBA + t] - hA.x : 0;
-  };
-  int blk = blockIdx.x;
-  if (blk < nblk) prefetch(blk);
-  while (blk < nblk) {
-    // stage the prefetched block
-    const int4 cA = hA, cB = hB;
-    const uint4 ce = pe;
-    const int nc = ((cA.x + cA.y + 7) >> 3) - (cA.x >> 3);
-#pragma unroll
-    for (int u = 0; u < RG_NC; ++u) if (t + u * RBA < nc) sC4[t + u * RBA] = pc[u];
-#pragma unroll
-    for (int u = 0; u < RG_NX; ++u) if (t + u * RBA < cA.w) sXd[t + u * RBA] = px[u];
-    sR[t] = pr;
-    __syncthreads();
-    const int nxt = blk + gridDim.x;
-    if (nxt < nblk) prefetch(nxt);                                   // in flight during the visit loop
-
-    if (t < cB.w) {
-      const int base = sR[t];
-      const int sbase = base + (cA.x & 7);                           // the position array starts at the 8-aligned slot
-      const int ci = cB.z + t;                                       // my own position in the column list
-      const double2 Pi = sXd[ci];
-      double dM = 0.0, dA = 0.0;
-      int pd = 0;                                                    // diagonal: the slot whose column is my own row
-      while (pd < 31 && sC[sbase + pd] < ci) ++pd;
-      for (int g = 0; g < cB.y; ++g) {
-        const uint4 ev = g == 0 ? ce : ell[cB.x + g * RBA + t];
-        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const unsigned e = (w[u >> 1] >> ((u & 1) * 16)) & 0xFFFFu;
-          if (e == 0xFFFFu) continue;
-          const int pj = e & 31u, pk = (e >> 5) & 31u, tg = e >> 10;
-          const double2 Pj = sXd[sC[sbase + pj]], Pk = sXd[sC[sbase + pk]];
-          const double2 m = an_idx[tg];
-          const double kap = kappa_idx[tg], rc = KONLY ? 0.0 : rhoc_idx[tg];
-          const ElemRow r = m.x == m.y ? element_row(Pi, Pj, Pk, rc, kap * m.x) : element_row_an(Pi, Pj, Pk, rc, m.x * kap, m.y * kap);
-          if (KONLY) {
-            dA += r.k0;
-            sMA[base + pj].y += r.k1;
-            sMA[base + pk].y += r.k2;
-            continue;
-          }
-          dM += r.m0;
-          dA += fma(dt, r.k0, r.m0);
-          double2 v = sMA[base + pj];
-          v.x += r.m1;
-          v.y += fma(dt, r.k1, r.m1);
-          sMA[base + pj] = v;
-          v = sMA[base + pk];
-          v.x += r.m2;
-          v.y += fma(dt, r.k2, r.m2);
-          sMA[base + pk] = v;
-        }
-      }
-      sMA[base + pd] = make_double2(dM, dA);
-    }
-    __syncthreads();
-    // stream the slab out and leave it zeroed for the next block (slot k stays with the lane that reads it here)
-    for (int k = t; k < cA.y; k += RBA) {
-      const double2 v = sMA[k];
-      if (!KONLY) Mv[cA.x + k] = v.x;
-      Av[cA.x + k] = v.y;
-      sMA[k] = make_double2(0.0, 0.0);
-    }
-    blk = nxt;
-    // (no barrier needed here, for the reasons given in k_assemble_rows)
-  }
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, nullptr, RowsAniso<KONLY>{kappa_idx, rhoc_idx, an_idx, dt}, Mv, Av, smem);
 }
 
 // Read-flux projection right-hand sides by row gather (same lists and staging as k_assemble_rows, plus the block's
@@ -632,12 +622,42 @@ __device__ __forceinline__ double ktab_eval(const KTab h, const double* __restri
   return a + (s - static_cast<double>(i)) * (b - a);
 }
 
-// Re-valuation of A = M + dt K(kappa(T)) at an evaluation state u* (hf_set_kappa_tables): the lists, staging, persistent
-// workgroups and summation order of k_assemble_rows<false>, plus the block's slice of u* staged next to the coordinates (as
-// k_grad_rows stages u).  u* = u, or 2 u - uprev when uprev is given (BDF2's extrapolated state).  Per triangle
-// T_e = ((lo + mid) + hi) / 3 of its three sorted nodal values - the same bits from each vertex's point of view, so A stays
-// exactly symmetric - and kappa_e = table(T_e) for a tabled tag, the constant kappa_idx otherwise.  M does not change: only
-// A is written, and a constant table gives A bit for bit as k_assemble_rows does.
+// The table policies (hf_set_kappa_tables, hf_set_rhoc_tables, hf_steady_picard_setup) stage the block's slice of an evaluation
+// state u* next to the coordinates, as k_grad_rows stages u.  Per triangle T_e = ((lo + mid) + hi) / 3 of its three sorted nodal
+// values - the same bits from each vertex's point of view, so the operators stay exactly symmetric - and a coefficient is
+// table(T_e) for a tabled tag (header n > 0, headers in static LDS), the constant by tag-dictionary index otherwise: constant
+// tables give the bits of k_assemble_rows.
+__device__ __forceinline__ double element_temperature(const double* sU, double ui, int cj, int ck) {
+#pragma clang fp contract(off)
+  return sorted_sum3(ui, sU[cj], sU[ck]) * (1.0 / 3.0);
+}
+
+// u* = u, or 2 u - uprev when uprev is given (BDF2's extrapolated state)
+struct EvalState {
+  const double *u, *uprev;
+  __device__ __forceinline__ double operator()(int node) const {
+#pragma clang fp contract(off)
+    return uprev ? 2.0 * u[node] - uprev[node] : u[node];
+  }
+};
+
+// A = M + dt K(kappa(T)) at u* in a one-value slab: M does not change, only A is written.
+struct RowsKappaT {
+  static constexpr bool PAIR = false, STATE = true, KONLY = false, NODE_FIRST = true;
+  static constexpr RgVariant ID = RG_KT;
+  const KTab* sK;
+  const double *kvals, *kappa_idx, *rhoc_idx;
+  double dt;
+  EvalState state;
+  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double* sU, double ui, int cj,
+                                         int ck) const {
+    const KTab kh = sK[tg];
+    double kappa = kappa_idx[tg];
+    if (kh.n > 0) kappa = ktab_eval(kh, kvals, element_temperature(sU, ui, cj, ck));
+    return element_row(Pi, Pj, Pk, rhoc_idx[tg], kappa);
+  }
+};
+
 __global__ __launch_bounds__(RBA) void k_assemble_rows_kT(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
                                                           const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
                                                           const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
@@ -648,104 +668,34 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_kT(int nblk, int cap /* s
                                                           double* __restrict__ Av) {
   extern __shared__ double smem[];
   __shared__ KTab sK[64];
-  double* sA = smem;                                                 // A per slot
-  double2* sXd = reinterpret_cast<double2*>(sA + cap);               // coordinates of the block's column list
-  double* sU = reinterpret_cast<double*>(sXd + capd);                // u* on the block's column list
-  int* sR = reinterpret_cast<int*>(sU + capd + (capd & 1));          // row starts inside the slab
-  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);               // column-list position per slot, from the 8-aligned start
-  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
-
-  const int t = threadIdx.x;
-  if (t < 64) sK[t] = ktab[t];
-  for (int k = t; k < cap; k += RBA) sA[k] = 0.0;
-
-  int4 hA, hB;
-  uint4 pe, pc[RG_NC];
-  double2 px[RG_NX];
-  double pu[RG_NX];
-  int pr = 0;
-  auto prefetch = [&](int blk) {
-#pragma clang fp contract(off)
-    hA = hdr[2 * blk];
-    hB = hdr[2 * blk + 1];
-    pe = ell[hB.x + t];
-    const int c0 = hA.x >> 3, nc = ((hA.x + hA.y + 7) >> 3) - c0;
-#pragma unroll
-    for (int q = 0; q < RG_NC; ++q) pc[q] = (t + q * RBA < nc) ? cid16[c0 + t + q * RBA] : make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int q = 0; q < RG_NX; ++q) {
-      const bool in = t + q * RBA < hA.w;
-      px[q] = in ? zrb[hA.z + t + q * RBA] : make_double2(0.0, 0.0);
-      const int node = in ? dict[hA.z + t + q * RBA] : 0;
-      pu[q] = !in ? 0.0 : uprev ? 2.0 * u[node] - uprev[node] : u[node];
-    }
-    pr = (t < hB.w) ? rowptr[blk * RBA + t] - hA.x : 0;
-  };
-  int blk = blockIdx.x;
-  if (blk < nblk) prefetch(blk);
-  while (blk < nblk) {
-    const int4 cA = hA, cB = hB;
-    const uint4 ce = pe;
-    const int nc = ((cA.x + cA.y + 7) >> 3) - (cA.x >> 3);
-#pragma unroll
-    for (int q = 0; q < RG_NC; ++q) if (t + q * RBA < nc) sC4[t + q * RBA] = pc[q];
-#pragma unroll
-    for (int q = 0; q < RG_NX; ++q) if (t + q * RBA < cA.w) { sXd[t + q * RBA] = px[q]; sU[t + q * RBA] = pu[q]; }
-    sR[t] = pr;
-    __syncthreads();
-    const int nxt = blk + gridDim.x;
-    if (nxt < nblk) prefetch(nxt);
-
-    if (t < cB.w) {
-      const int base = sR[t];
-      const int sbase = base + (cA.x & 7);
-      const int ci = cB.z + t;
-      const double2 Pi = sXd[ci];
-      const double ui = sU[ci];
-      double dA = 0.0;
-      int pd = 0;
-      while (pd < 31 && sC[sbase + pd] < ci) ++pd;
-      for (int g = 0; g < cB.y; ++g) {
-        const uint4 ev = g == 0 ? ce : ell[cB.x + g * RBA + t];
-        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
-          if (e == 0xFFFFu) continue;
-          const int pj = e & 31u, pk = (e >> 5) & 31u, tg = e >> 10;
-          const int cj = sC[sbase + pj], ck = sC[sbase + pk];
-          const double2 Pj = sXd[cj], Pk = sXd[ck];
-          const KTab kh = sK[tg];
-          double kappa = kappa_idx[tg];
-          if (kh.n > 0) {
-#pragma clang fp contract(off)
-            const double uj = sU[cj], uk = sU[ck];
-            const double ab_lo = fmin(ui, uj), ab_hi = fmax(ui, uj);
-            const double lo = fmin(ab_lo, uk), hi = fmax(ab_hi, uk), mid = fmax(ab_lo, fmin(ab_hi, uk));
-            kappa = ktab_eval(kh, kvals, ((lo + mid) + hi) * (1.0 / 3.0));
-          }
-          const ElemRow r = element_row(Pi, Pj, Pk, rhoc_idx[tg], kappa);
-          dA += fma(dt, r.k0, r.m0);
-          sA[base + pj] += fma(dt, r.k1, r.m1);
-          sA[base + pk] += fma(dt, r.k2, r.m2);
-        }
-      }
-      sA[base + pd] = dA;
-    }
-    __syncthreads();
-    for (int k = t; k < cA.y; k += RBA) {
-      Av[cA.x + k] = sA[k];
-      sA[k] = 0.0;
-    }
-    blk = nxt;
-  }
+  if (threadIdx.x < 64) sK[threadIdx.x] = ktab[threadIdx.x];
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict, RowsKappaT{sK, kvals, kappa_idx, rhoc_idx, dt, {u, uprev}},
+                     nullptr, Av, smem);
 }
 
-// Re-valuation of M = M(rho_c(T)) and A = M + dt K(kappa(T)) at an evaluation state u* (hf_set_rhoc_tables): k_assemble_rows_kT
-// with a second table header array for rho_c and the (M, A) slab of k_assemble_rows<false>.  T_e is computed once per element
-// visit - when either coefficient of the tag carries a table - and used for both; a tag without a table keeps its constant.
-// Both arrays are written: constant tables give M and A bit for bit as k_assemble_rows<false> does, and the sorted T_e keeps
-// both exactly symmetric.  Launched only while a capacity table is set.
+// M = M(rho_c(T)) and A = M + dt K(kappa(T)) at u*: a second table header array for rho_c and the (M, A) slab.  T_e is computed
+// once per element visit - when either coefficient of the tag carries a table - and used for both.  Both arrays are written.
+// Launched only while a capacity table is set.
+struct RowsBothT {
+  static constexpr bool PAIR = true, STATE = true, KONLY = false, NODE_FIRST = true;
+  static constexpr RgVariant ID = RG_CT;
+  const KTab *sK, *sCt;
+  const double *kvals, *cvals, *kappa_idx, *rhoc_idx;
+  double dt;
+  EvalState state;
+  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double* sU, double ui, int cj,
+                                         int ck) const {
+    const KTab kh = sK[tg], ch = sCt[tg];
+    double kappa = kappa_idx[tg], rho_c = rhoc_idx[tg];
+    if (kh.n > 0 || ch.n > 0) {
+      const double Te = element_temperature(sU, ui, cj, ck);
+      if (kh.n > 0) kappa = ktab_eval(kh, kvals, Te);
+      if (ch.n > 0) rho_c = ktab_eval(ch, cvals, Te);
+    }
+    return element_row(Pi, Pj, Pk, rho_c, kappa);
+  }
+};
+
 __global__ __launch_bounds__(RBA) void k_assemble_rows_cT(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
                                                           const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
                                                           const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
@@ -757,114 +707,28 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_cT(int nblk, int cap /* s
                                                           double* __restrict__ Mv, double* __restrict__ Av) {
   extern __shared__ double smem[];
   __shared__ KTab sK[64], sCt[64];
-  double2* sMA = reinterpret_cast<double2*>(smem);                   // (M, A) per slot
-  double2* sXd = sMA + cap;                                          // coordinates of the block's column list
-  double* sU = reinterpret_cast<double*>(sXd + capd);                // u* on the block's column list
-  int* sR = reinterpret_cast<int*>(sU + capd + (capd & 1));          // row starts inside the slab
-  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);               // column-list position per slot, from the 8-aligned start
-  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
-
-  const int t = threadIdx.x;
-  if (t < 64) { sK[t] = ktab[t]; sCt[t] = ctab[t]; }
-  for (int k = t; k < cap; k += RBA) sMA[k] = make_double2(0.0, 0.0);
-
-  int4 hA, hB;
-  uint4 pe, pc[RG_NC];
-  double2 px[RG_NX];
-  double pu[RG_NX];
-  int pr = 0;
-  auto prefetch = [&](int blk) {
-#pragma clang fp contract(off)
-    hA = hdr[2 * blk];
-    hB = hdr[2 * blk + 1];
-    pe = ell[hB.x + t];
-    const int c0 = hA.x >> 3, nc = ((hA.x + hA.y + 7) >> 3) - c0;
-#pragma unroll
-    for (int q = 0; q < RG_NC; ++q) pc[q] = (t + q * RBA < nc) ? cid16[c0 + t + q * RBA] : make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int q = 0; q < RG_NX; ++q) {
-      const bool in = t + q * RBA < hA.w;
-      px[q] = in ? zrb[hA.z + t + q * RBA] : make_double2(0.0, 0.0);
-      const int node = in ? dict[hA.z + t + q * RBA] : 0;
-      pu[q] = !in ? 0.0 : uprev ? 2.0 * u[node] - uprev[node] : u[node];
-    }
-    pr = (t < hB.w) ? rowptr[blk * RBA + t] - hA.x : 0;
-  };
-  int blk = blockIdx.x;
-  if (blk < nblk) prefetch(blk);
-  while (blk < nblk) {
-    const int4 cA = hA, cB = hB;
-    const uint4 ce = pe;
-    const int nc = ((cA.x + cA.y + 7) >> 3) - (cA.x >> 3);
-#pragma unroll
-    for (int q = 0; q < RG_NC; ++q) if (t + q * RBA < nc) sC4[t + q * RBA] = pc[q];
-#pragma unroll
-    for (int q = 0; q < RG_NX; ++q) if (t + q * RBA < cA.w) { sXd[t + q * RBA] = px[q]; sU[t + q * RBA] = pu[q]; }
-    sR[t] = pr;
-    __syncthreads();
-    const int nxt = blk + gridDim.x;
-    if (nxt < nblk) prefetch(nxt);
-
-    if (t < cB.w) {
-      const int base = sR[t];
-      const int sbase = base + (cA.x & 7);
-      const int ci = cB.z + t;
-      const double2 Pi = sXd[ci];
-      const double ui = sU[ci];
-      double dM = 0.0, dA = 0.0;
-      int pd = 0;
-      while (pd < 31 && sC[sbase + pd] < ci) ++pd;
-      for (int g = 0; g < cB.y; ++g) {
-        const uint4 ev = g == 0 ? ce : ell[cB.x + g * RBA + t];
-        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
-          if (e == 0xFFFFu) continue;
-          const int pj = e & 31u, pk = (e >> 5) & 31u, tg = e >> 10;
-          const int cj = sC[sbase + pj], ck = sC[sbase + pk];
-          const double2 Pj = sXd[cj], Pk = sXd[ck];
-          const KTab kh = sK[tg], ch = sCt[tg];
-          double kappa = kappa_idx[tg], rho_c = rhoc_idx[tg];
-          if (kh.n > 0 || ch.n > 0) {
-#pragma clang fp contract(off)
-            const double uj = sU[cj], uk = sU[ck];
-            const double ab_lo = fmin(ui, uj), ab_hi = fmax(ui, uj);
-            const double lo = fmin(ab_lo, uk), hi = fmax(ab_hi, uk), mid = fmax(ab_lo, fmin(ab_hi, uk));
-            const double Te = ((lo + mid) + hi) * (1.0 / 3.0);
-            if (kh.n > 0) kappa = ktab_eval(kh, kvals, Te);
-            if (ch.n > 0) rho_c = ktab_eval(ch, cvals, Te);
-          }
-          const ElemRow r = element_row(Pi, Pj, Pk, rho_c, kappa);
-          dM += r.m0;
-          dA += fma(dt, r.k0, r.m0);
-          double2 v = sMA[base + pj];
-          v.x += r.m1;
-          v.y += fma(dt, r.k1, r.m1);
-          sMA[base + pj] = v;
-          v = sMA[base + pk];
-          v.x += r.m2;
-          v.y += fma(dt, r.k2, r.m2);
-          sMA[base + pk] = v;
-        }
-      }
-      sMA[base + pd] = make_double2(dM, dA);
-    }
-    __syncthreads();
-    for (int k = t; k < cA.y; k += RBA) {
-      const double2 v = sMA[k];
-      Mv[cA.x + k] = v.x;
-      Av[cA.x + k] = v.y;
-      sMA[k] = make_double2(0.0, 0.0);
-    }
-    blk = nxt;
-  }
+  if (threadIdx.x < 64) { sK[threadIdx.x] = ktab[threadIdx.x]; sCt[threadIdx.x] = ctab[threadIdx.x]; }
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict,
+                     RowsBothT{sK, sCt, kvals, cvals, kappa_idx, rhoc_idx, dt, {u, uprev}}, Mv, Av, smem);
 }
 
-// Re-valuation of the stiffness alone, K = K(kappa(T)) at the state u (hf_steady_picard_setup / hf_steady_picard_solve): the
-// lists, the staging of the state, the persistent workgroups, the register prefetch and the summation order of
-// k_assemble_rows_kT with the additions of k_assemble_rows<true> - no M half, no dt - in a one-value slab.  With no table (every
-// header n = 0) or constant tables it gives the K of k_assemble_rows<true> bit for bit; the sorted T_e keeps K exactly symmetric.
+// The stiffness alone, K = K(kappa(T)) at the state u (hf_steady_picard_setup / hf_steady_picard_solve): RowsKappaT without M
+// and dt.  With no table (every header n = 0) or constant tables it gives the K of k_assemble_rows<true> bit for bit.
+struct RowsKappaTK {
+  static constexpr bool PAIR = false, STATE = true, KONLY = true, NODE_FIRST = false;
+  static constexpr RgVariant ID = RG_KT_K;
+  const KTab* sK;
+  const double *kvals, *kappa_idx, *u;
+  __device__ __forceinline__ double state(int node) const { return u[node]; }
+  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double* sU, double ui, int cj,
+                                         int ck) const {
+    const KTab kh = sK[tg];
+    double kappa = kappa_idx[tg];
+    if (kh.n > 0) kappa = ktab_eval(kh, kvals, element_temperature(sU, ui, cj, ck));
+    return element_row(Pi, Pj, Pk, 0.0, kappa);
+  }
+};
+
 __global__ __launch_bounds__(RBA) void k_assemble_rows_kT_K(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
                                                             const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
                                                             const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
@@ -874,95 +738,8 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_kT_K(int nblk, int cap /*
                                                             double* __restrict__ Kv) {
   extern __shared__ double smem[];
   __shared__ KTab sK[64];
-  double* sA = smem;                                                 // K per slot
-  double2* sXd = reinterpret_cast<double2*>(sA + cap);               // coordinates of the block's column list
-  double* sU = reinterpret_cast<double*>(sXd + capd);                // the state on the block's column list
-  int* sR = reinterpret_cast<int*>(sU + capd + (capd & 1));          // row starts inside the slab
-  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);               // column-list position per slot, from the 8-aligned start
-  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
-
-  const int t = threadIdx.x;
-  if (t < 64) sK[t] = ktab[t];
-  for (int k = t; k < cap; k += RBA) sA[k] = 0.0;
-
-  int4 hA, hB;
-  uint4 pe, pc[RG_NC];
-  double2 px[RG_NX];
-  double pu[RG_NX];
-  int pr = 0;
-  auto prefetch = [&](int blk) {
-    hA = hdr[2 * blk];
-    hB = hdr[2 * blk + 1];
-    pe = ell[hB.x + t];
-    const int c0 = hA.x >> 3, nc = ((hA.x + hA.y + 7) >> 3) - c0;
-#pragma unroll
-    for (int q = 0; q < RG_NC; ++q) pc[q] = (t + q * RBA < nc) ? cid16[c0 + t + q * RBA] : make_uint4(0, 0, 0, 0);
-#pragma unroll
-    for (int q = 0; q < RG_NX; ++q) {
-      const bool in = t + q * RBA < hA.w;
-      px[q] = in ? zrb[hA.z + t + q * RBA] : make_double2(0.0, 0.0);
-      pu[q] = in ? u[dict[hA.z + t + q * RBA]] : 0.0;
-    }
-    pr = (t < hB.w) ? rowptr[blk * RBA + t] - hA.x : 0;
-  };
-  int blk = blockIdx.x;
-  if (blk < nblk) prefetch(blk);
-  while (blk < nblk) {
-    const int4 cA = hA, cB = hB;
-    const uint4 ce = pe;
-    const int nc = ((cA.x + cA.y + 7) >> 3) - (cA.x >> 3);
-#pragma unroll
-    for (int q = 0; q < RG_NC; ++q) if (t + q * RBA < nc) sC4[t + q * RBA] = pc[q];
-#pragma unroll
-    for (int q = 0; q < RG_NX; ++q) if (t + q * RBA < cA.w) { sXd[t + q * RBA] = px[q]; sU[t + q * RBA] = pu[q]; }
-    sR[t] = pr;
-    __syncthreads();
-    const int nxt = blk + gridDim.x;
-    if (nxt < nblk) prefetch(nxt);
-
-    if (t < cB.w) {
-      const int base = sR[t];
-      const int sbase = base + (cA.x & 7);
-      const int ci = cB.z + t;
-      const double2 Pi = sXd[ci];
-      const double ui = sU[ci];
-      double dA = 0.0;
-      int pd = 0;
-      while (pd < 31 && sC[sbase + pd] < ci) ++pd;
-      for (int g = 0; g < cB.y; ++g) {
-        const uint4 ev = g == 0 ? ce : ell[cB.x + g * RBA + t];
-        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
-          if (e == 0xFFFFu) continue;
-          const int pj = e & 31u, pk = (e >> 5) & 31u, tg = e >> 10;
-          const int cj = sC[sbase + pj], ck = sC[sbase + pk];
-          const double2 Pj = sXd[cj], Pk = sXd[ck];
-          const KTab kh = sK[tg];
-          double kappa = kappa_idx[tg];
-          if (kh.n > 0) {
-#pragma clang fp contract(off)
-            const double uj = sU[cj], uk = sU[ck];
-            const double ab_lo = fmin(ui, uj), ab_hi = fmax(ui, uj);
-            const double lo = fmin(ab_lo, uk), hi = fmax(ab_hi, uk), mid = fmax(ab_lo, fmin(ab_hi, uk));
-            kappa = ktab_eval(kh, kvals, ((lo + mid) + hi) * (1.0 / 3.0));
-          }
-          const ElemRow r = element_row(Pi, Pj, Pk, 0.0, kappa);
-          dA += r.k0;
-          sA[base + pj] += r.k1;
-          sA[base + pk] += r.k2;
-        }
-      }
-      sA[base + pd] = dA;
-    }
-    __syncthreads();
-    for (int k = t; k < cA.y; k += RBA) {
-      Kv[cA.x + k] = sA[k];
-      sA[k] = 0.0;
-    }
-    blk = nxt;
-  }
+  if (threadIdx.x < 64) sK[threadIdx.x] = ktab[threadIdx.x];
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict, RowsKappaTK{sK, kvals, kappa_idx, u}, nullptr, Kv, smem);
 }
 
 // w = u^n, or BDF2's operand (4 u^n - u^{n-1}) / 3: the vector the re-valued M multiplies in Picard sweeps 2..p of a step with

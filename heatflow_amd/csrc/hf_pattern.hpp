@@ -359,64 +359,61 @@ int launch_assemble_lds(hf_ctx* ctx, bool colored, const double* kappa_tab, cons
   return HF_OK;
 }
 
-size_t rowgather_smem_bytes(int max_blk_nnz, int max_dict) {
+// Dynamic LDS of a row-gather kernel (rowgather_assemble): the value slab - (M, A) pairs or one value per slot - the column
+// list's coordinates, the staged evaluation state if any, the row starts and the 16-bit column positions
+size_t rowgather_lds_bytes(int max_blk_nnz, int max_dict, bool pair, bool state) {
   const size_t cap = static_cast<size_t>((max_blk_nnz + 1) & ~1);
-  return cap * 16 + static_cast<size_t>(max_dict) * 16 + (RBA + 4) * 4 + (cap / 8 + 3) * 16;
+  return cap * (pair ? 16 : 8) + static_cast<size_t>(max_dict) * 16 + (state ? static_cast<size_t>(max_dict + (max_dict & 1)) * 8 : 0) +
+         (RBA + 4) * 4 + (cap / 8 + 3) * 16;
 }
+size_t rowgather_smem_bytes(int max_blk_nnz, int max_dict) { return rowgather_lds_bytes(max_blk_nnz, max_dict, true, false); }
+size_t ct_smem_bytes(int max_blk_nnz, int max_dict) { return rowgather_lds_bytes(max_blk_nnz, max_dict, true, true); }   // k_assemble_rows_cT
 
-// k_assemble_rows_cT: the (M, A) slab of k_assemble_rows<false> plus the staged evaluation state of k_assemble_rows_kT
-size_t ct_smem_bytes(int max_blk_nnz, int max_dict) {
-  return rowgather_smem_bytes(max_blk_nnz, max_dict) + static_cast<size_t>(max_dict + (max_dict & 1)) * 8;
+// One launch of a row-gather kernel with the coefficient policy V (`tail`: the kernel's arguments after the lists): the LDS bytes
+// of V's slab width and staging, the opt-in above 64 KiB, persistent workgroups - as many as fit the chip at this LDS footprint,
+// from one occupancy query kept in ctx->rg_grid[V::ID] until the next mesh - and the launch.  `info`, if given, is asked when the
+// grid is worked out and returns a label to print the footprint and the grid under, or null.
+template <class V, class... KArgs, class... Tail>
+int launch_rowgather(hf_ctx* ctx,
+                     void (*kernel)(int, int, int, const int32_t*, const int4*, const uint4*, const uint4*, const double2*, KArgs...),
+                     const char* (*info)(), Tail... tail) {
+  const int cap = (ctx->max_blk_nnz + 1) & ~1;
+  const int capd = ctx->rg_max_dict;
+  const size_t sm = rowgather_lds_bytes(ctx->max_blk_nnz, capd, V::PAIR, V::STATE);
+  int& grid = ctx->rg_grid[V::ID];
+  if (grid == 0) {
+    const void* fn = reinterpret_cast<const void*>(kernel);
+    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
+    int per_cu = 0, ncu = 0;
+    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
+    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
+    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+    if (const char* label = info ? info() : nullptr)
+      std::fprintf(stderr, "%s: %zu bytes of dynamic LDS, %d workgroups per CU, grid %d of %d blocks\n", label, sm, per_cu, grid, ctx->nblk_a);
+  }
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr, ctx->d_rg_hdr,
+                     reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
+                     static_cast<KArgs>(tail)...);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
 }
 
 // Row-gather element kernel into (Mout, Aout); coefficient tables indexed by the tag dictionary.  KONLY: the stiffness
 // alone into Aout (Mout, rhoc_idx and dt unused).
 template <bool KONLY = false>
 int launch_assemble_rows(hf_ctx* ctx, const double* kappa_idx, const double* rhoc_idx, double dt, double* Mout, double* Aout) {
-  const int cap = (ctx->max_blk_nnz + 1) & ~1;
-  const int capd = ctx->rg_max_dict;
-  const size_t sm = rowgather_smem_bytes(ctx->max_blk_nnz, capd);
-  const void* fn = reinterpret_cast<const void*>(&k_assemble_rows<KONLY>);
-  int& grid = KONLY ? ctx->rg_grid_k : ctx->rg_grid;
-  if (grid == 0) {   // persistent workgroups: as many as fit the chip at this LDS footprint
-    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
-    int per_cu = 0, ncu = 0;
-    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
-    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
-    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
-  }
-  hipLaunchKernelGGL(k_assemble_rows<KONLY>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr,
-                     ctx->d_rg_hdr, reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid),
-                     ctx->d_rg_zrb, kappa_idx, rhoc_idx, dt, Mout, Aout);
-  HF_HIP(hipGetLastError());
-  return HF_OK;
+  return launch_rowgather<RowsConst<KONLY>>(ctx, &k_assemble_rows<KONLY>, nullptr, kappa_idx, rhoc_idx, dt, Mout, Aout);
 }
 
 // The same with the multipliers of hf_set_anisotropy (k_assemble_rows_an: the LDS footprint of k_assemble_rows, a grid of its own
 // from the occupancy query).  HEATFLOW_ANISO_INFO=1 prints the footprint, the workgroups per CU and the grid once per variant.
 template <bool KONLY = false>
 int launch_assemble_rows_an(hf_ctx* ctx, const double* kappa_idx, const double* rhoc_idx, double dt, double* Mout, double* Aout) {
-  const int cap = (ctx->max_blk_nnz + 1) & ~1;
-  const int capd = ctx->rg_max_dict;
-  const size_t sm = rowgather_smem_bytes(ctx->max_blk_nnz, capd);
-  const void* fn = reinterpret_cast<const void*>(&k_assemble_rows_an<KONLY>);
-  int& grid = KONLY ? ctx->an.grid_k : ctx->an.grid;
-  if (grid == 0) {
-    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
-    int per_cu = 0, ncu = 0;
-    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
-    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
-    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
-    if (const char* e = std::getenv("HEATFLOW_ANISO_INFO"))
-      if (e[0] == '1')
-        std::fprintf(stderr, "[aniso] k_assemble_rows_an<%s>: %zu bytes of dynamic LDS, %d workgroups per CU, grid %d of %d blocks\n",
-                     KONLY ? "true" : "false", sm, per_cu, grid, ctx->nblk_a);
-  }
-  hipLaunchKernelGGL(k_assemble_rows_an<KONLY>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr,
-                     ctx->d_rg_hdr, reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid),
-                     ctx->d_rg_zrb, kappa_idx, rhoc_idx, ctx->an.d_m, dt, Mout, Aout);
-  HF_HIP(hipGetLastError());
-  return HF_OK;
+  const auto info = []() -> const char* {
+    const char* e = std::getenv("HEATFLOW_ANISO_INFO");
+    return e && e[0] == '1' ? (KONLY ? "[aniso] k_assemble_rows_an<true>" : "[aniso] k_assemble_rows_an<false>") : nullptr;
+  };
+  return launch_rowgather<RowsAniso<KONLY>>(ctx, &k_assemble_rows_an<KONLY>, info, kappa_idx, rhoc_idx, ctx->an.d_m, dt, Mout, Aout);
 }
 
 // Row-gather assembly with whatever hf_set_anisotropy left: the existing kernel while no tag is anisotropic

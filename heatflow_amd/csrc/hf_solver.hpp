@@ -785,64 +785,20 @@ int kt_finish(hf_ctx* ctx) {
 // elimination, the lifting values and D^-1 as hf_assemble forms them - all on the stream, no host synchronisation.  The
 // hierarchy (if any) stays the one hf_assemble built: its fused fine-level legs hold the old operator from here on.
 int kt_revalue(hf_ctx* ctx, const double* u, const double* uprev) {
-  const int cap = (ctx->max_blk_nnz + 1) & ~1;
-  const int capd = ctx->rg_max_dict;
-  if (ctx->kt.c_on) {   // capacity tables: M and A in one pass (k_assemble_rows_cT), then the same three kernels
-    const size_t smc = ct_smem_bytes(ctx->max_blk_nnz, capd);
-    if (ctx->kt.cgrid == 0) {
-      const void* fn = reinterpret_cast<const void*>(&k_assemble_rows_cT);
-      if (smc > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smc)));
-      int per_cu = 0, ncu = 0;
-      HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, smc));
-      HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
-      ctx->kt.cgrid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
-    }
-    hipLaunchKernelGGL(k_assemble_rows_cT, dim3(ctx->kt.cgrid), dim3(RBA), smc, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr,
-                       ctx->d_rg_hdr, reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid),
-                       ctx->d_rg_zrb, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals, ctx->kt.chdr, ctx->kt.cvals, ctx->d_kappa_rg,
-                       ctx->d_rhoc_rg, ctx->dt, u, uprev, ctx->d_M, ctx->d_A);
-    return kt_finish(ctx);
-  }
-  const size_t sm = static_cast<size_t>(cap) * 8 + static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 +
-                    (RBA + 4) * 4 + (static_cast<size_t>(cap) / 8 + 3) * 16;
-  if (ctx->kt.grid == 0) {   // persistent workgroups: as many as fit the chip at this LDS footprint
-    const void* fn = reinterpret_cast<const void*>(&k_assemble_rows_kT);
-    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
-    int per_cu = 0, ncu = 0;
-    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
-    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
-    ctx->kt.grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
-  }
-  hipLaunchKernelGGL(k_assemble_rows_kT, dim3(ctx->kt.grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr,
-                     ctx->d_rg_hdr, reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid),
-                     ctx->d_rg_zrb, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev,
-                     ctx->d_A);
+  if (ctx->kt.c_on)   // capacity tables: M and A in one pass (k_assemble_rows_cT), then the same three kernels
+    HF_TRY(launch_rowgather<RowsBothT>(ctx, &k_assemble_rows_cT, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals, ctx->kt.chdr,
+                                       ctx->kt.cvals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev, ctx->d_M, ctx->d_A));
+  else
+    HF_TRY(launch_rowgather<RowsKappaT>(ctx, &k_assemble_rows_kT, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals,
+                                        ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev, ctx->d_A));
   return kt_finish(ctx);
 }
 
 // Picard steady state: Kout = K(kappa(T_e)) at the state u by the stiffness-only row-gather kernel (k_assemble_rows_kT_K, the
 // LDS footprint of k_assemble_rows_kT).  `hdr`: the conductivity table headers, or 64 empty ones while none are set.
 int steady_revalue(hf_ctx* ctx, const KTab* hdr, const double* u, double* Kout) {
-  const int cap = (ctx->max_blk_nnz + 1) & ~1;
-  const int capd = ctx->rg_max_dict;
-  const size_t sm = static_cast<size_t>(cap) * 8 + static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 +
-                    (RBA + 4) * 4 + (static_cast<size_t>(cap) / 8 + 3) * 16;
-  if (ctx->rg_grid_p == 0) {   // persistent workgroups: as many as fit the chip at this LDS footprint
-    const void* fn = reinterpret_cast<const void*>(&k_assemble_rows_kT_K);
-    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
-    int per_cu = 0, ncu = 0;
-    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
-    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
-    ctx->rg_grid_p = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
-    if (std::getenv("HEATFLOW_DEBUG"))
-      std::fprintf(stderr, "[steady picard] k_assemble_rows_kT_K: %zu bytes of dynamic LDS, %d workgroups per CU, grid %d of %d blocks\n", sm,
-                   per_cu, ctx->rg_grid_p, ctx->nblk_a);
-  }
-  hipLaunchKernelGGL(k_assemble_rows_kT_K, dim3(ctx->rg_grid_p), dim3(RBA), sm, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr,
-                     ctx->d_rg_hdr, reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid),
-                     ctx->d_rg_zrb, ctx->d_rg_dict, hdr, ctx->kt.vals, ctx->d_kappa_rg, u, Kout);
-  HF_HIP(hipGetLastError());
-  return HF_OK;
+  const auto info = []() -> const char* { return std::getenv("HEATFLOW_DEBUG") ? "[steady picard] k_assemble_rows_kT_K" : nullptr; };
+  return launch_rowgather<RowsKappaTK>(ctx, &k_assemble_rows_kT_K, info, ctx->d_rg_dict, hdr, ctx->kt.vals, ctx->d_kappa_rg, u, Kout);
 }
 
 // The solve of a step on the current operator, with the Jacobi fallback after a multigrid breakdown
