@@ -113,6 +113,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   tangent_free(ctx);
   kt_free(ctx);
   an_free(ctx);
+  value_lists_free(ctx);
   ctx->n = n; ctx->ne = ne; ctx->nnz = static_cast<int64_t>(T.colidx.size());
   ctx->nchunks = (n + RB - 1) / RB;
   ctx->nblk_a = (n + RBA - 1) / RBA;
@@ -590,6 +591,7 @@ int hf_create(int device_id, hf_ctx** out) {
   if (device_id < 0 || device_id >= count) return HF_ERR_ARG;
   hf_ctx* ctx = new hf_ctx();
   ctx->dev = device_id;
+  if (const char* e = std::getenv("HEATFLOW_VALUE_LISTS")) ctx->vl_mode = (e[0] == '0') ? 0 : (e[0] == '2') ? 2 : 1;
   auto bail = [&](int rc) { *out = ctx; return rc; };  // keep ctx so the caller can read the message
   if (hipSetDevice(device_id) != hipSuccess) return bail(fail(ctx, HF_ERR_HIP, "hipSetDevice(%d) failed", device_id));
   // non-blocking: no implicit ordering with the legacy stream, so contexts driven from different host
@@ -629,7 +631,7 @@ int hf_destroy(hf_ctx* ctx) {
   dev_free(&ctx->d_uprev); dev_free(&ctx->d_ustart);
   dev_free(&ctx->d_u); dev_free(&ctx->d_b); dev_free(&ctx->d_r); dev_free(&ctx->d_p); dev_free(&ctx->d_Ap);
   free_batch(ctx); free_batch_state(ctx->fluxb); free_batch_cols(ctx); free_amg(ctx); free_responses(ctx); proj_free(ctx); dev_free(&ctx->d_z); dev_free(&ctx->d_z2);
-  steady_free(ctx); load_free(ctx); tangent_free(ctx); kt_free(ctx); an_free(ctx);
+  steady_free(ctx); load_free(ctx); tangent_free(ctx); kt_free(ctx); an_free(ctx); value_lists_free(ctx);
   dev_free(&ctx->d_M1); dev_free(&ctx->d_dinv1); dev_free(&ctx->d_gz); dev_free(&ctx->d_gr); dev_free(&ctx->d_bz); dev_free(&ctx->d_br);
   dev_free(&ctx->d_tmp); dev_free(&ctx->d_part_pAp); dev_free(&ctx->d_part_rz); dev_free(&ctx->d_part_zz);
   dev_free(&ctx->d_part_bn); dev_free(&ctx->d_scal); dev_free(&ctx->d_samp_idx); dev_free(&ctx->d_samp); dev_free(&ctx->d_fsamp_idx);
@@ -847,6 +849,8 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
   ctx->dt = ctx->scheme == HF_TIME_BDF2 ? 2.0 * dt / 3.0 : dt;   // BDF2: A' = M + (2/3) dt K
   ctx->mode = mode;
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  value_lists_touch(ctx, ctx->d_A);
+  value_lists_touch(ctx, ctx->d_M);
   HF_TRY(launch_assemble(ctx));
   if (ctx->kt.on) {
     // kappa(T): M as assembled above, A re-valued at the current state, then elimination, lifting values and D^-1
@@ -863,12 +867,19 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
     hipLaunchKernelGGL(k_dinv, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr,
                        ctx->d_colidx, ctx->d_A, ctx->d_dinv);
   }
+  // the operators stand as the loops will read them: their value lists for k_spmv (inside the timed interval)
+  const bool lists = value_lists_wanted(ctx);
+  if (lists) {
+    HF_TRY(value_lists_build(ctx, 0, ctx->d_A));
+    HF_TRY(value_lists_build(ctx, 1, ctx->d_M));
+  }
   HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
   HF_HIP(hipGetLastError());
   HF_HIP(hipStreamSynchronize(ctx->stream));
   float ms = 0.f;
   HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   ctx->last_ms = ms;
+  if (lists) HF_TRY(value_lists_finish(ctx));
   if (ctx->precond == 1) {
     OperatorPrint now;
     HF_TRY(operator_print(ctx, now));
@@ -1485,6 +1496,7 @@ int hf_get_tangent(hf_ctx* ctx, int32_t j, double* s) {
 // After a valuation of the stiffness into steady.Kfree (on the swapped context): K_hat_S = the copy with the set S eliminated, the
 // lifting values K[free, S] taken before, and D^-1
 int steady_eliminate(hf_ctx* ctx) {
+  value_lists_touch(ctx, ctx->d_A);   // (the swapped context's d_A is the steady K, which carries no lists: a guard, not a path)
   HF_HIP(hipMemcpyAsync(ctx->d_A, ctx->steady.Kfree, sizeof(double) * ctx->nnz, hipMemcpyDeviceToDevice, ctx->stream));
   if (ctx->nlift > 0)
     hipLaunchKernelGGL(k_take_lift, dim3((ctx->nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift, ctx->d_lift_slot,
@@ -2005,6 +2017,34 @@ int hf_get_csr(hf_ctx* ctx, int32_t* rowptr, int32_t* colidx, double* A, double*
   if (colidx) std::memcpy(colidx, ctx->h_colidx.data(), sizeof(int32_t) * ctx->nnz);
   if (A) HF_HIP(copy_sync(ctx, A, ctx->d_A, sizeof(double) * ctx->nnz, hipMemcpyDeviceToHost));
   if (M) HF_HIP(copy_sync(ctx, M, ctx->d_M, sizeof(double) * ctx->nnz, hipMemcpyDeviceToHost));
+  return HF_OK;
+}
+
+int hf_set_value_lists(hf_ctx* ctx, int32_t mode) {
+  if (!ctx) return HF_ERR_ARG;
+  if (mode < 0 || mode > 2) return fail(ctx, HF_ERR_ARG, "hf_set_value_lists: unknown mode %d", mode);
+  ctx->vl_mode = mode;
+  return HF_OK;
+}
+
+int hf_get_value_lists(hf_ctx* ctx, int32_t which, int32_t* valid, int64_t* sum_vlist, int32_t* max_vlist, int32_t* vcap, int32_t* vptr,
+                       double* vlist, uint32_t* cv) {
+  if (!ctx) return HF_ERR_ARG;
+  if (which < 0 || which > 1) return fail(ctx, HF_ERR_ARG, "hf_get_value_lists: which = %d (0 = A, 1 = M)", which);
+  if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_get_value_lists before hf_assemble");
+  const hf_ctx::ValueLists& L = ctx->vl[which];
+  const bool live = L.valid && L.src == (which ? ctx->d_M : ctx->d_A);
+  if (valid) *valid = live ? 1 : 0;
+  if (sum_vlist) *sum_vlist = L.sum_vlist;
+  if (max_vlist) *max_vlist = L.max_vlist;
+  if (vcap) *vcap = ctx->vl_vcap;
+  if (vptr || vlist || cv) {
+    if (!live) return fail(ctx, HF_ERR_STATE, "hf_get_value_lists: the tables of %s are not valid", which ? "M" : "A");
+    HF_HIP(hipSetDevice(ctx->dev));
+    if (vptr) HF_HIP(copy_sync(ctx, vptr, L.vptr, sizeof(int32_t) * (static_cast<size_t>(ctx->nchunks_s) + 1), hipMemcpyDeviceToHost));
+    if (vlist) HF_HIP(copy_sync(ctx, vlist, L.vlist, sizeof(double) * static_cast<size_t>(L.sum_vlist), hipMemcpyDeviceToHost));
+    if (cv) HF_HIP(copy_sync(ctx, cv, L.cv, sizeof(uint32_t) * static_cast<size_t>(ctx->nnz), hipMemcpyDeviceToHost));
+  }
   return HF_OK;
 }
 

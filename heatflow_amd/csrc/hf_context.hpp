@@ -125,6 +125,24 @@ struct hf_ctx {
   int max_cdict = 0;
   bool cdict_own = false;      // every chunk's own rows sit contiguously in its column list (each row stores its diagonal): the kernels take x[row] from the staged slice
   bool c16 = true;             // HEATFLOW_SPMV_C16=0 keeps the 32-bit column stream
+  // value lists of d_A ([0]) and d_M ([1]) (ValComp in hf_kernels.hpp): a second, lossless encoding of the same values for k_spmv
+  // - per SpMV chunk the distinct 64-bit patterns of its values in ascending order, per nonzero the 16-bit position in that list
+  // packed with the 16-bit column position.  Built at the end of hf_assemble (value_lists_build in hf_pattern.hpp); `src` is
+  // the array the tables encode: launch_spmv takes them for that pointer only, and whoever writes the array afterwards clears
+  // `valid` (value_lists_touch).
+  struct ValueLists {
+    const double* src = nullptr;
+    int32_t *vptr = nullptr, *count = nullptr, *info = nullptr;   // list starts (nchunks_s + 1); list lengths; {sum, max} of the last build
+    double* vlist = nullptr;
+    uint32_t* cv = nullptr;        // cid | vid << 16 per nonzero
+    int64_t cap = 0;               // entries `vlist` holds
+    int64_t sum_vlist = 0;
+    int max_vlist = 0;
+    bool valid = false;
+  } vl[2];
+  int vl_mode = 1;             // HEATFLOW_VALUE_LISTS / hf_set_value_lists: 0 off, 1 on where the lists hold <= nnz / 2 entries, 2 always
+  int vl_vcap = 0;             // list entries staged in LDS per chunk (longer lists are read from global memory)
+  int vl_occ = 0;              // workgroups of the value-list kernel per CU at that footprint
   bool have_mesh = false, have_mat = false, assembled = false;
   double dt = 0.0;             // step of the assembled operator A = M + dt K: the step of hf_assemble (backward Euler) or 2/3 of it (BDF2)
   double dt_step = 0.0;        // the step hf_assemble was called with

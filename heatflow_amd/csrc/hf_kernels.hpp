@@ -977,6 +977,11 @@ __device__ __forceinline__ void mirror_breakdown(ScalMirror* m, unsigned epoch) 
 // own != 0 (square operators whose rows all store their diagonal): the chunk's own rows are a contiguous run of its sorted
 // column list, so the row-wise operand x[row] of MODE 4 / 8 / 9 is taken from the staged slice instead of read again.
 struct ColComp { const int32_t* dptr; const int32_t* dict; const uint16_t* id; int xd_off; int own; };
+// Value lists of the fine operator (VC, with C16): per chunk the distinct 64-bit patterns of its values (`vlist`, starts in
+// `vptr`, ascending as unsigned integers) and per nonzero one word cv = column position | value position << 16, instead of an
+// f64 value and a 16-bit column position: 4 + 8 (list entries / nnz) instead of 10 bytes per nonzero, the same doubles
+// multiplied.  Lists of up to `vcap` entries are staged in LDS behind the operand slice (vl_off), longer ones are read in place.
+struct ValComp : ColComp { const int32_t* vptr; const double* vlist; const uint32_t* cv; int vl_off; int vcap; };
 
 // The matrix stream (values, 16-bit positions) is read exactly once per launch: HF_NT_STREAM=1 marks those loads non-temporal
 // (A/B builds; 0 = plain loads)
@@ -1017,7 +1022,7 @@ __device__ __forceinline__ T stream_load(const T* p) {
 // BDF2 operand of the right-hand side: 4/3 u^n - 1/3 u^{n-1}
 __device__ __forceinline__ double bdf2_operand(double un, double unm1) { return (4.0 * un - unm1) * (1.0 / 3.0); }
 
-template <int MODE, bool C16 = false, typename VT = double, int UN = 8>
+template <int MODE, bool C16 = false, typename VT = double, int UN = 8, bool VC = false>
 __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_spmv(int n, int nchunks, int rpc /* rows per chunk, <= TS */,
                                               const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
                                               const VT* __restrict__ vals, const double* __restrict__ x,
@@ -1026,7 +1031,7 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                                               const double* __restrict__ dinv, double* __restrict__ pvec,
                                               double* __restrict__ part1, double* __restrict__ part2, double w,
                                               int npart /* partial slots the consumers sum (>= gridDim.x) */,
-                                              int parity, ColComp comp) {
+                                              int parity, typename std::conditional<VC, ValComp, ColComp>::type comp) {
   extern __shared__ double sprod[];
   __shared__ double s4[TS / 64];
   __shared__ int s_own;
@@ -1079,7 +1084,8 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
     }
     return conv;
   };
-  constexpr bool PIPELINED = C16 && (HF_PIPE == 2 || (HF_PIPE == 1 && sizeof(VT) == 4));
+  constexpr bool PIPELINED = C16 && !VC && (HF_PIPE == 2 || (HF_PIPE == 1 && sizeof(VT) == 4));
+  static_assert(!VC || (C16 && sizeof(VT) == 8), "value lists: the fine operator's f64 arrays on compressed columns");
   if (!PIPELINED && cycle_gate()) return;     // (the pipelined path requests its first chunk before it adds up the partials)
   const ChunkIter sched(nchunks);
   HF_STAMP(0);
@@ -1288,7 +1294,70 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       pb = rowptr[prow + 1] - k0;
     }
     RowOps e = row_operands(min(prow, r1 - 1), C16 && comp.own != 0);
-    if (C16) {
+    if constexpr (VC) {
+      // as the C16 branch below, on the packed stream: the first batch of words and the chunk's value list are requested before
+      // the operand slice is staged, so the three latencies overlap
+      double* xd = sprod + comp.xd_off;
+      double* vl = sprod + comp.vl_off;
+      const int d0 = comp.dptr[chunk], nd = comp.dptr[chunk + 1] - d0;
+      const int v0 = comp.vptr[chunk], nv = comp.vptr[chunk + 1] - v0;
+      const bool vin = nv <= comp.vcap;          // the same for every lane: the list sits in LDS, or is read in place
+      int k = k0 + threadIdx.x;
+      std::uint32_t cw[HF_UNROLL];
+#pragma unroll
+      for (int u = 0; u < HF_UNROLL; ++u) cw[u] = (k + u * TS < k1) ? stream_load(&comp.cv[k + u * TS]) : 0u;
+      double lv[2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int i = static_cast<int>(threadIdx.x) + u * TS;
+        lv[u] = (vin && i < nv) ? comp.vlist[v0 + i] : 0.0;
+      }
+      for (int i = threadIdx.x; i < nd; i += HF_STAGE_U * TS) {
+        int c[HF_STAGE_U];
+        double xv[HF_STAGE_U];
+#pragma unroll
+        for (int u = 0; u < HF_STAGE_U; ++u) c[u] = (i + u * TS < nd) ? comp.dict[d0 + i + u * TS] : 0;
+#pragma unroll
+        for (int u = 0; u < HF_STAGE_U; ++u) xv[u] = (i + u * TS < nd) ? opnd(c[u]) : 0.0;
+#pragma unroll
+        for (int u = 0; u < HF_STAGE_U; ++u)
+          if (i + u * TS < nd) {
+            xd[i + u * TS] = xv[u];
+            if ((MODE == 4 || MODE == 8 || MODE == 9 || MODE == 11) && c[u] == r0) s_own = i + u * TS;
+          }
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int i = static_cast<int>(threadIdx.x) + u * TS;
+        if (vin && i < nv) vl[i] = lv[u];
+      }
+      if (vin)
+        for (int i = threadIdx.x + 2 * TS; i < nv; i += TS) vl[i] = comp.vlist[v0 + i];   // lists longer than 2 TS (rare)
+      __syncthreads();
+      HF_STAMP(stamp_at); ++stamp_at;
+      if ((MODE == 4 || MODE == 8 || MODE == 9 || MODE == 11) && comp.own && pin) e.x = xd[s_own + (prow - r0)];
+      while (k < k1) {
+        const int kn = k + HF_UNROLL * TS;
+        std::uint32_t cn[HF_UNROLL];
+#pragma unroll
+        for (int u = 0; u < HF_UNROLL; ++u) cn[u] = (kn + u * TS < k1) ? stream_load(&comp.cv[kn + u * TS]) : 0u;
+        if (vin) {
+#pragma unroll
+          for (int u = 0; u < HF_UNROLL; ++u)
+            if (k + u * TS < k1) sprod[k - k0 + u * TS] = vl[cw[u] >> 16] * xd[cw[u] & 0xffffu];
+        } else {
+          double gv[HF_UNROLL];
+#pragma unroll
+          for (int u = 0; u < HF_UNROLL; ++u) gv[u] = (k + u * TS < k1) ? comp.vlist[v0 + static_cast<int>(cw[u] >> 16)] : 0.0;
+#pragma unroll
+          for (int u = 0; u < HF_UNROLL; ++u)
+            if (k + u * TS < k1) sprod[k - k0 + u * TS] = gv[u] * xd[cw[u] & 0xffffu];
+        }
+#pragma unroll
+        for (int u = 0; u < HF_UNROLL; ++u) cw[u] = cn[u];
+        k = kn;
+      }
+    } else if (C16) {
       // first batch of values / 16-bit ids is requested before the operand slice is staged, so both latencies overlap
       double* xd = sprod + comp.xd_off;
       const int d0 = comp.dptr[chunk], nd = comp.dptr[chunk + 1] - d0;
@@ -1379,6 +1448,130 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
       part2[blockIdx.x] = t2;
       for (int q = blockIdx.x + gridDim.x; q < npart; q += gridDim.x) { part1[q] = 0.0; part2[q] = 0.0; }
     }
+  }
+}
+
+// ------------------------------------------------------------------------------------------
+// Builder of the value lists (ValComp), three launches on the context's stream:
+//   k_vl_ids    one workgroup per chunk: the chunk's values as (64-bit pattern, origin) pairs in LDS, bitonic sort over the chunk
+//               padded to a power of two, list heads flagged and counted, cv[k] = column position | rank of vals[k] << 16
+//   k_vl_scan   one workgroup: list starts = exclusive sum of the chunks' counts; {sum, max} for the host
+//   k_vl_lists  vlist[vptr[chunk] + rank] = vals[k]; lanes that hold the same pattern store the same 8 bytes
+// Patterns are compared as unsigned integers (0.0 and -0.0 are two entries); the same values give the same tables.
+// ------------------------------------------------------------------------------------------
+constexpr int VL_MAX_CHUNK = 4096;   // nonzeros of the largest chunk the builder sorts (40 KiB of LDS)
+
+// inclusive sum over the workgroup's NW wavefronts; `total`: the workgroup's sum
+template <int NW>
+__device__ __forceinline__ int block_scan_incl(int v, int* sw, int& total) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  if (lane == 63) sw[w] = v;
+  __syncthreads();
+  int before = 0;
+  total = 0;
+#pragma unroll
+  for (int q = 0; q < NW; ++q) {
+    const int t = sw[q];
+    if (q < w) before += t;
+    total += t;
+  }
+  __syncthreads();
+  return v + before;
+}
+
+__global__ __launch_bounds__(TS) void k_vl_ids(int n, int nchunks, int rpc, const int32_t* __restrict__ rowptr,
+                                               const double* __restrict__ vals, const uint16_t* __restrict__ cid,
+                                               std::uint32_t* __restrict__ cv, int32_t* __restrict__ count) {
+  __shared__ unsigned long long skey[VL_MAX_CHUNK];
+  __shared__ uint16_t sorg[VL_MAX_CHUNK];
+  __shared__ int sw[TS / 64];
+  const int tid = static_cast<int>(threadIdx.x);
+  for (int chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+    const int r0 = chunk * rpc, r1 = min(n, r0 + rpc);
+    const int k0 = rowptr[r0], m = min(rowptr[r1] - k0, VL_MAX_CHUNK);   // (the host builds no lists for a mesh with longer chunks)
+    int np = 64;
+    while (np < m) np <<= 1;
+    for (int i = tid; i < np; i += TS) {
+      skey[i] = i < m ? static_cast<unsigned long long>(__double_as_longlong(vals[k0 + i])) : ~0ull;
+      sorg[i] = static_cast<uint16_t>(i);
+    }
+    __syncthreads();
+    // ascending by (pattern, origin): the pads (origin >= m) end up behind every entry of the chunk, whatever its pattern
+    for (int size = 2; size <= np; size <<= 1)
+      for (int stride = size >> 1; stride > 0; stride >>= 1) {
+        for (int t = tid; t < (np >> 1); t += TS) {
+          const int lo = 2 * t - (t & (stride - 1)), hi = lo + stride;
+          const bool up = (lo & size) == 0;
+          const unsigned long long ka = skey[lo], kb = skey[hi];
+          const uint16_t oa = sorg[lo], ob = sorg[hi];
+          const bool gt = ka > kb || (ka == kb && oa > ob);
+          if (gt == up) { skey[lo] = kb; skey[hi] = ka; sorg[lo] = ob; sorg[hi] = oa; }
+        }
+        __syncthreads();
+      }
+    // each lane ranks `per` consecutive sorted entries
+    const int per = (np + TS - 1) / TS;
+    const int i0 = tid * per;
+    int heads = 0;
+    for (int j = 0; j < per; ++j) {
+      const int i = i0 + j;
+      if (i < m && (i == 0 || skey[i] != skey[i - 1])) ++heads;
+    }
+    int total = 0;
+    int run = block_scan_incl<TS / 64>(heads, sw, total) - heads;   // list heads before this lane's entries
+    for (int j = 0; j < per; ++j) {
+      const int i = i0 + j;
+      if (i < m) {
+        if (i == 0 || skey[i] != skey[i - 1]) ++run;
+        const int k = k0 + sorg[i];
+        cv[k] = static_cast<std::uint32_t>(cid[k]) | (static_cast<std::uint32_t>(run - 1) << 16);
+      }
+    }
+    if (tid == 0) count[chunk] = total;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(1024) void k_vl_scan(int nchunks, const int32_t* __restrict__ count, int32_t* __restrict__ vptr,
+                                                  int32_t* __restrict__ info) {
+  __shared__ int sw[16];
+  __shared__ int smax[16];
+  const int tid = static_cast<int>(threadIdx.x);
+  int carry = 0, mx = 0;
+  for (int base = 0; base < nchunks; base += 1024) {
+    const int i = base + tid;
+    const int v = i < nchunks ? count[i] : 0;
+    mx = max(mx, v);
+    int total = 0;
+    const int incl = block_scan_incl<16>(v, sw, total);
+    if (i < nchunks) vptr[i] = carry + incl - v;
+    carry += total;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = max(mx, __shfl_down(mx, o, 64));
+  if ((tid & 63) == 0) smax[tid >> 6] = mx;
+  __syncthreads();
+  if (tid == 0) {
+    for (int q = 1; q < 16; ++q) mx = max(mx, smax[q]);
+    vptr[nchunks] = carry;
+    info[0] = carry;
+    info[1] = mx;
+  }
+}
+
+__global__ __launch_bounds__(TS) void k_vl_lists(int n, int nchunks, int rpc, const int32_t* __restrict__ rowptr,
+                                                 const double* __restrict__ vals, const std::uint32_t* __restrict__ cv,
+                                                 const int32_t* __restrict__ vptr, long long cap, double* __restrict__ vlist) {
+  if (vptr[nchunks] > cap) return;     // more list entries than the array holds: the host keeps the raw path
+  for (int chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
+    const int r0 = chunk * rpc, r1 = min(n, r0 + rpc);
+    const int k0 = rowptr[r0], k1 = rowptr[r1], v0 = vptr[chunk];
+    for (int k = k0 + threadIdx.x; k < k1; k += TS) vlist[v0 + static_cast<int>(cv[k] >> 16)] = vals[k];
   }
 }
 

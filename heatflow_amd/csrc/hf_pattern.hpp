@@ -441,6 +441,108 @@ int launch_assemble(hf_ctx* ctx) {
   return HF_OK;
 }
 
+// ---- value lists of d_A / d_M (hf_ctx::ValueLists, ValComp)
+inline void value_lists_touch(hf_ctx* c, const double* vals) {   // `vals` is about to be written: its tables no longer hold its values
+  for (auto& L : c->vl)
+    if (L.src == vals) L.valid = false;
+}
+inline const hf_ctx::ValueLists* value_lists_of(const hf_ctx* c, const double* vals) {
+  for (const auto& L : c->vl)
+    if (L.valid && L.src == vals) return &L;
+  return nullptr;
+}
+inline const hf_ctx::ValueLists* value_lists_of(const hf_ctx*, const float*) { return nullptr; }
+
+void value_lists_free(hf_ctx* ctx) {
+  for (auto& L : ctx->vl) {
+    dev_free(&L.vptr); dev_free(&L.count); dev_free(&L.info); dev_free(&L.vlist); dev_free(&L.cv);
+    L = hf_ctx::ValueLists();
+  }
+  ctx->vl_vcap = 0; ctx->vl_occ = 0;
+}
+
+// lists are built for this context's operators: the switch is on, the kernel runs on compressed columns, the values stay what
+// hf_assemble leaves (no coefficient tables) and the builder's sort holds the largest chunk
+bool value_lists_wanted(const hf_ctx* ctx) {
+  return ctx->vl_mode != 0 && ctx->c16 && !ctx->kt.on && ctx->max_chunk_nnz_s <= VL_MAX_CHUNK && ctx->nchunks_s > 0;
+}
+
+// Queue the build of the tables of `vals` (which: 0 = d_A, 1 = d_M) on the stream; value_lists_finish reads the outcome after the
+// caller's synchronisation.
+int value_lists_build(hf_ctx* ctx, int which, const double* vals) {
+  hf_ctx::ValueLists& L = ctx->vl[which];
+  L.valid = false;
+  L.src = vals;
+  const int64_t want = ctx->vl_mode == 2 ? ctx->nnz : ctx->nnz / 2;
+  if (!L.cv) {
+    HF_TRY(dev_alloc(ctx, &L.cv, ctx->nnz));
+    HF_TRY(dev_alloc(ctx, &L.vptr, static_cast<size_t>(ctx->nchunks_s) + 1));
+    HF_TRY(dev_alloc(ctx, &L.count, ctx->nchunks_s));
+    HF_TRY(dev_alloc(ctx, &L.info, 2));
+  }
+  if (!L.vlist || L.cap < want) {
+    HF_TRY(dev_alloc(ctx, &L.vlist, std::max<int64_t>(want, 1)));
+    L.cap = want;
+  }
+  const int grid = std::min(ctx->nchunks_s, 4096);
+  hipLaunchKernelGGL(k_vl_ids, dim3(grid), dim3(TS), 0, ctx->stream, ctx->n, ctx->nchunks_s, static_cast<int>(SRPC), ctx->d_rowptr, vals,
+                     ctx->d_cid, L.cv, L.count);
+  hipLaunchKernelGGL(k_vl_scan, dim3(1), dim3(1024), 0, ctx->stream, ctx->nchunks_s, L.count, L.vptr, L.info);
+  hipLaunchKernelGGL(k_vl_lists, dim3(grid), dim3(TS), 0, ctx->stream, ctx->n, ctx->nchunks_s, static_cast<int>(SRPC), ctx->d_rowptr, vals,
+                     L.cv, L.vptr, static_cast<long long>(L.cap), L.vlist);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+// List entries per chunk staged in LDS (ValComp::vcap): as many as keep the workgroups per CU of the kernel without a list - the
+// occupancy the chunk geometry was chosen for - up to the longest list and the 64-KiB window.  HEATFLOW_VALUE_LISTS_VCAP=<entries>
+// sets it instead (measurements: e.g. the longest list, one workgroup per CU fewer).
+int value_lists_vcap(hf_ctx* ctx, int longest) {
+  const void* fn = reinterpret_cast<const void*>(&k_spmv<9, true, double, HF_SPMV_UN, true>);
+  const size_t base = spmv_smem_bytes(ctx);
+  const int room = base < 64 * 1024 ? static_cast<int>((64 * 1024 - base) / 8) : 0;
+  int occ0 = 0;
+  HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ0, fn, TS, base));
+  int lo = 0, hi = std::min(longest, room), occ = occ0;
+  if (const char* e = std::getenv("HEATFLOW_VALUE_LISTS_VCAP")) {
+    lo = std::max(0, std::min(std::atoi(e), room));
+    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, fn, TS, base + static_cast<size_t>(lo) * 8));
+  } else {
+    while (lo < hi) {     // the largest footprint that keeps occ0 workgroups per CU
+      const int mid = (lo + hi + 1) / 2;
+      int o = 0;
+      HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, fn, TS, base + static_cast<size_t>(mid) * 8));
+      if (o >= occ0) lo = mid; else hi = mid - 1;
+    }
+  }
+  ctx->vl_vcap = lo;
+  ctx->vl_occ = occ;
+  return HF_OK;
+}
+
+// After the synchronisation that follows value_lists_build: sums, the nnz / 2 rule and the LDS share of the lists
+int value_lists_finish(hf_ctx* ctx) {
+  int longest = 0;
+  for (auto& L : ctx->vl) {
+    if (!L.src || !L.info) continue;
+    int32_t info[2] = {0, 0};
+    HF_HIP(copy_sync(ctx, info, L.info, sizeof info, hipMemcpyDeviceToHost));
+    L.sum_vlist = info[0];
+    L.max_vlist = info[1];
+    L.valid = L.sum_vlist <= L.cap && (ctx->vl_mode == 2 || L.sum_vlist <= ctx->nnz / 2);
+    if (L.valid) longest = std::max(longest, L.max_vlist);
+  }
+  if (longest > 0) HF_TRY(value_lists_vcap(ctx, longest));
+  if (std::getenv("HEATFLOW_DEBUG"))
+    for (int w = 0; w < 2; ++w)
+      std::fprintf(stderr, "[value lists] %s: %lld list entries for %lld nonzeros (share %.4f, %.2f bytes per nonzero), longest list %d, %s; %d entries per chunk in LDS, %d workgroups per CU\n",
+                   w ? "M" : "A", static_cast<long long>(ctx->vl[w].sum_vlist), static_cast<long long>(ctx->nnz),
+                   static_cast<double>(ctx->vl[w].sum_vlist) / static_cast<double>(std::max<int64_t>(ctx->nnz, 1)),
+                   4.0 + 8.0 * static_cast<double>(ctx->vl[w].sum_vlist) / static_cast<double>(std::max<int64_t>(ctx->nnz, 1)),
+                   ctx->vl[w].max_vlist, ctx->vl[w].valid ? "in use" : "not used", ctx->vl_vcap, ctx->vl_occ);
+  return HF_OK;
+}
+
 template <int MODE, typename VT = double>
 void launch_spmv(hf_ctx* c, const VT* vals, const double* x, double* y, double* part0 = nullptr,
                  const double* bvec = nullptr, double* pvec = nullptr, double* part1 = nullptr,
@@ -453,7 +555,20 @@ void launch_spmv(hf_ctx* c, const VT* vals, const double* x, double* y, double* 
                      static_cast<const int32_t*>(c->d_colidx), vals, x, y, (MODE == 0 ? nullptr : c->d_scal), part0, bvec,  \
                      dinv ? dinv : static_cast<const double*>(c->d_dinv), pvec, part1, part2, w, c->P, parity, comp
   const std::uint32_t smem = static_cast<std::uint32_t>(spmv_smem_bytes(c));
-  if (c->c16) {
+  // the value array has valid value lists (d_A or d_M since the last hf_assemble): the same products from the packed stream
+  const hf_ctx::ValueLists* L = c->c16 ? value_lists_of(c, vals) : nullptr;
+  if (L != nullptr) {
+    if constexpr (std::is_same<VT, double>::value) {
+      const ValComp vcomp{comp, L->vptr, L->vlist, L->cv, c->max_chunk_nnz_s + c->max_cdict, c->vl_vcap};
+      const std::uint32_t smem_v = smem + static_cast<std::uint32_t>(c->vl_vcap) * 8u;
+#define HF_SPMV_VARGS c->n, c->nchunks_s, static_cast<int>(SRPC), static_cast<const int32_t*>(c->d_rowptr),                   \
+                      static_cast<const int32_t*>(c->d_colidx), vals, x, y, (MODE == 0 ? nullptr : c->d_scal), part0, bvec,  \
+                      dinv ? dinv : static_cast<const double*>(c->d_dinv), pvec, part1, part2, w, c->P, parity, vcomp
+      if (ev_start != nullptr) hipExtLaunchKernelGGL((k_spmv<MODE, true, double, HF_SPMV_UN, true>), dim3(c->Ps), dim3(TS), smem_v, c->stream, ev_start, ev_stop, 0u, HF_SPMV_VARGS);
+      else hipLaunchKernelGGL((k_spmv<MODE, true, double, HF_SPMV_UN, true>), dim3(c->Ps), dim3(TS), smem_v, c->stream, HF_SPMV_VARGS);
+#undef HF_SPMV_VARGS
+    }
+  } else if (c->c16) {
     if (ev_start != nullptr) hipExtLaunchKernelGGL((k_spmv<MODE, true, VT, HF_SPMV_UN>), dim3(c->Ps), dim3(TS), smem, c->stream, ev_start, ev_stop, 0u, HF_SPMV_ARGS);
     else hipLaunchKernelGGL((k_spmv<MODE, true, VT, HF_SPMV_UN>), dim3(c->Ps), dim3(TS), smem, c->stream, HF_SPMV_ARGS);
   } else {

@@ -785,6 +785,8 @@ int kt_finish(hf_ctx* ctx) {
 // elimination, the lifting values and D^-1 as hf_assemble forms them - all on the stream, no host synchronisation.  The
 // hierarchy (if any) stays the one hf_assemble built: its fused fine-level legs hold the old operator from here on.
 int kt_revalue(hf_ctx* ctx, const double* u, const double* uprev) {
+  value_lists_touch(ctx, ctx->d_A);   // (no lists are built while tables are set; whatever an earlier hf_assemble left is stale now)
+  if (ctx->kt.c_on) value_lists_touch(ctx, ctx->d_M);
   if (ctx->kt.c_on)   // capacity tables: M and A in one pass (k_assemble_rows_cT), then the same three kernels
     HF_TRY(launch_rowgather<RowsBothT>(ctx, &k_assemble_rows_cT, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals, ctx->kt.chdr,
                                        ctx->kt.cvals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev, ctx->d_M, ctx->d_A));

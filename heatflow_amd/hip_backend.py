@@ -37,6 +37,7 @@ EXPORTS = [
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
     "hf_tangent_setup", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
+    "hf_set_value_lists", "hf_get_value_lists",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
 
@@ -148,6 +149,8 @@ def load_library():
         "hf_get_sizes": [vp, pi, pi, C.POINTER(i64), pi],
         "hf_get_csr": [vp, pi, pi, pd, pd],
         "hf_spmv": [vp, i32, pd, pd],
+        "hf_set_value_lists": [vp, i32],
+        "hf_get_value_lists": [vp, i32, pi, C.POINTER(i64), pi, pi, pi, pd, C.POINTER(C.c_uint32)],
         "hf_amg_apply": [vp, pd, pd, pd],
         "hf_batch_apply_precond": [vp, pd, pd, pd],
         "hf_dense_inverse": [vp, i32, pi, pi, pd, pd, pd, pd, pd],
@@ -669,6 +672,27 @@ class HeatflowHIP:
         y = np.empty(self.n, dtype=np.float64)
         self._check(self._lib.hf_spmv(self._ctx, int(which), _pd(x), _pd(y)))
         return y
+
+    def set_value_lists(self, mode):
+        """Value lists of A and M for the fine-level SpMV (0 off, 1 where they hold <= nnz / 2 entries, 2 always); effective
+        from the next assemble."""
+        self._check(self._lib.hf_set_value_lists(self._ctx, int(mode)))
+
+    def get_value_lists(self, which=0, arrays=False):
+        """dict(valid, sum_vlist, max_vlist, vcap) of the value lists of A (which = 0) or M (1); with arrays=True also vptr,
+        vlist and cv (the tables must be valid)."""
+        valid, mx, vcap, total = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        self._check(self._lib.hf_get_value_lists(self._ctx, int(which), C.byref(valid), C.byref(total), C.byref(mx), C.byref(vcap),
+                                                 None, None, None))
+        out = {"valid": bool(valid.value), "sum_vlist": total.value, "max_vlist": mx.value, "vcap": vcap.value}
+        if arrays:
+            vptr = np.empty((self.n + 511) // 512 + 1, dtype=np.int32)
+            vlist = np.empty(total.value, dtype=np.float64)
+            cv = np.empty(self.nnz, dtype=np.uint32)
+            self._check(self._lib.hf_get_value_lists(self._ctx, int(which), None, None, None, None, _pi(vptr), _pd(vlist),
+                                                     cv.ctypes.data_as(C.POINTER(C.c_uint32))))
+            out.update(vptr=vptr, vlist=vlist, cv=cv)
+        return out
 
     # -- preconditioner test entry points (tests/test_gpu_vcycle.py) ------------------------------------
     def amg_apply(self, r):

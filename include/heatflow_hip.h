@@ -443,6 +443,24 @@ int hf_get_csr(hf_ctx* ctx, int32_t* rowptr, int32_t* colidx, double* A, double*
 /* y = A x (which = 0) or y = M x (which = 1) through the SpMV kernel; host vectors. */
 int hf_spmv(hf_ctx* ctx, int32_t which, const double* x, double* y);
 
+/* Value lists: a second, lossless encoding of the values of A and M for the fine-level SpMV kernel.  Per chunk of 512 rows the
+ * distinct 64-bit patterns among the chunk's values (ascending as unsigned integers; 0.0 and -0.0 are two entries) and per nonzero
+ * a 32-bit word cv = 16-bit column position | 16-bit position in the chunk's list << 16, in place of an f64 value and a 16-bit
+ * column position: 4 + 8 (list entries / nnz) instead of 10 bytes per nonzero.  The kernel multiplies the same doubles in the
+ * same order, so every result is bit for bit that of the raw arrays, which stay the source of truth for everything else.
+ * hf_assemble builds the tables on the device after the Dirichlet elimination (not while kappa(T) / rho_c(T) tables are set);
+ * whatever writes A or M later invalidates them until the next hf_assemble.
+ * hf_set_value_lists  mode 0: off; 1 (default): used for a matrix whose lists hold at most nnz / 2 entries (a mesh without
+ *        repeated stencils keeps the raw arrays); 2: used whatever their length.  Effective from the next hf_assemble.  The
+ *        environment variable HEATFLOW_VALUE_LISTS=0|1|2 sets the mode a context starts with.
+ * hf_get_value_lists  which = 0: A, 1: M.  valid: the kernel reads the tables; sum_vlist / max_vlist: entries of all lists / of the
+ *        longest one at the last build; vcap: list entries per chunk the kernel stages in LDS (longer lists are read in place).
+ *        vptr (chunks + 1 values, chunks = ceil(n / 512)), vlist (sum_vlist values) and cv (nnz words) are copied out when not
+ *        NULL; HF_ERR_STATE if one is asked for while the tables are not valid.  Any pointer may be NULL. */
+int hf_set_value_lists(hf_ctx* ctx, int32_t mode);
+int hf_get_value_lists(hf_ctx* ctx, int32_t which, int32_t* valid, int64_t* sum_vlist, int32_t* max_vlist, int32_t* vcap, int32_t* vptr,
+                       double* vlist, uint32_t* cv);
+
 /* Test and diagnosis entry points of the multigrid preconditioner: each runs the production code path on its own, so
  * that a test can compare what the device computes with a restatement of the same algebra (tests/vcycle_oracle.py).
  *   hf_amg_apply           z = B r: one V(1,1) cycle exactly as the single-run PCG applies it (needs hf_set_precond(1, ...)

@@ -11,7 +11,12 @@ rows.sort(key=lambda r: int(r["Start_Timestamp"]))
 
 def short(n):
     m = re.search(r"(k[b]?_[a-z_0-9]+)(<[^>]*>)?", n)
-    return (m.group(1) + (m.group(2) or "")) if m else n[:30]
+    if not m:
+        return n[:30]
+    targs = m.group(2) or ""
+    if m.group(1) == "k_spmv":     # the value-list flag: "vl" where it is on, the name of before where it is off
+        targs = re.sub(r", false>$", ">", re.sub(r", true>$", ", vl>", targs))
+    return m.group(1) + targs
 
 
 names = [short(r["Kernel_Name"]) for r in rows]
@@ -22,7 +27,8 @@ i0, i1 = steps[which]
 t0 = int(rows[i0]["Start_Timestamp"])
 prev_end, busy, gaps = t0, 0, 0.0
 hot = {"k_pcg_update_amg", "k_spmv_vec<64, 0, float>", "k_spmv_row<0, float>", "k_dense_mv_f32", "k_spmv<3, true, double, 8>",
-       "k_spmv<0, true, float, 8>", "k_spmv<0, true, float, 4>", "k_spmv<6, true, float, 4>", "k_spmv<6, true, float, 8>", "k_spmv<4, true, double, 8>", "k_spmv<9, true, double, 8>"}
+       "k_spmv<0, true, float, 8>", "k_spmv<0, true, float, 4>", "k_spmv<6, true, float, 4>", "k_spmv<6, true, float, 8>", "k_spmv<4, true, double, 8>", "k_spmv<9, true, double, 8>",
+       "k_spmv<3, true, double, 8, vl>", "k_spmv<4, true, double, 8, vl>", "k_spmv<9, true, double, 8, vl>"}
 for i in range(i0, i1):
     s, e = int(rows[i]["Start_Timestamp"]), int(rows[i]["End_Timestamp"])
     gap = (s - prev_end) / 1e3
