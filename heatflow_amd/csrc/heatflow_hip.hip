@@ -406,6 +406,7 @@ int batch_alloc(hf_ctx* ctx, hf_ctx::Batch& B, int nv) {
   HF_TRY(dev_alloc(ctx, &B.palpha, static_cast<size_t>(nv) * (PROJ_MT + 1)));
   HF_TRY(dev_alloc(ctx, &B.ppart, static_cast<size_t>(nv) * 2 * PROJ_MT * MAXP));
   HF_HIP(hipMemsetAsync(B.pG, 0, sizeof(double) * nv * PROJ_MT * PROJ_MT, ctx->stream));
+  HF_HIP(hipMemsetAsync(B.palpha, 0, sizeof(double) * nv * (PROJ_MT + 1), ctx->stream));
   B.pnext = 0; B.ppending = -1;
   if (hipHostMalloc(reinterpret_cast<void**>(&B.h_scal), sizeof(Scal) * nv) != hipSuccess) return fail(ctx, HF_ERR_ALLOC, "hipHostMalloc failed");
   if (hipHostMalloc(reinterpret_cast<void**>(&B.h_mirror), sizeof(ScalMirror) * nv, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
@@ -2044,6 +2045,53 @@ int hf_get_value_lists(hf_ctx* ctx, int32_t which, int32_t* valid, int64_t* sum_
     if (vptr) HF_HIP(copy_sync(ctx, vptr, L.vptr, sizeof(int32_t) * (static_cast<size_t>(ctx->nchunks_s) + 1), hipMemcpyDeviceToHost));
     if (vlist) HF_HIP(copy_sync(ctx, vlist, L.vlist, sizeof(double) * static_cast<size_t>(L.sum_vlist), hipMemcpyDeviceToHost));
     if (cv) HF_HIP(copy_sync(ctx, cv, L.cv, sizeof(uint32_t) * static_cast<size_t>(ctx->nnz), hipMemcpyDeviceToHost));
+  }
+  return HF_OK;
+}
+
+// Read-only window on the projection basis of the start vector (kind 3): host code only, no kernel is launched.
+int hf_get_projection(hf_ctx* ctx, int32_t column, int32_t* mh, int32_t* mt, int32_t* used, int32_t* next, int32_t* pending, double* G,
+                      double* alpha, double* V, double* F) {
+  if (mh) *mh = PROJ_MH;
+  if (mt) *mt = PROJ_MT;
+  if (!used && !next && !pending && !G && !alpha && !V && !F) return HF_OK;   // the size query: needs no context
+  if (!ctx) return HF_ERR_ARG;
+  const hf_ctx::Batch& B = ctx->batch;
+  const bool single = column < 0;
+  if (single && !ctx->proj.ready) return fail(ctx, HF_ERR_STATE, "hf_get_projection: no projection basis is allocated yet (no step with start vector 3)");
+  if (!single && B.nv == 0) return fail(ctx, HF_ERR_STATE, "hf_get_projection: no batch is open");
+  if (!single && column >= B.nv) return fail(ctx, HF_ERR_ARG, "hf_get_projection: column %d outside [0,%d)", column, B.nv);
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  const int slots = single ? PROJ_MT : PROJ_MH;
+  const size_t n = static_cast<size_t>(ctx->n);
+  for (int k = 0; k < PROJ_MT; ++k)
+    if (used) used[k] = k < slots && (single ? ctx->proj.used[k] : B.pused[k]) ? 1 : 0;
+  if (next) *next = single ? ctx->proj.next : B.pnext;
+  if (pending) *pending = single ? ctx->proj.pending : B.ppending;
+  if (G)
+    HF_HIP(copy_sync(ctx, G, single ? ctx->proj.G : B.pG + static_cast<size_t>(column) * PROJ_MT * PROJ_MT, sizeof(double) * PROJ_MT * PROJ_MT,
+                     hipMemcpyDeviceToHost));
+  if (alpha)
+    HF_HIP(copy_sync(ctx, alpha, single ? ctx->proj.alpha : B.palpha + static_cast<size_t>(column) * (PROJ_MT + 1), sizeof(double) * (PROJ_MT + 1),
+                     hipMemcpyDeviceToHost));
+  if (V || F) {
+    // slots in use are copied, the others come back as zeros; a batch column is picked out of the interleaved vectors here
+    std::vector<double> wide(single ? 0 : n * B.nv);
+    for (int k = 0; k < PROJ_MT; ++k)
+      for (int s = 0; s < 2; ++s) {
+        double* out = s ? F : V;
+        if (!out) continue;
+        out += static_cast<size_t>(k) * n;
+        const bool on = k < slots && (single ? ctx->proj.used[k] : B.pused[k]);
+        if (!on) { std::fill(out, out + n, 0.0); continue; }
+        if (single) {
+          HF_HIP(copy_sync(ctx, out, s ? ctx->proj.F[k] : ctx->proj.V[k], sizeof(double) * n, hipMemcpyDeviceToHost));
+        } else {
+          HF_HIP(copy_sync(ctx, wide.data(), s ? B.pF[k] : B.pV[k], sizeof(double) * n * B.nv, hipMemcpyDeviceToHost));
+          for (size_t i = 0; i < n; ++i) out[i] = wide[i * B.nv + column];
+        }
+      }
   }
   return HF_OK;
 }

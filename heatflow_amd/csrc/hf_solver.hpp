@@ -640,6 +640,7 @@ int proj_ensure(hf_ctx* ctx) {
   HF_TRY(dev_alloc(ctx, &Q.alpha, PROJ_MT + 1));
   HF_TRY(dev_alloc(ctx, &Q.part, static_cast<size_t>(2) * PROJ_MT * MAXP));
   HF_HIP(hipMemsetAsync(Q.G, 0, sizeof(double) * PROJ_MT * PROJ_MT, ctx->stream));
+  HF_HIP(hipMemsetAsync(Q.alpha, 0, sizeof(double) * (PROJ_MT + 1), ctx->stream));   // hf_get_projection before the first solve: rank 0
   Q.ready = true;
   proj_clear(ctx);
   return HF_OK;

@@ -37,7 +37,7 @@ EXPORTS = [
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
     "hf_tangent_setup", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
-    "hf_set_value_lists", "hf_get_value_lists",
+    "hf_set_value_lists", "hf_get_value_lists", "hf_get_projection",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
 
@@ -151,6 +151,7 @@ def load_library():
         "hf_spmv": [vp, i32, pd, pd],
         "hf_set_value_lists": [vp, i32],
         "hf_get_value_lists": [vp, i32, pi, C.POINTER(i64), pi, pi, pi, pd, C.POINTER(C.c_uint32)],
+        "hf_get_projection": [vp, i32, pi, pi, pi, pi, pi, pd, pd, pd, pd],
         "hf_amg_apply": [vp, pd, pd, pd],
         "hf_batch_apply_precond": [vp, pd, pd, pd],
         "hf_dense_inverse": [vp, i32, pi, pi, pd, pd, pd, pd, pd],
@@ -165,6 +166,16 @@ def load_library():
         fn.restype = C.c_int
     _lib = lib
     return lib
+
+
+def projection_sizes():
+    """(PROJ_MH, PROJ_MT) of the library: solutions kept in the projection ring of the start vector, slots in all (ring +
+    boundary responses).  Needs no device."""
+    mh, mt = C.c_int32(), C.c_int32()
+    rc = load_library().hf_get_projection(None, -1, C.byref(mh), C.byref(mt), None, None, None, None, None, None, None)
+    if rc != HF_OK:
+        raise HipError(rc, "hf_get_projection: size query failed")
+    return mh.value, mt.value
 
 
 def blob_address(blob):
@@ -692,6 +703,28 @@ class HeatflowHIP:
             self._check(self._lib.hf_get_value_lists(self._ctx, int(which), None, None, None, None, _pi(vptr), _pd(vlist),
                                                      cv.ctypes.data_as(C.POINTER(C.c_uint32))))
             out.update(vptr=vptr, vlist=vlist, cv=cv)
+        return out
+
+    # -- start-vector test entry point (tests/test_gpu_start_vector.py) ---------------------------------
+    def projection_sizes(self):
+        return projection_sizes()
+
+    def get_projection(self, column=-1, arrays=False):
+        """The projection basis of the start vector (kind 3): dict(mh, mt, used (mt bools), next, pending, G (mt, mt) by slot,
+        alpha (mt coefficients by slot), rank); with arrays=True also V and F (mt, n), zero rows for slots not in use.
+        column = -1: the basis of step() / run(); column = j: column j of the open batch."""
+        mh, mt = self.projection_sizes()
+        used = np.zeros(mt, dtype=np.int32)
+        nxt, pend = C.c_int32(), C.c_int32()
+        G, alpha = np.empty((mt, mt)), np.empty(mt + 1)
+        V = np.empty((mt, self.n)) if arrays else None
+        F = np.empty((mt, self.n)) if arrays else None
+        self._check(self._lib.hf_get_projection(self._ctx, int(column), None, None, _pi(used), C.byref(nxt), C.byref(pend), _pd(G),
+                                                _pd(alpha), _pd(V), _pd(F)))
+        out = {"mh": mh, "mt": mt, "used": used.astype(bool), "next": nxt.value, "pending": pend.value, "G": G, "alpha": alpha[:mt].copy(),
+               "rank": int(alpha[mt])}                                        # (zero until the first solve: the buffer is cleared when allocated)
+        if arrays:
+            out.update(V=V, F=F)
         return out
 
     # -- preconditioner test entry points (tests/test_gpu_vcycle.py) ------------------------------------

@@ -483,6 +483,22 @@ int hf_batch_apply_precond(hf_ctx* ctx, const double* r, double* z, double* rz);
 int hf_dense_inverse(hf_ctx* ctx, int32_t n, const int32_t* ptr, const int32_t* idx, const double* val, const double* b,
                      double* inv, double* x64, double* x32);
 
+/* Test and diagnosis window on the projection basis of the start vector (hf_set_start_vector kind 3): read-only, host code,
+ * no kernel runs; the stream is synchronised first.  column = -1: the basis of hf_step / hf_run (mt slots: mh ring slots, then
+ * the boundary responses); column = j >= 0: column j of the open batch (mh ring slots, the others are reported unused).
+ *   mh, mt        solutions kept in the ring, slots in all.  With every other pointer NULL the call is a size query and
+ *                 needs neither a basis nor a context (ctx may be NULL).
+ *   used[mt]      1 for a slot that holds a pair; next: the ring slot the next solution overwrites; pending: the slot stored
+ *                 after the last step, whose Gram column the next step writes (-1: none).
+ *   G[mt * mt]    the Gram matrix by slot, G[k * mt + l] = V_k . F_l; entries of slots not in use, and the column of the
+ *                 pending slot, are whatever an earlier step left.
+ *   alpha[mt + 1] the coefficients of the last solve by slot, then the rank it kept (all zero before the first solve).
+ *   V, F          mt x n, row-major: the stored solutions (Dirichlet entries zeroed) and their right-hand sides; rows of
+ *                 slots not in use come back zero.
+ * Any pointer may be NULL.  HF_ERR_STATE while no basis is allocated (no step with kind 3 yet) or no batch is open. */
+int hf_get_projection(hf_ctx* ctx, int32_t column, int32_t* mh, int32_t* mt, int32_t* used, int32_t* next, int32_t* pending, double* G,
+                      double* alpha, double* V, double* F);
+
 /* Average duration (ms) of `reps` back-to-back launches of one kernel on the ctx stream,
  * bracketed by HIP events on that stream. */
 int hf_time_kernel(hf_ctx* ctx, int32_t which, int32_t reps, double* ms_avg);

@@ -813,7 +813,11 @@ def test_start_vector_kinds_same_answer_fewer_iterations(hip, precond, case_with
     correction (kind 2) costs one extra solve per operator (the heated line's profile is the only direction
     the second difference of the boundary values ever has) and needs fewer iterations than plain
     extrapolation (kind 1), which needs fewer than starting from u^n (kind 0); the A-norm projection on the last
-    solutions and that response (kind 3, the default) contains both as special cases and needs fewest."""
+    solutions and that response (kind 3, the default) contains both as special cases and needs fewest.
+
+    This test sees the start vectors only through iteration totals.  Whether the projected start vector is the right one - the
+    ring's bookkeeping, the Gram matrix, the small solve, the combination, for every kind - is checked in tests/test_gpu_start_vector.py against
+    tests/start_vector_oracle.py, which tests/test_start_vector_oracle_cpu.py judges first."""
     cfg, stack, mesh = case_with_diamond_small
     nsteps = 40
     out = {}
