@@ -6,7 +6,9 @@ absolute values, so that everything that scales a material's ``k`` (kappa sweeps
 meaning: both directions scale and the ratio stays.
 
 Not combined with the temperature-dependent keys (k_table, k_power, cv_table, cv_einstein) in one configuration - the table
-kernels are isotropic - nor with a fit or tangent on the anisotropic material itself, nor with the 1-D model.
+kernels are isotropic - nor with the 1-D model.  Tangents and fits name the directional conductivities of a material as
+``<material>.k_r`` and ``<material>.k_z`` (absolute, W/m/K) and its scalar as ``<material>.k`` (both directions, the ratio kept;
+DESIGN.md 3.13); the bare name of an anisotropic material stays refused there.
 """
 from __future__ import annotations
 
@@ -40,6 +42,20 @@ def material_aniso(name, mat):
     return out[0], out[1]
 
 
+PARAM_KINDS = {"k": "k", "k_r": "r", "k_z": "z"}     # suffix of a tangent / fit parameter -> column kind of run_tangent
+
+
+def split_param(name):
+    """("<material>", "k" | "r" | "z") of a parameter spelt ``<material>.k``, ``<material>.k_r`` or ``<material>.k_z``;
+    (name, None) for a name without a dot.  ValueError naming the parameter for any other suffix."""
+    if "." not in name:
+        return name, None
+    mat, suffix = name.rsplit(".", 1)
+    if suffix not in PARAM_KINDS:
+        raise ValueError(f"parameter {name!r}: unknown suffix {suffix!r} (<material>.k, <material>.k_r or <material>.k_z)")
+    return mat, PARAM_KINDS[suffix]
+
+
 def aniso_keys(cfg, names=None):
     """['mats.<name>.k_aniso', ...] of the materials of ``cfg`` (of ``names`` only, when given) that carry the key."""
     return [f"mats.{name}.{KEY}" for name, mat in sorted((cfg.get("mats") or {}).items())
@@ -62,9 +78,13 @@ def check_config(cfg):
     return out
 
 
-def refuse_aniso(cfg, where, names=None):
+DIRECTIONAL_HINT = ("; name the directional conductivities <material>.k_r / <material>.k_z, or the scalar <material>.k of both "
+                    "directions, instead")
+
+
+def refuse_aniso(cfg, where, names=None, hint=""):
     """ValueError naming the keys if ``cfg`` (its materials ``names`` only, when given) asks for an anisotropic conductivity:
-    ``where`` does not support it."""
+    ``where`` does not support it.  ``hint`` is appended to the message."""
     keys = aniso_keys(cfg, names)
     if keys:
-        raise ValueError(f"{where} does not support anisotropic conductivities ({', '.join(keys)})")
+        raise ValueError(f"{where} does not support anisotropic conductivities ({', '.join(keys)}){hint}")

@@ -82,7 +82,7 @@ void load_free(hf_ctx* ctx) {
 
 void tangent_free(hf_ctx* ctx) {
   free_batch_state(ctx->tanb);
-  dev_free(&ctx->tan.col); dev_free(&ctx->tan.F);
+  dev_free(&ctx->tan.col); dev_free(&ctx->tan.dir); dev_free(&ctx->tan.F);
   ctx->tan = hf_ctx::Tangent();
 }
 
@@ -556,7 +556,7 @@ int tangent_levels(hf_ctx* ctx) {
   return HF_OK;
 }
 
-// F = -K_j u for every tangent column j, from the context's current state
+// F = -K_j u for every tangent column j, from the context's current state, by the kernel of the set-up in force
 int tangent_load(hf_ctx* ctx) {
   const int capd = ctx->rg_max_dict;
   const size_t sm = static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 + (RBA + 4) * 4 +
@@ -565,12 +565,25 @@ int tangent_load(hf_ctx* ctx) {
 #define HF_TL(NV) hipLaunchKernelGGL(k_tangent_load<NV>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr, \
                                      reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), \
                                      ctx->d_rg_zrb, ctx->d_rg_dict, ctx->d_rowptr, ctx->tan.col, ctx->d_u, ctx->tan.F)
-  switch (ctx->tan.nv) {
-    case 2: HF_TL(2); break;
-    case 4: HF_TL(4); break;
-    case 8: HF_TL(8); break;
-    default: HF_TL(16); break;
+#define HF_TLD(NV) hipLaunchKernelGGL(k_tangent_load_dir<NV>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr, \
+                                      reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), \
+                                      ctx->d_rg_zrb, ctx->d_rg_dict, ctx->d_rowptr, ctx->tan.dir, ctx->d_u, ctx->tan.F)
+  if (ctx->tan.dir) {      // hf_tangent_setup_dir
+    switch (ctx->tan.nv) {
+      case 2: HF_TLD(2); break;
+      case 4: HF_TLD(4); break;
+      case 8: HF_TLD(8); break;
+      default: HF_TLD(16); break;
+    }
+  } else {
+    switch (ctx->tan.nv) {
+      case 2: HF_TL(2); break;
+      case 4: HF_TL(4); break;
+      case 8: HF_TL(8); break;
+      default: HF_TL(16); break;
+    }
   }
+#undef HF_TLD
 #undef HF_TL
   HF_HIP(hipGetLastError());
   return HF_OK;
@@ -775,6 +788,7 @@ int hf_set_anisotropy(hf_ctx* ctx, int32_t n, const int32_t* tags, const double*
     HF_HIP(copy_sync(ctx, ctx->an.d_m, m.data(), sizeof(double2) * 64, hipMemcpyHostToDevice));
     ctx->an.h_tag = std::move(aniso);
     ctx->an.hash = fnv1a(by_tag.data(), sizeof(double) * by_tag.size());
+    ctx->an.h_m = std::move(by_tag);
     ctx->an.on = true;
   } else {
     an_free(ctx);
@@ -783,7 +797,8 @@ int hf_set_anisotropy(hf_ctx* ctx, int32_t n, const int32_t* tags, const double*
   ctx->assembled = false;
   ctx->pred_iters = 0;
   ctx->steady.ready = false;   // K depends on the multipliers: hf_steady_setup again
-  // the tangent columns were checked against the old set of anisotropic tags: hf_tangent_setup again
+  // the tangent columns were checked against the old set of anisotropic tags, and a directional set-up took its kappa columns'
+  // weights from the old multipliers: hf_tangent_setup / hf_tangent_setup_dir again
   const bool from_steady = ctx->tan.steady_state;
   tangent_free(ctx);
   ctx->tan.steady_state = from_steady;
@@ -1402,6 +1417,73 @@ int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
   ctx->tan.npar = n_par;
   ctx->tan.nv = nv;
   ctx->tan.ready = true;
+  return HF_OK;
+}
+
+int hf_tangent_setup_dir(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col_k, const int32_t* tag_col_r, const int32_t* tag_col_z) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir before hf_set_mesh");
+  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: %s tables are set (tangents of the nonlinear loop are not supported)", kt_kind(ctx));
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a batch is open");
+  if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a load is set (tangents of pre-heated runs are not supported)");
+  if (n_par < 1 || n_par > NV_MAX) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: 1..%d parameters (got %d)", NV_MAX, n_par);
+  if (!tag_col_k && !tag_col_r && !tag_col_z) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: tag_col_k, tag_col_r and tag_col_z are all null");
+  const int32_t* tabs[3] = {tag_col_k, tag_col_r, tag_col_z};
+  const char* names[3] = {"kappa", "k_r", "k_z"};
+  for (int t = 0; t < ctx->tab_len; ++t) {
+    for (int q = 0; q < 3; ++q) {
+      const int32_t c = tabs[q] ? tabs[q][t] : -1;
+      if (c < -1 || c >= n_par)
+        return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: tag %d maps its %s to column %d outside [-1,%d)", t, names[q], c, n_par);
+      if (c >= 0 && !ctx->h_tag_used[t]) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: tag %d is not a cell tag of the mesh", t);
+    }
+    if (tag_col_k && tag_col_k[t] >= 0 && ((tag_col_r && tag_col_r[t] >= 0) || (tag_col_z && tag_col_z[t] >= 0)))
+      return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: tag %d has a kappa column and a directional one (k_r = m_r kappa and k_z = m_z kappa are not independent of kappa)", t);
+  }
+  if (!ctx->rg_ok || (ctx->assembled && ctx->mode != HF_ASM_ROW_GATHER))
+    return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: tangent loads are formed by the row-gather kernel only (HF_ASM_ROW_GATHER on a mesh with row-gather lists)");
+  HF_HIP(hipSetDevice(ctx->dev));
+  const bool from_steady = ctx->tan.steady_state;
+  tangent_free(ctx);
+  ctx->tan.steady_state = from_steady;
+  const int nv = n_par <= 2 ? 2 : n_par <= 4 ? 4 : n_par <= 8 ? 8 : 16;
+  std::vector<TanDir> dir(64, TanDir{-1, -1, 0.0, 0.0});    // by row-gather tag-dictionary index, as the coefficient tables of the kernel
+  for (size_t q = 0; q < ctx->h_rg_tags.size() && q < 64; ++q) {
+    const int32_t t = ctx->h_rg_tags[q];
+    TanDir& d = dir[q];
+    if (tag_col_k && tag_col_k[t] >= 0) {     // kappa: both directions into one column, weighted by the multipliers in force
+      const bool an = ctx->an.on && ctx->an.h_tag[t];
+      d = TanDir{tag_col_k[t], tag_col_k[t], an ? ctx->an.h_m[2 * t + 1] : 1.0, an ? ctx->an.h_m[2 * t] : 1.0};
+    } else {
+      if (tag_col_r && tag_col_r[t] >= 0) { d.c_r = tag_col_r[t]; d.w_r = 1.0; }
+      if (tag_col_z && tag_col_z[t] >= 0) { d.c_z = tag_col_z[t]; d.w_z = 1.0; }
+    }
+  }
+  hf_ctx::Batch& T = ctx->tanb;
+  T.opk = HF_BATCH_SHARED;
+  HF_TRY(batch_alloc(ctx, T, nv));
+  HF_TRY(dev_alloc(ctx, &ctx->tan.dir, 64));
+  HF_TRY(dev_alloc(ctx, &ctx->tan.F, static_cast<size_t>(ctx->n) * nv));
+  HF_HIP(copy_sync(ctx, ctx->tan.dir, dir.data(), sizeof(TanDir) * 64, hipMemcpyHostToDevice));
+  T.nv = nv;
+  T.bdf_hist = false;
+  T.load = ctx->tan.F;
+  ctx->tan.npar = n_par;
+  ctx->tan.nv = nv;
+  ctx->tan.ready = true;
+  return HF_OK;
+}
+
+int hf_tangent_load(hf_ctx* ctx, int32_t j, double* F) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_tangent_load before hf_tangent_setup / hf_tangent_setup_dir");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_load: a batch is open");
+  if (j < 0 || j >= ctx->tan.nv || !F) return fail(ctx, HF_ERR_ARG, "hf_tangent_load: column %d outside [0,%d) or null pointer", j, ctx->tan.nv);
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_TRY(tangent_load(ctx));
+  hipLaunchKernelGGL(kb_get_column, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->n), ctx->tan.nv, j, ctx->tan.F, ctx->d_tmp);
+  HF_HIP(hipGetLastError());
+  HF_HIP(copy_sync(ctx, F, ctx->d_tmp, sizeof(double) * ctx->n, hipMemcpyDeviceToHost));
   return HF_OK;
 }
 

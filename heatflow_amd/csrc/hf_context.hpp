@@ -100,6 +100,11 @@ constexpr int KT_MAX_KNOTS = 256;
 constexpr int KT_MAX_PICARD = 8;
 struct KTab { double t0, inv_dt; int n, off; };
 
+// Directional tangent loads (hf_tangent_setup_dir): per tag-dictionary index the destination columns of the tag's radial and
+// axial stiffness products (-1 = none) and their weights.  A column of k_r has (c, -1, 1, .), one of k_z (-1, c, ., 1), one of
+// kappa (c, c, m_r, m_z): d/dkappa of k_r K^r + k_z K^z with k_r = m_r kappa, k_z = m_z kappa.
+struct TanDir { int32_t c_r, c_z; double w_r, w_z; };
+
 // The row-gather assembly kernels: k_assemble_rows<false / true>, k_assemble_rows_an<false / true>, k_assemble_rows_kT,
 // k_assemble_rows_cT, k_assemble_rows_kT_K
 enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_VARIANTS };
@@ -184,6 +189,7 @@ struct hf_ctx {
     bool on = false;
     double2* d_m = nullptr;
     std::vector<char> h_tag;
+    std::vector<double> h_m;    // (m_z, m_r) by cell tag, 1 where isotropic: the weights of a kappa column (hf_tangent_setup_dir)
     uint64_t hash = 0;          // of the multipliers by cell tag (0 while off): part of the operator's fingerprint (OperatorPrint)
   } an;
   // device: matrices
@@ -337,12 +343,14 @@ struct hf_ctx {
   Batch fluxnb;                  // nv-column state of the batched loop's read-flux projection (hf_batch_run_flux): one gradient component of every column per PCG
   int32_t* d_fsamp_idx = nullptr;   // its sample nodes
   // tangent runs (hf_tangent_setup / hf_run_tangent): nv tangent columns s_j = du/dtheta_j in their own batch state, swapped
-  // into `batch` for the tangent stage of every step; their load F_j = -K_j u^{n+1} (k_tangent_load)
+  // into `batch` for the tangent stage of every step; their load F_j = -K_j u^{n+1} (k_tangent_load, or
+  // k_tangent_load_dir under hf_tangent_setup_dir)
   Batch tanb;
   struct Tangent {
     bool ready = false;
     int npar = 0, nv = 0;
     int32_t* col = nullptr;      // tangent column of each row-gather tag-dictionary entry (64), -1 = none
+    TanDir* dir = nullptr;       // hf_tangent_setup_dir: columns and weights per direction instead (64; k_tangent_load_dir), col stays null
     double* F = nullptr;         // n x nv, interleaved
     bool steady_state = false;   // the state comes from hf_steady_solve (it depends on kappa; s^0 = 0 would be wrong) until hf_set_state
     std::vector<int64_t> lev_sig;   // multigrid level sizes tanb.lev was laid out for

@@ -611,6 +611,99 @@ __global__ __launch_bounds__(RBA) void k_tangent_load(int nblk, int capd, const 
   }
 }
 
+// (K^r u)_me and (K^z u)_me of one element visit at unit conductivities, in the letters of element_row_of:
+// K^r_ab = ks (e_a.x e_b.x), K^z_ab = ks (e_a.y e_b.y), ks = area (rsum / 3) / d^2 - one division, as there.
+struct DirKu { double r, z; };
+__device__ __forceinline__ DirKu element_dir_ku(const double2 Pi, const double2 Pj, const double2 Pk, double ui, double uj, double uk) {
+#pragma clang fp contract(off)
+  const double eix = Pk.x - Pj.x, eiy = Pk.y - Pj.y;     // edge opposite "me"
+  const double ejx = Pi.x - Pk.x, ejy = Pi.y - Pk.y;     // opposite next
+  const double ekx = Pj.x - Pi.x, eky = Pj.y - Pi.y;     // opposite previous
+  const double c1 = fabs(ejx * eky - ejy * ekx), c2 = fabs(ekx * eiy - eky * eix), c3 = fabs(eix * ejy - eiy * ejx);
+  const double d = fmax(fmax(c1, c2), c3);
+  const double rsum = sorted_sum3(Pi.y, Pj.y, Pk.y);
+  const double area = 0.5 * d;
+  const double ks = area * (rsum * (1.0 / 3.0)) * (1.0 / (d * d));
+  DirKu o;
+  o.r = ks * ((eix * eix) * ui + (eix * ejx) * uj) + ks * ((eix * ekx) * uk);
+  o.z = ks * ((eiy * eiy) * ui + (eiy * ejy) * uj) + ks * ((eiy * eky) * uk);
+  return o;
+}
+
+// k_tangent_load's sibling for columns in k_r and k_z of anisotropic materials (same lists, staging, LDS carve-up and launch
+// geometry): F[i * NV + j] = -sum over the triangles e at node i of (w_r (K_e^r u)_i if c_r(tag) = j) + (w_z (K_e^z u)_i if
+// c_z(tag) = j), the table `dir` by tag-dictionary index in static LDS.  A visit whose tag has c_r == c_z and w_r == w_z is the
+// isotropic product of k_tangent_load times w, so a set-up of kappa columns on tags with multipliers (1, 1) gives its bits.
+// Each column's sum runs in list order in a register of the row's lane - no atomics, bitwise reproducible; columns nothing maps
+// to are written as zeros.
+template <int NV>
+__global__ __launch_bounds__(RBA) void k_tangent_load_dir(int nblk, int capd, const int4* __restrict__ hdr, const uint4* __restrict__ ell,
+                                                          const uint4* __restrict__ cid16, const double2* __restrict__ zrb,
+                                                          const int32_t* __restrict__ dict, const int32_t* __restrict__ rowptr,
+                                                          const TanDir* __restrict__ dir, const double* __restrict__ u,
+                                                          double* __restrict__ F) {
+  extern __shared__ double smem[];
+  __shared__ TanDir sdir[64];
+  double2* sXd = reinterpret_cast<double2*>(smem);
+  double* sU = smem + 2 * capd;
+  int* sR = reinterpret_cast<int*>(sU + capd + (capd & 1));
+  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);
+  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
+  const int t = threadIdx.x;
+  if (t < 64) sdir[t] = dir[t];
+  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const int4 cA = hdr[2 * blk], cB = hdr[2 * blk + 1];
+    const int c0 = cA.x >> 3, nc = ((cA.x + cA.y + 7) >> 3) - c0;
+    for (int i = t; i < nc; i += RBA) sC4[i] = cid16[c0 + i];
+    for (int i = t; i < cA.w; i += RBA) { sXd[i] = zrb[cA.z + i]; sU[i] = u[dict[cA.z + i]]; }
+    if (t < cB.w) sR[t] = rowptr[blk * RBA + t] - cA.x;
+    __syncthreads();
+    if (t < cB.w) {
+#pragma clang fp contract(off)
+      const int sbase = sR[t] + (cA.x & 7);
+      const int ci = cB.z + t;
+      const double2 Pi = sXd[ci];
+      const double ui = sU[ci];
+      double acc[NV];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+      for (int g = 0; g < cB.y; ++g) {
+        const uint4 ev = ell[cB.x + g * RBA + t];
+        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
+          if (e == 0xFFFFu) continue;
+          const TanDir td = sdir[e >> 10];
+          if (td.c_r < 0 && td.c_z < 0) continue;
+          const int pj = sC[sbase + (e & 31u)], pk = sC[sbase + ((e >> 5) & 31u)];
+          int cr = td.c_r, cz = td.c_z;
+          double ar, az;
+          if (cr == cz && td.w_r == td.w_z) {
+            const ElemRow r = element_row(Pi, sXd[pj], sXd[pk], 0.0, 1.0);
+            ar = td.w_r * ((r.k0 * ui + r.k1 * sU[pj]) + r.k2 * sU[pk]);
+            az = 0.0;
+            cz = -1;
+          } else {
+            const DirKu k = element_dir_ku(Pi, sXd[pj], sXd[pk], ui, sU[pj], sU[pk]);
+            ar = td.w_r * k.r;
+            az = td.w_z * k.z;
+          }
+#pragma unroll
+          for (int j = 0; j < NV; ++j) {
+            if (j == cr) acc[j] += ar;
+            if (j == cz) acc[j] += az;
+          }
+        }
+      }
+      double* out = F + static_cast<size_t>(blk * RBA + t) * NV;
+#pragma unroll
+      for (int j = 0; j < NV; ++j) out[j] = -acc[j];
+    }
+    __syncthreads();
+  }
+}
+
 // kappa(T) of one table (KTab): s = (T - t0) / dT, clamped to the end values, else v_i + (s - i) (v_{i+1} - v_i), i = floor(s)
 __device__ __forceinline__ double ktab_eval(const KTab h, const double* __restrict__ vals, double T) {
 #pragma clang fp contract(off)

@@ -42,7 +42,7 @@ def _dump_yaml(obj, f):
 from .bc import P1Space, RowDirichletBC
 from .geometry import stack_no_diamond, stack_with_diamond
 from .heating import HeatingCurve
-from .aniso import check_config, refuse_aniso
+from .aniso import DIRECTIONAL_HINT, check_config, refuse_aniso, split_param
 from .kappa_t import material_cv_table, material_table, picard_sweeps, refuse_tables
 from .mesh import Mesh, load_mesh_arrays
 from .solver import DEFAULT_MAX_IT, DEFAULT_RTOL, HeatProblem
@@ -472,7 +472,9 @@ class SimulationSession:
         ``times``, ``watchers`` {name: array}, ``iters``, timing numbers.  ``read_flux`` adds the
         per-step gradient projection of run_no_diamond.py:543-566 (``flux`` entry of the result).
         ``tangents`` = parameter names (material names - the derivative with respect to that material's conductivity
-        k - and / or "fwhm" of the heating profile) adds ``tangents`` {param: {watcher: d watcher / d param}} and
+        k -, "<material>.k_r" / "<material>.k_z" / "<material>.k" - its radial, its axial conductivity in W/m/K, or the
+        scalar k of both with the ratio of ``k_aniso`` kept; on isotropic materials the derivatives at m = (1, 1) -, and / or
+        "fwhm" of the heating profile) adds ``tangents`` {param: {watcher: d watcher / d param}} and
         ``tangent_iters`` (HeatProblem.run_tangent; not with a field sink or the flux projection)."""
         t_start = time.time()
         t_final = float(cfg["timing"]["t_final"])
@@ -487,8 +489,9 @@ class SimulationSession:
         if kt is not None and tangents:
             refuse_tables(cfg, "tangents")
         an = self._aniso(stack)
-        if an and tangents:      # the derivative with respect to an anisotropic material's k is a follow-up; others work
-            refuse_aniso(cfg, "a tangent with respect to the conductivity of an anisotropic material", set(tangents))
+        if an and tangents:      # a bare name means the isotropic k: an anisotropic material is named by direction
+            refuse_aniso(cfg, "a tangent with respect to the conductivity of an anisotropic material", set(tangents),
+                         DIRECTIONAL_HINT)
         key = self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an)
         fresh = self.problem is None or key != self._key
         self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme, kt, an)
@@ -518,7 +521,14 @@ class SimulationSession:
                 elif p in self.material_tags:
                     cond.append([self.material_tags[p]])
                 else:
-                    raise ValueError(f"tangents: unknown parameter {p!r} (a material name or 'fwhm')")
+                    try:
+                        mat, kind = split_param(p)
+                    except ValueError as e:
+                        raise ValueError(f"tangents: {e}") from None
+                    if kind is None or mat not in self.material_tags:
+                        raise ValueError(f"tangents: unknown parameter {p!r} (a material name, <material>.k_r, "
+                                         "<material>.k_z, <material>.k or 'fwhm')")
+                    cond.append([(self.material_tags[mat], kind)])
             times, samples, tsamp, iters, titers = prob.run_tangent(num_steps, nodes, conductivity=cond, boundary=bnd,
                                                                     time_varying=varying)
             tangent_out = {p: {nm: tsamp[:, j, k] for k, nm in enumerate(names)} for j, p in enumerate(params)}

@@ -20,25 +20,50 @@ import time
 import numpy as np
 
 from .parameter_sweep import build_stack, get_watcher_points, oside_curves
-from .aniso import refuse_aniso
+from .aniso import DIRECTIONAL_HINT, KEY, material_aniso, refuse_aniso, split_param
 from .kappa_t import refuse_tables
 
 DEFAULT_EXP_CSV = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "experimental_data",
                                "geballe_heat_data.csv")
 
 
+def _material_param(cfg, name):
+    """(material block, None | "k" | "r" | "z") of a parameter name; ValueError naming it for an unknown material or suffix."""
+    mat, kind = split_param(name)
+    if mat not in cfg["mats"]:
+        raise ValueError(f"parameter {name!r}: no material {mat!r} in the configuration")
+    return cfg["mats"][mat], kind
+
+
 def get_param(cfg, name):
-    return float(cfg["heating"]["fwhm"]) if name == "fwhm" else float(cfg["mats"][name]["k"])
+    """The value of a parameter: "fwhm", a material's k ("<m>" or "<m>.k"), or its directional conductivity "<m>.k_r" =
+    k * k_aniso.r / "<m>.k_z" = k * k_aniso.z in W/m/K (multiplier 1 where the block or the key is absent)."""
+    if name == "fwhm":
+        return float(cfg["heating"]["fwhm"])
+    mat, kind = _material_param(cfg, name)
+    if kind in (None, "k"):
+        return float(mat["k"])
+    m = material_aniso(name.rsplit(".", 1)[0], mat) or (1.0, 1.0)
+    return float(mat["k"]) * m[0 if kind == "r" else 1]
 
 
 def set_params(cfg, params, values):
-    """A copy of ``cfg`` with the parameters set: "fwhm" of the heating profile, else the conductivity k of a material."""
+    """A copy of ``cfg`` with the parameters set: "fwhm" of the heating profile, the conductivity k of a material ("<m>" or
+    "<m>.k"; the multipliers of a ``k_aniso`` block stay), or a directional conductivity: "<m>.k_r" writes k_aniso.r = value / k,
+    "<m>.k_z" k_aniso.z, creating the block where absent.  The k parameters are applied first, so a directional value holds
+    whatever the order of the names."""
     c = copy.deepcopy(cfg)
-    for name, v in zip(params, values):
+    pairs = list(zip(params, values))
+    for name, v in pairs:
         if name == "fwhm":
             c["heating"]["fwhm"] = float(v)
-        else:
-            c["mats"][name]["k"] = float(v)
+        elif _material_param(c, name)[1] in (None, "k"):
+            _material_param(c, name)[0]["k"] = float(v)
+    for name, v in pairs:
+        if name != "fwhm":
+            mat, kind = _material_param(c, name)
+            if kind in ("r", "z"):
+                mat.setdefault(KEY, {})[kind] = float(v) / float(mat["k"])
     return c
 
 
@@ -68,7 +93,8 @@ def residual_and_jacobian(res, params, exp, ic_temp):
 def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_CSV, x0=None, max_iter=20, *, xtol=1e-9,
                    ftol=1e-10, session=None, backend=None, device_id=0, rtol=1e-10, mesh=None, rebuild_mesh=None,
                    verbose=False):
-    """Levenberg-Marquardt fit of ``params`` (material names and / or "fwhm") to the experiment's o-side curve.
+    """Levenberg-Marquardt fit of ``params`` (material names, "<material>.k_r" / "<material>.k_z" / "<material>.k" - see
+    :func:`get_param` - and / or "fwhm") to the experiment's o-side curve.
     ``x0`` = start values (default: the configuration's).  ``session`` / ``backend`` / ``mesh`` = (coords, tris, tags,
     tag_map) reuse what the caller has; otherwise the mesh is loaded from ``mesh_folder``, or built there (``rebuild_mesh``
     True, or None and the folder holds no mesh).  A trial step costs one primal run; only an accepted step is followed by a
@@ -81,7 +107,10 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     scheme = time_scheme(cfg)
     refuse_tables(cfg, "heatflow_amd.fit")
     params = tuple(params)
-    refuse_aniso(cfg, "heatflow_amd.fit of the conductivity of an anisotropic material", set(params))
+    refuse_aniso(cfg, "heatflow_amd.fit of the conductivity of an anisotropic material", set(params), DIRECTIONAL_HINT)
+    for p in params:
+        if p != "fwhm":
+            _material_param(cfg, p)      # an unknown material or suffix, before any mesh or session is made
     exp = load_experiment(exp_csv)
     ic = float(cfg["heating"]["ic_temp"])
     stack = build_stack(cfg)
@@ -164,7 +193,7 @@ def main(argv=None, backend=None):
 
     ap = argparse.ArgumentParser(description="Fit conductivities (and fwhm) to the experimental o-side curve with tangent runs")
     ap.add_argument("--config", required=True)
-    ap.add_argument("--params", nargs="+", default=["p_sample"], help="material names and / or fwhm")
+    ap.add_argument("--params", nargs="+", default=["p_sample"], help="material names, <material>.k_r, <material>.k_z, <material>.k and / or fwhm")
     ap.add_argument("--exp-csv", default=DEFAULT_EXP_CSV)
     ap.add_argument("--mesh-folder", default=None,
                     help="mesh.msh + mesh_cfg.yaml to use; built there when absent (default: <output-dir>/mesh)")
@@ -187,6 +216,10 @@ def main(argv=None, backend=None):
     out["config"] = a.config
     with open(os.path.join(a.output_dir, "fit_summary.json"), "w") as f:
         json.dump(out, f, indent=2)
+    from .driver import _dump_yaml, _with_scheme
+
+    with open(os.path.join(a.output_dir, "used_config.yaml"), "w") as f:     # the configuration at the fitted values
+        _dump_yaml(_with_scheme(set_params(cfg, out["params"], out["values"])), f)
     print(json.dumps({k: out[k] for k in ("params", "values", "stderr", "rmse", "converged", "iterations", "runs", "seconds", "scheme")}))
     return 0
 

@@ -36,7 +36,7 @@ EXPORTS = [
     "hf_batch_begin", "hf_batch_load_column", "hf_batch_set_affine", "hf_batch_set_state", "hf_batch_get_state", "hf_batch_run", "hf_batch_run_flux", "hf_batch_end",
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
-    "hf_tangent_setup", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
+    "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
     "hf_set_value_lists", "hf_get_value_lists", "hf_get_projection",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
@@ -139,6 +139,8 @@ def load_library():
         "hf_get_load": [vp, pd],
         "hf_hold_load": [vp],
         "hf_tangent_setup": [vp, i32, pi],
+        "hf_tangent_setup_dir": [vp, i32, pi, pi, pi],
+        "hf_tangent_load": [vp, i32, pd],
         "hf_run_tangent": [vp, i32, pd, pd, dbl, dbl, i32, i32, pi, pd, pi, pd, pi],
         "hf_get_tangent": [vp, i32, pd],
         "hf_set_kappa_tables": [vp, i32, pi, pd, pd, pi, pd, i32],
@@ -417,6 +419,32 @@ class HeatflowHIP:
         self.tangent_nv = 0
         self._check(self._lib.hf_tangent_setup(self._ctx, int(n_par), _pi(tab)))
         self.tangent_nv = next(v for v in (2, 4, 8, 16) if v >= int(n_par))
+
+    def tangent_setup_dir(self, n_par, k=None, r=None, z=None):
+        """``n_par`` tangent columns as :meth:`tangent_setup`, in the directional conductivities (hf_tangent_setup_dir, DESIGN.md
+        3.13): ``k`` = {cell tag: column} for the tags whose kappa a column is (both directions, the ratio of k_aniso kept),
+        ``r`` / ``z`` = the same for the absolute k_r / k_z of a tag.  Isotropic and anisotropic tags alike."""
+        tabs = []
+        for name, m in (("k", k), ("r", r), ("z", z)):
+            if not m:
+                tabs.append(None)
+                continue
+            tab = np.full(self.tab_len, -1, dtype=np.int32)
+            for t, j in dict(m).items():
+                if not 0 <= int(t) < self.tab_len:
+                    raise ValueError(f"tangent_setup_dir: tag {t} ({name}) is not a cell tag of the mesh")
+                tab[int(t)] = int(j)
+            tabs.append(tab)
+        self.tangent_nv = 0
+        self._check(self._lib.hf_tangent_setup_dir(self._ctx, int(n_par), *(None if t is None else _pi(t) for t in tabs)))
+        self.tangent_nv = next(v for v in (2, 4, 8, 16) if v >= int(n_par))
+
+    def tangent_load(self, j):
+        """Column j of the tangent loads F = -K_j u at the current state, by the set-up in force (hf_tangent_load; tests and
+        diagnostics)."""
+        F = np.empty(self.n, dtype=np.float64)
+        self._check(self._lib.hf_tangent_load(self._ctx, int(j), _pd(F)))
+        return F
 
     def run_tangent(self, g_all, h_all=None, rtol=1e-10, atol=0.0, max_it=20000, nodes=None):
         """hf_run plus the tangents.  g_all (n_steps, n_bc); h_all (n_steps, n_bc, nv) or None (all zero).  Returns the

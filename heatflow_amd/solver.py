@@ -173,7 +173,10 @@ class HeatProblem:
 
     def run_tangent(self, num_steps, watcher_nodes, conductivity=(), boundary=None, time_varying=None, first_step=0):
         """:meth:`run` plus the derivatives of the watcher curves with respect to parameters theta_j (hf_run_tangent,
-        DESIGN.md 3.7).  Column j of ``conductivity`` = the cell tags whose conductivity theta_j is (they move together);
+        DESIGN.md 3.7).  Column j of ``conductivity`` = the cell tags whose conductivity theta_j is (they move together).  An
+        entry may also be a pair ``(tag, "k" | "r" | "z")``: the tag's kappa (both directions of an anisotropic
+        tag, their ratio kept), its k_r or its k_z in W/m/K; one tag may give its k_r to one column and its k_z to another.  Plain
+        tags only make the set-up of before (hf_tangent_setup, which refuses anisotropic tags), any pair hf_tangent_setup_dir;
         ``boundary`` = {column: {bc index: dg/dtheta_j callable (x, y, t)}} for parameters that enter the Dirichlet values
         (e.g. ``HeatingCurve.gaussian_dfwhm`` on the heated line).  A column may be both.  The derivatives are tabulated
         exactly as :meth:`run` tabulates g.  The first call after a set-up starts every tangent at zero, later calls
@@ -186,15 +189,34 @@ class HeatProblem:
         n_par = max([len(conductivity)] + [j + 1 for j in boundary])
         if n_par == 0:
             raise ValueError("run_tangent: no parameter (conductivity or boundary) given")
-        tag_col = {}
-        for j, tags in enumerate(conductivity):
-            for t in tags:
-                if int(t) in tag_col:
-                    raise ValueError(f"run_tangent: cell tag {t} is listed in two conductivity columns")
-                tag_col[int(t)] = j
-        spec = (n_par, tuple(sorted(tag_col.items())))
+        directional = any(isinstance(t, (tuple, list)) for tags in conductivity for t in tags)
+        if not directional:
+            tag_col = {}
+            for j, tags in enumerate(conductivity):
+                for t in tags:
+                    if int(t) in tag_col:
+                        raise ValueError(f"run_tangent: cell tag {t} is listed in two conductivity columns")
+                    tag_col[int(t)] = j
+            spec = (n_par, tuple(sorted(tag_col.items())))
+        else:
+            cols = {"k": {}, "r": {}, "z": {}}
+            for j, tags in enumerate(conductivity):
+                for t in tags:
+                    t, kind = (t[0], str(t[1])) if isinstance(t, (tuple, list)) else (t, "k")
+                    if kind not in cols:
+                        raise ValueError(f"run_tangent: cell tag {t}: unknown kind {kind!r} ('k', 'r' or 'z')")
+                    t = int(t)
+                    if t in cols[kind]:
+                        raise ValueError(f"run_tangent: cell tag {t} is listed in two conductivity columns ({kind})")
+                    if (t in cols["k"]) if kind != "k" else (t in cols["r"] or t in cols["z"]):
+                        raise ValueError(f"run_tangent: cell tag {t} has a kappa column and a directional one")
+                    cols[kind][t] = j
+            spec = (n_par, "dir") + tuple(tuple(sorted(cols[q].items())) for q in ("k", "r", "z"))
         if getattr(self, "_tangent_spec", None) != spec:     # a new set of parameters: the tangents start from zero
-            self.backend.tangent_setup(n_par, tag_col)
+            if directional:
+                self.backend.tangent_setup_dir(n_par, cols["k"], cols["r"], cols["z"])
+            else:
+                self.backend.tangent_setup(n_par, tag_col)
             self._tangent_spec = spec
         nv = self.backend.tangent_nv
         for bc in self.bcs:
@@ -220,6 +242,10 @@ class HeatProblem:
     def tangent(self, j):
         """The current tangent field of column j (n values)."""
         return self.backend.get_tangent(j)
+
+    def tangent_load(self, j):
+        """The load F_j = -K_j u of column j at the current state, by the tangent set-up in force (tests and diagnostics)."""
+        return self.backend.tangent_load(j)
 
 
     # -- steady state and pre-heated transients (with_ir_steady.ipynb cells 17-23) -------------

@@ -29,7 +29,7 @@
  *   hf_hold_load       b_equiv = A_free . u_ss with the transient's Dirichlet rows zeroed   with_ir_steady.ipynb cell 18
  *   hf_set_time_scheme no counterpart: the reference steps with backward Euler only (run_with_diamond.py:321-337);
  *                      HF_TIME_BDF2 is the second-order alternative
- *   hf_tangent_setup / hf_run_tangent / hf_get_tangent   no counterpart: the reference fits by re-running the forward model
+ *   hf_tangent_setup / hf_tangent_setup_dir / hf_run_tangent / hf_get_tangent / hf_tangent_load   no counterpart: the reference fits by re-running the forward model
  *                      over a grid (sweep_test.py:47-75, parameter_sweep.py:195-235); these give the derivatives of a run
  *   hf_set_kappa_tables / hf_get_picard_change   no counterpart: the reference's conductivities are constants per material
  *                      (run_with_diamond.py:286-301); these make them functions of the temperature
@@ -149,7 +149,8 @@ int hf_update_kappa(hf_ctx* ctx, int32_t n_mat, const int32_t* tags, const doubl
  * on a mesh without row-gather lists or after hf_assemble in another mode.  While a tag is anisotropic: hf_assemble in a mode
  * other than HF_ASM_ROW_GATHER -> HF_ERR_ARG; hf_set_kappa_tables, hf_set_rhoc_tables and hf_steady_picard_setup -> HF_ERR_STATE;
  * hf_tangent_setup with a column on an anisotropic tag -> HF_ERR_ARG (columns on isotropic tags work: their load is the unit
- * stiffness of those tags and the operator is the primal's).  Tangents with respect to m_z, m_r are not provided. */
+ * stiffness of those tags and the operator is the primal's).  hf_tangent_setup_dir takes columns in k_r, k_z and kappa of any
+ * tag, anisotropic ones included; the derivative with respect to a multiplier is kappa times the directional one. */
 int hf_set_anisotropy(hf_ctx* ctx, int32_t n, const int32_t* tags, const double* m_z, const double* m_r);
 
 /* Dirichlet DOFs (unique; the host resolves overlaps "later BC wins" beforehand).
@@ -372,8 +373,28 @@ int hf_get_load(hf_ctx* ctx, double* F);
  *        primal or any tangent column fails.
  * hf_get_tangent  copies column j (0 <= j < nv) of the tangent state out (n doubles).
  * hf_set_state, hf_set_materials, hf_assemble (hence hf_update_kappa), hf_steady_solve and hf_tangent_setup reset every
- * tangent to zero; hf_set_mesh removes the set-up. */
+ * tangent to zero; hf_set_mesh removes the set-up.
+ *
+ * Directional columns.  Per element K_e = k_r K_e^r + k_z K_e^z with k_r = m_r kappa, k_z = m_z kappa
+ * (hf_set_anisotropy; m = 1 on isotropic tags), so the step is affine in k_r and k_z of every tag and the recursion above holds
+ * with F_j = -K_t^r u^{n+1} for k_r of tag t (absolute, W/m/K), -K_t^z u^{n+1} for k_z, and -(m_r K_t^r + m_z K_t^z) u^{n+1} for
+ * kappa (both directions, the ratio kept: what hf_update_kappa scales).  M does not enter and the operator is the primal's.
+ * hf_tangent_setup_dir  as hf_tangent_setup with three tables of tab_len entries (-1 = none; any of them may be NULL = all -1):
+ *        tag_col_k[t] = j: column j is the kappa of tag t, weighted by the (m_r, m_z) the context holds at this call;
+ *        tag_col_r[t] = j / tag_col_z[t] = j: column j is the k_r / k_z of tag t.  Several tags may feed one column, and one tag
+ *        may feed its k_r into one column and its k_z into another.  Works on isotropic and anisotropic tags alike.
+ *        HF_ERR_ARG (the message names the tag): everything hf_tangent_setup refuses, all three tables NULL, a tag with a kappa
+ *        column and a directional one.  HF_ERR_STATE: as hf_tangent_setup.  The set-up replaces one of hf_tangent_setup and
+ *        the other way round; hf_run_tangent and hf_get_tangent serve whichever is in force, and everything that resets or
+ *        removes a set-up of hf_tangent_setup does the same to this one - hf_set_anisotropy removes it (the weights of its
+ *        kappa columns were the old multipliers).  With kappa columns only, on tags with multipliers (1, 1), the loads and the
+ *        tangents are bit for bit those of hf_tangent_setup with the same columns.
+ * hf_tangent_load  for tests and diagnostics: forms the loads F = -K_j u of every column from the current state with the set-up
+ *        in force (either kind), synchronises and copies column j (0 <= j < nv; n doubles) out.  Nothing else changes.
+ *        HF_ERR_STATE before a set-up or with a batch open, HF_ERR_ARG for j outside [0, nv). */
 int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col);
+int hf_tangent_setup_dir(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col_k, const int32_t* tag_col_r, const int32_t* tag_col_z);
+int hf_tangent_load(hf_ctx* ctx, int32_t j, double* F);
 int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const double* h_all, double rtol, double atol, int32_t max_it,
                    int32_t n_s, const int32_t* nodes, double* samples, int32_t* iters, double* tangent_samples, int32_t* tangent_iters);
 int hf_get_tangent(hf_ctx* ctx, int32_t j, double* s);
