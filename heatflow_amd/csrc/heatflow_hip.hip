@@ -80,6 +80,23 @@ void load_free(hf_ctx* ctx) {
   ctx->have_load = false;
 }
 
+void source_free(hf_ctx* ctx) {
+  dev_free(&ctx->src.F1); dev_free(&ctx->src.sum); dev_free(&ctx->src.absorb);
+  ctx->src = hf_ctx::Source();
+}
+
+// A run of n_steps steps needs that many amplitudes left in hf_set_source_amplitudes' list (an empty list: amplitude 0), and,
+// with a load set as well, the vector that step_load forms F0 + p_k F1 in
+int source_steps_ok(hf_ctx* ctx, int64_t n_steps, const char* call) {
+  hf_ctx::Source& S = ctx->src;
+  if (!S.on) return HF_OK;
+  if (!S.amp.empty() && S.next + static_cast<size_t>(n_steps) > S.amp.size())
+    return fail(ctx, HF_ERR_STATE, "%s: the source has %zu amplitudes left for %lld steps (hf_set_source_amplitudes)", call,
+                S.amp.size() - S.next, static_cast<long long>(n_steps));
+  if (ctx->have_load && !S.sum) HF_TRY(dev_alloc(ctx, &S.sum, ctx->n));
+  return HF_OK;
+}
+
 void tangent_free(hf_ctx* ctx) {
   free_batch_state(ctx->tanb);
   dev_free(&ctx->tan.col); dev_free(&ctx->tan.dir); dev_free(&ctx->tan.F);
@@ -110,6 +127,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   proj_free(ctx);
   steady_free(ctx);
   load_free(ctx);
+  source_free(ctx);
   tangent_free(ctx);
   kt_free(ctx);
   an_free(ctx);
@@ -645,7 +663,7 @@ int hf_destroy(hf_ctx* ctx) {
   dev_free(&ctx->d_uprev); dev_free(&ctx->d_ustart);
   dev_free(&ctx->d_u); dev_free(&ctx->d_b); dev_free(&ctx->d_r); dev_free(&ctx->d_p); dev_free(&ctx->d_Ap);
   free_batch(ctx); free_batch_state(ctx->fluxb); free_batch_cols(ctx); free_amg(ctx); free_responses(ctx); proj_free(ctx); dev_free(&ctx->d_z); dev_free(&ctx->d_z2);
-  steady_free(ctx); load_free(ctx); tangent_free(ctx); kt_free(ctx); an_free(ctx); value_lists_free(ctx);
+  steady_free(ctx); load_free(ctx); source_free(ctx); tangent_free(ctx); kt_free(ctx); an_free(ctx); value_lists_free(ctx);
   dev_free(&ctx->d_M1); dev_free(&ctx->d_dinv1); dev_free(&ctx->d_gz); dev_free(&ctx->d_gr); dev_free(&ctx->d_bz); dev_free(&ctx->d_br);
   dev_free(&ctx->d_tmp); dev_free(&ctx->d_part_pAp); dev_free(&ctx->d_part_rz); dev_free(&ctx->d_part_zz);
   dev_free(&ctx->d_part_bn); dev_free(&ctx->d_scal); dev_free(&ctx->d_samp_idx); dev_free(&ctx->d_samp); dev_free(&ctx->d_fsamp_idx);
@@ -1329,6 +1347,7 @@ int hf_step(hf_ctx* ctx, const double* g_bc, double rtol, double atol, int32_t m
   if (ctx->nbc > 0 && !g_bc) return fail(ctx, HF_ERR_ARG, "hf_step: g_bc is null");
   if (max_it <= 0 || rtol < 0 || atol < 0) return fail(ctx, HF_ERR_ARG, "hf_step: bad tolerances");
   HF_HIP(hipSetDevice(ctx->dev));
+  HF_TRY(source_steps_ok(ctx, 1, "hf_step"));
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   const int rc = step_device(ctx, g_bc, nullptr, rtol, atol, max_it);
   if (rc == HF_ERR_HIP) return rc;
@@ -1351,6 +1370,7 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
   for (int32_t q = 0; q < ns; ++q)
     if (nodes[q] < 0 || nodes[q] >= ctx->n) return fail(ctx, HF_ERR_ARG, "hf_run: node %d outside [0,%d)", nodes[q], ctx->n);
   HF_HIP(hipSetDevice(ctx->dev));
+  HF_TRY(source_steps_ok(ctx, n_steps, "hf_run"));
   DevTemp<double> t_gall, t_sall;
   double *&d_gall = t_gall.p, *&d_sall = t_sall.p;
   if (ctx->nbc > 0) {   // all boundary vectors in one transfer; the steps copy device to device
@@ -1387,6 +1407,7 @@ int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
   if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: %s tables are set (tangents of the nonlinear loop are not supported)", kt_kind(ctx));
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a batch is open");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a load is set (tangents of pre-heated runs are not supported)");
+  if (ctx->src.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a source is set (hf_set_source; tangents of sourced runs are not supported)");
   if (n_par < 1 || n_par > NV_MAX) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: 1..%d parameters (got %d)", NV_MAX, n_par);
   if (!tag_col) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tag_col is null");
   for (int t = 0; t < ctx->tab_len; ++t) {
@@ -1426,6 +1447,7 @@ int hf_tangent_setup_dir(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col_k, c
   if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: %s tables are set (tangents of the nonlinear loop are not supported)", kt_kind(ctx));
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a batch is open");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a load is set (tangents of pre-heated runs are not supported)");
+  if (ctx->src.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a source is set (hf_set_source; tangents of sourced runs are not supported)");
   if (n_par < 1 || n_par > NV_MAX) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: 1..%d parameters (got %d)", NV_MAX, n_par);
   if (!tag_col_k && !tag_col_r && !tag_col_z) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: tag_col_k, tag_col_r and tag_col_z are all null");
   const int32_t* tabs[3] = {tag_col_k, tag_col_r, tag_col_z};
@@ -1493,6 +1515,7 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a batch is open");
   if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: %s tables are set (tangents of the nonlinear loop are not supported)", kt_kind(ctx));
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a load is set (tangents of pre-heated runs are not supported)");
+  if (ctx->src.on) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a source is set (hf_set_source; tangents of sourced runs are not supported)");
   if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_run_tangent before hf_tangent_setup");
   if (ctx->tan.steady_state)
     return fail(ctx, HF_ERR_STATE, "hf_run_tangent: the state comes from hf_steady_solve and depends on the conductivities (tangents start at zero): hf_set_state first");
@@ -1830,6 +1853,80 @@ int hf_get_load(hf_ctx* ctx, double* F) {
   return HF_OK;
 }
 
+int hf_set_source(hf_ctx* ctx, int32_t n_tags, const int32_t* tags, double fwhm, double z0, double depth) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_set_source before hf_set_mesh");
+  HF_HIP(hipSetDevice(ctx->dev));
+  if (n_tags == 0) { source_free(ctx); return HF_OK; }
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_set_source: a batch is open (the batched loop has no load term)");
+  if (n_tags < 0 || !tags) return fail(ctx, HF_ERR_ARG, "hf_set_source: %d tags or a null pointer", n_tags);
+  if (!ctx->rg_ok) return fail(ctx, HF_ERR_ARG, "hf_set_source: the source's load is formed by the row-gather kernel only (a mesh with row-gather lists)");
+  if (!std::isfinite(fwhm) || !(fwhm > 0.0)) return fail(ctx, HF_ERR_ARG, "hf_set_source: fwhm must be positive and finite (got %g)", fwhm);
+  if (!std::isfinite(z0)) return fail(ctx, HF_ERR_ARG, "hf_set_source: z0 must be finite (got %g)", z0);
+  if (std::isnan(depth) || !(depth > 0.0)) return fail(ctx, HF_ERR_ARG, "hf_set_source: depth must be positive, or +inf for a uniform layer (got %g)", depth);
+  std::vector<int32_t> absorb(64, 0);    // by row-gather tag-dictionary index, as the coefficient tables of the kernels
+  for (int32_t q = 0; q < n_tags; ++q) {
+    const int32_t tg = tags[q];
+    if (tg < 0 || tg >= ctx->tab_len || !ctx->h_tag_used[tg]) return fail(ctx, HF_ERR_ARG, "hf_set_source: tag %d is not a cell tag of the mesh", tg);
+    for (int32_t q2 = 0; q2 < q; ++q2)
+      if (tags[q2] == tg) return fail(ctx, HF_ERR_ARG, "hf_set_source: tag %d is listed twice", tg);
+    for (size_t d = 0; d < ctx->h_rg_tags.size() && d < 64; ++d)
+      if (ctx->h_rg_tags[d] == tg) absorb[d] = 1;
+  }
+  source_free(ctx);   // a source that was on is off until the new one is complete: a failure below leaves none set
+  hf_ctx::Source& S = ctx->src;
+  HF_TRY(dev_alloc(ctx, &S.F1, ctx->n));
+  HF_TRY(dev_alloc(ctx, &S.absorb, 64));
+  HF_HIP(copy_sync(ctx, S.absorb, absorb.data(), sizeof(int32_t) * 64, hipMemcpyHostToDevice));
+  // k_tangent_load's LDS footprint (the source shape where it stages u); persistent workgroups from one occupancy query per mesh
+  const int capd = ctx->rg_max_dict;
+  const size_t sm = static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 + (RBA + 4) * 4 +
+                    (static_cast<size_t>((ctx->max_blk_nnz + 1) & ~1) / 8 + 3) * 16;
+  int& grid = ctx->rg_grid[RG_SOURCE];
+  if (grid == 0) {
+    const void* fn = reinterpret_cast<const void*>(&k_source_load);
+    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
+    int per_cu = 0, ncu = 0;
+    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
+    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
+    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+  }
+  const double c_r = 4.0 * M_LN2 / (fwhm * fwhm), inv_depth = std::isinf(depth) ? 0.0 : 1.0 / depth;
+  HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  hipLaunchKernelGGL(k_source_load, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr,
+                     reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
+                     ctx->d_rowptr, S.absorb, c_r, z0, inv_depth, S.F1);
+  HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+  HF_HIP(hipGetLastError());
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  ctx->last_ms = ms;
+  S.amp.clear();
+  S.next = 0;
+  S.on = true;
+  return HF_OK;
+}
+
+int hf_get_source(hf_ctx* ctx, double* F) {
+  if (!ctx || !F) return HF_ERR_ARG;
+  if (!ctx->src.on) return fail(ctx, HF_ERR_STATE, "hf_get_source: no source set");
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_HIP(copy_sync(ctx, F, ctx->src.F1, sizeof(double) * ctx->n, hipMemcpyDeviceToHost));
+  return HF_OK;
+}
+
+int hf_set_source_amplitudes(hf_ctx* ctx, int32_t n_amp, const double* p) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->src.on) return fail(ctx, HF_ERR_STATE, "hf_set_source_amplitudes: no source set (hf_set_source first)");
+  if (n_amp < 0 || (n_amp > 0 && !p)) return fail(ctx, HF_ERR_ARG, "hf_set_source_amplitudes: %d amplitudes or a null pointer", n_amp);
+  for (int32_t k = 0; k < n_amp; ++k)
+    if (!std::isfinite(p[k])) return fail(ctx, HF_ERR_ARG, "hf_set_source_amplitudes: amplitude %d is not finite", k);
+  ctx->src.amp.assign(p, p + n_amp);
+  ctx->src.next = 0;
+  return HF_OK;
+}
+
 int hf_hold_load(hf_ctx* ctx) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->steady.ready) return fail(ctx, HF_ERR_STATE, "hf_hold_load before hf_steady_setup (it needs the stiffness)");
@@ -1860,6 +1957,7 @@ int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
   if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_batch_begin: %s tables are set (batched sweeps of the nonlinear loop are not supported)", kt_kind(ctx));
   if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_batch_begin before hf_assemble");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_batch_begin: a load is set (the batched loop has no load term; hf_set_load(NULL) first)");
+  if (ctx->src.on) return fail(ctx, HF_ERR_STATE, "hf_batch_begin: a source is set (the batched loop has no load term; hf_set_source with n_tags = 0 first)");
   if (nv != 2 && nv != 4 && nv != 8 && nv != 16) return fail(ctx, HF_ERR_ARG, "hf_batch_begin: 2, 4, 8 or 16 columns (got %d)", nv);
   if (operator_kind < 0 || operator_kind > 2) return fail(ctx, HF_ERR_ARG, "hf_batch_begin: unknown operator kind %d", operator_kind);
   if (operator_kind == HF_BATCH_PER_COLUMN && ctx->precond == 1 && !ctx->amg_reuse)

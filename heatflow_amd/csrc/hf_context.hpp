@@ -107,7 +107,7 @@ struct TanDir { int32_t c_r, c_z; double w_r, w_z; };
 
 // The row-gather assembly kernels: k_assemble_rows<false / true>, k_assemble_rows_an<false / true>, k_assemble_rows_kT,
 // k_assemble_rows_cT, k_assemble_rows_kT_K
-enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_VARIANTS };
+enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_SOURCE, RG_VARIANTS };
 
 }  // namespace
 
@@ -297,6 +297,16 @@ struct hf_ctx {
   // load term of the time step (hf_set_load / hf_hold_load): b = M u^n + dt F
   double* d_load = nullptr;
   bool have_load = false;
+  // volumetric source of the time step (hf_set_source): b = M u^n + dt (F0 + p_k F1), F0 the load above (if any), F1 = the
+  // source's load at unit amplitude (k_source_load) and p_k the amplitude of the k-th step after hf_set_source_amplitudes
+  struct Source {
+    bool on = false;
+    double* F1 = nullptr;        // n doubles
+    double* sum = nullptr;       // F0 + p_k F1 of the current step (allocated by the first step that has a load too)
+    int32_t* absorb = nullptr;   // 64 flags by row-gather tag-dictionary index
+    std::vector<double> amp;     // amplitudes of the next steps; empty: amplitude 0
+    size_t next = 0;             // the next step's index into amp
+  } src;
   double *d_z = nullptr, *d_z2 = nullptr;
   // read-flux projection (hf_flux_setup): unit-rho_c r-weighted mass matrix and the projected gradient
   bool flux_ready = false;

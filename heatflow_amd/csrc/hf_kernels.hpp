@@ -704,6 +704,79 @@ __global__ __launch_bounds__(RBA) void k_tangent_load_dir(int nblk, int capd, co
   }
 }
 
+// Shape of the volumetric source (hf_set_source) at a node P = (z, r): s = exp(-(c_r r^2 + |z - z0| inv_depth)),
+// c_r = 4 ln2 / fwhm^2 and inv_depth = 1 / depth, both formed on the host (inv_depth = 0: uniform through the layer).
+// One double-precision exp per node; the argument is formed without contraction, so it has the bits of its restatement.
+__device__ __forceinline__ double source_shape(const double2 P, double c_r, double z0, double inv_depth) {
+#pragma clang fp contract(off)
+  const double x = c_r * (P.y * P.y) + fabs(P.x - z0) * inv_depth;
+  return exp(-x);
+}
+
+// Load of the volumetric source by row gather (k_tangent_load's lists, staging, LDS carve-up):
+// F[i] = sum over the triangles e at node i whose tag absorbs (absorb[tag-dictionary index] != 0) of (M_e s)_i, M_e the
+// r-weighted element mass at rho_c = 1 (element_row) and s the source shape at the element's three nodes, i.e. the P1
+// interpolant of s inside each absorbing element, cut off at the material boundary.  No state is staged: where
+// k_tangent_load stages u the block's column nodes get s, computed once per node from the staged coordinates, so every lane
+// that reads a node sees the same bits.  The sum runs in list order in a register of the row's lane - no atomics, bitwise
+// reproducible; rows with no absorbing triangle are written as zeros.
+__global__ __launch_bounds__(RBA) void k_source_load(int nblk, int capd, const int4* __restrict__ hdr, const uint4* __restrict__ ell,
+                                                     const uint4* __restrict__ cid16, const double2* __restrict__ zrb,
+                                                     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ absorb,
+                                                     double c_r, double z0, double inv_depth, double* __restrict__ F) {
+  extern __shared__ double smem[];
+  __shared__ int sabs[64];
+  double2* sXd = reinterpret_cast<double2*>(smem);
+  double* sS = smem + 2 * capd;
+  int* sR = reinterpret_cast<int*>(sS + capd + (capd & 1));
+  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);
+  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
+  const int t = threadIdx.x;
+  if (t < 64) sabs[t] = absorb[t];
+  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const int4 cA = hdr[2 * blk], cB = hdr[2 * blk + 1];
+    const int c0 = cA.x >> 3, nc = ((cA.x + cA.y + 7) >> 3) - c0;
+    for (int i = t; i < nc; i += RBA) sC4[i] = cid16[c0 + i];
+    for (int i = t; i < cA.w; i += RBA) {
+      const double2 P = zrb[cA.z + i];
+      sXd[i] = P;
+      sS[i] = source_shape(P, c_r, z0, inv_depth);
+    }
+    if (t < cB.w) sR[t] = rowptr[blk * RBA + t] - cA.x;
+    __syncthreads();
+    if (t < cB.w) {
+#pragma clang fp contract(off)
+      const int sbase = sR[t] + (cA.x & 7);
+      const int ci = cB.z + t;
+      const double2 Pi = sXd[ci];
+      const double si = sS[ci];
+      double acc = 0.0;
+      for (int g = 0; g < cB.y; ++g) {
+        const uint4 ev = ell[cB.x + g * RBA + t];
+        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
+          if (e == 0xFFFFu) continue;
+          if (sabs[e >> 10] == 0) continue;
+          const int pj = sC[sbase + (e & 31u)], pk = sC[sbase + ((e >> 5) & 31u)];
+          const ElemRow r = element_row(Pi, sXd[pj], sXd[pk], 1.0, 0.0);
+          acc += (r.m0 * si + r.m1 * sS[pj]) + r.m2 * sS[pk];
+        }
+      }
+      F[blk * RBA + t] = acc;
+    }
+    __syncthreads();
+  }
+}
+
+// F0 + p F1: the load of a step when a source (hf_set_source) acts on top of a load (hf_set_load / hf_hold_load)
+__global__ __launch_bounds__(TPB) void k_source_sum(int n, const double* __restrict__ F0, double p, const double* __restrict__ F1,
+                                                    double* __restrict__ out) {
+#pragma clang fp contract(off)
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = F0[i] + p * F1[i];
+}
+
 // kappa(T) of one table (KTab): s = (T - t0) / dT, clamped to the end values, else v_i + (s - i) (v_{i+1} - v_i), i = floor(s)
 __device__ __forceinline__ double ktab_eval(const KTab h, const double* __restrict__ vals, double T) {
 #pragma clang fp contract(off)

@@ -745,22 +745,44 @@ int prepare_response(hf_ctx* ctx, const double* g_new, int max_it, RespArgs* ra)
   return HF_OK;
 }
 
-// b = M u^n, plus dt F when a load is set (hf_set_load / hf_hold_load); without a load exactly the kernel of before
-void launch_rhs(hf_ctx* ctx) {
-  if (ctx->have_load)
-    launch_spmv<10>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, nullptr, nullptr, nullptr, nullptr, ctx->dt, ctx->d_load);
+// The load operand of one step's right-hand side, b = M u^n + w F.  F = null: no load.  A load alone (hf_set_load /
+// hf_hold_load): F = F0, w = dt'.  A source alone (hf_set_source): F = F1 and w = dt' p_k, so the amplitude costs no launch
+// and no pass over n.  Both: one small kernel forms F0 + p_k F1 first, and w = dt'.  p_k: the next entry of
+// hf_set_source_amplitudes' list (0 while the list is empty); the callers have checked that the list reaches.
+struct StepLoad { const double* F = nullptr; double w = 0.0; };
+StepLoad step_load(hf_ctx* ctx) {
+  StepLoad L;
+  if (ctx->have_load) { L.F = ctx->d_load; L.w = ctx->dt; }
+  hf_ctx::Source& S = ctx->src;
+  if (!S.on) return L;
+  const double p = S.next < S.amp.size() ? S.amp[S.next] : 0.0;
+  if (!S.amp.empty()) S.next += 1;
+  if (ctx->have_load) {
+    hipLaunchKernelGGL(k_source_sum, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_load, p, S.F1, S.sum);
+    L.F = S.sum;
+  } else {
+    L.F = S.F1;
+    L.w = ctx->dt * p;
+  }
+  return L;
+}
+
+// b = M u^n, plus w F when the step has a load (step_load); without one exactly the kernel of before
+void launch_rhs(hf_ctx* ctx, const StepLoad& L) {
+  if (L.F)
+    launch_spmv<10>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, nullptr, nullptr, nullptr, nullptr, L.w, L.F);
   else
     launch_spmv<0>(ctx, ctx->d_M, ctx->d_u, ctx->d_b);
 }
 
-// BDF2: b = M (4/3 u^n - 1/3 u^{n-1}), plus dt' F when a load is set, in one pass over M (k_spmv modes 12-15).  The same pass
+// BDF2: b = M (4/3 u^n - 1/3 u^{n-1}), plus w F when the step has a load, in one pass over M (k_spmv modes 12-15).  The same pass
 // writes `ustart`: the extrapolated start vector 2 u^n - u^{n-1} (extrap) or a copy of u^n, which the caller turns into the
 // next step's u^{n-1} by a pointer swap.  Without a history (a rest start) u^{n-1} = u^n.
-void launch_rhs_bdf2(hf_ctx* ctx, bool extrap) {
+void launch_rhs_bdf2(hf_ctx* ctx, bool extrap, const StepLoad& L) {
   const double* um1 = ctx->bdf_hist ? ctx->d_uprev : ctx->d_u;
-  if (ctx->have_load) {
-    if (extrap) launch_spmv<15>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, um1, ctx->d_ustart, nullptr, nullptr, ctx->dt, ctx->d_load);
-    else launch_spmv<14>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, um1, ctx->d_ustart, nullptr, nullptr, ctx->dt, ctx->d_load);
+  if (L.F) {
+    if (extrap) launch_spmv<15>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, um1, ctx->d_ustart, nullptr, nullptr, L.w, L.F);
+    else launch_spmv<14>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, um1, ctx->d_ustart, nullptr, nullptr, L.w, L.F);
   } else {
     if (extrap) launch_spmv<13>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, um1, ctx->d_ustart);
     else launch_spmv<12>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, um1, ctx->d_ustart);
@@ -855,15 +877,16 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
   }
   const double* g = g_dev ? g_dev : ctx->d_g;   // hf_run has every step's boundary values on the device already
   if (nb > 0 && !g_dev) HF_HIP(hipMemcpyAsync(ctx->d_g, g_host, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
+  const StepLoad L = step_load(ctx);   // the load and the source of this step, for every right-hand side below
   if (bdf2 && (projected || !ctx->extrapolate)) {
     // BDF2 with the projected start vector (kind 3) or u^n (kind 0): the right-hand side's pass keeps u^n for the next step
-    launch_rhs_bdf2(ctx, false);
+    launch_rhs_bdf2(ctx, false, L);
     std::swap(ctx->d_uprev, ctx->d_ustart);
     ctx->bdf_hist = true;
     ctx->have_prev = true;
   } else if (bdf2) {
     // BDF2 with the extrapolated start vector (kinds 1 and 2); from a rest start it is u^n
-    launch_rhs_bdf2(ctx, true);
+    launch_rhs_bdf2(ctx, true, L);
     HF_HIP(hipMemcpyAsync(ctx->d_uprev, ctx->d_u, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
     HF_HIP(hipMemcpyAsync(ctx->d_u, ctx->d_ustart, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
     ctx->bdf_hist = true;
@@ -871,13 +894,13 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
   } else if (projected) {
     // b = M u^n, lifting, set_bc; then the start vector = A-norm projection of the new solution on the span of the last
     // solutions and the boundary responses (kind 3)
-    launch_rhs(ctx);
+    launch_rhs(ctx, L);
     ctx->have_prev = true;
   } else if (ctx->extrapolate && ctx->have_prev) {
     // b = M u^n   (assemble_vector, run_with_diamond.py:476); with a previous step available the same
     // pass writes the extrapolated start vector 2 u^n - u^{n-1}, and the three state buffers rotate
-    if (ctx->have_load)
-      launch_spmv<11>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, ctx->d_uprev, ctx->d_ustart, nullptr, nullptr, ctx->dt, ctx->d_load);
+    if (L.F)
+      launch_spmv<11>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, ctx->d_uprev, ctx->d_ustart, nullptr, nullptr, L.w, L.F);
     else
       launch_spmv<8>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, ctx->d_uprev, ctx->d_ustart);
     // u^{n-1} <- u^n, iterate <- start vector
@@ -887,7 +910,7 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
     else
       HF_HIP(hipMemcpyAsync(ctx->d_u, ctx->d_ustart, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
   } else {
-    launch_rhs(ctx);
+    launch_rhs(ctx, L);
     if (ctx->extrapolate) {         // keep u^n for the next step
       HF_HIP(hipMemcpyAsync(ctx->d_uprev, ctx->d_u, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
       ctx->have_prev = true;
@@ -924,8 +947,8 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
       HF_TRY(kt_revalue(ctx, ctx->d_u, nullptr));
       if (!ct)
         HF_HIP(hipMemcpyAsync(ctx->d_b, ctx->kt.b0, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
-      else if (ctx->have_load)   // b = M_k w + dt' F with the M of this sweep (the history was rotated by sweep 1's pass)
-        launch_spmv<10>(ctx, ctx->d_M, ctx->kt.w, ctx->d_b, nullptr, nullptr, nullptr, nullptr, nullptr, ctx->dt, ctx->d_load);
+      else if (L.F)   // b = M_k w + dt' F with the M of this sweep (the history was rotated by sweep 1's pass)
+        launch_spmv<10>(ctx, ctx->d_M, ctx->kt.w, ctx->d_b, nullptr, nullptr, nullptr, nullptr, nullptr, L.w, L.F);
       else
         launch_spmv<0>(ctx, ctx->d_M, ctx->kt.w, ctx->d_b);
       if (nb > 0) {

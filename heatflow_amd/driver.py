@@ -45,6 +45,7 @@ from .heating import HeatingCurve
 from .aniso import DIRECTIONAL_HINT, check_config, refuse_aniso, split_param
 from .kappa_t import material_cv_table, material_table, picard_sweeps, refuse_tables
 from .mesh import Mesh, load_mesh_arrays
+from .source import amplitudes as source_amplitudes, parse_source, refuse_source
 from .solver import DEFAULT_MAX_IT, DEFAULT_RTOL, HeatProblem
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -172,9 +173,13 @@ def _with_scheme(cfg):
     """``cfg`` with the time scheme it runs with written out (``timing.scheme``), for used_config.yaml; with kappa(T) also
     ``timing.picard_sweeps`` and the tables that ran (``kappa_tables``: {material: {T0, dT, k}}); with cv(T) the same under
     ``rhoc_tables``: {material: {T0, dT, rho_cv}}, written only when a capacity table is set.  An anisotropic conductivity
-    travels with its material (``mats.<name>.k_aniso``), so it is written exactly when it is set."""
+    travels with its material (``mats.<name>.k_aniso``), so it is written exactly when it is set.  A volumetric
+    source (``heating.source``, heatflow_amd.source) is written exactly when it is set too, with its defaults filled in."""
     out = dict(cfg)
     out["timing"] = dict(cfg.get("timing") or {}, scheme=time_scheme(cfg))
+    src = parse_source(cfg)
+    if src is not None:
+        out["heating"] = dict(cfg["heating"], source=src.used_config())
     tables = {}
     for name, mat in sorted((cfg.get("mats") or {}).items()):
         t = material_table(name, mat) if isinstance(mat, dict) else None
@@ -227,6 +232,7 @@ class SimulationSession:
         self.hierarchy = hierarchy
         self.problem = None
         self._key = None
+        self._source_F1 = None     # the resident problem's source vector, read back once per problem
         self._tree = None
         self._space = None
         self._dof_cache = {}
@@ -252,8 +258,9 @@ class SimulationSession:
         scheme = time_scheme(cfg)
         kt = self._kappa_tables(cfg, stack)
         an = self._aniso(stack)
-        self._ensure_problem(self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an), tag_to_k, tag_to_rc, dt, bcs,
-                             float(cfg["heating"]["ic_temp"]), scheme, kt, an)
+        src = self._source(cfg, stack)
+        self._ensure_problem(self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an, src), tag_to_k, tag_to_rc, dt, bcs,
+                             float(cfg["heating"]["ic_temp"]), scheme, kt, an, src)
 
     def _tables(self, stack):
         tag_to_k = {self.material_tags[m.name]: m.properties["k"] for m in stack.materials}
@@ -264,6 +271,11 @@ class SimulationSession:
         """{cell tag: (m_r, m_z)} of the materials of ``stack`` with a ``k_aniso`` block ({}: an isotropic configuration)."""
         return {self.material_tags[m.name]: m.properties["k_aniso"] for m in stack.materials if "k_aniso" in m.properties}
 
+    def _source(self, cfg, stack):
+        """dict(tags, fwhm, z0, depth) of a configuration with a ``heating.source`` block (HeatProblem's ``source=``), or None."""
+        spec = parse_source(cfg)
+        return None if spec is None else spec.problem_source(stack, self.material_tags)
+
     def _kappa_tables(self, cfg, stack):
         """(tables {tag: (T0, dT, values)}, Picard sweeps, capacity tables {tag: (T0, dT, values)}) of a kappa(T) / cv(T)
         configuration, or None."""
@@ -273,9 +285,15 @@ class SimulationSession:
         return (tables, picard_sweeps(cfg), ctables) if tables or ctables else None
 
     def _boundary_conditions(self, cfg, stack, two_sided=False):
-        """[left, right, top, heated line(s)] of one configuration (reference run_with_diamond.py:343-374)."""
+        """[left, right, top, heated line(s)] of one configuration (reference run_with_diamond.py:343-374).  With a volumetric
+        source (``heating.source``) and ``keep_line: false`` the three outer edges only: both coupler faces are free, and
+        ``heating.file`` is not read."""
         ic_temp = float(cfg["heating"]["ic_temp"])
-        heat = HeatingCurve(_resolve(cfg["heating"]["file"]), ic_temp, float(cfg["heating"]["fwhm"]))
+        src = parse_source(cfg)
+        if src is not None and two_sided:
+            refuse_source(cfg, "two_sided=True (a second heated line)")
+        line = src is None or src.keep_line
+        heat = HeatingCurve(_resolve(cfg["heating"]["file"]), ic_temp, float(cfg["heating"]["fwhm"])) if line else None
         if self._space is None:
             self._space = P1Space(self.coords)
         V = self._space
@@ -291,9 +309,10 @@ class SimulationSession:
             located("left", ic_temp),
             located("right", ic_temp),
             located("top", ic_temp),      # named bottom_bc in the reference, location 'top'
-            located("x", heat.gaussian, coord=float(stack.heated_z), length=abs(stack.r_sample) * 2, center=0.0),
         ]
-        self._heats = [heat]            # the heated lines' curves, by position after the three edges (fwhm tangents)
+        if line:
+            bcs.append(located("x", heat.gaussian, coord=float(stack.heated_z), length=abs(stack.r_sample) * 2, center=0.0))
+        self._heats = [heat] if line else []   # the heated lines' curves, by position after the three edges (fwhm tangents)
         if two_sided:
             # EXTENSION without a reference implementation (BASELINE config 4 "konopkova two-sided",
             # SURVEY 8d C4): a second Gaussian Dirichlet line on the outer face of the o-side coupler,
@@ -303,7 +322,7 @@ class SimulationSession:
             self._heats.append(heat_o)
         return bcs
 
-    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler", kt=None, an=None):
+    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler", kt=None, an=None, src=None):
         # the resident problem is reusable only for exactly the same Dirichlet DOF sets, in the same order, and time scheme
         # (and kappa(T) tables and Picard sweeps, or anisotropy multipliers, when a configuration has them)
         key = (dt, tuple(sorted(tag_to_rc.items())),
@@ -315,9 +334,11 @@ class SimulationSession:
                 key += (tuple((t, float(v[0]), float(v[1]), tuple(float(x) for x in v[2])) for t, v in sorted(kt[2].items())),)
         if an:
             key += (("k_aniso",) + tuple(sorted(an.items())),)
+        if src:
+            key += (("source", tuple(src["tags"]), src["fwhm"], src["z0"], src["depth"]),)
         return key
 
-    def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme="backward_euler", kt=None, an=None):
+    def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme="backward_euler", kt=None, an=None, src=None):
         """The resident HeatProblem for ``key`` (built if absent), its operator valued for ``tag_to_k``."""
         if self.problem is None or key != self._key:
             self.close()
@@ -329,8 +350,9 @@ class SimulationSession:
                                        amg_reuse=True, pattern=self.pattern, amg=shared["blob"] if shared else None,
                                        scheme=scheme, **({"kappa_tables": kt[0], "picard": kt[1]} if kt else {}),
                                        **({"rhoc_tables": kt[2]} if kt and kt[2] else {}),
-                                       **({"k_aniso": an} if an else {}))
+                                       **({"k_aniso": an} if an else {}), **({"source": src} if src else {}))
             self._key = key
+            self._source_F1 = None
             self._k = dict(tag_to_k)
             # conductivities the multigrid levels were built for: this problem's, or those of the session that shared them
             self._k_hier = dict(shared["k"]) if shared else dict(tag_to_k)
@@ -378,6 +400,7 @@ class SimulationSession:
         nv = len(cfgs)
         for c in cfgs:
             refuse_tables(c, "run_batch (the batched loop)")
+            refuse_source(c, "run_batch (the batched loop)")
         if nv not in (2, 4, 8, 16):
             raise ValueError("run_batch: 2, 4, 8 or 16 configurations at a time")
         t_start = time.time()
@@ -475,8 +498,13 @@ class SimulationSession:
         k -, "<material>.k_r" / "<material>.k_z" / "<material>.k" - its radial, its axial conductivity in W/m/K, or the
         scalar k of both with the ratio of ``k_aniso`` kept; on isotropic materials the derivatives at m = (1, 1) -, and / or
         "fwhm" of the heating profile) adds ``tangents`` {param: {watcher: d watcher / d param}} and
-        ``tangent_iters`` (HeatProblem.run_tangent; not with a field sink or the flux projection)."""
+        ``tangent_iters`` (HeatProblem.run_tangent; not with a field sink or the flux projection).
+        A ``heating.source`` block (heatflow_amd.source) drives the run by absorbed laser power, the field sink and the flux
+        projection included; not with ``tangents`` or ``two_sided``."""
         t_start = time.time()
+        spec = parse_source(cfg)
+        if spec is not None and tangents:
+            refuse_source(cfg, "tangents=")
         t_final = float(cfg["timing"]["t_final"])
         num_steps = int(cfg["timing"]["num_steps"])
         dt = t_final / num_steps
@@ -492,13 +520,19 @@ class SimulationSession:
         if an and tangents:      # a bare name means the isotropic k: an anisotropic material is named by direction
             refuse_aniso(cfg, "a tangent with respect to the conductivity of an anisotropic material", set(tangents),
                          DIRECTIONAL_HINT)
-        key = self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an)
+        src = self._source(cfg, stack)
+        key = self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an, src)
         fresh = self.problem is None or key != self._key
-        self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme, kt, an)
+        self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme, kt, an, src)
         if not fresh:
             self.problem.set_state(ic_temp)
             self.problem.iters = []
         prob = self.problem
+        amp = None
+        if spec is not None:     # W -> W/m^3 per step, from the discrete source's own integral
+            if self._source_F1 is None:
+                self._source_F1 = prob.source_vector()
+            amp = source_amplitudes(spec, (np.arange(num_steps) + 1) * dt, self._source_F1, _resolve)
         names, nodes = self._watcher_nodes(watcher_points)
 
         flux = FluxSampler(self.coords) if read_flux else None
@@ -533,14 +567,15 @@ class SimulationSession:
                                                                     time_varying=varying)
             tangent_out = {p: {nm: tsamp[:, j, k] for k, nm in enumerate(names)} for j, p in enumerate(params)}
         elif field_sink is None and flux is None:
-            times, samples, iters = prob.run(num_steps, watcher_nodes=nodes, time_varying=varying)
+            times, samples, iters = prob.run(num_steps, watcher_nodes=nodes, time_varying=varying,
+                                             **({"source_amplitude": amp} if amp is not None else {}))
         else:  # step-wise: every field goes to the sink (visualisation) and / or through the flux projection
             for bc in bcs:
                 bc.update(0.0)
             times, rows, iters = [], [], []
             for step in range(num_steps):
                 t = (step + 1) * dt
-                it, _ = prob.step(t, only=varying)
+                it, _ = prob.step(t, only=varying, **({"source_amplitude": float(amp[step])} if amp is not None else {}))
                 if flux is not None:
                     prob.backend.flux_solve(self.rtol, 5000, want_z=False)          # d/dr only, on the device
                     flux.record_sampled(t, prob.backend.flux_sample(flux.nodes, want_z=False)[1])

@@ -22,6 +22,7 @@ import numpy as np
 from .parameter_sweep import build_stack, get_watcher_points, oside_curves
 from .aniso import DIRECTIONAL_HINT, KEY, material_aniso, refuse_aniso, split_param
 from .kappa_t import refuse_tables
+from .source import refuse_source
 
 DEFAULT_EXP_CSV = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "experimental_data",
                                "geballe_heat_data.csv")
@@ -106,6 +107,7 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     t0 = time.time()
     scheme = time_scheme(cfg)
     refuse_tables(cfg, "heatflow_amd.fit")
+    refuse_source(cfg, "heatflow_amd.fit")
     params = tuple(params)
     refuse_aniso(cfg, "heatflow_amd.fit of the conductivity of an anisotropic material", set(params), DIRECTIONAL_HINT)
     for p in params:

@@ -36,6 +36,7 @@ EXPORTS = [
     "hf_batch_begin", "hf_batch_load_column", "hf_batch_set_affine", "hf_batch_set_state", "hf_batch_get_state", "hf_batch_run", "hf_batch_run_flux", "hf_batch_end",
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
+    "hf_set_source", "hf_get_source", "hf_set_source_amplitudes",
     "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
     "hf_set_value_lists", "hf_get_value_lists", "hf_get_projection",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
@@ -138,6 +139,9 @@ def load_library():
         "hf_set_load": [vp, pd],
         "hf_get_load": [vp, pd],
         "hf_hold_load": [vp],
+        "hf_set_source": [vp, i32, pi, dbl, dbl, dbl],
+        "hf_get_source": [vp, pd],
+        "hf_set_source_amplitudes": [vp, i32, pd],
         "hf_tangent_setup": [vp, i32, pi],
         "hf_tangent_setup_dir": [vp, i32, pi, pi, pi],
         "hf_tangent_load": [vp, i32, pd],
@@ -696,6 +700,28 @@ class HeatflowHIP:
         F = np.empty(self.n, dtype=np.float64)
         self._check(self._lib.hf_get_load(self._ctx, _pd(F)))
         return F
+
+    # -- volumetric source: laser power absorbed in some cell tags (hf_set_source) --------
+    def set_source(self, tags, fwhm=1.0, z0=0.0, depth=float("inf")):
+        """Source shape s = exp(-4 ln2 r^2 / fwhm^2) exp(-|z - z0| / depth) inside the elements of the cell tags ``tags``
+        (depth = inf: uniform in z); its load F1 is formed on the device.  An empty ``tags`` (or None) clears the source."""
+        t = _i32([] if tags is None else tags).ravel()
+        if len(t) == 0:
+            self._check(self._lib.hf_set_source(self._ctx, 0, None, 1.0, 0.0, float("inf")))
+            return
+        self._check(self._lib.hf_set_source(self._ctx, len(t), _pi(t), float(fwhm), float(z0), float(depth)))
+
+    def get_source(self):
+        """F1: the source's load at unit amplitude (n values)."""
+        F = np.empty(self.n, dtype=np.float64)
+        self._check(self._lib.hf_get_source(self._ctx, _pd(F)))
+        return F
+
+    def set_source_amplitudes(self, p):
+        """Amplitudes (peak power densities, W/m^3) of the next len(p) steps: step k after the call uses p[k].  An empty list
+        means amplitude 0 for every step."""
+        p = _f64([] if p is None else p).ravel()
+        self._check(self._lib.hf_set_source_amplitudes(self._ctx, len(p), _pd(p) if len(p) else None))
 
     # -- inspection ----------------------------------------------------------------------
     def get_csr(self, values=True):

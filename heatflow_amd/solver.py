@@ -56,12 +56,16 @@ class HeatProblem:
     k_aniso : {cell tag: (m_r, m_z)} - anisotropic conductivities (hf_set_anisotropy): the tag conducts with
               k_r = m_r k along r and k_z = m_z k along z.  Set right after the materials, before the first assembly.  Not
               together with kappa_tables / rhoc_tables (ValueError).  None / {}: isotropic, the call sequence of before.
+    source : dict(tags=, fwhm=, z0=, depth=) - a volumetric source (hf_set_source): power absorbed in the cell
+              tags ``tags`` with the shape exp(-4 ln2 r^2 / fwhm^2) exp(-|z - z0| / depth) (``depth`` absent or inf: uniform
+              in z).  Set right after the materials; its amplitude per step is :meth:`run`'s ``source_amplitude``.  None: no
+              source, the call sequence of before.
     """
 
     def __init__(self, coords, tris, tags, tag_to_k, tag_to_rho_cv, dt, bcs, u0, *, backend=None, device_id=0,
                  assembly_mode=ASM_ROW_GATHER, rtol=DEFAULT_RTOL, atol=0.0, max_it=DEFAULT_MAX_IT,
                  precond=PC_JACOBI, amg_reuse=False, pattern=None, amg=None, scheme="backward_euler", kappa_tables=None,
-                 picard=1, rhoc_tables=None, k_aniso=None):
+                 picard=1, rhoc_tables=None, k_aniso=None, source=None):
         self.coords = np.ascontiguousarray(coords, dtype=np.float64)
         self.n = self.coords.shape[0]
         self.dt = float(dt)
@@ -77,6 +81,7 @@ class HeatProblem:
         if self.k_aniso and (self.kappa_tables or self.rhoc_tables):
             raise ValueError("HeatProblem: k_aniso together with kappa_tables / rhoc_tables is not supported "
                              "(the table kernels are isotropic)")
+        self.source = check_source(source)
         scheme_code = time_scheme_code(scheme)     # (an unknown name raises before any backend call)
         self.backend = backend if backend is not None else HeatflowHIP(device_id)
         self._own_backend = backend is None
@@ -90,6 +95,8 @@ class HeatProblem:
         self.set_materials(tag_to_k, tag_to_rho_cv, assemble=False)
         if self.k_aniso:         # isotropic problems make no extra call
             self.backend.set_anisotropy(self.k_aniso)
+        if self.source:          # problems without a source make no extra call
+            self.backend.set_source(self.source["tags"], self.source["fwhm"], self.source["z0"], self.source["depth"])
         if self.bcs:
             self.bc_dofs, self._owner, self._pos = merge_bcs(self.bcs)
         else:
@@ -152,18 +159,46 @@ class HeatProblem:
     def state(self):
         return self.backend.get_state()
 
-    def step(self, t, only=None):
+    def source_vector(self):
+        """F1 of the source: the load at unit amplitude (n values; 2 pi sum(F1) = the power in W per unit amplitude)."""
+        return self.backend.get_source()
+
+    def _source_amplitudes(self, source_amplitude, times):
+        """The amplitudes of the steps that end at ``times``: a callable p(t), or one value per step."""
+        if not self.source:
+            raise ValueError("source_amplitude: the problem has no source (HeatProblem(..., source=))")
+        if callable(source_amplitude):
+            p = np.array([float(source_amplitude(float(t))) for t in times], dtype=np.float64)
+        else:
+            p = np.asarray(source_amplitude, dtype=np.float64).ravel()
+        if p.shape != (len(times),):
+            raise ValueError(f"source_amplitude: {len(times)} values expected, got {p.shape[0]}")
+        if not np.all(np.isfinite(p)):
+            raise ValueError("source_amplitude: every amplitude must be finite")
+        return p
+
+    def step(self, t, only=None, source_amplitude=None):
+        """One step to time ``t``.  With a source, ``source_amplitude`` = p(t) or the value itself (None: 0)."""
+        if self.source:
+            self.backend.set_source_amplitudes([] if source_amplitude is None else self._source_amplitudes(source_amplitude, [t]))
+        elif source_amplitude is not None:
+            self._source_amplitudes(source_amplitude, [t])
         g = self.bc_values(t, only)
         it, res = self.backend.step(g, self.rtol, self.atol, self.max_it)
         self.iters.append(it)
         return it, res
 
-    def run(self, num_steps, watcher_nodes=None, time_varying=None, first_step=0):
+    def run(self, num_steps, watcher_nodes=None, time_varying=None, first_step=0, source_amplitude=None):
         """``num_steps`` steps t_k = (k+1) dt in one backend call (hf_run): the boundary values
-        of all steps are tabulated on the host first.  Returns (times, samples, iters)."""
+        of all steps are tabulated on the host first.  Returns (times, samples, iters).  With a source,
+        ``source_amplitude`` = a callable p(t) evaluated at (k+1) dt or one value per step, in W/m^3 (None: amplitude 0)."""
         for bc in self.bcs:
             bc.update(0.0)
         times = (np.arange(first_step, first_step + num_steps) + 1) * self.dt
+        if self.source:
+            self.backend.set_source_amplitudes([] if source_amplitude is None else self._source_amplitudes(source_amplitude, times))
+        elif source_amplitude is not None:
+            self._source_amplitudes(source_amplitude, times)
         g_all = np.empty((num_steps, len(self.bc_dofs)), dtype=np.float64)
         for k, t in enumerate(times):
             g_all[k] = self.bc_values(t, time_varying)
@@ -285,6 +320,33 @@ class HeatProblem:
         Dirichlet rows, 0 on them; it becomes the load and is returned.  Needs a solve_steady before (for K)."""
         self.backend.hold_load()
         return self.backend.get_load()
+
+
+def check_source(source):
+    """dict(tags, fwhm, z0, depth) of a volumetric source with int tags and float numbers (depth absent or None: inf), or None;
+    ValueError for an unknown key, no tag, a tag listed twice, or a number hf_set_source would refuse (before any backend
+    call)."""
+    if source is None:
+        return None
+    src = dict(source)
+    unknown = sorted(set(src) - {"tags", "fwhm", "z0", "depth"})
+    if unknown:
+        raise ValueError(f"source: unknown key {unknown[0]!r} (tags, fwhm, z0, depth)")
+    for key in ("tags", "fwhm", "z0"):
+        if key not in src:
+            raise ValueError(f"source: {key} is missing")
+    tags = [int(t) for t in np.atleast_1d(src["tags"])]
+    if not tags or len(set(tags)) != len(tags):
+        raise ValueError(f"source: tags must name at least one cell tag, each once (got {tags!r})")
+    fwhm, z0 = float(src["fwhm"]), float(src["z0"])
+    depth = float("inf") if src.get("depth") is None else float(src["depth"])
+    if not (np.isfinite(fwhm) and fwhm > 0.0):
+        raise ValueError(f"source: fwhm must be positive and finite, got {fwhm!r}")
+    if not np.isfinite(z0):
+        raise ValueError(f"source: z0 must be finite, got {z0!r}")
+    if not depth > 0.0:
+        raise ValueError(f"source: depth must be positive (or inf for a uniform layer), got {depth!r}")
+    return {"tags": tags, "fwhm": fwhm, "z0": z0, "depth": depth}
 
 
 def check_k_aniso(k_aniso):

@@ -1,0 +1,206 @@
+"""Laser-power heating: the ``heating.source`` block of a configuration.
+
+    heating:
+      source:
+        material: p_coupler        # a name or a list of names
+        power: 0.5                 # absorbed peak power, W
+        fwhm: 1.0e-5               # beam FWHM; defaults to heating.fwhm
+        depth: 2.0e-8              # absorption length; absent = uniform through the layer
+        face: outer                # outer | inner: which z face of the (first) material z0 is; default outer
+        pulse: {t0: 1.0e-6, fwhm: 5.0e-7}     # Gaussian in time, peak 1; or {file: x.csv}
+        keep_line: false           # true keeps the heated Dirichlet line as well
+
+The source is q(z, r, t) = p(t) s(z, r) with s = exp(-4 ln2 r^2 / fwhm^2) exp(-|z - z0| / depth) inside the listed materials
+(hf_set_source forms its load F1 on the GPU).  The absorbed power is P(t) = power * pulse(t); the amplitude handed to the time
+loop is the peak power density p(t) = P(t) / (2 pi sum_i F1_i), because the hat functions sum to one: the configured power is the
+discrete model's power exactly.  ``pulse`` is a Gaussian in time of peak 1, exp(-4 ln2 (t - t0)^2 / fwhm^2), or a CSV file with
+the columns ``time`` and ``power`` (the pulse shape in units of ``power``; linear interpolation, 0 outside the file's times).
+
+This module parses and validates the block and computes the amplitudes; it touches no GPU.
+"""
+from __future__ import annotations
+
+import csv
+import math
+import os
+from dataclasses import dataclass
+
+import numpy as np
+
+KEY = "heating.source"
+SOURCE_KEYS = ("material", "power", "fwhm", "depth", "face", "pulse", "keep_line")
+PULSE_KEYS = ("t0", "fwhm", "file")
+FACES = ("outer", "inner")
+
+
+@dataclass(frozen=True)
+class SourceSpec:
+    """A validated ``heating.source`` block."""
+
+    materials: tuple        # material names, the first one carries z0's face
+    power: float            # absorbed peak power, W
+    fwhm: float             # beam FWHM, m
+    depth: float            # absorption length, m (inf: uniform through the layer)
+    face: str               # "outer" | "inner"
+    pulse: tuple            # ("gaussian", t0, fwhm) or ("file", path)
+    keep_line: bool
+
+    def z0(self, stack):
+        """z of the absorbing face: the z face of the first material away from the sample mid-plane z = 0 (outer) or towards it
+        (inner)."""
+        box = stack.by_name(self.materials[0]).boundaries
+        zmin, zmax = float(box[0]), float(box[1])
+        outer_is_min = 0.5 * (zmin + zmax) < 0.0
+        return zmin if outer_is_min == (self.face == "outer") else zmax
+
+    def problem_source(self, stack, material_tags):
+        """The ``source=`` argument of HeatProblem: cell tags, fwhm, z0, depth."""
+        return {"tags": [int(material_tags[m]) for m in self.materials], "fwhm": self.fwhm, "z0": self.z0(stack),
+                "depth": self.depth}
+
+    def used_config(self):
+        """The block as it ran, every default written out (used_config.yaml)."""
+        out = {"material": list(self.materials), "power": self.power, "fwhm": self.fwhm, "face": self.face,
+               "keep_line": self.keep_line}
+        if math.isfinite(self.depth):
+            out["depth"] = self.depth
+        out["pulse"] = {"t0": self.pulse[1], "fwhm": self.pulse[2]} if self.pulse[0] == "gaussian" else {"file": self.pulse[1]}
+        return out
+
+
+def source_block(cfg):
+    """The raw ``heating.source`` block of ``cfg``, or None when the key is absent (or null)."""
+    return (cfg.get("heating") or {}).get("source")
+
+
+def refuse_source(cfg, where):
+    """ValueError naming the key if ``cfg`` asks for a volumetric source: ``where`` does not support it."""
+    if source_block(cfg) is not None:
+        raise ValueError(f"{where} does not support the volumetric source ({KEY})")
+
+
+def _positive(block, key, value):
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"{KEY}.{key}: a number is expected, got {value!r}") from None
+    if not (math.isfinite(v) and v > 0.0):
+        raise ValueError(f"{KEY}.{key} must be positive and finite, got {value!r}")
+    return v
+
+
+def parse_source(cfg):
+    """The :class:`SourceSpec` of ``cfg``'s ``heating.source`` block, or None when the key is absent.  ValueError naming the key
+    or the material for an unknown key, an unknown material, a non-positive number, an unknown face, or both or neither form
+    of ``pulse``."""
+    block = source_block(cfg)
+    if block is None:
+        return None
+    if not isinstance(block, dict):
+        raise ValueError(f"{KEY} must be a mapping, got {block!r}")
+    for key in block:
+        if key not in SOURCE_KEYS:
+            raise ValueError(f"{KEY}: unknown key {key!r} (expected one of {', '.join(SOURCE_KEYS)})")
+    if "material" not in block:
+        raise ValueError(f"{KEY}.material is missing")
+    mats = block["material"]
+    mats = [mats] if isinstance(mats, str) else list(mats or [])
+    if not mats:
+        raise ValueError(f"{KEY}.material names no material")
+    known = cfg.get("mats") or {}
+    for m in mats:
+        if m not in known:
+            raise ValueError(f"{KEY}.material: unknown material {m!r} (the configuration has {', '.join(sorted(known))})")
+    if len(set(mats)) != len(mats):
+        raise ValueError(f"{KEY}.material lists a material twice: {mats!r}")
+    if "power" not in block:
+        raise ValueError(f"{KEY}.power is missing")
+    power = _positive(block, "power", block["power"])
+    if "fwhm" in block:
+        fwhm = _positive(block, "fwhm", block["fwhm"])
+    elif "fwhm" in (cfg.get("heating") or {}):
+        fwhm = _positive(block, "fwhm", cfg["heating"]["fwhm"])
+    else:
+        raise ValueError(f"{KEY}.fwhm is missing and there is no heating.fwhm to default to")
+    depth = _positive(block, "depth", block["depth"]) if block.get("depth") is not None else math.inf
+    face = block.get("face", "outer")
+    if face not in FACES:
+        raise ValueError(f"{KEY}.face must be one of {', '.join(FACES)}, got {face!r}")
+    pulse = block.get("pulse")
+    if not isinstance(pulse, dict):
+        raise ValueError(f"{KEY}.pulse is missing: either {{t0, fwhm}} (a Gaussian in time) or {{file}} (a CSV)")
+    for key in pulse:
+        if key not in PULSE_KEYS:
+            raise ValueError(f"{KEY}.pulse: unknown key {key!r} (expected t0 and fwhm, or file)")
+    gaussian = "t0" in pulse or "fwhm" in pulse
+    if gaussian == ("file" in pulse):
+        raise ValueError(f"{KEY}.pulse needs exactly one form: either t0 and fwhm (a Gaussian in time) or file (a CSV)")
+    if gaussian:
+        if "t0" not in pulse or "fwhm" not in pulse:
+            raise ValueError(f"{KEY}.pulse: a Gaussian pulse needs both t0 and fwhm")
+        try:
+            t0 = float(pulse["t0"])
+        except (TypeError, ValueError):
+            raise ValueError(f"{KEY}.pulse.t0: a number is expected, got {pulse['t0']!r}") from None
+        if not math.isfinite(t0):
+            raise ValueError(f"{KEY}.pulse.t0 must be finite, got {pulse['t0']!r}")
+        spec = ("gaussian", t0, _positive(block, "pulse.fwhm", pulse["fwhm"]))
+    else:
+        spec = ("file", str(pulse["file"]))
+    keep = block.get("keep_line", False)
+    if not isinstance(keep, bool):
+        raise ValueError(f"{KEY}.keep_line must be true or false, got {keep!r}")
+    return SourceSpec(tuple(mats), power, fwhm, depth, face, spec, keep)
+
+
+def read_pulse_csv(path):
+    """(time, power) of a pulse file, sorted by time; ValueError when a column is missing or no row is numeric."""
+    times, vals = [], []
+    with open(path, newline="") as f:
+        rd = csv.DictReader(f)
+        cols = rd.fieldnames or []
+        for c in ("time", "power"):
+            if c not in cols:
+                raise ValueError(f"{KEY}.pulse.file {path} must contain a '{c}' column")
+        for row in rd:
+            try:
+                t, v = float(row["time"]), float(row["power"])
+            except (TypeError, ValueError):
+                continue
+            if math.isnan(t) or math.isnan(v):
+                continue
+            times.append(t)
+            vals.append(v)
+    if not times:
+        raise ValueError(f"{KEY}.pulse.file {path} holds no numeric rows")
+    order = np.argsort(np.array(times), kind="stable")
+    return np.array(times)[order], np.array(vals)[order]
+
+
+def pulse_values(spec, times, resolve=None):
+    """pulse(t) at ``times``: the Gaussian of peak 1, or the file's shape by linear interpolation (0 outside its times).
+    ``resolve``: maps the file's path as written to the one to open."""
+    t = np.asarray(times, dtype=np.float64)
+    if spec.pulse[0] == "gaussian":
+        _, t0, fwhm = spec.pulse
+        return np.exp(-4.0 * math.log(2.0) * (t - t0) ** 2 / (fwhm * fwhm))
+    path = spec.pulse[1]
+    if resolve is not None:
+        path = resolve(path)
+    elif not os.path.isfile(path):
+        raise FileNotFoundError(f"{KEY}.pulse.file: {path} not found")
+    tt, vv = read_pulse_csv(path)
+    return np.interp(t, tt, vv, left=0.0, right=0.0)
+
+
+def power_density(power_watts, source_vector):
+    """W -> W/m^3: the amplitude p with 2 pi p sum_i F1_i = power, F1 the source's load at unit amplitude."""
+    total = math.fsum(float(v) for v in np.asarray(source_vector, dtype=np.float64))
+    if not total > 0.0:
+        raise ValueError(f"{KEY}: the source vector sums to {total!r} - no absorbing element carries the beam")
+    return np.asarray(power_watts, dtype=np.float64) / (2.0 * math.pi * total)
+
+
+def amplitudes(spec, times, source_vector, resolve=None):
+    """The peak power densities p_k (W/m^3) of the steps that end at ``times``: power * pulse(t_k) / (2 pi sum F1)."""
+    return power_density(spec.power * pulse_values(spec, times, resolve), source_vector)

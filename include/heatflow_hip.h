@@ -350,6 +350,29 @@ int hf_set_load(hf_ctx* ctx, const double* F);
 int hf_hold_load(hf_ctx* ctx);
 int hf_get_load(hf_ctx* ctx, double* F);
 
+/* Volumetric source of the time step: laser power absorbed in some cell tags.  The source is separable,
+ * q(z, r, t) = p(t) s(z, r), with s = exp(-4 ln2 r^2 / fwhm^2) exp(-|z - z0| / depth) inside the elements of the listed tags
+ * (depth = +inf: uniform in z) and zero elsewhere.  s enters as its P1 interpolant inside each absorbing element:
+ *     F1_i = sum over e at i with tag(e) listed, sum over j in e, of (M_e at rho_c = 1)_ij s(z_j, r_j)
+ * formed on the device by the row-gather kernel k_source_load (bitwise reproducible; rows without an absorbing triangle are 0).
+ * Every hf_step / hf_run step then uses b = M u^n + dt (F0 + p_k F1) - BDF2: 2/3 dt, both terms at t_{n+1} - with F0 the load
+ * of hf_set_load / hf_hold_load if one is set, and p_k the step's amplitude (a peak power density, W/m^3).
+ * hf_set_source   needs a mesh with row-gather lists (HF_ERR_ARG otherwise); n_tags = 0 clears the source.  HF_ERR_ARG: a tag
+ *        that is not a cell tag of the mesh, a tag listed twice, fwhm not positive and finite, z0 not finite, depth not positive
+ *        (+inf is allowed).  HF_ERR_STATE: before hf_set_mesh, or while a batch is open.  hf_set_mesh clears it; it survives
+ *        hf_set_materials, hf_assemble and hf_update_kappa (it does not depend on the coefficients).  A new source starts with
+ *        an empty amplitude list.
+ * hf_get_source   copies F1 out (n doubles; HF_ERR_STATE if no source is set).
+ * hf_set_source_amplitudes   the amplitudes of the next n_amp steps: step k after the call uses p[k].  A step or run that
+ *        reaches beyond the list returns HF_ERR_STATE before any launch; a non-finite entry is HF_ERR_ARG; n_amp = 0 means
+ *        amplitude 0 for every step.  HF_ERR_STATE if no source is set.
+ * While a source is set hf_batch_begin, hf_tangent_setup, hf_tangent_setup_dir and hf_run_tangent return HF_ERR_STATE, as they
+ * do for a load.  The steady solves ignore the source: a continuous-wave laser of amplitude p is hf_set_load(p * F1) with F1 from
+ * hf_get_source, and then every call that takes a load (hf_steady_solve with use_load, hf_hold_load's sequence) applies. */
+int hf_set_source(hf_ctx* ctx, int32_t n_tags, const int32_t* tags, double fwhm, double z0, double depth);
+int hf_get_source(hf_ctx* ctx, double* F);
+int hf_set_source_amplitudes(hf_ctx* ctx, int32_t n_amp, const double* p);
+
 /* Tangent runs: the exact derivatives s_j = du/dtheta_j of the time loop with respect to up to 16 parameters, advanced next to
  * the primal.  A column's parameter scales the conductivity of the cell tags mapped to it (K_j = the sum of
  * their unit-conductivity r-weighted stiffness), enters the Dirichlet values through h_j = dg/dtheta_j, or both.  After every

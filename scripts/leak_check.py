@@ -21,6 +21,11 @@ for rep in range(12):
     be.batch_run(g, prob.rtol, 0.0, prob.max_it, None)
     be.batch_end()
     be.flux_setup(); be.flux_solve(prob.rtol, 5000)
+    # closed with a source and a load still set (after a step that used both): hf_destroy has to free them
+    be.set_source([mesh.material_tags["p_coupler"]], 1.4e-5, float(stack.by_name("p_coupler").boundaries[0]), 2.0e-8)
+    be.set_load(be.get_source())
+    be.set_source_amplitudes([1.0])
+    be.step(prob.bc_values(prob.dt, [prob.bcs[3]]), prob.rtol, 0.0, prob.max_it)
     prob.close()
     vals.append(free_mb())
 print("free MB after each create/run/destroy cycle:", [round(v) for v in vals])
