@@ -42,16 +42,18 @@ def coarse_apply(H, b):
     return X @ b
 
 
-def stored_cycle(H, A0, dinv0, r, stale=False, explicit=False):
+def stored_cycle(H, A0, dinv0, r, stale=False, explicit=False, post=True):
     """z = B r with the blob's stored operators.  ``stale``: the fine operator was re-valued under the frozen hierarchy
     (hf_update_kappa with reuse): a fused down leg alone gives way to the explicit one over the new A0 (vcycle()).
-    ``explicit``: both finest legs explicit whatever the blob holds (the batched cycle, BatchOps::vcycle)."""
+    ``explicit``: both finest legs explicit whatever the blob holds (the batched cycle, BatchOps::vcycle).  ``post`` = False (with
+    ``explicit``): the finest level's post-smoothing sweep is left out - a non-symmetric B, the fault tests/pcg_oracle.py injects."""
     L = H["levels"]
     nl = len(L)
     w0 = L[0]["omega"]
     z0 = w0 * (dinv0 * r)                              # what k_pcg_update_amg leaves: w * (D^-1 r)
+    assert post or explicit
     if nl == 1:
-        return z0 + w0 * dinv0 * (r - A0 @ z0)
+        return z0 + w0 * dinv0 * (r - A0 @ z0) if post else z0
     fused0 = L[0]["GP"] is not None and not explicit
     b = [None] * nl
     if L[0]["Rt"] is not None and not explicit and (fused0 or not stale):
@@ -66,7 +68,7 @@ def stored_cycle(H, A0, dinv0, r, stale=False, explicit=False):
     if fused0:
         return _m(L[0]["GP"]) @ np.concatenate([r, x])
     z = z0 + _m(L[0]["P"]) @ x
-    return z + w0 * dinv0 * (r - A0 @ z)
+    return z + w0 * dinv0 * (r - A0 @ z) if post else z
 
 
 def definition_cycle(H, A0, dinv0, r, coarse_solve=None):
