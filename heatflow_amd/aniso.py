@@ -43,16 +43,21 @@ def material_aniso(name, mat):
 
 
 PARAM_KINDS = {"k": "k", "k_r": "r", "k_z": "z"}     # suffix of a tangent / fit parameter -> column kind of run_tangent
+THICKNESS = "thickness"                              # suffix of a layer-thickness parameter -> kind "t" (a shape column)
 
 
 def split_param(name):
-    """("<material>", "k" | "r" | "z") of a parameter spelt ``<material>.k``, ``<material>.k_r`` or ``<material>.k_z``;
-    (name, None) for a name without a dot.  ValueError naming the parameter for any other suffix."""
+    """("<material>", "k" | "r" | "z") of a parameter spelt ``<material>.k``, ``<material>.k_r`` or ``<material>.k_z``,
+    ("<material>", "t") of ``<material>.thickness``; (name, None) for a name without a dot.  ValueError naming the parameter for
+    any other suffix."""
     if "." not in name:
         return name, None
     mat, suffix = name.rsplit(".", 1)
+    if suffix == THICKNESS:
+        return mat, "t"
     if suffix not in PARAM_KINDS:
-        raise ValueError(f"parameter {name!r}: unknown suffix {suffix!r} (<material>.k, <material>.k_r or <material>.k_z)")
+        raise ValueError(f"parameter {name!r}: unknown suffix {suffix!r} (<material>.k, <material>.k_r, <material>.k_z or "
+                         f"<material>.thickness)")
     return mat, PARAM_KINDS[suffix]
 
 

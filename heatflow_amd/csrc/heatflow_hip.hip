@@ -100,6 +100,7 @@ int source_steps_ok(hf_ctx* ctx, int64_t n_steps, const char* call) {
 void tangent_free(hf_ctx* ctx) {
   free_batch_state(ctx->tanb);
   dev_free(&ctx->tan.col); dev_free(&ctx->tan.dir); dev_free(&ctx->tan.F);
+  dev_free(&ctx->tan.sh.d_v); dev_free(&ctx->tan.sh.un); dev_free(&ctx->tan.sh.um1);
   ctx->tan = hf_ctx::Tangent();
 }
 
@@ -556,6 +557,7 @@ int tangent_reset(hf_ctx* ctx) {
   for (bool& u_ : T.pused) u_ = false;
   T.pnext = 0; T.ppending = -1;
   T.pred_iters = 0;
+  ctx->tan.sh.wmode = 0;   // the states kept for the shape columns' load belonged to the old trajectory; the velocities stay
   return HF_OK;
 }
 
@@ -574,7 +576,43 @@ int tangent_levels(hf_ctx* ctx) {
   return HF_OK;
 }
 
-// F = -K_j u for every tangent column j, from the context's current state, by the kernel of the set-up in force
+// The shape columns' part of the load (k_tangent_load_shape<NS>), added to what the load kernel of the set-up wrote: LDS for w and
+// the NS velocities next to k_tangent_load's footprint, persistent workgroups from one occupancy query per mesh
+template <int NS>
+int tangent_load_shape(hf_ctx* ctx, RgVariant id) {
+  const hf_ctx::Tangent::Shape& S = ctx->tan.sh;
+  const int capd = ctx->rg_max_dict;
+  const size_t sm = static_cast<size_t>(capd) * 16 + 2 * static_cast<size_t>(capd + (capd & 1)) * 8 +
+                    static_cast<size_t>((capd * NS + 1) & ~1) * 8 + (RBA + 4) * 4 +
+                    (static_cast<size_t>((ctx->max_blk_nnz + 1) & ~1) / 8 + 3) * 16;
+  int& grid = ctx->rg_grid[id];
+  if (grid == 0) {
+    const void* fn = reinterpret_cast<const void*>(&k_tangent_load_shape<NS>);
+    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
+    int per_cu = 0, ncu = 0;
+    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
+    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
+    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+    if (std::getenv("HEATFLOW_DEBUG"))
+      std::fprintf(stderr, "[tangent shape] k_tangent_load_shape<%d>: column list %d slots, %zu B dynamic LDS, %d workgroups per CU, grid %d of %d row blocks\n",
+                   NS, capd, sm, per_cu, grid, ctx->nblk_a);
+  }
+  const bool bdf2 = S.wmode == 2;
+  ShapeArgs a;
+  for (int s = 0; s < 4; ++s) a.dst[s] = S.col[s];
+  a.nv = ctx->tan.nv;
+  a.wmode = S.wmode;
+  a.dtp = ctx->dt;   // the operator's step: dt, or dt' = 2/3 dt under BDF2 (hf_assemble)
+  hipLaunchKernelGGL(k_tangent_load_shape<NS>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr,
+                     reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
+                     ctx->d_rg_dict, ctx->d_rowptr, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->an.on ? ctx->an.d_m : nullptr, ctx->d_u,
+                     S.un, bdf2 && S.hist ? S.um1 : S.un, S.d_v, a, ctx->tan.F);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+// F = -K_j u for every tangent column j, from the context's current state, by the kernel of the set-up in force; the columns
+// with a shape part (hf_tangent_set_shape) then get -Kdot u - Mdot w added
 int tangent_load(hf_ctx* ctx) {
   const int capd = ctx->rg_max_dict;
   const size_t sm = static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 + (RBA + 4) * 4 +
@@ -604,6 +642,13 @@ int tangent_load(hf_ctx* ctx) {
 #undef HF_TLD
 #undef HF_TL
   HF_HIP(hipGetLastError());
+  if (ctx->tan.sh.ncol > 0) {
+    switch (ctx->tan.sh.ns) {
+      case 1: return tangent_load_shape<1>(ctx, RG_SHAPE1);
+      case 2: return tangent_load_shape<2>(ctx, RG_SHAPE2);
+      default: return tangent_load_shape<4>(ctx, RG_SHAPE4);
+    }
+  }
   return HF_OK;
 }
 
@@ -1496,6 +1541,53 @@ int hf_tangent_setup_dir(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col_k, c
   return HF_OK;
 }
 
+int hf_tangent_set_shape(hf_ctx* ctx, int32_t j, const double* vz) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_shape before hf_tangent_setup / hf_tangent_setup_dir");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_shape: a batch is open");
+  if (j < 0 || j >= ctx->tan.npar) return fail(ctx, HF_ERR_ARG, "hf_tangent_set_shape: column %d outside [0,%d)", j, ctx->tan.npar);
+  hf_ctx::Tangent::Shape& S = ctx->tan.sh;
+  const size_t n = static_cast<size_t>(ctx->n);
+  int slot = -1;
+  for (int s = 0; s < S.ncol; ++s)
+    if (S.col[s] == j) slot = s;
+  if (vz) {
+    for (size_t i = 0; i < n; ++i)
+      if (!std::isfinite(vz[i])) return fail(ctx, HF_ERR_ARG, "hf_tangent_set_shape: the velocity of node %zu is not finite", i);
+    if (slot < 0 && S.ncol == 4)
+      return fail(ctx, HF_ERR_ARG, "hf_tangent_set_shape: column %d would be a fifth shape column (at most 4 per set-up)", j);
+  } else if (slot < 0) {
+    return HF_OK;   // the column had no shape part
+  }
+  HF_HIP(hipSetDevice(ctx->dev));
+  if (vz) {
+    if (slot < 0) slot = S.ncol++;
+    S.col[slot] = j;
+    S.h_v[slot].assign(vz, vz + n);
+  } else {
+    for (int s = slot; s + 1 < S.ncol; ++s) { S.col[s] = S.col[s + 1]; S.h_v[s].swap(S.h_v[s + 1]); }
+    S.ncol -= 1;
+    S.h_v[S.ncol].clear();
+    S.h_v[S.ncol].shrink_to_fit();
+  }
+  dev_free(&S.d_v);
+  if (S.ncol == 0) {
+    dev_free(&S.un); dev_free(&S.um1);
+    S = hf_ctx::Tangent::Shape();
+    return tangent_reset(ctx);
+  }
+  S.ns = S.ncol <= 1 ? 1 : S.ncol <= 2 ? 2 : 4;
+  for (int s = S.ncol; s < 4; ++s) S.col[s] = S.col[0];    // unused slots: zero velocities into a column that exists
+  std::vector<double> v(n * S.ns, 0.0);
+  for (int s = 0; s < S.ncol; ++s)
+    for (size_t i = 0; i < n; ++i) v[i * S.ns + s] = S.h_v[s][i];
+  HF_TRY(dev_alloc(ctx, &S.d_v, n * S.ns));
+  if (!S.un) HF_TRY(dev_alloc(ctx, &S.un, n));
+  if (!S.um1) HF_TRY(dev_alloc(ctx, &S.um1, n));
+  HF_HIP(copy_sync(ctx, S.d_v, v.data(), sizeof(double) * n * S.ns, hipMemcpyHostToDevice));
+  return tangent_reset(ctx);   // the tangents belonged to the old parameter
+}
+
 int hf_tangent_load(hf_ctx* ctx, int32_t j, double* F) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_tangent_load before hf_tangent_setup / hf_tangent_setup_dir");
@@ -1549,6 +1641,14 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
   int rc = HF_OK;
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   for (int32_t s = 0; s < n_steps && rc == HF_OK; ++s) {
+    if (ctx->tan.sh.ncol > 0) {   // shape columns: their load needs u^n and (BDF2) u^{n-1} after the step has moved the buffers
+      hf_ctx::Tangent::Shape& S = ctx->tan.sh;
+      const bool bdf2 = ctx->scheme == HF_TIME_BDF2;
+      S.hist = bdf2 && ctx->bdf_hist;
+      if (S.hist) HF_HIP(hipMemcpyAsync(S.um1, ctx->d_uprev, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+      HF_HIP(hipMemcpyAsync(S.un, ctx->d_u, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+      S.wmode = bdf2 ? 2 : 1;
+    }
     // the primal step, exactly hf_run's
     rc = step_device(ctx, ctx->nbc > 0 ? g_all + static_cast<size_t>(s) * ctx->nbc : nullptr,
                      ctx->nbc > 0 ? t_gall.p + static_cast<size_t>(s) * ctx->nbc : nullptr, rtol, atol, max_it);

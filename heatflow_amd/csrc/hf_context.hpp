@@ -107,7 +107,7 @@ struct TanDir { int32_t c_r, c_z; double w_r, w_z; };
 
 // The row-gather assembly kernels: k_assemble_rows<false / true>, k_assemble_rows_an<false / true>, k_assemble_rows_kT,
 // k_assemble_rows_cT, k_assemble_rows_kT_K
-enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_SOURCE, RG_VARIANTS };
+enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_SOURCE, RG_SHAPE1, RG_SHAPE2, RG_SHAPE4, RG_VARIANTS };
 
 }  // namespace
 
@@ -364,6 +364,17 @@ struct hf_ctx {
     double* F = nullptr;         // n x nv, interleaved
     bool steady_state = false;   // the state comes from hf_steady_solve (it depends on kappa; s^0 = 0 would be wrong) until hf_set_state
     std::vector<int64_t> lev_sig;   // multigrid level sizes tanb.lev was laid out for
+    // shape columns (hf_tangent_set_shape): up to 4 columns carry a nodal z-velocity; k_tangent_load_shape<ns>
+    // adds their part of the load.  Nothing below is allocated or touched while no column has one (ncol == 0).
+    struct Shape {
+      int ncol = 0, ns = 0;            // columns with a velocity; slots of the kernel (1, 2, 4)
+      int32_t col[4] = {0, 0, 0, 0};   // F column of each slot (a slot past ncol repeats slot 0's with zero velocities)
+      std::vector<double> h_v[4];      // the velocities of slot s, as given
+      double* d_v = nullptr;           // n x ns, interleaved by node
+      double *un = nullptr, *um1 = nullptr;   // u^n and u^{n-1} of the last step of hf_run_tangent (copies, kept for the load)
+      int wmode = 0;                   // of that step: 0 = none taken since the last reset, 1 = backward Euler, 2 = BDF2
+      bool hist = false;               // um1 holds u^{n-1} (false: a rest start, u^{n-1} = u^n)
+    } sh;
   } tan;
   int fsamp_cap = 0;
   // temperature-dependent conductivities (hf_set_kappa_tables): per row-gather tag-dictionary entry a table header (KTab,

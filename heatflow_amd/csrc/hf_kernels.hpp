@@ -704,6 +704,143 @@ __global__ __launch_bounds__(RBA) void k_tangent_load_dir(int nblk, int capd, co
   }
 }
 
+// Shape columns of a tangent run (hf_tangent_set_shape): the nodes move along z with the velocity v of a column,
+// the triangles stay.  With the letters of element_row_of (x = z, y = r), edot_a.x the difference of v over edge a, edot_a.y = 0:
+//   D = e_j.x e_k.y - e_j.y e_k.x (signed twice-area),  Ddot = edot_j.x e_k.y - e_j.y edot_k.x,  delta = Ddot / D
+//   Mdot_e = delta M_e,   Kdot_ab = -delta K_ab + ks k_r (edot_a.x e_b.x + e_a.x edot_b.x),  ks = area (rsum / 3) / d^2, d = |D|
+// isotropic tags with k_r = k_z = kappa.  What one visit shares between the columns:
+struct ShapeVisit {
+  double mk;            // (M_e w)_me - (K_e u)_me: delta multiplies it
+  double kk;            // ks k_r
+  double inv_D;         // 1 / D
+  double eix, ejx, ekx, ejy, eky;
+};
+__device__ __forceinline__ ShapeVisit shape_visit(const double2 Pi, const double2 Pj, const double2 Pk, double rho_c, double k_z, double k_r,
+                                                  double ui, double uj, double uk, double wi, double wj, double wk) {
+#pragma clang fp contract(off)
+  const double eix = Pk.x - Pj.x, eiy = Pk.y - Pj.y;     // edge opposite "me"
+  const double ejx = Pi.x - Pk.x, ejy = Pi.y - Pk.y;     // opposite next
+  const double ekx = Pj.x - Pi.x, eky = Pj.y - Pi.y;     // opposite previous
+  const double D = ejx * eky - ejy * ekx;
+  const double d = fabs(D);
+  const double rsum = sorted_sum3(Pi.y, Pj.y, Pk.y);
+  const double area = 0.5 * d;
+  const double ks = area * (rsum * (1.0 / 3.0)) * (1.0 / (d * d));
+  const double ms30 = rho_c * area * (1.0 / 30.0), ms60 = rho_c * area * (1.0 / 60.0);
+  const double k0 = ks * (k_r * (eix * eix) + k_z * (eiy * eiy));
+  const double k1 = ks * (k_r * (eix * ejx) + k_z * (eiy * ejy));
+  const double k2 = ks * (k_r * (eix * ekx) + k_z * (eiy * eky));
+  const double m0 = ms30 * (2.0 * Pi.y + rsum);
+  const double m1 = ms60 * (rsum + (Pi.y + Pj.y));
+  const double m2 = ms60 * (rsum + (Pi.y + Pk.y));
+  ShapeVisit o;
+  o.mk = ((m0 * wi + m1 * wj) + m2 * wk) - ((k0 * ui + k1 * uj) + k2 * uk);
+  o.kk = ks * k_r;
+  o.inv_D = 1.0 / D;
+  o.eix = eix; o.ejx = ejx; o.ekx = ekx; o.ejy = ejy; o.eky = eky;
+  return o;
+}
+
+// (Kdot_e u)_me + (Mdot_e w)_me of one column from its velocities at the visit's three nodes
+__device__ __forceinline__ double shape_term(const ShapeVisit& s, double vi, double vj, double vk, double ui, double uj, double uk) {
+#pragma clang fp contract(off)
+  const double dix = vk - vj, djx = vi - vk, dkx = vj - vi;
+  const double delta = (djx * s.eky - s.ejy * dkx) * s.inv_D;
+  const double g = (((dix * s.eix + s.eix * dix) * ui + (dix * s.ejx + s.eix * djx) * uj) + (dix * s.ekx + s.eix * dkx) * uk);
+  return delta * s.mk + s.kk * g;
+}
+
+struct ShapeArgs {
+  int32_t dst[4];       // F column of each shape slot
+  int32_t nv;           // columns of F
+  int32_t wmode;        // w: 0 = zero (no step taken), 1 = (u - un) / dtp (backward Euler), 2 = ((u - 4/3 un) + 1/3 um1) / dtp (BDF2)
+  double dtp;           // dt (backward Euler), 2/3 dt (BDF2)
+};
+
+// k_tangent_load's sibling for shape columns (same lists, block staging and launch geometry): it adds
+//   F[i * nv + dst[s]] -= sum over the triangles e at node i of (Kdot_e^s u)_i + (Mdot_e^s w)_i,   s < NS,
+// to what the load kernel of the set-up wrote.  Next to the coordinates and u = u^{n+1} the block's column nodes get w (formed
+// here from u, un = u^n and um1 = u^{n-1}) and their NS velocities (vz, interleaved by node).  kappa, rho_c and the multipliers
+// (m_z, m_r; null = none set) by tag-dictionary index, as the assembly kernels read them.  Each slot's sum runs in list order in
+// a register of the row's lane - no atomics, bitwise reproducible.  A triangle whose three velocities agree contributes an exact 0.
+template <int NS>
+__global__ __launch_bounds__(RBA) void k_tangent_load_shape(int nblk, int capd, const int4* __restrict__ hdr, const uint4* __restrict__ ell,
+                                                            const uint4* __restrict__ cid16, const double2* __restrict__ zrb,
+                                                            const int32_t* __restrict__ dict, const int32_t* __restrict__ rowptr,
+                                                            const double* __restrict__ kappa_idx, const double* __restrict__ rhoc_idx,
+                                                            const double2* __restrict__ an_idx, const double* __restrict__ u,
+                                                            const double* __restrict__ un, const double* __restrict__ um1,
+                                                            const double* __restrict__ vz, ShapeArgs a, double* __restrict__ F) {
+  extern __shared__ double smem[];
+  __shared__ double skr[64], skz[64], src[64];
+  const int capw = capd + (capd & 1), capv = (capd * NS + 1) & ~1;
+  double2* sXd = reinterpret_cast<double2*>(smem);
+  double* sU = smem + 2 * capd;
+  double* sW = sU + capw;
+  double* sV = sW + capw;
+  int* sR = reinterpret_cast<int*>(sV + capv);
+  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);
+  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
+  const int t = threadIdx.x;
+  if (t < 64) {
+#pragma clang fp contract(off)
+    const double kap = kappa_idx[t];
+    const double2 m = an_idx ? an_idx[t] : make_double2(1.0, 1.0);
+    skz[t] = m.x * kap;
+    skr[t] = m.y * kap;
+    src[t] = rhoc_idx[t];
+  }
+  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const int4 cA = hdr[2 * blk], cB = hdr[2 * blk + 1];
+    const int c0 = cA.x >> 3, nc = ((cA.x + cA.y + 7) >> 3) - c0;
+    for (int i = t; i < nc; i += RBA) sC4[i] = cid16[c0 + i];
+    for (int i = t; i < cA.w; i += RBA) {
+#pragma clang fp contract(off)
+      const int node = dict[cA.z + i];
+      const double u1 = u[node];
+      sXd[i] = zrb[cA.z + i];
+      sU[i] = u1;
+      double w = 0.0;
+      if (a.wmode == 1) w = (u1 - un[node]) / a.dtp;
+      else if (a.wmode == 2) w = ((u1 - (4.0 / 3.0) * un[node]) + (1.0 / 3.0) * um1[node]) / a.dtp;
+      sW[i] = w;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) sV[i * NS + s] = vz[static_cast<size_t>(node) * NS + s];
+    }
+    if (t < cB.w) sR[t] = rowptr[blk * RBA + t] - cA.x;
+    __syncthreads();
+    if (t < cB.w) {
+#pragma clang fp contract(off)
+      const int sbase = sR[t] + (cA.x & 7);
+      const int ci = cB.z + t;
+      const double2 Pi = sXd[ci];
+      const double ui = sU[ci], wi = sW[ci];
+      double vi[NS], acc[NS];
+#pragma unroll
+      for (int s = 0; s < NS; ++s) { vi[s] = sV[ci * NS + s]; acc[s] = 0.0; }
+      for (int g = 0; g < cB.y; ++g) {
+        const uint4 ev = ell[cB.x + g * RBA + t];
+        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
+          if (e == 0xFFFFu) continue;
+          const int tg = e >> 10;
+          const int pj = sC[sbase + (e & 31u)], pk = sC[sbase + ((e >> 5) & 31u)];
+          const double uj = sU[pj], uk = sU[pk];
+          const ShapeVisit sv = shape_visit(Pi, sXd[pj], sXd[pk], src[tg], skz[tg], skr[tg], ui, uj, uk, wi, sW[pj], sW[pk]);
+#pragma unroll
+          for (int s = 0; s < NS; ++s) acc[s] += shape_term(sv, vi[s], sV[pj * NS + s], sV[pk * NS + s], ui, uj, uk);
+        }
+      }
+      double* out = F + static_cast<size_t>(blk * RBA + t) * a.nv;
+#pragma unroll
+      for (int s = 0; s < NS; ++s) out[a.dst[s]] -= acc[s];
+    }
+    __syncthreads();
+  }
+}
+
 // Shape of the volumetric source (hf_set_source) at a node P = (z, r): s = exp(-(c_r r^2 + |z - z0| inv_depth)),
 // c_r = 4 ln2 / fwhm^2 and inv_depth = 1 / depth, both formed on the host (inv_depth = 0: uniform through the layer).
 // One double-precision exp per node; the argument is formed without contraction, so it has the bits of its restatement.

@@ -40,7 +40,7 @@ def _dump_yaml(obj, f):
 
 
 from .bc import P1Space, RowDirichletBC
-from .geometry import stack_no_diamond, stack_with_diamond
+from .geometry import check_thickness_name, stack_no_diamond, stack_with_diamond, thickness_velocity
 from .heating import HeatingCurve
 from .aniso import DIRECTIONAL_HINT, check_config, refuse_aniso, split_param
 from .kappa_t import material_cv_table, material_table, picard_sweeps, refuse_tables
@@ -496,8 +496,9 @@ class SimulationSession:
         per-step gradient projection of run_no_diamond.py:543-566 (``flux`` entry of the result).
         ``tangents`` = parameter names (material names - the derivative with respect to that material's conductivity
         k -, "<material>.k_r" / "<material>.k_z" / "<material>.k" - its radial, its axial conductivity in W/m/K, or the
-        scalar k of both with the ratio of ``k_aniso`` kept; on isotropic materials the derivatives at m = (1, 1) -, and / or
-        "fwhm" of the heating profile) adds ``tangents`` {param: {watcher: d watcher / d param}} and
+        scalar k of both with the ratio of ``k_aniso`` kept; on isotropic materials the derivatives at m = (1, 1) -,
+        "<material>.thickness" - the layer thickness ``mats.<material>.z`` in metres, the nodes of this session's mesh moving
+        with the stack (geometry.thickness_velocity) -, and / or "fwhm" of the heating profile) adds ``tangents`` {param: {watcher: d watcher / d param}} and
         ``tangent_iters`` (HeatProblem.run_tangent; not with a field sink or the flux projection).
         A ``heating.source`` block (heatflow_amd.source) drives the run by absorbed laser power, the field sink and the flux
         projection included; not with ``tangents`` or ``two_sided``."""
@@ -547,7 +548,7 @@ class SimulationSession:
             if field_sink is not None or flux is not None:
                 raise ValueError("tangents: not combined with a field sink or the read-flux projection")
             params = list(tangents)
-            cond, bnd = [], {}
+            cond, bnd, shp = [], {}, {}
             for j, p in enumerate(params):
                 if p == "fwhm":
                     cond.append([])
@@ -561,10 +562,18 @@ class SimulationSession:
                         raise ValueError(f"tangents: {e}") from None
                     if kind is None or mat not in self.material_tags:
                         raise ValueError(f"tangents: unknown parameter {p!r} (a material name, <material>.k_r, "
-                                         "<material>.k_z, <material>.k or 'fwhm')")
-                    cond.append([(self.material_tags[mat], kind)])
+                                         "<material>.k_z, <material>.k, <material>.thickness or 'fwhm')")
+                    if kind == "t":      # a layer thickness: the nodes of this session's mesh move with the stack of ``cfg``
+                        try:
+                            check_thickness_name(cfg, mat, p)
+                        except ValueError as e:
+                            raise ValueError(f"tangents: {e}") from None
+                        cond.append([])
+                        shp[j] = thickness_velocity(cfg, mat, self.coords[:, 0])
+                    else:
+                        cond.append([(self.material_tags[mat], kind)])
             times, samples, tsamp, iters, titers = prob.run_tangent(num_steps, nodes, conductivity=cond, boundary=bnd,
-                                                                    time_varying=varying)
+                                                                    time_varying=varying, **({"shape": shp} if shp else {}))
             tangent_out = {p: {nm: tsamp[:, j, k] for k, nm in enumerate(names)} for j, p in enumerate(params)}
         elif field_sink is None and flux is None:
             times, samples, iters = prob.run(num_steps, watcher_nodes=nodes, time_varying=varying,

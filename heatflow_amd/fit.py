@@ -19,6 +19,7 @@ import time
 
 import numpy as np
 
+from .geometry import check_thickness_name, thickness_velocity
 from .parameter_sweep import build_stack, get_watcher_points, oside_curves
 from .aniso import DIRECTIONAL_HINT, KEY, material_aniso, refuse_aniso, split_param
 from .kappa_t import refuse_tables
@@ -37,13 +38,17 @@ def _material_param(cfg, name):
 
 
 def get_param(cfg, name):
-    """The value of a parameter: "fwhm", a material's k ("<m>" or "<m>.k"), or its directional conductivity "<m>.k_r" =
-    k * k_aniso.r / "<m>.k_z" = k * k_aniso.z in W/m/K (multiplier 1 where the block or the key is absent)."""
+    """The value of a parameter: "fwhm", a material's k ("<m>" or "<m>.k"), its directional conductivity "<m>.k_r" =
+    k * k_aniso.r / "<m>.k_z" = k * k_aniso.z in W/m/K (multiplier 1 where the block or the key is absent), or its layer
+    thickness "<m>.thickness" = mats.<m>.z in metres (the materials whose z the stack reads)."""
     if name == "fwhm":
         return float(cfg["heating"]["fwhm"])
     mat, kind = _material_param(cfg, name)
     if kind in (None, "k"):
         return float(mat["k"])
+    if kind == "t":
+        check_thickness_name(cfg, name.rsplit(".", 1)[0], name)
+        return float(mat["z"])
     m = material_aniso(name.rsplit(".", 1)[0], mat) or (1.0, 1.0)
     return float(mat["k"]) * m[0 if kind == "r" else 1]
 
@@ -51,7 +56,7 @@ def get_param(cfg, name):
 def set_params(cfg, params, values):
     """A copy of ``cfg`` with the parameters set: "fwhm" of the heating profile, the conductivity k of a material ("<m>" or
     "<m>.k"; the multipliers of a ``k_aniso`` block stay), or a directional conductivity: "<m>.k_r" writes k_aniso.r = value / k,
-    "<m>.k_z" k_aniso.z, creating the block where absent.  The k parameters are applied first, so a directional value holds
+    "<m>.k_z" k_aniso.z, creating the block where absent; "<m>.thickness" writes mats.<m>.z in metres.  The k parameters are applied first, so a directional value holds
     whatever the order of the names."""
     c = copy.deepcopy(cfg)
     pairs = list(zip(params, values))
@@ -60,6 +65,9 @@ def set_params(cfg, params, values):
             c["heating"]["fwhm"] = float(v)
         elif _material_param(c, name)[1] in (None, "k"):
             _material_param(c, name)[0]["k"] = float(v)
+        elif _material_param(c, name)[1] == "t":
+            check_thickness_name(c, name.rsplit(".", 1)[0], name)
+            _material_param(c, name)[0]["z"] = float(v)
     for name, v in pairs:
         if name != "fwhm":
             mat, kind = _material_param(c, name)
@@ -94,8 +102,10 @@ def residual_and_jacobian(res, params, exp, ic_temp):
 def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_CSV, x0=None, max_iter=20, *, xtol=1e-9,
                    ftol=1e-10, session=None, backend=None, device_id=0, rtol=1e-10, mesh=None, rebuild_mesh=None,
                    verbose=False):
-    """Levenberg-Marquardt fit of ``params`` (material names, "<material>.k_r" / "<material>.k_z" / "<material>.k" - see
-    :func:`get_param` - and / or "fwhm") to the experiment's o-side curve.
+    """Levenberg-Marquardt fit of ``params`` (material names, "<material>.k_r" / "<material>.k_z" / "<material>.k" /
+    "<material>.thickness" - see :func:`get_param` - and / or "fwhm") to the experiment's o-side curve.  With a thickness among
+    them the mesh (``mesh`` / ``mesh_folder`` / the session's) is taken as that of ``cfg``; its triangles stay and its nodes move
+    with the trial thicknesses, so the fitted run lives on a deformed mesh (``deformed_mesh`` of the result).
     ``x0`` = start values (default: the configuration's).  ``session`` / ``backend`` / ``mesh`` = (coords, tris, tags,
     tag_map) reuse what the caller has; otherwise the mesh is loaded from ``mesh_folder``, or built there (``rebuild_mesh``
     True, or None and the folder holds no mesh).  A trial step costs one primal run; only an accepted step is followed by a
@@ -113,6 +123,9 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     for p in params:
         if p != "fwhm":
             _material_param(cfg, p)      # an unknown material or suffix, before any mesh or session is made
+    thick = [(j, p.rsplit(".", 1)[0]) for j, p in enumerate(params) if p != "fwhm" and _material_param(cfg, p)[1] == "t"]
+    for j, mat in thick:
+        check_thickness_name(cfg, mat, params[j])
     exp = load_experiment(exp_csv)
     ic = float(cfg["heating"]["ic_temp"])
     stack = build_stack(cfg)
@@ -123,14 +136,53 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
                 rebuild_mesh = not all(os.path.isfile(os.path.join(mesh_folder, f)) for f in ("mesh.msh", "mesh_cfg.yaml"))
             mesh = prepare_mesh(cfg, mesh_folder, rebuild_mesh, stack)
         coords, tris, tags, tag_map = mesh
-        session = SimulationSession(coords, tris, tags, tag_map, device_id=device_id, backend=backend, rtol=rtol)
+        if not thick:
+            session = SimulationSession(coords, tris, tags, tag_map, device_id=device_id, backend=backend, rtol=rtol)
     watchers = get_watcher_points(cfg)
     runs = tangent_runs = 0
+    # thickness parameters: the triangles of the mesh of ``cfg`` stay and its nodes move,
+    # z = z0 + sum_l V_l(z0) (theta_l - theta_l0), so the objective is smooth in theta and the tangent its exact derivative; every
+    # new set of thicknesses gets a session of its own on the moved nodes (one resident at a time)
+    moved = {"key": None, "session": None}
+    if thick:
+        if own:
+            base, kw = (np.asarray(coords, dtype=np.float64), tris, tags, tag_map), dict(device_id=device_id, backend=backend, rtol=rtol)
+        else:
+            base = (session.coords, session.tris, session.tags, session.material_tags)
+            kw = dict(device_id=session.device_id, backend=session.backend, rtol=session.rtol, max_it=session.max_it,
+                      assembly_mode=session.assembly_mode, precond=session.precond)
+        vel = {j: thickness_velocity(cfg, mat, base[0][:, 0]) for j, mat in thick}
+        theta0 = {j: get_param(cfg, params[j]) for j, _ in thick}
+        # the watcher nodes: those of the mesh of ``cfg``, followed as they move.  They are the nodes nearest to the moved
+        # configuration's watcher points on the moved mesh, except that a tie (a coupler one element thick has its mid-plane
+        # half-way between two nodes) is not decided anew by the rounding of every trial
+        from .driver import _parse_watchers
+        from .solver import nearest_nodes
+
+        w_names, w_pts = _parse_watchers(watchers)
+        w_nodes = nearest_nodes(base[0], w_pts)
+
+    def session_for(theta):
+        if not thick:
+            return session
+        key = tuple(float(theta[j]) for j, _ in thick)
+        if moved["key"] != key:
+            if moved["session"] is not None:
+                moved["session"].close()
+                moved["session"] = None
+            c = np.array(base[0], dtype=np.float64)
+            for j, _ in thick:
+                c[:, 0] += vel[j] * (float(theta[j]) - theta0[j])
+            moved["session"] = SimulationSession(c, base[1], base[2], base[3], **kw)
+            moved["key"] = key
+        return moved["session"]
 
     def run(theta, tangents):
         nonlocal runs, tangent_runs
         c = set_params(cfg, params, theta)
-        res = session.run(c, build_stack(c), watchers, tangents=params if tangents else None)
+        s = session_for(theta)
+        w = {nm: tuple(s.coords[i]) for nm, i in zip(w_names, w_nodes)} if thick else watchers
+        res = s.run(c, build_stack(c), w, tangents=params if tangents else None)
         runs += 1
         tangent_runs += bool(tangents)
         return res
@@ -181,12 +233,14 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
         except np.linalg.LinAlgError:
             stderr = np.full(p, np.nan)
     finally:
-        if own:
+        if own and session is not None:
             session.close()
+        if moved["session"] is not None:
+            moved["session"].close()
     return {"params": list(params), "values": theta.tolist(), "rmse": float(np.sqrt(cost / len(r))), "converged": bool(converged),
             "iterations": it, "history": history, "stderr": stderr.tolist(), "runs": runs, "tangent_runs": tangent_runs,
             "seconds": time.time() - t0, "tangent_iters_mean": float(np.mean(res["tangent_iters"])),
-            "pcg_iters_mean": float(np.mean(res["iters"])), "scheme": scheme}
+            "pcg_iters_mean": float(np.mean(res["iters"])), "scheme": scheme, "deformed_mesh": bool(thick)}
 
 
 def main(argv=None, backend=None):
@@ -195,7 +249,7 @@ def main(argv=None, backend=None):
 
     ap = argparse.ArgumentParser(description="Fit conductivities (and fwhm) to the experimental o-side curve with tangent runs")
     ap.add_argument("--config", required=True)
-    ap.add_argument("--params", nargs="+", default=["p_sample"], help="material names, <material>.k_r, <material>.k_z, <material>.k and / or fwhm")
+    ap.add_argument("--params", nargs="+", default=["p_sample"], help="material names, <material>.k_r, <material>.k_z, <material>.k, <material>.thickness and / or fwhm")
     ap.add_argument("--exp-csv", default=DEFAULT_EXP_CSV)
     ap.add_argument("--mesh-folder", default=None,
                     help="mesh.msh + mesh_cfg.yaml to use; built there when absent (default: <output-dir>/mesh)")

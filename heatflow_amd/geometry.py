@@ -139,6 +139,51 @@ def build_stack(cfg) -> Stack:
     return stack_with_diamond(cfg) if "p_diam" in cfg["mats"] else stack_no_diamond(cfg)
 
 
+THICKNESS_MATERIALS = ("p_sample", "p_ins", "o_ins", "p_coupler", "p_diam")     # whose ``z`` the stack builders read
+
+
+def check_thickness_name(cfg, name, param=None):
+    """ValueError naming the parameter unless ``mats.<name>.z`` is a thickness the stack of ``cfg`` is built from: p_sample,
+    p_ins, o_ins, p_coupler (both couplers) and, with diamonds, p_diam (both diamonds)."""
+    param = param or f"{name}.thickness"
+    ok = name in THICKNESS_MATERIALS and name in cfg["mats"] and (name != "p_diam" or "p_diam" in cfg["mats"])
+    if not ok:
+        allowed = [m for m in THICKNESS_MATERIALS if m in cfg["mats"]]
+        raise ValueError(f"parameter {param!r}: the stack does not read the thickness of {name!r} "
+                         f"(thickness parameters: {', '.join(m + '.thickness' for m in allowed)})")
+
+
+def _break_points(cfg):
+    """Every box's zmin and zmax in the stack's list order: the same positions in the list for any thicknesses."""
+    return [b for m in build_stack(cfg).materials for b in m.boundaries[:2]]
+
+
+def thickness_velocity(cfg, name, z):
+    """The z-velocity dz / d(mats.<name>.z) of the points ``z`` when the thickness of ``name`` changes and the mesh follows the
+    stack: a function of z alone (so the gasket annulus moves with the layers beside it), piecewise linear through
+    the stack's z break points with each break point's derivative as its value, constant outside them.  The stack is affine in
+    every thickness, so the difference of the stacks at twice the thickness and at the thickness, divided by the thickness, is that
+    derivative up to rounding.  The mid-plane z = 0 stays where it is."""
+    import copy
+
+    import numpy as np
+
+    check_thickness_name(cfg, name)
+    t = _f(cfg, name, "z")
+    moved = copy.deepcopy(cfg)
+    moved["mats"][name]["z"] = 2.0 * t
+    b0, b1 = np.array(_break_points(cfg)), np.array(_break_points(moved))
+    v = (b1 - b0) / t
+    half = np.round(2.0 * v) / 2.0        # both builders add whole and half thicknesses: the derivatives are 0, +-1/2, +-1
+    v = np.where(np.abs(v - half) < 1e-9, half, v)
+    zs, first = np.unique(b0, return_index=True)
+    for q, i in enumerate(first):         # break points shared by several boxes move as one
+        same = b0 == zs[q]
+        if np.max(np.abs(v[same] - v[i])) > 1e-9:
+            raise ValueError(f"thickness_velocity: the boxes that meet at z = {zs[q]!r} move apart with mats.{name}.z")
+    return np.interp(np.asarray(z, dtype=np.float64), zs, v[first])
+
+
 def watcher_points(cfg) -> dict:
     """Mid-plane of each coupler at r = 0 (reference with_diamond.py:15-37,
     no_diamond.py, parameter_sweep.py:69-120).  Values are (z, r)."""

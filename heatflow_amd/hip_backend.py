@@ -37,7 +37,7 @@ EXPORTS = [
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
     "hf_set_source", "hf_get_source", "hf_set_source_amplitudes",
-    "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
+    "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_set_shape", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
     "hf_set_value_lists", "hf_get_value_lists", "hf_get_projection",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
@@ -144,6 +144,7 @@ def load_library():
         "hf_set_source_amplitudes": [vp, i32, pd],
         "hf_tangent_setup": [vp, i32, pi],
         "hf_tangent_setup_dir": [vp, i32, pi, pi, pi],
+        "hf_tangent_set_shape": [vp, i32, pd],
         "hf_tangent_load": [vp, i32, pd],
         "hf_run_tangent": [vp, i32, pd, pd, dbl, dbl, i32, i32, pi, pd, pi, pd, pi],
         "hf_get_tangent": [vp, i32, pd],
@@ -442,6 +443,18 @@ class HeatflowHIP:
         self.tangent_nv = 0
         self._check(self._lib.hf_tangent_setup_dir(self._ctx, int(n_par), *(None if t is None else _pi(t) for t in tabs)))
         self.tangent_nv = next(v for v in (2, 4, 8, 16) if v >= int(n_par))
+
+    def tangent_set_shape(self, j, vz):
+        """Column j of the tangent set-up in force becomes (also) a shape column: the nodes move along z with the nodal velocity
+        ``vz`` (n values, dz_i / dtheta_j), the triangles stay (hf_tangent_set_shape).  ``None`` removes the
+        column's shape part.  At most 4 columns; every tangent starts from zero again."""
+        if vz is None:
+            self._check(self._lib.hf_tangent_set_shape(self._ctx, int(j), None))
+            return
+        v = np.ascontiguousarray(vz, dtype=np.float64).reshape(-1)
+        if v.size != self.n:
+            raise ValueError(f"tangent_set_shape: {v.size} velocities for {self.n} nodes")
+        self._check(self._lib.hf_tangent_set_shape(self._ctx, int(j), _pd(v)))
 
     def tangent_load(self, j):
         """Column j of the tangent loads F = -K_j u at the current state, by the set-up in force (hf_tangent_load; tests and

@@ -11,6 +11,7 @@ GPU instead of a cached MUMPS LU; it stops at ``||D^-1 r|| <= rtol ||D^-1 b||``
 """
 from __future__ import annotations
 
+import hashlib
 import time
 
 import numpy as np
@@ -206,7 +207,7 @@ class HeatProblem:
         self.iters.extend(int(i) for i in iters)
         return times, samples, iters
 
-    def run_tangent(self, num_steps, watcher_nodes, conductivity=(), boundary=None, time_varying=None, first_step=0):
+    def run_tangent(self, num_steps, watcher_nodes, conductivity=(), boundary=None, time_varying=None, first_step=0, shape=None):
         """:meth:`run` plus the derivatives of the watcher curves with respect to parameters theta_j (hf_run_tangent,
         DESIGN.md 3.7).  Column j of ``conductivity`` = the cell tags whose conductivity theta_j is (they move together).  An
         entry may also be a pair ``(tag, "k" | "r" | "z")``: the tag's kappa (both directions of an anisotropic
@@ -217,13 +218,20 @@ class HeatProblem:
         exactly as :meth:`run` tabulates g.  The first call after a set-up starts every tangent at zero, later calls
         continue them (as the state continues).  The tangents start at zero, i.e. the initial state is taken as independent
         of the parameters: after :meth:`solve_steady` (whose answer depends on the conductivities) the backend refuses a
-        tangent run until :meth:`set_state`.  Returns (times, samples, tangent samples (n_steps, n_par, n_s), iters,
-        tangent iters (n_steps, n_par))."""
+        tangent run until :meth:`set_state`.  ``shape`` = {column: vz} makes a column (also) a shape column:
+        the nodes move along z with the nodal velocity vz = dz / dtheta_j (n values, e.g. geometry.thickness_velocity at the
+        nodes' z), the triangles stay, and the column's tangent is the derivative at the moving nodes (hf_tangent_set_shape, at
+        most 4 columns).  Without ``shape`` the backend sees the calls of before.  Returns (times, samples, tangent samples
+        (n_steps, n_par, n_s), iters, tangent iters (n_steps, n_par))."""
         conductivity = [list(c) for c in conductivity]
         boundary = {int(j): dict(m) for j, m in (boundary or {}).items()}
-        n_par = max([len(conductivity)] + [j + 1 for j in boundary])
+        shape = {int(j): np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for j, v in (shape or {}).items()}
+        for j, v in shape.items():
+            if j < 0 or v.shape != (self.n,):
+                raise ValueError(f"run_tangent: shape column {j}: {self.n} velocities expected (got {v.size})")
+        n_par = max([len(conductivity)] + [j + 1 for j in boundary] + [j + 1 for j in shape])
         if n_par == 0:
-            raise ValueError("run_tangent: no parameter (conductivity or boundary) given")
+            raise ValueError("run_tangent: no parameter (conductivity, boundary or shape) given")
         directional = any(isinstance(t, (tuple, list)) for tags in conductivity for t in tags)
         if not directional:
             tag_col = {}
@@ -247,11 +255,15 @@ class HeatProblem:
                         raise ValueError(f"run_tangent: cell tag {t} has a kappa column and a directional one")
                     cols[kind][t] = j
             spec = (n_par, "dir") + tuple(tuple(sorted(cols[q].items())) for q in ("k", "r", "z"))
+        if shape:
+            spec += ("shape",) + tuple((j, hashlib.sha1(shape[j].tobytes()).hexdigest()) for j in sorted(shape))
         if getattr(self, "_tangent_spec", None) != spec:     # a new set of parameters: the tangents start from zero
             if directional:
                 self.backend.tangent_setup_dir(n_par, cols["k"], cols["r"], cols["z"])
             else:
                 self.backend.tangent_setup(n_par, tag_col)
+            for j in sorted(shape):                          # (the set-up removed whatever velocities were there)
+                self.backend.tangent_set_shape(j, shape[j])
             self._tangent_spec = spec
         nv = self.backend.tangent_nv
         for bc in self.bcs:

@@ -29,7 +29,7 @@
  *   hf_hold_load       b_equiv = A_free . u_ss with the transient's Dirichlet rows zeroed   with_ir_steady.ipynb cell 18
  *   hf_set_time_scheme no counterpart: the reference steps with backward Euler only (run_with_diamond.py:321-337);
  *                      HF_TIME_BDF2 is the second-order alternative
- *   hf_tangent_setup / hf_tangent_setup_dir / hf_run_tangent / hf_get_tangent / hf_tangent_load   no counterpart: the reference fits by re-running the forward model
+ *   hf_tangent_setup / hf_tangent_setup_dir / hf_tangent_set_shape / hf_run_tangent / hf_get_tangent / hf_tangent_load   no counterpart: the reference fits by re-running the forward model
  *                      over a grid (sweep_test.py:47-75, parameter_sweep.py:195-235); these give the derivatives of a run
  *   hf_set_kappa_tables / hf_get_picard_change   no counterpart: the reference's conductivities are constants per material
  *                      (run_with_diamond.py:286-301); these make them functions of the temperature
@@ -414,8 +414,24 @@ int hf_set_source_amplitudes(hf_ctx* ctx, int32_t n_amp, const double* p);
  *        tangents are bit for bit those of hf_tangent_setup with the same columns.
  * hf_tangent_load  for tests and diagnostics: forms the loads F = -K_j u of every column from the current state with the set-up
  *        in force (either kind), synchronises and copies column j (0 <= j < nv; n doubles) out.  Nothing else changes.
- *        HF_ERR_STATE before a set-up or with a batch open, HF_ERR_ARG for j outside [0, nv). */
+ *        HF_ERR_STATE before a set-up or with a batch open, HF_ERR_ARG for j outside [0, nv).
+ *
+ * Shape columns.  A column may be the derivative with respect to a parameter that moves the nodes along z with a
+ * nodal velocity v_i = dz_i / dtheta_j, the triangles kept.  s_j is then the derivative at the moving nodes, and the recursion
+ * above holds with F_j = -Kdot u^{n+1} - Mdot w added to the column's load, Kdot and Mdot the derivatives of the un-eliminated
+ * matrices and w = (u^{n+1} - u^n) / dt (backward Euler) or (u^{n+1} - 4/3 u^n + 1/3 u^{n-1}) / (2/3 dt) (BDF2, u^{-1} = u^0).
+ * hf_tangent_set_shape  valid after hf_tangent_setup or hf_tangent_setup_dir (a set-up of only -1 entries in hf_tangent_setup
+ *        makes boundary-only columns): column j (0 <= j < n_par) gets the velocities vz (n doubles); NULL removes column j's
+ *        shape part (no-op if it has none).  At most 4 columns of a set-up may have one.  A column may have conductivity entries
+ *        as well: the loads add.  Every tangent is reset to zero.  Either set-up and hf_set_mesh remove all velocities; whatever
+ *        only resets the tangents (hf_set_state, hf_assemble, ...) keeps them.  HF_ERR_STATE: no set-up, or a batch open.
+ *        HF_ERR_ARG (the message names the reason): j outside [0, n_par), a non-finite velocity, a fifth shape column.
+ *        hf_run_tangent keeps every refusal it has; the primal's samples, iterations and state stay bit for bit hf_run's, and a
+ *        run without shape columns launches exactly what it launched before.  hf_tangent_load gives the complete load of a
+ *        column: after hf_run_tangent it forms the last step's load again, bit for bit, from u^n (and u^{n-1}) kept by that run;
+ *        where no step has been taken since the tangents were last reset, w = 0. */
 int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col);
+int hf_tangent_set_shape(hf_ctx* ctx, int32_t j, const double* vz);
 int hf_tangent_setup_dir(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col_k, const int32_t* tag_col_r, const int32_t* tag_col_z);
 int hf_tangent_load(hf_ctx* ctx, int32_t j, double* F);
 int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const double* h_all, double rtol, double atol, int32_t max_it,
