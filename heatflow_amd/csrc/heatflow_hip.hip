@@ -241,6 +241,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   ctx->have_mesh = true;
   ctx->pred_iters = 0;
   ctx->flux_ready = false;
+  ctx->flux_valid = ctx->flux_formed = 0;
   if (!ctx->rg_ok) HF_TRY(ensure_owner_lists(ctx));   // the scatter kernels are this mesh's only assembly path: report their limits now
   return HF_OK;
 }
@@ -472,8 +473,12 @@ int batch_levels(hf_ctx* ctx, hf_ctx::Batch& B, int nv) {
 // on the unit-coefficient mass matrix of hf_flux_setup); `uprev` keeps the z component's last projection when both are asked for
 int ensure_batch_flux(hf_ctx* ctx, int nv, int ncomp) {
   hf_ctx::Batch& F = ctx->fluxnb;
+  // on every call: hf_flux_setup may have re-allocated the matrix, hf_batch_begin the staged SpMV's tables, since the state was made
+  F.sysA = ctx->d_M1; F.sysDinv = ctx->d_dinv1;
+  F.lds = ctx->bcols.nv == nv;        // same mesh, same nv: the main batch's staged SpMV serves the projection too
   if (F.nv == nv && (ncomp < 2 || F.uprev != nullptr)) return HF_OK;
   free_batch_state(F);
+  ctx->fluxnb_comp = -1;
   const size_t vec = static_cast<size_t>(ctx->n) * nv;
   for (double** v : {&F.u, &F.b, &F.r, &F.p, &F.Ap, &F.z}) {
     HF_TRY(dev_alloc(ctx, v, vec));
@@ -496,11 +501,18 @@ int ensure_batch_flux(hf_ctx* ctx, int nv, int ncomp) {
   F.Pb = static_cast<int>(std::min<size_t>((static_cast<size_t>(ctx->n) + rpb - 1) / rpb, MAXP));
   if (F.Pb >= 64) F.Pb &= ~7;
   F.opk = 0; F.pred_iters = 0;
-  F.sysA = ctx->d_M1; F.sysDinv = ctx->d_dinv1;
-  F.lds = ctx->bcols.nv == nv;        // same mesh, same nv: the main batch's staged SpMV serves the projection too
+  F.sysA = ctx->d_M1; F.sysDinv = ctx->d_dinv1;   // (free_batch_state cleared them)
   HF_HIP(hipStreamSynchronize(ctx->stream));
   F.nv = nv;
   return HF_OK;
+}
+
+// A projection whose right-hand side is exactly zero (a state reset to uniform) is zero.  PCG's stopping rule has no |b| to
+// measure against then and falls back to the start residual: it brings the warm start - the previous simulation's gradient -
+// down by rtol and stops, which at rtol = 1e-6 leaves 1e-6 of that gradient in the result.  x: the solved state's vector,
+// bn2 from the solve's host scalars (already fetched: no synchronisation is added).
+void zero_flat_column(hf_ctx* ctx, double bn2, double* x, int nv, int j) {
+  if (bn2 == 0.0) hipLaunchKernelGGL(kb_zero_column, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->n), nv, j, x);
 }
 
 // After a batched step: per wanted component, the gradient right-hand sides of all columns (k_grad_rows on column j of the
@@ -525,6 +537,7 @@ int batch_flux_step(hf_ctx* ctx, int components, double rtol, int max_it, int nf
                          ctx->d_rg_dict, ctx->d_rowptr, B.u, comp == 0 ? F.b + j : static_cast<double*>(nullptr),
                          comp == 1 ? F.b + j : static_cast<double*>(nullptr), nv, nv, j);
     HF_HIP(hipGetLastError());
+    ctx->fluxnb_comp = comp;
     std::swap(ctx->batch, ctx->fluxnb);
     const int rc = batch_dispatch(ctx, [&](auto ops) { return decltype(ops)::pcg(ctx, false, rtol, 0.0, max_it); });
     int itmax = 0;
@@ -532,6 +545,7 @@ int batch_flux_step(hf_ctx* ctx, int components, double rtol, int max_it, int nf
     std::swap(ctx->batch, ctx->fluxnb);
     if (it_out) it_out[done] = itmax;
     if (rc != HF_OK) { if (second) std::swap(F.u, F.uprev); return rc; }
+    for (int j = 0; j < nv; ++j) zero_flat_column(ctx, F.h_scal[j].bn2, F.u, nv, j);
     double* o = out + static_cast<size_t>(done) * nv * nfs;
     const int thr = nfs * nv;
     switch (nv) {
@@ -1254,6 +1268,7 @@ int hf_flux_setup(hf_ctx* ctx) {
     HF_HIP(hipStreamSynchronize(ctx->stream));
   }
   ctx->flux_ready = true;
+  ctx->flux_formed = 0;
   ctx->pred_flux[0] = ctx->pred_flux[1] = 0;
   return HF_OK;
 }
@@ -1279,6 +1294,8 @@ int hf_flux_solve(hf_ctx* ctx, int32_t components, double rtol, int32_t max_it, 
                        ctx->d_zr, ctx->d_u, ctx->d_bz, ctx->d_br);
   }
   HF_HIP(hipGetLastError());
+  ctx->flux_formed = components;
+  ctx->flux_formed_pair = both;
   if (both) {
     // both components as the two interleaved columns of one Jacobi-PCG on M_r(1): every pass over the matrix serves
     // both (reference: one 2n x 2n vector-P1 solve, run_no_diamond.py:479-489, 544-550); warm start = last projection
@@ -1289,6 +1306,7 @@ int hf_flux_solve(hf_ctx* ctx, int32_t components, double rtol, int32_t max_it, 
     if (iters) { iters[0] = it0; iters[1] = it1; }
     ctx->flux_valid = 0;
     if (rc != HF_OK) return rc;
+    for (int j = 0; j < 2; ++j) zero_flat_column(ctx, ctx->fluxb.h_scal[j].bn2, ctx->fluxb.u, 2, j);
     hipLaunchKernelGGL(kb_get_column, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->n), 2, 0, ctx->fluxb.u, ctx->d_gz);
     hipLaunchKernelGGL(kb_get_column, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->n), 2, 1, ctx->fluxb.u, ctx->d_gr);
     HF_HIP(hipGetLastError());
@@ -1303,6 +1321,7 @@ int hf_flux_solve(hf_ctx* ctx, int32_t components, double rtol, int32_t max_it, 
     const int rc = pcg_solve(ctx, sz, false, rtol, 0.0, max_it, &ctx->pred_flux[0]);
     if (iters) iters[0] = ctx->h_scal->iters;
     if (rc != HF_OK) return rc;
+    zero_flat_column(ctx, ctx->h_scal->bn2, ctx->d_gz, 1, 0);
     ctx->flux_valid |= 1;
   }
   if (components & 2) {
@@ -1310,6 +1329,7 @@ int hf_flux_solve(hf_ctx* ctx, int32_t components, double rtol, int32_t max_it, 
     const int rc = pcg_solve(ctx, sr, false, rtol, 0.0, max_it, &ctx->pred_flux[1]);
     if (iters) iters[1] = ctx->h_scal->iters;
     if (rc != HF_OK) return rc;
+    zero_flat_column(ctx, ctx->h_scal->bn2, ctx->d_gr, 1, 0);
     ctx->flux_valid |= 2;
   }
   return HF_OK;
@@ -2372,6 +2392,45 @@ int hf_get_projection(hf_ctx* ctx, int32_t column, int32_t* mh, int32_t* mt, int
           for (size_t i = 0; i < n; ++i) out[i] = wide[i * B.nv + column];
         }
       }
+  }
+  return HF_OK;
+}
+
+// Read-only window on the read-flux projection's linear systems: host code only, no kernel is launched.
+int hf_get_flux_system(hf_ctx* ctx, int32_t column, double* M1, double* dinv1, double* bz, double* br) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->flux_ready) return fail(ctx, HF_ERR_STATE, "hf_get_flux_system before hf_flux_setup");
+  const size_t n = static_cast<size_t>(ctx->n);
+  const hf_ctx::Batch& F = ctx->fluxnb;
+  if (column < 0) {
+    if ((bz && !(ctx->flux_formed & 1)) || (br && !(ctx->flux_formed & 2)))
+      return fail(ctx, HF_ERR_STATE, "hf_get_flux_system: that component's right-hand side was not formed by the last hf_flux_solve / hf_flux_project");
+  } else if (bz || br) {
+    if (ctx->batch.nv == 0 || F.nv != ctx->batch.nv || ctx->fluxnb_comp < 0)
+      return fail(ctx, HF_ERR_STATE, "hf_get_flux_system: no open batch has projected a gradient yet");
+    if (column >= F.nv) return fail(ctx, HF_ERR_ARG, "hf_get_flux_system: column %d outside [0,%d)", column, F.nv);
+    if ((bz && br) || (bz ? 0 : 1) != ctx->fluxnb_comp)
+      return fail(ctx, HF_ERR_STATE, "hf_get_flux_system: the batch holds the right-hand sides of the %s component only", ctx->fluxnb_comp ? "r" : "z");
+  }
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  if (M1) HF_HIP(copy_sync(ctx, M1, ctx->d_M1, sizeof(double) * ctx->nnz, hipMemcpyDeviceToHost));
+  if (dinv1) HF_HIP(copy_sync(ctx, dinv1, ctx->d_dinv1, sizeof(double) * n, hipMemcpyDeviceToHost));
+  if (!bz && !br) return HF_OK;
+  if (column < 0 && !ctx->flux_formed_pair) {
+    if (bz) HF_HIP(copy_sync(ctx, bz, ctx->d_bz, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (br) HF_HIP(copy_sync(ctx, br, ctx->d_br, sizeof(double) * n, hipMemcpyDeviceToHost));
+    return HF_OK;
+  }
+  // a column is picked out of the interleaved vector here
+  const size_t nv = column < 0 ? 2 : static_cast<size_t>(F.nv);
+  std::vector<double> wide(n * nv);
+  HF_HIP(copy_sync(ctx, wide.data(), column < 0 ? ctx->fluxb.b : F.b, sizeof(double) * n * nv, hipMemcpyDeviceToHost));
+  if (column < 0) {
+    for (size_t i = 0; i < n; ++i) { if (bz) bz[i] = wide[2 * i]; if (br) br[i] = wide[2 * i + 1]; }
+  } else {
+    double* out = bz ? bz : br;
+    for (size_t i = 0; i < n; ++i) out[i] = wide[i * nv + column];
   }
   return HF_OK;
 }

@@ -787,6 +787,10 @@ __global__ void kb_get_column(size_t n, int nv, int j, const double* __restrict_
   for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * blockDim.x)
     dst[i] = src[i * nv + j];
 }
+__global__ void kb_zero_column(size_t n, int nv, int j, double* __restrict__ dst) {
+  for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * blockDim.x)
+    dst[i * nv + j] = 0.0;
+}
 
 // ------------------------------------------------------------------------------------------
 // host side

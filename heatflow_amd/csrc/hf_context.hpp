@@ -311,6 +311,9 @@ struct hf_ctx {
   // read-flux projection (hf_flux_setup): unit-rho_c r-weighted mass matrix and the projected gradient
   bool flux_ready = false;
   int flux_valid = 0;          // components (bit 0 z, bit 1 r) the last projection solved
+  int flux_formed = 0;         // components whose right-hand side the last hf_flux_solve formed (hf_get_flux_system)
+  bool flux_formed_pair = false;   // ... as the two interleaved columns of fluxb.b (else d_bz / d_br)
+  int fluxnb_comp = -1;        // component whose right-hand sides fluxnb.b holds (0 z, 1 r; -1: no batched projection yet)
   double *d_M1 = nullptr, *d_dinv1 = nullptr, *d_gz = nullptr, *d_gr = nullptr, *d_bz = nullptr, *d_br = nullptr;
   int pred_flux[2] = {0, 0};
   // batched time loop (hf_batch_*, hf_batch.hpp): NV sweep points as interleaved columns

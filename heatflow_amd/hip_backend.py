@@ -38,7 +38,7 @@ EXPORTS = [
     "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
     "hf_set_source", "hf_get_source", "hf_set_source_amplitudes",
     "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_set_shape", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
-    "hf_set_value_lists", "hf_get_value_lists", "hf_get_projection",
+    "hf_set_value_lists", "hf_get_value_lists", "hf_get_projection", "hf_get_flux_system",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
 
@@ -159,6 +159,7 @@ def load_library():
         "hf_set_value_lists": [vp, i32],
         "hf_get_value_lists": [vp, i32, pi, C.POINTER(i64), pi, pi, pi, pd, C.POINTER(C.c_uint32)],
         "hf_get_projection": [vp, i32, pi, pi, pi, pi, pi, pd, pd, pd, pd],
+        "hf_get_flux_system": [vp, i32, pd, pd, pd, pd],
         "hf_amg_apply": [vp, pd, pd, pd],
         "hf_batch_apply_precond": [vp, pd, pd, pd],
         "hf_dense_inverse": [vp, i32, pi, pi, pd, pd, pd, pd, pd],
@@ -792,6 +793,22 @@ class HeatflowHIP:
                "rank": int(alpha[mt])}                                        # (zero until the first solve: the buffer is cleared when allocated)
         if arrays:
             out.update(V=V, F=F)
+        return out
+
+    # -- read-flux test entry point (tests/test_gpu_flux.py) ---------------------------------------------
+    def flux_system(self, column=-1, matrix=False, want_z=True, want_r=True):
+        """The linear systems of the read-flux projection: dict(bz, br) - the right-hand sides the last flux_solve /
+        flux_project formed (column = -1), or column j of the open batch's projection, which holds one component at a time
+        (ask for that one alone); a component not asked for is None.  matrix=True adds M1 (nnz values on get_csr's pattern)
+        and dinv1 (n)."""
+        M1 = np.empty(self.nnz, dtype=np.float64) if matrix else None
+        dinv1 = np.empty(self.n, dtype=np.float64) if matrix else None
+        bz = np.empty(self.n, dtype=np.float64) if want_z else None
+        br = np.empty(self.n, dtype=np.float64) if want_r else None
+        self._check(self._lib.hf_get_flux_system(self._ctx, int(column), _pd(M1), _pd(dinv1), _pd(bz), _pd(br)))
+        out = {"bz": bz, "br": br}
+        if matrix:
+            out.update(M1=M1, dinv1=dinv1)
         return out
 
     # -- preconditioner test entry points (tests/test_gpu_vcycle.py) ------------------------------------

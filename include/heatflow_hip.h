@@ -21,6 +21,7 @@
  *   hf_get_state       u_n.x.array (what xdmf.write_function would write)   :483-484
  *   hf_flux_setup      assemble_matrix(a_proj) + KSP/LU set-up       run_no_diamond.py:471-491
  *   hf_flux_project    assemble_vector(rhs_proj) + solver_proj.solve run_no_diamond.py:543-550
+ *   hf_get_flux_system no counterpart: a test window on the projection's matrix and right-hand sides (see below)
  *   hf_steady_setup    Space.build_steady_state_variational_forms + assemble_matrix(a_ss, bcs_ss) + solver set-up
  *                                                           space/space_and_forms.py:119-149, with_ir_steady.ipynb cell 17
  *   hf_steady_solve    assemble_vector(L_ss) + apply_lifting + set_bc + solve     with_ir_steady.ipynb cell 17
@@ -558,6 +559,22 @@ int hf_dense_inverse(hf_ctx* ctx, int32_t n, const int32_t* ptr, const int32_t* 
  * Any pointer may be NULL.  HF_ERR_STATE while no basis is allocated (no step with kind 3 yet) or no batch is open. */
 int hf_get_projection(hf_ctx* ctx, int32_t column, int32_t* mh, int32_t* mt, int32_t* used, int32_t* next, int32_t* pending, double* G,
                       double* alpha, double* V, double* F);
+
+/* Test and diagnosis window on the linear systems of the read-flux projection (hf_flux_setup, hf_flux_solve /
+ * hf_flux_project, the flux arguments of hf_batch_run_flux): read-only, host code, no kernel runs; the stream is
+ * synchronised first.  Any pointer may be NULL.  HF_ERR_STATE before hf_flux_setup (and again after a new hf_set_mesh).
+ *   M1[nnz]     the unit-coefficient r-weighted mass matrix on the context's CSR pattern (hf_get_csr's rowptr / colidx)
+ *   dinv1[n]    its inverse diagonal, the Jacobi preconditioner of the projection's solves
+ *   bz, br [n]  right-hand sides b_c[i] = sum over the triangles e at node i of (d_c T)_e |K| (2 r_i + r_j + r_k) / 12.
+ *     column = -1: what the last hf_flux_solve / hf_flux_project formed, wherever that call kept them (two plain arrays, or
+ *                  the two interleaved columns of its two-column solve).  Asking for a component that call was not asked
+ *                  for gives HF_ERR_STATE (the rule of hf_flux_sample, but for "formed": a solve that then failed to
+ *                  converge leaves its right-hand side readable).
+ *     column = j >= 0: column j of the open batch's projection.  That state holds ONE component at a time, the one the last
+ *                  step of hf_batch_run_flux solved last (r when flux_components has bit 1, else z): ask for that one
+ *                  alone.  Asking for both, or for the other one, gives HF_ERR_STATE, as does a call without an open
+ *                  batch or before its first projection; j >= nv gives HF_ERR_ARG. */
+int hf_get_flux_system(hf_ctx* ctx, int32_t column, double* M1, double* dinv1, double* bz, double* br);
 
 /* Average duration (ms) of `reps` back-to-back launches of one kernel on the ctx stream,
  * bracketed by HIP events on that stream. */
