@@ -44,17 +44,22 @@ def material_aniso(name, mat):
 
 PARAM_KINDS = {"k": "k", "k_r": "r", "k_z": "z"}     # suffix of a tangent / fit parameter -> column kind of run_tangent
 THICKNESS = "thickness"                              # suffix of a layer-thickness parameter -> kind "t" (a shape column)
+# suffixes of a heat-capacity parameter -> kind (a capacity column of run_tangent carries rho_c = rho * cv): the
+# tangent in cv is rho times that column, the tangent in rho is cv times it
+CAPACITY_KINDS = {"rho_c": "c", "cv": "cv", "rho": "rho"}
 
 
 def split_param(name):
     """("<material>", "k" | "r" | "z") of a parameter spelt ``<material>.k``, ``<material>.k_r`` or ``<material>.k_z``,
-    ("<material>", "t") of ``<material>.thickness``; (name, None) for a name without a dot.  ValueError naming the parameter for
-    any other suffix."""
+    ("<material>", "t") of ``<material>.thickness``, ("<material>", "c" | "cv" | "rho") of ``<material>.rho_c``, ``<material>.cv``
+    or ``<material>.rho``; (name, None) for a name without a dot.  ValueError naming the parameter for any other suffix."""
     if "." not in name:
         return name, None
     mat, suffix = name.rsplit(".", 1)
     if suffix == THICKNESS:
         return mat, "t"
+    if suffix in CAPACITY_KINDS:
+        return mat, CAPACITY_KINDS[suffix]
     if suffix not in PARAM_KINDS:
         raise ValueError(f"parameter {name!r}: unknown suffix {suffix!r} (<material>.k, <material>.k_r, <material>.k_z or "
                          f"<material>.thickness)")
@@ -93,3 +98,23 @@ def refuse_aniso(cfg, where, names=None, hint=""):
     keys = aniso_keys(cfg, names)
     if keys:
         raise ValueError(f"{where} does not support anisotropic conductivities ({', '.join(keys)}){hint}")
+
+
+def capacity_scale(mat, kind):
+    """The factor that turns the tangent in rho_c = rho * cv of the material block ``mat`` into the tangent in the parameter of
+    ``kind``: 1 for "c" (rho_c itself), rho for "cv", cv for "rho"."""
+    return 1.0 if kind == "c" else float(mat["rho"]) if kind == "cv" else float(mat["cv"])
+
+
+def check_capacity_names(names):
+    """ValueError naming both if two of ``<material>.rho_c``, ``<material>.cv`` and ``<material>.rho`` of one material are among
+    ``names``: they move the same rho * cv, so they are not independent."""
+    seen = {}
+    for name in names:
+        if "." not in name:
+            continue
+        mat, suffix = name.rsplit(".", 1)
+        if suffix in CAPACITY_KINDS:
+            if mat in seen:
+                raise ValueError(f"parameters {seen[mat]!r} and {name!r} are not independent: both move rho * cv of {mat!r}")
+            seen[mat] = name

@@ -100,7 +100,7 @@ int source_steps_ok(hf_ctx* ctx, int64_t n_steps, const char* call) {
 void tangent_free(hf_ctx* ctx) {
   free_batch_state(ctx->tanb);
   dev_free(&ctx->tan.col); dev_free(&ctx->tan.dir); dev_free(&ctx->tan.F);
-  dev_free(&ctx->tan.sh.d_v); dev_free(&ctx->tan.sh.un); dev_free(&ctx->tan.sh.um1);
+  dev_free(&ctx->tan.sh.d_v); dev_free(&ctx->tan.ccol); dev_free(&ctx->tan.un); dev_free(&ctx->tan.um1);
   ctx->tan = hf_ctx::Tangent();
 }
 
@@ -571,7 +571,7 @@ int tangent_reset(hf_ctx* ctx) {
   for (bool& u_ : T.pused) u_ = false;
   T.pnext = 0; T.ppending = -1;
   T.pred_iters = 0;
-  ctx->tan.sh.wmode = 0;   // the states kept for the shape columns' load belonged to the old trajectory; the velocities stay
+  ctx->tan.wmode = 0;   // the states kept for the shape and capacity columns' loads belonged to the old trajectory; the velocities and the capacity table stay
   return HF_OK;
 }
 
@@ -587,6 +587,20 @@ int tangent_levels(hf_ctx* ctx) {
   HF_TRY(batch_levels(ctx, T, T.nv));
   HF_HIP(hipStreamSynchronize(ctx->stream));
   ctx->tan.lev_sig = sig;
+  return HF_OK;
+}
+
+// u^n and u^{n-1} for the step rate w: held exactly while a shape column or a capacity column is set
+int tangent_rate_buffers(hf_ctx* ctx) {
+  hf_ctx::Tangent& T = ctx->tan;
+  if (T.sh.ncol == 0 && T.cmask == 0) {
+    dev_free(&T.un); dev_free(&T.um1);
+    T.wmode = 0;
+    T.hist = false;
+    return HF_OK;
+  }
+  if (!T.un) HF_TRY(dev_alloc(ctx, &T.un, static_cast<size_t>(ctx->n)));
+  if (!T.um1) HF_TRY(dev_alloc(ctx, &T.um1, static_cast<size_t>(ctx->n)));
   return HF_OK;
 }
 
@@ -611,22 +625,22 @@ int tangent_load_shape(hf_ctx* ctx, RgVariant id) {
       std::fprintf(stderr, "[tangent shape] k_tangent_load_shape<%d>: column list %d slots, %zu B dynamic LDS, %d workgroups per CU, grid %d of %d row blocks\n",
                    NS, capd, sm, per_cu, grid, ctx->nblk_a);
   }
-  const bool bdf2 = S.wmode == 2;
+  const bool bdf2 = ctx->tan.wmode == 2;
   ShapeArgs a;
   for (int s = 0; s < 4; ++s) a.dst[s] = S.col[s];
   a.nv = ctx->tan.nv;
-  a.wmode = S.wmode;
+  a.wmode = ctx->tan.wmode;
   a.dtp = ctx->dt;   // the operator's step: dt, or dt' = 2/3 dt under BDF2 (hf_assemble)
   hipLaunchKernelGGL(k_tangent_load_shape<NS>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr,
                      reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
                      ctx->d_rg_dict, ctx->d_rowptr, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->an.on ? ctx->an.d_m : nullptr, ctx->d_u,
-                     S.un, bdf2 && S.hist ? S.um1 : S.un, S.d_v, a, ctx->tan.F);
+                     ctx->tan.un, bdf2 && ctx->tan.hist ? ctx->tan.um1 : ctx->tan.un, S.d_v, a, ctx->tan.F);
   HF_HIP(hipGetLastError());
   return HF_OK;
 }
 
 // F = -K_j u for every tangent column j, from the context's current state, by the kernel of the set-up in force; the columns
-// with a shape part (hf_tangent_set_shape) then get -Kdot u - Mdot w added
+// that carry a rho_c (hf_tangent_set_capacity) then get -M^1_j w added, those with a shape part (hf_tangent_set_shape) -Kdot u - Mdot w
 int tangent_load(hf_ctx* ctx) {
   const int capd = ctx->rg_max_dict;
   const size_t sm = static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 + (RBA + 4) * 4 +
@@ -656,6 +670,22 @@ int tangent_load(hf_ctx* ctx) {
 #undef HF_TLD
 #undef HF_TL
   HF_HIP(hipGetLastError());
+  if (ctx->tan.cmask != 0) {   // capacity columns: -M^1_j w, on k_tangent_load's footprint and grid
+    const hf_ctx::Tangent& C = ctx->tan;
+    const double* um1 = C.wmode == 2 && C.hist ? C.um1 : C.un;
+#define HF_TLC(NV) hipLaunchKernelGGL(k_tangent_load_cap<NV>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr, \
+                                      reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), \
+                                      ctx->d_rg_zrb, ctx->d_rg_dict, ctx->d_rowptr, C.ccol, ctx->d_u, C.un, um1, C.wmode, \
+                                      ctx->dt /* dt, or dt' = 2/3 dt under BDF2 (hf_assemble) */, C.cmask, C.F)
+    switch (C.nv) {
+      case 2: HF_TLC(2); break;
+      case 4: HF_TLC(4); break;
+      case 8: HF_TLC(8); break;
+      default: HF_TLC(16); break;
+    }
+#undef HF_TLC
+    HF_HIP(hipGetLastError());
+  }
   if (ctx->tan.sh.ncol > 0) {
     switch (ctx->tan.sh.ns) {
       case 1: return tangent_load_shape<1>(ctx, RG_SHAPE1);
@@ -1592,8 +1622,8 @@ int hf_tangent_set_shape(hf_ctx* ctx, int32_t j, const double* vz) {
   }
   dev_free(&S.d_v);
   if (S.ncol == 0) {
-    dev_free(&S.un); dev_free(&S.um1);
     S = hf_ctx::Tangent::Shape();
+    HF_TRY(tangent_rate_buffers(ctx));
     return tangent_reset(ctx);
   }
   S.ns = S.ncol <= 1 ? 1 : S.ncol <= 2 ? 2 : 4;
@@ -1602,10 +1632,44 @@ int hf_tangent_set_shape(hf_ctx* ctx, int32_t j, const double* vz) {
   for (int s = 0; s < S.ncol; ++s)
     for (size_t i = 0; i < n; ++i) v[i * S.ns + s] = S.h_v[s][i];
   HF_TRY(dev_alloc(ctx, &S.d_v, n * S.ns));
-  if (!S.un) HF_TRY(dev_alloc(ctx, &S.un, n));
-  if (!S.um1) HF_TRY(dev_alloc(ctx, &S.um1, n));
+  HF_TRY(tangent_rate_buffers(ctx));
   HF_HIP(copy_sync(ctx, S.d_v, v.data(), sizeof(double) * n * S.ns, hipMemcpyHostToDevice));
   return tangent_reset(ctx);   // the tangents belonged to the old parameter
+}
+
+int hf_tangent_set_capacity(hf_ctx* ctx, int32_t tab_len, const int32_t* tag_col_c) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_capacity before hf_tangent_setup / hf_tangent_setup_dir");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_capacity: a batch is open");
+  if (tab_len < 0) return fail(ctx, HF_ERR_ARG, "hf_tangent_set_capacity: a table of %d entries", tab_len);
+  hf_ctx::Tangent& T = ctx->tan;
+  unsigned mask = 0;
+  if (tag_col_c)
+    for (int t = 0; t < tab_len; ++t) {
+      const int32_t c = tag_col_c[t];
+      if (c < -1 || c >= T.npar)
+        return fail(ctx, HF_ERR_ARG, "hf_tangent_set_capacity: tag %d maps its rho_c to column %d outside [-1,%d)", t, c, T.npar);
+      if (c >= 0 && (t >= ctx->tab_len || !ctx->h_tag_used[t]))
+        return fail(ctx, HF_ERR_ARG, "hf_tangent_set_capacity: tag %d is not a cell tag of the mesh", t);
+      if (c >= 0) mask |= 1u << c;
+    }
+  HF_HIP(hipSetDevice(ctx->dev));
+  if (mask == 0) {
+    dev_free(&T.ccol);
+    T.cmask = 0;
+    HF_TRY(tangent_rate_buffers(ctx));
+    return tangent_reset(ctx);
+  }
+  std::vector<int32_t> col(64, -1);    // by row-gather tag-dictionary index, as hf_tangent_setup's table
+  for (size_t q = 0; q < ctx->h_rg_tags.size() && q < 64; ++q) {
+    const int32_t t = ctx->h_rg_tags[q];
+    col[q] = t < tab_len ? tag_col_c[t] : -1;
+  }
+  if (!T.ccol) HF_TRY(dev_alloc(ctx, &T.ccol, 64));
+  HF_HIP(copy_sync(ctx, T.ccol, col.data(), sizeof(int32_t) * 64, hipMemcpyHostToDevice));
+  T.cmask = mask;
+  HF_TRY(tangent_rate_buffers(ctx));
+  return tangent_reset(ctx);   // the tangents belonged to the old parameters
 }
 
 int hf_tangent_load(hf_ctx* ctx, int32_t j, double* F) {
@@ -1661,8 +1725,8 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
   int rc = HF_OK;
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   for (int32_t s = 0; s < n_steps && rc == HF_OK; ++s) {
-    if (ctx->tan.sh.ncol > 0) {   // shape columns: their load needs u^n and (BDF2) u^{n-1} after the step has moved the buffers
-      hf_ctx::Tangent::Shape& S = ctx->tan.sh;
+    if (ctx->tan.sh.ncol > 0 || ctx->tan.cmask != 0) {   // shape and capacity columns: their load needs u^n and (BDF2) u^{n-1} after the step has moved the buffers
+      hf_ctx::Tangent& S = ctx->tan;
       const bool bdf2 = ctx->scheme == HF_TIME_BDF2;
       S.hist = bdf2 && ctx->bdf_hist;
       if (S.hist) HF_HIP(hipMemcpyAsync(S.um1, ctx->d_uprev, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));

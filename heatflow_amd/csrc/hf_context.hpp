@@ -374,10 +374,16 @@ struct hf_ctx {
       int32_t col[4] = {0, 0, 0, 0};   // F column of each slot (a slot past ncol repeats slot 0's with zero velocities)
       std::vector<double> h_v[4];      // the velocities of slot s, as given
       double* d_v = nullptr;           // n x ns, interleaved by node
-      double *un = nullptr, *um1 = nullptr;   // u^n and u^{n-1} of the last step of hf_run_tangent (copies, kept for the load)
-      int wmode = 0;                   // of that step: 0 = none taken since the last reset, 1 = backward Euler, 2 = BDF2
-      bool hist = false;               // um1 holds u^{n-1} (false: a rest start, u^{n-1} = u^n)
     } sh;
+    // capacity columns (hf_tangent_set_capacity): a column carries the rho_c of a set of cell tags;
+    // k_tangent_load_cap<nv> subtracts M^1_j w from the columns of `cmask`.  Nothing is allocated or launched while cmask == 0.
+    int32_t* ccol = nullptr;         // capacity column of each row-gather tag-dictionary entry (64), -1 = none
+    unsigned cmask = 0;              // bit j: some tag gives its rho_c to column j
+    // the step rate w = (u^{n+1} - u^n) / dt (BDF2: its three-level form) of the shape and the capacity columns' loads: allocated,
+    // and copied by every step of hf_run_tangent, exactly while a column of either kind is set (tangent_rate_buffers)
+    double *un = nullptr, *um1 = nullptr;   // u^n and u^{n-1} of the last step of hf_run_tangent (copies, kept for the load)
+    int wmode = 0;                   // of that step: 0 = none taken since the last reset, 1 = backward Euler, 2 = BDF2
+    bool hist = false;               // um1 holds u^{n-1} (false: a rest start, u^{n-1} = u^n)
   } tan;
   int fsamp_cap = 0;
   // temperature-dependent conductivities (hf_set_kappa_tables): per row-gather tag-dictionary entry a table header (KTab,

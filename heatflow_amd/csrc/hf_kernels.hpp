@@ -841,6 +841,80 @@ __global__ __launch_bounds__(RBA) void k_tangent_load_shape(int nblk, int capd, 
   }
 }
 
+// k_tangent_load's sibling for capacity columns (hf_tangent_set_capacity; same lists, LDS carve-up and launch
+// geometry): F[i * NV + j] -= sum over the triangles e at node i whose tag gives its rho_c to column j (ccol[tag-dictionary
+// index] = j) of (M^1_e w)_i, M^1_e the r-weighted element mass at rho_c = 1 (element_row, as k_source_load forms it).  No state is
+// staged: where k_tangent_load stages u the block's column nodes get the step rate w, formed from u = u^{n+1}, un = u^n and
+// um1 = u^{n-1} statement for statement as k_tangent_load_shape forms it, so a node's w has that kernel's bits.  It runs after the
+// load kernel of the set-up and touches only the columns of `cmask` (bit j: some tag maps to column j).  Each column's sum runs in
+// list order in a register of the row's lane - no atomics, bitwise reproducible.
+template <int NV>
+__global__ __launch_bounds__(RBA) void k_tangent_load_cap(int nblk, int capd, const int4* __restrict__ hdr, const uint4* __restrict__ ell,
+                                                          const uint4* __restrict__ cid16, const double2* __restrict__ zrb,
+                                                          const int32_t* __restrict__ dict, const int32_t* __restrict__ rowptr,
+                                                          const int32_t* __restrict__ ccol, const double* __restrict__ u,
+                                                          const double* __restrict__ un, const double* __restrict__ um1, int wmode,
+                                                          double dtp, unsigned cmask, double* __restrict__ F) {
+  extern __shared__ double smem[];
+  __shared__ int scc[64];
+  double2* sXd = reinterpret_cast<double2*>(smem);
+  double* sW = smem + 2 * capd;
+  int* sR = reinterpret_cast<int*>(sW + capd + (capd & 1));
+  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);
+  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
+  const int t = threadIdx.x;
+  if (t < 64) scc[t] = ccol[t];
+  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const int4 cA = hdr[2 * blk], cB = hdr[2 * blk + 1];
+    const int c0 = cA.x >> 3, nc = ((cA.x + cA.y + 7) >> 3) - c0;
+    for (int i = t; i < nc; i += RBA) sC4[i] = cid16[c0 + i];
+    for (int i = t; i < cA.w; i += RBA) {
+#pragma clang fp contract(off)
+      const int node = dict[cA.z + i];
+      const double u1 = u[node];
+      sXd[i] = zrb[cA.z + i];
+      double w = 0.0;
+      if (wmode == 1) w = (u1 - un[node]) / dtp;
+      else if (wmode == 2) w = ((u1 - (4.0 / 3.0) * un[node]) + (1.0 / 3.0) * um1[node]) / dtp;
+      sW[i] = w;
+    }
+    if (t < cB.w) sR[t] = rowptr[blk * RBA + t] - cA.x;
+    __syncthreads();
+    if (t < cB.w) {
+#pragma clang fp contract(off)
+      const int sbase = sR[t] + (cA.x & 7);
+      const int ci = cB.z + t;
+      const double2 Pi = sXd[ci];
+      const double wi = sW[ci];
+      double acc[NV];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+      for (int g = 0; g < cB.y; ++g) {
+        const uint4 ev = ell[cB.x + g * RBA + t];
+        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
+          if (e == 0xFFFFu) continue;
+          const int cj = scc[e >> 10];
+          if (cj < 0) continue;
+          const int pj = sC[sbase + (e & 31u)], pk = sC[sbase + ((e >> 5) & 31u)];
+          const ElemRow r = element_row(Pi, sXd[pj], sXd[pk], 1.0, 0.0);
+          const double mw = (r.m0 * wi + r.m1 * sW[pj]) + r.m2 * sW[pk];
+#pragma unroll
+          for (int j = 0; j < NV; ++j)
+            if (j == cj) acc[j] += mw;
+        }
+      }
+      double* out = F + static_cast<size_t>(blk * RBA + t) * NV;
+#pragma unroll
+      for (int j = 0; j < NV; ++j)
+        if ((cmask >> j) & 1u) out[j] -= acc[j];
+    }
+    __syncthreads();
+  }
+}
+
 // Shape of the volumetric source (hf_set_source) at a node P = (z, r): s = exp(-(c_r r^2 + |z - z0| inv_depth)),
 // c_r = 4 ln2 / fwhm^2 and inv_depth = 1 / depth, both formed on the host (inv_depth = 0: uniform through the layer).
 // One double-precision exp per node; the argument is formed without contraction, so it has the bits of its restatement.

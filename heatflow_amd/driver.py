@@ -42,7 +42,7 @@ def _dump_yaml(obj, f):
 from .bc import P1Space, RowDirichletBC
 from .geometry import check_thickness_name, stack_no_diamond, stack_with_diamond, thickness_velocity
 from .heating import HeatingCurve
-from .aniso import DIRECTIONAL_HINT, check_config, refuse_aniso, split_param
+from .aniso import CAPACITY_KINDS, DIRECTIONAL_HINT, capacity_scale, check_capacity_names, check_config, refuse_aniso, split_param
 from .kappa_t import material_cv_table, material_table, picard_sweeps, refuse_tables
 from .mesh import Mesh, load_mesh_arrays
 from .source import amplitudes as source_amplitudes, parse_source, refuse_source
@@ -498,8 +498,9 @@ class SimulationSession:
         k -, "<material>.k_r" / "<material>.k_z" / "<material>.k" - its radial, its axial conductivity in W/m/K, or the
         scalar k of both with the ratio of ``k_aniso`` kept; on isotropic materials the derivatives at m = (1, 1) -,
         "<material>.thickness" - the layer thickness ``mats.<material>.z`` in metres, the nodes of this session's mesh moving
-        with the stack (geometry.thickness_velocity) -, and / or "fwhm" of the heating profile) adds ``tangents`` {param: {watcher: d watcher / d param}} and
-        ``tangent_iters`` (HeatProblem.run_tangent; not with a field sink or the flux projection).
+        with the stack (geometry.thickness_velocity) -, "<material>.rho_c" / "<material>.cv" / "<material>.rho" -
+        the material's rho * cv in J/m^3/K, its cv or its rho (one of the three per material) -, and / or "fwhm"
+        of the heating profile) adds ``tangents`` {param: {watcher: d watcher / d param}} and ``tangent_iters`` (HeatProblem.run_tangent; not with a field sink or the flux projection).
         A ``heating.source`` block (heatflow_amd.source) drives the run by absorbed laser power, the field sink and the flux
         projection included; not with ``tangents`` or ``two_sided``."""
         t_start = time.time()
@@ -548,7 +549,11 @@ class SimulationSession:
             if field_sink is not None or flux is not None:
                 raise ValueError("tangents: not combined with a field sink or the read-flux projection")
             params = list(tangents)
-            cond, bnd, shp = [], {}, {}
+            try:
+                check_capacity_names(params)
+            except ValueError as e:
+                raise ValueError(f"tangents: {e}") from None
+            cond, bnd, shp, cap, cscale = [], {}, {}, {}, {}
             for j, p in enumerate(params):
                 if p == "fwhm":
                     cond.append([])
@@ -570,10 +575,21 @@ class SimulationSession:
                             raise ValueError(f"tangents: {e}") from None
                         cond.append([])
                         shp[j] = thickness_velocity(cfg, mat, self.coords[:, 0])
+                    elif kind in CAPACITY_KINDS.values():      # a column in rho_c = rho cv of the material; cv and rho by the chain rule
+                        if mat not in (cfg.get("mats") or {}):
+                            raise ValueError(f"tangents: parameter {p!r}: no material {mat!r} in the configuration")
+                        cond.append([])
+                        cap[j] = [self.material_tags[mat]]
+                        cscale[j] = capacity_scale(cfg["mats"][mat], kind)
                     else:
                         cond.append([(self.material_tags[mat], kind)])
             times, samples, tsamp, iters, titers = prob.run_tangent(num_steps, nodes, conductivity=cond, boundary=bnd,
-                                                                    time_varying=varying, **({"shape": shp} if shp else {}))
+                                                                    time_varying=varying, **({"shape": shp} if shp else {}),
+                                                                    **({"capacity": [cap.get(j, []) for j in range(len(params))]}
+                                                                       if cap else {}))
+            for j, f in cscale.items():
+                if f != 1.0:
+                    tsamp[:, j] *= f
             tangent_out = {p: {nm: tsamp[:, j, k] for k, nm in enumerate(names)} for j, p in enumerate(params)}
         elif field_sink is None and flux is None:
             times, samples, iters = prob.run(num_steps, watcher_nodes=nodes, time_varying=varying,

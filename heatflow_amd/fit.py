@@ -21,7 +21,8 @@ import numpy as np
 
 from .geometry import check_thickness_name, thickness_velocity
 from .parameter_sweep import build_stack, get_watcher_points, oside_curves
-from .aniso import DIRECTIONAL_HINT, KEY, material_aniso, refuse_aniso, split_param
+from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, KEY, capacity_scale, check_capacity_names, material_aniso, refuse_aniso,
+                    split_param)
 from .kappa_t import refuse_tables
 from .source import refuse_source
 
@@ -30,7 +31,7 @@ DEFAULT_EXP_CSV = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(_
 
 
 def _material_param(cfg, name):
-    """(material block, None | "k" | "r" | "z") of a parameter name; ValueError naming it for an unknown material or suffix."""
+    """(material block, None | "k" | "r" | "z" | "t" | "c" | "cv" | "rho") of a parameter name; ValueError naming it for an unknown material or suffix."""
     mat, kind = split_param(name)
     if mat not in cfg["mats"]:
         raise ValueError(f"parameter {name!r}: no material {mat!r} in the configuration")
@@ -40,7 +41,8 @@ def _material_param(cfg, name):
 def get_param(cfg, name):
     """The value of a parameter: "fwhm", a material's k ("<m>" or "<m>.k"), its directional conductivity "<m>.k_r" =
     k * k_aniso.r / "<m>.k_z" = k * k_aniso.z in W/m/K (multiplier 1 where the block or the key is absent), or its layer
-    thickness "<m>.thickness" = mats.<m>.z in metres (the materials whose z the stack reads)."""
+    thickness "<m>.thickness" = mats.<m>.z in metres (the materials whose z the stack reads), or its heat capacity: "<m>.rho_c" =
+    rho * cv in J/m^3/K, "<m>.cv", "<m>.rho"."""
     if name == "fwhm":
         return float(cfg["heating"]["fwhm"])
     mat, kind = _material_param(cfg, name)
@@ -49,6 +51,8 @@ def get_param(cfg, name):
     if kind == "t":
         check_thickness_name(cfg, name.rsplit(".", 1)[0], name)
         return float(mat["z"])
+    if kind in CAPACITY_KINDS.values():
+        return float(mat["rho"]) * float(mat["cv"]) if kind == "c" else float(mat[kind])
     m = material_aniso(name.rsplit(".", 1)[0], mat) or (1.0, 1.0)
     return float(mat["k"]) * m[0 if kind == "r" else 1]
 
@@ -56,10 +60,12 @@ def get_param(cfg, name):
 def set_params(cfg, params, values):
     """A copy of ``cfg`` with the parameters set: "fwhm" of the heating profile, the conductivity k of a material ("<m>" or
     "<m>.k"; the multipliers of a ``k_aniso`` block stay), or a directional conductivity: "<m>.k_r" writes k_aniso.r = value / k,
-    "<m>.k_z" k_aniso.z, creating the block where absent; "<m>.thickness" writes mats.<m>.z in metres.  The k parameters are applied first, so a directional value holds
+    "<m>.k_z" k_aniso.z, creating the block where absent; "<m>.thickness" writes mats.<m>.z in metres; "<m>.rho_c"
+    writes cv = value / rho and keeps rho, "<m>.cv" and "<m>.rho" write their key (two of the three on one material: ValueError).  The k parameters are applied first, so a directional value holds
     whatever the order of the names."""
     c = copy.deepcopy(cfg)
     pairs = list(zip(params, values))
+    check_capacity_names(params)
     for name, v in pairs:
         if name == "fwhm":
             c["heating"]["fwhm"] = float(v)
@@ -68,6 +74,12 @@ def set_params(cfg, params, values):
         elif _material_param(c, name)[1] == "t":
             check_thickness_name(c, name.rsplit(".", 1)[0], name)
             _material_param(c, name)[0]["z"] = float(v)
+        elif _material_param(c, name)[1] in CAPACITY_KINDS.values():
+            mat, kind = _material_param(c, name)
+            if kind == "c":
+                mat["cv"] = float(v) / float(mat["rho"])
+            else:
+                mat[kind] = float(v)
     for name, v in pairs:
         if name != "fwhm":
             mat, kind = _material_param(c, name)
@@ -101,9 +113,9 @@ def residual_and_jacobian(res, params, exp, ic_temp):
 
 def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_CSV, x0=None, max_iter=20, *, xtol=1e-9,
                    ftol=1e-10, session=None, backend=None, device_id=0, rtol=1e-10, mesh=None, rebuild_mesh=None,
-                   verbose=False):
+                   verbose=False, nuisance=None):
     """Levenberg-Marquardt fit of ``params`` (material names, "<material>.k_r" / "<material>.k_z" / "<material>.k" /
-    "<material>.thickness" - see :func:`get_param` - and / or "fwhm") to the experiment's o-side curve.  With a thickness among
+    "<material>.thickness" / "<material>.rho_c" / "<material>.cv" / "<material>.rho" - see :func:`get_param` - and / or "fwhm") to the experiment's o-side curve.  With a thickness among
     them the mesh (``mesh`` / ``mesh_folder`` / the session's) is taken as that of ``cfg``; its triangles stay and its nodes move
     with the trial thicknesses, so the fitted run lives on a deformed mesh (``deformed_mesh`` of the result).
     ``x0`` = start values (default: the configuration's).  ``session`` / ``backend`` / ``mesh`` = (coords, tris, tags,
@@ -111,7 +123,13 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     True, or None and the folder holds no mesh).  A trial step costs one primal run; only an accepted step is followed by a
     tangent run for the next Jacobian.  Returns {params, values, rmse, converged, iterations, history, stderr, runs,
     tangent_runs, seconds, scheme}.  The time scheme is the configuration's (``timing.scheme``, default backward Euler);
-    the tangents are those of the discrete loop of that scheme."""
+    the tangents are those of the discrete loop of that scheme.
+    ``nuisance`` = {name: relative sigma} adds a systematic-error budget: the names are parameters the fit accepts
+    that are not among ``params`` (assumed capacities, thicknesses, the beam width, other conductivities), sigma their relative
+    one-sigma uncertainty.  After convergence one more tangent run at the fitted values carries the columns params + nuisance; with
+    J the Jacobian of the fitted parameters and J_q the column of nuisance q, a nuisance that is off by sigma_q moves the fit by
+    d theta_q = -(J^T J)^-1 J^T J_q (sigma_q value_q).  The result gains ``systematic`` {nuisance: {param: shift}} and
+    ``systematic_total`` {param: root sum of squares over the nuisances}, next to ``stderr``."""
     from .driver import SimulationSession, prepare_mesh, time_scheme
 
     t0 = time.time()
@@ -123,6 +141,26 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     for p in params:
         if p != "fwhm":
             _material_param(cfg, p)      # an unknown material or suffix, before any mesh or session is made
+    nuisance = {str(q): v for q, v in dict(nuisance or {}).items()}
+    for q, sig in nuisance.items():
+        if q in params:
+            raise ValueError(f"nuisance {q!r} is a fitted parameter (a parameter is fitted or budgeted, not both)")
+        if q != "fwhm":
+            try:
+                mat_q, kind_q = _material_param(cfg, q)
+            except ValueError as e:
+                raise ValueError(f"nuisance {q!r}: {e}") from None
+            if kind_q == "t":
+                check_thickness_name(cfg, q.rsplit(".", 1)[0], q)
+        try:
+            ok = np.isfinite(float(sig)) and float(sig) > 0.0
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"nuisance {q!r}: the relative sigma must be positive and finite (got {sig!r})")
+    check_capacity_names(params + tuple(nuisance))
+    if nuisance:
+        refuse_aniso(cfg, "heatflow_amd.fit with the conductivity of an anisotropic material as a nuisance", set(nuisance), DIRECTIONAL_HINT)
     thick = [(j, p.rsplit(".", 1)[0]) for j, p in enumerate(params) if p != "fwhm" and _material_param(cfg, p)[1] == "t"]
     for j, mat in thick:
         check_thickness_name(cfg, mat, params[j])
@@ -182,7 +220,7 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
         c = set_params(cfg, params, theta)
         s = session_for(theta)
         w = {nm: tuple(s.coords[i]) for nm, i in zip(w_names, w_nodes)} if thick else watchers
-        res = s.run(c, build_stack(c), w, tangents=params if tangents else None)
+        res = s.run(c, build_stack(c), w, tangents=(params if tangents is True else tuple(tangents)) if tangents else None)
         runs += 1
         tangent_runs += bool(tangents)
         return res
@@ -232,6 +270,19 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
             stderr = np.sqrt(np.diag(s2 * np.linalg.inv(J.T @ J)))
         except np.linalg.LinAlgError:
             stderr = np.full(p, np.nan)
+        budget = {}
+        if nuisance:      # one tangent run at the fitted values with the columns params + nuisance
+            names = params + tuple(nuisance)
+            _, Jall = residual_and_jacobian(run(theta, names), names, exp, ic)
+            Jp = Jall[:, :p]
+            c_fit = set_params(cfg, params, theta)
+            pinv = np.linalg.solve(Jp.T @ Jp, Jp.T)
+            systematic = {}
+            for k, (q, sig) in enumerate(nuisance.items()):
+                shift = -(pinv @ Jall[:, p + k]) * (float(sig) * get_param(c_fit, q))
+                systematic[q] = {nm: float(v) for nm, v in zip(params, shift)}
+            budget = {"systematic": systematic,
+                      "systematic_total": {nm: float(np.sqrt(sum(systematic[q][nm] ** 2 for q in systematic))) for nm in params}}
     finally:
         if own and session is not None:
             session.close()
@@ -240,7 +291,7 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     return {"params": list(params), "values": theta.tolist(), "rmse": float(np.sqrt(cost / len(r))), "converged": bool(converged),
             "iterations": it, "history": history, "stderr": stderr.tolist(), "runs": runs, "tangent_runs": tangent_runs,
             "seconds": time.time() - t0, "tangent_iters_mean": float(np.mean(res["tangent_iters"])),
-            "pcg_iters_mean": float(np.mean(res["iters"])), "scheme": scheme, "deformed_mesh": bool(thick)}
+            "pcg_iters_mean": float(np.mean(res["iters"])), "scheme": scheme, "deformed_mesh": bool(thick), **budget}
 
 
 def main(argv=None, backend=None):
@@ -249,7 +300,7 @@ def main(argv=None, backend=None):
 
     ap = argparse.ArgumentParser(description="Fit conductivities (and fwhm) to the experimental o-side curve with tangent runs")
     ap.add_argument("--config", required=True)
-    ap.add_argument("--params", nargs="+", default=["p_sample"], help="material names, <material>.k_r, <material>.k_z, <material>.k, <material>.thickness and / or fwhm")
+    ap.add_argument("--params", nargs="+", default=["p_sample"], help="material names, <material>.k_r, <material>.k_z, <material>.k, <material>.thickness, <material>.rho_c, <material>.cv, <material>.rho and / or fwhm")
     ap.add_argument("--exp-csv", default=DEFAULT_EXP_CSV)
     ap.add_argument("--mesh-folder", default=None,
                     help="mesh.msh + mesh_cfg.yaml to use; built there when absent (default: <output-dir>/mesh)")
@@ -260,7 +311,19 @@ def main(argv=None, backend=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--scheme", choices=("backward_euler", "bdf2"), default=None,
                     help="time scheme (default: the configuration's timing.scheme, else backward_euler)")
+    ap.add_argument("--nuisance", nargs="+", default=None, metavar="NAME=REL",
+                    help="systematic-error budget: parameters that are assumed, not fitted, with their relative one-sigma "
+                         "uncertainty, e.g. p_ins.rho_c=0.15 p_sample.thickness=0.05 fwhm=0.1")
     a = ap.parse_args(argv)
+    nuisance = {}
+    for item in a.nuisance or ():
+        name, sep, rel = item.partition("=")
+        try:
+            nuisance[name] = float(rel)
+        except ValueError:
+            sep = ""
+        if not sep or not name:
+            ap.error(f"--nuisance {item!r}: NAME=REL expected")
     with open(a.config) as f:
         cfg = yaml.safe_load(f)
     if a.scheme is not None:
@@ -268,7 +331,7 @@ def main(argv=None, backend=None):
     os.makedirs(a.output_dir, exist_ok=True)
     mesh_folder = a.mesh_folder or os.path.join(a.output_dir, "mesh")
     out = fit_parameters(cfg, mesh_folder, a.params, a.exp_csv, a.x0, a.max_iter, device_id=a.device, backend=backend,
-                         rebuild_mesh=True if a.rebuild_mesh else None, verbose=True)
+                         rebuild_mesh=True if a.rebuild_mesh else None, verbose=True, **({"nuisance": nuisance} if nuisance else {}))
     out["config"] = a.config
     with open(os.path.join(a.output_dir, "fit_summary.json"), "w") as f:
         json.dump(out, f, indent=2)
@@ -276,7 +339,8 @@ def main(argv=None, backend=None):
 
     with open(os.path.join(a.output_dir, "used_config.yaml"), "w") as f:     # the configuration at the fitted values
         _dump_yaml(_with_scheme(set_params(cfg, out["params"], out["values"])), f)
-    print(json.dumps({k: out[k] for k in ("params", "values", "stderr", "rmse", "converged", "iterations", "runs", "seconds", "scheme")}))
+    print(json.dumps({k: out[k] for k in ("params", "values", "stderr", "rmse", "converged", "iterations", "runs", "seconds", "scheme",
+                                          "systematic", "systematic_total") if k in out}))
     return 0
 
 

@@ -37,7 +37,7 @@ EXPORTS = [
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
     "hf_set_source", "hf_get_source", "hf_set_source_amplitudes",
-    "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_set_shape", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
+    "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_set_shape", "hf_tangent_set_capacity", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
     "hf_set_value_lists", "hf_get_value_lists", "hf_get_projection", "hf_get_flux_system",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
@@ -145,6 +145,7 @@ def load_library():
         "hf_tangent_setup": [vp, i32, pi],
         "hf_tangent_setup_dir": [vp, i32, pi, pi, pi],
         "hf_tangent_set_shape": [vp, i32, pd],
+        "hf_tangent_set_capacity": [vp, i32, pi],
         "hf_tangent_load": [vp, i32, pd],
         "hf_run_tangent": [vp, i32, pd, pd, dbl, dbl, i32, i32, pi, pd, pi, pd, pi],
         "hf_get_tangent": [vp, i32, pd],
@@ -456,6 +457,21 @@ class HeatflowHIP:
         if v.size != self.n:
             raise ValueError(f"tangent_set_shape: {v.size} velocities for {self.n} nodes")
         self._check(self._lib.hf_tangent_set_shape(self._ctx, int(j), _pd(v)))
+
+    def tangent_set_capacity(self, tag_col):
+        """``tag_col`` = {cell tag: column}: the column carries the rho_c (J/m^3/K) of the tag (hf_tangent_set_capacity, DESIGN.md
+        3.16); several tags may share a column, and the column may have conductivity entries and a shape velocity too.  An empty
+        mapping (or None) removes the capacity columns.  Every tangent starts from zero again."""
+        tag_col = dict(tag_col or {})
+        if not tag_col:
+            self._check(self._lib.hf_tangent_set_capacity(self._ctx, 0, None))
+            return
+        tab = np.full(self.tab_len, -1, dtype=np.int32)
+        for t, j in tag_col.items():
+            if not 0 <= int(t) < self.tab_len:
+                raise ValueError(f"tangent_set_capacity: tag {t} is not a cell tag of the mesh")
+            tab[int(t)] = int(j)
+        self._check(self._lib.hf_tangent_set_capacity(self._ctx, self.tab_len, _pi(tab)))
 
     def tangent_load(self, j):
         """Column j of the tangent loads F = -K_j u at the current state, by the set-up in force (hf_tangent_load; tests and

@@ -207,7 +207,8 @@ class HeatProblem:
         self.iters.extend(int(i) for i in iters)
         return times, samples, iters
 
-    def run_tangent(self, num_steps, watcher_nodes, conductivity=(), boundary=None, time_varying=None, first_step=0, shape=None):
+    def run_tangent(self, num_steps, watcher_nodes, conductivity=(), boundary=None, time_varying=None, first_step=0, shape=None,
+                    capacity=()):
         """:meth:`run` plus the derivatives of the watcher curves with respect to parameters theta_j (hf_run_tangent,
         DESIGN.md 3.7).  Column j of ``conductivity`` = the cell tags whose conductivity theta_j is (they move together).  An
         entry may also be a pair ``(tag, "k" | "r" | "z")``: the tag's kappa (both directions of an anisotropic
@@ -221,7 +222,10 @@ class HeatProblem:
         tangent run until :meth:`set_state`.  ``shape`` = {column: vz} makes a column (also) a shape column:
         the nodes move along z with the nodal velocity vz = dz / dtheta_j (n values, e.g. geometry.thickness_velocity at the
         nodes' z), the triangles stay, and the column's tangent is the derivative at the moving nodes (hf_tangent_set_shape, at
-        most 4 columns).  Without ``shape`` the backend sees the calls of before.  Returns (times, samples, tangent samples
+        most 4 columns).  Without ``shape`` the backend sees the calls of before.  Column j of ``capacity`` (positional like
+        ``conductivity``; an empty list = none) = the cell tags whose rho_c = rho * cv in J/m^3/K theta_j is (DESIGN.md 3.16,
+        hf_tangent_set_capacity); a column may carry conductivities, a velocity and a capacity at once, a tag may be in one
+        capacity column only, and without ``capacity`` the backend sees the calls of before.  Returns (times, samples, tangent samples
         (n_steps, n_par, n_s), iters, tangent iters (n_steps, n_par))."""
         conductivity = [list(c) for c in conductivity]
         boundary = {int(j): dict(m) for j, m in (boundary or {}).items()}
@@ -229,7 +233,13 @@ class HeatProblem:
         for j, v in shape.items():
             if j < 0 or v.shape != (self.n,):
                 raise ValueError(f"run_tangent: shape column {j}: {self.n} velocities expected (got {v.size})")
-        n_par = max([len(conductivity)] + [j + 1 for j in boundary] + [j + 1 for j in shape])
+        cap_col = {}
+        for j, tags in enumerate(capacity or ()):
+            for t in tags:
+                if int(t) in cap_col:
+                    raise ValueError(f"run_tangent: cell tag {t} is listed in two capacity columns")
+                cap_col[int(t)] = j
+        n_par = max([len(conductivity), len(capacity or ())] + [j + 1 for j in boundary] + [j + 1 for j in shape])
         if n_par == 0:
             raise ValueError("run_tangent: no parameter (conductivity, boundary or shape) given")
         directional = any(isinstance(t, (tuple, list)) for tags in conductivity for t in tags)
@@ -257,11 +267,15 @@ class HeatProblem:
             spec = (n_par, "dir") + tuple(tuple(sorted(cols[q].items())) for q in ("k", "r", "z"))
         if shape:
             spec += ("shape",) + tuple((j, hashlib.sha1(shape[j].tobytes()).hexdigest()) for j in sorted(shape))
+        if cap_col:
+            spec += ("capacity",) + tuple(sorted(cap_col.items()))
         if getattr(self, "_tangent_spec", None) != spec:     # a new set of parameters: the tangents start from zero
             if directional:
                 self.backend.tangent_setup_dir(n_par, cols["k"], cols["r"], cols["z"])
             else:
                 self.backend.tangent_setup(n_par, tag_col)
+            if cap_col:                                      # (the set-up removed whatever capacity columns were there)
+                self.backend.tangent_set_capacity(cap_col)
             for j in sorted(shape):                          # (the set-up removed whatever velocities were there)
                 self.backend.tangent_set_shape(j, shape[j])
             self._tangent_spec = spec

@@ -430,9 +430,27 @@ int hf_set_source_amplitudes(hf_ctx* ctx, int32_t n_amp, const double* p);
  *        hf_run_tangent keeps every refusal it has; the primal's samples, iterations and state stay bit for bit hf_run's, and a
  *        run without shape columns launches exactly what it launched before.  hf_tangent_load gives the complete load of a
  *        column: after hf_run_tangent it forms the last step's load again, bit for bit, from u^n (and u^{n-1}) kept by that run;
- *        where no step has been taken since the tangents were last reset, w = 0. */
+ *        where no step has been taken since the tangents were last reset, w = 0.
+ *
+ * Capacity columns.  A column may carry the rho_c (J/m^3/K) of a set of cell tags.  With M^1_j the r-weighted
+ * mass matrix of the elements of those tags at rho_c = 1 (un-eliminated), the recursion above holds with F_j = -M^1_j w added to
+ * the column's load, w the step rate of the shape columns (same formulas, same order of operations).  Dirichlet rows carry h_j as
+ * before.  The mass is not directional, so anisotropic tags are allowed under either set-up.
+ * hf_tangent_set_capacity  valid after hf_tangent_setup or hf_tangent_setup_dir (a set-up of only -1 entries is allowed):
+ *        tag_col_c[t] = j (t < tab_len): column j carries the rho_c of cell tag t, -1 = none.  Several tags may feed one column.
+ *        NULL, or a table of only -1, removes the capacity columns.  A column may have conductivity entries and a shape velocity
+ *        as well: the loads add.  There is no limit on the number of capacity columns other than n_par <= 16.  Every tangent is
+ *        reset to zero.  Either set-up and hf_set_mesh remove the table; whatever only resets the tangents (hf_set_state,
+ *        hf_assemble, ...) keeps it.  HF_ERR_STATE: no set-up, or a batch open.  HF_ERR_ARG (the message names the tag): an
+ *        entry outside [-1, n_par), a non-negative entry on a tag that is not a cell tag of the mesh.
+ *        hf_run_tangent keeps every refusal it has (tables, a load, a source, the steady state); the primal's samples,
+ *        iterations and state stay bit for bit hf_run's, and a run without capacity columns launches exactly what it launched
+ *        before.  hf_tangent_load gives the complete load of a column, capacity part included, from u^n (and u^{n-1}) kept by
+ *        the last hf_run_tangent; where no step has been taken since the tangents were last reset, w = 0 and the capacity part
+ *        vanishes. */
 int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col);
 int hf_tangent_set_shape(hf_ctx* ctx, int32_t j, const double* vz);
+int hf_tangent_set_capacity(hf_ctx* ctx, int32_t tab_len, const int32_t* tag_col_c);
 int hf_tangent_setup_dir(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col_k, const int32_t* tag_col_r, const int32_t* tag_col_z);
 int hf_tangent_load(hf_ctx* ctx, int32_t j, double* F);
 int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const double* h_all, double rtol, double atol, int32_t max_it,
