@@ -11,6 +11,7 @@
 // once, symmetric Dirichlet elimination, solve), :469-481 (loop body).
 
 #include "hf_amg_io.hpp"
+#include "hf_monitor.hpp"
 
 // ==========================================================================================
 // C ABI
@@ -129,6 +130,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   steady_free(ctx);
   load_free(ctx);
   source_free(ctx);
+  monitor_free(ctx);
   tangent_free(ctx);
   kt_free(ctx);
   an_free(ctx);
@@ -752,7 +754,7 @@ int hf_destroy(hf_ctx* ctx) {
   dev_free(&ctx->d_uprev); dev_free(&ctx->d_ustart);
   dev_free(&ctx->d_u); dev_free(&ctx->d_b); dev_free(&ctx->d_r); dev_free(&ctx->d_p); dev_free(&ctx->d_Ap);
   free_batch(ctx); free_batch_state(ctx->fluxb); free_batch_cols(ctx); free_amg(ctx); free_responses(ctx); proj_free(ctx); dev_free(&ctx->d_z); dev_free(&ctx->d_z2);
-  steady_free(ctx); load_free(ctx); source_free(ctx); tangent_free(ctx); kt_free(ctx); an_free(ctx); value_lists_free(ctx);
+  steady_free(ctx); load_free(ctx); source_free(ctx); monitor_free(ctx); tangent_free(ctx); kt_free(ctx); an_free(ctx); value_lists_free(ctx);
   dev_free(&ctx->d_M1); dev_free(&ctx->d_dinv1); dev_free(&ctx->d_gz); dev_free(&ctx->d_gr); dev_free(&ctx->d_bz); dev_free(&ctx->d_br);
   dev_free(&ctx->d_tmp); dev_free(&ctx->d_part_pAp); dev_free(&ctx->d_part_rz); dev_free(&ctx->d_part_zz);
   dev_free(&ctx->d_part_bn); dev_free(&ctx->d_scal); dev_free(&ctx->d_samp_idx); dev_free(&ctx->d_samp); dev_free(&ctx->d_fsamp_idx);
@@ -1443,9 +1445,11 @@ int hf_step(hf_ctx* ctx, const double* g_bc, double rtol, double atol, int32_t m
   if (max_it <= 0 || rtol < 0 || atol < 0) return fail(ctx, HF_ERR_ARG, "hf_step: bad tolerances");
   HF_HIP(hipSetDevice(ctx->dev));
   HF_TRY(source_steps_ok(ctx, 1, "hf_step"));
+  HF_TRY(monitor_room(ctx, 1));
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   const int rc = step_device(ctx, g_bc, nullptr, rtol, atol, max_it);
   if (rc == HF_ERR_HIP) return rc;
+  if (ctx->mon.on && rc == HF_OK) monitor_record(ctx);
   HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
   HF_HIP(hipStreamSynchronize(ctx->stream));
   float ms = 0.f;
@@ -1466,6 +1470,7 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
     if (nodes[q] < 0 || nodes[q] >= ctx->n) return fail(ctx, HF_ERR_ARG, "hf_run: node %d outside [0,%d)", nodes[q], ctx->n);
   HF_HIP(hipSetDevice(ctx->dev));
   HF_TRY(source_steps_ok(ctx, n_steps, "hf_run"));
+  HF_TRY(monitor_room(ctx, n_steps));
   DevTemp<double> t_gall, t_sall;
   double *&d_gall = t_gall.p, *&d_sall = t_sall.p;
   if (ctx->nbc > 0) {   // all boundary vectors in one transfer; the steps copy device to device
@@ -1486,6 +1491,7 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
     if (ns > 0 && rc == HF_OK)
       hipLaunchKernelGGL(k_gather, dim3((ns + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, ctx->d_u,
                          d_sall + static_cast<size_t>(s) * ns);
+    if (ctx->mon.on && rc == HF_OK) monitor_record(ctx);
   }
   (void)hipEventRecord(ctx->ev1, ctx->stream);
   (void)hipStreamSynchronize(ctx->stream);
@@ -1722,6 +1728,7 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
   HF_TRY(ensure_batch_cols(ctx, nv));     // (a sweep since the last run may have laid the tables out for another width)
   T.lds = ctx->bcols.nv == nv;
   HF_TRY(tangent_levels(ctx));
+  HF_TRY(monitor_room(ctx, n_steps));
   int rc = HF_OK;
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   for (int32_t s = 0; s < n_steps && rc == HF_OK; ++s) {
@@ -1741,12 +1748,14 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
     if (ns > 0)
       hipLaunchKernelGGL(k_gather, dim3((ns + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, ctx->d_u,
                          t_sall.p + static_cast<size_t>(s) * ns);
+    if (ctx->mon.on) monitor_record(ctx);
     // the tangent stage: F = -K_j u^{n+1}, then one batched step of the columns with that load and boundary values h^{n+1}
     HF_TRY(tangent_load(ctx));
     const double* hs = ctx->nbc == 0 ? nullptr : t_hall.p + (h_all ? hstep * s : 0);
     std::swap(ctx->batch, ctx->tanb);
     rc = batch_dispatch(ctx, [&](auto ops) { return decltype(ops)::step(ctx, hs, rtol, atol, max_it); });
     std::swap(ctx->batch, ctx->tanb);
+    if (ctx->mon.on && rc != HF_OK) ctx->mon.count -= 1;   // a step that fails leaves no record
     if (tangent_iters)
       for (int j = 0; j < nv; ++j) tangent_iters[static_cast<size_t>(s) * nv + j] = T.h_scal[j].iters;
     if (ns > 0 && rc == HF_OK) {
@@ -2108,6 +2117,92 @@ int hf_set_source_amplitudes(hf_ctx* ctx, int32_t n_amp, const double* p) {
     if (!std::isfinite(p[k])) return fail(ctx, HF_ERR_ARG, "hf_set_source_amplitudes: amplitude %d is not finite", k);
   ctx->src.amp.assign(p, p + n_amp);
   ctx->src.next = 0;
+  return HF_OK;
+}
+
+int hf_set_monitors(hf_ctx* ctx, int32_t tab_len, const double* threshold) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_set_monitors before hf_set_mesh");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_set_monitors: a batch is open (the batched loop records nothing)");
+  if (tab_len < 0) return fail(ctx, HF_ERR_ARG, "hf_set_monitors: a table of %d entries", tab_len);
+  HF_HIP(hipSetDevice(ctx->dev));
+  std::vector<uint8_t> slot(static_cast<size_t>(ctx->tab_len), static_cast<uint8_t>(MON_NONE));
+  std::vector<double> theta(MON_ND, INFINITY);
+  std::vector<int32_t> tag_of(MON_ND, 0);
+  int nd = 0;
+  for (int32_t tg = 0; threshold && tg < tab_len; ++tg) {
+    const double th = threshold[tg];
+    if (std::isnan(th)) continue;
+    if (tg >= ctx->tab_len || !ctx->h_tag_used[tg]) return fail(ctx, HF_ERR_ARG, "hf_set_monitors: tag %d is not a cell tag of the mesh", tg);
+    if (th == -INFINITY) return fail(ctx, HF_ERR_ARG, "hf_set_monitors: the threshold of tag %d is -inf (NaN: not monitored, +inf: no hot part)", tg);
+    if (nd == MON_ND) return fail(ctx, HF_ERR_ARG, "hf_set_monitors: tag %d is the %dth monitored tag (at most %d)", tg, MON_ND + 1, MON_ND);
+    slot[tg] = static_cast<uint8_t>(nd);
+    tag_of[nd] = tg;
+    theta[nd++] = th;
+  }
+  monitor_free(ctx);   // monitors that were on are off until the new ones are complete: a failure below leaves none set
+  if (nd == 0) return HF_OK;
+  hf_ctx::Monitor& M = ctx->mon;
+  M.nd = nd;
+  M.nchunks = (ctx->ne + MON_T - 1) / MON_T;
+  M.grid = std::min(M.nchunks, MAXP);
+  if (M.grid >= 64) M.grid &= ~7;          // multiple of 8: one equal group of workgroups per XCD (ChunkIter)
+  const size_t G = static_cast<size_t>(M.grid) * MON_ND;
+  HF_TRY(dev_alloc(ctx, &M.slot, static_cast<size_t>(ctx->tab_len)));
+  HF_TRY(dev_alloc(ctx, &M.theta, MON_ND));
+  HF_TRY(dev_alloc(ctx, &M.tags, MON_ND));
+  HF_TRY(dev_alloc(ctx, &M.part_f, 5 * G));
+  HF_TRY(dev_alloc(ctx, &M.part_i, 2 * G));
+  HF_TRY(dev_alloc(ctx, &M.now, monitor_row(ctx)));
+  HF_HIP(copy_sync(ctx, M.slot, slot.data(), slot.size(), hipMemcpyHostToDevice));
+  HF_HIP(copy_sync(ctx, M.theta, theta.data(), sizeof(double) * MON_ND, hipMemcpyHostToDevice));
+  HF_HIP(copy_sync(ctx, M.tags, tag_of.data(), sizeof(int32_t) * MON_ND, hipMemcpyHostToDevice));
+  M.on = true;
+  return HF_OK;
+}
+
+int hf_monitor_now(hf_ctx* ctx, double* out) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_monitor_now before hf_set_mesh");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_monitor_now: a batch is open (the batched loop has no monitors)");
+  if (!ctx->mon.on) return fail(ctx, HF_ERR_STATE, "hf_monitor_now: no monitors set (hf_set_monitors first)");
+  if (!out) return fail(ctx, HF_ERR_ARG, "hf_monitor_now: null pointer");
+  HF_HIP(hipSetDevice(ctx->dev));
+  monitor_launch(ctx, ctx->mon.now);
+  HF_HIP(hipGetLastError());
+  HF_HIP(copy_sync(ctx, out, ctx->mon.now, sizeof(double) * monitor_row(ctx), hipMemcpyDeviceToHost));
+  return HF_OK;
+}
+
+int hf_monitor_count(hf_ctx* ctx, int32_t* n_records) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_monitor_count before hf_set_mesh");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_monitor_count: a batch is open (the batched loop has no monitors)");
+  if (!n_records) return fail(ctx, HF_ERR_ARG, "hf_monitor_count: null pointer");
+  *n_records = static_cast<int32_t>(ctx->mon.count);
+  return HF_OK;
+}
+
+int hf_get_monitors(hf_ctx* ctx, int32_t first, int32_t count, double* out) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_get_monitors before hf_set_mesh");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_get_monitors: a batch is open (the batched loop has no monitors)");
+  if (!ctx->mon.on) return fail(ctx, HF_ERR_STATE, "hf_get_monitors: no monitors set (hf_set_monitors first)");
+  if (first < 0 || count < 0 || static_cast<int64_t>(first) + count > ctx->mon.count)
+    return fail(ctx, HF_ERR_ARG, "hf_get_monitors: records [%d, %lld) outside the %lld records kept", first,
+                static_cast<long long>(first) + count, static_cast<long long>(ctx->mon.count));
+  if (count > 0 && !out) return fail(ctx, HF_ERR_ARG, "hf_get_monitors: null pointer for records [%d, %d)", first, first + count);
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_HIP(copy_sync(ctx, out, ctx->mon.rec + static_cast<size_t>(first) * monitor_row(ctx), sizeof(double) * static_cast<size_t>(count) * monitor_row(ctx),
+                   hipMemcpyDeviceToHost));
+  return HF_OK;
+}
+
+int hf_monitor_clear(hf_ctx* ctx) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_monitor_clear before hf_set_mesh");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_monitor_clear: a batch is open (the batched loop has no monitors)");
+  ctx->mon.count = 0;
   return HF_OK;
 }
 

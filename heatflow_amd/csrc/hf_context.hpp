@@ -307,6 +307,21 @@ struct hf_ctx {
     std::vector<double> amp;     // amplitudes of the next steps; empty: amplitude 0
     size_t next = 0;             // the next step's index into amp
   } src;
+  // region monitors (hf_set_monitors, hf_monitor.hpp): per monitored cell tag a record row after every step of hf_step / hf_run /
+  // hf_run_tangent.  Nothing below is allocated, and nothing is launched, while no monitors are set.
+  struct Monitor {
+    bool on = false;
+    int nd = 0;                  // monitored tags = entries of the monitor dictionary (ascending cell tag)
+    int nchunks = 0, grid = 0;   // chunks of MON_T triangles; workgroups of k_monitor = partials per dictionary index (from the mesh alone)
+    uint8_t* slot = nullptr;     // tab_len entries: dictionary index of a cell tag, 255 = not monitored
+    int32_t* tags = nullptr;     // 64 entries: the cell tag of a dictionary index
+    double* theta = nullptr;     // 64 thresholds by dictionary index (+inf: H = 0)
+    double* part_f = nullptr;    // 5 x grid x 64 doubles: I0, I1, H, the largest and the smallest value of every workgroup
+    int32_t* part_i = nullptr;   // 2 x grid x 64: their nodes
+    double* rec = nullptr;       // cap records of tab_len x 7 doubles
+    double* now = nullptr;       // one record, for hf_monitor_now
+    int64_t cap = 0, count = 0;
+  } mon;
   double *d_z = nullptr, *d_z2 = nullptr;
   // read-flux projection (hf_flux_setup): unit-rho_c r-weighted mass matrix and the projected gradient
   bool flux_ready = false;

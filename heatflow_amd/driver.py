@@ -45,6 +45,7 @@ from .heating import HeatingCurve
 from .aniso import CAPACITY_KINDS, DIRECTIONAL_HINT, capacity_scale, check_capacity_names, check_config, refuse_aniso, split_param
 from .kappa_t import material_cv_table, material_table, picard_sweeps, refuse_tables
 from .mesh import Mesh, load_mesh_arrays
+from .monitors import parse_monitors, problem_monitors, refuse_monitors, used_config as monitors_used_config, write_monitors_csv
 from .source import amplitudes as source_amplitudes, parse_source, refuse_source
 from .solver import DEFAULT_MAX_IT, DEFAULT_RTOL, HeatProblem
 
@@ -174,8 +175,12 @@ def _with_scheme(cfg):
     ``timing.picard_sweeps`` and the tables that ran (``kappa_tables``: {material: {T0, dT, k}}); with cv(T) the same under
     ``rhoc_tables``: {material: {T0, dT, rho_cv}}, written only when a capacity table is set.  An anisotropic conductivity
     travels with its material (``mats.<name>.k_aniso``), so it is written exactly when it is set.  A volumetric
-    source (``heating.source``, heatflow_amd.source) is written exactly when it is set too, with its defaults filled in."""
+    source (``heating.source``, heatflow_amd.source) is written exactly when it is set too, with its defaults filled in, and so
+    is a ``monitors`` block (heatflow_amd.monitors)."""
     out = dict(cfg)
+    mon = parse_monitors(cfg)
+    if mon is not None:
+        out["monitors"] = monitors_used_config(mon)
     out["timing"] = dict(cfg.get("timing") or {}, scheme=time_scheme(cfg))
     src = parse_source(cfg)
     if src is not None:
@@ -259,8 +264,9 @@ class SimulationSession:
         kt = self._kappa_tables(cfg, stack)
         an = self._aniso(stack)
         src = self._source(cfg, stack)
-        self._ensure_problem(self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an, src), tag_to_k, tag_to_rc, dt, bcs,
-                             float(cfg["heating"]["ic_temp"]), scheme, kt, an, src)
+        mon = self._monitors(cfg)
+        self._ensure_problem(self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an, src, mon), tag_to_k, tag_to_rc, dt, bcs,
+                             float(cfg["heating"]["ic_temp"]), scheme, kt, an, src, mon)
 
     def _tables(self, stack):
         tag_to_k = {self.material_tags[m.name]: m.properties["k"] for m in stack.materials}
@@ -275,6 +281,11 @@ class SimulationSession:
         """dict(tags, fwhm, z0, depth) of a configuration with a ``heating.source`` block (HeatProblem's ``source=``), or None."""
         spec = parse_source(cfg)
         return None if spec is None else spec.problem_source(stack, self.material_tags)
+
+    def _monitors(self, cfg):
+        """{region: {"tags", "above"}} of a configuration with a ``monitors`` block (HeatProblem's ``monitors=``), or None."""
+        spec = parse_monitors(cfg)
+        return None if spec is None else problem_monitors(spec, self.material_tags)
 
     def _kappa_tables(self, cfg, stack):
         """(tables {tag: (T0, dT, values)}, Picard sweeps, capacity tables {tag: (T0, dT, values)}) of a kappa(T) / cv(T)
@@ -322,7 +333,7 @@ class SimulationSession:
             self._heats.append(heat_o)
         return bcs
 
-    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler", kt=None, an=None, src=None):
+    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler", kt=None, an=None, src=None, mon=None):
         # the resident problem is reusable only for exactly the same Dirichlet DOF sets, in the same order, and time scheme
         # (and kappa(T) tables and Picard sweeps, or anisotropy multipliers, when a configuration has them)
         key = (dt, tuple(sorted(tag_to_rc.items())),
@@ -336,9 +347,12 @@ class SimulationSession:
             key += (("k_aniso",) + tuple(sorted(an.items())),)
         if src:
             key += (("source", tuple(src["tags"]), src["fwhm"], src["z0"], src["depth"]),)
+        if mon:
+            key += (("monitors",) + tuple((region, tuple(r["tags"]), r["above"]) for region, r in mon.items()),)
         return key
 
-    def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme="backward_euler", kt=None, an=None, src=None):
+    def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme="backward_euler", kt=None, an=None, src=None,
+                        mon=None):
         """The resident HeatProblem for ``key`` (built if absent), its operator valued for ``tag_to_k``."""
         if self.problem is None or key != self._key:
             self.close()
@@ -350,7 +364,8 @@ class SimulationSession:
                                        amg_reuse=True, pattern=self.pattern, amg=shared["blob"] if shared else None,
                                        scheme=scheme, **({"kappa_tables": kt[0], "picard": kt[1]} if kt else {}),
                                        **({"rhoc_tables": kt[2]} if kt and kt[2] else {}),
-                                       **({"k_aniso": an} if an else {}), **({"source": src} if src else {}))
+                                       **({"k_aniso": an} if an else {}), **({"source": src} if src else {}),
+                                       **({"monitors": mon} if mon else {}))
             self._key = key
             self._source_F1 = None
             self._k = dict(tag_to_k)
@@ -401,6 +416,7 @@ class SimulationSession:
         for c in cfgs:
             refuse_tables(c, "run_batch (the batched loop)")
             refuse_source(c, "run_batch (the batched loop)")
+            refuse_monitors(c, "run_batch (the batched loop)")
         if nv not in (2, 4, 8, 16):
             raise ValueError("run_batch: 2, 4, 8 or 16 configurations at a time")
         t_start = time.time()
@@ -502,7 +518,8 @@ class SimulationSession:
         the material's rho * cv in J/m^3/K, its cv or its rho (one of the three per material) -, and / or "fwhm"
         of the heating profile) adds ``tangents`` {param: {watcher: d watcher / d param}} and ``tangent_iters`` (HeatProblem.run_tangent; not with a field sink or the flux projection).
         A ``heating.source`` block (heatflow_amd.source) drives the run by absorbed laser power, the field sink and the flux
-        projection included; not with ``tangents`` or ``two_sided``."""
+        projection included; not with ``tangents`` or ``two_sided``.  A ``monitors`` block (heatflow_amd.monitors) adds
+        ``monitors`` {region: {field: one value per step}} to the result, whichever way the steps are taken."""
         t_start = time.time()
         spec = parse_source(cfg)
         if spec is not None and tangents:
@@ -523,13 +540,16 @@ class SimulationSession:
             refuse_aniso(cfg, "a tangent with respect to the conductivity of an anisotropic material", set(tangents),
                          DIRECTIONAL_HINT)
         src = self._source(cfg, stack)
-        key = self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an, src)
+        mon = self._monitors(cfg)
+        key = self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an, src, mon)
         fresh = self.problem is None or key != self._key
-        self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme, kt, an, src)
+        self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme, kt, an, src, mon)
         if not fresh:
             self.problem.set_state(ic_temp)
             self.problem.iters = []
         prob = self.problem
+        if mon and not fresh:    # the records of this run only
+            prob.clear_monitor_history()
         amp = None
         if spec is not None:     # W -> W/m^3 per step, from the discrete source's own integral
             if self._source_F1 is None:
@@ -622,6 +642,7 @@ class SimulationSession:
             "iters": np.asarray(iters), "loop_time": loop_time, "startup_time": t_loop - t_start,
             "n_dof": prob.n, "dt": dt, "flux": flux,
             **({"tangents": tangent_out, "tangent_iters": titers} if tangent_out is not None else {}),
+            **({"monitors": prob.monitor_history()} if mon else {}),
         }
 
 
@@ -784,6 +805,8 @@ def run_simulation_impl(kind, cfg, mesh_folder, rebuild_mesh=False, visualize_me
         if watcher_points is not None:
             write_watcher_csv(os.path.join(save_folder, "watcher_points.csv"), result["times"], result["watcher_names"],
                               result["watchers"])
+        if result.get("monitors") is not None:
+            write_monitors_csv(os.path.join(save_folder, "monitors.csv"), result["times"], result["monitors"])
         if result.get("flux") is not None:
             result["flux"].write(save_folder)
             print(f"Saved raw gradient data at r=0 nodes to {os.path.join(save_folder, 'radial_gradient_raw.csv')}")

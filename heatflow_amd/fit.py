@@ -25,6 +25,7 @@ from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, KEY, capacity_scale, check
                     split_param)
 from .kappa_t import refuse_tables
 from .source import refuse_source
+from .monitors import refuse_monitors
 
 DEFAULT_EXP_CSV = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "experimental_data",
                                "geballe_heat_data.csv")
@@ -136,6 +137,7 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     scheme = time_scheme(cfg)
     refuse_tables(cfg, "heatflow_amd.fit")
     refuse_source(cfg, "heatflow_amd.fit")
+    refuse_monitors(cfg, "heatflow_amd.fit")
     params = tuple(params)
     refuse_aniso(cfg, "heatflow_amd.fit of the conductivity of an anisotropic material", set(params), DIRECTIONAL_HINT)
     for p in params:

@@ -37,6 +37,7 @@ EXPORTS = [
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
     "hf_set_source", "hf_get_source", "hf_set_source_amplitudes",
+    "hf_set_monitors", "hf_monitor_now", "hf_monitor_count", "hf_get_monitors", "hf_monitor_clear",
     "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_set_shape", "hf_tangent_set_capacity", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
     "hf_set_value_lists", "hf_get_value_lists", "hf_get_projection", "hf_get_flux_system",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
@@ -142,6 +143,11 @@ def load_library():
         "hf_set_source": [vp, i32, pi, dbl, dbl, dbl],
         "hf_get_source": [vp, pd],
         "hf_set_source_amplitudes": [vp, i32, pd],
+        "hf_set_monitors": [vp, i32, pd],
+        "hf_monitor_now": [vp, pd],
+        "hf_monitor_count": [vp, pi],
+        "hf_get_monitors": [vp, i32, i32, pd],
+        "hf_monitor_clear": [vp],
         "hf_tangent_setup": [vp, i32, pi],
         "hf_tangent_setup_dir": [vp, i32, pi, pi, pi],
         "hf_tangent_set_shape": [vp, i32, pd],
@@ -752,6 +758,50 @@ class HeatflowHIP:
         means amplitude 0 for every step."""
         p = _f64([] if p is None else p).ravel()
         self._check(self._lib.hf_set_source_amplitudes(self._ctx, len(p), _pd(p) if len(p) else None))
+
+    # -- region monitors: per cell tag the extremes, int r dA, int u r dA and the hot part after every step (DESIGN.md 3.17) ----
+    MONITOR_FIELDS = ("T_max", "node_max", "T_min", "node_min", "I0", "I1", "H")
+
+    def set_monitors(self, thresholds):
+        """``thresholds`` = {cell tag: theta | None}: the tag is monitored, with the hot part H taken above ``theta`` (None, or
+        +inf: no hot part, H = 0).  An empty mapping (or None) removes the monitors.  Every call drops the records."""
+        thresholds = dict(thresholds or {})
+        if not thresholds:
+            self._check(self._lib.hf_set_monitors(self._ctx, 0, None))
+            return
+        tab = np.full(max(self.tab_len, max(int(t) for t in thresholds) + 1), np.nan, dtype=np.float64)
+        for t, th in thresholds.items():
+            if int(t) < 0:
+                raise ValueError(f"set_monitors: tag {t} is not a cell tag of the mesh")
+            th = float("inf") if th is None else float(th)
+            if np.isnan(th):
+                raise ValueError(f"set_monitors: the threshold of tag {t} is NaN (leave the tag out, or None for no hot part)")
+            tab[int(t)] = th
+        self._check(self._lib.hf_set_monitors(self._ctx, len(tab), _pd(tab)))
+
+    def monitor_now(self):
+        """The record of the current state, [tab_len, 7] (fields: MONITOR_FIELDS); nothing is recorded."""
+        out = np.empty((self.tab_len, 7), dtype=np.float64)
+        self._check(self._lib.hf_monitor_now(self._ctx, _pd(out)))
+        return out
+
+    def monitor_count(self):
+        c = C.c_int32()
+        self._check(self._lib.hf_monitor_count(self._ctx, C.byref(c)))
+        return int(c.value)
+
+    def get_monitors(self, first=0, count=None):
+        """Records ``first`` .. ``first + count - 1`` (default: all from ``first``) as an array [records, tab_len, 7]: one per step of
+        step / run / run_tangent since set_monitors / clear_monitor_records; rows of tags that are not monitored are zeros."""
+        first = int(first)
+        count = self.monitor_count() - first if count is None else int(count)
+        out = np.empty((max(count, 0), self.tab_len, 7), dtype=np.float64)
+        self._check(self._lib.hf_get_monitors(self._ctx, first, count, _pd(out)))
+        return out
+
+    def clear_monitor_records(self):
+        """Drop the records; the table of monitored tags stays."""
+        self._check(self._lib.hf_monitor_clear(self._ctx))
 
     # -- inspection ----------------------------------------------------------------------
     def get_csr(self, values=True):

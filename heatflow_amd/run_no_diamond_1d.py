@@ -34,6 +34,7 @@ from .mesh import load_mesh_arrays
 from .aniso import refuse_aniso
 from .kappa_t import refuse_tables
 from .source import refuse_source
+from .monitors import refuse_monitors
 
 
 def extract_1d_submesh_from_2d(coords, tris, tags, tolerance=1e-10):
@@ -98,6 +99,7 @@ def run_1d(cfg, mesh_folder_2d, mesh_folder_1d=None, rebuild_mesh=False, visuali
         raise ValueError(f"run_1d: timing.scheme {scheme!r} is not supported by the 1-D model (backward Euler only)")
     refuse_tables(cfg, "run_1d (the 1-D model)")
     refuse_source(cfg, "run_1d (the 1-D model)")
+    refuse_monitors(cfg, "run_1d (the 1-D model)")
     refuse_aniso(cfg, "run_1d (the 1-D model)")
     with suppress_output(suppress_print):
         t_start = time.time()

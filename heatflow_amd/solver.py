@@ -18,6 +18,7 @@ import numpy as np
 
 from .bc import gather_bc_values, gather_plan, merge_bcs
 from .hip_backend import ASM_ROW_GATHER, PC_AMG, PC_JACOBI, HeatflowHIP, time_scheme_code
+from .monitors import check_regions, combine as combine_monitors, tag_thresholds
 
 # Default PCG tolerance: at rtol = 1e-10 the temperature field agrees with a sparse
 # direct solve of the same system to ~3e-6 K (measured on the stock and the 1M-DOF
@@ -61,12 +62,17 @@ class HeatProblem:
               tags ``tags`` with the shape exp(-4 ln2 r^2 / fwhm^2) exp(-|z - z0| / depth) (``depth`` absent or inf: uniform
               in z).  Set right after the materials; its amplitude per step is :meth:`run`'s ``source_amplitude``.  None: no
               source, the call sequence of before.
+    monitors : {region: {"tags": [cell tags], "above": theta | None}} - region monitors (hf_set_monitors): after
+              every step of :meth:`step`, :meth:`run` and :meth:`run_tangent` the GPU records, per tag, the extremes, the volume
+              integrals and the part above ``above``; :meth:`monitor_history` and :meth:`monitors_now` combine them per region.
+              Set right after the materials.  ``energy`` is measured from ``u0`` when it is a scalar (attribute
+              ``monitor_T_ref``).  None / {}: no monitors, the call sequence of before.
     """
 
     def __init__(self, coords, tris, tags, tag_to_k, tag_to_rho_cv, dt, bcs, u0, *, backend=None, device_id=0,
                  assembly_mode=ASM_ROW_GATHER, rtol=DEFAULT_RTOL, atol=0.0, max_it=DEFAULT_MAX_IT,
                  precond=PC_JACOBI, amg_reuse=False, pattern=None, amg=None, scheme="backward_euler", kappa_tables=None,
-                 picard=1, rhoc_tables=None, k_aniso=None, source=None):
+                 picard=1, rhoc_tables=None, k_aniso=None, source=None, monitors=None):
         self.coords = np.ascontiguousarray(coords, dtype=np.float64)
         self.n = self.coords.shape[0]
         self.dt = float(dt)
@@ -83,6 +89,9 @@ class HeatProblem:
             raise ValueError("HeatProblem: k_aniso together with kappa_tables / rhoc_tables is not supported "
                              "(the table kernels are isotropic)")
         self.source = check_source(source)
+        self.monitors = check_regions(monitors)
+        self._monitor_tags = tag_thresholds(self.monitors) if self.monitors else {}
+        self.monitor_T_ref = float(u0) if np.isscalar(u0) else None
         scheme_code = time_scheme_code(scheme)     # (an unknown name raises before any backend call)
         self.backend = backend if backend is not None else HeatflowHIP(device_id)
         self._own_backend = backend is None
@@ -98,6 +107,8 @@ class HeatProblem:
             self.backend.set_anisotropy(self.k_aniso)
         if self.source:          # problems without a source make no extra call
             self.backend.set_source(self.source["tags"], self.source["fwhm"], self.source["z0"], self.source["depth"])
+        if self.monitors:        # problems without monitors make no extra call
+            self.backend.set_monitors(self._monitor_tags)
         if self.bcs:
             self.bc_dofs, self._owner, self._pos = merge_bcs(self.bcs)
         else:
@@ -128,6 +139,7 @@ class HeatProblem:
         """(Re)load the coefficient tables; with ``assemble`` re-value M, A (kappa sweeps reuse
         the mesh, the pattern and the Dirichlet set)."""
         tags = sorted(tag_to_k)
+        self._rho_c = {int(t): float(tag_to_rho_cv[t]) for t in tags}      # the constants of the monitors' energy
         self.backend.set_materials(np.array(tags, dtype=np.int32),
                                    np.array([tag_to_k[t] for t in tags], dtype=np.float64),
                                    np.array([tag_to_rho_cv[t] for t in tags], dtype=np.float64))
@@ -159,6 +171,30 @@ class HeatProblem:
 
     def state(self):
         return self.backend.get_state()
+
+    # -- region monitors -------------------------------------------------------------------
+    def _combine_monitors(self, records):
+        if not self.monitors:
+            raise ValueError("monitors: the problem has no monitors (HeatProblem(..., monitors=))")
+        return combine_monitors(records, self.monitors, self.coords, rho_c=self._rho_c, T_ref=self.monitor_T_ref,
+                                tabled=self.rhoc_tables)
+
+    def monitors_now(self):
+        """{region: {field: value}} of the current state (heatflow_amd.monitors for the fields); nothing is recorded."""
+        if not self.monitors:
+            raise ValueError("monitors: the problem has no monitors (HeatProblem(..., monitors=))")
+        return self._combine_monitors(self.backend.monitor_now())
+
+    def monitor_history(self, first=0, count=None):
+        """{region: {field: array}}: one value per recorded step (every step of step / run / run_tangent since the problem was
+        made or :meth:`clear_monitor_history` was called), from record ``first`` on."""
+        if not self.monitors:
+            raise ValueError("monitors: the problem has no monitors (HeatProblem(..., monitors=))")
+        return self._combine_monitors(self.backend.get_monitors(first, count))
+
+    def clear_monitor_history(self):
+        if self.monitors:
+            self.backend.clear_monitor_records()
 
     def source_vector(self):
         """F1 of the source: the load at unit amplitude (n values; 2 pi sum(F1) = the power in W per unit amplitude)."""

@@ -374,6 +374,41 @@ int hf_set_source(hf_ctx* ctx, int32_t n_tags, const int32_t* tags, double fwhm,
 int hf_get_source(hf_ctx* ctx, double* F);
 int hf_set_source_amplitudes(hf_ctx* ctx, int32_t n_amp, const double* p);
 
+/* Region monitors: after every step, per monitored cell tag t, over the triangles e with tag(e) = t and the
+ * nodal state u (A_e the triangle's area in (z, r), r_0..r_2 its nodal radii, rs their sum):
+ *     T_max, node_max   the largest nodal value over the nodes of those triangles and the smallest node id that attains it
+ *     T_min, node_min   the same for the smallest value
+ *     I0 = sum_e A_e rs / 3                                   = int r dA (the volume is 2 pi I0)
+ *     I1 = sum_e (A_e / 12) sum_i (rs + r_i) u_i              = int u_h r dA, exact for the P1 field
+ *     H  = int over {u_h > theta_t} of r dA                   the exact cut of the linear interpolant in each triangle; a node
+ *                                                             is "above" when u > theta, strictly
+ * formed by k_monitor (a lane per triangle, fixed chunks, partials per workgroup in a layout the mesh alone fixes, added in a
+ * fixed order by k_monitor_final): no atomics, the same bits from run to run and from context to context.  Two launches per
+ * record, on the stream, with no host synchronisation.  A context without monitors launches exactly what it launched before.
+ * hf_set_monitors  threshold[t], t < tab_len (tab_len = the mesh's largest cell tag + 1; entries a shorter table leaves out count
+ *        as NaN): NaN = tag t is not monitored, +inf = monitored with H = 0, finite = monitored with that theta.  NULL,
+ *        tab_len = 0 or a table of only NaN removes the monitors.  Every call drops the records.  At most 64 tags are monitored.
+ * hf_monitor_now   the record of the current state (after hf_set_state, a steady solve, ...): rows * 7 doubles, rows = the mesh's
+ *        largest cell tag + 1; nothing is recorded.
+ * hf_monitor_count the number of records kept.
+ * hf_get_monitors  records first .. first + count - 1: out[((k - first) * rows + t) * 7 + f], f = T_max, node_max, T_min,
+ *        node_min, I0, I1, H; node ids are stored as doubles; the row of a tag that is not monitored is seven exact zeros.
+ * hf_monitor_clear drops the records and keeps the table.
+ * Record k is the state after the k-th recorded step since the last hf_set_monitors / hf_monitor_clear: every step of hf_step,
+ * hf_run and hf_run_tangent (the primal state; under Picard sweeps once, after the last sweep) that returns HF_OK; a step that
+ * returns an error leaves no record.  These calls make room for their records before their first launch.  The batched loop
+ * (hf_batch_*) records nothing, and neither do the steady solves, which hf_monitor_now serves.
+ * HF_ERR_STATE: before hf_set_mesh; while a batch is open; hf_monitor_now / hf_get_monitors while no monitors are set.
+ * HF_ERR_ARG (the message names the call and the tag or range): a non-NaN entry on a tag that is not a cell tag of the mesh, -inf,
+ *        a 65th monitored tag, a range outside the records kept, null pointers.
+ * hf_set_mesh removes the monitors; they survive hf_set_materials, hf_assemble, hf_set_state, the table calls, the source calls
+ * and the steady calls (they depend on the mesh alone). */
+int hf_set_monitors(hf_ctx* ctx, int32_t tab_len, const double* threshold);
+int hf_monitor_now(hf_ctx* ctx, double* out);
+int hf_monitor_count(hf_ctx* ctx, int32_t* n_records);
+int hf_get_monitors(hf_ctx* ctx, int32_t first, int32_t count, double* out);
+int hf_monitor_clear(hf_ctx* ctx);
+
 /* Tangent runs: the exact derivatives s_j = du/dtheta_j of the time loop with respect to up to 16 parameters, advanced next to
  * the primal.  A column's parameter scales the conductivity of the cell tags mapped to it (K_j = the sum of
  * their unit-conductivity r-weighted stiffness), enters the Dirichlet values through h_j = dg/dtheta_j, or both.  After every
