@@ -1525,6 +1525,7 @@ int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
   tangent_free(ctx);
   ctx->tan.steady_state = from_steady;
   const int nv = n_par <= 2 ? 2 : n_par <= 4 ? 4 : n_par <= 8 ? 8 : 16;
+  if (ctx->mon.tnv != nv) montan_drop(ctx);   // derivative records of another width
   std::vector<int32_t> col(64, -1);    // by row-gather tag-dictionary index, as the coefficient tables of the kernel
   for (size_t q = 0; q < ctx->h_rg_tags.size(); ++q) col[q] = tag_col[ctx->h_rg_tags[q]];
   hf_ctx::Batch& T = ctx->tanb;
@@ -1570,6 +1571,7 @@ int hf_tangent_setup_dir(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col_k, c
   tangent_free(ctx);
   ctx->tan.steady_state = from_steady;
   const int nv = n_par <= 2 ? 2 : n_par <= 4 ? 4 : n_par <= 8 ? 8 : 16;
+  if (ctx->mon.tnv != nv) montan_drop(ctx);   // derivative records of another width
   std::vector<TanDir> dir(64, TanDir{-1, -1, 0.0, 0.0});    // by row-gather tag-dictionary index, as the coefficient tables of the kernel
   for (size_t q = 0; q < ctx->h_rg_tags.size() && q < 64; ++q) {
     const int32_t t = ctx->h_rg_tags[q];
@@ -1729,6 +1731,8 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
   T.lds = ctx->bcols.nv == nv;
   HF_TRY(tangent_levels(ctx));
   HF_TRY(monitor_room(ctx, n_steps));
+  HF_TRY(montan_room(ctx, nv, n_steps));
+  const bool mon_tan = ctx->mon.on && ctx->mon.tan_on;
   int rc = HF_OK;
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   for (int32_t s = 0; s < n_steps && rc == HF_OK; ++s) {
@@ -1756,6 +1760,7 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
     rc = batch_dispatch(ctx, [&](auto ops) { return decltype(ops)::step(ctx, hs, rtol, atol, max_it); });
     std::swap(ctx->batch, ctx->tanb);
     if (ctx->mon.on && rc != HF_OK) ctx->mon.count -= 1;   // a step that fails leaves no record
+    if (mon_tan && rc == HF_OK) montan_record(ctx);        // derivatives of that record along the columns just stepped
     if (tangent_iters)
       for (int j = 0; j < nv; ++j) tangent_iters[static_cast<size_t>(s) * nv + j] = T.h_scal[j].iters;
     if (ns > 0 && rc == HF_OK) {
@@ -2203,6 +2208,84 @@ int hf_monitor_clear(hf_ctx* ctx) {
   if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_monitor_clear before hf_set_mesh");
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_monitor_clear: a batch is open (the batched loop has no monitors)");
   ctx->mon.count = 0;
+  ctx->mon.tcount = 0;
+  ctx->mon.tindex.clear();
+  return HF_OK;
+}
+
+int hf_set_monitor_tangents(hf_ctx* ctx, int32_t on) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_set_monitor_tangents before hf_set_mesh");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_set_monitor_tangents: a batch is open (the batched loop has no monitors)");
+  if (on && !ctx->mon.on) return fail(ctx, HF_ERR_STATE, "hf_set_monitor_tangents: no monitors set (hf_set_monitors first)");
+  if (on) {
+    HF_HIP(hipSetDevice(ctx->dev));
+    HF_TRY(montan_parts(ctx));
+  }
+  ctx->mon.tan_on = on != 0;
+  return HF_OK;
+}
+
+int hf_monitor_tangent_count(hf_ctx* ctx, int32_t* n_records, int32_t* nv) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_monitor_tangent_count before hf_set_mesh");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_monitor_tangent_count: a batch is open (the batched loop has no monitors)");
+  if (!n_records || !nv) return fail(ctx, HF_ERR_ARG, "hf_monitor_tangent_count: null pointer");
+  *n_records = static_cast<int32_t>(ctx->mon.tcount);
+  *nv = ctx->mon.tnv;
+  return HF_OK;
+}
+
+int hf_get_monitor_tangents(hf_ctx* ctx, int32_t first, int32_t count, double* out, int32_t* record_index) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_get_monitor_tangents before hf_set_mesh");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_get_monitor_tangents: a batch is open (the batched loop has no monitors)");
+  if (!ctx->mon.on) return fail(ctx, HF_ERR_STATE, "hf_get_monitor_tangents: no monitors set (hf_set_monitors first)");
+  if (first < 0 || count < 0 || static_cast<int64_t>(first) + count > ctx->mon.tcount)
+    return fail(ctx, HF_ERR_ARG, "hf_get_monitor_tangents: records [%d, %lld) outside the %lld derivative records kept", first,
+                static_cast<long long>(first) + count, static_cast<long long>(ctx->mon.tcount));
+  if (count > 0 && !out) return fail(ctx, HF_ERR_ARG, "hf_get_monitor_tangents: null pointer for records [%d, %d)", first, first + count);
+  HF_HIP(hipSetDevice(ctx->dev));
+  const size_t row = montan_row(ctx, ctx->mon.tnv);
+  if (count > 0)
+    HF_HIP(copy_sync(ctx, out, ctx->mon.trec + static_cast<size_t>(first) * row, sizeof(double) * static_cast<size_t>(count) * row, hipMemcpyDeviceToHost));
+  if (record_index)
+    for (int32_t k = 0; k < count; ++k) record_index[k] = ctx->mon.tindex[static_cast<size_t>(first) + k];
+  return HF_OK;
+}
+
+int hf_monitor_tangent_eval(hf_ctx* ctx, int32_t nv, const double* s, int32_t n_shape, const int32_t* shape_col, const double* vz, double* out) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_monitor_tangent_eval before hf_set_mesh");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_monitor_tangent_eval: a batch is open (the batched loop has no monitors)");
+  if (!ctx->mon.on) return fail(ctx, HF_ERR_STATE, "hf_monitor_tangent_eval: no monitors set (hf_set_monitors first)");
+  if (nv != 2 && nv != 4 && nv != 8 && nv != 16) return fail(ctx, HF_ERR_ARG, "hf_monitor_tangent_eval: nv = %d (2, 4, 8 or 16 columns)", nv);
+  if (n_shape < 0 || n_shape > MON_NS) return fail(ctx, HF_ERR_ARG, "hf_monitor_tangent_eval: %d shape columns (0..%d)", n_shape, MON_NS);
+  if (!s || !out || (n_shape > 0 && (!shape_col || !vz))) return fail(ctx, HF_ERR_ARG, "hf_monitor_tangent_eval: null pointer");
+  MonShape sh{nullptr, n_shape, n_shape, {0, 0, 0, 0}};
+  for (int q = 0; q < n_shape; ++q) {
+    if (shape_col[q] < 0 || shape_col[q] >= nv)
+      return fail(ctx, HF_ERR_ARG, "hf_monitor_tangent_eval: shape column %d outside [0,%d)", shape_col[q], nv);
+    for (int p = 0; p < q; ++p)
+      if (shape_col[p] == shape_col[q]) return fail(ctx, HF_ERR_ARG, "hf_monitor_tangent_eval: shape column %d is listed twice", shape_col[q]);
+    sh.col[q] = shape_col[q];
+  }
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_TRY(montan_parts(ctx));
+  const size_t n = static_cast<size_t>(ctx->n);
+  DevTemp<double> t_s, t_v, t_out;
+  HF_TRY(dev_alloc(ctx, &t_s.p, n * nv));
+  HF_TRY(dev_alloc(ctx, &t_out.p, montan_row(ctx, nv)));
+  HF_HIP(copy_sync(ctx, t_s.p, s, sizeof(double) * n * nv, hipMemcpyHostToDevice));
+  if (n_shape > 0) {
+    HF_TRY(dev_alloc(ctx, &t_v.p, n * n_shape));
+    HF_HIP(copy_sync(ctx, t_v.p, vz, sizeof(double) * n * n_shape, hipMemcpyHostToDevice));
+    sh.v = t_v.p;
+  }
+  monitor_launch(ctx, ctx->mon.now);
+  montan_launch(ctx, nv, t_s.p, sh, ctx->mon.now, t_out.p);
+  HF_HIP(hipGetLastError());
+  HF_HIP(copy_sync(ctx, out, t_out.p, sizeof(double) * montan_row(ctx, nv), hipMemcpyDeviceToHost));
   return HF_OK;
 }
 

@@ -321,6 +321,15 @@ struct hf_ctx {
     double* rec = nullptr;       // cap records of tab_len x 7 doubles
     double* now = nullptr;       // one record, for hf_monitor_now
     int64_t cap = 0, count = 0;
+    // derivative records (hf_set_monitor_tangents): per record rows x tnv x 5 doubles, taken by hf_run_tangent after
+    // the tangent stage of every step.  Nothing below is allocated, and nothing is launched, while the switch is off (the partials
+    // also serve hf_monitor_tangent_eval, which allocates them on its first call).
+    bool tan_on = false;
+    int tnv = 0;                 // columns of a derivative record: the nv of the tangent set-up the records were taken under
+    double* tpart = nullptr;     // nd x (2 x 16 + 4) x grid doubles: dI1, dH per column and dI0 per shape slot of every workgroup
+    double* trec = nullptr;      // tcap records of tab_len x tnv x 5 doubles
+    int64_t tcap = 0, tcount = 0;
+    std::vector<int32_t> tindex; // the primal record each derivative record belongs to
   } mon;
   double *d_z = nullptr, *d_z2 = nullptr;
   // read-flux projection (hf_flux_setup): unit-rho_c r-weighted mass matrix and the projected gradient

@@ -185,11 +185,247 @@ __global__ __launch_bounds__(MON_FT) void k_monitor_final(int G, int tab_len, Mo
 }
 static_assert(MAXP <= MON_FT, "k_monitor_final holds one partial per lane");
 
+// ---- derivatives of the sums in tangent runs (hf_set_monitor_tangents) ----------------------------------------
+
+constexpr int MON_TF = 5;         // fields of a derivative row: dT_max, dT_min, dI0, dI1, dH
+constexpr int MON_NS = 4;         // shape slots (hf_tangent_set_shape allows 4 columns with a velocity)
+constexpr size_t MON_LDS = 64 * 1024 - 1024;   // dynamic LDS one workgroup of k_monitor_tan may ask for (s_th is static)
+
+// the shape slots of a launch: velocities n x stride interleaved by node, slot s belongs to column col[s]; n = 0: none
+struct MonShape { const double* v; int stride, n; int col[MON_NS]; };
+// what a workgroup of k_monitor_tan leaves: I1 / H[(index * nv + j) * workgroups + workgroup], I0[(index * 4 + slot) * workgroups + workgroup]
+struct MonTanPart { double *I1, *H, *I0; };
+
+// What the columns of one triangle share: monitor_term's quantities, operation for operation, and of a cut triangle the odd node
+// out `a` (b, c follow it in the triangle's order), sb, sc, the two differences of u, of r and the bracket
+//   G = (ra + (ra + sb (rb - ra))) + (ra + sc (rc - ra))
+struct MonGeo {
+  double d, A, rs, r0, r1, r2, I0, I1, H;
+  double sb, sc, dab, dac, rba, rca, G;
+  int a;           // -1: no cut (0 or 3 nodes above)
+  bool odd;        // one node above (H = cut); else two (H = I0 - cut)
+};
+__device__ __forceinline__ MonGeo monitor_geo(const double2 P0, const double2 P1, const double2 P2, double u0, double u1, double u2,
+                                              double theta) {
+#pragma clang fp contract(off)
+  MonGeo g;
+  g.d = (P1.x - P0.x) * (P2.y - P0.y) - (P2.x - P0.x) * (P1.y - P0.y);
+  g.A = 0.5 * fabs(g.d);
+  g.r0 = P0.y; g.r1 = P1.y; g.r2 = P2.y;
+  g.rs = (P0.y + P1.y) + P2.y;
+  g.I0 = (g.A * g.rs) / 3.0;
+  g.I1 = (g.A / 12.0) * (((g.rs + P0.y) * u0 + (g.rs + P1.y) * u1) + (g.rs + P2.y) * u2);
+  g.a = -1; g.odd = false;
+  g.sb = g.sc = g.dab = g.dac = g.rba = g.rca = g.G = 0.0;
+  const bool a0 = u0 > theta, a1 = u1 > theta, a2 = u2 > theta;
+  const int cnt = static_cast<int>(a0) + static_cast<int>(a1) + static_cast<int>(a2);
+  if (cnt == 0) { g.H = 0.0; return g; }
+  if (cnt == 3) { g.H = g.I0; return g; }
+  g.odd = cnt == 1;
+  const int a = (a0 == g.odd) ? 0 : (a1 == g.odd) ? 1 : 2;
+  g.a = a;
+  const double ua = a == 0 ? u0 : a == 1 ? u1 : u2, ub = a == 0 ? u1 : a == 1 ? u2 : u0, uc = a == 0 ? u2 : a == 1 ? u0 : u1;
+  const double ra = a == 0 ? P0.y : a == 1 ? P1.y : P2.y, rb = a == 0 ? P1.y : a == 1 ? P2.y : P0.y, rc = a == 0 ? P2.y : a == 1 ? P0.y : P1.y;
+  g.dab = ua - ub; g.dac = ua - uc;
+  g.sb = (ua - theta) / g.dab; g.sc = (ua - theta) / g.dac;
+  g.rba = rb - ra; g.rca = rc - ra;
+  g.G = (ra + (ra + g.sb * g.rba)) + (ra + g.sc * g.rca);
+  const double cut = (((g.A * g.sb) * g.sc) * g.G) / 3.0;
+  g.H = g.odd ? cut : g.I0 - cut;
+  return g;
+}
+
+// The derivatives of one triangle's I1 and H along one tangent column with nodal values t0, t1, t2 (u moves, the nodes do not),
+// every operation in the order DESIGN.md 3.18 pins (no contraction):
+//   J1   = (A / 12) (((rs + r0) t0 + (rs + r1) t1) + (rs + r2) t2)
+//   pb   = ((1 - sb) ta + sb tb) / (ua - ub),   pc = ((1 - sc) ta + sc tc) / (ua - uc)
+//   dcut = (A ((pb sc + sb pc) G + (sb sc) (pb (rb - ra) + pc (rc - ra)))) / 3;   dH = dcut (one above), -dcut (two above), else 0
+struct MonTan { double dI1, dH; };
+__device__ __forceinline__ MonTan monitor_term_tan(const MonGeo& g, double t0, double t1, double t2) {
+#pragma clang fp contract(off)
+  MonTan o;
+  o.dI1 = (g.A / 12.0) * (((g.rs + g.r0) * t0 + (g.rs + g.r1) * t1) + (g.rs + g.r2) * t2);
+  o.dH = 0.0;
+  if (g.a >= 0) {
+    const int a = g.a;
+    const double ta = a == 0 ? t0 : a == 1 ? t1 : t2, tb = a == 0 ? t1 : a == 1 ? t2 : t0, tc = a == 0 ? t2 : a == 1 ? t0 : t1;
+    const double pb = ((1.0 - g.sb) * ta + g.sb * tb) / g.dab;
+    const double pc = ((1.0 - g.sc) * ta + g.sc * tc) / g.dac;
+    const double dcut = (g.A * ((pb * g.sc + g.sb * pc) * g.G + (g.sb * g.sc) * (pb * g.rba + pc * g.rca))) / 3.0;
+    o.dH = g.odd ? dcut : -dcut;
+  }
+  return o;
+}
+
+// k_monitor's sibling for the derivatives: one lane per triangle, the same chunks, schedule, slot table and per-wave shuffle trees;
+// the lane loads its three nodes' NV tangents s[node * nvt + j0 .. + NV) as vectors, forms (dI1, dH) of every column and, per
+// shape slot, q = dd / d with dd = (v1 - v0) (r2 - r0) - (v2 - v0) (r1 - r0): dI0 = q I0 of the slot, and the slot's column gets
+// dI1 = J1 + q I1, dH = dH + q H.  The per-wave LDS accumulators - [wave][index][NV] for dI1 and dH, [wave][index][4] for dI0, sized
+// by the nd monitored - take one addition per chunk and index present, in ascending chunk order, and are added in wave order at the
+// end.  No atomics; the bits of column j depend on the mesh, the table, u, column j of s and the velocities only.
+template <int NV>
+__global__ __launch_bounds__(MON_T) void k_monitor_tan(int ne, int nchunks, int tab_len, int nd, int nvt, int j0, const int4* __restrict__ elem,
+                                                      const double2* __restrict__ zr, const double* __restrict__ u,
+                                                      const double* __restrict__ s, const uint8_t* __restrict__ slot_of_tag,
+                                                      const double* __restrict__ theta, MonShape sh, MonTanPart part) {
+  extern __shared__ double s_acc[];         // 4 x nd x NV (dI1), 4 x nd x NV (dH), 4 x nd x 4 (dI0), then tab_len bytes of slots
+  __shared__ double s_th[MON_ND];
+  const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+  const int nacc = 4 * nd * (2 * NV + MON_NS);
+  double* const s_I1 = s_acc;
+  double* const s_H = s_acc + 4 * nd * NV;
+  double* const s_I0 = s_acc + 8 * nd * NV;
+  uint8_t* const s_slot = reinterpret_cast<uint8_t*>(s_acc + nacc);
+  for (int i = t; i < tab_len; i += MON_T) s_slot[i] = slot_of_tag[i];
+  if (t < MON_ND) s_th[t] = theta[t];
+  for (int i = t; i < nacc; i += MON_T) s_acc[i] = 0.0;
+  __syncthreads();
+  for (ChunkIter it(nchunks); it.chunk < it.end; it.chunk += it.step) {
+    const int e = it.chunk * MON_T + t;
+    int d = -1;
+    int4 E = make_int4(0, 0, 0, 0);
+    if (e < ne) {
+      E = elem[e];
+      const int sl = s_slot[E.w];
+      if (sl != MON_NONE) d = sl;
+    }
+    double m1[NV], mH[NV], m0[MON_NS];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) { m1[j] = 0.0; mH[j] = 0.0; }
+#pragma unroll
+    for (int q = 0; q < MON_NS; ++q) m0[q] = 0.0;
+    if (d >= 0) {
+#pragma clang fp contract(off)
+      const MonGeo g = monitor_geo(zr[E.x], zr[E.y], zr[E.z], u[E.x], u[E.y], u[E.z], s_th[d]);
+      const double2* const s0 = reinterpret_cast<const double2*>(s + static_cast<size_t>(E.x) * nvt + j0);
+      const double2* const s1 = reinterpret_cast<const double2*>(s + static_cast<size_t>(E.y) * nvt + j0);
+      const double2* const s2 = reinterpret_cast<const double2*>(s + static_cast<size_t>(E.z) * nvt + j0);
+      double qs[MON_NS];
+#pragma unroll
+      for (int q = 0; q < MON_NS; ++q) {
+        qs[q] = 0.0;
+        if (q < sh.n) {
+          const double v0 = sh.v[static_cast<size_t>(E.x) * sh.stride + q], v1 = sh.v[static_cast<size_t>(E.y) * sh.stride + q],
+                       v2 = sh.v[static_cast<size_t>(E.z) * sh.stride + q];
+          const double dd = (v1 - v0) * (g.r2 - g.r0) - (v2 - v0) * (g.r1 - g.r0);
+          qs[q] = dd / g.d;
+          m0[q] = qs[q] * g.I0;
+        }
+      }
+#pragma unroll
+      for (int jj = 0; jj < NV / 2; ++jj) {
+        const double2 a = s0[jj], b = s1[jj], c = s2[jj];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int j = 2 * jj + h;
+          const MonTan m = monitor_term_tan(g, h ? a.y : a.x, h ? b.y : b.x, h ? c.y : c.x);
+          m1[j] = m.dI1; mH[j] = m.dH;
+#pragma unroll
+          for (int q = 0; q < MON_NS; ++q)
+            if (q < sh.n && sh.col[q] == j0 + j) { m1[j] = m1[j] + qs[q] * g.I1; mH[j] = mH[j] + qs[q] * g.H; }
+        }
+      }
+    }
+    unsigned long long todo = __ballot(d >= 0);      // the same in every lane: the loop is uniform over the wave
+    while (todo != 0ull) {
+      const int ds = __shfl(d, __ffsll(static_cast<long long>(todo)) - 1, 64);
+      const bool mine = d == ds;
+      double* const w1 = s_I1 + (wv * nd + ds) * NV;
+      double* const wH = s_H + (wv * nd + ds) * NV;
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+#pragma clang fp contract(off)
+        double a1 = mine ? m1[j] : 0.0, a2 = mine ? mH[j] : 0.0;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          a1 += __shfl_down(a1, o, 64);
+          a2 += __shfl_down(a2, o, 64);
+        }
+        if (lane == 0) { w1[j] += a1; wH[j] += a2; }
+      }
+#pragma unroll
+      for (int q = 0; q < MON_NS; ++q) {
+#pragma clang fp contract(off)
+        if (q < sh.n) {
+          double a0 = mine ? m0[q] : 0.0;
+#pragma unroll
+          for (int o = 32; o > 0; o >>= 1) a0 += __shfl_down(a0, o, 64);
+          if (lane == 0) s_I0[(wv * nd + ds) * MON_NS + q] += a0;
+        }
+      }
+      todo &= ~__ballot(mine);
+    }
+  }
+  __syncthreads();
+  const size_t G = gridDim.x;
+  for (int i = t; i < nd * NV; i += MON_T) {
+#pragma clang fp contract(off)
+    const int dd = i / NV, j = i - dd * NV;
+    const size_t o = (static_cast<size_t>(dd) * nvt + j0 + j) * G + blockIdx.x;
+    const int w = nd * NV;
+    part.I1[o] = ((s_I1[i] + s_I1[w + i]) + s_I1[2 * w + i]) + s_I1[3 * w + i];
+    part.H[o] = ((s_H[i] + s_H[w + i]) + s_H[2 * w + i]) + s_H[3 * w + i];
+  }
+  if (j0 == 0)
+    for (int i = t; i < nd * MON_NS; i += MON_T) {
+#pragma clang fp contract(off)
+      const int w = nd * MON_NS;
+      part.I0[static_cast<size_t>(i) * G + blockIdx.x] = ((s_I0[i] + s_I0[w + i]) + s_I0[2 * w + i]) + s_I0[3 * w + i];
+    }
+}
+
+// Workgroup (d, j) adds the G <= MON_FT partials of dictionary index d and column j as k_monitor_final does (lane g holds workgroup
+// g's, a shuffle tree per wave, then the 16 wave results front to back), gathers s_j at the nodes of the extremes, whose ids it
+// reads from the primal row of the same state, and writes the five fields of out[(tag * nvt + j) * 5 ..].  Workgroup (0, 0) also
+// writes the zero rows of the tags that are not monitored.
+__global__ __launch_bounds__(MON_FT) void k_monitor_tan_final(int G, int tab_len, int n, int nvt, MonTanPart part, MonShape sh,
+                                                             const double* __restrict__ s, const double* __restrict__ prim,
+                                                             const uint8_t* __restrict__ slot_of_tag, const int32_t* __restrict__ tag_of_slot,
+                                                             double* __restrict__ out) {
+  __shared__ double s_I0[16], s_I1[16], s_H[16];
+  const int d = blockIdx.x, j = blockIdx.y, t = threadIdx.x, wv = t >> 6, lane = t & 63;
+  int slot = -1;
+  for (int q = 0; q < MON_NS; ++q)
+    if (q < sh.n && sh.col[q] == j) slot = q;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+  if (t < G) {
+    const size_t o = (static_cast<size_t>(d) * nvt + j) * G + t;
+    a1 = part.I1[o]; a2 = part.H[o];
+    if (slot >= 0) a0 = part.I0[(static_cast<size_t>(d) * MON_NS + slot) * G + t];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma clang fp contract(off)
+    a0 += __shfl_down(a0, o, 64);
+    a1 += __shfl_down(a1, o, 64);
+    a2 += __shfl_down(a2, o, 64);
+  }
+  if (lane == 0) { s_I0[wv] = a0; s_I1[wv] = a1; s_H[wv] = a2; }
+  __syncthreads();
+  if (t == 0) {
+#pragma clang fp contract(off)
+    for (int k = 1; k < MON_FT / 64; ++k) { a0 += s_I0[k]; a1 += s_I1[k]; a2 += s_H[k]; }
+    const int tag = tag_of_slot[d];
+    const double* p = prim + static_cast<size_t>(tag) * MON_F;
+    const int imax = static_cast<int>(p[1]), imin = static_cast<int>(p[3]);
+    double* row = out + (static_cast<size_t>(tag) * nvt + j) * MON_TF;
+    row[0] = imax >= 0 && imax < n ? s[static_cast<size_t>(imax) * nvt + j] : 0.0;
+    row[1] = imin >= 0 && imin < n ? s[static_cast<size_t>(imin) * nvt + j] : 0.0;
+    row[2] = a0; row[3] = a1; row[4] = a2;
+  }
+  if (d == 0 && j == 0) {
+    const int per = nvt * MON_TF;
+    for (int k = t; k < tab_len * per; k += MON_FT)
+      if (slot_of_tag[k / per] == MON_NONE) out[k] = 0.0;
+  }
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------------
 
 void monitor_free(hf_ctx* ctx) {
   hf_ctx::Monitor& M = ctx->mon;
   dev_free(&M.slot); dev_free(&M.tags); dev_free(&M.theta); dev_free(&M.part_f); dev_free(&M.part_i); dev_free(&M.rec); dev_free(&M.now);
+  dev_free(&M.tpart); dev_free(&M.trec);
   M = hf_ctx::Monitor();
 }
 
@@ -229,6 +465,87 @@ inline void monitor_record(hf_ctx* ctx) {
   hf_ctx::Monitor& M = ctx->mon;
   monitor_launch(ctx, M.rec + static_cast<size_t>(M.count) * monitor_row(ctx));
   M.count += 1;
+}
+
+// ---- derivative records ---------------------------------------------------------------------------------------
+
+inline size_t montan_row(const hf_ctx* ctx, int nv) { return static_cast<size_t>(ctx->tab_len) * nv * MON_TF; }
+
+// dynamic LDS of k_monitor_tan<NV>: the accumulators of the nd monitored tags, then the slot table
+inline size_t montan_lds(const hf_ctx* ctx, int NV) {
+  return sizeof(double) * 4 * ctx->mon.nd * (2 * NV + MON_NS) + static_cast<size_t>((ctx->tab_len + 15) & ~15);
+}
+
+// The partials of k_monitor_tan, for the widest nv: allocated by hf_set_monitor_tangents(1) or the first hf_monitor_tangent_eval
+int montan_parts(hf_ctx* ctx) {
+  hf_ctx::Monitor& M = ctx->mon;
+  if (M.tpart) return HF_OK;
+  return dev_alloc(ctx, &M.tpart, static_cast<size_t>(M.nd) * (2 * NV_MAX + MON_NS) * M.grid);
+}
+
+// Drop the derivative records (the buffer goes too: its rows belong to one nv)
+void montan_drop(hf_ctx* ctx) {
+  hf_ctx::Monitor& M = ctx->mon;
+  dev_free(&M.trec);
+  M.tcap = 0; M.tcount = 0; M.tnv = 0;
+  M.tindex.clear();
+}
+
+// Room for n_more derivative records of nv columns behind the ones kept, before the caller's first launch (as monitor_room)
+int montan_room(hf_ctx* ctx, int nv, int64_t n_more) {
+  hf_ctx::Monitor& M = ctx->mon;
+  if (!M.on || !M.tan_on) return HF_OK;
+  if (M.tnv != nv) { montan_drop(ctx); M.tnv = nv; }
+  M.tindex.reserve(static_cast<size_t>(M.tcount + n_more));
+  if (M.tcount + n_more <= M.tcap) return HF_OK;
+  const int64_t cap = std::max<int64_t>(M.tcount + n_more, 2 * M.tcap);
+  double* grown = nullptr;
+  HF_TRY(dev_alloc(ctx, &grown, static_cast<size_t>(cap) * montan_row(ctx, nv)));
+  if (M.tcount > 0) {
+    const hipError_t e = copy_sync(ctx, grown, M.trec, sizeof(double) * static_cast<size_t>(M.tcount) * montan_row(ctx, nv), hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) { dev_free(&grown); return fail(ctx, HF_ERR_HIP, "monitor derivative records: copy failed: %s", hipGetErrorString(e)); }
+  }
+  dev_free(&M.trec);
+  M.trec = grown;
+  M.tcap = cap;
+  return HF_OK;
+}
+
+// The launches of one derivative row on the stream: tangents `s` (n x nv interleaved) of the state in ctx->d_u, whose primal row is
+// `prim`, into `out` (tab_len x nv x 5 doubles on the device).  The columns go in one launch where its accumulators fit the LDS
+// of a workgroup, else in groups of the widest power of two that does (a function of nd and nv alone), one launch per group.
+void montan_launch(hf_ctx* ctx, int nv, const double* s, const MonShape& sh, const double* prim, double* out) {
+  hf_ctx::Monitor& M = ctx->mon;
+  const size_t G = static_cast<size_t>(M.grid) * M.nd;
+  MonTanPart P;
+  P.I1 = M.tpart; P.H = M.tpart + G * NV_MAX; P.I0 = M.tpart + 2 * G * NV_MAX;
+  int gw = nv;
+  while (gw > 2 && montan_lds(ctx, gw) > MON_LDS) gw >>= 1;
+  const size_t sm = montan_lds(ctx, gw);
+  for (int j0 = 0; j0 < nv; j0 += gw) {
+#define HF_MT(NV) hipLaunchKernelGGL(k_monitor_tan<NV>, dim3(M.grid), dim3(MON_T), sm, ctx->stream, ctx->ne, M.nchunks, ctx->tab_len, M.nd, nv, \
+                                     j0, ctx->d_elem, ctx->d_zr, ctx->d_u, s, M.slot, M.theta, sh, P)
+    switch (gw) {
+      case 2: HF_MT(2); break;
+      case 4: HF_MT(4); break;
+      case 8: HF_MT(8); break;
+      default: HF_MT(16); break;
+    }
+#undef HF_MT
+  }
+  hipLaunchKernelGGL(k_monitor_tan_final, dim3(M.nd, nv), dim3(MON_FT), 0, ctx->stream, M.grid, ctx->tab_len, ctx->n, nv, P, sh, s, prim, M.slot,
+                     M.tags, out);
+}
+
+// The derivative record of the step whose primal record was taken last (the caller made room with montan_room)
+inline void montan_record(hf_ctx* ctx) {
+  hf_ctx::Monitor& M = ctx->mon;
+  const hf_ctx::Tangent::Shape& S = ctx->tan.sh;
+  MonShape sh{S.d_v, S.ns, S.ncol, {S.col[0], S.col[1], S.col[2], S.col[3]}};
+  montan_launch(ctx, M.tnv, ctx->tanb.u, sh, M.rec + static_cast<size_t>(M.count - 1) * monitor_row(ctx),
+                M.trec + static_cast<size_t>(M.tcount) * montan_row(ctx, M.tnv));
+  M.tindex.push_back(static_cast<int32_t>(M.count - 1));
+  M.tcount += 1;
 }
 
 }  // namespace

@@ -45,7 +45,8 @@ from .heating import HeatingCurve
 from .aniso import CAPACITY_KINDS, DIRECTIONAL_HINT, capacity_scale, check_capacity_names, check_config, refuse_aniso, split_param
 from .kappa_t import material_cv_table, material_table, picard_sweeps, refuse_tables
 from .mesh import Mesh, load_mesh_arrays
-from .monitors import parse_monitors, problem_monitors, refuse_monitors, used_config as monitors_used_config, write_monitors_csv
+from .monitors import (check_sigma, parse_monitors, problem_monitors, refuse_monitors, uncertainty as monitor_uncertainty,
+                       used_config as monitors_used_config, write_monitors_csv, write_uncertainty_csv)
 from .source import amplitudes as source_amplitudes, parse_source, refuse_source
 from .solver import DEFAULT_MAX_IT, DEFAULT_RTOL, HeatProblem
 
@@ -506,7 +507,8 @@ class SimulationSession:
                  "iters": iters[:, j].copy(), "loop_time": loop_time / nv, "startup_time": (t_loop - t_start) / nv,
                  "n_dof": prob.n, "dt": dt, "flux": fluxes[j], "batch": nv} for j in range(nv)]
 
-    def run(self, cfg, stack, watcher_points=None, field_sink=None, read_flux=False, two_sided=False, tangents=None):
+    def run(self, cfg, stack, watcher_points=None, field_sink=None, read_flux=False, two_sided=False, tangents=None,
+            monitor_tangents=False, monitor_sigma=None):
         """One simulation (reference loop run_with_diamond.py:456-504).  Returns a dict with
         ``times``, ``watchers`` {name: array}, ``iters``, timing numbers.  ``read_flux`` adds the
         per-step gradient projection of run_no_diamond.py:543-566 (``flux`` entry of the result).
@@ -519,8 +521,23 @@ class SimulationSession:
         of the heating profile) adds ``tangents`` {param: {watcher: d watcher / d param}} and ``tangent_iters`` (HeatProblem.run_tangent; not with a field sink or the flux projection).
         A ``heating.source`` block (heatflow_amd.source) drives the run by absorbed laser power, the field sink and the flux
         projection included; not with ``tangents`` or ``two_sided``.  A ``monitors`` block (heatflow_amd.monitors) adds
-        ``monitors`` {region: {field: one value per step}} to the result, whichever way the steps are taken."""
+        ``monitors`` {region: {field: one value per step}} to the result, whichever way the steps are taken.
+        ``monitor_tangents`` (with ``tangents`` and a ``monitors`` block) adds ``monitor_tangents``
+        {param: {region: {field: d field / d param per step}}}.  ``monitor_sigma`` = {param: relative one-sigma}, the names the
+        ones ``tangents`` accepts and the values from fit.get_param, implies those tangent columns and the derivatives and adds
+        ``monitor_uncertainty`` {region: {field: sqrt(sum_q (d field / d theta_q sigma_q theta_q)^2) per step}}."""
         t_start = time.time()
+        if monitor_tangents or monitor_sigma is not None:
+            arg = "monitor_sigma" if monitor_sigma is not None else "monitor_tangents"
+            if parse_monitors(cfg) is None:
+                raise ValueError(f"{arg}: the configuration has no monitors block (heatflow_amd.monitors)")
+            sigma = check_sigma(monitor_sigma) if monitor_sigma is not None else {}
+            tangents = list(tangents or ()) + [q for q in sigma if q not in (tangents or ())]
+            if not tangents:
+                raise ValueError("monitor_tangents: no parameter (tangents= names the columns)")
+            if len(tangents) > 16:
+                raise ValueError(f"{arg}: {len(tangents)} tangent columns (at most 16 per run)")
+            monitor_tangents = True
         spec = parse_source(cfg)
         if spec is not None and tangents:
             refuse_source(cfg, "tangents=")
@@ -564,7 +581,7 @@ class SimulationSession:
             prob._flux_ready = True
         print("Beginning loop...")
         t_loop = time.time()
-        tangent_out = None
+        tangent_out, extra = None, {}
         if tangents:
             if field_sink is not None or flux is not None:
                 raise ValueError("tangents: not combined with a field sink or the read-flux projection")
@@ -606,11 +623,20 @@ class SimulationSession:
             times, samples, tsamp, iters, titers = prob.run_tangent(num_steps, nodes, conductivity=cond, boundary=bnd,
                                                                     time_varying=varying, **({"shape": shp} if shp else {}),
                                                                     **({"capacity": [cap.get(j, []) for j in range(len(params))]}
-                                                                       if cap else {}))
+                                                                       if cap else {}),
+                                                                    **({"monitor_tangents": True} if monitor_tangents else {}))
             for j, f in cscale.items():
                 if f != 1.0:
                     tsamp[:, j] *= f
             tangent_out = {p: {nm: tsamp[:, j, k] for k, nm in enumerate(names)} for j, p in enumerate(params)}
+            if monitor_tangents:
+                dhist = prob.monitor_tangent_history(scale=[cscale.get(j, 1.0) for j in range(len(params))])
+                extra = {"monitor_tangents": {p: {region: {field: d[:, j] for field, d in f.items()} for region, f in dhist.items()}
+                                              for j, p in enumerate(params)}}
+                if monitor_sigma is not None:
+                    from .fit import get_param
+                    extra["monitor_uncertainty"] = monitor_uncertainty(extra["monitor_tangents"],
+                                                                       {q: s * get_param(cfg, q) for q, s in sigma.items()})
         elif field_sink is None and flux is None:
             times, samples, iters = prob.run(num_steps, watcher_nodes=nodes, time_varying=varying,
                                              **({"source_amplitude": amp} if amp is not None else {}))
@@ -643,6 +669,7 @@ class SimulationSession:
             "n_dof": prob.n, "dt": dt, "flux": flux,
             **({"tangents": tangent_out, "tangent_iters": titers} if tangent_out is not None else {}),
             **({"monitors": prob.monitor_history()} if mon else {}),
+            **extra,
         }
 
 
@@ -767,7 +794,7 @@ class _FieldWriter:
 def run_simulation_impl(kind, cfg, mesh_folder, rebuild_mesh=False, visualize_mesh=False, output_folder=None,
                         watcher_points=None, write_xdmf=True, suppress_print=False, *, device_id=0, backend=None,
                         session=None, rtol=DEFAULT_RTOL, max_it=DEFAULT_MAX_IT, read_flux=True, precond=None,
-                        two_sided=False, tangents=None):
+                        two_sided=False, tangents=None, monitor_tangents=False, monitor_sigma=None):
     with suppress_output(suppress_print):
         program_start = time.time()
         check_config(cfg)   # k_aniso blocks, and none of them next to a table key, before any mesh or session is made
@@ -795,7 +822,9 @@ def run_simulation_impl(kind, cfg, mesh_folder, rebuild_mesh=False, visualize_me
             if sink is not None:
                 sink(0.0, np.full(len(session.coords), float(cfg["heating"]["ic_temp"])))
             result = session.run(cfg, stack, watcher_points, field_sink=sink, read_flux=read_flux and kind == "no_diamond",
-                                 two_sided=two_sided, tangents=tangents)
+                                 two_sided=two_sided, tangents=tangents,
+                                 **({"monitor_tangents": monitor_tangents} if monitor_tangents else {}),
+                                 **({"monitor_sigma": monitor_sigma} if monitor_sigma is not None else {}))
         finally:
             if sink is not None:
                 sink.close()
@@ -807,6 +836,9 @@ def run_simulation_impl(kind, cfg, mesh_folder, rebuild_mesh=False, visualize_me
                               result["watchers"])
         if result.get("monitors") is not None:
             write_monitors_csv(os.path.join(save_folder, "monitors.csv"), result["times"], result["monitors"])
+        if result.get("monitor_uncertainty") is not None:
+            write_uncertainty_csv(os.path.join(save_folder, "monitor_uncertainty.csv"), result["times"], result["monitors"],
+                                  result["monitor_uncertainty"])
         if result.get("flux") is not None:
             result["flux"].write(save_folder)
             print(f"Saved raw gradient data at r=0 nodes to {os.path.join(save_folder, 'radial_gradient_raw.csv')}")
@@ -869,11 +901,25 @@ def cli(kind, argv=None):
     p.add_argument("--write-xdmf", action="store_true")
     p.add_argument("--suppress-print", action="store_true")
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--monitor-sigma", nargs="+", metavar="NAME=REL",
+                   help="relative one-sigma of input parameters (the names tangents accept, e.g. p_sample.rho_c=0.15 fwhm=0.1): "
+                        "writes monitor_uncertainty.csv, the first-order one-sigma band of every monitor field (needs a monitors block)")
     a = p.parse_args(argv)
+    sigma = None
+    if a.monitor_sigma:
+        sigma = {}
+        for item in a.monitor_sigma:
+            name, eq, rel = item.rpartition("=")
+            try:
+                sigma[name] = float(rel)
+            except ValueError:
+                eq = ""
+            if not eq or not name:
+                p.error(f"--monitor-sigma: NAME=REL expected, got {item!r}")
     with open(a.config) as f:
         cfg = yaml.safe_load(f)
     run_simulation_impl(kind, cfg, a.mesh_folder, a.rebuild_mesh, a.visualize_mesh, a.output_folder, a.watcher_points,
-                        a.write_xdmf, a.suppress_print, device_id=a.device)
+                        a.write_xdmf, a.suppress_print, device_id=a.device, **({"monitor_sigma": sigma} if sigma else {}))
     return 0
 
 

@@ -38,6 +38,7 @@ EXPORTS = [
     "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
     "hf_set_source", "hf_get_source", "hf_set_source_amplitudes",
     "hf_set_monitors", "hf_monitor_now", "hf_monitor_count", "hf_get_monitors", "hf_monitor_clear",
+    "hf_set_monitor_tangents", "hf_monitor_tangent_count", "hf_get_monitor_tangents", "hf_monitor_tangent_eval",
     "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_set_shape", "hf_tangent_set_capacity", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
     "hf_set_value_lists", "hf_get_value_lists", "hf_get_projection", "hf_get_flux_system",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
@@ -148,6 +149,10 @@ def load_library():
         "hf_monitor_count": [vp, pi],
         "hf_get_monitors": [vp, i32, i32, pd],
         "hf_monitor_clear": [vp],
+        "hf_set_monitor_tangents": [vp, i32],
+        "hf_monitor_tangent_count": [vp, pi, pi],
+        "hf_get_monitor_tangents": [vp, i32, i32, pd, pi],
+        "hf_monitor_tangent_eval": [vp, i32, pd, i32, pi, pd, pd],
         "hf_tangent_setup": [vp, i32, pi],
         "hf_tangent_setup_dir": [vp, i32, pi, pi, pi],
         "hf_tangent_set_shape": [vp, i32, pd],
@@ -802,6 +807,50 @@ class HeatflowHIP:
     def clear_monitor_records(self):
         """Drop the records; the table of monitored tags stays."""
         self._check(self._lib.hf_monitor_clear(self._ctx))
+
+    # -- derivatives of the monitor sums along the tangent columns (DESIGN.md 3.18) --------------------------------------------
+    MONITOR_TANGENT_FIELDS = ("dT_max", "dT_min", "dI0", "dI1", "dH")
+
+    def set_monitor_tangents(self, on):
+        """Switch the derivative records of run_tangent on or off (monitors must be set to switch them on)."""
+        self._check(self._lib.hf_set_monitor_tangents(self._ctx, 1 if on else 0))
+
+    def monitor_tangent_count(self):
+        """(derivative records kept, nv of their columns)."""
+        c, nv = C.c_int32(), C.c_int32()
+        self._check(self._lib.hf_monitor_tangent_count(self._ctx, C.byref(c), C.byref(nv)))
+        return int(c.value), int(nv.value)
+
+    def get_monitor_tangents(self, first=0, count=None):
+        """Derivative records ``first`` .. ``first + count - 1`` (default: all from ``first``) as (array [K, tab_len, nv, 5] with the
+        fields MONITOR_TANGENT_FIELDS, index [K] of the primal record of get_monitors each one belongs to)."""
+        first = int(first)
+        kept, nv = self.monitor_tangent_count()
+        count = kept - first if count is None else int(count)
+        out = np.empty((max(count, 0), self.tab_len, max(nv, 0), 5), dtype=np.float64)
+        index = np.empty(max(count, 0), dtype=np.int32)
+        self._check(self._lib.hf_get_monitor_tangents(self._ctx, first, count, _pd(out), _pi(index)))
+        return out, index
+
+    def monitor_tangent_eval(self, s, shape=None):
+        """The derivative row [tab_len, nv, 5] of the current state for the tangent fields ``s`` [n, nv] (nv = 2, 4, 8 or 16) and
+        ``shape`` = {column: nodal z-velocity} (at most 4): the kernels of the records on fields of the caller's; nothing is
+        recorded, and the monitors of the current state are evaluated on the way."""
+        s = np.ascontiguousarray(s, dtype=np.float64)
+        if s.ndim != 2 or s.shape[0] != self.n:
+            raise ValueError(f"monitor_tangent_eval: s must be [n = {self.n}, nv] (got {s.shape})")
+        shape = dict(shape or {})
+        cols = np.array(list(shape), dtype=np.int32)
+        vz = np.zeros((self.n, len(cols)), dtype=np.float64)
+        for q, j in enumerate(shape):
+            v = np.asarray(shape[j], dtype=np.float64).ravel()
+            if v.size != self.n:
+                raise ValueError(f"monitor_tangent_eval: shape column {j}: {self.n} velocities expected (got {v.size})")
+            vz[:, q] = v
+        out = np.empty((self.tab_len, s.shape[1], 5), dtype=np.float64)
+        self._check(self._lib.hf_monitor_tangent_eval(self._ctx, s.shape[1], _pd(s), len(cols), _pi(cols) if len(cols) else None,
+                                                      _pd(vz) if len(cols) else None, _pd(out)))
+        return out
 
     # -- inspection ----------------------------------------------------------------------
     def get_csr(self, values=True):

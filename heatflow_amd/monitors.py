@@ -16,6 +16,10 @@ combines the rows of a region's tags, in ascending tag order, into
     energy                  2 pi sum_t rho_c_t (I1_t - T_ref I0_t), the heat stored above T_ref = heating.ic_temp - left out when a
                             tag of the region carries a capacity table (the constant rho cv is then not the run's)
 
+In tangent runs the GPU can also leave the derivatives of the sums along every tangent column (hf_set_monitor_tangents, DESIGN.md
+3.18); :func:`combine_tangents` applies the chain rule per region and :func:`uncertainty` turns stated input uncertainties into
+one-sigma bands.
+
 It parses and validates the block and does the host arithmetic; it touches no GPU.
 """
 from __future__ import annotations
@@ -190,6 +194,70 @@ def combine(records, regions, coords, rho_c=None, T_ref=None, tabled=()):
     return out
 
 
+TANGENT_FIELDS = ("T_max", "T_min", "volume", "T_mean", "hot_volume", "hot_fraction", "energy")
+D_TMAX, D_TMIN, D_I0, D_I1, D_H = range(5)                        # fields of a derivative row (hf_get_monitor_tangents)
+
+
+def combine_tangents(records, drecords, regions, rho_c=None, T_ref=None, tabled=(), capacity_columns=None, scale=None):
+    """The chain rule of :func:`combine`: primal records [K, tab_len, 7] and the derivative records of the same
+    states [K, tab_len, n_par, 5] (HeatflowHIP.get_monitor_tangents, fields dT_max, dT_min, dI0, dI1, dH) -> {region: {field:
+    array (K, n_par)}} for T_max, T_min, volume, T_mean, hot_volume, hot_fraction and energy, the sums over a region's tags in
+    ascending tag order:
+
+        d volume = 2 pi sum dI0                       d T_mean = (sum dI1 - T_mean sum dI0) / sum I0
+        d hot_volume = 2 pi sum dH                    d hot_fraction = (sum dH - hot_fraction sum dI0) / sum I0
+        d T_max = dT_max of the tag that holds the region's peak (combine's tie rule: the lowest tag), d T_min likewise
+        d energy = 2 pi sum_t rho_c_t (dI1_t - T_ref dI0_t), plus 2 pi (I1_t - T_ref I0_t) in the column that carries the
+                   rho_c of tag t (``capacity_columns`` = {cell tag: column})
+
+    ``scale`` (n_par values, default ones) multiplies whole columns, as the watcher tangents of ``.cv`` and ``.rho`` are scaled.
+    ``hot_*`` and ``energy`` are left out wherever :func:`combine` leaves them out."""
+    rec = np.asarray(records, dtype=np.float64)
+    drec = np.asarray(drecords, dtype=np.float64)
+    if rec.ndim == 2:
+        rec = rec[None]
+    if drec.ndim == 3:
+        drec = drec[None]
+    if rec.shape[0] != drec.shape[0] or rec.shape[1] != drec.shape[1]:
+        raise ValueError(f"combine_tangents: records {rec.shape} and drecords {drec.shape} do not belong together")
+    K, _, n_par, _ = drec.shape
+    scale = np.ones(n_par) if scale is None else np.asarray(scale, dtype=np.float64).reshape(n_par)
+    tabled = {int(t) for t in tabled}
+    cap = {int(t): int(j) for t, j in (capacity_columns or {}).items()}
+    two_pi = 2.0 * math.pi
+    out = {}
+    for region, r in regions.items():
+        tags = sorted(int(t) for t in r["tags"])
+        tmax, tmin = np.full(K, -np.inf), np.full(K, np.inf)
+        dmax, dmin = np.zeros((K, n_par)), np.zeros((K, n_par))
+        s0, s1, sh = np.zeros(K), np.zeros(K), np.zeros(K)
+        d0, d1, dh, de = (np.zeros((K, n_par)) for _ in range(4))
+        for t in tags:
+            row, drow = rec[:, t, :], drec[:, t, :, :]
+            up = row[:, F_TMAX] > tmax
+            tmax = np.where(up, row[:, F_TMAX], tmax)
+            dmax = np.where(up[:, None], drow[:, :, D_TMAX], dmax)
+            dn = row[:, F_TMIN] < tmin
+            tmin = np.where(dn, row[:, F_TMIN], tmin)
+            dmin = np.where(dn[:, None], drow[:, :, D_TMIN], dmin)
+            s0, s1, sh = s0 + row[:, F_I0], s1 + row[:, F_I1], sh + row[:, F_H]
+            d0, d1, dh = d0 + drow[:, :, D_I0], d1 + drow[:, :, D_I1], dh + drow[:, :, D_H]
+            if rho_c is not None and T_ref is not None and t in rho_c:
+                de = de + float(rho_c[t]) * (drow[:, :, D_I1] - float(T_ref) * drow[:, :, D_I0])
+                if t in cap and 0 <= cap[t] < n_par:
+                    de[:, cap[t]] = de[:, cap[t]] + (row[:, F_I1] - float(T_ref) * row[:, F_I0])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mean, frac = (s1 / s0)[:, None], (sh / s0)[:, None]
+            f = {"T_max": dmax, "T_min": dmin, "volume": two_pi * d0, "T_mean": (d1 - mean * d0) / s0[:, None]}
+            if r["above"] is not None:
+                f["hot_volume"] = two_pi * dh
+                f["hot_fraction"] = (dh - frac * d0) / s0[:, None]
+        if rho_c is not None and T_ref is not None and all(t in rho_c for t in tags) and not (tabled & set(tags)):
+            f["energy"] = two_pi * de
+        out[region] = {k: v * scale[None, :] for k, v in f.items()}
+    return out
+
+
 def csv_columns(history):
     """The columns of monitors.csv after ``time``: ``<region>.<field>`` in the regions' order, fields in FIELDS' order."""
     return [(region, field) for region, f in history.items() for field in FIELDS if field in f]
@@ -203,3 +271,46 @@ def write_monitors_csv(path, times, history):
         w.writerow(["time"] + [f"{region}.{field}" for region, field in cols])
         for k, t in enumerate(times):
             w.writerow([repr(float(t))] + [repr(float(history[region][field][k])) for region, field in cols])
+
+
+def check_sigma(monitor_sigma):
+    """{parameter: relative one-sigma} of the drivers' ``monitor_sigma=`` as floats; ValueError naming the argument for anything
+    but a mapping of names to positive finite numbers."""
+    if not isinstance(monitor_sigma, dict) or not monitor_sigma:
+        raise ValueError(f"monitor_sigma must be a mapping {{parameter: relative one-sigma}}, got {monitor_sigma!r}")
+    out = {}
+    for name, v in monitor_sigma.items():
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"monitor_sigma: {name}: a number is expected, got {v!r}") from None
+        if not math.isfinite(f) or f <= 0.0:
+            raise ValueError(f"monitor_sigma: {name}: the relative one-sigma must be positive and finite, got {v!r}")
+        out[str(name)] = f
+    return out
+
+
+def uncertainty(derivatives, sigma_abs):
+    """First-order one-sigma bands: ``derivatives`` = {param: {region: {field: d field / d param per step}}} and ``sigma_abs`` =
+    {param: sigma_q theta_q} -> {region: {field: sqrt(sum_q (d field / d theta_q sigma_q theta_q)^2)}}, the parameters taken as
+    independent."""
+    out = {}
+    for q, s in sigma_abs.items():
+        for region, fields in derivatives[q].items():
+            for field, d in fields.items():
+                acc = out.setdefault(region, {})
+                term = (np.asarray(d, dtype=np.float64) * float(s)) ** 2
+                acc[field] = term if field not in acc else acc[field] + term
+    return {region: {field: np.sqrt(v) for field, v in fields.items()} for region, fields in out.items()}
+
+
+def write_uncertainty_csv(path, times, history, bands):
+    """``<out>/monitor_uncertainty.csv``: ``time, <region>.<field>, <region>.<field>.sigma, ...`` for every field with a band, the
+    regions in the monitors' order and the fields in FIELDS' order, one row per step."""
+    cols = [(region, field) for region, field in csv_columns(history) if field in bands.get(region, {})]
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["time"] + [c for region, field in cols for c in (f"{region}.{field}", f"{region}.{field}.sigma")])
+        for k, t in enumerate(times):
+            w.writerow([repr(float(t))] + [repr(float(v)) for region, field in cols
+                                           for v in (history[region][field][k], bands[region][field][k])])

@@ -18,7 +18,7 @@ import numpy as np
 
 from .bc import gather_bc_values, gather_plan, merge_bcs
 from .hip_backend import ASM_ROW_GATHER, PC_AMG, PC_JACOBI, HeatflowHIP, time_scheme_code
-from .monitors import check_regions, combine as combine_monitors, tag_thresholds
+from .monitors import check_regions, combine as combine_monitors, combine_tangents, tag_thresholds
 
 # Default PCG tolerance: at rtol = 1e-10 the temperature field agrees with a sparse
 # direct solve of the same system to ~3e-6 K (measured on the stock and the 1M-DOF
@@ -244,7 +244,7 @@ class HeatProblem:
         return times, samples, iters
 
     def run_tangent(self, num_steps, watcher_nodes, conductivity=(), boundary=None, time_varying=None, first_step=0, shape=None,
-                    capacity=()):
+                    capacity=(), monitor_tangents=False):
         """:meth:`run` plus the derivatives of the watcher curves with respect to parameters theta_j (hf_run_tangent,
         DESIGN.md 3.7).  Column j of ``conductivity`` = the cell tags whose conductivity theta_j is (they move together).  An
         entry may also be a pair ``(tag, "k" | "r" | "z")``: the tag's kappa (both directions of an anisotropic
@@ -261,8 +261,13 @@ class HeatProblem:
         most 4 columns).  Without ``shape`` the backend sees the calls of before.  Column j of ``capacity`` (positional like
         ``conductivity``; an empty list = none) = the cell tags whose rho_c = rho * cv in J/m^3/K theta_j is (DESIGN.md 3.16,
         hf_tangent_set_capacity); a column may carry conductivities, a velocity and a capacity at once, a tag may be in one
-        capacity column only, and without ``capacity`` the backend sees the calls of before.  Returns (times, samples, tangent samples
-        (n_steps, n_par, n_s), iters, tangent iters (n_steps, n_par))."""
+        capacity column only, and without ``capacity`` the backend sees the calls of before.  ``monitor_tangents`` (DESIGN.md
+        3.18; needs ``monitors=``) switches the derivative records of the region monitors on for this run:
+        :meth:`monitor_tangent_history` then gives the derivative of every monitor field along every column, per step; the
+        default makes no new backend call.  Returns (times, samples, tangent samples (n_steps, n_par, n_s), iters, tangent iters
+        (n_steps, n_par))."""
+        if monitor_tangents and not self.monitors:
+            raise ValueError("run_tangent: monitor_tangents needs monitors (HeatProblem(..., monitors=))")
         conductivity = [list(c) for c in conductivity]
         boundary = {int(j): dict(m) for j, m in (boundary or {}).items()}
         shape = {int(j): np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for j, v in (shape or {}).items()}
@@ -331,10 +336,33 @@ class HeatProblem:
                         continue
                     te = t if (time_varying is None or any(bc is b for b in time_varying)) else 0.0
                     h_all[k, sel, j] = _eval_on_dofs(deriv, bc.dof_coords, te)[src]
-        samples, iters, tsamples, titers = self.backend.run_tangent(g_all, h_all, self.rtol, self.atol, self.max_it,
-                                                                    watcher_nodes)
+        if monitor_tangents:
+            first = self.backend.monitor_tangent_count()[0]      # (a set-up with another nv has dropped the records of before)
+            self.backend.set_monitor_tangents(True)
+        try:
+            samples, iters, tsamples, titers = self.backend.run_tangent(g_all, h_all, self.rtol, self.atol, self.max_it,
+                                                                        watcher_nodes)
+        finally:
+            if monitor_tangents:
+                self.backend.set_monitor_tangents(False)
+        if monitor_tangents:     # this run's derivative records, its columns and the tags whose rho_c they carry (energy's explicit term)
+            self._mt_run = (first, num_steps, n_par, dict(cap_col))
         self.iters.extend(int(i) for i in iters)
         return times, samples, tsamples[:, :n_par], iters, titers[:, :n_par]
+
+    def monitor_tangent_history(self, scale=None):
+        """{region: {field: array (n_steps, n_par)}}: the derivatives of the monitor fields T_max, T_min, volume, T_mean,
+        hot_volume, hot_fraction and energy along the columns of the last :meth:`run_tangent` with ``monitor_tangents=True``, one
+        row per step (heatflow_amd.monitors.combine_tangents; ``scale`` multiplies whole columns)."""
+        if not self.monitors:
+            raise ValueError("monitors: the problem has no monitors (HeatProblem(..., monitors=))")
+        if getattr(self, "_mt_run", None) is None:
+            raise ValueError("monitor_tangents: no tangent run with monitor_tangents=True yet")
+        first, count, n_par, cap_col = self._mt_run
+        drec, index = self.backend.get_monitor_tangents(first, count)
+        rec = self.backend.get_monitors()[np.asarray(index, dtype=np.int64)]
+        return combine_tangents(rec, drec[:, :, :n_par], self.monitors, rho_c=self._rho_c, T_ref=self.monitor_T_ref,
+                                tabled=self.rhoc_tables, capacity_columns=cap_col, scale=scale)
 
     def tangent(self, j):
         """The current tangent field of column j (n values)."""

@@ -409,6 +409,32 @@ int hf_monitor_count(hf_ctx* ctx, int32_t* n_records);
 int hf_get_monitors(hf_ctx* ctx, int32_t first, int32_t count, double* out);
 int hf_monitor_clear(hf_ctx* ctx);
 
+/* Derivatives of the monitor sums in tangent runs: while monitors are set and the switch is on, every step of
+ * hf_run_tangent that returns HF_OK leaves, after its tangent stage, one derivative record next to the primal record of the same
+ * state: per cell tag t and tangent column j the five numbers dT_max = s_j[node_max], dT_min = s_j[node_min] (the nodes of the
+ * primal record), dI0, dI1, dH, with s_j the column's tangent field.  dI0 is zero except in a shape column
+ * (hf_tangent_set_shape), whose nodal z-velocity moves the triangles' areas.  k_monitor_tan<nv> and k_monitor_tan_final form
+ * them as k_monitor forms the sums: no atomics, no host synchronisation, the same bits from run to run.
+ * hf_set_monitor_tangents   the switch (off after hf_set_monitors and hf_set_mesh, which also drop the derivative records).
+ * hf_monitor_tangent_count  the derivative records kept and the nv of their columns (0 while none were taken).
+ * hf_get_monitor_tangents   records first .. first + count - 1: out[(((k - first) * rows + t) * nv + j) * 5 + f], f = dT_max, dT_min,
+ *        dI0, dI1, dH, rows = the mesh's largest cell tag + 1; rows of tags that are not monitored and padded columns are exact
+ *        zeros.  record_index[k - first] (may be NULL) = the index of the primal record (hf_get_monitors) that derivative record k
+ *        belongs to: primal records are also taken by hf_run and hf_step, so the two counts differ.
+ * hf_monitor_tangent_eval   the kernels' own door: uploads s (n x nv interleaved, nv = 2, 4, 8 or 16) and n_shape <= 4 nodal
+ *        velocities vz (n x n_shape interleaved, slot q belonging to column shape_col[q]), evaluates the monitors of the current
+ *        state and returns the derivative row out[(t * nv + j) * 5 + f].  It records nothing and needs neither a tangent set-up
+ *        nor an assembled operator.
+ * hf_monitor_clear drops the derivative records too; a tangent set-up with another nv drops them (their rows have nv columns).
+ * HF_ERR_STATE: before hf_set_mesh; while a batch is open; hf_set_monitor_tangents(1), hf_get_monitor_tangents and
+ *        hf_monitor_tangent_eval while no monitors are set.
+ * HF_ERR_ARG: a range outside the records kept, nv not in {2, 4, 8, 16}, n_shape outside 0..4, a shape_col outside [0, nv) or
+ *        listed twice, null pointers. */
+int hf_set_monitor_tangents(hf_ctx* ctx, int32_t on);
+int hf_monitor_tangent_count(hf_ctx* ctx, int32_t* n_records, int32_t* nv);
+int hf_get_monitor_tangents(hf_ctx* ctx, int32_t first, int32_t count, double* out, int32_t* record_index /* may be NULL */);
+int hf_monitor_tangent_eval(hf_ctx* ctx, int32_t nv, const double* s, int32_t n_shape, const int32_t* shape_col, const double* vz, double* out);
+
 /* Tangent runs: the exact derivatives s_j = du/dtheta_j of the time loop with respect to up to 16 parameters, advanced next to
  * the primal.  A column's parameter scales the conductivity of the cell tags mapped to it (K_j = the sum of
  * their unit-conductivity r-weighted stiffness), enters the Dirichlet values through h_j = dg/dtheta_j, or both.  After every
