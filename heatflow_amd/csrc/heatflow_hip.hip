@@ -81,7 +81,19 @@ void load_free(hf_ctx* ctx) {
   ctx->have_load = false;
 }
 
+// hf_source_derivatives' state and the source columns of the tangent set-up, which need it
+void source_diff_free(hf_ctx* ctx) {
+  hf_ctx::Source& S = ctx->src;
+  dev_free(&S.Gf); dev_free(&S.Gd); dev_free(&S.rows);
+  S.nrows = 0;
+  S.diff = false;
+  hf_ctx::Tangent& T = ctx->tan;
+  dev_free(&T.scoef);
+  T.ssteps = T.snext = 0; T.scur = -1; T.smask = 0;
+}
+
 void source_free(hf_ctx* ctx) {
+  source_diff_free(ctx);
   dev_free(&ctx->src.F1); dev_free(&ctx->src.sum); dev_free(&ctx->src.absorb);
   ctx->src = hf_ctx::Source();
 }
@@ -101,7 +113,7 @@ int source_steps_ok(hf_ctx* ctx, int64_t n_steps, const char* call) {
 void tangent_free(hf_ctx* ctx) {
   free_batch_state(ctx->tanb);
   dev_free(&ctx->tan.col); dev_free(&ctx->tan.dir); dev_free(&ctx->tan.F);
-  dev_free(&ctx->tan.sh.d_v); dev_free(&ctx->tan.ccol); dev_free(&ctx->tan.un); dev_free(&ctx->tan.um1);
+  dev_free(&ctx->tan.sh.d_v); dev_free(&ctx->tan.ccol); dev_free(&ctx->tan.un); dev_free(&ctx->tan.um1); dev_free(&ctx->tan.scoef);
   ctx->tan = hf_ctx::Tangent();
 }
 
@@ -573,6 +585,7 @@ int tangent_reset(hf_ctx* ctx) {
   for (bool& u_ : T.pused) u_ = false;
   T.pnext = 0; T.ppending = -1;
   T.pred_iters = 0;
+  ctx->tan.scur = -1;   // and so did the step whose source coefficients hf_tangent_load uses; the table and its position stay
   ctx->tan.wmode = 0;   // the states kept for the shape and capacity columns' loads belonged to the old trajectory; the velocities and the capacity table stay
   return HF_OK;
 }
@@ -690,10 +703,26 @@ int tangent_load(hf_ctx* ctx) {
   }
   if (ctx->tan.sh.ncol > 0) {
     switch (ctx->tan.sh.ns) {
-      case 1: return tangent_load_shape<1>(ctx, RG_SHAPE1);
-      case 2: return tangent_load_shape<2>(ctx, RG_SHAPE2);
-      default: return tangent_load_shape<4>(ctx, RG_SHAPE4);
+      case 1: HF_TRY(tangent_load_shape<1>(ctx, RG_SHAPE1)); break;
+      case 2: HF_TRY(tangent_load_shape<2>(ctx, RG_SHAPE2)); break;
+      default: HF_TRY(tangent_load_shape<4>(ctx, RG_SHAPE4)); break;
     }
+  }
+  if (ctx->tan.smask != 0 && ctx->tan.scur >= 0 && ctx->src.diff && ctx->src.nrows > 0) {   // source columns: c0 F1 + c1 G_f + c2 G_d on the source's rows
+    const hf_ctx::Tangent& C = ctx->tan;
+    const hf_ctx::Source& S = ctx->src;
+    const double* coef = C.scoef + static_cast<size_t>(C.scur) * C.nv * 3;
+    const int blocks = static_cast<int>((static_cast<int64_t>(S.nrows) * C.nv + 255) / 256);
+#define HF_TLS(NV) hipLaunchKernelGGL(kb_source_columns<NV>, dim3(blocks), dim3(256), 0, ctx->stream, S.nrows, S.rows, C.smask, coef, \
+                                      S.F1, S.Gf, S.Gd, C.F)
+    switch (C.nv) {
+      case 2: HF_TLS(2); break;
+      case 4: HF_TLS(4); break;
+      case 8: HF_TLS(8); break;
+      default: HF_TLS(16); break;
+    }
+#undef HF_TLS
+    HF_HIP(hipGetLastError());
   }
   return HF_OK;
 }
@@ -1508,7 +1537,7 @@ int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
   if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: %s tables are set (tangents of the nonlinear loop are not supported)", kt_kind(ctx));
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a batch is open");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a load is set (tangents of pre-heated runs are not supported)");
-  if (ctx->src.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a source is set (hf_set_source; tangents of sourced runs are not supported)");
+  if (ctx->src.on && !ctx->src.diff) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a source is set (hf_set_source; tangents of sourced runs are not supported)");
   if (n_par < 1 || n_par > NV_MAX) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: 1..%d parameters (got %d)", NV_MAX, n_par);
   if (!tag_col) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tag_col is null");
   for (int t = 0; t < ctx->tab_len; ++t) {
@@ -1549,7 +1578,7 @@ int hf_tangent_setup_dir(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col_k, c
   if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: %s tables are set (tangents of the nonlinear loop are not supported)", kt_kind(ctx));
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a batch is open");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a load is set (tangents of pre-heated runs are not supported)");
-  if (ctx->src.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a source is set (hf_set_source; tangents of sourced runs are not supported)");
+  if (ctx->src.on && !ctx->src.diff) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a source is set (hf_set_source; tangents of sourced runs are not supported)");
   if (n_par < 1 || n_par > NV_MAX) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: 1..%d parameters (got %d)", NV_MAX, n_par);
   if (!tag_col_k && !tag_col_r && !tag_col_z) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: tag_col_k, tag_col_r and tag_col_z are all null");
   const int32_t* tabs[3] = {tag_col_k, tag_col_r, tag_col_z};
@@ -1699,8 +1728,10 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a batch is open");
   if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: %s tables are set (tangents of the nonlinear loop are not supported)", kt_kind(ctx));
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a load is set (tangents of pre-heated runs are not supported)");
-  if (ctx->src.on) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a source is set (hf_set_source; tangents of sourced runs are not supported)");
+  if (ctx->src.on && !ctx->src.diff) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a source is set (hf_set_source; tangents of sourced runs are not supported)");
   if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_run_tangent before hf_tangent_setup");
+  if (ctx->src.on && ctx->tan.sh.ncol > 0)
+    return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a source is set and a column has a shape part (hf_set_source, hf_tangent_set_shape; the source's load depends on the node positions, and that term is not formed)");
   if (ctx->tan.steady_state)
     return fail(ctx, HF_ERR_STATE, "hf_run_tangent: the state comes from hf_steady_solve and depends on the conductivities (tangents start at zero): hf_set_state first");
   if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_run_tangent before hf_assemble");
@@ -1709,6 +1740,10 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
   if (ns < 0 || (ns > 0 && (!nodes || !samples || !tangent_samples))) return fail(ctx, HF_ERR_ARG, "hf_run_tangent: bad sample arguments");
   for (int32_t q = 0; q < ns; ++q)
     if (nodes[q] < 0 || nodes[q] >= ctx->n) return fail(ctx, HF_ERR_ARG, "hf_run_tangent: node %d outside [0,%d)", nodes[q], ctx->n);
+  HF_TRY(source_steps_ok(ctx, n_steps, "hf_run_tangent"));
+  if (ctx->tan.ssteps > 0 && ctx->tan.snext + static_cast<int64_t>(n_steps) > ctx->tan.ssteps)
+    return fail(ctx, HF_ERR_STATE, "hf_run_tangent: the source columns have %d rows left for %d steps (hf_tangent_set_source)",
+                ctx->tan.ssteps - ctx->tan.snext, n_steps);
   HF_HIP(hipSetDevice(ctx->dev));
   hf_ctx::Batch& T = ctx->tanb;
   const int nv = T.nv;
@@ -1754,6 +1789,7 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
                          t_sall.p + static_cast<size_t>(s) * ns);
     if (ctx->mon.on) monitor_record(ctx);
     // the tangent stage: F = -K_j u^{n+1}, then one batched step of the columns with that load and boundary values h^{n+1}
+    if (ctx->tan.ssteps > 0) ctx->tan.scur = ctx->tan.snext++;   // the source columns' coefficients of this step
     HF_TRY(tangent_load(ctx));
     const double* hs = ctx->nbc == 0 ? nullptr : t_hall.p + (h_all ? hstep * s : 0);
     std::swap(ctx->batch, ctx->tanb);
@@ -2102,8 +2138,94 @@ int hf_set_source(hf_ctx* ctx, int32_t n_tags, const int32_t* tags, double fwhm,
   ctx->last_ms = ms;
   S.amp.clear();
   S.next = 0;
+  S.fwhm = fwhm; S.z0 = z0; S.depth = depth;
   S.on = true;
   return HF_OK;
+}
+
+int hf_source_derivatives(hf_ctx* ctx, int32_t enable) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->src.on) return fail(ctx, HF_ERR_STATE, "hf_source_derivatives: no source set (hf_set_source first)");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_source_derivatives: a batch is open");
+  HF_HIP(hipSetDevice(ctx->dev));
+  source_diff_free(ctx);
+  if (!enable) return HF_OK;
+  hf_ctx::Source& S = ctx->src;
+  const size_t n = static_cast<size_t>(ctx->n);
+  DevTemp<int32_t> t_has;
+  HF_TRY(dev_alloc(ctx, &S.Gf, n));
+  HF_TRY(dev_alloc(ctx, &S.Gd, n));
+  HF_TRY(dev_alloc(ctx, &t_has.p, n));
+  // k_source_load's LDS footprint with s_f and s_d where it stages s; persistent workgroups from one occupancy query per mesh
+  const int capd = ctx->rg_max_dict;
+  const size_t sm = static_cast<size_t>(capd) * 16 + 2 * static_cast<size_t>(capd + (capd & 1)) * 8 + (RBA + 4) * 4 +
+                    (static_cast<size_t>((ctx->max_blk_nnz + 1) & ~1) / 8 + 3) * 16;
+  int& grid = ctx->rg_grid[RG_SOURCE_D];
+  if (grid == 0) {
+    const void* fn = reinterpret_cast<const void*>(&k_source_load_d);
+    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
+    int per_cu = 0, ncu = 0;
+    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
+    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
+    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+  }
+  const double c_r = 4.0 * M_LN2 / (S.fwhm * S.fwhm), inv_depth = std::isinf(S.depth) ? 0.0 : 1.0 / S.depth;
+  HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  hipLaunchKernelGGL(k_source_load_d, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr,
+                     reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
+                     ctx->d_rowptr, S.absorb, c_r, S.z0, inv_depth, S.fwhm, S.Gf, S.Gd, t_has.p);
+  HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+  HF_HIP(hipGetLastError());
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  ctx->last_ms = ms;
+  // the rows with an absorbing triangle, ascending: built once, on the host
+  std::vector<int32_t> has(n), rows;
+  HF_HIP(copy_sync(ctx, has.data(), t_has.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; ++i)
+    if (has[i]) rows.push_back(static_cast<int32_t>(i));
+  HF_TRY(dev_alloc(ctx, &S.rows, rows.size()));
+  HF_HIP(copy_sync(ctx, S.rows, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice));
+  S.nrows = static_cast<int>(rows.size());
+  S.diff = true;
+  return HF_OK;
+}
+
+int hf_get_source_derivative(hf_ctx* ctx, int32_t which, double* out) {
+  if (!ctx || !out) return HF_ERR_ARG;
+  if (!ctx->src.on || !ctx->src.diff)
+    return fail(ctx, HF_ERR_STATE, "hf_get_source_derivative: the source is not differentiable (hf_source_derivatives first)");
+  if (which < 0 || which > 1) return fail(ctx, HF_ERR_ARG, "hf_get_source_derivative: which = %d (0: fwhm, 1: depth)", which);
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_HIP(copy_sync(ctx, out, which == 0 ? ctx->src.Gf : ctx->src.Gd, sizeof(double) * ctx->n, hipMemcpyDeviceToHost));
+  return HF_OK;
+}
+
+int hf_tangent_set_source(hf_ctx* ctx, int32_t n_steps, const double* coef) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_source before hf_tangent_setup / hf_tangent_setup_dir");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_source: a batch is open");
+  if (!ctx->src.on || !ctx->src.diff)
+    return fail(ctx, HF_ERR_STATE, "hf_tangent_set_source: the source is not differentiable (hf_set_source, then hf_source_derivatives)");
+  if (n_steps < 0 || (n_steps > 0 && !coef)) return fail(ctx, HF_ERR_ARG, "hf_tangent_set_source: %d steps or a null pointer", n_steps);
+  hf_ctx::Tangent& T = ctx->tan;
+  const size_t len = static_cast<size_t>(n_steps) * T.nv * 3;
+  unsigned mask = 0;
+  for (size_t q = 0; q < len; ++q) {
+    if (!std::isfinite(coef[q]))
+      return fail(ctx, HF_ERR_ARG, "hf_tangent_set_source: the coefficient of step %zu, column %zu is not finite", q / (3 * T.nv), (q / 3) % T.nv);
+    if (coef[q] != 0.0) mask |= 1u << ((q / 3) % T.nv);
+  }
+  HF_HIP(hipSetDevice(ctx->dev));
+  dev_free(&T.scoef);
+  T.ssteps = T.snext = 0; T.scur = -1; T.smask = 0;
+  if (n_steps == 0) return HF_OK;
+  HF_TRY(dev_alloc(ctx, &T.scoef, len));
+  HF_HIP(copy_sync(ctx, T.scoef, coef, sizeof(double) * len, hipMemcpyHostToDevice));
+  T.ssteps = n_steps;
+  T.smask = mask;
+  return HF_OK;   // a schedule like the amplitudes': the tangents continue, as the state does
 }
 
 int hf_get_source(hf_ctx* ctx, double* F) {

@@ -778,6 +778,22 @@ __global__ void kb_gather(int ns, const int32_t* __restrict__ idx, const double*
   if (q < ns) out[static_cast<size_t>(j) * ns + q] = u[static_cast<size_t>(idx[q]) * NV + j];
 }
 
+// Source columns of a tangent run (hf_tangent_set_source): F[i * NV + j] += (c0 F1[i] + c1 G_f[i]) + c2 G_d[i] for
+// the rows i of the compact list `rows` (those with an absorbing triangle, ascending) and the columns j of `mask`; coef holds
+// (c0, c1, c2) of the step per column.  One thread per (row, column): a wave's stores to F are contiguous over j.
+template <int NV>
+__global__ void kb_source_columns(int nrows, const int32_t* __restrict__ rows, unsigned mask, const double* __restrict__ coef /* [NV][3] */,
+                                  const double* __restrict__ F1, const double* __restrict__ Gf, const double* __restrict__ Gd,
+                                  double* __restrict__ F) {
+#pragma clang fp contract(off)
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int q = t / NV, j = t % NV;
+  if (q >= nrows || !((mask >> j) & 1u)) return;
+  const int i = rows[q];
+  const double c0 = coef[3 * j], c1 = coef[3 * j + 1], c2 = coef[3 * j + 2];
+  F[static_cast<size_t>(i) * NV + j] += (c0 * F1[i] + c1 * Gf[i]) + c2 * Gd[i];
+}
+
 // column j of an interleaved array <- / -> a plain array
 __global__ void kb_put_column(size_t n, int nv, int j, const double* __restrict__ src, double* __restrict__ dst) {
   for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * blockDim.x)

@@ -107,7 +107,7 @@ struct TanDir { int32_t c_r, c_z; double w_r, w_z; };
 
 // The row-gather assembly kernels: k_assemble_rows<false / true>, k_assemble_rows_an<false / true>, k_assemble_rows_kT,
 // k_assemble_rows_cT, k_assemble_rows_kT_K
-enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_SOURCE, RG_SHAPE1, RG_SHAPE2, RG_SHAPE4, RG_VARIANTS };
+enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_SOURCE, RG_SOURCE_D, RG_SHAPE1, RG_SHAPE2, RG_SHAPE4, RG_VARIANTS };
 
 }  // namespace
 
@@ -306,6 +306,12 @@ struct hf_ctx {
     int32_t* absorb = nullptr;   // 64 flags by row-gather tag-dictionary index
     std::vector<double> amp;     // amplitudes of the next steps; empty: amplitude 0
     size_t next = 0;             // the next step's index into amp
+    double fwhm = 0.0, z0 = 0.0, depth = 0.0;   // as given to hf_set_source
+    // differentiable source (hf_source_derivatives).  Nothing below is allocated while `diff` is false.
+    bool diff = false;
+    double *Gf = nullptr, *Gd = nullptr;   // dF1/dfwhm, dF1/ddepth (k_source_load_d), n doubles each
+    int32_t* rows = nullptr;     // the rows with an absorbing triangle, ascending
+    int nrows = 0;
   } src;
   // region monitors (hf_set_monitors, hf_monitor.hpp): per monitored cell tag a record row after every step of hf_step / hf_run /
   // hf_run_tangent.  Nothing below is allocated, and nothing is launched, while no monitors are set.
@@ -408,6 +414,12 @@ struct hf_ctx {
     double *un = nullptr, *um1 = nullptr;   // u^n and u^{n-1} of the last step of hf_run_tangent (copies, kept for the load)
     int wmode = 0;                   // of that step: 0 = none taken since the last reset, 1 = backward Euler, 2 = BDF2
     bool hist = false;               // um1 holds u^{n-1} (false: a rest start, u^{n-1} = u^n)
+    // source columns (hf_tangent_set_source): per step and column (c0, c1, c2); kb_source_columns<nv> adds
+    // c0 F1 + c1 G_f + c2 G_d to the columns of `smask` on the source's rows.  Nothing is allocated or launched while smask == 0.
+    double* scoef = nullptr;         // ssteps x nv x 3 doubles
+    int ssteps = 0, snext = 0;       // rows of the table; the row the next step of hf_run_tangent uses
+    int scur = -1;                   // the row of the last step taken (-1: none since the table was set or the tangents were reset)
+    unsigned smask = 0;              // bit j: column j has a non-zero coefficient in some row
   } tan;
   int fsamp_cap = 0;
   // temperature-dependent conductivities (hf_set_kappa_tables): per row-gather tag-dictionary entry a table header (KTab,

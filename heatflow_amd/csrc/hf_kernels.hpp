@@ -981,6 +981,75 @@ __global__ __launch_bounds__(RBA) void k_source_load(int nblk, int capd, const i
   }
 }
 
+// k_source_load's sibling for a differentiable source (hf_source_derivatives; same lists, staging and launch
+// geometry): G_f = dF1/dfwhm and G_d = dF1/ddepth, the unit-capacity element mass applied to the nodal values
+//   s_f = s (2 c_r r^2 / fwhm)   and   s_d = s |z - z0| inv_depth^2   (0 for a uniform layer, inv_depth = 0)
+// inside the absorbing elements, exactly as k_source_load forms F1 from s.  In one pass the block's column nodes get s_f and s_d
+// from one s (s itself enters no sum and is not staged: one double per column node more LDS than k_source_load), each computed
+// once per node, so every lane that reads a node sees the same bits.
+// Each sum runs in list order in a register of the row's lane - no atomics, bitwise reproducible; rows with no absorbing
+// triangle are written as exact zeros, and `has` gets 1 for a row with an absorbing triangle, 0 otherwise.
+__global__ __launch_bounds__(RBA) void k_source_load_d(int nblk, int capd, const int4* __restrict__ hdr, const uint4* __restrict__ ell,
+                                                       const uint4* __restrict__ cid16, const double2* __restrict__ zrb,
+                                                       const int32_t* __restrict__ rowptr, const int32_t* __restrict__ absorb,
+                                                       double c_r, double z0, double inv_depth, double fwhm,
+                                                       double* __restrict__ Gf, double* __restrict__ Gd, int32_t* __restrict__ has) {
+  extern __shared__ double smem[];
+  __shared__ int sabs[64];
+  const int capw = capd + (capd & 1);
+  double2* sXd = reinterpret_cast<double2*>(smem);
+  double* sF = smem + 2 * capd;
+  double* sD = sF + capw;
+  int* sR = reinterpret_cast<int*>(sD + capw);
+  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);
+  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
+  const int t = threadIdx.x;
+  if (t < 64) sabs[t] = absorb[t];
+  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const int4 cA = hdr[2 * blk], cB = hdr[2 * blk + 1];
+    const int c0 = cA.x >> 3, nc = ((cA.x + cA.y + 7) >> 3) - c0;
+    for (int i = t; i < nc; i += RBA) sC4[i] = cid16[c0 + i];
+    for (int i = t; i < cA.w; i += RBA) {
+#pragma clang fp contract(off)
+      const double2 P = zrb[cA.z + i];
+      const double s = source_shape(P, c_r, z0, inv_depth);
+      sXd[i] = P;
+      sF[i] = s * (((2.0 * c_r) * (P.y * P.y)) / fwhm);
+      sD[i] = s * ((fabs(P.x - z0) * inv_depth) * inv_depth);
+    }
+    if (t < cB.w) sR[t] = rowptr[blk * RBA + t] - cA.x;
+    __syncthreads();
+    if (t < cB.w) {
+#pragma clang fp contract(off)
+      const int sbase = sR[t] + (cA.x & 7);
+      const int ci = cB.z + t;
+      const double2 Pi = sXd[ci];
+      const double fi = sF[ci], di = sD[ci];
+      double accf = 0.0, accd = 0.0;
+      int any = 0;
+      for (int g = 0; g < cB.y; ++g) {
+        const uint4 ev = ell[cB.x + g * RBA + t];
+        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
+          if (e == 0xFFFFu) continue;
+          if (sabs[e >> 10] == 0) continue;
+          const int pj = sC[sbase + (e & 31u)], pk = sC[sbase + ((e >> 5) & 31u)];
+          const ElemRow r = element_row(Pi, sXd[pj], sXd[pk], 1.0, 0.0);
+          accf += (r.m0 * fi + r.m1 * sF[pj]) + r.m2 * sF[pk];
+          accd += (r.m0 * di + r.m1 * sD[pj]) + r.m2 * sD[pk];
+          any = 1;
+        }
+      }
+      Gf[blk * RBA + t] = accf;
+      Gd[blk * RBA + t] = accd;
+      has[blk * RBA + t] = any;
+    }
+    __syncthreads();
+  }
+}
+
 // F0 + p F1: the load of a step when a source (hf_set_source) acts on top of a load (hf_set_load / hf_hold_load)
 __global__ __launch_bounds__(TPB) void k_source_sum(int n, const double* __restrict__ F0, double p, const double* __restrict__ F1,
                                                     double* __restrict__ out) {

@@ -47,7 +47,8 @@ from .kappa_t import material_cv_table, material_table, picard_sweeps, refuse_ta
 from .mesh import Mesh, load_mesh_arrays
 from .monitors import (check_sigma, parse_monitors, problem_monitors, refuse_monitors, uncertainty as monitor_uncertainty,
                        used_config as monitors_used_config, write_monitors_csv, write_uncertainty_csv)
-from .source import amplitudes as source_amplitudes, parse_source, refuse_source
+from .source import (SOURCE_PARAMS, amplitudes as source_amplitudes, check_source_param, parse_source, refuse_source, source_block,
+                     tangent_coefficients)
 from .solver import DEFAULT_MAX_IT, DEFAULT_RTOL, HeatProblem
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -239,6 +240,7 @@ class SimulationSession:
         self.problem = None
         self._key = None
         self._source_F1 = None     # the resident problem's source vector, read back once per problem
+        self._source_G = None      # its derivatives (G_f, G_d), read back once per problem by the first tangent run under it
         self._tree = None
         self._space = None
         self._dof_cache = {}
@@ -369,6 +371,7 @@ class SimulationSession:
                                        **({"monitors": mon} if mon else {}))
             self._key = key
             self._source_F1 = None
+            self._source_G = None
             self._k = dict(tag_to_k)
             # conductivities the multigrid levels were built for: this problem's, or those of the session that shared them
             self._k_hier = dict(shared["k"]) if shared else dict(tag_to_k)
@@ -520,7 +523,12 @@ class SimulationSession:
         the material's rho * cv in J/m^3/K, its cv or its rho (one of the three per material) -, and / or "fwhm"
         of the heating profile) adds ``tangents`` {param: {watcher: d watcher / d param}} and ``tangent_iters`` (HeatProblem.run_tangent; not with a field sink or the flux projection).
         A ``heating.source`` block (heatflow_amd.source) drives the run by absorbed laser power, the field sink and the flux
-        projection included; not with ``tangents`` or ``two_sided``.  A ``monitors`` block (heatflow_amd.monitors) adds
+        projection included; not with ``two_sided``, and with ``tangents`` only under ``heating.source.tangents: true`` (DESIGN.md
+        3.19).  Then ``tangents``, ``monitor_tangents`` and ``monitor_sigma`` take the names above and the source's own -
+        "source.power" (W), "source.fwhm", "source.depth" (m), "source.pulse.t0", "source.pulse.fwhm" (s) -; ValueError naming the
+        parameter for "source.depth" on a block without ``depth``, "source.pulse.*" on a file pulse, "<material>.thickness" under
+        a source (its load depends on the node positions; that term is not formed) and "fwhm" with ``keep_line: false`` (there is
+        no heated line; the beam's width is "source.fwhm"), and for any "source.*" name without a source.  A ``monitors`` block (heatflow_amd.monitors) adds
         ``monitors`` {region: {field: one value per step}} to the result, whichever way the steps are taken.
         ``monitor_tangents`` (with ``tangents`` and a ``monitors`` block) adds ``monitor_tangents``
         {param: {region: {field: d field / d param per step}}}.  ``monitor_sigma`` = {param: relative one-sigma}, the names the
@@ -539,8 +547,20 @@ class SimulationSession:
                 raise ValueError(f"{arg}: {len(tangents)} tangent columns (at most 16 per run)")
             monitor_tangents = True
         spec = parse_source(cfg)
-        if spec is not None and tangents:
+        if spec is not None and tangents and not spec.tangents:
             refuse_source(cfg, "tangents=")
+        for p in tangents or ():     # the source's own names, and the names a source rules out, before any problem is made
+            if p in SOURCE_PARAMS or p.startswith("source."):
+                try:
+                    check_source_param(spec, p)
+                except ValueError as e:
+                    raise ValueError(f"tangents: {e}") from None
+            elif spec is not None and p == "fwhm" and not spec.keep_line:
+                raise ValueError("tangents: parameter 'fwhm': the heated line is off (heating.source.keep_line: false); the beam's "
+                                 "width is 'source.fwhm'")
+            elif spec is not None and p.endswith(".thickness"):
+                raise ValueError(f"tangents: parameter {p!r}: a layer thickness under a volumetric source (heating.source) is not "
+                                 "supported (the source's load depends on the node positions, and that term is not formed)")
         t_final = float(cfg["timing"]["t_final"])
         num_steps = int(cfg["timing"]["num_steps"])
         dt = t_final / num_steps
@@ -590,11 +610,16 @@ class SimulationSession:
                 check_capacity_names(params)
             except ValueError as e:
                 raise ValueError(f"tangents: {e}") from None
-            cond, bnd, shp, cap, cscale = [], {}, {}, {}, {}
+            cond, bnd, shp, cap, cscale, srcp = [], {}, {}, {}, {}, {}
             for j, p in enumerate(params):
-                if p == "fwhm":
+                if p in SOURCE_PARAMS:
+                    cond.append([])
+                    srcp[j] = p
+                elif p == "fwhm":
                     cond.append([])
                     bnd[j] = {3 + q: h.gaussian_dfwhm for q, h in enumerate(self._heats)}
+                    if spec is not None and "fwhm" not in source_block(cfg):   # the beam takes heating.fwhm too: both terms
+                        srcp[j] = "source.fwhm"
                 elif p in self.material_tags:
                     cond.append([self.material_tags[p]])
                 else:
@@ -620,11 +645,23 @@ class SimulationSession:
                         cscale[j] = capacity_scale(cfg["mats"][mat], kind)
                     else:
                         cond.append([(self.material_tags[mat], kind)])
+            src_kw = {}
+            if spec is not None:     # the opt-in: the source becomes differentiable, its own parameters get their columns
+                src_cols = {}
+                if srcp:
+                    if self._source_G is None:
+                        self._source_G = (prob.source_derivative("fwhm"), prob.source_derivative("depth"))
+                    table = tangent_coefficients(spec, sorted(set(srcp.values())), (np.arange(num_steps) + 1) * dt, self._source_F1,
+                                                 self._source_G[0], self._source_G[1], _resolve)
+                    src_cols = {j: {"amplitude": table[p][:, 0], "fwhm": table[p][:, 1], "depth": table[p][:, 2]}
+                                for j, p in srcp.items()}
+                src_kw = {"source": src_cols, "source_amplitude": amp}
             times, samples, tsamp, iters, titers = prob.run_tangent(num_steps, nodes, conductivity=cond, boundary=bnd,
                                                                     time_varying=varying, **({"shape": shp} if shp else {}),
                                                                     **({"capacity": [cap.get(j, []) for j in range(len(params))]}
                                                                        if cap else {}),
-                                                                    **({"monitor_tangents": True} if monitor_tangents else {}))
+                                                                    **({"monitor_tangents": True} if monitor_tangents else {}),
+                                                                    **src_kw)
             for j, f in cscale.items():
                 if f != 1.0:
                     tsamp[:, j] *= f
@@ -902,7 +939,8 @@ def cli(kind, argv=None):
     p.add_argument("--suppress-print", action="store_true")
     p.add_argument("--device", type=int, default=0)
     p.add_argument("--monitor-sigma", nargs="+", metavar="NAME=REL",
-                   help="relative one-sigma of input parameters (the names tangents accept, e.g. p_sample.rho_c=0.15 fwhm=0.1): "
+                   help="relative one-sigma of input parameters (the names tangents accept, e.g. p_sample.rho_c=0.15 fwhm=0.1, under "
+                        "heating.source.tangents: true also source.power=0.05 source.fwhm=0.1): "
                         "writes monitor_uncertainty.csv, the first-order one-sigma band of every monitor field (needs a monitors block)")
     a = p.parse_args(argv)
     sigma = None

@@ -24,7 +24,7 @@ from .parameter_sweep import build_stack, get_watcher_points, oside_curves
 from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, KEY, capacity_scale, check_capacity_names, material_aniso, refuse_aniso,
                     split_param)
 from .kappa_t import refuse_tables
-from .source import refuse_source
+from .source import SOURCE_PARAMS, check_source_param, parse_source, refuse_source_tangents
 from .monitors import refuse_monitors
 
 DEFAULT_EXP_CSV = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "experimental_data",
@@ -39,13 +39,33 @@ def _material_param(cfg, name):
     return cfg["mats"][mat], kind
 
 
+def _is_source_param(name):
+    """A parameter of the volumetric source ("source.power", "source.fwhm", "source.depth", "source.pulse.t0", "source.pulse.fwhm");
+    any other "source.*" spelling is sent to check_source_param for its ValueError."""
+    return name in SOURCE_PARAMS or name.startswith("source.")
+
+
+def _source_param(cfg, name):
+    """The validated source of ``cfg`` for the source parameter ``name``; ValueError naming the parameter otherwise."""
+    spec = parse_source(cfg)
+    check_source_param(spec, name)
+    return spec
+
+
 def get_param(cfg, name):
     """The value of a parameter: "fwhm", a material's k ("<m>" or "<m>.k"), its directional conductivity "<m>.k_r" =
     k * k_aniso.r / "<m>.k_z" = k * k_aniso.z in W/m/K (multiplier 1 where the block or the key is absent), or its layer
     thickness "<m>.thickness" = mats.<m>.z in metres (the materials whose z the stack reads), or its heat capacity: "<m>.rho_c" =
-    rho * cv in J/m^3/K, "<m>.cv", "<m>.rho"."""
+    rho * cv in J/m^3/K, "<m>.cv", "<m>.rho"; or a parameter of the volumetric source: "source.power" in W,
+    "source.fwhm" (the beam's width, heating.fwhm where the block has none) and "source.depth" in metres, "source.pulse.t0" and
+    "source.pulse.fwhm" of a Gaussian pulse in seconds."""
     if name == "fwhm":
         return float(cfg["heating"]["fwhm"])
+    if _is_source_param(name):
+        spec = _source_param(cfg, name)
+        if name.startswith("source.pulse."):
+            return float(spec.pulse[1 if name.endswith(".t0") else 2])
+        return float({"source.power": spec.power, "source.fwhm": spec.fwhm, "source.depth": spec.depth}[name])
     mat, kind = _material_param(cfg, name)
     if kind in (None, "k"):
         return float(mat["k"])
@@ -62,7 +82,8 @@ def set_params(cfg, params, values):
     """A copy of ``cfg`` with the parameters set: "fwhm" of the heating profile, the conductivity k of a material ("<m>" or
     "<m>.k"; the multipliers of a ``k_aniso`` block stay), or a directional conductivity: "<m>.k_r" writes k_aniso.r = value / k,
     "<m>.k_z" k_aniso.z, creating the block where absent; "<m>.thickness" writes mats.<m>.z in metres; "<m>.rho_c"
-    writes cv = value / rho and keeps rho, "<m>.cv" and "<m>.rho" write their key (two of the three on one material: ValueError).  The k parameters are applied first, so a directional value holds
+    writes cv = value / rho and keeps rho, "<m>.cv" and "<m>.rho" write their key (two of the three on one material: ValueError); a source parameter writes its key of ``heating.source``
+    ("source.fwhm" writes heating.source.fwhm explicitly, whether the block had one or took heating.fwhm).  The k parameters are applied first, so a directional value holds
     whatever the order of the names."""
     c = copy.deepcopy(cfg)
     pairs = list(zip(params, values))
@@ -70,6 +91,13 @@ def set_params(cfg, params, values):
     for name, v in pairs:
         if name == "fwhm":
             c["heating"]["fwhm"] = float(v)
+        elif _is_source_param(name):
+            _source_param(c, name)
+            block = c["heating"]["source"]
+            if name.startswith("source.pulse."):
+                block["pulse"][name.rsplit(".", 1)[1]] = float(v)
+            else:
+                block[name.split(".", 1)[1]] = float(v)
         elif _material_param(c, name)[1] in (None, "k"):
             _material_param(c, name)[0]["k"] = float(v)
         elif _material_param(c, name)[1] == "t":
@@ -82,7 +110,7 @@ def set_params(cfg, params, values):
             else:
                 mat[kind] = float(v)
     for name, v in pairs:
-        if name != "fwhm":
+        if name != "fwhm" and not _is_source_param(name):
             mat, kind = _material_param(c, name)
             if kind in ("r", "z"):
                 mat.setdefault(KEY, {})[kind] = float(v) / float(mat["k"])
@@ -136,18 +164,29 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     t0 = time.time()
     scheme = time_scheme(cfg)
     refuse_tables(cfg, "heatflow_amd.fit")
-    refuse_source(cfg, "heatflow_amd.fit")
+    refuse_source_tangents(cfg, "heatflow_amd.fit")     # a source fits only under heating.source.tangents: true
     refuse_monitors(cfg, "heatflow_amd.fit")
     params = tuple(params)
     refuse_aniso(cfg, "heatflow_amd.fit of the conductivity of an anisotropic material", set(params), DIRECTIONAL_HINT)
     for p in params:
-        if p != "fwhm":
+        if p == "source.power":
+            raise ValueError("parameter 'source.power' cannot be fitted: the objective is normalised by the p-side span and the "
+                             "temperature rise is linear in the power, so its Jacobian column is identically zero (it is valid "
+                             "as a nuisance, in tangents= and in monitor_sigma=)")
+        if _is_source_param(p):
+            _source_param(cfg, p)
+        elif p != "fwhm":
             _material_param(cfg, p)      # an unknown material or suffix, before any mesh or session is made
     nuisance = {str(q): v for q, v in dict(nuisance or {}).items()}
     for q, sig in nuisance.items():
         if q in params:
             raise ValueError(f"nuisance {q!r} is a fitted parameter (a parameter is fitted or budgeted, not both)")
-        if q != "fwhm":
+        if _is_source_param(q):
+            try:
+                _source_param(cfg, q)
+            except ValueError as e:
+                raise ValueError(f"nuisance {q!r}: {e}") from None
+        elif q != "fwhm":
             try:
                 mat_q, kind_q = _material_param(cfg, q)
             except ValueError as e:
@@ -163,7 +202,7 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     check_capacity_names(params + tuple(nuisance))
     if nuisance:
         refuse_aniso(cfg, "heatflow_amd.fit with the conductivity of an anisotropic material as a nuisance", set(nuisance), DIRECTIONAL_HINT)
-    thick = [(j, p.rsplit(".", 1)[0]) for j, p in enumerate(params) if p != "fwhm" and _material_param(cfg, p)[1] == "t"]
+    thick = [(j, p.rsplit(".", 1)[0]) for j, p in enumerate(params) if p != "fwhm" and not _is_source_param(p) and _material_param(cfg, p)[1] == "t"]
     for j, mat in thick:
         check_thickness_name(cfg, mat, params[j])
     exp = load_experiment(exp_csv)
@@ -302,7 +341,7 @@ def main(argv=None, backend=None):
 
     ap = argparse.ArgumentParser(description="Fit conductivities (and fwhm) to the experimental o-side curve with tangent runs")
     ap.add_argument("--config", required=True)
-    ap.add_argument("--params", nargs="+", default=["p_sample"], help="material names, <material>.k_r, <material>.k_z, <material>.k, <material>.thickness, <material>.rho_c, <material>.cv, <material>.rho and / or fwhm")
+    ap.add_argument("--params", nargs="+", default=["p_sample"], help="material names, <material>.k_r, <material>.k_z, <material>.k, <material>.thickness, <material>.rho_c, <material>.cv, <material>.rho, fwhm, and under heating.source.tangents: true source.fwhm, source.depth, source.pulse.t0, source.pulse.fwhm")
     ap.add_argument("--exp-csv", default=DEFAULT_EXP_CSV)
     ap.add_argument("--mesh-folder", default=None,
                     help="mesh.msh + mesh_cfg.yaml to use; built there when absent (default: <output-dir>/mesh)")

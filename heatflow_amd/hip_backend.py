@@ -37,6 +37,7 @@ EXPORTS = [
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
     "hf_set_source", "hf_get_source", "hf_set_source_amplitudes",
+    "hf_source_derivatives", "hf_get_source_derivative", "hf_tangent_set_source",
     "hf_set_monitors", "hf_monitor_now", "hf_monitor_count", "hf_get_monitors", "hf_monitor_clear",
     "hf_set_monitor_tangents", "hf_monitor_tangent_count", "hf_get_monitor_tangents", "hf_monitor_tangent_eval",
     "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_set_shape", "hf_tangent_set_capacity", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
@@ -144,6 +145,9 @@ def load_library():
         "hf_set_source": [vp, i32, pi, dbl, dbl, dbl],
         "hf_get_source": [vp, pd],
         "hf_set_source_amplitudes": [vp, i32, pd],
+        "hf_source_derivatives": [vp, i32],
+        "hf_get_source_derivative": [vp, i32, pd],
+        "hf_tangent_set_source": [vp, i32, pd],
         "hf_set_monitors": [vp, i32, pd],
         "hf_monitor_now": [vp, pd],
         "hf_monitor_count": [vp, pi],
@@ -484,6 +488,20 @@ class HeatflowHIP:
             tab[int(t)] = int(j)
         self._check(self._lib.hf_tangent_set_capacity(self._ctx, self.tab_len, _pi(tab)))
 
+    def tangent_set_source(self, coef):
+        """Source columns of the tangent set-up in force (hf_tangent_set_source): ``coef`` (n_steps, nv, 3) holds
+        (c0, c1, c2) per step and column, and step k after the call adds c0 F1 + c1 G_f + c2 G_d to the column's load.  Needs a
+        differentiable source (:meth:`source_derivatives`).  ``None`` (or no rows) removes the source columns.  A schedule like
+        the amplitudes': the tangents are not reset."""
+        if coef is None or len(coef) == 0:
+            self._check(self._lib.hf_tangent_set_source(self._ctx, 0, None))
+            return
+        c = _f64(coef)
+        nv = self.tangent_nv or 2     # (no set-up: the library reports it)
+        if c.ndim != 3 or c.shape[1:] != (nv, 3):
+            raise ValueError(f"tangent_set_source: coef must be (n_steps, {nv}, 3), got {c.shape}")
+        self._check(self._lib.hf_tangent_set_source(self._ctx, c.shape[0], _pd(c)))
+
     def tangent_load(self, j):
         """Column j of the tangent loads F = -K_j u at the current state, by the set-up in force (hf_tangent_load; tests and
         diagnostics)."""
@@ -757,6 +775,18 @@ class HeatflowHIP:
         F = np.empty(self.n, dtype=np.float64)
         self._check(self._lib.hf_get_source(self._ctx, _pd(F)))
         return F
+
+    def source_derivatives(self, on=True):
+        """Make the current source differentiable (hf_source_derivatives): forms dF1/dfwhm and dF1/ddepth on the
+        device, after which the tangent calls accept the source.  ``on = False`` frees that again; set_source switches it off."""
+        self._check(self._lib.hf_source_derivatives(self._ctx, 1 if on else 0))
+
+    def get_source_derivative(self, which):
+        """dF1/dfwhm (``which`` = 0 or "fwhm") or dF1/ddepth (1 or "depth") of a differentiable source (n values)."""
+        w = {"fwhm": 0, "depth": 1}.get(which, which)
+        G = np.empty(self.n, dtype=np.float64)
+        self._check(self._lib.hf_get_source_derivative(self._ctx, int(w), _pd(G)))
+        return G
 
     def set_source_amplitudes(self, p):
         """Amplitudes (peak power densities, W/m^3) of the next len(p) steps: step k after the call uses p[k].  An empty list

@@ -1,7 +1,8 @@
 """Entry point for the five-material stack without diamonds/gasket (reference run_no_diamond.py).
 
 Same call as the reference ``run_simulation(cfg, mesh_folder, ...)``; see
-:mod:`heatflow_amd.run_with_diamond` for the extras.
+:mod:`heatflow_amd.run_with_diamond` for the extras - ``tangents=``, ``monitor_tangents=`` and ``monitor_sigma=`` under a
+``heating.source`` block with ``tangents: true`` and the source's own parameter names among them.
 """
 from .driver import cli, run_simulation_impl, suppress_output  # noqa: F401
 

@@ -4,7 +4,9 @@ Same call as the reference: ``run_simulation(cfg, mesh_folder, rebuild_mesh=Fals
 visualize_mesh=False, output_folder=None, watcher_points=None, write_xdmf=True,
 suppress_print=False)``.  Keyword-only extras (``device_id``, ``session``, ``rtol`` ...) select
 the GPU and let a sweep keep the mesh resident.  Returns the result dict of
-:func:`heatflow_amd.driver.run_simulation_impl` (the reference returns None).
+:func:`heatflow_amd.driver.run_simulation_impl` (the reference returns None).  ``tangents=``, ``monitor_tangents=`` and
+``monitor_sigma=`` work under a ``heating.source`` block that sets ``tangents: true`` and then also take the source's own
+parameters ("source.power", "source.fwhm", "source.depth", "source.pulse.t0", "source.pulse.fwhm").
 """
 from .driver import cli, run_simulation_impl, suppress_output  # noqa: F401
 

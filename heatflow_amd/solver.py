@@ -89,6 +89,9 @@ class HeatProblem:
             raise ValueError("HeatProblem: k_aniso together with kappa_tables / rhoc_tables is not supported "
                              "(the table kernels are isotropic)")
         self.source = check_source(source)
+        # hf_source_derivatives has been called for the source (run_tangent's source=, source_derivative).  False is always safe:
+        # the call is made again.  Code that sets the source on the backend directly leaves the library refusing, whatever this says.
+        self._source_diff = False
         self.monitors = check_regions(monitors)
         self._monitor_tags = tag_thresholds(self.monitors) if self.monitors else {}
         self.monitor_T_ref = float(u0) if np.isscalar(u0) else None
@@ -200,6 +203,18 @@ class HeatProblem:
         """F1 of the source: the load at unit amplitude (n values; 2 pi sum(F1) = the power in W per unit amplitude)."""
         return self.backend.get_source()
 
+    def source_derivative(self, which):
+        """dF1/dfwhm (``which`` = "fwhm") or dF1/ddepth ("depth") of the source (n values); makes the source
+        differentiable if it is not yet."""
+        if not self.source:
+            raise ValueError("source_derivative: the problem has no source (HeatProblem(..., source=))")
+        if which not in ("fwhm", "depth"):
+            raise ValueError(f"source_derivative: 'fwhm' or 'depth' expected, got {which!r}")
+        if not self._source_diff:
+            self.backend.source_derivatives(True)
+            self._source_diff = True
+        return self.backend.get_source_derivative(which)
+
     def _source_amplitudes(self, source_amplitude, times):
         """The amplitudes of the steps that end at ``times``: a callable p(t), or one value per step."""
         if not self.source:
@@ -244,7 +259,7 @@ class HeatProblem:
         return times, samples, iters
 
     def run_tangent(self, num_steps, watcher_nodes, conductivity=(), boundary=None, time_varying=None, first_step=0, shape=None,
-                    capacity=(), monitor_tangents=False):
+                    capacity=(), monitor_tangents=False, source_amplitude=None, source=None):
         """:meth:`run` plus the derivatives of the watcher curves with respect to parameters theta_j (hf_run_tangent,
         DESIGN.md 3.7).  Column j of ``conductivity`` = the cell tags whose conductivity theta_j is (they move together).  An
         entry may also be a pair ``(tag, "k" | "r" | "z")``: the tag's kappa (both directions of an anisotropic
@@ -264,7 +279,12 @@ class HeatProblem:
         capacity column only, and without ``capacity`` the backend sees the calls of before.  ``monitor_tangents`` (DESIGN.md
         3.18; needs ``monitors=``) switches the derivative records of the region monitors on for this run:
         :meth:`monitor_tangent_history` then gives the derivative of every monitor field along every column, per step; the
-        default makes no new backend call.  Returns (times, samples, tangent samples (n_steps, n_par, n_s), iters, tangent iters
+        default makes no new backend call.  ``source`` (needs ``source=`` on the problem) makes the problem's
+        source differentiable, after which the backend accepts a tangent run under it (``{}`` is enough; without the keyword a
+        problem with a source is refused as before), and gives the source columns: {column: {"amplitude": c0, "fwhm": c1, "depth":
+        c2}}, each one value per step or a callable of time (missing: 0), adds c0 F1 + c1 G_f + c2 G_d = d(p_k F1)/dtheta_j to the
+        column's load at step k (heatflow_amd.source.tangent_coefficients gives them for the source's own parameters).
+        ``source_amplitude`` has the meaning it has in :meth:`run`.  Shape columns under a source are refused.  Returns (times, samples, tangent samples (n_steps, n_par, n_s), iters, tangent iters
         (n_steps, n_par))."""
         if monitor_tangents and not self.monitors:
             raise ValueError("run_tangent: monitor_tangents needs monitors (HeatProblem(..., monitors=))")
@@ -280,9 +300,24 @@ class HeatProblem:
                 if int(t) in cap_col:
                     raise ValueError(f"run_tangent: cell tag {t} is listed in two capacity columns")
                 cap_col[int(t)] = j
-        n_par = max([len(conductivity), len(capacity or ())] + [j + 1 for j in boundary] + [j + 1 for j in shape])
+        if source is None and source_amplitude is not None:
+            raise ValueError("run_tangent: source_amplitude needs source= (tangents under a source are switched on by it)")
+        if source is not None and not self.source:
+            raise ValueError("run_tangent: source= needs a source (HeatProblem(..., source=))")
+        if source is not None and shape:
+            raise ValueError("run_tangent: shape columns under a source are not supported (the source's load depends on the "
+                             "node positions)")
+        src_cols = {}
+        for j, parts in (source or {}).items():
+            unknown = sorted(set(parts) - set(SOURCE_COLUMN_KEYS))
+            if int(j) < 0 or unknown:
+                raise ValueError(f"run_tangent: source column {j}: " + (f"unknown key {unknown[0]!r} (amplitude, fwhm, depth)"
+                                                                        if unknown else "a negative column"))
+            src_cols[int(j)] = dict(parts)
+        n_par = max([len(conductivity), len(capacity or ())] + [j + 1 for j in boundary] + [j + 1 for j in shape]
+                    + [j + 1 for j in src_cols])
         if n_par == 0:
-            raise ValueError("run_tangent: no parameter (conductivity, boundary or shape) given")
+            raise ValueError("run_tangent: no parameter (conductivity, boundary, shape or source) given")
         directional = any(isinstance(t, (tuple, list)) for tags in conductivity for t in tags)
         if not directional:
             tag_col = {}
@@ -310,6 +345,11 @@ class HeatProblem:
             spec += ("shape",) + tuple((j, hashlib.sha1(shape[j].tobytes()).hexdigest()) for j in sorted(shape))
         if cap_col:
             spec += ("capacity",) + tuple(sorted(cap_col.items()))
+        if src_cols:
+            spec += ("source",) + tuple(sorted(src_cols))
+        if source is not None and not self._source_diff:
+            self.backend.source_derivatives(True)            # (before the set-up, which refuses a source that is not differentiable)
+            self._source_diff = True
         if getattr(self, "_tangent_spec", None) != spec:     # a new set of parameters: the tangents start from zero
             if directional:
                 self.backend.tangent_setup_dir(n_par, cols["k"], cols["r"], cols["z"])
@@ -324,6 +364,15 @@ class HeatProblem:
         for bc in self.bcs:
             bc.update(0.0)
         times = (np.arange(first_step, first_step + num_steps) + 1) * self.dt
+        if source is not None:
+            self.backend.set_source_amplitudes([] if source_amplitude is None else self._source_amplitudes(source_amplitude, times))
+            if src_cols:
+                coef = np.zeros((num_steps, nv, 3), dtype=np.float64)
+                for j, parts in src_cols.items():
+                    for q, key in enumerate(SOURCE_COLUMN_KEYS):
+                        if parts.get(key) is not None:
+                            coef[:, j, q] = self._source_amplitudes(parts[key], times)
+                self.backend.tangent_set_source(coef)
         g_all = np.empty((num_steps, len(self.bc_dofs)), dtype=np.float64)
         h_all = np.zeros((num_steps, len(self.bc_dofs), nv), dtype=np.float64) if boundary else None
         for k, t in enumerate(times):
@@ -410,6 +459,9 @@ class HeatProblem:
         Dirichlet rows, 0 on them; it becomes the load and is returned.  Needs a solve_steady before (for K)."""
         self.backend.hold_load()
         return self.backend.get_load()
+
+
+SOURCE_COLUMN_KEYS = ("amplitude", "fwhm", "depth")     # c0, c1, c2 of a source column (run_tangent's source=)
 
 
 def check_source(source):

@@ -9,6 +9,7 @@
         face: outer                # outer | inner: which z face of the (first) material z0 is; default outer
         pulse: {t0: 1.0e-6, fwhm: 5.0e-7}     # Gaussian in time, peak 1; or {file: x.csv}
         keep_line: false           # true keeps the heated Dirichlet line as well
+        tangents: true             # opt in to tangent runs, fits and monitor error bars under the source
 
 The source is q(z, r, t) = p(t) s(z, r) with s = exp(-4 ln2 r^2 / fwhm^2) exp(-|z - z0| / depth) inside the listed materials
 (hf_set_source forms its load F1 on the GPU).  The absorbed power is P(t) = power * pulse(t); the amplitude handed to the time
@@ -28,7 +29,9 @@ from dataclasses import dataclass
 import numpy as np
 
 KEY = "heating.source"
-SOURCE_KEYS = ("material", "power", "fwhm", "depth", "face", "pulse", "keep_line")
+SOURCE_KEYS = ("material", "power", "fwhm", "depth", "face", "pulse", "keep_line", "tangents")
+# the source's own parameters in tangents=, monitor_sigma=, fits and --nuisance (under ``tangents: true``)
+SOURCE_PARAMS = ("source.power", "source.fwhm", "source.depth", "source.pulse.t0", "source.pulse.fwhm")
 PULSE_KEYS = ("t0", "fwhm", "file")
 FACES = ("outer", "inner")
 
@@ -44,6 +47,7 @@ class SourceSpec:
     face: str               # "outer" | "inner"
     pulse: tuple            # ("gaussian", t0, fwhm) or ("file", path)
     keep_line: bool
+    tangents: bool = False  # tangent runs, fits and monitor error bars are allowed under this source
 
     def z0(self, stack):
         """z of the absorbing face: the z face of the first material away from the sample mid-plane z = 0 (outer) or towards it
@@ -65,6 +69,8 @@ class SourceSpec:
         if math.isfinite(self.depth):
             out["depth"] = self.depth
         out["pulse"] = {"t0": self.pulse[1], "fwhm": self.pulse[2]} if self.pulse[0] == "gaussian" else {"file": self.pulse[1]}
+        if self.tangents:
+            out["tangents"] = True
         return out
 
 
@@ -77,6 +83,19 @@ def refuse_source(cfg, where):
     """ValueError naming the key if ``cfg`` asks for a volumetric source: ``where`` does not support it."""
     if source_block(cfg) is not None:
         raise ValueError(f"{where} does not support the volumetric source ({KEY})")
+
+
+def source_permits_tangents(cfg):
+    """True when ``cfg`` has a source that opts in to tangents (``heating.source.tangents: true``); a configuration without a
+    source needs no permission and gives False."""
+    block = source_block(cfg)
+    return isinstance(block, dict) and block.get("tangents") is True
+
+
+def refuse_source_tangents(cfg, where):
+    """:func:`refuse_source` unless the source opts in to tangents."""
+    if not source_permits_tangents(cfg):
+        refuse_source(cfg, where)
 
 
 def _positive(block, key, value):
@@ -150,7 +169,10 @@ def parse_source(cfg):
     keep = block.get("keep_line", False)
     if not isinstance(keep, bool):
         raise ValueError(f"{KEY}.keep_line must be true or false, got {keep!r}")
-    return SourceSpec(tuple(mats), power, fwhm, depth, face, spec, keep)
+    tangents = block.get("tangents", False)
+    if not isinstance(tangents, bool):
+        raise ValueError(f"{KEY}.tangents must be true or false, got {tangents!r}")
+    return SourceSpec(tuple(mats), power, fwhm, depth, face, spec, keep, tangents)
 
 
 def read_pulse_csv(path):
@@ -204,3 +226,57 @@ def power_density(power_watts, source_vector):
 def amplitudes(spec, times, source_vector, resolve=None):
     """The peak power densities p_k (W/m^3) of the steps that end at ``times``: power * pulse(t_k) / (2 pi sum F1)."""
     return power_density(spec.power * pulse_values(spec, times, resolve), source_vector)
+
+
+def check_source_param(spec, name):
+    """ValueError naming the parameter unless ``name`` (one of SOURCE_PARAMS) is a parameter of the source ``spec``."""
+    if name not in SOURCE_PARAMS:
+        raise ValueError(f"{name}: unknown source parameter (expected one of {', '.join(SOURCE_PARAMS)})")
+    if spec is None:
+        raise ValueError(f"{name}: the configuration has no volumetric source ({KEY})")
+    if name == "source.depth" and not math.isfinite(spec.depth):
+        raise ValueError(f"{name}: the source has no depth (uniform through the layer), so there is nothing to differentiate")
+    if name.startswith("source.pulse.") and spec.pulse[0] != "gaussian":
+        raise ValueError(f"{name}: the pulse comes from a file ({KEY}.pulse.file) and has no such parameter")
+
+
+def tangent_coefficients(spec, names, times, F1, G_f, G_d, resolve=None):
+    """{name: (n_steps, 3) array} of (c0, c1, c2) for the source parameters ``names`` at the steps that end at ``times``: the
+    load of a tangent column in that parameter is c0 F1 + c1 G_f + c2 G_d = d(p_k F1)/dtheta, with
+    p_k = P pulse_k / (2 pi sum F1) so that the configured power stays the discrete power:
+
+        source.power        c0 = p_k / P
+        source.fwhm         c0 = -p_k sum(G_f) / sum(F1),  c1 = p_k
+        source.depth        c0 = -p_k sum(G_d) / sum(F1),  c2 = p_k
+        source.pulse.t0     c0 = P / (2 pi sum F1) pulse_k 8 ln2 (t_k - t0) / w^2
+        source.pulse.fwhm   c0 = P / (2 pi sum F1) pulse_k 8 ln2 (t_k - t0)^2 / w^3       (w = pulse.fwhm)
+
+    G_f = dF1/dfwhm and G_d = dF1/ddepth come from the backend (HeatProblem.source_derivative); the sums are math.fsum's."""
+    t = np.asarray(times, dtype=np.float64)
+    total = math.fsum(float(v) for v in np.asarray(F1, dtype=np.float64))
+    if not total > 0.0:
+        raise ValueError(f"{KEY}: the source vector sums to {total!r} - no absorbing element carries the beam")
+    pulse = pulse_values(spec, t, resolve)
+    unit = 1.0 / (2.0 * math.pi * total)        # amplitude per watt
+    p = spec.power * pulse * unit
+    out = {}
+    for name in names:
+        check_source_param(spec, name)
+        c = np.zeros((len(t), 3), dtype=np.float64)
+        if name == "source.power":
+            c[:, 0] = pulse * unit
+        elif name == "source.fwhm":
+            c[:, 0] = -p * (math.fsum(float(v) for v in np.asarray(G_f, dtype=np.float64)) / total)
+            c[:, 1] = p
+        elif name == "source.depth":
+            c[:, 0] = -p * (math.fsum(float(v) for v in np.asarray(G_d, dtype=np.float64)) / total)
+            c[:, 2] = p
+        else:
+            _, t0, w = spec.pulse
+            k8 = 8.0 * math.log(2.0)
+            if name == "source.pulse.t0":
+                c[:, 0] = spec.power * unit * pulse * k8 * (t - t0) / (w * w)
+            else:
+                c[:, 0] = spec.power * unit * pulse * k8 * (t - t0) ** 2 / (w * w * w)
+        out[name] = c
+    return out

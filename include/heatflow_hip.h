@@ -374,6 +374,35 @@ int hf_set_source(hf_ctx* ctx, int32_t n_tags, const int32_t* tags, double fwhm,
 int hf_get_source(hf_ctx* ctx, double* F);
 int hf_set_source_amplitudes(hf_ctx* ctx, int32_t n_amp, const double* p);
 
+/* Differentiable source: tangent runs under a source, switched on explicitly.
+ * hf_source_derivatives   enable = 1: forms G_f = dF1/dfwhm and G_d = dF1/ddepth on the device (k_source_load_d: the
+ *        unit-capacity element mass applied to s_f = s 2 c_r r^2 / fwhm and s_d = s |z - z0| / depth^2 inside the absorbing
+ *        elements, as F1 is formed from s; bitwise reproducible; rows without an absorbing triangle are exact zeros, and G_d
+ *        is exactly zero for a uniform layer), builds the ascending list of the rows that have an absorbing triangle and
+ *        marks the source differentiable.  enable = 0 frees all of that, and the source columns of a tangent set-up with it.
+ *        hf_set_source, setting or clearing, switches it off, and so does hf_set_mesh.  HF_ERR_STATE: no source, a batch open.
+ * hf_get_source_derivative   copies G_f (which = 0) or G_d (which = 1) out (n doubles); HF_ERR_STATE unless the source is
+ *        differentiable.
+ * While the source is differentiable hf_tangent_setup, hf_tangent_setup_dir and hf_run_tangent accept it; their other refusals
+ * (a load, tables, the steady state, a batch) stay, and hf_run_tangent refuses a set-up with a shape column under a source
+ * (F1 depends on the node positions; that term is not formed).  The primal of hf_run_tangent under a source is bit for bit
+ * hf_run's with the same amplitudes, and it draws on the amplitude list as hf_run does.  Conductivity, capacity and heated-line
+ * columns keep their loads: the source reaches them through u alone.
+ * hf_tangent_set_source   coef = n_steps x nv x 3 doubles, (c0, c1, c2) per step and column (nv: the set-up's padded width):
+ *        step k of hf_run_tangent after the call adds c0 F1 + c1 G_f + c2 G_d to the load of every column that has a non-zero
+ *        entry in some row (kb_source_columns, on the source's rows only; launched only if there is such a column), in the
+ *        units of the other loads: d(p_k F1)/dtheta_j.  n_steps = 0 removes the source columns.  The table is a
+ *        schedule like the amplitudes': the tangents are not reset, so a later run continues them, and the position in the
+ *        table moves with every step hf_run_tangent starts and is rewound by hf_tangent_set_source alone - not by
+ *        hf_set_state, hf_assemble or anything else that resets the tangents, and not by a run that fails mid-way: set the
+ *        table again before the next run, as the amplitudes.  Either set-up, hf_set_source and hf_source_derivatives remove the table.  HF_ERR_STATE: no set-up, a batch
+ *        open, the source not differentiable; HF_ERR_ARG: a non-finite entry.  A run longer than the rows left returns
+ *        HF_ERR_STATE before any step.  hf_tangent_load includes the term with the coefficients of the last step taken, and
+ *        nothing where no step has been taken since the table was set or the tangents were reset. */
+int hf_source_derivatives(hf_ctx* ctx, int32_t enable);
+int hf_get_source_derivative(hf_ctx* ctx, int32_t which, double* out);
+int hf_tangent_set_source(hf_ctx* ctx, int32_t n_steps, const double* coef);
+
 /* Region monitors: after every step, per monitored cell tag t, over the triangles e with tag(e) = t and the
  * nodal state u (A_e the triangle's area in (z, r), r_0..r_2 its nodal radii, rs their sum):
  *     T_max, node_max   the largest nodal value over the nodes of those triangles and the smallest node id that attains it
