@@ -114,6 +114,7 @@ void tangent_free(hf_ctx* ctx) {
   free_batch_state(ctx->tanb);
   dev_free(&ctx->tan.col); dev_free(&ctx->tan.dir); dev_free(&ctx->tan.F);
   dev_free(&ctx->tan.sh.d_v); dev_free(&ctx->tan.ccol); dev_free(&ctx->tan.un); dev_free(&ctx->tan.um1); dev_free(&ctx->tan.scoef);
+  dev_free(&ctx->tan.tkoff); dev_free(&ctx->tan.tcoff); dev_free(&ctx->tan.tkvals); dev_free(&ctx->tan.tcvals);
   ctx->tan = hf_ctx::Tangent();
 }
 
@@ -605,10 +606,11 @@ int tangent_levels(hf_ctx* ctx) {
   return HF_OK;
 }
 
-// u^n and u^{n-1} for the step rate w: held exactly while a shape column or a capacity column is set
+// u^n and u^{n-1} for the step rate w: held exactly while a shape column or a capacity column is set, or table derivatives are on
+// (their load needs w and the evaluation state u*)
 int tangent_rate_buffers(hf_ctx* ctx) {
   hf_ctx::Tangent& T = ctx->tan;
-  if (T.sh.ncol == 0 && T.cmask == 0) {
+  if (T.sh.ncol == 0 && T.cmask == 0 && !ctx->kt.deriv) {
     dev_free(&T.un); dev_free(&T.um1);
     T.wmode = 0;
     T.hist = false;
@@ -650,6 +652,47 @@ int tangent_load_shape(hf_ctx* ctx, RgVariant id) {
                      reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
                      ctx->d_rg_dict, ctx->d_rowptr, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->an.on ? ctx->an.d_m : nullptr, ctx->d_u,
                      ctx->tan.un, bdf2 && ctx->tan.hist ? ctx->tan.um1 : ctx->tan.un, S.d_v, a, ctx->tan.F);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+
+// dynamic LDS of k_tangent_load_T<nv>: coordinates, u, w, u* and nv values of s* per column-list slot, the row offsets and the
+// 16-bit column ids of the block
+size_t tangent_load_T_bytes(const hf_ctx* ctx, int nv) {
+  const size_t capd = static_cast<size_t>(ctx->rg_max_dict);
+  return capd * 16 + 3 * (capd + (capd & 1)) * 8 + capd * nv * 8 + (RBA + 4) * 4 +
+         (static_cast<size_t>((ctx->max_blk_nnz + 1) & ~1) / 8 + 3) * 16;
+}
+
+// The tables' part of the load (k_tangent_load_T<NV>), added to what the kernels before it wrote: persistent
+// workgroups from one occupancy query per mesh, as tangent_load_shape
+template <int NV>
+int tangent_load_T(hf_ctx* ctx, RgVariant id) {
+  const hf_ctx::Tangent& C = ctx->tan;
+  const hf_ctx::KappaT& K = ctx->kt;
+  const hf_ctx::Batch& B = ctx->tanb;
+  const int capd = ctx->rg_max_dict;
+  const size_t sm = tangent_load_T_bytes(ctx, NV);
+  int& grid = ctx->rg_grid[id];
+  if (grid == 0) {
+    const void* fn = reinterpret_cast<const void*>(&k_tangent_load_T<NV>);
+    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
+    int per_cu = 0, ncu = 0;
+    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
+    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
+    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+    if (std::getenv("HEATFLOW_DEBUG"))
+      std::fprintf(stderr, "[tangent tables] k_tangent_load_T<%d>: column list %d slots, %zu B dynamic LDS, %d workgroups per CU, grid %d of %d row blocks\n",
+                   NV, capd, sm, per_cu, grid, ctx->nblk_a);
+  }
+  const bool hist = C.wmode == 2 && C.hist;   // the primal step evaluated at 2 u^n - u^{n-1}
+  hipLaunchKernelGGL(k_tangent_load_T<NV>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr,
+                     reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
+                     ctx->d_rg_dict, ctx->d_rowptr, K.hdr, K.vals, K.c_on ? K.chdr : static_cast<const KTab*>(nullptr), K.cvals,
+                     C.tkoff, C.tkvals, C.tcoff, C.tcvals, ctx->d_u, C.un, hist ? C.um1 : C.un, C.wmode,
+                     ctx->dt /* dt, or dt' = 2/3 dt under BDF2 (hf_assemble) */,
+                     EvalState{C.un, hist ? C.um1 : static_cast<const double*>(nullptr)}, B.u,
+                     hist && B.bdf_hist ? B.uprev : static_cast<const double*>(nullptr), C.F);
   HF_HIP(hipGetLastError());
   return HF_OK;
 }
@@ -724,6 +767,28 @@ int tangent_load(hf_ctx* ctx) {
 #undef HF_TLS
     HF_HIP(hipGetLastError());
   }
+  if (ctx->kt.deriv && ctx->kt.on && ctx->tan.wmode != 0) {   // tables: -(kdot K^1 u + cdot M^1 w) on the tabled tags, every column
+    switch (ctx->tan.nv) {
+      case 2: HF_TRY(tangent_load_T<2>(ctx, RG_TLT2)); break;
+      case 4: HF_TRY(tangent_load_T<4>(ctx, RG_TLT4)); break;
+      case 8: HF_TRY(tangent_load_T<8>(ctx, RG_TLT8)); break;
+      default: HF_TRY(tangent_load_T<16>(ctx, RG_TLT16)); break;
+    }
+  }
+  return HF_OK;
+}
+
+// What hf_tangent_setup / hf_tangent_setup_dir / hf_run_tangent refuse while tables are set: everything without
+// hf_table_derivatives (the texts of before), and with it a source and a mesh whose k_tangent_load_T footprint exceeds the LDS
+int tangent_tables_ok(hf_ctx* ctx, const char* fn, int n_par) {
+  if (!ctx->kt.on) return HF_OK;
+  if (!ctx->kt.deriv) return fail(ctx, HF_ERR_STATE, "%s: %s tables are set (tangents of the nonlinear loop are not supported)", fn, kt_kind(ctx));
+  if (ctx->src.on)
+    return fail(ctx, HF_ERR_STATE, "%s: a source is set and table derivatives are on (hf_set_source, hf_table_derivatives; tangents of sourced runs under tables are not supported)", fn);
+  const int nv = n_par <= 2 ? 2 : n_par <= 4 ? 4 : n_par <= 8 ? 8 : 16;
+  const size_t bytes = tangent_load_T_bytes(ctx, nv) + 2 * 64 * sizeof(KTab);
+  if (n_par > 0 && bytes > 160 * 1024)
+    return fail(ctx, HF_ERR_ARG, "%s: the staged states of k_tangent_load_T<%d> on this mesh need %zu B, more than the 160 KiB of LDS", fn, nv, bytes);
   return HF_OK;
 }
 
@@ -1092,6 +1157,7 @@ int kt_set_tables(hf_ctx* ctx, bool cap, int32_t n_tab, const int32_t* tags, con
   if (n_tab < 0) return fail(ctx, HF_ERR_ARG, "%s: negative table count", fn);
   HF_HIP(hipSetDevice(ctx->dev));
   hf_ctx::KappaT& K = ctx->kt;
+  K.deriv = false;   // hf_table_derivatives belongs to the tables it was switched on under
   if (n_tab == 0) {   // clear: without tables of the other kind every path is the constant-coefficient one again
     if (ctx->steady.picard) ctx->steady.ready = false;   // a Picard steady set-up belongs to the tables it was valued with
     if (cap ? K.c_on : K.k_on) {
@@ -1105,6 +1171,7 @@ int kt_set_tables(hf_ctx* ctx, bool cap, int32_t n_tab, const int32_t* tags, con
       HF_HIP(copy_sync(ctx, cap ? K.chdr : K.hdr, none.data(), sizeof(KTab) * 64, hipMemcpyHostToDevice));
       dev_free(cap ? &K.cvals : &K.vals);
       (cap ? K.ctabled : K.tabled).clear();
+      (cap ? K.h_chdr : K.h_hdr).clear();
       (cap ? K.c_on : K.k_on) = false;
       K.have_change = false;
     }
@@ -1159,6 +1226,7 @@ int kt_set_tables(hf_ctx* ctx, bool cap, int32_t n_tab, const int32_t* tags, con
   HF_HIP(copy_sync(ctx, cap ? K.chdr : K.hdr, hdr.data(), sizeof(KTab) * 64, hipMemcpyHostToDevice));
   HF_HIP(copy_sync(ctx, dvals, vals.data(), sizeof(double) * vals.size(), hipMemcpyHostToDevice));
   (cap ? K.ctabled : K.tabled) = std::move(tabled);
+  (cap ? K.h_chdr : K.h_hdr) = std::move(hdr);
   (cap ? K.c_on : K.k_on) = true;
   K.on = true;
   K.have_change = false;
@@ -1187,6 +1255,7 @@ int hf_set_picard(hf_ctx* ctx, int32_t sweeps) {
   if (sweeps < 1 || sweeps > KT_MAX_PICARD) return fail(ctx, HF_ERR_ARG, "hf_set_picard: sweeps %d outside 1..%d", sweeps, KT_MAX_PICARD);
   if (!ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_set_picard: no tables are set (hf_set_kappa_tables / hf_set_rhoc_tables first)");
   ctx->kt.picard = sweeps;
+  ctx->kt.deriv = false;
   return HF_OK;
 }
 
@@ -1534,7 +1603,7 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
 int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup before hf_set_mesh");
-  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: %s tables are set (tangents of the nonlinear loop are not supported)", kt_kind(ctx));
+  HF_TRY(tangent_tables_ok(ctx, "hf_tangent_setup", n_par >= 1 && n_par <= NV_MAX ? n_par : 0));
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a batch is open");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a load is set (tangents of pre-heated runs are not supported)");
   if (ctx->src.on && !ctx->src.diff) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a source is set (hf_set_source; tangents of sourced runs are not supported)");
@@ -1546,6 +1615,8 @@ int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
     if (tag_col[t] < -1 || tag_col[t] >= n_par)
       return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tag %d maps to column %d outside [-1,%d)", t, tag_col[t], n_par);
     if (tag_col[t] >= 0 && !ctx->h_tag_used[t]) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tag %d is not a cell tag of the mesh", t);
+    if (tag_col[t] >= 0 && ctx->kt.k_on && ctx->kt.tabled[t])
+      return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tag %d carries a conductivity table (its parameters enter through hf_tangent_set_tables, not through a conductivity column)", t);
   }
   if (!ctx->rg_ok || (ctx->assembled && ctx->mode != HF_ASM_ROW_GATHER))
     return fail(ctx, HF_ERR_ARG, "hf_tangent_setup: tangent loads are formed by the row-gather kernel only (HF_ASM_ROW_GATHER on a mesh with row-gather lists)");
@@ -1575,7 +1646,7 @@ int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
 int hf_tangent_setup_dir(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col_k, const int32_t* tag_col_r, const int32_t* tag_col_z) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir before hf_set_mesh");
-  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: %s tables are set (tangents of the nonlinear loop are not supported)", kt_kind(ctx));
+  HF_TRY(tangent_tables_ok(ctx, "hf_tangent_setup_dir", n_par >= 1 && n_par <= NV_MAX ? n_par : 0));
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a batch is open");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a load is set (tangents of pre-heated runs are not supported)");
   if (ctx->src.on && !ctx->src.diff) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a source is set (hf_set_source; tangents of sourced runs are not supported)");
@@ -1589,6 +1660,8 @@ int hf_tangent_setup_dir(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col_k, c
       if (c < -1 || c >= n_par)
         return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: tag %d maps its %s to column %d outside [-1,%d)", t, names[q], c, n_par);
       if (c >= 0 && !ctx->h_tag_used[t]) return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: tag %d is not a cell tag of the mesh", t);
+      if (c >= 0 && ctx->kt.k_on && ctx->kt.tabled[t])
+        return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: tag %d carries a conductivity table (its parameters enter through hf_tangent_set_tables, not through a %s column)", t, names[q]);
     }
     if (tag_col_k && tag_col_k[t] >= 0 && ((tag_col_r && tag_col_r[t] >= 0) || (tag_col_z && tag_col_z[t] >= 0)))
       return fail(ctx, HF_ERR_ARG, "hf_tangent_setup_dir: tag %d has a kappa column and a directional one (k_r = m_r kappa and k_z = m_z kappa are not independent of kappa)", t);
@@ -1633,6 +1706,8 @@ int hf_tangent_set_shape(hf_ctx* ctx, int32_t j, const double* vz) {
   if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_shape before hf_tangent_setup / hf_tangent_setup_dir");
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_shape: a batch is open");
   if (j < 0 || j >= ctx->tan.npar) return fail(ctx, HF_ERR_ARG, "hf_tangent_set_shape: column %d outside [0,%d)", j, ctx->tan.npar);
+  if (vz && ctx->kt.on && ctx->kt.deriv)
+    return fail(ctx, HF_ERR_STATE, "hf_tangent_set_shape: table derivatives are on (hf_table_derivatives; shape columns under tables are not supported)");
   hf_ctx::Tangent::Shape& S = ctx->tan.sh;
   const size_t n = static_cast<size_t>(ctx->n);
   int slot = -1;
@@ -1688,6 +1763,8 @@ int hf_tangent_set_capacity(hf_ctx* ctx, int32_t tab_len, const int32_t* tag_col
         return fail(ctx, HF_ERR_ARG, "hf_tangent_set_capacity: tag %d maps its rho_c to column %d outside [-1,%d)", t, c, T.npar);
       if (c >= 0 && (t >= ctx->tab_len || !ctx->h_tag_used[t]))
         return fail(ctx, HF_ERR_ARG, "hf_tangent_set_capacity: tag %d is not a cell tag of the mesh", t);
+      if (c >= 0 && ctx->kt.deriv && ctx->kt.c_on && ctx->kt.ctabled[t])
+        return fail(ctx, HF_ERR_ARG, "hf_tangent_set_capacity: tag %d carries a capacity table (its parameters enter through hf_tangent_set_tables, not through a capacity column)", t);
       if (c >= 0) mask |= 1u << c;
     }
   HF_HIP(hipSetDevice(ctx->dev));
@@ -1709,6 +1786,62 @@ int hf_tangent_set_capacity(hf_ctx* ctx, int32_t tab_len, const int32_t* tag_col
   return tangent_reset(ctx);   // the tangents belonged to the old parameters
 }
 
+int hf_table_derivatives(hf_ctx* ctx, int32_t enable) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_table_derivatives: no tables are set (hf_set_kappa_tables / hf_set_rhoc_tables first)");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_table_derivatives: a batch is open");
+  const bool on = enable != 0;
+  if (on == ctx->kt.deriv) return HF_OK;
+  HF_HIP(hipSetDevice(ctx->dev));
+  const bool from_steady = ctx->tan.steady_state;
+  tangent_free(ctx);   // a set-up made under the other setting was checked against other rules
+  ctx->tan.steady_state = from_steady;
+  ctx->kt.deriv = on;
+  return HF_OK;
+}
+
+int hf_tangent_set_tables(hf_ctx* ctx, int32_t kind, int32_t n_entries, const int32_t* column, const int32_t* tag, const double* values) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_tables before hf_tangent_setup / hf_tangent_setup_dir");
+  if (!ctx->kt.on || !ctx->kt.deriv) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_tables: table derivatives are off (hf_table_derivatives first)");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_tables: a batch is open");
+  if (kind != 0 && kind != 1) return fail(ctx, HF_ERR_ARG, "hf_tangent_set_tables: kind %d (0 = conductivity, 1 = rho_c)", kind);
+  if (n_entries < 0 || (n_entries > 0 && (!column || !tag || !values))) return fail(ctx, HF_ERR_ARG, "hf_tangent_set_tables: negative entry count or null pointer");
+  hf_ctx::Tangent& T = ctx->tan;
+  const hf_ctx::KappaT& K = ctx->kt;
+  const bool cap = kind == 1;
+  const char* what = cap ? "capacity" : "conductivity";
+  const std::vector<char>& tabled = cap ? K.ctabled : K.tabled;
+  const std::vector<KTab>& hdr = cap ? K.h_chdr : K.h_hdr;
+  std::vector<int32_t> off(static_cast<size_t>(64) * T.nv, -1);
+  size_t total = 0;
+  for (int32_t e = 0; e < n_entries; ++e) {
+    const int32_t tg = tag[e], c = column[e];
+    if (tg < 0 || tg >= static_cast<int32_t>(tabled.size()) || !tabled[tg])
+      return fail(ctx, HF_ERR_ARG, "hf_tangent_set_tables: tag %d carries no %s table", tg, what);
+    if (c < 0 || c >= T.npar) return fail(ctx, HF_ERR_ARG, "hf_tangent_set_tables: column %d outside [0,%d)", c, T.npar);
+    const size_t q = std::find(ctx->h_rg_tags.begin(), ctx->h_rg_tags.end(), tg) - ctx->h_rg_tags.begin();
+    if (q >= 64 || q >= hdr.size() || hdr[q].n <= 0) return fail(ctx, HF_ERR_ARG, "hf_tangent_set_tables: tag %d carries no %s table", tg, what);
+    if (off[q * T.nv + c] >= 0) return fail(ctx, HF_ERR_ARG, "hf_tangent_set_tables: column %d, tag %d listed twice", c, tg);
+    for (int k = 0; k < hdr[q].n; ++k)
+      if (!std::isfinite(values[total + k]))
+        return fail(ctx, HF_ERR_ARG, "hf_tangent_set_tables: value %d of column %d, tag %d is not finite", k, c, tg);
+    off[q * T.nv + c] = static_cast<int32_t>(total);
+    total += static_cast<size_t>(hdr[q].n);
+  }
+  HF_HIP(hipSetDevice(ctx->dev));
+  int32_t*& doff = cap ? T.tcoff : T.tkoff;
+  double*& dval = cap ? T.tcvals : T.tkvals;
+  dev_free(&doff); dev_free(&dval);
+  if (n_entries > 0) {
+    HF_TRY(dev_alloc(ctx, &doff, off.size()));
+    HF_TRY(dev_alloc(ctx, &dval, total));
+    HF_HIP(copy_sync(ctx, doff, off.data(), sizeof(int32_t) * off.size(), hipMemcpyHostToDevice));
+    HF_HIP(copy_sync(ctx, dval, values, sizeof(double) * total, hipMemcpyHostToDevice));
+  }
+  return tangent_reset(ctx);   // the tangents belonged to the old parameters
+}
+
 int hf_tangent_load(hf_ctx* ctx, int32_t j, double* F) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_tangent_load before hf_tangent_setup / hf_tangent_setup_dir");
@@ -1726,7 +1859,14 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
                    int32_t ns, const int32_t* nodes, double* samples, int32_t* iters, double* tangent_samples, int32_t* tangent_iters) {
   if (!ctx) return HF_ERR_ARG;
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a batch is open");
-  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: %s tables are set (tangents of the nonlinear loop are not supported)", kt_kind(ctx));
+  HF_TRY(tangent_tables_ok(ctx, "hf_run_tangent", 0));
+  const bool tables = ctx->kt.on && ctx->kt.deriv;
+  if (tables && ctx->kt.picard > 1)
+    return fail(ctx, HF_ERR_STATE, "hf_run_tangent: %d Picard sweeps per step are set (hf_set_picard; table derivatives cover the lagged scheme, one sweep)", ctx->kt.picard);
+  if (tables && ctx->mon.on && ctx->mon.tan_on)
+    return fail(ctx, HF_ERR_STATE, "hf_run_tangent: monitor tangents are on (hf_set_monitor_tangents; monitor derivatives under tables are not supported)");
+  if (tables && (ctx->tan.sh.ncol > 0 || ctx->tan.smask != 0))
+    return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a column has a shape or a source part (shape and source columns under tables are not supported)");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a load is set (tangents of pre-heated runs are not supported)");
   if (ctx->src.on && !ctx->src.diff) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a source is set (hf_set_source; tangents of sourced runs are not supported)");
   if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_run_tangent before hf_tangent_setup");
@@ -1765,13 +1905,15 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
   HF_TRY(ensure_batch_cols(ctx, nv));     // (a sweep since the last run may have laid the tables out for another width)
   T.lds = ctx->bcols.nv == nv;
   HF_TRY(tangent_levels(ctx));
+  if (tables) HF_TRY(tangent_rate_buffers(ctx));
+  T.noproj = tables;
   HF_TRY(monitor_room(ctx, n_steps));
   HF_TRY(montan_room(ctx, nv, n_steps));
   const bool mon_tan = ctx->mon.on && ctx->mon.tan_on;
   int rc = HF_OK;
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   for (int32_t s = 0; s < n_steps && rc == HF_OK; ++s) {
-    if (ctx->tan.sh.ncol > 0 || ctx->tan.cmask != 0) {   // shape and capacity columns: their load needs u^n and (BDF2) u^{n-1} after the step has moved the buffers
+    if (ctx->tan.sh.ncol > 0 || ctx->tan.cmask != 0 || tables) {   // shape and capacity columns, table derivatives: their load needs u^n and (BDF2) u^{n-1} after the step has moved the buffers
       hf_ctx::Tangent& S = ctx->tan;
       const bool bdf2 = ctx->scheme == HF_TIME_BDF2;
       S.hist = bdf2 && ctx->bdf_hist;
@@ -2208,6 +2350,8 @@ int hf_tangent_set_source(hf_ctx* ctx, int32_t n_steps, const double* coef) {
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_source: a batch is open");
   if (!ctx->src.on || !ctx->src.diff)
     return fail(ctx, HF_ERR_STATE, "hf_tangent_set_source: the source is not differentiable (hf_set_source, then hf_source_derivatives)");
+  if (ctx->kt.on && ctx->kt.deriv)
+    return fail(ctx, HF_ERR_STATE, "hf_tangent_set_source: table derivatives are on (hf_table_derivatives; source columns under tables are not supported)");
   if (n_steps < 0 || (n_steps > 0 && !coef)) return fail(ctx, HF_ERR_ARG, "hf_tangent_set_source: %d steps or a null pointer", n_steps);
   hf_ctx::Tangent& T = ctx->tan;
   const size_t len = static_cast<size_t>(n_steps) * T.nv * 3;

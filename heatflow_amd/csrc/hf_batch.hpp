@@ -1288,7 +1288,8 @@ struct BatchOps {
                            ctx->d_lift_ptr, ctx->d_lift_bc, Liftop(ctx), g_dev, B.b);
       }
     }
-    const ProjVecs act = proj_active(B);
+    ProjVecs act = proj_active(B);
+    if (B.noproj) act.m = 0;   // another operator every step: the columns start from s^n with their boundary values set
     // set_bc once: after the combination when there is one (the basis vectors are zero on the Dirichlet rows)
     if (nb > 0 && act.m == 0)
       hipLaunchKernelGGL((kb_set_bc<NV>), dim3((nb * NV + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, g_dev, B.b, B.u);
@@ -1303,7 +1304,7 @@ struct BatchOps {
     }
     const bool use_amg = ctx->precond == 1 && ctx->amg_ready;
     const int rc = pcg(ctx, use_amg, rtol, atol, max_it);
-    if (rc == HF_OK) {   // (solution with zeroed Dirichlet entries, right-hand side) joins every column's basis
+    if (rc == HF_OK && !B.noproj) {   // (solution with zeroed Dirichlet entries, right-hand side) joins every column's basis
       const int slot = B.pnext;
       hipLaunchKernelGGL(k_copy2, dim3(1024), dim3(TPB), 0, ctx->stream, ctx->n * NV, B.u, B.pV[slot], B.b, B.pF[slot]);
       if (nb > 0)

@@ -107,7 +107,7 @@ struct TanDir { int32_t c_r, c_z; double w_r, w_z; };
 
 // The row-gather assembly kernels: k_assemble_rows<false / true>, k_assemble_rows_an<false / true>, k_assemble_rows_kT,
 // k_assemble_rows_cT, k_assemble_rows_kT_K
-enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_SOURCE, RG_SOURCE_D, RG_SHAPE1, RG_SHAPE2, RG_SHAPE4, RG_VARIANTS };
+enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_SOURCE, RG_SOURCE_D, RG_SHAPE1, RG_SHAPE2, RG_SHAPE4, RG_TLT2, RG_TLT4, RG_TLT8, RG_TLT16, RG_VARIANTS };
 
 }  // namespace
 
@@ -374,6 +374,7 @@ struct hf_ctx {
     unsigned loaded = 0;         // bit j: column j's operator has been loaded (percol)
     bool lds = false;            // fine-pattern products through kb_spmv_lds (the context's `bcols` tables are for this nv)
     const double* load = nullptr;   // per-column load F (interleaved): b = M u + dt F (the tangent stage); null: b = M u
+    bool noproj = false;         // the operator changes from step to step (tangent runs under tables): the ring is neither combined from nor stored into
   } batch;
   // compressed columns of the batched loop's LDS-staged SpMV (BComp in hf_batch.hpp): per chunk of `rpc` rows a sorted
   // column list and per nonzero a 16-bit position in it; built on the first hf_batch_begin with a given nv, kept per mesh
@@ -420,6 +421,11 @@ struct hf_ctx {
     int ssteps = 0, snext = 0;       // rows of the table; the row the next step of hf_run_tangent uses
     int scur = -1;                   // the row of the last step taken (-1: none since the table was set or the tangents were reset)
     unsigned smask = 0;              // bit j: column j has a non-zero coefficient in some row
+    // derivative tables (hf_tangent_set_tables): per kind a [64][nv] table of offsets into the values (by
+    // tag-dictionary index and column, -1 = none).  Nothing is allocated while no entry of the kind is set; k_tangent_load_T<nv>
+    // runs exactly while hf_table_derivatives is on.
+    int32_t *tkoff = nullptr, *tcoff = nullptr;
+    double *tkvals = nullptr, *tcvals = nullptr;
   } tan;
   int fsamp_cap = 0;
   // temperature-dependent conductivities (hf_set_kappa_tables): per row-gather tag-dictionary entry a table header (KTab,
@@ -440,6 +446,10 @@ struct hf_ctx {
     double *pic = nullptr, *b0 = nullptr;   // evaluation state of the last sweep (for the change), b before lifting (sweeps > 1)
     unsigned long long* change = nullptr;   // max |u^{n+1,p} - u^{n+1,p-1}| of the last step's last sweep (bits of a double >= 0)
     bool have_change = false;
+    // hf_table_derivatives: tangent runs of the lagged scheme are allowed; host copies of both header arrays
+    // (by tag-dictionary index), which hf_tangent_set_tables sizes its entries by
+    bool deriv = false;
+    std::vector<KTab> h_hdr, h_chdr;
   } kt;
   // optional in-situ kernel timing (hf_set_profile): event pairs around each PCG SpMV launch
   bool prof = false;

@@ -1087,6 +1087,133 @@ struct EvalState {
   }
 };
 
+// d table / dT at T: the slope of the segment ktab_eval takes, branch for branch; 0 in both clamped ranges
+__device__ __forceinline__ double ktab_slope(const KTab h, const double* __restrict__ vals, double T) {
+#pragma clang fp contract(off)
+  const double s = (T - h.t0) * h.inv_dt;
+  if (!(s > 0.0)) return 0.0;
+  if (s >= static_cast<double>(h.n - 1)) return 0.0;
+  const int i = min(static_cast<int>(s), h.n - 2);
+  return (vals[h.off + i + 1] - vals[h.off + i]) * h.inv_dt;
+}
+
+// k_tangent_load_cap's sibling for tangent runs under kappa(T) / rho_c(T) tables (hf_table_derivatives; same lists,
+// block staging and launch geometry).  On every triangle e of a tabled tag, with T_e the element temperature of the evaluation state
+// u* the primal step valued its operators at (element_temperature: the assembly's bits) and sigma_j = the mean of column j's s* over
+// the triangle's nodes (s* formed from s^n, s^{n-1} as u* from u^n, u^{n-1}),
+//   F[i * NV + j] -= kdot_j (K^1_e u)_i + cdot_j (M^1_e w)_i,
+//   kdot_j = D^k_{j,tag}(T_e) + kappa'_tag(T_e) sigma_j,   cdot_j = D^c_{j,tag}(T_e) + rho_c'_tag(T_e) sigma_j,
+// K^1_e and M^1_e the element matrices at unit coefficients (one element_row), u = u^{n+1} and w the step rate as
+// k_tangent_load_cap forms it.  D: a derivative table on the tag's own grid (hf_tangent_set_tables), found through koff / coff
+// ([64][NV] offsets into dkvals / dcvals by tag-dictionary index and column, -1 = none; a null array: none of that kind) and evaluated by ktab_eval.  Next to the
+// coordinates the block's column nodes get u, w, u* and the NV values of s*.  Triangles of untabled tags are skipped before any
+// arithmetic, rows that meet none are not written.  Each column's sum runs in list order in a register of the row's lane - no
+// atomics, bitwise reproducible.  ctab == nullptr: no capacity tables.
+template <int NV>
+__global__ __launch_bounds__(RBA) void k_tangent_load_T(int nblk, int capd, const int4* __restrict__ hdr, const uint4* __restrict__ ell,
+                                                        const uint4* __restrict__ cid16, const double2* __restrict__ zrb,
+                                                        const int32_t* __restrict__ dict, const int32_t* __restrict__ rowptr,
+                                                        const KTab* __restrict__ ktab, const double* __restrict__ kvals,
+                                                        const KTab* __restrict__ ctab, const double* __restrict__ cvals,
+                                                        const int32_t* __restrict__ koff, const double* __restrict__ dkvals,
+                                                        const int32_t* __restrict__ coff, const double* __restrict__ dcvals,
+                                                        const double* __restrict__ u, const double* __restrict__ un,
+                                                        const double* __restrict__ um1, int wmode, double dtp, EvalState state,
+                                                        const double* __restrict__ s, const double* __restrict__ sprev,
+                                                        double* __restrict__ F) {
+  extern __shared__ double smem[];
+  __shared__ KTab sK[64], sCt[64];
+  const int capw = capd + (capd & 1);
+  double2* sXd = reinterpret_cast<double2*>(smem);
+  double* sU = smem + 2 * capd;
+  double* sW = sU + capw;
+  double* sE = sW + capw;
+  double* sS = sE + capw;
+  int* sR = reinterpret_cast<int*>(sS + static_cast<size_t>(capd) * NV);
+  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);
+  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
+  const int t = threadIdx.x;
+  if (t < 64) {
+    sK[t] = ktab[t];
+    sCt[t] = ctab ? ctab[t] : KTab{0.0, 0.0, 0, 0};
+  }
+  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const int4 cA = hdr[2 * blk], cB = hdr[2 * blk + 1];
+    const int c0 = cA.x >> 3, nc = ((cA.x + cA.y + 7) >> 3) - c0;
+    for (int i = t; i < nc; i += RBA) sC4[i] = cid16[c0 + i];
+    for (int i = t; i < cA.w; i += RBA) {
+#pragma clang fp contract(off)
+      const int node = dict[cA.z + i];
+      const double u1 = u[node];
+      sXd[i] = zrb[cA.z + i];
+      sU[i] = u1;
+      double w = 0.0;
+      if (wmode == 1) w = (u1 - un[node]) / dtp;
+      else if (wmode == 2) w = ((u1 - (4.0 / 3.0) * un[node]) + (1.0 / 3.0) * um1[node]) / dtp;
+      sW[i] = w;
+      sE[i] = state(node);
+#pragma unroll
+      for (int j = 0; j < NV; ++j) {
+        const double sj = s[static_cast<size_t>(node) * NV + j];
+        sS[i * NV + j] = sprev ? 2.0 * sj - sprev[static_cast<size_t>(node) * NV + j] : sj;
+      }
+    }
+    if (t < cB.w) sR[t] = rowptr[blk * RBA + t] - cA.x;
+    __syncthreads();
+    if (t < cB.w) {
+#pragma clang fp contract(off)
+      const int sbase = sR[t] + (cA.x & 7);
+      const int ci = cB.z + t;
+      const double2 Pi = sXd[ci];
+      const double ui = sU[ci], wi = sW[ci], ei = sE[ci];
+      double acc[NV];
+#pragma unroll
+      for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+      bool any = false;
+      for (int g = 0; g < cB.y; ++g) {
+        const uint4 ev = ell[cB.x + g * RBA + t];
+        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
+          if (e == 0xFFFFu) continue;
+          const int tg = e >> 10;
+          const KTab kh = sK[tg], ch = sCt[tg];
+          if (kh.n <= 0 && ch.n <= 0) continue;
+          any = true;
+          const int pj = sC[sbase + (e & 31u)], pk = sC[sbase + ((e >> 5) & 31u)];
+          const double Te = element_temperature(sE, ei, pj, pk);
+          const ElemRow r = element_row(Pi, sXd[pj], sXd[pk], 1.0, 1.0);
+          const double ku = (r.k0 * ui + r.k1 * sU[pj]) + r.k2 * sU[pk];
+          const double mw = (r.m0 * wi + r.m1 * sW[pj]) + r.m2 * sW[pk];
+          const double kslope = kh.n > 0 ? ktab_slope(kh, kvals, Te) : 0.0;
+          const double cslope = ch.n > 0 ? ktab_slope(ch, cvals, Te) : 0.0;
+#pragma unroll
+          for (int j = 0; j < NV; ++j) {
+            const double sigma = ((sS[ci * NV + j] + sS[pj * NV + j]) + sS[pk * NV + j]) * (1.0 / 3.0);
+            double kd = kslope * sigma, cd = cslope * sigma;
+            if (kh.n > 0) {
+              const int o = koff ? koff[tg * NV + j] : -1;
+              if (o >= 0) kd += ktab_eval(KTab{kh.t0, kh.inv_dt, kh.n, o}, dkvals, Te);
+            }
+            if (ch.n > 0) {
+              const int o = coff ? coff[tg * NV + j] : -1;
+              if (o >= 0) cd += ktab_eval(KTab{ch.t0, ch.inv_dt, ch.n, o}, dcvals, Te);
+            }
+            acc[j] += kd * ku + cd * mw;
+          }
+        }
+      }
+      if (any) {
+        double* out = F + static_cast<size_t>(blk * RBA + t) * NV;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) out[j] -= acc[j];
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // A = M + dt K(kappa(T)) at u* in a one-value slab: M does not change, only A is written.
 struct RowsKappaT {
   static constexpr bool PAIR = false, STATE = true, KONLY = false, NODE_FIRST = true;

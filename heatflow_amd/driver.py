@@ -43,7 +43,8 @@ from .bc import P1Space, RowDirichletBC
 from .geometry import check_thickness_name, stack_no_diamond, stack_with_diamond, thickness_velocity
 from .heating import HeatingCurve
 from .aniso import CAPACITY_KINDS, DIRECTIONAL_HINT, capacity_scale, check_capacity_names, check_config, refuse_aniso, split_param
-from .kappa_t import material_cv_table, material_table, picard_sweeps, refuse_tables
+from .kappa_t import (check_table_tangents, material_cv_table, material_table, picard_sweeps, refuse_tables, table_param,
+                      table_tangents)
 from .mesh import Mesh, load_mesh_arrays
 from .monitors import (check_sigma, parse_monitors, problem_monitors, refuse_monitors, uncertainty as monitor_uncertainty,
                        used_config as monitors_used_config, write_monitors_csv, write_uncertainty_csv)
@@ -570,8 +571,23 @@ class SimulationSession:
         tag_to_k, tag_to_rc = self._tables(stack)
         scheme = time_scheme(cfg)
         kt = self._kappa_tables(cfg, stack)
-        if kt is not None and tangents:
+        tab_on = kt is not None and bool(tangents) and table_tangents(cfg)   # timing.table_tangents
+        if kt is not None and tangents and not tab_on:
             refuse_tables(cfg, "tangents")
+        if tab_on:
+            if monitor_tangents:
+                raise ValueError(("monitor_sigma" if monitor_sigma is not None else "monitor_tangents")
+                                 + ": monitor derivatives together with timing.table_tangents are not supported")
+            check_table_tangents(cfg, "tangents", tangents)
+            for p in tangents:       # the names of the tables' parameters, before any problem is made
+                try:
+                    tp = None if p == "fwhm" else table_param(cfg, p)
+                except ValueError as e:
+                    raise ValueError(f"tangents: {e}") from None
+                mat, _, suffix = p.rpartition(".")
+                if tp is None and suffix in ("k_r", "k_z") and self.material_tags.get(mat) in kt[0]:
+                    raise ValueError(f"tangents: parameter {p!r}: {mat!r} carries a conductivity table (its parameters are "
+                                     f"{mat}.k or {mat}.k_power.exponent, or {mat}.k_table.scale)")
         an = self._aniso(stack)
         if an and tangents:      # a bare name means the isotropic k: an anisotropic material is named by direction
             refuse_aniso(cfg, "a tangent with respect to the conductivity of an anisotropic material", set(tangents),
@@ -610,9 +626,16 @@ class SimulationSession:
                 check_capacity_names(params)
             except ValueError as e:
                 raise ValueError(f"tangents: {e}") from None
-            cond, bnd, shp, cap, cscale, srcp = [], {}, {}, {}, {}, {}
+            cond, bnd, shp, cap, cscale, srcp, tabs = [], {}, {}, {}, {}, {}, {}
             for j, p in enumerate(params):
-                if p in SOURCE_PARAMS:
+                try:
+                    tp = table_param(cfg, p) if tab_on and p != "fwhm" else None
+                except ValueError as e:
+                    raise ValueError(f"tangents: {e}") from None
+                if tp is not None:       # a parameter of a material's table: a derivative table on the table's own grid
+                    cond.append([])
+                    tabs[j] = {tp[1]: {self.material_tags[tp[0]]: tp[2]}}
+                elif p in SOURCE_PARAMS:
                     cond.append([])
                     srcp[j] = p
                 elif p == "fwhm":
@@ -661,6 +684,7 @@ class SimulationSession:
                                                                     **({"capacity": [cap.get(j, []) for j in range(len(params))]}
                                                                        if cap else {}),
                                                                     **({"monitor_tangents": True} if monitor_tangents else {}),
+                                                                    **({"tables": tabs} if tab_on else {}),
                                                                     **src_kw)
             for j, f in cscale.items():
                 if f != 1.0:

@@ -23,7 +23,8 @@ from .geometry import check_thickness_name, thickness_velocity
 from .parameter_sweep import build_stack, get_watcher_points, oside_curves
 from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, KEY, capacity_scale, check_capacity_names, material_aniso, refuse_aniso,
                     split_param)
-from .kappa_t import refuse_tables
+from .kappa_t import (check_table_tangents, get_table_param, refuse_tables, set_table_param, split_table_param, table_keys,
+                      table_tangents)
 from .source import SOURCE_PARAMS, check_source_param, parse_source, refuse_source_tangents
 from .monitors import refuse_monitors
 
@@ -32,7 +33,11 @@ DEFAULT_EXP_CSV = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(_
 
 
 def _material_param(cfg, name):
-    """(material block, None | "k" | "r" | "z" | "t" | "c" | "cv" | "rho") of a parameter name; ValueError naming it for an unknown material or suffix."""
+    """(material block, None | "k" | "r" | "z" | "t" | "c" | "cv" | "rho") of a parameter name, "table" for a name of
+    kappa_t.TABLE_PARAM_SUFFIXES; ValueError naming it for an unknown material or suffix."""
+    if split_table_param(name) is not None:
+        get_table_param(cfg, name)       # (an unknown material or a missing block: ValueError)
+        return cfg["mats"][split_table_param(name)[0]], "table"
     mat, kind = split_param(name)
     if mat not in cfg["mats"]:
         raise ValueError(f"parameter {name!r}: no material {mat!r} in the configuration")
@@ -67,6 +72,8 @@ def get_param(cfg, name):
             return float(spec.pulse[1 if name.endswith(".t0") else 2])
         return float({"source.power": spec.power, "source.fwhm": spec.fwhm, "source.depth": spec.depth}[name])
     mat, kind = _material_param(cfg, name)
+    if kind == "table":      # "<m>.k_power.exponent", "<m>.cv_einstein.theta", or a table's scale (1 as it stands)
+        return get_table_param(cfg, name)
     if kind in (None, "k"):
         return float(mat["k"])
     if kind == "t":
@@ -98,6 +105,8 @@ def set_params(cfg, params, values):
                 block["pulse"][name.rsplit(".", 1)[1]] = float(v)
             else:
                 block[name.split(".", 1)[1]] = float(v)
+        elif _material_param(c, name)[1] == "table":
+            set_table_param(c, name, v)
         elif _material_param(c, name)[1] in (None, "k"):
             _material_param(c, name)[0]["k"] = float(v)
         elif _material_param(c, name)[1] == "t":
@@ -163,7 +172,11 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
 
     t0 = time.time()
     scheme = time_scheme(cfg)
-    refuse_tables(cfg, "heatflow_amd.fit")
+    tab_on = table_tangents(cfg) and bool(table_keys(cfg))      # timing.table_tangents
+    if tab_on:
+        check_table_tangents(cfg, "heatflow_amd.fit", tuple(params) + tuple(nuisance or ()))
+    else:
+        refuse_tables(cfg, "heatflow_amd.fit")
     refuse_source_tangents(cfg, "heatflow_amd.fit")     # a source fits only under heating.source.tangents: true
     refuse_monitors(cfg, "heatflow_amd.fit")
     params = tuple(params)
@@ -262,6 +275,10 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
         s = session_for(theta)
         w = {nm: tuple(s.coords[i]) for nm, i in zip(w_names, w_nodes)} if thick else watchers
         res = s.run(c, build_stack(c), w, tangents=(params if tangents is True else tuple(tangents)) if tangents else None)
+        if tangents:      # a table's scale: the run differentiates by a multiplier of the table as it stands, theta times the configuration's
+            for j, p in enumerate(params):
+                if p.endswith("_table.scale") and p in res["tangents"]:
+                    res["tangents"][p] = {nm: d / float(theta[j]) for nm, d in res["tangents"][p].items()}
         runs += 1
         tangent_runs += bool(tangents)
         return res

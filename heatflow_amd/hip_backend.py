@@ -40,7 +40,7 @@ EXPORTS = [
     "hf_source_derivatives", "hf_get_source_derivative", "hf_tangent_set_source",
     "hf_set_monitors", "hf_monitor_now", "hf_monitor_count", "hf_get_monitors", "hf_monitor_clear",
     "hf_set_monitor_tangents", "hf_monitor_tangent_count", "hf_get_monitor_tangents", "hf_monitor_tangent_eval",
-    "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_set_shape", "hf_tangent_set_capacity", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
+    "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_set_shape", "hf_tangent_set_capacity", "hf_table_derivatives", "hf_tangent_set_tables", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
     "hf_set_value_lists", "hf_get_value_lists", "hf_get_projection", "hf_get_flux_system",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
@@ -161,6 +161,8 @@ def load_library():
         "hf_tangent_setup_dir": [vp, i32, pi, pi, pi],
         "hf_tangent_set_shape": [vp, i32, pd],
         "hf_tangent_set_capacity": [vp, i32, pi],
+        "hf_table_derivatives": [vp, i32],
+        "hf_tangent_set_tables": [vp, i32, i32, pi, pi, pd],
         "hf_tangent_load": [vp, i32, pd],
         "hf_run_tangent": [vp, i32, pd, pd, dbl, dbl, i32, i32, pi, pd, pi, pd, pi],
         "hf_get_tangent": [vp, i32, pd],
@@ -487,6 +489,28 @@ class HeatflowHIP:
                 raise ValueError(f"tangent_set_capacity: tag {t} is not a cell tag of the mesh")
             tab[int(t)] = int(j)
         self._check(self._lib.hf_tangent_set_capacity(self._ctx, self.tab_len, _pi(tab)))
+
+    def table_derivatives(self, on=True):
+        """Allow tangent runs under kappa(T) / rho_c(T) tables (hf_table_derivatives; lagged scheme, one Picard
+        sweep).  Needs tables; set_kappa_tables, set_rhoc_tables and set_picard switch it off again.  A change drops the tangent
+        set-up."""
+        self._check(self._lib.hf_table_derivatives(self._ctx, 1 if on else 0))
+        self.tangent_nv = 0
+
+    def tangent_set_tables(self, kind, tables):
+        """Derivative tables of the tangent set-up in force (hf_tangent_set_tables): ``kind`` 0 = conductivity,
+        1 = rho_c (or "kappa" / "rhoc"); ``tables`` = {(column, cell tag): values}, d(knot value)/d(parameter of the column) at
+        the knots of the tag's table of that kind.  An empty mapping (or None) clears the kind.  Every tangent starts from zero
+        again."""
+        kind = {"kappa": 0, "rhoc": 1}.get(kind, kind)
+        items = sorted(((int(c), int(t)), np.asarray(v, dtype=np.float64).ravel()) for (c, t), v in (tables or {}).items())
+        if not items:
+            self._check(self._lib.hf_tangent_set_tables(self._ctx, int(kind), 0, None, None, None))
+            return
+        cols = _i32([c for (c, _), _ in items])
+        tags = _i32([t for (_, t), _ in items])
+        vals = _f64(np.concatenate([v for _, v in items]))
+        self._check(self._lib.hf_tangent_set_tables(self._ctx, int(kind), len(items), _pi(cols), _pi(tags), _pd(vals)))
 
     def tangent_set_source(self, coef):
         """Source columns of the tangent set-up in force (hf_tangent_set_source): ``coef`` (n_steps, nv, 3) holds

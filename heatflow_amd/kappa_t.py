@@ -127,3 +127,146 @@ def refuse_tables(cfg, where):
     keys = table_keys(cfg, CV_TABLE_KEYS)
     if keys:
         raise ValueError(f"{where} does not support temperature-dependent heat capacities ({', '.join(keys)})")
+
+
+def table_derivative(mat, name):
+    """(kind, values): the derivative of a material's table with respect to the parameter ``name``, at the table's own knots
+    (DESIGN.md 3.20).  ``mat`` is the material's entry of cfg["mats"], ``kind`` "kappa" or "rhoc" (the keys of
+    HeatProblem.run_tangent's ``tables=``).  The interpolation is linear in the knot values, so the derivative of the table is the
+    table of the knots' derivatives.  Names (``<m>`` = the material):
+      k_power      ``<m>`` / ``<m>.k``: table / k;   ``<m>.k_power.exponent``: table ln(T_ref / T_i)
+      k_table      ``<m>.k_table.scale`` (a multiplier at 1): table
+      cv_einstein  ``<m>.cv`` / ``<m>.rho`` / ``<m>.rho_c``: table / value;   ``<m>.cv_einstein.theta``: the analytic derivative
+      cv_table     ``<m>.cv_table.scale``: table
+    ValueError for a name the material's tables do not depend on this way."""
+    m, _, suffix = str(name).partition(".")
+    if suffix in ("", "k", "k_power.exponent", "k_table.scale"):
+        tab = material_table(m, mat)
+        if tab is None:
+            raise ValueError(f"{name}: material {m} has no conductivity table")
+        T0, dT, v = tab
+        v = np.asarray(v, dtype=np.float64)
+        if "k_table" in mat:
+            if suffix != "k_table.scale":
+                raise ValueError(f"{name}: a k_table material has no k to differentiate; its parameter is {m}.k_table.scale")
+            return "kappa", v.copy()
+        if suffix == "k_table.scale":
+            raise ValueError(f"{name}: material {m} has a k_power table, not a k_table ({m}.k or {m}.k_power.exponent)")
+        if suffix in ("", "k"):
+            return "kappa", v / float(mat["k"])
+        T = T0 + dT * np.arange(v.size)
+        return "kappa", v * np.log(float(mat["k_power"]["T_ref"]) / T)
+    if suffix in ("cv", "rho", "rho_c", "cv_einstein.theta", "cv_table.scale"):
+        tab = material_cv_table(m, mat)
+        if tab is None:
+            raise ValueError(f"{name}: material {m} has no capacity table")
+        T0, dT, v = tab
+        v = np.asarray(v, dtype=np.float64)
+        if "cv_table" in mat:
+            if suffix != "cv_table.scale":
+                raise ValueError(f"{name}: a cv_table material is differentiated through {m}.cv_table.scale only")
+            return "rhoc", v.copy()
+        if suffix == "cv_table.scale":
+            raise ValueError(f"{name}: material {m} has a cv_einstein table, not a cv_table")
+        if suffix in ("cv", "rho"):
+            return "rhoc", v / float(mat[suffix])
+        if suffix == "rho_c":
+            return "rhoc", v / (float(mat["rho"]) * float(mat["cv"]))
+        p = mat["cv_einstein"]
+        T = T0 + dT * np.arange(v.size)
+        dlnE = lambda x: 2.0 / x - 1.0 / np.tanh(0.5 * x)      # d ln E / dx, E = einstein_function
+        theta, T_ref = float(p["theta"]), float(p["T_ref"])
+        return "rhoc", v * (dlnE(theta / T) / T - dlnE(theta / T_ref) / T_ref)
+    raise ValueError(f"{name}: not a table parameter (.k, .k_power.exponent, .k_table.scale, .cv, .rho, .rho_c, "
+                     ".cv_einstein.theta, .cv_table.scale)")
+
+
+# -- tangent runs and fits under tables (timing.table_tangents, DESIGN.md 3.20) -------------------------------------------------
+TABLE_PARAM_SUFFIXES = ("k_power.exponent", "k_table.scale", "cv_einstein.theta", "cv_table.scale")
+
+
+def table_tangents(cfg):
+    """``timing.table_tangents``: the opt-in for tangent runs, fits and budgets of a configuration with tables (default off)."""
+    return bool((cfg.get("timing") or {}).get("table_tangents", False))
+
+
+def split_table_param(name):
+    """("<material>", suffix) of a name that ends in one of TABLE_PARAM_SUFFIXES, None for any other name."""
+    for suffix in TABLE_PARAM_SUFFIXES:
+        if str(name).endswith("." + suffix) and len(name) > len(suffix) + 1:
+            return name[:-len(suffix) - 1], suffix
+    return None
+
+
+def _table_material(cfg, name, mat):
+    mats = cfg.get("mats") or {}
+    if mat not in mats or not isinstance(mats[mat], dict):
+        raise ValueError(f"parameter {name!r}: no material {mat!r} in the configuration")
+    return mats[mat]
+
+
+def table_param(cfg, name):
+    """(material, kind, values) if ``name`` is a parameter of a table of ``cfg`` - one of TABLE_PARAM_SUFFIXES, or a bare material
+    name / ``.k`` of a material with a conductivity table, or ``.cv`` / ``.rho`` / ``.rho_c`` of one with a capacity table -, the
+    derivative table from :func:`table_derivative`; None for a name that no table depends on.  ValueError naming the parameter for
+    a table name on a material without that table."""
+    split = split_table_param(name)
+    if split is not None:
+        mat = split[0]
+        block = _table_material(cfg, name, mat)
+        if split[1].split(".")[0] not in block:
+            raise ValueError(f"parameter {name!r}: material {mat!r} has no {split[1].split('.')[0]} block")
+    else:
+        mat, _, suffix = str(name).partition(".")
+        block = (cfg.get("mats") or {}).get(mat)
+        if not isinstance(block, dict):
+            return None
+        if suffix in ("", "k"):
+            if not any(k in block for k in TABLE_KEYS):
+                return None
+        elif suffix in ("cv", "rho", "rho_c"):
+            if not any(k in block for k in CV_TABLE_KEYS):
+                return None
+        else:
+            return None
+    kind, values = table_derivative(block, name)
+    return mat, kind, values
+
+
+def get_table_param(cfg, name):
+    """The value of a name of TABLE_PARAM_SUFFIXES: the exponent, theta, or 1 for a scale (a multiplier of the table as it stands)."""
+    mat, suffix = split_table_param(name)
+    block = _table_material(cfg, name, mat)
+    key, field = suffix.split(".")
+    if key not in block:
+        raise ValueError(f"parameter {name!r}: material {mat!r} has no {key} block")
+    return 1.0 if field == "scale" else float(block[key][field])
+
+
+def set_table_param(cfg, name, value):
+    """Write a name of TABLE_PARAM_SUFFIXES into ``cfg`` (in place): the exponent or theta as given, a scale as the scaled list."""
+    mat, suffix = split_table_param(name)
+    block = _table_material(cfg, name, mat)
+    key, field = suffix.split(".")
+    if key not in block:
+        raise ValueError(f"parameter {name!r}: material {mat!r} has no {key} block")
+    if field == "scale":
+        lst = "k" if key == "k_table" else "cv"
+        block[key][lst] = [float(value) * float(v) for v in block[key][lst]]
+    else:
+        block[key][field] = float(value)
+
+
+def check_table_tangents(cfg, where, names=()):
+    """The refusals that stay under ``timing.table_tangents: true``: ValueError naming the argument for more than one Picard sweep, a
+    volumetric source and a layer thickness among ``names``."""
+    if picard_sweeps(cfg) > 1:
+        raise ValueError(f"{where}: timing.picard_sweeps = {picard_sweeps(cfg)} (timing.table_tangents covers the lagged scheme, "
+                         "picard_sweeps: 1)")
+    if isinstance(cfg.get("heating"), dict) and cfg["heating"].get("source") is not None:
+        raise ValueError(f"{where}: heating.source together with timing.table_tangents is not supported")
+    for p in names:
+        if str(p).endswith(".thickness"):
+            raise ValueError(f"{where}: parameter {p!r}: a layer thickness together with timing.table_tangents is not supported")
+        if str(p).startswith("source."):
+            raise ValueError(f"{where}: parameter {p!r}: a source parameter together with timing.table_tangents is not supported")

@@ -259,7 +259,7 @@ class HeatProblem:
         return times, samples, iters
 
     def run_tangent(self, num_steps, watcher_nodes, conductivity=(), boundary=None, time_varying=None, first_step=0, shape=None,
-                    capacity=(), monitor_tangents=False, source_amplitude=None, source=None):
+                    capacity=(), monitor_tangents=False, source_amplitude=None, source=None, tables=None):
         """:meth:`run` plus the derivatives of the watcher curves with respect to parameters theta_j (hf_run_tangent,
         DESIGN.md 3.7).  Column j of ``conductivity`` = the cell tags whose conductivity theta_j is (they move together).  An
         entry may also be a pair ``(tag, "k" | "r" | "z")``: the tag's kappa (both directions of an anisotropic
@@ -284,7 +284,14 @@ class HeatProblem:
         problem with a source is refused as before), and gives the source columns: {column: {"amplitude": c0, "fwhm": c1, "depth":
         c2}}, each one value per step or a callable of time (missing: 0), adds c0 F1 + c1 G_f + c2 G_d = d(p_k F1)/dtheta_j to the
         column's load at step k (heatflow_amd.source.tangent_coefficients gives them for the source's own parameters).
-        ``source_amplitude`` has the meaning it has in :meth:`run`.  Shape columns under a source are refused.  Returns (times, samples, tangent samples (n_steps, n_par, n_s), iters, tangent iters
+        ``source_amplitude`` has the meaning it has in :meth:`run`.  Shape columns under a source are refused.  ``tables``
+        (needs ``kappa_tables=`` or ``rhoc_tables=`` on the problem, one Picard sweep) allows the tangent run under
+        the tables (``{}`` is enough; without the keyword a problem with tables is refused as before) and gives the columns their
+        derivative tables: {column: {"kappa": {cell tag: values}, "rhoc": {cell tag: values}}}, values = d(knot value)/dtheta_j at
+        the knots of the tag's table (heatflow_amd.kappa_t.table_derivative gives them for the parameters of a material).  Every
+        column, with or without such a table, feels the tables through the coupling term kappa'(T) s.  Conductivity columns on
+        tags with a conductivity table, capacity columns on tags with a capacity table, shape columns, a source and
+        ``monitor_tangents`` are refused under ``tables``.  Returns (times, samples, tangent samples (n_steps, n_par, n_s), iters, tangent iters
         (n_steps, n_par))."""
         if monitor_tangents and not self.monitors:
             raise ValueError("run_tangent: monitor_tangents needs monitors (HeatProblem(..., monitors=))")
@@ -307,6 +314,26 @@ class HeatProblem:
         if source is not None and shape:
             raise ValueError("run_tangent: shape columns under a source are not supported (the source's load depends on the "
                              "node positions)")
+        if tables is not None and not (self.kappa_tables or self.rhoc_tables):
+            raise ValueError("run_tangent: tables= needs tables (HeatProblem(..., kappa_tables= / rhoc_tables=))")
+        if tables is not None and self.picard > 1:
+            raise ValueError(f"run_tangent: tables= covers the lagged scheme only (picard = 1, not {self.picard})")
+        if tables is not None and (shape or source is not None or monitor_tangents):
+            raise ValueError("run_tangent: tables= together with " + ("shape" if shape else "source" if source is not None
+                                                                      else "monitor_tangents") + " is not supported")
+        tab_cols = {0: {}, 1: {}}
+        for j, kinds in (tables or {}).items():
+            unknown = sorted(set(kinds) - {"kappa", "rhoc"})
+            if int(j) < 0 or unknown:
+                raise ValueError(f"run_tangent: tables column {j}: " + (f"unknown key {unknown[0]!r} (kappa, rhoc)"
+                                                                        if unknown else "a negative column"))
+            for q, key in enumerate(("kappa", "rhoc")):
+                own = {int(t): v for t, v in (self.kappa_tables if q == 0 else self.rhoc_tables).items()}
+                for t, v in (kinds.get(key) or {}).items():
+                    v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
+                    if int(t) not in own or v.shape != np.shape(own[int(t)][2]):
+                        raise ValueError(f"run_tangent: tables column {j}: cell tag {t} has no {key} table of {v.size} knots")
+                    tab_cols[q][(int(j), int(t))] = v
         src_cols = {}
         for j, parts in (source or {}).items():
             unknown = sorted(set(parts) - set(SOURCE_COLUMN_KEYS))
@@ -315,9 +342,9 @@ class HeatProblem:
                                                                         if unknown else "a negative column"))
             src_cols[int(j)] = dict(parts)
         n_par = max([len(conductivity), len(capacity or ())] + [j + 1 for j in boundary] + [j + 1 for j in shape]
-                    + [j + 1 for j in src_cols])
+                    + [j + 1 for j in src_cols] + [j + 1 for q in tab_cols for j, _ in tab_cols[q]])
         if n_par == 0:
-            raise ValueError("run_tangent: no parameter (conductivity, boundary, shape or source) given")
+            raise ValueError("run_tangent: no parameter (conductivity, boundary, shape, source or tables) given")
         directional = any(isinstance(t, (tuple, list)) for tags in conductivity for t in tags)
         if not directional:
             tag_col = {}
@@ -347,6 +374,13 @@ class HeatProblem:
             spec += ("capacity",) + tuple(sorted(cap_col.items()))
         if src_cols:
             spec += ("source",) + tuple(sorted(src_cols))
+        if tables is not None:
+            spec += ("tables",) + tuple((q, key, hashlib.sha1(tab_cols[q][key].tobytes()).hexdigest())
+                                        for q in tab_cols for key in sorted(tab_cols[q]))
+            if not getattr(self, "_table_deriv", False):
+                self.backend.table_derivatives(True)             # (before the set-up, which refuses tables without it)
+                self._table_deriv = True
+                self._tangent_spec = None                        # (the call dropped the set-up)
         if source is not None and not self._source_diff:
             self.backend.source_derivatives(True)            # (before the set-up, which refuses a source that is not differentiable)
             self._source_diff = True
@@ -359,6 +393,9 @@ class HeatProblem:
                 self.backend.tangent_set_capacity(cap_col)
             for j in sorted(shape):                          # (the set-up removed whatever velocities were there)
                 self.backend.tangent_set_shape(j, shape[j])
+            for q in (0, 1):                                 # (and whatever derivative tables)
+                if tab_cols[q]:
+                    self.backend.tangent_set_tables(q, tab_cols[q])
             self._tangent_spec = spec
         nv = self.backend.tangent_nv
         for bc in self.bcs:
@@ -418,7 +455,8 @@ class HeatProblem:
         return self.backend.get_tangent(j)
 
     def tangent_load(self, j):
-        """The load F_j = -K_j u of column j at the current state, by the tangent set-up in force (tests and diagnostics)."""
+        """The load F_j = -K_j u of column j at the current state, by the tangent set-up in force (tests and diagnostics); under
+        ``tables=`` the tables' term is included, formed from the columns as they stand."""
         return self.backend.tangent_load(j)
 
 

@@ -542,6 +542,33 @@ int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col);
 int hf_tangent_set_shape(hf_ctx* ctx, int32_t j, const double* vz);
 int hf_tangent_set_capacity(hf_ctx* ctx, int32_t tab_len, const int32_t* tag_col_c);
 int hf_tangent_setup_dir(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col_k, const int32_t* tag_col_r, const int32_t* tag_col_z);
+
+/* Tangent runs under kappa(T) / rho_c(T) tables, lagged scheme (one Picard sweep), switched on explicitly.
+ * With u* the evaluation state of the step, T_e the element temperature of u*, s* formed from s^n, s^{n-1} as u* is from u^n,
+ * u^{n-1}, and sigma_e the mean of s* over the element's nodes, every column's load gets, on every element of a tabled tag,
+ *     - [ kdot_e (K^1_e u^{n+1})_i + cdot_e (M^1_e w)_i ],
+ *     kdot_e = D^k_{j,tag}(T_e) + kappa'_tag(T_e) sigma_e,    cdot_e = D^c_{j,tag}(T_e) + rho_c'_tag(T_e) sigma_e,
+ * kappa' / rho_c' the slope of the table segment the evaluation took (0 in both clamped ranges), D the column's derivative table
+ * (below), K^1_e / M^1_e the element matrices at unit coefficients and w the step rate of the capacity columns
+ * (k_tangent_load_T<nv>, launched after the other load kernels; no atomics, bitwise reproducible).  The tangent stage solves with
+ * the operator and mass matrix the primal step just valued; its columns start from s^n (the projection ring assumes one operator).
+ * hf_table_derivatives   enable = 1 needs tables (HF_ERR_STATE otherwise, and with a batch open).  A change of the setting drops
+ *        a tangent set-up.  hf_set_kappa_tables, hf_set_rhoc_tables and hf_set_picard switch it off again.  While it is on
+ *        hf_tangent_setup, hf_tangent_setup_dir and hf_run_tangent no longer refuse the tables; they refuse instead
+ *        (the message names the cause): a conductivity column on a tag with a conductivity table and a capacity column on a tag
+ *        with a capacity table (HF_ERR_ARG; such parameters enter through hf_tangent_set_tables), a mesh whose staging would
+ *        exceed 160 KiB of LDS (HF_ERR_ARG), any source, shape columns, source columns, monitor tangents and more than one Picard
+ *        sweep (HF_ERR_STATE).  Without the call every message and return code is what it was.  The primal of hf_run_tangent
+ *        under tables is bit for bit hf_run's.
+ * hf_tangent_set_tables  kind 0 = conductivity, 1 = rho_c; entry e gives column column[e] the derivative table of cell tag
+ *        tag[e]: d(knot value)/d(parameter) at the knots of that tag's table of that kind, `values` being the entries'
+ *        tables concatenated.  Either sign.  n_entries = 0 clears the kind.  Every tangent is reset to zero; either set-up
+ *        removes the tables.  HF_ERR_STATE: no set-up, table derivatives off, a batch open.  HF_ERR_ARG (naming the offender): a
+ *        tag without a table of that kind, a column outside [0, n_par), a pair listed twice, a non-finite value.
+ * hf_tangent_load includes the term, formed from the u^n (and u^{n-1}) the last hf_run_tangent kept and from the columns as they
+ * stand (after a run: s^{n+1} in the place of s^n); nothing where no step has been taken since the tangents were reset. */
+int hf_table_derivatives(hf_ctx* ctx, int32_t enable);
+int hf_tangent_set_tables(hf_ctx* ctx, int32_t kind, int32_t n_entries, const int32_t* column, const int32_t* tag, const double* values);
 int hf_tangent_load(hf_ctx* ctx, int32_t j, double* F);
 int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const double* h_all, double rtol, double atol, int32_t max_it,
                    int32_t n_s, const int32_t* nodes, double* samples, int32_t* iters, double* tangent_samples, int32_t* tangent_iters);
