@@ -530,6 +530,13 @@ void zero_flat_column(hf_ctx* ctx, double bn2, double* x, int nv, int j) {
   if (bn2 == 0.0) hipLaunchKernelGGL(kb_zero_column, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->n), nv, j, x);
 }
 
+// out[column][q] = u[idx[q] * nv + column] of an interleaved batch vector (kb_gather<nv>)
+void batch_gather(hf_ctx* ctx, int nv, int ns, const int32_t* idx, const double* u, double* out) {
+  dispatch_nv(nv, [&](auto w) {
+    hipLaunchKernelGGL((kb_gather<decltype(w)::value>), dim3((ns * nv + 255) / 256), dim3(256), 0, ctx->stream, ns, idx, u, out);
+  });
+}
+
 // After a batched step: per wanted component, the gradient right-hand sides of all columns (k_grad_rows on column j of the
 // interleaved state), one nv-column Jacobi-PCG warm-started from that component's last projection, and the samples
 // out[component][column][node] (reference run_no_diamond.py:543-566, once per run and step).
@@ -537,21 +544,15 @@ int batch_flux_step(hf_ctx* ctx, int components, double rtol, int max_it, int nf
   hf_ctx::Batch& B = ctx->batch;
   hf_ctx::Batch& F = ctx->fluxnb;
   const int nv = B.nv;
-  const int capd = ctx->rg_max_dict;
-  const size_t sm = static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 + (RBA + 4) * 4 +
-                    (static_cast<size_t>((ctx->max_blk_nnz + 1) & ~1) / 8 + 3) * 16;
-  const int grid = std::min(ctx->nblk_a, 2048);
   int done = 0;
   for (int comp = 0; comp < 2; ++comp) {
     if (!((components >> comp) & 1)) continue;
     const bool second = done == 1;                     // the r component after the z component: its own warm start
     if (second) std::swap(F.u, F.uprev);
     for (int j = 0; j < nv; ++j)
-      hipLaunchKernelGGL(k_grad_rows, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr,
-                         reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
-                         ctx->d_rg_dict, ctx->d_rowptr, B.u, comp == 0 ? F.b + j : static_cast<double*>(nullptr),
-                         comp == 1 ? F.b + j : static_cast<double*>(nullptr), nv, nv, j);
-    HF_HIP(hipGetLastError());
+      HF_TRY(launch_rowvisit<VisitGrad>(ctx, &k_grad_rows, nullptr, ctx->d_rg_dict, ctx->d_rowptr, B.u,
+                                        comp == 0 ? F.b + j : static_cast<double*>(nullptr),
+                                        comp == 1 ? F.b + j : static_cast<double*>(nullptr), nv, nv, j));
     ctx->fluxnb_comp = comp;
     std::swap(ctx->batch, ctx->fluxnb);
     const int rc = batch_dispatch(ctx, [&](auto ops) { return decltype(ops)::pcg(ctx, false, rtol, 0.0, max_it); });
@@ -562,13 +563,7 @@ int batch_flux_step(hf_ctx* ctx, int components, double rtol, int max_it, int nf
     if (rc != HF_OK) { if (second) std::swap(F.u, F.uprev); return rc; }
     for (int j = 0; j < nv; ++j) zero_flat_column(ctx, F.h_scal[j].bn2, F.u, nv, j);
     double* o = out + static_cast<size_t>(done) * nv * nfs;
-    const int thr = nfs * nv;
-    switch (nv) {
-      case 2: hipLaunchKernelGGL((kb_gather<2>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, nfs, ctx->d_fsamp_idx, F.u, o); break;
-      case 4: hipLaunchKernelGGL((kb_gather<4>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, nfs, ctx->d_fsamp_idx, F.u, o); break;
-      case 8: hipLaunchKernelGGL((kb_gather<8>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, nfs, ctx->d_fsamp_idx, F.u, o); break;
-      default: hipLaunchKernelGGL((kb_gather<16>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, nfs, ctx->d_fsamp_idx, F.u, o); break;
-    }
+    batch_gather(ctx, nv, nfs, ctx->d_fsamp_idx, F.u, o);
     HF_HIP(hipGetLastError());
     if (second) std::swap(F.u, F.uprev);
     ++done;
@@ -621,159 +616,73 @@ int tangent_rate_buffers(hf_ctx* ctx) {
   return HF_OK;
 }
 
-// The shape columns' part of the load (k_tangent_load_shape<NS>), added to what the load kernel of the set-up wrote: LDS for w and
-// the NS velocities next to k_tangent_load's footprint, persistent workgroups from one occupancy query per mesh
-template <int NS>
-int tangent_load_shape(hf_ctx* ctx, RgVariant id) {
-  const hf_ctx::Tangent::Shape& S = ctx->tan.sh;
-  const int capd = ctx->rg_max_dict;
-  const size_t sm = static_cast<size_t>(capd) * 16 + 2 * static_cast<size_t>(capd + (capd & 1)) * 8 +
-                    static_cast<size_t>((capd * NS + 1) & ~1) * 8 + (RBA + 4) * 4 +
-                    (static_cast<size_t>((ctx->max_blk_nnz + 1) & ~1) / 8 + 3) * 16;
-  int& grid = ctx->rg_grid[id];
-  if (grid == 0) {
-    const void* fn = reinterpret_cast<const void*>(&k_tangent_load_shape<NS>);
-    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
-    int per_cu = 0, ncu = 0;
-    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
-    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
-    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
-    if (std::getenv("HEATFLOW_DEBUG"))
-      std::fprintf(stderr, "[tangent shape] k_tangent_load_shape<%d>: column list %d slots, %zu B dynamic LDS, %d workgroups per CU, grid %d of %d row blocks\n",
-                   NS, capd, sm, per_cu, grid, ctx->nblk_a);
-  }
-  const bool bdf2 = ctx->tan.wmode == 2;
-  ShapeArgs a;
-  for (int s = 0; s < 4; ++s) a.dst[s] = S.col[s];
-  a.nv = ctx->tan.nv;
-  a.wmode = ctx->tan.wmode;
-  a.dtp = ctx->dt;   // the operator's step: dt, or dt' = 2/3 dt under BDF2 (hf_assemble)
-  hipLaunchKernelGGL(k_tangent_load_shape<NS>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr,
-                     reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
-                     ctx->d_rg_dict, ctx->d_rowptr, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->an.on ? ctx->an.d_m : nullptr, ctx->d_u,
-                     ctx->tan.un, bdf2 && ctx->tan.hist ? ctx->tan.um1 : ctx->tan.un, S.d_v, a, ctx->tan.F);
-  HF_HIP(hipGetLastError());
-  return HF_OK;
-}
-
 // dynamic LDS of k_tangent_load_T<nv>: coordinates, u, w, u* and nv values of s* per column-list slot, the row offsets and the
 // 16-bit column ids of the block
-size_t tangent_load_T_bytes(const hf_ctx* ctx, int nv) {
-  const size_t capd = static_cast<size_t>(ctx->rg_max_dict);
-  return capd * 16 + 3 * (capd + (capd & 1)) * 8 + capd * nv * 8 + (RBA + 4) * 4 +
-         (static_cast<size_t>((ctx->max_blk_nnz + 1) & ~1) / 8 + 3) * 16;
-}
+size_t tangent_load_T_bytes(const hf_ctx* ctx, int nv) { return rowvisit_lds_bytes(ctx->max_blk_nnz, ctx->rg_max_dict, 3, nv); }
 
-// The tables' part of the load (k_tangent_load_T<NV>), added to what the kernels before it wrote: persistent
-// workgroups from one occupancy query per mesh, as tangent_load_shape
-template <int NV>
-int tangent_load_T(hf_ctx* ctx, RgVariant id) {
-  const hf_ctx::Tangent& C = ctx->tan;
-  const hf_ctx::KappaT& K = ctx->kt;
-  const hf_ctx::Batch& B = ctx->tanb;
-  const int capd = ctx->rg_max_dict;
-  const size_t sm = tangent_load_T_bytes(ctx, NV);
-  int& grid = ctx->rg_grid[id];
-  if (grid == 0) {
-    const void* fn = reinterpret_cast<const void*>(&k_tangent_load_T<NV>);
-    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
-    int per_cu = 0, ncu = 0;
-    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
-    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
-    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+// HEATFLOW_DEBUG: the footprint and the grid of a load kernel with a grid of its own, once per mesh
+auto tangent_load_info(const hf_ctx* ctx, const char* label, const char* kernel, int width) {
+  return [=](size_t sm, int per_cu, int grid) {
     if (std::getenv("HEATFLOW_DEBUG"))
-      std::fprintf(stderr, "[tangent tables] k_tangent_load_T<%d>: column list %d slots, %zu B dynamic LDS, %d workgroups per CU, grid %d of %d row blocks\n",
-                   NV, capd, sm, per_cu, grid, ctx->nblk_a);
-  }
-  const bool hist = C.wmode == 2 && C.hist;   // the primal step evaluated at 2 u^n - u^{n-1}
-  hipLaunchKernelGGL(k_tangent_load_T<NV>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr,
-                     reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
-                     ctx->d_rg_dict, ctx->d_rowptr, K.hdr, K.vals, K.c_on ? K.chdr : static_cast<const KTab*>(nullptr), K.cvals,
-                     C.tkoff, C.tkvals, C.tcoff, C.tcvals, ctx->d_u, C.un, hist ? C.um1 : C.un, C.wmode,
-                     ctx->dt /* dt, or dt' = 2/3 dt under BDF2 (hf_assemble) */,
-                     EvalState{C.un, hist ? C.um1 : static_cast<const double*>(nullptr)}, B.u,
-                     hist && B.bdf_hist ? B.uprev : static_cast<const double*>(nullptr), C.F);
-  HF_HIP(hipGetLastError());
-  return HF_OK;
+      std::fprintf(stderr, "[%s] %s<%d>: column list %d slots, %zu B dynamic LDS, %d workgroups per CU, grid %d of %d row blocks\n",
+                   label, kernel, width, ctx->rg_max_dict, sm, per_cu, grid, ctx->nblk_a);
+  };
 }
 
 // F = -K_j u for every tangent column j, from the context's current state, by the kernel of the set-up in force; the columns
-// that carry a rho_c (hf_tangent_set_capacity) then get -M^1_j w added, those with a shape part (hf_tangent_set_shape) -Kdot u - Mdot w
+// that carry a rho_c (hf_tangent_set_capacity) then get -M^1_j w added, those with a shape part (hf_tangent_set_shape) -Kdot u - Mdot w,
+// source columns their part of the source's load and, under table derivatives, every column the tables' term
 int tangent_load(hf_ctx* ctx) {
-  const int capd = ctx->rg_max_dict;
-  const size_t sm = static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 + (RBA + 4) * 4 +
-                    (static_cast<size_t>((ctx->max_blk_nnz + 1) & ~1) / 8 + 3) * 16;
-  const int grid = std::min(ctx->nblk_a, 2048);
-#define HF_TL(NV) hipLaunchKernelGGL(k_tangent_load<NV>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr, \
-                                     reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), \
-                                     ctx->d_rg_zrb, ctx->d_rg_dict, ctx->d_rowptr, ctx->tan.col, ctx->d_u, ctx->tan.F)
-#define HF_TLD(NV) hipLaunchKernelGGL(k_tangent_load_dir<NV>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr, \
-                                      reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), \
-                                      ctx->d_rg_zrb, ctx->d_rg_dict, ctx->d_rowptr, ctx->tan.dir, ctx->d_u, ctx->tan.F)
-  if (ctx->tan.dir) {      // hf_tangent_setup_dir
-    switch (ctx->tan.nv) {
-      case 2: HF_TLD(2); break;
-      case 4: HF_TLD(4); break;
-      case 8: HF_TLD(8); break;
-      default: HF_TLD(16); break;
-    }
-  } else {
-    switch (ctx->tan.nv) {
-      case 2: HF_TL(2); break;
-      case 4: HF_TL(4); break;
-      case 8: HF_TL(8); break;
-      default: HF_TL(16); break;
-    }
+  const hf_ctx::Tangent& C = ctx->tan;
+  const bool hist = C.wmode == 2 && C.hist;     // BDF2 with u^{n-1}: else um1 = un (not read, or the first step)
+  const double* um1 = hist ? C.um1 : C.un;
+  const double dtp = ctx->dt;                   // the operator's step: dt, or dt' = 2/3 dt under BDF2 (hf_assemble)
+  HF_TRY(dispatch_nv(C.nv, [&](auto w) {
+    constexpr int NV = decltype(w)::value;
+    if (C.dir)      // hf_tangent_setup_dir
+      return launch_rowvisit<VisitLoad>(ctx, &k_tangent_load_dir<NV>, nullptr, ctx->d_rg_dict, ctx->d_rowptr, C.dir, ctx->d_u, C.F);
+    return launch_rowvisit<VisitLoad>(ctx, &k_tangent_load<NV>, nullptr, ctx->d_rg_dict, ctx->d_rowptr, C.col, ctx->d_u, C.F);
+  }));
+  if (C.cmask != 0)   // capacity columns: -M^1_j w, on k_tangent_load's footprint and grid
+    HF_TRY(dispatch_nv(C.nv, [&](auto w) {
+      constexpr int NV = decltype(w)::value;
+      return launch_rowvisit<VisitLoad>(ctx, &k_tangent_load_cap<NV>, nullptr, ctx->d_rg_dict, ctx->d_rowptr, C.ccol, ctx->d_u, C.un,
+                                           um1, C.wmode, dtp, C.cmask, C.F);
+    }));
+  if (C.sh.ncol > 0) {   // shape columns: -(Kdot u + Mdot w), LDS for w and the ns velocities next to k_tangent_load's footprint
+    ShapeArgs a;
+    for (int s = 0; s < 4; ++s) a.dst[s] = C.sh.col[s];
+    a.nv = C.nv;
+    a.wmode = C.wmode;
+    a.dtp = dtp;
+    HF_TRY(dispatch_ns(C.sh.ns, [&](auto w) {
+      constexpr int NS = decltype(w)::value;
+      return launch_rowvisit<VisitShape<NS>>(ctx, &k_tangent_load_shape<NS>, tangent_load_info(ctx, "tangent shape", "k_tangent_load_shape", NS),
+                                             ctx->d_rg_dict, ctx->d_rowptr, ctx->d_kappa_rg, ctx->d_rhoc_rg,
+                                             ctx->an.on ? ctx->an.d_m : nullptr, ctx->d_u, C.un, um1, C.sh.d_v, a, C.F);
+    }));
   }
-#undef HF_TLD
-#undef HF_TL
-  HF_HIP(hipGetLastError());
-  if (ctx->tan.cmask != 0) {   // capacity columns: -M^1_j w, on k_tangent_load's footprint and grid
-    const hf_ctx::Tangent& C = ctx->tan;
-    const double* um1 = C.wmode == 2 && C.hist ? C.um1 : C.un;
-#define HF_TLC(NV) hipLaunchKernelGGL(k_tangent_load_cap<NV>, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr, \
-                                      reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), \
-                                      ctx->d_rg_zrb, ctx->d_rg_dict, ctx->d_rowptr, C.ccol, ctx->d_u, C.un, um1, C.wmode, \
-                                      ctx->dt /* dt, or dt' = 2/3 dt under BDF2 (hf_assemble) */, C.cmask, C.F)
-    switch (C.nv) {
-      case 2: HF_TLC(2); break;
-      case 4: HF_TLC(4); break;
-      case 8: HF_TLC(8); break;
-      default: HF_TLC(16); break;
-    }
-#undef HF_TLC
-    HF_HIP(hipGetLastError());
-  }
-  if (ctx->tan.sh.ncol > 0) {
-    switch (ctx->tan.sh.ns) {
-      case 1: HF_TRY(tangent_load_shape<1>(ctx, RG_SHAPE1)); break;
-      case 2: HF_TRY(tangent_load_shape<2>(ctx, RG_SHAPE2)); break;
-      default: HF_TRY(tangent_load_shape<4>(ctx, RG_SHAPE4)); break;
-    }
-  }
-  if (ctx->tan.smask != 0 && ctx->tan.scur >= 0 && ctx->src.diff && ctx->src.nrows > 0) {   // source columns: c0 F1 + c1 G_f + c2 G_d on the source's rows
-    const hf_ctx::Tangent& C = ctx->tan;
+  if (C.smask != 0 && C.scur >= 0 && ctx->src.diff && ctx->src.nrows > 0) {   // source columns: c0 F1 + c1 G_f + c2 G_d on the source's rows
     const hf_ctx::Source& S = ctx->src;
     const double* coef = C.scoef + static_cast<size_t>(C.scur) * C.nv * 3;
     const int blocks = static_cast<int>((static_cast<int64_t>(S.nrows) * C.nv + 255) / 256);
-#define HF_TLS(NV) hipLaunchKernelGGL(kb_source_columns<NV>, dim3(blocks), dim3(256), 0, ctx->stream, S.nrows, S.rows, C.smask, coef, \
-                                      S.F1, S.Gf, S.Gd, C.F)
-    switch (C.nv) {
-      case 2: HF_TLS(2); break;
-      case 4: HF_TLS(4); break;
-      case 8: HF_TLS(8); break;
-      default: HF_TLS(16); break;
-    }
-#undef HF_TLS
+    dispatch_nv(C.nv, [&](auto w) {
+      hipLaunchKernelGGL(kb_source_columns<decltype(w)::value>, dim3(blocks), dim3(256), 0, ctx->stream, S.nrows, S.rows, C.smask, coef,
+                         S.F1, S.Gf, S.Gd, C.F);
+    });
     HF_HIP(hipGetLastError());
   }
-  if (ctx->kt.deriv && ctx->kt.on && ctx->tan.wmode != 0) {   // tables: -(kdot K^1 u + cdot M^1 w) on the tabled tags, every column
-    switch (ctx->tan.nv) {
-      case 2: HF_TRY(tangent_load_T<2>(ctx, RG_TLT2)); break;
-      case 4: HF_TRY(tangent_load_T<4>(ctx, RG_TLT4)); break;
-      case 8: HF_TRY(tangent_load_T<8>(ctx, RG_TLT8)); break;
-      default: HF_TRY(tangent_load_T<16>(ctx, RG_TLT16)); break;
-    }
+  if (ctx->kt.deriv && ctx->kt.on && C.wmode != 0) {   // tables: -(kdot K^1 u + cdot M^1 w) on the tabled tags, every column
+    const hf_ctx::KappaT& K = ctx->kt;
+    const hf_ctx::Batch& B = ctx->tanb;
+    HF_TRY(dispatch_nv(C.nv, [&](auto w) {
+      constexpr int NV = decltype(w)::value;
+      return launch_rowvisit<VisitTables<NV>>(ctx, &k_tangent_load_T<NV>, tangent_load_info(ctx, "tangent tables", "k_tangent_load_T", NV),
+                                              ctx->d_rg_dict, ctx->d_rowptr, K.hdr, K.vals, K.c_on ? K.chdr : static_cast<const KTab*>(nullptr),
+                                              K.cvals, C.tkoff, C.tkvals, C.tcoff, C.tcvals, ctx->d_u, C.un, um1, C.wmode, dtp,
+                                              EvalState{C.un, hist ? C.um1 : static_cast<const double*>(nullptr)},   // the primal step evaluated at 2 u^n - u^{n-1}
+                                              B.u, hist && B.bdf_hist ? B.uprev : static_cast<const double*>(nullptr), C.F);
+    }));
   }
   return HF_OK;
 }
@@ -1410,14 +1319,8 @@ int hf_flux_solve(hf_ctx* ctx, int32_t components, double rtol, int32_t max_it, 
   HF_HIP(hipSetDevice(ctx->dev));
   const bool both = components == 3 && ctx->rg_ok && ctx->fluxb.nv == 2;
   if (ctx->rg_ok) {
-    const int capd = ctx->rg_max_dict;
-    const size_t sm = static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 + (RBA + 4) * 4 +
-                      (static_cast<size_t>((ctx->max_blk_nnz + 1) & ~1) / 8 + 3) * 16;
-    const int grid = std::min(ctx->nblk_a, 2048);
-    hipLaunchKernelGGL(k_grad_rows, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr,
-                       reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
-                       ctx->d_rg_dict, ctx->d_rowptr, ctx->d_u, both ? ctx->fluxb.b : ctx->d_bz, both ? ctx->fluxb.b + 1 : ctx->d_br,
-                       both ? 2 : 1, 1, 0);
+    HF_TRY(launch_rowvisit<VisitGrad>(ctx, &k_grad_rows, nullptr, ctx->d_rg_dict, ctx->d_rowptr, ctx->d_u, both ? ctx->fluxb.b : ctx->d_bz,
+                                      both ? ctx->fluxb.b + 1 : ctx->d_br, both ? 2 : 1, 1, 0));
   } else {
     HF_TRY(ensure_owner_lists(ctx));
     hipLaunchKernelGGL(k_grad_rhs, dim3(ctx->nblk_a), dim3(RBA), 0, ctx->stream, ctx->n, ctx->d_blk_eptr, ctx->d_blk_ent,
@@ -1943,13 +1846,7 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
       for (int j = 0; j < nv; ++j) tangent_iters[static_cast<size_t>(s) * nv + j] = T.h_scal[j].iters;
     if (ns > 0 && rc == HF_OK) {
       double* out = t_tall.p + static_cast<size_t>(s) * nv * ns;
-      const int thr = ns * nv;
-      switch (nv) {
-        case 2: hipLaunchKernelGGL((kb_gather<2>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, T.u, out); break;
-        case 4: hipLaunchKernelGGL((kb_gather<4>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, T.u, out); break;
-        case 8: hipLaunchKernelGGL((kb_gather<8>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, T.u, out); break;
-        default: hipLaunchKernelGGL((kb_gather<16>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, T.u, out); break;
-      }
+      batch_gather(ctx, nv, ns, ctx->d_samp_idx, T.u, out);
     }
   }
   (void)hipEventRecord(ctx->ev1, ctx->stream);
@@ -2255,25 +2152,11 @@ int hf_set_source(hf_ctx* ctx, int32_t n_tags, const int32_t* tags, double fwhm,
   HF_TRY(dev_alloc(ctx, &S.absorb, 64));
   HF_HIP(copy_sync(ctx, S.absorb, absorb.data(), sizeof(int32_t) * 64, hipMemcpyHostToDevice));
   // k_tangent_load's LDS footprint (the source shape where it stages u); persistent workgroups from one occupancy query per mesh
-  const int capd = ctx->rg_max_dict;
-  const size_t sm = static_cast<size_t>(capd) * 16 + static_cast<size_t>(capd + (capd & 1)) * 8 + (RBA + 4) * 4 +
-                    (static_cast<size_t>((ctx->max_blk_nnz + 1) & ~1) / 8 + 3) * 16;
-  int& grid = ctx->rg_grid[RG_SOURCE];
-  if (grid == 0) {
-    const void* fn = reinterpret_cast<const void*>(&k_source_load);
-    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
-    int per_cu = 0, ncu = 0;
-    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
-    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
-    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
-  }
   const double c_r = 4.0 * M_LN2 / (fwhm * fwhm), inv_depth = std::isinf(depth) ? 0.0 : 1.0 / depth;
+  HF_TRY(rowvisit_warm<VisitSource>(ctx, &k_source_load));    // (the occupancy query, if this mesh needs one, is not the kernel's time)
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  hipLaunchKernelGGL(k_source_load, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr,
-                     reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
-                     ctx->d_rowptr, S.absorb, c_r, z0, inv_depth, S.F1);
+  HF_TRY(launch_rowvisit<VisitSource>(ctx, &k_source_load, nullptr, ctx->d_rowptr, S.absorb, c_r, z0, inv_depth, S.F1));
   HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  HF_HIP(hipGetLastError());
   HF_HIP(hipStreamSynchronize(ctx->stream));
   float ms = 0.f;
   HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
@@ -2299,25 +2182,12 @@ int hf_source_derivatives(hf_ctx* ctx, int32_t enable) {
   HF_TRY(dev_alloc(ctx, &S.Gd, n));
   HF_TRY(dev_alloc(ctx, &t_has.p, n));
   // k_source_load's LDS footprint with s_f and s_d where it stages s; persistent workgroups from one occupancy query per mesh
-  const int capd = ctx->rg_max_dict;
-  const size_t sm = static_cast<size_t>(capd) * 16 + 2 * static_cast<size_t>(capd + (capd & 1)) * 8 + (RBA + 4) * 4 +
-                    (static_cast<size_t>((ctx->max_blk_nnz + 1) & ~1) / 8 + 3) * 16;
-  int& grid = ctx->rg_grid[RG_SOURCE_D];
-  if (grid == 0) {
-    const void* fn = reinterpret_cast<const void*>(&k_source_load_d);
-    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
-    int per_cu = 0, ncu = 0;
-    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
-    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
-    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
-  }
   const double c_r = 4.0 * M_LN2 / (S.fwhm * S.fwhm), inv_depth = std::isinf(S.depth) ? 0.0 : 1.0 / S.depth;
+  HF_TRY(rowvisit_warm<VisitSourceD>(ctx, &k_source_load_d));
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  hipLaunchKernelGGL(k_source_load_d, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr,
-                     reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
-                     ctx->d_rowptr, S.absorb, c_r, S.z0, inv_depth, S.fwhm, S.Gf, S.Gd, t_has.p);
+  HF_TRY(launch_rowvisit<VisitSourceD>(ctx, &k_source_load_d, nullptr, ctx->d_rowptr, S.absorb, c_r, S.z0, inv_depth, S.fwhm, S.Gf, S.Gd,
+                                       t_has.p));
   HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-  HF_HIP(hipGetLastError());
   HF_HIP(hipStreamSynchronize(ctx->stream));
   float ms = 0.f;
   HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
@@ -2685,12 +2555,10 @@ int hf_batch_set_affine(hf_ctx* ctx, int32_t n_tags, const int32_t* tags, const 
   op.v0 = ctx->d_A; op.v1 = B.A1;
   for (int j = 0; j < NV_MAX; ++j) op.delta[j] = B.delta[j];
   const int thr = ctx->n * B.nv;
-  switch (B.nv) {
-    case 2: hipLaunchKernelGGL((kb_affine_dinv<2>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr, ctx->d_colidx, op, B.dinv); break;
-    case 4: hipLaunchKernelGGL((kb_affine_dinv<4>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr, ctx->d_colidx, op, B.dinv); break;
-    case 8: hipLaunchKernelGGL((kb_affine_dinv<8>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr, ctx->d_colidx, op, B.dinv); break;
-    default: hipLaunchKernelGGL((kb_affine_dinv<16>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr, ctx->d_colidx, op, B.dinv); break;
-  }
+  dispatch_nv(B.nv, [&](auto w) {
+    hipLaunchKernelGGL((kb_affine_dinv<decltype(w)::value>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr,
+                       ctx->d_colidx, op, B.dinv);
+  });
   HF_HIP(hipGetLastError());
   HF_HIP(hipStreamSynchronize(ctx->stream));
   B.loaded = 1;
@@ -2785,13 +2653,7 @@ int hf_batch_run_flux(hf_ctx* ctx, int32_t n_steps, const double* g_all, double 
       for (int j = 0; j < nv; ++j) iters[static_cast<size_t>(s) * nv + j] = B.h_scal[j].iters;
     if (ns > 0 && rc == HF_OK) {
       double* out = t_sall.p + static_cast<size_t>(s) * nv * ns;
-      const int thr = ns * nv;
-      switch (nv) {
-        case 2: hipLaunchKernelGGL((kb_gather<2>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, B.u, out); break;
-        case 4: hipLaunchKernelGGL((kb_gather<4>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, B.u, out); break;
-        case 8: hipLaunchKernelGGL((kb_gather<8>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, B.u, out); break;
-        default: hipLaunchKernelGGL((kb_gather<16>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, B.u, out); break;
-      }
+      batch_gather(ctx, nv, ns, ctx->d_samp_idx, B.u, out);
     }
     if (flux_components != 0 && rc == HF_OK)
       rc = batch_flux_step(ctx, flux_components, flux_rtol, flux_max_it, nfs, t_fall.p + static_cast<size_t>(s) * ncomp * nv * nfs,

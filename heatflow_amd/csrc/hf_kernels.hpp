@@ -495,27 +495,59 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_an(int nblk, int cap /* s
   rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, nullptr, RowsAniso<KONLY>{kappa_idx, rhoc_idx, an_idx, dt}, Mv, Av, smem);
 }
 
-// Read-flux projection right-hand sides by row gather (same lists and staging as k_assemble_rows, plus the block's
-// slice of the state u): b_c[i] = sum over the triangles at node i of (d_c T)_e * |K| (2 r_i + r_j + r_k)/12, summed
-// in list order in a register - no LDS accumulation, no atomics, bitwise reproducible.
-__global__ __launch_bounds__(RBA) void k_grad_rows(int nblk, int capd, const int4* __restrict__ hdr, const uint4* __restrict__ ell,
-                                                   const uint4* __restrict__ cid16, const double2* __restrict__ zrb,
-                                                   const int32_t* __restrict__ dict, const int32_t* __restrict__ rowptr,
-                                                   const double* __restrict__ u, double* __restrict__ bz, double* __restrict__ br,
-                                                   int stride /* of the outputs - 1: plain arrays; 2: bz = out, br = out + 1 interleaved; nv: column j of an interleaved batch vector */,
-                                                   int ustride, int uoff /* the state is u[node * ustride + uoff] (batched loop: column uoff of nv) */) {
-  extern __shared__ double smem[];
+// What a load policy sees of the block's LDS: the column list's coordinates, its own per-node doubles behind them (sN; arrays
+// of capw = capd + (capd & 1) doubles first, then any interleaved columns), the rows' 16-bit column positions and capd.
+struct VisitLds {
+  double2* sXd;
+  double* sN;
+  const uint16_t* sC;
+  int capd;
+  __device__ __forceinline__ int capw() const { return capd + (capd & 1); }
+};
+
+// The body of the row-visit load kernels: rowgather_assemble's lists and block staging (without its register prefetch), but a
+// visit adds to registers of the row's lane, not to a slab - lane t of a workgroup owns row blk * RBA + t, walks the triangles at
+// its node in list order and stores once.  No atomics, no LDS accumulation: bitwise reproducible.  Per block of RBA rows the
+// body stages the rows' 16-bit column positions, the coordinates of the block's column list and the row starts; the visit loop
+// touches LDS only.  What a kernel adds is its load policy V:
+//   V::NODE, V::WIDE     per-node doubles in LDS behind the coordinates: NODE arrays of capw doubles, then capd * WIDE
+//                        interleaved ones (rounded up to even; 0: none).  rowvisit_lds_bytes (hf_pattern.hpp) sizes the launch
+//                        from the same two numbers
+//   V::OCC_GRID, V::ID   launch_rowvisit: a grid from one occupancy query cached in rg_grid[ID], else min(blocks, 2048)
+//   v.tables(t)          lane t < 64 fills entry t of the policy's by-tag tables (static LDS of the kernel)
+//   v.node(L, i, P, dict, g)   fill the per-node doubles of column slot i: P its coordinates, dict[g] its node id
+//   v.begin(L, ci)       the row's state: its own values (ci = its position in the column list) and zeroed accumulators
+//   row = v.visit(L, row, Pi, tg, ij, ik)   one triangle, row state in and out by value: tg the tag-dictionary index,
+//                        L.sC[ij] / L.sC[ik] the other two vertices' positions in the column list; early-outs come before those reads
+//   v.store(row, r)      write row r
+// The visit loop runs without contraction; a policy's functions state `fp contract(off)` themselves where they do arithmetic.
+template <class V>
+__device__ __forceinline__ void rowgather_visit(int nblk, int capd, const int4* __restrict__ hdr, const uint4* __restrict__ ell,
+                                                const uint4* __restrict__ cid16, const double2* __restrict__ zrb,
+                                                const int32_t* __restrict__ dict, const int32_t* __restrict__ rowptr, const V v,
+                                                double* smem) {
   double2* sXd = reinterpret_cast<double2*>(smem);
-  double* sU = smem + 2 * capd;
-  int* sR = reinterpret_cast<int*>(sU + capd + (capd & 1));
+  double* sN = smem + 2 * capd;
+  const int capw = capd + (capd & 1);
+  static_assert(V::NODE >= 1 && V::NODE <= 3, "one to three per-node arrays");
+  double* sEnd = sN + capw;                                          // array by array, as the kernels carved it up
+  if constexpr (V::NODE > 1) sEnd += capw;
+  if constexpr (V::NODE > 2) sEnd += capw;
+  int* sR = reinterpret_cast<int*>(sEnd + ((capd * V::WIDE + 1) & ~1));    // row starts
   uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);
   const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
+  const VisitLds L{sXd, sN, sC, capd};
   const int t = threadIdx.x;
+  if (t < 64) v.tables(t);
   for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
     const int4 cA = hdr[2 * blk], cB = hdr[2 * blk + 1];
     const int c0 = cA.x >> 3, nc = ((cA.x + cA.y + 7) >> 3) - c0;
     for (int i = t; i < nc; i += RBA) sC4[i] = cid16[c0 + i];
-    for (int i = t; i < cA.w; i += RBA) { sXd[i] = zrb[cA.z + i]; sU[i] = u[static_cast<size_t>(dict[cA.z + i]) * ustride + uoff]; }
+    for (int i = t; i < cA.w; i += RBA) {
+      const double2 P = zrb[cA.z + i];
+      sXd[i] = P;
+      v.node(L, i, P, dict, cA.z + i);
+    }
     if (t < cB.w) sR[t] = rowptr[blk * RBA + t] - cA.x;
     __syncthreads();
     if (t < cB.w) {
@@ -523,8 +555,7 @@ __global__ __launch_bounds__(RBA) void k_grad_rows(int nblk, int capd, const int
       const int sbase = sR[t] + (cA.x & 7);
       const int ci = cB.z + t;
       const double2 Pi = sXd[ci];
-      const double ui = sU[ci];
-      double az = 0.0, ar = 0.0;
+      auto row = v.begin(L, ci);
       for (int g = 0; g < cB.y; ++g) {
         const uint4 ev = ell[cB.x + g * RBA + t];
         const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
@@ -532,22 +563,84 @@ __global__ __launch_bounds__(RBA) void k_grad_rows(int nblk, int capd, const int
         for (int q = 0; q < 8; ++q) {
           const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
           if (e == 0xFFFFu) continue;
-          const int cj = sC[sbase + (e & 31u)], ck = sC[sbase + ((e >> 5) & 31u)];
-          const double2 Pj = sXd[cj], Pk = sXd[ck];
-          const double uj = sU[cj], uk = sU[ck];
-          const double d = (Pj.x - Pi.x) * (Pk.y - Pi.y) - (Pk.x - Pi.x) * (Pj.y - Pi.y);
-          const double gz = (ui * (Pj.y - Pk.y) + uj * (Pk.y - Pi.y) + uk * (Pi.y - Pj.y)) / d;
-          const double gr = (ui * (Pk.x - Pj.x) + uj * (Pi.x - Pk.x) + uk * (Pj.x - Pi.x)) / d;
-          const double wgt = 0.5 * fabs(d) * (Pi.y + ((Pi.y + Pj.y) + Pk.y)) / 12.0;
-          az += gz * wgt;
-          ar += gr * wgt;
+          row = v.visit(L, row, Pi, static_cast<int>(e >> 10), sbase + (e & 31u), sbase + ((e >> 5) & 31u));
         }
       }
-      if (bz != nullptr) bz[static_cast<size_t>(blk * RBA + t) * stride] = az;
-      if (br != nullptr) br[static_cast<size_t>(blk * RBA + t) * stride] = ar;
+      v.store(row, blk * RBA + t);
     }
     __syncthreads();
   }
+}
+
+// The load kernels that keep a body of their own (k_tangent_load, _dir, _cap, _T and k_source_load_d: folded into the body
+// above they compile to other registers, see profiles/rowvisit_unify_asm_compare.txt) state only what launch_rowvisit reads
+// of a policy: their per-node LDS and their grid rule.
+template <int N, int W, bool OCC = false, RgVariant I = RG_VARIANTS>
+struct VisitLaunch {
+  static constexpr int NODE = N, WIDE = W;
+  static constexpr bool OCC_GRID = OCC;
+  static constexpr RgVariant ID = I;
+};
+using VisitLoad = VisitLaunch<1, 0>;                          // sU; also k_tangent_load_dir and, with sW for sU, k_tangent_load_cap
+using VisitSourceD = VisitLaunch<2, 0, true, RG_SOURCE_D>;    // sF, sD
+template <int NV>
+using VisitTables = VisitLaunch<3, NV, true, NV == 2 ? RG_TLT2 : NV == 4 ? RG_TLT4 : NV == 8 ? RG_TLT8 : RG_TLT16>;   // sU, sW, sE, s*
+
+// The step rate of a node from u = u^{n+1}, un = u^n and um1 = u^{n-1}: 0 (wmode 0, no step taken), (u - un) / dtp (1: backward
+// Euler), ((u - 4/3 un) + 1/3 um1) / dtp (2: BDF2).  The one spelling for every kernel that stages w: a node's w has the same bits
+// in all of them.  un and um1 are read only where the mode uses them.
+__device__ __forceinline__ double step_rate(double u1, const double* __restrict__ un, const double* __restrict__ um1, int node,
+                                            int wmode, double dtp) {
+#pragma clang fp contract(off)
+  double w = 0.0;
+  if (wmode == 1) w = (u1 - un[node]) / dtp;
+  else if (wmode == 2) w = ((u1 - (4.0 / 3.0) * un[node]) + (1.0 / 3.0) * um1[node]) / dtp;
+  return w;
+}
+
+// Read-flux projection right-hand sides by row gather (same lists and staging as k_assemble_rows, plus the block's
+// slice of the state u): b_c[i] = sum over the triangles at node i of (d_c T)_e * |K| (2 r_i + r_j + r_k)/12, summed
+// in list order in a register - no LDS accumulation, no atomics, bitwise reproducible.
+struct VisitGrad {
+  static constexpr int NODE = 1, WIDE = 0;                 // sU: the state
+  static constexpr bool OCC_GRID = false;
+  const double* u;
+  double *bz, *br;
+  int stride, ustride, uoff;
+  struct Row { double ui, az, ar; };
+  __device__ __forceinline__ void tables(int) const {}
+  __device__ __forceinline__ void node(const VisitLds& L, int i, double2, const int32_t* __restrict__ dict, int g) const {
+    L.sN[i] = u[static_cast<size_t>(dict[g]) * ustride + uoff];
+  }
+  __device__ __forceinline__ Row begin(const VisitLds& L, int ci) const { return Row{L.sN[ci], 0.0, 0.0}; }
+  __device__ __forceinline__ Row visit(const VisitLds& L, Row r, const double2 Pi, int, unsigned ij, unsigned ik) const {
+#pragma clang fp contract(off)
+    const double* sU = L.sN;
+    const int cj = L.sC[ij], ck = L.sC[ik];
+    const double2 Pj = L.sXd[cj], Pk = L.sXd[ck];
+    const double ui = r.ui, uj = sU[cj], uk = sU[ck];
+    const double d = (Pj.x - Pi.x) * (Pk.y - Pi.y) - (Pk.x - Pi.x) * (Pj.y - Pi.y);
+    const double gz = (ui * (Pj.y - Pk.y) + uj * (Pk.y - Pi.y) + uk * (Pi.y - Pj.y)) / d;
+    const double gr = (ui * (Pk.x - Pj.x) + uj * (Pi.x - Pk.x) + uk * (Pj.x - Pi.x)) / d;
+    const double wgt = 0.5 * fabs(d) * (Pi.y + ((Pi.y + Pj.y) + Pk.y)) / 12.0;
+    r.az += gz * wgt;
+    r.ar += gr * wgt;
+    return r;
+  }
+  __device__ __forceinline__ void store(const Row& r, int row) const {
+    if (bz != nullptr) bz[static_cast<size_t>(row) * stride] = r.az;
+    if (br != nullptr) br[static_cast<size_t>(row) * stride] = r.ar;
+  }
+};
+
+__global__ __launch_bounds__(RBA) void k_grad_rows(int nblk, int capd, const int4* __restrict__ hdr, const uint4* __restrict__ ell,
+                                                   const uint4* __restrict__ cid16, const double2* __restrict__ zrb,
+                                                   const int32_t* __restrict__ dict, const int32_t* __restrict__ rowptr,
+                                                   const double* __restrict__ u, double* __restrict__ bz, double* __restrict__ br,
+                                                   int stride /* of the outputs - 1: plain arrays; 2: bz = out, br = out + 1 interleaved; nv: column j of an interleaved batch vector */,
+                                                   int ustride, int uoff /* the state is u[node * ustride + uoff] (batched loop: column uoff of nv) */) {
+  extern __shared__ double smem[];
+  rowgather_visit(nblk, capd, hdr, ell, cid16, zrb, dict, rowptr, VisitGrad{u, bz, br, stride, ustride, uoff}, smem);
 }
 
 // Per-parameter stiffness products of a tangent run (hf_run_tangent) by row gather (same lists and staging as k_grad_rows):
@@ -764,6 +857,62 @@ struct ShapeArgs {
 // (m_z, m_r; null = none set) by tag-dictionary index, as the assembly kernels read them.  Each slot's sum runs in list order in
 // a register of the row's lane - no atomics, bitwise reproducible.  A triangle whose three velocities agree contributes an exact 0.
 template <int NS>
+struct VisitShape {
+  static constexpr int NODE = 2, WIDE = NS;                // sU, sW, then the NS velocities of a node
+  static constexpr bool OCC_GRID = true;
+  static constexpr RgVariant ID = NS == 1 ? RG_SHAPE1 : NS == 2 ? RG_SHAPE2 : RG_SHAPE4;
+  double *skr, *skz, *src;                                 // [64] k_r, k_z and rho_c by tag-dictionary index
+  const double *kappa_idx, *rhoc_idx;
+  const double2* an_idx;
+  const double *u, *un, *um1, *vz;
+  ShapeArgs a;
+  double* F;
+  struct Row { double ui, wi, vi[NS], acc[NS]; };
+  __device__ __forceinline__ void tables(int t) const {
+#pragma clang fp contract(off)
+    const double kap = kappa_idx[t];
+    const double2 m = an_idx ? an_idx[t] : make_double2(1.0, 1.0);
+    skz[t] = m.x * kap;
+    skr[t] = m.y * kap;
+    src[t] = rhoc_idx[t];
+  }
+  __device__ __forceinline__ void node(const VisitLds& L, int i, double2, const int32_t* __restrict__ dict, int g) const {
+    double *sU = L.sN, *sW = sU + L.capw(), *sV = sW + L.capw();
+    const int node = dict[g];
+    const double u1 = u[node];
+    sU[i] = u1;
+    sW[i] = step_rate(u1, un, um1, node, a.wmode, a.dtp);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) sV[i * NS + s] = vz[static_cast<size_t>(node) * NS + s];
+  }
+  __device__ __forceinline__ Row begin(const VisitLds& L, int ci) const {
+    const double *sU = L.sN, *sW = sU + L.capw(), *sV = sW + L.capw();
+    Row r;
+    r.ui = sU[ci];
+    r.wi = sW[ci];
+#pragma unroll
+    for (int s = 0; s < NS; ++s) { r.vi[s] = sV[ci * NS + s]; r.acc[s] = 0.0; }
+    return r;
+  }
+  __device__ __forceinline__ Row visit(const VisitLds& L, Row r, const double2 Pi, int tg, unsigned ij, unsigned ik) const {
+#pragma clang fp contract(off)
+    const double *sU = L.sN, *sW = sU + L.capw(), *sV = sW + L.capw();
+    const int pj = L.sC[ij], pk = L.sC[ik];
+    const double uj = sU[pj], uk = sU[pk];
+    const ShapeVisit sv = shape_visit(Pi, L.sXd[pj], L.sXd[pk], src[tg], skz[tg], skr[tg], r.ui, uj, uk, r.wi, sW[pj], sW[pk]);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) r.acc[s] += shape_term(sv, r.vi[s], sV[pj * NS + s], sV[pk * NS + s], r.ui, uj, uk);
+    return r;
+  }
+  __device__ __forceinline__ void store(const Row& r, int row) const {
+#pragma clang fp contract(off)
+    double* out = F + static_cast<size_t>(row) * a.nv;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) out[a.dst[s]] -= r.acc[s];
+  }
+};
+
+template <int NS>
 __global__ __launch_bounds__(RBA) void k_tangent_load_shape(int nblk, int capd, const int4* __restrict__ hdr, const uint4* __restrict__ ell,
                                                             const uint4* __restrict__ cid16, const double2* __restrict__ zrb,
                                                             const int32_t* __restrict__ dict, const int32_t* __restrict__ rowptr,
@@ -773,72 +922,8 @@ __global__ __launch_bounds__(RBA) void k_tangent_load_shape(int nblk, int capd, 
                                                             const double* __restrict__ vz, ShapeArgs a, double* __restrict__ F) {
   extern __shared__ double smem[];
   __shared__ double skr[64], skz[64], src[64];
-  const int capw = capd + (capd & 1), capv = (capd * NS + 1) & ~1;
-  double2* sXd = reinterpret_cast<double2*>(smem);
-  double* sU = smem + 2 * capd;
-  double* sW = sU + capw;
-  double* sV = sW + capw;
-  int* sR = reinterpret_cast<int*>(sV + capv);
-  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);
-  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
-  const int t = threadIdx.x;
-  if (t < 64) {
-#pragma clang fp contract(off)
-    const double kap = kappa_idx[t];
-    const double2 m = an_idx ? an_idx[t] : make_double2(1.0, 1.0);
-    skz[t] = m.x * kap;
-    skr[t] = m.y * kap;
-    src[t] = rhoc_idx[t];
-  }
-  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    const int4 cA = hdr[2 * blk], cB = hdr[2 * blk + 1];
-    const int c0 = cA.x >> 3, nc = ((cA.x + cA.y + 7) >> 3) - c0;
-    for (int i = t; i < nc; i += RBA) sC4[i] = cid16[c0 + i];
-    for (int i = t; i < cA.w; i += RBA) {
-#pragma clang fp contract(off)
-      const int node = dict[cA.z + i];
-      const double u1 = u[node];
-      sXd[i] = zrb[cA.z + i];
-      sU[i] = u1;
-      double w = 0.0;
-      if (a.wmode == 1) w = (u1 - un[node]) / a.dtp;
-      else if (a.wmode == 2) w = ((u1 - (4.0 / 3.0) * un[node]) + (1.0 / 3.0) * um1[node]) / a.dtp;
-      sW[i] = w;
-#pragma unroll
-      for (int s = 0; s < NS; ++s) sV[i * NS + s] = vz[static_cast<size_t>(node) * NS + s];
-    }
-    if (t < cB.w) sR[t] = rowptr[blk * RBA + t] - cA.x;
-    __syncthreads();
-    if (t < cB.w) {
-#pragma clang fp contract(off)
-      const int sbase = sR[t] + (cA.x & 7);
-      const int ci = cB.z + t;
-      const double2 Pi = sXd[ci];
-      const double ui = sU[ci], wi = sW[ci];
-      double vi[NS], acc[NS];
-#pragma unroll
-      for (int s = 0; s < NS; ++s) { vi[s] = sV[ci * NS + s]; acc[s] = 0.0; }
-      for (int g = 0; g < cB.y; ++g) {
-        const uint4 ev = ell[cB.x + g * RBA + t];
-        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
-          if (e == 0xFFFFu) continue;
-          const int tg = e >> 10;
-          const int pj = sC[sbase + (e & 31u)], pk = sC[sbase + ((e >> 5) & 31u)];
-          const double uj = sU[pj], uk = sU[pk];
-          const ShapeVisit sv = shape_visit(Pi, sXd[pj], sXd[pk], src[tg], skz[tg], skr[tg], ui, uj, uk, wi, sW[pj], sW[pk]);
-#pragma unroll
-          for (int s = 0; s < NS; ++s) acc[s] += shape_term(sv, vi[s], sV[pj * NS + s], sV[pk * NS + s], ui, uj, uk);
-        }
-      }
-      double* out = F + static_cast<size_t>(blk * RBA + t) * a.nv;
-#pragma unroll
-      for (int s = 0; s < NS; ++s) out[a.dst[s]] -= acc[s];
-    }
-    __syncthreads();
-  }
+  rowgather_visit(nblk, capd, hdr, ell, cid16, zrb, dict, rowptr,
+                  VisitShape<NS>{skr, skz, src, kappa_idx, rhoc_idx, an_idx, u, un, um1, vz, a, F}, smem);
 }
 
 // k_tangent_load's sibling for capacity columns (hf_tangent_set_capacity; same lists, LDS carve-up and launch
@@ -931,54 +1016,39 @@ __device__ __forceinline__ double source_shape(const double2 P, double c_r, doub
 // k_tangent_load stages u the block's column nodes get s, computed once per node from the staged coordinates, so every lane
 // that reads a node sees the same bits.  The sum runs in list order in a register of the row's lane - no atomics, bitwise
 // reproducible; rows with no absorbing triangle are written as zeros.
+struct VisitSource {
+  static constexpr int NODE = 1, WIDE = 0;                 // sS: the source shape
+  static constexpr bool OCC_GRID = true;
+  static constexpr RgVariant ID = RG_SOURCE;
+  int* sabs;                                               // [64] absorbs or not, by tag-dictionary index
+  const int32_t* absorb;
+  double c_r, z0, inv_depth;
+  double* F;
+  struct Row { double si, acc; };
+  __device__ __forceinline__ void tables(int t) const { sabs[t] = absorb[t]; }
+  __device__ __forceinline__ void node(const VisitLds& L, int i, const double2 P, const int32_t*, int) const {
+    L.sN[i] = source_shape(P, c_r, z0, inv_depth);
+  }
+  __device__ __forceinline__ Row begin(const VisitLds& L, int ci) const { return Row{L.sN[ci], 0.0}; }
+  __device__ __forceinline__ Row visit(const VisitLds& L, Row r, const double2 Pi, int tg, unsigned ij, unsigned ik) const {
+#pragma clang fp contract(off)
+    const double* sS = L.sN;
+    if (sabs[tg] == 0) return r;
+    const int pj = L.sC[ij], pk = L.sC[ik];
+    const ElemRow e = element_row(Pi, L.sXd[pj], L.sXd[pk], 1.0, 0.0);
+    r.acc += (e.m0 * r.si + e.m1 * sS[pj]) + e.m2 * sS[pk];
+    return r;
+  }
+  __device__ __forceinline__ void store(const Row& r, int row) const { F[row] = r.acc; }
+};
+
 __global__ __launch_bounds__(RBA) void k_source_load(int nblk, int capd, const int4* __restrict__ hdr, const uint4* __restrict__ ell,
                                                      const uint4* __restrict__ cid16, const double2* __restrict__ zrb,
                                                      const int32_t* __restrict__ rowptr, const int32_t* __restrict__ absorb,
                                                      double c_r, double z0, double inv_depth, double* __restrict__ F) {
   extern __shared__ double smem[];
   __shared__ int sabs[64];
-  double2* sXd = reinterpret_cast<double2*>(smem);
-  double* sS = smem + 2 * capd;
-  int* sR = reinterpret_cast<int*>(sS + capd + (capd & 1));
-  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);
-  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
-  const int t = threadIdx.x;
-  if (t < 64) sabs[t] = absorb[t];
-  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
-    const int4 cA = hdr[2 * blk], cB = hdr[2 * blk + 1];
-    const int c0 = cA.x >> 3, nc = ((cA.x + cA.y + 7) >> 3) - c0;
-    for (int i = t; i < nc; i += RBA) sC4[i] = cid16[c0 + i];
-    for (int i = t; i < cA.w; i += RBA) {
-      const double2 P = zrb[cA.z + i];
-      sXd[i] = P;
-      sS[i] = source_shape(P, c_r, z0, inv_depth);
-    }
-    if (t < cB.w) sR[t] = rowptr[blk * RBA + t] - cA.x;
-    __syncthreads();
-    if (t < cB.w) {
-#pragma clang fp contract(off)
-      const int sbase = sR[t] + (cA.x & 7);
-      const int ci = cB.z + t;
-      const double2 Pi = sXd[ci];
-      const double si = sS[ci];
-      double acc = 0.0;
-      for (int g = 0; g < cB.y; ++g) {
-        const uint4 ev = ell[cB.x + g * RBA + t];
-        const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-          const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
-          if (e == 0xFFFFu) continue;
-          if (sabs[e >> 10] == 0) continue;
-          const int pj = sC[sbase + (e & 31u)], pk = sC[sbase + ((e >> 5) & 31u)];
-          const ElemRow r = element_row(Pi, sXd[pj], sXd[pk], 1.0, 0.0);
-          acc += (r.m0 * si + r.m1 * sS[pj]) + r.m2 * sS[pk];
-        }
-      }
-      F[blk * RBA + t] = acc;
-    }
-    __syncthreads();
-  }
+  rowgather_visit(nblk, capd, hdr, ell, cid16, zrb, nullptr, rowptr, VisitSource{sabs, absorb, c_r, z0, inv_depth, F}, smem);
 }
 
 // k_source_load's sibling for a differentiable source (hf_source_derivatives; same lists, staging and launch

@@ -522,17 +522,11 @@ void montan_launch(hf_ctx* ctx, int nv, const double* s, const MonShape& sh, con
   int gw = nv;
   while (gw > 2 && montan_lds(ctx, gw) > MON_LDS) gw >>= 1;
   const size_t sm = montan_lds(ctx, gw);
-  for (int j0 = 0; j0 < nv; j0 += gw) {
-#define HF_MT(NV) hipLaunchKernelGGL(k_monitor_tan<NV>, dim3(M.grid), dim3(MON_T), sm, ctx->stream, ctx->ne, M.nchunks, ctx->tab_len, M.nd, nv, \
-                                     j0, ctx->d_elem, ctx->d_zr, ctx->d_u, s, M.slot, M.theta, sh, P)
-    switch (gw) {
-      case 2: HF_MT(2); break;
-      case 4: HF_MT(4); break;
-      case 8: HF_MT(8); break;
-      default: HF_MT(16); break;
-    }
-#undef HF_MT
-  }
+  for (int j0 = 0; j0 < nv; j0 += gw)
+    dispatch_nv(gw, [&](auto w) {
+      hipLaunchKernelGGL(k_monitor_tan<decltype(w)::value>, dim3(M.grid), dim3(MON_T), sm, ctx->stream, ctx->ne, M.nchunks, ctx->tab_len,
+                         M.nd, nv, j0, ctx->d_elem, ctx->d_zr, ctx->d_u, s, M.slot, M.theta, sh, P);
+    });
   hipLaunchKernelGGL(k_monitor_tan_final, dim3(M.nd, nv), dim3(MON_FT), 0, ctx->stream, M.grid, ctx->tab_len, ctx->n, nv, P, sh, s, prim, M.slot,
                      M.tags, out);
 }

@@ -369,6 +369,25 @@ size_t rowgather_lds_bytes(int max_blk_nnz, int max_dict, bool pair, bool state)
 size_t rowgather_smem_bytes(int max_blk_nnz, int max_dict) { return rowgather_lds_bytes(max_blk_nnz, max_dict, true, false); }
 size_t ct_smem_bytes(int max_blk_nnz, int max_dict) { return rowgather_lds_bytes(max_blk_nnz, max_dict, true, true); }   // k_assemble_rows_cT
 
+// The persistent grid of a row-gather kernel with `sm` bytes of dynamic LDS: as many workgroups as fit the chip (opt-in above
+// 64 KiB), from one occupancy query kept in ctx->rg_grid[id] until the next mesh.  *per_cu_out, if given, receives the workgroups
+// per CU when the query was made now and -1 when the cached grid was used.
+int rowgather_grid(hf_ctx* ctx, RgVariant id, const void* fn, size_t sm, int* grid_out, int* per_cu_out = nullptr) {
+  int& grid = ctx->rg_grid[id];
+  int per_cu = -1;
+  if (grid == 0) {
+    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
+    int ncu = 0;
+    per_cu = 0;
+    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
+    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
+    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+  }
+  *grid_out = grid;
+  if (per_cu_out) *per_cu_out = per_cu;
+  return HF_OK;
+}
+
 // One launch of a row-gather kernel with the coefficient policy V (`tail`: the kernel's arguments after the lists): the LDS bytes
 // of V's slab width and staging, the opt-in above 64 KiB, persistent workgroups - as many as fit the chip at this LDS footprint,
 // from one occupancy query kept in ctx->rg_grid[V::ID] until the next mesh - and the launch.  `info`, if given, is asked when the
@@ -380,22 +399,73 @@ int launch_rowgather(hf_ctx* ctx,
   const int cap = (ctx->max_blk_nnz + 1) & ~1;
   const int capd = ctx->rg_max_dict;
   const size_t sm = rowgather_lds_bytes(ctx->max_blk_nnz, capd, V::PAIR, V::STATE);
-  int& grid = ctx->rg_grid[V::ID];
-  if (grid == 0) {
-    const void* fn = reinterpret_cast<const void*>(kernel);
-    if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
-    int per_cu = 0, ncu = 0;
-    HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
-    HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
-    grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+  int grid = 0, per_cu = -1;
+  HF_TRY(rowgather_grid(ctx, V::ID, reinterpret_cast<const void*>(kernel), sm, &grid, &per_cu));
+  if (per_cu >= 0)
     if (const char* label = info ? info() : nullptr)
       std::fprintf(stderr, "%s: %zu bytes of dynamic LDS, %d workgroups per CU, grid %d of %d blocks\n", label, sm, per_cu, grid, ctx->nblk_a);
-  }
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr, ctx->d_rg_hdr,
                      reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb,
                      static_cast<KArgs>(tail)...);
   HF_HIP(hipGetLastError());
   return HF_OK;
+}
+
+// Dynamic LDS of a row-visit load kernel (rowgather_visit): the column list's coordinates, `node` arrays of one double per
+// column-list slot (padded to even), `wide` interleaved doubles per slot (padded to even), the row starts and the 16-bit column
+// positions
+size_t rowvisit_lds_bytes(int max_blk_nnz, int max_dict, int node, int wide) {
+  const size_t capd = static_cast<size_t>(max_dict);
+  return capd * 16 + node * (capd + (capd & 1)) * 8 + ((capd * wide + 1) & ~static_cast<size_t>(1)) * 8 + (RBA + 4) * 4 +
+         (static_cast<size_t>((max_blk_nnz + 1) & ~1) / 8 + 3) * 16;
+}
+
+// One launch of a row-visit load kernel with the load policy V (`tail`: the kernel's arguments after the lists' six leading
+// ones): the LDS bytes of V's staging and V's grid rule - persistent workgroups from rowgather_grid (V::OCC_GRID), or one
+// workgroup per block up to 2048.  `info`, unless nullptr, is called with (bytes, workgroups per CU, grid) when the grid is worked out.
+template <class V, class K, class Info, class... Tail>
+int launch_rowvisit(hf_ctx* ctx, K kernel, Info info, Tail... tail) {
+  const int capd = ctx->rg_max_dict;
+  const size_t sm = rowvisit_lds_bytes(ctx->max_blk_nnz, capd, V::NODE, V::WIDE);
+  int grid = std::min(ctx->nblk_a, 2048);
+  if constexpr (V::OCC_GRID) {
+    int per_cu = -1;
+    HF_TRY(rowgather_grid(ctx, V::ID, reinterpret_cast<const void*>(kernel), sm, &grid, &per_cu));
+    if constexpr (!std::is_same_v<Info, std::nullptr_t>)
+      if (per_cu >= 0) info(sm, per_cu, grid);
+  }
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, capd, ctx->d_rg_hdr,
+                     reinterpret_cast<const uint4*>(ctx->d_rg_ell), reinterpret_cast<const uint4*>(ctx->d_rg_cid), ctx->d_rg_zrb, tail...);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
+}
+// The occupancy query of launch_rowvisit<V>, made now if this mesh has no grid yet: for callers that time the launch with events
+template <class V, class K>
+int rowvisit_warm(hf_ctx* ctx, K kernel) {
+  int grid = 0;
+  return rowgather_grid(ctx, V::ID, reinterpret_cast<const void*>(kernel),
+                        rowvisit_lds_bytes(ctx->max_blk_nnz, ctx->rg_max_dict, V::NODE, V::WIDE), &grid);
+}
+
+// f(std::integral_constant<int, NV>) for the batch width nv of a tangent set-up or a sweep: 2, 4, 8, else 16 (batch_dispatch's
+// style for the kernels that are templates on the width alone)
+template <class F>
+auto dispatch_nv(int nv, F&& f) {
+  switch (nv) {
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 8: return f(std::integral_constant<int, 8>{});
+    default: return f(std::integral_constant<int, 16>{});
+  }
+}
+// ... and for the shape slots of a tangent set-up: 1, 2, else 4
+template <class F>
+auto dispatch_ns(int ns, F&& f) {
+  switch (ns) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    default: return f(std::integral_constant<int, 4>{});
+  }
 }
 
 // Row-gather element kernel into (Mout, Aout); coefficient tables indexed by the tag dictionary.  KONLY: the stiffness
