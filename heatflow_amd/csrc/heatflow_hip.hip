@@ -38,42 +38,22 @@ struct BlobHeader {
   int64_t count[12];            // elements per section, in the order written below
 };
 
-// The steady operator's fields trade places with the transient's (hf_ctx::Steady): on the swapped context the lifting,
-// elimination, multigrid set-up and PCG code runs on K_hat_S, its set S and its hierarchy, and the transient's stay as they
-// are.  A second call swaps back.
-void steady_swap(hf_ctx* ctx) {
-  hf_ctx::Steady& S = ctx->steady;
-  std::swap(ctx->nbc, S.nbc); std::swap(ctx->d_bc_dofs, S.bc_dofs); std::swap(ctx->d_g, S.g);
-  std::swap(ctx->nlift_rows, S.nlift_rows); std::swap(ctx->nlift, S.nlift);
-  std::swap(ctx->d_lift_rows, S.lift_rows); std::swap(ctx->d_lift_ptr, S.lift_ptr); std::swap(ctx->d_lift_bc, S.lift_bc);
-  std::swap(ctx->d_lift_slot, S.lift_slot); std::swap(ctx->d_lift_val, S.lift_val);
-  std::swap(ctx->d_A, S.K); std::swap(ctx->d_dinv, S.dinv);
-  std::swap(ctx->amg, S.amg); std::swap(ctx->d_coarse_inv, S.coarse_inv); std::swap(ctx->d_coarse_inv_f, S.coarse_inv_f);
-  std::swap(ctx->coarse_n, S.coarse_n); std::swap(ctx->coarse_ld, S.coarse_ld); std::swap(ctx->amg_ready, S.amg_ready);
-  std::swap(ctx->amg_fine_stale, S.amg_fine_stale); std::swap(ctx->amg_opc, S.amg_opc); std::swap(ctx->amg_setup_s, S.amg_setup_s);
-  std::swap(ctx->amg_print, S.amg_print);
+// Everything a System owns: its hierarchy, the operator, D^-1, the Dirichlet set and the lifting lists (the steady set-up's
+// and the context's teardown)
+void free_system(System& S) {
+  free_amg(S);
+  dev_free(&S.bc_dofs); dev_free(&S.g); dev_free(&S.lift_rows); dev_free(&S.lift_ptr); dev_free(&S.lift_bc);
+  dev_free(&S.lift_slot); dev_free(&S.lift_val); dev_free(&S.A); dev_free(&S.dinv);
+  S.nbc = S.nlift_rows = S.nlift = 0;
+  S.pred_iters = 0;
 }
-struct SteadyScope {   // the steady operator in place for the lifetime of the scope, on every exit path
-  hf_ctx* c;
-  explicit SteadyScope(hf_ctx* ctx) : c(ctx) { steady_swap(c); }
-  ~SteadyScope() { steady_swap(c); }
-  SteadyScope(const SteadyScope&) = delete;
-  SteadyScope& operator=(const SteadyScope&) = delete;
-};
 
 void steady_free(hf_ctx* ctx) {
-  {
-    SteadyScope sw(ctx);
-    free_amg(ctx);
-  }
   hf_ctx::Steady& S = ctx->steady;
-  dev_free(&S.bc_dofs); dev_free(&S.g); dev_free(&S.lift_rows); dev_free(&S.lift_ptr); dev_free(&S.lift_bc);
-  dev_free(&S.lift_slot); dev_free(&S.lift_val); dev_free(&S.K); dev_free(&S.dinv); dev_free(&S.Kfree);
-  dev_free(&S.hdr0); dev_free(&S.xprev); dev_free(&S.change);
+  free_system(S.sys);
+  dev_free(&S.Kfree); dev_free(&S.hdr0); dev_free(&S.xprev); dev_free(&S.change);
   S.picard = false;
-  S.nbc = S.nlift_rows = S.nlift = 0;
   S.ready = false;
-  S.pred_iters = 0;
 }
 
 void load_free(hf_ctx* ctx) {
@@ -224,8 +204,8 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
     HF_HIP(hipGetLastError());
   }
   HF_TRY(dev_alloc(ctx, &ctx->d_M, ctx->nnz));
-  HF_TRY(dev_alloc(ctx, &ctx->d_A, ctx->nnz));
-  HF_TRY(dev_alloc(ctx, &ctx->d_dinv, n));
+  HF_TRY(dev_alloc(ctx, &ctx->sys.A, ctx->nnz));
+  HF_TRY(dev_alloc(ctx, &ctx->sys.dinv, n));
   HF_TRY(dev_alloc(ctx, &ctx->d_u, n));
   HF_TRY(dev_alloc(ctx, &ctx->d_uprev, n));
   HF_TRY(dev_alloc(ctx, &ctx->d_ustart, n));
@@ -240,7 +220,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   HF_TRY(dev_alloc(ctx, &ctx->d_tmp, n));
   HF_TRY(dev_alloc(ctx, &ctx->d_z, n));
   HF_TRY(dev_alloc(ctx, &ctx->d_z2, n));
-  free_amg(ctx);
+  free_amg(ctx->sys);
   HF_HIP(copy_sync(ctx, ctx->d_elem, elem.data(), sizeof(int4) * ne, hipMemcpyHostToDevice));
   HF_HIP(copy_sync(ctx, ctx->d_rowptr, T.rowptr.data(), sizeof(int32_t) * (n + 1), hipMemcpyHostToDevice));
   HF_HIP(copy_sync(ctx, ctx->d_colidx, T.colidx.data(), sizeof(int32_t) * ctx->nnz, hipMemcpyHostToDevice));
@@ -252,9 +232,9 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   ctx->h_rowptr.swap(T.rowptr);
   ctx->h_colidx.swap(T.colidx);
   // a new mesh invalidates the Dirichlet set
-  ctx->nbc = 0; ctx->nlift = 0; ctx->nlift_rows = 0;
+  ctx->sys.nbc = 0; ctx->sys.nlift = 0; ctx->sys.nlift_rows = 0;
   ctx->have_mesh = true;
-  ctx->pred_iters = 0;
+  ctx->sys.pred_iters = 0;
   ctx->flux_ready = false;
   ctx->flux_valid = ctx->flux_formed = 0;
   if (!ctx->rg_ok) HF_TRY(ensure_owner_lists(ctx));   // the scatter kernels are this mesh's only assembly path: report their limits now
@@ -457,11 +437,11 @@ int batch_alloc(hf_ctx* ctx, hf_ctx::Batch& B, int nv) {
 
 // the V-cycle's level vectors of an nv-column batch state for the context's current hierarchy (none without one)
 int batch_levels(hf_ctx* ctx, hf_ctx::Batch& B, int nv) {
-  if (ctx->precond == 1 && ctx->amg_ready) {   // level vectors, laid out as build_amg lays out the single-column ones
-    const size_t nl = ctx->amg.size();
+  if (ctx->sys.precond == 1 && ctx->sys.amg_ready) {   // level vectors, laid out as build_amg lays out the single-column ones
+    const size_t nl = ctx->sys.amg.size();
     B.lev.resize(nl);
     for (size_t l = 1; l < nl; ++l) {
-      const DevLevel& L = ctx->amg[l];
+      const DevLevel& L = ctx->sys.amg[l];
       hf_ctx::BatchLevel& Q = B.lev[l];
       if (l + 1 < nl) {
         const size_t len = (static_cast<size_t>(L.n) + L.P.ncol + 2) * nv;
@@ -477,7 +457,7 @@ int batch_levels(hf_ctx* ctx, hf_ctx::Batch& B, int nv) {
         HF_TRY(dev_alloc(ctx, &Q.x, (static_cast<size_t>(L.n) + 2) * nv));
         Q.res = Q.x;
       } else {
-        Q.res = B.lev[l - 1].cat + static_cast<size_t>(ctx->amg[l - 1].n) * nv;
+        Q.res = B.lev[l - 1].cat + static_cast<size_t>(ctx->sys.amg[l - 1].n) * nv;
       }
     }
   }
@@ -554,11 +534,9 @@ int batch_flux_step(hf_ctx* ctx, int components, double rtol, int max_it, int nf
                                         comp == 0 ? F.b + j : static_cast<double*>(nullptr),
                                         comp == 1 ? F.b + j : static_cast<double*>(nullptr), nv, nv, j));
     ctx->fluxnb_comp = comp;
-    std::swap(ctx->batch, ctx->fluxnb);
-    const int rc = batch_dispatch(ctx, [&](auto ops) { return decltype(ops)::pcg(ctx, false, rtol, 0.0, max_it); });
+    const int rc = batch_dispatch(ctx, F, [&](auto ops) { return decltype(ops)::pcg(ctx, F, false, rtol, 0.0, max_it); });
     int itmax = 0;
-    for (int j = 0; j < nv; ++j) itmax = std::max(itmax, ctx->batch.h_scal[j].iters);
-    std::swap(ctx->batch, ctx->fluxnb);
+    for (int j = 0; j < nv; ++j) itmax = std::max(itmax, F.h_scal[j].iters);
     if (it_out) it_out[done] = itmax;
     if (rc != HF_OK) { if (second) std::swap(F.u, F.uprev); return rc; }
     for (int j = 0; j < nv; ++j) zero_flat_column(ctx, F.h_scal[j].bn2, F.u, nv, j);
@@ -590,8 +568,8 @@ int tangent_reset(hf_ctx* ctx) {
 int tangent_levels(hf_ctx* ctx) {
   hf_ctx::Batch& T = ctx->tanb;
   std::vector<int64_t> sig;
-  if (ctx->precond == 1 && ctx->amg_ready)
-    for (const DevLevel& L : ctx->amg) { sig.push_back(L.n); sig.push_back(L.P.ncol); }
+  if (ctx->sys.precond == 1 && ctx->sys.amg_ready)
+    for (const DevLevel& L : ctx->sys.amg) { sig.push_back(L.n); sig.push_back(L.P.ncol); }
   if (sig == ctx->tan.lev_sig) return HF_OK;
   for (auto& L : T.lev) { dev_free(&L.x); dev_free(&L.cat); if (L.own_b) dev_free(&L.b); }
   T.lev.clear();
@@ -751,12 +729,10 @@ int hf_destroy(hf_ctx* ctx) {
   (void)hipSetDevice(ctx->dev);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   dev_free(&ctx->d_zr); dev_free(&ctx->d_elem); dev_free(&ctx->d_kappa); dev_free(&ctx->d_rhoc);
-  dev_free(&ctx->d_rowptr); dev_free(&ctx->d_colidx); dev_free(&ctx->d_cdict_ptr); dev_free(&ctx->d_cdict); dev_free(&ctx->d_cid); dev_free(&ctx->d_blk_eptr); dev_free(&ctx->d_blk_cptr); dev_free(&ctx->d_blk_ent); dev_free(&ctx->d_rg_hdr); dev_free(&ctx->d_rg_ell); dev_free(&ctx->d_rg_cid); dev_free(&ctx->d_rg_dict); dev_free(&ctx->d_rg_zrb); dev_free(&ctx->d_kappa_rg); dev_free(&ctx->d_rhoc_rg); dev_free(&ctx->d_M); dev_free(&ctx->d_A); dev_free(&ctx->d_dinv);
-  dev_free(&ctx->d_bc_dofs); dev_free(&ctx->d_g); dev_free(&ctx->d_lift_rows); dev_free(&ctx->d_lift_ptr);
-  dev_free(&ctx->d_lift_bc); dev_free(&ctx->d_lift_slot); dev_free(&ctx->d_lift_val);
+  dev_free(&ctx->d_rowptr); dev_free(&ctx->d_colidx); dev_free(&ctx->d_cdict_ptr); dev_free(&ctx->d_cdict); dev_free(&ctx->d_cid); dev_free(&ctx->d_blk_eptr); dev_free(&ctx->d_blk_cptr); dev_free(&ctx->d_blk_ent); dev_free(&ctx->d_rg_hdr); dev_free(&ctx->d_rg_ell); dev_free(&ctx->d_rg_cid); dev_free(&ctx->d_rg_dict); dev_free(&ctx->d_rg_zrb); dev_free(&ctx->d_kappa_rg); dev_free(&ctx->d_rhoc_rg); dev_free(&ctx->d_M);
   dev_free(&ctx->d_uprev); dev_free(&ctx->d_ustart);
   dev_free(&ctx->d_u); dev_free(&ctx->d_b); dev_free(&ctx->d_r); dev_free(&ctx->d_p); dev_free(&ctx->d_Ap);
-  free_batch(ctx); free_batch_state(ctx->fluxb); free_batch_cols(ctx); free_amg(ctx); free_responses(ctx); proj_free(ctx); dev_free(&ctx->d_z); dev_free(&ctx->d_z2);
+  free_batch(ctx); free_batch_state(ctx->fluxb); free_batch_cols(ctx); free_system(ctx->sys); free_responses(ctx); proj_free(ctx); dev_free(&ctx->d_z); dev_free(&ctx->d_z2);
   steady_free(ctx); load_free(ctx); source_free(ctx); monitor_free(ctx); tangent_free(ctx); kt_free(ctx); an_free(ctx); value_lists_free(ctx);
   dev_free(&ctx->d_M1); dev_free(&ctx->d_dinv1); dev_free(&ctx->d_gz); dev_free(&ctx->d_gr); dev_free(&ctx->d_bz); dev_free(&ctx->d_br);
   dev_free(&ctx->d_tmp); dev_free(&ctx->d_part_pAp); dev_free(&ctx->d_part_rz); dev_free(&ctx->d_part_zz);
@@ -907,7 +883,7 @@ int hf_set_anisotropy(hf_ctx* ctx, int32_t n, const int32_t* tags, const double*
   }
   free_batch(ctx);             // a batch holds operators of the old coefficients
   ctx->assembled = false;
-  ctx->pred_iters = 0;
+  ctx->sys.pred_iters = 0;
   ctx->steady.ready = false;   // K depends on the multipliers: hf_steady_setup again
   // the tangent columns were checked against the old set of anisotropic tags, and a directional set-up took its kappa columns'
   // weights from the old multipliers: hf_tangent_setup / hf_tangent_setup_dir again
@@ -952,12 +928,12 @@ int hf_set_dirichlet(hf_ctx* ctx, int32_t n_bc, const int32_t* dofs) {
     seen[dofs[q]] = 1;
   }
   free_batch(ctx);
-  ctx->nbc = n_bc;
-  HF_TRY(dev_alloc(ctx, &ctx->d_bc_dofs, n_bc));
-  HF_TRY(dev_alloc(ctx, &ctx->d_g, n_bc));
-  if (n_bc > 0) HF_HIP(copy_sync(ctx, ctx->d_bc_dofs, dofs, sizeof(int32_t) * n_bc, hipMemcpyHostToDevice));
-  HF_TRY(build_lift(ctx));
-  free_amg(ctx);
+  ctx->sys.nbc = n_bc;
+  HF_TRY(dev_alloc(ctx, &ctx->sys.bc_dofs, n_bc));
+  HF_TRY(dev_alloc(ctx, &ctx->sys.g, n_bc));
+  if (n_bc > 0) HF_HIP(copy_sync(ctx, ctx->sys.bc_dofs, dofs, sizeof(int32_t) * n_bc, hipMemcpyHostToDevice));
+  HF_TRY(build_lift(ctx, ctx->sys));
+  free_amg(ctx->sys);
   free_responses(ctx);
   ctx->assembled = false;  // A_hat depends on the BC set
   return HF_OK;
@@ -977,7 +953,7 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
   ctx->dt = ctx->scheme == HF_TIME_BDF2 ? 2.0 * dt / 3.0 : dt;   // BDF2: A' = M + (2/3) dt K
   ctx->mode = mode;
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  value_lists_touch(ctx, ctx->d_A);
+  value_lists_touch(ctx, ctx->sys.A);
   value_lists_touch(ctx, ctx->d_M);
   HF_TRY(launch_assemble(ctx));
   if (ctx->kt.on) {
@@ -985,20 +961,12 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
     // (capacity tables: M re-valued by the same launch)
     HF_TRY(kt_revalue(ctx, ctx->d_u, nullptr));
   } else {
-    if (ctx->nbc > 0) {
-      if (ctx->nlift > 0)
-        hipLaunchKernelGGL(k_take_lift, dim3((ctx->nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift,
-                           ctx->d_lift_slot, ctx->d_A, ctx->d_lift_val);
-      hipLaunchKernelGGL(k_bc_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs,
-                         ctx->d_rowptr, ctx->d_colidx, ctx->d_A);
-    }
-    hipLaunchKernelGGL(k_dinv, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr,
-                       ctx->d_colidx, ctx->d_A, ctx->d_dinv);
+    HF_TRY(eliminate(ctx, ctx->sys));
   }
   // the operators stand as the loops will read them: their value lists for k_spmv (inside the timed interval)
   const bool lists = value_lists_wanted(ctx);
   if (lists) {
-    HF_TRY(value_lists_build(ctx, 0, ctx->d_A));
+    HF_TRY(value_lists_build(ctx, 0, ctx->sys.A));
     HF_TRY(value_lists_build(ctx, 1, ctx->d_M));
   }
   HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
@@ -1008,24 +976,24 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
   HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
   ctx->last_ms = ms;
   if (lists) HF_TRY(value_lists_finish(ctx));
-  if (ctx->precond == 1) {
+  if (ctx->sys.precond == 1) {
     OperatorPrint now;
     HF_TRY(operator_print(ctx, now));
-    if (!(ctx->amg_ready && ctx->amg_reuse)) {
-      HF_TRY(build_amg_auto(ctx));
-      ctx->amg_print = std::move(now);
+    if (!(ctx->sys.amg_ready && ctx->amg_reuse)) {
+      HF_TRY(build_amg_auto(ctx, ctx->sys));
+      ctx->sys.amg_print = std::move(now);
     } else {
       // hierarchy kept (reuse) or installed from another context (hf_amg_install): its fused fine-level operators hold the
       // operator it was built from - usable only if that is this one
-      ctx->amg_fine_stale = !same_print(now, ctx->amg_print) || ctx->kt.on;   // (kappa(T): built from A at another state)
+      ctx->sys.amg_fine_stale = !same_print(now, ctx->sys.amg_print) || ctx->kt.on;   // (kappa(T): built from A at another state)
     }
   }
-  if (ctx->precond == 1 && ctx->amg_ready) {  // level 0 aliases the fine operator: refresh its pointers
-    ctx->amg[0].A.val = ctx->d_A;
-    ctx->amg[0].dinv = ctx->d_dinv;
+  if (ctx->sys.precond == 1 && ctx->sys.amg_ready) {  // level 0 aliases the fine operator: refresh its pointers
+    ctx->sys.amg[0].A.val = ctx->sys.A;
+    ctx->sys.amg[0].dinv = ctx->sys.dinv;
   }
   ctx->assembled = true;
-  ctx->pred_iters = 0;
+  ctx->sys.pred_iters = 0;
   ctx->have_prev = false;
   ctx->bdf_hist = false;
   free_responses(ctx);   // R depends on the operator
@@ -1035,9 +1003,9 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
 int hf_set_precond(hf_ctx* ctx, int32_t kind, int32_t reuse) {
   if (!ctx) return HF_ERR_ARG;
   if (kind < 0 || kind > 1) return fail(ctx, HF_ERR_ARG, "hf_set_precond: unknown preconditioner %d", kind);
-  if (kind != ctx->precond) { ctx->assembled = false; ctx->pred_iters = 0; (void)hipSetDevice(ctx->dev); free_batch(ctx); }
-  if (kind == 0) { (void)hipSetDevice(ctx->dev); free_amg(ctx); }
-  ctx->precond = kind;
+  if (kind != ctx->sys.precond) { ctx->assembled = false; ctx->sys.pred_iters = 0; (void)hipSetDevice(ctx->dev); free_batch(ctx); }
+  if (kind == 0) { (void)hipSetDevice(ctx->dev); free_amg(ctx->sys); }
+  ctx->sys.precond = kind;
   ctx->amg_reuse = reuse ? 1 : 0;
   return HF_OK;
 }
@@ -1049,7 +1017,7 @@ int hf_set_time_scheme(hf_ctx* ctx, int32_t scheme) {
     (void)hipSetDevice(ctx->dev);
     free_batch(ctx);
     ctx->assembled = false;
-    ctx->pred_iters = 0;
+    ctx->sys.pred_iters = 0;
     ctx->scheme = scheme;
   }
   return HF_OK;
@@ -1072,7 +1040,7 @@ int kt_set_tables(hf_ctx* ctx, bool cap, int32_t n_tab, const int32_t* tags, con
     if (cap ? K.c_on : K.k_on) {
       free_batch(ctx);
       ctx->assembled = false;
-      ctx->pred_iters = 0;
+      ctx->sys.pred_iters = 0;
     }
     if (!(cap ? K.k_on : K.c_on)) { kt_free(ctx); return HF_OK; }
     if (cap ? K.c_on : K.k_on) {
@@ -1140,7 +1108,7 @@ int kt_set_tables(hf_ctx* ctx, bool cap, int32_t n_tab, const int32_t* tags, con
   K.on = true;
   K.have_change = false;
   ctx->assembled = false;
-  ctx->pred_iters = 0;
+  ctx->sys.pred_iters = 0;
   return HF_OK;
 }
 
@@ -1202,38 +1170,38 @@ int hf_get_amg_fallbacks(hf_ctx* ctx, int64_t* count) {
 int hf_get_amg_info(hf_ctx* ctx, int32_t* n_levels, int32_t* level_rows, int32_t max_levels, double* op_complexity,
                     double* setup_seconds) {
   if (!ctx) return HF_ERR_ARG;
-  const int nl = ctx->amg_ready ? static_cast<int>(ctx->amg.size()) : 0;
+  const int nl = ctx->sys.amg_ready ? static_cast<int>(ctx->sys.amg.size()) : 0;
   if (n_levels) *n_levels = nl;
   if (level_rows)
-    for (int l = 0; l < nl && l < max_levels; ++l) level_rows[l] = ctx->amg[l].n;
-  if (op_complexity) *op_complexity = ctx->amg_ready ? ctx->amg_opc : 0.0;
-  if (setup_seconds) *setup_seconds = ctx->amg_ready ? ctx->amg_setup_s : 0.0;
+    for (int l = 0; l < nl && l < max_levels; ++l) level_rows[l] = ctx->sys.amg[l].n;
+  if (op_complexity) *op_complexity = ctx->sys.amg_ready ? ctx->sys.amg_opc : 0.0;
+  if (setup_seconds) *setup_seconds = ctx->sys.amg_ready ? ctx->sys.amg_setup_s : 0.0;
   return HF_OK;
 }
 
 int hf_amg_export_size(hf_ctx* ctx, int64_t* bytes) {
   if (!ctx || !bytes) return HF_ERR_ARG;
-  if (!ctx->amg_ready || !ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_amg_export_size: no multigrid hierarchy (hf_set_precond(1, ...) and hf_assemble first)");
+  if (!ctx->sys.amg_ready || !ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_amg_export_size: no multigrid hierarchy (hf_set_precond(1, ...) and hf_assemble first)");
   BlobOut o;
   o.ctx = ctx;
-  HF_TRY(walk_hierarchy(ctx, o, ctx->amg_print));
+  HF_TRY(walk_hierarchy(ctx, o, ctx->sys.amg_print));
   *bytes = static_cast<int64_t>(o.at);
   return HF_OK;
 }
 
 int hf_amg_export(hf_ctx* ctx, void* blob, int64_t bytes) {
   if (!ctx || !blob) return HF_ERR_ARG;
-  if (!ctx->amg_ready || !ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_amg_export: no multigrid hierarchy (hf_set_precond(1, ...) and hf_assemble first)");
+  if (!ctx->sys.amg_ready || !ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_amg_export: no multigrid hierarchy (hf_set_precond(1, ...) and hf_assemble first)");
   HF_HIP(hipSetDevice(ctx->dev));
   BlobOut sz;
   sz.ctx = ctx;
-  HF_TRY(walk_hierarchy(ctx, sz, ctx->amg_print));
+  HF_TRY(walk_hierarchy(ctx, sz, ctx->sys.amg_print));
   if (bytes != static_cast<int64_t>(sz.at)) return fail(ctx, HF_ERR_ARG, "hf_amg_export: buffer of %lld bytes, need %lld", (long long)bytes, (long long)sz.at);
   std::vector<unsigned char> host(sz.at, 0);
   BlobOut o;
   o.ctx = ctx;
   o.dst = host.data();
-  HF_TRY(walk_hierarchy(ctx, o, ctx->amg_print));
+  HF_TRY(walk_hierarchy(ctx, o, ctx->sys.amg_print));
   HF_HIP(hipStreamSynchronize(ctx->stream));
   HF_HIP(hipMemcpy(blob, host.data(), host.size(), hipMemcpyDefault));     // host or device destination
   return HF_OK;
@@ -1242,7 +1210,7 @@ int hf_amg_export(hf_ctx* ctx, void* blob, int64_t bytes) {
 int hf_amg_install(hf_ctx* ctx, const void* blob, int64_t bytes) {
   if (!ctx || !blob || bytes <= 0) return HF_ERR_ARG;
   if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_amg_install before hf_set_mesh");
-  if (ctx->precond != 1 || !ctx->amg_reuse) return fail(ctx, HF_ERR_STATE, "hf_amg_install needs hf_set_precond(1, reuse = 1): an installed hierarchy is a kept one");
+  if (ctx->sys.precond != 1 || !ctx->amg_reuse) return fail(ctx, HF_ERR_STATE, "hf_amg_install needs hf_set_precond(1, reuse = 1): an installed hierarchy is a kept one");
   HF_HIP(hipSetDevice(ctx->dev));
   free_batch(ctx);
   std::vector<unsigned char> staged;
@@ -1332,11 +1300,8 @@ int hf_flux_solve(hf_ctx* ctx, int32_t components, double rtol, int32_t max_it, 
   if (both) {
     // both components as the two interleaved columns of one Jacobi-PCG on M_r(1): every pass over the matrix serves
     // both (reference: one 2n x 2n vector-P1 solve, run_no_diamond.py:479-489, 544-550); warm start = last projection
-    std::swap(ctx->batch, ctx->fluxb);
-    const int rc = BatchOps<2, OP_SHARED>::pcg(ctx, false, rtol, 0.0, max_it);
-    const int it0 = ctx->batch.h_scal[0].iters, it1 = ctx->batch.h_scal[1].iters;
-    std::swap(ctx->batch, ctx->fluxb);
-    if (iters) { iters[0] = it0; iters[1] = it1; }
+    const int rc = BatchOps<2, OP_SHARED>::pcg(ctx, ctx->fluxb, false, rtol, 0.0, max_it);
+    if (iters) { iters[0] = ctx->fluxb.h_scal[0].iters; iters[1] = ctx->fluxb.h_scal[1].iters; }
     ctx->flux_valid = 0;
     if (rc != HF_OK) return rc;
     for (int j = 0; j < 2; ++j) zero_flat_column(ctx, ctx->fluxb.h_scal[j].bn2, ctx->fluxb.u, 2, j);
@@ -1351,7 +1316,7 @@ int hf_flux_solve(hf_ctx* ctx, int32_t components, double rtol, int32_t max_it, 
   // one scalar mass-matrix solve per wanted component, each warm-started from its previous projection
   if (components & 1) {
     const LinSys sz{ctx->d_M1, ctx->d_dinv1, ctx->d_gz, ctx->d_bz};
-    const int rc = pcg_solve(ctx, sz, false, rtol, 0.0, max_it, &ctx->pred_flux[0]);
+    const int rc = pcg_solve(ctx, ctx->sys, sz, false, rtol, 0.0, max_it, &ctx->pred_flux[0]);
     if (iters) iters[0] = ctx->h_scal->iters;
     if (rc != HF_OK) return rc;
     zero_flat_column(ctx, ctx->h_scal->bn2, ctx->d_gz, 1, 0);
@@ -1359,7 +1324,7 @@ int hf_flux_solve(hf_ctx* ctx, int32_t components, double rtol, int32_t max_it, 
   }
   if (components & 2) {
     const LinSys sr{ctx->d_M1, ctx->d_dinv1, ctx->d_gr, ctx->d_br};
-    const int rc = pcg_solve(ctx, sr, false, rtol, 0.0, max_it, &ctx->pred_flux[1]);
+    const int rc = pcg_solve(ctx, ctx->sys, sr, false, rtol, 0.0, max_it, &ctx->pred_flux[1]);
     if (iters) iters[1] = ctx->h_scal->iters;
     if (rc != HF_OK) return rc;
     zero_flat_column(ctx, ctx->h_scal->bn2, ctx->d_gr, 1, 0);
@@ -1442,7 +1407,7 @@ int hf_sample(hf_ctx* ctx, int32_t ns, const int32_t* nodes, double* out) {
 int hf_step(hf_ctx* ctx, const double* g_bc, double rtol, double atol, int32_t max_it, int32_t* iters, double* resid) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_step before hf_assemble");
-  if (ctx->nbc > 0 && !g_bc) return fail(ctx, HF_ERR_ARG, "hf_step: g_bc is null");
+  if (ctx->sys.nbc > 0 && !g_bc) return fail(ctx, HF_ERR_ARG, "hf_step: g_bc is null");
   if (max_it <= 0 || rtol < 0 || atol < 0) return fail(ctx, HF_ERR_ARG, "hf_step: bad tolerances");
   HF_HIP(hipSetDevice(ctx->dev));
   HF_TRY(source_steps_ok(ctx, 1, "hf_step"));
@@ -1465,7 +1430,7 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
            const int32_t* nodes, double* samples, int32_t* iters) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_run before hf_assemble");
-  if (n_steps <= 0 || (ctx->nbc > 0 && !g_all) || max_it <= 0) return fail(ctx, HF_ERR_ARG, "hf_run: bad arguments");
+  if (n_steps <= 0 || (ctx->sys.nbc > 0 && !g_all) || max_it <= 0) return fail(ctx, HF_ERR_ARG, "hf_run: bad arguments");
   if (ns < 0 || (ns > 0 && (!nodes || !samples))) return fail(ctx, HF_ERR_ARG, "hf_run: bad sample arguments");
   for (int32_t q = 0; q < ns; ++q)
     if (nodes[q] < 0 || nodes[q] >= ctx->n) return fail(ctx, HF_ERR_ARG, "hf_run: node %d outside [0,%d)", nodes[q], ctx->n);
@@ -1474,9 +1439,9 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
   HF_TRY(monitor_room(ctx, n_steps));
   DevTemp<double> t_gall, t_sall;
   double *&d_gall = t_gall.p, *&d_sall = t_sall.p;
-  if (ctx->nbc > 0) {   // all boundary vectors in one transfer; the steps copy device to device
-    HF_TRY(dev_alloc(ctx, &d_gall, static_cast<size_t>(n_steps) * ctx->nbc));
-    HF_HIP(copy_sync(ctx, d_gall, g_all, sizeof(double) * n_steps * ctx->nbc, hipMemcpyHostToDevice));
+  if (ctx->sys.nbc > 0) {   // all boundary vectors in one transfer; the steps copy device to device
+    HF_TRY(dev_alloc(ctx, &d_gall, static_cast<size_t>(n_steps) * ctx->sys.nbc));
+    HF_HIP(copy_sync(ctx, d_gall, g_all, sizeof(double) * n_steps * ctx->sys.nbc, hipMemcpyHostToDevice));
   }
   if (ns > 0) {
     HF_TRY(ensure_samples(ctx, ns));
@@ -1486,8 +1451,8 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
   int rc = HF_OK;
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   for (int32_t s = 0; s < n_steps && rc == HF_OK; ++s) {
-    rc = step_device(ctx, ctx->nbc > 0 ? g_all + static_cast<size_t>(s) * ctx->nbc : nullptr,
-                     ctx->nbc > 0 ? d_gall + static_cast<size_t>(s) * ctx->nbc : nullptr, rtol, atol, max_it, s == n_steps - 1);
+    rc = step_device(ctx, ctx->sys.nbc > 0 ? g_all + static_cast<size_t>(s) * ctx->sys.nbc : nullptr,
+                     ctx->sys.nbc > 0 ? d_gall + static_cast<size_t>(s) * ctx->sys.nbc : nullptr, rtol, atol, max_it, s == n_steps - 1);
     if (iters) iters[s] = ctx->h_scal->iters;
     if (ns > 0 && rc == HF_OK)
       hipLaunchKernelGGL(k_gather, dim3((ns + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, ctx->d_u,
@@ -1779,7 +1744,7 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
     return fail(ctx, HF_ERR_STATE, "hf_run_tangent: the state comes from hf_steady_solve and depends on the conductivities (tangents start at zero): hf_set_state first");
   if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_run_tangent before hf_assemble");
   if (ctx->mode != HF_ASM_ROW_GATHER) return fail(ctx, HF_ERR_ARG, "hf_run_tangent: the operator was not assembled by the row-gather kernel");
-  if (n_steps <= 0 || (ctx->nbc > 0 && !g_all) || max_it <= 0 || rtol < 0 || atol < 0) return fail(ctx, HF_ERR_ARG, "hf_run_tangent: bad arguments");
+  if (n_steps <= 0 || (ctx->sys.nbc > 0 && !g_all) || max_it <= 0 || rtol < 0 || atol < 0) return fail(ctx, HF_ERR_ARG, "hf_run_tangent: bad arguments");
   if (ns < 0 || (ns > 0 && (!nodes || !samples || !tangent_samples))) return fail(ctx, HF_ERR_ARG, "hf_run_tangent: bad sample arguments");
   for (int32_t q = 0; q < ns; ++q)
     if (nodes[q] < 0 || nodes[q] >= ctx->n) return fail(ctx, HF_ERR_ARG, "hf_run_tangent: node %d outside [0,%d)", nodes[q], ctx->n);
@@ -1790,11 +1755,11 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
   HF_HIP(hipSetDevice(ctx->dev));
   hf_ctx::Batch& T = ctx->tanb;
   const int nv = T.nv;
-  const size_t hstep = static_cast<size_t>(ctx->nbc) * nv;
+  const size_t hstep = static_cast<size_t>(ctx->sys.nbc) * nv;
   DevTemp<double> t_gall, t_hall, t_sall, t_tall;
-  if (ctx->nbc > 0) {
-    HF_TRY(dev_alloc(ctx, &t_gall.p, static_cast<size_t>(n_steps) * ctx->nbc));
-    HF_HIP(copy_sync(ctx, t_gall.p, g_all, sizeof(double) * n_steps * ctx->nbc, hipMemcpyHostToDevice));
+  if (ctx->sys.nbc > 0) {
+    HF_TRY(dev_alloc(ctx, &t_gall.p, static_cast<size_t>(n_steps) * ctx->sys.nbc));
+    HF_HIP(copy_sync(ctx, t_gall.p, g_all, sizeof(double) * n_steps * ctx->sys.nbc, hipMemcpyHostToDevice));
     HF_TRY(dev_alloc(ctx, &t_hall.p, h_all ? hstep * n_steps : hstep));
     if (h_all) HF_HIP(copy_sync(ctx, t_hall.p, h_all, sizeof(double) * hstep * n_steps, hipMemcpyHostToDevice));
     else HF_HIP(hipMemsetAsync(t_hall.p, 0, sizeof(double) * hstep, ctx->stream));   // every step's h = 0
@@ -1825,8 +1790,8 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
       S.wmode = bdf2 ? 2 : 1;
     }
     // the primal step, exactly hf_run's
-    rc = step_device(ctx, ctx->nbc > 0 ? g_all + static_cast<size_t>(s) * ctx->nbc : nullptr,
-                     ctx->nbc > 0 ? t_gall.p + static_cast<size_t>(s) * ctx->nbc : nullptr, rtol, atol, max_it);
+    rc = step_device(ctx, ctx->sys.nbc > 0 ? g_all + static_cast<size_t>(s) * ctx->sys.nbc : nullptr,
+                     ctx->sys.nbc > 0 ? t_gall.p + static_cast<size_t>(s) * ctx->sys.nbc : nullptr, rtol, atol, max_it);
     if (iters) iters[s] = ctx->h_scal->iters;
     if (rc != HF_OK) break;
     if (ns > 0)
@@ -1836,10 +1801,8 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
     // the tangent stage: F = -K_j u^{n+1}, then one batched step of the columns with that load and boundary values h^{n+1}
     if (ctx->tan.ssteps > 0) ctx->tan.scur = ctx->tan.snext++;   // the source columns' coefficients of this step
     HF_TRY(tangent_load(ctx));
-    const double* hs = ctx->nbc == 0 ? nullptr : t_hall.p + (h_all ? hstep * s : 0);
-    std::swap(ctx->batch, ctx->tanb);
-    rc = batch_dispatch(ctx, [&](auto ops) { return decltype(ops)::step(ctx, hs, rtol, atol, max_it); });
-    std::swap(ctx->batch, ctx->tanb);
+    const double* hs = ctx->sys.nbc == 0 ? nullptr : t_hall.p + (h_all ? hstep * s : 0);
+    rc = batch_dispatch(ctx, T, [&](auto ops) { return decltype(ops)::step(ctx, T, hs, rtol, atol, max_it); });
     if (ctx->mon.on && rc != HF_OK) ctx->mon.count -= 1;   // a step that fails leaves no record
     if (mon_tan && rc == HF_OK) montan_record(ctx);        // derivatives of that record along the columns just stepped
     if (tangent_iters)
@@ -1872,19 +1835,12 @@ int hf_get_tangent(hf_ctx* ctx, int32_t j, double* s) {
   return HF_OK;
 }
 
-// After a valuation of the stiffness into steady.Kfree (on the swapped context): K_hat_S = the copy with the set S eliminated, the
-// lifting values K[free, S] taken before, and D^-1
-int steady_eliminate(hf_ctx* ctx) {
-  value_lists_touch(ctx, ctx->d_A);   // (the swapped context's d_A is the steady K, which carries no lists: a guard, not a path)
-  HF_HIP(hipMemcpyAsync(ctx->d_A, ctx->steady.Kfree, sizeof(double) * ctx->nnz, hipMemcpyDeviceToDevice, ctx->stream));
-  if (ctx->nlift > 0)
-    hipLaunchKernelGGL(k_take_lift, dim3((ctx->nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift, ctx->d_lift_slot,
-                       ctx->d_A, ctx->d_lift_val);
-  hipLaunchKernelGGL(k_bc_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs, ctx->d_rowptr,
-                     ctx->d_colidx, ctx->d_A);
-  hipLaunchKernelGGL(k_dinv, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr, ctx->d_colidx, ctx->d_A, ctx->d_dinv);
-  HF_HIP(hipGetLastError());
-  return HF_OK;
+// After a valuation of the stiffness into steady.Kfree: K_hat_S = the copy with the set S eliminated, the lifting values
+// K[free, S] taken before, and D^-1
+int steady_eliminate(hf_ctx* ctx, System& S) {
+  value_lists_touch(ctx, S.A);   // (the steady K carries no lists: a guard, not a path)
+  HF_HIP(hipMemcpyAsync(S.A, ctx->steady.Kfree, sizeof(double) * ctx->nnz, hipMemcpyDeviceToDevice, ctx->stream));
+  return eliminate(ctx, S);
 }
 
 // hf_steady_setup (picard = false: the constant-coefficient K) and hf_steady_picard_setup (picard = true: K valued at the
@@ -1904,12 +1860,12 @@ int steady_setup_impl(hf_ctx* ctx, const char* fn, bool picard, int32_t n_s, con
   steady_free(ctx);
   hf_ctx::Steady& S = ctx->steady;
   const int n = ctx->n;
-  S.nbc = n_s;
-  HF_TRY(dev_alloc(ctx, &S.bc_dofs, n_s));
-  HF_TRY(dev_alloc(ctx, &S.g, n_s));
+  S.sys.nbc = n_s;
+  HF_TRY(dev_alloc(ctx, &S.sys.bc_dofs, n_s));
+  HF_TRY(dev_alloc(ctx, &S.sys.g, n_s));
   HF_TRY(dev_alloc(ctx, &S.Kfree, ctx->nnz));
-  HF_TRY(dev_alloc(ctx, &S.K, ctx->nnz));
-  HF_TRY(dev_alloc(ctx, &S.dinv, n));
+  HF_TRY(dev_alloc(ctx, &S.sys.A, ctx->nnz));
+  HF_TRY(dev_alloc(ctx, &S.sys.dinv, n));
   if (picard) {
     HF_TRY(dev_alloc(ctx, &S.xprev, n));
     HF_TRY(dev_alloc(ctx, &S.change, 1));
@@ -1919,25 +1875,22 @@ int steady_setup_impl(hf_ctx* ctx, const char* fn, bool picard, int32_t n_s, con
       HF_HIP(copy_sync(ctx, S.hdr0, none.data(), sizeof(KTab) * 64, hipMemcpyHostToDevice));
     }
   }
-  HF_HIP(copy_sync(ctx, S.bc_dofs, dofs, sizeof(int32_t) * n_s, hipMemcpyHostToDevice));
+  HF_HIP(copy_sync(ctx, S.sys.bc_dofs, dofs, sizeof(int32_t) * n_s, hipMemcpyHostToDevice));
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   // K = the dt K part of the transient operator at dt = 1 (r-weighted), kept as assembled for hf_hold_load
   if (picard) HF_TRY(steady_revalue(ctx, ctx->kt.hdr ? ctx->kt.hdr : S.hdr0, ctx->d_u, S.Kfree));
   else HF_TRY(launch_assemble_rows_any<true>(ctx, ctx->d_kappa_rg, ctx->d_rhoc_rg, 1.0, nullptr, S.Kfree));
-  {
-    SteadyScope sw(ctx);
-    HF_TRY(build_lift(ctx));    // lifting lists of S (into the swapped fields)
-    HF_TRY(steady_eliminate(ctx));
-    HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-    HF_HIP(hipGetLastError());
-    HF_HIP(hipStreamSynchronize(ctx->stream));
-    float ms = 0.f;
-    HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->last_ms = ms;
-    if (precond == 1) HF_TRY(build_amg_auto(ctx));   // hierarchy of K_hat_S, apart from the transient's
-  }
-  S.precond = precond;
-  S.pred_iters = 0;
+  HF_TRY(build_lift(ctx, S.sys));    // lifting lists of S
+  HF_TRY(steady_eliminate(ctx, S.sys));
+  HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+  HF_HIP(hipGetLastError());
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  ctx->last_ms = ms;
+  if (precond == 1) HF_TRY(build_amg_auto(ctx, S.sys));   // hierarchy of K_hat_S, apart from the transient's
+  S.sys.precond = precond;
+  S.sys.pred_iters = 0;
   S.picard = picard;
   S.ready = true;
   return HF_OK;
@@ -1969,77 +1922,57 @@ int hf_steady_picard_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, dou
   if (max_sweeps < 1 || max_sweeps > 1000) return fail(ctx, HF_ERR_ARG, "hf_steady_picard_solve: max_sweeps %d outside 1..1000", max_sweeps);
   HF_HIP(hipSetDevice(ctx->dev));
   const bool with_load = use_load != 0 && ctx->have_load;
-  hf_ctx::Steady& S = ctx->steady;   // (inside the scope below its swapped fields hold the transient's: use the context's)
+  hf_ctx::Steady& S = ctx->steady;
+  System& Y = S.sys;
   const KTab* hdr = ctx->kt.hdr ? ctx->kt.hdr : S.hdr0;
   int rc = HF_OK, nsweeps = 0;
   double chg = 0.0, nl = 0.0;
-  {
-    SteadyScope sw(ctx);
-    const int n = ctx->n, nb = ctx->nbc;
-    HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-    HF_HIP(hipMemcpyAsync(ctx->d_g, g_s, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
-    // K_hat_S, the lifting values and D^-1 at the current iterate; the hierarchy stays the one of the set-up, whose fused
-    // finest-level legs hold the operator it was built from
-    auto value = [&]() -> int {
-      HF_TRY(steady_revalue(ctx, hdr, ctx->d_u, S.Kfree));
-      HF_TRY(steady_eliminate(ctx));
-      if (S.precond == 1 && ctx->amg_ready) ctx->amg_fine_stale = true;
-      return HF_OK;
-    };
-    // b = F (or 0) - K[:, S] g_S on the free rows, b_S = g_S; the iterate receives u_S = g_S
-    auto rhs = [&]() -> int {
-      if (with_load) HF_HIP(hipMemcpyAsync(ctx->d_b, ctx->d_load, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
-      else HF_HIP(hipMemsetAsync(ctx->d_b, 0, sizeof(double) * n, ctx->stream));
-      if (ctx->nlift_rows > 0)
-        hipLaunchKernelGGL(k_lift, dim3((ctx->nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift_rows, ctx->d_lift_rows,
-                           ctx->d_lift_ptr, ctx->d_lift_bc, ctx->d_lift_val, ctx->d_g, ctx->d_b);
-      hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, ctx->d_g, ctx->d_b, ctx->d_u);
-      HF_HIP(hipGetLastError());
-      return HF_OK;
-    };
-    const LinSys sys{ctx->d_A, ctx->d_dinv, ctx->d_u, ctx->d_b};
-    for (int k = 1; k <= max_sweeps; ++k) {
-      HF_TRY(value());
-      HF_HIP(hipMemcpyAsync(S.xprev, ctx->d_u, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
-      HF_TRY(rhs());
-      const bool use_amg = S.precond == 1 && ctx->amg_ready;
-      rc = pcg_solve(ctx, sys, use_amg, rtol, atol, max_it, &S.pred_iters);
-      int it = ctx->h_scal->iters;
-      if (rc == HF_ERR_NOCONV && use_amg && ctx->h_scal->done == 2) {   // as hf_steady_solve: finish the sweep with Jacobi on a breakdown
-        ctx->amg_fallbacks += 1;
-        int pred = 0;
-        rc = pcg_solve(ctx, sys, false, rtol, atol, max_it, &pred);
-        it += ctx->h_scal->iters;
-      }
-      if (rc == HF_ERR_HIP) return rc;
-      nsweeps = k;
-      if (iters) iters[k - 1] = it;
-      // the one scalar the host reads per sweep: change_k = max |x_k - x_{k-1}|
-      unsigned long long bits = 0;
-      HF_HIP(hipMemsetAsync(S.change, 0, sizeof(unsigned long long), ctx->stream));
-      hipLaunchKernelGGL(k_max_abs_diff, dim3(ctx->P), dim3(TPB), 0, ctx->stream, n, ctx->d_u, S.xprev, S.change);
-      HF_HIP(hipGetLastError());
-      HF_HIP(copy_sync(ctx, &bits, S.change, sizeof bits, hipMemcpyDeviceToHost));
-      std::memcpy(&chg, &bits, sizeof bits);
-      if (rc != HF_OK || chg <= picard_tol) break;
-    }
-    // the final valuation, at the returned state: Kfree for hf_hold_load, and the relative start residual a further sweep
-    // would see (the start kernels of the Jacobi loop: ||D^-1 (b - K_hat_S u)|| / ||D^-1 b||)
+  const int n = ctx->n;
+  HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  HF_HIP(hipMemcpyAsync(Y.g, g_s, sizeof(double) * Y.nbc, hipMemcpyHostToDevice, ctx->stream));
+  // K_hat_S, the lifting values and D^-1 at the current iterate; the hierarchy stays the one of the set-up, whose fused
+  // finest-level legs hold the operator it was built from
+  auto value = [&]() -> int {
+    HF_TRY(steady_revalue(ctx, hdr, ctx->d_u, S.Kfree));
+    HF_TRY(steady_eliminate(ctx, Y));
+    if (Y.precond == 1 && Y.amg_ready) Y.amg_fine_stale = true;
+    return HF_OK;
+  };
+  const LinSys sys{Y.A, Y.dinv, ctx->d_u, ctx->d_b};
+  for (int k = 1; k <= max_sweeps; ++k) {
     HF_TRY(value());
-    HF_TRY(rhs());
-    ctx->epoch += 1;
-    launch_spmv<2>(ctx, ctx->d_A, ctx->d_u, ctx->d_r, ctx->d_part_rz, ctx->d_b, ctx->d_z, ctx->d_part_zz, ctx->d_part_bn, 0.0, ctx->d_dinv);
-    hipLaunchKernelGGL(k_pcg_begin, dim3(1), dim3(TPB), 0, ctx->stream, ctx->P, rtol, atol, ctx->d_part_zz, ctx->d_part_bn, ctx->d_scal,
-                       ctx->epoch);
+    HF_HIP(hipMemcpyAsync(S.xprev, ctx->d_u, sizeof(double) * n, hipMemcpyDeviceToDevice, ctx->stream));
+    HF_TRY(lifted_rhs(ctx, Y, with_load));
+    int it = 0;
+    rc = solve_with_fallback(ctx, Y, sys, rtol, atol, max_it, &it);   // (a sweep finished by Jacobi reports both solves' iterations)
+    if (rc == HF_ERR_HIP) return rc;
+    nsweeps = k;
+    if (iters) iters[k - 1] = it;
+    // the one scalar the host reads per sweep: change_k = max |x_k - x_{k-1}|
+    unsigned long long bits = 0;
+    HF_HIP(hipMemsetAsync(S.change, 0, sizeof(unsigned long long), ctx->stream));
+    hipLaunchKernelGGL(k_max_abs_diff, dim3(ctx->P), dim3(TPB), 0, ctx->stream, n, ctx->d_u, S.xprev, S.change);
     HF_HIP(hipGetLastError());
-    HF_TRY(read_scal(ctx));
-    nl = std::sqrt(ctx->h_scal->zz / std::max(ctx->h_scal->bn2, 1e-300));
-    HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-    HF_HIP(hipStreamSynchronize(ctx->stream));
-    float ms = 0.f;
-    HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->last_ms = ms;
+    HF_HIP(copy_sync(ctx, &bits, S.change, sizeof bits, hipMemcpyDeviceToHost));
+    std::memcpy(&chg, &bits, sizeof bits);
+    if (rc != HF_OK || chg <= picard_tol) break;
   }
+  // the final valuation, at the returned state: Kfree for hf_hold_load, and the relative start residual a further sweep
+  // would see (the start kernels of the Jacobi loop: ||D^-1 (b - K_hat_S u)|| / ||D^-1 b||)
+  HF_TRY(value());
+  HF_TRY(lifted_rhs(ctx, Y, with_load));
+  ctx->epoch += 1;
+  launch_spmv<2>(ctx, Y.A, ctx->d_u, ctx->d_r, ctx->d_part_rz, ctx->d_b, ctx->d_z, ctx->d_part_zz, ctx->d_part_bn, 0.0, Y.dinv);
+  hipLaunchKernelGGL(k_pcg_begin, dim3(1), dim3(TPB), 0, ctx->stream, ctx->P, rtol, atol, ctx->d_part_zz, ctx->d_part_bn, ctx->d_scal,
+                     ctx->epoch);
+  HF_HIP(hipGetLastError());
+  HF_TRY(read_scal(ctx));
+  nl = std::sqrt(ctx->h_scal->zz / std::max(ctx->h_scal->bn2, 1e-300));
+  HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  ctx->last_ms = ms;
   // a new state, as hf_set_state: the history of the start vector (and of BDF2) does not continue
   ctx->have_prev = false;
   ctx->bdf_hist = false;
@@ -2065,35 +1998,18 @@ int hf_steady_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, double rto
   if (max_it <= 0 || rtol < 0 || atol < 0) return fail(ctx, HF_ERR_ARG, "hf_steady_solve: bad tolerances");
   HF_HIP(hipSetDevice(ctx->dev));
   const bool with_load = use_load != 0 && ctx->have_load;
-  int rc = HF_OK;
-  {
-    SteadyScope sw(ctx);
-    const int nb = ctx->nbc;
-    HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-    // b = F (or 0) - K[:, S] g_S on the free rows, b_S = g_S; the iterate starts from the current state with u_S = g_S
-    if (with_load) HF_HIP(hipMemcpyAsync(ctx->d_b, ctx->d_load, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
-    else HF_HIP(hipMemsetAsync(ctx->d_b, 0, sizeof(double) * ctx->n, ctx->stream));
-    HF_HIP(hipMemcpyAsync(ctx->d_g, g_s, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
-    if (ctx->nlift_rows > 0)
-      hipLaunchKernelGGL(k_lift, dim3((ctx->nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift_rows, ctx->d_lift_rows,
-                         ctx->d_lift_ptr, ctx->d_lift_bc, ctx->d_lift_val, ctx->d_g, ctx->d_b);
-    hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, ctx->d_g, ctx->d_b, ctx->d_u);
-    HF_HIP(hipGetLastError());
-    const LinSys sys{ctx->d_A, ctx->d_dinv, ctx->d_u, ctx->d_b};
-    const bool use_amg = ctx->steady.precond == 1 && ctx->amg_ready;
-    rc = pcg_solve(ctx, sys, use_amg, rtol, atol, max_it, &ctx->steady.pred_iters);
-    if (rc == HF_ERR_NOCONV && use_amg && ctx->h_scal->done == 2) {   // as hf_step: finish with Jacobi on a breakdown
-      ctx->amg_fallbacks += 1;
-      int pred = 0;
-      rc = pcg_solve(ctx, sys, false, rtol, atol, max_it, &pred);
-    }
-    if (rc == HF_ERR_HIP) return rc;
-    HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
-    HF_HIP(hipStreamSynchronize(ctx->stream));
-    float ms = 0.f;
-    HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
-    ctx->last_ms = ms;
-  }
+  System& Y = ctx->steady.sys;
+  HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  // b = F (or 0) - K[:, S] g_S on the free rows, b_S = g_S; the iterate starts from the current state with u_S = g_S
+  HF_HIP(hipMemcpyAsync(Y.g, g_s, sizeof(double) * Y.nbc, hipMemcpyHostToDevice, ctx->stream));
+  HF_TRY(lifted_rhs(ctx, Y, with_load));
+  const int rc = solve_with_fallback(ctx, Y, LinSys{Y.A, Y.dinv, ctx->d_u, ctx->d_b}, rtol, atol, max_it);
+  if (rc == HF_ERR_HIP) return rc;
+  HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  ctx->last_ms = ms;
   // a new state, as hf_set_state: the history of the start vector (and of BDF2) does not continue
   ctx->have_prev = false;
   ctx->bdf_hist = false;
@@ -2436,8 +2352,8 @@ int hf_hold_load(hf_ctx* ctx) {
   if (!ctx->d_load) HF_TRY(dev_alloc(ctx, &ctx->d_load, n));
   HF_HIP(hipMemsetAsync(t_mask.p, 0, n, ctx->stream));
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
-  if (ctx->nbc > 0)    // rows of the transient's Dirichlet set B
-    hipLaunchKernelGGL(k_mark_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs, t_mask.p);
+  if (ctx->sys.nbc > 0)    // rows of the transient's Dirichlet set B
+    hipLaunchKernelGGL(k_mark_rows, dim3((ctx->sys.nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->sys.nbc, ctx->sys.bc_dofs, t_mask.p);
   hipLaunchKernelGGL(k_hold_load, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, ctx->stream, n, ctx->d_rowptr, ctx->d_colidx,
                      ctx->steady.Kfree, ctx->d_u, t_mask.p, ctx->d_load);
   HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
@@ -2458,7 +2374,7 @@ int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
   if (ctx->src.on) return fail(ctx, HF_ERR_STATE, "hf_batch_begin: a source is set (the batched loop has no load term; hf_set_source with n_tags = 0 first)");
   if (nv != 2 && nv != 4 && nv != 8 && nv != 16) return fail(ctx, HF_ERR_ARG, "hf_batch_begin: 2, 4, 8 or 16 columns (got %d)", nv);
   if (operator_kind < 0 || operator_kind > 2) return fail(ctx, HF_ERR_ARG, "hf_batch_begin: unknown operator kind %d", operator_kind);
-  if (operator_kind == HF_BATCH_PER_COLUMN && ctx->precond == 1 && !ctx->amg_reuse)
+  if (operator_kind == HF_BATCH_PER_COLUMN && ctx->sys.precond == 1 && !ctx->amg_reuse)
     return fail(ctx, HF_ERR_STATE, "hf_batch_begin: per-column operators need the frozen hierarchy (hf_set_precond(1, reuse = 1))");
   HF_HIP(hipSetDevice(ctx->dev));
   free_batch(ctx);
@@ -2468,11 +2384,11 @@ int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
   for (double& d : B.delta) d = 0.0;
   if (B.opk == HF_BATCH_PER_COLUMN) {
     HF_TRY(dev_alloc(ctx, &B.A, static_cast<size_t>(ctx->nnz) * nv));
-    HF_TRY(dev_alloc(ctx, &B.lift_val, static_cast<size_t>(std::max(ctx->nlift, 1)) * nv));
+    HF_TRY(dev_alloc(ctx, &B.lift_val, static_cast<size_t>(std::max(ctx->sys.nlift, 1)) * nv));
   }
   if (B.opk == HF_BATCH_AFFINE) {
     HF_TRY(dev_alloc(ctx, &B.A1, static_cast<size_t>(ctx->nnz)));
-    HF_TRY(dev_alloc(ctx, &B.lift1, static_cast<size_t>(std::max(ctx->nlift, 1))));
+    HF_TRY(dev_alloc(ctx, &B.lift1, static_cast<size_t>(std::max(ctx->sys.nlift, 1))));
   }
   if (B.opk != HF_BATCH_SHARED) HF_TRY(dev_alloc(ctx, &B.dinv, vec));
   HF_TRY(batch_alloc(ctx, B, nv));
@@ -2502,10 +2418,10 @@ int hf_batch_load_column(hf_ctx* ctx, int32_t j) {
   if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_batch_load_column: the context holds no assembled operator");
   if (j < 0 || j >= B.nv) return fail(ctx, HF_ERR_ARG, "hf_batch_load_column: column %d outside [0,%d)", j, B.nv);
   HF_HIP(hipSetDevice(ctx->dev));
-  hipLaunchKernelGGL(kb_put_column, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->nnz), B.nv, j, ctx->d_A, B.A);
-  hipLaunchKernelGGL(kb_put_column, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->n), B.nv, j, ctx->d_dinv, B.dinv);
-  if (ctx->nlift > 0)
-    hipLaunchKernelGGL(kb_put_column, dim3(64), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->nlift), B.nv, j, ctx->d_lift_val, B.lift_val);
+  hipLaunchKernelGGL(kb_put_column, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->nnz), B.nv, j, ctx->sys.A, B.A);
+  hipLaunchKernelGGL(kb_put_column, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->n), B.nv, j, ctx->sys.dinv, B.dinv);
+  if (ctx->sys.nlift > 0)
+    hipLaunchKernelGGL(kb_put_column, dim3(64), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->sys.nlift), B.nv, j, ctx->sys.lift_val, B.lift_val);
   HF_HIP(hipGetLastError());
   HF_HIP(hipStreamSynchronize(ctx->stream));
   B.loaded |= 1u << j;
@@ -2545,14 +2461,14 @@ int hf_batch_set_affine(hf_ctx* ctx, int32_t n_tags, const int32_t* tags, const 
   if (ctx->rg_ok) HF_TRY(launch_assemble_rows_any(ctx, t_k.p, t_c.p, ctx->dt, t_scratch.p, B.A1));   // (multipliers kept: A + delta A1 shifts k)
   else HF_TRY(launch_assemble_lds(ctx, true, t_k.p, t_c.p, ctx->dt, t_scratch.p, B.A1));
   // Dirichlet elimination of A1: lifting entries kept aside, Dirichlet rows and columns zero (the unit diagonal is A's)
-  if (ctx->nbc > 0) {
-    if (ctx->nlift > 0)
-      hipLaunchKernelGGL(k_zero_slots, dim3((ctx->nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift, ctx->d_lift_slot, B.A1, B.lift1);
-    hipLaunchKernelGGL(k_zero_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs, ctx->d_rowptr, B.A1);
+  if (ctx->sys.nbc > 0) {
+    if (ctx->sys.nlift > 0)
+      hipLaunchKernelGGL(k_zero_slots, dim3((ctx->sys.nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->sys.nlift, ctx->sys.lift_slot, B.A1, B.lift1);
+    hipLaunchKernelGGL(k_zero_rows, dim3((ctx->sys.nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->sys.nbc, ctx->sys.bc_dofs, ctx->d_rowptr, B.A1);
   }
   for (int j = 0; j < B.nv; ++j) B.delta[j] = delta[j];
   BOp op{};
-  op.v0 = ctx->d_A; op.v1 = B.A1;
+  op.v0 = ctx->sys.A; op.v1 = B.A1;
   for (int j = 0; j < NV_MAX; ++j) op.delta[j] = B.delta[j];
   const int thr = ctx->n * B.nv;
   dispatch_nv(B.nv, [&](auto w) {
@@ -2612,7 +2528,7 @@ int hf_batch_run_flux(hf_ctx* ctx, int32_t n_steps, const double* g_all, double 
   if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_batch_run before hf_assemble");
   if (B.opk == HF_BATCH_PER_COLUMN && B.loaded != (1u << B.nv) - 1u) return fail(ctx, HF_ERR_STATE, "hf_batch_run: not every column's operator has been loaded");
   if (B.opk == HF_BATCH_AFFINE && B.loaded == 0) return fail(ctx, HF_ERR_STATE, "hf_batch_run: hf_batch_set_affine has not been called");
-  if (n_steps <= 0 || (ctx->nbc > 0 && !g_all) || max_it <= 0 || rtol < 0 || atol < 0) return fail(ctx, HF_ERR_ARG, "hf_batch_run: bad arguments");
+  if (n_steps <= 0 || (ctx->sys.nbc > 0 && !g_all) || max_it <= 0 || rtol < 0 || atol < 0) return fail(ctx, HF_ERR_ARG, "hf_batch_run: bad arguments");
   if (ns < 0 || (ns > 0 && (!nodes || !samples))) return fail(ctx, HF_ERR_ARG, "hf_batch_run: bad sample arguments");
   for (int32_t q = 0; q < ns; ++q)
     if (nodes[q] < 0 || nodes[q] >= ctx->n) return fail(ctx, HF_ERR_ARG, "hf_batch_run: node %d outside [0,%d)", nodes[q], ctx->n);
@@ -2627,7 +2543,7 @@ int hf_batch_run_flux(hf_ctx* ctx, int32_t n_steps, const double* g_all, double 
   }
   HF_HIP(hipSetDevice(ctx->dev));
   const int nv = B.nv;
-  const size_t gstep = static_cast<size_t>(ctx->nbc) * nv;
+  const size_t gstep = static_cast<size_t>(ctx->sys.nbc) * nv;
   DevTemp<double> t_sall, t_fall;
   if (flux_components != 0) {
     HF_TRY(ensure_batch_flux(ctx, nv, ncomp));
@@ -2635,7 +2551,7 @@ int hf_batch_run_flux(hf_ctx* ctx, int32_t n_steps, const double* g_all, double 
     HF_HIP(copy_sync(ctx, ctx->d_fsamp_idx, flux_nodes, sizeof(int32_t) * nfs, hipMemcpyHostToDevice));
     HF_TRY(dev_alloc(ctx, &t_fall.p, static_cast<size_t>(n_steps) * ncomp * nv * nfs));
   }
-  if (ctx->nbc > 0) {
+  if (ctx->sys.nbc > 0) {
     HF_TRY(dev_alloc(ctx, &B.g, gstep * n_steps));
     HF_HIP(copy_sync(ctx, B.g, g_all, sizeof(double) * gstep * n_steps, hipMemcpyHostToDevice));
   }
@@ -2647,8 +2563,8 @@ int hf_batch_run_flux(hf_ctx* ctx, int32_t n_steps, const double* g_all, double 
   int rc = HF_OK;
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   for (int32_t s = 0; s < n_steps && rc == HF_OK; ++s) {
-    const double* gs = ctx->nbc > 0 ? B.g + gstep * s : nullptr;
-    rc = batch_dispatch(ctx, [&](auto ops) { return decltype(ops)::step(ctx, gs, rtol, atol, max_it); });
+    const double* gs = ctx->sys.nbc > 0 ? B.g + gstep * s : nullptr;
+    rc = batch_dispatch(ctx, B, [&](auto ops) { return decltype(ops)::step(ctx, B, gs, rtol, atol, max_it); });
     if (iters)
       for (int j = 0; j < nv; ++j) iters[static_cast<size_t>(s) * nv + j] = B.h_scal[j].iters;
     if (ns > 0 && rc == HF_OK) {
@@ -2675,7 +2591,7 @@ int hf_get_sizes(hf_ctx* ctx, int32_t* n, int32_t* ne, int64_t* nnz, int32_t* nb
   if (n) *n = ctx->n;
   if (ne) *ne = ctx->ne;
   if (nnz) *nnz = ctx->nnz;
-  if (nbc) *nbc = ctx->nbc;
+  if (nbc) *nbc = ctx->sys.nbc;
   return HF_OK;
 }
 
@@ -2686,7 +2602,7 @@ int hf_get_csr(hf_ctx* ctx, int32_t* rowptr, int32_t* colidx, double* A, double*
   HF_HIP(hipSetDevice(ctx->dev));
   if (rowptr) std::memcpy(rowptr, ctx->h_rowptr.data(), sizeof(int32_t) * (ctx->n + 1));
   if (colidx) std::memcpy(colidx, ctx->h_colidx.data(), sizeof(int32_t) * ctx->nnz);
-  if (A) HF_HIP(copy_sync(ctx, A, ctx->d_A, sizeof(double) * ctx->nnz, hipMemcpyDeviceToHost));
+  if (A) HF_HIP(copy_sync(ctx, A, ctx->sys.A, sizeof(double) * ctx->nnz, hipMemcpyDeviceToHost));
   if (M) HF_HIP(copy_sync(ctx, M, ctx->d_M, sizeof(double) * ctx->nnz, hipMemcpyDeviceToHost));
   return HF_OK;
 }
@@ -2704,7 +2620,7 @@ int hf_get_value_lists(hf_ctx* ctx, int32_t which, int32_t* valid, int64_t* sum_
   if (which < 0 || which > 1) return fail(ctx, HF_ERR_ARG, "hf_get_value_lists: which = %d (0 = A, 1 = M)", which);
   if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_get_value_lists before hf_assemble");
   const hf_ctx::ValueLists& L = ctx->vl[which];
-  const bool live = L.valid && L.src == (which ? ctx->d_M : ctx->d_A);
+  const bool live = L.valid && L.src == (which ? ctx->d_M : ctx->sys.A);
   if (valid) *valid = live ? 1 : 0;
   if (sum_vlist) *sum_vlist = L.sum_vlist;
   if (max_vlist) *max_vlist = L.max_vlist;
@@ -2810,7 +2726,7 @@ int hf_spmv(hf_ctx* ctx, int32_t which, const double* x, double* y) {
   if (!ctx->assembled || !x || !y || which < 0 || which > 1) return fail(ctx, HF_ERR_STATE, "hf_spmv: not assembled or bad arguments");
   HF_HIP(hipSetDevice(ctx->dev));
   HF_HIP(copy_sync(ctx, ctx->d_tmp, x, sizeof(double) * ctx->n, hipMemcpyHostToDevice));
-  launch_spmv<0>(ctx, which ? ctx->d_M : ctx->d_A, ctx->d_tmp, ctx->d_Ap);
+  launch_spmv<0>(ctx, which ? ctx->d_M : ctx->sys.A, ctx->d_tmp, ctx->d_Ap);
   HF_HIP(hipGetLastError());
   HF_HIP(hipStreamSynchronize(ctx->stream));
   HF_HIP(copy_sync(ctx, y, ctx->d_Ap, sizeof(double) * ctx->n, hipMemcpyDeviceToHost));
@@ -2822,29 +2738,29 @@ int hf_spmv(hf_ctx* ctx, int32_t which, const double* x, double* y) {
 // first, so that an entry read before it is written shows in z; the zero pads wire_levels lays out stay as they are.
 int hf_amg_apply(hf_ctx* ctx, const double* r, double* z, double* rz) {
   if (!ctx || !r || !z) return HF_ERR_ARG;
-  if (ctx->precond != 1 || !ctx->amg_ready || !ctx->assembled || ctx->amg.empty())
+  if (ctx->sys.precond != 1 || !ctx->sys.amg_ready || !ctx->assembled || ctx->sys.amg.empty())
     return fail(ctx, HF_ERR_STATE, "hf_amg_apply: no assembled operator with a multigrid hierarchy (hf_set_precond(1, ...) and hf_assemble first)");
   HF_HIP(hipSetDevice(ctx->dev));
-  const int n = ctx->n, nl = static_cast<int>(ctx->amg.size());
+  const int n = ctx->n, nl = static_cast<int>(ctx->sys.amg.size());
   HF_TRY(reset_scal(ctx));
   // z0 = w0 D^-1 r, as k_pcg_update_amg leaves it (w * (dinv * r))
   std::vector<double> dinv(n), z0(n);
-  HF_HIP(copy_sync(ctx, dinv.data(), ctx->d_dinv, sizeof(double) * n, hipMemcpyDeviceToHost));
-  const double w0 = ctx->amg[0].omega;
+  HF_HIP(copy_sync(ctx, dinv.data(), ctx->sys.dinv, sizeof(double) * n, hipMemcpyDeviceToHost));
+  const double w0 = ctx->sys.amg[0].omega;
   for (int i = 0; i < n; ++i) z0[i] = w0 * (dinv[i] * r[i]);
   auto poison = [&](double* p, size_t count) { return count ? hipMemsetAsync(p, 0xFF, sizeof(double) * count, ctx->stream) : hipSuccess; };
   HF_HIP(poison(ctx->d_tmp, n));
   HF_HIP(poison(ctx->d_z2, n));
   HF_HIP(poison(ctx->d_part_rz, MAXP));
   for (int l = 1; l < nl; ++l) {
-    DevLevel& L = ctx->amg[l];
-    if (L.cat) HF_HIP(poison(L.cat, static_cast<size_t>(L.n) + ctx->amg[l + 1].n));   // [b_l ; x_{l+1}], not the 2-entry tail
+    DevLevel& L = ctx->sys.amg[l];
+    if (L.cat) HF_HIP(poison(L.cat, static_cast<size_t>(L.n) + ctx->sys.amg[l + 1].n));   // [b_l ; x_{l+1}], not the 2-entry tail
     else HF_HIP(poison(L.b, L.n));                                                       // coarsest: not the pad [n, n + 4)
     if (l == 1) HF_HIP(poison(L.res, L.n));                                              // level 1's own x, or behind d_r
   }
   HF_HIP(copy_sync(ctx, ctx->d_r, r, sizeof(double) * n, hipMemcpyHostToDevice));
   HF_HIP(copy_sync(ctx, ctx->d_z, z0.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-  vcycle(ctx, 0);
+  vcycle(ctx, ctx->sys, 0);
   HF_HIP(hipGetLastError());
   HF_HIP(hipStreamSynchronize(ctx->stream));
   HF_HIP(copy_sync(ctx, z, ctx->d_z2, sizeof(double) * n, hipMemcpyDeviceToHost));
@@ -2862,16 +2778,16 @@ int hf_batch_apply_precond(hf_ctx* ctx, const double* r, double* z, double* rz) 
   if (!ctx || !r || !z) return HF_ERR_ARG;
   hf_ctx::Batch& B = ctx->batch;
   if (B.nv == 0) return fail(ctx, HF_ERR_STATE, "hf_batch_apply_precond: no batch is open (hf_batch_begin)");
-  if (ctx->precond != 1 || !ctx->amg_ready || !ctx->assembled || ctx->amg.empty() || B.lev.size() != ctx->amg.size())
+  if (ctx->sys.precond != 1 || !ctx->sys.amg_ready || !ctx->assembled || ctx->sys.amg.empty() || B.lev.size() != ctx->sys.amg.size())
     return fail(ctx, HF_ERR_STATE, "hf_batch_apply_precond: the batch has no multigrid hierarchy");
   HF_HIP(hipSetDevice(ctx->dev));
-  const int nv = B.nv, nl = static_cast<int>(ctx->amg.size());
+  const int nv = B.nv, nl = static_cast<int>(ctx->sys.amg.size());
   const size_t n = static_cast<size_t>(ctx->n), vec = n * nv;
   // interleaved r and z0 = w0 D_j^-1 r_j (D^-1 per column unless the columns share the operator)
   const bool dpc = B.opk != HF_BATCH_SHARED;
   std::vector<double> dinv(dpc ? vec : n), ri(vec), z0(vec);
-  HF_HIP(copy_sync(ctx, dinv.data(), dpc ? B.dinv : ctx->d_dinv, sizeof(double) * dinv.size(), hipMemcpyDeviceToHost));
-  const double w0 = ctx->amg[0].omega;
+  HF_HIP(copy_sync(ctx, dinv.data(), dpc ? B.dinv : ctx->sys.dinv, sizeof(double) * dinv.size(), hipMemcpyDeviceToHost));
+  const double w0 = ctx->sys.amg[0].omega;
   for (size_t i = 0; i < n; ++i)
     for (int j = 0; j < nv; ++j) {
       const size_t q = i * nv + j;
@@ -2884,15 +2800,15 @@ int hf_batch_apply_precond(hf_ctx* ctx, const double* r, double* z, double* rz) 
   HF_HIP(poison(B.part_rz, static_cast<size_t>(nv) * MAXP));
   for (int l = 1; l < nl; ++l) {
     const hf_ctx::BatchLevel& Q = B.lev[l];
-    const size_t ln = static_cast<size_t>(ctx->amg[l].n);
-    if (Q.cat) HF_HIP(poison(Q.cat, (ln + ctx->amg[l + 1].n) * nv));
+    const size_t ln = static_cast<size_t>(ctx->sys.amg[l].n);
+    if (Q.cat) HF_HIP(poison(Q.cat, (ln + ctx->sys.amg[l + 1].n) * nv));
     else HF_HIP(poison(Q.b, ln * nv));
     if (l == 1) HF_HIP(poison(Q.res, ln * nv));
   }
   HF_HIP(hipMemsetAsync(B.scal, 0, sizeof(Scal) * nv, ctx->stream));     // every column runs
   HF_HIP(copy_sync(ctx, B.r, ri.data(), sizeof(double) * vec, hipMemcpyHostToDevice));
   HF_HIP(copy_sync(ctx, B.z, z0.data(), sizeof(double) * vec, hipMemcpyHostToDevice));
-  HF_TRY(batch_dispatch(ctx, [&](auto ops) { decltype(ops)::vcycle(ctx, 0); return HF_OK; }));
+  HF_TRY(batch_dispatch(ctx, B, [&](auto ops) { decltype(ops)::vcycle(ctx, B, 0); return HF_OK; }));
   HF_HIP(hipGetLastError());
   HF_HIP(hipStreamSynchronize(ctx->stream));
   std::vector<double> zi(vec);
@@ -2968,24 +2884,24 @@ int hf_time_kernel(hf_ctx* ctx, int32_t which, int32_t reps, double* ms_avg) {
     HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
     for (int k = 0; k < nrep; ++k) {
       switch (which) {
-        case HF_K_SPMV: launch_spmv<0>(ctx, ctx->d_A, ctx->d_tmp, ctx->d_Ap); break;
+        case HF_K_SPMV: launch_spmv<0>(ctx, ctx->sys.A, ctx->d_tmp, ctx->d_Ap); break;
         case HF_K_RHS: launch_spmv<0>(ctx, ctx->d_M, ctx->d_tmp, ctx->d_b); break;
         case HF_K_PCG_SPMV:  // iteration head as in the loop (beta = 1 from the benign partials set below)
-          launch_spmv<9>(ctx, ctx->d_A, ctx->d_tmp, ctx->d_Ap, ctx->d_part_pAp, nullptr, ctx->d_p, ctx->d_part_rz,
+          launch_spmv<9>(ctx, ctx->sys.A, ctx->d_tmp, ctx->d_Ap, ctx->d_part_pAp, nullptr, ctx->d_p, ctx->d_part_rz,
                          ctx->d_part_zz);
           break;
         case HF_K_PCG_UPDATE:
           // alpha from whatever the partial slots hold: make them benign (pAp = P, rz = 0 -> alpha = 0)
           hipLaunchKernelGGL(k_pcg_update, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->nchunks, ctx->P, 0,
                              ctx->d_scal, ctx->d_part_bn, ctx->d_part_rz, ctx->d_part_zz, ctx->d_r, ctx->d_p,
-                             ctx->d_tmp, ctx->d_Ap, ctx->d_dinv, ctx->d_z);
+                             ctx->d_tmp, ctx->d_Ap, ctx->sys.dinv, ctx->d_z);
           break;
         case HF_K_PCG_DIR:
           return fail(ctx, HF_ERR_ARG, "HF_K_PCG_DIR: the direction update is fused into the PCG SpMV (HF_K_PCG_SPMV)");
         case HF_K_ASSEMBLE: HF_TRY(launch_assemble(ctx)); break;
         case HF_K_STREAM_READ:
           hipLaunchKernelGGL(k_stream_read, dim3(MAXP), dim3(TS), 0, ctx->stream, static_cast<size_t>(ctx->nnz) / 2,
-                             reinterpret_cast<const double2*>(ctx->d_A), static_cast<size_t>(ctx->nnz) / 4,
+                             reinterpret_cast<const double2*>(ctx->sys.A), static_cast<size_t>(ctx->nnz) / 4,
                              reinterpret_cast<const double2*>(ctx->d_colidx), ctx->d_tmp);
           break;
         default: return fail(ctx, HF_ERR_ARG, "hf_time_kernel: unknown kernel %d", which);

@@ -473,9 +473,9 @@ int gdownload(hf_ctx* ctx, const GCsr& g, amg::Csr& h) {
 // level that does not fit the device kernels (a row longer than GA_MAXROW, a product row with more than GA_CAP candidate
 // columns), the coarsest level and a stalled coarsening go to amg::build, which continues from that level's operator.
 // HEATFLOW_AMG_SETUP=host takes build_amg (the host-only set-up) instead.
-int build_amg_device(hf_ctx* ctx) {
+int build_amg_device(hf_ctx* ctx, System& sys) {
   const auto t0 = std::chrono::steady_clock::now();
-  free_amg(ctx);
+  free_amg(sys);
   amg::Params prm;
   amg_params(ctx, prm);
   const bool f32 = ctx->amg_f32;
@@ -488,10 +488,10 @@ int build_amg_device(hf_ctx* ctx) {
   Ah.ptr.assign(ctx->h_rowptr.begin(), ctx->h_rowptr.end());
   Ah.idx.assign(ctx->h_colidx.begin(), ctx->h_colidx.end());
   Ah.val.resize(ctx->nnz);
-  HF_HIP(copy_sync(ctx, Ah.val.data(), ctx->d_A, sizeof(double) * ctx->nnz, hipMemcpyDeviceToHost));
+  HF_HIP(copy_sync(ctx, Ah.val.data(), sys.A, sizeof(double) * ctx->nnz, hipMemcpyDeviceToHost));
   lap("operator downloaded");
   GCsr Ag;                                         // the same operator on the device
-  Ag.nrow = Ag.ncol = ctx->n; Ag.nnz = ctx->nnz; Ag.ptr = ctx->d_rowptr; Ag.idx = ctx->d_colidx; Ag.val = ctx->d_A; Ag.owned = false;
+  Ag.nrow = Ag.ncol = ctx->n; Ag.nnz = ctx->nnz; Ag.ptr = ctx->d_rowptr; Ag.idx = ctx->d_colidx; Ag.val = sys.A; Ag.owned = false;
   const double nnz0 = static_cast<double>(ctx->nnz);
   double nnz_sum = nnz0;
   struct Cleanup { GCsr* g; ~Cleanup() { gfree(*g); } } cleanup_ag{&Ag};
@@ -528,7 +528,7 @@ int build_amg_device(hf_ctx* ctx) {
     HF_HIP(copy_sync(ctx, d_agg.p, agg.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice));
     HF_HIP(copy_sync(ctx, d_diag.p, d.data(), sizeof(double) * n, hipMemcpyHostToDevice));
     if (lev == 0) {
-      d_dinv = ctx->d_dinv;                        // k_dinv formed 1 / A_ii from the same values
+      d_dinv = sys.dinv;                        // k_dinv formed 1 / A_ii from the same values
     } else {
       HF_TRY(dev_alloc(ctx, &d_dinv_tmp.p, n));
       HF_HIP(copy_sync(ctx, d_dinv_tmp.p, dinv.data(), sizeof(double) * n, hipMemcpyHostToDevice));
@@ -594,8 +594,8 @@ int build_amg_device(hf_ctx* ctx) {
       lap("  fused legs");
     }
     // the level joins the hierarchy
-    ctx->amg.resize(static_cast<size_t>(lev) + 1);
-    DevLevel& L = ctx->amg[lev];
+    sys.amg.resize(static_cast<size_t>(lev) + 1);
+    DevLevel& L = sys.amg[lev];
     L.n = n;
     L.omega = omega;
     if (lev > 0) {
@@ -621,18 +621,18 @@ int build_amg_device(hf_ctx* ctx) {
   if (!amg::build(std::move(Ah), prm, H)) return fail(ctx, HF_ERR_STATE, "AMG set-up failed (non-positive diagonal or singular coarse operator)");
   lap("+ coarse levels on the host");
   const size_t base = static_cast<size_t>(lev);
-  ctx->amg.resize(base + H.levels.size());
-  HF_TRY(upload_host_levels(ctx, H, base));
+  sys.amg.resize(base + H.levels.size());
+  HF_TRY(upload_host_levels(ctx, sys, H, base));
   for (size_t k = 1; k < H.levels.size(); ++k) nnz_sum += static_cast<double>(H.levels[k].A.nnz());     // operator complexity: sum of nnz(A_l) / nnz(A_0)
   const double opc = nnz_sum / nnz0;
-  const int coarse_n = ctx->amg.size() == 1 ? 0 : H.levels.back().A.nrow;
-  return finish_amg(ctx, H.levels.back().A, coarse_n, opc, t0);
+  const int coarse_n = sys.amg.size() == 1 ? 0 : H.levels.back().A.nrow;
+  return finish_amg(ctx, sys, H.levels.back().A, coarse_n, opc, t0);
 }
 
-int build_amg_auto(hf_ctx* ctx) {
+int build_amg_auto(hf_ctx* ctx, System& sys) {
   static const bool host_only = std::getenv("HEATFLOW_AMG_SETUP") && std::string(std::getenv("HEATFLOW_AMG_SETUP")) == "host";
   static const bool study = std::getenv("HEATFLOW_AMG_PROLONG_STEPS") != nullptr;      // more than one prolongator smoothing step exists on the host only
-  return (host_only || study) ? build_amg(ctx) : build_amg_device(ctx);
+  return (host_only || study) ? build_amg(ctx, sys) : build_amg_device(ctx, sys);
 }
 
 }  // namespace

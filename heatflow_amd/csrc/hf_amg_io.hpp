@@ -47,9 +47,9 @@ int operator_print(hf_ctx* ctx, OperatorPrint& f) {
   HF_HIP(copy_sync(ctx, f.rhoc.data(), ctx->d_rhoc, sizeof(double) * ctx->tab_len, hipMemcpyDeviceToHost));
   for (int t = 0; t < ctx->tab_len; ++t)
     if (!ctx->h_tag_used[t]) f.kappa[t] = f.rhoc[t] = 0.0;        // tags the mesh does not use carry NaN: not part of the operator
-  f.nbc = ctx->nbc;
-  std::vector<int32_t> dofs(ctx->nbc);
-  if (ctx->nbc > 0) HF_HIP(copy_sync(ctx, dofs.data(), ctx->d_bc_dofs, sizeof(int32_t) * ctx->nbc, hipMemcpyDeviceToHost));
+  f.nbc = ctx->sys.nbc;
+  std::vector<int32_t> dofs(ctx->sys.nbc);
+  if (ctx->sys.nbc > 0) HF_HIP(copy_sync(ctx, dofs.data(), ctx->sys.bc_dofs, sizeof(int32_t) * ctx->sys.nbc, hipMemcpyDeviceToHost));
   f.bc_hash = fnv1a(dofs.data(), sizeof(int32_t) * dofs.size());
   f.an_hash = ctx->an.on ? ctx->an.hash : 0;
   return HF_OK;
@@ -98,8 +98,8 @@ void put_csr(BlobOut& o, const DevCsr& m, bool alias_fine /* level 0's A: the co
 int walk_hierarchy(hf_ctx* ctx, BlobOut& o, const OperatorPrint& f) {
   AmgBlobHeader h{};
   std::memcpy(h.magic, AMG_MAGIC, 8);
-  h.nnz = ctx->nnz; h.n = ctx->n; h.nl = static_cast<int32_t>(ctx->amg.size()); h.fuse0 = ctx->amg_fuse0; h.f32 = ctx->amg_f32 ? 1 : 0;
-  h.coarse_n = ctx->coarse_n; h.coarse_ld = ctx->coarse_ld; h.nbc = f.nbc; h.tab_len = ctx->tab_len; h.opc = ctx->amg_opc; h.dt = f.dt;
+  h.nnz = ctx->nnz; h.n = ctx->n; h.nl = static_cast<int32_t>(ctx->sys.amg.size()); h.fuse0 = ctx->amg_fuse0; h.f32 = ctx->amg_f32 ? 1 : 0;
+  h.coarse_n = ctx->sys.coarse_n; h.coarse_ld = ctx->sys.coarse_ld; h.nbc = f.nbc; h.tab_len = ctx->tab_len; h.opc = ctx->sys.amg_opc; h.dt = f.dt;
   h.bc_hash = f.bc_hash;
   h.scheme = f.scheme;
   h.an_hash = f.an_hash;
@@ -107,15 +107,15 @@ int walk_hierarchy(hf_ctx* ctx, BlobOut& o, const OperatorPrint& f) {
   o.host(&h, sizeof h);
   o.host(f.kappa.data(), sizeof(double) * f.kappa.size());
   o.host(f.rhoc.data(), sizeof(double) * f.rhoc.size());
-  for (size_t l = 0; l < ctx->amg.size(); ++l) {
-    const DevLevel& L = ctx->amg[l];
+  for (size_t l = 0; l < ctx->sys.amg.size(); ++l) {
+    const DevLevel& L = ctx->sys.amg[l];
     struct { int32_t n, pad_; double omega; } lv{L.n, 0, L.omega};
     o.host(&lv, sizeof lv);
     if (l > 0) o.dev(L.dinv, sizeof(double) * static_cast<size_t>(L.n));
     put_csr(o, L.A, l == 0);
     put_csr(o, L.P, false); put_csr(o, L.R, false); put_csr(o, L.Rt, false); put_csr(o, L.GP, false);
   }
-  if (ctx->coarse_n > 0) o.dev(ctx->d_coarse_inv, sizeof(double) * static_cast<size_t>(ctx->coarse_n) * ctx->coarse_ld);
+  if (ctx->sys.coarse_n > 0) o.dev(ctx->sys.coarse_inv, sizeof(double) * static_cast<size_t>(ctx->sys.coarse_n) * ctx->sys.coarse_ld);
   if (o.dst) {                                         // the total is known now: patch the header
     h.total_bytes = static_cast<int64_t>(o.at);
     std::memcpy(o.dst + head_at, &h, sizeof h);
@@ -241,12 +241,12 @@ int install_hierarchy(hf_ctx* ctx, const unsigned char* blob, size_t bytes) {
   if (!in.ok) return fail(ctx, HF_ERR_ARG, "hf_amg_install: blob truncated");
   theirs.kappa.assign(pk, pk + h.tab_len);
   theirs.rhoc.assign(pc, pc + h.tab_len);
-  free_amg(ctx);
-  ctx->amg.resize(h.nl);
+  free_amg(ctx->sys);
+  ctx->sys.amg.resize(h.nl);
   int prev_n = ctx->n;
-  auto bail = [&](int rc) { free_amg(ctx); return rc; };
+  auto bail = [&](int rc) { free_amg(ctx->sys); return rc; };
   for (int l = 0; l < h.nl; ++l) {
-    DevLevel& L = ctx->amg[l];
+    DevLevel& L = ctx->sys.amg[l];
     struct Lv { int32_t n, pad_; double omega; };
     const Lv* lv = static_cast<const Lv*>(in.take(sizeof(Lv)));
     if (!lv || lv->n <= 0 || (l == 0 && lv->n != ctx->n) || !(lv->omega > 0.0)) return bail(fail(ctx, HF_ERR_ARG, "hf_amg_install: bad level record"));
@@ -275,30 +275,30 @@ int install_hierarchy(hf_ctx* ctx, const unsigned char* blob, size_t bytes) {
     if (!ok) return bail(fail(ctx, HF_ERR_ARG, "hf_amg_install: the operators of level %d do not fit together", l));
     prev_n = last ? 0 : L.P.ncol;
   }
-  if (h.nl > 1 && h.coarse_n != ctx->amg.back().n) return bail(fail(ctx, HF_ERR_ARG, "hf_amg_install: dense inverse of %d rows for a coarsest level of %d", h.coarse_n, ctx->amg.back().n));
-  ctx->coarse_n = 0;
+  if (h.nl > 1 && h.coarse_n != ctx->sys.amg.back().n) return bail(fail(ctx, HF_ERR_ARG, "hf_amg_install: dense inverse of %d rows for a coarsest level of %d", h.coarse_n, ctx->sys.amg.back().n));
+  ctx->sys.coarse_n = 0;
   if (h.coarse_n > 0) {
     const size_t cnt = static_cast<size_t>(h.coarse_n) * h.coarse_ld;
     const double* inv = static_cast<const double*>(in.take(sizeof(double) * cnt));
     if (!inv) return bail(fail(ctx, HF_ERR_ARG, "hf_amg_install: blob truncated"));
-    int rc = dev_alloc(ctx, &ctx->d_coarse_inv, cnt);
+    int rc = dev_alloc(ctx, &ctx->sys.coarse_inv, cnt);
     if (rc != HF_OK) return bail(rc);
-    if (hipMemcpyAsync(ctx->d_coarse_inv, inv, sizeof(double) * cnt, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return bail(fail(ctx, HF_ERR_HIP, "hf_amg_install: copy failed"));
+    if (hipMemcpyAsync(ctx->sys.coarse_inv, inv, sizeof(double) * cnt, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) return bail(fail(ctx, HF_ERR_HIP, "hf_amg_install: copy failed"));
     if (h.f32) {
-      rc = dev_alloc(ctx, &ctx->d_coarse_inv_f, cnt);
+      rc = dev_alloc(ctx, &ctx->sys.coarse_inv_f, cnt);
       if (rc != HF_OK) return bail(rc);
-      hipLaunchKernelGGL(k_to_float, dim3(1024), dim3(256), 0, ctx->stream, cnt, ctx->d_coarse_inv, ctx->d_coarse_inv_f);
+      hipLaunchKernelGGL(k_to_float, dim3(1024), dim3(256), 0, ctx->stream, cnt, ctx->sys.coarse_inv, ctx->sys.coarse_inv_f);
     }
-    ctx->coarse_n = h.coarse_n; ctx->coarse_ld = h.coarse_ld;
+    ctx->sys.coarse_n = h.coarse_n; ctx->sys.coarse_ld = h.coarse_ld;
   }
-  ctx->amg_fuse0 = h.fuse0; ctx->amg_f32 = h.f32 != 0; ctx->amg_opc = h.opc;
-  int rc = wire_levels(ctx);
+  ctx->amg_fuse0 = h.fuse0; ctx->amg_f32 = h.f32 != 0; ctx->sys.amg_opc = h.opc;
+  int rc = wire_levels(ctx, ctx->sys);
   if (rc != HF_OK) return bail(rc);
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return bail(fail(ctx, HF_ERR_HIP, "hf_amg_install: copies failed"));
-  ctx->amg_print = std::move(theirs);
-  ctx->amg_ready = true;
-  ctx->amg_fine_stale = true;                    // until hf_assemble has compared this context's operator with the fingerprint
-  ctx->amg_setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  ctx->sys.amg_print = std::move(theirs);
+  ctx->sys.amg_ready = true;
+  ctx->sys.amg_fine_stale = true;                    // until hf_assemble has compared this context's operator with the fingerprint
+  ctx->sys.amg_setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return HF_OK;
 }
 

@@ -962,30 +962,27 @@ void blaunch_csr(hf_ctx* c, const DevCsr& m, const double* x, double* y) {
 template <int NV, int OPK>
 struct BatchOps {
   static constexpr bool DPC = OPK != OP_SHARED;       // D^-1 stored per column
-  static BOp Aop(hf_ctx* c) {
-    const hf_ctx::Batch& B = c->batch;
+  static BOp Aop(hf_ctx* c, const hf_ctx::Batch& B) {
     BOp o{};
-    o.v0 = B.sysA ? B.sysA : (OPK == OP_PERCOL ? B.A : c->d_A);
+    o.v0 = B.sysA ? B.sysA : (OPK == OP_PERCOL ? B.A : c->sys.A);
     o.v1 = B.A1;
     for (int j = 0; j < NV_MAX; ++j) o.delta[j] = B.delta[j];
     return o;
   }
-  static BOp Liftop(hf_ctx* c) {
-    const hf_ctx::Batch& B = c->batch;
+  static BOp Liftop(hf_ctx* c, const hf_ctx::Batch& B) {
     BOp o{};
-    o.v0 = OPK == OP_PERCOL ? B.lift_val : c->d_lift_val;
+    o.v0 = OPK == OP_PERCOL ? B.lift_val : c->sys.lift_val;
     o.v1 = B.lift1;
     for (int j = 0; j < NV_MAX; ++j) o.delta[j] = B.delta[j];
     return o;
   }
-  static const double* Avals(hf_ctx* c) { return c->d_A; }   // tag: "the system operator" (any pointer but d_M)
-  static const double* Dinv(hf_ctx* c) { return c->batch.sysDinv ? c->batch.sysDinv : (DPC ? c->batch.dinv : c->d_dinv); }
+  static const double* Avals(hf_ctx* c) { return c->sys.A; }   // tag: "the system operator" (any pointer but d_M)
+  static const double* Dinv(hf_ctx* c, const hf_ctx::Batch& B) { return B.sysDinv ? B.sysDinv : (DPC ? B.dinv : c->sys.dinv); }
 
   template <int MODE>
-  static void spmv(hf_ctx* c, const double* vals, const double* x, double* y, double* part0 = nullptr, const double* bvec = nullptr,
+  static void spmv(hf_ctx* c, hf_ctx::Batch& B, const double* vals, const double* x, double* y, double* part0 = nullptr, const double* bvec = nullptr,
                    double* pvec = nullptr, double* part1 = nullptr, double* part2 = nullptr, double w = 0.0, int parity = 0,
                    hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr /* hf_set_profile: the launch carries its own start / stop events */) {
-    hf_ctx::Batch& B = c->batch;
     if (B.lds && OPK != OP_PERCOL) {    // chunk operands staged in LDS, 16-bit column positions
       const hf_ctx::BatchCols& T = c->bcols;
       const BComp comp{T.ptr, T.dict, T.own, T.id, T.rpc, T.nchunks, T.cap_nnz, T.cap_dict};
@@ -995,15 +992,15 @@ struct BatchOps {
         BOp m{};
         m.v0 = c->d_M;
         hipLaunchKernelGGL((kb_spmv_lds<MODE, NV, OP_SHARED>), dim3(grid), dim3(KB_BT), batch_lds_bytes(T.cap_nnz, T.cap_dict, NV, false), c->stream,
-                           c->n, c->d_rowptr, m, x, y, B.scal, part0, bvec, c->d_dinv, pvec, part1, part2, w, B.red, parity, comp, B.Pb);
+                           c->n, c->d_rowptr, m, x, y, B.scal, part0, bvec, c->sys.dinv, pvec, part1, part2, w, B.red, parity, comp, B.Pb);
       } else {
         constexpr int OPL = OPK == OP_PERCOL ? OP_SHARED : OPK;     // (never instantiated for per-column values)
         if (ev0 != nullptr)
           hipExtLaunchKernelGGL((kb_spmv_lds<MODE, NV, OPL>), dim3(grid), dim3(KB_BT), static_cast<std::uint32_t>(batch_lds_bytes(T.cap_nnz, T.cap_dict, NV, OPL == OP_AFFINE)),
-                                c->stream, ev0, ev1, 0u, c->n, c->d_rowptr, Aop(c), x, y, B.scal, part0, bvec, Dinv(c), pvec, part1, part2, w, B.red, parity, comp, B.Pb);
+                                c->stream, ev0, ev1, 0u, c->n, c->d_rowptr, Aop(c, B), x, y, B.scal, part0, bvec, Dinv(c, B), pvec, part1, part2, w, B.red, parity, comp, B.Pb);
         else
           hipLaunchKernelGGL((kb_spmv_lds<MODE, NV, OPL>), dim3(grid), dim3(KB_BT), batch_lds_bytes(T.cap_nnz, T.cap_dict, NV, OPL == OP_AFFINE), c->stream,
-                             c->n, c->d_rowptr, Aop(c), x, y, B.scal, part0, bvec, Dinv(c), pvec, part1, part2, w, B.red, parity, comp, B.Pb);
+                             c->n, c->d_rowptr, Aop(c, B), x, y, B.scal, part0, bvec, Dinv(c, B), pvec, part1, part2, w, B.red, parity, comp, B.Pb);
       }
       return;
     }
@@ -1012,19 +1009,18 @@ struct BatchOps {
       BOp m{};
       m.v0 = c->d_M;
       hipLaunchKernelGGL((kb_spmv<MODE, NV, OP_SHARED>), dim3(B.Pb), dim3(KB_BT), 0, c->stream, c->n, c->d_rowptr, c->d_colidx, m, x, y,
-                         B.scal, part0, bvec, c->d_dinv, pvec, part1, part2, w, B.red, parity);
+                         B.scal, part0, bvec, c->sys.dinv, pvec, part1, part2, w, B.red, parity);
     } else if (ev0 != nullptr) {
-      hipExtLaunchKernelGGL((kb_spmv<MODE, NV, OPK>), dim3(B.Pb), dim3(KB_BT), 0u, c->stream, ev0, ev1, 0u, c->n, c->d_rowptr, c->d_colidx, Aop(c), x, y,
-                            B.scal, part0, bvec, Dinv(c), pvec, part1, part2, w, B.red, parity);
+      hipExtLaunchKernelGGL((kb_spmv<MODE, NV, OPK>), dim3(B.Pb), dim3(KB_BT), 0u, c->stream, ev0, ev1, 0u, c->n, c->d_rowptr, c->d_colidx, Aop(c, B), x, y,
+                            B.scal, part0, bvec, Dinv(c, B), pvec, part1, part2, w, B.red, parity);
     } else {
-      hipLaunchKernelGGL((kb_spmv<MODE, NV, OPK>), dim3(B.Pb), dim3(KB_BT), 0, c->stream, c->n, c->d_rowptr, c->d_colidx, Aop(c), x, y,
-                         B.scal, part0, bvec, Dinv(c), pvec, part1, part2, w, B.red, parity);
+      hipLaunchKernelGGL((kb_spmv<MODE, NV, OPK>), dim3(B.Pb), dim3(KB_BT), 0, c->stream, c->n, c->d_rowptr, c->d_colidx, Aop(c, B), x, y,
+                         B.scal, part0, bvec, Dinv(c, B), pvec, part1, part2, w, B.red, parity);
     }
   }
 
   // BDF2 right-hand side on the shared M (kb_spmv / kb_spmv_lds mode 12, or 14 with the per-column load F)
-  static void rhs_bdf2(hf_ctx* c, const double* u, const double* uprev, double* b, const double* F, double* ucopy, double w) {
-    hf_ctx::Batch& B = c->batch;
+  static void rhs_bdf2(hf_ctx* c, hf_ctx::Batch& B, const double* u, const double* uprev, double* b, const double* F, double* ucopy, double w) {
     BOp m{};
     m.v0 = c->d_M;
     if (B.lds) {
@@ -1049,80 +1045,77 @@ struct BatchOps {
                          B.scal, nullptr, uprev, nullptr, ucopy, nullptr, nullptr, w, B.red, 0);
   }
 
-  static void reduce(hf_ctx* c, const double* part_a, double* out_a, const double* part_b = nullptr, double* out_b = nullptr,
+  static void reduce(hf_ctx* c, const hf_ctx::Batch& B, const double* part_a, double* out_a, const double* part_b = nullptr, double* out_b = nullptr,
                      Scal* test = nullptr) {
-    hipLaunchKernelGGL(kb_reduce, dim3(part_b ? 2 * NV : NV), dim3(TPB), 0, c->stream, c->batch.Pb, NV, part_a, out_a, part_b, out_b, test,
-                       test ? c->batch.d_mirror : static_cast<ScalMirror*>(nullptr));
+    hipLaunchKernelGGL(kb_reduce, dim3(part_b ? 2 * NV : NV), dim3(TPB), 0, c->stream, B.Pb, NV, part_a, out_a, part_b, out_b, test,
+                       test ? B.d_mirror : static_cast<ScalMirror*>(nullptr));
   }
 
   // z = B r for every column: the V(1,1) cycle of hf_solver.hpp's vcycle() on interleaved vectors
-  static void vcycle(hf_ctx* c, int out_slot) {
-    hf_ctx::Batch& B = c->batch;
-    const int nl = static_cast<int>(c->amg.size());
-    const double w0 = c->amg[0].omega;
+  static void vcycle(hf_ctx* c, hf_ctx::Batch& B, int out_slot) {
+    const int nl = static_cast<int>(c->sys.amg.size());
+    const double w0 = c->sys.amg[0].omega;
     double* rz_out = B.part_rz + static_cast<size_t>(out_slot) * NV * MAXP;
     if (nl == 1) {
-      spmv<4>(c, Avals(c), B.z, B.z2, rz_out, B.r, nullptr, nullptr, nullptr, w0);
-      reduce(c, rz_out, B.red->rz[out_slot], B.part_zz, B.red->zz);
+      spmv<4>(c, B, Avals(c), B.z, B.z2, rz_out, B.r, nullptr, nullptr, nullptr, w0);
+      reduce(c, B, rz_out, B.red->rz[out_slot], B.part_zz, B.red->zz);
       return;
     }
-    spmv<3>(c, Avals(c), B.z, B.tmp, nullptr, B.r);
-    blaunch_csr<NV, 0>(c, c->amg[0].R, B.tmp, B.lev[1].b);
-    for (int l = 1; l + 1 < nl; ++l) blaunch_csr<NV, 0>(c, c->amg[l].Rt, B.lev[l].b, B.lev[l + 1].b);
+    spmv<3>(c, B, Avals(c), B.z, B.tmp, nullptr, B.r);
+    blaunch_csr<NV, 0>(c, c->sys.amg[0].R, B.tmp, B.lev[1].b);
+    for (int l = 1; l + 1 < nl; ++l) blaunch_csr<NV, 0>(c, c->sys.amg[l].Rt, B.lev[l].b, B.lev[l + 1].b);
     {
-      const DevLevel& Lc = c->amg[nl - 1];
-      if (c->coarse_n > 0) {
+      const DevLevel& Lc = c->sys.amg[nl - 1];
+      if (c->sys.coarse_n > 0) {
         const int g = std::max(1, std::min((Lc.n + 3) / 4, 1024));
         static const int dense_cpl = std::getenv("HEATFLOW_BATCH_DENSE_CPL") ? std::atoi(std::getenv("HEATFLOW_BATCH_DENSE_CPL")) : NV;   // measured: a lane per column wins (few rows)
         constexpr int DC = NV >= 4 ? 4 : NV;
-        if (dense_cpl < NV && c->d_coarse_inv_f != nullptr)
-          hipLaunchKernelGGL((kb_dense_rc<NV, DC, float>), dim3(g), dim3(TPB), 0, c->stream, Lc.n, c->coarse_ld, c->d_coarse_inv_f,
+        if (dense_cpl < NV && c->sys.coarse_inv_f != nullptr)
+          hipLaunchKernelGGL((kb_dense_rc<NV, DC, float>), dim3(g), dim3(TPB), 0, c->stream, Lc.n, c->sys.coarse_ld, c->sys.coarse_inv_f,
                              B.lev[nl - 1].b, B.lev[nl - 1].res);
-        else if (c->d_coarse_inv_f != nullptr)
-          hipLaunchKernelGGL((kb_dense<NV, float>), dim3(g), dim3(TPB), 0, c->stream, Lc.n, c->coarse_ld, c->d_coarse_inv_f,
+        else if (c->sys.coarse_inv_f != nullptr)
+          hipLaunchKernelGGL((kb_dense<NV, float>), dim3(g), dim3(TPB), 0, c->stream, Lc.n, c->sys.coarse_ld, c->sys.coarse_inv_f,
                              B.lev[nl - 1].b, B.lev[nl - 1].res);
         else
-          hipLaunchKernelGGL((kb_dense<NV, double>), dim3(g), dim3(TPB), 0, c->stream, Lc.n, c->coarse_ld, c->d_coarse_inv,
+          hipLaunchKernelGGL((kb_dense<NV, double>), dim3(g), dim3(TPB), 0, c->stream, Lc.n, c->sys.coarse_ld, c->sys.coarse_inv,
                              B.lev[nl - 1].b, B.lev[nl - 1].res);
       } else {
         const int g = std::max(1, std::min((Lc.n * NV + TPB - 1) / TPB, 1024));
         hipLaunchKernelGGL((kb_scale<NV>), dim3(g), dim3(TPB), 0, c->stream, Lc.n, Lc.omega, Lc.dinv, B.lev[nl - 1].b, B.lev[nl - 1].res);
       }
     }
-    for (int l = nl - 2; l >= 1; --l) blaunch_csr<NV, 0>(c, c->amg[l].GP, B.lev[l].cat, B.lev[l].res);
-    blaunch_csr<NV, 1>(c, c->amg[0].P, B.lev[1].res, B.z);
-    spmv<4>(c, Avals(c), B.z, B.z2, rz_out, B.r, nullptr, nullptr, nullptr, w0);
-    reduce(c, rz_out, B.red->rz[out_slot], B.part_zz, B.red->zz);   // r.z of this cycle and (D^-1 r)^2 of the last update
+    for (int l = nl - 2; l >= 1; --l) blaunch_csr<NV, 0>(c, c->sys.amg[l].GP, B.lev[l].cat, B.lev[l].res);
+    blaunch_csr<NV, 1>(c, c->sys.amg[0].P, B.lev[1].res, B.z);
+    spmv<4>(c, B, Avals(c), B.z, B.z2, rz_out, B.r, nullptr, nullptr, nullptr, w0);
+    reduce(c, B, rz_out, B.red->rz[out_slot], B.part_zz, B.red->zz);   // r.z of this cycle and (D^-1 r)^2 of the last update
   }
 
   // `part` (multigrid only): the whole iteration, up to the reduction that tests and publishes, or the V-cycle after it
-  static void iteration(hf_ctx* c, bool use_amg, int parity, CyclePart part = CYCLE_ALL) {
-    if (part == CYCLE_REST) { vcycle(c, parity ^ 1); return; }
-    hf_ctx::Batch& B = c->batch;
+  static void iteration(hf_ctx* c, hf_ctx::Batch& B, bool use_amg, int parity, CyclePart part = CYCLE_ALL) {
+    if (part == CYCLE_REST) { vcycle(c, B, parity ^ 1); return; }
     // hf_set_profile: the iteration heads of a solve (its first PROF_PAIRS) carry event pairs, harvested when the solve ends
     const bool timed = c->prof && c->prof_used < PROF_PAIRS;
     hipEvent_t e0 = timed ? c->prof_ev[2 * c->prof_used] : nullptr, e1 = timed ? c->prof_ev[2 * c->prof_used + 1] : nullptr;
     if (timed) c->prof_used++;
     if (use_amg) {
-      spmv<9>(c, Avals(c), B.z2, B.Ap, B.part_pAp, nullptr, B.p, B.part_rz, B.part_zz, 0.0, parity, e0, e1);
-      reduce(c, B.part_pAp, B.red->pAp);
+      spmv<9>(c, B, Avals(c), B.z2, B.Ap, B.part_pAp, nullptr, B.p, B.part_rz, B.part_zz, 0.0, parity, e0, e1);
+      reduce(c, B, B.part_pAp, B.red->pAp);
       hipLaunchKernelGGL((kb_update<NV, true, DPC>), dim3(B.Pb), dim3(TPB), 0, c->stream, c->n, B.red, parity, B.scal,
-                         B.part_rz, B.part_zz, B.u, B.r, B.p, B.Ap, Dinv(c), c->amg[0].omega, B.z);
+                         B.part_rz, B.part_zz, B.u, B.r, B.p, B.Ap, Dinv(c, B), c->sys.amg[0].omega, B.z);
       // (D^-1 r)^2 of the new iterates: columns that have converged are marked done here, so that the V-cycle below
       // does no work for them (it used to be found out by the next iteration head, one cycle too late)
-      reduce(c, B.part_zz, B.red->zz, nullptr, nullptr, B.scal);
-      if (part == CYCLE_ALL) vcycle(c, parity ^ 1);
+      reduce(c, B, B.part_zz, B.red->zz, nullptr, nullptr, B.scal);
+      if (part == CYCLE_ALL) vcycle(c, B, parity ^ 1);
     } else {
-      spmv<9>(c, Avals(c), B.z, B.Ap, B.part_pAp, nullptr, B.p, B.part_rz, B.part_zz, 0.0, parity, e0, e1);
-      reduce(c, B.part_pAp, B.red->pAp);
+      spmv<9>(c, B, Avals(c), B.z, B.Ap, B.part_pAp, nullptr, B.p, B.part_rz, B.part_zz, 0.0, parity, e0, e1);
+      reduce(c, B, B.part_pAp, B.red->pAp);
       hipLaunchKernelGGL((kb_update<NV, false, DPC>), dim3(B.Pb), dim3(TPB), 0, c->stream, c->n, B.red, parity, B.scal,
-                         B.part_rz, B.part_zz, B.u, B.r, B.p, B.Ap, Dinv(c), 0.0, B.z);
-      reduce(c, B.part_rz + static_cast<size_t>(parity ^ 1) * NV * MAXP, B.red->rz[parity ^ 1], B.part_zz, B.red->zz);
+                         B.part_rz, B.part_zz, B.u, B.r, B.p, B.Ap, Dinv(c, B), 0.0, B.z);
+      reduce(c, B, B.part_rz + static_cast<size_t>(parity ^ 1) * NV * MAXP, B.red->rz[parity ^ 1], B.part_zz, B.red->zz);
     }
   }
 
-  static int read_scal(hf_ctx* ctx, bool* all_done, int* max_iters, bool* breakdown) {
-    hf_ctx::Batch& B = ctx->batch;
+  static int read_scal(hf_ctx* ctx, hf_ctx::Batch& B, bool* all_done, int* max_iters, bool* breakdown) {
     HF_HIP(hipMemcpyAsync(B.h_scal, B.scal, sizeof(Scal) * NV, hipMemcpyDeviceToHost, ctx->stream));
     HF_HIP(hipStreamSynchronize(ctx->stream));
     *all_done = true; *max_iters = 0; *breakdown = false;
@@ -1136,9 +1129,8 @@ struct BatchOps {
 
   // Wait on host memory until every column's iterate after update k has been tested or the column has ended
   // (wait_tested of the single-column loop, per column); fills B.h_scal from the mirrors
-  static int wait_tested(hf_ctx* ctx, int k, bool* all_done, int* max_iters, bool* breakdown) {
+  static int wait_tested(hf_ctx* ctx, hf_ctx::Batch& B, int k, bool* all_done, int* max_iters, bool* breakdown) {
     static const double limit_s = std::getenv("HEATFLOW_POLL_TIMEOUT_S") ? std::atof(std::getenv("HEATFLOW_POLL_TIMEOUT_S")) : 60.0;
-    hf_ctx::Batch& B = ctx->batch;
     const unsigned ep = B.epoch;
     const auto t0 = std::chrono::steady_clock::now();
     auto last_query = t0;
@@ -1174,13 +1166,13 @@ struct BatchOps {
   }
 
   // PCG on all columns, started from B.u; iteration counts / residuals are left in B.h_scal
-  static int pcg(hf_ctx* ctx, bool use_amg, double rtol, double atol, int max_it) {
-    if (!ctx->prof) return pcg_run(ctx, use_amg, rtol, atol, max_it);
+  static int pcg(hf_ctx* ctx, hf_ctx::Batch& B, bool use_amg, double rtol, double atol, int max_it) {
+    if (!ctx->prof) return pcg_run(ctx, B, use_amg, rtol, atol, max_it);
     ctx->prof_used = 0;
-    const int rc = pcg_run(ctx, use_amg, rtol, atol, max_it);
+    const int rc = pcg_run(ctx, B, use_amg, rtol, atol, max_it);
     (void)hipStreamSynchronize(ctx->stream);
     int most = 0;                                     // iteration heads that really ran: those of the slowest column
-    for (int j = 0; j < NV; ++j) most = std::max(most, ctx->batch.h_scal[j].iters);
+    for (int j = 0; j < NV; ++j) most = std::max(most, B.h_scal[j].iters);
     for (int k = 0; k < ctx->prof_used && k < most; ++k) {
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, ctx->prof_ev[2 * k], ctx->prof_ev[2 * k + 1]) == hipSuccess) { ctx->prof_spmv_ms += ms; ctx->prof_spmv_n += 1; }
@@ -1189,20 +1181,19 @@ struct BatchOps {
     return rc;
   }
 
-  static int pcg_run(hf_ctx* ctx, bool use_amg, double rtol, double atol, int max_it) {
-    hf_ctx::Batch& B = ctx->batch;
+  static int pcg_run(hf_ctx* ctx, hf_ctx::Batch& B, bool use_amg, double rtol, double atol, int max_it) {
     // a new epoch instead of a reset of the mirrors: launches of the previous solve's blind burst may still be queued
     // (they publish nothing once their column has converged, and whatever reaches the mirrors late carries the old epoch)
     B.epoch += 1;
     HF_HIP(hipMemsetAsync(B.scal, 0, sizeof(Scal) * NV, ctx->stream));
     if (!use_amg) {
-      spmv<2>(ctx, Avals(ctx), B.u, B.r, B.part_rz, B.b, B.z, B.part_zz, B.part_bn, 0.0);
+      spmv<2>(ctx, B, Avals(ctx), B.u, B.r, B.part_rz, B.b, B.z, B.part_zz, B.part_bn, 0.0);
       hipLaunchKernelGGL((kb_begin<NV>), dim3(1), dim3(TPB), 0, ctx->stream, B.Pb, rtol, atol, B.part_zz, B.part_bn, B.part_rz, B.scal, B.red, B.d_mirror, B.epoch);
     } else {
-      spmv<5>(ctx, Avals(ctx), B.u, B.r, nullptr, B.b, B.z, B.part_zz, B.part_bn, ctx->amg[0].omega);
+      spmv<5>(ctx, B, Avals(ctx), B.u, B.r, nullptr, B.b, B.z, B.part_zz, B.part_bn, ctx->sys.amg[0].omega);
       hipLaunchKernelGGL((kb_begin<NV>), dim3(1), dim3(TPB), 0, ctx->stream, B.Pb, rtol, atol, B.part_zz, B.part_bn,
                          static_cast<const double*>(nullptr), B.scal, B.red, B.d_mirror, B.epoch);
-      vcycle(ctx, 0);
+      vcycle(ctx, B, 0);
     }
     HF_HIP(hipGetLastError());
     bool all_done = false, breakdown = false;
@@ -1212,7 +1203,7 @@ struct BatchOps {
       // columns publishes every column's outcome, and the V-cycle that follows it gives the host the time to queue
       // the next iteration
       if (B.pred_iters <= 0) {
-        HF_TRY(wait_tested(ctx, 0, &all_done, &iters, &breakdown));
+        HF_TRY(wait_tested(ctx, B, 0, &all_done, &iters, &breakdown));
         if (all_done) return HF_OK;
       }
       // after the blind burst the V-cycle of an iteration is held back until its test says that a column still needs it
@@ -1221,13 +1212,13 @@ struct BatchOps {
       int burst = std::max(1, std::min(max_it, B.pred_iters - 2));
       bool rest_pending = false;
       while (true) {
-        if (rest_pending) iteration(ctx, true, (launched - 1) & 1, CYCLE_REST);
+        if (rest_pending) iteration(ctx, B, true, (launched - 1) & 1, CYCLE_REST);
         const bool split = hold_back && burst == 1 && launched > 0;
-        for (int k = 0; k < burst; ++k) iteration(ctx, true, (launched + k) & 1, split ? CYCLE_FIRST : CYCLE_ALL);
+        for (int k = 0; k < burst; ++k) iteration(ctx, B, true, (launched + k) & 1, split ? CYCLE_FIRST : CYCLE_ALL);
         rest_pending = split;
         launched += burst;
         HF_HIP(hipGetLastError());
-        HF_TRY(wait_tested(ctx, launched, &all_done, &iters, &breakdown));
+        HF_TRY(wait_tested(ctx, B, launched, &all_done, &iters, &breakdown));
         if (all_done || breakdown || launched >= max_it) break;
         burst = 1;
       }
@@ -1237,15 +1228,15 @@ struct BatchOps {
       return HF_OK;
     }
     if (B.pred_iters <= 0) {
-      HF_TRY(read_scal(ctx, &all_done, &iters, &breakdown));
+      HF_TRY(read_scal(ctx, B, &all_done, &iters, &breakdown));
       if (all_done) return HF_OK;
     }
     int burst = std::max(1, std::min(max_it, B.pred_iters > 0 ? B.pred_iters : (use_amg ? 8 : 32)));
     while (true) {
-      for (int k = 0; k < burst; ++k) iteration(ctx, use_amg, (launched + k) & 1);
+      for (int k = 0; k < burst; ++k) iteration(ctx, B, use_amg, (launched + k) & 1);
       launched += burst;
       HF_HIP(hipGetLastError());
-      HF_TRY(read_scal(ctx, &all_done, &iters, &breakdown));
+      HF_TRY(read_scal(ctx, B, &all_done, &iters, &breakdown));
       if (all_done || launched >= max_it) break;
       burst = std::max(1, std::min(std::max(use_amg ? 1 : 8, launched / 8), max_it - launched));
     }
@@ -1267,32 +1258,31 @@ struct BatchOps {
   // load B.load (interleaved; the tangent stage of hf_run_tangent) when one is set.  Start vector:
   // per column the A-norm projection of the new solution on the span of its last solutions (kind 3 of the
   // single-column loop, without the boundary responses)
-  static int step(hf_ctx* ctx, const double* g_dev, double rtol, double atol, int max_it) {
-    hf_ctx::Batch& B = ctx->batch;
-    const int nb = ctx->nbc;
+  static int step(hf_ctx* ctx, hf_ctx::Batch& B, const double* g_dev, double rtol, double atol, int max_it) {
+    const int nb = ctx->sys.nbc;
     if (ctx->scheme == HF_TIME_BDF2) {
       // b = M (4/3 u^n - 1/3 u^{n-1}) (+ dt' F) in one pass over M; the same pass copies u^n into `ustart`, which then
       // becomes u^{n-1} of the next step (pointer swap, no copy).  From a rest start (no history) u^{n-1} = u^n.
-      rhs_bdf2(ctx, B.u, B.bdf_hist ? B.uprev : B.u, B.b, B.load, B.ustart, ctx->dt);
+      rhs_bdf2(ctx, B, B.u, B.bdf_hist ? B.uprev : B.u, B.b, B.load, B.ustart, ctx->dt);
       std::swap(B.uprev, B.ustart);
       B.bdf_hist = true;
     } else if (B.load != nullptr) {
-      spmv<10>(ctx, ctx->d_M, B.u, B.b, nullptr, B.load, nullptr, nullptr, nullptr, ctx->dt);   // b = M u + dt F
+      spmv<10>(ctx, B, ctx->d_M, B.u, B.b, nullptr, B.load, nullptr, nullptr, nullptr, ctx->dt);   // b = M u + dt F
     } else {
-      spmv<0>(ctx, ctx->d_M, B.u, B.b);
+      spmv<0>(ctx, B, ctx->d_M, B.u, B.b);
     }
     if (nb > 0) {
-      if (ctx->nlift_rows > 0) {
-        const int thr = ctx->nlift_rows * NV;
-        hipLaunchKernelGGL((kb_lift<NV, OPK>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift_rows, ctx->d_lift_rows,
-                           ctx->d_lift_ptr, ctx->d_lift_bc, Liftop(ctx), g_dev, B.b);
+      if (ctx->sys.nlift_rows > 0) {
+        const int thr = ctx->sys.nlift_rows * NV;
+        hipLaunchKernelGGL((kb_lift<NV, OPK>), dim3((thr + 255) / 256), dim3(256), 0, ctx->stream, ctx->sys.nlift_rows, ctx->sys.lift_rows,
+                           ctx->sys.lift_ptr, ctx->sys.lift_bc, Liftop(ctx, B), g_dev, B.b);
       }
     }
     ProjVecs act = proj_active(B);
     if (B.noproj) act.m = 0;   // another operator every step: the columns start from s^n with their boundary values set
     // set_bc once: after the combination when there is one (the basis vectors are zero on the Dirichlet rows)
     if (nb > 0 && act.m == 0)
-      hipLaunchKernelGGL((kb_set_bc<NV>), dim3((nb * NV + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, g_dev, B.b, B.u);
+      hipLaunchKernelGGL((kb_set_bc<NV>), dim3((nb * NV + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->sys.bc_dofs, g_dev, B.b, B.u);
     if (act.m > 0) {
       hipLaunchKernelGGL((kb_proj_dots<NV>), dim3(B.Pb), dim3(TPB), 0, ctx->stream, ctx->n, act, B.b,
                          B.ppending >= 0 ? B.pF[B.ppending] : static_cast<const double*>(nullptr), B.ppart);
@@ -1300,15 +1290,15 @@ struct BatchOps {
       B.ppending = -1;
       hipLaunchKernelGGL((kb_proj_combine<NV>), dim3(B.Pb), dim3(TPB), 0, ctx->stream, ctx->n, act, B.palpha, B.u);
       if (nb > 0)
-        hipLaunchKernelGGL((kb_set_bc<NV>), dim3((nb * NV + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, g_dev, B.b, B.u);
+        hipLaunchKernelGGL((kb_set_bc<NV>), dim3((nb * NV + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->sys.bc_dofs, g_dev, B.b, B.u);
     }
-    const bool use_amg = ctx->precond == 1 && ctx->amg_ready;
-    const int rc = pcg(ctx, use_amg, rtol, atol, max_it);
+    const bool use_amg = ctx->sys.precond == 1 && ctx->sys.amg_ready;
+    const int rc = pcg(ctx, B, use_amg, rtol, atol, max_it);
     if (rc == HF_OK && !B.noproj) {   // (solution with zeroed Dirichlet entries, right-hand side) joins every column's basis
       const int slot = B.pnext;
       hipLaunchKernelGGL(k_copy2, dim3(1024), dim3(TPB), 0, ctx->stream, ctx->n * NV, B.u, B.pV[slot], B.b, B.pF[slot]);
       if (nb > 0)
-        hipLaunchKernelGGL((kb_zero_bc<NV>), dim3((nb * NV + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, B.pV[slot]);
+        hipLaunchKernelGGL((kb_zero_bc<NV>), dim3((nb * NV + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->sys.bc_dofs, B.pV[slot]);
       B.pused[slot] = true;
       B.ppending = slot;
       B.pnext = (slot + 1) % PROJ_MH;
@@ -1319,8 +1309,7 @@ struct BatchOps {
 
 // dispatch over (nv, per-column operator)
 template <typename F>
-int batch_dispatch(hf_ctx* ctx, F&& f) {
-  const hf_ctx::Batch& B = ctx->batch;
+int batch_dispatch(hf_ctx* ctx, const hf_ctx::Batch& B, F&& f) {
   switch (B.nv * 4 + B.opk) {
     case 8: return f(BatchOps<2, OP_SHARED>());
     case 9: return f(BatchOps<2, OP_PERCOL>());

@@ -118,7 +118,7 @@ struct hf_ctx {
   std::string err;
   double last_ms = 0.0;
 
-  int32_t n = 0, ne = 0, nbc = 0;
+  int32_t n = 0, ne = 0;
   int64_t nnz = 0;
   int nchunks = 0, P = 0;      // 256-row chunks and grid of the vector kernels / assembly
   int nchunks_s = 0, Ps = 0;   // 512-row chunks and grid of the SpMV kernel (Ps <= P partials)
@@ -130,7 +130,7 @@ struct hf_ctx {
   int max_cdict = 0;
   bool cdict_own = false;      // every chunk's own rows sit contiguously in its column list (each row stores its diagonal): the kernels take x[row] from the staged slice
   bool c16 = true;             // HEATFLOW_SPMV_C16=0 keeps the 32-bit column stream
-  // value lists of d_A ([0]) and d_M ([1]) (ValComp in hf_kernels.hpp): a second, lossless encoding of the same values for k_spmv
+  // value lists of sys.A ([0]) and d_M ([1]) (ValComp in hf_kernels.hpp): a second, lossless encoding of the same values for k_spmv
   // - per SpMV chunk the distinct 64-bit patterns of its values in ascending order, per nonzero the 16-bit position in that list
   // packed with the 16-bit column position.  Built at the end of hf_assemble (value_lists_build in hf_pattern.hpp); `src` is
   // the array the tables encode: launch_spmv takes them for that pointer only, and whoever writes the array afterwards clears
@@ -192,14 +192,8 @@ struct hf_ctx {
     std::vector<double> h_m;    // (m_z, m_r) by cell tag, 1 where isotropic: the weights of a kappa column (hf_tangent_setup_dir)
     uint64_t hash = 0;          // of the multipliers by cell tag (0 while off): part of the operator's fingerprint (OperatorPrint)
   } an;
-  // device: matrices
-  double *d_M = nullptr, *d_A = nullptr, *d_dinv = nullptr;
-  // device: Dirichlet
-  int32_t* d_bc_dofs = nullptr;
-  double* d_g = nullptr;
-  int32_t nlift_rows = 0, nlift = 0;
-  int32_t *d_lift_rows = nullptr, *d_lift_ptr = nullptr, *d_lift_bc = nullptr, *d_lift_slot = nullptr;
-  double* d_lift_val = nullptr;
+  // device: the mass matrix (the operators that are solved with live in a System, below)
+  double* d_M = nullptr;
   // device: vectors
   double *d_u = nullptr, *d_b = nullptr, *d_r = nullptr, *d_p = nullptr, *d_Ap = nullptr;
   double *d_uprev = nullptr, *d_ustart = nullptr;   // u^{n-1} and the buffer of the next start vector (rotated with d_u)
@@ -234,11 +228,8 @@ struct hf_ctx {
   int32_t* d_samp_idx = nullptr;
   double* d_samp = nullptr;
   int samp_cap = 0;
-  int pred_iters = 0;
   // multigrid preconditioner (hf_set_precond): device hierarchy
-  int precond = 0;             // 0 Jacobi, 1 smoothed-aggregation AMG V(1,1)
   int amg_reuse = 0;           // 1: keep the coarse levels across hf_assemble calls (kappa sweeps)
-  bool amg_ready = false;
   struct DevCsr {
     int nrow = 0, ncol = 0, lanes = 8; int64_t nnz = 0; int32_t *ptr = nullptr, *idx = nullptr; double* val = nullptr;
     float* valf = nullptr;                     // single-precision values (transfer operators of the preconditioner); val is then null
@@ -258,22 +249,38 @@ struct hf_ctx {
     bool own_b = false;
     double omega = 0; int n = 0;
   };
-  std::vector<DevLevel> amg;
-  double* d_coarse_inv = nullptr;
-  float* d_coarse_inv_f = nullptr;   // the same in single precision (amg_f32)
-  int coarse_n = 0, coarse_ld = 0;   // dense inverse, row-major, leading dimension a multiple of 4 (16-byte row loads)
-  bool amg_fine_stale = false;       // frozen hierarchy (reuse) and the fine operator re-valued since it was built: the fused down leg Rt_0 no longer matches A
   int amg_fuse0 = 0;                 // finest level of the V-cycle: 0 explicit sweeps, 1 fused legs Rt_0 / GP_0, 2 fused down leg only (chosen by size in build_amg; HEATFLOW_AMG_FUSE0 overrides)
   bool amg_f32 = true;               // operators of the preconditioner below the fine level stored in float (HEATFLOW_AMG_F32=0: double)
-  double amg_opc = 0.0, amg_setup_s = 0.0;
   // what the fine operator the hierarchy was built from depends on besides the mesh (hf_amg_io.hpp): time step, coefficient
   // tables, Dirichlet set - compared with the context's own operator whenever a kept or installed hierarchy meets a new hf_assemble
-  struct OperatorPrint { double dt = 0.0; std::vector<double> kappa, rhoc; int32_t nbc = 0; uint64_t bc_hash = 0; int32_t scheme = 0; uint64_t an_hash = 0; } amg_print;
+  struct OperatorPrint { double dt = 0.0; std::vector<double> kappa, rhoc; int32_t nbc = 0; uint64_t bc_hash = 0; int32_t scheme = 0; uint64_t an_hash = 0; };
   long long amg_fallbacks = 0;   // steps finished by Jacobi-PCG after a multigrid-PCG breakdown
-  // steady state (hf_steady_setup / hf_steady_solve): the stiffness K on the pattern - as assembled (Kfree, for hf_hold_load)
-  // and with its own Dirichlet set S eliminated (K) -, the lifting columns K[free, S], D^-1 and a multigrid hierarchy of
-  // its own.  While the steady operator is set up or solved these fields trade places with the transient's (steady_swap in
-  // heatflow_hip.hip), so that the solver code runs on them unchanged and the transient's stay untouched.
+  // An eliminated operator on the mesh's pattern and what solves it: its Dirichlet set with the lifting columns A[free, set],
+  // D^-1, the choice of preconditioner and a multigrid hierarchy of its own.  The context holds two, the transient's
+  // A = M + dt K (`sys`) and the steady K_hat_S (`steady.sys`); the lifting, elimination, multigrid set-up and PCG code takes
+  // the one it works on as an argument.
+  struct System {
+    int32_t nbc = 0;
+    int32_t* bc_dofs = nullptr;
+    double* g = nullptr;         // boundary values of the current solve
+    int32_t nlift_rows = 0, nlift = 0;
+    int32_t *lift_rows = nullptr, *lift_ptr = nullptr, *lift_bc = nullptr, *lift_slot = nullptr;
+    double* lift_val = nullptr;
+    double *A = nullptr, *dinv = nullptr;
+    int precond = 0;             // 0 Jacobi, 1 smoothed-aggregation AMG V(1,1)
+    int pred_iters = 0;
+    std::vector<DevLevel> amg;
+    double* coarse_inv = nullptr;
+    float* coarse_inv_f = nullptr;     // the same in single precision (amg_f32)
+    int coarse_n = 0, coarse_ld = 0;   // dense inverse, row-major, leading dimension a multiple of 4 (16-byte row loads)
+    bool amg_ready = false;
+    bool amg_fine_stale = false;       // frozen hierarchy (reuse) and the fine operator re-valued since it was built: the fused down leg Rt_0 no longer matches A
+    double amg_opc = 0.0, amg_setup_s = 0.0;
+    OperatorPrint amg_print;
+  } sys;
+  // steady state (hf_steady_setup / hf_steady_solve): the stiffness K on the pattern as assembled (Kfree, for hf_hold_load) and,
+  // with its own Dirichlet set S eliminated, as a System of its own (sys), which the solver code is given in place of the
+  // transient's.
   // picard: the set-up made last is hf_steady_picard_setup's - K and Kfree are valued at a state through the tables
   // (k_assemble_rows_kT_K) and go stale with the tables as well as with the materials.
   struct Steady {
@@ -282,17 +289,8 @@ struct hf_ctx {
     KTab* hdr0 = nullptr;                   // 64 empty table headers, for a Picard set-up while no table is set
     double* xprev = nullptr;                // the iterate a Picard sweep started from (for the change)
     unsigned long long* change = nullptr;   // max |x_k - x_{k-1}| of the last sweep (bits of a double >= 0)
-    int precond = 0, pred_iters = 0;
-    int32_t nbc = 0, nlift_rows = 0, nlift = 0;
-    int32_t *bc_dofs = nullptr, *lift_rows = nullptr, *lift_ptr = nullptr, *lift_bc = nullptr, *lift_slot = nullptr;
-    double *g = nullptr, *lift_val = nullptr, *K = nullptr, *dinv = nullptr, *Kfree = nullptr;
-    std::vector<DevLevel> amg;
-    double* coarse_inv = nullptr;
-    float* coarse_inv_f = nullptr;
-    int coarse_n = 0, coarse_ld = 0;
-    bool amg_ready = false, amg_fine_stale = false;
-    double amg_opc = 0.0, amg_setup_s = 0.0;
-    OperatorPrint amg_print;
+    double* Kfree = nullptr;
+    System sys;
   } steady;
   // load term of the time step (hf_set_load / hf_hold_load): b = M u^n + dt F
   double* d_load = nullptr;
@@ -350,8 +348,8 @@ struct hf_ctx {
   struct BatchLevel { double *x = nullptr, *cat = nullptr, *b = nullptr, *res = nullptr; bool own_b = false; };
   struct Batch {
     int nv = 0;                  // 0: no batch open
-    int opk = 0;                 // fine operator of the columns: 0 shared (ctx->d_A), 1 one per column, 2 affine A + d_j A1
-    const double *sysA = nullptr, *sysDinv = nullptr;   // shared operator other than ctx->d_A (the flux projection's mass matrix)
+    int opk = 0;                 // fine operator of the columns: 0 shared (ctx->sys.A), 1 one per column, 2 affine A + d_j A1
+    const double *sysA = nullptr, *sysDinv = nullptr;   // shared operator other than ctx->sys.A (the flux projection's mass matrix)
     double *A = nullptr, *dinv = nullptr, *lift_val = nullptr;            // per-column operator data (opk 1; dinv also opk 2)
     double *A1 = nullptr, *lift1 = nullptr;                               // affine part and its lifting values (opk 2)
     double delta[NV_MAX] = {};
@@ -383,11 +381,11 @@ struct hf_ctx {
     int32_t *ptr = nullptr, *dict = nullptr, *own = nullptr;
     uint16_t* id = nullptr;
   } bcols;
-  Batch fluxb;                   // two-column state of the read-flux projection (both components in one PCG), swapped into `batch` while it runs
+  Batch fluxb;                   // two-column state of the read-flux projection (both components in one PCG)
   Batch fluxnb;                  // nv-column state of the batched loop's read-flux projection (hf_batch_run_flux): one gradient component of every column per PCG
   int32_t* d_fsamp_idx = nullptr;   // its sample nodes
-  // tangent runs (hf_tangent_setup / hf_run_tangent): nv tangent columns s_j = du/dtheta_j in their own batch state, swapped
-  // into `batch` for the tangent stage of every step; their load F_j = -K_j u^{n+1} (k_tangent_load, or
+  // tangent runs (hf_tangent_setup / hf_run_tangent): nv tangent columns s_j = du/dtheta_j in their own batch state, which
+  // the tangent stage of every step hands to the batched loop; their load F_j = -K_j u^{n+1} (k_tangent_load, or
   // k_tangent_load_dir under hf_tangent_setup_dir)
   Batch tanb;
   struct Tangent {

@@ -495,23 +495,23 @@ int launch_assemble_rows_any(hf_ctx* ctx, const double* kappa_idx, const double*
 
 int launch_assemble(hf_ctx* ctx) {
   if (ctx->mode == HF_ASM_ROW_GATHER && ctx->rg_ok)
-    return launch_assemble_rows_any(ctx, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, ctx->d_M, ctx->d_A);
+    return launch_assemble_rows_any(ctx, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, ctx->d_M, ctx->sys.A);
   if (ctx->mode == HF_ASM_ROW_GATHER)   // lists not available for this mesh (row > 32 entries or > 64 cell tags): deterministic LDS variant
-    return launch_assemble_lds(ctx, true, ctx->d_kappa, ctx->d_rhoc, ctx->dt, ctx->d_M, ctx->d_A);
+    return launch_assemble_lds(ctx, true, ctx->d_kappa, ctx->d_rhoc, ctx->dt, ctx->d_M, ctx->sys.A);
   if (ctx->mode == HF_ASM_LDS_COLORED || ctx->mode == HF_ASM_LDS_ATOMIC) {
-    return launch_assemble_lds(ctx, ctx->mode == HF_ASM_LDS_COLORED, ctx->d_kappa, ctx->d_rhoc, ctx->dt, ctx->d_M, ctx->d_A);
+    return launch_assemble_lds(ctx, ctx->mode == HF_ASM_LDS_COLORED, ctx->d_kappa, ctx->d_rhoc, ctx->dt, ctx->d_M, ctx->sys.A);
   } else {
     HF_HIP(hipMemsetAsync(ctx->d_M, 0, sizeof(double) * ctx->nnz, ctx->stream));
-    HF_HIP(hipMemsetAsync(ctx->d_A, 0, sizeof(double) * ctx->nnz, ctx->stream));
+    HF_HIP(hipMemsetAsync(ctx->sys.A, 0, sizeof(double) * ctx->nnz, ctx->stream));
     hipLaunchKernelGGL(k_assemble_global, dim3((ctx->ne + TPB - 1) / TPB), dim3(TPB), 0, ctx->stream, ctx->ne,
                        ctx->d_rowptr, ctx->d_colidx, ctx->d_elem, ctx->d_zr, ctx->d_kappa, ctx->d_rhoc, ctx->dt,
-                       ctx->d_M, ctx->d_A);
+                       ctx->d_M, ctx->sys.A);
   }
   HF_HIP(hipGetLastError());
   return HF_OK;
 }
 
-// ---- value lists of d_A / d_M (hf_ctx::ValueLists, ValComp)
+// ---- value lists of sys.A / d_M (hf_ctx::ValueLists, ValComp)
 inline void value_lists_touch(hf_ctx* c, const double* vals) {   // `vals` is about to be written: its tables no longer hold its values
   for (auto& L : c->vl)
     if (L.src == vals) L.valid = false;
@@ -537,7 +537,7 @@ bool value_lists_wanted(const hf_ctx* ctx) {
   return ctx->vl_mode != 0 && ctx->c16 && !ctx->kt.on && ctx->max_chunk_nnz_s <= VL_MAX_CHUNK && ctx->nchunks_s > 0;
 }
 
-// Queue the build of the tables of `vals` (which: 0 = d_A, 1 = d_M) on the stream; value_lists_finish reads the outcome after the
+// Queue the build of the tables of `vals` (which: 0 = sys.A, 1 = d_M) on the stream; value_lists_finish reads the outcome after the
 // caller's synchronisation.
 int value_lists_build(hf_ctx* ctx, int which, const double* vals) {
   hf_ctx::ValueLists& L = ctx->vl[which];
@@ -618,14 +618,15 @@ void launch_spmv(hf_ctx* c, const VT* vals, const double* x, double* y, double* 
                  const double* bvec = nullptr, double* pvec = nullptr, double* part1 = nullptr,
                  double* part2 = nullptr, double w = 0.0, const double* dinv = nullptr, hipEvent_t ev_start = nullptr,
                  hipEvent_t ev_stop = nullptr, int parity = 0) {
+  // dinv null: the transient system's (left out only by the transient's own callers and in modes that do not read it)
   // With events: the launch carries them (hipExtLaunchKernelGGL), so they bracket the kernel's own
   // execution on the device - the same interval rocprofv3 reports - not the launch gap before it.
   const ColComp comp{c->d_cdict_ptr, c->d_cdict, c->d_cid, c->max_chunk_nnz_s, c->cdict_own ? 1 : 0};
 #define HF_SPMV_ARGS c->n, c->nchunks_s, static_cast<int>(SRPC), static_cast<const int32_t*>(c->d_rowptr),                    \
                      static_cast<const int32_t*>(c->d_colidx), vals, x, y, (MODE == 0 ? nullptr : c->d_scal), part0, bvec,  \
-                     dinv ? dinv : static_cast<const double*>(c->d_dinv), pvec, part1, part2, w, c->P, parity, comp
+                     dinv ? dinv : static_cast<const double*>(c->sys.dinv), pvec, part1, part2, w, c->P, parity, comp
   const std::uint32_t smem = static_cast<std::uint32_t>(spmv_smem_bytes(c));
-  // the value array has valid value lists (d_A or d_M since the last hf_assemble): the same products from the packed stream
+  // the value array has valid value lists (sys.A or d_M since the last hf_assemble): the same products from the packed stream
   const hf_ctx::ValueLists* L = c->c16 ? value_lists_of(c, vals) : nullptr;
   if (L != nullptr) {
     if constexpr (std::is_same<VT, double>::value) {
@@ -633,7 +634,7 @@ void launch_spmv(hf_ctx* c, const VT* vals, const double* x, double* y, double* 
       const std::uint32_t smem_v = smem + static_cast<std::uint32_t>(c->vl_vcap) * 8u;
 #define HF_SPMV_VARGS c->n, c->nchunks_s, static_cast<int>(SRPC), static_cast<const int32_t*>(c->d_rowptr),                   \
                       static_cast<const int32_t*>(c->d_colidx), vals, x, y, (MODE == 0 ? nullptr : c->d_scal), part0, bvec,  \
-                      dinv ? dinv : static_cast<const double*>(c->d_dinv), pvec, part1, part2, w, c->P, parity, vcomp
+                      dinv ? dinv : static_cast<const double*>(c->sys.dinv), pvec, part1, part2, w, c->P, parity, vcomp
       if (ev_start != nullptr) hipExtLaunchKernelGGL((k_spmv<MODE, true, double, HF_SPMV_UN, true>), dim3(c->Ps), dim3(TS), smem_v, c->stream, ev_start, ev_stop, 0u, HF_SPMV_VARGS);
       else hipLaunchKernelGGL((k_spmv<MODE, true, double, HF_SPMV_UN, true>), dim3(c->Ps), dim3(TS), smem_v, c->stream, HF_SPMV_VARGS);
 #undef HF_SPMV_VARGS

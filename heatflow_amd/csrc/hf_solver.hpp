@@ -9,21 +9,22 @@ namespace {
 // ------------------------------------------------------------------------------------------
 using DevCsr = hf_ctx::DevCsr;
 using DevLevel = hf_ctx::DevLevel;
+using System = hf_ctx::System;
 
 void free_dev_csr(DevCsr& m) { dev_free(&m.ptr); dev_free(&m.idx); dev_free(&m.val); dev_free(&m.valf); dev_free(&m.dptr); dev_free(&m.dict); dev_free(&m.cid); m = DevCsr(); }
 
-void free_amg(hf_ctx* ctx) {
-  for (size_t l = 0; l < ctx->amg.size(); ++l) {
-    DevLevel& L = ctx->amg[l];
+void free_amg(System& S) {
+  for (size_t l = 0; l < S.amg.size(); ++l) {
+    DevLevel& L = S.amg[l];
     if (l > 0) { free_dev_csr(L.A); dev_free(&L.dinv); dev_free(&L.x); dev_free(&L.cat); }
     if (L.own_b) dev_free(&L.b);
     free_dev_csr(L.P); free_dev_csr(L.R); free_dev_csr(L.Rt); free_dev_csr(L.GP);
   }
-  ctx->amg.clear();
-  dev_free(&ctx->d_coarse_inv);
-  dev_free(&ctx->d_coarse_inv_f);
-  ctx->coarse_n = 0;
-  ctx->amg_ready = false;
+  S.amg.clear();
+  dev_free(&S.coarse_inv);
+  dev_free(&S.coarse_inv_f);
+  S.coarse_n = 0;
+  S.amg_ready = false;
 }
 
 // lanes of a wavefront that share a row in the sub-wave kernels: about one entry per lane (HEATFLOW_VEC_PER_LANE: A/B)
@@ -82,17 +83,17 @@ int upload_csr(hf_ctx* ctx, const amg::Csr& h, DevCsr& d, bool f32 = false, bool
 // context's own operator; an intermediate level's right-hand side b is the head of `cat` = [b_l ; result of level l + 1],
 // the operand of its fused up leg; a level's result goes to `res` (the tail of the finer level's cat, or - level 1 - its
 // own x, or behind d_r when the finest level's up leg is fused); the coarsest level owns a zero-padded b.
-int wire_levels(hf_ctx* ctx) {
-  const size_t nl = ctx->amg.size();
+int wire_levels(hf_ctx* ctx, System& S) {
+  const size_t nl = S.amg.size();
   for (size_t l = 0; l < nl; ++l) {
-    DevLevel& L = ctx->amg[l];
+    DevLevel& L = S.amg[l];
     if (l == 0) {
-      L.A.nrow = L.A.ncol = ctx->n; L.A.nnz = ctx->nnz; L.A.ptr = ctx->d_rowptr; L.A.idx = ctx->d_colidx; L.A.val = ctx->d_A;
-      L.dinv = ctx->d_dinv;
+      L.A.nrow = L.A.ncol = ctx->n; L.A.nnz = ctx->nnz; L.A.ptr = ctx->d_rowptr; L.A.idx = ctx->d_colidx; L.A.val = S.A;
+      L.dinv = S.dinv;
       continue;
     }
     if (l + 1 < nl) {
-      const size_t len = static_cast<size_t>(L.n) + ctx->amg[l + 1].n + 2;
+      const size_t len = static_cast<size_t>(L.n) + S.amg[l + 1].n + 2;
       HF_TRY(dev_alloc(ctx, &L.cat, len));
       HF_HIP(hipMemsetAsync(L.cat, 0, sizeof(double) * len, ctx->stream));
       L.b = L.cat;
@@ -103,9 +104,9 @@ int wire_levels(hf_ctx* ctx) {
     }
     if (l == 1) {
       HF_TRY(dev_alloc(ctx, &L.x, L.n + 2));
-      L.res = ctx->amg[0].GP.nrow > 0 ? ctx->d_r + ctx->n : L.x;
+      L.res = S.amg[0].GP.nrow > 0 ? ctx->d_r + ctx->n : L.x;
     } else {
-      L.res = ctx->amg[l - 1].cat + ctx->amg[l - 1].n;
+      L.res = S.amg[l - 1].cat + S.amg[l - 1].n;
     }
   }
   return HF_OK;
@@ -133,13 +134,13 @@ void amg_params(hf_ctx* ctx, amg::Params& prm) {
   prm.fuse_fine_down_only = ctx->amg_fuse0 == 2;
 }
 
-// Levels built on the host go to the device: H.levels[k] becomes level base + k of ctx->amg (already sized).
-int upload_host_levels(hf_ctx* ctx, const amg::Hierarchy& H, size_t base) {
+// Levels built on the host go to the device: H.levels[k] becomes level base + k of ctx->sys.amg (already sized).
+int upload_host_levels(hf_ctx* ctx, System& S, const amg::Hierarchy& H, size_t base) {
   const bool f32 = ctx->amg_f32;
-  const size_t nl = ctx->amg.size();
+  const size_t nl = S.amg.size();
   for (size_t k = 0; k < H.levels.size(); ++k) {
     const size_t l = base + k;
-    DevLevel& L = ctx->amg[l];
+    DevLevel& L = S.amg[l];
     const amg::Level& hl = H.levels[k];
     L.n = static_cast<int>(hl.dinv.size());
     L.omega = hl.omega;
@@ -209,14 +210,14 @@ int dense_inverse(hf_ctx* ctx, int nc, const int32_t* ptr, const int32_t* idx, c
 // Last steps of a set-up once every level's operators are on the device: the finest level's fused legs are dropped when they
 // are too small for the only kernel that carries their epilogues, the level vectors are wired, the dense inverse of the
 // coarsest operator (host copy Ac) is formed on the device by Gauss-Jordan.
-int finish_amg(hf_ctx* ctx, const amg::Csr& Ac, int coarse_n, double op_complexity, const std::chrono::steady_clock::time_point t0) {
+int finish_amg(hf_ctx* ctx, System& S, const amg::Csr& Ac, int coarse_n, double op_complexity, const std::chrono::steady_clock::time_point t0) {
   const bool f32 = ctx->amg_f32;
-  const size_t nl = ctx->amg.size();
+  const size_t nl = S.amg.size();
   auto lap = [&](const char* what) {
     if (std::getenv("HEATFLOW_DEBUG")) std::fprintf(stderr, "[amg setup] %-28s %.3f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
   };
   {
-    DevLevel& L = ctx->amg[0];
+    DevLevel& L = S.amg[0];
     if (L.Rt.nrow > 0 && (L.Rt.rpc == 0 || (L.GP.nrow > 0 && L.GP.rpc == 0))) {    // too small for the LDS-staged kernel (the only one with the convergence test / r.z epilogue): explicit sweeps
       free_dev_csr(L.Rt);
       free_dev_csr(L.GP);
@@ -229,47 +230,47 @@ int finish_amg(hf_ctx* ctx, const amg::Csr& Ac, int coarse_n, double op_complexi
                                m.valf ? "f32" : "f64", m.cid ? " c16" : "");
     };
     for (size_t l = 0; l < nl; ++l) {
-      show("A", l, ctx->amg[l].A); show("P", l, ctx->amg[l].P); show("R", l, ctx->amg[l].R);
-      show("Rt", l, ctx->amg[l].Rt); show("GP", l, ctx->amg[l].GP);
+      show("A", l, S.amg[l].A); show("P", l, S.amg[l].P); show("R", l, S.amg[l].R);
+      show("Rt", l, S.amg[l].Rt); show("GP", l, S.amg[l].GP);
     }
   }
-  HF_TRY(wire_levels(ctx));
+  HF_TRY(wire_levels(ctx, S));
   lap("+ operators on the device");
   // coarsest level: dense inverse by Gauss-Jordan on the device
-  ctx->coarse_n = 0;
+  S.coarse_n = 0;
   if (nl > 1 && coarse_n > 0 && coarse_n <= 4096) {
     const int nc = coarse_n;
     const int ld = (nc + 3) & ~3;
-    HF_TRY(dev_alloc(ctx, &ctx->d_coarse_inv, static_cast<size_t>(nc) * ld));
-    HF_TRY(dense_inverse(ctx, nc, Ac.ptr.data(), Ac.idx.data(), Ac.val.data(), ctx->d_coarse_inv));
+    HF_TRY(dev_alloc(ctx, &S.coarse_inv, static_cast<size_t>(nc) * ld));
+    HF_TRY(dense_inverse(ctx, nc, Ac.ptr.data(), Ac.idx.data(), Ac.val.data(), S.coarse_inv));
     if (f32) {
-      HF_TRY(dev_alloc(ctx, &ctx->d_coarse_inv_f, static_cast<size_t>(nc) * ld));
-      hipLaunchKernelGGL(k_to_float, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(nc) * ld, ctx->d_coarse_inv, ctx->d_coarse_inv_f);
+      HF_TRY(dev_alloc(ctx, &S.coarse_inv_f, static_cast<size_t>(nc) * ld));
+      hipLaunchKernelGGL(k_to_float, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(nc) * ld, S.coarse_inv, S.coarse_inv_f);
       HF_HIP(hipGetLastError());
     }
     HF_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->coarse_ld = ld;
-    ctx->coarse_n = nc;
+    S.coarse_ld = ld;
+    S.coarse_n = nc;
   }
   lap("+ dense inverse");
-  ctx->amg_opc = op_complexity;
-  ctx->amg_fine_stale = false;
-  ctx->amg_ready = true;
-  ctx->amg_setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  S.amg_opc = op_complexity;
+  S.amg_fine_stale = false;
+  S.amg_ready = true;
+  S.amg_setup_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return HF_OK;
 }
 
 // Build the hierarchy from the assembled, eliminated fine operator, everything on the host (download -> host set-up ->
 // upload): the reference implementation of the set-up; hf_amg_gpu.hpp forms the same operators on the device.
-int build_amg(hf_ctx* ctx) {
+int build_amg(hf_ctx* ctx, System& S) {
   const auto t0 = std::chrono::steady_clock::now();
-  free_amg(ctx);
+  free_amg(S);
   amg::Csr A0;
   A0.nrow = A0.ncol = ctx->n;
   A0.ptr.assign(ctx->h_rowptr.begin(), ctx->h_rowptr.end());
   A0.idx.assign(ctx->h_colidx.begin(), ctx->h_colidx.end());
   A0.val.resize(ctx->nnz);
-  HF_HIP(copy_sync(ctx, A0.val.data(), ctx->d_A, sizeof(double) * ctx->nnz, hipMemcpyDeviceToHost));
+  HF_HIP(copy_sync(ctx, A0.val.data(), S.A, sizeof(double) * ctx->nnz, hipMemcpyDeviceToHost));
   amg::Hierarchy H;
   amg::Params prm;
   amg_params(ctx, prm);
@@ -279,9 +280,9 @@ int build_amg(hf_ctx* ctx) {
   lap("operator downloaded");
   if (!amg::build(std::move(A0), prm, H)) return fail(ctx, HF_ERR_STATE, "AMG set-up failed (non-positive diagonal or singular coarse operator)");
   lap("+ host hierarchy");
-  ctx->amg.resize(H.levels.size());
-  HF_TRY(upload_host_levels(ctx, H, 0));
-  return finish_amg(ctx, H.levels.back().A, H.coarse_n, H.op_complexity, t0);
+  S.amg.resize(H.levels.size());
+  HF_TRY(upload_host_levels(ctx, S, H, 0));
+  return finish_amg(ctx, S, H.levels.back().A, H.coarse_n, H.op_complexity, t0);
 }
 
 // VMODE 0: y = A x, 1: y += A x; LDS-staged kernel when the matrix is big enough to fill the chip,
@@ -378,65 +379,65 @@ void launch_vec(hf_ctx* c, const DevCsr& m, const double* x, double* y) {
 // `part`: the whole cycle, only its first kernel (the one that tests), or everything after it - the polled loop holds the
 // rest of a cycle back while the test it is waiting for may end the solve (pcg_solve).
 enum CyclePart { CYCLE_ALL = 0, CYCLE_FIRST = 1, CYCLE_REST = 2 };
-void vcycle(hf_ctx* c, int out_slot, bool test_convergence = false, CyclePart part = CYCLE_ALL) {
-  const int nl = static_cast<int>(c->amg.size());
-  DevLevel& L0 = c->amg[0];
+void vcycle(hf_ctx* c, System& S, int out_slot, bool test_convergence = false, CyclePart part = CYCLE_ALL) {
+  const int nl = static_cast<int>(S.amg.size());
+  DevLevel& L0 = S.amg[0];
   if (nl == 1) {  // no coarse level: one more Jacobi sweep keeps the operator symmetric
     if (part != CYCLE_REST)
-      launch_spmv<4>(c, c->d_A, c->d_z, c->d_z2, c->d_part_rz + out_slot * MAXP, c->d_r, nullptr, nullptr, nullptr, L0.omega);
+      launch_spmv<4>(c, S.A, c->d_z, c->d_z2, c->d_part_rz + out_slot * MAXP, c->d_r, nullptr, nullptr, nullptr, L0.omega, S.dinv);
     return;
   }
   const bool fused0 = L0.GP.nrow > 0;     // both legs of the finest level fused
   // A fused down leg alone must match the operator the explicit up leg sweeps over: after a re-valuation under a frozen
   // hierarchy it does not (Rt_0 holds the old A), the cycle would no longer be symmetric and PCG breaks down - the
   // explicit down leg takes over.  With both legs fused the cycle is a fixed SPD operator of the old A: weaker, but sound.
-  if (L0.Rt.nrow > 0 && (fused0 || !c->amg_fine_stale)) {
+  if (L0.Rt.nrow > 0 && (fused0 || !S.amg_fine_stale)) {
     // finest level through its fused legs: b_1 = Rt_0 r (pre-smoothing from zero, residual and restriction in one
     // operator; early exit if the update before it has converged)
-    if (part != CYCLE_REST) launch_stream<0>(c, L0.Rt, c->d_r, c->amg[1].b, nullptr, nullptr, test_convergence ? c->d_part_zz : nullptr);
+    if (part != CYCLE_REST) launch_stream<0>(c, L0.Rt, c->d_r, S.amg[1].b, nullptr, nullptr, test_convergence ? c->d_part_zz : nullptr);
   } else {
     if (part != CYCLE_REST)
-      launch_spmv<3>(c, c->d_A, c->d_z, c->d_tmp, nullptr, c->d_r, nullptr, nullptr,   // t = r - A z (+ early exit on convergence)
-                     test_convergence ? c->d_part_zz : nullptr);
-    if (part != CYCLE_FIRST) launch_vec<0>(c, L0.R, c->d_tmp, c->amg[1].b);      // b_1 = R_0 t
+      launch_spmv<3>(c, S.A, c->d_z, c->d_tmp, nullptr, c->d_r, nullptr, nullptr,   // t = r - A z (+ early exit on convergence)
+                     test_convergence ? c->d_part_zz : nullptr, 0.0, S.dinv);
+    if (part != CYCLE_FIRST) launch_vec<0>(c, L0.R, c->d_tmp, S.amg[1].b);      // b_1 = R_0 t
   }
   if (part == CYCLE_FIRST) return;
-  for (int l = 1; l + 1 < nl; ++l) launch_vec<0>(c, c->amg[l].Rt, c->amg[l].b, c->amg[l + 1].b);   // b_{l+1} = Rt_l b_l
+  for (int l = 1; l + 1 < nl; ++l) launch_vec<0>(c, S.amg[l].Rt, S.amg[l].b, S.amg[l + 1].b);   // b_{l+1} = Rt_l b_l
   {
-    DevLevel& Lc = c->amg[nl - 1];
-    if (c->coarse_n > 0) {
+    DevLevel& Lc = S.amg[nl - 1];
+    if (S.coarse_n > 0) {
       const int g = std::max(1, std::min((Lc.n + 1) / 2, 2048));
-      if (c->d_coarse_inv_f != nullptr)
-        hipLaunchKernelGGL(k_dense_mv_f32, dim3(g), dim3(TPB), 0, c->stream, Lc.n, c->coarse_ld, c->d_coarse_inv_f, Lc.b, Lc.res, c->d_scal);
+      if (S.coarse_inv_f != nullptr)
+        hipLaunchKernelGGL(k_dense_mv_f32, dim3(g), dim3(TPB), 0, c->stream, Lc.n, S.coarse_ld, S.coarse_inv_f, Lc.b, Lc.res, c->d_scal);
       else
-        hipLaunchKernelGGL(k_dense_mv, dim3(g), dim3(TPB), 0, c->stream, Lc.n, c->coarse_ld, c->d_coarse_inv, Lc.b, Lc.res, c->d_scal);
+        hipLaunchKernelGGL(k_dense_mv, dim3(g), dim3(TPB), 0, c->stream, Lc.n, S.coarse_ld, S.coarse_inv, Lc.b, Lc.res, c->d_scal);
     } else {
       const int g = std::max(1, std::min((Lc.n + TPB - 1) / TPB, 1024));
       hipLaunchKernelGGL(k_scale, dim3(g), dim3(TPB), 0, c->stream, Lc.n, Lc.omega, Lc.dinv, Lc.b, Lc.res, c->d_scal);
     }
   }
-  for (int l = nl - 2; l >= 1; --l) launch_vec<0>(c, c->amg[l].GP, c->amg[l].cat, c->amg[l].res);  // x_l = GP_l [b_l; x_{l+1}]
+  for (int l = nl - 2; l >= 1; --l) launch_vec<0>(c, S.amg[l].GP, S.amg[l].cat, S.amg[l].res);  // x_l = GP_l [b_l; x_{l+1}]
   if (fused0) {
     // z = GP_0 [r; x_1] (prolongation and post-smoothing in one operator) with the r.z partials
     launch_stream<7>(c, L0.GP, c->d_r, c->d_z2, c->d_part_rz + out_slot * MAXP, c->d_r, nullptr);
     return;
   }
-  launch_vec<1>(c, L0.P, c->amg[1].res, c->d_z);                                // z += P_0 x_1
-  launch_spmv<4>(c, c->d_A, c->d_z, c->d_z2, c->d_part_rz + out_slot * MAXP, c->d_r, nullptr, nullptr, nullptr, L0.omega);
+  launch_vec<1>(c, L0.P, S.amg[1].res, c->d_z);                                // z += P_0 x_1
+  launch_spmv<4>(c, S.A, c->d_z, c->d_z2, c->d_part_rz + out_slot * MAXP, c->d_r, nullptr, nullptr, nullptr, L0.omega, S.dinv);
 }
 
 // One multigrid-PCG iteration: iteration head (as above), update (alpha, x, r, z0 = w D^-1 r), V-cycle (z, r.z)
-void launch_amg_iteration(hf_ctx* c, double* x, int parity, CyclePart part = CYCLE_ALL) {
-  if (part == CYCLE_REST) { vcycle(c, parity ^ 1, true, CYCLE_REST); return; }
+void launch_amg_iteration(hf_ctx* c, System& S, double* x, int parity, CyclePart part = CYCLE_ALL) {
+  if (part == CYCLE_REST) { vcycle(c, S, parity ^ 1, true, CYCLE_REST); return; }
   const bool timed = c->prof && c->prof_used < PROF_PAIRS;
   hipEvent_t e0 = timed ? c->prof_ev[2 * c->prof_used] : nullptr, e1 = timed ? c->prof_ev[2 * c->prof_used + 1] : nullptr;
-  launch_spmv<9>(c, c->d_A, c->d_z2, c->d_Ap, c->d_part_pAp, nullptr, c->d_p, c->d_part_rz, c->d_part_zz, 0.0, nullptr, e0,
+  launch_spmv<9>(c, S.A, c->d_z2, c->d_Ap, c->d_part_pAp, nullptr, c->d_p, c->d_part_rz, c->d_part_zz, 0.0, S.dinv, e0,
                  e1, parity);
   if (timed) c->prof_used++;
   hipLaunchKernelGGL(k_pcg_update_amg, dim3(c->P), dim3(TPB), 0, c->stream, c->n, c->nchunks, c->P, parity, c->d_scal,
-                     c->d_part_pAp, c->d_part_rz, c->d_part_zz, x, c->d_r, c->d_p, c->d_Ap, c->d_dinv,
-                     c->amg[0].omega, c->amg[0].GP.nrow > 0 ? static_cast<double*>(nullptr) : c->d_z);
-  vcycle(c, parity ^ 1, true, part);
+                     c->d_part_pAp, c->d_part_rz, c->d_part_zz, x, c->d_r, c->d_p, c->d_Ap, S.dinv,
+                     S.amg[0].omega, S.amg[0].GP.nrow > 0 ? static_cast<double*>(nullptr) : c->d_z);
+  vcycle(c, S, parity ^ 1, true, part);
 }
 
 // HEATFLOW_POLL=0: bursts + copy-back of the scalars instead of the polled, one-test-ahead loops (A/B and diagnosis)
@@ -513,7 +514,7 @@ void harvest_profile(hf_ctx* ctx) {
 
 // PCG on `sys` started from sys.x.  Jacobi: any system on the pattern; AMG: the main system only.
 // Iteration count / residual are left in h_scal; *pred carries the burst-size hint between calls.
-int pcg_solve(hf_ctx* ctx, const LinSys& sys, bool use_amg, double rtol, double atol, int max_it, int* pred) {
+int pcg_solve(hf_ctx* ctx, System& S, const LinSys& sys, bool use_amg, double rtol, double atol, int max_it, int* pred) {
   static const bool trace_res = std::getenv("HEATFLOW_TRACE_RES") != nullptr;   // diagnostics: bursts of 2, residual printed after each
   // a new epoch: whatever an earlier solve's queued launches might still write to the mirror is not this solve's progress
   ctx->epoch += 1;
@@ -526,15 +527,15 @@ int pcg_solve(hf_ctx* ctx, const LinSys& sys, bool use_amg, double rtol, double 
   } else {
     // r = b - A x, z0 = w D^-1 r; tolerance; z = B r (V-cycle, r.z into slot 0)
     launch_spmv<5>(ctx, sys.A, sys.x, ctx->d_r, nullptr, sys.b, ctx->d_z, ctx->d_part_zz, ctx->d_part_bn,
-                   ctx->amg[0].omega);
+                   S.amg[0].omega, sys.dinv);
     hipLaunchKernelGGL(k_pcg_begin, dim3(1), dim3(TPB), 0, ctx->stream, ctx->P, rtol, atol, ctx->d_part_zz,
                        ctx->d_part_bn, ctx->d_scal, ctx->epoch);
-    vcycle(ctx, 0);
+    vcycle(ctx, S, 0);
   }
   HF_HIP(hipGetLastError());
 
   int launched = 0;
-  if (use_amg && !trace_res && ctx->amg.size() > 1 && poll_enabled()) {   // (a one-level hierarchy has no V-cycle kernel that tests: bursts below)
+  if (use_amg && !trace_res && S.amg.size() > 1 && poll_enabled()) {   // (a one-level hierarchy has no V-cycle kernel that tests: bursts below)
     // Multigrid iterations are queued one test ahead: the first kernel of a V-cycle publishes the convergence test of
     // the iterate it starts from (ScalMirror), so the host learns the outcome while that cycle still has its other ten
     // kernels to run and has the next iteration queued before they finish - no copy, no synchronisation, no idle
@@ -557,9 +558,9 @@ int pcg_solve(hf_ctx* ctx, const LinSys& sys, bool use_amg, double rtol, double 
     int burst = std::max(1, std::min(max_it, *pred - 2));
     bool rest_pending = false;      // the last launched iteration stops after its testing kernel
     while (true) {
-      if (rest_pending) launch_amg_iteration(ctx, sys.x, (launched - 1) & 1, CYCLE_REST);
+      if (rest_pending) launch_amg_iteration(ctx, S, sys.x, (launched - 1) & 1, CYCLE_REST);
       const bool split = hold_back && burst == 1 && launched > 0;
-      for (int k = 0; k < burst; ++k) launch_amg_iteration(ctx, sys.x, (launched + k) & 1, split ? CYCLE_FIRST : CYCLE_ALL);
+      for (int k = 0; k < burst; ++k) launch_amg_iteration(ctx, S, sys.x, (launched + k) & 1, split ? CYCLE_FIRST : CYCLE_ALL);
       rest_pending = split;
       launched += burst;
       HF_HIP(hipGetLastError());
@@ -585,7 +586,7 @@ int pcg_solve(hf_ctx* ctx, const LinSys& sys, bool use_amg, double rtol, double 
   while (true) {
     ctx->prof_base = launched;
     for (int k = 0; k < burst; ++k) {
-      if (use_amg) launch_amg_iteration(ctx, sys.x, (launched + k) & 1);
+      if (use_amg) launch_amg_iteration(ctx, S, sys.x, (launched + k) & 1);
       else launch_pcg_iteration(ctx, sys, (launched + k) & 1);
     }
     launched += burst;
@@ -659,8 +660,8 @@ int proj_store(hf_ctx* ctx, int slot, const double* u, const double* rhs) {
   hf_ctx::Proj& Q = ctx->proj;
   // one kernel for both copies: a device-to-device hipMemcpyAsync costs several times a launch on the host side
   hipLaunchKernelGGL(k_copy2, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, u, Q.V[slot], rhs, Q.F[slot]);
-  if (ctx->nbc > 0)
-    hipLaunchKernelGGL(k_zero_entries, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs, Q.V[slot]);
+  if (ctx->sys.nbc > 0)
+    hipLaunchKernelGGL(k_zero_entries, dim3((ctx->sys.nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->sys.nbc, ctx->sys.bc_dofs, Q.V[slot]);
   Q.used[slot] = true;
   return HF_OK;
 }
@@ -678,19 +679,19 @@ void proj_column(hf_ctx* ctx, int slot, const double* f, bool solve) {
 int solve_response(hf_ctx* ctx, const std::vector<double>& dir, int max_it, double** w_out) {
   double* w = nullptr;
   HF_TRY(dev_alloc(ctx, &w, ctx->n));
-  const int nb = ctx->nbc;
+  const int nb = ctx->sys.nbc;
   HF_HIP(hipMemsetAsync(w, 0, sizeof(double) * ctx->n, ctx->stream));
   HF_HIP(hipMemsetAsync(ctx->d_b, 0, sizeof(double) * ctx->n, ctx->stream));
-  HF_HIP(hipMemcpyAsync(ctx->d_g, dir.data(), sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
-  if (ctx->nlift_rows > 0)
-    hipLaunchKernelGGL(k_lift, dim3((ctx->nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift_rows,
-                       ctx->d_lift_rows, ctx->d_lift_ptr, ctx->d_lift_bc, ctx->d_lift_val, ctx->d_g, ctx->d_b);
-  hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, ctx->d_g, ctx->d_b, w);
-  const LinSys sys{ctx->d_A, ctx->d_dinv, w, ctx->d_b};
-  const bool use_amg = ctx->precond == 1 && ctx->amg_ready;
-  int pred = ctx->pred_iters;
-  int rc = pcg_solve(ctx, sys, use_amg, 1e-8, 0.0, max_it, &pred);
-  if (rc == HF_ERR_NOCONV && use_amg && ctx->h_scal->done == 2) rc = pcg_solve(ctx, sys, false, 1e-8, 0.0, max_it, &pred);
+  HF_HIP(hipMemcpyAsync(ctx->sys.g, dir.data(), sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
+  if (ctx->sys.nlift_rows > 0)
+    hipLaunchKernelGGL(k_lift, dim3((ctx->sys.nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->sys.nlift_rows,
+                       ctx->sys.lift_rows, ctx->sys.lift_ptr, ctx->sys.lift_bc, ctx->sys.lift_val, ctx->sys.g, ctx->d_b);
+  hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->sys.bc_dofs, ctx->sys.g, ctx->d_b, w);
+  const LinSys sys{ctx->sys.A, ctx->sys.dinv, w, ctx->d_b};
+  const bool use_amg = ctx->sys.precond == 1 && ctx->sys.amg_ready;
+  int pred = ctx->sys.pred_iters;
+  int rc = pcg_solve(ctx, ctx->sys, sys, use_amg, 1e-8, 0.0, max_it, &pred);
+  if (rc == HF_ERR_NOCONV && use_amg && ctx->h_scal->done == 2) rc = pcg_solve(ctx, ctx->sys, sys, false, 1e-8, 0.0, max_it, &pred);
   if (rc != HF_OK) { dev_free(&w); return rc; }
   ctx->resp_solves += 1;
   *w_out = w;
@@ -706,7 +707,7 @@ int solve_response(hf_ctx* ctx, const std::vector<double>& dir, int max_it, doub
 // of the boundary values is expanded in the known directions; a remainder that is not rounding noise becomes a
 // new direction (one extra solve, at most MAXRESP per operator).  Never fatal: on failure the correction is off.
 int prepare_response(hf_ctx* ctx, const double* g_new, int max_it, RespArgs* ra) {
-  const int nb = ctx->nbc;
+  const int nb = ctx->sys.nbc;
   ra->k = 0;
   std::vector<double> rem(nb);
   double nrm2 = 0.0, gn2 = 0.0;
@@ -789,17 +790,15 @@ void launch_rhs_bdf2(hf_ctx* ctx, bool extrap, const StepLoad& L) {
   }
 }
 
-// After a re-valuation of A: the Dirichlet elimination, the lifting values and D^-1 as hf_assemble forms them
-int kt_finish(hf_ctx* ctx) {
-  if (ctx->nbc > 0) {
-    if (ctx->nlift > 0)
-      hipLaunchKernelGGL(k_take_lift, dim3((ctx->nlift + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift, ctx->d_lift_slot, ctx->d_A,
-                         ctx->d_lift_val);
-    hipLaunchKernelGGL(k_bc_rows, dim3((ctx->nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->nbc, ctx->d_bc_dofs, ctx->d_rowptr,
-                       ctx->d_colidx, ctx->d_A);
+// After a valuation of S.A on the whole pattern: the lifting values A[free, set] taken out, the Dirichlet rows and columns
+// eliminated, D^-1 (hf_assemble, every re-valuation under tables, the steady set-up and its Picard sweeps)
+int eliminate(hf_ctx* ctx, System& S) {
+  if (S.nbc > 0) {
+    if (S.nlift > 0)
+      hipLaunchKernelGGL(k_take_lift, dim3((S.nlift + 255) / 256), dim3(256), 0, ctx->stream, S.nlift, S.lift_slot, S.A, S.lift_val);
+    hipLaunchKernelGGL(k_bc_rows, dim3((S.nbc + 255) / 256), dim3(256), 0, ctx->stream, S.nbc, S.bc_dofs, ctx->d_rowptr, ctx->d_colidx, S.A);
   }
-  hipLaunchKernelGGL(k_dinv, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr, ctx->d_colidx, ctx->d_A,
-                     ctx->d_dinv);
+  hipLaunchKernelGGL(k_dinv, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr, ctx->d_colidx, S.A, S.dinv);
   HF_HIP(hipGetLastError());
   return HF_OK;
 }
@@ -808,15 +807,15 @@ int kt_finish(hf_ctx* ctx) {
 // elimination, the lifting values and D^-1 as hf_assemble forms them - all on the stream, no host synchronisation.  The
 // hierarchy (if any) stays the one hf_assemble built: its fused fine-level legs hold the old operator from here on.
 int kt_revalue(hf_ctx* ctx, const double* u, const double* uprev) {
-  value_lists_touch(ctx, ctx->d_A);   // (no lists are built while tables are set; whatever an earlier hf_assemble left is stale now)
+  value_lists_touch(ctx, ctx->sys.A);   // (no lists are built while tables are set; whatever an earlier hf_assemble left is stale now)
   if (ctx->kt.c_on) value_lists_touch(ctx, ctx->d_M);
   if (ctx->kt.c_on)   // capacity tables: M and A in one pass (k_assemble_rows_cT), then the same three kernels
     HF_TRY(launch_rowgather<RowsBothT>(ctx, &k_assemble_rows_cT, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals, ctx->kt.chdr,
-                                       ctx->kt.cvals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev, ctx->d_M, ctx->d_A));
+                                       ctx->kt.cvals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev, ctx->d_M, ctx->sys.A));
   else
     HF_TRY(launch_rowgather<RowsKappaT>(ctx, &k_assemble_rows_kT, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals,
-                                        ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev, ctx->d_A));
-  return kt_finish(ctx);
+                                        ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev, ctx->sys.A));
+  return eliminate(ctx, ctx->sys);
 }
 
 // Picard steady state: Kout = K(kappa(T_e)) at the state u by the stiffness-only row-gather kernel (k_assemble_rows_kT_K, the
@@ -826,27 +825,40 @@ int steady_revalue(hf_ctx* ctx, const KTab* hdr, const double* u, double* Kout) 
   return launch_rowgather<RowsKappaTK>(ctx, &k_assemble_rows_kT_K, info, ctx->d_rg_dict, hdr, ctx->kt.vals, ctx->d_kappa_rg, u, Kout);
 }
 
-// The solve of a step on the current operator, with the Jacobi fallback after a multigrid breakdown
-int step_solve(hf_ctx* ctx, double rtol, double atol, int max_it) {
-  const LinSys sys{ctx->d_A, ctx->d_dinv, ctx->d_u, ctx->d_b};
-  const bool use_amg = ctx->precond == 1 && ctx->amg_ready;
-  int rc = pcg_solve(ctx, sys, use_amg, rtol, atol, max_it, &ctx->pred_iters);
+// Multigrid PCG on S where it has a hierarchy; on a breakdown inside that loop (p.Ap <= 0: the preconditioner was not SPD for
+// this operator) the solve is finished with the Jacobi preconditioner from the current iterate - still on the GPU - and the
+// event counted.  h_scal holds the count of the solve that ran last; *both receives the two solves' sum.
+int solve_with_fallback(hf_ctx* ctx, System& S, const LinSys& sys, double rtol, double atol, int max_it, int* both = nullptr) {
+  const bool use_amg = S.precond == 1 && S.amg_ready;
+  int rc = pcg_solve(ctx, S, sys, use_amg, rtol, atol, max_it, &S.pred_iters);
+  if (both) *both = ctx->h_scal->iters;
   if (rc == HF_ERR_NOCONV && use_amg && ctx->h_scal->done == 2) {
-    // breakdown inside the multigrid-preconditioned loop (p.Ap <= 0: the preconditioner was not SPD for
-    // this operator): finish the step with the Jacobi preconditioner from the current iterate - still on
-    // the GPU - and count the event
     ctx->amg_fallbacks += 1;
     int pred = 0;
-    rc = pcg_solve(ctx, sys, false, rtol, atol, max_it, &pred);
+    rc = pcg_solve(ctx, S, sys, false, rtol, atol, max_it, &pred);
+    if (both) *both += ctx->h_scal->iters;
   }
   return rc;
+}
+
+// Right-hand side of a steady solve on S with the boundary values S.g: b = F (the load, or 0) - A[:, set] g on the free rows,
+// b_set = g; the iterate d_u receives u_set = g
+int lifted_rhs(hf_ctx* ctx, System& S, bool with_load) {
+  if (with_load) HF_HIP(hipMemcpyAsync(ctx->d_b, ctx->d_load, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+  else HF_HIP(hipMemsetAsync(ctx->d_b, 0, sizeof(double) * ctx->n, ctx->stream));
+  if (S.nlift_rows > 0)
+    hipLaunchKernelGGL(k_lift, dim3((S.nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, S.nlift_rows, S.lift_rows, S.lift_ptr,
+                       S.lift_bc, S.lift_val, S.g, ctx->d_b);
+  hipLaunchKernelGGL(k_set_bc, dim3((S.nbc + 255) / 256), dim3(256), 0, ctx->stream, S.nbc, S.bc_dofs, S.g, ctx->d_b, ctx->d_u);
+  HF_HIP(hipGetLastError());
+  return HF_OK;
 }
 
 // One time step to the boundary values g_host (n_bc doubles on the host; g_dev = the same values already on
 // the device, or null).  Leaves iteration count / residual in h_scal (kappa(T): the iterations of all Picard sweeps).
 // last: the step whose Picard change hf_get_picard_change reports (kappa(T) only).
 int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double rtol, double atol, int max_it, bool last = true) {
-  const int nb = ctx->nbc;
+  const int nb = ctx->sys.nbc;
   RespArgs ra{};
   ra.k = 0;
   const bool kt = ctx->kt.on;
@@ -868,15 +880,15 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
     // pass moves the state buffers
     const double* um1 = bdf2 && ctx->bdf_hist ? ctx->d_uprev : nullptr;
     HF_TRY(kt_revalue(ctx, ctx->d_u, um1));
-    if (ctx->precond == 1 && ctx->amg_ready) ctx->amg_fine_stale = true;
+    if (ctx->sys.precond == 1 && ctx->sys.amg_ready) ctx->sys.amg_fine_stale = true;
     if (track && sweeps == 1)
       hipLaunchKernelGGL(k_eval_state, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u, um1, ctx->kt.pic);
     if (ct && sweeps > 1)   // the vector M multiplies, for the sweeps that form the right-hand side again
       hipLaunchKernelGGL(k_picard_w, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u,
                          bdf2 ? (ctx->bdf_hist ? ctx->d_uprev : ctx->d_u) : nullptr, ctx->kt.w);
   }
-  const double* g = g_dev ? g_dev : ctx->d_g;   // hf_run has every step's boundary values on the device already
-  if (nb > 0 && !g_dev) HF_HIP(hipMemcpyAsync(ctx->d_g, g_host, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
+  const double* g = g_dev ? g_dev : ctx->sys.g;   // hf_run has every step's boundary values on the device already
+  if (nb > 0 && !g_dev) HF_HIP(hipMemcpyAsync(ctx->sys.g, g_host, sizeof(double) * nb, hipMemcpyHostToDevice, ctx->stream));
   const StepLoad L = step_load(ctx);   // the load and the source of this step, for every right-hand side below
   if (bdf2 && (projected || !ctx->extrapolate)) {
     // BDF2 with the projected start vector (kind 3) or u^n (kind 0): the right-hand side's pass keeps u^n for the next step
@@ -920,13 +932,13 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
   if (sweeps > 1 && !ct)   // b before lifting: the same for every sweep of the step while M is fixed
     HF_HIP(hipMemcpyAsync(ctx->kt.b0, ctx->d_b, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
   if (nb > 0) {
-    if (ctx->nlift_rows > 0)  // apply_lifting (:477)
-      hipLaunchKernelGGL(k_lift, dim3((ctx->nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift_rows,
-                         ctx->d_lift_rows, ctx->d_lift_ptr, ctx->d_lift_bc, ctx->d_lift_val, g, ctx->d_b);
+    if (ctx->sys.nlift_rows > 0)  // apply_lifting (:477)
+      hipLaunchKernelGGL(k_lift, dim3((ctx->sys.nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->sys.nlift_rows,
+                         ctx->sys.lift_rows, ctx->sys.lift_ptr, ctx->sys.lift_bc, ctx->sys.lift_val, g, ctx->d_b);
     // set_bc (:479); the same values seed the iterate.  With a projected start vector it runs once, after the combination
     // below: the basis vectors are zero on the Dirichlet rows, so the dot products do not see what b holds there
     if (!combine)
-      hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, g,
+      hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->sys.bc_dofs, g,
                          ctx->d_b, ctx->d_u);
   }
   if (combine) {
@@ -935,9 +947,9 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
     Q.pending = -1;
     hipLaunchKernelGGL(k_proj_combine, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, proj_active(ctx), Q.alpha, ctx->d_u);
     if (nb > 0)
-      hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, g, ctx->d_b, ctx->d_u);
+      hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->sys.bc_dofs, g, ctx->d_b, ctx->d_u);
   }
-  int rc = step_solve(ctx, rtol, atol, max_it);
+  int rc = solve_with_fallback(ctx, ctx->sys, LinSys{ctx->sys.A, ctx->sys.dinv, ctx->d_u, ctx->d_b}, rtol, atol, max_it);
   if (kt) {
     // Picard sweeps 2..p: re-evaluate at the latest iterate, lift with the new operator and solve again from that iterate
     int total = ctx->h_scal->iters;
@@ -952,12 +964,12 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
       else
         launch_spmv<0>(ctx, ctx->d_M, ctx->kt.w, ctx->d_b);
       if (nb > 0) {
-        if (ctx->nlift_rows > 0)
-          hipLaunchKernelGGL(k_lift, dim3((ctx->nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->nlift_rows,
-                             ctx->d_lift_rows, ctx->d_lift_ptr, ctx->d_lift_bc, ctx->d_lift_val, g, ctx->d_b);
-        hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->d_bc_dofs, g, ctx->d_b, ctx->d_u);
+        if (ctx->sys.nlift_rows > 0)
+          hipLaunchKernelGGL(k_lift, dim3((ctx->sys.nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->sys.nlift_rows,
+                             ctx->sys.lift_rows, ctx->sys.lift_ptr, ctx->sys.lift_bc, ctx->sys.lift_val, g, ctx->d_b);
+        hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->sys.bc_dofs, g, ctx->d_b, ctx->d_u);
       }
-      rc = step_solve(ctx, rtol, atol, max_it);
+      rc = solve_with_fallback(ctx, ctx->sys, LinSys{ctx->sys.A, ctx->sys.dinv, ctx->d_u, ctx->d_b}, rtol, atol, max_it);
       total += ctx->h_scal->iters;
     }
     ctx->h_scal->iters = total;
@@ -989,11 +1001,11 @@ int ensure_samples(hf_ctx* ctx, int ns) {
   return HF_OK;
 }
 
-int build_lift(hf_ctx* ctx) {
+int build_lift(hf_ctx* ctx, System& S) {
   // Host: for every free row i and BC column j with A_ij in the pattern -> (row i, bc index of j, slot)
-  const int32_t n = ctx->n, nbc = ctx->nbc;
+  const int32_t n = ctx->n, nbc = S.nbc;
   std::vector<int32_t> dofs(nbc);
-  HF_HIP(copy_sync(ctx, dofs.data(), ctx->d_bc_dofs, sizeof(int32_t) * nbc, hipMemcpyDeviceToHost));
+  HF_HIP(copy_sync(ctx, dofs.data(), S.bc_dofs, sizeof(int32_t) * nbc, hipMemcpyDeviceToHost));
   std::vector<int32_t> bc_index(n, -1);
   for (int32_t q = 0; q < nbc; ++q) bc_index[dofs[q]] = q;
   // free rows adjacent to a BC dof = columns of the BC rows (pattern is symmetric)
@@ -1016,18 +1028,18 @@ int build_lift(hf_ctx* ctx) {
     }
     ptr[r + 1] = static_cast<int32_t>(lbc.size());
   }
-  ctx->nlift_rows = static_cast<int32_t>(rows.size());
-  ctx->nlift = static_cast<int32_t>(lbc.size());
-  HF_TRY(dev_alloc(ctx, &ctx->d_lift_rows, rows.size()));
-  HF_TRY(dev_alloc(ctx, &ctx->d_lift_ptr, ptr.size()));
-  HF_TRY(dev_alloc(ctx, &ctx->d_lift_bc, lbc.size()));
-  HF_TRY(dev_alloc(ctx, &ctx->d_lift_slot, lslot.size()));
-  HF_TRY(dev_alloc(ctx, &ctx->d_lift_val, lbc.size()));
-  if (!rows.empty()) HF_HIP(copy_sync(ctx, ctx->d_lift_rows, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice));
-  HF_HIP(copy_sync(ctx, ctx->d_lift_ptr, ptr.data(), sizeof(int32_t) * ptr.size(), hipMemcpyHostToDevice));
+  S.nlift_rows = static_cast<int32_t>(rows.size());
+  S.nlift = static_cast<int32_t>(lbc.size());
+  HF_TRY(dev_alloc(ctx, &S.lift_rows, rows.size()));
+  HF_TRY(dev_alloc(ctx, &S.lift_ptr, ptr.size()));
+  HF_TRY(dev_alloc(ctx, &S.lift_bc, lbc.size()));
+  HF_TRY(dev_alloc(ctx, &S.lift_slot, lslot.size()));
+  HF_TRY(dev_alloc(ctx, &S.lift_val, lbc.size()));
+  if (!rows.empty()) HF_HIP(copy_sync(ctx, S.lift_rows, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice));
+  HF_HIP(copy_sync(ctx, S.lift_ptr, ptr.data(), sizeof(int32_t) * ptr.size(), hipMemcpyHostToDevice));
   if (!lbc.empty()) {
-    HF_HIP(copy_sync(ctx, ctx->d_lift_bc, lbc.data(), sizeof(int32_t) * lbc.size(), hipMemcpyHostToDevice));
-    HF_HIP(copy_sync(ctx, ctx->d_lift_slot, lslot.data(), sizeof(int32_t) * lslot.size(), hipMemcpyHostToDevice));
+    HF_HIP(copy_sync(ctx, S.lift_bc, lbc.data(), sizeof(int32_t) * lbc.size(), hipMemcpyHostToDevice));
+    HF_HIP(copy_sync(ctx, S.lift_slot, lslot.data(), sizeof(int32_t) * lslot.size(), hipMemcpyHostToDevice));
   }
   return HF_OK;
 }
