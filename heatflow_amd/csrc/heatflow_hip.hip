@@ -90,6 +90,26 @@ int source_steps_ok(hf_ctx* ctx, int64_t n_steps, const char* call) {
   return HF_OK;
 }
 
+// The argument checks of hf_set_source, with the texts under the caller's name (hf_batch_set_source applies them per column), and
+// the absorbing flags by row-gather tag-dictionary index, as the coefficient tables of the kernels
+int source_args_ok(hf_ctx* ctx, const char* call, int32_t n_tags, const int32_t* tags, double fwhm, double z0, double depth,
+                   std::vector<int32_t>& absorb) {
+  if (n_tags < 0 || !tags) return fail(ctx, HF_ERR_ARG, "%s: %d tags or a null pointer", call, n_tags);
+  if (!std::isfinite(fwhm) || !(fwhm > 0.0)) return fail(ctx, HF_ERR_ARG, "%s: fwhm must be positive and finite (got %g)", call, fwhm);
+  if (!std::isfinite(z0)) return fail(ctx, HF_ERR_ARG, "%s: z0 must be finite (got %g)", call, z0);
+  if (std::isnan(depth) || !(depth > 0.0)) return fail(ctx, HF_ERR_ARG, "%s: depth must be positive, or +inf for a uniform layer (got %g)", call, depth);
+  absorb.assign(64, 0);
+  for (int32_t q = 0; q < n_tags; ++q) {
+    const int32_t tg = tags[q];
+    if (tg < 0 || tg >= ctx->tab_len || !ctx->h_tag_used[tg]) return fail(ctx, HF_ERR_ARG, "%s: tag %d is not a cell tag of the mesh", call, tg);
+    for (int32_t q2 = 0; q2 < q; ++q2)
+      if (tags[q2] == tg) return fail(ctx, HF_ERR_ARG, "%s: tag %d is listed twice", call, tg);
+    for (size_t d = 0; d < ctx->h_rg_tags.size() && d < 64; ++d)
+      if (ctx->h_rg_tags[d] == tg) absorb[d] = 1;
+  }
+  return HF_OK;
+}
+
 void tangent_free(hf_ctx* ctx) {
   free_batch_state(ctx->tanb);
   dev_free(&ctx->tan.col); dev_free(&ctx->tan.dir); dev_free(&ctx->tan.F);
@@ -2050,18 +2070,8 @@ int hf_set_source(hf_ctx* ctx, int32_t n_tags, const int32_t* tags, double fwhm,
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_set_source: a batch is open (the batched loop has no load term)");
   if (n_tags < 0 || !tags) return fail(ctx, HF_ERR_ARG, "hf_set_source: %d tags or a null pointer", n_tags);
   if (!ctx->rg_ok) return fail(ctx, HF_ERR_ARG, "hf_set_source: the source's load is formed by the row-gather kernel only (a mesh with row-gather lists)");
-  if (!std::isfinite(fwhm) || !(fwhm > 0.0)) return fail(ctx, HF_ERR_ARG, "hf_set_source: fwhm must be positive and finite (got %g)", fwhm);
-  if (!std::isfinite(z0)) return fail(ctx, HF_ERR_ARG, "hf_set_source: z0 must be finite (got %g)", z0);
-  if (std::isnan(depth) || !(depth > 0.0)) return fail(ctx, HF_ERR_ARG, "hf_set_source: depth must be positive, or +inf for a uniform layer (got %g)", depth);
-  std::vector<int32_t> absorb(64, 0);    // by row-gather tag-dictionary index, as the coefficient tables of the kernels
-  for (int32_t q = 0; q < n_tags; ++q) {
-    const int32_t tg = tags[q];
-    if (tg < 0 || tg >= ctx->tab_len || !ctx->h_tag_used[tg]) return fail(ctx, HF_ERR_ARG, "hf_set_source: tag %d is not a cell tag of the mesh", tg);
-    for (int32_t q2 = 0; q2 < q; ++q2)
-      if (tags[q2] == tg) return fail(ctx, HF_ERR_ARG, "hf_set_source: tag %d is listed twice", tg);
-    for (size_t d = 0; d < ctx->h_rg_tags.size() && d < 64; ++d)
-      if (ctx->h_rg_tags[d] == tg) absorb[d] = 1;
-  }
+  std::vector<int32_t> absorb;
+  HF_TRY(source_args_ok(ctx, "hf_set_source", n_tags, tags, fwhm, z0, depth, absorb));
   source_free(ctx);   // a source that was on is off until the new one is complete: a failure below leaves none set
   hf_ctx::Source& S = ctx->src;
   HF_TRY(dev_alloc(ctx, &S.F1, ctx->n));
@@ -2514,6 +2524,152 @@ int hf_batch_get_state(hf_ctx* ctx, int32_t j, double* u) {
   return HF_OK;
 }
 
+int hf_batch_set_source(hf_ctx* ctx, int32_t n_tags, const int32_t* tags, double z0, const double* fwhm, const double* depth) {
+  if (!ctx) return HF_ERR_ARG;
+  hf_ctx::Batch& B = ctx->batch;
+  if (B.nv == 0) return fail(ctx, HF_ERR_STATE, "hf_batch_set_source: no batch is open");
+  HF_HIP(hipSetDevice(ctx->dev));
+  if (n_tags == 0) { HF_HIP(hipStreamSynchronize(ctx->stream)); free_batch_source(ctx); return HF_OK; }
+  if (!ctx->rg_ok) return fail(ctx, HF_ERR_STATE, "hf_batch_set_source: the source's load is formed by the row-gather kernel only (a mesh with row-gather lists)");
+  if (!fwhm || !depth) return fail(ctx, HF_ERR_ARG, "hf_batch_set_source: null pointer");
+  const int nv = B.nv;
+  const size_t n = static_cast<size_t>(ctx->n);
+  std::vector<int32_t> absorb;
+  for (int j = 0; j < nv; ++j) HF_TRY(source_args_ok(ctx, "hf_batch_set_source", n_tags, tags, fwhm[j], z0, depth[j], absorb));
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  free_batch_source(ctx);   // a source that was on is off until the new one is complete: a failure below leaves none set
+  hf_ctx::BatchSource& S = ctx->bsrc;
+  DevTemp<int32_t> t_absorb;
+  DevTemp<double> t_F;
+  HF_TRY(dev_alloc(ctx, &t_absorb.p, 64));
+  HF_TRY(dev_alloc(ctx, &t_F.p, n));
+  HF_TRY(dev_alloc(ctx, &S.F1, n * nv));
+  HF_TRY(dev_alloc(ctx, &S.load, n * nv));
+  HF_HIP(copy_sync(ctx, t_absorb.p, absorb.data(), sizeof(int32_t) * 64, hipMemcpyHostToDevice));
+  HF_HIP(hipMemsetAsync(S.load, 0, sizeof(double) * n * nv, ctx->stream));
+  // hf_set_source's launch per distinct (fwhm, depth), the same kernel on the same inputs; its result goes to every column that has the pair
+  HF_TRY(rowvisit_warm<VisitSource>(ctx, &k_source_load));
+  HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
+  for (int j = 0; j < nv; ++j) {
+    bool seen = false;
+    for (int q = 0; q < j && !seen; ++q) seen = fwhm[q] == fwhm[j] && depth[q] == depth[j];
+    if (seen) continue;
+    const double c_r = 4.0 * M_LN2 / (fwhm[j] * fwhm[j]), inv_depth = std::isinf(depth[j]) ? 0.0 : 1.0 / depth[j];
+    HF_TRY(launch_rowvisit<VisitSource>(ctx, &k_source_load, nullptr, ctx->d_rowptr, t_absorb.p, c_r, z0, inv_depth, t_F.p));
+    for (int q = j; q < nv; ++q)
+      if (fwhm[q] == fwhm[j] && depth[q] == depth[j])
+        hipLaunchKernelGGL(kb_put_column, dim3(1024), dim3(256), 0, ctx->stream, n, nv, q, t_F.p, S.F1);
+  }
+  HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
+  HF_HIP(hipGetLastError());
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  float ms = 0.f;
+  HF_HIP(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+  ctx->last_ms = ms;
+  // the rows with an absorbing triangle, ascending: the nodes of the triangles of the listed tags, from the host copy of the mesh
+  std::vector<char> has(n, 0);
+  std::vector<char> listed(static_cast<size_t>(ctx->tab_len), 0);
+  for (int32_t q = 0; q < n_tags; ++q) listed[tags[q]] = 1;
+  for (size_t e = 0; e < static_cast<size_t>(ctx->ne); ++e)
+    if (listed[ctx->h_tag[e]]) { has[ctx->h_tri[3 * e]] = 1; has[ctx->h_tri[3 * e + 1]] = 1; has[ctx->h_tri[3 * e + 2]] = 1; }
+  std::vector<int32_t> rows;
+  for (size_t i = 0; i < n; ++i)
+    if (has[i]) rows.push_back(static_cast<int32_t>(i));
+  HF_TRY(dev_alloc(ctx, &S.rows, rows.size()));
+  HF_HIP(copy_sync(ctx, S.rows, rows.data(), sizeof(int32_t) * rows.size(), hipMemcpyHostToDevice));
+  S.nrows = static_cast<int>(rows.size());
+  S.steps = 0; S.next = 0;
+  S.on = true;
+  B.load = S.load;
+  return HF_OK;
+}
+
+int hf_batch_get_source(hf_ctx* ctx, int32_t j, double* F) {
+  if (!ctx) return HF_ERR_ARG;
+  const hf_ctx::Batch& B = ctx->batch;
+  if (B.nv == 0) return fail(ctx, HF_ERR_STATE, "hf_batch_get_source: no batch is open");
+  if (!ctx->bsrc.on) return fail(ctx, HF_ERR_STATE, "hf_batch_get_source: no source set (hf_batch_set_source first)");
+  if (j < 0 || j >= B.nv || !F) return fail(ctx, HF_ERR_ARG, "hf_batch_get_source: bad column or null pointer");
+  HF_HIP(hipSetDevice(ctx->dev));
+  hipLaunchKernelGGL(kb_get_column, dim3(1024), dim3(256), 0, ctx->stream, static_cast<size_t>(ctx->n), B.nv, j, ctx->bsrc.F1, ctx->d_tmp);
+  HF_HIP(hipGetLastError());
+  HF_HIP(copy_sync(ctx, F, ctx->d_tmp, sizeof(double) * ctx->n, hipMemcpyDeviceToHost));
+  return HF_OK;
+}
+
+int hf_batch_set_source_amplitudes(hf_ctx* ctx, int32_t n_steps, const double* p) {
+  if (!ctx) return HF_ERR_ARG;
+  const hf_ctx::Batch& B = ctx->batch;
+  if (B.nv == 0) return fail(ctx, HF_ERR_STATE, "hf_batch_set_source_amplitudes: no batch is open");
+  hf_ctx::BatchSource& S = ctx->bsrc;
+  if (!S.on) return fail(ctx, HF_ERR_STATE, "hf_batch_set_source_amplitudes: no source set (hf_batch_set_source first)");
+  if (n_steps < 0 || (n_steps > 0 && !p)) return fail(ctx, HF_ERR_ARG, "hf_batch_set_source_amplitudes: %d steps or a null pointer", n_steps);
+  const size_t len = static_cast<size_t>(n_steps) * B.nv;
+  for (size_t q = 0; q < len; ++q)
+    if (!std::isfinite(p[q])) return fail(ctx, HF_ERR_ARG, "hf_batch_set_source_amplitudes: the amplitude of step %zu, column %zu is not finite", q / B.nv, q % B.nv);
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  dev_free(&S.amp);
+  S.steps = 0; S.next = 0;
+  if (n_steps == 0) return HF_OK;
+  HF_TRY(dev_alloc(ctx, &S.amp, len));
+  HF_HIP(copy_sync(ctx, S.amp, p, sizeof(double) * len, hipMemcpyHostToDevice));
+  S.steps = n_steps;
+  return HF_OK;
+}
+
+int hf_batch_set_monitors(hf_ctx* ctx, int32_t on) {
+  if (!ctx) return HF_ERR_ARG;
+  if (ctx->batch.nv == 0) return fail(ctx, HF_ERR_STATE, "hf_batch_set_monitors: no batch is open");
+  if (on && !ctx->mon.on) return fail(ctx, HF_ERR_STATE, "hf_batch_set_monitors: no monitors set (hf_set_monitors before hf_batch_begin)");
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  free_batch_monitors(ctx);
+  if (!on) return HF_OK;
+  hf_ctx::BatchMonitor& M = ctx->bmon;
+  const size_t G = static_cast<size_t>(ctx->mon.grid) * ctx->mon.nd, GV = G * ctx->batch.nv;
+  HF_TRY(dev_alloc(ctx, &M.part_f, G + 4 * GV));
+  HF_TRY(dev_alloc(ctx, &M.part_i, 2 * GV));
+  HF_TRY(dev_alloc(ctx, &M.now, bmon_row(ctx)));
+  M.on = true;
+  return HF_OK;
+}
+
+int hf_batch_monitor_now(hf_ctx* ctx, double* out) {
+  if (!ctx) return HF_ERR_ARG;
+  if (ctx->batch.nv == 0) return fail(ctx, HF_ERR_STATE, "hf_batch_monitor_now: no batch is open");
+  if (!ctx->bmon.on) return fail(ctx, HF_ERR_STATE, "hf_batch_monitor_now: the batch's monitors are off (hf_batch_set_monitors first)");
+  if (!out) return fail(ctx, HF_ERR_ARG, "hf_batch_monitor_now: null pointer");
+  HF_HIP(hipSetDevice(ctx->dev));
+  bmon_launch(ctx, ctx->bmon.now);
+  HF_HIP(hipGetLastError());
+  HF_HIP(copy_sync(ctx, out, ctx->bmon.now, sizeof(double) * bmon_row(ctx), hipMemcpyDeviceToHost));
+  return HF_OK;
+}
+
+int hf_batch_monitor_count(hf_ctx* ctx, int32_t* n_records) {
+  if (!ctx) return HF_ERR_ARG;
+  if (ctx->batch.nv == 0) return fail(ctx, HF_ERR_STATE, "hf_batch_monitor_count: no batch is open");
+  if (!n_records) return fail(ctx, HF_ERR_ARG, "hf_batch_monitor_count: null pointer");
+  *n_records = static_cast<int32_t>(ctx->bmon.count);
+  return HF_OK;
+}
+
+int hf_batch_get_monitors(hf_ctx* ctx, int32_t first, int32_t count, double* out) {
+  if (!ctx) return HF_ERR_ARG;
+  if (ctx->batch.nv == 0) return fail(ctx, HF_ERR_STATE, "hf_batch_get_monitors: no batch is open");
+  const hf_ctx::BatchMonitor& M = ctx->bmon;
+  if (!M.on) return fail(ctx, HF_ERR_STATE, "hf_batch_get_monitors: the batch's monitors are off (hf_batch_set_monitors first)");
+  if (first < 0 || count < 0 || static_cast<int64_t>(first) + count > M.count)
+    return fail(ctx, HF_ERR_ARG, "hf_batch_get_monitors: records [%d, %lld) outside the %lld records kept", first,
+                static_cast<long long>(first) + count, static_cast<long long>(M.count));
+  if (count > 0 && !out) return fail(ctx, HF_ERR_ARG, "hf_batch_get_monitors: null pointer for records [%d, %d)", first, first + count);
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_HIP(copy_sync(ctx, out, M.rec + static_cast<size_t>(first) * bmon_row(ctx), sizeof(double) * static_cast<size_t>(count) * bmon_row(ctx),
+                   hipMemcpyDeviceToHost));
+  return HF_OK;
+}
+
 int hf_batch_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, double atol, int32_t max_it, int32_t ns,
                  const int32_t* nodes, double* samples, int32_t* iters) {
   return hf_batch_run_flux(ctx, n_steps, g_all, rtol, atol, max_it, ns, nodes, samples, iters, 0, 0.0, 0, 0, nullptr, nullptr, nullptr);
@@ -2541,10 +2697,15 @@ int hf_batch_run_flux(hf_ctx* ctx, int32_t n_steps, const double* g_all, double 
     for (int32_t q = 0; q < nfs; ++q)
       if (flux_nodes[q] < 0 || flux_nodes[q] >= ctx->n) return fail(ctx, HF_ERR_ARG, "hf_batch_run_flux: node %d outside [0,%d)", flux_nodes[q], ctx->n);
   }
+  hf_ctx::BatchSource& BS = ctx->bsrc;
+  if (BS.on && BS.steps > 0 && BS.next + n_steps > BS.steps)
+    return fail(ctx, HF_ERR_STATE, "%s: the source has %lld amplitudes left for %lld steps (hf_batch_set_source_amplitudes)",
+                flux_components != 0 ? "hf_batch_run_flux" : "hf_batch_run", static_cast<long long>(BS.steps - BS.next), static_cast<long long>(n_steps));
   HF_HIP(hipSetDevice(ctx->dev));
   const int nv = B.nv;
   const size_t gstep = static_cast<size_t>(ctx->sys.nbc) * nv;
   DevTemp<double> t_sall, t_fall;
+  HF_TRY(bmon_room(ctx, n_steps));
   if (flux_components != 0) {
     HF_TRY(ensure_batch_flux(ctx, nv, ncomp));
     if (nfs > ctx->fsamp_cap) { HF_TRY(dev_alloc(ctx, &ctx->d_fsamp_idx, nfs)); ctx->fsamp_cap = nfs; }
@@ -2564,7 +2725,16 @@ int hf_batch_run_flux(hf_ctx* ctx, int32_t n_steps, const double* g_all, double 
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   for (int32_t s = 0; s < n_steps && rc == HF_OK; ++s) {
     const double* gs = ctx->sys.nbc > 0 ? B.g + gstep * s : nullptr;
+    if (BS.on && BS.nrows > 0) {   // the step's load p_j F1_j on the absorbing rows (B.load points at it)
+      const double* p = BS.steps > 0 ? BS.amp + static_cast<size_t>(BS.next) * nv : nullptr;
+      const int blocks = (BS.nrows * nv + 255) / 256;
+      dispatch_nv(nv, [&](auto w) {
+        hipLaunchKernelGGL(kb_source_load<decltype(w)::value>, dim3(blocks), dim3(256), 0, ctx->stream, BS.nrows, BS.rows, p, BS.F1, BS.load);
+      });
+    }
+    if (BS.on && BS.steps > 0) BS.next += 1;
     rc = batch_dispatch(ctx, B, [&](auto ops) { return decltype(ops)::step(ctx, B, gs, rtol, atol, max_it); });
+    if (ctx->bmon.on && rc == HF_OK) bmon_record(ctx);
     if (iters)
       for (int j = 0; j < nv; ++j) iters[static_cast<size_t>(s) * nv + j] = B.h_scal[j].iters;
     if (ns > 0 && rc == HF_OK) {

@@ -794,6 +794,20 @@ __global__ void kb_source_columns(int nrows, const int32_t* __restrict__ rows, u
   F[static_cast<size_t>(i) * NV + j] += (c0 * F1[i] + c1 * Gf[i]) + c2 * Gd[i];
 }
 
+// The source of a batched sweep (hf_batch_set_source): load[i * NV + j] = p[j] F1[i * NV + j] for the rows i of
+// the compact list `rows` (those with an absorbing triangle, ascending); the rest of `load` was zeroed once.  p holds the step's
+// amplitude per column (null: amplitude 0).  One thread per (row, column), shaped like kb_source_columns: a wave's stores are
+// contiguous over j, vector stores, no atomics.
+template <int NV>
+__global__ void kb_source_load(int nrows, const int32_t* __restrict__ rows, const double* __restrict__ p /* [NV] */,
+                               const double* __restrict__ F1, double* __restrict__ load) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int q = t / NV, j = t % NV;
+  if (q >= nrows) return;
+  const size_t o = static_cast<size_t>(rows[q]) * NV + j;
+  load[o] = (p != nullptr ? p[j] : 0.0) * F1[o];
+}
+
 // column j of an interleaved array <- / -> a plain array
 __global__ void kb_put_column(size_t n, int nv, int j, const double* __restrict__ src, double* __restrict__ dst) {
   for (size_t i = static_cast<size_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n; i += static_cast<size_t>(gridDim.x) * blockDim.x)
@@ -827,7 +841,25 @@ void free_batch_state(hf_ctx::Batch& B) {
   B.sysA = B.sysDinv = nullptr;
 }
 
-void free_batch(hf_ctx* ctx) { free_batch_state(ctx->batch); free_batch_state(ctx->fluxnb); }
+// the open batch's own source and monitor records die with it
+void free_batch_source(hf_ctx* ctx) {
+  hf_ctx::BatchSource& S = ctx->bsrc;
+  dev_free(&S.F1); dev_free(&S.load); dev_free(&S.rows); dev_free(&S.amp);
+  S = hf_ctx::BatchSource();
+  ctx->batch.load = nullptr;
+}
+void free_batch_monitors(hf_ctx* ctx) {
+  hf_ctx::BatchMonitor& M = ctx->bmon;
+  dev_free(&M.part_f); dev_free(&M.part_i); dev_free(&M.rec); dev_free(&M.now);
+  M = hf_ctx::BatchMonitor();
+}
+
+void free_batch(hf_ctx* ctx) {
+  free_batch_source(ctx);
+  free_batch_monitors(ctx);
+  free_batch_state(ctx->batch);
+  free_batch_state(ctx->fluxnb);
+}
 
 void free_batch_cols(hf_ctx* ctx) {
   hf_ctx::BatchCols& T = ctx->bcols;

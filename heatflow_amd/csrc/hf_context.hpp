@@ -381,6 +381,30 @@ struct hf_ctx {
     int32_t *ptr = nullptr, *dict = nullptr, *own = nullptr;
     uint16_t* id = nullptr;
   } bcols;
+  // source of the open batch (hf_batch_set_source): per column the load at unit amplitude and a table of
+  // amplitudes; kb_source_load<nv> forms `load` = p_j F1_j on the absorbing rows before every step's right-hand side, and
+  // batch.load points at it while the source is on.  Nothing below is allocated, and nothing is launched, while it is off; it
+  // dies with the batch (free_batch).
+  struct BatchSource {
+    bool on = false;
+    double* F1 = nullptr;        // n x nv, interleaved
+    double* load = nullptr;      // n x nv, interleaved: zeroed once, only the absorbing rows are ever written
+    int32_t* rows = nullptr;     // the rows with an absorbing triangle, ascending
+    int nrows = 0;
+    double* amp = nullptr;       // steps x nv amplitudes of the next steps, on the device; steps = 0: amplitude 0
+    int64_t steps = 0, next = 0;
+  } bsrc;
+  // monitor records of the open batch (hf_batch_set_monitors): the context's table (mon.slot, mon.tags, mon.theta
+  // and the schedule mon.nchunks / mon.grid), partials and records of its own.  Nothing below is allocated, and nothing is
+  // launched, while the switch is off; it dies with the batch.
+  struct BatchMonitor {
+    bool on = false;
+    double* part_f = nullptr;    // nd x grid (I0), then 4 x nd x nv x grid doubles: I1, H, the largest and the smallest value
+    int32_t* part_i = nullptr;   // 2 x nd x nv x grid: their nodes
+    double* rec = nullptr;       // cap records of nv x tab_len x 7 doubles
+    double* now = nullptr;       // one record, for hf_batch_monitor_now
+    int64_t cap = 0, count = 0;
+  } bmon;
   Batch fluxb;                   // two-column state of the read-flux projection (both components in one PCG)
   Batch fluxnb;                  // nv-column state of the batched loop's read-flux projection (hf_batch_run_flux): one gradient component of every column per PCG
   int32_t* d_fsamp_idx = nullptr;   // its sample nodes

@@ -420,6 +420,183 @@ __global__ __launch_bounds__(MON_FT) void k_monitor_tan_final(int G, int tab_len
   }
 }
 
+// ---- records of a batched sweep (hf_batch_set_monitors) ----------------------------------------------------------
+
+// what a workgroup of kb_monitor leaves: I0[index * workgroups + workgroup] (the columns share it) and, per column,
+// X[(index * nvt + j) * workgroups + workgroup]
+struct MonBPart {
+  double *I0, *I1, *H, *vmax, *vmin;
+  int32_t *imax, *imin;
+};
+
+// k_monitor's sibling for the interleaved state u[node * nvt + j] of a batch: one lane per triangle, the same chunks, ChunkIter
+// schedule, slot table and thresholds.  The lane loads its three nodes' NV values u[node * nvt + j0 .. + NV) as vectors and runs
+// k_monitor's body once per column: monitor_term on the column's three values (its I0 does not depend on them and is reduced once
+// per triangle, for the launch with j0 = 0), the extremes by mon_take_max / mon_take_min, per dictionary index present in the wave
+// the same masked shuffle tree, one addition per chunk to the wave's LDS accumulator [wave][index][column] in ascending chunk
+// order, the four waves added in wave order at the end.  Every accumulator of column j therefore sees the sequence of operations
+// k_monitor's sees for the field u[. * nvt + j]: the same bits.  No atomics.
+template <int NV>
+__global__ __launch_bounds__(MON_T) void kb_monitor(int ne, int nchunks, int tab_len, int nd, int nvt, int j0, const int4* __restrict__ elem,
+                                                   const double2* __restrict__ zr, const double* __restrict__ u,
+                                                   const uint8_t* __restrict__ slot_of_tag, const double* __restrict__ theta, MonBPart part) {
+  extern __shared__ double s_acc[];         // 4 x [4][nd][NV] doubles (I1, H, vmax, vmin), [4][nd] (I0), 2 x [4][nd][NV] ints, then the slots
+  __shared__ double s_th[MON_ND];
+  const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+  const int W = 4 * nd * NV;                // entries of one per-column accumulator array
+  double* const s_I1 = s_acc;
+  double* const s_H = s_acc + W;
+  double* const s_vmax = s_acc + 2 * W;
+  double* const s_vmin = s_acc + 3 * W;
+  double* const s_I0 = s_acc + 4 * W;
+  int* const s_imax = reinterpret_cast<int*>(s_I0 + 4 * nd);
+  int* const s_imin = s_imax + W;
+  uint8_t* const s_slot = reinterpret_cast<uint8_t*>(s_imin + W);
+  for (int i = t; i < tab_len; i += MON_T) s_slot[i] = slot_of_tag[i];
+  if (t < MON_ND) s_th[t] = theta[t];
+  for (int i = t; i < W; i += MON_T) {
+    s_I1[i] = 0.0; s_H[i] = 0.0; s_vmax[i] = -INFINITY; s_vmin[i] = INFINITY;
+    s_imax[i] = INT32_MAX; s_imin[i] = INT32_MAX;
+  }
+  for (int i = t; i < 4 * nd; i += MON_T) s_I0[i] = 0.0;
+  __syncthreads();
+  for (ChunkIter it(nchunks); it.chunk < it.end; it.chunk += it.step) {
+    const int e = it.chunk * MON_T + t;
+    int d = -1;
+    int4 E = make_int4(0, 0, 0, 0);
+    if (e < ne) {
+      E = elem[e];
+      const int s = s_slot[E.w];
+      if (s != MON_NONE) d = s;
+    }
+    double2 P0 = make_double2(0.0, 0.0), P1 = P0, P2 = P0;
+    double th = 0.0;
+    const double2 *q0 = nullptr, *q1 = nullptr, *q2 = nullptr;
+    if (d >= 0) {
+      P0 = zr[E.x]; P1 = zr[E.y]; P2 = zr[E.z];
+      th = s_th[d];
+      q0 = reinterpret_cast<const double2*>(u + static_cast<size_t>(E.x) * nvt + j0);
+      q1 = reinterpret_cast<const double2*>(u + static_cast<size_t>(E.y) * nvt + j0);
+      q2 = reinterpret_cast<const double2*>(u + static_cast<size_t>(E.z) * nvt + j0);
+    }
+    const unsigned long long present = __ballot(d >= 0);      // the same in every lane: the loops below are uniform over the wave
+#pragma unroll
+    for (int jj = 0; jj < NV / 2; ++jj) {
+      double2 a = make_double2(0.0, 0.0), b = a, c = a;
+      if (d >= 0) { a = q0[jj]; b = q1[jj]; c = q2[jj]; }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int j = 2 * jj + h;
+        MonTerm m{0.0, 0.0, 0.0};
+        double vmax = -INFINITY, vmin = INFINITY;
+        int imax = INT32_MAX, imin = INT32_MAX;
+        if (d >= 0) {
+          const double u0 = h ? a.y : a.x, u1 = h ? b.y : b.x, u2 = h ? c.y : c.x;
+          m = monitor_term(P0, P1, P2, u0, u1, u2, th);
+          vmax = u0; imax = E.x; mon_take_max(vmax, imax, u1, E.y); mon_take_max(vmax, imax, u2, E.z);
+          vmin = u0; imin = E.x; mon_take_min(vmin, imin, u1, E.y); mon_take_min(vmin, imin, u2, E.z);
+        }
+        const bool with_I0 = j == 0 && j0 == 0;              // I0 of the triangle: reduced with the first column of the first group
+        unsigned long long todo = present;
+        while (todo != 0ull) {
+          const int ds = __shfl(d, __ffsll(static_cast<long long>(todo)) - 1, 64);
+          const bool mine = d == ds;
+          double a0 = mine ? m.I0 : 0.0, a1 = mine ? m.I1 : 0.0, a2 = mine ? m.H : 0.0;
+          double bmax = mine ? vmax : -INFINITY, bmin = mine ? vmin : INFINITY;
+          int jmax = mine ? imax : INT32_MAX, jmin = mine ? imin : INT32_MAX;
+#pragma unroll
+          for (int o = 32; o > 0; o >>= 1) {
+#pragma clang fp contract(off)
+            if (with_I0) a0 += __shfl_down(a0, o, 64);
+            a1 += __shfl_down(a1, o, 64);
+            a2 += __shfl_down(a2, o, 64);
+            mon_take_max(bmax, jmax, __shfl_down(bmax, o, 64), __shfl_down(jmax, o, 64));
+            mon_take_min(bmin, jmin, __shfl_down(bmin, o, 64), __shfl_down(jmin, o, 64));
+          }
+          if (lane == 0) {
+#pragma clang fp contract(off)
+            const int k = (wv * nd + ds) * NV + j;
+            if (with_I0) s_I0[wv * nd + ds] += a0;
+            s_I1[k] += a1; s_H[k] += a2;
+            double v = s_vmax[k]; int i = s_imax[k];
+            mon_take_max(v, i, bmax, jmax);
+            s_vmax[k] = v; s_imax[k] = i;
+            v = s_vmin[k]; i = s_imin[k];
+            mon_take_min(v, i, bmin, jmin);
+            s_vmin[k] = v; s_imin[k] = i;
+          }
+          todo &= ~__ballot(mine);
+        }
+      }
+    }
+  }
+  __syncthreads();
+  const size_t G = gridDim.x;
+  const int w = nd * NV;
+  for (int i = t; i < w; i += MON_T) {
+#pragma clang fp contract(off)
+    const int dd = i / NV, j = i - dd * NV;
+    const size_t o = (static_cast<size_t>(dd) * nvt + j0 + j) * G + blockIdx.x;
+    part.I1[o] = ((s_I1[i] + s_I1[w + i]) + s_I1[2 * w + i]) + s_I1[3 * w + i];
+    part.H[o] = ((s_H[i] + s_H[w + i]) + s_H[2 * w + i]) + s_H[3 * w + i];
+    double v = s_vmax[i], x = s_vmin[i];
+    int p = s_imax[i], q = s_imin[i];
+    for (int k = 1; k < 4; ++k) {
+      mon_take_max(v, p, s_vmax[k * w + i], s_imax[k * w + i]);
+      mon_take_min(x, q, s_vmin[k * w + i], s_imin[k * w + i]);
+    }
+    part.vmax[o] = v; part.imax[o] = p; part.vmin[o] = x; part.imin[o] = q;
+  }
+  if (j0 == 0)
+    for (int i = t; i < nd; i += MON_T) {
+#pragma clang fp contract(off)
+      part.I0[static_cast<size_t>(i) * G + blockIdx.x] = ((s_I0[i] + s_I0[nd + i]) + s_I0[2 * nd + i]) + s_I0[3 * nd + i];
+    }
+}
+
+// Workgroup (d, j) adds the G <= MON_FT partials of dictionary index d and column j exactly as k_monitor_final adds those of d
+// (lane g holds workgroup g's, a shuffle tree per wave, then the 16 wave results front to back) and writes the seven fields of
+// out[(j * tab_len + tag) * 7 ..].  Workgroup (0, j) also writes the zero rows of column j's tags that are not monitored.
+__global__ __launch_bounds__(MON_FT) void kb_monitor_final(int G, int tab_len, int nvt, MonBPart part, const uint8_t* __restrict__ slot_of_tag,
+                                                          const int32_t* __restrict__ tag_of_slot, double* __restrict__ out) {
+  __shared__ double s_I0[16], s_I1[16], s_H[16], s_vmax[16], s_vmin[16];
+  __shared__ int s_imax[16], s_imin[16];
+  const int d = blockIdx.x, jc = blockIdx.y, t = threadIdx.x, wv = t >> 6, lane = t & 63;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, v = -INFINITY, w = INFINITY;
+  int i = INT32_MAX, j = INT32_MAX;
+  if (t < G) {
+    const size_t o = (static_cast<size_t>(d) * nvt + jc) * G + t;
+    a0 = part.I0[static_cast<size_t>(d) * G + t]; a1 = part.I1[o]; a2 = part.H[o];
+    v = part.vmax[o]; i = part.imax[o]; w = part.vmin[o]; j = part.imin[o];
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma clang fp contract(off)
+    a0 += __shfl_down(a0, o, 64);
+    a1 += __shfl_down(a1, o, 64);
+    a2 += __shfl_down(a2, o, 64);
+    mon_take_max(v, i, __shfl_down(v, o, 64), __shfl_down(i, o, 64));
+    mon_take_min(w, j, __shfl_down(w, o, 64), __shfl_down(j, o, 64));
+  }
+  if (lane == 0) { s_I0[wv] = a0; s_I1[wv] = a1; s_H[wv] = a2; s_vmax[wv] = v; s_imax[wv] = i; s_vmin[wv] = w; s_imin[wv] = j; }
+  __syncthreads();
+  double* const col = out + static_cast<size_t>(jc) * tab_len * MON_F;
+  if (t == 0) {
+#pragma clang fp contract(off)
+    for (int k = 1; k < MON_FT / 64; ++k) {
+      a0 += s_I0[k]; a1 += s_I1[k]; a2 += s_H[k];
+      mon_take_max(v, i, s_vmax[k], s_imax[k]);
+      mon_take_min(w, j, s_vmin[k], s_imin[k]);
+    }
+    double* row = col + static_cast<size_t>(tag_of_slot[d]) * MON_F;
+    row[0] = v; row[1] = static_cast<double>(i); row[2] = w; row[3] = static_cast<double>(j);
+    row[4] = a0; row[5] = a1; row[6] = a2;
+  }
+  if (d == 0)
+    for (int k = t; k < tab_len * MON_F; k += MON_FT)
+      if (slot_of_tag[k / MON_F] == MON_NONE) col[k] = 0.0;
+}
+
 // ---- host side --------------------------------------------------------------------------------------------------------------
 
 void monitor_free(hf_ctx* ctx) {
@@ -540,6 +717,62 @@ inline void montan_record(hf_ctx* ctx) {
                 M.trec + static_cast<size_t>(M.tcount) * montan_row(ctx, M.tnv));
   M.tindex.push_back(static_cast<int32_t>(M.count - 1));
   M.tcount += 1;
+}
+
+// ---- records of the open batch -----------------------------------------------------------------------------------
+
+inline size_t bmon_row(const hf_ctx* ctx) { return static_cast<size_t>(ctx->batch.nv) * monitor_row(ctx); }
+
+// dynamic LDS of kb_monitor<NV>: per wave and monitored tag four doubles and two ints per column and one double (I0), then the slots
+inline size_t bmon_lds(const hf_ctx* ctx, int NV) {
+  return static_cast<size_t>(4) * ctx->mon.nd * (static_cast<size_t>(NV) * (4 * sizeof(double) + 2 * sizeof(int)) + sizeof(double)) +
+         static_cast<size_t>((ctx->tab_len + 15) & ~15);
+}
+
+// Room for n_more records of the open batch behind the ones kept, before the caller's first launch (as monitor_room)
+int bmon_room(hf_ctx* ctx, int64_t n_more) {
+  hf_ctx::BatchMonitor& M = ctx->bmon;
+  if (!M.on || M.count + n_more <= M.cap) return HF_OK;
+  const int64_t cap = std::max<int64_t>(M.count + n_more, 2 * M.cap);
+  double* grown = nullptr;
+  HF_TRY(dev_alloc(ctx, &grown, static_cast<size_t>(cap) * bmon_row(ctx)));
+  if (M.count > 0) {
+    const hipError_t e = copy_sync(ctx, grown, M.rec, sizeof(double) * static_cast<size_t>(M.count) * bmon_row(ctx), hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) { dev_free(&grown); return fail(ctx, HF_ERR_HIP, "batch monitor records: copy failed: %s", hipGetErrorString(e)); }
+  }
+  dev_free(&M.rec);
+  M.rec = grown;
+  M.cap = cap;
+  return HF_OK;
+}
+
+// The launches of one evaluation of the open batch's state, on the stream, into `out` (nv x tab_len x MON_F doubles on the device).
+// The columns go in one launch where its accumulators fit the LDS of a workgroup, else in groups of the widest power of two that
+// does (a function of nd and nv alone), one launch per group, as montan_launch does.
+void bmon_launch(hf_ctx* ctx, double* out) {
+  const hf_ctx::Monitor& M = ctx->mon;
+  const hf_ctx::BatchMonitor& Q = ctx->bmon;
+  const int nv = ctx->batch.nv;
+  const size_t G = static_cast<size_t>(M.grid) * M.nd, GV = G * nv;
+  MonBPart P;
+  P.I0 = Q.part_f; P.I1 = Q.part_f + G; P.H = P.I1 + GV; P.vmax = P.H + GV; P.vmin = P.vmax + GV;
+  P.imax = Q.part_i; P.imin = Q.part_i + GV;
+  int gw = nv;
+  while (gw > 2 && bmon_lds(ctx, gw) > MON_LDS) gw >>= 1;
+  const size_t sm = bmon_lds(ctx, gw);
+  for (int j0 = 0; j0 < nv; j0 += gw)
+    dispatch_nv(gw, [&](auto w) {
+      hipLaunchKernelGGL(kb_monitor<decltype(w)::value>, dim3(M.grid), dim3(MON_T), sm, ctx->stream, ctx->ne, M.nchunks, ctx->tab_len, M.nd,
+                         nv, j0, ctx->d_elem, ctx->d_zr, ctx->batch.u, M.slot, M.theta, P);
+    });
+  hipLaunchKernelGGL(kb_monitor_final, dim3(M.nd, nv), dim3(MON_FT), 0, ctx->stream, M.grid, ctx->tab_len, nv, P, M.slot, M.tags, out);
+}
+
+// The record of the batched step that has just been queued (the caller made room with bmon_room)
+inline void bmon_record(hf_ctx* ctx) {
+  hf_ctx::BatchMonitor& M = ctx->bmon;
+  bmon_launch(ctx, M.rec + static_cast<size_t>(M.count) * bmon_row(ctx));
+  M.count += 1;
 }
 
 }  // namespace

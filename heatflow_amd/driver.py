@@ -46,10 +46,10 @@ from .aniso import CAPACITY_KINDS, DIRECTIONAL_HINT, capacity_scale, check_capac
 from .kappa_t import (check_table_tangents, material_cv_table, material_table, picard_sweeps, refuse_tables, table_param,
                       table_tangents)
 from .mesh import Mesh, load_mesh_arrays
-from .monitors import (check_sigma, parse_monitors, problem_monitors, refuse_monitors, uncertainty as monitor_uncertainty,
+from .monitors import (check_sigma, parse_monitors, problem_monitors, refuse_monitors_sweeps, uncertainty as monitor_uncertainty,
                        used_config as monitors_used_config, write_monitors_csv, write_uncertainty_csv)
-from .source import (SOURCE_PARAMS, amplitudes as source_amplitudes, check_source_param, parse_source, refuse_source, source_block,
-                     tangent_coefficients)
+from .source import (SOURCE_PARAMS, amplitudes as source_amplitudes, check_source_param, parse_source, refuse_source,
+                     refuse_source_sweeps, source_block, tangent_coefficients)
 from .solver import DEFAULT_MAX_IT, DEFAULT_RTOL, HeatProblem
 
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -416,14 +416,38 @@ class SimulationSession:
         sweep that share geometry, time stepping and rho_c; they may differ in the boundary values (fwhm,
         heating curve: one shared operator) and in the conductivities (one operator per column, shared
         frozen multigrid hierarchy).  ``read_flux`` adds run_no_diamond's per-step gradient projection for every
-        column (hf_batch_run_flux).  Returns one result dict per configuration, as :meth:`run` does."""
+        column (hf_batch_run_flux).  Returns one result dict per configuration, as :meth:`run` does.
+        Under ``heating.source.sweeps: true`` the configurations may carry a ``heating.source`` block: they must
+        agree on its ``material`` list, ``face`` and ``keep_line`` and may differ in ``power``, the beam's ``fwhm``, ``depth`` and
+        ``pulse``; the batch gets a source of its own (hf_batch_set_source) with one amplitude column per configuration.  Under
+        ``timing.sweep_monitors: true`` they may carry a ``monitors`` block, the same in all of them; every result then has
+        ``monitors`` as :meth:`run` returns it.  A mismatch is a ValueError naming what differs."""
         nv = len(cfgs)
         for c in cfgs:
             refuse_tables(c, "run_batch (the batched loop)")
-            refuse_source(c, "run_batch (the batched loop)")
-            refuse_monitors(c, "run_batch (the batched loop)")
+            refuse_source_sweeps(c, "run_batch (the batched loop)")
+            refuse_monitors_sweeps(c, "run_batch (the batched loop)")
         if nv not in (2, 4, 8, 16):
             raise ValueError("run_batch: 2, 4, 8 or 16 configurations at a time")
+        specs = [parse_source(c) for c in cfgs]
+        if any(sp is not None for sp in specs):
+            if any(sp is None for sp in specs):
+                raise ValueError("run_batch: some configurations have a heating.source block and some have none")
+            for what, get in (("material", lambda sp: sp.materials), ("face", lambda sp: sp.face),
+                              ("keep_line", lambda sp: sp.keep_line)):
+                for j, sp in enumerate(specs):
+                    if get(sp) != get(specs[0]):
+                        raise ValueError(f"run_batch: the configurations must share heating.source.{what} "
+                                         f"(configuration 0 has {get(specs[0])!r}, configuration {j} has {get(sp)!r})")
+            z0s = [sp.z0(st) for sp, st in zip(specs, stacks)]
+            if any(z != z0s[0] for z in z0s):
+                raise ValueError(f"run_batch: the configurations must share the absorbing face's z (heating.source: z0 = {z0s!r})")
+        mon_specs = [parse_monitors(c) for c in cfgs]
+        for j, m in enumerate(mon_specs):
+            if m != mon_specs[0]:
+                raise ValueError(f"run_batch: the configurations must share the monitors block (configuration {j} differs from "
+                                 "configuration 0)")
+        mon = self._monitors(cfgs[0])
         t_start = time.time()
         cfg0 = cfgs[0]
         num_steps = int(cfg0["timing"]["num_steps"])
@@ -446,7 +470,16 @@ class SimulationSession:
         # the operators an affine family A + (kappa_j - kappa_ref) A1: two shared matrices instead of nv
         varying = [t for t in mid[1] if any(c[1][t] != mid[1][t] for c in cols)]
         affine = percol and len(varying) == 1
-        self._ensure_problem(mid[3], mid[1], mid[2], dt, mid[0], ic_temp, scheme, None, self._aniso(stacks[nv // 2]))
+        # the batch's problem carries the monitors' table and no source of its own (the batch gets one: hf_batch_begin refuses the
+        # context's); a resident problem that differs by its source alone (a single run before, or prepare) gives the source up
+        an_mid = self._aniso(stacks[nv // 2])
+        key = self._problem_key(dt, mid[2], mid[0], scheme, None, an_mid, None, mon)
+        if specs[0] is not None and self.problem is not None and self.problem.source and \
+                self._key == self._problem_key(dt, mid[2], mid[0], scheme, None, an_mid, self.problem.source, mon):
+            self.problem.backend.set_source(None)
+            self.problem.source = None
+            self._key, self._source_F1, self._source_G = key, None, None
+        self._ensure_problem(key, mid[1], mid[2], dt, mid[0], ic_temp, scheme, None, an_mid, None, mon)
         prob = self.problem
         be = prob.backend
         if percol and self.precond == 1:             # all columns share the hierarchy: keep every column within its range
@@ -461,7 +494,10 @@ class SimulationSession:
         tabulated = {}                                   # columns with the same boundary definition share one table
         for j, (bcs, _, _, _) in enumerate(cols):
             h = cfgs[j]["heating"]
-            sig = (str(h["file"]), float(h["ic_temp"]), float(h["fwhm"]), len(bcs))
+            if len(bcs) > 3:
+                sig = (str(h["file"]), float(h["ic_temp"]), float(h["fwhm"]), len(bcs))
+            else:                                        # keep_line: false - the three outer edges only, no heating file
+                sig = (None, float(h["ic_temp"]), None, len(bcs))
             if sig not in tabulated:
                 prob.bcs = bcs
                 for bc in bcs:
@@ -488,6 +524,17 @@ class SimulationSession:
                     be.batch_load_column(j)
             for j in range(nv):
                 be.batch_set_state(j, np.full(prob.n, ic_temp))
+            if specs[0] is not None:     # the batch's own source; W -> W/m^3 per step and column, from each column's own integral
+                be.batch_set_source([int(self.material_tags[m]) for m in specs[0].materials], [sp.fwhm for sp in specs], z0s[0],
+                                    [sp.depth for sp in specs])
+                amp, vectors = np.empty((num_steps, nv), dtype=np.float64), {}
+                for j, sp in enumerate(specs):
+                    if (sp.fwhm, sp.depth) not in vectors:       # columns with the same (fwhm, depth) download once
+                        vectors[(sp.fwhm, sp.depth)] = be.batch_get_source(j)
+                    amp[:, j] = source_amplitudes(sp, times, vectors[(sp.fwhm, sp.depth)], _resolve)
+                be.batch_set_source_amplitudes(amp)
+            if mon:
+                be.batch_set_monitors(True)
             print("Beginning loop...")
             t_loop = time.time()
             if flux0 is None:
@@ -496,6 +543,7 @@ class SimulationSession:
                 samples, iters, grad = be.batch_run(g_all, self.rtol, 0.0, self.max_it, nodes, flux_nodes=flux0.nodes,
                                                     flux_components=2, flux_rtol=self.rtol, flux_max_it=5000)
             loop_time = time.time() - t_loop
+            records = be.batch_get_monitors() if mon else None      # [step, column, tag, field]
         finally:
             be.batch_end()
         fluxes = [None] * nv
@@ -509,7 +557,8 @@ class SimulationSession:
         return [{"times": times.copy(), "watcher_names": names,
                  "watchers": {nm: samples[:, j, k].copy() for k, nm in enumerate(names)},
                  "iters": iters[:, j].copy(), "loop_time": loop_time / nv, "startup_time": (t_loop - t_start) / nv,
-                 "n_dof": prob.n, "dt": dt, "flux": fluxes[j], "batch": nv} for j in range(nv)]
+                 "n_dof": prob.n, "dt": dt, "flux": fluxes[j], "batch": nv,
+                 **({"monitors": prob._combine_monitors(records[:, j])} if mon else {})} for j in range(nv)]
 
     def run(self, cfg, stack, watcher_points=None, field_sink=None, read_flux=False, two_sided=False, tangents=None,
             monitor_tangents=False, monitor_sigma=None):
@@ -942,6 +991,8 @@ def run_simulation_batch_impl(kind, cfgs, output_folders, watcher_points_list, s
                 write_watcher_csv(os.path.join(folder, "watcher_points.csv"), res["times"], res["watcher_names"], res["watchers"])
             if res.get("flux") is not None:
                 res["flux"].write(folder)
+            if res.get("monitors") is not None:
+                write_monitors_csv(os.path.join(folder, "monitors.csv"), res["times"], res["monitors"])
             res["save_folder"] = folder
             res["total_time"] = (time.time() - t0) / len(cfgs)
         return results

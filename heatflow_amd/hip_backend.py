@@ -34,6 +34,8 @@ EXPORTS = [
     "hf_pattern_export", "hf_amg_export_size", "hf_amg_export", "hf_amg_install", "hf_set_materials",
     "hf_update_kappa", "hf_set_dirichlet", "hf_assemble", "hf_set_time_scheme", "hf_set_precond", "hf_set_start_vector", "hf_get_response_solves", "hf_get_amg_info", "hf_get_amg_fallbacks", "hf_set_state", "hf_get_state", "hf_sample", "hf_step", "hf_run",
     "hf_batch_begin", "hf_batch_load_column", "hf_batch_set_affine", "hf_batch_set_state", "hf_batch_get_state", "hf_batch_run", "hf_batch_run_flux", "hf_batch_end",
+    "hf_batch_set_source", "hf_batch_get_source", "hf_batch_set_source_amplitudes",
+    "hf_batch_set_monitors", "hf_batch_monitor_now", "hf_batch_monitor_count", "hf_batch_get_monitors",
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
     "hf_set_source", "hf_get_source", "hf_set_source_amplitudes",
@@ -131,6 +133,13 @@ def load_library():
         "hf_batch_run": [vp, i32, pd, dbl, dbl, i32, i32, pi, pd, pi],
         "hf_batch_run_flux": [vp, i32, pd, dbl, dbl, i32, i32, pi, pd, pi, i32, dbl, i32, i32, pi, pd, pi],
         "hf_batch_end": [vp],
+        "hf_batch_set_source": [vp, i32, pi, dbl, pd, pd],
+        "hf_batch_get_source": [vp, i32, pd],
+        "hf_batch_set_source_amplitudes": [vp, i32, pd],
+        "hf_batch_set_monitors": [vp, i32],
+        "hf_batch_monitor_now": [vp, pd],
+        "hf_batch_monitor_count": [vp, pi],
+        "hf_batch_get_monitors": [vp, i32, i32, pd],
         "hf_flux_setup": [vp],
         "hf_flux_project": [vp, dbl, i32, pd, pd, pi],
         "hf_flux_solve": [vp, i32, dbl, i32, pi],
@@ -690,6 +699,68 @@ class HeatflowHIP:
     def batch_end(self):
         self._check(self._lib.hf_batch_end(self._ctx))
         self.batch_nv = 0
+
+    # -- a source and monitor records of the open batch -----------------------------------------------------
+    def _batch_columns(self, name, v):
+        """``v`` as nv values: a scalar for every column, or one per column."""
+        a = _f64(v).ravel()
+        nv = self.batch_nv or len(a)            # no batch open on this side: the library reports it
+        if a.size == 1:
+            a = np.full(nv, a[0], dtype=np.float64)
+        if a.shape != (nv,):
+            raise ValueError(f"batch_set_source: {name} must be a scalar or {nv} values")
+        return np.ascontiguousarray(a)
+
+    def batch_set_source(self, tags, fwhm=1.0, z0=0.0, depth=float("inf")):
+        """The open batch's own source: column j gets the load of set_source(tags, fwhm[j], z0, depth[j]) (``fwhm`` and ``depth``: a
+        scalar or one value per column).  An empty ``tags`` (or None) removes it.  It dies with batch_end."""
+        t = _i32([] if tags is None else tags).ravel()
+        if len(t) == 0:
+            self._check(self._lib.hf_batch_set_source(self._ctx, 0, None, 0.0, None, None))
+            return
+        f, d = self._batch_columns("fwhm", fwhm), self._batch_columns("depth", depth)
+        self._check(self._lib.hf_batch_set_source(self._ctx, len(t), _pi(t), float(z0), _pd(f), _pd(d)))
+
+    def batch_get_source(self, j):
+        """Column j of the batch's source: F1_j at unit amplitude (n values)."""
+        F = np.empty(self.n, dtype=np.float64)
+        self._check(self._lib.hf_batch_get_source(self._ctx, int(j), _pd(F)))
+        return F
+
+    def batch_set_source_amplitudes(self, p):
+        """p[n_steps, nv]: the amplitudes of the next steps of batch_run, one column per sweep point.  An empty table (or None)
+        means amplitude 0 for every step."""
+        p = _f64([] if p is None else p)
+        if p.size == 0:
+            self._check(self._lib.hf_batch_set_source_amplitudes(self._ctx, 0, None))
+            return
+        if p.ndim != 2 or (self.batch_nv and p.shape[1] != self.batch_nv):
+            raise ValueError(f"batch_set_source_amplitudes: p must be (n_steps, {self.batch_nv or 'nv'})")
+        self._check(self._lib.hf_batch_set_source_amplitudes(self._ctx, p.shape[0], _pd(p)))
+
+    def batch_set_monitors(self, on=True):
+        """Switch the open batch's monitor records on (one per step of batch_run from now on, under the table of set_monitors,
+        which is set before batch_begin) or off (the batch's records are dropped)."""
+        self._check(self._lib.hf_batch_set_monitors(self._ctx, 1 if on else 0))
+
+    def batch_monitor_now(self):
+        """The record of the batch's current state, [nv, tab_len, 7] (fields: MONITOR_FIELDS); nothing is recorded."""
+        out = np.empty((max(self.batch_nv, 1), self.tab_len, 7), dtype=np.float64)
+        self._check(self._lib.hf_batch_monitor_now(self._ctx, _pd(out)))
+        return out
+
+    def batch_monitor_count(self):
+        c = C.c_int32()
+        self._check(self._lib.hf_batch_monitor_count(self._ctx, C.byref(c)))
+        return int(c.value)
+
+    def batch_get_monitors(self, first=0, count=None):
+        """Records ``first`` .. ``first + count - 1`` of the open batch (default: all from ``first``) as [records, nv, tab_len, 7]."""
+        first = int(first)
+        count = self.batch_monitor_count() - first if count is None else int(count)
+        out = np.empty((max(count, 0), max(self.batch_nv, 1), self.tab_len, 7), dtype=np.float64)
+        self._check(self._lib.hf_batch_get_monitors(self._ctx, first, count, _pd(out)))
+        return out
 
     # -- read-flux projection (run_no_diamond) ----------------------------------------------
     def flux_setup(self):

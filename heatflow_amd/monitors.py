@@ -46,6 +46,21 @@ def refuse_monitors(cfg, where):
         raise ValueError(f"{where} does not support region monitors ({KEY})")
 
 
+def sweep_monitors(cfg):
+    """``timing.sweep_monitors``: True opts in to the sweeps and run_batch with a ``monitors`` block (the block's own
+    keys are region names, so the switch lives in ``timing``).  ValueError naming the key unless it is a bool."""
+    v = (cfg.get("timing") or {}).get("sweep_monitors", False)
+    if not isinstance(v, bool):
+        raise ValueError(f"timing.sweep_monitors must be true or false, got {v!r}")
+    return v
+
+
+def refuse_monitors_sweeps(cfg, where):
+    """:func:`refuse_monitors` unless ``timing.sweep_monitors`` opts in."""
+    if not sweep_monitors(cfg):
+        refuse_monitors(cfg, where)
+
+
 def _above(region, value):
     if value is None:
         return None

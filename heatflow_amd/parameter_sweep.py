@@ -37,8 +37,8 @@ from .driver import (SimulationSession, build_pattern_blob, flush_mesh_writes, p
 from .geometry import build_stack, watcher_points as _watcher_points
 from .hip_backend import HipError, NotConverged
 from .kappa_t import refuse_tables
-from .source import refuse_source
-from .monitors import refuse_monitors
+from .source import refuse_source_sweeps
+from .monitors import refuse_monitors_sweeps
 
 
 def batch_failure(e, n_points):
@@ -382,8 +382,8 @@ def run_parameter_sweep(base_config_path, output_dir, fwhm_range, k_range, width
         base_config.setdefault("timing", {})["scheme"] = scheme
     time_scheme(base_config)          # an unknown scheme raises before any work
     refuse_tables(base_config, "run_parameter_sweep")
-    refuse_source(base_config, "run_parameter_sweep")
-    refuse_monitors(base_config, "run_parameter_sweep")
+    refuse_source_sweeps(base_config, "run_parameter_sweep")
+    refuse_monitors_sweeps(base_config, "run_parameter_sweep")
     combos, fwhm_vals, k_vals, width_vals = create_parameter_grid(fwhm_range, k_range, width_range, num_points)
     if device_id is None:
         device_id = local_device()
@@ -518,8 +518,8 @@ def run_kappa_sweep(cfg, mesh_folder, k_values, output_dir, *, rebuild_mesh=Fals
     rank, world = world_info()
     time_scheme(cfg)                  # an unknown scheme raises before any work
     refuse_tables(cfg, "run_kappa_sweep")
-    refuse_source(cfg, "run_kappa_sweep")
-    refuse_monitors(cfg, "run_kappa_sweep")
+    refuse_source_sweeps(cfg, "run_kappa_sweep")
+    refuse_monitors_sweeps(cfg, "run_kappa_sweep")
     if device_id is None:
         device_id = local_device()
     stack = build_stack(cfg)

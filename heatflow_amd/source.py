@@ -10,6 +10,7 @@
         pulse: {t0: 1.0e-6, fwhm: 5.0e-7}     # Gaussian in time, peak 1; or {file: x.csv}
         keep_line: false           # true keeps the heated Dirichlet line as well
         tangents: true             # opt in to tangent runs, fits and monitor error bars under the source
+        sweeps: true               # opt in to the sweeps and run_batch under the source
 
 The source is q(z, r, t) = p(t) s(z, r) with s = exp(-4 ln2 r^2 / fwhm^2) exp(-|z - z0| / depth) inside the listed materials
 (hf_set_source forms its load F1 on the GPU).  The absorbed power is P(t) = power * pulse(t); the amplitude handed to the time
@@ -29,7 +30,7 @@ from dataclasses import dataclass
 import numpy as np
 
 KEY = "heating.source"
-SOURCE_KEYS = ("material", "power", "fwhm", "depth", "face", "pulse", "keep_line", "tangents")
+SOURCE_KEYS = ("material", "power", "fwhm", "depth", "face", "pulse", "keep_line", "tangents", "sweeps")
 # the source's own parameters in tangents=, monitor_sigma=, fits and --nuisance (under ``tangents: true``)
 SOURCE_PARAMS = ("source.power", "source.fwhm", "source.depth", "source.pulse.t0", "source.pulse.fwhm")
 PULSE_KEYS = ("t0", "fwhm", "file")
@@ -48,6 +49,7 @@ class SourceSpec:
     pulse: tuple            # ("gaussian", t0, fwhm) or ("file", path)
     keep_line: bool
     tangents: bool = False  # tangent runs, fits and monitor error bars are allowed under this source
+    sweeps: bool = False    # run_parameter_sweep, run_kappa_sweep and run_batch are allowed under this source
 
     def z0(self, stack):
         """z of the absorbing face: the z face of the first material away from the sample mid-plane z = 0 (outer) or towards it
@@ -71,6 +73,8 @@ class SourceSpec:
         out["pulse"] = {"t0": self.pulse[1], "fwhm": self.pulse[2]} if self.pulse[0] == "gaussian" else {"file": self.pulse[1]}
         if self.tangents:
             out["tangents"] = True
+        if self.sweeps:
+            out["sweeps"] = True
         return out
 
 
@@ -95,6 +99,19 @@ def source_permits_tangents(cfg):
 def refuse_source_tangents(cfg, where):
     """:func:`refuse_source` unless the source opts in to tangents."""
     if not source_permits_tangents(cfg):
+        refuse_source(cfg, where)
+
+
+def source_permits_sweeps(cfg):
+    """True when ``cfg`` has a source that opts in to the sweeps (``heating.source.sweeps: true``); a configuration without a
+    source needs no permission and gives False."""
+    block = source_block(cfg)
+    return isinstance(block, dict) and block.get("sweeps") is True
+
+
+def refuse_source_sweeps(cfg, where):
+    """:func:`refuse_source` unless the source opts in to the sweeps."""
+    if not source_permits_sweeps(cfg):
         refuse_source(cfg, where)
 
 
@@ -172,7 +189,10 @@ def parse_source(cfg):
     tangents = block.get("tangents", False)
     if not isinstance(tangents, bool):
         raise ValueError(f"{KEY}.tangents must be true or false, got {tangents!r}")
-    return SourceSpec(tuple(mats), power, fwhm, depth, face, spec, keep, tangents)
+    sweeps = block.get("sweeps", False)
+    if not isinstance(sweeps, bool):
+        raise ValueError(f"{KEY}.sweeps must be true or false, got {sweeps!r}")
+    return SourceSpec(tuple(mats), power, fwhm, depth, face, spec, keep, tangents, sweeps)
 
 
 def read_pulse_csv(path):

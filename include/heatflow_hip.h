@@ -282,6 +282,35 @@ int hf_batch_run_flux(hf_ctx* ctx, int32_t n_steps, const double* g_bc_all, doub
                       int32_t* flux_iters);
 int hf_batch_end(hf_ctx* ctx);
 
+/* A source and monitor records for the open batch.  Both are opt-in and die with hf_batch_end (and with
+ * whatever closes the batch); a batch without them launches, allocates and returns exactly what it did before.  The context's
+ * own source stays refused by hf_batch_begin, and hf_set_source stays refused while a batch is open.
+ * hf_batch_set_source   column j gets the load F1_j of hf_set_source(tags, fwhm[j], z0, depth[j]) - k_source_load itself, one
+ *        launch per distinct (fwhm, depth) - stored interleaved (n x nv) next to the ascending list of rows with an absorbing
+ *        triangle.  Per column the argument checks of hf_set_source (HF_ERR_ARG); n_tags = 0 removes the batch's source.
+ *        HF_ERR_STATE: no batch open, a mesh without row-gather lists.  A new source starts with an empty amplitude table.
+ * hf_batch_get_source   column j of it (n doubles): bit for bit hf_get_source after hf_set_source with that column's arguments.
+ * hf_batch_set_source_amplitudes   p = n_steps x nv ([step][column]): step k after the call uses row k.  All finite (HF_ERR_ARG);
+ *        n_steps = 0: amplitude 0 for every step.  hf_batch_run / hf_batch_run_flux of more steps than rows are left return
+ *        HF_ERR_STATE and take no step.
+ * Per step kb_source_load<nv> writes load = p_j F1_j on the absorbing rows and the right-hand side is b = M u + dt load (BDF2: its
+ * counterpart), under every operator kind and preconditioner.  A hold load F0 stays refused (hf_batch_begin: a load is set).
+ * hf_batch_set_monitors   on = 1: every step of hf_batch_run / hf_batch_run_flux from now on leaves one record of all columns,
+ *        under the table of hf_set_monitors (set before hf_batch_begin, shared by the columns).  on = 0 drops the batch's records.
+ *        HF_ERR_STATE: no batch open; on = 1 while no monitors are set.  The context's own records are never touched.
+ * hf_batch_monitor_now    one record of the batch's current state, out[(j * rows + t) * 7 + f] (rows, f as hf_get_monitors);
+ *        nothing is recorded.
+ * hf_batch_monitor_count  the records kept since the switch.
+ * hf_batch_get_monitors   records first .. first + count - 1: out[(((k - first) * nv + j) * rows + t) * 7 + f].
+ * Column j's rows are bit for bit those k_monitor gives for column j's state (kb_monitor<nv>, kb_monitor_final): no atomics. */
+int hf_batch_set_source(hf_ctx* ctx, int32_t n_tags, const int32_t* tags, double z0, const double* fwhm /* nv */, const double* depth /* nv */);
+int hf_batch_get_source(hf_ctx* ctx, int32_t j, double* F);
+int hf_batch_set_source_amplitudes(hf_ctx* ctx, int32_t n_steps, const double* p /* n_steps x nv */);
+int hf_batch_set_monitors(hf_ctx* ctx, int32_t on);
+int hf_batch_monitor_now(hf_ctx* ctx, double* out);
+int hf_batch_monitor_count(hf_ctx* ctx, int32_t* n_records);
+int hf_batch_get_monitors(hf_ctx* ctx, int32_t first, int32_t count, double* out);
+
 /* Read-flux projection of run_no_diamond (reference run_no_diamond.py:471-491 set-up, :543-550 per
  * step): grad_smooth = L2 projection of grad(T) onto vector P1 with weight r.  hf_flux_setup
  * assembles the unit-coefficient r-weighted mass matrix on the mesh's pattern (once per mesh);
