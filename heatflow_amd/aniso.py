@@ -5,8 +5,10 @@ k_z = m_z k along the cell axis.  Either key may be absent and is then 1; both m
 absolute values, so that everything that scales a material's ``k`` (kappa sweeps, ``--k-range``, the affine batch) keeps its
 meaning: both directions scale and the ratio stays.
 
-Not combined with the temperature-dependent keys (k_table, k_power, cv_table, cv_einstein) in one configuration - the table
-kernels are isotropic - nor with the 1-D model.  Tangents and fits name the directional conductivities of a material as
+Combined with the temperature-dependent keys (k_table, k_power, cv_table, cv_einstein) in one configuration only under
+``timing.aniso_tables: true`` (k_r = m_r kappa(T_e), k_z = m_z kappa(T_e), forward runs and the Picard steady
+state; tangents, fits, sweeps and batches of such a configuration stay refused) - without the key the combination is refused,
+the table kernels are isotropic - and never with the 1-D model.  Tangents and fits name the directional conductivities of a material as
 ``<material>.k_r`` and ``<material>.k_z`` (absolute, W/m/K) and its scalar as ``<material>.k`` (both directions, the ratio kept;
 DESIGN.md 3.13); the bare name of an anisotropic material stays refused there.
 """
@@ -17,6 +19,29 @@ import math
 from .kappa_t import CV_TABLE_KEYS, TABLE_KEYS, table_keys
 
 KEY = "k_aniso"
+SWITCH = "timing.aniso_tables"
+
+
+def aniso_tables(cfg):
+    """``timing.aniso_tables``: True opts in to ``k_aniso`` next to the kappa(T) / cv(T) keys (default off).
+    ValueError naming the key for anything but true or false."""
+    v = (cfg.get("timing") or {}).get("aniso_tables", False)
+    if not isinstance(v, bool):
+        raise ValueError(f"{SWITCH} must be true or false, got {v!r}")
+    return v
+
+
+def refuse_aniso_tables(cfg, where):
+    """ValueError naming ``timing.aniso_tables`` and the keys if ``cfg`` sets the switch and carries both an anisotropic
+    conductivity and a kappa(T) or cv(T) key: the switch covers forward runs and the Picard steady state, ``where`` is not among
+    them.  Without the switch nothing is raised here: the caller's refusals of before follow, with the messages they had."""
+    if not aniso_tables(cfg):
+        return
+    keys, tables = aniso_keys(cfg), table_keys(cfg, TABLE_KEYS + CV_TABLE_KEYS)
+    if keys and tables:
+        raise ValueError(f"{where}: {SWITCH} covers forward runs and the steady state only; anisotropic conductivities "
+                         f"({', '.join(keys)}) together with temperature-dependent coefficients ({', '.join(tables)}) are not "
+                         f"supported here")
 
 
 def material_aniso(name, mat):
@@ -74,13 +99,14 @@ def aniso_keys(cfg, names=None):
 
 def check_config(cfg):
     """Every ``k_aniso`` block of ``cfg`` parsed (ValueError for a bad one), and ValueError naming the keys if the configuration
-    also carries a kappa(T) or cv(T) key.  Returns {material name: (m_r, m_z)}."""
+    also carries a kappa(T) or cv(T) key without ``timing.aniso_tables: true``.  Returns {material name: (m_r, m_z)}."""
+    both = aniso_tables(cfg)
     out = {}
     for name, mat in sorted((cfg.get("mats") or {}).items()):
         m = material_aniso(name, mat)
         if m is not None:
             out[name] = m
-    if out:
+    if out and not both:
         tables = table_keys(cfg, TABLE_KEYS + CV_TABLE_KEYS)
         if tables:
             raise ValueError(f"anisotropic conductivities ({', '.join(aniso_keys(cfg))}) are not supported together with "

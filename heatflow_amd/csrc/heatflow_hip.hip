@@ -147,6 +147,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   tangent_free(ctx);
   kt_free(ctx);
   an_free(ctx);
+  ctx->an_tables = false;
   value_lists_free(ctx);
   ctx->n = n; ctx->ne = ne; ctx->nnz = static_cast<int64_t>(T.colidx.size());
   ctx->nchunks = (n + RB - 1) / RB;
@@ -689,6 +690,8 @@ int tangent_load(hf_ctx* ctx) {
 // hf_table_derivatives (the texts of before), and with it a source and a mesh whose k_tangent_load_T footprint exceeds the LDS
 int tangent_tables_ok(hf_ctx* ctx, const char* fn, int n_par) {
   if (!ctx->kt.on) return HF_OK;
+  if (ctx->an.on)   // (only under hf_set_aniso_tables: k_tangent_load_T and k_tangent_load_dir know nothing of each other)
+    return fail(ctx, HF_ERR_STATE, "%s: %s tables are set on anisotropic conductivities (hf_set_aniso_tables; tangents of that combination are not supported)", fn, kt_kind(ctx));
   if (!ctx->kt.deriv) return fail(ctx, HF_ERR_STATE, "%s: %s tables are set (tangents of the nonlinear loop are not supported)", fn, kt_kind(ctx));
   if (ctx->src.on)
     return fail(ctx, HF_ERR_STATE, "%s: a source is set and table derivatives are on (hf_set_source, hf_table_derivatives; tangents of sourced runs under tables are not supported)", fn);
@@ -879,8 +882,10 @@ int hf_set_anisotropy(hf_ctx* ctx, int32_t n, const int32_t* tags, const double*
     aniso[tg] = 1; any = true;
     by_tag[2 * tg] = m_z[i]; by_tag[2 * tg + 1] = m_r[i];
   }
-  if (any && ctx->kt.on)
+  if (any && ctx->kt.on && !ctx->an_tables)
     return fail(ctx, HF_ERR_STATE, "hf_set_anisotropy: %s tables are set (the table kernels are isotropic)", kt_kind(ctx));
+  if (any && ctx->kt.on && ctx->kt.deriv)
+    return fail(ctx, HF_ERR_STATE, "hf_set_anisotropy: table derivatives are on (hf_table_derivatives; tangents under tables on anisotropic tags are not supported)");
   if (any && (!ctx->rg_ok || (ctx->assembled && ctx->mode != HF_ASM_ROW_GATHER)))
     return fail(ctx, HF_ERR_ARG, "hf_set_anisotropy: anisotropic conductivities are assembled by the row-gather kernel only (HF_ASM_ROW_GATHER on a mesh with row-gather lists)");
   for (int tg = 0; tg < ctx->tab_len; ++tg) {
@@ -910,6 +915,16 @@ int hf_set_anisotropy(hf_ctx* ctx, int32_t n, const int32_t* tags, const double*
   const bool from_steady = ctx->tan.steady_state;
   tangent_free(ctx);
   ctx->tan.steady_state = from_steady;
+  return HF_OK;
+}
+
+int hf_set_aniso_tables(hf_ctx* ctx, int32_t on) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_set_aniso_tables before hf_set_mesh");
+  if (on == 0 && ctx->kt.on && ctx->an.on)
+    return fail(ctx, HF_ERR_STATE, "hf_set_aniso_tables: %s tables (hf_set_kappa_tables / hf_set_rhoc_tables) and anisotropic conductivities (hf_set_anisotropy) are both set: clear one of them first",
+                kt_kind(ctx));
+  ctx->an_tables = on != 0;   // a permission only: the operators that stand were formed by the kernels their state asked for
   return HF_OK;
 }
 
@@ -1075,7 +1090,8 @@ int kt_set_tables(hf_ctx* ctx, bool cap, int32_t n_tab, const int32_t* tags, con
     return HF_OK;
   }
   if (!tags || !t0 || !dT || !n_knots || !values) return fail(ctx, HF_ERR_ARG, "%s: null pointer", fn);
-  if (ctx->an.on) return fail(ctx, HF_ERR_STATE, "%s: anisotropic conductivities are set (hf_set_anisotropy; the table kernels are isotropic)", fn);
+  if (ctx->an.on && !ctx->an_tables)
+    return fail(ctx, HF_ERR_STATE, "%s: anisotropic conductivities are set (hf_set_anisotropy; the table kernels are isotropic)", fn);
   if (!ctx->rg_ok || (ctx->assembled && ctx->mode != HF_ASM_ROW_GATHER))
     return fail(ctx, HF_ERR_ARG, "%s: %s is evaluated by the row-gather kernel only (HF_ASM_ROW_GATHER on a mesh with row-gather lists)", fn, what);
   if (cap && ct_smem_bytes(ctx->max_blk_nnz, ctx->rg_max_dict) + 2 * 64 * sizeof(KTab) > 160 * 1024)
@@ -1678,6 +1694,8 @@ int hf_table_derivatives(hf_ctx* ctx, int32_t enable) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_table_derivatives: no tables are set (hf_set_kappa_tables / hf_set_rhoc_tables first)");
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_table_derivatives: a batch is open");
+  if (ctx->an.on && enable != 0)
+    return fail(ctx, HF_ERR_STATE, "hf_table_derivatives: anisotropic conductivities are set (hf_set_anisotropy; tangents under tables on anisotropic tags are not supported)");
   const bool on = enable != 0;
   if (on == ctx->kt.deriv) return HF_OK;
   HF_HIP(hipSetDevice(ctx->dev));
@@ -1690,6 +1708,8 @@ int hf_table_derivatives(hf_ctx* ctx, int32_t enable) {
 
 int hf_tangent_set_tables(hf_ctx* ctx, int32_t kind, int32_t n_entries, const int32_t* column, const int32_t* tag, const double* values) {
   if (!ctx) return HF_ERR_ARG;
+  if (ctx->an.on && ctx->kt.on)   // (only under hf_set_aniso_tables; no set-up can stand then, so this names the reason rather than the order)
+    return fail(ctx, HF_ERR_STATE, "hf_tangent_set_tables: anisotropic conductivities are set (hf_set_anisotropy; tangents under tables on anisotropic tags are not supported)");
   if (!ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_tables before hf_tangent_setup / hf_tangent_setup_dir");
   if (!ctx->kt.on || !ctx->kt.deriv) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_tables: table derivatives are off (hf_table_derivatives first)");
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_set_tables: a batch is open");
@@ -1926,7 +1946,7 @@ int hf_steady_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t preco
 int hf_steady_picard_setup(hf_ctx* ctx, int32_t n_s, const int32_t* dofs, int32_t precond) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->have_mesh || !ctx->have_mat) return fail(ctx, HF_ERR_STATE, "hf_steady_picard_setup needs hf_set_mesh and hf_set_materials first");
-  if (ctx->an.on)
+  if (ctx->an.on && !ctx->an_tables)
     return fail(ctx, HF_ERR_STATE, "hf_steady_picard_setup: anisotropic conductivities are set (hf_set_anisotropy; the table kernels are isotropic)");
   return steady_setup_impl(ctx, "hf_steady_picard_setup", true, n_s, dofs, precond);
 }

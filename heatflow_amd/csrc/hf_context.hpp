@@ -106,8 +106,8 @@ struct KTab { double t0, inv_dt; int n, off; };
 struct TanDir { int32_t c_r, c_z; double w_r, w_z; };
 
 // The row-gather assembly kernels: k_assemble_rows<false / true>, k_assemble_rows_an<false / true>, k_assemble_rows_kT,
-// k_assemble_rows_cT, k_assemble_rows_kT_K
-enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_SOURCE, RG_SOURCE_D, RG_SHAPE1, RG_SHAPE2, RG_SHAPE4, RG_TLT2, RG_TLT4, RG_TLT8, RG_TLT16, RG_VARIANTS };
+// k_assemble_rows_cT, k_assemble_rows_kT_K and the three table kernels on anisotropic tags (k_assemble_rows_kT_an, _cT_an, _kT_K_an)
+enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_SOURCE, RG_SOURCE_D, RG_SHAPE1, RG_SHAPE2, RG_SHAPE4, RG_TLT2, RG_TLT4, RG_TLT8, RG_TLT16, RG_KT_AN, RG_CT_AN, RG_KT_K_AN, RG_VARIANTS };
 
 }  // namespace
 
@@ -192,6 +192,7 @@ struct hf_ctx {
     std::vector<double> h_m;    // (m_z, m_r) by cell tag, 1 where isotropic: the weights of a kappa column (hf_tangent_setup_dir)
     uint64_t hash = 0;          // of the multipliers by cell tag (0 while off): part of the operator's fingerprint (OperatorPrint)
   } an;
+  bool an_tables = false;      // hf_set_aniso_tables: tables and anisotropic tags together (the _an table kernels); hf_set_mesh resets it
   // device: the mass matrix (the operators that are solved with live in a System, below)
   double* d_M = nullptr;
   // device: vectors

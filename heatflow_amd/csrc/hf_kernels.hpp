@@ -217,7 +217,8 @@ __global__ __launch_bounds__(RBA) void k_assemble_lds(int n, int cap, const int3
 
 // ------------------------------------------------------------------------------------------
 // Assembly, row gather (HF_ASM_ROW_GATHER): the element routines, then one body (rowgather_assemble) behind the five kernels
-// k_assemble_rows, k_assemble_rows_an, k_assemble_rows_kT, k_assemble_rows_cT and k_assemble_rows_kT_K.
+// k_assemble_rows, k_assemble_rows_an, k_assemble_rows_kT, k_assemble_rows_cT and k_assemble_rows_kT_K, and the table kernels'
+// three siblings on anisotropic tags (k_assemble_rows_kT_an, k_assemble_rows_cT_an, k_assemble_rows_kT_K_an).
 // Every triangle is evaluated once per vertex ("me", next, previous in the triangle's own cyclic
 // order).  The formulas are symmetric by construction, so the three evaluations agree bit for bit
 // where they must (A_ij == A_ji) without agreeing on a vertex order:
@@ -1383,6 +1384,119 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_kT_K(int nblk, int cap /*
   __shared__ KTab sK[64];
   if (threadIdx.x < 64) sK[threadIdx.x] = ktab[threadIdx.x];
   rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict, RowsKappaTK{sK, kvals, kappa_idx, u}, nullptr, Kv, smem);
+}
+
+// The three table kernels on anisotropic tags (hf_set_aniso_tables): each policy finds kappa (and rho_c) exactly as its sibling
+// above does - the same T_e, the same table evaluation - and then chooses the element routine exactly as RowsAniso::row does,
+// with an_idx[tg] = (m_z, m_r): k_z = m_z kappa(T_e), k_r = m_r kappa(T_e), rho_c untouched.  So with every multiplier 1 they
+// give their siblings' bits, with constant tables those of k_assemble_rows_an, and in a mixed mesh a row that touches only tags
+// with m_z == m_r keeps the bits of the isotropic table kernel.  Policies of their own, not a parameter of the ones above, so
+// the siblings keep their machine code; flags, LDS carve-up and footprint are the siblings'.  Launched only while a tag is
+// anisotropic and tables are set (kt_revalue, steady_revalue).
+__device__ __forceinline__ ElemRow element_row_m(const double2 Pi, const double2 Pj, const double2 Pk, double rho_c, double kappa, const double2 m) {
+  return m.x == m.y ? element_row(Pi, Pj, Pk, rho_c, kappa * m.x) : element_row_an(Pi, Pj, Pk, rho_c, m.x * kappa, m.y * kappa);
+}
+
+struct RowsKappaTAn {
+  static constexpr bool PAIR = false, STATE = true, KONLY = false, NODE_FIRST = true;
+  static constexpr RgVariant ID = RG_KT_AN;
+  const KTab* sK;
+  const double *kvals, *kappa_idx, *rhoc_idx;
+  const double2* an_idx;
+  double dt;
+  EvalState state;
+  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double* sU, double ui, int cj,
+                                         int ck) const {
+    const KTab kh = sK[tg];
+    double kappa = kappa_idx[tg];
+    if (kh.n > 0) kappa = ktab_eval(kh, kvals, element_temperature(sU, ui, cj, ck));
+    return element_row_m(Pi, Pj, Pk, rhoc_idx[tg], kappa, an_idx[tg]);
+  }
+};
+
+__global__ __launch_bounds__(RBA) void k_assemble_rows_kT_an(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
+                                                             const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
+                                                             const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
+                                                             const double2* __restrict__ zrb, const int32_t* __restrict__ dict,
+                                                             const KTab* __restrict__ ktab, const double* __restrict__ kvals,
+                                                             const double* __restrict__ kappa_idx, const double* __restrict__ rhoc_idx,
+                                                             const double2* __restrict__ an_idx /* (m_z, m_r) */,
+                                                             double dt, const double* __restrict__ u, const double* __restrict__ uprev,
+                                                             double* __restrict__ Av) {
+  extern __shared__ double smem[];
+  __shared__ KTab sK[64];
+  if (threadIdx.x < 64) sK[threadIdx.x] = ktab[threadIdx.x];
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict,
+                     RowsKappaTAn{sK, kvals, kappa_idx, rhoc_idx, an_idx, dt, {u, uprev}}, nullptr, Av, smem);
+}
+
+struct RowsBothTAn {
+  static constexpr bool PAIR = true, STATE = true, KONLY = false, NODE_FIRST = true;
+  static constexpr RgVariant ID = RG_CT_AN;
+  const KTab *sK, *sCt;
+  const double *kvals, *cvals, *kappa_idx, *rhoc_idx;
+  const double2* an_idx;
+  double dt;
+  EvalState state;
+  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double* sU, double ui, int cj,
+                                         int ck) const {
+    const KTab kh = sK[tg], ch = sCt[tg];
+    double kappa = kappa_idx[tg], rho_c = rhoc_idx[tg];
+    if (kh.n > 0 || ch.n > 0) {
+      const double Te = element_temperature(sU, ui, cj, ck);
+      if (kh.n > 0) kappa = ktab_eval(kh, kvals, Te);
+      if (ch.n > 0) rho_c = ktab_eval(ch, cvals, Te);
+    }
+    return element_row_m(Pi, Pj, Pk, rho_c, kappa, an_idx[tg]);
+  }
+};
+
+__global__ __launch_bounds__(RBA) void k_assemble_rows_cT_an(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
+                                                             const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
+                                                             const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
+                                                             const double2* __restrict__ zrb, const int32_t* __restrict__ dict,
+                                                             const KTab* __restrict__ ktab, const double* __restrict__ kvals,
+                                                             const KTab* __restrict__ ctab, const double* __restrict__ cvals,
+                                                             const double* __restrict__ kappa_idx, const double* __restrict__ rhoc_idx,
+                                                             const double2* __restrict__ an_idx /* (m_z, m_r) */,
+                                                             double dt, const double* __restrict__ u, const double* __restrict__ uprev,
+                                                             double* __restrict__ Mv, double* __restrict__ Av) {
+  extern __shared__ double smem[];
+  __shared__ KTab sK[64], sCt[64];
+  if (threadIdx.x < 64) { sK[threadIdx.x] = ktab[threadIdx.x]; sCt[threadIdx.x] = ctab[threadIdx.x]; }
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict,
+                     RowsBothTAn{sK, sCt, kvals, cvals, kappa_idx, rhoc_idx, an_idx, dt, {u, uprev}}, Mv, Av, smem);
+}
+
+struct RowsKappaTKAn {
+  static constexpr bool PAIR = false, STATE = true, KONLY = true, NODE_FIRST = false;
+  static constexpr RgVariant ID = RG_KT_K_AN;
+  const KTab* sK;
+  const double *kvals, *kappa_idx;
+  const double2* an_idx;
+  const double* u;
+  __device__ __forceinline__ double state(int node) const { return u[node]; }
+  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double* sU, double ui, int cj,
+                                         int ck) const {
+    const KTab kh = sK[tg];
+    double kappa = kappa_idx[tg];
+    if (kh.n > 0) kappa = ktab_eval(kh, kvals, element_temperature(sU, ui, cj, ck));
+    return element_row_m(Pi, Pj, Pk, 0.0, kappa, an_idx[tg]);
+  }
+};
+
+__global__ __launch_bounds__(RBA) void k_assemble_rows_kT_K_an(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
+                                                               const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
+                                                               const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
+                                                               const double2* __restrict__ zrb, const int32_t* __restrict__ dict,
+                                                               const KTab* __restrict__ ktab, const double* __restrict__ kvals,
+                                                               const double* __restrict__ kappa_idx,
+                                                               const double2* __restrict__ an_idx /* (m_z, m_r) */,
+                                                               const double* __restrict__ u, double* __restrict__ Kv) {
+  extern __shared__ double smem[];
+  __shared__ KTab sK[64];
+  if (threadIdx.x < 64) sK[threadIdx.x] = ktab[threadIdx.x];
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict, RowsKappaTKAn{sK, kvals, kappa_idx, an_idx, u}, nullptr, Kv, smem);
 }
 
 // w = u^n, or BDF2's operand (4 u^n - u^{n-1}) / 3: the vector the re-valued M multiplies in Picard sweeps 2..p of a step with

@@ -809,6 +809,15 @@ int eliminate(hf_ctx* ctx, System& S) {
 int kt_revalue(hf_ctx* ctx, const double* u, const double* uprev) {
   value_lists_touch(ctx, ctx->sys.A);   // (no lists are built while tables are set; whatever an earlier hf_assemble left is stale now)
   if (ctx->kt.c_on) value_lists_touch(ctx, ctx->d_M);
+  if (ctx->an.on) {   // tables on anisotropic tags (hf_set_aniso_tables): the siblings that take the multipliers
+    if (ctx->kt.c_on)
+      HF_TRY(launch_rowgather<RowsBothTAn>(ctx, &k_assemble_rows_cT_an, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals, ctx->kt.chdr,
+                                           ctx->kt.cvals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->an.d_m, ctx->dt, u, uprev, ctx->d_M, ctx->sys.A));
+    else
+      HF_TRY(launch_rowgather<RowsKappaTAn>(ctx, &k_assemble_rows_kT_an, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals,
+                                            ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->an.d_m, ctx->dt, u, uprev, ctx->sys.A));
+    return eliminate(ctx, ctx->sys);
+  }
   if (ctx->kt.c_on)   // capacity tables: M and A in one pass (k_assemble_rows_cT), then the same three kernels
     HF_TRY(launch_rowgather<RowsBothT>(ctx, &k_assemble_rows_cT, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals, ctx->kt.chdr,
                                        ctx->kt.cvals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev, ctx->d_M, ctx->sys.A));
@@ -819,8 +828,14 @@ int kt_revalue(hf_ctx* ctx, const double* u, const double* uprev) {
 }
 
 // Picard steady state: Kout = K(kappa(T_e)) at the state u by the stiffness-only row-gather kernel (k_assemble_rows_kT_K, the
-// LDS footprint of k_assemble_rows_kT).  `hdr`: the conductivity table headers, or 64 empty ones while none are set.
+// LDS footprint of k_assemble_rows_kT; k_assemble_rows_kT_K_an while a tag is anisotropic).  `hdr`: the conductivity table
+// headers, or 64 empty ones while none are set.
 int steady_revalue(hf_ctx* ctx, const KTab* hdr, const double* u, double* Kout) {
+  if (ctx->an.on) {
+    const auto info = []() -> const char* { return std::getenv("HEATFLOW_DEBUG") ? "[steady picard] k_assemble_rows_kT_K_an" : nullptr; };
+    return launch_rowgather<RowsKappaTKAn>(ctx, &k_assemble_rows_kT_K_an, info, ctx->d_rg_dict, hdr, ctx->kt.vals, ctx->d_kappa_rg,
+                                           ctx->an.d_m, u, Kout);
+  }
   const auto info = []() -> const char* { return std::getenv("HEATFLOW_DEBUG") ? "[steady picard] k_assemble_rows_kT_K" : nullptr; };
   return launch_rowgather<RowsKappaTK>(ctx, &k_assemble_rows_kT_K, info, ctx->d_rg_dict, hdr, ctx->kt.vals, ctx->d_kappa_rg, u, Kout);
 }

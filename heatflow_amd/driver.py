@@ -42,7 +42,8 @@ def _dump_yaml(obj, f):
 from .bc import P1Space, RowDirichletBC
 from .geometry import check_thickness_name, stack_no_diamond, stack_with_diamond, thickness_velocity
 from .heating import HeatingCurve
-from .aniso import CAPACITY_KINDS, DIRECTIONAL_HINT, capacity_scale, check_capacity_names, check_config, refuse_aniso, split_param
+from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, aniso_tables, capacity_scale, check_capacity_names, check_config, refuse_aniso,
+                    refuse_aniso_tables, split_param)
 from .kappa_t import (check_table_tangents, material_cv_table, material_table, picard_sweeps, refuse_tables, table_param,
                       table_tangents)
 from .mesh import Mesh, load_mesh_arrays
@@ -177,7 +178,8 @@ def _with_scheme(cfg):
     """``cfg`` with the time scheme it runs with written out (``timing.scheme``), for used_config.yaml; with kappa(T) also
     ``timing.picard_sweeps`` and the tables that ran (``kappa_tables``: {material: {T0, dT, k}}); with cv(T) the same under
     ``rhoc_tables``: {material: {T0, dT, rho_cv}}, written only when a capacity table is set.  An anisotropic conductivity
-    travels with its material (``mats.<name>.k_aniso``), so it is written exactly when it is set.  A volumetric
+    travels with its material (``mats.<name>.k_aniso``), so it is written exactly when it is set, and ``timing.aniso_tables``
+    with the timing block, so only when the configuration sets it.  A volumetric
     source (``heating.source``, heatflow_amd.source) is written exactly when it is set too, with its defaults filled in, and so
     is a ``monitors`` block (heatflow_amd.monitors)."""
     out = dict(cfg)
@@ -269,8 +271,9 @@ class SimulationSession:
         an = self._aniso(stack)
         src = self._source(cfg, stack)
         mon = self._monitors(cfg)
-        self._ensure_problem(self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an, src, mon), tag_to_k, tag_to_rc, dt, bcs,
-                             float(cfg["heating"]["ic_temp"]), scheme, kt, an, src, mon)
+        ant = aniso_tables(cfg)
+        self._ensure_problem(self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an, src, mon, ant), tag_to_k, tag_to_rc, dt, bcs,
+                             float(cfg["heating"]["ic_temp"]), scheme, kt, an, src, mon, ant)
 
     def _tables(self, stack):
         tag_to_k = {self.material_tags[m.name]: m.properties["k"] for m in stack.materials}
@@ -337,7 +340,7 @@ class SimulationSession:
             self._heats.append(heat_o)
         return bcs
 
-    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler", kt=None, an=None, src=None, mon=None):
+    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler", kt=None, an=None, src=None, mon=None, ant=False):
         # the resident problem is reusable only for exactly the same Dirichlet DOF sets, in the same order, and time scheme
         # (and kappa(T) tables and Picard sweeps, or anisotropy multipliers, when a configuration has them)
         key = (dt, tuple(sorted(tag_to_rc.items())),
@@ -353,10 +356,12 @@ class SimulationSession:
             key += (("source", tuple(src["tags"]), src["fwhm"], src["z0"], src["depth"]),)
         if mon:
             key += (("monitors",) + tuple((region, tuple(r["tags"]), r["above"]) for region, r in mon.items()),)
+        if ant:                  # timing.aniso_tables: the context's switch is set when the problem is made
+            key += (("aniso_tables",),)
         return key
 
     def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme="backward_euler", kt=None, an=None, src=None,
-                        mon=None):
+                        mon=None, ant=False):
         """The resident HeatProblem for ``key`` (built if absent), its operator valued for ``tag_to_k``."""
         if self.problem is None or key != self._key:
             self.close()
@@ -369,7 +374,7 @@ class SimulationSession:
                                        scheme=scheme, **({"kappa_tables": kt[0], "picard": kt[1]} if kt else {}),
                                        **({"rhoc_tables": kt[2]} if kt and kt[2] else {}),
                                        **({"k_aniso": an} if an else {}), **({"source": src} if src else {}),
-                                       **({"monitors": mon} if mon else {}))
+                                       **({"monitors": mon} if mon else {}), **({"aniso_tables": True} if ant else {}))
             self._key = key
             self._source_F1 = None
             self._source_G = None
@@ -620,6 +625,8 @@ class SimulationSession:
         tag_to_k, tag_to_rc = self._tables(stack)
         scheme = time_scheme(cfg)
         kt = self._kappa_tables(cfg, stack)
+        if tangents:             # both kinds: timing.aniso_tables covers the forward run only, with timing.table_tangents too
+            refuse_aniso_tables(cfg, "monitor_sigma" if monitor_sigma is not None else "tangents")
         tab_on = kt is not None and bool(tangents) and table_tangents(cfg)   # timing.table_tangents
         if kt is not None and tangents and not tab_on:
             refuse_tables(cfg, "tangents")
@@ -643,9 +650,10 @@ class SimulationSession:
                          DIRECTIONAL_HINT)
         src = self._source(cfg, stack)
         mon = self._monitors(cfg)
-        key = self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an, src, mon)
+        ant = aniso_tables(cfg)
+        key = self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an, src, mon, ant)
         fresh = self.problem is None or key != self._key
-        self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme, kt, an, src, mon)
+        self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme, kt, an, src, mon, ant)
         if not fresh:
             self.problem.set_state(ic_temp)
             self.problem.iters = []

@@ -134,7 +134,8 @@ def stack_no_diamond(cfg) -> Stack:
 
 def build_stack(cfg) -> Stack:
     """Pick the stack by the presence of ``p_diam`` (as parameter_sweep.py:92).  A configuration that combines ``k_aniso`` with
-    a kappa(T) / cv(T) key is refused here (ValueError naming the keys), before any mesh or GPU work."""
+    a kappa(T) / cv(T) key without ``timing.aniso_tables: true`` is refused here (ValueError naming the keys), before any mesh or
+    GPU work."""
     check_config(cfg)
     return stack_with_diamond(cfg) if "p_diam" in cfg["mats"] else stack_no_diamond(cfg)
 

@@ -42,7 +42,7 @@ EXPORTS = [
     "hf_source_derivatives", "hf_get_source_derivative", "hf_tangent_set_source",
     "hf_set_monitors", "hf_monitor_now", "hf_monitor_count", "hf_get_monitors", "hf_monitor_clear",
     "hf_set_monitor_tangents", "hf_monitor_tangent_count", "hf_get_monitor_tangents", "hf_monitor_tangent_eval",
-    "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_set_shape", "hf_tangent_set_capacity", "hf_table_derivatives", "hf_tangent_set_tables", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_get_sizes", "hf_get_csr", "hf_spmv",
+    "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_set_shape", "hf_tangent_set_capacity", "hf_table_derivatives", "hf_tangent_set_tables", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_set_aniso_tables", "hf_get_sizes", "hf_get_csr", "hf_spmv",
     "hf_set_value_lists", "hf_get_value_lists", "hf_get_projection", "hf_get_flux_system",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
@@ -180,6 +180,7 @@ def load_library():
         "hf_set_rhoc_tables": [vp, i32, pi, pd, pd, pi, pd],
         "hf_set_picard": [vp, i32],
         "hf_set_anisotropy": [vp, i32, pi, pd, pd],
+        "hf_set_aniso_tables": [vp, i32],
         "hf_get_sizes": [vp, pi, pi, C.POINTER(i64), pi],
         "hf_get_csr": [vp, pi, pi, pd, pd],
         "hf_spmv": [vp, i32, pd, pd],
@@ -606,6 +607,12 @@ class HeatflowHIP:
         nk = _i32([len(v) for v in vals])
         allv = _f64(np.concatenate(vals))
         self._check(self._lib.hf_set_rhoc_tables(self._ctx, len(tags), _pi(tags), _pd(t0), _pd(dT), _pi(nk), _pd(allv)))
+
+    # -- tables on anisotropic tags (hf_set_aniso_tables) -------------------------------
+    def set_aniso_tables(self, on):
+        """Allow (``on`` true) or refuse again kappa(T) / rho_c(T) tables together with anisotropic tags.  Off by default and
+        after every set_mesh; switching off while both are set is refused."""
+        self._check(self._lib.hf_set_aniso_tables(self._ctx, 1 if on else 0))
 
     # -- anisotropic conductivities (hf_set_anisotropy, DESIGN.md 3.12) ---------------------------------
     def set_anisotropy(self, multipliers):

@@ -57,7 +57,12 @@ class HeatProblem:
     picard : Picard sweeps per step with tables (1..8; 1 = the lagged scheme)
     k_aniso : {cell tag: (m_r, m_z)} - anisotropic conductivities (hf_set_anisotropy): the tag conducts with
               k_r = m_r k along r and k_z = m_z k along z.  Set right after the materials, before the first assembly.  Not
-              together with kappa_tables / rhoc_tables (ValueError).  None / {}: isotropic, the call sequence of before.
+              together with kappa_tables / rhoc_tables (ValueError) unless ``aniso_tables``.  None / {}: isotropic, the call
+              sequence of before.
+    aniso_tables : True allows k_aniso together with kappa_tables / rhoc_tables (hf_set_aniso_tables): the switch
+              is set right after the materials, before set_anisotropy and the tables; k_r = m_r kappa(T_e), k_z = m_z kappa(T_e).
+              Forward runs and :meth:`solve_steady`; tangent runs of such a problem stay refused by the library.  False (default):
+              the combination is a ValueError and no extra call is made.
     source : dict(tags=, fwhm=, z0=, depth=) - a volumetric source (hf_set_source): power absorbed in the cell
               tags ``tags`` with the shape exp(-4 ln2 r^2 / fwhm^2) exp(-|z - z0| / depth) (``depth`` absent or inf: uniform
               in z).  Set right after the materials; its amplitude per step is :meth:`run`'s ``source_amplitude``.  None: no
@@ -72,7 +77,7 @@ class HeatProblem:
     def __init__(self, coords, tris, tags, tag_to_k, tag_to_rho_cv, dt, bcs, u0, *, backend=None, device_id=0,
                  assembly_mode=ASM_ROW_GATHER, rtol=DEFAULT_RTOL, atol=0.0, max_it=DEFAULT_MAX_IT,
                  precond=PC_JACOBI, amg_reuse=False, pattern=None, amg=None, scheme="backward_euler", kappa_tables=None,
-                 picard=1, rhoc_tables=None, k_aniso=None, source=None, monitors=None):
+                 picard=1, rhoc_tables=None, k_aniso=None, source=None, monitors=None, aniso_tables=False):
         self.coords = np.ascontiguousarray(coords, dtype=np.float64)
         self.n = self.coords.shape[0]
         self.dt = float(dt)
@@ -85,7 +90,8 @@ class HeatProblem:
         self.rhoc_tables = dict(rhoc_tables or {})
         self.picard = int(picard)
         self.k_aniso = check_k_aniso(k_aniso)
-        if self.k_aniso and (self.kappa_tables or self.rhoc_tables):
+        self.aniso_tables = bool(aniso_tables)
+        if self.k_aniso and (self.kappa_tables or self.rhoc_tables) and not self.aniso_tables:
             raise ValueError("HeatProblem: k_aniso together with kappa_tables / rhoc_tables is not supported "
                              "(the table kernels are isotropic)")
         self.source = check_source(source)
@@ -106,6 +112,8 @@ class HeatProblem:
             self.backend.set_mesh(self.coords, tris, tags, pattern=pattern)
         self.mesh_seconds = time.perf_counter() - t0
         self.set_materials(tag_to_k, tag_to_rho_cv, assemble=False)
+        if self.aniso_tables:    # (off is every context's default: no extra call)
+            self.backend.set_aniso_tables(True)
         if self.k_aniso:         # isotropic problems make no extra call
             self.backend.set_anisotropy(self.k_aniso)
         if self.source:          # problems without a source make no extra call

@@ -154,6 +154,24 @@ int hf_update_kappa(hf_ctx* ctx, int32_t n_mat, const int32_t* tags, const doubl
  * tag, anisotropic ones included; the derivative with respect to a multiplier is kappa times the directional one. */
 int hf_set_anisotropy(hf_ctx* ctx, int32_t n, const int32_t* tags, const double* m_z, const double* m_r);
 
+/* Tables on anisotropic tags (opt-in).  Off by default, and hf_set_mesh switches it off: every call, message
+ * and error code is then the one documented above.  on != 0 lifts four of the refusals: hf_set_kappa_tables, hf_set_rhoc_tables
+ * and hf_steady_picard_setup are accepted while a tag is anisotropic, and hf_set_anisotropy while tables are set.  A tag keeps
+ * its multipliers and its scalar conductivity is table(T_e) where it has a table, else its constant:
+ *     k_r = m_r kappa(T_e),  k_z = m_z kappa(T_e)   (the ratio does not depend on the temperature),  rho_c(T_e) as without multipliers,
+ * with T_e the element temperature of hf_set_kappa_tables.  While tables and an anisotropic tag are both set, the re-valuations
+ * run k_assemble_rows_kT_an / k_assemble_rows_cT_an (the time step, hf_assemble) and k_assemble_rows_kT_K_an (the Picard steady
+ * state) in place of their isotropic siblings; otherwise nothing new is launched.  With every multiplier 1 the results are the
+ * isotropic table path's bit for bit, with constant tables those of hf_set_anisotropy alone.  The staleness rules of both calls
+ * stay as they are.
+ * Still refused under the switch (HF_ERR_STATE, the message names the call): hf_table_derivatives(1) and hf_tangent_set_tables
+ * while a tag is anisotropic; hf_set_anisotropy leaving a tag anisotropic while table derivatives are on; hf_tangent_setup,
+ * hf_tangent_setup_dir and hf_run_tangent while tables are set on an anisotropic context (the table loads and the directional
+ * loads know nothing of each other); hf_batch_begin under tables; and (HF_ERR_ARG) every assembly mode but HF_ASM_ROW_GATHER.
+ * Errors: HF_ERR_STATE before hf_set_mesh, and for on == 0 while tables and an anisotropic tag are both set (the message names
+ * both: clear one first). */
+int hf_set_aniso_tables(hf_ctx* ctx, int32_t on);
+
 /* Dirichlet DOFs (unique; the host resolves overlaps "later BC wins" beforehand).
  * The order defines the order of g_bc in hf_step.  n_bc = 0 removes all BCs. */
 int hf_set_dirichlet(hf_ctx* ctx, int32_t n_bc, const int32_t* dofs);
