@@ -106,7 +106,9 @@ struct KTab { double t0, inv_dt; int n, off; };
 struct TanDir { int32_t c_r, c_z; double w_r, w_z; };
 
 // The row-gather assembly kernels: k_assemble_rows<false / true>, k_assemble_rows_an<false / true>, k_assemble_rows_kT,
-// k_assemble_rows_cT, k_assemble_rows_kT_K and the three table kernels on anisotropic tags (k_assemble_rows_kT_an, _cT_an, _kT_K_an)
+// k_assemble_rows_cT, k_assemble_rows_kT_K and the three table kernels on anisotropic tags (k_assemble_rows_kT_an, _cT_an, _kT_K_an).
+// The policies name theirs from their template parameters: RowsConst<K, AN> RG_ROWS / RG_ROWS_K / RG_AN / RG_AN_K, RowsTable<CAP, K, AN>
+// RG_KT / RG_CT / RG_KT_K and the *_AN three.
 enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_SOURCE, RG_SOURCE_D, RG_SHAPE1, RG_SHAPE2, RG_SHAPE4, RG_TLT2, RG_TLT4, RG_TLT8, RG_TLT16, RG_KT_AN, RG_CT_AN, RG_KT_K_AN, RG_VARIANTS };
 
 }  // namespace

@@ -439,17 +439,29 @@ __device__ __forceinline__ void rowgather_assemble(int nblk, int cap /* slab slo
   }
 }
 
-// Constant coefficients by tag-dictionary index.  KONLY (the steady operator, hf_steady_setup): Av receives K, the slab's M
-// half stays zero, Mv is not written (may be null); rhoc_idx and dt are not used.
-template <bool K>
+// (m_z, m_r) of a tag on top of its kappa: k_z = m_z kappa along z, k_r = m_r kappa along r.  m_z == m_r goes through element_row
+// with kappa * m (x * 1.0 is exact: multipliers 1 give the isotropic bits), anything else through element_row_an.
+__device__ __forceinline__ ElemRow element_row_m(const double2 Pi, const double2 Pj, const double2 Pk, double rho_c, double kappa, const double2 m) {
+  return m.x == m.y ? element_row(Pi, Pj, Pk, rho_c, kappa * m.x) : element_row_an(Pi, Pj, Pk, rho_c, m.x * kappa, m.y * kappa);
+}
+
+// Constant coefficients by tag-dictionary index.  K (the steady operator, hf_steady_setup): Av receives K, the slab's M half
+// stays zero, Mv is not written (may be null); rhoc_idx and dt are not used.
+// AN (hf_set_anisotropy, k_assemble_rows_an): a second 64-entry table by tag-dictionary index, an_idx[tg] = (m_z, m_r), through
+// element_row_m.  With every multiplier 1 M and A come out bit for bit as k_assemble_rows gives them, and in a mixed mesh every
+// row that touches only elements of tags with m_z == m_r keeps its bits.  Not AN: an_idx is not used.
+template <bool K, bool AN>
 struct RowsConst {
   static constexpr bool PAIR = true, STATE = false, KONLY = K;
-  static constexpr RgVariant ID = K ? RG_ROWS_K : RG_ROWS;
+  static constexpr RgVariant ID = AN ? (K ? RG_AN_K : RG_AN) : (K ? RG_ROWS_K : RG_ROWS);
   const double *kappa_idx, *rhoc_idx;
+  const double2* an_idx;
   double dt;
   __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double*, double, int, int) const {
-    if (KONLY) return element_row(Pi, Pj, Pk, 0.0, kappa_idx[tg]);
-    return element_row(Pi, Pj, Pk, rhoc_idx[tg], kappa_idx[tg]);
+    const double2 m = AN ? an_idx[tg] : make_double2(1.0, 1.0);   // read first: with kappa_idx first k_assemble_rows_an compiles otherwise
+    const double kappa = kappa_idx[tg], rho_c = K ? 0.0 : rhoc_idx[tg];
+    if constexpr (AN) return element_row_m(Pi, Pj, Pk, rho_c, kappa, m);
+    else return element_row(Pi, Pj, Pk, rho_c, kappa);
   }
 };
 
@@ -462,26 +474,8 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows(int nblk, int cap /* slab
                                                        const double* __restrict__ kappa_idx, const double* __restrict__ rhoc_idx,
                                                        double dt, double* __restrict__ Mv, double* __restrict__ Av) {
   extern __shared__ double smem[];
-  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, nullptr, RowsConst<KONLY>{kappa_idx, rhoc_idx, dt}, Mv, Av, smem);
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, nullptr, RowsConst<KONLY, false>{kappa_idx, rhoc_idx, nullptr, dt}, Mv, Av, smem);
 }
-
-// RowsConst with a second 64-entry table by tag-dictionary index, an_idx[tg] = (m_z, m_r): the conductivity of tag tg is
-// k_z = m_z kappa along z and k_r = m_r kappa along r.  An element whose tag has m_z == m_r goes through element_row with
-// kappa * m, so with every multiplier 1 (x * 1.0 is exact) M and A come out bit for bit as k_assemble_rows gives them, and in a
-// mixed mesh every row that touches only such elements keeps its bits.
-template <bool K>
-struct RowsAniso {
-  static constexpr bool PAIR = true, STATE = false, KONLY = K;
-  static constexpr RgVariant ID = K ? RG_AN_K : RG_AN;
-  const double *kappa_idx, *rhoc_idx;
-  const double2* an_idx;
-  double dt;
-  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double*, double, int, int) const {
-    const double2 m = an_idx[tg];
-    const double kap = kappa_idx[tg], rc = KONLY ? 0.0 : rhoc_idx[tg];
-    return m.x == m.y ? element_row(Pi, Pj, Pk, rc, kap * m.x) : element_row_an(Pi, Pj, Pk, rc, m.x * kap, m.y * kap);
-  }
-};
 
 template <bool KONLY>
 __global__ __launch_bounds__(RBA) void k_assemble_rows_an(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
@@ -493,7 +487,7 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_an(int nblk, int cap /* s
                                                           const double2* __restrict__ an_idx /* (m_z, m_r) */,
                                                           double dt, double* __restrict__ Mv, double* __restrict__ Av) {
   extern __shared__ double smem[];
-  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, nullptr, RowsAniso<KONLY>{kappa_idx, rhoc_idx, an_idx, dt}, Mv, Av, smem);
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, nullptr, RowsConst<KONLY, true>{kappa_idx, rhoc_idx, an_idx, dt}, Mv, Av, smem);
 }
 
 // What a load policy sees of the block's LDS: the column list's coordinates, its own per-node doubles behind them (sN; arrays
@@ -1285,20 +1279,54 @@ __global__ __launch_bounds__(RBA) void k_tangent_load_T(int nblk, int capd, cons
   }
 }
 
-// A = M + dt K(kappa(T)) at u* in a one-value slab: M does not change, only A is written.
-struct RowsKappaT {
-  static constexpr bool PAIR = false, STATE = true, KONLY = false, NODE_FIRST = true;
-  static constexpr RgVariant ID = RG_KT;
-  const KTab* sK;
-  const double *kvals, *kappa_idx, *rhoc_idx;
+// The coefficient policy of the six table kernels, one yes/no choice per axis:
+//   CAP  a capacity table next to the conductivity table (k_assemble_rows_cT, _cT_an; launched only while a capacity table is
+//        set): a second header array sCt for rho_c and the (M, A) slab, M = M(rho_c(T)) and A = M + dt K(kappa(T)) at u*, both
+//        arrays written.  T_e is computed once per element visit - when either coefficient of the tag carries a table - and
+//        used for both.  Not CAP: a one-value slab; M does not change, only A (or K) is written; sCt and cvals are not used.
+//   K    the stiffness alone, K = K(kappa(T)) at the state u (k_assemble_rows_kT_K, _kT_K_an; hf_steady_picard_setup /
+//        hf_steady_picard_solve): no M, no dt, rho_c = 0, the state is u itself (uprev, rhoc_idx and dt are not used).  With no
+//        table (every header n = 0) or constant tables it gives the K of k_assemble_rows<true> bit for bit.  Not with CAP.
+//   AN   the (m_z, m_r) multipliers on anisotropic tags (the three *_an kernels; hf_set_aniso_tables; launched only while a tag
+//        is anisotropic and tables are set - kt_revalue, steady_revalue): kappa (and rho_c) are found exactly as without AN - the
+//        same T_e, the same table evaluation - and the element routine is then chosen as RowsConst<K, true>::row chooses it,
+//        with an_idx[tg] = (m_z, m_r): k_z = m_z kappa(T_e), k_r = m_r kappa(T_e), rho_c untouched.  So with every multiplier 1
+//        an *_an kernel gives its sibling's bits, with constant tables those of k_assemble_rows_an, and in a mixed mesh a row
+//        that touches only tags with m_z == m_r keeps the bits of the isotropic table kernel.  Not AN: an_idx is not used.
+// The flags, hence LDS carve-up and footprint, depend on (CAP, K) alone.  Every instantiation compiles to the machine code its
+// kernel had under a struct of its own (profiles/rows_table_asm_compare.txt).
+template <bool CAP, bool K, bool AN>
+struct RowsTable {
+  static_assert(!(CAP && K), "no stiffness-only kernel with a capacity table");
+  static constexpr bool PAIR = CAP, STATE = true, KONLY = K, NODE_FIRST = !K;
+  static constexpr RgVariant ID = AN ? (CAP ? RG_CT_AN : K ? RG_KT_K_AN : RG_KT_AN) : (CAP ? RG_CT : K ? RG_KT_K : RG_KT);
+  const KTab *sK, *sCt;
+  const double *kvals, *cvals, *kappa_idx, *rhoc_idx;
+  const double2* an_idx;
   double dt;
-  EvalState state;
+  EvalState ustar;
+  __device__ __forceinline__ double state(int node) const {
+    if constexpr (K) return ustar.u[node];
+    else return ustar(node);
+  }
   __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double* sU, double ui, int cj,
                                          int ck) const {
     const KTab kh = sK[tg];
-    double kappa = kappa_idx[tg];
-    if (kh.n > 0) kappa = ktab_eval(kh, kvals, element_temperature(sU, ui, cj, ck));
-    return element_row(Pi, Pj, Pk, rhoc_idx[tg], kappa);
+    double kappa = kappa_idx[tg], rho_c = 0.0;
+    if constexpr (CAP) {
+      const KTab ch = sCt[tg];
+      rho_c = rhoc_idx[tg];
+      if (kh.n > 0 || ch.n > 0) {
+        const double Te = element_temperature(sU, ui, cj, ck);
+        if (kh.n > 0) kappa = ktab_eval(kh, kvals, Te);
+        if (ch.n > 0) rho_c = ktab_eval(ch, cvals, Te);
+      }
+    } else {
+      if (kh.n > 0) kappa = ktab_eval(kh, kvals, element_temperature(sU, ui, cj, ck));
+      if constexpr (!K) rho_c = rhoc_idx[tg];
+    }
+    if constexpr (AN) return element_row_m(Pi, Pj, Pk, rho_c, kappa, an_idx[tg]);
+    else return element_row(Pi, Pj, Pk, rho_c, kappa);
   }
 };
 
@@ -1313,32 +1341,9 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_kT(int nblk, int cap /* s
   extern __shared__ double smem[];
   __shared__ KTab sK[64];
   if (threadIdx.x < 64) sK[threadIdx.x] = ktab[threadIdx.x];
-  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict, RowsKappaT{sK, kvals, kappa_idx, rhoc_idx, dt, {u, uprev}},
-                     nullptr, Av, smem);
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict,
+                     RowsTable<false, false, false>{sK, nullptr, kvals, nullptr, kappa_idx, rhoc_idx, nullptr, dt, {u, uprev}}, nullptr, Av, smem);
 }
-
-// M = M(rho_c(T)) and A = M + dt K(kappa(T)) at u*: a second table header array for rho_c and the (M, A) slab.  T_e is computed
-// once per element visit - when either coefficient of the tag carries a table - and used for both.  Both arrays are written.
-// Launched only while a capacity table is set.
-struct RowsBothT {
-  static constexpr bool PAIR = true, STATE = true, KONLY = false, NODE_FIRST = true;
-  static constexpr RgVariant ID = RG_CT;
-  const KTab *sK, *sCt;
-  const double *kvals, *cvals, *kappa_idx, *rhoc_idx;
-  double dt;
-  EvalState state;
-  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double* sU, double ui, int cj,
-                                         int ck) const {
-    const KTab kh = sK[tg], ch = sCt[tg];
-    double kappa = kappa_idx[tg], rho_c = rhoc_idx[tg];
-    if (kh.n > 0 || ch.n > 0) {
-      const double Te = element_temperature(sU, ui, cj, ck);
-      if (kh.n > 0) kappa = ktab_eval(kh, kvals, Te);
-      if (ch.n > 0) rho_c = ktab_eval(ch, cvals, Te);
-    }
-    return element_row(Pi, Pj, Pk, rho_c, kappa);
-  }
-};
 
 __global__ __launch_bounds__(RBA) void k_assemble_rows_cT(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
                                                           const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
@@ -1353,25 +1358,8 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_cT(int nblk, int cap /* s
   __shared__ KTab sK[64], sCt[64];
   if (threadIdx.x < 64) { sK[threadIdx.x] = ktab[threadIdx.x]; sCt[threadIdx.x] = ctab[threadIdx.x]; }
   rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict,
-                     RowsBothT{sK, sCt, kvals, cvals, kappa_idx, rhoc_idx, dt, {u, uprev}}, Mv, Av, smem);
+                     RowsTable<true, false, false>{sK, sCt, kvals, cvals, kappa_idx, rhoc_idx, nullptr, dt, {u, uprev}}, Mv, Av, smem);
 }
-
-// The stiffness alone, K = K(kappa(T)) at the state u (hf_steady_picard_setup / hf_steady_picard_solve): RowsKappaT without M
-// and dt.  With no table (every header n = 0) or constant tables it gives the K of k_assemble_rows<true> bit for bit.
-struct RowsKappaTK {
-  static constexpr bool PAIR = false, STATE = true, KONLY = true, NODE_FIRST = false;
-  static constexpr RgVariant ID = RG_KT_K;
-  const KTab* sK;
-  const double *kvals, *kappa_idx, *u;
-  __device__ __forceinline__ double state(int node) const { return u[node]; }
-  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double* sU, double ui, int cj,
-                                         int ck) const {
-    const KTab kh = sK[tg];
-    double kappa = kappa_idx[tg];
-    if (kh.n > 0) kappa = ktab_eval(kh, kvals, element_temperature(sU, ui, cj, ck));
-    return element_row(Pi, Pj, Pk, 0.0, kappa);
-  }
-};
 
 __global__ __launch_bounds__(RBA) void k_assemble_rows_kT_K(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
                                                             const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
@@ -1383,36 +1371,9 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_kT_K(int nblk, int cap /*
   extern __shared__ double smem[];
   __shared__ KTab sK[64];
   if (threadIdx.x < 64) sK[threadIdx.x] = ktab[threadIdx.x];
-  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict, RowsKappaTK{sK, kvals, kappa_idx, u}, nullptr, Kv, smem);
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict,
+                     RowsTable<false, true, false>{sK, nullptr, kvals, nullptr, kappa_idx, nullptr, nullptr, 0.0, {u, nullptr}}, nullptr, Kv, smem);
 }
-
-// The three table kernels on anisotropic tags (hf_set_aniso_tables): each policy finds kappa (and rho_c) exactly as its sibling
-// above does - the same T_e, the same table evaluation - and then chooses the element routine exactly as RowsAniso::row does,
-// with an_idx[tg] = (m_z, m_r): k_z = m_z kappa(T_e), k_r = m_r kappa(T_e), rho_c untouched.  So with every multiplier 1 they
-// give their siblings' bits, with constant tables those of k_assemble_rows_an, and in a mixed mesh a row that touches only tags
-// with m_z == m_r keeps the bits of the isotropic table kernel.  Policies of their own, not a parameter of the ones above, so
-// the siblings keep their machine code; flags, LDS carve-up and footprint are the siblings'.  Launched only while a tag is
-// anisotropic and tables are set (kt_revalue, steady_revalue).
-__device__ __forceinline__ ElemRow element_row_m(const double2 Pi, const double2 Pj, const double2 Pk, double rho_c, double kappa, const double2 m) {
-  return m.x == m.y ? element_row(Pi, Pj, Pk, rho_c, kappa * m.x) : element_row_an(Pi, Pj, Pk, rho_c, m.x * kappa, m.y * kappa);
-}
-
-struct RowsKappaTAn {
-  static constexpr bool PAIR = false, STATE = true, KONLY = false, NODE_FIRST = true;
-  static constexpr RgVariant ID = RG_KT_AN;
-  const KTab* sK;
-  const double *kvals, *kappa_idx, *rhoc_idx;
-  const double2* an_idx;
-  double dt;
-  EvalState state;
-  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double* sU, double ui, int cj,
-                                         int ck) const {
-    const KTab kh = sK[tg];
-    double kappa = kappa_idx[tg];
-    if (kh.n > 0) kappa = ktab_eval(kh, kvals, element_temperature(sU, ui, cj, ck));
-    return element_row_m(Pi, Pj, Pk, rhoc_idx[tg], kappa, an_idx[tg]);
-  }
-};
 
 __global__ __launch_bounds__(RBA) void k_assemble_rows_kT_an(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
                                                              const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
@@ -1427,29 +1388,8 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_kT_an(int nblk, int cap /
   __shared__ KTab sK[64];
   if (threadIdx.x < 64) sK[threadIdx.x] = ktab[threadIdx.x];
   rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict,
-                     RowsKappaTAn{sK, kvals, kappa_idx, rhoc_idx, an_idx, dt, {u, uprev}}, nullptr, Av, smem);
+                     RowsTable<false, false, true>{sK, nullptr, kvals, nullptr, kappa_idx, rhoc_idx, an_idx, dt, {u, uprev}}, nullptr, Av, smem);
 }
-
-struct RowsBothTAn {
-  static constexpr bool PAIR = true, STATE = true, KONLY = false, NODE_FIRST = true;
-  static constexpr RgVariant ID = RG_CT_AN;
-  const KTab *sK, *sCt;
-  const double *kvals, *cvals, *kappa_idx, *rhoc_idx;
-  const double2* an_idx;
-  double dt;
-  EvalState state;
-  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double* sU, double ui, int cj,
-                                         int ck) const {
-    const KTab kh = sK[tg], ch = sCt[tg];
-    double kappa = kappa_idx[tg], rho_c = rhoc_idx[tg];
-    if (kh.n > 0 || ch.n > 0) {
-      const double Te = element_temperature(sU, ui, cj, ck);
-      if (kh.n > 0) kappa = ktab_eval(kh, kvals, Te);
-      if (ch.n > 0) rho_c = ktab_eval(ch, cvals, Te);
-    }
-    return element_row_m(Pi, Pj, Pk, rho_c, kappa, an_idx[tg]);
-  }
-};
 
 __global__ __launch_bounds__(RBA) void k_assemble_rows_cT_an(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
                                                              const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
@@ -1465,25 +1405,8 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_cT_an(int nblk, int cap /
   __shared__ KTab sK[64], sCt[64];
   if (threadIdx.x < 64) { sK[threadIdx.x] = ktab[threadIdx.x]; sCt[threadIdx.x] = ctab[threadIdx.x]; }
   rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict,
-                     RowsBothTAn{sK, sCt, kvals, cvals, kappa_idx, rhoc_idx, an_idx, dt, {u, uprev}}, Mv, Av, smem);
+                     RowsTable<true, false, true>{sK, sCt, kvals, cvals, kappa_idx, rhoc_idx, an_idx, dt, {u, uprev}}, Mv, Av, smem);
 }
-
-struct RowsKappaTKAn {
-  static constexpr bool PAIR = false, STATE = true, KONLY = true, NODE_FIRST = false;
-  static constexpr RgVariant ID = RG_KT_K_AN;
-  const KTab* sK;
-  const double *kvals, *kappa_idx;
-  const double2* an_idx;
-  const double* u;
-  __device__ __forceinline__ double state(int node) const { return u[node]; }
-  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double* sU, double ui, int cj,
-                                         int ck) const {
-    const KTab kh = sK[tg];
-    double kappa = kappa_idx[tg];
-    if (kh.n > 0) kappa = ktab_eval(kh, kvals, element_temperature(sU, ui, cj, ck));
-    return element_row_m(Pi, Pj, Pk, 0.0, kappa, an_idx[tg]);
-  }
-};
 
 __global__ __launch_bounds__(RBA) void k_assemble_rows_kT_K_an(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
                                                                const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
@@ -1496,7 +1419,8 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_kT_K_an(int nblk, int cap
   extern __shared__ double smem[];
   __shared__ KTab sK[64];
   if (threadIdx.x < 64) sK[threadIdx.x] = ktab[threadIdx.x];
-  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict, RowsKappaTKAn{sK, kvals, kappa_idx, an_idx, u}, nullptr, Kv, smem);
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict,
+                     RowsTable<false, true, true>{sK, nullptr, kvals, nullptr, kappa_idx, nullptr, an_idx, 0.0, {u, nullptr}}, nullptr, Kv, smem);
 }
 
 // w = u^n, or BDF2's operand (4 u^n - u^{n-1}) / 3: the vector the re-valued M multiplies in Picard sweeps 2..p of a step with

@@ -472,7 +472,7 @@ auto dispatch_ns(int ns, F&& f) {
 // alone into Aout (Mout, rhoc_idx and dt unused).
 template <bool KONLY = false>
 int launch_assemble_rows(hf_ctx* ctx, const double* kappa_idx, const double* rhoc_idx, double dt, double* Mout, double* Aout) {
-  return launch_rowgather<RowsConst<KONLY>>(ctx, &k_assemble_rows<KONLY>, nullptr, kappa_idx, rhoc_idx, dt, Mout, Aout);
+  return launch_rowgather<RowsConst<KONLY, false>>(ctx, &k_assemble_rows<KONLY>, nullptr, kappa_idx, rhoc_idx, dt, Mout, Aout);
 }
 
 // The same with the multipliers of hf_set_anisotropy (k_assemble_rows_an: the LDS footprint of k_assemble_rows, a grid of its own
@@ -483,7 +483,7 @@ int launch_assemble_rows_an(hf_ctx* ctx, const double* kappa_idx, const double* 
     const char* e = std::getenv("HEATFLOW_ANISO_INFO");
     return e && e[0] == '1' ? (KONLY ? "[aniso] k_assemble_rows_an<true>" : "[aniso] k_assemble_rows_an<false>") : nullptr;
   };
-  return launch_rowgather<RowsAniso<KONLY>>(ctx, &k_assemble_rows_an<KONLY>, info, kappa_idx, rhoc_idx, ctx->an.d_m, dt, Mout, Aout);
+  return launch_rowgather<RowsConst<KONLY, true>>(ctx, &k_assemble_rows_an<KONLY>, info, kappa_idx, rhoc_idx, ctx->an.d_m, dt, Mout, Aout);
 }
 
 // Row-gather assembly with whatever hf_set_anisotropy left: the existing kernel while no tag is anisotropic

@@ -809,21 +809,24 @@ int eliminate(hf_ctx* ctx, System& S) {
 int kt_revalue(hf_ctx* ctx, const double* u, const double* uprev) {
   value_lists_touch(ctx, ctx->sys.A);   // (no lists are built while tables are set; whatever an earlier hf_assemble left is stale now)
   if (ctx->kt.c_on) value_lists_touch(ctx, ctx->d_M);
+  int rc;
   if (ctx->an.on) {   // tables on anisotropic tags (hf_set_aniso_tables): the siblings that take the multipliers
     if (ctx->kt.c_on)
-      HF_TRY(launch_rowgather<RowsBothTAn>(ctx, &k_assemble_rows_cT_an, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals, ctx->kt.chdr,
-                                           ctx->kt.cvals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->an.d_m, ctx->dt, u, uprev, ctx->d_M, ctx->sys.A));
+      rc = launch_rowgather<RowsTable<true, false, true>>(ctx, &k_assemble_rows_cT_an, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals,
+                                                          ctx->kt.chdr, ctx->kt.cvals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->an.d_m, ctx->dt, u,
+                                                          uprev, ctx->d_M, ctx->sys.A);
     else
-      HF_TRY(launch_rowgather<RowsKappaTAn>(ctx, &k_assemble_rows_kT_an, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals,
-                                            ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->an.d_m, ctx->dt, u, uprev, ctx->sys.A));
-    return eliminate(ctx, ctx->sys);
+      rc = launch_rowgather<RowsTable<false, false, true>>(ctx, &k_assemble_rows_kT_an, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals,
+                                                           ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->an.d_m, ctx->dt, u, uprev, ctx->sys.A);
+  } else if (ctx->kt.c_on) {   // capacity tables: M and A in one pass (k_assemble_rows_cT), then the same three kernels
+    rc = launch_rowgather<RowsTable<true, false, false>>(ctx, &k_assemble_rows_cT, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals,
+                                                         ctx->kt.chdr, ctx->kt.cvals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev,
+                                                         ctx->d_M, ctx->sys.A);
+  } else {
+    rc = launch_rowgather<RowsTable<false, false, false>>(ctx, &k_assemble_rows_kT, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals,
+                                                          ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev, ctx->sys.A);
   }
-  if (ctx->kt.c_on)   // capacity tables: M and A in one pass (k_assemble_rows_cT), then the same three kernels
-    HF_TRY(launch_rowgather<RowsBothT>(ctx, &k_assemble_rows_cT, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals, ctx->kt.chdr,
-                                       ctx->kt.cvals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev, ctx->d_M, ctx->sys.A));
-  else
-    HF_TRY(launch_rowgather<RowsKappaT>(ctx, &k_assemble_rows_kT, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals,
-                                        ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, uprev, ctx->sys.A));
+  HF_TRY(rc);
   return eliminate(ctx, ctx->sys);
 }
 
@@ -833,11 +836,11 @@ int kt_revalue(hf_ctx* ctx, const double* u, const double* uprev) {
 int steady_revalue(hf_ctx* ctx, const KTab* hdr, const double* u, double* Kout) {
   if (ctx->an.on) {
     const auto info = []() -> const char* { return std::getenv("HEATFLOW_DEBUG") ? "[steady picard] k_assemble_rows_kT_K_an" : nullptr; };
-    return launch_rowgather<RowsKappaTKAn>(ctx, &k_assemble_rows_kT_K_an, info, ctx->d_rg_dict, hdr, ctx->kt.vals, ctx->d_kappa_rg,
+    return launch_rowgather<RowsTable<false, true, true>>(ctx, &k_assemble_rows_kT_K_an, info, ctx->d_rg_dict, hdr, ctx->kt.vals, ctx->d_kappa_rg,
                                            ctx->an.d_m, u, Kout);
   }
   const auto info = []() -> const char* { return std::getenv("HEATFLOW_DEBUG") ? "[steady picard] k_assemble_rows_kT_K" : nullptr; };
-  return launch_rowgather<RowsKappaTK>(ctx, &k_assemble_rows_kT_K, info, ctx->d_rg_dict, hdr, ctx->kt.vals, ctx->d_kappa_rg, u, Kout);
+  return launch_rowgather<RowsTable<false, true, false>>(ctx, &k_assemble_rows_kT_K, info, ctx->d_rg_dict, hdr, ctx->kt.vals, ctx->d_kappa_rg, u, Kout);
 }
 
 // Multigrid PCG on S where it has a hierarchy; on a breakdown inside that loop (p.Ap <= 0: the preconditioner was not SPD for

@@ -1,8 +1,11 @@
 """usage (GPU box): python scripts/rowgather_bits_record.py [OUT.json]
 Records tests/golden/rowgather_bits.json (default OUT), the fixture of tests/test_gpu_rowgather_bits.py: SHA-256 digests of the
-mesh arrays and of what each of the seven row-gather assembly kernels writes on the two small cases, computed by that test's own
-digests().  Run it with the library whose bits are to be pinned (HEATFLOW_HIP_LIB selects one); the committed file comes from
-the library of the commit before the kernels were folded into rowgather_assemble.  Prints the digests it wrote."""
+mesh arrays and of what each of the ten row-gather assembly kernels writes on the two small cases, computed by that test's own
+digests().  Run it with the library whose bits are to be pinned (HEATFLOW_HIP_LIB selects one).  The committed file's entries
+of the first seven kernels come from the library of the commit before the kernels were folded into rowgather_assemble; the
+*_an entries (tables on anisotropic tags) from the library of the commit before the coefficient policies were folded into
+RowsTable, recorded twice in separate processes with the same file both times, and the older entries came out as committed.
+Prints the digests it wrote."""
 import json
 import os
 import sys

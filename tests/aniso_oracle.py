@@ -16,9 +16,8 @@ as tests/test_steady_cpu.py and tests/test_gpu_steady.py restate them.
 import numpy as np
 import scipy.sparse.linalg as spla
 
+from loops_oracle import BDF2, BE, linear_loop
 from oracle import heat_oracle as ho
-
-BE, BDF2 = 0, 1
 
 
 def cell_multipliers(tags, aniso):
@@ -101,22 +100,9 @@ def operator(coords, tris, tags, tag_to_k, tag_to_rc, aniso, dtp):
 
 def aniso_fields(coords, tris, tags, tag_to_k, tag_to_rc, dt, bc_dofs, u0, g_all, aniso, scheme=BE):
     """Every step's field (n_steps x n): the loop of kappa_T_oracle.linear_fields on the anisotropic operator."""
-    bc_dofs = np.asarray(bc_dofs, dtype=np.int64)
     dtp = 2.0 * dt / 3.0 if scheme == BDF2 else float(dt)
     M, A, _ = operator(coords, tris, tags, tag_to_k, tag_to_rc, aniso, dtp)
-    Ahat = ho.eliminate_dirichlet(A, bc_dofs)
-    lift = A[:, bc_dofs].tocsr()
-    lu = spla.splu(Ahat.tocsc())
-    u = np.array(u0, dtype=np.float64)
-    up = u.copy()
-    out = []
-    for g in np.asarray(g_all, dtype=np.float64):
-        b = M @ ((4.0 * u - up) / 3.0) if scheme == BDF2 else M @ u
-        b -= lift @ g
-        b[bc_dofs] = g
-        up, u = u, lu.solve(b)
-        out.append(u.copy())
-    return np.array(out)
+    return linear_loop(M, A, bc_dofs, u0, g_all, scheme)
 
 
 def steady_solve(K, dofs, g, F=None):

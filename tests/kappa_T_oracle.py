@@ -11,11 +11,9 @@ Per step:
 built on oracle.heat_oracle's element matrices, assembly and elimination.
 """
 import numpy as np
-import scipy.sparse.linalg as spla
 
+from loops_oracle import BDF2, BE, linear_loop, table_loop
 from oracle import heat_oracle as ho
-
-BE, BDF2 = 0, 1
 
 
 def table_eval(T, T0, dT, values):
@@ -76,58 +74,18 @@ class KappaTOperator:
 
 def kappa_t_fields(coords, tris, tags, tag_to_k, tag_to_rc, dt, bc_dofs, u0, g_all, tables, scheme=BE, picard=1):
     """Every step's field of the kappa(T) loop (n_steps x n) and the Picard change of every step."""
-    bc_dofs = np.asarray(bc_dofs, dtype=np.int64)
     dtp = 2.0 * dt / 3.0 if scheme == BDF2 else float(dt)
-    op = KappaTOperator(coords, tris, tags, tag_to_k, tag_to_rc, dtp, tables)
-    u = np.array(u0, dtype=np.float64)
-    up = None
-    fields, changes = [], []
-    for g in np.asarray(g_all, dtype=np.float64):
-        if scheme == BDF2:
-            um1 = u if up is None else up
-            b0 = op.M @ ((4.0 * u - um1) / 3.0)
-            x = u.copy() if up is None else 2.0 * u - up
-        else:
-            b0 = op.M @ u
-            x = u.copy()
-        change = 0.0
-        for _ in range(int(picard)):
-            Ahat, lift = op.eliminated(x, bc_dofs)
-            b = b0.copy()
-            if len(bc_dofs):
-                b -= lift @ g
-                b[bc_dofs] = g
-            xn = spla.splu(Ahat.tocsc()).solve(b)
-            change = float(np.abs(xn - x).max())
-            x = xn
-        up, u = u, x
-        fields.append(u.copy())
-        changes.append(change)
-    return np.array(fields), np.array(changes)
+    op = KappaTOperator(coords, tris, tags, tag_to_k, tag_to_rc, dtp, tables)   # M does not change: valued once
+    return table_loop(lambda _, x: (op.M, op.A(x)), dt, bc_dofs, u0, g_all, scheme, picard)
 
 
 def linear_fields(coords, tris, tags, tag_to_k, tag_to_rc, dt, bc_dofs, u0, g_all, scheme=BE):
     """The same loop with constant conductivities, through oracle.heat_oracle's operator (one factorisation)."""
-    bc_dofs = np.asarray(bc_dofs, dtype=np.int64)
     dtp = 2.0 * dt / 3.0 if scheme == BDF2 else float(dt)
     kappa, rc = ho.cell_coefficients(np.asarray(tags), tag_to_k, tag_to_rc)
     Me, Ke = ho.element_matrices(np.asarray(coords, dtype=np.float64), np.asarray(tris, dtype=np.int64), rc, kappa)
     n = len(coords)
-    M = ho.assemble_csr(n, tris, Me)
-    A = ho.assemble_csr(n, tris, Me + dtp * Ke)
-    Ahat = ho.eliminate_dirichlet(A, bc_dofs)
-    lift = A[:, bc_dofs].tocsr()
-    lu = spla.splu(Ahat.tocsc())
-    u = np.array(u0, dtype=np.float64)
-    up = u.copy()
-    out = []
-    for g in np.asarray(g_all, dtype=np.float64):
-        b = M @ ((4.0 * u - up) / 3.0) if scheme == BDF2 else M @ u
-        b -= lift @ g
-        b[bc_dofs] = g
-        up, u = u, lu.solve(b)
-        out.append(u.copy())
-    return np.array(out)
+    return linear_loop(ho.assemble_csr(n, tris, Me), ho.assemble_csr(n, tris, Me + dtp * Ke), bc_dofs, u0, g_all, scheme)
 
 
 def problem_inputs(cfg, stack, mesh, num_steps):

@@ -13,9 +13,9 @@ built on oracle.heat_oracle's element matrices, assembly and elimination and kap
 tables the loop is kappa_T_oracle.linear_fields', with conductivity tables only kappa_T_oracle.kappa_t_fields'.
 """
 import numpy as np
-import scipy.sparse.linalg as spla
 
 from kappa_T_oracle import BDF2, BE, element_kappa
+from loops_oracle import table_loop
 from oracle import heat_oracle as ho
 
 __all__ = ["BE", "BDF2", "einstein", "einstein_tables", "operators", "rhoc_t_fields"]
@@ -47,31 +47,6 @@ def operators(coords, tris, tags, tag_to_k, tag_to_rc, dtp, x, kappa_tables=None
 def rhoc_t_fields(coords, tris, tags, tag_to_k, tag_to_rc, dt, bc_dofs, u0, g_all, rhoc_tables=None, kappa_tables=None,
                   scheme=BE, picard=1):
     """Every step's field of the loop (n_steps x n) and the Picard change of every step."""
-    bc_dofs = np.asarray(bc_dofs, dtype=np.int64)
-    dtp = 2.0 * dt / 3.0 if scheme == BDF2 else float(dt)
-    u = np.array(u0, dtype=np.float64)
-    up = None
-    fields, changes = [], []
-    for g in np.asarray(g_all, dtype=np.float64):
-        if scheme == BDF2:
-            um1 = u if up is None else up
-            w = (4.0 * u - um1) / 3.0
-            x = u.copy() if up is None else 2.0 * u - up
-        else:
-            w = u
-            x = u.copy()
-        change = 0.0
-        for _ in range(int(picard)):
-            M, A = operators(coords, tris, tags, tag_to_k, tag_to_rc, dtp, x, kappa_tables, rhoc_tables)
-            b = M @ w
-            if len(bc_dofs):
-                b -= A[:, bc_dofs].tocsr() @ g
-                b[bc_dofs] = g
-                A = ho.eliminate_dirichlet(A, bc_dofs)
-            xn = spla.splu(A.tocsc()).solve(b)
-            change = float(np.abs(xn - x).max())
-            x = xn
-        up, u = u, x
-        fields.append(u.copy())
-        changes.append(change)
-    return np.array(fields), np.array(changes)
+    def operators_at(dtp, x):
+        return operators(coords, tris, tags, tag_to_k, tag_to_rc, dtp, x, kappa_tables, rhoc_tables)
+    return table_loop(operators_at, dt, bc_dofs, u0, g_all, scheme, picard)
