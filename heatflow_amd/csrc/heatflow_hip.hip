@@ -148,6 +148,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   kt_free(ctx);
   an_free(ctx);
   ctx->an_tables = false;
+  ctx->batch_tables = false;
   value_lists_free(ctx);
   ctx->n = n; ctx->ne = ne; ctx->nnz = static_cast<int64_t>(T.colidx.size());
   ctx->nchunks = (n + RB - 1) / RB;
@@ -1167,6 +1168,8 @@ int hf_set_picard(hf_ctx* ctx, int32_t sweeps) {
   if (!ctx) return HF_ERR_ARG;
   if (sweeps < 1 || sweeps > KT_MAX_PICARD) return fail(ctx, HF_ERR_ARG, "hf_set_picard: sweeps %d outside 1..%d", sweeps, KT_MAX_PICARD);
   if (!ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_set_picard: no tables are set (hf_set_kappa_tables / hf_set_rhoc_tables first)");
+  if (sweeps > 1 && ctx->batch.nv > 0 && ctx->batch.tables)
+    return fail(ctx, HF_ERR_STATE, "hf_set_picard: a batch under tables is open (hf_set_batch_tables; it takes one sweep per step)");
   ctx->kt.picard = sweeps;
   ctx->kt.deriv = false;
   return HF_OK;
@@ -2398,14 +2401,29 @@ int hf_hold_load(hf_ctx* ctx) {
 
 int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
   if (!ctx) return HF_ERR_ARG;
-  if (ctx->kt.on) return fail(ctx, HF_ERR_STATE, "hf_batch_begin: %s tables are set (batched sweeps of the nonlinear loop are not supported)", kt_kind(ctx));
+  const bool tables = ctx->kt.on;
+  if (tables && !ctx->batch_tables)
+    return fail(ctx, HF_ERR_STATE, "hf_batch_begin: %s tables are set (batched sweeps of the nonlinear loop are not supported)", kt_kind(ctx));
+  if (tables) {   // hf_set_batch_tables: what the batch under tables does not cover
+    if (ctx->kt.picard > 1)
+      return fail(ctx, HF_ERR_STATE, "hf_batch_begin: hf_set_picard is at %d sweeps per step (a batch under tables, hf_set_batch_tables, takes one sweep)", ctx->kt.picard);
+    if (ctx->an.on)
+      return fail(ctx, HF_ERR_STATE, "hf_batch_begin: hf_set_anisotropy has left a tag anisotropic (a batch under tables, hf_set_batch_tables, is isotropic)");
+    if (ctx->kt.deriv)
+      return fail(ctx, HF_ERR_STATE, "hf_batch_begin: hf_table_derivatives is on (a batch under tables, hf_set_batch_tables, has no tangents)");
+  }
   if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_batch_begin before hf_assemble");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_batch_begin: a load is set (the batched loop has no load term; hf_set_load(NULL) first)");
   if (ctx->src.on) return fail(ctx, HF_ERR_STATE, "hf_batch_begin: a source is set (the batched loop has no load term; hf_set_source with n_tags = 0 first)");
   if (nv != 2 && nv != 4 && nv != 8 && nv != 16) return fail(ctx, HF_ERR_ARG, "hf_batch_begin: 2, 4, 8 or 16 columns (got %d)", nv);
   if (operator_kind < 0 || operator_kind > 2) return fail(ctx, HF_ERR_ARG, "hf_batch_begin: unknown operator kind %d", operator_kind);
+  if (tables && operator_kind != HF_BATCH_PER_COLUMN)
+    return fail(ctx, HF_ERR_ARG, "hf_batch_begin: operator kind %d (%s) under tables (hf_set_batch_tables): only HF_BATCH_PER_COLUMN is re-valued per column",
+                operator_kind, operator_kind == HF_BATCH_SHARED ? "HF_BATCH_SHARED" : "HF_BATCH_AFFINE");
   if (operator_kind == HF_BATCH_PER_COLUMN && ctx->sys.precond == 1 && !ctx->amg_reuse)
     return fail(ctx, HF_ERR_STATE, "hf_batch_begin: per-column operators need the frozen hierarchy (hf_set_precond(1, reuse = 1))");
+  if (tables && kbt_lds_bytes(ctx->max_blk_nnz, ctx->rg_max_dict, ctx->kt.c_on) + KBT_STATIC_LDS > 160 * 1024)
+    return fail(ctx, HF_ERR_ARG, "hf_batch_begin: the slab of %d columns, the staged states and the table headers of this mesh exceed the 160 KiB of LDS", KBT_G);
   HF_HIP(hipSetDevice(ctx->dev));
   free_batch(ctx);
   hf_ctx::Batch& B = ctx->batch;
@@ -2415,6 +2433,18 @@ int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
   if (B.opk == HF_BATCH_PER_COLUMN) {
     HF_TRY(dev_alloc(ctx, &B.A, static_cast<size_t>(ctx->nnz) * nv));
     HF_TRY(dev_alloc(ctx, &B.lift_val, static_cast<size_t>(std::max(ctx->sys.nlift, 1)) * nv));
+  }
+  if (tables) {
+    // every column starts from the context's constants (hf_batch_set_column_kappa changes a column's); the operators are
+    // valued by the first step, or by hf_batch_revalue
+    if (ctx->kt.c_on) HF_TRY(dev_alloc(ctx, &B.M, static_cast<size_t>(ctx->nnz) * nv));
+    std::vector<double> k64(64);
+    HF_HIP(copy_sync(ctx, k64.data(), ctx->d_kappa_rg, sizeof(double) * 64, hipMemcpyDeviceToHost));
+    B.h_kcol.resize(static_cast<size_t>(64) * nv);
+    for (int q = 0; q < 64; ++q)
+      for (int j = 0; j < nv; ++j) B.h_kcol[static_cast<size_t>(q) * nv + j] = k64[q];
+    HF_TRY(dev_alloc(ctx, &B.kcol, B.h_kcol.size()));
+    HF_HIP(copy_sync(ctx, B.kcol, B.h_kcol.data(), sizeof(double) * B.h_kcol.size(), hipMemcpyHostToDevice));
   }
   if (B.opk == HF_BATCH_AFFINE) {
     HF_TRY(dev_alloc(ctx, &B.A1, static_cast<size_t>(ctx->nnz)));
@@ -2430,7 +2460,78 @@ int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
   B.have_prev = false;
   B.bdf_hist = false;
   B.pred_iters = 0;
-  B.loaded = 0;
+  B.loaded = tables ? (1u << nv) - 1u : 0;   // under tables every step values every column's operator itself
+  B.tables = tables;
+  B.noproj = tables;                         // ... so a ring of old solutions would belong to other operators
+  return HF_OK;
+}
+
+int hf_set_batch_tables(hf_ctx* ctx, int32_t on) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_set_batch_tables before hf_set_mesh");
+  if (on == 0 && ctx->batch.nv > 0 && ctx->batch.tables) {   // the open batch was accepted under the switch
+    (void)hipSetDevice(ctx->dev);
+    (void)hipStreamSynchronize(ctx->stream);
+    free_batch(ctx);
+  }
+  ctx->batch_tables = on != 0;
+  return HF_OK;
+}
+
+int hf_batch_set_column_kappa(hf_ctx* ctx, int32_t j, int32_t n_tags, const int32_t* tags, const double* k) {
+  if (!ctx) return HF_ERR_ARG;
+  hf_ctx::Batch& B = ctx->batch;
+  if (B.nv == 0 || !B.tables) return fail(ctx, HF_ERR_STATE, "hf_batch_set_column_kappa: no batch under tables is open (hf_set_batch_tables, hf_batch_begin)");
+  if (j < 0 || j >= B.nv) return fail(ctx, HF_ERR_ARG, "hf_batch_set_column_kappa: column %d outside [0,%d)", j, B.nv);
+  if (n_tags <= 0 || !tags || !k) return fail(ctx, HF_ERR_ARG, "hf_batch_set_column_kappa: bad arguments");
+  for (int32_t q = 0; q < n_tags; ++q) {
+    if (tags[q] < 0 || tags[q] >= ctx->tab_len || !ctx->h_tag_used[tags[q]])
+      return fail(ctx, HF_ERR_ARG, "hf_batch_set_column_kappa: tag %d is not a cell tag of the mesh", tags[q]);
+    if (ctx->kt.k_on && ctx->kt.tabled[tags[q]])
+      return fail(ctx, HF_ERR_ARG, "hf_batch_set_column_kappa: tag %d carries a kappa(T) table (hf_set_kappa_tables; per-column tables are not supported)", tags[q]);
+    if (!(k[q] > 0.0) || !std::isfinite(k[q])) return fail(ctx, HF_ERR_ARG, "hf_batch_set_column_kappa: the conductivity of tag %d is not positive and finite", tags[q]);
+  }
+  for (int32_t q = 0; q < n_tags; ++q) {
+    const size_t at = std::find(ctx->h_rg_tags.begin(), ctx->h_rg_tags.end(), tags[q]) - ctx->h_rg_tags.begin();
+    if (at >= ctx->h_rg_tags.size() || at >= 64) return fail(ctx, HF_ERR_ARG, "hf_batch_set_column_kappa: tag %d has no row-gather dictionary entry", tags[q]);
+    B.h_kcol[at * B.nv + j] = k[q];
+  }
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_HIP(copy_sync(ctx, B.kcol, B.h_kcol.data(), sizeof(double) * B.h_kcol.size(), hipMemcpyHostToDevice));
+  return HF_OK;
+}
+
+int hf_batch_revalue(hf_ctx* ctx, int32_t max_workgroups) {
+  if (!ctx) return HF_ERR_ARG;
+  hf_ctx::Batch& B = ctx->batch;
+  if (B.nv == 0 || !B.tables) return fail(ctx, HF_ERR_STATE, "hf_batch_revalue: no batch under tables is open (hf_set_batch_tables, hf_batch_begin)");
+  if (max_workgroups < 0) return fail(ctx, HF_ERR_ARG, "hf_batch_revalue: negative workgroup cap %d", max_workgroups);
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_TRY(batch_dispatch(ctx, B, [&](auto ops) { return decltype(ops)::revalue(ctx, B, max_workgroups); }));
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  return HF_OK;
+}
+
+int hf_batch_get_operator(hf_ctx* ctx, int32_t j, double* A, double* dinv, double* lift, double* M) {
+  if (!ctx) return HF_ERR_ARG;
+  hf_ctx::Batch& B = ctx->batch;
+  if (B.nv == 0 || B.opk != HF_BATCH_PER_COLUMN) return fail(ctx, HF_ERR_STATE, "hf_batch_get_operator: no batch with per-column operators is open");
+  if (j < 0 || j >= B.nv) return fail(ctx, HF_ERR_ARG, "hf_batch_get_operator: column %d outside [0,%d)", j, B.nv);
+  if (M && !B.M) return fail(ctx, HF_ERR_STATE, "hf_batch_get_operator: M requested without capacity tables in the batch (M is the context's shared one: hf_get_csr)");
+  HF_HIP(hipSetDevice(ctx->dev));
+  DevTemp<double> t;
+  HF_TRY(dev_alloc(ctx, &t.p, static_cast<size_t>(ctx->nnz)));
+  const auto column = [&](const double* src, size_t len, double* out) -> int {
+    if (!out || len == 0) return HF_OK;
+    hipLaunchKernelGGL(kb_get_column, dim3(1024), dim3(256), 0, ctx->stream, len, B.nv, j, src, t.p);
+    HF_HIP(hipGetLastError());
+    HF_HIP(copy_sync(ctx, out, t.p, sizeof(double) * len, hipMemcpyDeviceToHost));
+    return HF_OK;
+  };
+  HF_TRY(column(B.A, static_cast<size_t>(ctx->nnz), A));
+  HF_TRY(column(B.dinv, static_cast<size_t>(ctx->n), dinv));
+  HF_TRY(column(B.lift_val, static_cast<size_t>(ctx->sys.nlift), lift));
+  HF_TRY(column(B.M, static_cast<size_t>(ctx->nnz), M));
   return HF_OK;
 }
 
@@ -2548,6 +2649,8 @@ int hf_batch_set_source(hf_ctx* ctx, int32_t n_tags, const int32_t* tags, double
   if (!ctx) return HF_ERR_ARG;
   hf_ctx::Batch& B = ctx->batch;
   if (B.nv == 0) return fail(ctx, HF_ERR_STATE, "hf_batch_set_source: no batch is open");
+  if (B.tables && n_tags != 0)
+    return fail(ctx, HF_ERR_STATE, "hf_batch_set_source: the batch runs under tables (hf_set_batch_tables; a source together with tables is not supported in the batch)");
   HF_HIP(hipSetDevice(ctx->dev));
   if (n_tags == 0) { HF_HIP(hipStreamSynchronize(ctx->stream)); free_batch_source(ctx); return HF_OK; }
   if (!ctx->rg_ok) return fail(ctx, HF_ERR_STATE, "hf_batch_set_source: the source's load is formed by the row-gather kernel only (a mesh with row-gather lists)");
@@ -2641,6 +2744,8 @@ int hf_batch_set_source_amplitudes(hf_ctx* ctx, int32_t n_steps, const double* p
 int hf_batch_set_monitors(hf_ctx* ctx, int32_t on) {
   if (!ctx) return HF_ERR_ARG;
   if (ctx->batch.nv == 0) return fail(ctx, HF_ERR_STATE, "hf_batch_set_monitors: no batch is open");
+  if (ctx->batch.tables && on)
+    return fail(ctx, HF_ERR_STATE, "hf_batch_set_monitors: the batch runs under tables (hf_set_batch_tables; monitors together with tables are not supported in the batch)");
   if (on && !ctx->mon.on) return fail(ctx, HF_ERR_STATE, "hf_batch_set_monitors: no monitors set (hf_set_monitors before hf_batch_begin)");
   HF_HIP(hipSetDevice(ctx->dev));
   HF_HIP(hipStreamSynchronize(ctx->stream));

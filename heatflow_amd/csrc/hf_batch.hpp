@@ -823,9 +823,219 @@ __global__ void kb_zero_column(size_t n, int nv, int j, double* __restrict__ dst
 }
 
 // ------------------------------------------------------------------------------------------
+// Batches under kappa(T) / rho_c(T) tables (hf_set_batch_tables): one launch re-values the operators of all NV
+// columns, each at its own column's evaluation state.
+// ------------------------------------------------------------------------------------------
+constexpr int KBT_G = 2;   // columns per walk of the visit loop: the slab of KBT_G columns keeps two workgroups on a CU with (M, A) pairs
+
+// What element_row_of<false> computes before a coefficient enters, statement for statement: the same for every column of a visit
+struct VisitGeom { double area, r3, invd2, g0, g1, g2, f0, f1, f2; };
+__device__ __forceinline__ VisitGeom visit_geom(const double2 Pi, const double2 Pj, const double2 Pk) {
+#pragma clang fp contract(off)
+  const double eix = Pk.x - Pj.x, eiy = Pk.y - Pj.y;
+  const double ejx = Pi.x - Pk.x, ejy = Pi.y - Pk.y;
+  const double ekx = Pj.x - Pi.x, eky = Pj.y - Pi.y;
+  const double c1 = fabs(ejx * eky - ejy * ekx), c2 = fabs(ekx * eiy - eky * eix), c3 = fabs(eix * ejy - eiy * ejx);
+  const double d = fmax(fmax(c1, c2), c3);
+  const double rsum = sorted_sum3(Pi.y, Pj.y, Pk.y);
+  VisitGeom G;
+  G.area = 0.5 * d;
+  G.r3 = rsum * (1.0 / 3.0);
+  G.invd2 = 1.0 / (d * d);
+  G.g0 = eix * eix + eiy * eiy;
+  G.g1 = eix * ejx + eiy * ejy;
+  G.g2 = eix * ekx + eiy * eky;
+  G.f0 = 2.0 * Pi.y + rsum;
+  G.f1 = rsum + (Pi.y + Pj.y);
+  G.f2 = rsum + (Pi.y + Pk.y);
+  return G;
+}
+// ... and what it computes from there: the products in element_row_of<false>'s order, so the bits are element_row's
+__device__ __forceinline__ ElemRow visit_row(const VisitGeom& G, double rho_c, double kappa) {
+#pragma clang fp contract(off)
+  const double ks = kappa * G.area * G.r3 * G.invd2;
+  const double ms30 = rho_c * G.area * (1.0 / 30.0), ms60 = rho_c * G.area * (1.0 / 60.0);
+  ElemRow o;
+  o.k0 = ks * G.g0;
+  o.k1 = ks * G.g1;
+  o.k2 = ks * G.g2;
+  o.m0 = ms30 * G.f0;
+  o.m1 = ms60 * G.f1;
+  o.m2 = ms60 * G.f2;
+  return o;
+}
+
+// The batched sibling of k_assemble_rows_kT (CAP = false) and k_assemble_rows_cT (CAP = true): rowgather_assemble's lists, lane t
+// owns row blk * RBA + t, no atomics, additions in list order.  Per block the 16-bit column positions, the coordinates and the row
+// starts are staged once; then, per group of KBT_G columns, the group's evaluation states (u, or 2 u - uprev; interleaved vectors:
+// the group's states of a list entry are adjacent) are staged, the visit loop is walked into a slab of KBT_G values (or (M, A)
+// pairs) per slot, and the slab is streamed out to Av[k * NV + j] (and Mv).  Column j's conductivity on a tag is its table at T_e(j)
+// or the column's constant kcol[tg * NV + j]; rho_c is its table's value or the shared constant.  The element geometry is computed
+// once per visit and group (visit_geom), the coefficients enter as in element_row (visit_row): per column the bits are those of
+// RowsTable<CAP, false, false>::row in rowgather_assemble.  Workgroups are persistent (blk += gridDim.x); the register prefetch of
+// the next block is not kept: its registers would be live across KBT_G-column walks that already hold 2 KBT_G accumulators.
+template <int NV, bool CAP>
+__global__ __launch_bounds__(RBA) void kb_assemble_rows_T(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
+                                                          const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
+                                                          const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
+                                                          const double2* __restrict__ zrb, const int32_t* __restrict__ dict,
+                                                          const KTab* __restrict__ ktab, const double* __restrict__ kvals,
+                                                          const KTab* __restrict__ ctab, const double* __restrict__ cvals,
+                                                          const double* __restrict__ kcol /* [64][NV] */, const double* __restrict__ rhoc_idx,
+                                                          double dt, const double* __restrict__ u, const double* __restrict__ uprev,
+                                                          double* __restrict__ Mv, double* __restrict__ Av) {
+  constexpr int G = KBT_G;
+  static_assert(NV % G == 0, "column groups");
+  using Slot = std::conditional_t<CAP, double2, double>;
+  extern __shared__ double smem[];
+  __shared__ KTab sK[64];
+  __shared__ KTab sCt[CAP ? 64 : 1];
+  Slot* sS = reinterpret_cast<Slot*>(smem);                          // [cap][G]
+  double2* sXd = reinterpret_cast<double2*>(sS + static_cast<size_t>(cap) * G);   // [capd]
+  double* sU = reinterpret_cast<double*>(sXd + capd);                // [capd][G]
+  int* sR = reinterpret_cast<int*>(sU + static_cast<size_t>(capd) * G);   // row starts inside the slab
+  uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);
+  const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
+  const int t = threadIdx.x;
+  if (t < 64) {
+    sK[t] = ktab[t];
+    if constexpr (CAP) sCt[t] = ctab[t];
+  }
+  for (int k = t; k < cap * G; k += RBA) sS[k] = Slot();
+  for (int blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
+    const int4 cA = hdr[2 * blk];                                    // (k0, nk, d0, nd)
+    const int4 cB = hdr[2 * blk + 1];                                // (ell offset in 16-byte units, groups of 8 visits, local id of row r0, rows)
+    const int c0 = cA.x >> 3, nc = ((cA.x + cA.y + 7) >> 3) - c0;
+    for (int i = t; i < nc; i += RBA) sC4[i] = cid16[c0 + i];
+    for (int i = t; i < cA.w; i += RBA) sXd[i] = zrb[cA.z + i];
+    sR[t] = (t < cB.w) ? rowptr[blk * RBA + t] - cA.x : 0;
+    for (int g0 = 0; g0 < NV; g0 += G) {
+      {
+#pragma clang fp contract(off)
+        for (int i = t; i < cA.w * G; i += RBA) {
+          const size_t o = static_cast<size_t>(dict[cA.z + i / G]) * NV + g0 + i % G;
+          sU[i] = uprev ? 2.0 * u[o] - uprev[o] : u[o];
+        }
+      }
+      __syncthreads();
+      if (t < cB.w) {
+        const int base = sR[t];
+        const int sbase = base + (cA.x & 7);
+        const int ci = cB.z + t;
+        const double2 Pi = sXd[ci];
+        double dM[G], dA[G];
+#pragma unroll
+        for (int g = 0; g < G; ++g) { dM[g] = 0.0; dA[g] = 0.0; }
+        int pd = 0;
+        while (pd < 31 && sC[sbase + pd] < ci) ++pd;
+        for (int gv = 0; gv < cB.y; ++gv) {
+          const uint4 ev = ell[cB.x + gv * RBA + t];
+          const unsigned w[4] = {ev.x, ev.y, ev.z, ev.w};
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            const unsigned e = (w[q >> 1] >> ((q & 1) * 16)) & 0xFFFFu;
+            if (e == 0xFFFFu) continue;
+            const int pj = e & 31u, pk = (e >> 5) & 31u, tg = e >> 10;
+            const int cj = sC[sbase + pj], ck = sC[sbase + pk];
+            const VisitGeom geo = visit_geom(Pi, sXd[cj], sXd[ck]);
+            const KTab kh = sK[tg];
+            const KTab ch = CAP ? sCt[tg] : KTab{0.0, 0.0, 0, 0};
+            const double rc0 = rhoc_idx[tg];
+            const bool tabled = kh.n > 0 || (CAP && ch.n > 0);
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+              double kappa = kcol[tg * NV + g0 + g], rho_c = rc0;
+              if (tabled) {
+#pragma clang fp contract(off)
+                const double Te = sorted_sum3(sU[ci * G + g], sU[cj * G + g], sU[ck * G + g]) * (1.0 / 3.0);
+                if (kh.n > 0) kappa = ktab_eval(kh, kvals, Te);
+                if (CAP && ch.n > 0) rho_c = ktab_eval(ch, cvals, Te);
+              }
+              const ElemRow r = visit_row(geo, rho_c, kappa);
+              if constexpr (CAP) {
+                dM[g] += r.m0;
+                dA[g] += fma(dt, r.k0, r.m0);
+                double2 s = sS[(base + pj) * G + g];
+                s.x += r.m1;
+                s.y += fma(dt, r.k1, r.m1);
+                sS[(base + pj) * G + g] = s;
+                s = sS[(base + pk) * G + g];
+                s.x += r.m2;
+                s.y += fma(dt, r.k2, r.m2);
+                sS[(base + pk) * G + g] = s;
+              } else {
+                dA[g] += fma(dt, r.k0, r.m0);
+                sS[(base + pj) * G + g] += fma(dt, r.k1, r.m1);
+                sS[(base + pk) * G + g] += fma(dt, r.k2, r.m2);
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+          if constexpr (CAP) sS[(base + pd) * G + g] = make_double2(dM[g], dA[g]);
+          else sS[(base + pd) * G + g] = dA[g];
+        }
+      }
+      __syncthreads();
+      // stream the group's slab out and leave it zeroed (slot i stays with the lane that reads it here); the next group's staging
+      // touches sU only, and every lane has passed the barrier that ended the visit loop
+      for (int i = t; i < cA.y * G; i += RBA) {
+        const size_t o = static_cast<size_t>(cA.x + i / G) * NV + g0 + i % G;
+        const Slot s = sS[i];
+        if constexpr (CAP) { Mv[o] = s.x; Av[o] = s.y; }
+        else Av[o] = s;
+        sS[i] = Slot();
+      }
+    }
+  }
+}
+
+size_t kbt_lds_bytes(int max_blk_nnz, int max_dict, bool cap_tables) {
+  const size_t cap = static_cast<size_t>((max_blk_nnz + 1) & ~1);
+  return cap * KBT_G * (cap_tables ? 16 : 8) + static_cast<size_t>(max_dict) * 16 + static_cast<size_t>(max_dict) * KBT_G * 8 + (RBA + 4) * 4 +
+         (cap / 8 + 3) * 16;
+}
+constexpr size_t KBT_STATIC_LDS = 2 * 64 * sizeof(KTab);
+
+// The batched form of eliminate(): k_take_lift, k_bc_rows and k_dinv on interleaved values, thread = (entry, column)
+template <int NV>
+__global__ void kb_take_lift(int nlift, const int32_t* __restrict__ slot, double* __restrict__ A, double* __restrict__ val) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int q = t / NV, j = t % NV;
+  if (q >= nlift) return;
+  const size_t o = static_cast<size_t>(slot[q]) * NV + j;
+  val[static_cast<size_t>(q) * NV + j] = A[o];
+  A[o] = 0.0;
+}
+template <int NV>
+__global__ void kb_bc_rows(int nbc, const int32_t* __restrict__ dofs, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+                           double* __restrict__ A) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int q = t / NV, j = t % NV;
+  if (q >= nbc) return;
+  const int row = dofs[q];
+  for (int k = rowptr[row]; k < rowptr[row + 1]; ++k) A[static_cast<size_t>(k) * NV + j] = (colidx[k] == row) ? 1.0 : 0.0;
+}
+template <int NV>
+__global__ void kb_dinv(int n, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx, const double* __restrict__ A,
+                        double* __restrict__ dinv) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  const int row = t / NV, j = t % NV;
+  if (row >= n) return;
+  double d = 0.0;
+  for (int k = rowptr[row]; k < rowptr[row + 1]; ++k)
+    if (colidx[k] == row) d = A[static_cast<size_t>(k) * NV + j];
+  dinv[static_cast<size_t>(row) * NV + j] = 1.0 / d;
+}
+
+// ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
 void free_batch_state(hf_ctx::Batch& B) {
+  dev_free(&B.M); dev_free(&B.kcol);
+  B.h_kcol.clear();
+  B.tables = false; B.rv_grid = 0;
   dev_free(&B.A); dev_free(&B.A1); dev_free(&B.dinv); dev_free(&B.lift_val); dev_free(&B.lift1); dev_free(&B.g);
   dev_free(&B.u); dev_free(&B.uprev); dev_free(&B.ustart); dev_free(&B.b); dev_free(&B.r); dev_free(&B.p); dev_free(&B.Ap);
   dev_free(&B.z); dev_free(&B.z2); dev_free(&B.tmp);
@@ -1036,7 +1246,17 @@ struct BatchOps {
       }
       return;
     }
-    // M is always shared (rho_c does not change inside a batch): MODE 0 / 8 on M use the shared-value kernel
+    // capacity tables in the batch (hf_set_batch_tables): the right-hand side's products run on the columns' own M
+    if constexpr (OPK == OP_PERCOL) {
+      if (vals == c->d_M && B.M != nullptr) {
+        BOp m{};
+        m.v0 = B.M;
+        hipLaunchKernelGGL((kb_spmv<MODE, NV, OP_PERCOL>), dim3(B.Pb), dim3(KB_BT), 0, c->stream, c->n, c->d_rowptr, c->d_colidx, m, x, y,
+                           B.scal, part0, bvec, Dinv(c, B), pvec, part1, part2, w, B.red, parity);
+        return;
+      }
+    }
+    // otherwise M is shared (rho_c does not change inside a batch): MODE 0 / 8 on M use the shared-value kernel
     if (vals == c->d_M) {
       BOp m{};
       m.v0 = c->d_M;
@@ -1055,6 +1275,18 @@ struct BatchOps {
   static void rhs_bdf2(hf_ctx* c, hf_ctx::Batch& B, const double* u, const double* uprev, double* b, const double* F, double* ucopy, double w) {
     BOp m{};
     m.v0 = c->d_M;
+    if constexpr (OPK == OP_PERCOL) {
+      if (B.M != nullptr) {   // capacity tables in the batch: the columns' own M
+        m.v0 = B.M;
+        if (F != nullptr)
+          hipLaunchKernelGGL((kb_spmv<14, NV, OP_PERCOL>), dim3(B.Pb), dim3(KB_BT), 0, c->stream, c->n, c->d_rowptr, c->d_colidx, m, u, b,
+                             B.scal, nullptr, uprev, F, ucopy, nullptr, nullptr, w, B.red, 0);
+        else
+          hipLaunchKernelGGL((kb_spmv<12, NV, OP_PERCOL>), dim3(B.Pb), dim3(KB_BT), 0, c->stream, c->n, c->d_rowptr, c->d_colidx, m, u, b,
+                             B.scal, nullptr, uprev, nullptr, ucopy, nullptr, nullptr, w, B.red, 0);
+        return;
+      }
+    }
     if (B.lds) {
       const hf_ctx::BatchCols& T = c->bcols;
       const BComp comp{T.ptr, T.dict, T.own, T.id, T.rpc, T.nchunks, T.cap_nnz, T.cap_dict};
@@ -1278,6 +1510,51 @@ struct BatchOps {
     return HF_OK;
   }
 
+  // A_j = M_j + dt' K_j (and M_j with capacity tables) of every column at the column's evaluation state - u^n, or 2 u^n - u^{n-1}
+  // for BDF2 with a history - by one launch of kb_assemble_rows_T, then the batched eliminate(): lifting values, Dirichlet rows
+  // and columns, D^-1.  All on the stream.  max_workgroups > 0 caps the grid (hf_batch_revalue).
+  static int revalue(hf_ctx* ctx, hf_ctx::Batch& B, int max_workgroups) {
+    if constexpr (OPK != OP_PERCOL) {
+      return fail(ctx, HF_ERR_STATE, "batch re-valuation needs per-column operators");
+    } else {
+      const hf_ctx::KappaT& K = ctx->kt;
+      const bool capt = K.c_on;
+      const int cap = (ctx->max_blk_nnz + 1) & ~1, capd = ctx->rg_max_dict;
+      const size_t sm = kbt_lds_bytes(ctx->max_blk_nnz, capd, capt);
+      const void* fn = capt ? reinterpret_cast<const void*>(&kb_assemble_rows_T<NV, true>) : reinterpret_cast<const void*>(&kb_assemble_rows_T<NV, false>);
+      if (B.rv_grid == 0) {
+        if (sm > 64 * 1024) HF_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(sm)));
+        int ncu = 0, per_cu = 0;
+        HF_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, RBA, sm));
+        HF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, ctx->dev));
+        B.rv_grid = std::max(1, std::min(ctx->nblk_a, std::max(1, per_cu) * std::max(1, ncu)));
+        if (std::getenv("HEATFLOW_DEBUG"))
+          std::fprintf(stderr, "[batch tables] kb_assemble_rows_T<%d, %s>: %zu bytes of dynamic LDS, %d workgroups per CU, grid %d of %d blocks\n", NV,
+                       capt ? "true" : "false", sm, per_cu, B.rv_grid, ctx->nblk_a);
+      }
+      const int grid = max_workgroups > 0 ? std::min(B.rv_grid, max_workgroups) : B.rv_grid;
+      const double* um1 = ctx->scheme == HF_TIME_BDF2 && B.bdf_hist ? B.uprev : nullptr;
+      const uint4* ell = reinterpret_cast<const uint4*>(ctx->d_rg_ell);
+      const uint4* cid = reinterpret_cast<const uint4*>(ctx->d_rg_cid);
+      if (capt)
+        hipLaunchKernelGGL((kb_assemble_rows_T<NV, true>), dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr, ctx->d_rg_hdr, ell,
+                           cid, ctx->d_rg_zrb, ctx->d_rg_dict, K.hdr, K.vals, K.chdr, K.cvals, B.kcol, ctx->d_rhoc_rg, ctx->dt, B.u, um1, B.M, B.A);
+      else
+        hipLaunchKernelGGL((kb_assemble_rows_T<NV, false>), dim3(grid), dim3(RBA), sm, ctx->stream, ctx->nblk_a, cap, capd, ctx->d_rowptr, ctx->d_rg_hdr, ell,
+                           cid, ctx->d_rg_zrb, ctx->d_rg_dict, K.hdr, K.vals, static_cast<const KTab*>(nullptr), static_cast<const double*>(nullptr), B.kcol,
+                           ctx->d_rhoc_rg, ctx->dt, B.u, um1, static_cast<double*>(nullptr), B.A);
+      const System& S = ctx->sys;
+      if (S.nbc > 0) {
+        if (S.nlift > 0)
+          hipLaunchKernelGGL((kb_take_lift<NV>), dim3((S.nlift * NV + 255) / 256), dim3(256), 0, ctx->stream, S.nlift, S.lift_slot, B.A, B.lift_val);
+        hipLaunchKernelGGL((kb_bc_rows<NV>), dim3((S.nbc * NV + 255) / 256), dim3(256), 0, ctx->stream, S.nbc, S.bc_dofs, ctx->d_rowptr, ctx->d_colidx, B.A);
+      }
+      hipLaunchKernelGGL((kb_dinv<NV>), dim3((ctx->n * NV + 255) / 256), dim3(256), 0, ctx->stream, ctx->n, ctx->d_rowptr, ctx->d_colidx, B.A, B.dinv);
+      HF_HIP(hipGetLastError());
+      return HF_OK;
+    }
+  }
+
   static ProjVecs proj_active(const hf_ctx::Batch& B) {
     ProjVecs a{};
     a.m = 0;
@@ -1292,6 +1569,9 @@ struct BatchOps {
   // single-column loop, without the boundary responses)
   static int step(hf_ctx* ctx, hf_ctx::Batch& B, const double* g_dev, double rtol, double atol, int max_it) {
     const int nb = ctx->sys.nbc;
+    // under tables every column's operators are re-valued at its evaluation state first, as step_device does, before the
+    // right-hand side's pass moves the state buffers
+    if (B.tables) HF_TRY(revalue(ctx, B, 0));
     if (ctx->scheme == HF_TIME_BDF2) {
       // b = M (4/3 u^n - 1/3 u^{n-1}) (+ dt' F) in one pass over M; the same pass copies u^n into `ustart`, which then
       // becomes u^{n-1} of the next step (pointer swap, no copy).  From a rest start (no history) u^{n-1} = u^n.

@@ -194,7 +194,8 @@ struct hf_ctx {
     std::vector<double> h_m;    // (m_z, m_r) by cell tag, 1 where isotropic: the weights of a kappa column (hf_tangent_setup_dir)
     uint64_t hash = 0;          // of the multipliers by cell tag (0 while off): part of the operator's fingerprint (OperatorPrint)
   } an;
-  bool an_tables = false;      // hf_set_aniso_tables: tables and anisotropic tags together (the _an table kernels); hf_set_mesh resets it
+  bool batch_tables = false;   // hf_set_batch_tables: hf_batch_begin accepts tables (per-column operators, re-valued every step); hf_set_mesh resets it
+  bool an_tables = false;     // hf_set_aniso_tables: tables and anisotropic tags together (the _an table kernels); hf_set_mesh resets it
   // device: the mass matrix (the operators that are solved with live in a System, below)
   double* d_M = nullptr;
   // device: vectors
@@ -376,6 +377,13 @@ struct hf_ctx {
     bool lds = false;            // fine-pattern products through kb_spmv_lds (the context's `bcols` tables are for this nv)
     const double* load = nullptr;   // per-column load F (interleaved): b = M u + dt F (the tangent stage); null: b = M u
     bool noproj = false;         // the operator changes from step to step (tangent runs under tables): the ring is neither combined from nor stored into
+    // a batch under tables (hf_set_batch_tables): every step re-values A (and, with capacity tables, M) of every
+    // column at the column's own state (kb_assemble_rows_T).  Nothing below is allocated while `tables` is false.
+    bool tables = false;
+    double* M = nullptr;         // per-column mass matrices, interleaved like A (capacity tables only; else M stays the shared d_M)
+    double* kcol = nullptr;      // [64][nv]: column j's constant conductivity by tag-dictionary index (hf_batch_set_column_kappa)
+    std::vector<double> h_kcol;  // its host copy
+    int rv_grid = 0;             // persistent grid of kb_assemble_rows_T for this batch (0: not yet queried)
   } batch;
   // compressed columns of the batched loop's LDS-staged SpMV (BComp in hf_batch.hpp): per chunk of `rpc` rows a sorted
   // column list and per nonzero a 16-bit position in it; built on the first hf_batch_begin with a given nv, kept per mesh

@@ -44,7 +44,8 @@ from .geometry import check_thickness_name, stack_no_diamond, stack_with_diamond
 from .heating import HeatingCurve
 from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, aniso_tables, capacity_scale, check_capacity_names, check_config, refuse_aniso,
                     refuse_aniso_tables, split_param)
-from .kappa_t import (check_table_tangents, material_cv_table, material_table, picard_sweeps, refuse_tables, table_param,
+from .kappa_t import (check_sweep_tables, check_table_tangents, material_cv_table, material_table, picard_sweeps, refuse_tables,
+                      refuse_tables_unless_swept, sweep_tables, table_keys, table_param,
                       table_tangents)
 from .mesh import Mesh, load_mesh_arrays
 from .monitors import (check_sigma, parse_monitors, problem_monitors, refuse_monitors_sweeps, uncertainty as monitor_uncertainty,
@@ -340,7 +341,7 @@ class SimulationSession:
             self._heats.append(heat_o)
         return bcs
 
-    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler", kt=None, an=None, src=None, mon=None, ant=False):
+    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler", kt=None, an=None, src=None, mon=None, ant=False, bt=False):
         # the resident problem is reusable only for exactly the same Dirichlet DOF sets, in the same order, and time scheme
         # (and kappa(T) tables and Picard sweeps, or anisotropy multipliers, when a configuration has them)
         key = (dt, tuple(sorted(tag_to_rc.items())),
@@ -358,6 +359,8 @@ class SimulationSession:
             key += (("monitors",) + tuple((region, tuple(r["tags"]), r["above"]) for region, r in mon.items()),)
         if ant:                  # timing.aniso_tables: the context's switch is set when the problem is made
             key += (("aniso_tables",),)
+        if bt:                   # timing.sweep_tables: run_batch sets the context's switch on the problem it opens its batch on
+            key += (("sweep_tables",),)
         return key
 
     def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme="backward_euler", kt=None, an=None, src=None,
@@ -426,10 +429,15 @@ class SimulationSession:
         agree on its ``material`` list, ``face`` and ``keep_line`` and may differ in ``power``, the beam's ``fwhm``, ``depth`` and
         ``pulse``; the batch gets a source of its own (hf_batch_set_source) with one amplitude column per configuration.  Under
         ``timing.sweep_monitors: true`` they may carry a ``monitors`` block, the same in all of them; every result then has
-        ``monitors`` as :meth:`run` returns it.  A mismatch is a ValueError naming what differs."""
+        ``monitors`` as :meth:`run` returns it.  A mismatch is a ValueError naming what differs.
+        Under ``timing.sweep_tables: true`` the configurations may carry kappa(T) / cv(T) keys: they must agree
+        on every table and on ``picard_sweeps: 1`` and may differ in the boundary values and in the constants of the materials
+        without a conductivity table; the batch opens with per-column operators that every step re-values on the GPU, each
+        column at its own temperatures (hf_set_batch_tables, hf_batch_set_column_kappa)."""
         nv = len(cfgs)
         for c in cfgs:
-            refuse_tables(c, "run_batch (the batched loop)")
+            check_sweep_tables(c, "run_batch (the batched loop)")
+            refuse_tables_unless_swept(c, "run_batch (the batched loop)")
             refuse_source_sweeps(c, "run_batch (the batched loop)")
             refuse_monitors_sweeps(c, "run_batch (the batched loop)")
         if nv not in (2, 4, 8, 16):
@@ -453,6 +461,22 @@ class SimulationSession:
                 raise ValueError(f"run_batch: the configurations must share the monitors block (configuration {j} differs from "
                                  "configuration 0)")
         mon = self._monitors(cfgs[0])
+        # tables (timing.sweep_tables): the same in every configuration, material by material
+        tabled = [bool(table_keys(c)) for c in cfgs]
+        if any(tabled):
+            if not all(sweep_tables(c) for c in cfgs):
+                raise ValueError("run_batch: the configurations must share timing.sweep_tables")
+            names = sorted({str(nm) for c in cfgs for nm in (c.get("mats") or {})})
+            for nm in names:
+                per = []
+                for c in cfgs:
+                    mat = (c.get("mats") or {}).get(nm)
+                    tabs = (material_table(nm, mat), material_cv_table(nm, mat)) if isinstance(mat, dict) else (None, None)
+                    per.append(tuple(None if t is None else (float(t[0]), float(t[1]), tuple(float(v) for v in t[2])) for t in tabs))
+                for j, t in enumerate(per):
+                    if t != per[0]:
+                        raise ValueError(f"run_batch: the configurations must share every table under timing.sweep_tables: the tables "
+                                         f"of material {nm} differ between configuration 0 and configuration {j}")
         t_start = time.time()
         cfg0 = cfgs[0]
         num_steps = int(cfg0["timing"]["num_steps"])
@@ -475,16 +499,19 @@ class SimulationSession:
         # the operators an affine family A + (kappa_j - kappa_ref) A1: two shared matrices instead of nv
         varying = [t for t in mid[1] if any(c[1][t] != mid[1][t] for c in cols)]
         affine = percol and len(varying) == 1
+        kt = self._kappa_tables(cfgs[nv // 2], stacks[nv // 2]) if any(tabled) else None
+        if kt is not None:       # under tables every column has its own operator, re-valued by the batch itself
+            percol, affine = True, False
         # the batch's problem carries the monitors' table and no source of its own (the batch gets one: hf_batch_begin refuses the
         # context's); a resident problem that differs by its source alone (a single run before, or prepare) gives the source up
         an_mid = self._aniso(stacks[nv // 2])
-        key = self._problem_key(dt, mid[2], mid[0], scheme, None, an_mid, None, mon)
+        key = self._problem_key(dt, mid[2], mid[0], scheme, kt, an_mid, None, mon, False, kt is not None)
         if specs[0] is not None and self.problem is not None and self.problem.source and \
                 self._key == self._problem_key(dt, mid[2], mid[0], scheme, None, an_mid, self.problem.source, mon):
             self.problem.backend.set_source(None)
             self.problem.source = None
             self._key, self._source_F1, self._source_G = key, None, None
-        self._ensure_problem(key, mid[1], mid[2], dt, mid[0], ic_temp, scheme, None, an_mid, None, mon)
+        self._ensure_problem(key, mid[1], mid[2], dt, mid[0], ic_temp, scheme, kt, an_mid, None, mon)
         prob = self.problem
         be = prob.backend
         if percol and self.precond == 1:             # all columns share the hierarchy: keep every column within its range
@@ -518,9 +545,16 @@ class SimulationSession:
             print("Setting up radial heat flux sampling...")
             be.flux_setup()                    # once per mesh: the unit-coefficient mass matrix does not depend on kappa
             prob._flux_ready = True
+        if kt is not None:
+            be.set_state(np.full(prob.n, ic_temp))       # (a resident problem may stand at the end of an earlier run)
+            be.set_batch_tables(True)
         be.batch_begin(nv, per_column_operator=2 if affine else (1 if percol else 0))
         try:
-            if affine:
+            if kt is not None:   # the constants of the materials without a conductivity table, column by column
+                free = sorted(t for t in mid[1] if t not in kt[0])
+                for j, (_, tk, _, _) in enumerate(cols):
+                    be.batch_set_column_kappa(j, free, [tk[t] for t in free])
+            elif affine:
                 be.batch_set_affine(varying, [c[1][varying[0]] - mid[1][varying[0]] for c in cols])
             elif percol:
                 for j, (_, tk, trc, _) in enumerate(cols):

@@ -36,6 +36,7 @@ EXPORTS = [
     "hf_batch_begin", "hf_batch_load_column", "hf_batch_set_affine", "hf_batch_set_state", "hf_batch_get_state", "hf_batch_run", "hf_batch_run_flux", "hf_batch_end",
     "hf_batch_set_source", "hf_batch_get_source", "hf_batch_set_source_amplitudes",
     "hf_batch_set_monitors", "hf_batch_monitor_now", "hf_batch_monitor_count", "hf_batch_get_monitors",
+    "hf_set_batch_tables", "hf_batch_set_column_kappa", "hf_batch_revalue", "hf_batch_get_operator",
     "hf_flux_setup", "hf_flux_project", "hf_flux_solve", "hf_flux_sample",
     "hf_steady_setup", "hf_steady_solve", "hf_steady_picard_setup", "hf_steady_picard_solve", "hf_set_load", "hf_get_load", "hf_hold_load",
     "hf_set_source", "hf_get_source", "hf_set_source_amplitudes",
@@ -140,6 +141,10 @@ def load_library():
         "hf_batch_monitor_now": [vp, pd],
         "hf_batch_monitor_count": [vp, pi],
         "hf_batch_get_monitors": [vp, i32, i32, pd],
+        "hf_set_batch_tables": [vp, i32],
+        "hf_batch_set_column_kappa": [vp, i32, i32, pi, pd],
+        "hf_batch_revalue": [vp, i32],
+        "hf_batch_get_operator": [vp, i32, pd, pd, pd, pd],
         "hf_flux_setup": [vp],
         "hf_flux_project": [vp, dbl, i32, pd, pd, pi],
         "hf_flux_solve": [vp, i32, dbl, i32, pi],
@@ -364,6 +369,7 @@ class HeatflowHIP:
         d = _i32(dofs)
         self._check(self._lib.hf_set_dirichlet(self._ctx, len(d), _pi(d) if len(d) else None))
         self._refresh_sizes()
+        self._bc_dofs = d.copy()                # batch_get_operator sizes the lifting values by it
 
     def set_precond(self, kind=PC_JACOBI, reuse=False):
         """PC_JACOBI (0) or PC_AMG (1); call before assemble()."""
@@ -706,6 +712,44 @@ class HeatflowHIP:
     def batch_end(self):
         self._check(self._lib.hf_batch_end(self._ctx))
         self.batch_nv = 0
+
+    # -- batches under kappa(T) / rho_c(T) tables (hf_set_batch_tables) ----------------------------------------
+    def set_batch_tables(self, on):
+        """Allow (``on`` true) or refuse again batch_begin while tables are set.  Under the switch the batch opens with
+        per-column operators only and every step re-values them on the GPU, each column at its own state.  Off by default and
+        after every set_mesh; switching off closes an open batch under tables."""
+        self._check(self._lib.hf_set_batch_tables(self._ctx, 1 if on else 0))
+
+    def batch_set_column_kappa(self, j, tags, k):
+        """Column j's constant conductivities of the cell tags ``tags`` (tags without a conductivity table); the default is the
+        context's."""
+        t, v = _i32(tags).ravel(), _f64(k).ravel()
+        if t.shape != v.shape:
+            raise ValueError("batch_set_column_kappa: one conductivity per tag expected")
+        self._check(self._lib.hf_batch_set_column_kappa(self._ctx, int(j), len(t), _pi(t), _pd(v)))
+
+    def batch_revalue(self, max_workgroups=0):
+        """Re-value and eliminate every column's operators at the batch's current states, without stepping (a test window).
+        ``max_workgroups`` > 0 caps the kernel's grid."""
+        self._check(self._lib.hf_batch_revalue(self._ctx, int(max_workgroups)))
+
+    def lift_slots(self):
+        """CSR positions of the lifting values: the pattern entries (free row, Dirichlet column), ascending."""
+        rowptr, colidx = self.get_csr(values=False)[:2]
+        is_bc = np.zeros(self.n, dtype=bool)
+        is_bc[np.asarray(getattr(self, "_bc_dofs", []), dtype=np.int64)] = True
+        rows = np.repeat(np.arange(self.n), np.diff(rowptr))
+        return np.nonzero(~is_bc[rows] & is_bc[colidx])[0]
+
+    def batch_get_operator(self, j, want_M=False):
+        """Column j of the open batch's per-column operator, de-interleaved: dict(A=(nnz,), dinv=(n,), lift=(n_lift,)) and, with
+        ``want_M`` (capacity tables in the batch), M=(nnz,).  ``lift`` follows :meth:`lift_slots`."""
+        out = {"A": np.empty(self.nnz), "dinv": np.empty(self.n), "lift": np.empty(len(self.lift_slots()))}
+        if want_M:
+            out["M"] = np.empty(self.nnz)
+        self._check(self._lib.hf_batch_get_operator(self._ctx, int(j), _pd(out["A"]), _pd(out["dinv"]),
+                                                    _pd(out["lift"]) if len(out["lift"]) else None, _pd(out.get("M"))))
+        return out
 
     # -- a source and monitor records of the open batch (DESIGN.md 3.21) -----------------------------------------------------
     def _batch_columns(self, name, v):

@@ -129,6 +129,56 @@ def refuse_tables(cfg, where):
         raise ValueError(f"{where} does not support temperature-dependent heat capacities ({', '.join(keys)})")
 
 
+SWEEP_SWITCH = "timing.sweep_tables"
+
+
+def sweep_tables(cfg):
+    """``timing.sweep_tables``: True opts in to kappa(T) / cv(T) keys in the sweeps and the batched loop (default
+    off).  ValueError naming the key for anything but true or false."""
+    v = (cfg.get("timing") or {}).get("sweep_tables", False)
+    if not isinstance(v, bool):
+        raise ValueError(f"{SWEEP_SWITCH} must be true or false, got {v!r}")
+    return v
+
+
+def refuse_tables_unless_swept(cfg, where):
+    """:func:`refuse_tables` unless ``timing.sweep_tables`` is set: the three sweep entry points' check."""
+    if not sweep_tables(cfg):
+        refuse_tables(cfg, where)
+
+
+def check_sweep_tables(cfg, where, swept=()):
+    """What stays refused under ``timing.sweep_tables: true`` for a configuration with tables: ValueError naming both keys (or
+    the argument) involved.  ``swept``: the materials whose ``k`` a kappa sweep varies."""
+    if not sweep_tables(cfg) or not table_keys(cfg):
+        return
+    tables = ", ".join(table_keys(cfg))
+    timing = cfg.get("timing") or {}
+    if picard_sweeps(cfg) > 1:
+        raise ValueError(f"{where}: timing.picard_sweeps = {picard_sweeps(cfg)} together with {SWEEP_SWITCH} is not supported "
+                         "(the batch under tables takes one sweep per step, picard_sweeps: 1)")
+    aniso = [f"mats.{name}.k_aniso" for name, mat in sorted((cfg.get("mats") or {}).items()) if isinstance(mat, dict) and "k_aniso" in mat]
+    if aniso:
+        extra = " (also with timing.aniso_tables)" if timing.get("aniso_tables") else ""
+        raise ValueError(f"{where}: {', '.join(aniso)} together with {SWEEP_SWITCH} is not supported{extra}: the batch under tables "
+                         f"({tables}) is isotropic")
+    if isinstance(cfg.get("heating"), dict) and cfg["heating"].get("source") is not None:
+        raise ValueError(f"{where}: heating.source together with {SWEEP_SWITCH} is not supported (also with heating.source.sweeps: "
+                         f"true): the batch under tables ({tables}) has no source")
+    if cfg.get("monitors") is not None:
+        raise ValueError(f"{where}: monitors together with {SWEEP_SWITCH} is not supported (also with timing.sweep_monitors: true): "
+                         f"the batch under tables ({tables}) keeps no records")
+    if table_tangents(cfg):
+        raise ValueError(f"{where}: timing.table_tangents together with {SWEEP_SWITCH} is not supported (batched columns have no "
+                         "tangents)")
+    for name in swept:
+        mat = (cfg.get("mats") or {}).get(name)
+        keys = [k for k in TABLE_KEYS if isinstance(mat, dict) and k in mat]
+        if keys:
+            raise ValueError(f"{where}: a k range over {name} together with mats.{name}.{keys[0]} is not supported under "
+                             f"{SWEEP_SWITCH} (per-column tables: every point shares the tables)")
+
+
 def table_derivative(mat, name):
     """(kind, values): the derivative of a material's table with respect to the parameter ``name``, at the table's own knots
     (DESIGN.md 3.20).  ``mat`` is the material's entry of cfg["mats"], ``kind`` "kappa" or "rhoc" (the keys of

@@ -329,6 +329,35 @@ int hf_batch_monitor_now(hf_ctx* ctx, double* out);
 int hf_batch_monitor_count(hf_ctx* ctx, int32_t* n_records);
 int hf_batch_get_monitors(hf_ctx* ctx, int32_t first, int32_t count, double* out);
 
+/* Batches under kappa(T) / rho_c(T) tables.  Opt-in: without the switch every call, message, launch and result
+ * is what it was.
+ * hf_set_batch_tables   on = 1: hf_batch_begin(nv, HF_BATCH_PER_COLUMN) is accepted while tables are set (the other operator kinds:
+ *        HF_ERR_ARG, the message names the kind).  Every step of hf_batch_run / hf_batch_run_flux then re-values A_j = M_j + dt' K_j
+ *        of all nv columns in one launch (kb_assemble_rows_T<nv, CAP>), each column at its own evaluation state - u^n, or
+ *        2 u^n - u^{n-1} for BDF2 with a history - eliminates (kb_take_lift, kb_bc_rows, kb_dinv) and solves from u^n with the
+ *        boundary values set (no projection ring: another operator every step).  With capacity tables M_j is re-valued too and
+ *        the right-hand side is formed with it.  Per column the operators are bit for bit those the single run's re-valuation
+ *        (k_assemble_rows_kT / _cT and eliminate) gives at that column's state and constants.  The multigrid hierarchy is the
+ *        frozen one hf_assemble built (hf_set_precond(1, reuse = 1)), shared by the columns.
+ *        Refused by hf_batch_begin under the switch (HF_ERR_STATE, the message names the call that set the condition): hf_set_picard
+ *        above 1, hf_set_anisotropy with an anisotropic tag, hf_table_derivatives on.  hf_batch_set_source and
+ *        hf_batch_set_monitors(1) are refused by a batch under tables (HF_ERR_STATE), and hf_set_picard above 1 while one is open.
+ *        on = 0 (the default, and after every hf_set_mesh): hf_batch_begin refuses tables as before; an open batch under tables
+ *        is closed.  hf_set_kappa_tables and hf_set_rhoc_tables close an open batch as well.  HF_ERR_STATE before hf_set_mesh.
+ * hf_batch_set_column_kappa   column j's constant conductivities of the listed cell tags (tags without a table; the default is the
+ *        context's).  A tag that carries a conductivity table: HF_ERR_ARG, the message names the tag.  rho_c stays shared.
+ *        HF_ERR_STATE unless a batch under tables is open.
+ * Read-only test windows:
+ * hf_batch_revalue   re-values and eliminates at the batch's current states without stepping; max_workgroups > 0 caps the grid
+ *        (a workgroup then takes several row blocks), 0 = the launcher's own grid.
+ * hf_batch_get_operator   column j of the batch's per-column operator, de-interleaved: A (nnz), dinv (n), lift (the lifting
+ *        values, one per pattern entry (free row, Dirichlet column) in CSR order) and M (nnz).  Any pointer may be NULL; M without
+ *        capacity tables in the batch is HF_ERR_STATE. */
+int hf_set_batch_tables(hf_ctx* ctx, int32_t on);
+int hf_batch_set_column_kappa(hf_ctx* ctx, int32_t j, int32_t n_tags, const int32_t* tags, const double* k);
+int hf_batch_revalue(hf_ctx* ctx, int32_t max_workgroups);
+int hf_batch_get_operator(hf_ctx* ctx, int32_t j, double* A, double* dinv, double* lift, double* M);
+
 /* Read-flux projection of run_no_diamond (reference run_no_diamond.py:471-491 set-up, :543-550 per
  * step): grad_smooth = L2 projection of grad(T) onto vector P1 with weight r.  hf_flux_setup
  * assembles the unit-coefficient r-weighted mass matrix on the mesh's pattern (once per mesh);
