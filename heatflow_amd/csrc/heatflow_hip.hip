@@ -122,7 +122,45 @@ void kt_free(hf_ctx* ctx) {
   hf_ctx::KappaT& K = ctx->kt;
   dev_free(&K.hdr); dev_free(&K.vals); dev_free(&K.pic); dev_free(&K.b0); dev_free(&K.change);
   dev_free(&K.chdr); dev_free(&K.cvals); dev_free(&K.w);
+  dev_free(&K.ccum); dev_free(&K.e); dev_free(&K.hchange);
   K = hf_ctx::KappaT();
+}
+
+// back to the lagged form (the capacity tables were cleared): the form's buffers and history go
+void enthalpy_off(hf_ctx* ctx) {
+  hf_ctx::KappaT& K = ctx->kt;
+  dev_free(&K.ccum); dev_free(&K.e); dev_free(&K.hchange);
+  K.hcap = 0;
+  K.hsweeps.clear();
+  K.h_cvals.clear();
+  K.form = 0;
+  K.tol = 0.0;
+  K.relax = 1.0;
+  if (K.picard > KT_MAX_PICARD) K.picard = KT_MAX_PICARD;
+}
+
+// Room for the change words of n_more steps behind the ones kept (enthalpy form; before the caller's first launch)
+int enthalpy_room(hf_ctx* ctx, int64_t n_more) {
+  hf_ctx::KappaT& K = ctx->kt;
+  if (K.form != 1) return HF_OK;
+  const int64_t have = static_cast<int64_t>(K.hsweeps.size());
+  if (have + n_more <= K.hcap) return HF_OK;
+  const int64_t cap = std::max<int64_t>(have + n_more, 2 * K.hcap);
+  unsigned long long* grown = nullptr;
+  HF_TRY(dev_alloc(ctx, &grown, static_cast<size_t>(cap)));
+  if (have > 0) {
+    const hipError_t e = copy_sync(ctx, grown, K.hchange, sizeof(unsigned long long) * static_cast<size_t>(have), hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) { dev_free(&grown); return fail(ctx, HF_ERR_HIP, "Picard history: copy failed: %s", hipGetErrorString(e)); }
+  }
+  dev_free(&K.hchange);
+  K.hchange = grown;
+  K.hcap = cap;
+  return HF_OK;
+}
+
+// what the enthalpy form (hf_set_capacity_form) does not cover: the refusal of `fn`
+int enthalpy_refuses(hf_ctx* ctx, const char* fn, const char* what) {
+  return fail(ctx, HF_ERR_STATE, "%s: the enthalpy form of the capacity is set (hf_set_capacity_form; %s)", fn, what);
 }
 
 // hf_set_anisotropy's state: every tag isotropic again
@@ -146,6 +184,7 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   monitor_free(ctx);
   tangent_free(ctx);
   kt_free(ctx);
+  heat_free(ctx);
   an_free(ctx);
   ctx->an_tables = false;
   ctx->batch_tables = false;
@@ -757,7 +796,7 @@ int hf_destroy(hf_ctx* ctx) {
   dev_free(&ctx->d_uprev); dev_free(&ctx->d_ustart);
   dev_free(&ctx->d_u); dev_free(&ctx->d_b); dev_free(&ctx->d_r); dev_free(&ctx->d_p); dev_free(&ctx->d_Ap);
   free_batch(ctx); free_batch_state(ctx->fluxb); free_batch_cols(ctx); free_system(ctx->sys); free_responses(ctx); proj_free(ctx); dev_free(&ctx->d_z); dev_free(&ctx->d_z2);
-  steady_free(ctx); load_free(ctx); source_free(ctx); monitor_free(ctx); tangent_free(ctx); kt_free(ctx); an_free(ctx); value_lists_free(ctx);
+  steady_free(ctx); load_free(ctx); source_free(ctx); monitor_free(ctx); tangent_free(ctx); kt_free(ctx); heat_free(ctx); an_free(ctx); value_lists_free(ctx);
   dev_free(&ctx->d_M1); dev_free(&ctx->d_dinv1); dev_free(&ctx->d_gz); dev_free(&ctx->d_gr); dev_free(&ctx->d_bz); dev_free(&ctx->d_br);
   dev_free(&ctx->d_tmp); dev_free(&ctx->d_part_pAp); dev_free(&ctx->d_part_rz); dev_free(&ctx->d_part_zz);
   dev_free(&ctx->d_part_bn); dev_free(&ctx->d_scal); dev_free(&ctx->d_samp_idx); dev_free(&ctx->d_samp); dev_free(&ctx->d_fsamp_idx);
@@ -883,6 +922,7 @@ int hf_set_anisotropy(hf_ctx* ctx, int32_t n, const int32_t* tags, const double*
     aniso[tg] = 1; any = true;
     by_tag[2 * tg] = m_z[i]; by_tag[2 * tg + 1] = m_r[i];
   }
+  if (any && ctx->kt.form == 1) return enthalpy_refuses(ctx, "hf_set_anisotropy", "its kernel is isotropic");
   if (any && ctx->kt.on && !ctx->an_tables)
     return fail(ctx, HF_ERR_STATE, "hf_set_anisotropy: %s tables are set (the table kernels are isotropic)", kt_kind(ctx));
   if (any && ctx->kt.on && ctx->kt.deriv)
@@ -1049,6 +1089,7 @@ int hf_set_precond(hf_ctx* ctx, int32_t kind, int32_t reuse) {
 int hf_set_time_scheme(hf_ctx* ctx, int32_t scheme) {
   if (!ctx) return HF_ERR_ARG;
   if (scheme != HF_TIME_BACKWARD_EULER && scheme != HF_TIME_BDF2) return fail(ctx, HF_ERR_ARG, "hf_set_time_scheme: unknown scheme %d", scheme);
+  if (scheme == HF_TIME_BDF2 && ctx->kt.form == 1) return enthalpy_refuses(ctx, "hf_set_time_scheme", "it is backward Euler's, BDF2 is not covered");
   if (scheme != ctx->scheme) {   // the assembled operator and an open batch belong to the other scheme
     (void)hipSetDevice(ctx->dev);
     free_batch(ctx);
@@ -1078,7 +1119,7 @@ int kt_set_tables(hf_ctx* ctx, bool cap, int32_t n_tab, const int32_t* tags, con
       ctx->assembled = false;
       ctx->sys.pred_iters = 0;
     }
-    if (!(cap ? K.k_on : K.c_on)) { kt_free(ctx); return HF_OK; }
+    if (!(cap ? K.k_on : K.c_on)) { kt_free(ctx); return HF_OK; }   // (the form too: lagged again)
     if (cap ? K.c_on : K.k_on) {
       const std::vector<KTab> none(64, KTab{0.0, 0.0, 0, 0});
       HF_HIP(copy_sync(ctx, cap ? K.chdr : K.hdr, none.data(), sizeof(KTab) * 64, hipMemcpyHostToDevice));
@@ -1087,6 +1128,7 @@ int kt_set_tables(hf_ctx* ctx, bool cap, int32_t n_tab, const int32_t* tags, con
       (cap ? K.h_chdr : K.h_hdr).clear();
       (cap ? K.c_on : K.k_on) = false;
       K.have_change = false;
+      if (cap) enthalpy_off(ctx);   // the form belongs to the capacity tables
     }
     return HF_OK;
   }
@@ -1141,6 +1183,11 @@ int kt_set_tables(hf_ctx* ctx, bool cap, int32_t n_tab, const int32_t* tags, con
   HF_HIP(copy_sync(ctx, dvals, vals.data(), sizeof(double) * vals.size(), hipMemcpyHostToDevice));
   (cap ? K.ctabled : K.tabled) = std::move(tabled);
   (cap ? K.h_chdr : K.h_hdr) = std::move(hdr);
+  if (cap) {   // the cumulative trapezoids (hf_set_capacity_form, hf_stored_heat) are built from the new values on their next use
+    dev_free(&K.ccum);
+    K.h_cvals = std::move(vals);
+    if (K.form == 1) HF_TRY(kt_ensure_cum(ctx));
+  }
   (cap ? K.c_on : K.k_on) = true;
   K.on = true;
   K.have_change = false;
@@ -1175,12 +1222,157 @@ int hf_set_picard(hf_ctx* ctx, int32_t sweeps) {
   return HF_OK;
 }
 
+int hf_set_capacity_form(hf_ctx* ctx, int32_t form) {
+  if (!ctx) return HF_ERR_ARG;
+  if (form != HF_CAPACITY_LAGGED && form != HF_CAPACITY_ENTHALPY) return fail(ctx, HF_ERR_ARG, "hf_set_capacity_form: unknown form %d", form);
+  hf_ctx::KappaT& K = ctx->kt;
+  if (form == K.form) return HF_OK;
+  HF_HIP(hipSetDevice(ctx->dev));
+  if (form == HF_CAPACITY_LAGGED) {
+    const bool c_on = K.c_on;
+    std::vector<double> keep = std::move(K.h_cvals);
+    enthalpy_off(ctx);
+    K.h_cvals = std::move(keep);
+    K.have_change = false;
+    if (c_on) { ctx->assembled = false; ctx->sys.pred_iters = 0; }
+    return HF_OK;
+  }
+  if (!K.c_on) return fail(ctx, HF_ERR_STATE, "hf_set_capacity_form: no capacity table is set (hf_set_rhoc_tables first)");
+  if (ctx->scheme == HF_TIME_BDF2) return fail(ctx, HF_ERR_STATE, "hf_set_capacity_form: BDF2 is the time scheme (the enthalpy form is backward Euler's)");
+  if (ctx->an.on) return fail(ctx, HF_ERR_STATE, "hf_set_capacity_form: a tag is anisotropic (hf_set_anisotropy; the enthalpy kernel is isotropic)");
+  // (an assembly mode other than the row gather cannot be met here: hf_set_rhoc_tables refuses it, and hf_assemble refuses another
+  // mode while the tables are set)
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_set_capacity_form: a batch is open (the batched loop takes the lagged form)");
+  if (ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "hf_set_capacity_form: a tangent is set up (tangent runs take the lagged form)");
+  if (ht_smem_bytes(ctx->max_blk_nnz, ctx->rg_max_dict) + 2 * 64 * sizeof(KTab) > 160 * 1024)
+    return fail(ctx, HF_ERR_ARG, "hf_set_capacity_form: the (M, A) slab, the two staged states and the table headers of this mesh exceed the 160 KiB of LDS");
+  HF_TRY(kt_ensure_cum(ctx));
+  HF_TRY(dev_alloc(ctx, &K.e, ctx->n));
+  K.form = 1;
+  K.tol = 0.0;
+  K.relax = 1.0;
+  K.hsweeps.clear();
+  K.have_change = false;
+  K.deriv = false;
+  ctx->assembled = false;
+  ctx->sys.pred_iters = 0;
+  return HF_OK;
+}
+
+int hf_set_picard_control(hf_ctx* ctx, double tol, double relax, int32_t max_sweeps) {
+  if (!ctx) return HF_ERR_ARG;
+  if (ctx->kt.form != 1) return fail(ctx, HF_ERR_STATE, "hf_set_picard_control: the capacity form is lagged (hf_set_capacity_form first; hf_set_picard sets its sweeps)");
+  if (!(tol >= 0.0) || !std::isfinite(tol)) return fail(ctx, HF_ERR_ARG, "hf_set_picard_control: tol %g is not >= 0 and finite", tol);
+  if (!(relax > 0.0) || !(relax <= 1.0)) return fail(ctx, HF_ERR_ARG, "hf_set_picard_control: relax %g outside (0, 1]", relax);
+  if (max_sweeps < 1 || max_sweeps > KT_MAX_SWEEPS) return fail(ctx, HF_ERR_ARG, "hf_set_picard_control: max_sweeps %d outside 1..%d", max_sweeps, KT_MAX_SWEEPS);
+  ctx->kt.tol = tol;
+  ctx->kt.relax = relax;
+  ctx->kt.picard = max_sweeps;
+  return HF_OK;
+}
+
+int hf_enthalpy_revalue(hf_ctx* ctx, const double* un, const double* e) {
+  if (!ctx) return HF_ERR_ARG;
+  if (ctx->kt.form != 1) return fail(ctx, HF_ERR_STATE, "hf_enthalpy_revalue: the capacity form is lagged (hf_set_capacity_form first)");
+  if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "hf_enthalpy_revalue before hf_assemble");
+  if (!un || !e) return fail(ctx, HF_ERR_ARG, "hf_enthalpy_revalue: null pointer");
+  HF_HIP(hipSetDevice(ctx->dev));
+  DevTemp<double> d_un;
+  HF_TRY(dev_alloc(ctx, &d_un.p, ctx->n));
+  HF_HIP(copy_sync(ctx, d_un.p, un, sizeof(double) * ctx->n, hipMemcpyHostToDevice));
+  HF_HIP(copy_sync(ctx, ctx->kt.e, e, sizeof(double) * ctx->n, hipMemcpyHostToDevice));
+  HF_TRY(kt_revalue(ctx, ctx->kt.e, nullptr, d_un.p));
+  if (ctx->sys.precond == 1 && ctx->sys.amg_ready) ctx->sys.amg_fine_stale = true;
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  return HF_OK;
+}
+
+int hf_get_picard_history(hf_ctx* ctx, int32_t* sweeps, double* change, int32_t cap, int32_t* n) {
+  if (!ctx || !n) return HF_ERR_ARG;
+  if (ctx->kt.form != 1) return fail(ctx, HF_ERR_STATE, "hf_get_picard_history: the capacity form is lagged (hf_set_capacity_form first)");
+  const int64_t have = static_cast<int64_t>(ctx->kt.hsweeps.size());
+  *n = static_cast<int32_t>(have);
+  if (cap < 0) return fail(ctx, HF_ERR_ARG, "hf_get_picard_history: negative capacity");
+  const int64_t m = std::min<int64_t>(have, cap);
+  if (m > 0 && (!sweeps || !change)) return fail(ctx, HF_ERR_ARG, "hf_get_picard_history: null pointer");
+  if (m == 0) return HF_OK;
+  HF_HIP(hipSetDevice(ctx->dev));
+  std::memcpy(sweeps, ctx->kt.hsweeps.data(), sizeof(int32_t) * static_cast<size_t>(m));
+  HF_HIP(copy_sync(ctx, change, ctx->kt.hchange, sizeof(double) * static_cast<size_t>(m), hipMemcpyDeviceToHost));   // (the bits of doubles >= 0)
+  return HF_OK;
+}
+
+int hf_clear_picard_history(hf_ctx* ctx) {
+  if (!ctx) return HF_ERR_ARG;
+  if (ctx->kt.form != 1) return fail(ctx, HF_ERR_STATE, "hf_clear_picard_history: the capacity form is lagged (hf_set_capacity_form first)");
+  ctx->kt.hsweeps.clear();
+  ctx->kt.have_change = false;
+  return HF_OK;
+}
+
+int hf_stored_heat(hf_ctx* ctx, double T_ref, double* out) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh || !ctx->have_mat) return fail(ctx, HF_ERR_STATE, "hf_stored_heat needs hf_set_mesh and hf_set_materials first");
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_stored_heat: a batch is open (the stored heat is the single state's)");
+  if (!ctx->rg_ok) return fail(ctx, HF_ERR_STATE, "hf_stored_heat: the mesh has no row-gather lists (their tag dictionary is the record's)");
+  if (!std::isfinite(T_ref)) return fail(ctx, HF_ERR_ARG, "hf_stored_heat: T_ref is not finite");
+  if (!out) return fail(ctx, HF_ERR_ARG, "hf_stored_heat: null pointer");
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_TRY(heat_ensure(ctx));
+  heat_launch(ctx, T_ref, ctx->heat.now);
+  HF_HIP(hipGetLastError());
+  HF_HIP(copy_sync(ctx, out, ctx->heat.now, sizeof(double) * static_cast<size_t>(ctx->tab_len), hipMemcpyDeviceToHost));
+  return HF_OK;
+}
+
+int hf_set_heat_records(hf_ctx* ctx, int32_t on, double T_ref) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!ctx->have_mesh || !ctx->have_mat) return fail(ctx, HF_ERR_STATE, "hf_set_heat_records needs hf_set_mesh and hf_set_materials first");
+  if (!on) { ctx->heat.rec_on = false; return HF_OK; }
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_set_heat_records: a batch is open (the batched loop records nothing)");
+  if (!ctx->rg_ok) return fail(ctx, HF_ERR_STATE, "hf_set_heat_records: the mesh has no row-gather lists (their tag dictionary is the record's)");
+  if (!std::isfinite(T_ref)) return fail(ctx, HF_ERR_ARG, "hf_set_heat_records: T_ref is not finite");
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_TRY(heat_ensure(ctx));
+  ctx->heat.rec_on = true;
+  ctx->heat.T_ref = T_ref;
+  return HF_OK;
+}
+
+int hf_heat_count(hf_ctx* ctx, int32_t* n_records) {
+  if (!ctx || !n_records) return HF_ERR_ARG;
+  *n_records = static_cast<int32_t>(ctx->heat.count);
+  return HF_OK;
+}
+
+int hf_get_heat(hf_ctx* ctx, int32_t first, int32_t count, double* out) {
+  if (!ctx) return HF_ERR_ARG;
+  if (first < 0 || count < 0 || static_cast<int64_t>(first) + count > ctx->heat.count)
+    return fail(ctx, HF_ERR_ARG, "hf_get_heat: records [%d, %lld) outside the %lld records kept", first,
+                static_cast<long long>(first) + count, static_cast<long long>(ctx->heat.count));
+  if (count == 0) return HF_OK;
+  if (!out) return fail(ctx, HF_ERR_ARG, "hf_get_heat: null pointer");
+  HF_HIP(hipSetDevice(ctx->dev));
+  HF_HIP(copy_sync(ctx, out, ctx->heat.rec + static_cast<size_t>(first) * ctx->tab_len,
+                   sizeof(double) * static_cast<size_t>(count) * ctx->tab_len, hipMemcpyDeviceToHost));
+  return HF_OK;
+}
+
+int hf_clear_heat_records(hf_ctx* ctx) {
+  if (!ctx) return HF_ERR_ARG;
+  ctx->heat.count = 0;
+  return HF_OK;
+}
+
 int hf_get_picard_change(hf_ctx* ctx, double* max_du) {
   if (!ctx || !max_du) return HF_ERR_ARG;
   if (!ctx->kt.on || !ctx->kt.have_change) return fail(ctx, HF_ERR_STATE, "hf_get_picard_change: no step with kappa(T) tables since they were set");
   HF_HIP(hipSetDevice(ctx->dev));
   unsigned long long bits = 0;
-  HF_HIP(copy_sync(ctx, &bits, ctx->kt.change, sizeof bits, hipMemcpyDeviceToHost));
+  if (ctx->kt.form == 1)   // the enthalpy form: the last entry of the history
+    HF_HIP(copy_sync(ctx, &bits, ctx->kt.hchange + (ctx->kt.hsweeps.size() - 1), sizeof bits, hipMemcpyDeviceToHost));
+  else
+    HF_HIP(copy_sync(ctx, &bits, ctx->kt.change, sizeof bits, hipMemcpyDeviceToHost));
   std::memcpy(max_du, &bits, sizeof bits);
   return HF_OK;
 }
@@ -1451,10 +1643,13 @@ int hf_step(hf_ctx* ctx, const double* g_bc, double rtol, double atol, int32_t m
   HF_HIP(hipSetDevice(ctx->dev));
   HF_TRY(source_steps_ok(ctx, 1, "hf_step"));
   HF_TRY(monitor_room(ctx, 1));
+  HF_TRY(enthalpy_room(ctx, 1));
+  HF_TRY(heat_room(ctx, 1));
   HF_HIP(hipEventRecord(ctx->ev0, ctx->stream));
   const int rc = step_device(ctx, g_bc, nullptr, rtol, atol, max_it);
   if (rc == HF_ERR_HIP) return rc;
   if (ctx->mon.on && rc == HF_OK) monitor_record(ctx);
+  if (ctx->heat.rec_on && rc == HF_OK) heat_record(ctx);
   HF_HIP(hipEventRecord(ctx->ev1, ctx->stream));
   HF_HIP(hipStreamSynchronize(ctx->stream));
   float ms = 0.f;
@@ -1476,6 +1671,8 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
   HF_HIP(hipSetDevice(ctx->dev));
   HF_TRY(source_steps_ok(ctx, n_steps, "hf_run"));
   HF_TRY(monitor_room(ctx, n_steps));
+  HF_TRY(enthalpy_room(ctx, n_steps));
+  HF_TRY(heat_room(ctx, n_steps));
   DevTemp<double> t_gall, t_sall;
   double *&d_gall = t_gall.p, *&d_sall = t_sall.p;
   if (ctx->sys.nbc > 0) {   // all boundary vectors in one transfer; the steps copy device to device
@@ -1497,6 +1694,7 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
       hipLaunchKernelGGL(k_gather, dim3((ns + 255) / 256), dim3(256), 0, ctx->stream, ns, ctx->d_samp_idx, ctx->d_u,
                          d_sall + static_cast<size_t>(s) * ns);
     if (ctx->mon.on && rc == HF_OK) monitor_record(ctx);
+    if (ctx->heat.rec_on && rc == HF_OK) heat_record(ctx);
   }
   (void)hipEventRecord(ctx->ev1, ctx->stream);
   (void)hipStreamSynchronize(ctx->stream);
@@ -1510,6 +1708,7 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
 int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup before hf_set_mesh");
+  if (ctx->kt.form == 1) return enthalpy_refuses(ctx, "hf_tangent_setup", "tangent runs take the lagged form");
   HF_TRY(tangent_tables_ok(ctx, "hf_tangent_setup", n_par >= 1 && n_par <= NV_MAX ? n_par : 0));
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a batch is open");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup: a load is set (tangents of pre-heated runs are not supported)");
@@ -1553,6 +1752,7 @@ int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
 int hf_tangent_setup_dir(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col_k, const int32_t* tag_col_r, const int32_t* tag_col_z) {
   if (!ctx) return HF_ERR_ARG;
   if (!ctx->have_mesh) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir before hf_set_mesh");
+  if (ctx->kt.form == 1) return enthalpy_refuses(ctx, "hf_tangent_setup_dir", "tangent runs take the lagged form");
   HF_TRY(tangent_tables_ok(ctx, "hf_tangent_setup_dir", n_par >= 1 && n_par <= NV_MAX ? n_par : 0));
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a batch is open");
   if (ctx->have_load) return fail(ctx, HF_ERR_STATE, "hf_tangent_setup_dir: a load is set (tangents of pre-heated runs are not supported)");
@@ -2402,6 +2602,7 @@ int hf_hold_load(hf_ctx* ctx) {
 int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
   if (!ctx) return HF_ERR_ARG;
   const bool tables = ctx->kt.on;
+  if (ctx->kt.form == 1) return enthalpy_refuses(ctx, "hf_batch_begin", "the batched loop takes the lagged form");
   if (tables && !ctx->batch_tables)
     return fail(ctx, HF_ERR_STATE, "hf_batch_begin: %s tables are set (batched sweeps of the nonlinear loop are not supported)", kt_kind(ctx));
   if (tables) {   // hf_set_batch_tables: what the batch under tables does not cover

@@ -98,6 +98,7 @@ struct BRed { double pAp[NV_MAX], rz[2][NV_MAX], zz[NV_MAX], bn[NV_MAX]; };
 // t0 + i / inv_dt, i = 0..n-1, values vals[off + i], clamped to the end values outside it; n = 0: no table
 constexpr int KT_MAX_KNOTS = 256;
 constexpr int KT_MAX_PICARD = 8;
+constexpr int KT_MAX_SWEEPS = 64;      // the sweep cap of the enthalpy form (hf_set_picard_control)
 struct KTab { double t0, inv_dt; int n, off; };
 
 // Directional tangent loads (hf_tangent_setup_dir): per tag-dictionary index the destination columns of the tag's radial and
@@ -108,8 +109,8 @@ struct TanDir { int32_t c_r, c_z; double w_r, w_z; };
 // The row-gather assembly kernels: k_assemble_rows<false / true>, k_assemble_rows_an<false / true>, k_assemble_rows_kT,
 // k_assemble_rows_cT, k_assemble_rows_kT_K and the three table kernels on anisotropic tags (k_assemble_rows_kT_an, _cT_an, _kT_K_an).
 // The policies name theirs from their template parameters: RowsConst<K, AN> RG_ROWS / RG_ROWS_K / RG_AN / RG_AN_K, RowsTable<CAP, K, AN>
-// RG_KT / RG_CT / RG_KT_K and the *_AN three.
-enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_SOURCE, RG_SOURCE_D, RG_SHAPE1, RG_SHAPE2, RG_SHAPE4, RG_TLT2, RG_TLT4, RG_TLT8, RG_TLT16, RG_KT_AN, RG_CT_AN, RG_KT_K_AN, RG_VARIANTS };
+// RG_KT / RG_CT / RG_KT_K and the *_AN three; RowsEnthalpy (k_assemble_rows_hT) RG_HT.
+enum RgVariant { RG_ROWS, RG_ROWS_K, RG_AN, RG_AN_K, RG_KT, RG_CT, RG_KT_K, RG_SOURCE, RG_SOURCE_D, RG_SHAPE1, RG_SHAPE2, RG_SHAPE4, RG_TLT2, RG_TLT4, RG_TLT8, RG_TLT16, RG_KT_AN, RG_CT_AN, RG_KT_K_AN, RG_HT, RG_VARIANTS };
 
 }  // namespace
 
@@ -483,7 +484,31 @@ struct hf_ctx {
     // (by tag-dictionary index), which hf_tangent_set_tables sizes its entries by
     bool deriv = false;
     std::vector<KTab> h_hdr, h_chdr;
+    // the enthalpy form of the capacity (hf_set_capacity_form).  Nothing below is allocated, launched or read
+    // while form == 0 and hf_stored_heat has not been called.
+    int form = 0;                    // 0 lagged: rho_c(T_e(x_{k-1})); 1 enthalpy: the chord capacity between u^n and e_{k-1}
+    double tol = 0.0, relax = 1.0;   // hf_set_picard_control: stop at change_k <= tol (0: every sweep runs), e += relax (x - e)
+    std::vector<double> h_cvals;     // host copy of cvals, from which ccum is built on first use
+    double* ccum = nullptr;          // cumulative trapezoids per knot, in knot units: the layout of cvals
+    double* e = nullptr;             // the evaluation state e_{k-1}
+    unsigned long long* hchange = nullptr;   // change_k of the last sweep of every step since the form was set / the history cleared
+    int64_t hcap = 0;
+    std::vector<int32_t> hsweeps;    // sweeps of every such step
   } kt;
+  // stored heat (hf_stored_heat, hf_set_heat_records): per cell tag sum_e vol_e (H_tag(Tw_e(u)) - H_tag(T_ref))
+  struct Heat {
+    bool ready = false;              // the buffers below exist (first use)
+    int nd = 0, nchunks = 0, grid = 0;   // row-gather dictionary entries; k_monitor's chunks and grid
+    uint8_t* slot = nullptr;         // tab_len entries: row-gather dictionary index of a cell tag, 255 = not a cell tag of the mesh
+    int32_t* tags = nullptr;         // 64 entries: the cell tag of a dictionary index
+    KTab* none = nullptr;            // 64 empty headers, for a context without capacity tables
+    double* part = nullptr;          // grid x 64 partials
+    double* now = nullptr;           // one record (tab_len doubles), for hf_stored_heat
+    bool rec_on = false;
+    double T_ref = 0.0;
+    double* rec = nullptr;           // cap records of tab_len doubles
+    int64_t cap = 0, count = 0;
+  } heat;
   // optional in-situ kernel timing (hf_set_profile): event pairs around each PCG SpMV launch
   bool prof = false;
   std::vector<hipEvent_t> prof_ev;

@@ -278,6 +278,12 @@ __device__ __forceinline__ ElemRow element_row_an(const double2 Pi, const double
   return element_row_of<true>(Pi, Pj, Pk, rho_c, k_z, k_r);
 }
 
+// V::STATE2 (optional member, STATE only): a second state is staged behind the first (sU2; v.state2(node)), and a visit receives both
+template <class V, class = void>
+struct rg_state2 : std::false_type {};
+template <class V>
+struct rg_state2<V, std::void_t<decltype(V::STATE2)>> : std::bool_constant<V::STATE2> {};
+
 constexpr int RG_NC = 4;   // 16-byte vectors of column positions a lane can prefetch (RBA * 8 * RG_NC >= slab slots: rows hold <= 32 entries)
 constexpr int RG_NX = 5;   // coordinate pairs a lane can prefetch (RBA * RG_NX >= column-list length, checked on the host)
 
@@ -313,10 +319,13 @@ __device__ __forceinline__ void rowgather_assemble(int nblk, int cap /* slab slo
                                                    const double2* __restrict__ zrb, const int32_t* __restrict__ dict, const V v,
                                                    double* __restrict__ Mv, double* __restrict__ Av, double* smem) {
   using Slot = std::conditional_t<V::PAIR, double2, double>;
+  constexpr bool S2 = rg_state2<V>::value;
+  if constexpr (S2) static_assert(V::STATE && V::NODE_FIRST, "the second state is prefetched next to the first, in the NODE_FIRST spelling");
   Slot* sS = reinterpret_cast<Slot*>(smem);                          // (M, A), A or K per slot
   double2* sXd = reinterpret_cast<double2*>(sS + cap);               // coordinates of the block's column list
   double* sU = reinterpret_cast<double*>(sXd + capd);                // STATE: the evaluation state on the block's column list
-  int* sR = reinterpret_cast<int*>(V::STATE ? sU + capd + (capd & 1) : sU);   // row starts inside the slab
+  double* sU2 = sU + capd + (capd & 1);                              // STATE2: the second state behind it
+  int* sR = reinterpret_cast<int*>(S2 ? sU2 + capd + (capd & 1) : V::STATE ? sU + capd + (capd & 1) : sU);   // row starts inside the slab
   uint4* sC4 = reinterpret_cast<uint4*>(sR + RBA + 4);               // column-list position per slot, from the 8-aligned start
   const uint16_t* sC = reinterpret_cast<const uint16_t*>(sC4);
 
@@ -328,6 +337,7 @@ __device__ __forceinline__ void rowgather_assemble(int nblk, int cap /* slab slo
   uint4 pe, pc[RG_NC];
   double2 px[RG_NX];
   double pu[V::STATE ? RG_NX : 1];
+  double pu2[S2 ? RG_NX : 1];
   int pr = 0;
   auto prefetch = [&](int blk) {
     hA = hdr[2 * blk];                                               // (k0, nk, d0, nd)
@@ -344,6 +354,7 @@ __device__ __forceinline__ void rowgather_assemble(int nblk, int cap /* slab slo
         if constexpr (V::NODE_FIRST) {
           const int node = in ? dict[hA.z + t + q * RBA] : 0;
           pu[q] = in ? v.state(node) : 0.0;
+          if constexpr (S2) pu2[q] = in ? v.state2(node) : 0.0;
         } else {
           pu[q] = in ? v.state(dict[hA.z + t + q * RBA]) : 0.0;
         }
@@ -365,6 +376,7 @@ __device__ __forceinline__ void rowgather_assemble(int nblk, int cap /* slab slo
       if (t + q * RBA < cA.w) {
         sXd[t + q * RBA] = px[q];
         if constexpr (V::STATE) sU[t + q * RBA] = pu[q];
+        if constexpr (S2) sU2[t + q * RBA] = pu2[q];
       }
     sR[t] = pr;
     __syncthreads();
@@ -378,6 +390,8 @@ __device__ __forceinline__ void rowgather_assemble(int nblk, int cap /* slab slo
       const double2 Pi = sXd[ci];
       double ui = 0.0;
       if constexpr (V::STATE) ui = sU[ci];
+      double ui2 = 0.0;
+      if constexpr (S2) ui2 = sU2[ci];
       double dM = 0.0, dA = 0.0;
       int pd = 0;                                                    // diagonal: the slot whose column is my own row
       while (pd < 31 && sC[sbase + pd] < ci) ++pd;
@@ -391,7 +405,9 @@ __device__ __forceinline__ void rowgather_assemble(int nblk, int cap /* slab slo
           const int pj = e & 31u, pk = (e >> 5) & 31u, tg = e >> 10;
           const int cj = sC[sbase + pj], ck = sC[sbase + pk];
           const double2 Pj = sXd[cj], Pk = sXd[ck];
-          const ElemRow r = v.row(tg, Pi, Pj, Pk, sU, ui, cj, ck);
+          ElemRow r;
+          if constexpr (S2) r = v.row(tg, Pi, Pj, Pk, sU, ui, sU2, ui2, cj, ck);
+          else r = v.row(tg, Pi, Pj, Pk, sU, ui, cj, ck);
           if constexpr (V::PAIR && V::KONLY) {
             dA += r.k0;
             sS[base + pj].y += r.k1;
@@ -1421,6 +1437,110 @@ __global__ __launch_bounds__(RBA) void k_assemble_rows_kT_K_an(int nblk, int cap
   if (threadIdx.x < 64) sK[threadIdx.x] = ktab[threadIdx.x];
   rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict,
                      RowsTable<false, true, true>{sK, nullptr, kvals, nullptr, kappa_idx, nullptr, an_idx, 0.0, {u, nullptr}}, nullptr, Kv, smem);
+}
+
+// The mean of the clamped piecewise-linear table over [min, max] of Ta and Tb (symmetric in them), for the enthalpy form of the
+// capacity (hf_set_capacity_form).  Everything in knot units s = (T - t0) / dT.  Both ends in one segment, or in
+// one clamped range: the table at the midpoint - exact for a linear piece, no cancellation as Tb -> Ta, and ktab_eval's own
+// arithmetic at Ta == Tb.  Otherwise (first partial piece as length x midpoint value + cum[j] - cum[i] of the whole segments
+// between + last partial piece) / (max - min); cum[j] = sum_{i < j} (v_i + v_{i+1}) / 2, the cumulative trapezoids per knot
+// (built on the host, the layout of vals).
+__device__ __forceinline__ double ktab_mean(const KTab h, const double* __restrict__ vals, const double* __restrict__ cum, double Ta,
+                                            double Tb) {
+#pragma clang fp contract(off)
+  const double sl = (fmin(Ta, Tb) - h.t0) * h.inv_dt, sh = (fmax(Ta, Tb) - h.t0) * h.inv_dt;
+  const double top = static_cast<double>(h.n - 1);
+  if (!(sh > 0.0)) return vals[h.off];
+  if (sl >= top) return vals[h.off + h.n - 1];
+  const bool below = !(sl > 0.0), above = sh >= top;
+  const int il = below ? 0 : min(static_cast<int>(sl), h.n - 2);
+  const int ih = above ? h.n - 1 : min(static_cast<int>(sh), h.n - 2);
+  if (!below && !above && il == ih) {
+    const double a = vals[h.off + il], b = vals[h.off + il + 1];
+    const double sm = sl + 0.5 * (sh - sl);
+    return a + (sm - static_cast<double>(il)) * (b - a);
+  }
+  double head, tail;
+  int jl;
+  if (below) {
+    head = (0.0 - sl) * vals[h.off];
+    jl = 0;
+  } else {
+    const double a = vals[h.off + il], b = vals[h.off + il + 1];
+    const double x = sl - static_cast<double>(il);                  // in [0, 1): the piece runs from x to 1
+    head = (1.0 - x) * (a + (0.5 * (x + 1.0)) * (b - a));
+    jl = il + 1;
+  }
+  if (above) {
+    tail = (sh - top) * vals[h.off + h.n - 1];
+  } else {
+    const double a = vals[h.off + ih], b = vals[h.off + ih + 1];
+    const double x = sh - static_cast<double>(ih);                  // the piece runs from 0 to x
+    tail = x * (a + (0.5 * x) * (b - a));
+  }
+  return ((head + (cum[h.off + ih] - cum[h.off + jl])) + tail) / (sh - sl);
+}
+
+// The r-weighted element temperature Tw_e = sum_j (rs + r_j) u_j / (4 rs), rs = r_0 + r_1 + r_2: the volume average of the P1 field
+// (k_monitor's I1 / I0).  rs and the sum of the three products go through sorted_sum3, so the three rows that visit a triangle
+// - and k_stored_heat - get the same bits.
+__device__ __forceinline__ double element_tw(double r0, double r1, double r2, double u0, double u1, double u2) {
+#pragma clang fp contract(off)
+  const double rs = sorted_sum3(r0, r1, r2);
+  return sorted_sum3((rs + r0) * u0, (rs + r1) * u1, (rs + r2) * u2) / (4.0 * rs);
+}
+
+// The coefficient policy of the enthalpy form (hf_set_capacity_form; k_assemble_rows_hT): RowsTable<true, false,
+// false>'s slab, headers and conductivity (kappa = table(T_e) at the plain-mean T_e of the evaluation state e, sU), and a second
+// staged state u^n (sU2): the capacity of a tabled tag is the chord value, the table's mean between Tw_e(u^n) and Tw_e(e)
+// (ktab_mean; table(Tw_e) where they are equal), so that 1^T M (x - u^n) is the change of the stored heat when e = x.
+struct RowsEnthalpy {
+  static constexpr bool PAIR = true, STATE = true, STATE2 = true, KONLY = false, NODE_FIRST = true;
+  static constexpr RgVariant ID = RG_HT;
+  const KTab *sK, *sCt;
+  const double *kvals, *cvals, *ccum, *kappa_idx, *rhoc_idx;
+  double dt;
+  const double *e, *un;
+  __device__ __forceinline__ double state(int node) const { return e[node]; }
+  __device__ __forceinline__ double state2(int node) const { return un[node]; }
+  __device__ __forceinline__ ElemRow row(int tg, const double2 Pi, const double2 Pj, const double2 Pk, const double* sU, double ui,
+                                         const double* sU2, double ui2, int cj, int ck) const {
+    const KTab kh = sK[tg], ch = sCt[tg];
+    double kappa = kappa_idx[tg], rho_c = rhoc_idx[tg];
+    if (kh.n > 0) kappa = ktab_eval(kh, kvals, element_temperature(sU, ui, cj, ck));
+    if (ch.n > 0) {
+      const double Ta = element_tw(Pi.y, Pj.y, Pk.y, ui2, sU2[cj], sU2[ck]);
+      const double Tb = element_tw(Pi.y, Pj.y, Pk.y, ui, sU[cj], sU[ck]);
+      rho_c = ktab_mean(ch, cvals, ccum, Ta, Tb);
+    }
+    return element_row(Pi, Pj, Pk, rho_c, kappa);
+  }
+};
+
+__global__ __launch_bounds__(RBA) void k_assemble_rows_hT(int nblk, int cap /* slab slots, even */, int capd /* column-list slots */,
+                                                          const int32_t* __restrict__ rowptr, const int4* __restrict__ hdr,
+                                                          const uint4* __restrict__ ell, const uint4* __restrict__ cid16,
+                                                          const double2* __restrict__ zrb, const int32_t* __restrict__ dict,
+                                                          const KTab* __restrict__ ktab, const double* __restrict__ kvals,
+                                                          const KTab* __restrict__ ctab, const double* __restrict__ cvals,
+                                                          const double* __restrict__ ccum,
+                                                          const double* __restrict__ kappa_idx, const double* __restrict__ rhoc_idx,
+                                                          double dt, const double* __restrict__ e, const double* __restrict__ un,
+                                                          double* __restrict__ Mv, double* __restrict__ Av) {
+  extern __shared__ double smem[];
+  __shared__ KTab sK[64], sCt[64];
+  if (threadIdx.x < 64) { sK[threadIdx.x] = ktab[threadIdx.x]; sCt[threadIdx.x] = ctab[threadIdx.x]; }
+  rowgather_assemble(nblk, cap, capd, rowptr, hdr, ell, cid16, zrb, dict,
+                     RowsEnthalpy{sK, sCt, kvals, cvals, ccum, kappa_idx, rhoc_idx, dt, e, un}, Mv, Av, smem);
+}
+
+// out = e + w (x - e): the relaxed evaluation state of the enthalpy form's next sweep (launched only when w < 1; out may be e)
+__global__ __launch_bounds__(TPB) void k_relax(int n, const double* e, const double* __restrict__ x, double w, double* out) {
+#pragma clang fp contract(off)
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
+    const double ei = e[i];
+    out[i] = ei + w * (x[i] - ei);
+  }
 }
 
 // w = u^n, or BDF2's operand (4 u^n - u^{n-1}) / 3: the vector the re-valued M multiplies in Picard sweeps 2..p of a step with

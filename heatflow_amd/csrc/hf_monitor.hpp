@@ -775,4 +775,179 @@ inline void bmon_record(hf_ctx* ctx) {
   M.count += 1;
 }
 
+// ---- stored heat (hf_stored_heat, hf_set_heat_records) -----------------------------------------------------------
+
+// Per cell tag sum_e vol_e (H_tag(Tw_e(u)) - H_tag(T_ref)), vol_e = (A_e rs) / 3 as k_monitor's I0, Tw_e the r-weighted element
+// temperature of the assembly (element_tw) and H_tag the integral of the tag's clamped capacity table - formed without a
+// difference of two integrals as mean(T_ref, Tw_e) (Tw_e - T_ref) (ktab_mean) - or rho_c T of a tag without one.  k_monitor's
+// reduction with one accumulator: one lane per triangle, the same chunks and schedule, per-wave shuffle trees into per-wave LDS
+// accumulators in ascending chunk order, the four waves added in wave order.  The dictionary is the row-gather tag dictionary
+// (every cell tag of the mesh).  No atomics; the bits depend on the mesh, the tables, T_ref and u only.
+__global__ __launch_bounds__(MON_T) void k_stored_heat(int ne, int nchunks, int tab_len, int nd, const int4* __restrict__ elem,
+                                                      const double2* __restrict__ zr, const double* __restrict__ u,
+                                                      const uint8_t* __restrict__ slot_of_tag, const KTab* __restrict__ ctab,
+                                                      const double* __restrict__ cvals, const double* __restrict__ ccum,
+                                                      const double* __restrict__ rhoc_idx, double T_ref, double* __restrict__ part) {
+  extern __shared__ uint8_t s_slot[];       // tab_len entries: dictionary index of a cell tag
+  __shared__ KTab s_ct[MON_ND];
+  __shared__ double s_rc[MON_ND];
+  __shared__ double s_E[4][MON_ND];
+  const int t = threadIdx.x, wv = t >> 6, lane = t & 63;
+  for (int i = t; i < tab_len; i += MON_T) s_slot[i] = slot_of_tag[i];
+  if (t < MON_ND) { s_ct[t] = ctab[t]; s_rc[t] = rhoc_idx[t]; }
+  s_E[wv][lane] = 0.0;
+  __syncthreads();
+  for (ChunkIter it(nchunks); it.chunk < it.end; it.chunk += it.step) {
+    const int e = it.chunk * MON_T + t;
+    int d = -1;
+    int4 E = make_int4(0, 0, 0, 0);
+    if (e < ne) {
+      E = elem[e];
+      const int s = s_slot[E.w];
+      if (s != MON_NONE) d = s;
+    }
+    double m = 0.0;
+    if (d >= 0) {
+#pragma clang fp contract(off)
+      const double2 P0 = zr[E.x], P1 = zr[E.y], P2 = zr[E.z];
+      const double dd = (P1.x - P0.x) * (P2.y - P0.y) - (P2.x - P0.x) * (P1.y - P0.y);
+      const double vol = ((0.5 * fabs(dd)) * ((P0.y + P1.y) + P2.y)) / 3.0;
+      const double Tw = element_tw(P0.y, P1.y, P2.y, u[E.x], u[E.y], u[E.z]);
+      const KTab ch = s_ct[d];
+      const double c = ch.n > 0 ? ktab_mean(ch, cvals, ccum, T_ref, Tw) : s_rc[d];
+      m = vol * (c * (Tw - T_ref));
+    }
+    unsigned long long todo = __ballot(d >= 0);      // the same in every lane: the loop is uniform over the wave
+    while (todo != 0ull) {
+      const int ds = __shfl(d, __ffsll(static_cast<long long>(todo)) - 1, 64);
+      const bool mine = d == ds;
+      double a = mine ? m : 0.0;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+#pragma clang fp contract(off)
+        a += __shfl_down(a, o, 64);
+      }
+      if (lane == 0) {
+#pragma clang fp contract(off)
+        s_E[wv][ds] += a;
+      }
+      todo &= ~__ballot(mine);
+    }
+  }
+  __syncthreads();
+  if (t < nd) {
+#pragma clang fp contract(off)
+    part[static_cast<size_t>(t) * gridDim.x + blockIdx.x] = ((s_E[0][t] + s_E[1][t]) + s_E[2][t]) + s_E[3][t];
+  }
+}
+
+// Workgroup d adds the G <= MON_FT partials of dictionary index d as k_monitor_final does and writes its tag's entry; workgroup 0
+// also writes the zeros of the entries that are no cell tag of the mesh.
+__global__ __launch_bounds__(MON_FT) void k_stored_heat_final(int G, int tab_len, const double* __restrict__ part,
+                                                             const uint8_t* __restrict__ slot_of_tag,
+                                                             const int32_t* __restrict__ tag_of_slot, double* __restrict__ out) {
+  __shared__ double s_E[16];
+  const int d = blockIdx.x, t = threadIdx.x, wv = t >> 6, lane = t & 63;
+  double a = t < G ? part[static_cast<size_t>(d) * G + t] : 0.0;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+#pragma clang fp contract(off)
+    a += __shfl_down(a, o, 64);
+  }
+  if (lane == 0) s_E[wv] = a;
+  __syncthreads();
+  if (t == 0) {
+#pragma clang fp contract(off)
+    for (int k = 1; k < MON_FT / 64; ++k) a += s_E[k];
+    out[tag_of_slot[d]] = a;
+  }
+  if (d == 0)
+    for (int k = t; k < tab_len; k += MON_FT)
+      if (slot_of_tag[k] == MON_NONE) out[k] = 0.0;
+}
+
+void heat_free(hf_ctx* ctx) {
+  hf_ctx::Heat& Q = ctx->heat;
+  dev_free(&Q.slot); dev_free(&Q.tags); dev_free(&Q.none); dev_free(&Q.part); dev_free(&Q.now); dev_free(&Q.rec);
+  Q = hf_ctx::Heat();
+}
+
+// The cumulative trapezoids of the capacity tables, on their first use (hf_set_capacity_form, hf_stored_heat)
+int kt_ensure_cum(hf_ctx* ctx) {
+  hf_ctx::KappaT& K = ctx->kt;
+  if (!K.c_on || K.ccum) return HF_OK;
+  std::vector<double> cum(K.h_cvals.size(), 0.0);
+  for (const KTab& h : K.h_chdr)
+    for (int i = 1; i < h.n; ++i) cum[h.off + i] = cum[h.off + i - 1] + 0.5 * (K.h_cvals[h.off + i - 1] + K.h_cvals[h.off + i]);
+  HF_TRY(dev_alloc(ctx, &K.ccum, cum.size()));
+  HF_HIP(copy_sync(ctx, K.ccum, cum.data(), sizeof(double) * cum.size(), hipMemcpyHostToDevice));
+  return HF_OK;
+}
+
+// The buffers of the stored heat, on its first use: the dictionary is the row-gather tag dictionary, the schedule k_monitor's
+int heat_ensure(hf_ctx* ctx) {
+  hf_ctx::Heat& Q = ctx->heat;
+  HF_TRY(kt_ensure_cum(ctx));
+  if (Q.ready) return HF_OK;
+  const int nd = static_cast<int>(std::min<size_t>(ctx->h_rg_tags.size(), MON_ND));
+  std::vector<uint8_t> slot(static_cast<size_t>(ctx->tab_len), static_cast<uint8_t>(MON_NONE));
+  std::vector<int32_t> tag_of(MON_ND, 0);
+  for (int d = 0; d < nd; ++d) {
+    const int32_t tg = ctx->h_rg_tags[d];
+    if (tg >= 0 && tg < ctx->tab_len) slot[tg] = static_cast<uint8_t>(d);
+    tag_of[d] = tg;
+  }
+  Q.nd = nd;
+  Q.nchunks = (ctx->ne + MON_T - 1) / MON_T;
+  Q.grid = std::min(Q.nchunks, MAXP);
+  if (Q.grid >= 64) Q.grid &= ~7;
+  const std::vector<KTab> none(MON_ND, KTab{0.0, 0.0, 0, 0});
+  HF_TRY(dev_alloc(ctx, &Q.slot, static_cast<size_t>(ctx->tab_len)));
+  HF_TRY(dev_alloc(ctx, &Q.tags, MON_ND));
+  HF_TRY(dev_alloc(ctx, &Q.none, MON_ND));
+  HF_TRY(dev_alloc(ctx, &Q.part, static_cast<size_t>(Q.grid) * MON_ND));
+  HF_TRY(dev_alloc(ctx, &Q.now, static_cast<size_t>(ctx->tab_len)));
+  HF_HIP(copy_sync(ctx, Q.slot, slot.data(), slot.size(), hipMemcpyHostToDevice));
+  HF_HIP(copy_sync(ctx, Q.tags, tag_of.data(), sizeof(int32_t) * MON_ND, hipMemcpyHostToDevice));
+  HF_HIP(copy_sync(ctx, Q.none, none.data(), sizeof(KTab) * MON_ND, hipMemcpyHostToDevice));
+  Q.ready = true;
+  return HF_OK;
+}
+
+// Room for n_more heat records behind the ones kept (as monitor_room: before the caller's first launch)
+int heat_room(hf_ctx* ctx, int64_t n_more) {
+  hf_ctx::Heat& Q = ctx->heat;
+  if (!Q.rec_on) return HF_OK;
+  HF_TRY(heat_ensure(ctx));      // (tables set after the switch: their cumulative trapezoids)
+  if (Q.count + n_more <= Q.cap) return HF_OK;
+  const int64_t cap = std::max<int64_t>(Q.count + n_more, 2 * Q.cap);
+  double* grown = nullptr;
+  HF_TRY(dev_alloc(ctx, &grown, static_cast<size_t>(cap) * ctx->tab_len));
+  if (Q.count > 0) {
+    const hipError_t e = copy_sync(ctx, grown, Q.rec, sizeof(double) * static_cast<size_t>(Q.count) * ctx->tab_len, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) { dev_free(&grown); return fail(ctx, HF_ERR_HIP, "heat records: copy failed: %s", hipGetErrorString(e)); }
+  }
+  dev_free(&Q.rec);
+  Q.rec = grown;
+  Q.cap = cap;
+  return HF_OK;
+}
+
+// The two launches of one evaluation of the current state, on the stream, into `out` (tab_len doubles on the device)
+void heat_launch(hf_ctx* ctx, double T_ref, double* out) {
+  hf_ctx::Heat& Q = ctx->heat;
+  const bool tabled = ctx->kt.c_on;
+  hipLaunchKernelGGL(k_stored_heat, dim3(Q.grid), dim3(MON_T), static_cast<size_t>((ctx->tab_len + 15) & ~15), ctx->stream, ctx->ne,
+                     Q.nchunks, ctx->tab_len, Q.nd, ctx->d_elem, ctx->d_zr, ctx->d_u, Q.slot, tabled ? ctx->kt.chdr : Q.none,
+                     tabled ? ctx->kt.cvals : nullptr, tabled ? ctx->kt.ccum : nullptr, ctx->d_rhoc_rg, T_ref, Q.part);
+  hipLaunchKernelGGL(k_stored_heat_final, dim3(Q.nd), dim3(MON_FT), 0, ctx->stream, Q.grid, ctx->tab_len, Q.part, Q.slot, Q.tags, out);
+}
+
+// The heat record of the step that has just been queued (the caller made room with heat_room)
+inline void heat_record(hf_ctx* ctx) {
+  hf_ctx::Heat& Q = ctx->heat;
+  heat_launch(ctx, Q.T_ref, Q.rec + static_cast<size_t>(Q.count) * ctx->tab_len);
+  Q.count += 1;
+}
+
 }  // namespace

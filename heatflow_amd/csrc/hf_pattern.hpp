@@ -368,6 +368,8 @@ size_t rowgather_lds_bytes(int max_blk_nnz, int max_dict, bool pair, bool state)
 }
 size_t rowgather_smem_bytes(int max_blk_nnz, int max_dict) { return rowgather_lds_bytes(max_blk_nnz, max_dict, true, false); }
 size_t ct_smem_bytes(int max_blk_nnz, int max_dict) { return rowgather_lds_bytes(max_blk_nnz, max_dict, true, true); }   // k_assemble_rows_cT
+size_t state2_lds_bytes(int max_dict) { return static_cast<size_t>(max_dict + (max_dict & 1)) * 8; }   // a policy's second staged state
+size_t ht_smem_bytes(int max_blk_nnz, int max_dict) { return ct_smem_bytes(max_blk_nnz, max_dict) + state2_lds_bytes(max_dict); }   // k_assemble_rows_hT
 
 // The persistent grid of a row-gather kernel with `sm` bytes of dynamic LDS: as many workgroups as fit the chip (opt-in above
 // 64 KiB), from one occupancy query kept in ctx->rg_grid[id] until the next mesh.  *per_cu_out, if given, receives the workgroups
@@ -398,7 +400,7 @@ int launch_rowgather(hf_ctx* ctx,
                      const char* (*info)(), Tail... tail) {
   const int cap = (ctx->max_blk_nnz + 1) & ~1;
   const int capd = ctx->rg_max_dict;
-  const size_t sm = rowgather_lds_bytes(ctx->max_blk_nnz, capd, V::PAIR, V::STATE);
+  const size_t sm = rowgather_lds_bytes(ctx->max_blk_nnz, capd, V::PAIR, V::STATE) + (rg_state2<V>::value ? state2_lds_bytes(capd) : 0);
   int grid = 0, per_cu = -1;
   HF_TRY(rowgather_grid(ctx, V::ID, reinterpret_cast<const void*>(kernel), sm, &grid, &per_cu));
   if (per_cu >= 0)

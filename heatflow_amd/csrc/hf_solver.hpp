@@ -806,11 +806,18 @@ int eliminate(hf_ctx* ctx, System& S) {
 // kappa(T): A = M + dt K(kappa(T_e)) at the evaluation state u (or 2 u - uprev) by the row-gather kernel, then the Dirichlet
 // elimination, the lifting values and D^-1 as hf_assemble forms them - all on the stream, no host synchronisation.  The
 // hierarchy (if any) stays the one hf_assemble built: its fused fine-level legs hold the old operator from here on.
-int kt_revalue(hf_ctx* ctx, const double* u, const double* uprev) {
+// The enthalpy form of the capacity (hf_set_capacity_form): `u` is the evaluation state e_{k-1} and `un` the
+// state u^n the chord capacity starts from (null: u itself - the capacity is then table(Tw_e)); k_assemble_rows_hT.
+int kt_revalue(hf_ctx* ctx, const double* u, const double* uprev, const double* un = nullptr) {
   value_lists_touch(ctx, ctx->sys.A);   // (no lists are built while tables are set; whatever an earlier hf_assemble left is stale now)
   if (ctx->kt.c_on) value_lists_touch(ctx, ctx->d_M);
   int rc;
-  if (ctx->an.on) {   // tables on anisotropic tags (hf_set_aniso_tables): the siblings that take the multipliers
+  if (ctx->kt.form == 1) {
+    const auto info = []() -> const char* { return std::getenv("HEATFLOW_DEBUG") ? "[enthalpy] k_assemble_rows_hT" : nullptr; };
+    rc = launch_rowgather<RowsEnthalpy>(ctx, &k_assemble_rows_hT, info, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals, ctx->kt.chdr,
+                                        ctx->kt.cvals, ctx->kt.ccum, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->dt, u, un ? un : u, ctx->d_M,
+                                        ctx->sys.A);
+  } else if (ctx->an.on) {   // tables on anisotropic tags (hf_set_aniso_tables): the siblings that take the multipliers
     if (ctx->kt.c_on)
       rc = launch_rowgather<RowsTable<true, false, true>>(ctx, &k_assemble_rows_cT_an, nullptr, ctx->d_rg_dict, ctx->kt.hdr, ctx->kt.vals,
                                                           ctx->kt.chdr, ctx->kt.cvals, ctx->d_kappa_rg, ctx->d_rhoc_rg, ctx->an.d_m, ctx->dt, u,
@@ -892,7 +899,8 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
   if (kind >= 2 && hist_ok && !(bdf2 && kind == 2)) HF_TRY(prepare_response(ctx, g_host, max_it, &ra));
   const int sweeps = kt ? ctx->kt.picard : 1;
   const bool ct = kt && ctx->kt.c_on;   // capacity tables: M is re-valued too, so every sweep forms its own right-hand side
-  const bool track = kt && last;   // the Picard change of this step is kept
+  const bool enth = kt && ctx->kt.form == 1;   // the enthalpy form: its own sweeps below (stop rule, relaxation, history)
+  const bool track = kt && last && !enth;   // the Picard change of this step is kept
   if (kt) {
     // the first sweep evaluates at u^n (backward Euler) or 2 u^n - u^{n-1} (BDF2 with a history), before the right-hand side's
     // pass moves the state buffers
@@ -901,6 +909,8 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
     if (ctx->sys.precond == 1 && ctx->sys.amg_ready) ctx->sys.amg_fine_stale = true;
     if (track && sweeps == 1)
       hipLaunchKernelGGL(k_eval_state, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u, um1, ctx->kt.pic);
+    if (enth && sweeps == 1)   // (one sweep: u^n is needed for the change alone)
+      HF_HIP(hipMemcpyAsync(ctx->kt.pic, ctx->d_u, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
     if (ct && sweeps > 1)   // the vector M multiplies, for the sweeps that form the right-hand side again
       hipLaunchKernelGGL(k_picard_w, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u,
                          bdf2 ? (ctx->bdf_hist ? ctx->d_uprev : ctx->d_u) : nullptr, ctx->kt.w);
@@ -968,7 +978,56 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
       hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->sys.bc_dofs, g, ctx->d_b, ctx->d_u);
   }
   int rc = solve_with_fallback(ctx, ctx->sys, LinSys{ctx->sys.A, ctx->sys.dinv, ctx->d_u, ctx->d_b}, rtol, atol, max_it);
-  if (kt) {
+  if (enth) {
+    // The enthalpy form's sweeps 2..P.  e_0 = u^n; after sweep k: change_k = max |x_k - e_{k-1}| - formed when a
+    // tolerance is set or the sweep is the last - stop at change_k <= tol or k = P, else e_k = e_{k-1} + relax (x_k - e_{k-1}) and
+    // M_{k+1}, A_{k+1} from (u^n, e_k).  u^n: kt.w, kept before sweep 1's pass moved the buffers (P > 1); with P = 1 only the
+    // change needs it, and it is the copy in kt.pic.  The word of the step's last change is its entry of the history.
+    hf_ctx::KappaT& K = ctx->kt;
+    const double* un = sweeps > 1 ? K.w : K.pic;
+    if (static_cast<int64_t>(K.hsweeps.size()) >= K.hcap) return fail(ctx, HF_ERR_STATE, "enthalpy step: no room in the Picard history");
+    unsigned long long* word = K.hchange + K.hsweeps.size();
+    int total = ctx->h_scal->iters, used = 1;
+    for (int k = 1; rc == HF_OK; ++k) {
+      used = k;
+      const double* e = k == 1 ? un : K.e;
+      const bool end = k == sweeps;
+      if (K.tol > 0.0 || end) {
+        HF_HIP(hipMemsetAsync(word, 0, sizeof(unsigned long long), ctx->stream));
+        hipLaunchKernelGGL(k_max_abs_diff, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u, e, word);
+      }
+      if (end) break;
+      if (K.tol > 0.0) {   // the stop rule: the word of this sweep (the solve has synchronised already; this waits for one reduction)
+        unsigned long long bits = 0;
+        HF_HIP(copy_sync(ctx, &bits, word, sizeof bits, hipMemcpyDeviceToHost));
+        double change;
+        std::memcpy(&change, &bits, sizeof bits);
+        if (change <= K.tol) break;
+      }
+      if (K.relax < 1.0)
+        hipLaunchKernelGGL(k_relax, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, e, ctx->d_u, K.relax, K.e);
+      else
+        HF_HIP(hipMemcpyAsync(K.e, ctx->d_u, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
+      HF_TRY(kt_revalue(ctx, K.e, nullptr, un));
+      if (L.F)   // b = M_k u^n + dt F with the M of this sweep
+        launch_spmv<10>(ctx, ctx->d_M, un, ctx->d_b, nullptr, nullptr, nullptr, nullptr, nullptr, L.w, L.F);
+      else
+        launch_spmv<0>(ctx, ctx->d_M, un, ctx->d_b);
+      if (nb > 0) {
+        if (ctx->sys.nlift_rows > 0)
+          hipLaunchKernelGGL(k_lift, dim3((ctx->sys.nlift_rows + 255) / 256), dim3(256), 0, ctx->stream, ctx->sys.nlift_rows,
+                             ctx->sys.lift_rows, ctx->sys.lift_ptr, ctx->sys.lift_bc, ctx->sys.lift_val, g, ctx->d_b);
+        hipLaunchKernelGGL(k_set_bc, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, nb, ctx->sys.bc_dofs, g, ctx->d_b, ctx->d_u);
+      }
+      rc = solve_with_fallback(ctx, ctx->sys, LinSys{ctx->sys.A, ctx->sys.dinv, ctx->d_u, ctx->d_b}, rtol, atol, max_it);
+      total += ctx->h_scal->iters;
+    }
+    ctx->h_scal->iters = total;
+    if (rc == HF_OK) {
+      K.hsweeps.push_back(used);
+      K.have_change = true;
+    }
+  } else if (kt) {
     // Picard sweeps 2..p: re-evaluate at the latest iterate, lift with the new operator and solve again from that iterate
     int total = ctx->h_scal->iters;
     for (int k = 2; k <= sweeps && rc == HF_OK; ++k) {

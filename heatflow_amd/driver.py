@@ -28,6 +28,7 @@ import os
 import sys
 import threading
 import time
+import warnings
 
 import numpy as np
 import yaml
@@ -44,7 +45,8 @@ from .geometry import check_thickness_name, stack_no_diamond, stack_with_diamond
 from .heating import HeatingCurve
 from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, aniso_tables, capacity_scale, check_capacity_names, check_config, refuse_aniso,
                     refuse_aniso_tables, split_param)
-from .kappa_t import (check_sweep_tables, check_table_tangents, material_cv_table, material_table, picard_sweeps, refuse_tables,
+from .kappa_t import (capacity_form, check_capacity_form, check_sweep_tables, check_table_tangents, material_cv_table, picard_control,
+                      refuse_enthalpy, material_table, picard_sweeps, refuse_tables,
                       refuse_tables_unless_swept, sweep_tables, table_keys, table_param,
                       table_tangents)
 from .mesh import Mesh, load_mesh_arrays
@@ -301,7 +303,14 @@ class SimulationSession:
         tables = {self.material_tags[m.name]: m.properties["k_table"] for m in stack.materials if "k_table" in m.properties}
         ctables = {self.material_tags[m.name]: m.properties["rho_cv_table"] for m in stack.materials
                    if "rho_cv_table" in m.properties}
-        return (tables, picard_sweeps(cfg), ctables) if tables or ctables else None
+        if not (tables or ctables):
+            check_capacity_form(cfg)
+            return None
+        form = {}
+        if check_capacity_form(cfg) == "enthalpy":     # (absent / lagged: HeatProblem sees the arguments of before)
+            tol, relax = picard_control(cfg)
+            form = {"capacity_form": "enthalpy", "picard_tol": tol, "picard_relax": relax}
+        return tables, picard_sweeps(cfg), ctables, form
 
     def _boundary_conditions(self, cfg, stack, two_sided=False):
         """[left, right, top, heated line(s)] of one configuration (reference run_with_diamond.py:343-374).  With a volumetric
@@ -351,6 +360,8 @@ class SimulationSession:
             key += (tuple((t, float(v[0]), float(v[1]), tuple(float(x) for x in v[2])) for t, v in sorted(kt[0].items())), kt[1])
             if kt[2]:
                 key += (tuple((t, float(v[0]), float(v[1]), tuple(float(x) for x in v[2])) for t, v in sorted(kt[2].items())),)
+            if len(kt) > 3 and kt[3]:
+                key += (("capacity_form",) + tuple(sorted(kt[3].items(), key=lambda q: q[0])),)
         if an:
             key += (("k_aniso",) + tuple(sorted(an.items())),)
         if src:
@@ -376,6 +387,7 @@ class SimulationSession:
                                        amg_reuse=True, pattern=self.pattern, amg=shared["blob"] if shared else None,
                                        scheme=scheme, **({"kappa_tables": kt[0], "picard": kt[1]} if kt else {}),
                                        **({"rhoc_tables": kt[2]} if kt and kt[2] else {}),
+                                       **(kt[3] if kt and len(kt) > 3 else {}),
                                        **({"k_aniso": an} if an else {}), **({"source": src} if src else {}),
                                        **({"monitors": mon} if mon else {}), **({"aniso_tables": True} if ant else {}))
             self._key = key
@@ -436,6 +448,7 @@ class SimulationSession:
         column at its own temperatures (hf_set_batch_tables, hf_batch_set_column_kappa)."""
         nv = len(cfgs)
         for c in cfgs:
+            refuse_enthalpy(c, "run_batch (the batched loop)")
             check_sweep_tables(c, "run_batch (the batched loop)")
             refuse_tables_unless_swept(c, "run_batch (the batched loop)")
             refuse_source_sweeps(c, "run_batch (the batched loop)")
@@ -658,7 +671,10 @@ class SimulationSession:
         varying = bcs[3:]
         tag_to_k, tag_to_rc = self._tables(stack)
         scheme = time_scheme(cfg)
+        if tangents:
+            refuse_enthalpy(cfg, "monitor_sigma=" if monitor_sigma is not None else "tangents=")
         kt = self._kappa_tables(cfg, stack)
+        enth = kt is not None and bool(kt[3])        # timing.capacity_form: enthalpy
         if tangents:             # both kinds: timing.aniso_tables covers the forward run only, with timing.table_tangents too
             refuse_aniso_tables(cfg, "monitor_sigma" if monitor_sigma is not None else "tangents")
         tab_on = kt is not None and bool(tangents) and table_tangents(cfg)   # timing.table_tangents
@@ -694,6 +710,12 @@ class SimulationSession:
         prob = self.problem
         if mon and not fresh:    # the records of this run only
             prob.clear_monitor_history()
+        if enth:                 # the sweeps and changes of this run only; with monitors the stored heat per step, for `energy`
+            if not fresh:
+                prob.clear_picard_history()
+            if mon:
+                prob.clear_heat_history()
+                prob.record_heat()
         amp = None
         if spec is not None:     # W -> W/m^3 per step, from the discrete source's own integral
             if self._source_F1 is None:
@@ -814,13 +836,32 @@ class SimulationSession:
         loop_time = time.time() - t_loop
         print(f"Simulation progress: 100% (step {num_steps}/{num_steps}) | Avg time/step: {loop_time / num_steps:.4f} s"
               f" | PCG iterations/step: mean {np.mean(iters):.0f}, max {int(np.max(iters))}")
+        mon_out, picard_out = None, {}
+        if mon:
+            mon_out = prob.monitor_history()
+            if enth:             # every region's energy from the heat records: the stored heat the scheme conserves, tabled tags included
+                heat = prob.heat_history()
+                for region, r in mon.items():
+                    mon_out[region]["energy"] = sum(heat[int(t)] for t in r["tags"])
+        if enth:
+            hist = prob.picard_history()
+            picard_out = {"picard": {"sweeps": np.asarray(hist["sweeps"]), "change": np.asarray(hist["change"])}}
+            tol = kt[3]["picard_tol"]
+            if tol:
+                late = np.flatnonzero((picard_out["picard"]["sweeps"] >= kt[1]) & (picard_out["picard"]["change"] > tol))
+                if late.size:
+                    warnings.warn(f"timing.picard_sweeps = {kt[1]}: step {int(late[0]) + 1} ended at the cap with a Picard change of "
+                                  f"{picard_out['picard']['change'][late[0]]:.3g} K > timing.picard_tol = {tol:g} K "
+                                  f"({late.size} such step(s); more sweeps or timing.picard_relax < 1 may help)", RuntimeWarning,
+                                  stacklevel=2)
         return {
             "times": np.asarray(times), "watcher_names": names,
             "watchers": {nm: samples[:, k] for k, nm in enumerate(names)},
             "iters": np.asarray(iters), "loop_time": loop_time, "startup_time": t_loop - t_start,
             "n_dof": prob.n, "dt": dt, "flux": flux,
             **({"tangents": tangent_out, "tangent_iters": titers} if tangent_out is not None else {}),
-            **({"monitors": prob.monitor_history()} if mon else {}),
+            **({"monitors": mon_out} if mon else {}),
+            **picard_out,
             **extra,
         }
 

@@ -23,7 +23,7 @@ from .geometry import check_thickness_name, thickness_velocity
 from .parameter_sweep import build_stack, get_watcher_points, oside_curves
 from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, KEY, capacity_scale, check_capacity_names, material_aniso, refuse_aniso,
                     refuse_aniso_tables, split_param)
-from .kappa_t import (check_table_tangents, get_table_param, refuse_tables, set_table_param, split_table_param, table_keys,
+from .kappa_t import (check_table_tangents, refuse_enthalpy, get_table_param, refuse_tables, set_table_param, split_table_param, table_keys,
                       table_tangents)
 from .source import SOURCE_PARAMS, check_source_param, parse_source, refuse_source_tangents
 from .monitors import refuse_monitors
@@ -172,6 +172,7 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
 
     t0 = time.time()
     scheme = time_scheme(cfg)
+    refuse_enthalpy(cfg, "heatflow_amd.fit")
     refuse_aniso_tables(cfg, "heatflow_amd.fit")     # both kinds: forward runs only, with timing.table_tangents too
     tab_on = table_tangents(cfg) and bool(table_keys(cfg))      # timing.table_tangents
     if tab_on:

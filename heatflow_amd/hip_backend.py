@@ -29,6 +29,8 @@ def time_scheme_code(name):
         raise ValueError(f"unknown time scheme {name!r} (expected one of {sorted(TIME_SCHEMES)})")
     return TIME_SCHEMES[name]
 
+CAPACITY_FORMS = {"lagged": 0, "enthalpy": 1}     # hf_set_capacity_form
+
 EXPORTS = [
     "hf_version", "hf_create", "hf_destroy", "hf_last_error", "hf_set_mesh", "hf_set_mesh_prebuilt", "hf_pattern_export_size",
     "hf_pattern_export", "hf_amg_export_size", "hf_amg_export", "hf_amg_install", "hf_set_materials",
@@ -43,7 +45,9 @@ EXPORTS = [
     "hf_source_derivatives", "hf_get_source_derivative", "hf_tangent_set_source",
     "hf_set_monitors", "hf_monitor_now", "hf_monitor_count", "hf_get_monitors", "hf_monitor_clear",
     "hf_set_monitor_tangents", "hf_monitor_tangent_count", "hf_get_monitor_tangents", "hf_monitor_tangent_eval",
-    "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_set_shape", "hf_tangent_set_capacity", "hf_table_derivatives", "hf_tangent_set_tables", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard", "hf_set_anisotropy", "hf_set_aniso_tables", "hf_get_sizes", "hf_get_csr", "hf_spmv",
+    "hf_tangent_setup", "hf_tangent_setup_dir", "hf_tangent_set_shape", "hf_tangent_set_capacity", "hf_table_derivatives", "hf_tangent_set_tables", "hf_tangent_load", "hf_run_tangent", "hf_get_tangent", "hf_set_kappa_tables", "hf_get_picard_change", "hf_set_rhoc_tables", "hf_set_picard",
+    "hf_set_capacity_form", "hf_set_picard_control", "hf_get_picard_history", "hf_clear_picard_history", "hf_enthalpy_revalue",
+    "hf_stored_heat", "hf_set_heat_records", "hf_heat_count", "hf_get_heat", "hf_clear_heat_records", "hf_set_anisotropy", "hf_set_aniso_tables", "hf_get_sizes", "hf_get_csr", "hf_spmv",
     "hf_set_value_lists", "hf_get_value_lists", "hf_get_projection", "hf_get_flux_system",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
 ]
@@ -184,6 +188,16 @@ def load_library():
         "hf_get_picard_change": [vp, pd],
         "hf_set_rhoc_tables": [vp, i32, pi, pd, pd, pi, pd],
         "hf_set_picard": [vp, i32],
+        "hf_set_capacity_form": [vp, i32],
+        "hf_set_picard_control": [vp, dbl, dbl, i32],
+        "hf_get_picard_history": [vp, pi, pd, i32, pi],
+        "hf_clear_picard_history": [vp],
+        "hf_enthalpy_revalue": [vp, pd, pd],
+        "hf_stored_heat": [vp, dbl, pd],
+        "hf_set_heat_records": [vp, i32, dbl],
+        "hf_heat_count": [vp, pi],
+        "hf_get_heat": [vp, i32, i32, pd],
+        "hf_clear_heat_records": [vp],
         "hf_set_anisotropy": [vp, i32, pi, pd, pd],
         "hf_set_aniso_tables": [vp, i32],
         "hf_get_sizes": [vp, pi, pi, C.POINTER(i64), pi],
@@ -646,6 +660,64 @@ class HeatflowHIP:
         d = C.c_double()
         self._check(self._lib.hf_get_picard_change(self._ctx, C.byref(d)))
         return float(d.value)
+
+    # -- the enthalpy form of the capacity and the stored heat ---------------------------
+    def set_capacity_form(self, form):
+        """``form`` = "lagged" (the default) or "enthalpy" (hf_set_capacity_form): energy-conserving steps under capacity
+        tables, backward Euler only.  Invalidates the assembly: set the state, then assemble()."""
+        if form not in CAPACITY_FORMS:
+            raise ValueError(f"set_capacity_form: unknown form {form!r} (expected one of {sorted(CAPACITY_FORMS)})")
+        self._check(self._lib.hf_set_capacity_form(self._ctx, CAPACITY_FORMS[form]))
+
+    def set_picard_control(self, tol=0.0, relax=1.0, max_sweeps=8):
+        """Stop rule, relaxation and sweep cap (1..64) of the enthalpy form's iteration (hf_set_picard_control); ``tol`` = 0
+        runs every sweep."""
+        self._check(self._lib.hf_set_picard_control(self._ctx, float(tol), float(relax), int(max_sweeps)))
+
+    def picard_history(self):
+        """(sweeps, change): per step since the form was set or the history cleared, the sweeps used and the last change_k."""
+        n = C.c_int32()
+        self._check(self._lib.hf_get_picard_history(self._ctx, None, None, 0, C.byref(n)))
+        sweeps, change = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.float64)
+        if n.value:
+            self._check(self._lib.hf_get_picard_history(self._ctx, _pi(sweeps), _pd(change), n.value, C.byref(n)))
+        return sweeps, change
+
+    def clear_picard_history(self):
+        self._check(self._lib.hf_clear_picard_history(self._ctx))
+
+    def enthalpy_revalue(self, un, e):
+        """M and A (get_csr) as one sweep of the enthalpy form values them at the pair (u^n, e) - a test window."""
+        un, e = _f64(un), _f64(e)
+        if un.shape != (self.n,) or e.shape != (self.n,):
+            raise ValueError(f"enthalpy_revalue: two vectors of {self.n} values expected")
+        self._check(self._lib.hf_enthalpy_revalue(self._ctx, _pd(un), _pd(e)))
+
+    def stored_heat(self, T_ref):
+        """Per cell tag sum_e vol_e (H_tag(Tw_e(u)) - H_tag(T_ref)) of the current state, in J per radian (tab_len values;
+        hf_stored_heat)."""
+        out = np.zeros(self.tab_len, dtype=np.float64)
+        self._check(self._lib.hf_stored_heat(self._ctx, float(T_ref), _pd(out)))
+        return out
+
+    def set_heat_records(self, on, T_ref=0.0):
+        """One stored-heat record per step of step / run from now on, measured from ``T_ref`` (hf_set_heat_records)."""
+        self._check(self._lib.hf_set_heat_records(self._ctx, 1 if on else 0, float(T_ref)))
+
+    def heat_count(self):
+        n = C.c_int32()
+        self._check(self._lib.hf_heat_count(self._ctx, C.byref(n)))
+        return int(n.value)
+
+    def get_heat(self, first=0, count=None):
+        """Heat records [first, first + count) (count None: to the last), an array (count, tab_len)."""
+        count = self.heat_count() - int(first) if count is None else int(count)
+        out = np.zeros((max(count, 0), self.tab_len), dtype=np.float64)
+        self._check(self._lib.hf_get_heat(self._ctx, int(first), count, _pd(out) if out.size else None))
+        return out
+
+    def clear_heat_records(self):
+        self._check(self._lib.hf_clear_heat_records(self._ctx))
 
     # -- batched time loop: nv sweep points as the columns of one multi-vector PCG ------------------
     def batch_begin(self, nv, per_column_operator=False):

@@ -9,8 +9,14 @@ and, besides its constant ``cv``:
   ``cv_table: {T_min, T_max, cv: [...]}``               values of cv on a uniform grid; the table handed down is rho * cv
   ``cv_einstein: {theta, T_ref, T_min, T_max[, knots]}`` rho cv E(theta / T) / E(theta / T_ref), E(x) = x^2 e^x / (e^x - 1)^2 (an
                                                         Einstein solid), with the material's ``cv`` as the value at T_ref
+and a latent heat (needs ``timing.capacity_form: enthalpy``):
+  ``latent: {T_melt, heat, width[, T_min, T_max, knots]}`` a hat of base ``width`` centred at T_melt added to the material's rho * cv
+                                                        table, carrying rho * heat (heat in J/kg); alone on its own grid, next
+                                                        to cv_table / cv_einstein on theirs
 The table is what the library evaluates: piecewise linear, clamped to the end values outside [T_min, T_max].
-``timing.picard_sweeps`` (default 1) sets the Picard sweeps per step.
+``timing.picard_sweeps`` (default 1) sets the Picard sweeps per step.  ``timing.capacity_form: lagged | enthalpy`` (absent:
+lagged) chooses the form of the capacity; under the enthalpy form ``picard_sweeps`` is the sweep cap (1..64),
+``timing.picard_tol`` (K, optional, >= 0) the stop tolerance and ``timing.picard_relax`` (in (0, 1], default 1) the relaxation.
 """
 from __future__ import annotations
 
@@ -18,8 +24,11 @@ import numpy as np
 
 MAX_KNOTS = 256
 MAX_PICARD = 8
+MAX_SWEEPS = 64          # the sweep cap of the enthalpy form
 TABLE_KEYS = ("k_table", "k_power")
-CV_TABLE_KEYS = ("cv_table", "cv_einstein")
+CV_TABLE_KEYS = ("cv_table", "cv_einstein", "latent")
+FORM_KEY = "timing.capacity_form"
+SWEEP_SWITCH = "timing.sweep_tables"
 
 
 def power_law_table(k_ref, T_ref, exponent, T_min, T_max, knots=MAX_KNOTS):
@@ -81,8 +90,67 @@ def einstein_table(rho_cv_ref, theta, T_ref, T_min, T_max, knots=MAX_KNOTS):
     return T_min, dT, v
 
 
+def latent_hat(name, mat, T0, dT, knots):
+    """The values a ``latent`` block adds at the knots T0 + i dT: the hat of base ``width`` centred at ``T_melt``, sampled at the
+    knots and rescaled so that the trapezoid integral of the added part is rho * heat exactly - the table's own integral, which is
+    the H the enthalpy form conserves, then carries the configured latent heat.  ValueError for a hat with fewer than three knots
+    inside its support (naming ``width`` and the grid spacing) or outside the grid."""
+    b = mat["latent"]
+    unknown = sorted(set(b) - {"T_melt", "heat", "width", "T_min", "T_max", "knots"})
+    if unknown:
+        raise ValueError(f"mats.{name}.latent: unknown key {unknown[0]!r} (T_melt, heat, width, T_min, T_max, knots)")
+    for key in ("T_melt", "heat", "width"):
+        if key not in b:
+            raise ValueError(f"mats.{name}.latent: {key} is missing")
+    T_melt, heat, width, rho = float(b["T_melt"]), float(b["heat"]), float(b["width"]), float(mat["rho"])
+    if not (heat > 0.0 and width > 0.0 and rho > 0.0 and np.isfinite(heat) and np.isfinite(width) and np.isfinite(T_melt)):
+        raise ValueError(f"mats.{name}.latent: need heat > 0 (J/kg), width > 0 (K), a finite T_melt and rho > 0")
+    T = T0 + dT * np.arange(knots)
+    hat = np.maximum(0.0, 1.0 - np.abs(T - T_melt) / (0.5 * width))
+    inside = int(np.count_nonzero(hat > 0.0))
+    if T_melt - 0.5 * width < T[0] or T_melt + 0.5 * width > T[-1]:
+        raise ValueError(f"mats.{name}.latent: the hat {T_melt - 0.5 * width:g}..{T_melt + 0.5 * width:g} K leaves the table's grid "
+                         f"{T[0]:g}..{T[-1]:g} K")
+    if inside < 3:
+        raise ValueError(f"mats.{name}.latent: width = {width:g} K holds {inside} knot(s) of a grid with spacing {dT:g} K (at least "
+                         "three are needed inside the hat: widen it or refine the grid)")
+    area = float(np.sum(0.5 * (hat[1:] + hat[:-1]) * dT))
+    return hat * (rho * heat / area)
+
+
 def material_cv_table(name, mat):
-    """The (T0, dT, values of rho * cv) capacity table of one material entry of cfg["mats"], or None without a cv key."""
+    """The (T0, dT, values of rho * cv) capacity table of one material entry of cfg["mats"], or None without a cv key.  A
+    ``latent`` block adds its hat (latent_hat): alone on its own grid (T_min, T_max, knots; the base is the constant rho * cv),
+    next to cv_table / cv_einstein on theirs (then T_min / T_max / knots in the block are a ValueError)."""
+    if "latent" in mat:
+        base = _material_cv_base(name, mat)
+        b = mat["latent"]
+        if not isinstance(b, dict):
+            raise ValueError(f"mats.{name}.latent: a block {{T_melt, heat, width, ...}} expected")
+        if base is not None:
+            own = [k for k in ("T_min", "T_max", "knots") if k in b]
+            other = "cv_table" if "cv_table" in mat else "cv_einstein"
+            if own:
+                raise ValueError(f"mats.{name}.latent.{own[0]} together with mats.{name}.{other} is not supported (the hat is sampled "
+                                 f"on the grid of {other})")
+            T0, dT, v = base
+        else:
+            for key in ("T_min", "T_max"):
+                if key not in b:
+                    raise ValueError(f"mats.{name}.latent: {key} is missing (the block's own grid; or give cv_table / cv_einstein)")
+            knots = int(b.get("knots", MAX_KNOTS))
+            if not 3 <= knots <= MAX_KNOTS:
+                raise ValueError(f"mats.{name}.latent: knots must be 3..{MAX_KNOTS} (got {knots})")
+            T0, T1, rc = float(b["T_min"]), float(b["T_max"]), float(mat["rho"]) * float(mat["cv"])
+            if not T1 > T0 or not rc > 0.0:
+                raise ValueError(f"mats.{name}.latent: need T_max > T_min and rho cv > 0")
+            dT, v = (T1 - T0) / (knots - 1), np.full(knots, rc)
+        return T0, dT, np.asarray(v, dtype=np.float64) + latent_hat(name, mat, T0, dT, len(v))
+    return _material_cv_base(name, mat)
+
+
+def _material_cv_base(name, mat):
+    """material_cv_table without the ``latent`` block."""
     if "cv_table" in mat and "cv_einstein" in mat:
         raise ValueError(f"mats.{name}: cv_table and cv_einstein are exclusive")
     if "cv_table" in mat:
@@ -102,11 +170,96 @@ def material_cv_table(name, mat):
 
 
 def picard_sweeps(cfg):
-    """``timing.picard_sweeps`` (default 1), checked against 1..8."""
-    p = int((cfg.get("timing") or {}).get("picard_sweeps", 1) or 1)
-    if not 1 <= p <= MAX_PICARD:
-        raise ValueError(f"timing.picard_sweeps must be 1..{MAX_PICARD} (got {p})")
+    """``timing.picard_sweeps`` (default 1), checked against 1..8; under ``timing.capacity_form: enthalpy`` the sweep cap, 1..64."""
+    raw = (cfg.get("timing") or {}).get("picard_sweeps", 1)
+    top = MAX_SWEEPS if capacity_form(cfg) == "enthalpy" else MAX_PICARD
+    p = int(raw or 1) if top == MAX_PICARD or raw is None else int(raw)      # (the lagged form reads 0 as absent, as it did)
+    if not 1 <= p <= top:
+        raise ValueError(f"timing.picard_sweeps must be 1..{top} (got {p})"
+                         + (f" under {FORM_KEY}: enthalpy" if top == MAX_SWEEPS else ""))
     return p
+
+
+def capacity_form(cfg):
+    """``timing.capacity_form``: "lagged" (also when absent) or "enthalpy"; ValueError naming the key for anything else."""
+    v = (cfg.get("timing") or {}).get("capacity_form", "lagged")
+    if v is None:
+        v = "lagged"
+    if v not in ("lagged", "enthalpy"):
+        raise ValueError(f"{FORM_KEY} must be lagged or enthalpy, got {v!r}")
+    return v
+
+
+def picard_control(cfg):
+    """(tol or None, relax) of ``timing.picard_tol`` (K, >= 0) and ``timing.picard_relax`` (in (0, 1], default 1): ValueError
+    naming the key for a value outside, and naming both keys for either one without ``timing.capacity_form: enthalpy``."""
+    timing = cfg.get("timing") or {}
+    tol, relax = timing.get("picard_tol"), timing.get("picard_relax")
+    if capacity_form(cfg) != "enthalpy":
+        for key, v in (("picard_tol", tol), ("picard_relax", relax)):
+            if v is not None:
+                raise ValueError(f"timing.{key} needs {FORM_KEY}: enthalpy (the lagged form takes a fixed number of sweeps)")
+        return None, 1.0
+    if tol is not None:
+        try:
+            tol = float(tol)
+        except (TypeError, ValueError):
+            raise ValueError(f"timing.picard_tol must be a tolerance >= 0 in K, got {tol!r}") from None
+        if not (tol >= 0.0 and np.isfinite(tol)):
+            raise ValueError(f"timing.picard_tol must be a tolerance >= 0 in K, got {tol!r}")
+    try:
+        relax = 1.0 if relax is None else float(relax)
+    except (TypeError, ValueError):
+        raise ValueError(f"timing.picard_relax must be in (0, 1], got {relax!r}") from None
+    if not 0.0 < relax <= 1.0:
+        raise ValueError(f"timing.picard_relax must be in (0, 1], got {relax!r}")
+    return tol, relax
+
+
+def latent_keys(cfg):
+    return table_keys(cfg, ("latent",))
+
+
+def check_capacity_form(cfg):
+    """The combinations of the enthalpy form's keys a forward run refuses, each a ValueError naming both keys: ``latent`` without
+    ``timing.capacity_form: enthalpy``; the enthalpy form without a capacity table, with ``timing.scheme: bdf2``, a ``k_aniso``,
+    ``timing.sweep_tables`` or ``timing.table_tangents``.  Also checks the values of the form's own keys.  Returns the form."""
+    form = capacity_form(cfg)
+    lat = latent_keys(cfg)
+    if form != "enthalpy" and lat:
+        raise ValueError(f"{lat[0]} needs {FORM_KEY}: enthalpy (a step of the lagged form that jumps across the bump never sees it)")
+    picard_control(cfg)
+    picard_sweeps(cfg)
+    if form != "enthalpy":
+        return form
+    timing = cfg.get("timing") or {}
+    if not table_keys(cfg, CV_TABLE_KEYS):
+        raise ValueError(f"{FORM_KEY}: enthalpy needs a capacity table (mats.<name>.cv_table, cv_einstein or latent)")
+    if (timing.get("scheme") or "backward_euler") != "backward_euler":
+        raise ValueError(f"{FORM_KEY}: enthalpy together with timing.scheme: {timing.get('scheme')} is not supported (backward "
+                         "Euler only)")
+    aniso = [f"mats.{name}.k_aniso" for name, mat in sorted((cfg.get("mats") or {}).items()) if isinstance(mat, dict) and "k_aniso" in mat]
+    if aniso:
+        raise ValueError(f"{FORM_KEY}: enthalpy together with {aniso[0]} is not supported (also with timing.aniso_tables: the "
+                         "enthalpy kernel is isotropic)")
+    if timing.get("sweep_tables"):
+        raise ValueError(f"{FORM_KEY}: enthalpy together with {SWEEP_SWITCH} is not supported (the batch under tables takes the "
+                         "lagged form)")
+    if timing.get("table_tangents"):
+        raise ValueError(f"{FORM_KEY}: enthalpy together with timing.table_tangents is not supported (tangent runs take the lagged "
+                         "form)")
+    return form
+
+
+def refuse_enthalpy(cfg, where):
+    """ValueError naming the key and ``where`` if ``cfg`` asks for the enthalpy form (or a ``latent`` block): ``where`` - tangents=,
+    monitor_sigma=, heatflow_amd.fit, the sweeps, run_batch, the 1-D model - runs the lagged form only."""
+    if capacity_form(cfg) == "enthalpy":
+        raise ValueError(f"{where} together with {FORM_KEY}: enthalpy is not supported (it runs the lagged form only)")
+    lat = latent_keys(cfg)
+    if lat:
+        raise ValueError(f"{where} together with {lat[0]} is not supported ({lat[0]} needs {FORM_KEY}: enthalpy, which {where} does "
+                         "not run)")
 
 
 def table_keys(cfg, keys=TABLE_KEYS + CV_TABLE_KEYS):
@@ -129,7 +282,6 @@ def refuse_tables(cfg, where):
         raise ValueError(f"{where} does not support temperature-dependent heat capacities ({', '.join(keys)})")
 
 
-SWEEP_SWITCH = "timing.sweep_tables"
 
 
 def sweep_tables(cfg):

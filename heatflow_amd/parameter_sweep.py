@@ -36,7 +36,7 @@ from .driver import (SimulationSession, build_pattern_blob, flush_mesh_writes, p
                      run_simulation_impl, time_scheme)
 from .geometry import build_stack, watcher_points as _watcher_points
 from .hip_backend import HipError, NotConverged
-from .kappa_t import check_sweep_tables, refuse_tables_unless_swept
+from .kappa_t import check_sweep_tables, refuse_enthalpy, refuse_tables_unless_swept
 from .source import refuse_source_sweeps
 from .monitors import refuse_monitors_sweeps
 
@@ -381,6 +381,7 @@ def run_parameter_sweep(base_config_path, output_dir, fwhm_range, k_range, width
     if scheme is not None:
         base_config.setdefault("timing", {})["scheme"] = scheme
     time_scheme(base_config)          # an unknown scheme raises before any work
+    refuse_enthalpy(base_config, "run_parameter_sweep")
     refuse_tables_unless_swept(base_config, "run_parameter_sweep")     # timing.sweep_tables: the batch re-values per column
     check_sweep_tables(base_config, "run_parameter_sweep", swept=("p_sample",))
     refuse_source_sweeps(base_config, "run_parameter_sweep")
@@ -518,6 +519,7 @@ def run_kappa_sweep(cfg, mesh_folder, k_values, output_dir, *, rebuild_mesh=Fals
     The time scheme is the configuration's ``timing.scheme`` (default backward Euler)."""
     rank, world = world_info()
     time_scheme(cfg)                  # an unknown scheme raises before any work
+    refuse_enthalpy(cfg, "run_kappa_sweep")
     refuse_tables_unless_swept(cfg, "run_kappa_sweep")
     check_sweep_tables(cfg, "run_kappa_sweep", swept=("p_sample",))
     refuse_source_sweeps(cfg, "run_kappa_sweep")

@@ -32,7 +32,7 @@ from .driver import _parse_watchers, _resolve, suppress_output, write_watcher_cs
 from .heating import HeatingCurve
 from .mesh import load_mesh_arrays
 from .aniso import refuse_aniso
-from .kappa_t import refuse_tables
+from .kappa_t import refuse_enthalpy, refuse_tables
 from .source import refuse_source
 from .monitors import refuse_monitors
 
@@ -97,6 +97,7 @@ def run_1d(cfg, mesh_folder_2d, mesh_folder_1d=None, rebuild_mesh=False, visuali
     scheme = (cfg.get("timing") or {}).get("scheme") or "backward_euler"
     if scheme != "backward_euler":
         raise ValueError(f"run_1d: timing.scheme {scheme!r} is not supported by the 1-D model (backward Euler only)")
+    refuse_enthalpy(cfg, "run_1d (the 1-D model)")
     refuse_tables(cfg, "run_1d (the 1-D model)")
     refuse_source(cfg, "run_1d (the 1-D model)")
     refuse_monitors(cfg, "run_1d (the 1-D model)")

@@ -54,7 +54,14 @@ class HeatProblem:
     rhoc_tables : {cell tag: (T0, dT, values of rho * cv)} - temperature-dependent heat capacities (hf_set_rhoc_tables, DESIGN.md
               3.10): every evaluation re-values M as well as A.  With or without kappa_tables; the same order (tables, state,
               assembly).  None / {}: constant capacities.
-    picard : Picard sweeps per step with tables (1..8; 1 = the lagged scheme)
+    picard : Picard sweeps per step with tables (1..8; 1 = the lagged scheme); under ``capacity_form="enthalpy"`` the sweep cap
+              (1..64)
+    capacity_form : "lagged" (default: rho_c at the element temperature of the last iterate; no extra call is
+              made) or "enthalpy" (hf_set_capacity_form): the chord capacity between u^n and the evaluation
+              state, so that a converged step conserves the stored heat of :meth:`stored_heat`.  Needs ``rhoc_tables``;
+              backward Euler only; not with ``k_aniso``; :meth:`run_tangent` and the batched sweeps are refused by the library.
+    picard_tol : enthalpy form: stop a step's sweeps at max |x_k - e_{k-1}| <= picard_tol (K); None / 0: all ``picard`` sweeps
+    picard_relax : enthalpy form: e_k = e_{k-1} + picard_relax (x_k - e_{k-1}), in (0, 1]
     k_aniso : {cell tag: (m_r, m_z)} - anisotropic conductivities (hf_set_anisotropy): the tag conducts with
               k_r = m_r k along r and k_z = m_z k along z.  Set right after the materials, before the first assembly.  Not
               together with kappa_tables / rhoc_tables (ValueError) unless ``aniso_tables``.  None / {}: isotropic, the call
@@ -77,7 +84,8 @@ class HeatProblem:
     def __init__(self, coords, tris, tags, tag_to_k, tag_to_rho_cv, dt, bcs, u0, *, backend=None, device_id=0,
                  assembly_mode=ASM_ROW_GATHER, rtol=DEFAULT_RTOL, atol=0.0, max_it=DEFAULT_MAX_IT,
                  precond=PC_JACOBI, amg_reuse=False, pattern=None, amg=None, scheme="backward_euler", kappa_tables=None,
-                 picard=1, rhoc_tables=None, k_aniso=None, source=None, monitors=None, aniso_tables=False):
+                 picard=1, rhoc_tables=None, k_aniso=None, source=None, monitors=None, aniso_tables=False,
+                 capacity_form="lagged", picard_tol=None, picard_relax=1.0):
         self.coords = np.ascontiguousarray(coords, dtype=np.float64)
         self.n = self.coords.shape[0]
         self.dt = float(dt)
@@ -94,6 +102,8 @@ class HeatProblem:
         if self.k_aniso and (self.kappa_tables or self.rhoc_tables) and not self.aniso_tables:
             raise ValueError("HeatProblem: k_aniso together with kappa_tables / rhoc_tables is not supported "
                              "(the table kernels are isotropic)")
+        self.capacity_form, self.picard_tol, self.picard_relax = check_capacity_form(
+            capacity_form, self.picard, picard_tol, picard_relax, scheme=scheme, rhoc_tables=self.rhoc_tables, k_aniso=self.k_aniso)
         self.source = check_source(source)
         # hf_source_derivatives has been called for the source (run_tangent's source=, source_derivative).  False is always safe:
         # the call is made again.  Code that sets the source on the backend directly leaves the library refusing, whatever this says.
@@ -134,10 +144,15 @@ class HeatProblem:
         u = np.full(self.n, float(u0)) if np.isscalar(u0) else np.asarray(u0, dtype=np.float64)
         if self.kappa_tables or self.rhoc_tables:   # tables: the operator (and the hierarchy built from it) is evaluated at u0
             if self.kappa_tables:
-                self.backend.set_kappa_tables(self.kappa_tables, self.picard)
+                # (under the enthalpy form the cap, which may exceed this call's 1..8, is set_picard_control's below)
+                self.backend.set_kappa_tables(self.kappa_tables, self.picard if self.capacity_form == "lagged" else 1)
             if self.rhoc_tables:
                 self.backend.set_rhoc_tables(self.rhoc_tables)
-                self.backend.set_picard(self.picard)
+                if self.capacity_form == "enthalpy":    # (lagged is every context's default: no extra call)
+                    self.backend.set_capacity_form("enthalpy")
+                    self.backend.set_picard_control(self.picard_tol or 0.0, self.picard_relax, self.picard)
+                else:
+                    self.backend.set_picard(self.picard)
             self.backend.set_state(u)
             self.backend.assemble(self.dt, self.assembly_mode)
         else:
@@ -160,6 +175,44 @@ class HeatProblem:
     def picard_change(self):
         """max |u^{n+1,p} - u^{n+1,p-1}| of the last step's last Picard sweep (with tables only)."""
         return self.backend.picard_change()
+
+    def picard_history(self):
+        """{"sweeps", "change"}: per step since the problem was made, the sweeps used and the last max |x_k - e_{k-1}| (enthalpy
+        form only)."""
+        if self.capacity_form != "enthalpy":
+            raise ValueError('picard_history: needs capacity_form="enthalpy"')
+        sweeps, change = self.backend.picard_history()
+        return {"sweeps": sweeps, "change": change}
+
+    def stored_heat(self, T_ref=None):
+        """{cell tag: the heat stored in the tag's cells above ``T_ref`` in J}: 2 pi sum_e vol_e (H_tag(Tw_e(u)) - H_tag(T_ref)),
+        scaled as the monitors' ``energy`` is (hf_stored_heat).  ``T_ref`` None: the scalar u0 of the problem.
+        With any tables or none, under both capacity forms."""
+        T_ref = self._heat_T_ref(T_ref)
+        rec = self.backend.stored_heat(T_ref)
+        return {int(t): 2.0 * np.pi * float(rec[int(t)]) for t in sorted(self._rho_c)}
+
+    def _heat_T_ref(self, T_ref):
+        if T_ref is None:
+            T_ref = self.monitor_T_ref
+        if T_ref is None:
+            raise ValueError("stored_heat: T_ref is needed (the problem's u0 is not a scalar)")
+        return float(T_ref)
+
+    def clear_picard_history(self):
+        self.backend.clear_picard_history()
+
+    def clear_heat_history(self):
+        self.backend.clear_heat_records()
+
+    def record_heat(self, on=True, T_ref=None):
+        """Keep one stored-heat record per step of :meth:`step` / :meth:`run` from now on (hf_set_heat_records)."""
+        self.backend.set_heat_records(bool(on), self._heat_T_ref(T_ref) if on else 0.0)
+
+    def heat_history(self, first=0, count=None):
+        """{cell tag: array}: the stored heat (J, as :meth:`stored_heat`) after every recorded step (:meth:`record_heat`)."""
+        rec = self.backend.get_heat(first, count)
+        return {int(t): 2.0 * np.pi * rec[:, int(t)] for t in sorted(self._rho_c)}
 
     def close(self):
         if self._own_backend:
@@ -535,6 +588,33 @@ def check_source(source):
     if not depth > 0.0:
         raise ValueError(f"source: depth must be positive (or inf for a uniform layer), got {depth!r}")
     return {"tags": tags, "fwhm": fwhm, "z0": z0, "depth": depth}
+
+
+def check_capacity_form(form, picard, picard_tol, picard_relax, *, scheme="backward_euler", rhoc_tables=None, k_aniso=None):
+    """(form, tol or None, relax) of HeatProblem's capacity_form / picard_tol / picard_relax; ValueError (naming the argument)
+    for an unknown form, the combinations the enthalpy form does not cover, a cap outside 1..64, a negative tolerance, a
+    relaxation outside (0, 1], and for a tolerance or relaxation under the lagged form - before any backend call."""
+    if form not in ("lagged", "enthalpy"):
+        raise ValueError(f"capacity_form: 'lagged' or 'enthalpy' expected, got {form!r}")
+    tol = None if picard_tol is None else float(picard_tol)
+    relax = float(picard_relax)
+    if form == "lagged":
+        if tol is not None or relax != 1.0:
+            raise ValueError('picard_tol / picard_relax need capacity_form="enthalpy" (the lagged form takes a fixed number of sweeps)')
+        return form, None, 1.0
+    if not rhoc_tables:
+        raise ValueError('capacity_form="enthalpy" needs rhoc_tables (it is the form of the tabled capacity)')
+    if scheme != "backward_euler":
+        raise ValueError(f'capacity_form="enthalpy" with scheme={scheme!r} is not supported (backward Euler only)')
+    if k_aniso:
+        raise ValueError('capacity_form="enthalpy" with k_aniso is not supported (the enthalpy kernel is isotropic)')
+    if not 1 <= int(picard) <= 64:
+        raise ValueError(f'picard: the sweep cap of capacity_form="enthalpy" is 1..64, got {picard!r}')
+    if tol is not None and not (tol >= 0.0 and np.isfinite(tol)):
+        raise ValueError(f"picard_tol: a tolerance >= 0 in K expected, got {picard_tol!r}")
+    if not (0.0 < relax <= 1.0):
+        raise ValueError(f"picard_relax: a factor in (0, 1] expected, got {picard_relax!r}")
+    return form, tol, relax
 
 
 def check_k_aniso(k_aniso):

@@ -689,7 +689,7 @@ int hf_get_picard_change(hf_ctx* ctx, double* max_du);
  * table of exactly the shape and evaluation of a conductivity table, taken at the same T_e of the same evaluation state u*.  A tag
  * may carry a capacity table, a conductivity table, both or neither; capacity tables work with no conductivity table set.
  *   model     the non-conservative form rho_c(T) dT/dt = div(k grad T) with the capacity lagged (p = 1) or iterated (p > 1); an
- *             enthalpy formulation is not attempted.
+ *             enthalpy form is hf_set_capacity_form's, below.
  *   step      x_0 = u*;  sweep k = 1..p:  M_k = M(rho_c(x_{k-1})),  A_k = M_k + dt' K(kappa(x_{k-1})),
  *             A_k x_k = M_k w (+ dt' F) - A_k[:, B] g on the free rows, (x_k)_B = g;  u^{n+1} = x_p.  w = u^n (BDF2:
  *             (4 u^n - u^{n-1}) / 3).  The right-hand side is formed again in every sweep, with the M of that sweep (one more pass
@@ -708,6 +708,59 @@ int hf_get_picard_change(hf_ctx* ctx, double* max_du);
 int hf_set_rhoc_tables(hf_ctx* ctx, int32_t n_tab, const int32_t* tags, const double* t0, const double* dT, const int32_t* n_knots,
                        const double* values);
 int hf_set_picard(hf_ctx* ctx, int32_t sweeps);
+
+/* The enthalpy form of the capacity: energy-conserving steps under capacity tables, backward Euler only.  Per
+ * step, with e the evaluation state, w the relaxation, tol the stop tolerance and P the sweep cap:
+ *     e_0 = u^n;  sweep k = 1, 2, ...:
+ *       Ta_e = Tw_e(u^n), Tb_e = Tw_e(e_{k-1}),  Tw_e(u) = sum_j (rs + r_j) u_j / (4 rs), rs = r_0 + r_1 + r_2 (the volume average)
+ *       rho_c_e = the mean of the tag's clamped capacity table over [Ta_e, Tb_e] (table(Ta_e) where they are equal; the constant
+ *                 of a tag without a capacity table);  kappa_e = table(T_e(e_{k-1})) at the plain-mean T_e, or the constant
+ *       M_k = M(rho_c), A_k = M_k + dt K(kappa);  A_k x_k = M_k u^n + dt F - A_k[:, B] g on the free rows, (x_k)_B = g  (PCG from x_{k-1})
+ *       change_k = max |x_k - e_{k-1}|;  stop when change_k <= tol or k = P;  e_k = e_{k-1} + w (x_k - e_{k-1})
+ *     u^{n+1} = x_k
+ * With E(u) = sum_e vol_e H_tag(Tw_e(u)), vol_e = A_e rs / 3 and H_tag the integral of the clamped table (rho_c T for a constant
+ * tag), E(x) - E(u) = sum over all rows of [M(chord capacity between u and x) (x - u)]_i holds to rounding, so a converged step
+ * conserves E; the defect of a stopped step is of the order of change_k.  One row-gather launch per evaluation
+ * (k_assemble_rows_hT: both states staged, no atomics, bitwise reproducible), then the elimination as under the lagged form.
+ * hf_set_capacity_form   HF_CAPACITY_LAGGED (the default: everything above this comment) or HF_CAPACITY_ENTHALPY.  A change
+ *        invalidates the assembly; the enthalpy form starts with tol = 0, w = 1 and the sweeps of hf_set_picard as P.
+ *        HF_ERR_STATE, the message naming the cause: no capacity table is set (which covers an assembly mode other than the row
+ *        gather: hf_set_rhoc_tables refuses that mode, and hf_assemble refuses another mode while the tables are set), BDF2 is the
+ *        scheme, a tag is anisotropic (also under hf_set_aniso_tables), a batch is open, a tangent is set up.  HF_ERR_ARG: an
+ *        unknown form; a mesh whose slab, two staged states and headers exceed the 160 KiB of LDS.  Under the enthalpy form
+ *        hf_set_time_scheme(HF_TIME_BDF2), hf_batch_begin, hf_tangent_setup / hf_tangent_setup_dir and hf_set_anisotropy with an
+ *        anisotropic tag are refused (HF_ERR_STATE).  Clearing the capacity tables returns the form to lagged.
+ * hf_set_picard_control  tol >= 0 in K (0: all max_sweeps run and nothing is read back between sweeps), 0 < relax <= 1,
+ *        1 <= max_sweeps <= 64 (HF_ERR_ARG outside); HF_ERR_STATE under the lagged form, whose hf_set_picard keeps 1..8.
+ * hf_get_picard_history  *n = the steps taken since the form was set or the history cleared; the first min(*n, cap) steps' sweeps
+ *        and last change_k go to `sweeps` and `change`.  hf_get_picard_change reports the last step's.  hf_clear_picard_history
+ *        empties it.
+ * hf_enthalpy_revalue    INTERNAL, for the tests only (like hf_get_flux_system: a window, not part of the interface a driver uses):
+ *        M and A (hf_get_csr) as one sweep's re-valuation leaves them at the pair (un, e) of host vectors, elimination included.
+ *        It overwrites the operators and the evaluation state and marks the fine multigrid level stale; the next step values its
+ *        own.  HF_ERR_STATE under the lagged form or before hf_assemble. */
+enum { HF_CAPACITY_LAGGED = 0, HF_CAPACITY_ENTHALPY = 1 };
+int hf_set_capacity_form(hf_ctx* ctx, int32_t form);
+int hf_set_picard_control(hf_ctx* ctx, double tol, double relax, int32_t max_sweeps);
+int hf_get_picard_history(hf_ctx* ctx, int32_t* sweeps, double* change, int32_t cap, int32_t* n);
+int hf_clear_picard_history(hf_ctx* ctx);
+int hf_enthalpy_revalue(hf_ctx* ctx, const double* un, const double* e);
+
+/* The stored heat: out[tag] = sum over the tag's elements of vol_e (H_tag(Tw_e(u)) - H_tag(T_ref)) for the
+ * current state, tab_len doubles (max cell tag + 1; 0 for a number that is no cell tag), in J per radian.  With any tables, or
+ * none, and under both forms.  One lane per triangle, k_monitor's schedule and reduction (k_stored_heat, k_stored_heat_final): no
+ * atomics, the bits depend on the mesh, the tables, T_ref and u only.  The records live in a buffer of their own; the monitor
+ * records are untouched.
+ * hf_stored_heat         on demand.  HF_ERR_STATE before hf_set_mesh / hf_set_materials, with a batch open, on a mesh without
+ *        row-gather lists.
+ * hf_set_heat_records    on = 1: one record per step of hf_step / hf_run from now on, measured from T_ref, queued on the stream as
+ *        the monitor record is; on = 0 stops (the records stay).  hf_heat_count, hf_get_heat (records [first, first + count),
+ *        count x tab_len doubles; HF_ERR_ARG outside the records kept), hf_clear_heat_records.  hf_set_mesh drops them. */
+int hf_stored_heat(hf_ctx* ctx, double T_ref, double* out);
+int hf_set_heat_records(hf_ctx* ctx, int32_t on, double T_ref);
+int hf_heat_count(hf_ctx* ctx, int32_t* n_records);
+int hf_get_heat(hf_ctx* ctx, int32_t first, int32_t count, double* out);
+int hf_clear_heat_records(hf_ctx* ctx);
 
 int hf_get_sizes(hf_ctx* ctx, int32_t* n, int32_t* n_e, int64_t* nnz, int32_t* n_bc);
 /* Any pointer may be NULL.  A is the matrix as it stands (eliminated when BCs are set). */
