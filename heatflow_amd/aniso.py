@@ -16,7 +16,8 @@ from __future__ import annotations
 
 import math
 
-from .kappa_t import CV_TABLE_KEYS, TABLE_KEYS, table_keys
+from .kappa_t import CV_TABLE_KEYS, TABLE_KEYS, split_table_param, table_keys
+from .source import SOURCE_PARAMS
 
 KEY = "k_aniso"
 SWITCH = "timing.aniso_tables"
@@ -89,6 +90,23 @@ def split_param(name):
         raise ValueError(f"parameter {name!r}: unknown suffix {suffix!r} (<material>.k, <material>.k_r, <material>.k_z or "
                          f"<material>.thickness)")
     return mat, PARAM_KINDS[suffix]
+
+
+def classify_param(name, tables=True):
+    """(kind, material) of a tangent / fit parameter by its spelling alone - the one grammar of tangents=, monitor_sigma=,
+    fit.get_param and fit.set_params: ("fwhm", None); ("source", None) for every "source.*" name (source.check_source_param tells
+    the source's own from a misspelt one); ("table", <m>) for a name of kappa_t.TABLE_PARAM_SUFFIXES (``tables`` False: such a
+    name is an unknown suffix, as in a run without tables); else the suffix as the kind, "k" | "k_r" | "k_z" | "thickness" | "rho_c"
+    | "cv" | "rho", "k" also for the bare "<m>".  :func:`split_param`'s ValueError for any other suffix.  Whether the material
+    exists, reads its thickness or carries the table is the caller's to check, against what it holds."""
+    if name == "fwhm":
+        return "fwhm", None
+    if name in SOURCE_PARAMS or name.startswith("source."):
+        return "source", None
+    if tables and split_table_param(name) is not None:
+        return "table", split_table_param(name)[0]
+    mat, _ = split_param(name)
+    return (name.rsplit(".", 1)[1] if "." in name else "k"), mat
 
 
 def aniso_keys(cfg, names=None):

@@ -19,9 +19,12 @@ sparsity pattern and mass matrix resident so a sweep re-values only what changed
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import copy
 import csv
+import dataclasses
+import functools
 import hashlib
 import json
 import os
@@ -43,9 +46,9 @@ def _dump_yaml(obj, f):
 from .bc import P1Space, RowDirichletBC
 from .geometry import check_thickness_name, stack_no_diamond, stack_with_diamond, thickness_velocity
 from .heating import HeatingCurve
-from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, aniso_tables, capacity_scale, check_capacity_names, check_config, refuse_aniso,
-                    refuse_aniso_tables, split_param)
-from .kappa_t import (capacity_form, check_capacity_form, check_sweep_tables, check_table_tangents, material_cv_table, picard_control,
+from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, PARAM_KINDS, aniso_tables, capacity_scale, check_capacity_names, check_config,
+                    classify_param, refuse_aniso, refuse_aniso_tables)
+from .kappa_t import (check_capacity_form, check_sweep_tables, check_table_tangents, material_cv_table, picard_control,
                       refuse_enthalpy, material_table, picard_sweeps, refuse_tables,
                       refuse_tables_unless_swept, sweep_tables, table_keys, table_param,
                       table_tangents)
@@ -193,22 +196,15 @@ def _with_scheme(cfg):
     src = parse_source(cfg)
     if src is not None:
         out["heating"] = dict(cfg["heating"], source=src.used_config())
-    tables = {}
-    for name, mat in sorted((cfg.get("mats") or {}).items()):
-        t = material_table(name, mat) if isinstance(mat, dict) else None
-        if t is not None:
-            tables[name] = {"T0": float(t[0]), "dT": float(t[1]), "k": [float(v) for v in t[2]]}
-    if tables:
-        out["timing"]["picard_sweeps"] = picard_sweeps(cfg)
-        out["kappa_tables"] = tables
-    ctables = {}
-    for name, mat in sorted((cfg.get("mats") or {}).items()):
-        t = material_cv_table(name, mat) if isinstance(mat, dict) else None
-        if t is not None:
-            ctables[name] = {"T0": float(t[0]), "dT": float(t[1]), "rho_cv": [float(v) for v in t[2]]}
-    if ctables:
-        out["timing"]["picard_sweeps"] = picard_sweeps(cfg)
-        out["rhoc_tables"] = ctables
+    for key, table_of, values in (("kappa_tables", material_table, "k"), ("rhoc_tables", material_cv_table, "rho_cv")):
+        tables = {}
+        for name, mat in sorted((cfg.get("mats") or {}).items()):
+            t = table_of(name, mat) if isinstance(mat, dict) else None
+            if t is not None:
+                tables[name] = {"T0": float(t[0]), "dT": float(t[1]), values: [float(v) for v in t[2]]}
+        if tables:
+            out["timing"]["picard_sweeps"] = picard_sweeps(cfg)
+            out[key] = tables
     return out
 
 
@@ -221,6 +217,76 @@ def build_pattern_blob(coords, tris, tags, device_id=0):
     with HeatflowHIP(device_id) as be:
         be.set_mesh(coords, tris, tags)
         return be.export_pattern()
+
+
+def _table_key(tables):
+    return tuple((t, float(v[0]), float(v[1]), tuple(float(x) for x in v[2])) for t, v in sorted(tables.items()))
+
+
+@dataclasses.dataclass(frozen=True, eq=False)
+class ProblemSpec:
+    """What a resident HeatProblem is made for, apart from the conductivities (which are re-valued in place): a session reuses its
+    problem exactly while :attr:`key` stays the same, and makes one with :meth:`problem_kwargs`.  Both derive from the same
+    fields, so a feature that adds a field is in the key as soon as it is in the keywords."""
+
+    dt: float
+    scheme: str
+    rho_c: dict                         # {cell tag: rho cv}
+    bcs: list                           # RowDirichletBC in application order
+    kappa_tables: dict = dataclasses.field(default_factory=dict)      # {cell tag: (T0, dT, values)}
+    rhoc_tables: dict = dataclasses.field(default_factory=dict)
+    picard: int = 1                     # sweeps per step (the cap under the enthalpy form); it counts only with tables
+    enthalpy: bool = False              # timing.capacity_form: enthalpy (DESIGN.md 3.24), with its tolerance and relaxation
+    picard_tol: float | None = None
+    picard_relax: float = 1.0
+    k_aniso: dict = dataclasses.field(default_factory=dict)           # {cell tag: (m_r, m_z)}
+    source: dict | None = None          # dict(tags, fwhm, z0, depth)
+    monitors: dict | None = None        # {region: {"tags", "above"}}
+    aniso_tables: bool = False          # timing.aniso_tables: the context's switch is set when the problem is made
+    batch_tables: bool = False          # timing.sweep_tables: run_batch sets the context's switch on the problem it opens its batch on
+
+    @property
+    def tabled(self):
+        return bool(self.kappa_tables or self.rhoc_tables)
+
+    @functools.cached_property
+    def key(self):
+        """Hashable; the resident problem is reusable only for exactly the same Dirichlet DOF sets, in the same order, time step,
+        capacities and scheme, and the same of every feature that is switched on.  Regions and source tags count in their given
+        order; ``batch_tables`` is in the key and not in the keywords (the batch sets that switch itself)."""
+        key = (self.dt, tuple(sorted(self.rho_c.items())),
+               tuple(hashlib.sha1(np.ascontiguousarray(b.row_dofs, dtype=np.int64).tobytes()).hexdigest() for b in self.bcs),
+               self.scheme)
+        if self.tabled:
+            key += (_table_key(self.kappa_tables), self.picard)
+            if self.rhoc_tables:
+                key += (_table_key(self.rhoc_tables),)
+            if self.enthalpy:
+                key += (("capacity_form", "enthalpy", self.picard_tol, self.picard_relax),)
+        if self.k_aniso:
+            key += (("k_aniso",) + tuple(sorted(self.k_aniso.items())),)
+        if self.source:
+            key += (("source", tuple(self.source["tags"]), self.source["fwhm"], self.source["z0"], self.source["depth"]),)
+        if self.monitors:
+            key += (("monitors",) + tuple((region, tuple(r["tags"]), r["above"]) for region, r in self.monitors.items()),)
+        for name in ("aniso_tables", "batch_tables"):
+            if getattr(self, name):
+                key += ((name,),)
+        return key
+
+    def problem_kwargs(self):
+        """HeatProblem's keywords after the positional (mesh, k, rho_c, dt, bcs, u0); a feature that is off adds none."""
+        kw = {"scheme": self.scheme}
+        if self.tabled:
+            kw.update(kappa_tables=self.kappa_tables, picard=self.picard)
+        if self.rhoc_tables:
+            kw["rhoc_tables"] = self.rhoc_tables
+        if self.enthalpy:
+            kw.update(capacity_form="enthalpy", picard_tol=self.picard_tol, picard_relax=self.picard_relax)
+        for name in ("k_aniso", "source", "monitors", "aniso_tables"):
+            if getattr(self, name):
+                kw[name] = getattr(self, name)
+        return kw
 
 
 class SimulationSession:
@@ -244,10 +310,9 @@ class SimulationSession:
         # conductivity it was built for}}; installed by the first problem this session creates instead of a host set-up
         self.hierarchy = hierarchy
         self.problem = None
-        self._key = None
+        self._spec = None          # the ProblemSpec of the resident problem
         self._source_F1 = None     # the resident problem's source vector, read back once per problem
         self._source_G = None      # its derivatives (G_f, G_d), read back once per problem by the first tangent run under it
-        self._tree = None
         self._space = None
         self._dof_cache = {}
 
@@ -265,27 +330,29 @@ class SimulationSession:
 
     def prepare(self, cfg, stack):
         """Create the resident problem for ``cfg`` (mesh tables, matrices, multigrid hierarchy) without running a step."""
-        num_steps = int(cfg["timing"]["num_steps"])
-        dt = float(cfg["timing"]["t_final"]) / num_steps
-        bcs = self._boundary_conditions(cfg, stack)
-        tag_to_k, tag_to_rc = self._tables(stack)
-        scheme = time_scheme(cfg)
-        kt = self._kappa_tables(cfg, stack)
-        an = self._aniso(stack)
-        src = self._source(cfg, stack)
-        mon = self._monitors(cfg)
-        ant = aniso_tables(cfg)
-        self._ensure_problem(self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an, src, mon, ant), tag_to_k, tag_to_rc, dt, bcs,
-                             float(cfg["heating"]["ic_temp"]), scheme, kt, an, src, mon, ant)
+        self._ensure_problem(self.spec(cfg, stack), self._tables(stack)[0], float(cfg["heating"]["ic_temp"]))
+
+    def spec(self, cfg, stack, two_sided=False, lagged_for=None):
+        """The :class:`ProblemSpec` of ``cfg`` on this session's mesh; ValueError for what a forward run of it refuses.
+        ``lagged_for`` names a request that runs the lagged capacity form only (tangents=): the enthalpy form is refused for it,
+        before the form's own keys are checked."""
+        shared = self._shared_spec(cfg, stack, two_sided)
+        if lagged_for:
+            refuse_enthalpy(cfg, lagged_for)
+        return dataclasses.replace(shared, **self._table_fields(cfg, stack), source=self._source(cfg, stack),
+                                   monitors=self._monitors(cfg), aniso_tables=aniso_tables(cfg))
+
+    def _shared_spec(self, cfg, stack, two_sided=False):
+        """The part of the spec the columns of a batch must share: time step, scheme, capacities, Dirichlet sets, anisotropy."""
+        dt = float(cfg["timing"]["t_final"]) / int(cfg["timing"]["num_steps"])
+        bcs = self._boundary_conditions(cfg, stack, two_sided)
+        aniso = {self.material_tags[m.name]: m.properties["k_aniso"] for m in stack.materials if "k_aniso" in m.properties}
+        return ProblemSpec(dt, time_scheme(cfg), self._tables(stack)[1], bcs, k_aniso=aniso)
 
     def _tables(self, stack):
         tag_to_k = {self.material_tags[m.name]: m.properties["k"] for m in stack.materials}
         tag_to_rc = {self.material_tags[m.name]: m.properties["rho_cv"] for m in stack.materials}
         return tag_to_k, tag_to_rc
-
-    def _aniso(self, stack):
-        """{cell tag: (m_r, m_z)} of the materials of ``stack`` with a ``k_aniso`` block ({}: an isotropic configuration)."""
-        return {self.material_tags[m.name]: m.properties["k_aniso"] for m in stack.materials if "k_aniso" in m.properties}
 
     def _source(self, cfg, stack):
         """dict(tags, fwhm, z0, depth) of a configuration with a ``heating.source`` block (HeatProblem's ``source=``), or None."""
@@ -297,20 +364,20 @@ class SimulationSession:
         spec = parse_monitors(cfg)
         return None if spec is None else problem_monitors(spec, self.material_tags)
 
-    def _kappa_tables(self, cfg, stack):
-        """(tables {tag: (T0, dT, values)}, Picard sweeps, capacity tables {tag: (T0, dT, values)}) of a kappa(T) / cv(T)
-        configuration, or None."""
+    def _table_fields(self, cfg, stack):
+        """The spec's fields of a kappa(T) / cv(T) configuration: the tables {tag: (T0, dT, values)}, the Picard sweeps and, under
+        timing.capacity_form: enthalpy, the form with its control; {} without tables."""
         tables = {self.material_tags[m.name]: m.properties["k_table"] for m in stack.materials if "k_table" in m.properties}
         ctables = {self.material_tags[m.name]: m.properties["rho_cv_table"] for m in stack.materials
                    if "rho_cv_table" in m.properties}
+        form = check_capacity_form(cfg)
         if not (tables or ctables):
-            check_capacity_form(cfg)
-            return None
-        form = {}
-        if check_capacity_form(cfg) == "enthalpy":     # (absent / lagged: HeatProblem sees the arguments of before)
+            return {}
+        fields = {"kappa_tables": tables, "rhoc_tables": ctables, "picard": picard_sweeps(cfg)}
+        if form == "enthalpy":     # (absent / lagged: HeatProblem sees the arguments of before)
             tol, relax = picard_control(cfg)
-            form = {"capacity_form": "enthalpy", "picard_tol": tol, "picard_relax": relax}
-        return tables, picard_sweeps(cfg), ctables, form
+            fields.update(enthalpy=True, picard_tol=tol, picard_relax=relax)
+        return fields
 
     def _boundary_conditions(self, cfg, stack, two_sided=False):
         """[left, right, top, heated line(s)] of one configuration (reference run_with_diamond.py:343-374).  With a volumetric
@@ -350,78 +417,52 @@ class SimulationSession:
             self._heats.append(heat_o)
         return bcs
 
-    def _problem_key(self, dt, tag_to_rc, bcs, scheme="backward_euler", kt=None, an=None, src=None, mon=None, ant=False, bt=False):
-        # the resident problem is reusable only for exactly the same Dirichlet DOF sets, in the same order, and time scheme
-        # (and kappa(T) tables and Picard sweeps, or anisotropy multipliers, when a configuration has them)
-        key = (dt, tuple(sorted(tag_to_rc.items())),
-               tuple(hashlib.sha1(np.ascontiguousarray(b.row_dofs, dtype=np.int64).tobytes()).hexdigest() for b in bcs),
-               scheme)
-        if kt is not None:
-            key += (tuple((t, float(v[0]), float(v[1]), tuple(float(x) for x in v[2])) for t, v in sorted(kt[0].items())), kt[1])
-            if kt[2]:
-                key += (tuple((t, float(v[0]), float(v[1]), tuple(float(x) for x in v[2])) for t, v in sorted(kt[2].items())),)
-            if len(kt) > 3 and kt[3]:
-                key += (("capacity_form",) + tuple(sorted(kt[3].items(), key=lambda q: q[0])),)
-        if an:
-            key += (("k_aniso",) + tuple(sorted(an.items())),)
-        if src:
-            key += (("source", tuple(src["tags"]), src["fwhm"], src["z0"], src["depth"]),)
-        if mon:
-            key += (("monitors",) + tuple((region, tuple(r["tags"]), r["above"]) for region, r in mon.items()),)
-        if ant:                  # timing.aniso_tables: the context's switch is set when the problem is made
-            key += (("aniso_tables",),)
-        if bt:                   # timing.sweep_tables: run_batch sets the context's switch on the problem it opens its batch on
-            key += (("sweep_tables",),)
-        return key
-
-    def _ensure_problem(self, key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme="backward_euler", kt=None, an=None, src=None,
-                        mon=None, ant=False):
-        """The resident HeatProblem for ``key`` (built if absent), its operator valued for ``tag_to_k``."""
-        if self.problem is None or key != self._key:
+    def _ensure_problem(self, spec, tag_to_k, ic_temp):
+        """The resident HeatProblem for ``spec`` (built if absent), its operator valued for ``tag_to_k``.  True if it was built."""
+        if self.problem is None or spec.key != self._spec.key:
             self.close()
             print("Assigning material properties...")
             shared = self.hierarchy if (self.hierarchy is not None and self.precond == 1) else None
-            self.problem = HeatProblem(self.coords, self.tris, self.tags, tag_to_k, tag_to_rc, dt, bcs, ic_temp,
+            self.problem = HeatProblem(self.coords, self.tris, self.tags, tag_to_k, spec.rho_c, spec.dt, spec.bcs, ic_temp,
                                        backend=self.backend, device_id=self.device_id, rtol=self.rtol,
                                        max_it=self.max_it, assembly_mode=self.assembly_mode, precond=self.precond,
                                        amg_reuse=True, pattern=self.pattern, amg=shared["blob"] if shared else None,
-                                       scheme=scheme, **({"kappa_tables": kt[0], "picard": kt[1]} if kt else {}),
-                                       **({"rhoc_tables": kt[2]} if kt and kt[2] else {}),
-                                       **(kt[3] if kt and len(kt) > 3 else {}),
-                                       **({"k_aniso": an} if an else {}), **({"source": src} if src else {}),
-                                       **({"monitors": mon} if mon else {}), **({"aniso_tables": True} if ant else {}))
-            self._key = key
+                                       **spec.problem_kwargs())
+            self._spec = spec
             self._source_F1 = None
             self._source_G = None
             self._k = dict(tag_to_k)
             # conductivities the multigrid levels were built for: this problem's, or those of the session that shared them
             self._k_hier = dict(shared["k"]) if shared else dict(tag_to_k)
             self.hierarchy = None                    # a later problem of this session (other dt / Dirichlet set) builds its own
-            if shared and set(self._k_hier) == set(tag_to_k):
-                drift = max(max(tag_to_k[t] / self._k_hier[t], self._k_hier[t] / tag_to_k[t]) for t in tag_to_k)
-                if drift > 2.0:                      # too far from this point's operator to be a good frozen hierarchy: rebuild
-                    self.problem.backend.set_precond(1, False)
-                    self.problem.set_materials(tag_to_k, tag_to_rc)
-                    self.problem.backend.set_precond(1, True)
-                    self._k_hier = dict(tag_to_k)
+            if shared and set(self._k_hier) == set(tag_to_k) and self._out_of_range(tag_to_k):
+                self._rebuild_hierarchy(tag_to_k)    # too far from this point's operator to be a good frozen hierarchy
             print("Material properties assigned.")
-            return
-        self.problem.bcs = bcs
+            return True
+        self.problem.bcs = spec.bcs
         if tag_to_k != self._k:
-            self._revalue(tag_to_k, tag_to_rc)
+            self._revalue(tag_to_k)
+        return False
 
-    def _revalue(self, tag_to_k, tag_to_rc, allow_rebuild=True):
-        # re-value A on the resident pattern; the frozen coarse levels stay a good preconditioner
-        # while no conductivity moved by more than 2x from the values they were built for
-        # (measured: 3.8 -> 60 W/m/K triples the iteration count), beyond that rebuild them
-        drift = max(max(tag_to_k[t] / self._k_hier[t], self._k_hier[t] / tag_to_k[t]) for t in tag_to_k)
-        if drift > 2.0 and self.precond == 1 and allow_rebuild:
-            self.problem.backend.set_precond(1, False)
-            self.problem.set_materials(tag_to_k, tag_to_rc)
-            self.problem.backend.set_precond(1, True)
-            self._k_hier = dict(tag_to_k)
+    def _out_of_range(self, *k_maps):
+        """The frozen coarse levels stay a good preconditioner while no conductivity moved by more than 2x from the values they
+        were built for (measured: 3.8 -> 60 W/m/K triples the iteration count): True if one of ``k_maps`` is beyond that."""
+        return max(max(k[t] / self._k_hier[t], self._k_hier[t] / k[t]) for k in k_maps for t in k) > 2.0
+
+    def _rebuild_hierarchy(self, tag_to_k):
+        """Re-value the resident operator for ``tag_to_k`` and build the multigrid levels from it."""
+        be = self.problem.backend
+        be.set_precond(1, False)
+        self.problem.set_materials(tag_to_k, self._spec.rho_c)
+        be.set_precond(1, True)
+        self._k_hier = dict(tag_to_k)
+
+    def _revalue(self, tag_to_k, allow_rebuild=True):
+        # re-value A on the resident pattern, and beyond the hierarchy's range rebuild it
+        if self._out_of_range(tag_to_k) and self.precond == 1 and allow_rebuild:
+            self._rebuild_hierarchy(tag_to_k)
         else:
-            self.problem.set_materials(tag_to_k, tag_to_rc)
+            self.problem.set_materials(tag_to_k, self._spec.rho_c)
         self._k = dict(tag_to_k)
 
     def _watcher_nodes(self, watcher_points):
@@ -431,31 +472,29 @@ class SimulationSession:
         from .solver import nearest_nodes
         return names, nearest_nodes(self.coords, coords_w)
 
-    def run_batch(self, cfgs, stacks, watcher_points=None, read_flux=False):
-        """``len(cfgs)`` in (2, 4, 8, 16) simulations of this mesh advanced together (hf_batch_*): the points of a
-        sweep that share geometry, time stepping and rho_c; they may differ in the boundary values (fwhm,
-        heating curve: one shared operator) and in the conductivities (one operator per column, shared
-        frozen multigrid hierarchy).  ``read_flux`` adds run_no_diamond's per-step gradient projection for every
-        column (hf_batch_run_flux).  Returns one result dict per configuration, as :meth:`run` does.
-        Under ``heating.source.sweeps: true`` the configurations may carry a ``heating.source`` block (DESIGN.md 3.21): they must
-        agree on its ``material`` list, ``face`` and ``keep_line`` and may differ in ``power``, the beam's ``fwhm``, ``depth`` and
-        ``pulse``; the batch gets a source of its own (hf_batch_set_source) with one amplitude column per configuration.  Under
-        ``timing.sweep_monitors: true`` they may carry a ``monitors`` block, the same in all of them; every result then has
-        ``monitors`` as :meth:`run` returns it.  A mismatch is a ValueError naming what differs.
-        Under ``timing.sweep_tables: true`` the configurations may carry kappa(T) / cv(T) keys (DESIGN.md 3.23): they must agree
-        on every table and on ``picard_sweeps: 1`` and may differ in the boundary values and in the constants of the materials
-        without a conductivity table; the batch opens with per-column operators that every step re-values on the GPU, each
-        column at its own temperatures (hf_set_batch_tables, hf_batch_set_column_kappa)."""
-        nv = len(cfgs)
+    def _flux_sampler(self, read_flux):
+        """A FluxSampler of this mesh with ``read_flux`` (else None), the resident problem's projection set up."""
+        if not read_flux:
+            return None
+        if not getattr(self.problem, "_flux_ready", False):
+            print("Setting up radial heat flux sampling...")
+            self.problem.backend.flux_setup()  # once per mesh: the unit-coefficient mass matrix does not depend on kappa
+            self.problem._flux_ready = True
+        return FluxSampler(self.coords)
+
+    def _check_batch(self, cfgs, stacks):
+        """What the configurations of a batch must not ask for and must share, apart from the problem's own spec; a mismatch is a
+        ValueError naming what differs.  Returns (their parsed sources, the absorbing face's z or None, the problem's monitors,
+        whether any of them carries tables)."""
         for c in cfgs:
             refuse_enthalpy(c, "run_batch (the batched loop)")
             check_sweep_tables(c, "run_batch (the batched loop)")
             refuse_tables_unless_swept(c, "run_batch (the batched loop)")
             refuse_source_sweeps(c, "run_batch (the batched loop)")
             refuse_monitors_sweeps(c, "run_batch (the batched loop)")
-        if nv not in (2, 4, 8, 16):
+        if len(cfgs) not in (2, 4, 8, 16):
             raise ValueError("run_batch: 2, 4, 8 or 16 configurations at a time")
-        specs = [parse_source(c) for c in cfgs]
+        specs, z0 = [parse_source(c) for c in cfgs], None
         if any(sp is not None for sp in specs):
             if any(sp is None for sp in specs):
                 raise ValueError("run_batch: some configurations have a heating.source block and some have none")
@@ -468,6 +507,7 @@ class SimulationSession:
             z0s = [sp.z0(st) for sp, st in zip(specs, stacks)]
             if any(z != z0s[0] for z in z0s):
                 raise ValueError(f"run_batch: the configurations must share the absorbing face's z (heating.source: z0 = {z0s!r})")
+            z0 = z0s[0]
         mon_specs = [parse_monitors(c) for c in cfgs]
         for j, m in enumerate(mon_specs):
             if m != mon_specs[0]:
@@ -490,55 +530,65 @@ class SimulationSession:
                     if t != per[0]:
                         raise ValueError(f"run_batch: the configurations must share every table under timing.sweep_tables: the tables "
                                          f"of material {nm} differ between configuration 0 and configuration {j}")
+        return specs, z0, mon, any(tabled)
+
+    def run_batch(self, cfgs, stacks, watcher_points=None, read_flux=False):
+        """``len(cfgs)`` in (2, 4, 8, 16) simulations of this mesh advanced together (hf_batch_*): the points of a
+        sweep that share geometry, time stepping and rho_c; they may differ in the boundary values (fwhm,
+        heating curve: one shared operator) and in the conductivities (one operator per column, shared
+        frozen multigrid hierarchy).  ``read_flux`` adds run_no_diamond's per-step gradient projection for every
+        column (hf_batch_run_flux).  Returns one result dict per configuration, as :meth:`run` does.
+        Under ``heating.source.sweeps: true`` the configurations may carry a ``heating.source`` block (DESIGN.md 3.21): they must
+        agree on its ``material`` list, ``face`` and ``keep_line`` and may differ in ``power``, the beam's ``fwhm``, ``depth`` and
+        ``pulse``; the batch gets a source of its own (hf_batch_set_source) with one amplitude column per configuration.  Under
+        ``timing.sweep_monitors: true`` they may carry a ``monitors`` block, the same in all of them; every result then has
+        ``monitors`` as :meth:`run` returns it.  A mismatch is a ValueError naming what differs.
+        Under ``timing.sweep_tables: true`` the configurations may carry kappa(T) / cv(T) keys (DESIGN.md 3.23): they must agree
+        on every table and on ``picard_sweeps: 1`` and may differ in the boundary values and in the constants of the materials
+        without a conductivity table; the batch opens with per-column operators that every step re-values on the GPU, each
+        column at its own temperatures (hf_set_batch_tables, hf_batch_set_column_kappa)."""
+        nv = len(cfgs)
+        sources, z0, mon, tabled = self._check_batch(cfgs, stacks)
         t_start = time.time()
-        cfg0 = cfgs[0]
-        num_steps = int(cfg0["timing"]["num_steps"])
-        dt = float(cfg0["timing"]["t_final"]) / num_steps
-        ic_temp = float(cfg0["heating"]["ic_temp"])
-        scheme = time_scheme(cfg0)
-        cols = []
+        num_steps = int(cfgs[0]["timing"]["num_steps"])
+        ic_temp = float(cfgs[0]["heating"]["ic_temp"])
+        cols = []                # (what the columns must share, conductivities) per column
         for cfg, stack in zip(cfgs, stacks):
-            bcs = self._boundary_conditions(cfg, stack)
-            tk, trc = self._tables(stack)
-            key = self._problem_key(float(cfg["timing"]["t_final"]) / int(cfg["timing"]["num_steps"]), trc, bcs, time_scheme(cfg),
-                                    None, self._aniso(stack))
-            cols.append((bcs, tk, trc, key))
-            if int(cfg["timing"]["num_steps"]) != num_steps or float(cfg["heating"]["ic_temp"]) != ic_temp or key != cols[0][3]:
+            cols.append((self._shared_spec(cfg, stack), self._tables(stack)[0]))
+            if int(cfg["timing"]["num_steps"]) != num_steps or float(cfg["heating"]["ic_temp"]) != ic_temp \
+                    or cols[-1][0].key != cols[0][0].key:
                 raise ValueError("run_batch: the configurations must share time stepping (and scheme), ic_temp, rho_c, the Dirichlet sets "
                                  "and the anisotropy multipliers (k_aniso)")
-        percol = any(c[1] != cols[0][1] for c in cols)
-        mid = cols[nv // 2]
+        percol = any(tk != cols[0][1] for _, tk in cols)
+        mid, mid_k = cols[nv // 2]
         # conductivities that differ between the columns; a single one (sweep_test.py's kappa_sample list) makes
         # the operators an affine family A + (kappa_j - kappa_ref) A1: two shared matrices instead of nv
-        varying = [t for t in mid[1] if any(c[1][t] != mid[1][t] for c in cols)]
+        varying = [t for t in mid_k if any(tk[t] != mid_k[t] for _, tk in cols)]
         affine = percol and len(varying) == 1
-        kt = self._kappa_tables(cfgs[nv // 2], stacks[nv // 2]) if any(tabled) else None
-        if kt is not None:       # under tables every column has its own operator, re-valued by the batch itself
-            percol, affine = True, False
         # the batch's problem carries the monitors' table and no source of its own (the batch gets one: hf_batch_begin refuses the
-        # context's); a resident problem that differs by its source alone (a single run before, or prepare) gives the source up
-        an_mid = self._aniso(stacks[nv // 2])
-        key = self._problem_key(dt, mid[2], mid[0], scheme, kt, an_mid, None, mon, False, kt is not None)
-        if specs[0] is not None and self.problem is not None and self.problem.source and \
-                self._key == self._problem_key(dt, mid[2], mid[0], scheme, None, an_mid, self.problem.source, mon):
+        # context's); under tables every column has its own operator, re-valued by the batch itself
+        fields = self._table_fields(cfgs[nv // 2], stacks[nv // 2]) if tabled else {}
+        spec = dataclasses.replace(mid, monitors=mon, batch_tables=bool(fields), **fields)
+        if spec.tabled:
+            percol, affine = True, False
+        # a resident problem that differs by its source alone (a single run before, or prepare) gives the source up
+        if sources[0] is not None and self.problem is not None and self.problem.source and \
+                self._spec.key == dataclasses.replace(spec, source=self.problem.source).key:
             self.problem.backend.set_source(None)
             self.problem.source = None
-            self._key, self._source_F1, self._source_G = key, None, None
-        self._ensure_problem(key, mid[1], mid[2], dt, mid[0], ic_temp, scheme, kt, an_mid, None, mon)
+            self._spec, self._source_F1, self._source_G = spec, None, None
+        self._ensure_problem(spec, mid_k, ic_temp)
         prob = self.problem
         be = prob.backend
-        if percol and self.precond == 1:             # all columns share the hierarchy: keep every column within its range
-            worst = max(max(max(c[1][t] / self._k_hier[t], self._k_hier[t] / c[1][t]) for t in c[1]) for c in cols)
-            if worst > 2.0:
-                be.set_precond(1, False)
-                prob.set_materials(mid[1], mid[2])
-                be.set_precond(1, True)
-                self._k_hier, self._k = dict(mid[1]), dict(mid[1])
-        times = (np.arange(num_steps) + 1) * dt
+        # all columns share the hierarchy: keep every column within its range
+        if percol and self.precond == 1 and self._out_of_range(*(tk for _, tk in cols)):
+            self._rebuild_hierarchy(mid_k)
+            self._k = dict(mid_k)
+        times = (np.arange(num_steps) + 1) * spec.dt
         g_all = np.empty((num_steps, len(prob.bc_dofs), nv), dtype=np.float64)
         tabulated = {}                                   # columns with the same boundary definition share one table
-        for j, (bcs, _, _, _) in enumerate(cols):
-            h = cfgs[j]["heating"]
+        for j, (col, _) in enumerate(cols):
+            bcs, h = col.bcs, cfgs[j]["heating"]
             if len(bcs) > 3:
                 sig = (str(h["file"]), float(h["ic_temp"]), float(h["fwhm"]), len(bcs))
             else:                                        # keep_line: false - the three outer edges only, no heating file
@@ -549,38 +599,34 @@ class SimulationSession:
                     bc.update(0.0)
                 tabulated[sig] = np.stack([prob.bc_values(t, bcs[3:]) for t in times])
             g_all[:, :, j] = tabulated[sig]
-        prob.bcs = cols[-1][0]
+        prob.bcs = cols[-1][0].bcs
         names, nodes = self._watcher_nodes(watcher_points)
-        if affine and mid[1] != self._k:
-            self._revalue(mid[1], mid[2], allow_rebuild=False)     # the context's operator is the reference of the family
-        flux0 = FluxSampler(self.coords) if read_flux else None
-        if flux0 is not None and not getattr(prob, "_flux_ready", False):
-            print("Setting up radial heat flux sampling...")
-            be.flux_setup()                    # once per mesh: the unit-coefficient mass matrix does not depend on kappa
-            prob._flux_ready = True
-        if kt is not None:
+        if affine and mid_k != self._k:
+            self._revalue(mid_k, allow_rebuild=False)     # the context's operator is the reference of the family
+        flux0 = self._flux_sampler(read_flux)
+        if spec.tabled:
             be.set_state(np.full(prob.n, ic_temp))       # (a resident problem may stand at the end of an earlier run)
             be.set_batch_tables(True)
         be.batch_begin(nv, per_column_operator=2 if affine else (1 if percol else 0))
         try:
-            if kt is not None:   # the constants of the materials without a conductivity table, column by column
-                free = sorted(t for t in mid[1] if t not in kt[0])
-                for j, (_, tk, _, _) in enumerate(cols):
+            if spec.tabled:      # the constants of the materials without a conductivity table, column by column
+                free = sorted(t for t in mid_k if t not in spec.kappa_tables)
+                for j, (_, tk) in enumerate(cols):
                     be.batch_set_column_kappa(j, free, [tk[t] for t in free])
             elif affine:
-                be.batch_set_affine(varying, [c[1][varying[0]] - mid[1][varying[0]] for c in cols])
+                be.batch_set_affine(varying, [tk[varying[0]] - mid_k[varying[0]] for _, tk in cols])
             elif percol:
-                for j, (_, tk, trc, _) in enumerate(cols):
+                for j, (_, tk) in enumerate(cols):
                     if tk != self._k:
-                        self._revalue(tk, trc, allow_rebuild=False)
+                        self._revalue(tk, allow_rebuild=False)
                     be.batch_load_column(j)
             for j in range(nv):
                 be.batch_set_state(j, np.full(prob.n, ic_temp))
-            if specs[0] is not None:     # the batch's own source; W -> W/m^3 per step and column, from each column's own integral
-                be.batch_set_source([int(self.material_tags[m]) for m in specs[0].materials], [sp.fwhm for sp in specs], z0s[0],
-                                    [sp.depth for sp in specs])
+            if sources[0] is not None:   # the batch's own source; W -> W/m^3 per step and column, from each column's own integral
+                be.batch_set_source([int(self.material_tags[m]) for m in sources[0].materials], [sp.fwhm for sp in sources], z0,
+                                    [sp.depth for sp in sources])
                 amp, vectors = np.empty((num_steps, nv), dtype=np.float64), {}
-                for j, sp in enumerate(specs):
+                for j, sp in enumerate(sources):
                     if (sp.fwhm, sp.depth) not in vectors:       # columns with the same (fwhm, depth) download once
                         vectors[(sp.fwhm, sp.depth)] = be.batch_get_source(j)
                     amp[:, j] = source_amplitudes(sp, times, vectors[(sp.fwhm, sp.depth)], _resolve)
@@ -609,7 +655,7 @@ class SimulationSession:
         return [{"times": times.copy(), "watcher_names": names,
                  "watchers": {nm: samples[:, j, k].copy() for k, nm in enumerate(names)},
                  "iters": iters[:, j].copy(), "loop_time": loop_time / nv, "startup_time": (t_loop - t_start) / nv,
-                 "n_dof": prob.n, "dt": dt, "flux": fluxes[j], "batch": nv,
+                 "n_dof": prob.n, "dt": spec.dt, "flux": fluxes[j], "batch": nv,
                  **({"monitors": prob._combine_monitors(records[:, j])} if mon else {})} for j in range(nv)]
 
     def run(self, cfg, stack, watcher_points=None, field_sink=None, read_flux=False, two_sided=False, tangents=None,
@@ -637,12 +683,73 @@ class SimulationSession:
         ones ``tangents`` accepts and the values from fit.get_param, implies those tangent columns and the derivatives and adds
         ``monitor_uncertainty`` {region: {field: sqrt(sum_q (d field / d theta_q sigma_q theta_q)^2) per step}}."""
         t_start = time.time()
+        tangents, monitor_tangents, sigma, source = self._check_request(cfg, tangents, monitor_tangents, monitor_sigma)
+        arg = "monitor_sigma" if monitor_sigma is not None else "tangents"
+        num_steps = int(cfg["timing"]["num_steps"])
+        ic_temp = float(cfg["heating"]["ic_temp"])
+        spec = self.spec(cfg, stack, two_sided, lagged_for=arg + "=" if tangents else None)
+        tab_on = bool(tangents) and self._check_tangent_request(cfg, spec, tangents, monitor_tangents, arg)
+        dt, varying, mon = spec.dt, spec.bcs[3:], spec.monitors
+        fresh = self._ensure_problem(spec, self._tables(stack)[0], ic_temp)
+        if not fresh:
+            self.problem.set_state(ic_temp)
+            self.problem.iters = []
+        prob = self.problem
+        if mon and not fresh:    # the records of this run only
+            prob.clear_monitor_history()
+        if spec.enthalpy:        # the sweeps and changes of this run only; with monitors the stored heat per step, for `energy`
+            if not fresh:
+                prob.clear_picard_history()
+            if mon:
+                prob.clear_heat_history()
+                prob.record_heat()
+        amp = None
+        if source is not None:   # W -> W/m^3 per step, from the discrete source's own integral
+            if self._source_F1 is None:
+                self._source_F1 = prob.source_vector()
+            amp = source_amplitudes(source, (np.arange(num_steps) + 1) * dt, self._source_F1, _resolve)
+        names, nodes = self._watcher_nodes(watcher_points)
+
+        flux = self._flux_sampler(read_flux)
+        print("Beginning loop...")
+        t_loop = time.time()
+        tangent_out, extra = {}, {}
+        if tangents:
+            if field_sink is not None or flux is not None:
+                raise ValueError("tangents: not combined with a field sink or the read-flux projection")
+            cols = self._tangent_columns(cfg, source, list(tangents), tab_on, monitor_tangents, (np.arange(num_steps) + 1) * dt, amp)
+            times, samples, tsamp, iters, titers = prob.run_tangent(num_steps, nodes, time_varying=varying, **cols.kwargs)
+            tangent_out, extra = self._tangent_results(cfg, list(tangents), names, tsamp, titers, cols.scale, monitor_tangents, sigma)
+        elif field_sink is None and flux is None:
+            times, samples, iters = prob.run(num_steps, watcher_nodes=nodes, time_varying=varying,
+                                             **({"source_amplitude": amp} if amp is not None else {}))
+        else:  # step-wise: every field goes to the sink (visualisation) and / or through the flux projection
+            times, samples, iters = self._run_stepwise(spec.bcs, num_steps, dt, amp, nodes, flux, field_sink)
+        loop_time = time.time() - t_loop
+        print(f"Simulation progress: 100% (step {num_steps}/{num_steps}) | Avg time/step: {loop_time / num_steps:.4f} s"
+              f" | PCG iterations/step: mean {np.mean(iters):.0f}, max {int(np.max(iters))}")
+        return {
+            "times": np.asarray(times), "watcher_names": names,
+            "watchers": {nm: samples[:, k] for k, nm in enumerate(names)},
+            "iters": np.asarray(iters), "loop_time": loop_time, "startup_time": t_loop - t_start,
+            "n_dof": prob.n, "dt": dt, "flux": flux,
+            **tangent_out,
+            **self._history_results(spec),
+            **extra,
+        }
+
+    # -- the steps of run(), each in the order run() takes them --------------------------------------------------------------------
+    def _check_request(self, cfg, tangents, monitor_tangents, monitor_sigma):
+        """What a run is asked for against the configuration alone, before any problem is made: (the tangent columns with those
+        ``monitor_sigma`` implies, whether the monitors' derivatives are wanted, the checked sigmas or None, the parsed source
+        or None); ValueError naming the argument or the parameter otherwise."""
+        sigma = None
         if monitor_tangents or monitor_sigma is not None:
             arg = "monitor_sigma" if monitor_sigma is not None else "monitor_tangents"
             if parse_monitors(cfg) is None:
                 raise ValueError(f"{arg}: the configuration has no monitors block (heatflow_amd.monitors)")
-            sigma = check_sigma(monitor_sigma) if monitor_sigma is not None else {}
-            tangents = list(tangents or ()) + [q for q in sigma if q not in (tangents or ())]
+            sigma = check_sigma(monitor_sigma) if monitor_sigma is not None else None
+            tangents = list(tangents or ()) + [q for q in sigma or () if q not in (tangents or ())]
             if not tangents:
                 raise ValueError("monitor_tangents: no parameter (tangents= names the columns)")
             if len(tangents) > 16:
@@ -651,7 +758,7 @@ class SimulationSession:
         spec = parse_source(cfg)
         if spec is not None and tangents and not spec.tangents:
             refuse_source(cfg, "tangents=")
-        for p in tangents or ():     # the source's own names, and the names a source rules out, before any problem is made
+        for p in tangents or ():     # the source's own names, and the names a source rules out
             if p in SOURCE_PARAMS or p.startswith("source."):
                 try:
                     check_source_param(spec, p)
@@ -663,207 +770,153 @@ class SimulationSession:
             elif spec is not None and p.endswith(".thickness"):
                 raise ValueError(f"tangents: parameter {p!r}: a layer thickness under a volumetric source (heating.source) is not "
                                  "supported (the source's load depends on the node positions, and that term is not formed)")
-        t_final = float(cfg["timing"]["t_final"])
-        num_steps = int(cfg["timing"]["num_steps"])
-        dt = t_final / num_steps
-        ic_temp = float(cfg["heating"]["ic_temp"])
-        bcs = self._boundary_conditions(cfg, stack, two_sided)
-        varying = bcs[3:]
-        tag_to_k, tag_to_rc = self._tables(stack)
-        scheme = time_scheme(cfg)
-        if tangents:
-            refuse_enthalpy(cfg, "monitor_sigma=" if monitor_sigma is not None else "tangents=")
-        kt = self._kappa_tables(cfg, stack)
-        enth = kt is not None and bool(kt[3])        # timing.capacity_form: enthalpy
-        if tangents:             # both kinds: timing.aniso_tables covers the forward run only, with timing.table_tangents too
-            refuse_aniso_tables(cfg, "monitor_sigma" if monitor_sigma is not None else "tangents")
-        tab_on = kt is not None and bool(tangents) and table_tangents(cfg)   # timing.table_tangents
-        if kt is not None and tangents and not tab_on:
+        return tangents, monitor_tangents, sigma, spec
+
+    def _check_tangent_request(self, cfg, spec, tangents, monitor_tangents, arg):
+        """What tangent columns rule out in the problem ``spec`` describes, before it is made.  Returns whether the run
+        differentiates through the tables (timing.table_tangents)."""
+        refuse_aniso_tables(cfg, arg)    # both kinds: timing.aniso_tables covers the forward run only, with timing.table_tangents too
+        tab_on = spec.tabled and table_tangents(cfg)
+        if spec.tabled and not tab_on:
             refuse_tables(cfg, "tangents")
         if tab_on:
             if monitor_tangents:
-                raise ValueError(("monitor_sigma" if monitor_sigma is not None else "monitor_tangents")
+                raise ValueError(("monitor_sigma" if arg == "monitor_sigma" else "monitor_tangents")
                                  + ": monitor derivatives together with timing.table_tangents are not supported")
             check_table_tangents(cfg, "tangents", tangents)
-            for p in tangents:       # the names of the tables' parameters, before any problem is made
+            for p in tangents:       # the names of the tables' parameters
                 try:
                     tp = None if p == "fwhm" else table_param(cfg, p)
                 except ValueError as e:
                     raise ValueError(f"tangents: {e}") from None
                 mat, _, suffix = p.rpartition(".")
-                if tp is None and suffix in ("k_r", "k_z") and self.material_tags.get(mat) in kt[0]:
+                if tp is None and suffix in ("k_r", "k_z") and self.material_tags.get(mat) in spec.kappa_tables:
                     raise ValueError(f"tangents: parameter {p!r}: {mat!r} carries a conductivity table (its parameters are "
                                      f"{mat}.k or {mat}.k_power.exponent, or {mat}.k_table.scale)")
-        an = self._aniso(stack)
-        if an and tangents:      # a bare name means the isotropic k: an anisotropic material is named by direction
+        if spec.k_aniso:         # a bare name means the isotropic k: an anisotropic material is named by direction
             refuse_aniso(cfg, "a tangent with respect to the conductivity of an anisotropic material", set(tangents),
                          DIRECTIONAL_HINT)
-        src = self._source(cfg, stack)
-        mon = self._monitors(cfg)
-        ant = aniso_tables(cfg)
-        key = self._problem_key(dt, tag_to_rc, bcs, scheme, kt, an, src, mon, ant)
-        fresh = self.problem is None or key != self._key
-        self._ensure_problem(key, tag_to_k, tag_to_rc, dt, bcs, ic_temp, scheme, kt, an, src, mon, ant)
-        if not fresh:
-            self.problem.set_state(ic_temp)
-            self.problem.iters = []
-        prob = self.problem
-        if mon and not fresh:    # the records of this run only
-            prob.clear_monitor_history()
-        if enth:                 # the sweeps and changes of this run only; with monitors the stored heat per step, for `energy`
-            if not fresh:
-                prob.clear_picard_history()
-            if mon:
-                prob.clear_heat_history()
-                prob.record_heat()
-        amp = None
-        if spec is not None:     # W -> W/m^3 per step, from the discrete source's own integral
-            if self._source_F1 is None:
-                self._source_F1 = prob.source_vector()
-            amp = source_amplitudes(spec, (np.arange(num_steps) + 1) * dt, self._source_F1, _resolve)
-        names, nodes = self._watcher_nodes(watcher_points)
+        return tab_on
 
-        flux = FluxSampler(self.coords) if read_flux else None
-        if flux is not None and not getattr(prob, "_flux_ready", False):
-            print("Setting up radial heat flux sampling...")
-            prob.backend.flux_setup()          # once per mesh: the unit-coefficient mass matrix does not depend on kappa
-            prob._flux_ready = True
-        print("Beginning loop...")
-        t_loop = time.time()
-        tangent_out, extra = None, {}
-        if tangents:
-            if field_sink is not None or flux is not None:
-                raise ValueError("tangents: not combined with a field sink or the read-flux projection")
-            params = list(tangents)
+    def _tangent_columns(self, cfg, source, params, tab_on, monitor_tangents, times, amp):
+        """The columns of ``params`` as HeatProblem.run_tangent takes them: TangentColumns(its keywords, {column: the factor
+        that turns the column's rho_c tangent into the named capacity parameter's})."""
+        prob = self.problem
+        try:
+            check_capacity_names(params)
+        except ValueError as e:
+            raise ValueError(f"tangents: {e}") from None
+        cond, bnd, shp, cap, cscale, srcp, tabs = [], {}, {}, {}, {}, {}, {}
+        for j, p in enumerate(params):
             try:
-                check_capacity_names(params)
+                kind, mat = classify_param(p, tables=tab_on)
+                tp = table_param(cfg, p) if tab_on and kind != "fwhm" else None
+                if kind == "thickness" and mat in self.material_tags:
+                    check_thickness_name(cfg, mat, p)
             except ValueError as e:
                 raise ValueError(f"tangents: {e}") from None
-            cond, bnd, shp, cap, cscale, srcp, tabs = [], {}, {}, {}, {}, {}, {}
-            for j, p in enumerate(params):
-                try:
-                    tp = table_param(cfg, p) if tab_on and p != "fwhm" else None
-                except ValueError as e:
-                    raise ValueError(f"tangents: {e}") from None
-                if tp is not None:       # a parameter of a material's table: a derivative table on the table's own grid
-                    cond.append([])
-                    tabs[j] = {tp[1]: {self.material_tags[tp[0]]: tp[2]}}
-                elif p in SOURCE_PARAMS:
-                    cond.append([])
-                    srcp[j] = p
-                elif p == "fwhm":
-                    cond.append([])
-                    bnd[j] = {3 + q: h.gaussian_dfwhm for q, h in enumerate(self._heats)}
-                    if spec is not None and "fwhm" not in source_block(cfg):   # the beam takes heating.fwhm too: both terms
-                        srcp[j] = "source.fwhm"
-                elif p in self.material_tags:
-                    cond.append([self.material_tags[p]])
-                else:
-                    try:
-                        mat, kind = split_param(p)
-                    except ValueError as e:
-                        raise ValueError(f"tangents: {e}") from None
-                    if kind is None or mat not in self.material_tags:
-                        raise ValueError(f"tangents: unknown parameter {p!r} (a material name, <material>.k_r, "
-                                         "<material>.k_z, <material>.k, <material>.thickness or 'fwhm')")
-                    if kind == "t":      # a layer thickness: the nodes of this session's mesh move with the stack of ``cfg``
-                        try:
-                            check_thickness_name(cfg, mat, p)
-                        except ValueError as e:
-                            raise ValueError(f"tangents: {e}") from None
-                        cond.append([])
-                        shp[j] = thickness_velocity(cfg, mat, self.coords[:, 0])
-                    elif kind in CAPACITY_KINDS.values():      # a column in rho_c = rho cv of the material; cv and rho by the chain rule
-                        if mat not in (cfg.get("mats") or {}):
-                            raise ValueError(f"tangents: parameter {p!r}: no material {mat!r} in the configuration")
-                        cond.append([])
-                        cap[j] = [self.material_tags[mat]]
-                        cscale[j] = capacity_scale(cfg["mats"][mat], kind)
-                    else:
-                        cond.append([(self.material_tags[mat], kind)])
-            src_kw = {}
-            if spec is not None:     # the opt-in: the source becomes differentiable, its own parameters get their columns
-                src_cols = {}
-                if srcp:
-                    if self._source_G is None:
-                        self._source_G = (prob.source_derivative("fwhm"), prob.source_derivative("depth"))
-                    table = tangent_coefficients(spec, sorted(set(srcp.values())), (np.arange(num_steps) + 1) * dt, self._source_F1,
-                                                 self._source_G[0], self._source_G[1], _resolve)
-                    src_cols = {j: {"amplitude": table[p][:, 0], "fwhm": table[p][:, 1], "depth": table[p][:, 2]}
-                                for j, p in srcp.items()}
-                src_kw = {"source": src_cols, "source_amplitude": amp}
-            times, samples, tsamp, iters, titers = prob.run_tangent(num_steps, nodes, conductivity=cond, boundary=bnd,
-                                                                    time_varying=varying, **({"shape": shp} if shp else {}),
-                                                                    **({"capacity": [cap.get(j, []) for j in range(len(params))]}
-                                                                       if cap else {}),
-                                                                    **({"monitor_tangents": True} if monitor_tangents else {}),
-                                                                    **({"tables": tabs} if tab_on else {}),
-                                                                    **src_kw)
-            for j, f in cscale.items():
-                if f != 1.0:
-                    tsamp[:, j] *= f
-            tangent_out = {p: {nm: tsamp[:, j, k] for k, nm in enumerate(names)} for j, p in enumerate(params)}
-            if monitor_tangents:
-                dhist = prob.monitor_tangent_history(scale=[cscale.get(j, 1.0) for j in range(len(params))])
-                extra = {"monitor_tangents": {p: {region: {field: d[:, j] for field, d in f.items()} for region, f in dhist.items()}
-                                              for j, p in enumerate(params)}}
-                if monitor_sigma is not None:
-                    from .fit import get_param
-                    extra["monitor_uncertainty"] = monitor_uncertainty(extra["monitor_tangents"],
-                                                                       {q: s * get_param(cfg, q) for q, s in sigma.items()})
-        elif field_sink is None and flux is None:
-            times, samples, iters = prob.run(num_steps, watcher_nodes=nodes, time_varying=varying,
-                                             **({"source_amplitude": amp} if amp is not None else {}))
-        else:  # step-wise: every field goes to the sink (visualisation) and / or through the flux projection
-            for bc in bcs:
-                bc.update(0.0)
-            times, rows, iters = [], [], []
-            for step in range(num_steps):
-                t = (step + 1) * dt
-                it, _ = prob.step(t, only=varying, **({"source_amplitude": float(amp[step])} if amp is not None else {}))
-                if flux is not None:
-                    prob.backend.flux_solve(self.rtol, 5000, want_z=False)          # d/dr only, on the device
-                    flux.record_sampled(t, prob.backend.flux_sample(flux.nodes, want_z=False)[1])
-                if field_sink is not None:
-                    u = prob.state()
-                    field_sink(t, u)
-                    rows.append(u[nodes] if nodes is not None else np.zeros(0))
-                else:
-                    rows.append(prob.backend.sample(nodes) if nodes is not None else np.zeros(0))
-                times.append(t)
-                iters.append(it)
-            times, samples, iters = np.array(times), np.array(rows), np.array(iters)
-        loop_time = time.time() - t_loop
-        print(f"Simulation progress: 100% (step {num_steps}/{num_steps}) | Avg time/step: {loop_time / num_steps:.4f} s"
-              f" | PCG iterations/step: mean {np.mean(iters):.0f}, max {int(np.max(iters))}")
-        mon_out, picard_out = None, {}
-        if mon:
-            mon_out = prob.monitor_history()
-            if enth:             # every region's energy from the heat records: the stored heat the scheme conserves, tabled tags included
+            cond.append([])
+            if tp is not None:       # a parameter of a material's table: a derivative table on the table's own grid
+                tabs[j] = {tp[1]: {self.material_tags[tp[0]]: tp[2]}}
+            elif kind == "source":
+                srcp[j] = p
+            elif kind == "fwhm":
+                bnd[j] = {3 + q: h.gaussian_dfwhm for q, h in enumerate(self._heats)}
+                if source is not None and "fwhm" not in source_block(cfg):     # the beam takes heating.fwhm too: both terms
+                    srcp[j] = "source.fwhm"
+            elif mat not in self.material_tags:
+                raise ValueError(f"tangents: unknown parameter {p!r} (a material name, <material>.k_r, "
+                                 "<material>.k_z, <material>.k, <material>.thickness or 'fwhm')")
+            elif kind == "thickness":     # the nodes of this session's mesh move with the stack of ``cfg``
+                shp[j] = thickness_velocity(cfg, mat, self.coords[:, 0])
+            elif kind in CAPACITY_KINDS:  # a column in rho_c = rho cv of the material; cv and rho by the chain rule
+                if mat not in (cfg.get("mats") or {}):
+                    raise ValueError(f"tangents: parameter {p!r}: no material {mat!r} in the configuration")
+                cap[j] = [self.material_tags[mat]]
+                cscale[j] = capacity_scale(cfg["mats"][mat], CAPACITY_KINDS[kind])
+            else:                         # the bare name: the set-up of isotropic tags; "<m>.k" / ".k_r" / ".k_z": the directional one
+                cond[j] = [self.material_tags[mat] if p == mat else (self.material_tags[mat], PARAM_KINDS[kind])]
+        kwargs = {"conductivity": cond, "boundary": bnd, **({"shape": shp} if shp else {}),
+                  **({"capacity": [cap.get(j, []) for j in range(len(params))]} if cap else {}),
+                  **({"monitor_tangents": True} if monitor_tangents else {}), **({"tables": tabs} if tab_on else {})}
+        if source is not None:   # the opt-in: the source becomes differentiable, its own parameters get their columns
+            src_cols = {}
+            if srcp:
+                if self._source_G is None:
+                    self._source_G = (prob.source_derivative("fwhm"), prob.source_derivative("depth"))
+                table = tangent_coefficients(source, sorted(set(srcp.values())), times, self._source_F1, self._source_G[0],
+                                             self._source_G[1], _resolve)
+                src_cols = {j: {"amplitude": table[p][:, 0], "fwhm": table[p][:, 1], "depth": table[p][:, 2]}
+                            for j, p in srcp.items()}
+            kwargs.update(source=src_cols, source_amplitude=amp)
+        return TangentColumns(kwargs, cscale)
+
+    def _tangent_results(self, cfg, params, names, tsamp, titers, cscale, monitor_tangents, sigma):
+        """The result entries of a tangent run, in two parts: ``tangents`` and ``tangent_iters``; with the monitors' derivatives
+        ``monitor_tangents`` and (under ``monitor_sigma``, ``sigma`` not None) ``monitor_uncertainty``."""
+        for j, f in cscale.items():
+            if f != 1.0:
+                tsamp[:, j] *= f
+        out = {"tangents": {p: {nm: tsamp[:, j, k] for k, nm in enumerate(names)} for j, p in enumerate(params)},
+               "tangent_iters": titers}
+        extra = {}
+        if monitor_tangents:
+            dhist = self.problem.monitor_tangent_history(scale=[cscale.get(j, 1.0) for j in range(len(params))])
+            extra["monitor_tangents"] = {p: {region: {field: d[:, j] for field, d in f.items()} for region, f in dhist.items()}
+                                         for j, p in enumerate(params)}
+            if sigma is not None:
+                from .fit import get_param
+                extra["monitor_uncertainty"] = monitor_uncertainty(extra["monitor_tangents"],
+                                                                   {q: s * get_param(cfg, q) for q, s in sigma.items()})
+        return out, extra
+
+    def _run_stepwise(self, bcs, num_steps, dt, amp, nodes, flux, field_sink):
+        """The steps one by one: every field goes to ``field_sink`` and / or through the flux projection of ``flux``."""
+        prob = self.problem
+        for bc in bcs:
+            bc.update(0.0)
+        times, rows, iters = [], [], []
+        for step in range(num_steps):
+            t = (step + 1) * dt
+            it, _ = prob.step(t, only=bcs[3:], **({"source_amplitude": float(amp[step])} if amp is not None else {}))
+            if flux is not None:
+                prob.backend.flux_solve(self.rtol, 5000, want_z=False)          # d/dr only, on the device
+                flux.record_sampled(t, prob.backend.flux_sample(flux.nodes, want_z=False)[1])
+            if field_sink is not None:
+                u = prob.state()
+                field_sink(t, u)
+                rows.append(u[nodes] if nodes is not None else np.zeros(0))
+            else:
+                rows.append(prob.backend.sample(nodes) if nodes is not None else np.zeros(0))
+            times.append(t)
+            iters.append(it)
+        return np.array(times), np.array(rows), np.array(iters)
+
+    def _history_results(self, spec):
+        """The result entries the resident problem recorded along the run: ``monitors`` and, under the enthalpy form, ``picard``
+        (with a RuntimeWarning for steps that ended at the sweep cap above the tolerance)."""
+        prob, out = self.problem, {}
+        if spec.monitors:
+            out["monitors"] = prob.monitor_history()
+            if spec.enthalpy:    # every region's energy from the heat records: the stored heat the scheme conserves, tabled tags included
                 heat = prob.heat_history()
-                for region, r in mon.items():
-                    mon_out[region]["energy"] = sum(heat[int(t)] for t in r["tags"])
-        if enth:
+                for region, r in spec.monitors.items():
+                    out["monitors"][region]["energy"] = sum(heat[int(t)] for t in r["tags"])
+        if spec.enthalpy:
             hist = prob.picard_history()
-            picard_out = {"picard": {"sweeps": np.asarray(hist["sweeps"]), "change": np.asarray(hist["change"])}}
-            tol = kt[3]["picard_tol"]
-            if tol:
-                late = np.flatnonzero((picard_out["picard"]["sweeps"] >= kt[1]) & (picard_out["picard"]["change"] > tol))
+            sweeps, change = np.asarray(hist["sweeps"]), np.asarray(hist["change"])
+            out["picard"] = {"sweeps": sweeps, "change": change}
+            if spec.picard_tol:
+                late = np.flatnonzero((sweeps >= spec.picard) & (change > spec.picard_tol))
                 if late.size:
-                    warnings.warn(f"timing.picard_sweeps = {kt[1]}: step {int(late[0]) + 1} ended at the cap with a Picard change of "
-                                  f"{picard_out['picard']['change'][late[0]]:.3g} K > timing.picard_tol = {tol:g} K "
+                    warnings.warn(f"timing.picard_sweeps = {spec.picard}: step {int(late[0]) + 1} ended at the cap with a Picard "
+                                  f"change of {change[late[0]]:.3g} K > timing.picard_tol = {spec.picard_tol:g} K "
                                   f"({late.size} such step(s); more sweeps or timing.picard_relax < 1 may help)", RuntimeWarning,
-                                  stacklevel=2)
-        return {
-            "times": np.asarray(times), "watcher_names": names,
-            "watchers": {nm: samples[:, k] for k, nm in enumerate(names)},
-            "iters": np.asarray(iters), "loop_time": loop_time, "startup_time": t_loop - t_start,
-            "n_dof": prob.n, "dt": dt, "flux": flux,
-            **({"tangents": tangent_out, "tangent_iters": titers} if tangent_out is not None else {}),
-            **({"monitors": mon_out} if mon else {}),
-            **picard_out,
-            **extra,
-        }
+                                  stacklevel=3)
+        return out
+
+
+TangentColumns = collections.namedtuple("TangentColumns", "kwargs scale")
 
 
 class FluxSampler:

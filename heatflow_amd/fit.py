@@ -21,40 +21,33 @@ import numpy as np
 
 from .geometry import check_thickness_name, thickness_velocity
 from .parameter_sweep import build_stack, get_watcher_points, oside_curves
-from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, KEY, capacity_scale, check_capacity_names, material_aniso, refuse_aniso,
-                    refuse_aniso_tables, split_param)
-from .kappa_t import (check_table_tangents, refuse_enthalpy, get_table_param, refuse_tables, set_table_param, split_table_param, table_keys,
+from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, KEY, PARAM_KINDS, check_capacity_names, classify_param, material_aniso,
+                    refuse_aniso, refuse_aniso_tables)
+from .kappa_t import (check_table_tangents, refuse_enthalpy, get_table_param, refuse_tables, set_table_param, table_keys,
                       table_tangents)
-from .source import SOURCE_PARAMS, check_source_param, parse_source, refuse_source_tangents
+from .source import check_source_param, parse_source, refuse_source_tangents
 from .monitors import refuse_monitors
 
 DEFAULT_EXP_CSV = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "experimental_data",
                                "geballe_heat_data.csv")
 
 
-def _material_param(cfg, name):
-    """(material block, None | "k" | "r" | "z" | "t" | "c" | "cv" | "rho") of a parameter name, "table" for a name of
-    kappa_t.TABLE_PARAM_SUFFIXES; ValueError naming it for an unknown material or suffix."""
-    if split_table_param(name) is not None:
+def _resolve_param(cfg, name):
+    """(kind, material name, what carries it) of a parameter name, the kind and the name from aniso.classify_param: the material's
+    block of ``cfg``, the validated source for a "source.*" name, None for "fwhm".  ValueError naming the parameter for an unknown
+    material or suffix, a table name on a material without that block, and a source name the source does not have."""
+    kind, mat = classify_param(name)
+    if kind == "fwhm":
+        return kind, mat, None
+    if kind == "source":
+        spec = parse_source(cfg)
+        check_source_param(spec, name)
+        return kind, mat, spec
+    if kind == "table":
         get_table_param(cfg, name)       # (an unknown material or a missing block: ValueError)
-        return cfg["mats"][split_table_param(name)[0]], "table"
-    mat, kind = split_param(name)
-    if mat not in cfg["mats"]:
+    elif mat not in cfg["mats"]:
         raise ValueError(f"parameter {name!r}: no material {mat!r} in the configuration")
-    return cfg["mats"][mat], kind
-
-
-def _is_source_param(name):
-    """A parameter of the volumetric source ("source.power", "source.fwhm", "source.depth", "source.pulse.t0", "source.pulse.fwhm");
-    any other "source.*" spelling is sent to check_source_param for its ValueError."""
-    return name in SOURCE_PARAMS or name.startswith("source.")
-
-
-def _source_param(cfg, name):
-    """The validated source of ``cfg`` for the source parameter ``name``; ValueError naming the parameter otherwise."""
-    spec = parse_source(cfg)
-    check_source_param(spec, name)
-    return spec
+    return kind, mat, cfg["mats"][mat]
 
 
 def get_param(cfg, name):
@@ -64,25 +57,24 @@ def get_param(cfg, name):
     rho * cv in J/m^3/K, "<m>.cv", "<m>.rho"; or a parameter of the volumetric source: "source.power" in W,
     "source.fwhm" (the beam's width, heating.fwhm where the block has none) and "source.depth" in metres, "source.pulse.t0" and
     "source.pulse.fwhm" of a Gaussian pulse in seconds."""
-    if name == "fwhm":
+    kind, mat, block = _resolve_param(cfg, name)
+    if kind == "fwhm":
         return float(cfg["heating"]["fwhm"])
-    if _is_source_param(name):
-        spec = _source_param(cfg, name)
+    if kind == "source":
         if name.startswith("source.pulse."):
-            return float(spec.pulse[1 if name.endswith(".t0") else 2])
-        return float({"source.power": spec.power, "source.fwhm": spec.fwhm, "source.depth": spec.depth}[name])
-    mat, kind = _material_param(cfg, name)
+            return float(block.pulse[1 if name.endswith(".t0") else 2])
+        return float({"source.power": block.power, "source.fwhm": block.fwhm, "source.depth": block.depth}[name])
     if kind == "table":      # DESIGN.md 3.20: "<m>.k_power.exponent", "<m>.cv_einstein.theta", or a table's scale (1 as it stands)
         return get_table_param(cfg, name)
-    if kind in (None, "k"):
-        return float(mat["k"])
-    if kind == "t":
-        check_thickness_name(cfg, name.rsplit(".", 1)[0], name)
-        return float(mat["z"])
-    if kind in CAPACITY_KINDS.values():
-        return float(mat["rho"]) * float(mat["cv"]) if kind == "c" else float(mat[kind])
-    m = material_aniso(name.rsplit(".", 1)[0], mat) or (1.0, 1.0)
-    return float(mat["k"]) * m[0 if kind == "r" else 1]
+    if kind == "k":
+        return float(block["k"])
+    if kind == "thickness":
+        check_thickness_name(cfg, mat, name)
+        return float(block["z"])
+    if kind in CAPACITY_KINDS:
+        return float(block["rho"]) * float(block["cv"]) if kind == "rho_c" else float(block[kind])
+    m = material_aniso(mat, block) or (1.0, 1.0)
+    return float(block["k"]) * m[0 if kind == "k_r" else 1]
 
 
 def set_params(cfg, params, values):
@@ -93,36 +85,33 @@ def set_params(cfg, params, values):
     ("source.fwhm" writes heating.source.fwhm explicitly, whether the block had one or took heating.fwhm).  The k parameters are applied first, so a directional value holds
     whatever the order of the names."""
     c = copy.deepcopy(cfg)
-    pairs = list(zip(params, values))
     check_capacity_names(params)
-    for name, v in pairs:
-        if name == "fwhm":
+    directional = []
+    for name, v in zip(params, values):
+        kind, mat, block = _resolve_param(c, name)
+        if kind == "fwhm":
             c["heating"]["fwhm"] = float(v)
-        elif _is_source_param(name):
-            _source_param(c, name)
+        elif kind == "source":
             block = c["heating"]["source"]
             if name.startswith("source.pulse."):
                 block["pulse"][name.rsplit(".", 1)[1]] = float(v)
             else:
                 block[name.split(".", 1)[1]] = float(v)
-        elif _material_param(c, name)[1] == "table":
+        elif kind == "table":
             set_table_param(c, name, v)
-        elif _material_param(c, name)[1] in (None, "k"):
-            _material_param(c, name)[0]["k"] = float(v)
-        elif _material_param(c, name)[1] == "t":
-            check_thickness_name(c, name.rsplit(".", 1)[0], name)
-            _material_param(c, name)[0]["z"] = float(v)
-        elif _material_param(c, name)[1] in CAPACITY_KINDS.values():
-            mat, kind = _material_param(c, name)
-            if kind == "c":
-                mat["cv"] = float(v) / float(mat["rho"])
-            else:
-                mat[kind] = float(v)
-    for name, v in pairs:
-        if name != "fwhm" and not _is_source_param(name):
-            mat, kind = _material_param(c, name)
-            if kind in ("r", "z"):
-                mat.setdefault(KEY, {})[kind] = float(v) / float(mat["k"])
+        elif kind == "k":
+            block["k"] = float(v)
+        elif kind == "thickness":
+            check_thickness_name(c, mat, name)
+            block["z"] = float(v)
+        elif kind == "rho_c":
+            block["cv"] = float(v) / float(block["rho"])
+        elif kind in CAPACITY_KINDS:
+            block[kind] = float(v)
+        else:
+            directional.append((block, PARAM_KINDS[kind], v))
+    for block, direction, v in directional:
+        block.setdefault(KEY, {})[direction] = float(v) / float(block["k"])
     return c
 
 
@@ -188,26 +177,17 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
             raise ValueError("parameter 'source.power' cannot be fitted: the objective is normalised by the p-side span and the "
                              "temperature rise is linear in the power, so its Jacobian column is identically zero (it is valid "
                              "as a nuisance, in tangents= and in monitor_sigma=)")
-        if _is_source_param(p):
-            _source_param(cfg, p)
-        elif p != "fwhm":
-            _material_param(cfg, p)      # an unknown material or suffix, before any mesh or session is made
+        _resolve_param(cfg, p)           # an unknown material or suffix, before any mesh or session is made
     nuisance = {str(q): v for q, v in dict(nuisance or {}).items()}
     for q, sig in nuisance.items():
         if q in params:
             raise ValueError(f"nuisance {q!r} is a fitted parameter (a parameter is fitted or budgeted, not both)")
-        if _is_source_param(q):
-            try:
-                _source_param(cfg, q)
-            except ValueError as e:
-                raise ValueError(f"nuisance {q!r}: {e}") from None
-        elif q != "fwhm":
-            try:
-                mat_q, kind_q = _material_param(cfg, q)
-            except ValueError as e:
-                raise ValueError(f"nuisance {q!r}: {e}") from None
-            if kind_q == "t":
-                check_thickness_name(cfg, q.rsplit(".", 1)[0], q)
+        try:
+            kind_q, mat_q, _ = _resolve_param(cfg, q)
+        except ValueError as e:
+            raise ValueError(f"nuisance {q!r}: {e}") from None
+        if kind_q == "thickness":
+            check_thickness_name(cfg, mat_q, q)
         try:
             ok = np.isfinite(float(sig)) and float(sig) > 0.0
         except (TypeError, ValueError):
@@ -217,7 +197,7 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     check_capacity_names(params + tuple(nuisance))
     if nuisance:
         refuse_aniso(cfg, "heatflow_amd.fit with the conductivity of an anisotropic material as a nuisance", set(nuisance), DIRECTIONAL_HINT)
-    thick = [(j, p.rsplit(".", 1)[0]) for j, p in enumerate(params) if p != "fwhm" and not _is_source_param(p) and _material_param(cfg, p)[1] == "t"]
+    thick = [(j, classify_param(p)[1]) for j, p in enumerate(params) if classify_param(p)[0] == "thickness"]
     for j, mat in thick:
         check_thickness_name(cfg, mat, params[j])
     exp = load_experiment(exp_csv)

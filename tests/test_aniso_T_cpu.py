@@ -3,6 +3,7 @@ tests/aniso_T_oracle.py against the two restatements it composes (bit for bit wh
 identity under tables, two problems that separate the directions, the configuration key with everything that stays refused,
 used_config.yaml, the example configuration, HeatProblem's call order and the header."""
 import copy
+import dataclasses
 import inspect
 import os
 import re
@@ -401,9 +402,13 @@ def test_session_carries_the_switch_into_the_problem_and_keys_the_resident_probl
     s.run(cfg, stack, wp)
     assert be.set_mesh_calls == 1
     # the key carries the switch: the same problem without it is another resident problem
-    base = s._problem_key(1.0, {1: 2.0}, [], "backward_euler", None, {1: (2.0, 0.25)}, None, None)
-    assert s._problem_key(1.0, {1: 2.0}, [], "backward_euler", None, {1: (2.0, 0.25)}, None, None, False) == base
-    assert s._problem_key(1.0, {1: 2.0}, [], "backward_euler", None, {1: (2.0, 0.25)}, None, None, True) != base
+    from heatflow_amd.driver import ProblemSpec
+
+    base = ProblemSpec(1.0, "backward_euler", {1: 2.0}, [], k_aniso={1: (2.0, 0.25)})
+    assert dataclasses.replace(base, aniso_tables=False).key == base.key
+    assert dataclasses.replace(base, aniso_tables=True).key != base.key
+    assert "aniso_tables" not in base.problem_kwargs()
+    assert dataclasses.replace(base, aniso_tables=True).problem_kwargs()["aniso_tables"] is True
     only_an = copy.deepcopy(cfg)
     for m in only_an["mats"].values():
         m.pop("k_power", None)

@@ -2,6 +2,7 @@
 without it (word for word) and with it (naming both keys), what the configurations of a batch must share, the calls run_batch makes
 under the key, the problem key, used_config.yaml, and the header / backend lists of the new entry points."""
 import copy
+import dataclasses
 import os
 import re
 
@@ -222,12 +223,12 @@ def test_the_problem_key_carries_the_switch(small):
     cfg = _cfg()
     s = _session(mesh, Recorder(len(mesh.coords)))
     stack = _stacks([cfg])[0]
-    bcs = s._boundary_conditions(cfg, stack)
-    tk, trc = s._tables(stack)
-    kt = s._kappa_tables(cfg, stack)
-    off = s._problem_key(1e-8, trc, bcs, "backward_euler", kt)
-    on = s._problem_key(1e-8, trc, bcs, "backward_euler", kt, None, None, None, False, True)
-    assert on != off and on[:len(off)] == off and on[-1] == ("sweep_tables",)
+    spec = s.spec(cfg, stack)
+    assert spec.tabled and not spec.batch_tables
+    off, on = spec.key, dataclasses.replace(spec, batch_tables=True).key
+    assert on != off and on[:len(off)] == off and on[-1] == ("batch_tables",)
+    # the switch is the batch's to set: it is no keyword of the problem
+    assert dataclasses.replace(spec, batch_tables=True).problem_kwargs() == spec.problem_kwargs()
     # a problem made for a single run under the same tables is not reused by the batch
     from heatflow_amd.parameter_sweep import get_watcher_points
 

@@ -312,7 +312,7 @@ def test_session_is_not_reused_for_a_different_dirichlet_set_with_the_same_dof_s
     be = OracleBackend()
     sess = SimulationSession(coords, tris, tags, tag_map, backend=be)
     sess.run(cfg, stack, watcher_points(cfg))
-    key1, dofs1 = sess._key, sess.problem.bc_dofs.copy()
+    spec1, dofs1 = sess._spec, sess.problem.bc_dofs.copy()
     real = drv.RowDirichletBC
 
     class SameSum(real):                        # heated line: two DOFs swapped for two others with the same sum
@@ -332,7 +332,8 @@ def test_session_is_not_reused_for_a_different_dirichlet_set_with_the_same_dof_s
         sess.run(cfg, stack, watcher_points(cfg))
     finally:
         drv.RowDirichletBC = real
-    assert sess._key != key1 and sess._key[:2] == key1[:2]
+    assert sess._spec.key != spec1.key and (sess._spec.dt, sess._spec.rho_c) == (spec1.dt, spec1.rho_c)
+    assert sess._spec.key[:2] == spec1.key[:2]
     assert int(dofs1.sum()) == int(sess.problem.bc_dofs.sum()) and not np.array_equal(dofs1, sess.problem.bc_dofs)
     assert be.set_mesh_calls == 2               # a new HeatProblem was built for the new Dirichlet set
 

@@ -210,11 +210,16 @@ def test_session_hands_the_capacity_tables_to_the_problem(small):
     _, _, mesh = small
     s = SimulationSession(mesh.coords, mesh.tris, mesh.tags, mesh.material_tags, backend=RecordingBackend())
     cfg = _cv_cfg()
-    kt = s._kappa_tables(cfg, build_stack(cfg))
-    assert kt[0] == {} and kt[1] == 1 and set(kt[2]) == {mesh.material_tags["p_ins"], mesh.material_tags["o_ins"]}
-    assert kt[2][mesh.material_tags["o_ins"]][2][1] == 4131 * 800.0
+    spec = s.spec(cfg, build_stack(cfg))
+    assert spec.kappa_tables == {} and spec.picard == 1
+    assert set(spec.rhoc_tables) == {mesh.material_tags["p_ins"], mesh.material_tags["o_ins"]}
+    assert spec.rhoc_tables[mesh.material_tags["o_ins"]][2][1] == 4131 * 800.0
+    kw = spec.problem_kwargs()
+    assert kw["kappa_tables"] == {} and kw["picard"] == 1 and kw["rhoc_tables"] is spec.rhoc_tables
     plain = load_cfg("geballe_with_diamond")
-    assert s._kappa_tables(plain, build_stack(plain)) is None
+    none = s.spec(plain, build_stack(plain))
+    assert not none.tabled and none.kappa_tables == {} and none.rhoc_tables == {}
+    assert not {"kappa_tables", "rhoc_tables", "picard"} & set(none.problem_kwargs())
 
 
 def test_used_config_records_the_capacity_tables():

@@ -3,6 +3,7 @@ high-order quadrature of the true source), the amplitudes (Gaussian and CSV puls
 ``heating.source`` block (parsing, defaults, face, used_config.yaml, the three-edge boundary set), every Python refusal,
 HeatProblem's call order, the session end to end on a scipy stand-in, and the header against EXPORTS."""
 import copy
+import dataclasses
 import math
 import os
 import re
@@ -223,12 +224,18 @@ def test_boundary_set_problem_key_and_optional_heating_file(small):
         s._boundary_conditions(_small_cfg({**_source_cfg(keep_line=True), "heating": {k: v for k, v in kept["heating"].items() if k != "file"}}), stack)
     src = s._source(cfg, stack)
     tk, trc = s._tables(stack)
-    base = s._problem_key(7.5e-8, trc, three)
-    assert s._source(plain, stack) is None and s._problem_key(7.5e-8, trc, three, src=None) == base
-    k1 = s._problem_key(7.5e-8, trc, three, src=src)
-    k2 = s._problem_key(7.5e-8, trc, three, src=s._source(_small_cfg(_source_cfg(depth=2e-8)), stack))
-    k3 = s._problem_key(7.5e-8, trc, three, src=s._source(_small_cfg(_source_cfg(power=0.4)), stack))
-    assert k1 != base and k1 != k2 and k1 == k3                  # the shape is part of the key, the power is an amplitude
+    from heatflow_amd.driver import ProblemSpec
+
+    base = ProblemSpec(7.5e-8, "backward_euler", trc, three)
+    assert s._source(plain, stack) is None and dataclasses.replace(base, source=None).key == base.key
+    k1 = dataclasses.replace(base, source=src).key
+    k2 = dataclasses.replace(base, source=s._source(_small_cfg(_source_cfg(depth=2e-8)), stack)).key
+    k3 = dataclasses.replace(base, source=s._source(_small_cfg(_source_cfg(power=0.4)), stack)).key
+    assert k1 != base.key and k1 != k2 and k1 == k3              # the shape is part of the key, the power is an amplitude
+    # the session's own spec of the configuration carries that source, in the key and in the problem's keywords
+    spec = s.spec(cfg, stack)
+    assert spec.source == src and spec.problem_kwargs()["source"] == src and "source" not in s.spec(plain, stack).problem_kwargs()
+    assert spec.key != dataclasses.replace(spec, source=None).key
 
 
 # ---- refusals ---------------------------------------------------------------------------------------------------------------
