@@ -272,6 +272,8 @@ int install_mesh(hf_ctx* ctx, int32_t n, int32_t ne, const double* zr, const int
   HF_TRY(dev_alloc(ctx, &ctx->d_ustart, n));
   ctx->have_prev = false;
   ctx->bdf_hist = false;
+  varstep_control_free(ctx);      // (sized for the old mesh)
+  ctx->vs = hf_ctx::VarStep();
   free_responses(ctx);
   HF_TRY(dev_alloc(ctx, &ctx->d_b, n));
   HF_TRY(dev_alloc(ctx, &ctx->d_r, 2 * static_cast<size_t>(n) + 4));   // the level-1 result of a fused finest level lives behind r: [r; x_1]
@@ -796,6 +798,7 @@ int hf_destroy(hf_ctx* ctx) {
   dev_free(&ctx->d_uprev); dev_free(&ctx->d_ustart);
   dev_free(&ctx->d_u); dev_free(&ctx->d_b); dev_free(&ctx->d_r); dev_free(&ctx->d_p); dev_free(&ctx->d_Ap);
   free_batch(ctx); free_batch_state(ctx->fluxb); free_batch_cols(ctx); free_system(ctx->sys); free_responses(ctx); proj_free(ctx); dev_free(&ctx->d_z); dev_free(&ctx->d_z2);
+  varstep_control_free(ctx);
   steady_free(ctx); load_free(ctx); source_free(ctx); monitor_free(ctx); tangent_free(ctx); kt_free(ctx); heat_free(ctx); an_free(ctx); value_lists_free(ctx);
   dev_free(&ctx->d_M1); dev_free(&ctx->d_dinv1); dev_free(&ctx->d_gz); dev_free(&ctx->d_gr); dev_free(&ctx->d_bz); dev_free(&ctx->d_br);
   dev_free(&ctx->d_tmp); dev_free(&ctx->d_part_pAp); dev_free(&ctx->d_part_rz); dev_free(&ctx->d_part_zz);
@@ -1011,6 +1014,7 @@ int hf_set_dirichlet(hf_ctx* ctx, int32_t n_bc, const int32_t* dofs) {
   HF_TRY(build_lift(ctx, ctx->sys));
   free_amg(ctx->sys);
   free_responses(ctx);
+  ctx->vs.mask_ok = false;   // (the free rows of hf_get_step_error)
   ctx->assembled = false;  // A_hat depends on the BC set
   return HF_OK;
 }
@@ -1072,6 +1076,13 @@ int hf_assemble(hf_ctx* ctx, double dt, int32_t mode) {
   ctx->sys.pred_iters = 0;
   ctx->have_prev = false;
   ctx->bdf_hist = false;
+  // variable steps: the record is at rest, and the following steps have the size of this assembly again
+  varstep_rest(ctx);
+  ctx->vs.on = false;
+  ctx->vs.carry = ctx->vs.last_changed = false;
+  ctx->vs.list.clear();
+  ctx->vs.next = 0;
+  ctx->vs.dt_next = dt;
   free_responses(ctx);   // R depends on the operator
   return tangent_reset(ctx);   // and so do the tangents (hf_update_kappa comes here too)
 }
@@ -1096,6 +1107,7 @@ int hf_set_time_scheme(hf_ctx* ctx, int32_t scheme) {
     ctx->assembled = false;
     ctx->sys.pred_iters = 0;
     ctx->scheme = scheme;
+    varstep_rest(ctx);
   }
   return HF_OK;
 }
@@ -1606,6 +1618,7 @@ int hf_set_state(hf_ctx* ctx, const double* u) {
   HF_HIP(hipStreamSynchronize(ctx->stream));
   ctx->have_prev = false;
   ctx->bdf_hist = false;   // BDF2: a rest start, u^{-1} = u^n
+  varstep_rest(ctx);
   ctx->g_hist = 0;       // the state no longer continues the recursion the boundary history belongs to
   proj_clear(ctx, true);
   ctx->tan.steady_state = false;
@@ -1641,6 +1654,7 @@ int hf_step(hf_ctx* ctx, const double* g_bc, double rtol, double atol, int32_t m
   if (ctx->sys.nbc > 0 && !g_bc) return fail(ctx, HF_ERR_ARG, "hf_step: g_bc is null");
   if (max_it <= 0 || rtol < 0 || atol < 0) return fail(ctx, HF_ERR_ARG, "hf_step: bad tolerances");
   HF_HIP(hipSetDevice(ctx->dev));
+  HF_TRY(varstep_ready(ctx, 1, "hf_step"));
   HF_TRY(source_steps_ok(ctx, 1, "hf_step"));
   HF_TRY(monitor_room(ctx, 1));
   HF_TRY(enthalpy_room(ctx, 1));
@@ -1669,6 +1683,7 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
   for (int32_t q = 0; q < ns; ++q)
     if (nodes[q] < 0 || nodes[q] >= ctx->n) return fail(ctx, HF_ERR_ARG, "hf_run: node %d outside [0,%d)", nodes[q], ctx->n);
   HF_HIP(hipSetDevice(ctx->dev));
+  HF_TRY(varstep_ready(ctx, n_steps, "hf_run"));
   HF_TRY(source_steps_ok(ctx, n_steps, "hf_run"));
   HF_TRY(monitor_room(ctx, n_steps));
   HF_TRY(enthalpy_room(ctx, n_steps));
@@ -1703,6 +1718,151 @@ int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_all, double rtol, doubl
   ctx->last_ms = ms;
   if (ns > 0 && rc == HF_OK) (void)copy_sync(ctx, samples, d_sall, sizeof(double) * n_steps * ns, hipMemcpyDeviceToHost);
   return rc;
+}
+
+// ---- variable time steps -----------------------------------------------------------------------------------------
+
+// What hf_set_step, hf_set_step_list and hf_set_step_control refuse, under the caller's name
+static int varstep_refusals(hf_ctx* ctx, const char* fn) {
+  if (!ctx->assembled) return fail(ctx, HF_ERR_STATE, "%s before hf_assemble", fn);
+  if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "%s: a batch is open (the batched loop, and with it the flux projection's batched run, takes hf_assemble's step)", fn);
+  if (ctx->tan.ready) return fail(ctx, HF_ERR_STATE, "%s: a tangent set-up is in force (the tangent kernels carry the constant-step coefficients 4/3 and 1/3)", fn);
+  if (ctx->kt.form == 1) return enthalpy_refuses(ctx, fn, "its sweeps take hf_assemble's step");
+  if (!(ctx->mode == HF_ASM_ROW_GATHER && ctx->rg_ok))
+    return fail(ctx, HF_ERR_STATE, "%s: the operator is re-valued by the row-gather kernel only (hf_assemble with HF_ASM_ROW_GATHER on a mesh it covers)", fn);
+  return HF_OK;
+}
+
+int hf_set_step(hf_ctx* ctx, double dt) {
+  if (!ctx) return HF_ERR_ARG;
+  if (!(dt > 0.0) || !std::isfinite(dt)) return fail(ctx, HF_ERR_ARG, "hf_set_step: dt must be positive and finite");
+  HF_TRY(varstep_refusals(ctx, "hf_set_step"));
+  hf_ctx::VarStep& V = ctx->vs;
+  if (ctx->scheme == HF_TIME_BDF2 && ctx->bdf_hist && V.nh > 0 && dt / V.h[0] > BDF2_MAX_RATIO)
+    return fail(ctx, HF_ERR_ARG, "hf_set_step: a BDF2 step of %.6e after one of %.6e: the ratio %.4f exceeds 1 + sqrt 2", dt, V.h[0], dt / V.h[0]);
+  V.on = true;
+  V.dt_next = dt;
+  V.list.clear();
+  V.next = 0;
+  return HF_OK;
+}
+
+int hf_set_step_list(hf_ctx* ctx, int32_t n, const double* dt) {
+  if (!ctx) return HF_ERR_ARG;
+  if (n < 0 || (n > 0 && !dt)) return fail(ctx, HF_ERR_ARG, "hf_set_step_list: %d entries or a null pointer", n);
+  for (int32_t k = 0; k < n; ++k)
+    if (!(dt[k] > 0.0) || !std::isfinite(dt[k])) return fail(ctx, HF_ERR_ARG, "hf_set_step_list: entry %d must be positive and finite", k);
+  hf_ctx::VarStep& V = ctx->vs;
+  if (n == 0) {   // clear: the following steps have the size of the last hf_set_step (or hf_assemble's)
+    V.list.clear();
+    V.next = 0;
+    return HF_OK;
+  }
+  HF_TRY(varstep_refusals(ctx, "hf_set_step_list"));
+  V.on = true;
+  V.list.assign(dt, dt + n);
+  V.next = 0;
+  return HF_OK;
+}
+
+int hf_set_step_control(hf_ctx* ctx, int32_t on) {
+  if (!ctx) return HF_ERR_ARG;
+  HF_HIP(hipSetDevice(ctx->dev));
+  hf_ctx::VarStep& V = ctx->vs;
+  if (!on) {
+    if (V.control) { HF_HIP(hipStreamSynchronize(ctx->stream)); varstep_control_free(ctx); }
+    return HF_OK;
+  }
+  HF_TRY(varstep_refusals(ctx, "hf_set_step_control"));
+  if (V.control) return HF_OK;
+  if (V.nh != 0)
+    return fail(ctx, HF_ERR_STATE, "hf_set_step_control: %d steps into a run (its history starts at rest: switch it on after hf_assemble, hf_set_state or hf_steady_solve)", V.nh);
+  HF_TRY(dev_alloc(ctx, &V.b0, ctx->n));
+  HF_TRY(dev_alloc(ctx, &V.p1, ctx->n));
+  HF_TRY(dev_alloc(ctx, &V.s_uprev, ctx->n));
+  HF_TRY(dev_alloc(ctx, &V.free_row, ctx->n));
+  HF_TRY(dev_alloc(ctx, &V.err, 1));
+  V.control = true;     // (u^{n-2}: allocated by the first BDF2 step, varstep_ready)
+  V.pending = V.store_pending = V.mask_ok = false;
+  return HF_OK;
+}
+
+int hf_get_step_error(hf_ctx* ctx, double atol_e, double rtol_e, double* err) {
+  if (!ctx || !err) return HF_ERR_ARG;
+  hf_ctx::VarStep& V = ctx->vs;
+  if (!V.control) return fail(ctx, HF_ERR_STATE, "hf_get_step_error: the step control is off (hf_set_step_control)");
+  if (!V.pending) return fail(ctx, HF_ERR_STATE, "hf_get_step_error: no step to judge (none taken since the control was switched on, or the last one was rejected)");
+  if (!(atol_e >= 0.0) || !(rtol_e >= 0.0) || !(atol_e + rtol_e > 0.0) || !std::isfinite(atol_e + rtol_e))
+    return fail(ctx, HF_ERR_ARG, "hf_get_step_error: atol_e and rtol_e must be finite, non-negative and not both zero");
+  HF_HIP(hipSetDevice(ctx->dev));
+  // the history: u^n, u^{n-1}, u^{n-2} at distances d0, d1, d2; what lies before the start is the rest state, dt0 apart
+  const bool bdf2 = ctx->scheme == HF_TIME_BDF2;
+  const double d0 = V.h[0], d1 = V.nh >= 2 ? V.h[1] : V.dt0, d2 = V.nh >= 3 ? V.h[2] : V.dt0;
+  const double* h0 = V.b0;
+  const double* h1 = V.nh >= 2 ? V.p1 : V.b0;
+  const double* h2 = V.nh >= 3 ? V.p2 : h1;
+  double w0, w1, w2 = 0.0, c;
+  if (bdf2) {   // quadratic Lagrange extrapolation to t_{n+1}; c = the BDF2 residual constant over the leading coefficient
+    const double s = d0 + d1 + d2, om = d0 / d1;
+    w0 = (d0 + d1) * s / (d1 * (d1 + d2));
+    w1 = -(d0 * s) / (d1 * d2);
+    w2 = d0 * (d0 + d1) / ((d1 + d2) * d2);
+    c = d0 * (1.0 + om) / ((1.0 + 2.0 * om) * s);
+  } else {      // linear extrapolation
+    w0 = (d0 + d1) / d1;
+    w1 = -d0 / d1;
+    c = d0 / (d0 + d1);
+  }
+  HF_HIP(hipMemsetAsync(V.err, 0, sizeof(unsigned long long), ctx->stream));
+  hipLaunchKernelGGL(k_step_error, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u, h0, h1, bdf2 ? h2 : static_cast<const double*>(nullptr),
+                     w0, w1, w2, c, atol_e, rtol_e, V.free_row, V.err);
+  HF_HIP(hipGetLastError());
+  unsigned long long bits = 0;
+  HF_HIP(copy_sync(ctx, &bits, V.err, sizeof bits, hipMemcpyDeviceToHost));
+  std::memcpy(err, &bits, sizeof bits);
+  return HF_OK;
+}
+
+int hf_step_reject(hf_ctx* ctx) {
+  if (!ctx) return HF_ERR_ARG;
+  hf_ctx::VarStep& V = ctx->vs;
+  if (!V.control) return fail(ctx, HF_ERR_STATE, "hf_step_reject: the step control is off (hf_set_step_control)");
+  if (!V.pending) return fail(ctx, HF_ERR_STATE, "hf_step_reject: no step to undo (none taken since the control was switched on, or the last one was rejected already)");
+  HF_HIP(hipSetDevice(ctx->dev));
+  hipLaunchKernelGGL(k_copy2, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, V.b0, ctx->d_u, V.s_uprev, ctx->d_uprev);
+  HF_HIP(hipGetLastError());
+  HF_HIP(hipStreamSynchronize(ctx->stream));
+  const hf_ctx::VarStep::Saved& S = V.saved;
+  V.t = S.t; V.dt0 = S.dt0; V.dt_eff = S.dt_eff; V.nh = S.nh;
+  for (int k = 0; k < 3; ++k) V.h[k] = S.h[k];
+  V.next = S.list_next;
+  ctx->bdf_hist = S.bdf_hist; ctx->have_prev = S.have_prev; ctx->g_hist = S.g_hist;
+  ctx->h_g0 = S.g0; ctx->h_g1 = S.g1;
+  ctx->src.next = S.src_next;
+  ctx->mon.count = S.mon_count;
+  ctx->heat.count = S.heat_count;
+  ctx->sys.pred_iters = S.pred_iters;
+  ctx->start_kind = S.start_kind;
+  ctx->extrapolate = S.start_kind >= 1 ? 1 : 0;
+  ctx->kt.have_change = S.kt_have_change;
+  while (ctx->resp.size() > S.resp) {   // boundary responses the step added (a change of the operator had dropped them all: nothing to pop)
+    ctx->proj.used[PROJ_MH + static_cast<int>(ctx->resp.size()) - 1] = false;
+    dev_free(&ctx->resp.back().w);
+    ctx->resp.pop_back();
+  }
+  V.pending = V.store_pending = false;
+  V.carry = V.last_changed;
+  return HF_OK;
+}
+
+int hf_get_step_info(hf_ctx* ctx, double* t, double* dt_last, double* dt_eff, int64_t* revaluations) {
+  if (!ctx) return HF_ERR_ARG;
+  const hf_ctx::VarStep& V = ctx->vs;
+  if (t) *t = V.t;
+  if (dt_last) *dt_last = V.h[0];
+  if (dt_eff) *dt_eff = V.dt_eff;
+  if (revaluations) *revaluations = V.revaluations;
+  return HF_OK;
 }
 
 int hf_tangent_setup(hf_ctx* ctx, int32_t n_par, const int32_t* tag_col) {
@@ -1970,6 +2130,8 @@ int hf_run_tangent(hf_ctx* ctx, int32_t n_steps, const double* g_all, const doub
                    int32_t ns, const int32_t* nodes, double* samples, int32_t* iters, double* tangent_samples, int32_t* tangent_iters) {
   if (!ctx) return HF_ERR_ARG;
   if (ctx->batch.nv > 0) return fail(ctx, HF_ERR_STATE, "hf_run_tangent: a batch is open");
+  if (ctx->vs.on || ctx->vs.control)
+    return fail(ctx, HF_ERR_STATE, "hf_run_tangent: variable steps are set (hf_set_step / hf_set_step_list / hf_set_step_control; the tangent kernels take hf_assemble's step: assemble again, switch the control off)");
   HF_TRY(tangent_tables_ok(ctx, "hf_run_tangent", 0));
   const bool tables = ctx->kt.on && ctx->kt.deriv;
   if (tables && ctx->kt.picard > 1)
@@ -2219,6 +2381,7 @@ int hf_steady_picard_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, dou
   // a new state, as hf_set_state: the history of the start vector (and of BDF2) does not continue
   ctx->have_prev = false;
   ctx->bdf_hist = false;
+  varstep_rest(ctx);
   ctx->g_hist = 0;
   proj_clear(ctx, true);
   HF_TRY(tangent_reset(ctx));
@@ -2256,6 +2419,7 @@ int hf_steady_solve(hf_ctx* ctx, const double* g_s, int32_t use_load, double rto
   // a new state, as hf_set_state: the history of the start vector (and of BDF2) does not continue
   ctx->have_prev = false;
   ctx->bdf_hist = false;
+  varstep_rest(ctx);
   ctx->g_hist = 0;
   proj_clear(ctx, true);
   if (rc != HF_ERR_HIP) HF_TRY(tangent_reset(ctx));
@@ -2603,6 +2767,8 @@ int hf_batch_begin(hf_ctx* ctx, int32_t nv, int32_t operator_kind) {
   if (!ctx) return HF_ERR_ARG;
   const bool tables = ctx->kt.on;
   if (ctx->kt.form == 1) return enthalpy_refuses(ctx, "hf_batch_begin", "the batched loop takes the lagged form");
+  if (ctx->vs.on || ctx->vs.control)
+    return fail(ctx, HF_ERR_STATE, "hf_batch_begin: variable steps are set (hf_set_step / hf_set_step_list / hf_set_step_control; the batched loop takes hf_assemble's step: assemble again, switch the control off)");
   if (tables && !ctx->batch_tables)
     return fail(ctx, HF_ERR_STATE, "hf_batch_begin: %s tables are set (batched sweeps of the nonlinear loop are not supported)", kt_kind(ctx));
   if (tables) {   // hf_set_batch_tables: what the batch under tables does not cover

@@ -509,6 +509,42 @@ struct hf_ctx {
     double* rec = nullptr;           // cap records of tab_len doubles
     int64_t cap = 0, count = 0;
   } heat;
+  // variable time steps (hf_set_step, hf_set_step_list, hf_set_step_control).  The time record (t, h, nh, dt0,
+  // dt_eff) is host arithmetic of every step; nothing else below is allocated, launched or read while `on` and `control` are false.
+  struct VarStep {
+    bool on = false;             // hf_set_step / hf_set_step_list since the last hf_assemble: steps take their size from dt_next / list
+    double t = 0.0;              // time of the state since the record was last "at rest"
+    double h[3] = {0.0, 0.0, 0.0};   // sizes of the last steps taken, h[0] the newest
+    int nh = 0;                  // steps taken since rest
+    double dt0 = 0.0;            // size of the first of them (the spacing of the virtual rest states before it)
+    double dt_eff = 0.0;         // dt' of the last step taken (ctx->dt is the dt' sys.A holds: the same except after a rejection)
+    double dt_next = 0.0;        // hf_set_step: size of the following steps
+    std::vector<double> list;    // hf_set_step_list: sizes of the next steps, consumed one per step
+    size_t next = 0;
+    long long revaluations = 0;  // launches of the assembly kernel for a new dt' (under tables: steps whose dt' differed)
+    bool last_changed = false;   // the last step changed the operator ...
+    bool carry = false;          // ... and was rejected: its redo, which finds the operator in place, still runs as a step that changed it
+    // hf_set_step_control: what an estimate and a rejection need
+    bool control = false;
+    double *b0 = nullptr, *p1 = nullptr, *p2 = nullptr;   // u^n (copied before the step), u^{n-1}, u^{n-2} (BDF2 only)
+    double* s_uprev = nullptr;   // d_uprev as it was before the step
+    uint8_t* free_row = nullptr; // 1 on the free rows (k_step_error)
+    bool mask_ok = false;
+    unsigned long long* err = nullptr;
+    bool pending = false;        // a step has been taken under control and neither committed (by the next step) nor rejected
+    bool store_pending = false;  // ... and its (solution, right-hand side) pair still has to join the projection ring
+    struct Saved {
+      double t, h[3], dt0, dt_eff;
+      int nh;
+      bool bdf_hist, have_prev;
+      int g_hist;
+      std::vector<double> g0, g1;
+      size_t src_next, list_next, resp;
+      int64_t mon_count, heat_count;
+      int pred_iters, start_kind;
+      bool kt_have_change;
+    } saved;
+  } vs;
   // optional in-situ kernel timing (hf_set_profile): event pairs around each PCG SpMV launch
   bool prof = false;
   std::vector<hipEvent_t> prof_ev;

@@ -1573,6 +1573,60 @@ __global__ __launch_bounds__(TPB) void k_eval_state(int n, const double* __restr
   for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) out[i] = uprev ? 2.0 * u[i] - uprev[i] : u[i];
 }
 
+// Variable-step BDF2 (hf_set_step), launched only on a step whose ratio w = dt_n / dt_{n-1} is not 1:
+// k_picard_w_var: out = a u^n - b u^{n-1}, the operand of the right-hand side as k_spmv's VB instances stage it;
+// k_eval_state_var: out = (1 + w) u^n - w u^{n-1}, the evaluation state of the table kernels.
+__device__ __forceinline__ double bdf2_operand_var(double a, double b, double un, double unm1) {
+#pragma clang fp contract(off)
+  return a * un - b * unm1;
+}
+__global__ __launch_bounds__(TPB) void k_picard_w_var(int n, const double* __restrict__ u, const double* __restrict__ um1, double a, double b,
+                                                      double* __restrict__ out) {
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) out[i] = bdf2_operand_var(a, b, u[i], um1[i]);
+}
+__global__ __launch_bounds__(TPB) void k_eval_state_var(int n, const double* __restrict__ u, const double* __restrict__ uprev, double w,
+                                                        double* __restrict__ out) {
+#pragma clang fp contract(off)
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) out[i] = (1.0 + w) * u[i] - w * uprev[i];
+}
+
+// Local-error indicator of the last step (hf_get_step_error): over the rows with free[i] != 0,
+//   max_i |c (((u_i - w0 h0_i) - w1 h1_i) - w2 h2_i)| / (atol + rtol |u_i|)
+// into *out as k_max_abs_diff leaves its maximum (the bits of a double >= 0 order as unsigned integers; *out zeroed before): the
+// answer does not depend on the order in which the workgroups arrive.  h2 null: the term is left out (backward Euler).  A row whose
+// quotient is NaN or infinite makes the result +inf.
+__global__ __launch_bounds__(TPB) void k_step_error(int n, const double* __restrict__ u, const double* __restrict__ h0,
+                                                    const double* __restrict__ h1, const double* __restrict__ h2, double w0, double w1,
+                                                    double w2, double c, double atol, double rtol, const uint8_t* __restrict__ free_row,
+                                                    unsigned long long* __restrict__ out) {
+#pragma clang fp contract(off)
+  __shared__ double s[TPB];
+  double m = 0.0;
+  for (int i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) {
+    if (!free_row[i]) continue;
+    const double ui = u[i];
+    double d = (ui - w0 * h0[i]) - w1 * h1[i];
+    if (h2) d = d - w2 * h2[i];
+    const double q = fabs(c * d) / (atol + rtol * fabs(ui));
+    // a state or quotient that is not finite must not vanish in fmax (which drops NaN): the step's indicator is +inf, whose bits
+    // order above every finite value, and the caller rejects the step
+    m = (q <= 1.7976931348623157e308) ? fmax(m, q) : __longlong_as_double(0x7ff0000000000000LL);
+  }
+  s[threadIdx.x] = m;
+  __syncthreads();
+  for (int h = TPB / 2; h > 0; h >>= 1) {
+    if (threadIdx.x < h) s[threadIdx.x] = fmax(s[threadIdx.x], s[threadIdx.x + h]);
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) atomicMax(out, static_cast<unsigned long long>(__double_as_longlong(s[0])));
+}
+
+// mask[dofs[q]] = 0 (the Dirichlet rows of k_step_error's row mask, which is set to 1 before)
+__global__ void k_clear_bytes(int m, const int32_t* __restrict__ dofs, uint8_t* __restrict__ mask) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q < m) mask[dofs[q]] = 0;
+}
+
 // per-block copy of the coordinates of each block's column list (hf_set_mesh, once)
 __global__ void k_gather_coords(int64_t total, const int32_t* __restrict__ dict, const double2* __restrict__ zr,
                                 double2* __restrict__ zrb) {
@@ -1823,7 +1877,18 @@ __device__ __forceinline__ T stream_load(const T* p) {
 // BDF2 operand of the right-hand side: 4/3 u^n - 1/3 u^{n-1}
 __device__ __forceinline__ double bdf2_operand(double un, double unm1) { return (4.0 * un - unm1) * (1.0 / 3.0); }
 
-template <int MODE, bool C16 = false, typename VT = double, int UN = 8, bool VC = false>
+// Variable-step BDF2 (hf_set_step): the operand a u^n - b u^{n-1} with a = (1+w)^2 / (1+2w), b = w^2 / (1+2w) of the
+// step ratio w.  The VB instances of k_spmv (modes 12-15 only) take a and b behind the column tables; every other instance has the
+// argument list of before.  bdf2_operand_var (above, with k_picard_w_var) is the one expression of it, uncontracted: the same bits wherever it is formed.
+template <class Base>
+struct BdfVarComp : Base { double ca, cb; };
+template <bool VC, bool VB>
+struct SpmvComp {
+  using base = typename std::conditional<VC, ValComp, ColComp>::type;
+  using type = typename std::conditional<VB, BdfVarComp<base>, base>::type;
+};
+
+template <int MODE, bool C16 = false, typename VT = double, int UN = 8, bool VC = false, bool VB = false>
 __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void k_spmv(int n, int nchunks, int rpc /* rows per chunk, <= TS */,
                                               const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
                                               const VT* __restrict__ vals, const double* __restrict__ x,
@@ -1832,13 +1897,17 @@ __global__ __launch_bounds__(TS) __attribute__((amdgpu_waves_per_eu(8, 8))) void
                                               const double* __restrict__ dinv, double* __restrict__ pvec,
                                               double* __restrict__ part1, double* __restrict__ part2, double w,
                                               int npart /* partial slots the consumers sum (>= gridDim.x) */,
-                                              int parity, typename std::conditional<VC, ValComp, ColComp>::type comp) {
+                                              int parity, typename SpmvComp<VC, VB>::type comp) {
   extern __shared__ double sprod[];
   __shared__ double s4[TS / 64];
   __shared__ int s_own;
-  constexpr bool BDF = MODE >= 12 && MODE <= 15;   // operand x[c] -> 4/3 x[c] - 1/3 bvec[c]
+  constexpr bool BDF = MODE >= 12 && MODE <= 15;   // operand x[c] -> 4/3 x[c] - 1/3 bvec[c] (VB: a x[c] - b bvec[c])
+  static_assert(!VB || BDF, "variable BDF2 coefficients: the right-hand side modes 12-15 only");
   // the operand slice as staged: x, or the BDF2 combination of x and bvec (two gathers per list entry, one slice in LDS)
-  auto opnd = [&](int c) { return BDF ? bdf2_operand(x[c], bvec[c]) : x[c]; };   // position of the chunk's first row in its column list (ColComp::own)
+  auto opnd = [&](int c) {   // position of the chunk's first row in its column list (ColComp::own)
+    if constexpr (VB) return bdf2_operand_var(comp.ca, comp.cb, x[c], bvec[c]);
+    else return BDF ? bdf2_operand(x[c], bvec[c]) : x[c];
+  };
   // launches inside the PCG loop return at once after convergence; MODE 0 / 7 are also used outside it (right-hand
   // side, debug products), where the launcher passes no `scal`
   if ((MODE == 3 || MODE == 4 || MODE == 6 || MODE == 9) && scal->done) return;

@@ -651,6 +651,34 @@ void launch_spmv(hf_ctx* c, const VT* vals, const double* x, double* y, double* 
 #undef HF_SPMV_ARGS
 }
 
+// Modes 12-15 with the coefficients (a, b) of a variable BDF2 step (k_spmv's VB instances): launch_spmv's choice
+// of the stream - value lists, compressed columns, plain - with a and b behind the tables.  Launched only on a step whose ratio is
+// not 1; every other step goes through launch_spmv.
+template <int MODE>
+void launch_spmv_bdfvar(hf_ctx* c, const double* vals, const double* x, double* y, const double* bvec, double* pvec, double w,
+                        const double* F, double a, double b) {
+  static_assert(MODE >= 12 && MODE <= 15, "the BDF2 right-hand side modes");
+  const ColComp comp{c->d_cdict_ptr, c->d_cdict, c->d_cid, c->max_chunk_nnz_s, c->cdict_own ? 1 : 0};
+#define HF_SPMV_BARGS c->n, c->nchunks_s, static_cast<int>(SRPC), static_cast<const int32_t*>(c->d_rowptr),                             \
+                      static_cast<const int32_t*>(c->d_colidx), vals, x, y, c->d_scal, static_cast<double*>(nullptr), bvec,          \
+                      F ? F : static_cast<const double*>(c->sys.dinv), pvec, static_cast<double*>(nullptr), static_cast<double*>(nullptr), \
+                      w, c->P, 0
+  const std::uint32_t smem = static_cast<std::uint32_t>(spmv_smem_bytes(c));
+  const hf_ctx::ValueLists* L = c->c16 ? value_lists_of(c, vals) : nullptr;
+  if (L != nullptr) {
+    const BdfVarComp<ValComp> vcomp{{comp, L->vptr, L->vlist, L->cv, c->max_chunk_nnz_s + c->max_cdict, c->vl_vcap}, a, b};
+    hipLaunchKernelGGL((k_spmv<MODE, true, double, HF_SPMV_UN, true, true>), dim3(c->Ps), dim3(TS), smem + static_cast<std::uint32_t>(c->vl_vcap) * 8u,
+                       c->stream, HF_SPMV_BARGS, vcomp);
+  } else if (c->c16) {
+    hipLaunchKernelGGL((k_spmv<MODE, true, double, HF_SPMV_UN, false, true>), dim3(c->Ps), dim3(TS), smem, c->stream, HF_SPMV_BARGS,
+                       BdfVarComp<ColComp>{comp, a, b});
+  } else {
+    hipLaunchKernelGGL((k_spmv<MODE, false, double, 8, false, true>), dim3(c->Ps), dim3(TS), smem, c->stream, HF_SPMV_BARGS,
+                       BdfVarComp<ColComp>{comp, a, b});
+  }
+#undef HF_SPMV_BARGS
+}
+
 constexpr int PROF_PAIRS = 64;
 
 // A linear system on the context's sparsity pattern: values, inverse diagonal, unknown, right-hand side.

@@ -779,8 +779,17 @@ void launch_rhs(hf_ctx* ctx, const StepLoad& L) {
 // BDF2: b = M (4/3 u^n - 1/3 u^{n-1}), plus w F when the step has a load, in one pass over M (k_spmv modes 12-15).  The same pass
 // writes `ustart`: the extrapolated start vector 2 u^n - u^{n-1} (extrap) or a copy of u^n, which the caller turns into the
 // next step's u^{n-1} by a pointer swap.  Without a history (a rest start) u^{n-1} = u^n.
-void launch_rhs_bdf2(hf_ctx* ctx, bool extrap, const StepLoad& L) {
+// ab: the coefficients (a, b) of a variable step whose ratio is not 1 (b = M (a u^n - b u^{n-1})); null: the
+// launches of before.
+void launch_rhs_bdf2(hf_ctx* ctx, bool extrap, const StepLoad& L, const double* ab = nullptr) {
   const double* um1 = ctx->bdf_hist ? ctx->d_uprev : ctx->d_u;
+  if (ab) {
+    if (L.F && extrap) launch_spmv_bdfvar<15>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, um1, ctx->d_ustart, L.w, L.F, ab[0], ab[1]);
+    else if (L.F) launch_spmv_bdfvar<14>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, um1, ctx->d_ustart, L.w, L.F, ab[0], ab[1]);
+    else if (extrap) launch_spmv_bdfvar<13>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, um1, ctx->d_ustart, 0.0, nullptr, ab[0], ab[1]);
+    else launch_spmv_bdfvar<12>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, um1, ctx->d_ustart, 0.0, nullptr, ab[0], ab[1]);
+    return;
+  }
   if (L.F) {
     if (extrap) launch_spmv<15>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, um1, ctx->d_ustart, nullptr, nullptr, L.w, L.F);
     else launch_spmv<14>(ctx, ctx->d_M, ctx->d_u, ctx->d_b, nullptr, um1, ctx->d_ustart, nullptr, nullptr, L.w, L.F);
@@ -879,6 +888,109 @@ int lifted_rhs(hf_ctx* ctx, System& S, bool with_load) {
   return HF_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// variable time steps (hf_set_step, hf_set_step_list, hf_set_step_control)
+// ------------------------------------------------------------------------------------------
+constexpr double BDF2_MAX_RATIO = 2.414213562373095;   // 1 + sqrt 2: zero-stability limit of variable-step BDF2
+
+// the time record "at rest" (hf_assemble, hf_set_state, hf_steady_solve, hf_set_time_scheme): t = 0, no step taken
+void varstep_rest(hf_ctx* ctx) {
+  hf_ctx::VarStep& V = ctx->vs;
+  V.t = 0.0;
+  V.h[0] = V.h[1] = V.h[2] = 0.0;
+  V.nh = 0;
+  V.dt0 = V.dt_eff = 0.0;
+  V.pending = V.store_pending = false;
+}
+
+void varstep_control_free(hf_ctx* ctx) {
+  hf_ctx::VarStep& V = ctx->vs;
+  dev_free(&V.b0); dev_free(&V.p1); dev_free(&V.p2); dev_free(&V.s_uprev); dev_free(&V.free_row); dev_free(&V.err);
+  V.control = V.pending = V.store_pending = V.mask_ok = false;
+}
+
+// Before the first launch of hf_step / hf_run: the list reaches, every BDF2 ratio is admissible, the buffers of the step
+// control exist for the scheme.  Nothing to do without the new calls.
+int varstep_ready(hf_ctx* ctx, int64_t n_steps, const char* call) {
+  hf_ctx::VarStep& V = ctx->vs;
+  if (!V.on && !V.control) return HF_OK;
+  if (V.on) {
+    if (!V.list.empty() && V.next + static_cast<size_t>(n_steps) > V.list.size())
+      return fail(ctx, HF_ERR_STATE, "%s: the step list has %zu entries left for %lld steps (hf_set_step_list)", call, V.list.size() - V.next,
+                  static_cast<long long>(n_steps));
+    if (ctx->scheme == HF_TIME_BDF2) {
+      double prev = ctx->bdf_hist && V.nh > 0 ? V.h[0] : 0.0;
+      for (int64_t s = 0; s < n_steps; ++s) {
+        const double h = V.list.empty() ? V.dt_next : V.list[V.next + static_cast<size_t>(s)];
+        if (prev > 0.0 && h / prev > BDF2_MAX_RATIO)
+          return fail(ctx, HF_ERR_ARG, "%s: a BDF2 step of %.6e after one of %.6e: the ratio %.4f exceeds 1 + sqrt 2 (hf_set_step / hf_set_step_list)", call, h, prev, h / prev);
+        prev = h;
+      }
+    }
+  }
+  if (V.control) {
+    if (ctx->scheme == HF_TIME_BDF2 && !V.p2) HF_TRY(dev_alloc(ctx, &V.p2, ctx->n));
+    if (!V.mask_ok) {
+      HF_HIP(hipMemsetAsync(V.free_row, 1, ctx->n, ctx->stream));
+      if (ctx->sys.nbc > 0)
+        hipLaunchKernelGGL(k_clear_bytes, dim3((ctx->sys.nbc + 255) / 256), dim3(256), 0, ctx->stream, ctx->sys.nbc, ctx->sys.bc_dofs, V.free_row);
+      HF_HIP(hipGetLastError());
+      V.mask_ok = true;
+    }
+  }
+  return HF_OK;
+}
+
+// Step control, before a step touches anything: the step before it is committed (the history vectors rotate; its pair joins the
+// projection ring, which was held back so that a rejection finds the ring as the step found it), then u^n and d_uprev are copied
+// and the host state a rejection restores is saved.
+int varstep_before(hf_ctx* ctx) {
+  hf_ctx::VarStep& V = ctx->vs;
+  const bool bdf2 = ctx->scheme == HF_TIME_BDF2;
+  if (V.pending) {
+    double* oldest = bdf2 ? V.p2 : V.p1;
+    if (bdf2) V.p2 = V.p1;
+    V.p1 = V.b0;
+    V.b0 = oldest;
+    if (V.store_pending) {
+      hf_ctx::Proj& Q = ctx->proj;
+      HF_TRY(proj_store(ctx, Q.next, ctx->d_u, ctx->d_b));
+      Q.pending = Q.next;
+      Q.next = (Q.next + 1) % PROJ_MH;
+    }
+    V.pending = V.store_pending = false;
+  }
+  hipLaunchKernelGGL(k_copy2, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u, V.b0, ctx->d_uprev, V.s_uprev);
+  hf_ctx::VarStep::Saved& S = V.saved;
+  S.t = V.t; S.dt0 = V.dt0; S.dt_eff = V.dt_eff; S.nh = V.nh;
+  for (int k = 0; k < 3; ++k) S.h[k] = V.h[k];
+  S.bdf_hist = ctx->bdf_hist; S.have_prev = ctx->have_prev; S.g_hist = ctx->g_hist;
+  S.g0 = ctx->h_g0; S.g1 = ctx->h_g1;
+  S.src_next = ctx->src.next; S.list_next = V.next; S.resp = ctx->resp.size();
+  S.mon_count = ctx->mon.count; S.heat_count = ctx->heat.count;
+  S.pred_iters = ctx->sys.pred_iters;
+  S.start_kind = ctx->start_kind;          // (prepare_response lowers it to 1 when its extra solve fails)
+  S.kt_have_change = ctx->kt.have_change;
+  return HF_OK;
+}
+
+// A step whose dt' differs from the one sys.A holds: the assembly kernel hf_assemble launches, at the new dt', and the elimination
+// - on the stream, no host synchronisation (under tables the step's own kt_revalue reads ctx->dt; setting it is all).  What belongs
+// to one operator is dropped; the hierarchy stays the one hf_assemble built.
+int varstep_revalue(hf_ctx* ctx, double dtp) {
+  ctx->dt = dtp;
+  ctx->vs.revaluations += 1;
+  if (!ctx->kt.on) {
+    value_lists_touch(ctx, ctx->sys.A);   // (M is written with the bits it holds: its lists stay)
+    HF_TRY(launch_assemble(ctx));
+    HF_TRY(eliminate(ctx, ctx->sys));
+  }
+  if (ctx->sys.precond == 1 && ctx->sys.amg_ready) ctx->sys.amg_fine_stale = true;
+  free_responses(ctx);
+  ctx->sys.pred_iters = 0;
+  return HF_OK;
+}
+
 // One time step to the boundary values g_host (n_bc doubles on the host; g_dev = the same values already on
 // the device, or null).  Leaves iteration count / residual in h_scal (kappa(T): the iterations of all Picard sweeps).
 // last: the step whose Picard change hf_get_picard_change reports (kappa(T) only).
@@ -887,11 +999,38 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
   RespArgs ra{};
   ra.k = 0;
   const bool kt = ctx->kt.on;
-  // kappa(T): kinds 2 and 3 assume one operator for the whole run (the boundary responses and the projection basis solve
-  // with it) - under tables they run as kind 1; kind 0 stays
-  const int kind = kt && ctx->start_kind >= 2 ? 1 : ctx->start_kind;
-  const bool projected = kind == 3;
   const bool bdf2 = ctx->scheme == HF_TIME_BDF2;
+  // Variable steps: the size h of this step, BDF2's ratio omega to the step before it (1 from rest) and its
+  // coefficients, and dt'; an operator that holds another dt' is re-valued here, lazily.  Without hf_set_step / hf_set_step_list
+  // h is hf_assemble's step and nothing below the record is touched.
+  hf_ctx::VarStep& V = ctx->vs;
+  double h = ctx->dt_step, omega = 1.0, ab[2] = {0.0, 0.0};
+  bool changed = false;
+  if (V.control) HF_TRY(varstep_before(ctx));
+  if (V.on) {
+    h = V.list.empty() ? V.dt_next : V.list[V.next++];   // (the callers have checked that the list reaches)
+    if (bdf2 && ctx->bdf_hist && V.nh > 0) omega = h / V.h[0];
+    double dtp = h;
+    if (bdf2 && omega == 1.0) {
+      dtp = 2.0 * h / 3.0;
+    } else if (bdf2) {
+      dtp = h * (1.0 + omega) / (1.0 + 2.0 * omega);
+      ab[0] = (1.0 + omega) * (1.0 + omega) / (1.0 + 2.0 * omega);
+      ab[1] = omega * omega / (1.0 + 2.0 * omega);
+    }
+    if (std::memcmp(&dtp, &ctx->dt, sizeof dtp) != 0) {
+      HF_TRY(varstep_revalue(ctx, dtp));
+      changed = true;
+    }
+    if (V.carry) changed = true;
+    V.carry = false;
+    V.last_changed = changed;
+  }
+  const double* abp = bdf2 && omega != 1.0 ? ab : nullptr;
+  // kappa(T): kinds 2 and 3 assume one operator for the whole run (the boundary responses and the projection basis solve
+  // with it) - under tables, and on a step that changed the operator, they run as kind 1; kind 0 stays
+  const int kind = (kt || changed) && ctx->start_kind >= 2 ? 1 : ctx->start_kind;
+  const bool projected = kind == 3;
   if (projected) HF_TRY(proj_ensure(ctx));
   const bool hist_ok = nb > 0 && ctx->extrapolate && ctx->have_prev && ctx->g_hist >= 2;
   // (BDF2: kind 2's correction assumes backward Euler's one-step recursion - kind 2 runs as kind 1; kind 3 keeps the
@@ -905,13 +1044,22 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
     // the first sweep evaluates at u^n (backward Euler) or 2 u^n - u^{n-1} (BDF2 with a history), before the right-hand side's
     // pass moves the state buffers
     const double* um1 = bdf2 && ctx->bdf_hist ? ctx->d_uprev : nullptr;
-    HF_TRY(kt_revalue(ctx, ctx->d_u, um1));
+    if (abp && um1) {
+      // a variable BDF2 step: the evaluation state (1 + omega) u^n - omega u^{n-1} is formed first (the table kernels extrapolate
+      // with omega = 1 themselves); kt.pic then holds what the Picard change of a one-sweep step is measured against
+      hipLaunchKernelGGL(k_eval_state_var, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u, um1, omega, ctx->kt.pic);
+      HF_TRY(kt_revalue(ctx, ctx->kt.pic, nullptr));
+    } else {
+      HF_TRY(kt_revalue(ctx, ctx->d_u, um1));
+    }
     if (ctx->sys.precond == 1 && ctx->sys.amg_ready) ctx->sys.amg_fine_stale = true;
-    if (track && sweeps == 1)
+    if (track && sweeps == 1 && !(abp && um1))
       hipLaunchKernelGGL(k_eval_state, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u, um1, ctx->kt.pic);
     if (enth && sweeps == 1)   // (one sweep: u^n is needed for the change alone)
       HF_HIP(hipMemcpyAsync(ctx->kt.pic, ctx->d_u, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
-    if (ct && sweeps > 1)   // the vector M multiplies, for the sweeps that form the right-hand side again
+    if (ct && sweeps > 1 && abp)   // the vector M multiplies, for the sweeps that form the right-hand side again
+      hipLaunchKernelGGL(k_picard_w_var, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u, ctx->d_uprev, ab[0], ab[1], ctx->kt.w);
+    else if (ct && sweeps > 1)
       hipLaunchKernelGGL(k_picard_w, dim3(ctx->P), dim3(TPB), 0, ctx->stream, ctx->n, ctx->d_u,
                          bdf2 ? (ctx->bdf_hist ? ctx->d_uprev : ctx->d_u) : nullptr, ctx->kt.w);
   }
@@ -920,13 +1068,13 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
   const StepLoad L = step_load(ctx);   // the load and the source of this step, for every right-hand side below
   if (bdf2 && (projected || !ctx->extrapolate)) {
     // BDF2 with the projected start vector (kind 3) or u^n (kind 0): the right-hand side's pass keeps u^n for the next step
-    launch_rhs_bdf2(ctx, false, L);
+    launch_rhs_bdf2(ctx, false, L, abp);
     std::swap(ctx->d_uprev, ctx->d_ustart);
     ctx->bdf_hist = true;
     ctx->have_prev = true;
   } else if (bdf2) {
     // BDF2 with the extrapolated start vector (kinds 1 and 2); from a rest start it is u^n
-    launch_rhs_bdf2(ctx, true, L);
+    launch_rhs_bdf2(ctx, true, L, abp);
     HF_HIP(hipMemcpyAsync(ctx->d_uprev, ctx->d_u, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
     HF_HIP(hipMemcpyAsync(ctx->d_u, ctx->d_ustart, sizeof(double) * ctx->n, hipMemcpyDeviceToDevice, ctx->stream));
     ctx->bdf_hist = true;
@@ -936,7 +1084,8 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
     // solutions and the boundary responses (kind 3)
     launch_rhs(ctx, L);
     ctx->have_prev = true;
-  } else if (ctx->extrapolate && ctx->have_prev) {
+  } else if (ctx->extrapolate && ctx->have_prev && !(changed && ctx->start_kind == 3)) {
+    // (a kind-3 run that changed the operator steps as kind 1, but its earlier steps kept no u^{n-1}: this step starts from u^n)
     // b = M u^n   (assemble_vector, run_with_diamond.py:476); with a previous step available the same
     // pass writes the extrapolated start vector 2 u^n - u^{n-1}, and the three state buffers rotate
     if (L.F)
@@ -1056,7 +1205,9 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
       ctx->kt.have_change = true;
     }
   }
-  if (rc == HF_OK && projected) {   // the new solution and its right-hand side join the projection basis
+  if (rc == HF_OK && projected && V.control) {
+    V.store_pending = true;        // under step control the pair joins the ring when the step is committed (varstep_before)
+  } else if (rc == HF_OK && projected) {   // the new solution and its right-hand side join the projection basis
     hf_ctx::Proj& Q = ctx->proj;
     HF_TRY(proj_store(ctx, Q.next, ctx->d_u, ctx->d_b));
     Q.pending = Q.next;
@@ -1066,6 +1217,14 @@ int step_device(hf_ctx* ctx, const double* g_host, const double* g_dev, double r
     ctx->h_g1.swap(ctx->h_g0);
     ctx->h_g0.assign(g_host, g_host + nb);
     if (ctx->g_hist < 2) ctx->g_hist += 1;
+  }
+  if (rc == HF_OK) {   // the time record
+    V.h[2] = V.h[1]; V.h[1] = V.h[0]; V.h[0] = h;
+    if (V.nh == 0) V.dt0 = h;
+    V.nh += 1;
+    V.t += h;
+    V.dt_eff = ctx->dt;
+    if (V.control) V.pending = true;
   }
   return rc;
 }

@@ -48,11 +48,12 @@ from .geometry import check_thickness_name, stack_no_diamond, stack_with_diamond
 from .heating import HeatingCurve
 from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, PARAM_KINDS, aniso_tables, capacity_scale, check_capacity_names, check_config,
                     classify_param, refuse_aniso, refuse_aniso_tables)
-from .kappa_t import (check_capacity_form, check_sweep_tables, check_table_tangents, material_cv_table, picard_control,
+from .kappa_t import (capacity_form, check_capacity_form, check_sweep_tables, check_table_tangents, material_cv_table, picard_control,
                       refuse_enthalpy, material_table, picard_sweeps, refuse_tables,
                       refuse_tables_unless_swept, sweep_tables, table_keys, table_param,
                       table_tangents)
 from .mesh import Mesh, load_mesh_arrays
+from .stepping import assembled_step, refuse_variable_steps, timing_plan
 from .monitors import (check_sigma, parse_monitors, problem_monitors, refuse_monitors_sweeps, uncertainty as monitor_uncertainty,
                        used_config as monitors_used_config, write_monitors_csv, write_uncertainty_csv)
 from .source import (SOURCE_PARAMS, amplitudes as source_amplitudes, check_source_param, parse_source, refuse_source,
@@ -344,7 +345,7 @@ class SimulationSession:
 
     def _shared_spec(self, cfg, stack, two_sided=False):
         """The part of the spec the columns of a batch must share: time step, scheme, capacities, Dirichlet sets, anisotropy."""
-        dt = float(cfg["timing"]["t_final"]) / int(cfg["timing"]["num_steps"])
+        dt = assembled_step(cfg)     # t_final / num_steps; the first step under timing.steps, dt_init under timing.adaptive
         bcs = self._boundary_conditions(cfg, stack, two_sided)
         aniso = {self.material_tags[m.name]: m.properties["k_aniso"] for m in stack.materials if "k_aniso" in m.properties}
         return ProblemSpec(dt, time_scheme(cfg), self._tables(stack)[1], bcs, k_aniso=aniso)
@@ -488,6 +489,7 @@ class SimulationSession:
         whether any of them carries tables)."""
         for c in cfgs:
             refuse_enthalpy(c, "run_batch (the batched loop)")
+            refuse_variable_steps(c, "run_batch (the batched loop)")
             check_sweep_tables(c, "run_batch (the batched loop)")
             refuse_tables_unless_swept(c, "run_batch (the batched loop)")
             refuse_source_sweeps(c, "run_batch (the batched loop)")
@@ -685,7 +687,17 @@ class SimulationSession:
         t_start = time.time()
         tangents, monitor_tangents, sigma, source = self._check_request(cfg, tangents, monitor_tangents, monitor_sigma)
         arg = "monitor_sigma" if monitor_sigma is not None else "tangents"
-        num_steps = int(cfg["timing"]["num_steps"])
+        # the time loop's plan (heatflow_amd.stepping.timing_plan): equal steps, a list, or controlled steps
+        plan, plan_data = timing_plan(cfg)
+        if plan != "uniform":
+            if tangents:
+                refuse_variable_steps(cfg, arg + "=")
+            if read_flux:
+                refuse_variable_steps(cfg, "the read-flux run")
+            if capacity_form(cfg) == "enthalpy":
+                refuse_variable_steps(cfg, "timing.capacity_form: enthalpy")
+        dts = np.asarray(plan_data, dtype=np.float64) if plan == "steps" else None
+        num_steps = plan_data if plan == "uniform" else len(dts) if plan == "steps" else 0
         ic_temp = float(cfg["heating"]["ic_temp"])
         spec = self.spec(cfg, stack, two_sided, lagged_for=arg + "=" if tangents else None)
         tab_on = bool(tangents) and self._check_tangent_request(cfg, spec, tangents, monitor_tangents, arg)
@@ -707,7 +719,12 @@ class SimulationSession:
         if source is not None:   # W -> W/m^3 per step, from the discrete source's own integral
             if self._source_F1 is None:
                 self._source_F1 = prob.source_vector()
-            amp = source_amplitudes(source, (np.arange(num_steps) + 1) * dt, self._source_F1, _resolve)
+            if plan == "adaptive":   # the step ends are not known beforehand: the amplitude of any time
+                F1 = self._source_F1
+                amp = lambda t: float(source_amplitudes(source, np.array([float(t)]), F1, _resolve)[0])
+            else:
+                ends = np.cumsum(dts) if plan == "steps" else (np.arange(num_steps) + 1) * dt
+                amp = source_amplitudes(source, ends, self._source_F1, _resolve)
         names, nodes = self._watcher_nodes(watcher_points)
 
         flux = self._flux_sampler(read_flux)
@@ -720,11 +737,23 @@ class SimulationSession:
             cols = self._tangent_columns(cfg, source, list(tangents), tab_on, monitor_tangents, (np.arange(num_steps) + 1) * dt, amp)
             times, samples, tsamp, iters, titers = prob.run_tangent(num_steps, nodes, time_varying=varying, **cols.kwargs)
             tangent_out, extra = self._tangent_results(cfg, list(tangents), names, tsamp, titers, cols.scale, monitor_tangents, sigma)
+        elif plan == "adaptive":
+            sink = None if field_sink is None else (lambda t: field_sink(t, prob.state()))
+            times, samples, iters, info = prob.run_adaptive(float(cfg["timing"]["t_final"]), plan_data["tol"], watcher_nodes=nodes,
+                                                            time_varying=varying, on_accept=sink,
+                                                            **{k: v for k, v in plan_data.items() if k != "tol"},
+                                                            **({"source_amplitude": amp} if amp is not None else {}))
+            extra = {"steps_taken": [float(h) for h in info["dt"]],
+                     "adaptive": {k: info[k] for k in ("accepted", "rejected", "revaluations")}}
+            num_steps = len(times)
+        elif plan == "steps" and field_sink is None:
+            times, samples, iters = prob.run_steps(dts, watcher_nodes=nodes, time_varying=varying,
+                                                   **({"source_amplitude": amp} if amp is not None else {}))
         elif field_sink is None and flux is None:
             times, samples, iters = prob.run(num_steps, watcher_nodes=nodes, time_varying=varying,
                                              **({"source_amplitude": amp} if amp is not None else {}))
         else:  # step-wise: every field goes to the sink (visualisation) and / or through the flux projection
-            times, samples, iters = self._run_stepwise(spec.bcs, num_steps, dt, amp, nodes, flux, field_sink)
+            times, samples, iters = self._run_stepwise(spec.bcs, num_steps, dt, amp, nodes, flux, field_sink, dts)
         loop_time = time.time() - t_loop
         print(f"Simulation progress: 100% (step {num_steps}/{num_steps}) | Avg time/step: {loop_time / num_steps:.4f} s"
               f" | PCG iterations/step: mean {np.mean(iters):.0f}, max {int(np.max(iters))}")
@@ -870,14 +899,25 @@ class SimulationSession:
                                                                    {q: s * get_param(cfg, q) for q, s in sigma.items()})
         return out, extra
 
-    def _run_stepwise(self, bcs, num_steps, dt, amp, nodes, flux, field_sink):
-        """The steps one by one: every field goes to ``field_sink`` and / or through the flux projection of ``flux``."""
+    def _run_stepwise(self, bcs, num_steps, dt, amp, nodes, flux, field_sink, dts=None):
+        """The steps one by one: every field goes to ``field_sink`` and / or through the flux projection of ``flux``.  ``dts``: the
+        sizes of a step list (timing.steps); None: equal steps of ``dt``."""
         prob = self.problem
         for bc in bcs:
             bc.update(0.0)
         times, rows, iters = [], [], []
+        ends = None if dts is None else np.cumsum(dts)
+        try:
+            return self._stepwise_loop(prob, bcs, num_steps, dt, amp, nodes, flux, field_sink, dts, ends, times, rows, iters)
+        finally:
+            if dts is not None:
+                prob._restore_step()
+
+    def _stepwise_loop(self, prob, bcs, num_steps, dt, amp, nodes, flux, field_sink, dts, ends, times, rows, iters):
         for step in range(num_steps):
-            t = (step + 1) * dt
+            t = (step + 1) * dt if dts is None else float(ends[step])
+            if dts is not None:
+                prob.backend.set_step(float(dts[step]))
             it, _ = prob.step(t, only=bcs[3:], **({"source_amplitude": float(amp[step])} if amp is not None else {}))
             if flux is not None:
                 prob.backend.flux_solve(self.rtol, 5000, want_z=False)          # d/dr only, on the device
@@ -1077,6 +1117,12 @@ def run_simulation_impl(kind, cfg, mesh_folder, rebuild_mesh=False, visualize_me
             if own_session:
                 session.close()
 
+        if result.get("steps_taken") is not None and output_folder is not None:
+            # an adaptive run: the accepted step sizes, so that the run can be replayed as a list (HeatProblem.run_steps)
+            used = _with_scheme(cfg)
+            used["timing"] = dict(used["timing"], steps_taken=[float(h) for h in result["steps_taken"]])
+            with open(os.path.join(save_folder, "used_config.yaml"), "w") as f:
+                _dump_yaml(used, f)
         if watcher_points is not None:
             write_watcher_csv(os.path.join(save_folder, "watcher_points.csv"), result["times"], result["watcher_names"],
                               result["watchers"])

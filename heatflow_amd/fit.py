@@ -23,6 +23,7 @@ from .geometry import check_thickness_name, thickness_velocity
 from .parameter_sweep import build_stack, get_watcher_points, oside_curves
 from .aniso import (CAPACITY_KINDS, DIRECTIONAL_HINT, KEY, PARAM_KINDS, check_capacity_names, classify_param, material_aniso,
                     refuse_aniso, refuse_aniso_tables)
+from .stepping import refuse_variable_steps
 from .kappa_t import (check_table_tangents, refuse_enthalpy, get_table_param, refuse_tables, set_table_param, table_keys,
                       table_tangents)
 from .source import check_source_param, parse_source, refuse_source_tangents
@@ -162,6 +163,7 @@ def fit_parameters(cfg, mesh_folder, params=("p_sample",), exp_csv=DEFAULT_EXP_C
     t0 = time.time()
     scheme = time_scheme(cfg)
     refuse_enthalpy(cfg, "heatflow_amd.fit")
+    refuse_variable_steps(cfg, "heatflow_amd.fit")
     refuse_aniso_tables(cfg, "heatflow_amd.fit")     # both kinds: forward runs only, with timing.table_tangents too
     tab_on = table_tangents(cfg) and bool(table_keys(cfg))      # timing.table_tangents
     if tab_on:

@@ -50,6 +50,7 @@ EXPORTS = [
     "hf_stored_heat", "hf_set_heat_records", "hf_heat_count", "hf_get_heat", "hf_clear_heat_records", "hf_set_anisotropy", "hf_set_aniso_tables", "hf_get_sizes", "hf_get_csr", "hf_spmv",
     "hf_set_value_lists", "hf_get_value_lists", "hf_get_projection", "hf_get_flux_system",
     "hf_amg_apply", "hf_batch_apply_precond", "hf_dense_inverse", "hf_time_kernel", "hf_set_profile", "hf_get_profile", "hf_last_gpu_ms",
+    "hf_set_step", "hf_set_step_list", "hf_set_step_control", "hf_get_step_error", "hf_step_reject", "hf_get_step_info",
 ]
 
 
@@ -130,6 +131,12 @@ def load_library():
         "hf_sample": [vp, i32, pi, pd],
         "hf_step": [vp, pd, dbl, dbl, i32, pi, pd],
         "hf_run": [vp, i32, pd, dbl, dbl, i32, i32, pi, pd, pi],
+        "hf_set_step": [vp, dbl],
+        "hf_set_step_list": [vp, i32, pd],
+        "hf_set_step_control": [vp, i32],
+        "hf_get_step_error": [vp, dbl, dbl, pd],
+        "hf_step_reject": [vp],
+        "hf_get_step_info": [vp, pd, pd, pd, C.POINTER(i64)],
         "hf_batch_begin": [vp, i32, i32],
         "hf_batch_load_column": [vp, i32],
         "hf_batch_set_affine": [vp, i32, pi, pd],
@@ -460,6 +467,38 @@ class HeatflowHIP:
         self.last_run_iters = iters
         self._check(rc)
         return samples, iters
+
+    # -- variable time steps ----------------------------------------------------
+    def set_step(self, dt):
+        """The following steps of step / run have size ``dt`` (hf_set_step); the operator is re-valued by the next step whose
+        effective step differs from the one it holds."""
+        self._check(self._lib.hf_set_step(self._ctx, float(dt)))
+
+    def set_step_list(self, dts):
+        """The sizes of the next steps, one consumed per step (hf_set_step_list); an empty list clears it."""
+        d = _f64(dts).ravel()
+        self._check(self._lib.hf_set_step_list(self._ctx, len(d), _pd(d) if len(d) else None))
+
+    def set_step_control(self, on=True):
+        """Keep what :meth:`step_error` and :meth:`step_reject` need (hf_set_step_control); switched on at rest."""
+        self._check(self._lib.hf_set_step_control(self._ctx, 1 if on else 0))
+
+    def step_error(self, atol=1.0, rtol=0.0):
+        """The local-error indicator of the step taken last, max over the free rows of |estimate| / (atol + rtol |u|)
+        (hf_get_step_error)."""
+        err = C.c_double()
+        self._check(self._lib.hf_get_step_error(self._ctx, float(atol), float(rtol), C.byref(err)))
+        return err.value
+
+    def step_reject(self):
+        """Undo the step taken last (hf_step_reject)."""
+        self._check(self._lib.hf_step_reject(self._ctx))
+
+    def step_info(self):
+        """{"t", "dt_last", "dt_eff", "revaluations"} of the context's time record (hf_get_step_info)."""
+        t, dl, de, rv = C.c_double(), C.c_double(), C.c_double(), C.c_int64()
+        self._check(self._lib.hf_get_step_info(self._ctx, C.byref(t), C.byref(dl), C.byref(de), C.byref(rv)))
+        return {"t": t.value, "dt_last": dl.value, "dt_eff": de.value, "revaluations": int(rv.value)}
 
     # -- tangent runs: derivatives of the time loop with respect to conductivities and boundary parameters ----------
     def tangent_setup(self, n_par, tag_col):

@@ -37,6 +37,7 @@ from .driver import (SimulationSession, build_pattern_blob, flush_mesh_writes, p
 from .geometry import build_stack, watcher_points as _watcher_points
 from .hip_backend import HipError, NotConverged
 from .kappa_t import check_sweep_tables, refuse_enthalpy, refuse_tables_unless_swept
+from .stepping import refuse_variable_steps
 from .source import refuse_source_sweeps
 from .monitors import refuse_monitors_sweeps
 
@@ -382,6 +383,7 @@ def run_parameter_sweep(base_config_path, output_dir, fwhm_range, k_range, width
         base_config.setdefault("timing", {})["scheme"] = scheme
     time_scheme(base_config)          # an unknown scheme raises before any work
     refuse_enthalpy(base_config, "run_parameter_sweep")
+    refuse_variable_steps(base_config, "run_parameter_sweep")
     refuse_tables_unless_swept(base_config, "run_parameter_sweep")     # timing.sweep_tables: the batch re-values per column
     check_sweep_tables(base_config, "run_parameter_sweep", swept=("p_sample",))
     refuse_source_sweeps(base_config, "run_parameter_sweep")
@@ -520,6 +522,7 @@ def run_kappa_sweep(cfg, mesh_folder, k_values, output_dir, *, rebuild_mesh=Fals
     rank, world = world_info()
     time_scheme(cfg)                  # an unknown scheme raises before any work
     refuse_enthalpy(cfg, "run_kappa_sweep")
+    refuse_variable_steps(cfg, "run_kappa_sweep")
     refuse_tables_unless_swept(cfg, "run_kappa_sweep")
     check_sweep_tables(cfg, "run_kappa_sweep", swept=("p_sample",))
     refuse_source_sweeps(cfg, "run_kappa_sweep")

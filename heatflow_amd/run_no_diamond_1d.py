@@ -33,6 +33,7 @@ from .heating import HeatingCurve
 from .mesh import load_mesh_arrays
 from .aniso import refuse_aniso
 from .kappa_t import refuse_enthalpy, refuse_tables
+from .stepping import refuse_variable_steps
 from .source import refuse_source
 from .monitors import refuse_monitors
 
@@ -98,6 +99,7 @@ def run_1d(cfg, mesh_folder_2d, mesh_folder_1d=None, rebuild_mesh=False, visuali
     if scheme != "backward_euler":
         raise ValueError(f"run_1d: timing.scheme {scheme!r} is not supported by the 1-D model (backward Euler only)")
     refuse_enthalpy(cfg, "run_1d (the 1-D model)")
+    refuse_variable_steps(cfg, "run_1d (the 1-D model)")
     refuse_tables(cfg, "run_1d (the 1-D model)")
     refuse_source(cfg, "run_1d (the 1-D model)")
     refuse_monitors(cfg, "run_1d (the 1-D model)")

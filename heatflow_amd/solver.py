@@ -319,6 +319,147 @@ class HeatProblem:
         self.iters.extend(int(i) for i in iters)
         return times, samples, iters
 
+    # -- variable time steps ------------------------------------------------------
+    def _varstep_refusals(self, what):
+        if self.capacity_form == "enthalpy":
+            raise ValueError(f'{what}: capacity_form="enthalpy" is not supported (its sweeps take the assembled step)')
+        if self.assembly_mode != ASM_ROW_GATHER:
+            raise ValueError(f"{what}: needs assembly_mode=ASM_ROW_GATHER (the operator is re-valued by the row-gather kernel)")
+
+    def _consistent_start(self, t, time_varying):
+        """The state's Dirichlet entries take the boundary values of the time ``t``.  Every step overwrites those entries; what
+        this changes is the first right-hand side M u^n, where the consistent mass matrix couples them to the neighbouring rows:
+        a drive that is not exactly zero at the start would otherwise enter as a jump of the boundary, to which those rows respond
+        by a fixed fraction of the jump at any step size - an error no step size resolves."""
+        if float(self.backend.step_info()["t"]) != 0.0:
+            raise ValueError("consistent start: the run is already under way (the state would be set again, which puts the "
+                             "backend's time record and BDF2's history back to rest); start from set_state or solve_steady")
+        g = self.bc_values(t, time_varying)
+        if len(self.bc_dofs):
+            u = self.backend.get_state()
+            u[self.bc_dofs] = g
+            self.backend.set_state(u)
+
+    def _restore_step(self):
+        """The following steps have the assembled size ``dt`` again (hf_set_step is sticky: without this a later :meth:`run` or
+        :meth:`step`, which tabulate their boundary values at multiples of ``dt``, would step with the last variable size).  Under
+        BDF2 the library refuses a step more than 1 + sqrt 2 times the one before it; where ``dt`` is that much larger than the
+        last step taken (a run that ended on a short step, or left through NotConverged) the state is set again, so that the
+        next step starts from rest - first order for one step, instead of an unstable ratio."""
+        try:
+            self.backend.set_step(self.dt)
+        except ValueError:
+            self.backend.set_state(self.backend.get_state())
+            self.backend.set_step(self.dt)
+
+    def run_steps(self, dts, watcher_nodes=None, time_varying=None, source_amplitude=None, t_start=None, consistent_start=False):
+        """One step per entry of ``dts`` (s) in one backend call (hf_set_step_list + hf_run): the operator is re-valued on the GPU
+        whenever the effective step changes.  Boundary values and source amplitudes are tabulated at the step ends
+        ``t_start + cumsum(dts)`` (``t_start`` None: the backend's time record, 0 after the set-up, set_state or solve_steady).
+        BDF2 refuses a step more than 1 + sqrt 2 times the one before.  Afterwards the list is cleared and later steps have the
+        assembled size ``dt`` again (see _restore_step).  ``consistent_start``: the state's Dirichlet entries first take the boundary values of the start time
+        (as :meth:`run_adaptive` does; the state is set again, so the run starts at rest).  Returns (times, samples, iters)."""
+        self._varstep_refusals("run_steps")
+        dts = np.asarray(dts, dtype=np.float64).ravel()
+        if dts.size == 0 or not (np.all(np.isfinite(dts)) and np.all(dts > 0.0)):
+            raise ValueError("run_steps: dts must be a non-empty list of positive, finite step sizes")
+        t0 = float(self.backend.step_info()["t"]) if t_start is None else float(t_start)
+        times = np.cumsum(np.concatenate([[t0], dts]))[1:]
+        for bc in self.bcs:
+            bc.update(0.0)
+        if consistent_start:
+            self._consistent_start(t0, time_varying)
+        if self.source:
+            self.backend.set_source_amplitudes([] if source_amplitude is None else self._source_amplitudes(source_amplitude, times))
+        elif source_amplitude is not None:
+            self._source_amplitudes(source_amplitude, times)
+        g_all = np.empty((len(dts), len(self.bc_dofs)), dtype=np.float64)
+        for k, t in enumerate(times):
+            g_all[k] = self.bc_values(t, time_varying)
+        self.backend.set_step_list(dts)
+        try:
+            samples, iters = self.backend.run(g_all, self.rtol, self.atol, self.max_it, watcher_nodes)
+        finally:
+            self.backend.set_step_list([])
+            self._restore_step()
+        self.iters.extend(int(i) for i in iters)
+        return times, samples, iters
+
+    def run_adaptive(self, t_final, tol, watcher_nodes=None, time_varying=None, dt_init=None, dt_min=None, dt_max=None, atol=None,
+                     rtol=0.0, source_amplitude=None, safety=0.9, shrink=0.25, grow=2.0, keep=(1.0, 1.2), on_accept=None):
+        """Steps of controlled size from the backend's current time (0 after the set-up, set_state or solve_steady; the run starts
+        at rest) to ``t_final``: hf_step, then the local-error indicator of the step (hf_get_step_error: max over the free rows of
+        |estimate| / (atol + rtol |u|), ``atol`` None = ``tol``), then the controller of :mod:`heatflow_amd.stepping` accepts the
+        step or undoes it (hf_step_reject) and proposes the next size.  The last step lands on ``t_final``.  ``dt_init`` None:
+        (t_final - t) / 400.  The state's Dirichlet entries first take the boundary values of the start time (a drive that is not
+        exactly zero there must not enter as a jump: see _consistent_start).  ``source_amplitude``: a callable p(t).  The indicator is conservative (it overstates the true local
+        error 1.3 x to 2 x on the stock small mesh), not a bound, and it reads every kink of a data-driven boundary curve as error:
+        adaptive steps pay off under smooth drives only.  Raises NotConverged when a step of ``dt_min`` is still
+        rejected.  Returns (times, samples, iters, info), info = {"accepted", "rejected", "revaluations", "dt", "err"} with the
+        accepted sizes and their estimates (in units of ``tol``'s, i.e. K with the default atol).  ``on_accept(t)`` is called after
+        every accepted step, with the state in place (the drivers' field sink)."""
+        from .hip_backend import HF_ERR_NOCONV, NotConverged
+        from .stepping import StepController, scheme_order
+
+        self._varstep_refusals("run_adaptive")
+        if source_amplitude is not None and not callable(source_amplitude):
+            raise ValueError("run_adaptive: source_amplitude must be a callable p(t) (the step ends are not known beforehand)")
+        be = self.backend
+        t = float(be.step_info()["t"])
+        t_final = float(t_final)
+        if not t_final > t:
+            raise ValueError(f"run_adaptive: t_final {t_final!r} is not ahead of the current time {t!r}")
+        ctrl = StepController(float(tol), scheme_order(self.scheme), safety=safety, shrink=shrink, grow=grow, keep=keep,
+                              dt_min=dt_min, dt_max=dt_max)
+        atol = float(tol) if atol is None else float(atol)
+        dt = ctrl.limit((t_final - t) / 400.0 if dt_init is None else float(dt_init))
+        nodes = None if watcher_nodes is None or len(watcher_nodes) == 0 else np.asarray(watcher_nodes, dtype=np.int32)
+        for bc in self.bcs:
+            bc.update(0.0)
+        self._consistent_start(t, time_varying)
+        reval0 = be.step_info()["revaluations"]
+        times, samples, iters, dts, errs = [], [], [], [], []
+        rejected = 0
+        be.set_step_control(True)
+        try:
+            while True:
+                h, lands = ctrl.toward(t, dt, t_final)
+                t_new = t_final if lands else t + h
+                be.set_step(h)
+                if self.source:
+                    be.set_source_amplitudes([] if source_amplitude is None else self._source_amplitudes(source_amplitude, [t_new]))
+                it, _ = be.step(self.bc_values(t_new, time_varying), self.rtol, self.atol, self.max_it)
+                self.iters.append(int(it))
+                err = be.step_error(atol, float(rtol)) * ctrl.tol
+                ok, dt_next = ctrl.decide(err, h)
+                if not ok:
+                    be.step_reject()
+                    rejected += 1
+                    if ctrl.at_floor(h):
+                        raise NotConverged(HF_ERR_NOCONV, f"run_adaptive: a step of dt_min = {ctrl.dt_min:.3e} s at t = {t:.6e} s "
+                                                          f"is still rejected (estimate {err:.3e} against tol {ctrl.tol:.3e})")
+                    dt = dt_next
+                    continue
+                t = t_new
+                times.append(t)
+                iters.append(int(it))
+                dts.append(h)
+                errs.append(err)
+                if nodes is not None:
+                    samples.append(be.sample(nodes))
+                if on_accept is not None:
+                    on_accept(t)
+                if lands:
+                    break
+                dt = dt_next if h == dt else max(dt_next, min(dt, ctrl.grow * h))   # (a step shortened to split the rest does not hold the size back)
+        finally:
+            be.set_step_control(False)
+            self._restore_step()
+        info = {"accepted": len(dts), "rejected": rejected, "revaluations": be.step_info()["revaluations"] - reval0,
+                "dt": np.array(dts), "err": np.array(errs)}
+        samp = np.array(samples) if nodes is not None else np.empty((len(dts), 0))
+        return np.array(times), samp, np.array(iters, dtype=np.int32), info
+
     def run_tangent(self, num_steps, watcher_nodes, conductivity=(), boundary=None, time_varying=None, first_step=0, shape=None,
                     capacity=(), monitor_tangents=False, source_amplitude=None, source=None, tables=None):
         """:meth:`run` plus the derivatives of the watcher curves with respect to parameters theta_j (hf_run_tangent,

@@ -260,6 +260,53 @@ int hf_step(hf_ctx* ctx, const double* g_bc, double rtol, double atol, int32_t m
 int hf_run(hf_ctx* ctx, int32_t n_steps, const double* g_bc_all, double rtol, double atol, int32_t max_it,
            int32_t n_s, const int32_t* nodes, double* samples, int32_t* iters);
 
+/* Variable time steps.  The context keeps a time record: the time t, the sizes of the last three steps and the
+ * effective step dt' of the last one; hf_assemble, hf_set_state, hf_steady_solve and a change of hf_set_time_scheme put it "at
+ * rest" (t = 0, no step taken).  Without any call below nothing new is allocated or launched: every step has hf_assemble's size.
+ *
+ * hf_set_step: the following steps of hf_step / hf_run have size dt.  Backward Euler: dt' = dt.  BDF2 with the ratio
+ * w = dt_n / dt_{n-1} to the step before (w = 1 from rest, where the history before t = 0 is constant):
+ *     A' u^{n+1} = M (a u^n - b u^{n-1}) + dt' F,  A' = M + dt' K,  dt' = dt_n (1+w)/(1+2w),  a = (1+w)^2/(1+2w),  b = w^2/(1+2w).
+ * The operator is re-valued lazily: the next step whose dt' differs bitwise from the one A holds launches hf_assemble's
+ * row-gather kernel with it and eliminates again, on the stream (under tables the step's own re-valuation takes the new dt').
+ * A and D^-1 are then bit for bit what hf_assemble leaves at that step under backward Euler; M is unchanged.  What belongs to one
+ * operator is dropped (boundary responses, projection ring; start-vector kinds 2 and 3 run as kind 1 on that step), A's value
+ * lists go stale, and the multigrid hierarchy stays the one hf_assemble built (frozen, never rebuilt here).  A step with w == 1
+ * on an operator that holds its dt' launches exactly the kernels of a constant-step run.
+ * Refused (HF_ERR_STATE): before hf_assemble, an open batch, a tangent set-up, the enthalpy form of the capacity, an assembly mode
+ * other than HF_ASM_ROW_GATHER; (HF_ERR_ARG): dt <= 0 or not finite, a BDF2 step with w > 1 + sqrt 2 (the zero-stability limit;
+ * checked again by hf_step / hf_run before any launch).  While variable steps are set hf_batch_begin and hf_run_tangent are
+ * refused; hf_assemble ends them.
+ *
+ * hf_set_step_list: the sizes of the next n steps, one entry consumed per step (as hf_set_source_amplitudes' amplitudes); a list
+ * too short for a run is HF_ERR_STATE before any launch; n = 0 clears the list. */
+int hf_set_step(hf_ctx* ctx, double dt);
+int hf_set_step_list(hf_ctx* ctx, int32_t n, const double* dt);
+
+/* Step control: while on, every step keeps what a local-error estimate and a rejection need (copies of u^n and of the start
+ * vector's u^{n-1}, the states u^{n-1} and - BDF2 - u^{n-2}; allocated here, freed by on = 0).  Switched on at rest only.
+ *
+ * hf_get_step_error: err = max over the free rows of |c (u_i - w0 h0_i - w1 h1_i - w2 h2_i)| / (atol_e + rtol_e |u_i|) for the
+ * step taken last: u - the Lagrange extrapolation of the history (h0, h1, h2 = u^n, u^{n-1}, u^{n-2}) to t_{n+1}, linear for
+ * backward Euler, quadratic for BDF2, times the ratio of the scheme's local-error constant to the predictor's:
+ *     backward Euler  c = dt_n / (dt_n + dt_{n-1});   BDF2  c = dt_n (1+w) / ((1+2w) (dt_n + dt_{n-1} + dt_{n-2}))
+ * (1/2 and 2/9 at constant step).  History before the start of the run is the rest state at spacing dt_0, the first step's size.
+ * A conservative indicator, not a bound: on the stock small mesh it overstates the true local error 1.3 x (BDF2) to 2 x
+ * (backward Euler).  Deterministic (no contraction, an order-independent maximum).
+ *
+ * hf_step_reject: undoes the step taken last: state, u^{n-1}, histories, time record, the source's next amplitude and the step
+ * list's next entry are bit for bit what they were before it; its monitor and heat records are dropped.  Taking the step again
+ * with the same size gives bit for bit the first attempt's answer.  Not rolled back: the operator (the next step re-values it if
+ * its dt' differs), the count of re-valuations, the count of multigrid fallbacks, and under tables the value hf_get_picard_change
+ * reports (its "have a change" flag is).  A state that is not finite makes hf_get_step_error return +inf, never 0.  HF_ERR_STATE when there is no step to undo (rejecting twice in a row).
+ *
+ * hf_get_step_info: the time, the size of the last step, its dt', and the number of re-valuations for a new dt' so far (any may
+ * be NULL).  After a rejection the first three are those of the step before; the count is not rolled back. */
+int hf_set_step_control(hf_ctx* ctx, int32_t on);
+int hf_get_step_error(hf_ctx* ctx, double atol_e, double rtol_e, double* err);
+int hf_step_reject(hf_ctx* ctx);
+int hf_get_step_info(hf_ctx* ctx, double* t, double* dt_last, double* dt_eff, int64_t* revaluations);
+
 /* Batched time loop: nv = 2, 4, 8 or 16 sweep points of ONE mesh, Dirichlet set and rho_c advance together as the
  * columns of a multi-vector PCG (reference: the independent runs of the parameter grid, parameter_sweep.py:195-235,
  * and of the kappa list, sweep_test.py:47-52).  Vectors are stored interleaved on the device, every index and every
